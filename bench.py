@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Groth16 batch-verify throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N = 1 runs in this process.  N > 1: if the process was started by torch.distributed.run (WORLD_SIZE set) it is one rank of
 the job; otherwise bench.py starts the N ranks ITSELF -- `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -40,11 +40,6 @@ import time
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-# The HIP runtime multiplexes every stream of a process onto a few hardware queues (four by default), and streams that share a queue run one
-# after the other.  A rank of this bench has the library's two sub-batch streams, its copy stream and -- under torch.distributed -- RCCL's own
-# streams; with eight queues none of them shares (measured with RCCL initialised: the two sub-batch streams overlap 1.75 x instead of not at all,
-# 185 against 192 ms per step).  Read by the runtime when it initialises, i.e. before torch is imported; a deployment sets the same variable.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
 def algo_bytes_per_proof(n_public):
     """256 B proof + 32 B per public input in, 1 B status out (321 B at 2 inputs, 33 025 B at 1024)."""
@@ -94,6 +89,8 @@ def _fracs(mads_per_s):
     return r
 METRIC = "Groth16 verifies/sec (2 pub-inputs) at batch=2^20, 1/2/4/8 MI355X"
 SEED = 0xB2540002
+DUMP_MAX_VALUES = 1 << 24        # 64 MB of float32: the whole vector up to here
+DUMP_SAMPLE = 1 << 22            # beyond: this many positions, 4 B value + 8 B index each (48 MB)
 
 
 def parse_args(argv=None):
@@ -114,10 +111,29 @@ def parse_args(argv=None):
     ap.add_argument("--host-buffers", action="store_true", help="also time the host-buffer entry (PCIe-inclusive), reported beside `value`")
     ap.add_argument("--rehearse-one-gpu", action="store_true", help="REHEARSAL of --gpus N on ONE GPU: N rank processes, all on cuda:0, gloo for the status gather and the "
                     "reductions (RCCL refuses two ranks on one device); the line says so and its value is not a scaling number")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last timed step computed (the gathered status "
+                    "bytes a caller receives) to DIR/status.npy as float32; more than %d proofs: a fixed, seeded sample of %d, with its proof indices in DIR/status_index.npy" % (DUMP_MAX_VALUES, DUMP_SAMPLE))
     a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.warmup < 0:
+        ap.error("--warmup must not be negative")
     if a.batch_log2 is None:
         a.batch_log2 = 18 if a.plonk else 20
     return a
+
+
+def dump_outputs(directory, status):
+    """--dump-outputs: the last timed step's gathered status bytes (one per proof, global order) as DIR/status.npy (float32).  A larger batch is sampled
+    at positions drawn from a fixed seed, so that two builds given the same arguments write the same positions; they go to DIR/status_index.npy (float64)."""
+    import numpy as np
+    st = status.cpu().numpy().astype(np.float32)
+    os.makedirs(directory, exist_ok=True)
+    if st.size > DUMP_MAX_VALUES:
+        idx = np.sort(np.random.default_rng(0xB254).choice(st.size, DUMP_SAMPLE, replace=False))
+        st = st[idx]
+        np.save(os.path.join(directory, "status_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(directory, "status.npy"), st)
 
 
 def free_port():
@@ -319,6 +335,8 @@ def run_rank(args, make_verifier, backend, rank, world, local_rank, synth, emit=
     assert got == expected, "rank %d: statuses differ from the expected statuses" % rank
     assert full.numel() == n_total, "gathered vector has the wrong length"
     assert bytes(full[lo:hi].cpu().numpy().tobytes()) == expected, "gathered statuses are wrong"
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, full)
 
     out = None
     if rank == 0:
@@ -877,6 +895,8 @@ def run_rank_plonk(args, pkg, backend, rank, world, local_rank, rehearse):
     assert full.numel() == n_total and bytes(full[lo:hi].cpu().numpy().tobytes()) == st, "gathered statuses are wrong"
     if rank != 0:
         return None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, full)
     value = n_total * args.steps / elapsed
     stage_ms, _lanes = pvk.last_timing(local_rank)
     km = (_load_json("kernel_mads.json") or {}).get("kernels", {})

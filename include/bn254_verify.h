@@ -245,7 +245,7 @@ void bn254_set_profile_kernels(unsigned mask);
 int bn254_groth16_last_kernel_ms(const bn254_g16_pvk* pvk, int device, float ms[BN254_G16_NUM_KERNELS]);
 int bn254_groth16_rlc_state(const bn254_g16_pvk* pvk, int device, float* fallback_share, unsigned* bypassed_calls);   /* BN254_FLAG_RLC, adaptive use */
 /* A large batch runs as two sub-batches on two streams; the HIP runtime maps the streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4) and
- * streams that share a queue run one after the other.  The library does not touch the environment (GPU_MAX_HW_QUEUES=8 is a deployment setting);
+ * streams that share a queue run one after the other.  The library does not touch the environment (the number of queues is a deployment setting);
  * it measures: a two-stream batch of a (key, device) is bracketed with events, a later call reads them.  overlap = sum of the two sub-batches' durations /
  * their union (~2 side by side, ~1 one after the other; -1 not measured yet).  One measurement decides nothing (another tenant's kernels, a tool that serialises dispatches):
  * three in a row must read "one after the other" before single_stream = 1 (batches that fit one launch then run as one sub-batch), one that reads "side by side" settles it

@@ -48,7 +48,7 @@ hipError_t bn254_launch_plonk_dbg_zeta(const void* d_work, size_t n, uint8_t* d_
 // The HIP runtime multiplexes every stream of the process onto GPU_MAX_HW_QUEUES hardware queues -- four by default -- and streams that share a queue run one
 // after the other: the two sub-batch streams of a large Groth16 batch then lose their overlap once a third party (RCCL) has streams too, and eight PlonK chains
 // run at 1.20 instead of 1.51 M proofs/s (profiles/r03_batch_sweep_fine.txt).  The runtime reads the variable when it initialises, so it is a DEPLOYMENT setting
-// (GPU_MAX_HW_QUEUES=8 in the environment of the process); the library does not touch the environment.  What it does instead: the first batch
+// (GPU_MAX_HW_QUEUES in the environment of the process); the library does not touch the environment.  What it does instead: the first batch
 // that runs two sub-batch streams brackets them with events, the next call reads the overlap (bn254_groth16_stream_overlap), and a device whose sub-batch streams
 // were found to run one after the other gets one sub-batch per launch from then on (same work, fewer launches) and a line in bn254_last_diagnostic().
 static thread_local std::string g_diag;
@@ -683,8 +683,8 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
         if (d->ov_serial_votes >= OV_AGREE || d->ov_probe) {
           d->single_stream = fallback;
           d->diag = "the two sub-batch streams of a Groth16 batch ran one after the other on this device (overlap " + std::to_string(d->ov_ratio) + ", " +
-                    std::to_string(d->ov_serial_votes) + " measurements in a row): the process's streams share a hardware queue -- set GPU_MAX_HW_QUEUES=8 before the HIP runtime "
-                    "initialises (INTEGRATION.md)" + (fallback ? "; using one sub-batch per launch, re-measured every " + std::to_string(OV_REPROBE) + " batches" : "");
+                    std::to_string(d->ov_serial_votes) + " measurements in a row): the process's streams share a hardware queue -- give it more queues (GPU_MAX_HW_QUEUES, read when the HIP runtime "
+                    "initialises; INTEGRATION.md)" + (fallback ? "; using one sub-batch per launch, re-measured every " + std::to_string(OV_REPROBE) + " batches" : "");
         }
       } else {
         d->ov_serial_votes = 0;

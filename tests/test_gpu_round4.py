@@ -219,7 +219,7 @@ def test_plonk_large_proof_stride_lds(pkg, O, fixtures):
 
 def test_stream_overlap_is_measured_not_assumed(pkg, L):
     """The library no longer touches GPU_MAX_HW_QUEUES: the first batch that runs two sub-batch streams is bracketed with events and a later call reads the overlap
-    (bn254_groth16_stream_overlap).  Here (tests/conftest.py asks for eight hardware queues) the two streams run side by side; a process whose streams share a queue
+    (bn254_groth16_stream_overlap).  With enough hardware queues the two streams run side by side; a process whose streams share a queue
     gets overlap ~ 1, one sub-batch per launch from then on and a line in bn254_last_diagnostic."""
     import time
     n = 1 << 17

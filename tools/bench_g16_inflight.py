@@ -1,6 +1,5 @@
 """Groth16 batches of 4096 with several calls in flight: k prepared handles of the same key, k streams, one host thread enqueues round-robin."""
 import importlib, os, sys, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch

@@ -1,6 +1,5 @@
 """PlonK batches of 4096 with several calls in flight (host threads; one prepared key per thread and, second experiment, one shared key)."""
 import importlib, json, os, random, sys, threading, time
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
