@@ -156,8 +156,8 @@ int bn254_groth16_proof_write_raw(const uint8_t a[64], const uint8_t b[128], con
  * load_plonk_verifying_key_from_bytes (plonk/converter.rs:18-119, hoisted into vk_prepare) + verify_plonk
  * (plonk/verify.rs:46-317: Fiat-Shamir transcripts transcript.rs:15-108, BSB22 hash_to_field.rs:9-122, kzg::fold_proof and
  * kzg::batch_verify_multi_points plonk/kzg.rs:87-190).  Everything per proof runs on the GPU: the transcripts, the hash-to-field and the scalar-field
- * arithmetic as one-proof-per-lane kernels (csrc/bn254_k_plonk.hip, compiled from the same source as the host-thread stages that BN254_PLONK_HOST=1 still
- * selects), every group operation (24 G1 scalar multiplications and the two-pair pairing check per proof) as before.
+ * arithmetic as one-proof-per-lane kernels (csrc/bn254_k_plonk.hip, compiled from the same source as the host build of the stages that the library's
+ * self-test checks them against), every group operation (24 G1 scalar multiplications and the two-pair pairing check per proof) as before.
  * Status bytes: BN254_ACCEPT or an error code; PlonK never returns BN254_REJECT (plonk/verify.rs:316).  Each proof occupies
  * proof_stride bytes (>= its length: 904 for the SP1 circuits); public inputs are n_public x 32 big-endian bytes per proof.
  * Threads: a prepared key may be used from several host threads at once.  Each call takes one of the key's eight per-device contexts (stream, device
@@ -174,8 +174,8 @@ int bn254_plonk_verify_batch(const bn254_plonk_pvk* pvk, const uint8_t* proofs, 
  * weight (drawn per call, folded into the scalars of the multi-scalar multiplication at no group cost), the weighted points of the 64 proofs of a wavefront are
  * added and ONE pairing check runs per group; the proofs of a group that fails are then checked one by one, so the status bytes are those of the exact path
  * except that a forged proof is accepted with probability ~2^-127 (weights are odd 128-bit values; the same kind of batching the reference applies to a proof's two openings, plonk/kzg.rs:149-187).
- * Honoured from 8192 proofs per pass (BN254_PLONK_RLC_MIN); below, the one remaining pairing is the same latency-bound launch and the flag changes nothing.  (The
- * diagnostic host-thread stages of BN254_PLONK_HOST=1 ignore the flag.)  Any other flag bit is refused with BN254_E_BAD_ARG. */
+ * Honoured from 8192 proofs per pass (BN254_PLONK_RLC_MIN); below, the one remaining pairing is the same latency-bound launch and the flag changes nothing.
+ * Any other flag bit is refused with BN254_E_BAD_ARG. */
 int bn254_plonk_verify_batch_flags(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
                                    size_t n_public, size_t n, uint8_t* status, int device, unsigned flags);
 /* The same three entry shapes as Groth16 (north_star: one verify_batch surface for both verifiers):
@@ -203,8 +203,8 @@ int bn254_plonk_verify(const uint8_t* proof, size_t proof_len, const uint8_t* vk
  * Same status bytes whatever the plan. */
 void bn254_set_plonk_params(long piece, int workers, long big_from, long big_piece);
 /* Durations (ms) of the first sub-batch of the bn254_plonk_verify_batch that finished last on `device`, from HIP events on the sub-batch's stream:
- *   [0] host: staging copy into pinned memory (with BN254_PLONK_HOST=1: stage 1 on host threads)      [1] k_plonk_stage1
- *   [2] k_g1_msm_rows of the linearised-polynomial digest   [3] its k_g1_sum_affine                   [4] k_plonk_stage2 (BN254_PLONK_HOST=1: host stage 2)
+ *   [0] host: staging copy into pinned memory                                                           [1] k_plonk_stage1
+ *   [2] k_g1_msm_rows of the linearised-polynomial digest   [3] its k_g1_sum_affine                   [4] k_plonk_stage2
  *   [5] k_g1_msm_rows of the KZG check (P0 and P1)          [6] their k_g1_sum_affine                 [7] the pairing check     [8] the sub-batch, host wall time
  * lanes: lanes (rows x items rounded up to 64) of the two k_g1_msm_rows launches. */
 #define BN254_PLONK_NUM_TIMINGS 9

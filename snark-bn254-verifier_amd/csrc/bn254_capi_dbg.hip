@@ -1,0 +1,434 @@
+// bn254_capi_dbg.hip -- the bn254_dbg_* probes of the C ABI (include/bn254_verify.h; tests and tools): device arithmetic, plans, tables, the
+// VALU peak -- and the synthetic workload generator of the bench and the tests.
+#include "bn254_capi_internal.h"
+
+extern "C" {
+
+int bn254_dbg_key_cache_slots(void) { return KeyCache<bn254_g16_pvk, bn254_groth16_vk_free>::capacity(); }
+
+// Host-only probe of the Groth16 plan (bn254_g16_plan.h): for a key with key_inputs public inputs (comb: its MSM tables are in comb form), a context RESERVED for
+// `reserved` proofs and a batch of n proofs with n_public inputs each -- what the context allocates, and every launch the batch makes: out[] receives, per launch,
+// 8 values {chunk, first proof of the chunk, proofs, stream slot (-1: caller's stream, not concurrent), form (0 lanes, 1 cooperative, 2 latency mode), Miller steps
+// per launch, workspace bytes it addresses (first byte offset, one past the last)}; alloc[] = {workspace bytes, partial-sum bytes, digit bytes, proofs per wide launch}.
+// Returns the number of launches through *n_launches (at most max_launches are written).
+int bn254_dbg_g16_plan(size_t key_inputs, int comb, size_t reserved, size_t n, size_t n_public, int n_streams, int single_stream, uint64_t alloc[4], uint64_t* out,
+                       int max_launches, int* n_launches) {
+  if (!alloc || !out || !n_launches || n_streams < 1 || n_streams > 4) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const G16Alloc a = g16_alloc_for(reserved, key_inputs, comb != 0);
+  alloc[0] = (uint64_t)a.ws_proofs * G16_WS_BYTES_PER_PROOF; alloc[1] = a.msm_part_bytes; alloc[2] = a.msm_digit_bytes; alloc[3] = a.msm_part_proofs;
+  int k = 0;
+  const size_t chunk = G16_MAX_BATCH;
+  int ci = 0;
+  for (size_t off = 0; off < n; off += chunk, ci++) {
+    const size_t m = n - off < chunk ? n - off : chunk;
+    G16ChunkPlan p;
+    if (!g16_plan_chunk(p, m, key_inputs, n_public, n_streams, single_stream != 0)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    for (int pi = 0; pi < p.parts; pi++) {
+      const G16Part& q = p.part[pi];
+      const G16Form f = g16_launch_form(q.count, n_public, n_public == key_inputs, p.wide, p.parts > 1, p.split_small && p.parts == 1, true, -1);
+      if (k < max_launches) {
+        uint64_t* o = out + 8 * (size_t)k;
+        o[0] = (uint64_t)ci; o[1] = q.first; o[2] = q.count; o[3] = (uint64_t)(int64_t)q.stream_slot; o[4] = (uint64_t)f.form; o[5] = (uint64_t)f.run_steps;
+        o[6] = (uint64_t)q.first * G16_WS_BYTES_PER_PROOF; o[7] = (uint64_t)(q.first + q.count) * G16_WS_BYTES_PER_PROOF;
+      }
+      k++;
+    }
+  }
+  *n_launches = k;
+  return BN254_OK;
+}
+
+// ... and of the group status bytes of the RLC mode for a chunk of m proofs: what the launch parts address against what a context reserved for `reserved` proofs holds
+int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, uint64_t* need, uint64_t* alloc) {
+  if (!need || !alloc || m == 0 || n_streams < 1 || n_streams > 4 || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > 3) return set_err(BN254_E_BAD_ARG, "bad argument");
+  *need = g16_rlc_need(m, n_streams, log2_group, log2_share, min_lanes); *alloc = g16_rlc_alloc(reserved);
+  return BN254_OK;
+}
+
+// ---------------------------------------------------------------- device-arithmetic probes (tests)
+struct DevBuf {   // frees on every exit path
+  uint8_t* p = nullptr;
+  ~DevBuf() { if (p) (void)hipFree(p); }
+};
+static int run_probe(size_t in_a, size_t in_b, size_t out_sz, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int device,
+                     hipError_t (*launch)(const uint8_t*, const uint8_t*, uint8_t*, size_t)) {
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (n == 0) return BN254_OK;
+  DevBuf da, db, dout;
+  HIPCK(hipMalloc((void**)&da.p, in_a * n));
+  HIPCK(hipMemcpy(da.p, a, in_a * n, hipMemcpyHostToDevice));
+  if (in_b && b) { HIPCK(hipMalloc((void**)&db.p, in_b * n)); HIPCK(hipMemcpy(db.p, b, in_b * n, hipMemcpyHostToDevice)); }
+  HIPCK(hipMalloc((void**)&dout.p, out_sz * n));
+  hipError_t e = launch(da.p, db.p, dout.p, n);
+  if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
+  HIPCK(hipDeviceSynchronize());
+  HIPCK(hipMemcpy(o, dout.p, out_sz * n, hipMemcpyDeviceToHost));
+  return BN254_OK;
+}
+// probe (tests): stage 1 of the device path alone -- zeta (32-byte big-endian, canonical; zero where the proof failed before the challenges) and the
+// stage-1 status of each proof (BN254_ACCEPT = alive, or the error code the stage decided)
+int bn254_dbg_plonk_stage1(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n,
+                           uint8_t* zeta_out, uint8_t* status_out, int device) {
+  if (!pvk || !proofs || !zeta_out || !status_out || n == 0 || n > PLONK_MAX_LAUNCH) return set_err(BN254_E_BAD_ARG, "bad argument");
+  PlonkDev* d;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(pvk->mu);
+    if ((rc = plonk_ensure_dev(pvk, device, &d))) return rc;
+  }
+  PlonkLease lease(d, 1);
+  PlonkCtx& c = lease.ctx(0);
+  if ((rc = plonk_ensure_ctx(pvk, c, n, 0))) return rc;
+  const size_t pb = n * proof_stride, ib = n * n_public * 32;
+  DevBuf in, zo, so;
+  HIPCK(hipMalloc((void**)&in.p, pb + ib + 4)); HIPCK(hipMalloc((void**)&zo.p, 32 * n)); HIPCK(hipMalloc((void**)&so.p, n));
+  HIPCK(hipMemcpy(in.p, proofs, pb, hipMemcpyHostToDevice));
+  if (ib) HIPCK(hipMemcpy(in.p + pb, public_inputs, ib, hipMemcpyHostToDevice));
+  uint32_t lam_key[11] = {0};
+  hipError_t e = bn254_launch_plonk_stage1(d->d_key, in.p, proof_stride, in.p + pb, n_public, n, lam_key, c.d_work, c.terms, c.flags, plonk_stage1_terms(pvk->key), c.stream);
+  if (e == hipSuccess) e = bn254_launch_plonk_dbg_zeta(c.d_work, n, zo.p, so.p, c.stream);
+  if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
+  HIPCK(hipStreamSynchronize(c.stream));
+  HIPCK(hipMemcpy(zeta_out, zo.p, 32 * n, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(status_out, so.p, n, hipMemcpyDeviceToHost));
+  return BN254_OK;
+}
+
+// the multiply-add issue rate of THIS device (lane-level v_mad_u64_u32 per second, sixteen independent chains per lane, four wavefronts per SIMD, best of five
+// launches of ~0.25 ms): what bench.py divides its VALU rooflines by (the constant of profiles/r01_ubench_valu.txt, 35.1e12, stays as the reference)
+int bn254_dbg_valu_peak(int device, double* mads_per_s) {
+  if (!mads_per_s) return set_err(BN254_E_BAD_ARG, "bad argument");
+  int rc = check_device(device);
+  if (rc) return rc;
+  *mads_per_s = bn254_measure_valu_peak(12);
+  return *mads_per_s > 0 ? BN254_OK : set_err(BN254_E_HIP, "peak measurement failed");
+}
+int bn254_dbg_valu_peak_sustained(int device, double ms_target, double* mads_per_s) {
+  if (!mads_per_s || !(ms_target > 0.0) || ms_target > 2000.0) return set_err(BN254_E_BAD_ARG, "bad argument");
+  int rc = check_device(device);
+  if (rc) return rc;
+  *mads_per_s = bn254_measure_valu_sustained(ms_target);
+  return *mads_per_s > 0 ? BN254_OK : set_err(BN254_E_HIP, "peak measurement failed");
+}
+int bn254_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device) {
+  return run_probe(32, 32, 32, a, b, out, n, device, [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_fp_mul(x, y, o, m, nullptr); });
+}
+static thread_local int g_probe_op = 0;
+static thread_local int32_t* g_probe_ws = nullptr;
+static thread_local uint8_t* g_probe_kinds = nullptr;
+static int probe_ws_alloc(size_t n, int device) {
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (n > G16_MAX_LAUNCH) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  HIPCK(hipMalloc((void**)&g_probe_ws, (n ? n : 1) * (size_t)G16_WS_BYTES_PER_PROOF));
+  HIPCK(hipMalloc((void**)&g_probe_kinds, n ? n : 1));  // status bytes of the probe lanes
+  return BN254_OK;
+}
+static void probe_ws_free() { if (g_probe_ws) (void)hipFree(g_probe_ws); if (g_probe_kinds) (void)hipFree(g_probe_kinds); g_probe_ws = nullptr; g_probe_kinds = nullptr; }
+int bn254_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device) {
+  g_probe_op = op;
+  int rc = probe_ws_alloc(n, device);
+  if (rc) return rc;
+  rc = run_probe(384, b ? 384 : 0, 384, a, b, out, n, device, [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_fp12_op(g_probe_op, x, y, o, m, g_probe_ws, g_probe_kinds, nullptr); });
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* out_gt, size_t n, int device) {
+  int rc = probe_ws_alloc(n, device);
+  if (rc) return rc;
+  rc = run_probe(64, 128, 384, g1, g2, out_gt, n, device, [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_pairing(x, y, o, m, g_probe_ws, g_probe_kinds, nullptr); });
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_g2_subgroup_ate(const uint8_t* g1, const uint8_t* g2, uint8_t* out_flags, size_t n, int device) {
+  int rc = probe_ws_alloc(n, device);
+  if (rc) return rc;
+  rc = run_probe(64, 128, 1, g1, g2, out_flags, n, device, [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_g2_ate(x, y, o, m, g_probe_ws, g_probe_kinds, nullptr); });
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_g2_subgroup(const uint8_t* g2, uint8_t* out_flags, size_t n, int device) {
+  return run_probe(128, 0, 1, g2, nullptr, out_flags, n, device, [](const uint8_t* x, const uint8_t*, uint8_t* o, size_t m) { return bn254_launch_dbg_g2_subgroup(x, o, m, nullptr); });
+}
+
+#if defined(BN254_PLONK_MARKS)
+// diagnostics build: stage 1 of ONE proof on the host, and the intermediate values it dumped (bn254_plonk.hpp::PL_DUMP): the reference the device's dump is held to
+int bn254_dbg_plonk_dump_host(const bn254_plonk_pvk* pvk, const uint8_t* proof, size_t proof_len, const uint8_t* inputs, size_t n_public, uint8_t out[64 * 32], int* status) {
+  if (!pvk || !proof || !out || !status) return set_err(BN254_E_BAD_ARG, "bad argument");
+  PlonkWork wk; std::vector<MsmTerm> terms(plonk_stage1_terms(pvk->key)); std::vector<uint8_t> fl(terms.size());
+  memset(g_plonk_dump_host, 0, sizeof g_plonk_dump_host);
+  g_plonk_sha_n_host = 0;
+  wk.lambda = fr_ctx().one;
+  *status = plonk_stage1(pvk->key, proof, proof_len, inputs, n_public, wk, terms.data(), fl.data());
+  memcpy(out, g_plonk_dump_host, 64 * 32);
+  return BN254_OK;
+}
+int bn254_dbg_plonk_sha_dump_host(uint32_t out[32 * 24], uint32_t* n) { memcpy(out, g_plonk_sha_dump_host, sizeof g_plonk_sha_dump_host); *n = g_plonk_sha_n_host; return BN254_OK; }
+#endif
+// GLV decomposition probe (host only): k (32 bytes big-endian, any value: reduced mod r) -> |k1|, |k2| (16 bytes big-endian each) and signs
+int bn254_dbg_glv_decompose(const uint8_t k32[32], uint8_t k1_16[16], uint8_t k2_16[16], int* neg1, int* neg2) {
+  if (!k32 || !k1_16 || !k2_16 || !neg1 || !neg2) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const FrCtx& F = fr_ctx();
+  Glv g = glv_decompose(F.to_canon(F.from_be32(k32)));
+  for (int i = 0; i < 8; i++) { k1_16[i] = (uint8_t)(g.k1[1] >> (56 - 8 * i)); k1_16[8 + i] = (uint8_t)(g.k1[0] >> (56 - 8 * i)); k2_16[i] = (uint8_t)(g.k2[1] >> (56 - 8 * i)); k2_16[8 + i] = (uint8_t)(g.k2[0] >> (56 - 8 * i)); }
+  *neg1 = g.neg1 ? 1 : 0; *neg2 = g.neg2 ? 1 : 0;
+  return BN254_OK;
+}
+
+// host-only probe of the Fr inversion the PlonK stages use (bn254_plonk.hpp::FrCtx::inverse, binary extended GCD; which = 1: the Fermat form it replaced;
+// field = 1: the same code instantiated for Fp, as the curve checks of the proof points use it).  in / out: 32-byte big-endian canonical values.
+// host-only probes of the PlonK batch plan and of the scratch sizing (tests: every pass of every plan must fit the scratch of a context of its capacity)
+int bn254_dbg_plonk_plan(size_t n, size_t piece, int max_workers, int* workers, size_t* per_worker, size_t* per_pass) {
+  if (!workers || !per_worker || !per_pass || n == 0 || piece == 0 || max_workers < 1) return set_err(BN254_E_BAD_ARG, "bad argument");
+  plonk_plan(n, piece, max_workers, workers, per_worker, per_pass);
+  return BN254_OK;
+}
+size_t bn254_dbg_plonk_scratch_lanes(size_t capacity, int n_var) { return plonk_scratch_lanes(capacity, n_var); }
+size_t bn254_dbg_plonk_part_points(size_t capacity, int n_qcp, int stage) {
+  if (n_qcp < 0 || n_qcp > PLONK_MAX_QCP || stage < 1 || stage > 3) return 0;
+  PlonkKey key; key.n_qcp = (uint32_t)n_qcp;
+  MsmShape sh;
+  if (stage == 1) plonk_msm1_shape(key, sh); else plonk_msm2_shape(key, sh, stage == 3);
+  return plonk_part_points(capacity, sh);
+}
+// the row plan of one MSM launch of the PlonK path (stage 1: the digest; 2: the KZG check) for a key with n_qcp commitments and a batch of n proofs:
+// rows, rows with a window table, scratch lanes the launch needs, the longest row in the planner's cost units, rows per sum; rows_out (optional):
+// MSM_MAX_ROWS x 9 ints {variable term, pos_lo, pos_hi, unit term, sum, scratch slot, first fixed window, one past the last, joint-row term mask}
+int bn254_dbg_plonk_msm_plan(int n_qcp, int stage, size_t n, size_t lane_budget, int* n_rows, int* n_var_rows, size_t* scratch_lanes, int* chain, int sum_rows[2],
+                             int fixed_terms[2], int* rows_out) {
+  if (n_qcp < 0 || n_qcp > PLONK_MAX_QCP || (stage != 1 && stage != 2) || n == 0 || !n_rows || !n_var_rows || !scratch_lanes || !chain || !sum_rows || !fixed_terms)
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  PlonkKey key; key.n_qcp = (uint32_t)n_qcp;
+  MsmShape sh;
+  if (stage == 1) plonk_msm1_shape(key, sh); else plonk_msm2_shape(key, sh);
+  MsmPlan plan;
+  if (!msm_plan_build(plan, sh, (n + 63) & ~(size_t)63, lane_budget ? lane_budget : msm_lane_budget(), 0, plonk_joint_g((n + 63) & ~(size_t)63))) return set_err(BN254_E_BAD_ARG, "shape cannot be planned");
+  *n_rows = plan.n_rows; *n_var_rows = plan.n_var_rows; *scratch_lanes = bn254_g1_msm_scratch_lanes(plan, n); *chain = msm_plan_chain(plan);
+  for (int k = 0; k < 2; k++) { sum_rows[k] = plan.count[k]; fixed_terms[k] = plan.n_fixed[k]; }
+  if (rows_out)
+    for (int r = 0; r < plan.n_rows; r++) {
+      const MsmRow& w = plan.row[r];
+      int* o = rows_out + 9 * r;
+      o[0] = w.n_joint ? -1 : w.var_term; o[1] = w.pos_lo; o[2] = w.pos_hi; o[3] = w.unit_term; o[4] = w.sum; o[5] = w.glv_slot; o[6] = w.fw_lo; o[7] = w.fw_hi;
+      o[8] = 0;                                     // a joint row: the bit mask of the terms it walks together
+      for (int j = 0; j < w.n_joint; j++) o[8] |= 1 << plan.var_list[w.sum][w.var_term + j];
+    }
+  return BN254_OK;
+}
+int bn254_dbg_fr_inverse(const uint8_t in32[32], uint8_t out32[32], int which, int field) {
+  if (!in32 || !out32) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const FrCtx& F = field ? fp64_ctx().F : fr_ctx();
+  const FrM a = F.from_be_reduce(in32, 32);
+  F.to_be(out32, which == 1 ? F.inverse_fermat(a) : which == 2 ? F.inverse_bgcd(a) : F.inverse(a));
+  return BN254_OK;
+}
+// n products a_i * b_i in the field (operands: any 256-bit values, reduced and converted to Montgomery form first), through the
+// product form the DEVICE stages use (form 32: eight 32-bit words) or the host's (form 64: four 64-bit limbs on __int128); out = canonical big-endian
+int bn254_dbg_fr_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int form, int field) {
+  if ((!a || !b || !out) && n) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (form != 32 && form != 64) return set_err(BN254_E_BAD_ARG, "form is 32 or 64");
+  const FrCtx& F = field ? fp64_ctx().F : fr_ctx();
+  for (size_t i = 0; i < n; i++) {
+    const FrM x = F.from_be_reduce(a + 32 * i, 32), y = F.from_be_reduce(b + 32 * i, 32);
+    F.to_be(out + 32 * i, form == 32 ? F.mul_w32(x, y) : F.mul_w64(x, y));
+  }
+  return BN254_OK;
+}
+
+// The fixed-base tables a device built for a key (bn254_k_comb.hip) against the host constructions (build_comb_table / build_window_table): the tables of the first `inputs`
+// points are read back and compared entry by entry as field values.  *mismatches = entries that differ (0: identical); needs a device.
+static int compare_tables(int form, const std::vector<int32_t>& pts, const int32_t* d_tab, int inputs, size_t* mismatches) {
+  const size_t np = pts.size() / (2 * BN_NL), n_entries = form == 0 ? ((size_t)1 << G16_COMB_TEETH) : (size_t)32 * 255, per = n_entries * MSM_ENTRY_DWORDS;
+  if ((size_t)inputs > np) inputs = (int)np;
+  std::vector<int32_t> dev_tab((size_t)inputs * per), host_tab(per);
+  HIPCK(hipMemcpy(dev_tab.data(), d_tab, dev_tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+  size_t bad = 0;
+  for (int i = 0; i < inputs; i++) {
+    G1Aff K; K.x = fp_from_limbs(pts.data() + (size_t)i * 2 * BN_NL); K.y = fp_from_limbs(pts.data() + (size_t)i * 2 * BN_NL + BN_NL);
+    if (form == 0) build_comb_table(host_tab.data(), K); else build_window_table(host_tab.data(), K);
+    for (size_t e = form == 0 ? 1 : 0; e < n_entries; e++) {
+      const int32_t* a = dev_tab.data() + (size_t)i * per + e * MSM_ENTRY_DWORDS; const int32_t* b = host_tab.data() + e * MSM_ENTRY_DWORDS;
+      if (!fp_eq(fp_from_limbs(a), fp_from_limbs(b)) || !fp_eq(fp_from_limbs(a + BN_NL), fp_from_limbs(b + BN_NL)) || a[18] != 0 || a[19] != 0) bad++;
+    }
+  }
+  *mismatches = bad;
+  return BN254_OK;
+}
+// window tables of MSM_FW_BITS bits (form 2): MSM_FW_WINDOWS x (2^MSM_FW_BITS - 1) entries per point: every window's first, middle and last entries and a pseudo-random
+// sample, each against d 2^(bits w) P by double-and-add
+static int compare_window_tables(const std::vector<int32_t>& pts, const int32_t* d_tab, size_t* mismatches) {
+  const size_t np = pts.size() / (2 * BN_NL), per = (size_t)MSM_FW_WINDOWS * MSM_FW_ENTRIES;
+  size_t bad = 0;
+  uint64_t x = 0x9E3779B97F4A7C15ull;
+  std::vector<int32_t> e(MSM_ENTRY_DWORDS);
+  for (size_t i = 0; i < np; i++) {
+    G1Aff P; P.x = fp_from_limbs(pts.data() + i * 2 * BN_NL); P.y = fp_from_limbs(pts.data() + i * 2 * BN_NL + BN_NL);
+    G1Proj bw = g1_from_affine(P);
+    for (int w = 0; w < MSM_FW_WINDOWS; w++) {
+      std::vector<uint32_t> ds = {1, 2, 3, 255 % MSM_FW_ENTRIES + 1, 256 % MSM_FW_ENTRIES + 1, (MSM_FW_ENTRIES >> 1), (MSM_FW_ENTRIES >> 1) + 1, MSM_FW_ENTRIES - 1, MSM_FW_ENTRIES};
+      for (int k = 0; k < 14; k++) { x ^= x >> 12; x ^= x << 25; x ^= x >> 27; ds.push_back(1 + (uint32_t)((x * 0x2545F4914F6CDD1Dull) >> 40) % MSM_FW_ENTRIES); }
+      for (uint32_t dd : ds) {
+        HIPCK(hipMemcpy(e.data(), d_tab + (i * per + (size_t)w * MSM_FW_ENTRIES + dd - 1) * MSM_ENTRY_DWORDS, MSM_ENTRY_DWORDS * sizeof(int32_t), hipMemcpyDeviceToHost));
+        G1Proj acc = g1_identity();
+        for (int bit = MSM_FW_BITS - 1; bit >= 0; bit--) { acc = g1_dbl(acc); if ((dd >> bit) & 1) acc = g1_add(acc, bw); }
+        const G1Aff want = g1_to_affine(acc);
+        if (!fp_eq(fp_from_limbs(e.data()), want.x) || !fp_eq(fp_from_limbs(e.data() + BN_NL), want.y) || e[18] != 0 || e[19] != 0) bad++;
+      }
+      for (int b = 0; b < MSM_FW_BITS; b++) bw = g1_dbl(bw);
+    }
+  }
+  *mismatches = bad;
+  return BN254_OK;
+}
+int bn254_dbg_comb_table_compare(const bn254_g16_pvk* pvk, int device, int inputs, size_t* mismatches) {
+  if (!pvk || !mismatches || inputs < 1) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (pvk->host.kpts.empty()) return set_err(BN254_E_BAD_ARG, "the key's tables were not built on the device");
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  int rc = ensure_dev(pvk, *d, device, 1);
+  if (rc) return rc;
+  const int form = g16_table_form(pvk->host);
+  if (form == 2) return compare_window_tables(pvk->host.kpts, d->msm, mismatches);
+  return compare_tables(form, pvk->host.kpts, d->msm, inputs, mismatches);
+}
+int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t* mismatches) {
+  if (!pvk || !mismatches) return set_err(BN254_E_BAD_ARG, "bad argument");
+  PlonkDev* d;
+  std::lock_guard<std::mutex> lk(pvk->mu);
+  int rc = plonk_ensure_dev(pvk, device, &d);
+  if (rc) return rc;
+  return compare_window_tables(pvk->fixed_pts, d->fixed_tabs, mismatches);
+}
+// host-only probe of the comb tables of keys with many public inputs: x * P from build_comb_table(P) and the column digits the kernels use
+int bn254_dbg_comb_mul(const uint8_t p64[64], const uint8_t x32[32], uint8_t out64[64]) {
+  if (!p64 || !x32 || !out64) return set_err(BN254_E_BAD_ARG, "bad argument");
+  G1Aff P; P.x = fp_from_be(p64); P.y = fp_from_be(p64 + 32);
+  if (!g1_on_curve(P)) return set_err(BN254_E_BAD_ARG, "not a curve point");
+  std::vector<int32_t> tab(((size_t)1 << G16_COMB_TEETH) * MSM_ENTRY_DWORDS);
+  build_comb_table(tab.data(), P);
+  uint32_t w[8];
+  for (int k = 0; k < 8; k++) { const uint8_t* q = x32 + 28 - 4 * k; w[k] = (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | (uint32_t)q[3]; }
+  G1Proj acc = g1_identity();
+  for (int col = G16_COMB_COLS - 1; col >= 0; col--) {
+    acc = g1_dbl(acc);
+    const uint32_t idx = g16_comb_digit(w, col);
+    if (idx) {
+      G1Aff e; e.x = fp_from_limbs(tab.data() + (size_t)idx * MSM_ENTRY_DWORDS); e.y = fp_from_limbs(tab.data() + (size_t)idx * MSM_ENTRY_DWORDS + BN_NL);
+      acc = g1_add_mixed(acc, e);
+    }
+  }
+  if (g1_is_identity(acc)) { memset(out64, 0, 64); return BN254_OK; }
+  enc_g1_uncompressed(out64, g1_to_affine(acc));
+  return BN254_OK;
+}
+
+// ---------------------------------------------------------------- synthetic workload generator
+size_t bn254_synth_groth16_vk_len(size_t n_public) { return 292 + 32 * (n_public + 1) + 4 + 128; }
+
+int bn254_synth_groth16(uint64_t seed, size_t n_public, size_t n, int invalid_every, int agree, int threads, uint8_t* vk_out,
+                        uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected) {
+  return bn254_synth_groth16_range(seed, n_public, 0, n, invalid_every, agree, threads, vk_out, proofs_out, inputs_out, expected);
+}
+// proofs [first, first + n) of the stream bn254_synth_groth16 generates for `seed` (proof i is a function of (seed, i) alone), written to
+// positions 0 .. n-1 of the output buffers: a rank of a sharded job generates its own contiguous shard only
+int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size_t n, int invalid_every, int agree, int threads, uint8_t* vk_out,
+                              uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected) {
+  if (!vk_out || (n && (!proofs_out || !expected)) || (n && n_public && !inputs_out)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  static GenTables* tabs = nullptr;
+  static std::mutex tmu;
+  {
+    std::lock_guard<std::mutex> lk(tmu);
+    if (!tabs) { tabs = new GenTables(); build_gen_tables(*tabs); }
+  }
+  SplitMix64 rng{seed};
+  // trapdoors; beta, gamma, delta rejection-sampled into the mode-agreement set when asked:
+  // y(beta G2), y(gamma G2) must have c0 / c1 in DIFFERENT halves of [0,p), y(delta G2) in the SAME half
+  auto same_half = [](const G2Aff& q) { return fp_is_large(q.y.c0) == fp_is_large(q.y.c1); };
+  U256 alpha = fr_random(rng, true), beta, gamma, delta;
+  G2Aff beta2, gamma2, delta2;
+  const bool agree_modes = (agree & 1) != 0;     // agree bit 1 (value 2): every proof with index = 3 mod 7 has L = the identity (see the worker)
+  for (;;) { beta = fr_random(rng, true); beta2 = g2_mul_gen(*tabs, beta); if (!agree_modes || !same_half(beta2)) break; }
+  for (;;) { gamma = fr_random(rng, true); gamma2 = g2_mul_gen(*tabs, gamma); if (!agree_modes || !same_half(gamma2)) break; }
+  for (;;) { delta = fr_random(rng, true); delta2 = g2_mul_gen(*tabs, delta); if (!agree_modes || same_half(delta2)) break; }
+  std::vector<U256> kk(n_public + 1);
+  for (auto& k : kk) k = fr_random(rng, true);
+  // gnark-compressed vk: alpha1 | beta1 | beta2 | gamma2 | delta1 | delta2 | nK | K.. | 0 (no commitments) | 2 x G2 infinity
+  memset(vk_out, 0, bn254_synth_groth16_vk_len(n_public));
+  enc_g1_compressed(vk_out, g1_to_affine(g1_mul_gen(*tabs, alpha)));
+  enc_g1_compressed(vk_out + 32, g1_to_affine(g1_mul_gen(*tabs, beta)));
+  enc_g2_compressed(vk_out + 64, beta2);
+  enc_g2_compressed(vk_out + 128, gamma2);
+  enc_g1_compressed(vk_out + 192, g1_to_affine(g1_mul_gen(*tabs, delta)));
+  enc_g2_compressed(vk_out + 224, delta2);
+  uint32_t nk = (uint32_t)(n_public + 1);
+  vk_out[288] = (uint8_t)(nk >> 24); vk_out[289] = (uint8_t)(nk >> 16); vk_out[290] = (uint8_t)(nk >> 8); vk_out[291] = (uint8_t)nk;
+  for (size_t i = 0; i <= n_public; i++) enc_g1_compressed(vk_out + 292 + 32 * i, g1_to_affine(g1_mul_gen(*tabs, kk[i])));
+  size_t off = 292 + 32 * (n_public + 1) + 4;
+  vk_out[off] = 0x40; vk_out[off + 64] = 0x40;
+  if (n == 0) return BN254_OK;
+  U256 delta_inv = fr_inv(delta), alpha_beta = fr_mul(alpha, beta);
+  // a few twist points outside the r-torsion for the NOT_IN_SUBGROUP class
+  std::vector<G2Aff> bad_b;
+  if (invalid_every > 0) {
+    SplitMix64 r2{seed ^ 0xabcdef1234567ull};
+    while (bad_b.size() < 4) {
+      G2Aff q; U256 t0 = fr_random(r2, false), t1 = fr_random(r2, false);
+      uint8_t b0[32], b1[32]; u256_to_be(b0, t0); u256_to_be(b1, t1);
+      q.x.c0 = fp_from_be(b0); q.x.c1 = fp_from_be(b1);
+      if (!fp2_sqrt(q.y, fp2_add(fp2_mul(fp2_sqr(q.x), q.x), g2_twist_b()))) continue;
+      if (g2_in_subgroup(q)) continue;  // probability ~ 1/cofactor
+      bad_b.push_back(q);
+    }
+  }
+  if (threads <= 0) { threads = (int)std::thread::hardware_concurrency(); if (threads <= 0) threads = 1; }
+  if ((size_t)threads > n) threads = (int)n;
+  G1Aff g1gen; g1gen.x = fp_one(); g1gen.y = fp_add(fp_one(), fp_one());
+  auto worker = [&](int tid) {
+    for (size_t li = tid; li < n; li += threads) {
+      const size_t i = first + li;   // global index: seeds the proof and selects its class
+      SplitMix64 r{seed * 0x9e3779b97f4a7c15ull + 0x1000 + i};
+      U256 a = fr_random(r, true), b = fr_random(r, true);
+      U256 ell = kk[0];
+      std::vector<U256> xs(n_public);
+      for (size_t s = 0; s < n_public; s++) { xs[s] = fr_random(r, false); ell = fr_add(ell, fr_mul(xs[s], kk[s + 1])); }
+      if ((agree & 2) && n_public > 0 && i % 7 == 3) {
+        // L = K0 + sum x_s K_s = the identity: the last input cancels the rest (valid proofs whose public-input point is the point at infinity --
+        // bn::pairing_batch skips such a pair; the kernels replace its line by 1)
+        const size_t last = n_public - 1;
+        ell = fr_sub(ell, fr_mul(xs[last], kk[last + 1]));
+        U256 zero = {{0, 0, 0, 0}};
+        xs[last] = fr_mul(fr_sub(zero, ell), fr_inv(kk[last + 1]));
+        ell = zero;
+      }
+      // c = (a b - alpha beta - gamma ell) / delta   =>   e(A,B) = e(alpha,beta) e(L,gamma) e(C,delta)
+      U256 c = fr_mul(fr_sub(fr_sub(fr_mul(a, b), alpha_beta), fr_mul(gamma, ell)), delta_inv);
+      G1Aff A = g1_to_affine(g1_mul_gen(*tabs, a));
+      G2Aff B = g2_mul_gen(*tabs, b);
+      G1Proj Cp = g1_mul_gen(*tabs, c);
+      uint8_t st = BN254_ACCEPT;
+      int cls = -1;
+      if (invalid_every > 0 && (i % (size_t)invalid_every) == (size_t)invalid_every - 1) cls = (int)((i / (size_t)invalid_every) % 5);
+      if (cls == 1) { Cp = g1_add_mixed(Cp, g1gen); st = BN254_REJECT; }
+      if (cls == 3) { B = bad_b[(i / (size_t)invalid_every) % bad_b.size()]; st = BN254_ERR_NOT_IN_SUBGROUP; }
+      G1Aff C = g1_is_identity(Cp) ? g1gen : g1_to_affine(Cp);
+      uint8_t* p = proofs_out + 256 * li;
+      enc_g1_uncompressed(p, A); enc_g2_uncompressed(p + 64, B); enc_g1_uncompressed(p + 192, C);
+      for (size_t s = 0; s < n_public; s++) u256_to_be(inputs_out + (li * n_public + s) * 32, xs[s]);
+      if (cls == 0 && n_public > 0) {  // x_0 + 1 (as raw integer; stays below 2^256)
+        U256 one = {{1, 0, 0, 0}}, t; u256_add(t, xs[0], one); u256_to_be(inputs_out + li * n_public * 32, t); st = BN254_REJECT;
+      }
+      if (cls == 2) {  // A.y + 1 mod p: off the curve (y+1 = -y only for y = (p-1)/2)
+        Fp y1 = fp_add(A.y, fp_one()); fp_to_be(p + 32, y1); st = BN254_ERR_NOT_ON_CURVE;
+      }
+      if (cls == 4) { memset(p, 0xff, 32); st = BN254_ERR_NOT_MEMBER; }  // A.x = 2^256 - 1 >= p
+      expected[li] = st;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; t++) th.emplace_back(worker, t);
+  for (auto& x : th) x.join();
+  return BN254_OK;
+}
+
+}  // extern "C"

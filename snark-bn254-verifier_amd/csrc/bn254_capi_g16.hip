@@ -1,0 +1,695 @@
+// bn254_capi_g16.hip -- the Groth16 half of the C ABI (include/bn254_verify.h): per (key, device) state and tables, the exact and RLC enqueue paths,
+// the stream-overlap bookkeeping, the pinned ring of the host-buffer entry, and every bn254_groth16_* entry.
+#include "bn254_capi_internal.h"
+
+// The HIP runtime multiplexes every stream of the process onto GPU_MAX_HW_QUEUES hardware queues -- four by default -- and streams that share a queue run one
+// after the other: the two sub-batch streams of a large Groth16 batch then lose their overlap once a third party (RCCL) has streams too, and eight PlonK chains
+// run at 1.20 instead of 1.51 M proofs/s (profiles/r03_batch_sweep_fine.txt).  The runtime reads the variable when it initialises, so it is a DEPLOYMENT setting
+// (GPU_MAX_HW_QUEUES in the environment of the process); the library does not touch the environment.  What it does instead: the first batch
+// that runs two sub-batch streams brackets them with events, the next call reads the overlap (bn254_groth16_stream_overlap), and a device whose sub-batch streams
+// were found to run one after the other gets one sub-batch per launch from then on (same work, fewer launches) and a line in bn254_last_diagnostic().
+static thread_local std::string g_diag;
+static std::atomic<int> g_profiling{0};
+static std::atomic<unsigned> g_prof_mask{0xffffffffu};
+static std::atomic<unsigned> g_prof_epoch{0};   // bumped by the two profiling setters: an accumulating profile (mode 2) starts over at the next batch
+// Knobs of the RLC batch mode.  Initial values come from the environment (env_long); afterwards only bn254_set_rlc_params changes them.
+#define RLC_MIN_BATCH 64            // below this the mode has no groups to speak of
+#define RLC_PAYS_FROM 200000        // the mode is a longer pipeline (~18 ms whatever the size): measured 0.12 x at 4096, 0.45 x at 16384, 0.94 x at 2^17, 2.0 x at 2^20
+static std::atomic<long> g_rlc_min_batch{[] { long v = env_long("BN254_RLC_MIN_BATCH", RLC_PAYS_FROM); return v < RLC_MIN_BATCH ? (long)RLC_MIN_BATCH : v; }()};
+static std::atomic<int> g_rlc_adaptive{env_long("BN254_RLC_ADAPTIVE", 1) != 0 ? 1 : 0};
+static std::atomic<long> g_rlc_share_min_lanes{env_long("BN254_RLC_SHARE_MIN_LANES", 65536)};
+
+static void rlc_dev_free(RlcDev& r) {
+  void* ptrs[] = {r.btab, r.tab, r.one, r.grp_status, r.idx, r.fb_proofs, r.fb_inputs, r.fb_status};
+  for (auto q : ptrs) if (q) (void)hipFree(q);
+  if (r.h_status) (void)hipHostFree(r.h_status);
+  if (r.h_idx) (void)hipHostFree(r.h_idx);
+  const RlcDev keep = r;
+  r = RlcDev();
+  r.have_obs = keep.have_obs; r.fb_share = keep.fb_share; r.bypassed = keep.bypassed; r.bypassed_total = keep.bypassed_total;
+}
+#define OV_AGREE 3
+#define OV_REPROBE 256
+
+DevState* dev_state(const bn254_g16_pvk* pvk, int device) {
+  std::lock_guard<std::mutex> lk(pvk->mu);
+  return &pvk->dev[device];   // std::map nodes never move
+}
+// caller holds d.mu
+int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n) {
+  int rc = check_device(device);
+  if (rc) return rc;
+  if (!d.ready) {
+    if ((rc = upload(&d.k0, pvk->host.k0)) || (rc = upload(&d.gtab, pvk->host.gtab)) || (rc = upload(&d.dtab, pvk->host.dtab)) || (rc = upload(&d.target, pvk->host.target)))
+      return rc;
+    // comb tables above 16 inputs; 13-bit windows (bn254_fw.h) up to 16; byte windows only for the diagnostic BN254_WIDE_COMB=0 (k_g16_msm_partial)
+    if (!pvk->host.kpts.empty() && pvk->host.msm.empty()) { if ((rc = build_tables_on_device(g16_table_form(pvk->host), pvk->host.kpts, &d.msm))) return rc; }
+    else if ((rc = upload(&d.msm, pvk->host.msm))) return rc;
+    HIPCK(hipEventCreateWithFlags(&d.busy_ev, hipEventDisableTiming));
+    d.ready = true;
+  }
+  // what a reservation of n proofs needs (bn254_g16_plan.h: the same function the plan probe and its property test read)
+  const G16Alloc need = g16_alloc_for(n, pvk->host.key_inputs(), pvk->host.msm_comb);
+  if (need.ws_proofs > d.ws_cap) {
+    if (d.ws) HIPCK(hipFree(d.ws));   // hipFree waits for the device: no batch is still using the old workspace
+    d.ws = nullptr; d.ws_cap = 0;
+    HIPCK(hipMalloc((void**)&d.ws, need.ws_proofs * (size_t)G16_WS_BYTES_PER_PROOF));
+    d.ws_cap = need.ws_proofs;
+  }
+  // keys with many public inputs: partial sums (and comb digits) of the public-input MSM, for the proofs of one launch.  Sized HERE (reserve /
+  // the entry points call ensure_dev before they enqueue), so that the enqueue path itself never allocates or frees
+  if (need.msm_part_proofs > d.msm_part_cap) {
+    if (d.msm_part) HIPCK(hipFree(d.msm_part));
+    d.msm_part = nullptr; d.msm_part_cap = 0;
+    HIPCK(hipMalloc((void**)&d.msm_part, need.msm_part_bytes + need.msm_digit_bytes));
+    d.msm_part_cap = need.msm_part_proofs; d.msm_chunks = need.msm_chunks;
+  }
+  if (g_profiling.load() && !d.ev_ready) {
+    for (int i = 0; i < 5; i++) HIPCK(hipEventCreate(&d.ev[i]));
+    const int cap = 1024;  // launches per sub-batch: ~720
+    d.prof_ev.resize(2 * cap); d.prof_kid.resize(cap);
+    for (auto& e : d.prof_ev) HIPCK(hipEventCreate(&e));
+    d.prof.ev = d.prof_ev.data(); d.prof.kid = d.prof_kid.data(); d.prof.cap = cap;
+    d.prof2_ev.resize(2 * cap); d.prof2_kid.resize(cap);
+    for (auto& e : d.prof2_ev) HIPCK(hipEventCreate(&e));
+    d.prof2.ev = d.prof2_ev.data(); d.prof2.kid = d.prof2_kid.data(); d.prof2.cap = cap;
+    d.ev_ready = true;
+  }
+  return BN254_OK;
+}
+static int ensure_aux(DevState& d, int count) {
+  if (count > 3) count = 3;
+  if (!d.fork_ev) {
+    HIPCK(hipEventCreateWithFlags(&d.fork_ev, hipEventDisableTiming));
+    for (int i = 0; i < 4; i++) HIPCK(hipEventCreateWithFlags(&d.join_ev[i], hipEventDisableTiming));
+  }
+  while (d.aux_count < count) { HIPCK(hipStreamCreateWithFlags(&d.aux[d.aux_count], hipStreamNonBlocking)); d.aux_count++; }
+  return BN254_OK;
+}
+// part pi of a batch split over concurrent streams: slot pi % 4, slot 0 = the caller's stream, slots 1..3 = the auxiliary streams
+static inline hipStream_t part_stream(DevState& d, hipStream_t user, int pi) { const int k = pi % 4; return k == 0 ? user : d.aux[k - 1]; }
+static void dev_free(DevState& d) {
+  int32_t* ptrs[] = {d.k0, d.gtab, d.dtab, d.target, d.msm, d.ws, d.msm_part};
+  for (auto q : ptrs) if (q) (void)hipFree(q);
+  uint8_t* bp[] = {d.st_proofs, d.st_inputs, d.st_status};
+  for (auto q : bp) if (q) (void)hipFree(q);
+  if (d.ev_ready) { for (int i = 0; i < 5; i++) (void)hipEventDestroy(d.ev[i]); for (auto& e : d.prof_ev) (void)hipEventDestroy(e); for (auto& e : d.prof2_ev) (void)hipEventDestroy(e); }
+  for (int i = 0; i < d.aux_count; i++) (void)hipStreamDestroy(d.aux[i]);
+  if (d.fork_ev) { (void)hipEventDestroy(d.fork_ev); for (int i = 0; i < 4; i++) (void)hipEventDestroy(d.join_ev[i]); }
+  if (d.busy_ev) (void)hipEventDestroy(d.busy_ev);
+  for (auto& e : d.ov_ev) if (e) (void)hipEventDestroy(e);
+  if (d.host_stream) (void)hipStreamDestroy(d.host_stream);
+  if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);
+  for (int i = 0; i < 3; i++) { if (d.pin[i]) (void)hipHostFree(d.pin[i]); if (d.pin_ev[i]) (void)hipEventDestroy(d.pin_ev[i]); }
+  rlc_dev_free(d.rlc);
+}
+static int grow(uint8_t** p, size_t* cap, size_t need) {
+  if (need <= *cap) return BN254_OK;
+  if (*p) HIPCK(hipFree(*p));
+  *p = nullptr; *cap = 0;
+  HIPCK(hipMalloc((void**)p, need));
+  *cap = need;
+  return BN254_OK;
+}
+
+static KeyCache<bn254_g16_pvk, bn254_groth16_vk_free>& g16_key_cache() { static auto* c = new KeyCache<bn254_g16_pvk, bn254_groth16_vk_free>(); return *c; }
+
+extern "C" {
+
+void bn254_set_profiling(int enabled) { g_profiling.store(enabled); g_prof_epoch++; }
+void bn254_set_profile_kernels(unsigned mask) { g_prof_mask.store(mask); g_prof_epoch++; }
+int bn254_groth16_num_kernel_kinds(void) { return KID_COUNT; }
+const char* bn254_groth16_kernel_kind_name(int i) {
+  if (i == KID_MSM_PARTIAL) { const char* e = getenv("BN254_WIDE_COMB"); if (!(e && atoi(e) == 0)) return "k_g16_msm_partial_comb"; }   // the table form in use
+  return (i >= 0 && i < KID_COUNT) ? bn254_kernel_kind_names[i] : "";
+}
+const char* bn254_groth16_kernel_name(int i) {
+  static const char* names[BN254_G16_NUM_KERNELS] = {"phase_prepare", "phase_miller", "phase_subgroup", "phase_finalexp"};
+  return (i >= 0 && i < BN254_G16_NUM_KERNELS) ? names[i] : "";
+}
+
+int bn254_groth16_vk_prepare(const uint8_t* vk, size_t vk_len, unsigned mode, bn254_g16_pvk** out) {
+  if (!vk || !out || mode > 1) return set_err(BN254_E_BAD_ARG, "bad argument");
+  *out = nullptr;
+  G16Key key;
+  if (parse_g16_vk(key, vk, vk_len, (int)mode) != DEC_OK) return set_err(BN254_E_VK, "verifying key does not parse");
+  bn254_g16_pvk* p = new (std::nothrow) bn254_g16_pvk();
+  if (!p) return set_err(BN254_E_NOMEM, "out of memory");
+  if (!prepare_g16(p->host, key, (int)mode)) { delete p; return set_err(BN254_E_VK, "no line table for a G2 element of the key (unreachable for a point on the twist: bn254_host.hpp::prepare_g16)"); }
+  *out = p;
+  return BN254_OK;
+}
+void bn254_groth16_vk_free(bn254_g16_pvk* pvk) {
+  if (!pvk) return;
+  for (auto& kv : pvk->dev) {
+    if (hipSetDevice(kv.first) != hipSuccess) continue;
+    (void)hipDeviceSynchronize();
+    dev_free(kv.second);
+  }
+  delete pvk;
+}
+size_t bn254_groth16_vk_num_public(const bn254_g16_pvk* pvk) { return pvk ? (pvk->host.n_k ? pvk->host.n_k - 1 : (size_t)-1) : 0; }
+
+int bn254_groth16_reserve(const bn254_g16_pvk* pvk, size_t n, int device) {
+  if (!pvk) return set_err(BN254_E_BAD_ARG, "null key");
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  return ensure_dev(pvk, *d, device, n ? n : 1);
+}
+
+}  // extern "C"
+
+// Enqueue the exact pipeline for n proofs on `user`.  Caller holds d->mu and has called ensure_dev.
+static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* d_proofs, size_t proof_stride, const void* d_inputs,
+                             size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
+  // BN254_STREAMS = 1..4 sub-batches in flight (default 2: +4.5 % over one stream at 2^20, profiles/r01_streams.txt)
+  static const int n_streams = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
+  // BN254_CHUNK_LOG2 (experiment): proofs per workspace chunk, default 2^20
+  static const size_t chunk = [] { const char* e = getenv("BN254_CHUNK_LOG2"); int v = e ? atoi(e) : 20; if (v < 12) v = 12; if (v > 20) v = 20; return (size_t)1 << v; }();
+  const int profiling = g_profiling.load();
+  // the overlap of the sub-batch streams, measured on an earlier batch: read it once it is there (no waiting)
+  if (d->ov_state == 1 && hipEventQuery(d->ov_ev[1]) == hipSuccess && hipEventQuery(d->ov_ev[3]) == hipSuccess) {
+    float a0 = 0, a1 = 0, s1 = 0, e1 = 0;
+    if (hipEventElapsedTime(&a0, d->ov_ev[0], d->ov_ev[1]) == hipSuccess && hipEventElapsedTime(&a1, d->ov_ev[2], d->ov_ev[3]) == hipSuccess &&
+        hipEventElapsedTime(&s1, d->ov_ev[0], d->ov_ev[2]) == hipSuccess && hipEventElapsedTime(&e1, d->ov_ev[0], d->ov_ev[3]) == hipSuccess) {
+      const float lo_ = s1 < 0 ? s1 : 0, hi_ = e1 > a0 ? e1 : a0;
+      d->ov_ratio = (a0 + a1) / (hi_ - lo_ > 1e-6f ? hi_ - lo_ : 1e-6f);
+      static const bool fallback = [] { const char* e = getenv("BN254_STREAM_FALLBACK"); return !e || atoi(e) != 0; }();
+      if (d->ov_ratio < 1.15f) {
+        d->ov_serial_votes++;
+        if (d->ov_serial_votes >= OV_AGREE || d->ov_probe) {
+          d->single_stream = fallback;
+          d->diag = "the two sub-batch streams of a Groth16 batch ran one after the other on this device (overlap " + std::to_string(d->ov_ratio) + ", " +
+                    std::to_string(d->ov_serial_votes) + " measurements in a row): the process's streams share a hardware queue -- give it more queues (GPU_MAX_HW_QUEUES, read when the HIP runtime "
+                    "initialises; INTEGRATION.md)" + (fallback ? "; using one sub-batch per launch, re-measured every " + std::to_string(OV_REPROBE) + " batches" : "");
+        }
+      } else {
+        d->ov_serial_votes = 0;
+        if (d->single_stream) d->diag = "the sub-batch streams overlap again (" + std::to_string(d->ov_ratio) + "): back to two sub-batches side by side";
+        d->single_stream = false;
+      }
+      // keep measuring until the question is settled either way: OV_AGREE agreeing answers
+      d->ov_state = (d->ov_serial_votes > 0 && d->ov_serial_votes < OV_AGREE && !d->single_stream) ? 0 : 2;
+    } else d->ov_state = 2;
+    d->ov_probe = false;
+  }
+  // on one sub-batch per launch: every OV_REPROBE-th batch tries two streams again and is measured
+  bool probe_now = false;
+  if (d->single_stream && d->ov_state == 2 && ++d->ov_batches % OV_REPROBE == 0) { probe_now = true; d->ov_probe = true; d->ov_state = 0; }
+  for (size_t off = 0; off < n; off += chunk) {
+    size_t m = n - off < chunk ? n - off : chunk;
+    G16ChunkPlan plan;
+    if (!g16_plan_chunk(plan, m, pvk->host.key_inputs(), n_public, n_streams, d->single_stream && !probe_now)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    const bool wide = plan.wide, concurrent = plan.concurrent, split_small = plan.split_small;
+    const int parts = plan.parts;
+    // the buffers were sized by ensure_dev (bn254_groth16_reserve or the entry point itself): this path only enqueues, after checking the plan against them
+    if (m > d->ws_cap) return set_err(BN254_E_BAD_ARG, "workspace smaller than the batch: bn254_groth16_reserve first");
+    if (wide) for (int pi = 0; pi < parts; pi++)
+      if (plan.part[pi].count > d->msm_part_cap) return set_err(BN254_E_BAD_ARG, "workspace of a key with many public inputs is smaller than the batch: bn254_groth16_reserve first");
+    if (concurrent || split_small) { int rc = ensure_aux(*d, concurrent ? parts - 1 : 2); if (rc) return rc; }
+    if (concurrent) HIPCK(hipEventRecord(d->fork_ev, user));
+    // the first two sub-batches of a batch that runs several, while the question is open -- and only when the two are of (nearly) equal size: a short second part
+    // beside a long first one reads as "no overlap" whatever the queues do
+    const bool measure_overlap = concurrent && parts >= 2 && d->ov_state == 0 && plan.part[1].count * 10 >= plan.part[0].count * 9;
+    if (measure_overlap) for (auto& e : d->ov_ev) if (!e) HIPCK(hipEventCreate(&e));
+    for (int pi = 0; pi < parts; pi++) {
+      const size_t lo = plan.part[pi].first, hi = lo + plan.part[pi].count;
+      hipStream_t st = concurrent ? part_stream(*d, user, pi) : user;
+      if (concurrent && pi < 4 && st != user) HIPCK(hipStreamWaitEvent(st, d->fork_ev, 0));
+      if (measure_overlap && pi < 2) HIPCK(hipEventRecord(d->ov_ev[2 * pi], st));
+      G16LaunchArgs a;
+      a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
+      a.inputs = (const uint8_t*)d_inputs + (off + lo) * n_public * 32; a.n_public = (int)n_public; a.n = hi - lo;
+      a.ws = d->ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.status = (uint8_t*)d_status + off + lo; a.msm_tab = d->msm; a.k0 = d->k0;
+      a.gtab = d->gtab; a.dtab = d->dtab; a.target = d->target;
+      a.inputs_match_key = pvk->host.inputs_match(n_public) ? 1 : 0;
+      a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+      a.part_of_larger = parts > 1 ? 1 : 0;
+      a.msm_part = wide ? d->msm_part : nullptr;
+      a.msm_comb = pvk->host.msm_comb ? 1 : 0;
+      a.msm_digits = (wide && pvk->host.msm_comb) ? (uint16_t*)(d->msm_part + d->msm_chunks * 27 * d->msm_part_cap) : nullptr;
+      if (split_small && parts == 1) {
+        a.split_streams[0] = d->aux[0]; a.split_streams[1] = d->aux[1];
+        a.split_ev[0] = d->fork_ev; a.split_ev[1] = d->join_ev[1]; a.split_ev[2] = d->join_ev[2];
+      }
+      // the events bracket the kernels of the LAST chunk only (one chunk for n <= 2^20)
+      const bool prof_this = profiling && d->ev_ready && pi == 0;
+      // mode 1: the event pairs of THIS batch; mode 2: the pairs accumulate over the batches enqueued since the last call of a profiling setter (a caller that
+      // times many back-to-back batches reads them once at the end instead of synchronising with every batch; a full pool simply stops recording)
+      const unsigned epoch = g_prof_epoch.load();
+      const bool keep = profiling == 2 && d->prof_epoch == epoch && d->prof.used > 0;
+      if (prof_this) {
+        d->prof.mask = g_prof_mask.load(); d->prof_n = a.n; d->prof_epoch = epoch;
+        if (!keep) { d->prof.used = 0; d->prof2.used = 0; d->prof2_used = false; }
+      }
+      const bool prof_second = profiling && d->ev_ready && pi == 1;
+      if (prof_second) { d->prof2.mask = g_prof_mask.load(); if (!keep) d->prof2.used = 0; d->prof2_used = true; }
+      hipError_t e = bn254_launch_g16(a, st, prof_this ? d->ev : nullptr, prof_this ? &d->prof : (prof_second ? &d->prof2 : nullptr));
+      if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
+                                           std::string("kernel launch: ") + hipGetErrorString(e));
+      if (measure_overlap && pi < 2) HIPCK(hipEventRecord(d->ov_ev[2 * pi + 1], st));
+      if (concurrent && (pi + 4 >= parts) && st != user) { HIPCK(hipEventRecord(d->join_ev[pi % 4], st)); HIPCK(hipStreamWaitEvent(user, d->join_ev[pi % 4], 0)); }
+    }
+    if (measure_overlap) d->ov_state = 1;
+  }
+  d->ev_recorded = profiling && d->ev_ready;
+  return BN254_OK;
+}
+
+// ---- BN254_FLAG_RLC (bn254_rlc.h): first pass in groups, exact second pass over the proofs of groups that failed -----------------------------
+static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_public) {
+  RlcDev& r = d->rlc;
+  if (!r.ready) {
+    {
+      std::lock_guard<std::mutex> lk(pvk->mu);
+      if (!pvk->rlc_host.ready && !prepare_g16_rlc(pvk->rlc_host, pvk->host)) return set_err(BN254_E_VK, "degenerate key element (RLC tables)");
+    }
+    int rc;
+    if ((rc = upload(&r.btab, pvk->rlc_host.btab)) || (rc = upload(&r.one, pvk->rlc_host.one))) return rc;
+    if ((rc = build_tables_on_device(2, pvk->rlc_host.pts, &r.tab))) return rc;      // -alpha and K[0]: 13-bit windows like the key's own (vm_rlc_group_points reads both)
+    r.ready = true;
+  }
+  if (n > r.grp_cap) {
+    if (r.grp_status) HIPCK(hipFree(r.grp_status));
+    if (r.idx) HIPCK(hipFree(r.idx));
+    if (r.h_status) HIPCK(hipHostFree(r.h_status));
+    if (r.h_idx) HIPCK(hipHostFree(r.h_idx));
+    r.grp_status = nullptr; r.idx = nullptr; r.h_status = nullptr; r.h_idx = nullptr; r.grp_cap = r.idx_cap = r.h_cap = 0;
+    const size_t cap = g16_rlc_alloc(n);               // group status regions of the launch parts are rounded up to 256 each (bn254_g16_plan.h)
+    HIPCK(hipMalloc((void**)&r.grp_status, cap));
+    HIPCK(hipMalloc((void**)&r.idx, cap * sizeof(uint32_t)));
+    HIPCK(hipHostMalloc((void**)&r.h_status, cap, hipHostMallocDefault));
+    HIPCK(hipHostMalloc((void**)&r.h_idx, cap * sizeof(uint32_t), hipHostMallocDefault));
+    r.grp_cap = r.idx_cap = r.h_cap = n;
+  }
+  (void)n_public;
+  return BN254_OK;
+}
+static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
+                           size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
+  (void)device;
+  static const int n_streams = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
+  static const int log2_group = [] { const char* e = getenv("BN254_RLC_GROUP_LOG2"); int v = e ? atoi(e) : 5; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
+  // proofs per lane in the Miller loop (shared accumulator, one squaring of f per lane and step): 2^BN254_RLC_SHARE_LOG2, at most the group
+  static const int log2_share_env = [] { const char* e = getenv("BN254_RLC_SHARE_LOG2"); int v = e ? atoi(e) : 3; return v < 0 ? 0 : (v > 3 ? 3 : v); }();
+  uint32_t key[11];
+  if (getrandom(key, sizeof key, 0) != (ssize_t)sizeof key) return set_err(BN254_E_HIP, "getrandom failed: no weights for the RLC mode");
+  size_t seen_checked = 0, seen_fallback = 0;
+  const size_t chunk = G16_MAX_BATCH;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = n - off < chunk ? n - off : chunk;
+    int rc = rlc_ensure(pvk, d, m, n_public);
+    if (rc) return rc;
+    RlcDev& r = d->rlc;
+    const int parts = g16_rlc_parts(m, n_streams);
+    {
+      const long ml0 = g_rlc_share_min_lanes.load();
+      if (g16_rlc_need(m, n_streams, log2_group, log2_share_env, ml0 < 1 ? 1 : (size_t)ml0) > g16_rlc_alloc(r.grp_cap)) return set_err(BN254_E_HIP, "RLC group buffer smaller than the batch (internal sizing error)");
+    }
+    const bool concurrent = parts > 1;
+    if (concurrent) { rc = ensure_aux(*d, parts - 1); if (rc) return rc; HIPCK(hipEventRecord(d->fork_ev, user)); }
+    const size_t per = ((m + parts - 1) / parts + 255) / 256 * 256;
+    size_t grp_off = 0;
+    for (int pi = 0; pi < parts; pi++) {
+      const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
+      if (lo >= hi) break;
+      hipStream_t st = concurrent ? part_stream(*d, user, pi) : user;
+      if (concurrent && pi < 4 && st != user) HIPCK(hipStreamWaitEvent(st, d->fork_ev, 0));
+      G16LaunchArgs a;
+      a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
+      a.inputs = (const uint8_t*)d_inputs + (off + lo) * n_public * 32; a.n_public = (int)n_public; a.n = hi - lo;
+      a.ws = d->ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.status = (uint8_t*)d_status + off + lo; a.msm_tab = d->msm; a.k0 = d->k0;
+      a.gtab = d->gtab; a.dtab = d->dtab; a.target = d->target;
+      a.inputs_match_key = 1;
+      a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+      a.msm_part = nullptr;
+      RlcLaunchArgs ra;
+      memcpy(ra.key, key, sizeof key);
+      ra.counter_base = (uint32_t)(off + lo);
+      // sharing needs enough lanes to fill the GPU; small parts keep one proof per lane
+      const long ml = g_rlc_share_min_lanes.load();
+      const int log2_share = g16_rlc_share(a.n, log2_group, log2_share_env, ml < 1 ? 1 : (size_t)ml);
+      ra.plan = rlc_plan((uint32_t)a.n, log2_group, log2_share);
+      ra.grp_status = r.grp_status + grp_off; grp_off += ((size_t)ra.plan.groups + 255) / 256 * 256;
+      ra.btab = r.btab; ra.rlc_tab = r.tab; ra.one = r.one;
+      hipError_t e = bn254_launch_g16_rlc(a, ra, st);
+      if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
+                                           std::string("kernel launch (rlc): ") + hipGetErrorString(e));
+      if (concurrent && (pi + 4 >= parts) && st != user) { HIPCK(hipEventRecord(d->join_ev[pi % 4], st)); HIPCK(hipStreamWaitEvent(user, d->join_ev[pi % 4], 0)); }
+    }
+    // which proofs are still pending (their group's product was not one)?  One stream synchronisation per chunk.
+    HIPCK(hipMemcpyAsync(r.h_status, (const uint8_t*)d_status + off, m, hipMemcpyDeviceToHost, user));
+    HIPCK(hipStreamSynchronize(user));
+    uint32_t cnt = 0;
+    for (size_t i = 0; i < m; i++) {
+      if (r.h_status[i] == BN254_ST_PENDING) r.h_idx[cnt++] = (uint32_t)i;
+      else if (r.h_status[i] == BN254_ST_ACCEPT) seen_checked++;
+    }
+    seen_checked += cnt; seen_fallback += cnt;
+    if (cnt == 0) continue;
+    if (cnt > r.fb_cap || (size_t)cnt * n_public * 32 > r.fb_in_cap) {
+      void* ptrs[] = {r.fb_proofs, r.fb_inputs, r.fb_status};
+      for (auto q : ptrs) if (q) HIPCK(hipFree(q));
+      r.fb_proofs = r.fb_inputs = r.fb_status = nullptr; r.fb_cap = r.fb_in_cap = 0;
+      const size_t cap = ((size_t)cnt + 4095) / 4096 * 4096;
+      HIPCK(hipMalloc((void**)&r.fb_proofs, cap * 256));
+      HIPCK(hipMalloc((void**)&r.fb_inputs, cap * (n_public ? n_public : 1) * 32));
+      HIPCK(hipMalloc((void**)&r.fb_status, cap));
+      r.fb_cap = cap; r.fb_in_cap = cap * n_public * 32;
+    }
+    HIPCK(hipMemcpyAsync(r.idx, r.h_idx, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, user));
+    hipError_t e = bn254_launch_gather_rows(r.fb_proofs, (const uint8_t*)d_proofs + off * proof_stride, proof_stride, 256, r.idx, cnt, user);
+    if (e == hipSuccess && n_public) e = bn254_launch_gather_rows(r.fb_inputs, (const uint8_t*)d_inputs + off * n_public * 32, n_public * 32, (uint32_t)(n_public * 32), r.idx, cnt, user);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("gather launch: ") + hipGetErrorString(e));
+    rc = g16_enqueue_exact(pvk, d, r.fb_proofs, 256, r.fb_inputs, n_public, cnt, r.fb_status, user, flags);
+    if (rc) return rc;
+    e = bn254_launch_scatter_status((uint8_t*)d_status + off, r.fb_status, r.idx, cnt, user);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("scatter launch: ") + hipGetErrorString(e));
+  }
+  if (seen_checked) {
+    RlcDev& r = d->rlc;
+    const float share = (float)seen_fallback / (float)seen_checked;
+    r.fb_share = r.have_obs ? 0.5f * r.fb_share + 0.5f * share : share;
+    r.have_obs = true;
+  }
+  return BN254_OK;
+}
+// The RLC pass costs about half an exact pass and every proof of a failed group pays the exact pass on top, so the mode loses once about half
+// of the proofs fall back (measured: 0.84 x at 1/16 invalid proofs and groups of 32).  While the recent share is above RLC_BYPASS_SHARE the
+// batch entry points run the exact path directly (same status bytes by construction) and re-measure with an RLC pass every RLC_PROBE_EVERY calls.
+// BN254_RLC_ADAPTIVE=0 switches this off.
+#define RLC_BYPASS_SHARE 0.45f
+#define RLC_PROBE_EVERY 8
+static bool rlc_bypass(RlcDev& r) {
+  const bool adaptive = g_rlc_adaptive.load() != 0;   // bn254_set_rlc_params
+  if (!adaptive || !r.have_obs || r.fb_share <= RLC_BYPASS_SHARE) { r.bypassed = 0; return false; }
+  if (r.bypassed + 1 >= RLC_PROBE_EVERY) { r.bypassed = 0; return false; }
+  r.bypassed++; r.bypassed_total++;
+  return true;
+}
+// does a batch of this shape qualify for the RLC mode at all (the adaptive bypass, rlc_bypass, is decided separately, once per call)
+static bool rlc_eligible(const bn254_g16_pvk* pvk, size_t n_public, size_t n, unsigned flags) {
+  return (flags & BN254_FLAG_RLC) && pvk->host.inputs_match(n_public) && n_public <= (size_t)RLC_MAX_PUBLIC && n >= (size_t)g_rlc_min_batch.load();
+}
+// one batch on `user`: waits for the previous batch of this (key, device), runs the exact or the RLC pipeline, records busy_ev.
+// use_rlc: -1 = decide here; 0 / 1 = the caller (the host-buffer entry, which must know before it cuts the batch into chunks) has decided
+static int g16_enqueue(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
+                       size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags, int use_rlc = -1) {
+  if (d->busy_valid) HIPCK(hipStreamWaitEvent(user, d->busy_ev, 0));
+  int rc;
+  // BN254_FLAG_RLC is honoured where it pays: from RLC_PAYS_FROM proofs (bn254_set_rlc_params / BN254_RLC_MIN_BATCH at load time move the
+  // threshold: the tests run the mode on small batches); smaller batches take the exact path -- same status bytes
+  const bool rlc = use_rlc >= 0 ? use_rlc != 0 : (rlc_eligible(pvk, n_public, n, flags) && !rlc_bypass(d->rlc));
+  if (rlc) rc = g16_enqueue_rlc(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
+  else rc = g16_enqueue_exact(pvk, d, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
+  if (rc) return rc;
+  HIPCK(hipEventRecord(d->busy_ev, user));
+  d->busy_valid = true;
+  return BN254_OK;
+}
+
+extern "C" {
+
+int bn254_groth16_verify_batch_device(const bn254_g16_pvk* pvk, const void* d_proofs, size_t proof_stride, const void* d_inputs,
+                                      size_t n_public, size_t n, void* d_status, int device, void* hip_stream, unsigned flags) {
+  int rc = check_batch_args(false, pvk, d_proofs, proof_stride, d_inputs, n_public, n, d_status, flags);
+  if (rc || n == 0) return rc;
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
+  return g16_enqueue(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, (hipStream_t)hip_stream, flags);
+}
+
+void bn254_set_rlc_params(long min_batch, int adaptive, long share_min_lanes) {
+  if (min_batch >= 0) g_rlc_min_batch.store(min_batch < RLC_MIN_BATCH ? (long)RLC_MIN_BATCH : min_batch);
+  if (adaptive >= 0) g_rlc_adaptive.store(adaptive ? 1 : 0);
+  if (share_min_lanes >= 0) g_rlc_share_min_lanes.store(share_min_lanes < 1 ? 1 : share_min_lanes);
+}
+
+int bn254_groth16_rlc_state(const bn254_g16_pvk* pvk, int device, float* fallback_share, unsigned* bypassed_calls) {
+  if (!pvk) return set_err(BN254_E_BAD_ARG, "bad argument");
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (fallback_share) *fallback_share = d->rlc.have_obs ? d->rlc.fb_share : -1.f;
+  if (bypassed_calls) *bypassed_calls = d->rlc.bypassed_total;
+  return BN254_OK;
+}
+
+const char* bn254_last_diagnostic(void) { return g_diag.c_str(); }
+
+// How the two sub-batch streams of this (key, device) ran on the first batch that used two: sum of their durations / their union (about 2: side by side; about
+// 1: one after the other, i.e. they share a hardware queue -- see GPU_MAX_HW_QUEUES in INTEGRATION.md); -1 while no such batch has been measured.
+int bn254_groth16_stream_overlap(const bn254_g16_pvk* pvk, int device, float* overlap, int* single_stream) {
+  if (!pvk || !overlap) return set_err(BN254_E_BAD_ARG, "bad argument");
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  *overlap = d->ov_ratio;            // -1 until the first measurement has been read
+  if (single_stream) *single_stream = d->single_stream ? 1 : 0;
+  g_diag = d->diag;                  // the explanation belongs to the (key, device); the caller's thread receives it here
+  return BN254_OK;
+}
+
+int bn254_groth16_last_kernel_ms(const bn254_g16_pvk* pvk, int device, float ms[BN254_G16_NUM_KERNELS]) {
+  if (!pvk || !ms) return set_err(BN254_E_BAD_ARG, "bad argument");
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (!d->ev_recorded) return set_err(BN254_E_BAD_ARG, "no profiled batch on this device");
+  HIPCK(hipSetDevice(device));
+  HIPCK(hipEventSynchronize(d->ev[4]));
+  for (int i = 0; i < BN254_G16_NUM_KERNELS; i++) HIPCK(hipEventElapsedTime(&ms[i], d->ev[i], d->ev[i + 1]));
+  return BN254_OK;
+}
+
+int bn254_groth16_kernel_profile(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], size_t* proofs_per_launch) {
+  if (!pvk || !launches || !total_ms) return set_err(BN254_E_BAD_ARG, "bad argument");
+  DevState* dp = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(dp->mu);
+  DevState& d = *dp;
+  if (!d.ev_recorded) return set_err(BN254_E_BAD_ARG, "no profiled batch on this device");
+  HIPCK(hipSetDevice(device));
+  for (int k = 0; k < KID_COUNT; k++) { launches[k] = 0; total_ms[k] = 0.f; }
+  for (int i = 0; i < d.prof.used; i++) {
+    HIPCK(hipEventSynchronize(d.prof.ev[2 * i + 1]));
+    float ms = 0.f;
+    HIPCK(hipEventElapsedTime(&ms, d.prof.ev[2 * i], d.prof.ev[2 * i + 1]));
+    launches[d.prof.kid[i]]++; total_ms[d.prof.kid[i]] += ms;
+  }
+  if (proofs_per_launch) *proofs_per_launch = d.prof_n;
+  return BN254_OK;
+}
+
+// Launches, summed durations AND the union of the launch intervals per kernel kind over the first TWO sub-batches of the last profiled batch (they
+// run on two streams side by side).  union_ms[k] = length of the union of the intervals [start, end] of every launch of kind k, on a common time
+// base (HIP events of both streams against the first sub-batch's first event): for two streams that run the same kernel at the same time it is
+// about one launch's duration, for launches that happen to run one after the other it is the sum -- either way "work of all those launches / union"
+// is the rate the GPU delivered while that kernel kind was running.
+int bn254_groth16_kernel_profile_all(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], float union_ms[], size_t* proofs_per_launch) {
+  if (!pvk || !launches || !total_ms || !union_ms) return set_err(BN254_E_BAD_ARG, "bad argument");
+  DevState* dp = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(dp->mu);
+  DevState& d = *dp;
+  if (!d.ev_recorded || d.prof.used == 0) return set_err(BN254_E_BAD_ARG, "no profiled batch on this device");
+  HIPCK(hipSetDevice(device));
+  std::vector<std::vector<std::pair<float, float>>> iv(KID_COUNT);
+  for (int k = 0; k < KID_COUNT; k++) { launches[k] = 0; total_ms[k] = 0.f; union_ms[k] = 0.f; }
+  const hipEvent_t ref = d.prof.ev[0];
+  const G16Prof* ps[2] = {&d.prof, d.prof2_used ? &d.prof2 : nullptr};
+  for (const G16Prof* p : ps) {
+    if (!p) continue;
+    for (int i = 0; i < p->used; i++) {
+      HIPCK(hipEventSynchronize(p->ev[2 * i + 1]));
+      float a = 0.f, b = 0.f;
+      HIPCK(hipEventElapsedTime(&a, ref, p->ev[2 * i]));
+      HIPCK(hipEventElapsedTime(&b, ref, p->ev[2 * i + 1]));
+      launches[p->kid[i]]++; total_ms[p->kid[i]] += b - a;
+      iv[p->kid[i]].push_back({a, b});
+    }
+  }
+  for (int k = 0; k < KID_COUNT; k++) {
+    auto& v = iv[k];
+    std::sort(v.begin(), v.end());
+    float cur_lo = 0.f, cur_hi = 0.f; bool open = false;
+    for (auto& x : v) {
+      if (!open) { cur_lo = x.first; cur_hi = x.second; open = true; }
+      else if (x.first <= cur_hi) { if (x.second > cur_hi) cur_hi = x.second; }
+      else { union_ms[k] += cur_hi - cur_lo; cur_lo = x.first; cur_hi = x.second; }
+    }
+    if (open) union_ms[k] += cur_hi - cur_lo;
+  }
+  if (proofs_per_launch) *proofs_per_launch = d.prof_n;
+  return BN254_OK;
+}
+
+// Host buffers.  The caller's memory is pageable, and a hipMemcpyAsync from pageable memory is neither asynchronous nor fast (the runtime stages
+// it through its own bounce buffer while the calling thread waits).  So the library keeps a ring of three PINNED pieces per (key, device): host
+// threads copy piece i + 1 of the caller's buffers into the ring while piece i travels to the device (a true asynchronous copy on the copy
+// stream) and the previous compute chunk runs; a compute chunk (2^17 proofs first, so that the exposed copy is short, then 2^18) waits on the
+// GPU for the event of its last piece.  Only stream-scoped synchronisation, one status copy at the end.  The device lock is held for the whole
+// call: the staging buffers belong to this batch until its statuses are back.
+#define HOST_RING 3
+static int host_ring_ensure(DevState& d, size_t piece_bytes) {
+  if (piece_bytes <= d.pin_cap) return BN254_OK;
+  for (int i = 0; i < HOST_RING; i++) {
+    if (d.pin[i]) HIPCK(hipHostFree(d.pin[i]));
+    d.pin[i] = nullptr;
+  }
+  d.pin_cap = 0;
+  for (int i = 0; i < HOST_RING; i++) {
+    HIPCK(hipHostMalloc((void**)&d.pin[i], piece_bytes, hipHostMallocDefault));
+    if (!d.pin_ev[i]) HIPCK(hipEventCreateWithFlags(&d.pin_ev[i], hipEventDisableTiming));
+  }
+  d.pin_cap = piece_bytes;
+  return BN254_OK;
+}
+int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                               size_t n_public, size_t n, uint8_t* status, int device, unsigned flags) {
+  int rc = check_batch_args(false, pvk, proofs, proof_stride, public_inputs, n_public, n, status, flags);
+  if (rc || n == 0) return rc;
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
+  const size_t in_row = n_public * 32, row = proof_stride + in_row;
+  size_t pb = n * proof_stride, ib = n * in_row;
+  if ((rc = grow(&d->st_proofs, &d->st_proofs_cap, pb)) || (rc = grow(&d->st_inputs, &d->st_inputs_cap, ib ? ib : 32)) ||
+      (rc = grow(&d->st_status, &d->st_status_cap, n)))
+    return rc;
+  if (!d->host_stream) { HIPCK(hipStreamCreateWithFlags(&d->host_stream, hipStreamNonBlocking)); HIPCK(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking)); }
+  // compute chunks: a short first one (its copy is the only exposed one: 2^17 proofs = 42 MB, under a millisecond of DMA), then the rest in chunks
+  // as large as the workspace allows -- every chunk boundary drains both sub-batch streams, so fewer chunks is faster
+  static const size_t first_chunk = [] { const char* e = getenv("BN254_HOST_FIRST_CHUNK_LOG2"); int v = e ? atoi(e) : 17; if (v < 12) v = 12; if (v > 20) v = 20; return (size_t)1 << v; }();
+  const size_t hchunk = (size_t)G16_MAX_BATCH - first_chunk;
+  // copy pieces: about 20 MB of the caller's bytes each (65536 proofs at 2 public inputs), a multiple of 256 proofs
+  static const size_t piece_bytes_target = [] { const char* e = getenv("BN254_HOST_PIECE_MB"); long v = e ? atol(e) : 20; return (size_t)(v < 1 ? 1 : v) << 20; }();
+  size_t piece = piece_bytes_target / row / 256 * 256;
+  if (piece < 256) piece = 256;
+  if (piece > n) piece = (n + 255) / 256 * 256;
+  if ((rc = host_ring_ensure(*d, piece * row))) return rc;
+  // the RLC mode forms its groups over the whole batch it is handed: keep it in one piece -- but only when this call really runs the mode
+  // (same predicate as g16_enqueue, the adaptive bypass included, decided ONCE here); a flag that will be ignored keeps the chunked
+  // copy / compute overlap
+  const int use_rlc = (rlc_eligible(pvk, n_public, n, flags) && !rlc_bypass(d->rlc)) ? 1 : 0;
+  static const bool timing = getenv("BN254_HOST_TIMING") != nullptr;   // diagnostics on stderr: where the host thread spends the call
+  auto now = [] { return std::chrono::steady_clock::now(); };
+  auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+  double t_copy = 0, t_wait = 0, t_enq = 0;
+  const auto t_begin = now();
+  size_t copied = 0, computed = 0, slot_uses = 0;
+  // the first chunk is short (its copy is the only exposed one) unless the batch is small anyway
+  size_t c_end = (use_rlc || n < 2 * first_chunk) ? n : first_chunk;
+  while (computed < n) {
+    hipEvent_t last = nullptr;
+    while (copied < c_end) {
+      const size_t m = c_end - copied < piece ? c_end - copied : piece;
+      const int slot = (int)(slot_uses % HOST_RING);
+      auto ta = now();
+      if (slot_uses >= HOST_RING) HIPCK(hipEventSynchronize(d->pin_ev[slot]));     // the piece that used this slot has left for the device
+      auto tb = now();
+      parallel_copy(d->pin[slot], proofs + copied * proof_stride, m * proof_stride);
+      if (in_row) parallel_copy(d->pin[slot] + m * proof_stride, public_inputs + copied * in_row, m * in_row);
+      auto tc = now();
+      t_wait += ms(ta, tb); t_copy += ms(tb, tc);
+      HIPCK(hipMemcpyAsync(d->st_proofs + copied * proof_stride, d->pin[slot], m * proof_stride, hipMemcpyHostToDevice, d->copy_stream));
+      if (in_row) HIPCK(hipMemcpyAsync(d->st_inputs + copied * in_row, d->pin[slot] + m * proof_stride, m * in_row, hipMemcpyHostToDevice, d->copy_stream));
+      HIPCK(hipEventRecord(d->pin_ev[slot], d->copy_stream));
+      last = d->pin_ev[slot];
+      slot_uses++; copied += m;
+    }
+    if (last) HIPCK(hipStreamWaitEvent(d->host_stream, last, 0));
+    auto td = now();
+    rc = g16_enqueue(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, d->st_inputs + computed * in_row, n_public, c_end - computed,
+                     d->st_status + computed, d->host_stream, flags, use_rlc);
+    if (rc) {   // pieces of the pinned ring and earlier chunks may still be in flight: the ring and the staging buffers must be quiescent when the lock is released
+      const std::string keep = g_err;
+      (void)hipStreamSynchronize(d->copy_stream); (void)hipStreamSynchronize(d->host_stream);
+      g_err = keep;
+      return rc;
+    }
+    t_enq += ms(td, now());
+    computed = c_end;
+    c_end = n - c_end < hchunk ? n : c_end + hchunk;
+  }
+  const auto t_enqueued = now();
+  HIPCK(hipMemcpyAsync(status, d->st_status, n, hipMemcpyDeviceToHost, d->host_stream));
+  HIPCK(hipStreamSynchronize(d->host_stream));
+  if (timing) fprintf(stderr, "host-buffer batch %zu: pieces of %zu proofs; host copies %.2f ms, ring waits %.2f ms, kernel enqueue %.2f ms, all enqueued after %.2f ms, done after %.2f ms\n",
+                      n, piece, t_copy, t_wait, t_enq, ms(t_begin, t_enqueued), ms(t_begin, now()));
+  return BN254_OK;
+}
+
+int bn254_groth16_verify_batch_multi(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                                     size_t n_public, size_t n, uint8_t* status, uint64_t device_mask, unsigned flags) {
+  int prc = check_batch_args(false, pvk, proofs, proof_stride, public_inputs, n_public, n, status, flags);
+  if (prc) return prc;
+  if (!device_mask) return set_err(BN254_E_BAD_ARG, "bad argument");
+  int cnt = 0;
+  if (hipGetDeviceCount(&cnt) != hipSuccess || cnt <= 0) return set_err(BN254_E_NO_DEVICE, "no HIP device available (this library has no CPU fallback)");
+  int devs[64], nsh = 0; size_t los[64], cnts[64];
+  if ((prc = bn254_shard_plan(n, device_mask, cnt, devs, los, cnts, &nsh))) return prc;
+  const size_t w = (size_t)nsh;
+  if (w == 1) return bn254_groth16_verify_batch(pvk, proofs, proof_stride, public_inputs, n_public, n, status, devs[0], flags);
+  // one host thread per device drives its shard
+  std::vector<int> rcs(w, BN254_OK); std::vector<std::string> errs(w);
+  std::vector<std::thread> th;
+  for (size_t r = 0; r < w; r++) {
+    const size_t lo = los[r], cntp = cnts[r];
+    th.emplace_back([&, r, lo, cntp]() {
+      if (!cntp) return;
+      rcs[r] = bn254_groth16_verify_batch(pvk, proofs + lo * proof_stride, proof_stride, public_inputs ? public_inputs + lo * n_public * 32 : nullptr, n_public, cntp,
+                                          status + lo, devs[r], flags);
+      if (rcs[r]) errs[r] = g_err;   // thread-local in the worker
+    });
+  }
+  for (auto& t : th) t.join();
+  for (size_t r = 0; r < w; r++) if (rcs[r]) return set_err(rcs[r], "device " + std::to_string(devs[r]) + ": " + errs[r]);
+  return BN254_OK;
+}
+
+// load_groth16_proof_from_bytes (groth16/converter.rs:14-26) on the host, for the one case in which no kernel can run: a single proof against key bytes that do not
+// load.  A, B, C in this order; per point: every coordinate < p (Field(NotMember)), the curve equation (Group(NotOnCurve)), and for B the r-torsion (Group(NotInSubgroup)).
+static uint8_t g16_proof_loader_status(const uint8_t* p /* 256 bytes */) {
+  auto g1 = [](const uint8_t* b) -> uint8_t {
+    if (!be_lt_p(b) || !be_lt_p(b + 32)) return BN254_ERR_NOT_MEMBER;
+    G1Aff a; a.x = fp_from_be(b); a.y = fp_from_be(b + 32);
+    return g1_on_curve(a) ? BN254_ACCEPT : BN254_ERR_NOT_ON_CURVE;
+  };
+  uint8_t st = g1(p);
+  if (st != BN254_ACCEPT) return st;
+  for (int i = 0; i < 4; i++) if (!be_lt_p(p + 64 + 32 * i)) return BN254_ERR_NOT_MEMBER;
+  G2Aff b; b.x.c1 = fp_from_be(p + 64); b.x.c0 = fp_from_be(p + 96); b.y.c1 = fp_from_be(p + 128); b.y.c0 = fp_from_be(p + 160);
+  if (!g2_on_curve(b)) return BN254_ERR_NOT_ON_CURVE;
+  if (!g2_in_subgroup(b)) return BN254_ERR_NOT_IN_SUBGROUP;
+  return g1(p + 192);
+}
+int bn254_groth16_verify(const uint8_t* proof, size_t proof_len, const uint8_t* vk, size_t vk_len, const uint8_t* public_inputs,
+                         size_t n_public, unsigned mode, uint8_t* status) {
+  if (!proof || !vk || !status || mode > 1) return set_err(BN254_E_BAD_ARG, "bad argument");
+  // reference order: the proof is loaded (and its errors surface) before the key (lib.rs:45-46).  A short proof buffer is a
+  // slice-index panic there.
+  if (proof_len < 256) { *status = BN254_ERR_MALFORMED; return BN254_OK; }
+  // the reference parses the key on every call (lib.rs:46); here the prepared form of the last few keys is kept (exact byte match), so a
+  // caller that verifies one proof at a time against the same key pays the preparation (9 ms of an 11 ms call) once
+  std::shared_ptr<bn254_g16_pvk> pvk = g16_key_cache().find(vk, vk_len, mode);
+  if (!pvk) {
+    bn254_g16_pvk* raw = nullptr;
+    int rc = bn254_groth16_vk_prepare(vk, vk_len, mode, &raw);
+    if (rc == BN254_E_VK) {
+      // the key does not load (lib.rs:46 panics) -- but the proof was loaded first (lib.rs:45), so its loader error wins.  Nothing can be launched without a key: the
+      // loader's checks (< p, curve equation, r-torsion of B; groth16/converter.rs:14-26) run here on the host, once, for this one proof
+      const uint8_t ps = g16_proof_loader_status(proof);
+      *status = ps == BN254_ACCEPT ? (uint8_t)BN254_ERR_MALFORMED : ps;
+      return BN254_OK;
+    }
+    if (rc) return rc;
+    pvk = g16_key_cache().insert(vk, vk_len, mode, raw);
+  }
+  return bn254_groth16_verify_batch(pvk.get(), proof, proof_len, public_inputs, n_public, 1, status, 0, 0);
+}
+
+int bn254_groth16_proof_write_raw(const uint8_t a[64], const uint8_t b[128], const uint8_t c[64], uint8_t out[BN254_GROTH16_RAW_PROOF_LEN]) {
+  if (!a || !b || !c || !out) return set_err(BN254_E_BAD_ARG, "bad argument");
+  memcpy(out, a, 64); memcpy(out + 64, b, 128); memcpy(out + 192, c, 64);
+  memset(out + 256, 0, BN254_GROTH16_RAW_PROOF_LEN - 256);   // u32 nbCommitments = 0, then the 64-byte commitment PoK (zero)
+  return BN254_OK;
+}
+
+}  // extern "C"

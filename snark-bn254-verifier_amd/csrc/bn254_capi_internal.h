@@ -1,0 +1,239 @@
+// bn254_capi_internal.h -- what the translation units of the C ABI (bn254_capi*.hip) share: the per (key, device) state of both protocols, the key
+// cache of the single-proof entries, and the helpers more than one of them calls.  Private: nothing outside csrc/ includes it.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <cstdlib>
+#include <dlfcn.h>
+#include <algorithm>
+#include <map>
+#include <mutex>
+#include <string>
+#include <vector>
+#include "../../include/bn254_verify.h"
+#include "bn254_host.hpp"
+#include "bn254_plonk.hpp"
+#include "bn254_rlc.h"
+#include "bn254_g16_plan.h"
+#include <sys/random.h>
+#include <atomic>
+#include <thread>
+#include <condition_variable>
+#include <deque>
+#include <functional>
+#include <memory>
+#include <chrono>
+#include <cstdio>
+#include <stdexcept>
+
+using namespace bn254host;
+
+// bn254_k_plonk.hip: the PlonK host stages as device kernels (the same bn254_plonk.hpp source, one proof per lane)
+size_t bn254_plonk_work_bytes();
+size_t bn254_plonk_key_bytes();
+hipError_t bn254_plonk_dev_init(int device);
+hipError_t bn254_plonk_self_test(const void* key_host, const void* d_key, std::string* why);
+hipError_t bn254_launch_plonk_stage1(const void* d_key, const uint8_t* d_proofs, size_t stride, const uint8_t* d_inputs, size_t n_public, size_t n, const uint32_t lam_key[11],
+                                     void* d_work, void* d_terms, uint8_t* d_flags, int T1, hipStream_t s);
+hipError_t bn254_launch_plonk_stage2(const void* d_key, const uint8_t* d_proofs, size_t stride, size_t n, void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf,
+                                     void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2, const uint32_t* weight_key, hipStream_t s);
+hipError_t bn254_launch_plonk_group_sums(int32_t* ws, const uint8_t* status, size_t n, int32_t* grp_ws, uint8_t* grp_status, int e_p0, int inf0, int e_p1, int inf1, hipStream_t s);
+hipError_t bn254_launch_plonk_group_scatter(uint8_t* status, size_t n, const uint8_t* grp_status, uint32_t* n_failed, hipStream_t s);
+
+hipError_t bn254_launch_plonk_dbg_zeta(const void* d_work, size_t n, uint8_t* d_zeta, uint8_t* d_status, hipStream_t s);
+
+#define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_err(BN254_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+
+// Initial values of the knobs come from the environment, read ONCE when the library is loaded (getenv racing a host's setenv is undefined behaviour).
+static inline long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
+
+// BN254_FLAG_RLC: per (key, device) buffers of the random-linear-combination batch mode (bn254_rlc.h)
+struct RlcDev {
+  bool ready = false;
+  int32_t *btab = nullptr, *tab = nullptr, *one = nullptr;            // key-side tables (uploaded once)
+  uint8_t* grp_status = nullptr; size_t grp_cap = 0;
+  uint32_t* idx = nullptr; size_t idx_cap = 0;
+  uint8_t *fb_proofs = nullptr, *fb_inputs = nullptr, *fb_status = nullptr; size_t fb_cap = 0, fb_in_cap = 0;
+  uint8_t* h_status = nullptr; uint32_t* h_idx = nullptr; size_t h_cap = 0;   // pinned
+  // adaptive use of the mode: share of the checked proofs the last RLC passes sent to the exact fallback (exponential average) and how many
+  // calls have bypassed the mode since the last pass that measured it
+  bool have_obs = false; float fb_share = 0.f; unsigned bypassed = 0, bypassed_total = 0;
+};
+
+
+// Per (key, device) state.  `mu` serialises everything that touches it: uploads, (re)allocation and the enqueue of a batch.  The
+// workspace and the staging buffers are shared by all batches against this key on this device, so a batch first waits (on the GPU:
+// hipStreamWaitEvent) for `busy_ev`, the completion event of the previous batch, whatever stream that one ran on.
+struct DevState {
+  std::mutex mu;
+  bool ready = false;
+  int32_t *k0 = nullptr, *gtab = nullptr, *dtab = nullptr, *target = nullptr, *msm = nullptr;
+  int32_t* ws = nullptr; size_t ws_cap = 0;                         // proofs the workspace can hold
+  int32_t* msm_part = nullptr; size_t msm_part_cap = 0, msm_chunks = 0;             // wide keys: partial sums of the public-input MSM (proofs it holds)
+  uint8_t *st_proofs = nullptr, *st_inputs = nullptr, *st_status = nullptr;  // staging for the host-buffer entry point
+  size_t st_proofs_cap = 0, st_inputs_cap = 0, st_status_cap = 0;
+  hipStream_t host_stream = nullptr, copy_stream = nullptr;   // host-buffer entry: copy / compute overlap
+  uint8_t* pin[3] = {nullptr, nullptr, nullptr}; size_t pin_cap = 0; hipEvent_t pin_ev[3] = {nullptr, nullptr, nullptr};   // ring of pinned pieces (HOST_RING)
+  hipEvent_t busy_ev = nullptr; bool busy_valid = false;
+  hipEvent_t ev[5]; bool ev_ready = false; bool ev_recorded = false;
+  // concurrent sub-batches (see g16_enqueue_exact): part 0 runs on the caller's stream, parts 1..3 on these, created when first needed -- every
+  // stream of a process shares the runtime's few hardware queues (four by default), and a copy stream that lands on the queue of a busy compute
+  // stream waits behind its kernels (measured: 3 GB/s instead of 55), so no stream is created that is not used
+  hipStream_t aux[3] = {nullptr, nullptr, nullptr}; int aux_count = 0; hipEvent_t fork_ev = nullptr, join_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // per-launch timing of the first sub-batch (bn254_groth16_kernel_profile)
+  std::vector<hipEvent_t> prof_ev; std::vector<uint8_t> prof_kid; G16Prof prof{0, nullptr, nullptr, 0, 0}; size_t prof_n = 0; unsigned prof_epoch = 0;
+  // the same for the SECOND sub-batch (its launches run on another stream beside the first's): bn254_groth16_kernel_profile_all
+  std::vector<hipEvent_t> prof2_ev; std::vector<uint8_t> prof2_kid; G16Prof prof2{0, nullptr, nullptr, 0, 0}; bool prof2_used = false;
+  RlcDev rlc;                                                       // BN254_FLAG_RLC buffers (bn254_rlc.hpp)
+  // do the sub-batch streams overlap?  ov_ev: start / end of part 0 and of part 1 of the first two-stream batch; ov_state 0: not measured, 1: events recorded,
+  // 2: measured (ov_ratio = sum of the two durations / their union: ~2 side by side, ~1 one after the other); single_stream: fall back to one sub-batch per launch
+  hipEvent_t ov_ev[4] = {nullptr, nullptr, nullptr, nullptr}; int ov_state = 0; float ov_ratio = -1.f; bool single_stream = false;
+  // the decision is not taken from one measurement (another tenant's kernels, a profiler that serialises dispatches): OV_AGREE consecutive measurements must say
+  // "serialised" before the plan changes, a measurement that says "side by side" resets the count; once on one sub-batch per launch, every OV_REPROBE-th batch runs two
+  // again and is measured, so that a transient cause does not pin the key to the slower plan for its lifetime.  `diag`: the explanation, per (key, device), handed out by
+  // bn254_groth16_stream_overlap through bn254_last_diagnostic() of the calling thread
+  int ov_serial_votes = 0; unsigned ov_batches = 0; bool ov_probe = false; std::string diag;
+};
+struct bn254_g16_pvk {
+  G16Prepared host;
+  mutable G16PreparedRlc rlc_host;       // built on the first BN254_FLAG_RLC batch (under mu)
+  mutable std::mutex mu;                 // protects the map below (lookup / insertion only) and rlc_host
+  mutable std::map<int, DevState> dev;
+};
+
+// ---------------------------------------------------------------- PlonK (BASELINE configs[3])
+// One PlonkCtx = one sub-batch in flight: its own stream, device buffers and pinned host staging.  A batch is cut into sub-batches that worker
+// threads drive concurrently, so the host work of one sub-batch (staging copies, status read-back) overlaps the GPU stages of the others; every
+// wait is stream-scoped.
+#define PLONK_WORKERS 8
+// proofs per pass at most.  Until round 4 this was 65 536 -- one wavefront per SIMD for every one-lane-per-proof kernel of a pass, which left the pairing stage of the
+// largest passes at 0.39 of the multiply-add peak; a pass of 2^18 proofs gives the same kernels four (the context's buffers for it: 5.4 GB at the SP1 key shape)
+#define PLONK_MAX_LAUNCH 262144
+struct PlonkCtx {
+  size_t cap = 0;                      // proofs the buffers below hold
+  hipStream_t stream = nullptr, aux = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  hipEvent_t tk[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // timing: before stage 1 | after it | MSM rows | sum | stage 2 | MSM rows | sums | pairing check
+  float last_ms[BN254_PLONK_NUM_TIMINGS] = {0}; size_t last_lanes[2] = {0, 0}; bool last_valid = false;
+  int32_t *ws = nullptr, *part = nullptr, *glv_tab = nullptr;   // part: the rows of an MSM launch (bn254_msm.h); glv_tab: the window tables of its variable rows
+  size_t part_points = 0;              // projective points (rows x items) `part` holds (plonk_part_points of the capacity)
+  size_t glv_lanes = 0;                // lanes glv_tab holds (plonk_scratch_lanes of the capacity); a launch checks its need against it before it is enqueued
+  MsmTerm* terms = nullptr; uint8_t* flags = nullptr; uint32_t* words = nullptr; uint8_t *inf = nullptr, *status = nullptr;
+  uint8_t* h_status = nullptr;         // pinned: the status bytes of a pass on their way back
+  // device-side stages (bn254_k_plonk.hip): the batch's proofs and inputs in device memory (through a pinned copy), per-proof state between the stages
+  uint8_t *d_in = nullptr, *h_in = nullptr; size_t in_cap = 0; void* d_work = nullptr;
+  // BN254_FLAG_RLC: the pairing checks of a pass batched over groups of 64 proofs -- the groups' points and status bytes in a workspace of their own, failed groups counted
+  int32_t* grp_ws = nullptr; uint8_t* grp_status = nullptr; uint32_t* d_fail = nullptr; uint32_t* h_fail = nullptr;
+};
+struct PlonkDev {
+  bool ready = false;
+  int32_t *tab0 = nullptr, *tab1 = nullptr, *one = nullptr;
+  int32_t* fixed_tabs = nullptr;       // window tables of the key's G1 points (plonk_num_tables x MSM_FW_WINDOWS x MSM_FW_ENTRIES entries, bn254_fw.h)
+  void* d_key = nullptr;               // the parsed key (PlonkKey) for the device-side stages
+  PlonkCtx ctx[PLONK_WORKERS];
+  // The contexts are handed out to calls: a call takes one per sub-batch (all at once, so two calls cannot wait for each other) and returns them when it
+  // is done.  Calls on ONE prepared key from several host threads therefore run side by side, up to PLONK_WORKERS sub-batches in flight; at 4096 proofs a
+  // batch is a chain of latency-bound launches that leaves most of the GPU idle, and two batches in flight verify 1.35 x as many proofs per second.
+  std::mutex pool_mu; std::condition_variable pool_cv; bool busy[PLONK_WORKERS] = {};
+  float last_ms[BN254_PLONK_NUM_TIMINGS] = {0}; size_t last_lanes[2] = {0, 0}; bool last_valid = false;   // first sub-batch of the call that finished last
+};
+struct PlonkLease {   // the contexts of one call
+  PlonkDev* d; int idx[PLONK_WORKERS]; int n = 0;
+  PlonkLease(PlonkDev* d_, int want) : d(d_) {
+    std::unique_lock<std::mutex> lk(d->pool_mu);
+    d->pool_cv.wait(lk, [&] { int f = 0; for (bool b : d->busy) f += b ? 0 : 1; return f >= want; });
+    for (int i = 0; i < PLONK_WORKERS && n < want; i++) if (!d->busy[i]) { d->busy[i] = true; idx[n++] = i; }
+  }
+  PlonkCtx& ctx(int w) const { return d->ctx[idx[w]]; }
+  ~PlonkLease() {
+    {
+      std::lock_guard<std::mutex> lk(d->pool_mu);
+      const PlonkCtx& c = d->ctx[idx[0]];
+      if (c.last_valid) { for (int i = 0; i < BN254_PLONK_NUM_TIMINGS; i++) d->last_ms[i] = c.last_ms[i]; d->last_lanes[0] = c.last_lanes[0]; d->last_lanes[1] = c.last_lanes[1]; d->last_valid = true; }
+      for (int i = 0; i < n; i++) d->busy[idx[i]] = false;
+    }
+    d->pool_cv.notify_all();
+  }
+  PlonkLease(const PlonkLease&) = delete; PlonkLease& operator=(const PlonkLease&) = delete;
+};
+struct bn254_plonk_pvk {
+  PlonkKey key;
+  std::vector<int32_t> tab0, tab1, one;
+  std::vector<int32_t> fixed_pts;      // every key point that enters an MSM (bn254_plonk.hpp::plonk_table_point) as affine digits, 18 dwords each: their window tables
+                                       // (MSM_FW_BITS, bn254_fw.h) are built on the device that uses them (bn254_k_comb.hip form 2)
+  MsmShape shape1, shape2, shape2_rlc; // term kinds of the two MSM launches (plonk_msm1_shape / plonk_msm2_shape; _rlc: the weighted form of BN254_FLAG_RLC)
+  mutable std::mutex mu;               // protects the map below (lookup / insertion / first upload); batches take contexts from the device's pool
+  mutable std::map<int, PlonkDev> dev;
+};
+
+// ---- prepared keys of the single-proof entry points (bn254_groth16_verify, bn254_plonk_verify): the last KEY_CACHE_SLOTS keys by exact bytes.
+// Entries are shared_ptrs: an evicted key is freed when its last in-flight call returns.  The cache object itself is never destroyed (keys hold
+// device memory; freeing it from a static destructor would race the HIP runtime's own teardown).  BN254_KEY_CACHE=0 switches it off, BN254_KEY_CACHE=N (1 .. 64) sets the
+// number of keys kept (a caller that rotates through more keys than slots pays the preparation, ~9 ms of an 11 ms call, on every miss).
+#define KEY_CACHE_SLOTS 4
+#define KEY_CACHE_MAX_SLOTS 64
+template <class T, void (*FREE)(T*)>
+class KeyCache {
+ public:
+  std::shared_ptr<T> find(const uint8_t* vk, size_t len, unsigned mode) {
+    if (!slots()) return nullptr;
+    std::lock_guard<std::mutex> lk(mu_);
+    for (auto& e : e_)
+      if (e.h && e.mode == mode && e.bytes.size() == len && memcmp(e.bytes.data(), vk, len) == 0) { e.tick = ++clock_; return e.h; }
+    return nullptr;
+  }
+  static int capacity() { return slots(); }
+  std::shared_ptr<T> insert(const uint8_t* vk, size_t len, unsigned mode, T* raw) {
+    std::shared_ptr<T> h(raw, [](T* p) { FREE(p); });
+    if (!slots()) return h;
+    std::lock_guard<std::mutex> lk(mu_);
+    Entry* v = &e_[0];
+    for (auto& e : e_) { if (!e.h) { v = &e; break; } if (e.tick < v->tick) v = &e; }
+    v->bytes.assign(vk, vk + len); v->mode = mode; v->h = h; v->tick = ++clock_;
+    return h;
+  }
+
+ private:
+  // unset: KEY_CACHE_SLOTS; 0: off; N: N slots (at most KEY_CACHE_MAX_SLOTS)
+  static int slots() { static const int n = [] { const char* e = getenv("BN254_KEY_CACHE"); long v = e ? atol(e) : KEY_CACHE_SLOTS; return (int)(v < 0 ? 0 : (v > KEY_CACHE_MAX_SLOTS ? KEY_CACHE_MAX_SLOTS : v)); }(); return n; }
+  struct Entry { std::vector<uint8_t> bytes; unsigned mode = 0; std::shared_ptr<T> h; uint64_t tick = 0; };
+  std::mutex mu_; std::vector<Entry> e_ = std::vector<Entry>((size_t)(slots() > 0 ? slots() : 1)); uint64_t clock_ = 0;
+};
+
+// Shared helpers (internal linkage across the bn254_capi*.hip objects only: none of them is part of the exported ABI)
+#pragma GCC visibility push(hidden)
+extern thread_local std::string g_err;     // bn254_last_error() of the calling thread
+int set_err(int code, const std::string& msg);
+int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* inputs, size_t n_public, size_t n, const void* status,
+                     unsigned flags);
+int check_device(int device);
+void parallel_copy(uint8_t* dst, const uint8_t* src, size_t bytes);
+int build_tables_on_device(int form, const std::vector<int32_t>& pts, int32_t** dst);
+// bn254_capi_g16.hip
+DevState* dev_state(const bn254_g16_pvk* pvk, int device);
+int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n);
+// bn254_capi_plonk.hip
+int plonk_ensure_dev(const bn254_plonk_pvk* pvk, int device, PlonkDev** out);
+int plonk_ensure_ctx(const bn254_plonk_pvk* pvk, PlonkCtx& c, size_t n, size_t in_bytes);
+int plonk_joint_g(size_t m_pad);
+size_t msm_lane_budget();
+size_t plonk_scratch_lanes(size_t need, int n_var);
+size_t plonk_part_points(size_t need, const MsmShape& shape);
+void plonk_plan(size_t n, size_t piece, int max_workers, int* workers, size_t* per, size_t* pass);
+#pragma GCC visibility pop
+
+// *dst stays null unless the copy is complete: a caller that retries after a failure uploads exactly what is still missing (a sanitizer run of the
+// allocation-failure paths found the retry overwriting -- leaking -- the tables an earlier, partly failed attempt had already uploaded)
+template <typename T> static int upload(T** dst, const std::vector<T>& src) {
+  if (*dst) return BN254_OK;
+  size_t bytes = (src.size() ? src.size() : 1) * sizeof(T);
+  T* p = nullptr;
+  HIPCK(hipMalloc((void**)&p, bytes));
+  if (!src.empty()) {
+    hipError_t e = hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(p); return set_err(BN254_E_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+  }
+  *dst = p;
+  return BN254_OK;
+}
+
+// the table form of a Groth16 key (build_tables_on_device: 0 comb tables, 1 byte windows, 2 windows of MSM_FW_BITS)
+static inline int g16_table_form(const G16Prepared& h) { return h.msm_comb ? 0 : h.key_inputs() > (size_t)G16_WIDE_MSM_MIN_INPUTS ? 1 : 2; }

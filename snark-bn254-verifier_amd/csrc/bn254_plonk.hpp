@@ -6,8 +6,8 @@
 //   per proof, DEVICE     everything: parsing, the Fiat-Shamir transcripts (SHA-256), BSB22 hash-to-field, the Fr arithmetic of the linearisation and the GLV
 //                         decomposition (PlonkStage1 / PlonkStage2 below, one proof per lane in csrc/bn254_k_plonk.hip), then every group operation: the two
 //                         multi-scalar multiplications as rows (bn254_msm.h, k_g1_msm_rows) and the two-pair pairing check (bn254_kernels.hip / bn254_coop12.hip)
-// The same stage code compiles for the host: the library runs it there only under BN254_PLONK_HOST=1 (a debugging aid) and the sanitizer harness of
-// tests/hostsan does.  The second transcript hashes the first MSM's result, so a pass is stage 1 -> MSM -> stage 2 -> MSM -> pairing, all on one stream.
+// The same stage code compiles for the host: the library's known-answer self-test of the device stages, the BN254_PLONK_MARKS dumps, tools/repro and the
+// sanitizer harness of tests/hostsan run it there.  The second transcript hashes the first MSM's result, so a pass is stage 1 -> MSM -> stage 2 -> MSM -> pairing, all on one stream.
 // Nothing here is shared with oracle/: this is product code.
 #pragma once
 #include <cstring>
@@ -806,8 +806,8 @@ inline void plonk_msm2_shape(const PlonkKey& vk, MsmShape& sh, bool joint = fals
 // Stage 1 (plonk/verify.rs:46-284): everything up to the scalars of the linearised polynomial digest.  On a failed check the
 // proof's final status is returned and its terms are left zeroed.
 // The stage has ONE field inversion (of the product of its denominators, Montgomery's trick), which is a third of its host time; it is
-// therefore written in two halves around it -- a() up to the product `acc`, b(1 / acc) from there -- so that a batch can invert the
-// products of many proofs with a single inversion (bn254_capi.hip::plonk_run); plonk_stage1() below runs both halves for one proof.
+// therefore written in two halves around it -- a() up to the product `acc`, b(1 / acc) from there -- so that a caller can invert the
+// products of many proofs with a single inversion; plonk_stage1() below runs both halves for one proof.
 struct PlonkStage1 {
 #if defined(__HIP_DEVICE_COMPILE__)
   enum { MAXIN = 8 };    // a lane keeps the stage's arrays in its private memory: the batched inversion covers 8 public inputs, further ones invert singly

@@ -1,5 +1,5 @@
 // tests/hostsan/hip/hip_runtime.h -- TEST HARNESS: a stand-in for the HIP runtime API backed by host memory, so that the HOST half of the product
-// (snark-bn254-verifier_amd/csrc/bn254_capi.hip: parsers, key preparation, plans, the pinned ring of the host-buffer entry, context pools, host thread pool)
+// (snark-bn254-verifier_amd/csrc/bn254_capi*.hip: parsers, key preparation, plans, the pinned ring of the host-buffer entry, context pools, host thread pool)
 // compiles with g++ and runs under AddressSanitizer / UBSan in this GPU-less container (tests/hostsan/hostsan_main.cpp, tests/test_hostsan.py).  "Device" memory is
 // malloc'ed, copies are memcpy, streams run in order at call time (every enqueue completes before it returns), events are time stamps.  Not part of the product.
 #pragma once

@@ -256,14 +256,20 @@ def test_comb_table_constants_never_vanish():
     assert all(sum(((idx >> i) & 1) << (cols * i) for i in range(teeth)) % R for idx in range(1, 1 << teeth))
 
 
-def test_no_constant_kzg_batching_scalar_in_the_product():
-    """The PlonK path keys its batching scalars with getrandom(2) on every call (a ChaCha20 key and nonce, expanded per proof); no literal
+def test_kzg_batching_scalar_keyed_per_call_and_expanded_on_the_device():
+    """The PlonK path keys its batching scalars with getrandom(2) on every call (a ChaCha20 key and nonce, expanded per proof by k_plonk_stage1); no literal
     scalar may come back."""
     import re
-    src = open(os.path.join(ROOT, "snark-bn254-verifier_amd", "csrc", "bn254_capi.hip")).read()
-    body = src[src.index("static int plonk_run("):src.index("int bn254_plonk_verify(const uint8_t* proof")]
-    assert "getrandom(seed" in body and "chacha20_block4(lw" in body and "from_be_reduce((const uint8_t*)lw, 48)" in body
-    assert not re.search(r"lambda\s*=\s*fr_ctx\(\)\.from_u64", src)
+    csrc = os.path.join(ROOT, "snark-bn254-verifier_amd", "csrc")
+    src = open(os.path.join(csrc, "bn254_capi_plonk.hip")).read()
+    body = src[src.index("static int plonk_run_device("):src.index("int bn254_plonk_last_timing(")]
+    assert "getrandom((uint8_t*)lam_key" in body and "bn254_launch_plonk_stage1(" in body
+    kern = open(os.path.join(csrc, "bn254_k_plonk.hip")).read()
+    stage1 = kern[kern.index("k_plonk_stage1(const PlonkKey*"):kern.index("hipError_t bn254_launch_plonk_stage1(")]
+    assert "chacha20_block4(lw" in stage1 and "from_be_reduce(lb, 48)" in stage1
+    for f in os.listdir(csrc):
+        if f.endswith((".h", ".hpp", ".hip")):
+            assert not re.search(r"lambda\s*=\s*fr_ctx\(\)\.from_u64", open(os.path.join(csrc, f)).read()), f
 
 
 def test_glv_decomposition(pkg):

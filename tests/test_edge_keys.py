@@ -222,6 +222,27 @@ def test_key_without_k_points_prepares(pkg):
     p0.close()
 
 
+def test_batch_entries_refuse_an_n_public_whose_records_overflow(pkg, fixtures):
+    """The SIZE_MAX input count of a key without K points, passed back as n_public, and a count for which n * (proof_stride + 32 n_public) wraps: every
+    host-buffer batch entry answers BN254_E_BAD_ARG before it touches a device or sizes a buffer (the wrapped sizes read out of bounds)."""
+    L = pkg.lib()
+    n, stride = 4, 256
+    proofs, inputs, st = bytes(n * stride), bytes(64), (C.c_uint8 * n)()
+    g0 = pkg.PreparedVk(_key_without_k(pkg.synth_groth16(3, 0, 0, invalid_every=0, agree=True, threads=1)[0]))
+    _fx, vk = fixtures
+    pl = pkg.PreparedPlonkVk(vk)
+    try:
+        for n_public in (2 ** 64 - 1, g0.n_public, 2 ** 57):                      # 2^57: the row fits in 64 bits, 4 rows do not
+            assert L.bn254_groth16_verify_batch(g0._h, proofs, stride, inputs, n_public, n, st, 0, 0) == -1, n_public
+            assert L.bn254_groth16_verify_batch_multi(g0._h, proofs, stride, inputs, n_public, n, st, 1, 0) == -1, n_public
+            assert L.bn254_plonk_verify_batch_flags(pl._h, proofs, stride, inputs, n_public, n, st, 0, 0) == -1, n_public
+            assert L.bn254_plonk_verify_batch_multi(pl._h, proofs, stride, inputs, n_public, n, st, 1, 0) == -1, n_public
+            assert b"overflow" in L.bn254_last_error()
+    finally:
+        g0.close()
+        pl.close()
+
+
 def test_line_tables_exist_for_every_twist_point():
     """Why bn254_groth16_vk_prepare cannot fail on a key that parsed.  A key's G2 elements are on the twist by construction (y is computed from x) but unchecked
     otherwise, and the product walks them with AFFINE line tables, which have no value where the walk meets T = +-S or T = O.  That needs (a) in the main loop: the

@@ -2,7 +2,7 @@
 sanitizers on the CPU builds only, the GPU pool has none:
   * the oracle (oracle/*.c) and the host build of the product's arithmetic headers with the bound tracker (tests/hostsim) rebuilt with -fsanitize=address,undefined
     and run through their own test files in a child interpreter that preloads the sanitizer runtimes;
-  * the HOST HALF OF THE PRODUCT -- csrc/bn254_capi.hip with its parsers, key preparation, plans, pinned ring, context pools and thread pool -- compiled with g++
+  * the HOST HALF OF THE PRODUCT -- csrc/bn254_capi*.hip with its parsers, key preparation, plans, pinned ring, context pools and thread pool -- compiled with g++
     against a host-memory stand-in for the HIP runtime (tests/hostsan) and driven through the C ABI: malformed-bytes fuzz of the three parsers that take
     attacker-shaped lengths (groth16/converter.rs:28-65, plonk/converter.rs:18-119, the SP1 fixture reader), batches around every plan boundary on the fake
     device, the RLC fallback, wide keys, PlonK calls in flight, an allocation failure at every allocation of a call.

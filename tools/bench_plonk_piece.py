@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """PlonK batches above 65 536 proofs: proofs per pass x passes in flight, on the device-resident entry (bn254_plonk_verify_batch_device) and, for the chosen plan, on
 the host-buffer entry.  One JSON line per (batch, plan) with the stage durations of the first pass (HIP events on its stream) -- what PLONK_BIG_PIECE_DEFAULT in
-csrc/bn254_capi.hip is read off (profiles/r05_plonk_piece_sweep.txt).  Status bytes of every plan must be equal."""
+csrc/bn254_capi_plonk.hip is read off (profiles/r05_plonk_piece_sweep.txt).  Status bytes of every plan must be equal."""
 import argparse, importlib, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

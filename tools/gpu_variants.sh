@@ -19,7 +19,6 @@ run plonk_onepass_max BN254_PLONK_BIG_FROM=1 BN254_PLONK_BIG_PIECE=262144
 run msm_budget_small BN254_MSM_LANE_BUDGET=4096
 run msm_budget_large BN254_MSM_LANE_BUDGET=1048576
 run coop_fixed_off BN254_COOP_FIXED_MAX=0
-run plonk_host BN254_PLONK_HOST=1
 run tables_host BN254_TABLES_HOST=1
 fi
 if [ -z "$ONLY_LIBS" ]; then
