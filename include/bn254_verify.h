@@ -83,6 +83,10 @@ enum { BN254_VK_REFERENCE = 0, BN254_VK_GNARK = 1 };
  *     getrandom(2) per call.  The call synchronises the stream once (to learn which groups failed).
  *     The mode is a longer pipeline than the exact path and pays from about 200 000 proofs (2.0 x at 2^20): below that the flag is
  *     ignored (bn254_set_rlc_params, or BN254_RLC_MIN_BATCH in the environment when the library is loaded, moves the threshold; never below 64).
+ *     Every key width is accepted.  Keys with more than 8 public inputs form the public-input sum once per group (group scalars sum_i r_i x_ij, then the key's own
+ *     fixed-base tables), so the mode pays much earlier there: it is honoured from min(threshold above, 4096 + 6 000 000 / n_public) proofs -- about 10 000 at
+ *     1024 inputs (4.2 x at 65 536), 27 500 at 256, the threshold above up to about 30 inputs -- the measured crossovers; BN254_RLC_WIDE_MIN_BATCH in the environment
+ *     at load time replaces the formula by one value for all such keys.
  *     Adaptive: an RLC pass costs about half an exact pass and every proof of a failed group pays the exact pass on top, so per
  *     (key, device) the share of proofs that fell back is tracked, and while it is above 0.45 the flag is ignored (the exact path
  *     runs: same status bytes) except for one measuring RLC pass every 8 calls.  bn254_set_rlc_params(-1, 0, -1) (or
@@ -320,6 +324,18 @@ int bn254_dbg_g16_plan(size_t key_inputs, int comb, size_t reserved, size_t n, s
 /* ... and of BN254_FLAG_RLC's group status bytes: what the launch parts of a chunk of m proofs address (need) against what a context whose RLC buffers were sized
  * for `reserved` proofs holds (alloc) */
 int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, uint64_t* need, uint64_t* alloc);
+/* ... and of its wide form (keys with more than 8 public inputs, csrc/bn254_g16_plan.h::g16_rlc_wide_alloc): alloc = {group scalar row bytes, digit bytes, partial-sum bytes}
+ * a context allocates for a chunk of m proofs against a key of key_inputs inputs whose tables have msm_form (0 comb, 1 byte windows, 2 13-bit windows); parts_out: 2 values
+ * per launch part {first group, groups}, as the enqueue places them (at most max_parts written, *n_parts = parts) */
+int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, size_t key_inputs, int msm_form, uint64_t alloc[3],
+                                uint64_t* parts_out, int max_parts, int* n_parts);
+/* host compile of the wide RLC group stage (csrc/bn254_rlc.h: rlc_group_scalar, vm_rlc_group_points_wide) on given data: n proofs in the groups of
+ * rlc_plan(n, log2_group, log2_share), weights (16 bytes per proof: k1, k2 as little-endian u64, r_i = k1 + k2 lambda mod r), live (n bytes, 0: the proof
+ * contributes weight 0), inputs (n x n_public x 32 bytes, big-endian, used modulo r); kpts = K_0 .. K_n_public and alpha64, uncompressed.  *groups_out = groups;
+ * scalars_out = nullptr stops there, else it receives every group's scalars s_gj = sum_i r_i x_ij mod r (groups x n_public x 32 bytes, big-endian) and l_out the
+ * point t_0 K_0 + sum_j s_gj K_j of group `group` (t_0 = sum of its live weights), uncompressed, all zero for the identity */
+int bn254_dbg_rlc_wide_group(const uint8_t* kpts, const uint8_t alpha64[64], const uint8_t* weights, const uint8_t* live, const uint8_t* inputs, size_t n_public, size_t n,
+                             int log2_group, int log2_share, unsigned group, uint8_t* scalars_out, unsigned* groups_out, uint8_t l_out[64]);
 size_t bn254_dbg_plonk_scratch_lanes(size_t capacity, int n_var);
 /* ... and the projective points (rows x items) the row buffer of a context of `capacity` proofs holds for launches of that key shape and stage (stage 3: the weighted
  * second launch of BN254_FLAG_RLC): n_rows x n of every launch over n <= capacity items must fit (tests/test_msm_rows.py) */

@@ -125,6 +125,34 @@ def set_rlc_params(min_batch=-1, adaptive=-1, share_min_lanes=-1):
     lib().bn254_set_rlc_params(min_batch, adaptive, share_min_lanes)
 
 
+def dbg_rlc_wide_plan(m, n_streams=2, log2_group=5, log2_share=3, min_lanes=65536, key_inputs=1024, msm_form=0):
+    """Wide form of FLAG_RLC (keys with more than 8 inputs), bn254_dbg_g16_rlc_wide_plan: ({rows, digits, part}: bytes a context allocates for a chunk of m
+    proofs, [(first group, groups)] per launch part as the enqueue places them)."""
+    L = lib()
+    L.bn254_dbg_g16_rlc_wide_plan.argtypes = [C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                              C.c_int, C.POINTER(C.c_int)]
+    alloc = (C.c_uint64 * 3)(); parts = (C.c_uint64 * 64)(); k = C.c_int()
+    _check(L.bn254_dbg_g16_rlc_wide_plan(m, n_streams, log2_group, log2_share, min_lanes, key_inputs, msm_form, alloc, parts, 32, C.byref(k)))
+    return {"rows": alloc[0], "digits": alloc[1], "part": alloc[2]}, [(parts[2 * i], parts[2 * i + 1]) for i in range(k.value)]
+
+
+def dbg_rlc_wide_group(kpts, alpha, weights, live, inputs, n_public, n, log2_group=5, log2_share=0, group=0):
+    """Host compile of the wide FLAG_RLC group stage (bn254_dbg_rlc_wide_group).  kpts: K_0 .. K_n_public (64-byte uncompressed each, concatenated), alpha: 64 bytes,
+    weights: 16 bytes per proof (k1, k2 little-endian u64), live: n bytes, inputs: n x n_public x 32 bytes.  Returns (per group a list of n_public 32-byte scalars
+    sum r_i x_ij mod r, the uncompressed point t_0 K_0 + sum_j s_j K_j of group `group`, 64 zero bytes for the identity)."""
+    L = lib()
+    L.bn254_dbg_rlc_wide_group.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_uint, C.c_void_p,
+                                           C.POINTER(C.c_uint), C.c_void_p]
+    groups = C.c_uint()
+    _check(L.bn254_dbg_rlc_wide_group(None, None, None, None, None, n_public, n, log2_group, log2_share, 0, None, C.byref(groups), None))
+    g = groups.value
+    out = (C.c_uint8 * max(1, g * n_public * 32))(); lo = (C.c_uint8 * 64)()
+    _check(L.bn254_dbg_rlc_wide_group(bytes(kpts), bytes(alpha), bytes(weights), bytes(live), bytes(inputs) if n_public else None, n_public, n, log2_group, log2_share,
+                                      group, out, C.byref(groups), lo))
+    raw = bytes(out)
+    return [[raw[(gi * n_public + j) * 32:(gi * n_public + j + 1) * 32] for j in range(n_public)] for gi in range(g)], bytes(lo)
+
+
 def set_plonk_params(piece=-1, workers=-1, big_from=-1, big_piece=-1):
     """Knobs of the PlonK batch plan (bn254_set_plonk_params; -1 leaves a knob alone)."""
     L = lib()

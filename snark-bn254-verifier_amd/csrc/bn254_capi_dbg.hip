@@ -45,6 +45,101 @@ int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_gr
   return BN254_OK;
 }
 
+// ... and of the wide form (keys with more than RLC_MAX_PUBLIC inputs): alloc = {row, digit, partial-sum bytes} rlc_ensure allocates for a chunk of m proofs;
+// parts_out: 2 values per launch part {first group, groups} as g16_enqueue_rlc places them (at most max_parts written, *n_parts = parts)
+int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, size_t key_inputs, int msm_form, uint64_t alloc[3],
+                                uint64_t* parts_out, int max_parts, int* n_parts) {
+  if (!alloc || !n_parts || m == 0 || m > (size_t)G16_MAX_BATCH || n_streams < 1 || n_streams > 4 || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > 3 ||
+      msm_form < 0 || msm_form > 2 || (max_parts > 0 && !parts_out))
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  const G16RlcWide a = g16_rlc_wide_alloc(g16_round256(g16_rlc_wide_groups(m, n_streams, log2_group, log2_share, min_lanes)), key_inputs, msm_form);
+  alloc[0] = a.rows_bytes; alloc[1] = a.digit_bytes; alloc[2] = a.part_bytes;
+  const int parts = g16_rlc_parts(m, n_streams);
+  const size_t per = ((m + parts - 1) / parts + 255) / 256 * 256;
+  size_t off = 0; int k = 0;
+  for (int pi = 0; pi < parts; pi++) {
+    const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
+    if (lo >= hi) break;
+    const RlcPlan pl = rlc_plan((uint32_t)(hi - lo), log2_group, g16_rlc_share(hi - lo, log2_group, log2_share, min_lanes < 1 ? 1 : min_lanes));
+    if (k < max_parts) { parts_out[2 * k] = off; parts_out[2 * k + 1] = pl.groups; }
+    off += pl.groups; k++;
+  }
+  *n_parts = k;
+  return BN254_OK;
+}
+
+// Host compile of the wide RLC group stage (bn254_rlc.h): the group scalars s_gj = sum r_i x_ij of every group of rlc_plan(n, log2_group, log2_share) from
+// given weights (16 bytes per proof: k1, k2 as little-endian u64; r_i = k1 + k2 lambda) and liveness bytes (0: weight 0), and for group `group` the
+// point L = t_0 K_0 + sum_j s_j K_j through vm_rlc_group_points_wide with 13-bit window entries of the key points (computed on the fly).  kpts: K_0 .. K_n_public,
+// 64-byte uncompressed each.  scalars_out (groups x n_public x 32 bytes, big-endian; nullptr: only *groups_out) ; l_out: L uncompressed, all zero for the identity.
+namespace {
+struct HostLane {
+  Fp e[VE_COUNT];
+  Fp ld(int i) const { return e[i]; }
+  void st(int i, const Fp& a) { e[i] = a; }
+};
+struct LazyWindows {   // entry d of window w of P: (d + 1) 2^(MSM_FW_BITS w) P, affine
+  std::vector<G1Proj> bw;
+  explicit LazyWindows(const G1Aff& P) : bw(MSM_FW_WINDOWS) {
+    G1Proj b = g1_from_affine(P);
+    for (int w = 0; w < MSM_FW_WINDOWS; w++) { bw[w] = b; for (int k = 0; k < MSM_FW_BITS; k++) b = g1_dbl(b); }
+  }
+  G1Aff operator()(int w, int d) const {
+    const uint32_t m = (uint32_t)d + 1;
+    G1Proj acc = g1_identity();
+    for (int bit = MSM_FW_BITS - 1; bit >= 0; bit--) { acc = g1_dbl(acc); if ((m >> bit) & 1) acc = g1_add(acc, bw[w]); }
+    return g1_to_affine(acc);
+  }
+};
+}  // namespace
+int bn254_dbg_rlc_wide_group(const uint8_t* kpts, const uint8_t alpha64[64], const uint8_t* weights, const uint8_t* live, const uint8_t* inputs, size_t n_public, size_t n,
+                             int log2_group, int log2_share, unsigned group, uint8_t* scalars_out, unsigned* groups_out, uint8_t l_out[64]) {
+  if (!groups_out || n == 0 || n > (size_t)G16_MAX_LAUNCH || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > log2_group || log2_share > 3 || (n >> log2_share) == 0)
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  const RlcPlan plan = rlc_plan((uint32_t)n, log2_group, log2_share);
+  *groups_out = plan.groups;
+  if (!scalars_out) return BN254_OK;
+  if (!kpts || !alpha64 || !weights || !live || (n_public && !inputs) || !l_out || group >= plan.groups) return set_err(BN254_E_BAD_ARG, "bad argument");
+  auto load_input = [&](uint32_t i, int j, uint32_t x[8]) { words_from_be(x, inputs + ((size_t)i * n_public + (size_t)j) * 32); };
+  auto load_weight = [&](uint32_t i, uint32_t k[4]) -> bool {
+    if (!live[i]) return false;
+    for (int q = 0; q < 4; q++) { const uint8_t* b = weights + 16 * (size_t)i + 4 * q; k[q] = (uint32_t)b[0] | (uint32_t)b[1] << 8 | (uint32_t)b[2] << 16 | (uint32_t)b[3] << 24; }
+    return true;
+  };
+  for (uint32_t g = 0; g < plan.groups; g++)
+    for (size_t j = 0; j < n_public; j++) {
+      const Fr8 sj = rlc_group_scalar(g, (int)j, (uint32_t)n, plan, load_input, load_weight);
+      words_to_be(scalars_out + ((size_t)g * n_public + j) * 32, sj.w);
+    }
+  // the group's lane after the fold: t_0 = sum of its live weights, C' = O
+  Fr8 t0 = fr8_zero();
+  rlc_for_each_member(group, (uint32_t)n, plan, [&](uint32_t i) { uint32_t k[4]; if (load_weight(i, k)) t0 = fr8_add(t0, rlc_weight(k)); });
+  HostLane w;
+  for (auto& e : w.e) e = fp_zero();
+  w.st(RLC_T, fr8_to_slot(t0));
+  w.st(RLC_C, fp_zero()); w.st(RLC_C + 1, fp_one()); w.st(RLC_C + 2, fp_zero());
+  std::vector<LazyWindows> kw;
+  for (size_t j = 0; j <= n_public; j++) {
+    G1Aff K; K.x = fp_from_be(kpts + 64 * j); K.y = fp_from_be(kpts + 64 * j + 32);
+    if (!g1_on_curve(K)) return set_err(BN254_E_BAD_ARG, "key point not on the curve");
+    kw.emplace_back(K);
+  }
+  G1Aff A; A.x = fp_from_be(alpha64); A.y = fp_from_be(alpha64 + 32);
+  if (!g1_on_curve(A)) return set_err(BN254_E_BAD_ARG, "alpha not on the curve");
+  const LazyWindows na(g1_neg(A));
+  G1Proj Lk = g1_identity();
+  for (size_t j = 0; j < n_public; j++) {
+    Fr8 sj;
+    words_from_be(sj.w, scalars_out + ((size_t)group * n_public + j) * 32);
+    Lk = g1_window_sum(Lk, sj, [&](int wi, int d) { return kw[j + 1](wi, d); });
+  }
+  const int fl = vm_rlc_group_points_wide(w, Lk, [&](int b, int wi, int d) { return b == 0 ? na(wi, d) : kw[0](wi, d); });
+  if (fl & 1) { memset(l_out, 0, 64); return BN254_OK; }
+  G1Aff L; L.x = w.ld(VE_LX); L.y = w.ld(VE_LY);
+  enc_g1_uncompressed(l_out, L);
+  return BN254_OK;
+}
+
 // ---------------------------------------------------------------- device-arithmetic probes (tests)
 struct DevBuf {   // frees on every exit path
   uint8_t* p = nullptr;

@@ -18,9 +18,21 @@ static std::atomic<unsigned> g_prof_epoch{0};   // bumped by the two profiling s
 static std::atomic<long> g_rlc_min_batch{[] { long v = env_long("BN254_RLC_MIN_BATCH", RLC_PAYS_FROM); return v < RLC_MIN_BATCH ? (long)RLC_MIN_BATCH : v; }()};
 static std::atomic<int> g_rlc_adaptive{env_long("BN254_RLC_ADAPTIVE", 1) != 0 ? 1 : 0};
 static std::atomic<long> g_rlc_share_min_lanes{env_long("BN254_RLC_SHARE_MIN_LANES", 65536)};
+// Keys with more than RLC_MAX_PUBLIC inputs do their public-input MSM once per group instead of once per proof (bn254_rlc.h, group scalars), and that MSM is most
+// of an exact pass at large widths: there the mode pays from far fewer proofs.  Measured crossovers, all proofs valid (profiles/r06_rlc_wide_vs_exact.txt): about
+// 9 500 proofs at 1024 inputs, 15 000 at 512, 26 000 at 256, 50 000 at 128, 90 000 at 40, 140 000 at 9 and 16 -- fitted (conservatively below 128) by
+// RLC_WIDE_PAYS_FIXED + RLC_WIDE_PAYS_SCALE / n_public.  BN254_RLC_WIDE_MIN_BATCH in the environment at load time replaces the fit by one value for every such key.
+// A wide key honours the flag from the smaller of that and the threshold above, so bn254_set_rlc_params(64, ...) lowers both, and the default of the one above
+// (RLC_PAYS_FROM) caps the fit for narrow-ish keys.
+#define RLC_WIDE_PAYS_FIXED 4096
+#define RLC_WIDE_PAYS_SCALE 6000000
+static const long g_rlc_wide_min_batch_env = [] { long v = env_long("BN254_RLC_WIDE_MIN_BATCH", -1); return v < 0 ? -1L : (v < RLC_MIN_BATCH ? (long)RLC_MIN_BATCH : v); }();
+static long rlc_wide_pays_from(size_t n_public) {
+  return g_rlc_wide_min_batch_env >= 0 ? g_rlc_wide_min_batch_env : (long)(RLC_WIDE_PAYS_FIXED + RLC_WIDE_PAYS_SCALE / (n_public ? n_public : 1));
+}
 
 static void rlc_dev_free(RlcDev& r) {
-  void* ptrs[] = {r.btab, r.tab, r.one, r.grp_status, r.idx, r.fb_proofs, r.fb_inputs, r.fb_status};
+  void* ptrs[] = {r.btab, r.tab, r.one, r.grp_status, r.idx, r.fb_proofs, r.fb_inputs, r.fb_status, r.grp_rows, r.grp_digits, r.grp_part};
   for (auto q : ptrs) if (q) (void)hipFree(q);
   if (r.h_status) (void)hipHostFree(r.h_status);
   if (r.h_idx) (void)hipHostFree(r.h_idx);
@@ -257,7 +269,7 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
 }
 
 // ---- BN254_FLAG_RLC (bn254_rlc.h): first pass in groups, exact second pass over the proofs of groups that failed -----------------------------
-static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_public) {
+static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_public, size_t wide_groups) {
   RlcDev& r = d->rlc;
   if (!r.ready) {
     {
@@ -282,7 +294,17 @@ static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_
     HIPCK(hipHostMalloc((void**)&r.h_idx, cap * sizeof(uint32_t), hipHostMallocDefault));
     r.grp_cap = r.idx_cap = r.h_cap = n;
   }
-  (void)n_public;
+  if (n_public > (size_t)RLC_MAX_PUBLIC && wide_groups > r.wide_cap) {
+    void* ptrs[] = {r.grp_rows, r.grp_digits, r.grp_part};
+    for (auto q : ptrs) if (q) HIPCK(hipFree(q));
+    r.grp_rows = nullptr; r.grp_digits = nullptr; r.grp_part = nullptr; r.wide_cap = 0;
+    const size_t cap = g16_round256(wide_groups);
+    const G16RlcWide a = g16_rlc_wide_alloc(cap, n_public, g16_table_form(pvk->host));
+    HIPCK(hipMalloc((void**)&r.grp_rows, a.rows_bytes));
+    if (a.digit_bytes) HIPCK(hipMalloc((void**)&r.grp_digits, a.digit_bytes));
+    if (a.part_bytes) HIPCK(hipMalloc((void**)&r.grp_part, a.part_bytes));
+    r.wide_cap = cap;
+  }
   return BN254_OK;
 }
 static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
@@ -298,14 +320,17 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
   const size_t chunk = G16_MAX_BATCH;
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
-    int rc = rlc_ensure(pvk, d, m, n_public);
+    const long ml0 = g_rlc_share_min_lanes.load();
+    const size_t min_lanes = ml0 < 1 ? 1 : (size_t)ml0;
+    const bool wide = n_public > (size_t)RLC_MAX_PUBLIC;
+    int rc = rlc_ensure(pvk, d, m, n_public, wide ? g16_rlc_wide_groups(m, n_streams, log2_group, log2_share_env, min_lanes) : 0);
     if (rc) return rc;
     RlcDev& r = d->rlc;
     const int parts = g16_rlc_parts(m, n_streams);
-    {
-      const long ml0 = g_rlc_share_min_lanes.load();
-      if (g16_rlc_need(m, n_streams, log2_group, log2_share_env, ml0 < 1 ? 1 : (size_t)ml0) > g16_rlc_alloc(r.grp_cap)) return set_err(BN254_E_HIP, "RLC group buffer smaller than the batch (internal sizing error)");
-    }
+    if (g16_rlc_need(m, n_streams, log2_group, log2_share_env, min_lanes) > g16_rlc_alloc(r.grp_cap)) return set_err(BN254_E_HIP, "RLC group buffer smaller than the batch (internal sizing error)");
+    const int msm_form = g16_table_form(pvk->host);
+    const size_t chunks_w = (n_public + G16_WIDE_MSM_INPUTS_PER_LANE - 1) / G16_WIDE_MSM_INPUTS_PER_LANE;
+    size_t wide_off = 0;   // groups of the parts before this one (bn254_g16_plan.h::g16_rlc_wide_groups)
     const bool concurrent = parts > 1;
     if (concurrent) { rc = ensure_aux(*d, parts - 1); if (rc) return rc; HIPCK(hipEventRecord(d->fork_ev, user)); }
     const size_t per = ((m + parts - 1) / parts + 255) / 256 * 256;
@@ -332,6 +357,14 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
       ra.plan = rlc_plan((uint32_t)a.n, log2_group, log2_share);
       ra.grp_status = r.grp_status + grp_off; grp_off += ((size_t)ra.plan.groups + 255) / 256 * 256;
       ra.btab = r.btab; ra.rlc_tab = r.tab; ra.one = r.one;
+      if (wide) {
+        if (wide_off + ra.plan.groups > r.wide_cap) return set_err(BN254_E_HIP, "RLC group scalar buffer smaller than the batch (internal sizing error)");
+        ra.grp_rows = r.grp_rows + wide_off * n_public * 32;
+        ra.grp_digits = r.grp_digits ? r.grp_digits + wide_off * (size_t)G16_COMB_COLS * n_public : nullptr;
+        ra.grp_part = r.grp_part ? r.grp_part + wide_off * chunks_w * 27 : nullptr;
+        ra.msm_form = msm_form;
+        wide_off += ra.plan.groups;
+      }
       hipError_t e = bn254_launch_g16_rlc(a, ra, st);
       if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
                                            std::string("kernel launch (rlc): ") + hipGetErrorString(e));
@@ -389,7 +422,9 @@ static bool rlc_bypass(RlcDev& r) {
 }
 // does a batch of this shape qualify for the RLC mode at all (the adaptive bypass, rlc_bypass, is decided separately, once per call)
 static bool rlc_eligible(const bn254_g16_pvk* pvk, size_t n_public, size_t n, unsigned flags) {
-  return (flags & BN254_FLAG_RLC) && pvk->host.inputs_match(n_public) && n_public <= (size_t)RLC_MAX_PUBLIC && n >= (size_t)g_rlc_min_batch.load();
+  long from = g_rlc_min_batch.load();
+  if (n_public > (size_t)RLC_MAX_PUBLIC) { const long wide_from = rlc_wide_pays_from(n_public); if (wide_from < from) from = wide_from; }
+  return (flags & BN254_FLAG_RLC) && pvk->host.inputs_match(n_public) && n >= (size_t)from;
 }
 // one batch on `user`: waits for the previous batch of this (key, device), runs the exact or the RLC pipeline, records busy_ev.
 // use_rlc: -1 = decide here; 0 / 1 = the caller (the host-buffer entry, which must know before it cuts the batch into chunks) has decided

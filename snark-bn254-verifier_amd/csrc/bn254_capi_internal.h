@@ -54,6 +54,8 @@ struct RlcDev {
   uint32_t* idx = nullptr; size_t idx_cap = 0;
   uint8_t *fb_proofs = nullptr, *fb_inputs = nullptr, *fb_status = nullptr; size_t fb_cap = 0, fb_in_cap = 0;
   uint8_t* h_status = nullptr; uint32_t* h_idx = nullptr; size_t h_cap = 0;   // pinned
+  // keys with more than RLC_MAX_PUBLIC inputs: group scalar rows, digits and chunk sums of the groups' MSM (bn254_g16_plan.h::g16_rlc_wide_alloc), for wide_cap groups
+  uint8_t* grp_rows = nullptr; uint16_t* grp_digits = nullptr; int32_t* grp_part = nullptr; size_t wide_cap = 0;
   // adaptive use of the mode: share of the checked proofs the last RLC passes sent to the exact fallback (exponential average) and how many
   // calls have bypassed the mode since the last pass that measured it
   bool have_obs = false; float fb_share = 0.f; unsigned bypassed = 0, bypassed_total = 0;

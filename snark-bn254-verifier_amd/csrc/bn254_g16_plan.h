@@ -116,4 +116,30 @@ inline size_t g16_rlc_need(size_t m, int n_streams, int log2_group, int log2_sha
   return off;
 }
 
+// ---- BN254_FLAG_RLC, keys with more than RLC_MAX_PUBLIC inputs: the group scalars and the groups' MSM scratch of one workspace chunk ------------------------
+// The launch parts of a chunk (the walk of g16_rlc_need) put their groups side by side: part pi starts at the sum of the groups before it.
+// g16_rlc_wide_groups(m, ...) is that sum, what rlc_ensure sizes the buffers for and what g16_enqueue_rlc checks every part against.
+inline size_t g16_rlc_wide_groups(size_t m, int n_streams, int log2_group, int log2_share_env, size_t min_lanes) {
+  const int parts = g16_rlc_parts(m, n_streams);
+  const size_t per = g16_round256((m + parts - 1) / parts);
+  size_t groups = 0;
+  for (int pi = 0; pi < parts; pi++) {
+    const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
+    if (lo >= hi) break;
+    groups += rlc_plan((uint32_t)(hi - lo), log2_group, g16_rlc_share(hi - lo, log2_group, log2_share_env, min_lanes)).groups;
+  }
+  return groups;
+}
+// bytes per group: its row of scalars (key_inputs x 32 B, big-endian like an input row), and for the tables of keys with more than 16 inputs (form 0: comb,
+// 1: byte windows; 2: the 13-bit windows of up to 16 inputs need neither) the column digits (form 0) and the chunk sums of k_g16_msm_partial(_comb)
+struct G16RlcWide { size_t rows_bytes, digit_bytes, part_bytes; };
+inline G16RlcWide g16_rlc_wide_alloc(size_t groups, size_t key_inputs, int msm_form) {
+  G16RlcWide a;
+  const size_t chunks = (key_inputs + G16_WIDE_MSM_INPUTS_PER_LANE - 1) / G16_WIDE_MSM_INPUTS_PER_LANE;
+  a.rows_bytes = groups * key_inputs * 32;
+  a.digit_bytes = msm_form == 0 ? (size_t)G16_COMB_COLS * key_inputs * groups * sizeof(uint16_t) : 0;
+  a.part_bytes = msm_form != 2 ? chunks * 27 * groups * sizeof(int32_t) : 0;
+  return a;
+}
+
 }  // namespace bn254

@@ -115,6 +115,13 @@ struct RlcLaunchArgs {
   const int32_t* btab;      // line table of the G2 argument paired with alpha
   const int32_t* rlc_tab;   // window tables of -alpha and K[0]: 2 * 32 * 255 entries of MSM_ENTRY_DWORDS
   const int32_t* one;       // 108 dwords: 1 in GT
+  // keys with more than RLC_MAX_PUBLIC inputs (bn254_rlc.h, group scalars): rows of plan.groups x n_public x 32 bytes, and for msm_form 0 / 1 (more than 16 inputs:
+  // comb / byte-window tables) the digits (G16_COMB_COLS x n_public x groups u16, form 0) and partial sums (ceil(n_public / 16) x 27 x groups dwords) of the
+  // groups' MSM; msm_form 2: the key's 13-bit window tables.  nullptr rows: the narrow form (t_j slots per lane)
+  uint8_t* grp_rows = nullptr;
+  uint16_t* grp_digits = nullptr;
+  int32_t* grp_part = nullptr;
+  int msm_form = 2;
 };
 hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, hipStream_t s);
 hipError_t bn254_launch_gather_rows(uint8_t* dst, const uint8_t* src, size_t src_stride, uint32_t row_bytes, const uint32_t* idx, uint32_t m, hipStream_t s);

@@ -588,6 +588,80 @@ k_rlc_group_step(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, in
   l2.m = uni_ld2(entry2); l2.c = uni_ld2(entry2 + 2 * BN_NL); l2.xc = uni_ld2(entry2 + 4 * BN_NL);
   vm_miller_step_fixed3<DO_SQR>(w, e, l0, VE_LX, (st & BN254_ST_LINF) != 0, l1, VE_CX, (st & BN254_ST_LINF2) != 0, l2, VE_AX, (st & BN254_ST_LINF3) != 0);
 }
+// ---- wide keys (n_public > RLC_MAX_PUBLIC, bn254_rlc.h): t_0 = r_i per proof, the public-input sum once per group from the group scalars --------------
+// per pending proof: as k_rlc_scale without the n_public products; the weight's halves k1 | k2 go to RLC_W for k_rlc_group_scalars
+__global__ void __launch_bounds__(256, 2)
+k_rlc_scale_wide(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, ChaChaKey key, uint32_t counter_base) {
+  VM_KERNEL_PROLOGUE();
+  const uint32_t ii = i < n ? i : n - 1;
+  uint32_t r[4];
+  chacha20_block4(r, key, counter_base + ii);
+  vm_rlc_scale(w, r, 0, [&](int, uint32_t*) {});
+  Fr8 k = fr8_zero();
+#pragma unroll
+  for (int q = 0; q < 4; q++) k.w[q] = r[q];
+  w.st(RLC_W, fr8_to_slot(k));
+}
+// s_gj = sum_{i in g} r_i x_ij mod r (bn254_rlc.h::rlc_group_scalar), lane t = g * n_public + j: the lanes of a wavefront read consecutive 32-byte inputs of a
+// member's row (contiguous over j; a wavefront spans one or two groups, whose members are walked in the same order), and write the group's row of scalars
+// rows[(g * n_public + j) * 32] -- big-endian, the layout of the batch's own input rows -- contiguously.  A proof that is no longer pending (loader error, r-torsion
+// failure, STRICT_SCALARS) has weight 0, as k_rlc_neutral gives its t_0.
+__global__ void __launch_bounds__(256)
+k_rlc_group_scalars(const int32_t* __restrict__ ws, uint32_t n, const uint8_t* __restrict__ status, const uint8_t* __restrict__ inputs, int n_public, RlcPlan plan,
+                    uint8_t* __restrict__ rows) {
+  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
+  if (t >= plan.groups * (uint32_t)n_public) return;
+  const uint32_t g = t / (uint32_t)n_public;
+  const int j = (int)(t - g * (uint32_t)n_public);
+  const bool aligned = (((uintptr_t)inputs) & 3) == 0;
+  const Fr8 s = rlc_group_scalar(g, j, n, plan,
+      [&](uint32_t i, int jj, uint32_t x[8]) {
+        const uint8_t* sp = inputs + ((size_t)i * (size_t)n_public + (size_t)jj) * 32;
+        if (aligned) { uint32_t d[8];
+#pragma unroll
+          for (int k = 0; k < 8; k++) d[k] = ((const uint32_t*)sp)[k];
+          be_field_to_words(x, d);
+        } else words_from_be(x, sp);
+      },
+      [&](uint32_t i, uint32_t k[4]) -> bool {
+        if (!(status[i] & BN254_ST_PENDING)) return false;
+#pragma unroll
+        for (int q = 0; q < 4; q++) k[q] = (uint32_t)ws[((size_t)RLC_W * BN_NL + q) * n + i];
+        return true;
+      });
+  words_to_be(rows + (size_t)t * 32, s.w);
+}
+// group stage of a wide key, one lane per group (bn254_rlc.h::vm_rlc_group_points_wide).  form 2 (up to 16 inputs): sum_j s_j K_j from the key's 13-bit window
+// tables and the group's row of scalars; forms 0 / 1: the chunk sums k_g16_msm_partial(_comb) left in `part` for the group "pseudo-proofs" (no K_0 there)
+__global__ void __launch_bounds__(256, 2)
+k_rlc_group_points_wide(int32_t* ws, uint32_t n, uint8_t* __restrict__ grp_status, uint32_t groups, int n_public, const int32_t* __restrict__ rlc_tab,
+                        const int32_t* __restrict__ msm_tab, const uint8_t* __restrict__ rows, const int32_t* __restrict__ part, int chunks, int form) {
+  const uint32_t g = blockIdx.x * 256u + threadIdx.x;
+  if (__builtin_amdgcn_ballot_w64(g < groups) == 0) return;
+  const uint32_t gg = g < groups ? g : groups - 1;
+  DevWs w(ws, n, g < groups ? g : DEAD_LANE);
+  G1Proj Lk = g1_identity();
+  if (__builtin_amdgcn_readfirstlane(form) == 2) {
+    for (int j = 0; j < n_public; j++) {
+      Fr8 sj;
+      words_from_be(sj.w, rows + ((size_t)gg * (size_t)n_public + (size_t)j) * 32);
+      Lk = g1_window_sum(Lk, sj, [&](int wi, int d) { return msm_entry(msm_tab, (size_t)(j * MSM_FW_WINDOWS + wi) * MSM_FW_ENTRIES + d); });
+    }
+  } else {
+    for (int c = 0; c < chunks; c++) {
+      const int32_t* o = part + (size_t)c * 27 * groups + gg;
+      G1Proj q;
+#pragma unroll
+      for (int l = 0; l < BN_NL; l++) { q.x.v[l] = o[(size_t)l * groups]; q.y.v[l] = o[(size_t)(9 + l) * groups]; q.z.v[l] = o[(size_t)(18 + l) * groups]; }
+      BN_SETB(q.x, 3.0, 0.5); BN_SETB(q.y, 3.0, 0.5); BN_SETB(q.z, 3.0, 0.5);
+      Lk = g1_add(Lk, q);
+    }
+    Lk.x = fp_reduce(Lk.x); Lk.y = fp_reduce(Lk.y); Lk.z = fp_reduce(Lk.z);
+    BN_SETB(Lk.x, 1.01, 0.5); BN_SETB(Lk.y, 1.01, 0.5); BN_SETB(Lk.z, 1.01, 0.5);
+  }
+  const int fl = vm_rlc_group_points_wide(w, Lk, [&](int b, int wi, int d) { return msm_entry(rlc_tab, (size_t)(b * MSM_FW_WINDOWS + wi) * MSM_FW_ENTRIES + d); });
+  if (g < groups) grp_status[g] = (uint8_t)(BN254_ST_PENDING | ((fl & 1) ? BN254_ST_LINF : 0) | ((fl & 2) ? BN254_ST_LINF2 : 0) | ((fl & 4) ? BN254_ST_LINF3 : 0));
+}
 // every pending proof takes its group's verdict: ACCEPT, or it stays pending (0x80) for the exact path
 __global__ void __launch_bounds__(256, 2)
 k_rlc_scatter(uint8_t* __restrict__ status, uint32_t n, const uint8_t* __restrict__ grp_status, RlcPlan plan) {
@@ -855,7 +929,11 @@ hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, 
   if (a.strict_scalars && a.n_public > 0) hipLaunchKernelGGL(k_g16_check_scalars, dim3(grid), dim3(256), 0, s, a.inputs, a.n_public, n, a.status);
   LaunchOps ops{a.ws, n, a.status, grid, s, {nullptr, nullptr, nullptr}, nullptr};
   BN_LAUNCH(KID_VM_INIT, k_vm_init, a.ws, n, (const uint8_t*)a.status);
-  hipLaunchKernelGGL(k_rlc_scale, dim3(grid), dim3(256), 0, s, a.ws, n, (const uint8_t*)a.status, a.inputs, a.n_public, key, r.counter_base);
+  // wide keys carry t_0 alone through the fold (slots: the Fr values per lane), their group scalars come from k_rlc_group_scalars
+  const bool wide = r.grp_rows != nullptr;
+  const int slots = wide ? 0 : a.n_public;
+  if (wide) hipLaunchKernelGGL(k_rlc_scale_wide, dim3(grid), dim3(256), 0, s, a.ws, n, (const uint8_t*)a.status, key, r.counter_base);
+  else hipLaunchKernelGGL(k_rlc_scale, dim3(grid), dim3(256), 0, s, a.ws, n, (const uint8_t*)a.status, a.inputs, a.n_public, key, r.counter_base);
   const uint8_t* kinds = step_kinds_host();
   const int share = 1 << r.plan.pre;
   if (share == 1) {
@@ -872,18 +950,35 @@ hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, 
     }
   }
   BN_LAUNCH(KID_SUBGROUP, k_g16_subgroup, n, a.ws, a.status, a.inputs_match_key, (int)VE_T);
-  hipLaunchKernelGGL(k_rlc_neutral, dim3(grid), dim3(256), 0, s, a.ws, n, (const uint8_t*)a.status, a.n_public, share == 1 ? 1 : 0);
+  hipLaunchKernelGGL(k_rlc_neutral, dim3(grid), dim3(256), 0, s, a.ws, n, (const uint8_t*)a.status, slots, share == 1 ? 1 : 0);
   uint32_t cur = n;
   for (int k = 0; k < r.plan.rounds; k++) {
     const uint32_t half = r.plan.half[k];
-    hipLaunchKernelGGL(k_rlc_fold, dim3(grid_for(cur - half)), dim3(256), 0, s, a.ws, n, cur, half, a.n_public, k >= r.plan.pre ? 1 : 0);
+    hipLaunchKernelGGL(k_rlc_fold, dim3(grid_for(cur - half)), dim3(256), 0, s, a.ws, n, cur, half, slots, k >= r.plan.pre ? 1 : 0);
     cur = half;
   }
   // group stage: lanes [0, groups) of the same workspace, their own status bytes
   const uint32_t groups = r.plan.groups;
   const unsigned ggrid = grid_for(groups);
-  (void)hipMemsetAsync(r.grp_status, 0, ((size_t)groups + 255) / 256 * 256, s);
-  hipLaunchKernelGGL(k_rlc_group_points, dim3(ggrid), dim3(256), 0, s, a.ws, n, r.grp_status, groups, a.n_public, r.rlc_tab, a.msm_tab);
+  if (wide) {
+    // the group scalars become the input rows of `groups` pseudo-proofs: the key's own fixed-base kernels sum them (no K_0: vm_rlc_group_points_wide adds t_0 K_0)
+    const size_t lanes = (size_t)groups * (size_t)a.n_public;
+    hipLaunchKernelGGL(k_rlc_group_scalars, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, (const int32_t*)a.ws, n, (const uint8_t*)a.status, a.inputs, a.n_public, r.plan, r.grp_rows);
+    (void)hipMemsetAsync(r.grp_status, BN254_ST_PENDING, ((size_t)groups + 255) / 256 * 256, s);    // every pseudo-proof takes part in the partial sums
+    const int per = G16_WIDE_MSM_INPUTS_PER_LANE, chunks = r.msm_form == 2 ? 0 : (a.n_public + per - 1) / per;
+    const unsigned pg = (unsigned)(((size_t)groups * chunks + 255) / 256);
+    if (r.msm_form == 0) {
+      hipLaunchKernelGGL(k_g16_comb_digits, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, (const uint8_t*)r.grp_rows, a.n_public, groups, r.grp_digits);
+      hipLaunchKernelGGL(k_g16_msm_partial_comb, dim3(pg), dim3(256), 0, s, (const uint16_t*)r.grp_digits, a.n_public, groups, per, chunks, (const uint8_t*)r.grp_status, a.msm_tab, r.grp_part);
+    } else if (r.msm_form == 1) {
+      hipLaunchKernelGGL(k_g16_msm_partial, dim3(pg), dim3(256), 0, s, (const uint8_t*)r.grp_rows, a.n_public, groups, per, chunks, (const uint8_t*)r.grp_status, a.msm_tab, r.grp_part);
+    }
+    hipLaunchKernelGGL(k_rlc_group_points_wide, dim3(ggrid), dim3(256), 0, s, a.ws, n, r.grp_status, groups, a.n_public, r.rlc_tab, a.msm_tab, (const uint8_t*)r.grp_rows,
+                       (const int32_t*)r.grp_part, chunks, r.msm_form);
+  } else {
+    (void)hipMemsetAsync(r.grp_status, 0, ((size_t)groups + 255) / 256 * 256, s);
+    hipLaunchKernelGGL(k_rlc_group_points, dim3(ggrid), dim3(256), 0, s, a.ws, n, r.grp_status, groups, a.n_public, r.rlc_tab, a.msm_tab);
+  }
   LaunchOps gops{a.ws, n, r.grp_status, ggrid, s, {a.gtab, a.dtab, r.btab}, nullptr};
   gops.inf_mask[0] = BN254_ST_LINF; gops.inf_mask[1] = BN254_ST_LINF2; gops.inf_mask[2] = BN254_ST_LINF3;
   for (int st_ = 0; st_ < BN_ATE_STEPS; st_++) {

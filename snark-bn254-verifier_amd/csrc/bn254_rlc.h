@@ -24,6 +24,7 @@ enum {
   RLC_C = VE_S1,            // r_i C_i, projective (3 Fp)
   RLC_T = VE_S1 + 3,        // t_0 = r_i, t_j = r_i x_ij mod r  (j = 1..n_public): Fr values, 8 x 32-bit words in the low 8 digits of a slot
   RLC_MAX_PUBLIC = 8,       // 3 + 1 + 8 = 12 slots
+  RLC_W = RLC_T + 1,        // wide keys (n_public > RLC_MAX_PUBLIC): the weight's two 64-bit halves k1 | k2 as raw words, for the group scalars (rlc_group_scalar)
   RLC_ACC = VE_S2,          // group stage: accumulator of the three table-driven pairs
   RLC_HI = 512              // fold accessor: element ids >= RLC_HI address the partner lane
 };
@@ -349,18 +350,9 @@ BN_HD G1Proj g1_window_sum(G1Proj acc, const Fr8& k, const TL& entry) {
   }
   return acc;
 }
-// group stage, one lane per group: the three G1 arguments of the table-driven pairs from the folded scalars and the folded C'
-//   VE_LX/LY <- t_0 K_0 + sum_j t_j K_j      VE_CX/CY <- affine(C')      VE_AX/AY <- t_0 (-alpha)      RLC_ACC <- 1
-// TAB(b, w, d): entry d of window w of base b (0: -alpha, 1: K_0, 1 + j: K_j).  Returns the identity flags (bit 0: L, 1: C, 2: alpha term).
-template <class W, class TAB>
-BN_HD int vm_rlc_group_points(W& w, int n_public, const TAB& tab) {
-  const Fr8 t0 = fr8_from_slot(w.ld(RLC_T));
-  G1Proj Pa = g1_window_sum(g1_identity(), t0, [&](int wi, int d) { return tab(0, wi, d); });
-  G1Proj L = g1_window_sum(g1_identity(), t0, [&](int wi, int d) { return tab(1, wi, d); });
-  for (int j = 1; j <= n_public; j++) {
-    const Fr8 tj = fr8_from_slot(w.ld(RLC_T + j));
-    L = g1_window_sum(L, tj, [&](int wi, int d) { return tab(1 + j, wi, d); });
-  }
+// the tail of the group stage: the three G1 arguments to affine with one inversion, RLC_ACC <- 1; returns the identity flags (bit 0: L, 1: C, 2: alpha term)
+template <class W>
+BN_HD int vm_rlc_group_store(W& w, const G1Proj& Pa, const G1Proj& L) {
   G1Proj Cg; Cg.x = w.ld(RLC_C); Cg.y = w.ld(RLC_C + 1); Cg.z = w.ld(RLC_C + 2);
   BN_SETB(Cg.x, 1.01, 0.5); BN_SETB(Cg.y, 1.01, 0.5); BN_SETB(Cg.z, 1.01, 0.5);
   const bool ia = g1_is_identity(Pa), il = g1_is_identity(L), ic = g1_is_identity(Cg);
@@ -377,5 +369,94 @@ BN_HD int vm_rlc_group_points(W& w, int n_public, const TAB& tab) {
   w.st(RLC_ACC, fp_one());
   for (int e = 1; e < 12; e++) w.st(RLC_ACC + e, fp_zero());
   return (il ? 1 : 0) | (ic ? 2 : 0) | (ia ? 4 : 0);
+}
+// group stage, one lane per group: the three G1 arguments of the table-driven pairs from the folded scalars and the folded C'
+//   VE_LX/LY <- t_0 K_0 + sum_j t_j K_j      VE_CX/CY <- affine(C')      VE_AX/AY <- t_0 (-alpha)      RLC_ACC <- 1
+// TAB(b, w, d): entry d of window w of base b (0: -alpha, 1: K_0, 1 + j: K_j).  Returns the identity flags (bit 0: L, 1: C, 2: alpha term).
+template <class W, class TAB>
+BN_HD int vm_rlc_group_points(W& w, int n_public, const TAB& tab) {
+  const Fr8 t0 = fr8_from_slot(w.ld(RLC_T));
+  G1Proj Pa = g1_window_sum(g1_identity(), t0, [&](int wi, int d) { return tab(0, wi, d); });
+  G1Proj L = g1_window_sum(g1_identity(), t0, [&](int wi, int d) { return tab(1, wi, d); });
+  for (int j = 1; j <= n_public; j++) {
+    const Fr8 tj = fr8_from_slot(w.ld(RLC_T + j));
+    L = g1_window_sum(L, tj, [&](int wi, int d) { return tab(1 + j, wi, d); });
+  }
+  return vm_rlc_group_store(w, Pa, L);
+}
+// ---- wide keys (n_public > RLC_MAX_PUBLIC): the public-input sum once per group from GROUP SCALARS -------------------------------------------------------
+//     sum_{i in g} r_i L_i = t_0 K_0 + sum_j s_j K_j,   t_0 = sum_i r_i,   s_j = sum_i r_i x_ij mod r   (i over the live members of group g)
+// The per-proof stage keeps t_0 = r_i only (the fold carries it like RLC_T of the narrow form) and parks the weight's halves k1 | k2 in RLC_W.  Since
+// r_i = k1 + k2 lambda, s_j = (sum_i x_ij k1_i) + lambda (sum_i x_ij k2_i): two sums of 256 x 64-bit products, reduced mod r once at the end.
+// a += x * k (x: 8 words, k: 2 words) into an 11-word accumulator
+BN_HD void fr_acc_mul64(uint32_t acc[11], const uint32_t x[8], uint32_t k_lo, uint32_t k_hi) {
+  uint32_t p[10];
+  uint64_t c = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) { uint64_t s = (uint64_t)x[j] * k_lo + c; p[j] = (uint32_t)s; c = s >> 32; }
+  p[8] = (uint32_t)c; p[9] = 0; c = 0;
+#pragma unroll
+  for (int j = 0; j < 8; j++) { uint64_t s = (uint64_t)x[j] * k_hi + p[j + 1] + c; p[j + 1] = (uint32_t)s; c = s >> 32; }
+  p[9] = (uint32_t)c;
+  c = 0;
+#pragma unroll
+  for (int j = 0; j < 10; j++) { c += (uint64_t)acc[j] + p[j]; acc[j] = (uint32_t)c; c >>= 32; }
+  acc[10] += (uint32_t)c;
+}
+// an 11-word value T < 2^352 -> T 2^-128 mod r: four word steps of Montgomery reduction leave (T + M r) / 2^128 < 2^224 + r < 2r (M < 2^128), one
+// conditional subtraction
+BN_HD Fr8 fr_acc_redc128(const uint32_t acc[11]) {
+  uint32_t t[13];
+#pragma unroll
+  for (int i = 0; i < 11; i++) t[i] = acc[i];
+  t[11] = 0; t[12] = 0;
+#pragma unroll
+  for (int s = 0; s < 4; s++) {
+    const uint32_t m = t[s] * BN_R_NINV32;
+    uint64_t c = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) { uint64_t v = (uint64_t)m * bn_r_word(j) + t[s + j] + c; t[s + j] = (uint32_t)v; c = v >> 32; }
+#pragma unroll
+    for (int j = s + 8; j < 13; j++) { c += t[j]; t[j] = (uint32_t)c; c >>= 32; }
+  }
+  uint32_t u[9];
+#pragma unroll
+  for (int i = 0; i < 9; i++) u[i] = t[4 + i];
+  return fr8_cond_sub_r(u);
+}
+// s_j of group g.  LX(i, j, w[8]): input j of proof i as little-endian words (raw, used modulo r); LW(i, k[4]) -> false for a proof that contributes nothing
+// (loader error, r-torsion failure, a dead lane: weight 0), else k = k1 lo, k1 hi, k2 lo, k2 hi.
+// Bounds: each product x k < 2^256 2^64 = 2^320; a group has at most 2^rounds <= 2^28 members (RlcPlan.half[28]), so each sum stays below 2^348 < 2^352
+// (11 words): no reduction inside the loop.  End: u_a = redc128(sum_a) = sum_a 2^-128, and s_j = u_1 c + u_2 (lambda c) in Montgomery products with
+// c = 2^384 mod r, i.e. mont(u, c) = u 2^128 (u < r and c < r, so u c < r 2^256 as fr8_mont_mul needs).
+template <class LX, class LW>
+BN_HD Fr8 rlc_group_scalar(uint32_t g, int j, uint32_t n, const RlcPlan& p, const LX& load_input, const LW& load_weight) {
+  uint32_t a1[11], a2[11];
+#pragma unroll
+  for (int i = 0; i < 11; i++) { a1[i] = 0; a2[i] = 0; }
+  rlc_for_each_member(g, n, p, [&](uint32_t i) {
+    uint32_t k[4];
+    if (!load_weight(i, k)) return;
+    uint32_t x[8];
+    load_input(i, j, x);
+    fr_acc_mul64(a1, x, k[0], k[1]);
+    fr_acc_mul64(a2, x, k[2], k[3]);
+  });
+  Fr8 r2, t128 = fr8_zero(), lam;
+#pragma unroll
+  for (int i = 0; i < 8; i++) { r2.w[i] = bn_r2_word(i); lam.w[i] = bn_glv_lambda_word(i); }
+  t128.w[4] = 1;
+  const Fr8 c = fr8_mont_mul(r2, t128);            // 2^512 2^128 / 2^256 = 2^384 mod r
+  const Fr8 lc = fr8_mul_plain(lam, c);            // lambda 2^384 mod r
+  return fr8_add(fr8_mont_mul(fr_acc_redc128(a1), c), fr8_mont_mul(fr_acc_redc128(a2), lc));
+}
+// group stage of a wide key, one lane per group: L = Lk + t_0 K_0 with Lk = sum_j s_j K_j computed from the group scalars (13-bit windows up to 16 inputs,
+// the comb kernels above); C' and the alpha term as in vm_rlc_group_points.  K_0 enters here once, with coefficient t_0.  TAB(b, w, d): b = 0 -alpha, 1 K_0.
+template <class W, class TAB>
+BN_HD int vm_rlc_group_points_wide(W& w, const G1Proj& Lk, const TAB& tab) {
+  const Fr8 t0 = fr8_from_slot(w.ld(RLC_T));
+  G1Proj Pa = g1_window_sum(g1_identity(), t0, [&](int wi, int d) { return tab(0, wi, d); });
+  G1Proj L = g1_window_sum(Lk, t0, [&](int wi, int d) { return tab(1, wi, d); });
+  return vm_rlc_group_store(w, Pa, L);
 }
 }  // namespace bn254

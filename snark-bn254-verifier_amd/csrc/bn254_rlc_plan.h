@@ -27,5 +27,22 @@ BN_PLAN_HD uint32_t rlc_group_of(uint32_t i, const RlcPlan& p) {
   for (int k = 0; k < p.rounds; k++) if (i >= p.half[k]) i -= p.half[k];
   return i;
 }
+// the members of group g (the i < n with rlc_group_of(i, p) == g), in increasing order of their fold bits.  A member is g + sum_k b_k half[k]: walking the
+// rounds backwards, lane v of the lanes after round k has the preimages v (always: v < half[k] <= cur_k) and v + half[k] when that is below cur_k, the lane
+// count before round k (n for k = 0, half[k - 1] after).  The mask walk costs 2^rounds steps of `rounds` comparisons: 2^5 or 2^6 with the default groups of 32.
+template <class F>
+BN_PLAN_HD void rlc_for_each_member(uint32_t g, uint32_t n, const RlcPlan& p, const F& f) {
+  const uint32_t masks = 1u << p.rounds;
+  for (uint32_t mask = 0; mask < masks; mask++) {
+    uint64_t v = g;
+    bool ok = true;
+    for (int k = p.rounds - 1; k >= 0 && ok; k--) {
+      if (!((mask >> k) & 1u)) continue;
+      v += p.half[k];
+      ok = v < (uint64_t)(k == 0 ? n : p.half[k - 1]);
+    }
+    if (ok && v < n) f((uint32_t)v);
+  }
+}
 
 }  // namespace bn254

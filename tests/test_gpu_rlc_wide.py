@@ -1,0 +1,144 @@
+"""GPU tests of BN254_FLAG_RLC for keys with more than 8 public inputs: the public-input sum once per group from group scalars
+(snark-bn254-verifier_amd/csrc/bn254_rlc.h, bn254_kernels.hip: k_rlc_group_scalars, k_rlc_group_points_wide).  Every status byte equals the exact path's and
+the generator's, and on a sample the oracle's; the mode really runs (rlc_state reports a fallback share)."""
+import random
+
+import pytest
+
+pytestmark = pytest.mark.gpu
+R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
+
+
+@pytest.fixture(scope="module")
+def L(pkg):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU; the product has no CPU fallback"
+    return pkg.lib()
+
+
+@pytest.fixture(autouse=True)
+def _rlc_always(pkg):
+    """The RLC kernels on every call (from 64 proofs, no adaptive bypass); the defaults test_gpu_round2.py relies on afterwards."""
+    pkg.set_rlc_params(min_batch=64, adaptive=0)
+    yield
+    pkg.set_rlc_params(min_batch=200000, adaptive=1)
+
+
+def _shuffle(proofs, inputs, exp, n_public, seed):
+    n = len(exp)
+    perm = list(range(n))
+    random.Random(seed).shuffle(perm)
+    row = 32 * n_public
+    return (b"".join(proofs[256 * i:256 * (i + 1)] for i in perm), b"".join(inputs[row * i:row * (i + 1)] for i in perm), bytes(exp[i] for i in perm))
+
+
+WIDTHS = [(9, 1500), (16, 1500), (17, 1200), (40, 1000), (1024, 500)]
+
+
+@pytest.mark.parametrize("n_public,n", WIDTHS)
+def test_rlc_wide_matches_exact(pkg, O, L, n_public, n):
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2541000 + n_public, n_public, n, invalid_every=37, agree=True, threads=16)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        assert pvk.rlc_state()[0] == -1.0
+        for k, (p, i, e) in enumerate(((proofs, inputs, exp), _shuffle(proofs, inputs, exp, n_public, n_public))):
+            rlc = pvk.verify_batch(p, i, flags=pkg.FLAG_RLC)
+            share = pvk.rlc_state()[0]
+            assert share != -1.0                                  # the mode ran (above 8 inputs it never did before)
+            assert 0.0 < share <= 1.0, share                      # the workload's invalid proofs send their groups to the fallback
+            assert rlc == pvk.verify_batch(p, i) == e
+            assert set(e) - {1}, "the workload has invalid proofs"
+            idx = list(range(0, n, max(1, n // 12)))[:12]
+            row = 32 * n_public
+            sp, si = b"".join(p[256 * j:256 * (j + 1)] for j in idx), b"".join(i[row * j:row * (j + 1)] for j in idx)
+            assert O.groth16_verify_many(sp, 256, vk, si, n_public, len(idx)) == bytes(rlc[j] for j in idx)
+    finally:
+        pvk.close()
+
+
+@pytest.mark.parametrize("n_public", [9, 17, 40])
+def test_rlc_wide_all_valid_no_fallback(pkg, L, n_public):
+    n = 2048
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2542000 + n_public, n_public, n, invalid_every=0, agree=True, threads=16)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        assert pvk.verify_batch(proofs, inputs, flags=pkg.FLAG_RLC) == exp == b"\x01" * n
+        assert pvk.rlc_state()[0] < 0.01
+    finally:
+        pvk.close()
+
+
+def test_rlc_wide_device_entry(pkg, L):
+    import torch
+    n_public, n = 17, 1024
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2543000, n_public, n, invalid_every=29, agree=True, threads=16)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        dev = torch.device("cuda:0")
+        dp = torch.frombuffer(bytearray(proofs), dtype=torch.uint8).to(dev)
+        di = torch.frombuffer(bytearray(inputs), dtype=torch.uint8).to(dev)
+        ds = torch.full((n,), 0xEE, dtype=torch.uint8, device=dev)
+        s = torch.cuda.current_stream(dev)
+        torch.cuda.synchronize(dev)
+        pvk.verify_batch_device(dp.data_ptr(), di.data_ptr(), ds.data_ptr(), n, 256, n_public, 0, s.cuda_stream, flags=pkg.FLAG_RLC)
+        s.synchronize()
+        assert bytes(ds.cpu().numpy().tobytes()) == exp
+        assert pvk.rlc_state()[0] != -1.0
+    finally:
+        pvk.close()
+
+
+def test_rlc_wide_input_len_and_strict(pkg, L):
+    n_public, n = 12, 600
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2544000, n_public, n, invalid_every=0, agree=True, threads=16)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        # wrong number of public inputs under the flag: exact semantics
+        assert pvk.verify_batch(proofs, inputs[:32 * (n_public - 1) * n], n, n_public=n_public - 1, flags=pkg.FLAG_RLC) == bytes([pkg.ERR_INPUT_LEN]) * n
+        # an input >= r: used modulo r by default (x + r verifies like x), NOT_MEMBER under STRICT_SCALARS, ahead of the group check
+        bad = bytearray(inputs)
+        row = 32 * n_public
+        j = 123
+        x = int.from_bytes(bad[row * j + 32 * 5:row * j + 32 * 6], "big")
+        assert x + R < 1 << 256
+        bad[row * j + 32 * 5:row * j + 32 * 6] = (x + R).to_bytes(32, "big")
+        bad = bytes(bad)
+        assert pvk.verify_batch(proofs, bad, flags=pkg.FLAG_RLC) == exp
+        want = bytes(pkg.ERR_NOT_MEMBER if i == j else 1 for i in range(n))
+        assert pvk.verify_batch(proofs, bad, flags=pkg.FLAG_RLC | pkg.FLAG_STRICT_SCALARS) == want == pvk.verify_batch(proofs, bad, flags=pkg.FLAG_STRICT_SCALARS)
+        assert pvk.rlc_state()[0] != -1.0
+    finally:
+        pvk.close()
+
+
+def test_rlc_wide_fallback_in_several_launches(pkg, L):
+    """Every group fails (every other proof invalid, shuffled: the generator's period would leave whole index classes -- groups -- valid): the exact fallback
+    takes about 100 000 proofs of a 17-input key, more than one launch of the wide MSM (G16_WIDE_MSM_MAX_PROOFS = 65 536) -- and the RLC pass itself runs as two
+    launch parts on two streams (from 32 768 proofs)."""
+    n_public, n = 17, 140000
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2545000, n_public, n, invalid_every=2, agree=True, threads=16)
+    proofs, inputs, exp = _shuffle(proofs, inputs, exp, n_public, 5)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        assert pvk.verify_batch(proofs, inputs, flags=pkg.FLAG_RLC) == exp == pvk.verify_batch(proofs, inputs)
+        assert pvk.rlc_state()[0] > 0.9
+    finally:
+        pvk.close()
+
+
+@pytest.mark.skipif("BN254_RLC_WIDE_MIN_BATCH" in __import__("os").environ, reason="the environment replaces the default wide threshold")
+def test_rlc_wide_default_threshold(pkg, L):
+    """At the library's default thresholds a 512-input key takes the mode from about 15 800 proofs (4096 + 6 000 000 / 512, the measured crossover), far below
+    the 200 000 of keys with up to 8 inputs: 8192 proofs run the exact path, 16 384 the RLC pass -- same status bytes either way."""
+    pkg.set_rlc_params(min_batch=200000, adaptive=1)
+    n_public, n = 512, 16384
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2546000, n_public, n, invalid_every=0, agree=True, threads=16)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        h = n // 2
+        assert pvk.verify_batch(proofs[:256 * h], inputs[:32 * n_public * h], h, flags=pkg.FLAG_RLC) == exp[:h]
+        assert pvk.rlc_state()[0] == -1.0
+        assert pvk.verify_batch(proofs, inputs, flags=pkg.FLAG_RLC) == exp
+        assert pvk.rlc_state()[0] == 0.0
+    finally:
+        pvk.close()
