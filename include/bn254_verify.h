@@ -90,8 +90,24 @@ enum { BN254_VK_REFERENCE = 0, BN254_VK_GNARK = 1 };
  *     Adaptive: an RLC pass costs about half an exact pass and every proof of a failed group pays the exact pass on top, so per
  *     (key, device) the share of proofs that fell back is tracked, and while it is above 0.45 the flag is ignored (the exact path
  *     runs: same status bytes) except for one measuring RLC pass every 8 calls.  bn254_set_rlc_params(-1, 0, -1) (or
- *     BN254_RLC_ADAPTIVE=0 in the environment at load time) switches this off; bn254_groth16_rlc_state reports the tracked share (-1: no RLC pass yet) and the number of bypassed calls. */
-enum { BN254_FLAG_STRICT_SCALARS = 1u, BN254_FLAG_RLC = 2u };
+ *     BN254_RLC_ADAPTIVE=0 in the environment at load time) switches this off; bn254_groth16_rlc_state reports the tracked share (-1: no RLC pass yet) and the number of bypassed calls.
+ * BN254_FLAG_COMPRESSED_PROOFS  (Groth16 batch entries only: bn254_groth16_verify_batch, _multi, which passes it to every shard, and _device; the PlonK
+ *     entries refuse it, and bn254_groth16_verify takes no flags) every record starts with gnark's COMPRESSED proof, its default serialisation (WriteTo):
+ *     A (32) | B (64: x.c1 | x.c0, the flag bits in the first byte) | C (32), so proof_stride >= 128; bytes past 128 are ignored.  The points are decompressed
+ *     on the device (one proof per lane) and the raw pipeline runs on the result.  Definition: a compressed record has the status the raw path gives to the
+ *     256-byte record bn254_g1_decompress(A, checked=0) | bn254_g2_decompress(B, BN254_VK_GNARK, checked=0) | bn254_g1_decompress(C, checked=0), except that
+ *     if any of the three decompressions fails the status is BN254_ERR_MALFORMED (it takes precedence over BN254_ERR_INPUT_LEN and the strict-scalar error:
+ *     the reference loads the proof before it prepares the inputs, lib.rs:45).  Consequences:
+ *       - proof points always use gnark's lexicographic root order, whatever mode the key was prepared with (BN254_VK_REFERENCE's c0-only order is a quirk of
+ *         the key loader);
+ *       - decompression is unchecked: B's r-torsion is still tested by the pipeline, so BN254_ERR_NOT_IN_SUBGROUP stays possible;
+ *       - BN254_ERR_NOT_MEMBER and BN254_ERR_NOT_ON_CURVE cannot occur (x >= p is silently reduced, a decoded point lies on its curve);
+ *       - the codec's quirks carry over: flag 0b00 is MALFORMED; the G1 infinity flag is MALFORMED (3 is a non-residue); the G2 infinity flag gives the G2
+ *         generator; an infinity flag with non-zero bits in the rest of its first 32 bytes is MALFORMED.
+ *     Works with BN254_FLAG_RLC and BN254_FLAG_STRICT_SCALARS.  Device scratch: 257 bytes per proof of the largest compressed batch so far (at most 2^20 proofs:
+ *     269 MB), allocated by the first compressed call that needs it -- bn254_groth16_reserve does not reserve it, so before capturing a compressed batch into a
+ *     graph, run one compressed batch of at least that size on the (key, device). */
+enum { BN254_FLAG_STRICT_SCALARS = 1u, BN254_FLAG_RLC = 2u, BN254_FLAG_COMPRESSED_PROOFS = 4u };
 
 typedef struct bn254_g16_pvk bn254_g16_pvk;
 
@@ -109,7 +125,8 @@ void bn254_groth16_vk_free(bn254_g16_pvk* pvk);
 size_t bn254_groth16_vk_num_public(const bn254_g16_pvk* pvk);
 
 /* verify_batch on host buffers.  proofs: n records of proof_stride bytes (>= 256; bytes beyond 256 -- gnark's commitment
- * count / commitments / PoK -- are ignored exactly as in groth16/converter.rs:15-25).  public_inputs: n * n_public * 32 bytes,
+ * count / commitments / PoK -- are ignored exactly as in groth16/converter.rs:15-25; with BN254_FLAG_COMPRESSED_PROOFS: gnark's compressed
+ * proof, >= 128 bytes, bytes beyond 128 ignored).  public_inputs: n * n_public * 32 bytes,
  * big-endian, NOT range-checked and used modulo r exactly like bn::Fr::from_slice + AffineG1 * Fr.
  * status: n bytes.  device: HIP device ordinal. */
 int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride,
@@ -146,7 +163,8 @@ int bn254_groth16_reserve(const bn254_g16_pvk* pvk, size_t n, int device);
 /* Groth16Verifier::verify (lib.rs:44-49) as one call: one proof, one status byte, vk given as bytes on every call like the
  * reference.  The prepared form of the last four keys (exact byte match, per mode) is kept, so only the first call with a key pays
  * its preparation (about 6.5 ms of an 8.5 ms call; 2 ms afterwards: profiles/r05_new_key_cost.txt); BN254_KEY_CACHE=0 in the environment switches the cache off, BN254_KEY_CACHE=N (1 .. 64) keeps the last N keys (default 4).
- * bn254_plonk_verify does the same.  Runs on the GPU (device 0). */
+ * bn254_plonk_verify does the same.  Runs on the GPU (device 0).  The proof is the raw layout only: it takes no flags, so gnark's compressed proofs
+ * (BN254_FLAG_COMPRESSED_PROOFS) go through the batch entries, with n = 1 if need be. */
 int bn254_groth16_verify(const uint8_t* proof, size_t proof_len, const uint8_t* vk, size_t vk_len,
                          const uint8_t* public_inputs, size_t n_public, unsigned mode, uint8_t* status);
 
@@ -329,6 +347,9 @@ int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_gr
  * per launch part {first group, groups}, as the enqueue places them (at most max_parts written, *n_parts = parts) */
 int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, size_t key_inputs, int msm_form, uint64_t alloc[3],
                                 uint64_t* parts_out, int max_parts, int* n_parts);
+/* host compile of k_g16_decompress's body (csrc/bn254_codec.h::g16_decompress_record) over k compressed records at `stride` (>= 128): raw_out receives k raw 256-byte
+ * records, pre_out k bytes (0: decompressed, 1: one of the three points did not decompress -- its raw record is then all ones) */
+int bn254_dbg_g16_decompress(const uint8_t* records, size_t stride, size_t k, uint8_t* raw_out, uint8_t* pre_out);
 /* host compile of the wide RLC group stage (csrc/bn254_rlc.h: rlc_group_scalar, vm_rlc_group_points_wide) on given data: n proofs in the groups of
  * rlc_plan(n, log2_group, log2_share), weights (16 bytes per proof: k1, k2 as little-endian u64, r_i = k1 + k2 lambda mod r), live (n bytes, 0: the proof
  * contributes weight 0), inputs (n x n_public x 32 bytes, big-endian, used modulo r); kpts = K_0 .. K_n_public and alpha64, uncompressed.  *groups_out = groups;

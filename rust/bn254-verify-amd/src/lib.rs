@@ -46,6 +46,11 @@ pub enum VkMode { Reference = 0, Gnark = 1 }
 
 pub const FLAG_STRICT_SCALARS: u32 = sys::BN254_FLAG_STRICT_SCALARS as u32;
 pub const FLAG_RLC: u32 = sys::BN254_FLAG_RLC as u32;
+/// Records are gnark's compressed proofs (A 32 | B 64 | C 32, `proof_stride >= 128`), decompressed on the device; see the header for the status of each record.
+pub const FLAG_COMPRESSED_PROOFS: u32 = sys::BN254_FLAG_COMPRESSED_PROOFS as u32;
+
+/// Smallest Groth16 record the flags allow: 128 bytes for compressed proofs, 256 for the raw layout.
+fn g16_min_stride(flags: u32) -> usize { if flags & FLAG_COMPRESSED_PROOFS != 0 { 128 } else { 256 } }
 
 fn flatten(proofs: &[&[u8]], min_stride: usize) -> (Vec<u8>, usize) {
     let stride = proofs.iter().map(|p| p.len()).max().unwrap_or(min_stride).max(min_stride);
@@ -67,16 +72,17 @@ impl PreparedGroth16Vk {
     pub fn num_public(&self) -> usize { unsafe { sys::bn254_groth16_vk_num_public(self.h) } }
     /// Allocations ahead of the first batch (otherwise the first call makes them).
     pub fn reserve(&self, n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_groth16_reserve(self.h, n, device) }) }
-    /// `n` proofs, `proof_stride` bytes apart (>= 256: A | B | C as gnark writes them), `n_public` 32-byte inputs each; host buffers in, status bytes out.
+    /// `n` proofs, `proof_stride` bytes apart (>= 256: A | B | C as gnark writes them; with `FLAG_COMPRESSED_PROOFS` >= 128: gnark's compressed form), `n_public`
+    /// 32-byte inputs each; host buffers in, status bytes out.
     pub fn verify_batch_raw(&self, proofs: &[u8], proof_stride: usize, public_inputs: &[u8], n_public: usize, n: usize, device: i32, flags: u32) -> Result<Vec<Status>, Error> {
-        assert!(proof_stride >= 256 && proofs.len() >= n * proof_stride && public_inputs.len() >= n * n_public * 32);
+        assert!(proof_stride >= g16_min_stride(flags) && proofs.len() >= n * proof_stride && public_inputs.len() >= n * n_public * 32);
         let mut st = vec![0u8; n];
         check(unsafe { sys::bn254_groth16_verify_batch(self.h, proofs.as_ptr(), proof_stride, public_inputs.as_ptr(), n_public, n, st.as_mut_ptr(), device, flags) })?;
         Ok(st.into_iter().map(Status::from).collect())
     }
     /// The same over the GPUs selected by `device_mask` (contiguous shards, one host thread per device: SURVEY.md section 8(e)).
     pub fn verify_batch_multi_raw(&self, proofs: &[u8], proof_stride: usize, public_inputs: &[u8], n_public: usize, n: usize, device_mask: u64, flags: u32) -> Result<Vec<Status>, Error> {
-        assert!(proof_stride >= 256 && proofs.len() >= n * proof_stride && public_inputs.len() >= n * n_public * 32);
+        assert!(proof_stride >= g16_min_stride(flags) && proofs.len() >= n * proof_stride && public_inputs.len() >= n * n_public * 32);
         let mut st = vec![0u8; n];
         check(unsafe { sys::bn254_groth16_verify_batch_multi(self.h, proofs.as_ptr(), proof_stride, public_inputs.as_ptr(), n_public, n, st.as_mut_ptr(), device_mask, flags) })?;
         Ok(st.into_iter().map(Status::from).collect())
@@ -108,14 +114,20 @@ impl Groth16Verifier {
     }
     /// New: N proofs against one key, one `Status` each; nothing panics.
     pub fn verify_batch(proofs: &[&[u8]], vk: &[u8], public_inputs: &[&[[u8; 32]]]) -> Result<Vec<Status>, Error> {
+        Self::verify_batch_opts(proofs, vk, public_inputs, false)
+    }
+    /// `verify_batch` with the proof layout as an option: `compressed` = gnark's compressed proofs (its default `WriteTo` form, 128 bytes: A | B | C),
+    /// decompressed on the device (`FLAG_COMPRESSED_PROOFS`); a proof that does not decompress is `Status::Malformed`.
+    pub fn verify_batch_opts(proofs: &[&[u8]], vk: &[u8], public_inputs: &[&[[u8; 32]]], compressed: bool) -> Result<Vec<Status>, Error> {
         assert_eq!(proofs.len(), public_inputs.len());
         let pvk = PreparedGroth16Vk::new(vk, VkMode::Reference)?;
-        let (buf, stride) = flatten(proofs, 256);
+        let (flags, min_len) = if compressed { (FLAG_COMPRESSED_PROOFS, 128) } else { (0, 256) };
+        let (buf, stride) = flatten(proofs, min_len);
         let n_public = public_inputs.first().map_or(0, |x| x.len());
         assert!(public_inputs.iter().all(|x| x.len() == n_public), "one input count per batch (a wrong count is a per-key error: InputLen for every proof)");
         let inputs: Vec<u8> = public_inputs.iter().flat_map(|xs| xs.iter().flatten().copied()).collect();
-        let mut st = pvk.verify_batch_raw(&buf, stride, &inputs, n_public, proofs.len(), 0, 0)?;
-        for (s, p) in st.iter_mut().zip(proofs) { if p.len() < 256 { *s = Status::Malformed; } }   // a slice-index panic in the reference
+        let mut st = pvk.verify_batch_raw(&buf, stride, &inputs, n_public, proofs.len(), 0, flags)?;
+        for (s, p) in st.iter_mut().zip(proofs) { if p.len() < min_len { *s = Status::Malformed; } }   // a slice-index panic in the reference
         Ok(st)
     }
 }

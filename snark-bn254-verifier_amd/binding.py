@@ -7,7 +7,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 REJECT, ACCEPT, ERR_NOT_MEMBER, ERR_NOT_ON_CURVE, ERR_NOT_IN_SUBGROUP, ERR_INPUT_LEN, ERR_MALFORMED = range(7)
 VK_REFERENCE, VK_GNARK = 0, 1
-FLAG_STRICT_SCALARS, FLAG_RLC = 1, 2
+FLAG_STRICT_SCALARS, FLAG_RLC, FLAG_COMPRESSED_PROOFS = 1, 2, 4
+COMPRESSED_PROOF_LEN = 128   # gnark's compressed Groth16 proof: A (32) | B (64) | C (32)
 RAW_PROOF_LEN = 324
 NUM_KERNELS = 4
 ABI_VERSION = 5   # include/bn254_verify.h: BN254_ABI_VERSION
@@ -244,6 +245,38 @@ class PlonkVerifier:
         return st.value
 
 
+def _g16_layout(flags, proof_stride, compressed):
+    """(flags, proof_stride) of a Groth16 batch call: compressed=True sets FLAG_COMPRESSED_PROOFS; the default stride is that of the layout."""
+    if compressed:
+        flags |= FLAG_COMPRESSED_PROOFS
+    if proof_stride is None:
+        proof_stride = COMPRESSED_PROOF_LEN if flags & FLAG_COMPRESSED_PROOFS else 256
+    return flags, proof_stride
+
+
+def compress_proof(raw):
+    """gnark's compressed form (128 bytes) of a raw Groth16 proof A (64) | B (128) | C (64): bn254_g1_compress / bn254_g2_compress of the three points."""
+    L = lib()
+    raw = bytes(raw)
+    a, b, c = (C.c_uint8 * 32)(), (C.c_uint8 * 64)(), (C.c_uint8 * 32)()
+    _check(L.bn254_g1_compress(raw[0:64], a))
+    _check(L.bn254_g2_compress(raw[64:192], b))
+    _check(L.bn254_g1_compress(raw[192:256], c))
+    return bytes(a) + bytes(b) + bytes(c)
+
+
+def dbg_g16_decompress(records, k=None, stride=COMPRESSED_PROOF_LEN):
+    """Host compile of k_g16_decompress's body (bn254_dbg_g16_decompress): (k raw 256-byte records, k pre-status bytes: 0 decompressed, 1 MALFORMED)."""
+    L = lib()
+    L.bn254_dbg_g16_decompress.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p]
+    records = bytes(records)
+    if k is None:
+        k = len(records) // stride
+    raw = (C.c_uint8 * max(1, 256 * k))(); pre = (C.c_uint8 * max(1, k))()
+    _check(L.bn254_dbg_g16_decompress(records, stride, k, raw, pre))
+    return bytes(raw)[:256 * k], bytes(pre)[:k]
+
+
 class PreparedVk:
     """Opaque prepared verifying key (bn254_groth16_vk_prepare)."""
 
@@ -256,9 +289,11 @@ class PreparedVk:
     def handle(self):
         return self._h
 
-    def verify_batch(self, proofs, public_inputs, n=None, proof_stride=256, n_public=None, device=0, flags=0):
+    def verify_batch(self, proofs, public_inputs, n=None, proof_stride=None, n_public=None, device=0, flags=0, compressed=False):
         """proofs: bytes (n * proof_stride); public_inputs: bytes (n * n_public * 32). Returns n status bytes.
-        flags: FLAG_STRICT_SCALARS | FLAG_RLC (include/bn254_verify.h)."""
+        flags: FLAG_STRICT_SCALARS | FLAG_RLC (include/bn254_verify.h).  compressed: the records are gnark's compressed proofs (FLAG_COMPRESSED_PROOFS;
+        proof_stride defaults to 128 then, 256 otherwise)."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
         n_public = self.n_public if n_public is None else n_public
         if n is None:
             n = len(proofs) // proof_stride
@@ -266,8 +301,9 @@ class PreparedVk:
         _check(lib().bn254_groth16_verify_batch(self._h, bytes(proofs), proof_stride, bytes(public_inputs), n_public, n, st, device, flags))
         return bytes(st)[:n]
 
-    def verify_batch_multi(self, proofs, public_inputs, device_mask, n=None, proof_stride=256, n_public=None, flags=0):
+    def verify_batch_multi(self, proofs, public_inputs, device_mask, n=None, proof_stride=None, n_public=None, flags=0, compressed=False):
         """Same over the GPUs selected by the bits of device_mask (contiguous shards, one host thread per device)."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
         n_public = self.n_public if n_public is None else n_public
         if n is None:
             n = len(proofs) // proof_stride
@@ -275,8 +311,9 @@ class PreparedVk:
         _check(lib().bn254_groth16_verify_batch_multi(self._h, bytes(proofs), proof_stride, bytes(public_inputs), n_public, n, st, device_mask, flags))
         return bytes(st)[:n]
 
-    def verify_batch_device(self, d_proofs, d_inputs, d_status, n, proof_stride=256, n_public=None, device=0, stream=None, flags=0):
+    def verify_batch_device(self, d_proofs, d_inputs, d_status, n, proof_stride=None, n_public=None, device=0, stream=None, flags=0, compressed=False):
         """Raw device pointers (ints); enqueues on `stream` (a hipStream_t value) and returns (FLAG_RLC: after one stream sync)."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
         n_public = self.n_public if n_public is None else n_public
         _check(lib().bn254_groth16_verify_batch_device(self._h, d_proofs, proof_stride, d_inputs, n_public, n, d_status, device, stream, flags))
 

@@ -17,7 +17,9 @@ int set_err(int code, const std::string& msg) { g_err = msg; return code; }
 // inputs, bn254_groth16_vk_num_public, and n * row would wrap).
 int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* inputs, size_t n_public, size_t n, const void* status,
                      unsigned flags) {
-  if (!pvk || (n && (!proofs || !status)) || (n && n_public && !inputs) || (!plonk && (proof_stride < 256 || (flags & ~3u)))) return set_err(BN254_E_BAD_ARG, "bad argument");
+  // Groth16: raw records of >= 256 bytes, or with BN254_FLAG_COMPRESSED_PROOFS gnark's compressed records of >= 128 bytes
+  const size_t min_stride = (!plonk && (flags & BN254_FLAG_COMPRESSED_PROOFS)) ? 128 : 256;
+  if (!pvk || (n && (!proofs || !status)) || (n && n_public && !inputs) || (!plonk && (proof_stride < min_stride || (flags & ~7u)))) return set_err(BN254_E_BAD_ARG, "bad argument");
   if (plonk && (flags & ~(unsigned)BN254_FLAG_RLC)) return set_err(BN254_E_BAD_ARG, "unknown flag (the PlonK batch entry knows BN254_FLAG_RLC)");
   if (n && (n_public > (SIZE_MAX - proof_stride) / 32 || proof_stride + 32 * n_public > SIZE_MAX / n))
     return set_err(BN254_E_BAD_ARG, "n_public too large: n records of proof_stride + 32 n_public bytes overflow the address space");
@@ -296,4 +298,19 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 #include "bn254_capi_g16.hip"
 #include "bn254_capi_plonk.hip"
 #include "bn254_capi_dbg.hip"
+// Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
+// the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
+hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t in[32], out[64];
+    memcpy(in, src + (size_t)i * stride, 128);
+    pre[i] = g16_decompress_record(in, out) ? 0 : 1;
+    memcpy(raw + (size_t)i * 256, out, 256);
+  }
+  return hipSuccess;
+}
+hipError_t bn254_launch_g16_status_merge(uint8_t* status, const uint8_t* pre, uint32_t n, hipStream_t) {
+  for (uint32_t i = 0; i < n; i++) if (pre[i]) status[i] = BN254_ST_MALFORMED;
+  return hipSuccess;
+}
 #endif

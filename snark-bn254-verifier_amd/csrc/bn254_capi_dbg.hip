@@ -92,6 +92,17 @@ struct LazyWindows {   // entry d of window w of P: (d + 1) 2^(MSM_FW_BITS w) P,
   }
 };
 }  // namespace
+// BN254_FLAG_COMPRESSED_PROOFS: the body of k_g16_decompress (bn254_codec.h), compiled for the host, over k records
+int bn254_dbg_g16_decompress(const uint8_t* records, size_t stride, size_t k, uint8_t* raw_out, uint8_t* pre_out) {
+  if ((k && (!records || !raw_out || !pre_out)) || stride < 128) return set_err(BN254_E_BAD_ARG, "bad argument");
+  for (size_t i = 0; i < k; i++) {
+    uint32_t in[32], out[64];
+    memcpy(in, records + i * stride, 128);
+    pre_out[i] = g16_decompress_record(in, out) ? 0 : 1;
+    memcpy(raw_out + i * 256, out, 256);
+  }
+  return BN254_OK;
+}
 int bn254_dbg_rlc_wide_group(const uint8_t* kpts, const uint8_t alpha64[64], const uint8_t* weights, const uint8_t* live, const uint8_t* inputs, size_t n_public, size_t n,
                              int log2_group, int log2_share, unsigned group, uint8_t* scalars_out, unsigned* groups_out, uint8_t l_out[64]) {
   if (!groups_out || n == 0 || n > (size_t)G16_MAX_LAUNCH || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > log2_group || log2_share > 3 || (n >> log2_share) == 0)

@@ -89,6 +89,17 @@ int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n) {
   }
   return BN254_OK;
 }
+// BN254_FLAG_COMPRESSED_PROOFS: the decompression scratch for a batch of n proofs (caller holds d.mu).  Grown here, by the entry points before they enqueue,
+// never by the enqueue path: a compressed batch allocates only when it is larger than every compressed batch before it on this (key, device)
+static int ensure_cmp(DevState& d, size_t n) {
+  const G16CmpAlloc need = g16_cmp_alloc(n);
+  if (need.proofs <= d.cmp_cap) return BN254_OK;
+  if (d.cmp) HIPCK(hipFree(d.cmp));   // hipFree waits for the device: no batch is still using the old scratch
+  d.cmp = nullptr; d.cmp_cap = 0;
+  HIPCK(hipMalloc((void**)&d.cmp, need.raw_bytes + need.pre_bytes));
+  d.cmp_cap = need.proofs;
+  return BN254_OK;
+}
 static int ensure_aux(DevState& d, int count) {
   if (count > 3) count = 3;
   if (!d.fork_ev) {
@@ -103,7 +114,7 @@ static inline hipStream_t part_stream(DevState& d, hipStream_t user, int pi) { c
 static void dev_free(DevState& d) {
   int32_t* ptrs[] = {d.k0, d.gtab, d.dtab, d.target, d.msm, d.ws, d.msm_part};
   for (auto q : ptrs) if (q) (void)hipFree(q);
-  uint8_t* bp[] = {d.st_proofs, d.st_inputs, d.st_status};
+  uint8_t* bp[] = {d.st_proofs, d.st_inputs, d.st_status, d.cmp};
   for (auto q : bp) if (q) (void)hipFree(q);
   if (d.ev_ready) { for (int i = 0; i < 5; i++) (void)hipEventDestroy(d.ev[i]); for (auto& e : d.prof_ev) (void)hipEventDestroy(e); for (auto& e : d.prof2_ev) (void)hipEventDestroy(e); }
   for (int i = 0; i < d.aux_count; i++) (void)hipStreamDestroy(d.aux[i]);
@@ -426,6 +437,32 @@ static bool rlc_eligible(const bn254_g16_pvk* pvk, size_t n_public, size_t n, un
   if (n_public > (size_t)RLC_MAX_PUBLIC) { const long wide_from = rlc_wide_pays_from(n_public); if (wide_from < from) from = wide_from; }
   return (flags & BN254_FLAG_RLC) && pvk->host.inputs_match(n_public) && n >= (size_t)from;
 }
+// BN254_FLAG_COMPRESSED_PROOFS, chunk by chunk (at most G16_MAX_BATCH proofs, the chunk of both pipelines): k_g16_decompress writes the raw records and the
+// pre-status bytes into the scratch, the raw pipeline chosen for the whole batch runs on the scratch at stride 256 with the flag cleared, and k_g16_status_merge
+// makes MALFORMED override.  A record that does not decompress becomes all ones, which the loader refuses with NOT_MEMBER at its first test: the proof is then
+// no longer pending, so it contributes the neutral element to its RLC group and never sends the group to the exact fallback.  Everything is enqueued on `user`
+// (the sub-batch streams of the exact path join it), so the next chunk's decompression overwrites the scratch only after this chunk is done with it.
+static int g16_enqueue_compressed(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
+                                  size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags, bool rlc) {
+  const unsigned raw_flags = flags & ~(unsigned)BN254_FLAG_COMPRESSED_PROOFS;
+  for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
+    const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
+    if (g16_cmp_alloc(m).proofs > d->cmp_cap) return set_err(BN254_E_BAD_ARG, "decompression scratch smaller than the batch (internal sizing error)");
+    uint8_t* raw = d->cmp;
+    uint8_t* pre = d->cmp + d->cmp_cap * 256;
+    uint8_t* st = (uint8_t*)d_status + off;
+    const uint8_t* in = (const uint8_t*)d_inputs + off * n_public * 32;
+    hipError_t e = bn254_launch_g16_decompress((const uint8_t*)d_proofs + off * proof_stride, proof_stride, (uint32_t)m, raw, pre, user);
+    if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
+                                         std::string("kernel launch (decompress): ") + hipGetErrorString(e));
+    int rc = rlc ? g16_enqueue_rlc(pvk, d, device, raw, 256, in, n_public, m, st, user, raw_flags)
+                 : g16_enqueue_exact(pvk, d, raw, 256, in, n_public, m, st, user, raw_flags);
+    if (rc) return rc;
+    e = bn254_launch_g16_status_merge(st, pre, (uint32_t)m, user);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("kernel launch (status merge): ") + hipGetErrorString(e));
+  }
+  return BN254_OK;
+}
 // one batch on `user`: waits for the previous batch of this (key, device), runs the exact or the RLC pipeline, records busy_ev.
 // use_rlc: -1 = decide here; 0 / 1 = the caller (the host-buffer entry, which must know before it cuts the batch into chunks) has decided
 static int g16_enqueue(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
@@ -435,7 +472,8 @@ static int g16_enqueue(const bn254_g16_pvk* pvk, DevState* d, int device, const 
   // BN254_FLAG_RLC is honoured where it pays: from RLC_PAYS_FROM proofs (bn254_set_rlc_params / BN254_RLC_MIN_BATCH at load time move the
   // threshold: the tests run the mode on small batches); smaller batches take the exact path -- same status bytes
   const bool rlc = use_rlc >= 0 ? use_rlc != 0 : (rlc_eligible(pvk, n_public, n, flags) && !rlc_bypass(d->rlc));
-  if (rlc) rc = g16_enqueue_rlc(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
+  if (flags & BN254_FLAG_COMPRESSED_PROOFS) rc = g16_enqueue_compressed(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags, rlc);
+  else if (rlc) rc = g16_enqueue_rlc(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
   else rc = g16_enqueue_exact(pvk, d, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
   if (rc) return rc;
   HIPCK(hipEventRecord(d->busy_ev, user));
@@ -452,6 +490,7 @@ int bn254_groth16_verify_batch_device(const bn254_g16_pvk* pvk, const void* d_pr
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
   if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
+  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
   return g16_enqueue(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, (hipStream_t)hip_stream, flags);
 }
 
@@ -583,6 +622,7 @@ int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, 
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
   if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
+  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
   const size_t in_row = n_public * 32, row = proof_stride + in_row;
   size_t pb = n * proof_stride, ib = n * in_row;
   if ((rc = grow(&d->st_proofs, &d->st_proofs_cap, pb)) || (rc = grow(&d->st_inputs, &d->st_inputs_cap, ib ? ib : 32)) ||

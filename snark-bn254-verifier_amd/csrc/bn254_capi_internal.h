@@ -86,6 +86,9 @@ struct DevState {
   // the same for the SECOND sub-batch (its launches run on another stream beside the first's): bn254_groth16_kernel_profile_all
   std::vector<hipEvent_t> prof2_ev; std::vector<uint8_t> prof2_kid; G16Prof prof2{0, nullptr, nullptr, 0, 0}; bool prof2_used = false;
   RlcDev rlc;                                                       // BN254_FLAG_RLC buffers (bn254_rlc.hpp)
+  // BN254_FLAG_COMPRESSED_PROOFS: raw records of the decompressed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_cmp_alloc); grown at the
+  // first compressed batch that needs more (cmp_cap proofs)
+  uint8_t* cmp = nullptr; size_t cmp_cap = 0;
   // do the sub-batch streams overlap?  ov_ev: start / end of part 0 and of part 1 of the first two-stream batch; ov_state 0: not measured, 1: events recorded,
   // 2: measured (ov_ratio = sum of the two durations / their union: ~2 side by side, ~1 one after the other); single_stream: fall back to one sub-batch per launch
   hipEvent_t ov_ev[4] = {nullptr, nullptr, nullptr, nullptr}; int ov_state = 0; float ov_ratio = -1.f; bool single_stream = false;

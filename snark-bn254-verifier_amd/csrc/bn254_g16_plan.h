@@ -142,4 +142,18 @@ inline G16RlcWide g16_rlc_wide_alloc(size_t groups, size_t key_inputs, int msm_f
   return a;
 }
 
+// ---- BN254_FLAG_COMPRESSED_PROOFS: the decompression scratch of a (key, device) ------------------------------------------------------------------------------
+// A compressed batch is decompressed and verified in chunks of at most G16_MAX_BATCH proofs (the chunk of the exact and the RLC paths): per proof one raw
+// 256-byte record and one pre-status byte.  g16_cmp_alloc(n) is what a batch of n proofs needs (the pre bytes start at raw_bytes, a multiple of 256);
+// ensure_cmp grows the scratch to it and the enqueue checks every chunk against it.
+inline size_t g16_cmp_chunk(size_t n) { return n < (size_t)G16_MAX_BATCH ? n : (size_t)G16_MAX_BATCH; }
+struct G16CmpAlloc { size_t proofs, raw_bytes, pre_bytes; };
+inline G16CmpAlloc g16_cmp_alloc(size_t n) {
+  G16CmpAlloc a;
+  a.proofs = g16_round256(g16_cmp_chunk(n));
+  a.raw_bytes = a.proofs * 256;
+  a.pre_bytes = a.proofs;
+  return a;
+}
+
 }  // namespace bn254

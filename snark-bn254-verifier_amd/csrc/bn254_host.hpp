@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 #include "bn254_vm.h"
+#include "bn254_codec.h"
 #include "bn254_kernels.h"
 
 namespace bn254host {
@@ -25,94 +26,9 @@ inline void fp_to_limbs(int32_t* out, const Fp& a) {
 inline Fp fp_from_be(const uint8_t* be32) { uint32_t w[8]; words_from_be(w, be32); return fp_from_words(w); }
 inline void fp_to_be(uint8_t* be32, const Fp& a) { uint32_t w[8]; fp_to_words(w, a); words_to_be(be32, w); }
 inline bool be_lt_p(const uint8_t* be32) { uint32_t w[8]; words_from_be(w, be32); return !words_ge(w, BN_P_WORDS); }
-inline bool fp_is_large(const Fp& a) {  // canonical value > (p-1)/2
-  uint32_t w[8]; fp_to_words(w, a);
-  bool ge = words_ge(w, BN_P_HALF_WORDS);
-  bool eq = true; for (int i = 0; i < 8; i++) eq &= (w[i] == BN_P_HALF_WORDS[i]);
-  return ge && !eq;
-}
-inline int fp_cmp_canon(const Fp& a, const Fp& b) {
-  uint32_t x[8], y[8]; fp_to_words(x, a); fp_to_words(y, b);
-  for (int i = 7; i >= 0; i--) { if (x[i] < y[i]) return -1; if (x[i] > y[i]) return 1; }
-  return 0;
-}
-inline bool fp_sqrt(Fp& out, const Fp& a) {  // p = 3 mod 4
-  Fp r = fp_pow_bits(fp_reduce(fp_norm(a)), BN_EXP_SQRT_BITS, BN_EXP_SQRT_NBITS);
-  if (!fp_eq(fp_sqr(r), a)) return false;
-  out = r;
-  return true;
-}
-inline Fp2 fp2_pow_bits(const Fp2& a, const uint8_t* bits, int nbits) {
-  Fp2 acc = a;
-  for (int i = 1; i < nbits; i++) { acc = fp2_sqr(acc); if (bits[i]) acc = fp2_mul(acc, a); }
-  return acc;
-}
-// square root in Fp2 = Fp[i]/(i^2+1), p = 3 mod 4 (complex method); which root comes back is unspecified
-inline bool fp2_sqrt(Fp2& out, const Fp2& a) {
-  if (fp2_is_zero(a)) { out = fp2_zero(); return true; }
-  Fp2 a1 = fp2_pow_bits(a, BN_EXP_PM3O4_BITS, BN_EXP_PM3O4_NBITS);
-  Fp2 alpha = fp2_mul(fp2_sqr(a1), a);
-  Fp2 a0 = fp2_mul(fp2_conj(alpha), alpha);
-  Fp2 minus_one; minus_one.c0 = fp_neg(fp_one()); minus_one.c1 = fp_zero();
-  if (fp2_eq(a0, minus_one)) return false;
-  Fp2 x0 = fp2_mul(a1, a), r;
-  if (fp2_eq(alpha, minus_one)) { r.c0 = fp_neg(x0.c1); r.c1 = x0.c0; }
-  else { Fp2 b = fp2_pow_bits(fp2_add(alpha, fp2_one()), BN_EXP_PM1O2_BITS, BN_EXP_PM1O2_NBITS); r = fp2_mul(b, x0); }
-  if (!fp2_eq(fp2_sqr(r), a)) return false;
-  out = r;
-  return true;
-}
-inline bool fp2_lex_large(const Fp2& y) { return fp_is_zero(y.c1) ? fp_is_large(y.c0) : fp_is_large(y.c1); }  // gnark's LexicographicallyLargest
-
 // ---------------------------------------------------------------- gnark codecs
-enum { DEC_OK = 0, DEC_MALFORMED = 1 };
-// converter.rs:23-43: flag in the top two bits, x silently reduced mod p, infinity must be all zero, flag 0b00 panics
-inline int deserialize_with_flags(Fp& x, int& flag, const uint8_t* b32) {
-  int m = b32[0] >> 6;
-  if (m == 0) return DEC_MALFORMED;
-  if (m == 1) {
-    if (b32[0] & 0x3f) return DEC_MALFORMED;
-    for (int i = 1; i < 32; i++) if (b32[i]) return DEC_MALFORMED;
-    x = fp_zero(); flag = 1; return DEC_OK;
-  }
-  uint8_t t[32]; memcpy(t, b32, 32); t[0] &= 0x3f;
-  x = fp_from_be(t);  // fp_from_words reduces any 256-bit value mod p
-  flag = m;
-  return DEC_OK;
-}
-// converter.rs:62-76 (unchecked): y = sqrt(x^3+3), flag 10 -> smaller root, 11 -> larger; the infinity flag falls through
-// with x = 0, and 3 is a non-residue mod p, so it ends in InvalidPoint (a panic in the reference)
-inline int dec_g1_compressed(G1Aff& o, const uint8_t* b32) {
-  Fp x; int flag;
-  if (deserialize_with_flags(x, flag, b32) != DEC_OK) return DEC_MALFORMED;
-  Fp y;
-  if (!fp_sqrt(y, fp_add(fp_mul(fp_sqr(x), x), fp_from_limbs(BN_THREE)))) return DEC_MALFORMED;
-  Fp ny = fp_neg(y);
-  if (fp_cmp_canon(y, ny) > 0) { Fp s = y; y = ny; ny = s; }
-  o.x = x; o.y = (flag == 3) ? ny : y;
-  return DEC_OK;
-}
-// converter.rs:113-133 (unchecked).  mode 0 (reference): the two roots are ordered by the real part c0 alone, as the pinned
-// `bn` does, flag 10 -> first; mode 1 (gnark): flag 10 -> lexicographically smallest.  The infinity flag
-// yields the G2 GENERATOR (AffineG2::one(), converter.rs:122-124).
-inline int dec_g2_compressed(G2Aff& o, const uint8_t* b64, int mode) {
-  Fp x1; int flag;
-  if (deserialize_with_flags(x1, flag, b64) != DEC_OK) return DEC_MALFORMED;
-  Fp x0 = fp_from_be(b64 + 32);
-  if (flag == 1) {
-    o.x.c0 = fp_from_limbs(BN_G2_GEN[0]); o.x.c1 = fp_from_limbs(BN_G2_GEN[1]);
-    o.y.c0 = fp_from_limbs(BN_G2_GEN[2]); o.y.c1 = fp_from_limbs(BN_G2_GEN[3]);
-    return DEC_OK;
-  }
-  Fp2 x; x.c0 = x0; x.c1 = x1;
-  Fp2 y;
-  if (!fp2_sqrt(y, fp2_add(fp2_mul(fp2_sqr(x), x), g2_twist_b()))) return DEC_MALFORMED;
-  Fp2 ny = fp2_neg(y);
-  bool y_first = (mode == 0) ? (fp_cmp_canon(y.c0, ny.c0) < 0) : !fp2_lex_large(y);
-  o.x = x;
-  o.y = (flag == 2) ? (y_first ? y : ny) : (y_first ? ny : y);
-  return DEC_OK;
-}
+// the square roots, root orderings and the compressed-point decoders (dec_g1_compressed / dec_g2_compressed) live in bn254_codec.h, shared with
+// k_g16_decompress; the encoders stay here
 inline void enc_g1_uncompressed(uint8_t* b64, const G1Aff& p) { fp_to_be(b64, p.x); fp_to_be(b64 + 32, p.y); }
 inline void enc_g2_uncompressed(uint8_t* b, const G2Aff& p) { fp_to_be(b, p.x.c1); fp_to_be(b + 32, p.x.c0); fp_to_be(b + 64, p.y.c1); fp_to_be(b + 96, p.y.c0); }
 inline void enc_g1_compressed(uint8_t* b32, const G1Aff& p) { fp_to_be(b32, p.x); b32[0] |= fp_is_large(p.y) ? 0xc0 : 0x80; }

@@ -126,6 +126,10 @@ struct RlcLaunchArgs {
 hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, hipStream_t s);
 hipError_t bn254_launch_gather_rows(uint8_t* dst, const uint8_t* src, size_t src_stride, uint32_t row_bytes, const uint32_t* idx, uint32_t m, hipStream_t s);
 hipError_t bn254_launch_scatter_status(uint8_t* status, const uint8_t* fb_status, const uint32_t* idx, uint32_t m, hipStream_t s);
+// BN254_FLAG_COMPRESSED_PROOFS (bn254_codec.h): n <= G16_MAX_BATCH compressed records at `stride` -> n raw 256-byte records in raw and n pre-status bytes
+// (0 decompressed, 1 MALFORMED); after the raw pipeline, k_g16_status_merge writes MALFORMED over the status of every proof whose pre byte is set
+hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t s);
+hipError_t bn254_launch_g16_status_merge(uint8_t* status, const uint8_t* pre, uint32_t n, hipStream_t s);
 #define G1_GLV_TAB_BYTES_PER_LANE (16 * 28 * 4)
 // PlonK's G1 multi-scalar multiplications as rows of a plan (bn254_msm.h, bn254_k_msm.hip)
 namespace bn254 { struct MsmPlan; }

@@ -25,6 +25,7 @@
 #include "bn254_devws.h"
 #include "bn254_rlc.h"
 #include "bn254_g16_plan.h"
+#include "bn254_codec.h"
 
 namespace bn254 {
 
@@ -687,6 +688,33 @@ __global__ void k_scatter_status(uint8_t* __restrict__ status, const uint8_t* __
   const uint32_t k = blockIdx.x * 256u + threadIdx.x;
   if (k < m) status[idx[k]] = fb_status[k];
 }
+// BN254_FLAG_COMPRESSED_PROOFS: one compressed record per lane (bn254_codec.h::g16_decompress_record, the code bn254_dbg_g16_decompress runs on the
+// host) -> the 256-byte raw record at raw + 256 i, and pre[i] = 1 if it did not decompress (its raw record is then all ones, which the loader answers with
+// NOT_MEMBER; k_g16_status_merge turns the final status into MALFORMED).  About 1 900 field products per lane (two Fp roots, one Fp2 root): compute-bound,
+// so the 128-byte record is simply loaded per lane -- four 16-byte loads when the records are 16-byte aligned (stride 128), bytes otherwise.
+__global__ void __launch_bounds__(256, 2) k_g16_decompress(const uint8_t* __restrict__ src, size_t stride, uint32_t n, uint8_t* __restrict__ raw, uint8_t* __restrict__ pre) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* p = src + (size_t)i * stride;
+  uint32_t in[32], out[64];
+  if (((((uintptr_t)src) | stride) & 15) == 0) {   // wave-uniform
+#pragma unroll
+    for (int k = 0; k < 8; k++) { const uint4 v = ((const uint4*)p)[k]; in[4 * k] = v.x; in[4 * k + 1] = v.y; in[4 * k + 2] = v.z; in[4 * k + 3] = v.w; }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 32; k++) in[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+  }
+  const bool ok = g16_decompress_record(in, out);
+  uint4* q = (uint4*)(raw + (size_t)i * 256);
+#pragma unroll
+  for (int k = 0; k < 16; k++) q[k] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
+  pre[i] = ok ? 0 : 1;
+}
+// after the raw pipeline over the decompressed records: a record that did not decompress is MALFORMED, whatever the loader said about its all-ones stand-in
+__global__ void __launch_bounds__(256) k_g16_status_merge(uint8_t* __restrict__ status, const uint8_t* __restrict__ pre, uint32_t n) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n && pre[i]) status[i] = BN254_ST_MALFORMED;
+}
 
 // =====================================================================================================================
 // the issue rate of the instruction every field product is made of, measured on THIS device: sixteen independent v_mad_u64_u32 chains per lane, two
@@ -999,6 +1027,14 @@ hipError_t bn254_launch_gather_rows(uint8_t* dst, const uint8_t* src, size_t src
 }
 hipError_t bn254_launch_scatter_status(uint8_t* status, const uint8_t* fb_status, const uint32_t* idx, uint32_t m, hipStream_t s) {
   if (m) hipLaunchKernelGGL(k_scatter_status, dim3(grid_for(m)), dim3(256), 0, s, status, fb_status, idx, m);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_g16_decompress, dim3(grid_for(n)), dim3(256), 0, s, src, stride, n, raw, pre);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_g16_status_merge(uint8_t* status, const uint8_t* pre, uint32_t n, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_g16_status_merge, dim3(grid_for(n)), dim3(256), 0, s, status, pre, n);
   return hipGetLastError();
 }
 // lane-level multiply-adds per second of the current device: the best launch of k_valu_peak at four wavefronts per SIMD, each about 2 ms long (a

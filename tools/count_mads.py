@@ -98,6 +98,10 @@ def short(sym):
 # ---- loop models: a loop is recognised by the multiply-adds of one iteration --------------------------------------------------------------------
 FP_SQR, FP_MUL = 126, 162            # fp_sqr: 45 + 81; fp_mul: 81 + 81 (bn254_fp.h)
 INV_SET_BITS = PM2_BITS.count("1") - 1
+# the square roots of k_g16_decompress (bn254_codec.h, BN254_FLAG_COMPRESSED_PROOFS): fp_pow_bits by (p+1)/4 (fp_sqrt, twice: A and C) and fp2_pow_bits by
+# (p-3)/4 and (p-1)/2 (fp2_sqrt, in this order in the code object: B); each loop squares once per bit after the first and multiplies on set bits
+SQRT_EXPONENTS = {"fp": [bin((P + 1) // 4)[2:]], "fp2": [bin((P - 3) // 4)[2:], bin((P - 1) // 2)[2:]]}
+FP2_SQR_MADS, FP2_POW_STEP_MADS = 324, 810   # fp2_sqr; fp2_sqr + fp2_mul
 INV_GCD_ROUND_MADS = 90               # fp_inv: (a, b) and (u, v) updates of one round: 4 x 18 digit products + 2 x 9 for the Montgomery digit
 N_PUBLIC = 2                          # BASELINE configs[2]
 TRIPS_BY_KERNEL = {                   # loops whose trip count is a launch parameter: (kernel, mads of one iteration) -> trips, why
@@ -210,7 +214,14 @@ def model_kernel(name, ins):
         inner = [g for g in groups if g is not (h, latches, c) and h <= g[0] and g[1][-1] <= latches[-1] and (g[0], g[1][-1]) != (h, latches[-1])]
         own = c - sum(g[2] for g in inner if not any(o is not g and o[0] <= g[0] and g[1][-1] <= o[1][-1] and o in inner for o in inner))
         first = count_in(mads, h, latches[0])
-        if len(latches) == 2 and first == FP_SQR and c == FP_SQR + FP_MUL:
+        if name == "k_g16_decompress" and len(latches) == 2 and ((first, c) == (FP_SQR, FP_SQR + FP_MUL) or (first, c) == (FP2_SQR_MADS, FP2_POW_STEP_MADS)):
+            kind = "fp" if c == FP_SQR + FP_MUL else "fp2"
+            k = sum(1 for g in groups if g[0] < h and count_in(mads, g[0], g[1][0]) == first and g[2] == c and len(g[1]) == 2)   # earlier loops of this kind
+            bits = SQRT_EXPONENTS[kind][k % len(SQRT_EXPONENTS[kind])]
+            weight_ranges.append((h, latches[0], float(len(bits) - 1)))
+            weight_ranges.append((latches[0] + 1, latches[1], float(bits.count("1") - 1)))
+            notes.append("%s square-root exponentiation: %d squarings + %d products" % (kind, len(bits) - 1, bits.count("1") - 1))
+        elif len(latches) == 2 and first == FP_SQR and c == FP_SQR + FP_MUL:
             # fp_pow_bits with the exponent p - 2: a squaring per bit, a product on set bits (second latch region)
             weight_ranges.append((h, latches[0], float(INV_SQUARINGS)))
             weight_ranges.append((latches[0] + 1, latches[1], float(INV_SET_BITS)))
