@@ -249,6 +249,44 @@ int bn254_g2_decompress(const uint8_t in[64], uint8_t out[128], unsigned mode, i
 int bn254_sp1_fixture_parse(const uint8_t* buf, size_t len, int* variant, uint8_t* raw_proof, size_t raw_cap, size_t* raw_len,
                             uint8_t public_inputs[64], uint8_t vkey_hash[32]);
 
+/* ---- SP1 proofs from their public values ---------------------------------------------------------------------------------------------------------------
+ * An SP1 proof (SP1ProofWithPublicValues) is verified against the two circuit inputs vkey_hash | committed_values_digest (examples/script/src/main.rs:115-138),
+ * and the caller holds the program's public values, not the digest:
+ *     committed_values_digest = SHA-256(public_values) with the top three bits of byte 0 cleared.
+ * bn254_sp1_public_values_digest computes it on the host.  The batch entries below compute it on the device, one proof per lane, and then run the unchanged
+ * Groth16 or PlonK pipeline.  One SP1 circuit key serves every program of its SP1 version (the programs differ in vkey_hash, input 0), so one batch against
+ * one prepared key may hold proofs of many programs.
+ * Definition, for proof i of a batch of n:
+ *   - its public values are the bytes [pv_offsets[i], pv_offsets[i+1]) of public_values; pv_offsets has n + 1 entries.  The offsets are absolute: a caller
+ *     shards a batch by passing pv_offsets + first (and proofs, vkey hashes, status moved by `first` records) with the same public_values pointer;
+ *   - its vkey hash is the 32 bytes at vkey_hashes + i * vkey_stride (big-endian, as bn254_sp1_fixture_parse writes it).  vkey_stride 0: one hash for the
+ *     whole batch; any other stride must be at least 32;
+ *   - its status is the status the matching RAW batch entry (bn254_groth16_verify_batch[_device], bn254_plonk_verify_batch_flags / _device) returns for the
+ *     same proof record with n_public = 2 and the input row vkey_hash_i | digest_i, under the same flags: BN254_FLAG_STRICT_SCALARS (a vkey hash >= r is
+ *     BN254_ERR_NOT_MEMBER; a digest is < 2^253 < r), BN254_FLAG_RLC and, for Groth16, BN254_FLAG_COMPRESSED_PROOFS.  A key whose width is not 2 therefore
+ *     gives BN254_ERR_INPUT_LEN (or a loader status), as the raw entry does;
+ *   - bad ranges.  Host-buffer entries read pv_offsets on the host: decreasing offsets are BN254_E_BAD_ARG before any device is touched.  The device entries
+ *     take pv_bytes, the size of the buffer at d_public_values, and never read outside [0, pv_bytes): a proof with off[i] > off[i+1] or off[i+1] > pv_bytes
+ *     gets BN254_ERR_MALFORMED, which overrides its pipeline status (the precedence of compressed records that do not decompress).
+ * Every argument error (NULL pointers with n > 0, vkey_stride 1 .. 31, an unknown flag, STRICT or COMPRESSED on the PlonK entries, decreasing host offsets)
+ * is BN254_E_BAD_ARG, reported before any device is touched; n = 0 returns BN254_OK.
+ * The Groth16 entries hash into a per-(key, device) row scratch of 65 bytes per proof of the largest SP1 batch so far (chunks of at most 2^20 proofs: 68 MB),
+ * allocated by the first SP1 call that needs it -- bn254_groth16_reserve does not reserve it, so before capturing an SP1 batch into a graph, run one SP1
+ * batch of at least that size on the (key, device).  The host entry also stages the values, offsets and vkey hashes in per-(key, device) buffers.
+ * bn254_sp1_groth16_verify_batch_device enqueues on hip_stream like bn254_groth16_verify_batch_device.  The PlonK entries keep the rows in memory of the
+ * call (calls on one key run side by side), and bn254_sp1_plonk_verify_batch_device is host-synchronous like bn254_plonk_verify_batch_device. */
+int bn254_sp1_public_values_digest(const uint8_t* public_values, size_t len, uint8_t out[32]);
+int bn254_sp1_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* vkey_hashes, size_t vkey_stride,
+                                   const uint8_t* public_values, const uint64_t* pv_offsets, size_t n, uint8_t* status, int device, unsigned flags);
+int bn254_sp1_groth16_verify_batch_device(const bn254_g16_pvk* pvk, const void* d_proofs, size_t proof_stride, const void* d_vkey_hashes, size_t vkey_stride,
+                                          const void* d_public_values, size_t pv_bytes, const uint64_t* d_pv_offsets, size_t n, void* d_status, int device,
+                                          void* hip_stream, unsigned flags);
+int bn254_sp1_plonk_verify_batch(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* vkey_hashes, size_t vkey_stride,
+                                 const uint8_t* public_values, const uint64_t* pv_offsets, size_t n, uint8_t* status, int device, unsigned flags);
+int bn254_sp1_plonk_verify_batch_device(const bn254_plonk_pvk* pvk, const void* d_proofs, size_t proof_stride, const void* d_vkey_hashes, size_t vkey_stride,
+                                        const void* d_public_values, size_t pv_bytes, const uint64_t* d_pv_offsets, size_t n, void* d_status, int device,
+                                        void* hip_stream, unsigned flags);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * A sub-batch above COOP12_MAX_PROOFS runs as about 120 kernel launches: k_g16_prepare, k_vm_init, the whole Miller loop as ONE k_miller_run (or a few, g16_launch_form),
  * k_g16_subgroup, one launch per Fp12-level operation of the final exponentiation (k_f12_mul x 60, k_f12_cyclo_sqr_n x 39, ...) and k_g16_compare; up to
@@ -303,6 +341,9 @@ int bn254_synth_groth16(uint64_t seed, size_t n_public, size_t n, int invalid_ev
  * generates just its own contiguous shard; the key is the same for every range */
 int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size_t n, int invalid_every, int agree, int threads,
                               uint8_t* vk_out, uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected_status_out);
+/* the key of bn254_synth_groth16(seed, n_public, .., agree = 1, ..) and, for n given input rows (n x n_public x 32 bytes, big-endian, used modulo r), one valid
+ * 256-byte raw proof per row: the SP1 tests need proofs for inputs they cannot choose (a digest) */
+int bn254_synth_groth16_for_inputs(uint64_t seed, size_t n_public, size_t n, const uint8_t* inputs, int threads, uint8_t* vk_out, uint8_t* proofs_out);
 
 /* ---- probes of the device arithmetic, used by the GPU parity tests (tests/test_gpu_*.py) ---------------------------
  * Each runs one lane per item on `device` and copies the result back.  Fp12 layout: 12 x 32 bytes in tower order
@@ -350,6 +391,14 @@ int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log
 /* host compile of k_g16_decompress's body (csrc/bn254_codec.h::g16_decompress_record) over k compressed records at `stride` (>= 128): raw_out receives k raw 256-byte
  * records, pre_out k bytes (0: decompressed, 1: one of the three points did not decompress -- its raw record is then all ones) */
 int bn254_dbg_g16_decompress(const uint8_t* records, size_t stride, size_t k, uint8_t* raw_out, uint8_t* pre_out);
+/* the body of k_sp1_public_inputs (csrc/bn254_sha256.h) over n proofs, with the device entries' range rule (pv_bytes): rows_out receives n rows vkey_hash | digest
+ * (64 bytes each), bad_out n bytes (1: the range is not inside [0, pv_bytes) -- the row then holds the digest of the empty string).  device -1: compiled for
+ * the host; device >= 0: the kernel on that device */
+int bn254_dbg_sp1_public_inputs(const uint8_t* vkey_hashes, size_t vkey_stride, const uint8_t* public_values, size_t pv_bytes, const uint64_t* pv_offsets, size_t n,
+                                uint8_t* rows_out, uint8_t* bad_out, int device);
+/* the row scratch an SP1 Groth16 batch of n proofs needs (csrc/bn254_g16_plan.h::g16_sp1_alloc): out = {proofs it holds, bytes of rows (the pre bytes start there),
+ * bytes of pre-status bytes} */
+int bn254_dbg_g16_sp1_alloc(size_t n, uint64_t out[3]);
 /* host compile of the wide RLC group stage (csrc/bn254_rlc.h: rlc_group_scalar, vm_rlc_group_points_wide) on given data: n proofs in the groups of
  * rlc_plan(n, log2_group, log2_share), weights (16 bytes per proof: k1, k2 as little-endian u64, r_i = k1 + k2 lambda mod r), live (n bytes, 0: the proof
  * contributes weight 0), inputs (n x n_public x 32 bytes, big-endian, used modulo r); kpts = K_0 .. K_n_public and alpha64, uncompressed.  *groups_out = groups;

@@ -119,6 +119,28 @@ inline Bytes pack(const std::vector<Bytes>& proofs, size_t min_len, size_t* stri
 }
 }  // namespace detail
 
+namespace detail {
+// the host buffers of an SP1 batch: values concatenated, n + 1 offsets, vkey hashes (one for all: stride 0; one per proof: stride 32)
+struct Sp1Buffers {
+  Bytes pv, vk; std::vector<uint64_t> offs; size_t n, stride;
+  Sp1Buffers(const std::vector<std::array<uint8_t, 32>>& vkey_hashes, const std::vector<Bytes>& public_values) : n(public_values.size()) {
+    if (vkey_hashes.size() != 1 && vkey_hashes.size() != n) throw std::invalid_argument("one vkey hash, or one per proof");
+    offs.reserve(n + 1);
+    for (const Bytes& v : public_values) { offs.push_back(pv.size()); pv.insert(pv.end(), v.begin(), v.end()); }
+    offs.push_back(pv.size());
+    if (pv.empty()) pv.push_back(0);
+    for (const auto& h : vkey_hashes) vk.insert(vk.end(), h.begin(), h.end());
+    stride = (vkey_hashes.size() == 1 && n != 1) ? 0 : 32;
+  }
+};
+}  // namespace detail
+// SP1's committed_values_digest: SHA-256(public_values) with the top three bits of byte 0 cleared (the circuit's input 1; input 0 is the program's vkey hash)
+inline std::array<uint8_t, 32> sp1_public_values_digest(const Bytes& public_values) {
+  std::array<uint8_t, 32> out{};
+  detail::check(bn254_sp1_public_values_digest(public_values.data(), public_values.size(), out.data()));
+  return out;
+}
+
 // A verifying key prepared once (decompression, e(alpha, beta), line tables, window tables: the work lib.rs:46 and groth16/verify.rs:70 repeat per call)
 class PreparedGroth16Vk {
  public:
@@ -138,6 +160,15 @@ class PreparedGroth16Vk {
     Bytes st(n ? n : 1);
     detail::check(bn254_groth16_verify_batch(h_, proofs, stride, public_inputs, n_public, n, st.data(), device, flags));
     st.resize(n);
+    return st;
+  }
+  // SP1 proofs from their public values: proof i verified against vkey_hashes[i] (or the one hash) | SHA-256(public_values[i]) & mask, the digest made on the device
+  Bytes verify_sp1_batch(const uint8_t* proofs, size_t stride, const std::vector<std::array<uint8_t, 32>>& vkey_hashes, const std::vector<Bytes>& public_values,
+                         int device = 0, unsigned flags = 0) const {
+    detail::Sp1Buffers b(vkey_hashes, public_values);
+    Bytes st(b.n ? b.n : 1);
+    detail::check(bn254_sp1_groth16_verify_batch(h_, proofs, stride, b.vk.data(), b.stride, b.pv.data(), b.offs.data(), b.n, st.data(), device, flags));
+    st.resize(b.n);
     return st;
   }
   Bytes verify_batch_multi(const uint8_t* proofs, size_t stride, const uint8_t* public_inputs, size_t n_public, size_t n, uint64_t device_mask, unsigned flags = 0) const {
@@ -204,6 +235,15 @@ class PreparedPlonkVk {
     Bytes st(n ? n : 1);
     detail::check(bn254_plonk_verify_batch_flags(h_, proofs, stride, public_inputs, n_public, n, st.data(), device, flags));
     st.resize(n);
+    return st;
+  }
+  // SP1 proofs from their public values, as PreparedGroth16Vk::verify_sp1_batch (flags: BN254_FLAG_RLC only)
+  Bytes verify_sp1_batch(const uint8_t* proofs, size_t stride, const std::vector<std::array<uint8_t, 32>>& vkey_hashes, const std::vector<Bytes>& public_values,
+                         int device = 0, unsigned flags = 0) const {
+    detail::Sp1Buffers b(vkey_hashes, public_values);
+    Bytes st(b.n ? b.n : 1);
+    detail::check(bn254_sp1_plonk_verify_batch(h_, proofs, stride, b.vk.data(), b.stride, b.pv.data(), b.offs.data(), b.n, st.data(), device, flags));
+    st.resize(b.n);
     return st;
   }
   // the same over the GPUs selected by device_mask (contiguous shards, one host thread per device)

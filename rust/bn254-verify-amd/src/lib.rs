@@ -59,6 +59,26 @@ fn flatten(proofs: &[&[u8]], min_stride: usize) -> (Vec<u8>, usize) {
     (buf, stride)
 }
 
+/// SP1's committed_values_digest of a proof's public values: SHA-256 with the top three bits of byte 0 cleared (the circuit's input 1; input 0 is the program's
+/// vkey hash).
+pub fn sp1_public_values_digest(public_values: &[u8]) -> Result<[u8; 32], Error> {
+    let mut out = [0u8; 32];
+    check(unsafe { sys::bn254_sp1_public_values_digest(public_values.as_ptr(), public_values.len(), out.as_mut_ptr()) })?;
+    Ok(out)
+}
+
+/// The host buffers of an SP1 batch: the values concatenated and the n + 1 offsets; the vkey hashes as one hash (stride 0) or one per proof (stride 32).
+fn sp1_buffers(vkey_hashes: &[[u8; 32]], public_values: &[&[u8]]) -> (Vec<u8>, Vec<u64>, Vec<u8>, usize) {
+    assert!(vkey_hashes.len() == 1 || vkey_hashes.len() == public_values.len(), "one vkey hash, or one per proof");
+    let mut pv = Vec::new();
+    let mut offs = Vec::with_capacity(public_values.len() + 1);
+    for v in public_values { offs.push(pv.len() as u64); pv.extend_from_slice(v); }
+    offs.push(pv.len() as u64);
+    let vk: Vec<u8> = vkey_hashes.iter().flat_map(|h| h.iter().copied()).collect();
+    let stride = if vkey_hashes.len() == 1 && public_values.len() != 1 { 0 } else { 32 };
+    (pv, offs, vk, stride)
+}
+
 /// `load_groth16_verifying_key_from_bytes` + `pairing(alpha, beta)` (`groth16/converter.rs:28-89`, `groth16/verify.rs:70`), done once.
 pub struct PreparedGroth16Vk { h: *mut sys::Bn254G16Pvk }
 unsafe impl Send for PreparedGroth16Vk {}
@@ -93,6 +113,17 @@ impl PreparedGroth16Vk {
     pub unsafe fn verify_batch_device(&self, d_proofs: *const c_void, proof_stride: usize, d_inputs: *const c_void, n_public: usize, n: usize, d_status: *mut c_void, device: i32,
                                       hip_stream: *mut c_void, flags: u32) -> Result<(), Error> {
         check(sys::bn254_groth16_verify_batch_device(self.h, d_proofs, proof_stride, d_inputs, n_public, n, d_status, device, hip_stream, flags))
+    }
+    /// SP1 proofs from their public values: `n = public_values.len()` proofs `proof_stride` bytes apart, each verified against vkey_hash_i | digest(values_i), the
+    /// digest made on the device.  `vkey_hashes`: one for the whole batch or one per proof.  `flags` as `verify_batch_raw` (a key of another width than 2 gives
+    /// `Status::InputLen`).
+    pub fn verify_sp1_batch(&self, proofs: &[u8], proof_stride: usize, vkey_hashes: &[[u8; 32]], public_values: &[&[u8]], device: i32, flags: u32) -> Result<Vec<Status>, Error> {
+        let n = public_values.len();
+        assert!(proof_stride >= g16_min_stride(flags) && proofs.len() >= n * proof_stride);
+        let (pv, offs, vk, stride) = sp1_buffers(vkey_hashes, public_values);
+        let mut st = vec![0u8; n];
+        check(unsafe { sys::bn254_sp1_groth16_verify_batch(self.h, proofs.as_ptr(), proof_stride, vk.as_ptr(), stride, pv.as_ptr(), offs.as_ptr(), n, st.as_mut_ptr(), device, flags) })?;
+        Ok(st.into_iter().map(Status::from).collect())
     }
 }
 impl Drop for PreparedGroth16Vk { fn drop(&mut self) { unsafe { sys::bn254_groth16_vk_free(self.h) } } }
@@ -160,6 +191,15 @@ impl PreparedPlonkVk {
         assert!(proofs.len() >= n * proof_stride && public_inputs.len() >= n * n_public * 32);
         let mut st = vec![0u8; n];
         check(unsafe { sys::bn254_plonk_verify_batch_flags(self.h, proofs.as_ptr(), proof_stride, public_inputs.as_ptr(), n_public, n, st.as_mut_ptr(), device, flags) })?;
+        Ok(st.into_iter().map(Status::from).collect())
+    }
+    /// SP1 proofs from their public values, as `PreparedGroth16Vk::verify_sp1_batch`; `flags`: `sys::BN254_FLAG_RLC` only.
+    pub fn verify_sp1_batch(&self, proofs: &[u8], proof_stride: usize, vkey_hashes: &[[u8; 32]], public_values: &[&[u8]], device: i32, flags: u32) -> Result<Vec<Status>, Error> {
+        let n = public_values.len();
+        assert!(proofs.len() >= n * proof_stride);
+        let (pv, offs, vk, stride) = sp1_buffers(vkey_hashes, public_values);
+        let mut st = vec![0u8; n];
+        check(unsafe { sys::bn254_sp1_plonk_verify_batch(self.h, proofs.as_ptr(), proof_stride, vk.as_ptr(), stride, pv.as_ptr(), offs.as_ptr(), n, st.as_mut_ptr(), device, flags) })?;
         Ok(st.into_iter().map(Status::from).collect())
     }
     /// The same over the GPUs selected by `device_mask` (contiguous shards, one host thread per device: SURVEY.md section 8(e)).

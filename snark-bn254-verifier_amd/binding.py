@@ -203,6 +203,17 @@ class PreparedPlonkVk:
         n_public = self.n_public if n_public is None else n_public
         _check(lib().bn254_plonk_verify_batch_device(self._h, d_proofs, proof_stride, d_inputs, n_public, n, d_status, device, stream, flags))
 
+    def verify_sp1_batch(self, proofs, vkey_hashes, public_values, proof_stride=904, device=0, flags=0):
+        """SP1 proofs from their public values (bn254_sp1_plonk_verify_batch): as PreparedVk.verify_sp1_batch; flags: FLAG_RLC only."""
+        return _sp1_host_call(lib().bn254_sp1_plonk_verify_batch, self._h, proofs, proof_stride, vkey_hashes, public_values, len(public_values), device, flags)
+
+    def verify_sp1_batch_device(self, d_proofs, d_vkey_hashes, d_public_values, pv_bytes, d_offsets, d_status, n, proof_stride=904, vkey_stride=32, device=0,
+                                stream=None, flags=0):
+        """Raw device pointers (ints).  Host-synchronous like verify_batch_device (bn254_sp1_plonk_verify_batch_device)."""
+        fn = lib().bn254_sp1_plonk_verify_batch_device
+        fn.argtypes = _SP1_DEVICE_ARGTYPES
+        _check(fn(self._h, d_proofs, proof_stride, d_vkey_hashes, vkey_stride, d_public_values, pv_bytes, d_offsets, n, d_status, device, stream, flags))
+
     def reserve(self, n, proof_stride=0, device=0):
         """Allocate now what a batch of up to n proofs needs (proof_stride > 0: also the pinned staging of the host-buffer entry)."""
         _check(lib().bn254_plonk_reserve(self._h, n, proof_stride, device))
@@ -277,6 +288,86 @@ def dbg_g16_decompress(records, k=None, stride=COMPRESSED_PROOF_LEN):
     return bytes(raw)[:256 * k], bytes(pre)[:k]
 
 
+def sp1_public_values_digest(public_values):
+    """SP1's committed_values_digest: SHA-256(public_values) with the top three bits of byte 0 cleared (bn254_sp1_public_values_digest, on the host)."""
+    L = lib()
+    L.bn254_sp1_public_values_digest.argtypes = [C.c_char_p, C.c_size_t, C.c_void_p]
+    out = (C.c_uint8 * 32)()
+    pv = bytes(public_values)
+    _check(L.bn254_sp1_public_values_digest(pv, len(pv), out))
+    return bytes(out)
+
+
+def sp1_pack_values(public_values, base=0):
+    """A list of byte strings -> (their concatenation, the n + 1 absolute offsets of the SP1 entries as a ctypes uint64 array; the first is `base`)."""
+    import numpy as np
+    vals = public_values if all(isinstance(v, bytes) for v in public_values) else [bytes(v) for v in public_values]
+    offs = (C.c_uint64 * (len(vals) + 1))()
+    o = np.frombuffer(offs, dtype=np.uint64)
+    o[0] = base
+    np.cumsum(np.fromiter(map(len, vals), dtype=np.uint64, count=len(vals)), out=o[1:])
+    o[1:] += np.uint64(base)
+    return b"".join(vals), offs
+
+
+def _sp1_vkey_hashes(vkey_hashes, n):
+    """One 32-byte hash for the whole batch (stride 0) or a list of n (stride 32) -> (bytes, stride)."""
+    if isinstance(vkey_hashes, (bytes, bytearray)):
+        if len(vkey_hashes) != 32:
+            raise ValueError("one vkey hash is 32 bytes; pass a list for one hash per proof")
+        return bytes(vkey_hashes), 0
+    hs = [bytes(h) for h in vkey_hashes]
+    if len(hs) != n or any(len(h) != 32 for h in hs):
+        raise ValueError("vkey_hashes: one 32-byte hash, or n of them")
+    return b"".join(hs), 32
+
+
+def _offsets_ptr(offsets):
+    """A ctypes uint64 array, or an int (a device pointer)."""
+    return offsets if isinstance(offsets, int) else C.cast(offsets, C.c_void_p)
+
+
+def dbg_sp1_public_inputs(vkey_hashes, vkey_stride, public_values, offsets, n=None, pv_bytes=None, device=-1):
+    """k_sp1_public_inputs's body (bn254_dbg_sp1_public_inputs) on host buffers: device -1 runs the host compile, device >= 0 the kernel.  offsets: n + 1
+    integers.  Returns (n rows of 64 bytes vkey_hash | digest, n bad-range bytes)."""
+    L = lib()
+    L.bn254_dbg_sp1_public_inputs.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+    offs = list(offsets)
+    if n is None:
+        n = len(offs) - 1
+    pv = bytes(public_values)
+    pv_bytes = len(pv) if pv_bytes is None else pv_bytes
+    oa = (C.c_uint64 * max(1, len(offs)))(*offs)
+    rows = (C.c_uint8 * max(1, 64 * n))(); bad = (C.c_uint8 * max(1, n))()
+    _check(L.bn254_dbg_sp1_public_inputs(bytes(vkey_hashes), vkey_stride, pv, pv_bytes, C.cast(oa, C.c_void_p), n, rows, bad, device))
+    return bytes(rows)[:64 * n], bytes(bad)[:n]
+
+
+def synth_groth16_for_inputs(seed, n_public, inputs, n=None, threads=0):
+    """(vk, proofs): the key of synth_groth16(seed, n_public, ..) and one valid 256-byte proof per input row (n x n_public x 32 bytes, used modulo r)."""
+    L = lib()
+    L.bn254_synth_groth16_for_inputs.argtypes = [C.c_uint64, C.c_size_t, C.c_size_t, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p]
+    inputs = bytes(inputs)
+    if n is None:
+        n = len(inputs) // (32 * n_public)
+    vk = (C.c_uint8 * L.bn254_synth_groth16_vk_len(n_public))()
+    proofs = (C.c_uint8 * max(256 * n, 1))()
+    _check(L.bn254_synth_groth16_for_inputs(seed, n_public, n, inputs, threads, vk, proofs))
+    return bytes(vk), bytes(proofs)[:256 * n]
+
+
+def _sp1_host_call(fn, handle, proofs, proof_stride, vkey_hashes, public_values, n, device, flags):
+    vk, vstride = _sp1_vkey_hashes(vkey_hashes, n)
+    pv, offs = sp1_pack_values(public_values)
+    st = (C.c_uint8 * max(n, 1))()
+    fn.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_uint]
+    _check(fn(handle, bytes(proofs), proof_stride, vk, vstride, pv, C.cast(offs, C.c_void_p), n, st, device, flags))
+    return bytes(st)[:n]
+
+
+_SP1_DEVICE_ARGTYPES = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+
+
 class PreparedVk:
     """Opaque prepared verifying key (bn254_groth16_vk_prepare)."""
 
@@ -316,6 +407,20 @@ class PreparedVk:
         flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
         n_public = self.n_public if n_public is None else n_public
         _check(lib().bn254_groth16_verify_batch_device(self._h, d_proofs, proof_stride, d_inputs, n_public, n, d_status, device, stream, flags))
+
+    def verify_sp1_batch(self, proofs, vkey_hashes, public_values, proof_stride=None, device=0, flags=0, compressed=False):
+        """SP1 proofs from their public values (bn254_sp1_groth16_verify_batch): proofs as verify_batch takes them (n records); vkey_hashes: one 32-byte
+        hash or a list of n; public_values: a list of n byte strings.  The inputs vkey_hash | SHA-256(values) & mask are made on the device.  Returns n status bytes."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
+        return _sp1_host_call(lib().bn254_sp1_groth16_verify_batch, self._h, proofs, proof_stride, vkey_hashes, public_values, len(public_values), device, flags)
+
+    def verify_sp1_batch_device(self, d_proofs, d_vkey_hashes, d_public_values, pv_bytes, d_offsets, d_status, n, proof_stride=None, vkey_stride=32, device=0,
+                                stream=None, flags=0, compressed=False):
+        """Raw device pointers (ints; d_offsets: n + 1 uint64 values); enqueues on `stream` like verify_batch_device (bn254_sp1_groth16_verify_batch_device)."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
+        fn = lib().bn254_sp1_groth16_verify_batch_device
+        fn.argtypes = _SP1_DEVICE_ARGTYPES
+        _check(fn(self._h, d_proofs, proof_stride, d_vkey_hashes, vkey_stride, d_public_values, pv_bytes, d_offsets, n, d_status, device, stream, flags))
 
     def reserve(self, n, device=0):
         _check(lib().bn254_groth16_reserve(self._h, n, device))

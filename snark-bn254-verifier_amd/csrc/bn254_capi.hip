@@ -1,6 +1,7 @@
 // bn254_capi.hip -- implementation of the C ABI declared in include/bn254_verify.h: version, errors and status strings, the host plumbing the
 // protocol files share, the point codecs and the SP1 fixture parser, the shard plan and the status all-gather of multi-device jobs.
-// The protocols live beside it: bn254_capi_g16.hip (Groth16), bn254_capi_plonk.hip (PlonK), bn254_capi_dbg.hip (test probes, workload generator).
+// The protocols live beside it: bn254_capi_g16.hip (Groth16), bn254_capi_plonk.hip (PlonK), bn254_capi_sp1.hip (SP1 proofs from their public values),
+// bn254_capi_dbg.hip (test probes, workload generator).
 // Host orchestration only: key preparation (bn254_host.hpp), device buffers, kernel launches (bn254_kernels.hip).
 // There is deliberately no CPU implementation of verify here: if HIP is unusable the calls fail (BN254_E_NO_DEVICE).
 #include "bn254_capi_internal.h"
@@ -292,11 +293,12 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 }  // extern "C"
 
 // The host half of the library is also built as ONE translation unit: tests/hostsan compiles this file with g++ against a stand-in HIP runtime (no hipcc,
-// so no __HIPCC__) and drives the C ABI under the sanitizers.  There this file brings the other three files of the C ABI with it; hipcc builds each as its
+// so no __HIPCC__) and drives the C ABI under the sanitizers.  There this file brings the other four files of the C ABI with it; hipcc builds each as its
 // own object (Makefile).
 #if !defined(__HIPCC__)
 #include "bn254_capi_g16.hip"
 #include "bn254_capi_plonk.hip"
+#include "bn254_capi_sp1.hip"
 #include "bn254_capi_dbg.hip"
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
@@ -311,6 +313,15 @@ hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32
 }
 hipError_t bn254_launch_g16_status_merge(uint8_t* status, const uint8_t* pre, uint32_t n, hipStream_t) {
   for (uint32_t i = 0; i < n; i++) if (pre[i]) status[i] = BN254_ST_MALFORMED;
+  return hipSuccess;
+}
+hipError_t bn254_launch_sp1_public_inputs(const uint8_t* vkh, size_t vkh_stride, const uint8_t* pv, uint64_t pv_bytes, uint64_t pv_base, const uint64_t* off, uint32_t n,
+                                          uint8_t* rows, uint8_t* pre, hipStream_t) {
+  for (uint32_t i = 0; i < n; i++) {
+    uint32_t row[16];
+    pre[i] = bn254::sp1_row(vkh + (size_t)i * vkh_stride, pv, pv_bytes, pv_base, off[i], off[i + 1], row) ? 0 : 1;
+    memcpy(rows + (size_t)i * 64, row, 64);
+  }
   return hipSuccess;
 }
 #endif

@@ -432,15 +432,10 @@ int bn254_dbg_comb_mul(const uint8_t p64[64], const uint8_t x32[32], uint8_t out
 // ---------------------------------------------------------------- synthetic workload generator
 size_t bn254_synth_groth16_vk_len(size_t n_public) { return 292 + 32 * (n_public + 1) + 4 + 128; }
 
-int bn254_synth_groth16(uint64_t seed, size_t n_public, size_t n, int invalid_every, int agree, int threads, uint8_t* vk_out,
-                        uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected) {
-  return bn254_synth_groth16_range(seed, n_public, 0, n, invalid_every, agree, threads, vk_out, proofs_out, inputs_out, expected);
-}
-// proofs [first, first + n) of the stream bn254_synth_groth16 generates for `seed` (proof i is a function of (seed, i) alone), written to
-// positions 0 .. n-1 of the output buffers: a rank of a sharded job generates its own contiguous shard only
-int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size_t n, int invalid_every, int agree, int threads, uint8_t* vk_out,
-                              uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected) {
-  if (!vk_out || (n && (!proofs_out || !expected)) || (n && n_public && !inputs_out)) return set_err(BN254_E_BAD_ARG, "bad argument");
+// the key of the synthetic workload and its trapdoors: the first part of the stream of `seed` (every range and bn254_synth_groth16_for_inputs make the same key)
+namespace {
+struct SynthKey { U256 alpha, beta, gamma, delta; std::vector<U256> kk; GenTables* tabs; };
+void synth_key(uint64_t seed, size_t n_public, int agree, uint8_t* vk_out, SynthKey& key) {
   static GenTables* tabs = nullptr;
   static std::mutex tmu;
   {
@@ -472,6 +467,23 @@ int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size
   for (size_t i = 0; i <= n_public; i++) enc_g1_compressed(vk_out + 292 + 32 * i, g1_to_affine(g1_mul_gen(*tabs, kk[i])));
   size_t off = 292 + 32 * (n_public + 1) + 4;
   vk_out[off] = 0x40; vk_out[off + 64] = 0x40;
+  key.alpha = alpha; key.beta = beta; key.gamma = gamma; key.delta = delta; key.kk = kk; key.tabs = tabs;
+}
+}  // namespace
+int bn254_synth_groth16(uint64_t seed, size_t n_public, size_t n, int invalid_every, int agree, int threads, uint8_t* vk_out,
+                        uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected) {
+  return bn254_synth_groth16_range(seed, n_public, 0, n, invalid_every, agree, threads, vk_out, proofs_out, inputs_out, expected);
+}
+// proofs [first, first + n) of the stream bn254_synth_groth16 generates for `seed` (proof i is a function of (seed, i) alone), written to
+// positions 0 .. n-1 of the output buffers: a rank of a sharded job generates its own contiguous shard only
+int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size_t n, int invalid_every, int agree, int threads, uint8_t* vk_out,
+                              uint8_t* proofs_out, uint8_t* inputs_out, uint8_t* expected) {
+  if (!vk_out || (n && (!proofs_out || !expected)) || (n && n_public && !inputs_out)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  SynthKey key;
+  synth_key(seed, n_public, agree, vk_out, key);
+  GenTables* tabs = key.tabs;
+  const U256 &alpha = key.alpha, &beta = key.beta, &gamma = key.gamma, &delta = key.delta;
+  const std::vector<U256>& kk = key.kk;
   if (n == 0) return BN254_OK;
   U256 delta_inv = fr_inv(delta), alpha_beta = fr_mul(alpha, beta);
   // a few twist points outside the r-torsion for the NOT_IN_SUBGROUP class
@@ -529,6 +541,42 @@ int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size
       }
       if (cls == 4) { memset(p, 0xff, 32); st = BN254_ERR_NOT_MEMBER; }  // A.x = 2^256 - 1 >= p
       expected[li] = st;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; t++) th.emplace_back(worker, t);
+  for (auto& x : th) x.join();
+  return BN254_OK;
+}
+
+// valid proofs for given public inputs under the key of bn254_synth_groth16(seed, n_public, .., agree = 1): A = a G1, B = b G2, C = (a b - alpha beta - gamma ell) / delta G1
+// with ell = k_0 + sum (x_s mod r) k_s (the trapdoor formula of the generator above); a, b from (seed, i) like the generator's proof i
+int bn254_synth_groth16_for_inputs(uint64_t seed, size_t n_public, size_t n, const uint8_t* inputs, int threads, uint8_t* vk_out, uint8_t* proofs_out) {
+  if (!vk_out || (n && !proofs_out) || (n && n_public && !inputs)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  SynthKey key;
+  synth_key(seed, n_public, 1, vk_out, key);
+  if (n == 0) return BN254_OK;
+  const U256 delta_inv = fr_inv(key.delta), alpha_beta = fr_mul(key.alpha, key.beta), r = u256_r();
+  if (threads <= 0) { threads = (int)std::thread::hardware_concurrency(); if (threads <= 0) threads = 1; }
+  if ((size_t)threads > n) threads = (int)n;
+  auto worker = [&](int tid) {
+    for (size_t i = tid; i < n; i += threads) {
+      SplitMix64 g{seed * 0x9e3779b97f4a7c15ull + 0x1000 + i};
+      const U256 a = fr_random(g, true), b = fr_random(g, true);
+      U256 ell = key.kk[0];
+      for (size_t s = 0; s < n_public; s++) {
+        const uint8_t* q = inputs + (i * n_public + s) * 32;
+        U256 x;
+        for (int l = 0; l < 4; l++) { x.l[l] = 0; for (int j = 0; j < 8; j++) x.l[l] = x.l[l] << 8 | q[(3 - l) * 8 + j]; }
+        while (u256_cmp(x, r) >= 0) u256_sub(x, x, r);   // 2^256 < 6 r
+        ell = fr_add(ell, fr_mul(x, key.kk[s + 1]));
+      }
+      const U256 c = fr_mul(fr_sub(fr_sub(fr_mul(a, b), alpha_beta), fr_mul(key.gamma, ell)), delta_inv);
+      uint8_t* p = proofs_out + 256 * i;
+      enc_g1_uncompressed(p, g1_to_affine(g1_mul_gen(*key.tabs, a)));
+      enc_g2_uncompressed(p + 64, g2_mul_gen(*key.tabs, b));
+      const G1Proj cp = g1_mul_gen(*key.tabs, c);
+      if (g1_is_identity(cp)) { memset(p + 192, 0, 64); } else enc_g1_uncompressed(p + 192, g1_to_affine(cp));
     }
   };
   std::vector<std::thread> th;

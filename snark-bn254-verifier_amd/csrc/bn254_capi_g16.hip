@@ -100,6 +100,16 @@ static int ensure_cmp(DevState& d, size_t n) {
   d.cmp_cap = need.proofs;
   return BN254_OK;
 }
+// SP1 public inputs: the row scratch for a batch of n proofs (caller holds d.mu); grown like the decompression scratch above, never by the enqueue path
+static int ensure_sp1(DevState& d, size_t n) {
+  const G16Sp1Alloc need = g16_sp1_alloc(n);
+  if (need.proofs <= d.sp1_cap) return BN254_OK;
+  if (d.sp1) HIPCK(hipFree(d.sp1));
+  d.sp1 = nullptr; d.sp1_cap = 0;
+  HIPCK(hipMalloc((void**)&d.sp1, need.row_bytes + need.pre_bytes));
+  d.sp1_cap = need.proofs;
+  return BN254_OK;
+}
 static int ensure_aux(DevState& d, int count) {
   if (count > 3) count = 3;
   if (!d.fork_ev) {
@@ -114,7 +124,7 @@ static inline hipStream_t part_stream(DevState& d, hipStream_t user, int pi) { c
 static void dev_free(DevState& d) {
   int32_t* ptrs[] = {d.k0, d.gtab, d.dtab, d.target, d.msm, d.ws, d.msm_part};
   for (auto q : ptrs) if (q) (void)hipFree(q);
-  uint8_t* bp[] = {d.st_proofs, d.st_inputs, d.st_status, d.cmp};
+  uint8_t* bp[] = {d.st_proofs, d.st_inputs, d.st_status, d.cmp, d.sp1, d.st_pv, d.st_off, d.st_vkh};
   for (auto q : bp) if (q) (void)hipFree(q);
   if (d.ev_ready) { for (int i = 0; i < 5; i++) (void)hipEventDestroy(d.ev[i]); for (auto& e : d.prof_ev) (void)hipEventDestroy(e); for (auto& e : d.prof2_ev) (void)hipEventDestroy(e); }
   for (int i = 0; i < d.aux_count; i++) (void)hipStreamDestroy(d.aux[i]);
@@ -481,6 +491,47 @@ static int g16_enqueue(const bn254_g16_pvk* pvk, DevState* d, int device, const 
   return BN254_OK;
 }
 
+// SP1 public inputs, chunk by chunk (at most G16_MAX_BATCH proofs, as g16_enqueue_compressed): k_sp1_public_inputs writes the rows vkey_hash | digest and the
+// pre-status bytes into the row scratch, the pipeline chosen for the whole batch (with BN254_FLAG_COMPRESSED_PROOFS: decompression first) runs on the rows with
+// n_public = 2, and k_g16_status_merge makes MALFORMED override for a range outside the values buffer.  Everything is on `user`, so the next chunk's hashing
+// overwrites the rows only after this chunk is done with them.  use_rlc as in g16_enqueue.
+static int g16_enqueue_sp1(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const Sp1Src& s, size_t n, void* d_status,
+                           hipStream_t user, unsigned flags, int use_rlc = -1) {
+  if (d->busy_valid) HIPCK(hipStreamWaitEvent(user, d->busy_ev, 0));
+  const bool rlc = use_rlc >= 0 ? use_rlc != 0 : (rlc_eligible(pvk, 2, n, flags) && !rlc_bypass(d->rlc));
+  const unsigned raw_flags = flags & ~(unsigned)BN254_FLAG_COMPRESSED_PROOFS;
+  for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
+    const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
+    if (g16_sp1_alloc(m).proofs > d->sp1_cap) return set_err(BN254_E_BAD_ARG, "SP1 row scratch smaller than the batch (internal sizing error)");
+    uint8_t* rows = d->sp1;
+    uint8_t* pre = d->sp1 + d->sp1_cap * 64;
+    uint8_t* st = (uint8_t*)d_status + off;
+    const uint8_t* pr = (const uint8_t*)d_proofs + off * proof_stride;
+    hipError_t e = bn254_launch_sp1_public_inputs(s.vkh + off * s.vkh_stride, s.vkh_stride, s.pv, s.pv_bytes, s.pv_base, s.off + off, (uint32_t)m, rows, pre, user);
+    if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
+                                         std::string("kernel launch (SP1 public inputs): ") + hipGetErrorString(e));
+    int rc;
+    if (flags & BN254_FLAG_COMPRESSED_PROOFS) rc = g16_enqueue_compressed(pvk, d, device, pr, proof_stride, rows, 2, m, st, user, flags, rlc);
+    else if (rlc) rc = g16_enqueue_rlc(pvk, d, device, pr, proof_stride, rows, 2, m, st, user, raw_flags);
+    else rc = g16_enqueue_exact(pvk, d, pr, proof_stride, rows, 2, m, st, user, raw_flags);
+    if (rc) return rc;
+    e = bn254_launch_g16_status_merge(st, pre, (uint32_t)m, user);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("kernel launch (status merge): ") + hipGetErrorString(e));
+  }
+  HIPCK(hipEventRecord(d->busy_ev, user));
+  d->busy_valid = true;
+  return BN254_OK;
+}
+int g16_sp1_device(const bn254_g16_pvk* pvk, const void* d_proofs, size_t proof_stride, const Sp1Src& s, size_t n, void* d_status, int device, hipStream_t user, unsigned flags) {
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  int rc;
+  if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
+  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
+  if ((rc = ensure_sp1(*d, n))) return rc;
+  return g16_enqueue_sp1(pvk, d, device, d_proofs, proof_stride, s, n, d_status, user, flags);
+}
+
 extern "C" {
 
 int bn254_groth16_verify_batch_device(const bn254_g16_pvk* pvk, const void* d_proofs, size_t proof_stride, const void* d_inputs,
@@ -615,18 +666,28 @@ static int host_ring_ensure(DevState& d, size_t piece_bytes) {
   d.pin_cap = piece_bytes;
   return BN254_OK;
 }
-int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
-                               size_t n_public, size_t n, uint8_t* status, int device, unsigned flags) {
-  int rc = check_batch_args(false, pvk, proofs, proof_stride, public_inputs, n_public, n, status, flags);
-  if (rc || n == 0) return rc;
+}  // extern "C"
+
+// The host-buffer batch.  sp1 = nullptr: the raw entry.  sp1 != nullptr (host buffers, offsets already checked to be non-decreasing): the public inputs are the
+// SP1 rows -- nothing is read from public_inputs; at the start of every compute chunk its offsets, values and vkey hashes go through the same pinned ring
+// ahead of its proofs (each byte once: the values are staged as bytes [off[0], off[n]) of the caller's buffer), the chunk is hashed on the device and the
+// rows never leave it.
+static int g16_host_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                          size_t n_public, size_t n, uint8_t* status, int device, unsigned flags, const Sp1Src* sp1) {
+  int rc;
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
   if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
   if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
+  if (sp1) n_public = 0;   // staged per proof: the proof only (the rows are made on the device)
   const size_t in_row = n_public * 32, row = proof_stride + in_row;
   size_t pb = n * proof_stride, ib = n * in_row;
   if ((rc = grow(&d->st_proofs, &d->st_proofs_cap, pb)) || (rc = grow(&d->st_inputs, &d->st_inputs_cap, ib ? ib : 32)) ||
       (rc = grow(&d->st_status, &d->st_status_cap, n)))
+    return rc;
+  const uint64_t pv_total = sp1 ? sp1->off[n] - sp1->off[0] : 0;
+  if (sp1 && ((rc = ensure_sp1(*d, n)) || (rc = grow(&d->st_pv, &d->st_pv_cap, pv_total ? pv_total : 4)) ||
+              (rc = grow(&d->st_off, &d->st_off_cap, (n + 1) * 8)) || (rc = grow(&d->st_vkh, &d->st_vkh_cap, sp1->vkh_stride ? n * 32 : 32))))
     return rc;
   if (!d->host_stream) { HIPCK(hipStreamCreateWithFlags(&d->host_stream, hipStreamNonBlocking)); HIPCK(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking)); }
   // compute chunks: a short first one (its copy is the only exposed one: 2^17 proofs = 42 MB, under a millisecond of DMA), then the rest in chunks
@@ -642,7 +703,7 @@ int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, 
   // the RLC mode forms its groups over the whole batch it is handed: keep it in one piece -- but only when this call really runs the mode
   // (same predicate as g16_enqueue, the adaptive bypass included, decided ONCE here); a flag that will be ignored keeps the chunked
   // copy / compute overlap
-  const int use_rlc = (rlc_eligible(pvk, n_public, n, flags) && !rlc_bypass(d->rlc)) ? 1 : 0;
+  const int use_rlc = (rlc_eligible(pvk, sp1 ? 2 : n_public, n, flags) && !rlc_bypass(d->rlc)) ? 1 : 0;
   static const bool timing = getenv("BN254_HOST_TIMING") != nullptr;   // diagnostics on stderr: where the host thread spends the call
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
@@ -653,6 +714,40 @@ int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, 
   size_t c_end = (use_rlc || n < 2 * first_chunk) ? n : first_chunk;
   while (computed < n) {
     hipEvent_t last = nullptr;
+    // bytes [0, len) of a device buffer through the ring, fill(pin, from, k) writing bytes [from, from + k) into the pinned piece
+    auto push = [&](uint8_t* dst, size_t len, const std::function<void(uint8_t*, size_t, size_t)>& fill) -> int {
+      for (size_t from = 0; from < len;) {
+        const size_t k = len - from < d->pin_cap ? len - from : d->pin_cap;
+        const int slot = (int)(slot_uses % HOST_RING);
+        if (slot_uses >= HOST_RING) HIPCK(hipEventSynchronize(d->pin_ev[slot]));
+        fill(d->pin[slot], from, k);
+        HIPCK(hipMemcpyAsync(dst + from, d->pin[slot], k, hipMemcpyHostToDevice, d->copy_stream));
+        HIPCK(hipEventRecord(d->pin_ev[slot], d->copy_stream));
+        last = d->pin_ev[slot];
+        slot_uses++; from += k;
+      }
+      return BN254_OK;
+    };
+    if (sp1) {   // this chunk's offsets (the first chunk: off[0 .. c_end], later ones off[computed + 1 .. c_end]), values and vkey hashes
+      const size_t o_lo = computed ? computed + 1 : 0;
+      const uint8_t* osrc = (const uint8_t*)(sp1->off + o_lo);
+      const uint64_t v_lo = sp1->off[computed] - sp1->off[0], v_hi = sp1->off[c_end] - sp1->off[0];
+      const uint8_t* vsrc = sp1->pv + sp1->off[computed];
+      const size_t vk_stride = sp1->vkh_stride; const uint8_t* vk = sp1->vkh; const size_t first = computed;
+      if ((rc = push(d->st_off + o_lo * 8, (c_end + 1 - o_lo) * 8, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, osrc + f, k); })) ||
+          (rc = push(d->st_pv + v_lo, v_hi - v_lo, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, vsrc + f, k); })))
+        return rc;
+      if (vk_stride == 0 && computed == 0) rc = push(d->st_vkh, 32, [&](uint8_t* q, size_t, size_t) { memcpy(q, vk, 32); });
+      else if (vk_stride == 32) rc = push(d->st_vkh + first * 32, (c_end - first) * 32, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, vk + first * 32 + f, k); });
+      else if (vk_stride) rc = push(d->st_vkh + first * 32, (c_end - first) * 32, [&](uint8_t* q, size_t f, size_t k) {
+        for (size_t b = f; b < f + k;) {   // compacted to 32 bytes per proof
+          const size_t r = b / 32, o = b % 32, t = 32 - o < f + k - b ? 32 - o : f + k - b;
+          memcpy(q + (b - f), vk + (first + r) * vk_stride + o, t);
+          b += t;
+        }
+      });
+      if (rc) return rc;
+    }
     while (copied < c_end) {
       const size_t m = c_end - copied < piece ? c_end - copied : piece;
       const int slot = (int)(slot_uses % HOST_RING);
@@ -671,8 +766,13 @@ int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, 
     }
     if (last) HIPCK(hipStreamWaitEvent(d->host_stream, last, 0));
     auto td = now();
-    rc = g16_enqueue(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, d->st_inputs + computed * in_row, n_public, c_end - computed,
-                     d->st_status + computed, d->host_stream, flags, use_rlc);
+    if (sp1) {
+      const Sp1Src staged{d->st_vkh + (sp1->vkh_stride ? computed * 32 : 0), (size_t)(sp1->vkh_stride ? 32 : 0), d->st_pv, pv_total, sp1->off[0], (const uint64_t*)d->st_off + computed};
+      rc = g16_enqueue_sp1(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, staged, c_end - computed, d->st_status + computed, d->host_stream,
+                           flags, use_rlc);
+    } else
+      rc = g16_enqueue(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, d->st_inputs + computed * in_row, n_public, c_end - computed,
+                       d->st_status + computed, d->host_stream, flags, use_rlc);
     if (rc) {   // pieces of the pinned ring and earlier chunks may still be in flight: the ring and the staging buffers must be quiescent when the lock is released
       const std::string keep = g_err;
       (void)hipStreamSynchronize(d->copy_stream); (void)hipStreamSynchronize(d->host_stream);
@@ -689,6 +789,18 @@ int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, 
   if (timing) fprintf(stderr, "host-buffer batch %zu: pieces of %zu proofs; host copies %.2f ms, ring waits %.2f ms, kernel enqueue %.2f ms, all enqueued after %.2f ms, done after %.2f ms\n",
                       n, piece, t_copy, t_wait, t_enq, ms(t_begin, t_enqueued), ms(t_begin, now()));
   return BN254_OK;
+}
+int g16_sp1_host(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const Sp1Src& s, size_t n, uint8_t* status, int device, unsigned flags) {
+  return g16_host_batch(pvk, proofs, proof_stride, nullptr, 0, n, status, device, flags, &s);
+}
+
+extern "C" {
+
+int bn254_groth16_verify_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                               size_t n_public, size_t n, uint8_t* status, int device, unsigned flags) {
+  int rc = check_batch_args(false, pvk, proofs, proof_stride, public_inputs, n_public, n, status, flags);
+  if (rc || n == 0) return rc;
+  return g16_host_batch(pvk, proofs, proof_stride, public_inputs, n_public, n, status, device, flags, nullptr);
 }
 
 int bn254_groth16_verify_batch_multi(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,

@@ -89,6 +89,10 @@ struct DevState {
   // BN254_FLAG_COMPRESSED_PROOFS: raw records of the decompressed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_cmp_alloc); grown at the
   // first compressed batch that needs more (cmp_cap proofs)
   uint8_t* cmp = nullptr; size_t cmp_cap = 0;
+  // SP1 public inputs: rows vkey_hash | digest of the hashed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_sp1_alloc; sp1_cap proofs), grown at
+  // the first SP1 batch that needs more.  The host-buffer entry stages the batch's values, offsets and vkey hashes in st_pv / st_off / st_vkh.
+  uint8_t* sp1 = nullptr; size_t sp1_cap = 0;
+  uint8_t *st_pv = nullptr, *st_off = nullptr, *st_vkh = nullptr; size_t st_pv_cap = 0, st_off_cap = 0, st_vkh_cap = 0;
   // do the sub-batch streams overlap?  ov_ev: start / end of part 0 and of part 1 of the first two-stream batch; ov_state 0: not measured, 1: events recorded,
   // 2: measured (ov_ratio = sum of the two durations / their union: ~2 side by side, ~1 one after the other); single_stream: fall back to one sub-batch per launch
   hipEvent_t ov_ev[4] = {nullptr, nullptr, nullptr, nullptr}; int ov_state = 0; float ov_ratio = -1.f; bool single_stream = false;
@@ -139,6 +143,9 @@ struct PlonkDev {
   // batch is a chain of latency-bound launches that leaves most of the GPU idle, and two batches in flight verify 1.35 x as many proofs per second.
   std::mutex pool_mu; std::condition_variable pool_cv; bool busy[PLONK_WORKERS] = {};
   float last_ms[BN254_PLONK_NUM_TIMINGS] = {0}; size_t last_lanes[2] = {0, 0}; bool last_valid = false;   // first sub-batch of the call that finished last
+  // SP1 entries (bn254_capi_sp1.hip): device buffers for the rows, pre-status bytes and staged values of a call.  A call takes one for itself (calls on one key run side
+  // by side, so the rows cannot live in the key's state) and gives it back for the next call: a hipFree per call would wait for every other call's work on the device
+  std::mutex sp1_mu; std::vector<std::pair<uint8_t*, size_t>> sp1_bufs;
 };
 struct PlonkLease {   // the contexts of one call
   PlonkDev* d; int idx[PLONK_WORKERS]; int n = 0;
@@ -215,6 +222,14 @@ int build_tables_on_device(int form, const std::vector<int32_t>& pts, int32_t** 
 // bn254_capi_g16.hip
 DevState* dev_state(const bn254_g16_pvk* pvk, int device);
 int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n);
+// SP1 public inputs (bn254_capi_sp1.hip): where the vkey hashes and the values of a batch are.  Proof i's vkey hash is the 32 bytes at vkh + i vkh_stride
+// (vkh_stride 0: one for all), its values the bytes [off[i] - pv_base, off[i+1] - pv_base) of pv, a buffer of pv_bytes bytes; off holds n + 1 entries
+struct Sp1Src { const uint8_t* vkh; size_t vkh_stride; const uint8_t* pv; uint64_t pv_bytes, pv_base; const uint64_t* off; };
+int check_sp1_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* vkh, size_t vkh_stride, const void* pv, uint64_t pv_bytes,
+                   const uint64_t* off, bool host_offsets, size_t n, const void* status, unsigned flags);
+// the batch on device buffers (enqueued on `user`) / on host buffers (staged through the pinned ring; returns when the status bytes are back)
+int g16_sp1_device(const bn254_g16_pvk* pvk, const void* d_proofs, size_t proof_stride, const Sp1Src& s, size_t n, void* d_status, int device, hipStream_t user, unsigned flags);
+int g16_sp1_host(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const Sp1Src& s, size_t n, uint8_t* status, int device, unsigned flags);
 // bn254_capi_plonk.hip
 int plonk_ensure_dev(const bn254_plonk_pvk* pvk, int device, PlonkDev** out);
 int plonk_ensure_ctx(const bn254_plonk_pvk* pvk, PlonkCtx& c, size_t n, size_t in_bytes);
@@ -223,6 +238,10 @@ size_t msm_lane_budget();
 size_t plonk_scratch_lanes(size_t need, int n_var);
 size_t plonk_part_points(size_t need, const MsmShape& shape);
 void plonk_plan(size_t n, size_t piece, int max_workers, int* workers, size_t* per, size_t* pass);
+// a PlonK batch whose public inputs are already rows of two inputs in device memory (d_rows, 64 bytes per proof): resident = true, proofs and status are device
+// memory too; false, they are host buffers and only the proofs are staged
+int plonk_batch_rows(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* d_rows, size_t n, uint8_t* status, int device, unsigned flags,
+                     bool resident);
 #pragma GCC visibility pop
 
 // *dst stays null unless the copy is complete: a caller that retries after a failure uploads exactly what is still missing (a sanitizer run of the

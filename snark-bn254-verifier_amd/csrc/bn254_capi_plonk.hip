@@ -20,6 +20,8 @@ static void plonk_dev_free(PlonkDev& d) {
   void* ptrs[] = {d.tab0, d.tab1, d.one, d.fixed_tabs, d.d_key};
   for (auto q : ptrs) if (q) (void)hipFree(q);
   for (auto& c : d.ctx) plonk_ctx_free(c);
+  for (auto& b : d.sp1_bufs) (void)hipFree(b.first);
+  d.sp1_bufs.clear();
   d.ready = false; d.tab0 = d.tab1 = d.one = d.fixed_tabs = nullptr; d.d_key = nullptr;
 }
 int plonk_ensure_dev(const bn254_plonk_pvk* pvk, int device, PlonkDev** out) {
@@ -233,15 +235,16 @@ static int plonk_msm(const PlonkDev* d, PlonkCtx& c, const MsmShape& shape, size
 // The same sub-batch with BOTH host stages on the device (bn254_k_plonk.hip): one H2D copy of the proofs and inputs, stage 1 -> digest MSM -> stage 2 ->
 // folding MSMs -> pairing check on the context's stream without a host wait in between, one D2H copy of the status bytes.
 // resident: proofs / public_inputs / status are DEVICE memory of `device` (bn254_plonk_verify_batch_device): no staging copy, the status bytes leave with a device-to-device copy.
+// d_rows (SP1 public inputs): the pass's public inputs are already in device memory (n_public = 2), so with host buffers only the proofs are staged
 static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, PlonkCtx& c, int device, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
-                            size_t n_public, size_t m, uint8_t* status, unsigned flags, bool resident) {
+                            size_t n_public, size_t m, uint8_t* status, unsigned flags, bool resident, const uint8_t* d_rows = nullptr) {
   HIPCK(hipSetDevice(device));
   const PlonkKey& key = pvk->key;
   const int T1 = plonk_stage1_terms(key), T2 = plonk_stage2_terms(key), TT = T2 + 2;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   auto t0 = now();
-  const size_t pb = m * proof_stride, ib = m * n_public * 32, need = pb + ib;
+  const size_t pb = m * proof_stride, ib = d_rows ? 0 : m * n_public * 32, need = pb + ib;
   if (!resident && need > c.in_cap) return set_err(BN254_E_HIP, "PlonK context staging smaller than the pass (internal sizing error)");   // sized by plonk_ensure_ctx
   if (m > c.cap) return set_err(BN254_E_HIP, "PlonK context smaller than the pass (internal sizing error)");
   // The KZG batching scalar of every proof: fresh, uniform and unpredictable to the prover, as the reference draws it
@@ -261,7 +264,7 @@ static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, Plonk
   }
   auto t1_ = now();
   if (!resident) HIPCK(hipMemcpyAsync(c.d_in, c.h_in, need, hipMemcpyHostToDevice, c.stream));
-  const uint8_t* d_proofs = resident ? proofs : c.d_in; const uint8_t* d_inputs = resident ? public_inputs : c.d_in + pb;
+  const uint8_t* d_proofs = resident ? proofs : c.d_in; const uint8_t* d_inputs = d_rows ? d_rows : resident ? public_inputs : c.d_in + pb;
   HIPCK(hipEventRecord(c.tk[0], c.stream));
   hipError_t e = bn254_launch_plonk_stage1(d->d_key, d_proofs, proof_stride, d_inputs, n_public, m, lam_key, c.d_work, c.terms, c.flags, T1, c.stream);
   if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("PlonK stage 1 launch: ") + hipGetErrorString(e));
@@ -341,8 +344,9 @@ static void plonk_plan_for(size_t n, int* workers, size_t* per, size_t* pass_cap
 
 // One batch.  resident = false: proofs / public_inputs / status are the caller's host buffers (each pass stages its share through the context's pinned memory);
 // resident = true: they are device memory of `device` and nothing is staged.  Either way the call returns when every status byte is where the caller asked for it.
+// d_rows: see plonk_run_device (public_inputs is then ignored and n_public must be 2)
 static int plonk_batch(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n, uint8_t* status,
-                       int device, unsigned flags, bool resident) {
+                       int device, unsigned flags, bool resident, const uint8_t* d_rows = nullptr) {
   PlonkDev* d;
   int rc;
   {
@@ -357,13 +361,14 @@ static int plonk_batch(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t
   int workers; size_t per, pass_cap;                                  // sub-batches, proofs per sub-batch, proofs per (equal-sized) pass of a sub-batch
   plonk_plan_for(n, &workers, &per, &pass_cap);
   PlonkLease lease(d, workers);   // waits until that many contexts are free
-  for (int w = 0; w < workers; w++) if ((rc = plonk_ensure_ctx(pvk, lease.ctx(w), pass_cap, !resident ? pass_cap * (proof_stride + n_public * 32) : 0))) return rc;
+  for (int w = 0; w < workers; w++) if ((rc = plonk_ensure_ctx(pvk, lease.ctx(w), pass_cap, !resident ? pass_cap * (proof_stride + (d_rows ? 0 : n_public * 32)) : 0))) return rc;
   std::vector<int> rcs(workers, BN254_OK); std::vector<std::string> errs(workers);
   auto body = [&](int w) {
     const size_t lo = (size_t)w * per, hi = lo + per < n ? lo + per : n;
     for (size_t off = lo; off < hi; off += pass_cap) {
       const size_t m = hi - off < pass_cap ? hi - off : pass_cap;
-      int r = plonk_run_device(pvk, d, lease.ctx(w), device, proofs + off * proof_stride, proof_stride, public_inputs + off * n_public * 32, n_public, m, status + off, flags, resident);
+      int r = plonk_run_device(pvk, d, lease.ctx(w), device, proofs + off * proof_stride, proof_stride, d_rows ? nullptr : public_inputs + off * n_public * 32, n_public, m,
+                               status + off, flags, resident, d_rows ? d_rows + off * 64 : nullptr);
       if (r) {
         // work of this pass may still be enqueued on the context's streams: drain them before the lease hands the context (its staging, its term and status
         // buffers) to the next call
@@ -381,6 +386,10 @@ static int plonk_batch(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t
   }
   for (int w = 0; w < workers; w++) if (rcs[w]) return set_err(rcs[w], errs[w]);
   return BN254_OK;
+}
+int plonk_batch_rows(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* d_rows, size_t n, uint8_t* status, int device, unsigned flags,
+                     bool resident) {
+  return plonk_batch(pvk, proofs, proof_stride, nullptr, 2, n, status, device, flags, resident, d_rows);
 }
 
 extern "C" {

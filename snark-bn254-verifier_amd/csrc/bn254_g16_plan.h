@@ -156,4 +156,17 @@ inline G16CmpAlloc g16_cmp_alloc(size_t n) {
   return a;
 }
 
+// ---- SP1 public inputs (bn254_verify.h, "SP1 proofs from their public values"): the row scratch of a (key, device) ----------------------------------------------
+// An SP1 batch is hashed and verified in chunks of at most G16_MAX_BATCH proofs: per proof one 64-byte row vkey_hash | digest (the public inputs the raw
+// pipeline reads, n_public = 2) and one pre-status byte.  g16_sp1_alloc(n) is what a batch of n proofs needs (the pre bytes start at row_bytes, a multiple of
+// 256); ensure_sp1 grows the scratch to it and the enqueue checks every chunk against it.
+struct G16Sp1Alloc { size_t proofs, row_bytes, pre_bytes; };
+inline G16Sp1Alloc g16_sp1_alloc(size_t n) {
+  G16Sp1Alloc a;
+  a.proofs = g16_round256(n < (size_t)G16_MAX_BATCH ? n : (size_t)G16_MAX_BATCH);
+  a.row_bytes = a.proofs * 64;
+  a.pre_bytes = a.proofs;
+  return a;
+}
+
 }  // namespace bn254

@@ -130,6 +130,10 @@ hipError_t bn254_launch_scatter_status(uint8_t* status, const uint8_t* fb_status
 // (0 decompressed, 1 MALFORMED); after the raw pipeline, k_g16_status_merge writes MALFORMED over the status of every proof whose pre byte is set
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t s);
 hipError_t bn254_launch_g16_status_merge(uint8_t* status, const uint8_t* pre, uint32_t n, hipStream_t s);
+// SP1 public inputs (bn254_sha256.h): n proofs, proof i's values = bytes [off[i] - pv_base, off[i+1] - pv_base) of pv (pv_bytes long), its vkey hash the 32 bytes at
+// vkh + i vkh_stride -> the 64-byte row vkey_hash | digest at rows + 64 i and pre[i] (1: the range is not inside the buffer; k_g16_status_merge makes it MALFORMED)
+hipError_t bn254_launch_sp1_public_inputs(const uint8_t* vkh, size_t vkh_stride, const uint8_t* pv, uint64_t pv_bytes, uint64_t pv_base, const uint64_t* off, uint32_t n,
+                                          uint8_t* rows, uint8_t* pre, hipStream_t s);
 #define G1_GLV_TAB_BYTES_PER_LANE (16 * 28 * 4)
 // PlonK's G1 multi-scalar multiplications as rows of a plan (bn254_msm.h, bn254_k_msm.hip)
 namespace bn254 { struct MsmPlan; }

@@ -26,6 +26,7 @@
 #include "bn254_rlc.h"
 #include "bn254_g16_plan.h"
 #include "bn254_codec.h"
+#include "bn254_sha256.h"
 
 namespace bn254 {
 
@@ -715,6 +716,32 @@ __global__ void __launch_bounds__(256) k_g16_status_merge(uint8_t* __restrict__ 
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i < n && pre[i]) status[i] = BN254_ST_MALFORMED;
 }
+// SP1 public inputs (bn254_sha256.h): one proof per lane.  Lane i hashes bytes [off[i] - pv_base, off[i+1] - pv_base) of pv (pv_bytes long) and writes the 64-byte
+// row vkey_hash_i | digest_i to rows + 64 i, and pre[i] = 1 if the range is not inside the buffer (the row then carries the digest of the empty string).  The
+// block loop is wavefront-uniform: it runs to the longest message of the wavefront (a ballot of "this lane has a block left" ends it), and a lane that has no
+// block left computes and discards it -- no lane leaves early, so the 64 rounds run once per block for the whole wavefront.  About 1 850 VALU instructions
+// per block; the loads are aligned dwords.  No LDS, no scratch.
+__global__ void __launch_bounds__(256) k_sp1_public_inputs(const uint8_t* __restrict__ vkh, size_t vkh_stride, const uint8_t* __restrict__ pv, uint64_t pv_bytes,
+                                                           uint64_t pv_base, const uint64_t* __restrict__ off, uint32_t n, uint8_t* __restrict__ rows,
+                                                           uint8_t* __restrict__ pre) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const bool lane = i < n;
+  uint64_t start = 0, len = 0;
+  bool ok = false;
+  if (lane) ok = sp1_range(off[i], off[i + 1], pv_base, pv_bytes, &start, &len);
+  const uint64_t nb = lane ? sha256_blocks(len) : 0;
+  uint32_t h[8];
+  sha256_init(h);
+  for (uint64_t b = 0; __ballot(b < nb) != 0; b++) sp1_sha256_block(h, pv, pv_bytes, start, len, b);
+  if (!lane) return;
+  uint32_t v[8], dg[8];
+  sp1_load_vkey_hash(vkh + (size_t)i * vkh_stride, v);
+  sp1_digest_words(h, dg);
+  uint4* q = (uint4*)(rows + (size_t)i * 64);
+  q[0] = make_uint4(v[0], v[1], v[2], v[3]); q[1] = make_uint4(v[4], v[5], v[6], v[7]);
+  q[2] = make_uint4(dg[0], dg[1], dg[2], dg[3]); q[3] = make_uint4(dg[4], dg[5], dg[6], dg[7]);
+  pre[i] = ok ? 0 : 1;
+}
 
 // =====================================================================================================================
 // the issue rate of the instruction every field product is made of, measured on THIS device: sixteen independent v_mad_u64_u32 chains per lane, two
@@ -1035,6 +1062,11 @@ hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32
 }
 hipError_t bn254_launch_g16_status_merge(uint8_t* status, const uint8_t* pre, uint32_t n, hipStream_t s) {
   if (n) hipLaunchKernelGGL(k_g16_status_merge, dim3(grid_for(n)), dim3(256), 0, s, status, pre, n);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_sp1_public_inputs(const uint8_t* vkh, size_t vkh_stride, const uint8_t* pv, uint64_t pv_bytes, uint64_t pv_base, const uint64_t* off, uint32_t n,
+                                          uint8_t* rows, uint8_t* pre, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_sp1_public_inputs, dim3(grid_for(n)), dim3(256), 0, s, vkh, vkh_stride, pv, pv_bytes, pv_base, off, n, rows, pre);
   return hipGetLastError();
 }
 // lane-level multiply-adds per second of the current device: the best launch of k_valu_peak at four wavefronts per SIMD, each about 2 ms long (a
