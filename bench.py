@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- Groth16 batch-verify throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it generates the workload, warms up, times the K steps, checks their statuses,
+writes --dump-outputs and prints the line.  --full adds everything else the bench measures or checks, after the timed region: the
+multiply-add peak probe and the VALU rooflines priced against it, and at N = 1 `cpu_baseline`, `configs` and `rlc_mode` (below).
 
 N = 1 runs in this process.  N > 1: if the process was started by torch.distributed.run (WORLD_SIZE set) it is one rank of
 the job; otherwise bench.py starts the N ranks ITSELF -- `python -m torch.distributed.run --nproc-per-node N bench.py ...` as a
@@ -15,18 +19,18 @@ For N > 1 that batch is sharded: rank r verifies the contiguous range sharding.s
 GPU at N = 2 / 4 / 8 -- with no data-path communication: STRONG scaling, `global_batch` stays 2^20.  Every rank
 generates only its own range of the proof stream (bn254_synth_groth16_range).  --weak keeps 2^batch-log2 proofs PER GPU instead.
 After the timed region the statuses are compared with the generator's expected statuses: a wrong answer aborts the bench.
-At N = 1 the line also carries `configs`: the other BASELINE configurations (batch 4096, PlonK 4096, 1024 public inputs x 4096, the
-host-buffer entry at 2^20, single-proof latency), each timed in this run with its own roofline and status check.
+With --full at N = 1 the line also carries `configs`: the other BASELINE configurations (batch 4096, PlonK 4096, 1024 public inputs x 4096,
+the host-buffer entry at 2^20, single-proof latency), each timed in this run with its own roofline and status check.
 
 One JSON line on rank 0:
-  roofline      the binding bound of this path, the integer VALU: 32x32+64-bit multiply-adds of the dominant kernel kind (static count
+  roofline      (--full) the binding bound of this path, the integer VALU: 32x32+64-bit multiply-adds of the dominant kernel kind (static count
                 from the gfx950 code object, profiles/kernel_mads.json written by tools/count_mads.py) x proofs per launch / the
                 kernel's average launch duration (HIP events around every launch of that kind INSIDE the timed region, on the
                 launch stream), against the measured v_mad_u64_u32 issue peak (profiles/r01_ubench_valu.txt).  `traffic` = HBM
                 bytes per launch from the committed rocprofv3 --pmc passes (profiles/pmc_traffic.json).
   hbm_roofline  SURVEY.md section 8(d)'s algorithmic bytes (321 B/proof) x proofs/s against the HBM peak: the figure north_star
                 asks for, ~1e-4 because the path is arithmetic-bound.
-  cpu_baseline  the CPU oracle (C restatement of the reference algorithm) on this box's host cores on a bounded sample;
+  cpu_baseline  (--full) the CPU oracle (C restatement of the reference algorithm) on this box's host cores on a bounded sample;
                 rank 0, N = 1 only.  Rows: reference-faithful on all cores (the headline `value`), on one core, and batch mode.
 """
 import argparse
@@ -102,11 +106,14 @@ def parse_args(argv=None):
     ap.add_argument("--plonk", action="store_true", help="the PlonK path instead (BASELINE configs[3] at scale): one call of 2^batch-log2 proofs sharded over the GPUs like the "
                     "Groth16 batch (contiguous ranges, resident buffers, all_gather of the status bytes); prints its own line, not the headline metric")
     ap.add_argument("--weak", action="store_true", help="weak scaling: 2^batch-log2 proofs PER GPU (the global batch grows with --gpus)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (the other BASELINE configurations, N = 1 only)")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also measure and check everything beyond the headline figure: the multiply-add "
+                    "peak and the VALU rooflines, and at N = 1 `cpu_baseline`, `configs` and `rlc_mode` (each can be left out by its --no-* option); with --plonk: "
+                    "the peak, the rooflines, the oracle check of the first statuses and `cpu_baseline`")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the `configs` block (the other BASELINE configurations, N = 1 only)")
     ap.add_argument("--n-public", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--cpu-sample", type=int, default=16384, help="proofs timed on the host per cpu_baseline row")
-    ap.add_argument("--no-rlc", action="store_true", help="skip the rlc_mode side measurement (all-valid batch, exact against RLC)")
+    ap.add_argument("--no-rlc", action="store_true", help="with --full: skip the rlc_mode side measurement (all-valid batch, exact against RLC)")
     ap.add_argument("--rlc", action="store_true", help="time the random-linear-combination batch mode instead of the exact path")
     ap.add_argument("--host-buffers", action="store_true", help="also time the host-buffer entry (PCIe-inclusive), reported beside `value`")
     ap.add_argument("--rehearse-one-gpu", action="store_true", help="REHEARSAL of --gpus N on ONE GPU: N rank processes, all on cuda:0, gloo for the status gather and the "
@@ -309,7 +316,7 @@ def run_rank(args, make_verifier, backend, rank, world, local_rank, synth, emit=
             v.sync()                              # experiment: the host waits for every batch (what rounds 1-3a did through the per-step profile read)
     fence()
     elapsed = time.perf_counter() - t_start
-    if rank == 0 and getattr(v, "pkg", None) is not None:
+    if args.full and rank == 0 and getattr(v, "pkg", None) is not None:
         # the multiply-add peak of THIS box, measured while the GPU is as warm as it was in the timed region (an idle GPU reads 10 % low: its clocks take tens of
         # milliseconds of load to settle; at the start of the run the measurement said 29.7 .. 33.0 T, after the timed region it agrees with tools/ubench_valu)
         measure_valu_peak(v.pkg, v.local_rank)
@@ -368,8 +375,10 @@ def run_rank(args, make_verifier, backend, rank, world, local_rank, synth, emit=
             # equal to steps x sub-batches unless the event pool (1024 launches per sub-batch stream) filled up during a very long run
             per_pass_launches = breakdown.get(dom, (0, 0.0))[0] if breakdown_is_first_subbatch else 0
             passes = prof[dom][0] / per_pass_launches if per_pass_launches else args.steps * (2 if per_launch < n else 1)
-            out["roofline"] = _valu_roofline(dom, prof[dom], per_launch, passes=passes)
-            out["valu_whole_path"] = _valu_whole_path(breakdown, value / world)
+            if args.full:
+                # fractions of the peak that measure_valu_peak took after the timed region
+                out["roofline"] = _valu_roofline(dom, prof[dom], per_launch, passes=passes)
+                out["valu_whole_path"] = _valu_whole_path(breakdown, value / world)
             out["valu_issue_bound"] = _valu_issue_bound(breakdown, ms_per_step, n)
             out["hbm_roofline"]["traffic_bytes_per_proof"] = _traffic_whole_path(breakdown, algo)
         emit(json.dumps(out))
@@ -879,19 +888,21 @@ def run_rank_plonk(args, pkg, backend, rank, world, local_rank, rehearse):
         full = step()
     fence()
     elapsed = time.perf_counter() - t_start
-    if rank == 0:
+    if args.full and rank == 0:
         measure_valu_peak(pkg, local_rank)
     if grouped:
         t = torch.tensor([elapsed], dtype=torch.float64, device=torch.device("cpu") if backend == "gloo" else dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # correctness of the timed work: the shard's bytes (ACCEPT exactly where the workload left the inputs alone; the first 16 against the oracle), and the gathered vector
+    # correctness of the timed work: the shard's bytes (ACCEPT exactly where the workload left the inputs alone; with --full the first 16 against the oracle), and the
+    # gathered vector
     st = bytes(d_st.cpu().numpy().tobytes())
     assert all((st[i - lo] == pkg.ACCEPT) == (i % 8 != 7) for i in range(lo, hi)), "rank %d: PlonK statuses differ from the workload's" % rank
-    from oracle import oracle as O
-    m = min(16, n)
-    assert st[:m] == bytes(O.plonk_verify(proofs[lo + i], vk, [int.from_bytes(inputs[lo + i][:32], "big"), int.from_bytes(inputs[lo + i][32:], "big")]) for i in range(m)), \
-        "rank %d: PlonK statuses differ from the oracle" % rank
+    if args.full:
+        from oracle import oracle as O
+        m = min(16, n)
+        assert st[:m] == bytes(O.plonk_verify(proofs[lo + i], vk, [int.from_bytes(inputs[lo + i][:32], "big"), int.from_bytes(inputs[lo + i][32:], "big")]) for i in range(m)), \
+            "rank %d: PlonK statuses differ from the oracle" % rank
     assert full.numel() == n_total and bytes(full[lo:hi].cpu().numpy().tobytes()) == st, "gathered statuses are wrong"
     if rank != 0:
         return None
@@ -899,12 +910,6 @@ def run_rank_plonk(args, pkg, backend, rank, world, local_rank, rehearse):
         dump_outputs(args.dump_outputs, full)
     value = n_total * args.steps / elapsed
     stage_ms, _lanes = pvk.last_timing(local_rank)
-    km = (_load_json("kernel_mads.json") or {}).get("kernels", {})
-    acct = _plonk_accounting(pkg, km, n, stage_ms)
-    whole = acct["whole"]
-    if whole:
-        ach = whole["mads_per_proof"] * value / world
-        whole.update({"achieved": ach / 1e12, **_peak_fields(), "unit": "T mad/s", **_fracs(ach)})
     out = {"metric": "PlonK verifies/sec (2 pub-inputs) at batch=2^%d%s%s" % (args.batch_log2, " per GPU" if args.weak else "", ", RLC batch mode" if args.rlc else ""),
            "value": value, "unit": "proofs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed * 1e3 / args.steps,
            "higher_is_better": True, "scaling": "weak" if args.weak else "strong", "vs_baseline": None, "dtype": "int64", "data": "synthetic",
@@ -914,8 +919,18 @@ def run_rank_plonk(args, pkg, backend, rank, world, local_rank, rehearse):
                       "batch_per_gpu": n, "global_batch": n_total, "n_public": 2, "mode": "rlc (one pairing check per 64 proofs, exact fallback)" if args.rlc else "exact",
                       "parallelism": "independent contiguous proof shards x%d + all_gather of status bytes" % world, "gen_seconds": round(gen_s, 1),
                       "context_footprint": dict(zip(("bytes", "contexts"), pvk.footprint(local_rank)))},
-           "stages_ms": stage_ms, "roofline": acct["roofline"], "pairing_check": acct["pairing"], "valu_whole_path": whole,
-           "status_check": "every status byte of every shard == the workload's (ACCEPT unless the inputs were mutated); first 16 of each shard == oracle; gathered vector checked"}
+           "stages_ms": stage_ms,
+           "status_check": "every status byte of every shard == the workload's (ACCEPT unless the inputs were mutated); %sgathered vector checked"
+                           % ("first 16 of each shard == oracle; " if args.full else "")}
+    if not args.full:
+        return out
+    km = (_load_json("kernel_mads.json") or {}).get("kernels", {})
+    acct = _plonk_accounting(pkg, km, n, stage_ms)
+    whole = acct["whole"]
+    if whole:
+        ach = whole["mads_per_proof"] * value / world
+        whole.update({"achieved": ach / 1e12, **_peak_fields(), "unit": "T mad/s", **_fracs(ach)})
+    out.update(roofline=acct["roofline"], pairing_check=acct["pairing"], valu_whole_path=whole)
     if world == 1 and not args.no_cpu_baseline:
         m = min(512, n)
         t = time.perf_counter()
@@ -1001,13 +1016,13 @@ def main(argv=None):
             out["config"]["parallelism"] += " [rehearsal on one GPU]"
         if world == 1:
             headline = (args.n_public, args.batch_log2, bool(args.rlc), bool(args.weak)) == (2, 20, False, False)
-            if not args.no_cpu_baseline:
+            if args.full and not args.no_cpu_baseline:
                 out["cpu_baseline"] = _cpu_baseline(args, keep["vk"], keep["proofs"], keep["inputs"], keep["expected0"])
-            if headline and not args.no_configs:
+            if args.full and headline and not args.no_configs:
                 out["configs"] = other_configs(args, pkg, local_rank, out["value"], keep)
             elif args.host_buffers:
                 out["host_buffers"] = _host_buffer_line(args, pkg, keep["vk"], keep["proofs"], keep["inputs"], keep["expected0"], local_rank)
-            if not args.no_rlc and not args.rlc and args.n_public <= 8:
+            if args.full and not args.no_rlc and not args.rlc and args.n_public <= 8:
                 out["rlc_mode"] = _rlc_line(args, pkg, local_rank)
         print(json.dumps(out), flush=True)
     if use_dist:

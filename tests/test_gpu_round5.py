@@ -163,12 +163,12 @@ def test_tables_built_on_device_match_the_host_construction(pkg, fixtures):
 
 
 def test_bench_plonk_mode_prints_the_contract_line():
-    """`python bench.py --plonk` (one PlonK call sharded like the Groth16 batch; here 2^12 proofs on one GPU): ONE JSON line with the fields of the bench contract, the PlonK
-    metric name, a roofline and a CPU baseline; its own checks (every status byte against the workload, the first 16 against the oracle, the gathered vector) have passed
-    when it prints."""
+    """`python bench.py --plonk --full` (one PlonK call sharded like the Groth16 batch; here 2^12 proofs on one GPU): ONE JSON line with the fields of the bench contract, the
+    PlonK metric name, a roofline and a CPU baseline; its own checks (every status byte against the workload, the first 16 against the oracle, the gathered vector) have
+    passed when it prints."""
     import json, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--plonk", "--batch-log2", "12", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--plonk", "--full", "--batch-log2", "12", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -177,3 +177,32 @@ def test_bench_plonk_mode_prints_the_contract_line():
         assert k in d, k
     assert d["metric"].startswith("PlonK verifies/sec") and d["n_gpus"] == 1 and d["steps"] == 2 and d["value"] > 1e5 and d["config"]["global_batch"] == 4096
     assert d["roofline"]["bound"] == "valu" and 0 < d["roofline"]["frac"] < 1 and d["cpu_baseline"]["kind"] == "port"
+
+
+def test_bench_plain_run_leaves_the_side_measurements_to_full(pkg):
+    """`python bench.py --gpus 1 --steps K --warmup W` (here at 2^12 proofs) does only what its headline figure needs: the contract fields, its statuses checked and
+    dumped.  The multiply-add peak probe with the rooflines priced against it, `cpu_baseline` and `rlc_mode` come with --full, which still carries all of them."""
+    import json, subprocess, sys, tempfile
+    import numpy as np
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = {}, {}
+    with tempfile.TemporaryDirectory() as td:
+        for full in (False, True):
+            d = os.path.join(td, "full" if full else "plain")
+            cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--batch-log2", "12", "--steps", "2", "--warmup", "1", "--dump-outputs", d]
+            r = subprocess.run(cmd + (["--full", "--cpu-sample", "256"] if full else []), capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            out = [l for l in r.stdout.splitlines() if l.startswith("{")]
+            assert len(out) == 1
+            lines[full], dumps[full] = json.loads(out[0]), np.load(os.path.join(d, "status.npy"))
+    exp = pkg.synth_groth16(bench.SEED, 2, 4096, invalid_every=16, agree=True, threads=16)[3]
+    extras = {"roofline", "valu_whole_path", "cpu_baseline", "rlc_mode"}
+    for full, d in lines.items():
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in d, k
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["config"]["global_batch"] == 4096 and d["value"] > 0
+        assert bytes(dumps[full].astype(np.uint8)) == exp
+    assert not extras & set(lines[False]), extras & set(lines[False])
+    assert extras <= set(lines[True]), extras - set(lines[True])
+    assert lines[True]["roofline"]["peak_measured"] and lines[True]["cpu_baseline"]["kind"] == "port"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """PlonK batch verification rate (BASELINE configs[3]: batch 4096, SP1 circuit, 2 public inputs) on one MI355X: bench.plonk_config as a
-stand-alone command (the default bench.py run carries the same measurement in its `configs` block).  Prints one JSON line."""
+stand-alone command (`bench.py --full` carries the same measurement in its `configs` block).  Prints one JSON line."""
 import argparse, importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

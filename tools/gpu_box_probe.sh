@@ -4,8 +4,8 @@
 # (inside both bench lines).  TAG=name of the output files.
 set -o pipefail
 O=$PWD/gpurun_out/r05v; mkdir -p $O; T=${TAG:-box}
-python bench.py --steps 10 --warmup 3 --no-configs --no-cpu-baseline --no-rlc > $O/$T.json 2> $O/$T.err || { tail -5 $O/$T.err; exit 1; }
-BN254_STREAMS=1 python bench.py --steps 5 --warmup 2 --no-configs --no-cpu-baseline --no-rlc > $O/${T}_one_stream.json 2> $O/${T}_one_stream.err || { tail -5 $O/${T}_one_stream.err; exit 1; }
+python bench.py --full --steps 10 --warmup 3 --no-configs --no-cpu-baseline --no-rlc > $O/$T.json 2> $O/$T.err || { tail -5 $O/$T.err; exit 1; }
+BN254_STREAMS=1 python bench.py --full --steps 5 --warmup 2 --no-configs --no-cpu-baseline --no-rlc > $O/${T}_one_stream.json 2> $O/${T}_one_stream.err || { tail -5 $O/${T}_one_stream.err; exit 1; }
 python - > $O/$T.copy_rate <<'PY'
 import torch, json
 a = torch.empty(1 << 30, dtype=torch.uint8, device="cuda"); b = torch.empty_like(a)
@@ -30,7 +30,7 @@ if [ -n "$CARD" ]; then
       sleep 0.05
     done ) > $O/$T.clock_samples 2>/dev/null &
   SAMPLER=$!
-  python bench.py --steps 20 --warmup 3 --no-configs --no-cpu-baseline --no-rlc > $O/${T}_sampled.json 2> $O/${T}_sampled.err
+  python bench.py --full --steps 20 --warmup 3 --no-configs --no-cpu-baseline --no-rlc > $O/${T}_sampled.json 2> $O/${T}_sampled.err
   kill $SAMPLER 2>/dev/null
   wait $SAMPLER 2>/dev/null
   wc -l $O/$T.clock_samples

@@ -22,7 +22,7 @@ for mode in ("device", "host"):
     pvk.close() if hasattr(pvk, "close") else None
 PY
 cat $O/wide_key_costs.txt
-python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-rlc > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
+python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-rlc > $O/bench.json 2> $O/bench.err || { tail -5 $O/bench.err; exit 1; }
 python - <<'PY'
 import json
 d=None

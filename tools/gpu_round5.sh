@@ -13,8 +13,8 @@ python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1 || fail pytest $O/p
 tail -2 $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
 tail -1 $O/smoke.log
-python bench.py > $O/bench_default.json 2> $O/bench_default.err || fail bench_default $O/bench_default.err
-python bench.py --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || fail bench_default $O/bench_default.err
+python bench.py --full --steps 10 --warmup 3 > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err
 cut -c1-300 $O/bench.json
 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 1 --steps 3 --warmup 1 --no-configs --no-cpu-baseline --no-rlc > $O/bench_torchrun.json 2> $O/bench_torchrun.err || fail torchrun $O/bench_torchrun.err
 python bench.py --gpus 2 --rehearse-one-gpu --steps 3 --warmup 1 --no-configs --no-cpu-baseline --no-rlc > $O/bench_rehearse2.json 2> $O/bench_rehearse2.err || fail rehearse $O/bench_rehearse2.err
