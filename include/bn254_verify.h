@@ -160,6 +160,37 @@ int bn254_groth16_verify_batch_device(const bn254_g16_pvk* pvk, const void* d_pr
 /* pre-allocate the per-device workspace for batches of up to n proofs and upload the key's tables */
 int bn254_groth16_reserve(const bn254_g16_pvk* pvk, size_t n, int device);
 
+/* ---- Batches over many keys ---------------------------------------------------------------------------------------------------------------------------------
+ * One call for proofs of many circuits.  pvks: a list of n_keys prepared keys (1 .. 65 536 entries; a handle may occur more than once; keys prepared with different
+ * `mode`s may share a list).  Proof i is verified against pvks[key_index[i]] (key_index: n 32-bit unsigned little-endian words).  Its public inputs are the first
+ * 32 * num_public(that key) bytes of row i of public_inputs; rows are input_stride bytes apart, and input_stride must be at least 32 * the largest num_public of the
+ * list, else BN254_E_BAD_ARG (a list of keys without inputs may pass a null pointer and stride 0).
+ *   DEFINITION OF CORRECTNESS: status[i] equals, byte for byte, what bn254_groth16_verify_batch(pvks[key_index[i]], proof_i, inputs_i, n_public =
+ * bn254_groth16_vk_num_public(that key), 1, ..., flags without BN254_FLAG_RLC) writes; for a key without K points (num_public == SIZE_MAX), what that call writes
+ * with n_public = 0.  n_keys == 1 gives the single-key bytes.
+ *   key_index[i] >= n_keys: the host-buffer entry checks the whole vector first and returns BN254_E_BAD_ARG without touching status; the device entry cannot, writes
+ * BN254_ERR_MALFORMED for that proof and verifies the others.
+ *   Flags: BN254_FLAG_STRICT_SCALARS (the inputs checked are those of the proof's key) and BN254_FLAG_COMPRESSED_PROOFS work as in the single-key entries.
+ * BN254_FLAG_RLC is accepted and IGNORED: by its contract the status bytes are those of the exact path, and that is the path a mixed batch takes (groups of the
+ * random-linear-combination mode are per key; mixed-key groups do not exist yet).
+ *   Limits of this revision, refused with BN254_E_BAD_ARG and a text in bn254_last_diagnostic(): a key with more than 16 public inputs in the list (such keys run
+ * the wide multi-scalar-multiplication kernels, a different pipeline: one bn254_groth16_verify_batch call per key), and more than 65 536 entries.
+ *   How it runs: the proofs are grouped on the device so that every wavefront (64 lanes) works for one key -- at most 63 idle lanes per key that has proofs, so the
+ * workspace is that of n + min(n_keys, n) * 63 proofs -- and the one-proof-per-lane kernels run at every size: a SMALL mixed batch does not get the cooperative
+ * small-batch kernels or the latency mode of the single-key entries.  The host-buffer entry uploads index, records and input rows first (through pinned memory) and
+ * then runs the same pipeline; it returns when the status bytes are back.
+ *   Device state of a list: kept per (list of handles in order, device), the four most recently used lists, least recently used out first; bn254_groth16_vk_free of
+ * a member drops every cached list that contains it (and a call with a list that names a freed key is undefined, as any use of a freed handle).  A list does NOT
+ * build its members' own per-device tables (13 MB per K point): it keeps 38.5 KB of line tables per distinct key and byte-window tables of 652 800 bytes per K point
+ * (a 2-input key: 1.3 MB; 4096 of them: 5.4 GB), built on the device at the list's first use.  bn254_groth16_reserve_keys returns BN254_E_NOMEM when they do not fit.
+ *   bn254_groth16_reserve_keys does for a list what bn254_groth16_reserve does for a key: after it, a _device call with the same handles in the same order and up
+ * to n proofs (raw records) allocates nothing and copies nothing from pageable memory.  The _device entry only enqueues on hip_stream (NULL = default stream). */
+int bn254_groth16_verify_batch_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride,
+                                    const uint8_t* public_inputs, size_t input_stride, size_t n, uint8_t* status, int device, unsigned flags);
+int bn254_groth16_verify_batch_keys_device(const bn254_g16_pvk* const* pvks, size_t n_keys, const void* d_key_index, const void* d_proofs, size_t proof_stride,
+                                           const void* d_public_inputs, size_t input_stride, size_t n, void* d_status, int device, void* hip_stream, unsigned flags);
+int bn254_groth16_reserve_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, size_t n, int device);
+
 /* Groth16Verifier::verify (lib.rs:44-49) as one call: one proof, one status byte, vk given as bytes on every call like the
  * reference.  The prepared form of the last four keys (exact byte match, per mode) is kept, so only the first call with a key pays
  * its preparation (about 6.5 ms of an 8.5 ms call; 2 ms afterwards: profiles/r05_new_key_cost.txt); BN254_KEY_CACHE=0 in the environment switches the cache off, BN254_KEY_CACHE=N (1 .. 64) keeps the last N keys (default 4).
@@ -429,10 +460,16 @@ int bn254_dbg_key_cache_slots(void);
  * than 16 public inputs): every entry of the first `inputs` inputs against bn254_host.hpp::build_comb_table.  13-bit window tables (up to 16 inputs): every window's first,
  * middle and last entries and a pseudo-random sample of every input, each against d 2^(13 w) K by double-and-add. */
 int bn254_dbg_comb_table_compare(const bn254_g16_pvk* pvk, int device, int inputs, size_t* mismatches);
+/* the grouping of a batch over many keys (csrc/bn254_keys.h): slot -> proof index (all ones: a padding slot) and granule (64 slots) -> key.  out_slot_to_proof holds
+ * bn254_dbg_g16_keys_slot_bound(n, n_keys) words, out_granule_key a word per 64 of them; *out_n_slots: slots in use.  device -1: compiled for the host; >= 0: the
+ * kernels on that device */
+size_t bn254_dbg_g16_keys_slot_bound(size_t n, size_t n_keys);
+int bn254_dbg_g16_keys_group(const unsigned* key_index, size_t n, size_t n_keys, int device, unsigned* out_slot_to_proof, unsigned* out_granule_key, size_t* out_n_slots);
 int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t* mismatches);   /* the window tables of a PlonK key's points (csrc/bn254_fw.h): every window's first, middle and last entries and a pseudo-random sample */
 
-/* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5: this round --
- * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  A binding compares it with the value it was generated for. */
+/* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
+ * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
+ * keys -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

@@ -216,6 +216,21 @@ struct Groth16Verifier {
     for (size_t i = 0; i < n; i++) if (is_short[i]) st[i] = BN254_ERR_MALFORMED;      // a buffer the loader cannot slice: a panic in the reference
     return st;
   }
+  // one batch over many keys (bn254_verify.h, "Batches over many keys"): proof i is verified against keys[key_index[i]]; its inputs are the first
+  // 32 x num_public(that key) bytes of row i of public_inputs (input_stride bytes per row).  Keys with more than 16 public inputs are refused.
+  static Bytes verify_batch_keys(const std::vector<const PreparedGroth16Vk*>& keys, const std::vector<unsigned>& key_index, const uint8_t* proofs, size_t stride,
+                                 const uint8_t* public_inputs, size_t input_stride, int device = 0, unsigned flags = 0) {
+    std::vector<const bn254_g16_pvk*> h(keys.size());
+    for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
+    Bytes st(key_index.size());
+    detail::check(bn254_groth16_verify_batch_keys(h.data(), h.size(), key_index.data(), proofs, stride, public_inputs, input_stride, key_index.size(), st.data(), device, flags));
+    return st;
+  }
+  static void reserve_keys(const std::vector<const PreparedGroth16Vk*>& keys, size_t n, int device = 0) {
+    std::vector<const bn254_g16_pvk*> h(keys.size());
+    for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
+    detail::check(bn254_groth16_reserve_keys(h.data(), h.size(), n, device));
+  }
   static Result<bool, Groth16Error> outcome(uint8_t status) { return detail::groth16_outcome(status); }
 };
 

@@ -143,6 +143,25 @@ impl Groth16Verifier {
             s => panic!("loader error {s:?}"),           // lib.rs:45-46: unwrap() of Field / Group / InvalidPoint errors
         }
     }
+    /// One batch over many keys (`bn254_groth16_verify_batch_keys`): proof `i` is verified against `keys[key_index[i]]`; its inputs are the first
+    /// `32 * num_public(that key)` bytes of row `i` of `public_inputs` (`input_stride` bytes per row, at least 32 x the largest input count of the list).  A key may
+    /// occur more than once in `keys`; keys with more than 16 public inputs and an index outside the list are refused (`BN254_E_BAD_ARG`).  `FLAG_RLC` is accepted
+    /// and ignored.  The device state of the list is cached by the library under the handles in order.
+    pub fn verify_batch_keys(keys: &[&PreparedGroth16Vk], key_index: &[u32], proofs: &[u8], proof_stride: usize, public_inputs: &[u8], input_stride: usize, device: i32,
+                             flags: u32) -> Result<Vec<Status>, Error> {
+        let n = key_index.len();
+        assert!(proof_stride >= g16_min_stride(flags) && proofs.len() >= n * proof_stride && public_inputs.len() >= n * input_stride);
+        let h: Vec<*const sys::Bn254G16Pvk> = keys.iter().map(|k| k.h as *const sys::Bn254G16Pvk).collect();
+        let mut st = vec![0u8; n];
+        check(unsafe { sys::bn254_groth16_verify_batch_keys(h.as_ptr() as *mut *const sys::Bn254G16Pvk, h.len(), key_index.as_ptr(), proofs.as_ptr(), proof_stride, public_inputs.as_ptr(), input_stride, n,
+                                                            st.as_mut_ptr(), device, flags) })?;
+        Ok(st.into_iter().map(Status::from).collect())
+    }
+    /// Tables and workspace of a key list ahead of its first batch of up to `n` proofs (`bn254_groth16_reserve_keys`).
+    pub fn reserve_keys(keys: &[&PreparedGroth16Vk], n: usize, device: i32) -> Result<(), Error> {
+        let h: Vec<*const sys::Bn254G16Pvk> = keys.iter().map(|k| k.h as *const sys::Bn254G16Pvk).collect();
+        check(unsafe { sys::bn254_groth16_reserve_keys(h.as_ptr() as *mut *const sys::Bn254G16Pvk, h.len(), n, device) })
+    }
     /// New: N proofs against one key, one `Status` each; nothing panics.
     pub fn verify_batch(proofs: &[&[u8]], vk: &[u8], public_inputs: &[&[[u8; 32]]]) -> Result<Vec<Status>, Error> {
         Self::verify_batch_opts(proofs, vk, public_inputs, false)

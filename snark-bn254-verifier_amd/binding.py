@@ -462,6 +462,63 @@ class PreparedVk:
             pass
 
 
+class KeySet:
+    """A list of prepared Groth16 keys for batches over many keys (bn254_groth16_verify_batch_keys): proof i is verified against keys[key_index[i]].  keys: PreparedVk
+    objects (one may occur more than once); the list keeps them alive.  Keys with more than 16 public inputs are refused by the library."""
+
+    def __init__(self, keys):
+        self.keys = list(keys)
+        self._arr = (C.c_void_p * max(len(self.keys), 1))(*[k.handle.value for k in self.keys])
+        self.input_stride = 32 * max([k.n_public for k in self.keys if k.n_public != C.c_size_t(-1).value] or [0])
+
+    def _index(self, key_index):
+        import array
+        a = array.array("I", key_index)
+        assert a.itemsize == 4
+        return a
+
+    def verify_batch(self, key_index, proofs, public_inputs, n=None, proof_stride=None, input_stride=None, device=0, flags=0, compressed=False):
+        """key_index: n ints; proofs: n records; public_inputs: n rows of input_stride bytes (default: 32 x the largest input count of the list), row i holding the
+        inputs of proof i's key first.  Returns n status bytes."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
+        idx = self._index(key_index)
+        n = len(idx) if n is None else n
+        st = (C.c_uint8 * max(n, 1))()
+        fn = lib().bn254_groth16_verify_batch_keys
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_uint]
+        _check(fn(self._arr, len(self.keys), idx.buffer_info()[0] if len(idx) else None, bytes(proofs), proof_stride, bytes(public_inputs),
+                  self.input_stride if input_stride is None else input_stride, n, st, device, flags))
+        return bytes(st)[:n]
+
+    def verify_batch_device(self, d_key_index, d_proofs, d_inputs, d_status, n, proof_stride=None, input_stride=None, device=0, stream=None, flags=0, compressed=False):
+        """Raw device pointers (ints; d_key_index: n uint32 values); enqueues on `stream` (a hipStream_t value) and returns."""
+        flags, proof_stride = _g16_layout(flags, proof_stride, compressed)
+        fn = lib().bn254_groth16_verify_batch_keys_device
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+        _check(fn(self._arr, len(self.keys), d_key_index, d_proofs, proof_stride, d_inputs, self.input_stride if input_stride is None else input_stride, n, d_status, device,
+                  stream, flags))
+
+    def reserve(self, n, device=0):
+        fn = lib().bn254_groth16_reserve_keys
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
+        _check(fn(self._arr, len(self.keys), n, device))
+
+
+def dbg_keys_group(key_index, n_keys, device=-1):
+    """The grouping of a batch over many keys (bn254_dbg_g16_keys_group; device -1: the host compile of csrc/bn254_keys.h): (slot_to_proof, granule_key, n_slots) --
+    slot_to_proof has the workspace bound's length (0xffffffff: no proof), granule_key one entry per 64 slots."""
+    import array
+    L = lib()
+    L.bn254_dbg_g16_keys_slot_bound.argtypes = [C.c_size_t, C.c_size_t]; L.bn254_dbg_g16_keys_slot_bound.restype = C.c_size_t
+    L.bn254_dbg_g16_keys_group.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t)]
+    idx = array.array("I", key_index)
+    bound = L.bn254_dbg_g16_keys_slot_bound(len(idx), n_keys)
+    s2p = array.array("I", bytes(4 * bound)); gk = array.array("I", bytes(4 * (bound // 64)))
+    ns = C.c_size_t(0)
+    _check(L.bn254_dbg_g16_keys_group(idx.buffer_info()[0], len(idx), n_keys, device, s2p.buffer_info()[0], gk.buffer_info()[0] if len(gk) else None, C.byref(ns)))
+    return s2p, gk, int(ns.value)
+
+
 class Groth16Verifier:
     """Mirror of the reference's `Groth16Verifier` (verifier/src/lib.rs:29-49)."""
 

@@ -27,6 +27,39 @@ int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t pro
   return BN254_OK;
 }
 
+int check_key_list(const bn254_g16_pvk* const* pvks, size_t n_keys, size_t* max_public) {
+  if (!pvks || n_keys == 0) return set_err(BN254_E_BAD_ARG, "bad argument: empty key list");
+  if (n_keys > (size_t)G16_KEYS_MAX_KEYS) {
+    set_diag("a key list holds at most " + std::to_string(G16_KEYS_MAX_KEYS) + " entries (got " + std::to_string(n_keys) + ")");
+    return set_err(BN254_E_BAD_ARG, "key list too long");
+  }
+  size_t mx = 0;
+  for (size_t k = 0; k < n_keys; k++) {
+    if (!pvks[k]) return set_err(BN254_E_BAD_ARG, "bad argument: null key in the list");
+    const size_t ki = pvks[k]->host.key_inputs();
+    if (ki > (size_t)G16_KEYS_MAX_PUBLIC) {
+      set_diag("entry " + std::to_string(k) + " of the key list has " + std::to_string(ki) + " public inputs: batches over many keys take keys with up to " +
+               std::to_string(G16_KEYS_MAX_PUBLIC) + " (wider keys run the wide MSM kernels: one call per key, bn254_groth16_verify_batch)");
+      return set_err(BN254_E_BAD_ARG, "a key of the list has more than 16 public inputs");
+    }
+    if (ki > mx) mx = ki;
+  }
+  *max_public = mx;
+  return BN254_OK;
+}
+int check_keys_args(const bn254_g16_pvk* const* pvks, size_t n_keys, const void* key_index, const void* proofs, size_t proof_stride, const void* inputs, size_t input_stride,
+                    size_t n, const void* status, unsigned flags, size_t* max_public) {
+  int rc = check_key_list(pvks, n_keys, max_public);
+  if (rc) return rc;
+  // records, status and flags as in every Groth16 batch entry (the input rows are checked below: their width is the list's, not an argument)
+  if ((rc = check_batch_args(false, pvks, proofs, proof_stride, nullptr, 0, n, status, flags))) return rc;
+  if (n && !key_index) return set_err(BN254_E_BAD_ARG, "bad argument: null key index");
+  if (input_stride < 32 * *max_public) return set_err(BN254_E_BAD_ARG, "input_stride is smaller than the inputs of the widest key of the list (32 bytes each)");
+  if (n && *max_public && !inputs) return set_err(BN254_E_BAD_ARG, "bad argument: null public inputs");
+  if (n && (input_stride > SIZE_MAX / n || bn254::keys_slot_bound(n, n_keys) > 0xffff0000ull)) return set_err(BN254_E_BAD_ARG, "batch too large: slots and input rows are addressed with 32 / 64 bits");
+  return BN254_OK;
+}
+
 int check_device(int device) {
   int cnt = 0;
   hipError_t e = hipGetDeviceCount(&cnt);
@@ -300,6 +333,12 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 #include "bn254_capi_plonk.hip"
 #include "bn254_capi_sp1.hip"
 #include "bn254_capi_dbg.hip"
+// batches over many keys: tests/hostsan/hostsan_keys.cpp brings the file and stand-ins for its launchers; the older harness only needs the hook of bn254_groth16_vk_free
+#if defined(BN254_HOSTSAN_KEYS)
+#include "bn254_capi_keys.hip"
+#else
+void keys_sets_drop(const bn254_g16_pvk*) {}
+#endif
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {

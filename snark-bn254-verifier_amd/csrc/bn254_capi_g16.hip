@@ -9,6 +9,7 @@
 // that runs two sub-batch streams brackets them with events, the next call reads the overlap (bn254_groth16_stream_overlap), and a device whose sub-batch streams
 // were found to run one after the other gets one sub-batch per launch from then on (same work, fewer launches) and a line in bn254_last_diagnostic().
 static thread_local std::string g_diag;
+void set_diag(const std::string& msg) { g_diag = msg; }
 static std::atomic<int> g_profiling{0};
 static std::atomic<unsigned> g_prof_mask{0xffffffffu};
 static std::atomic<unsigned> g_prof_epoch{0};   // bumped by the two profiling setters: an accumulating profile (mode 2) starts over at the next batch
@@ -174,6 +175,7 @@ int bn254_groth16_vk_prepare(const uint8_t* vk, size_t vk_len, unsigned mode, bn
 }
 void bn254_groth16_vk_free(bn254_g16_pvk* pvk) {
   if (!pvk) return;
+  keys_sets_drop(pvk);     // cached key sets that contain the key hold copies of its tables and its handle
   for (auto& kv : pvk->dev) {
     if (hipSetDevice(kv.first) != hipSuccess) continue;
     (void)hipDeviceSynchronize();

@@ -217,6 +217,13 @@ int set_err(int code, const std::string& msg);
 int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* inputs, size_t n_public, size_t n, const void* status,
                      unsigned flags);
 int check_device(int device);
+// a batch over a key list (bn254_capi_keys.hip): the list itself (every handle non-null, at most G16_KEYS_MAX_KEYS entries, no key above G16_KEYS_MAX_PUBLIC inputs; the
+// limits are refused with a bn254_last_diagnostic() text) -> *max_public, the largest input count; then the batch arguments against it
+int check_key_list(const bn254_g16_pvk* const* pvks, size_t n_keys, size_t* max_public);
+int check_keys_args(const bn254_g16_pvk* const* pvks, size_t n_keys, const void* key_index, const void* proofs, size_t proof_stride, const void* inputs, size_t input_stride,
+                    size_t n, const void* status, unsigned flags, size_t* max_public);
+void set_diag(const std::string& msg);     // bn254_last_diagnostic() of the calling thread (bn254_capi_g16.hip)
+void keys_sets_drop(const bn254_g16_pvk* member);   // bn254_capi_keys.hip: forget every cached key set that contains this key
 void parallel_copy(uint8_t* dst, const uint8_t* src, size_t bytes);
 int build_tables_on_device(int form, const std::vector<int32_t>& pts, int32_t** dst);
 // bn254_capi_g16.hip

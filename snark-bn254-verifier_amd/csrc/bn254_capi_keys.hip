@@ -1,0 +1,366 @@
+// bn254_capi_keys.hip -- Groth16 batches over many verifying keys in one call (include/bn254_verify.h, "Batches over many keys"): the per (key list, device) state --
+// descriptors, the keys' line tables, byte-window tables of all their K points in one allocation, the slot workspace -- its cache, and the three entries.
+// The kernels are in bn254_k_keys.hip / bn254_k_miller.hip, the grouping arithmetic in bn254_keys.h.
+#include "bn254_capi_internal.h"
+#include "bn254_keys.h"
+
+using bn254::G16KeyDesc;
+
+// A set does NOT make its members' own per-device state ready: ensure_dev builds a key's 13-bit window tables (13 MB per K point, bn254_fw.h), and a key that is only
+// used through sets must never cost that.  The set keeps, per DISTINCT handle of the list (a handle may occur many times): both line tables, K[0] and e(alpha, beta)
+// from the key's host half (KEYS_BLOB_DWORDS dwords, 38.5 KB) and byte-window tables of K[1..] (bn254_k_comb.hip form 1: 32 x 255 entries of 80 bytes = 652 800 bytes
+// per point), all keys in one allocation each.
+#define KEYS_BLOB_DWORDS ((size_t)2 * BN_ATE_STEPS * FIXED_LINE_DWORDS + 2 * BN_NL + 12 * BN_NL)
+#define KEYS_TABLE_BYTES_PER_POINT ((size_t)32 * 255 * MSM_ENTRY_DWORDS * 4)
+#define KEYS_HOST_RING 3
+#define KEYS_HOST_PIECE ((size_t)16 << 20)
+
+namespace {
+
+struct KeySet {
+  std::vector<const bn254_g16_pvk*> list;   // the handles as passed (order matters: key_index refers to it)
+  int device = 0;
+  size_t max_public = 0;
+  std::mutex mu;                            // everything below: uploads, (re)allocation and the enqueue of a batch
+  bool ready = false;
+  int32_t *blob = nullptr, *msm = nullptr; G16KeyDesc* desc = nullptr;
+  // what a reservation of n proofs sizes: the slot workspace (one chunk), the grouping buffers over keys_slot_bound(n, n_keys) slots
+  size_t cap_n = 0, slot_cap = 0, ws_cap = 0;
+  int32_t* ws = nullptr;
+  uint32_t *count = nullptr, *base = nullptr, *cursor = nullptr, *n_slots = nullptr, *slot_to_proof = nullptr, *granule_key = nullptr;
+  uint8_t* slot_status = nullptr;
+  uint8_t* cmp = nullptr; size_t cmp_cap = 0;                       // BN254_FLAG_COMPRESSED_PROOFS: raw records of the whole batch, then one pre-status byte per proof
+  hipStream_t aux = nullptr; hipEvent_t fork_ev = nullptr, join_ev = nullptr, busy_ev = nullptr; bool busy_valid = false;
+  // host-buffer entry: device copies of the caller's buffers, the pinned ring they travel through, its streams
+  uint8_t *st_proofs = nullptr, *st_inputs = nullptr, *st_index = nullptr, *st_status = nullptr; size_t st_proofs_cap = 0, st_inputs_cap = 0, st_index_cap = 0, st_status_cap = 0;
+  uint8_t* pin[KEYS_HOST_RING] = {nullptr, nullptr, nullptr}; hipEvent_t pin_ev[KEYS_HOST_RING] = {nullptr, nullptr, nullptr};
+  hipStream_t host_stream = nullptr, copy_stream = nullptr;
+  ~KeySet() {
+    if (!ready && !ws && !blob) return;
+    if (hipSetDevice(device) != hipSuccess) return;
+    (void)hipDeviceSynchronize();
+    void* ptrs[] = {blob, msm, desc, ws, count, base, cursor, n_slots, slot_to_proof, granule_key, slot_status, cmp, st_proofs, st_inputs, st_index, st_status};
+    for (auto q : ptrs) if (q) (void)hipFree(q);
+    for (auto q : pin) if (q) (void)hipHostFree(q);
+    for (auto e : pin_ev) if (e) (void)hipEventDestroy(e);
+    hipEvent_t evs[] = {fork_ev, join_ev, busy_ev};
+    for (auto e : evs) if (e) (void)hipEventDestroy(e);
+    hipStream_t ss[] = {aux, host_stream, copy_stream};
+    for (auto s : ss) if (s) (void)hipStreamDestroy(s);
+  }
+};
+
+// The cache: the last KEYS_SET_SLOTS (list, device) pairs, least recently used out first.  Entries are shared_ptrs: a set that is evicted, or dropped because one of its
+// members was freed, releases its device memory when the last call that still holds it returns.  Never destroyed (as the key cache: device memory must not be freed from
+// a static destructor).
+#define KEYS_SET_SLOTS 4
+struct SetCache {
+  std::mutex mu;
+  struct Entry { std::shared_ptr<KeySet> set; uint64_t tick = 0; };
+  Entry e[KEYS_SET_SLOTS];
+  uint64_t clock = 0;
+  std::shared_ptr<KeySet> get(const bn254_g16_pvk* const* pvks, size_t n_keys, int device, size_t max_public) {
+    std::shared_ptr<KeySet> evicted;      // released outside the lock: its destructor waits for the device
+    std::shared_ptr<KeySet> out;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      for (auto& x : e)
+        if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) { x.tick = ++clock; return x.set; }
+      Entry* v = &e[0];
+      for (auto& x : e) { if (!x.set) { v = &x; break; } if (x.tick < v->tick) v = &x; }
+      evicted = std::move(v->set);
+      out = std::make_shared<KeySet>();
+      out->list.assign(pvks, pvks + n_keys); out->device = device; out->max_public = max_public;
+      v->set = out; v->tick = ++clock;
+    }
+    return out;
+  }
+  void drop(const bn254_g16_pvk* member) {
+    std::vector<std::shared_ptr<KeySet>> gone;
+    {
+      std::lock_guard<std::mutex> lk(mu);
+      for (auto& x : e)
+        if (x.set && std::find(x.set->list.begin(), x.set->list.end(), member) != x.set->list.end()) gone.push_back(std::move(x.set));
+    }
+  }
+};
+SetCache& set_cache() { static auto* c = new SetCache(); return *c; }
+
+template <class T> int dev_alloc(T** p, size_t count) {
+  if (*p) { HIPCK(hipFree(*p)); *p = nullptr; }
+  hipError_t e = hipMalloc((void**)p, (count ? count : 1) * sizeof(T));
+  if (e == hipErrorOutOfMemory) { *p = nullptr; return set_err(BN254_E_NOMEM, "device memory exhausted (key set)"); }
+  if (e != hipSuccess) { *p = nullptr; return set_err(BN254_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
+  return BN254_OK;
+}
+
+// caller holds s.mu.  First use: descriptors, line tables and byte-window tables of the distinct keys.  Then the buffers of a batch of n proofs.
+int ensure_set(KeySet& s, size_t n) {
+  int rc = check_device(s.device);
+  if (rc) return rc;
+  const size_t n_keys = s.list.size();
+  if (!s.ready) {
+    std::map<const bn254_g16_pvk*, size_t> uniq;        // handle -> its number among the distinct ones
+    std::vector<const bn254_g16_pvk*> order;
+    for (auto p : s.list) if (uniq.emplace(p, order.size()).second) order.push_back(p);
+    std::vector<size_t> first_point(order.size());
+    std::vector<int32_t> pts, blob(order.size() * KEYS_BLOB_DWORDS);
+    for (size_t u = 0; u < order.size(); u++) {
+      const G16Prepared& h = order[u]->host;
+      first_point[u] = pts.size() / (2 * BN_NL);
+      pts.insert(pts.end(), h.kpts.begin(), h.kpts.end());
+      if (h.kpts.size() != h.key_inputs() * 2 * BN_NL || h.gtab.size() != (size_t)BN_ATE_STEPS * FIXED_LINE_DWORDS || h.dtab.size() != h.gtab.size() || h.k0.size() != 2 * BN_NL ||
+          h.target.size() != 12 * BN_NL)
+        return set_err(BN254_E_BAD_ARG, "a key of the set does not carry its K points (prepared with host-built tables: BN254_TABLES_HOST)");
+      int32_t* b = blob.data() + u * KEYS_BLOB_DWORDS;
+      memcpy(b, h.gtab.data(), h.gtab.size() * 4); b += h.gtab.size();
+      memcpy(b, h.dtab.data(), h.dtab.size() * 4); b += h.dtab.size();
+      memcpy(b, h.k0.data(), h.k0.size() * 4); b += h.k0.size();
+      memcpy(b, h.target.data(), h.target.size() * 4);
+    }
+    // the tables must fit beside the construction scratch (226 MB at most, bn254_capi.hip::build_tables_on_device) and leave room for a workspace
+    size_t free_b = 0, total_b = 0;
+    HIPCK(hipMemGetInfo(&free_b, &total_b));
+    const size_t n_points = pts.size() / (2 * BN_NL), table_bytes = n_points * KEYS_TABLE_BYTES_PER_POINT;
+    if (table_bytes + ((size_t)512 << 20) > free_b)
+      return set_err(BN254_E_NOMEM, "the byte-window tables of the set (" + std::to_string(table_bytes >> 20) + " MB, 652 800 bytes per K point) do not fit the device's free memory (" +
+                                        std::to_string(free_b >> 20) + " MB)");
+    if ((rc = upload(&s.blob, blob))) return rc;
+    if (n_points && (rc = build_tables_on_device(1, pts, &s.msm))) return rc;
+    std::vector<G16KeyDesc> desc(n_keys);
+    for (size_t k = 0; k < n_keys; k++) {
+      const size_t u = uniq[s.list[k]];
+      const G16Prepared& h = s.list[k]->host;
+      const int32_t* b = s.blob + u * KEYS_BLOB_DWORDS;
+      G16KeyDesc& d = desc[k];
+      d.gtab = b; d.dtab = b + (size_t)BN_ATE_STEPS * FIXED_LINE_DWORDS; d.k0 = d.dtab + (size_t)BN_ATE_STEPS * FIXED_LINE_DWORDS; d.target = d.k0 + 2 * BN_NL;
+      d.msm_tab = s.msm ? s.msm + first_point[u] * (KEYS_TABLE_BYTES_PER_POINT / 4) : s.blob;     // (never read for a key without inputs)
+      d.n_public = (int32_t)h.key_inputs();
+      d.inputs_match = h.n_k ? 1 : 0;
+    }
+    if ((rc = upload(&s.desc, desc))) return rc;
+    HIPCK(hipEventCreateWithFlags(&s.busy_ev, hipEventDisableTiming));
+    HIPCK(hipEventCreateWithFlags(&s.fork_ev, hipEventDisableTiming));
+    HIPCK(hipEventCreateWithFlags(&s.join_ev, hipEventDisableTiming));
+    HIPCK(hipStreamCreateWithFlags(&s.aux, hipStreamNonBlocking));
+    if ((rc = dev_alloc(&s.count, n_keys)) || (rc = dev_alloc(&s.base, n_keys)) || (rc = dev_alloc(&s.cursor, n_keys)) || (rc = dev_alloc(&s.n_slots, 1))) return rc;
+    s.ready = true;
+  }
+  if (n > s.cap_n) {
+    const size_t slot_cap = (size_t)bn254::keys_slot_bound(n, n_keys);
+    const size_t ws_slots = bn254::g16_round256(slot_cap < (size_t)G16_MAX_BATCH ? slot_cap : (size_t)G16_MAX_BATCH);
+    s.cap_n = 0;
+    if (ws_slots > s.ws_cap) {
+      s.ws_cap = 0;
+      if (s.ws) { HIPCK(hipFree(s.ws)); s.ws = nullptr; }
+      hipError_t e = hipMalloc((void**)&s.ws, ws_slots * (size_t)G16_WS_BYTES_PER_PROOF);
+      if (e != hipSuccess) { s.ws = nullptr; return set_err(e == hipErrorOutOfMemory ? BN254_E_NOMEM : BN254_E_HIP, std::string("workspace of the key set: ") + hipGetErrorString(e)); }
+      s.ws_cap = ws_slots;
+    }
+    s.slot_cap = 0;
+    if ((rc = dev_alloc(&s.slot_to_proof, slot_cap)) || (rc = dev_alloc(&s.granule_key, slot_cap / G16_KEYS_GRANULE + 1)) || (rc = dev_alloc(&s.slot_status, slot_cap + 256))) return rc;
+    s.slot_cap = slot_cap; s.cap_n = n;
+  }
+  return BN254_OK;
+}
+int ensure_set_cmp(KeySet& s, size_t n) {
+  if (n <= s.cmp_cap) return BN254_OK;
+  s.cmp_cap = 0;
+  int rc = dev_alloc(&s.cmp, bn254::g16_round256(n) * 257);
+  if (rc) return rc;
+  s.cmp_cap = n;
+  return BN254_OK;
+}
+
+int launch_err(hipError_t e, const char* what) {
+  return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP, std::string("kernel launch (") + what + "): " + hipGetErrorString(e));
+}
+
+// Enqueue one batch on `user`.  Caller holds s.mu and has called ensure_set (and ensure_set_cmp).  exact_slots: the batch's slots where the caller knows them (the
+// host-buffer entry has counted the index), 0: only the device will know -- the launches then cover keys_slot_bound(n, n_keys) slots and the wavefronts past the real
+// figure leave at once.  Chunks of G16_MAX_BATCH SLOTS share the workspace; a chunk's sub-batches run side by side on `user` and the set's second stream, as in
+// g16_enqueue_exact; both cuts are multiples of 256 slots, so they fall inside a key's run but never inside a granule.
+int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_t proof_stride, const void* d_inputs, size_t input_stride, size_t n, void* d_status, hipStream_t user,
+                 unsigned flags, size_t exact_slots) {
+  static const int n_streams = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 2 ? 2 : v); }();
+  const uint32_t n_keys = (uint32_t)s.list.size();
+  const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
+  if (n > s.cap_n || bound > s.slot_cap) return set_err(BN254_E_BAD_ARG, "buffers of the key set smaller than the batch (internal sizing error)");
+  if (s.busy_valid) HIPCK(hipStreamWaitEvent(user, s.busy_ev, 0));
+  const uint8_t* proofs = (const uint8_t*)d_proofs;
+  uint8_t* pre = nullptr;
+  if (flags & BN254_FLAG_COMPRESSED_PROOFS) {
+    // the decompression never sees a key: the whole batch in proof order first (slots of a chunk refer to proofs anywhere in it), MALFORMED merged at the end
+    if (n > s.cmp_cap) return set_err(BN254_E_BAD_ARG, "decompression scratch smaller than the batch (internal sizing error)");
+    pre = s.cmp + bn254::g16_round256(s.cmp_cap) * 256;
+    for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
+      const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
+      hipError_t e = bn254_launch_g16_decompress(proofs + off * proof_stride, proof_stride, (uint32_t)m, s.cmp + off * 256, pre + off, user);
+      if (e != hipSuccess) return launch_err(e, "decompress");
+    }
+    proofs = s.cmp; proof_stride = 256;
+  }
+  hipError_t e = bn254_launch_keys_group((const uint32_t*)d_key_index, (uint32_t)n, n_keys, (uint32_t)bound, s.count, s.base, s.cursor, s.n_slots, s.slot_to_proof, s.granule_key,
+                                         (uint8_t*)d_status, user);
+  if (e != hipSuccess) return launch_err(e, "grouping");
+  const size_t slots = exact_slots ? exact_slots : bound;
+  for (size_t off = 0; off < slots; off += G16_MAX_BATCH) {
+    const size_t m = slots - off < (size_t)G16_MAX_BATCH ? slots - off : (size_t)G16_MAX_BATCH;
+    bn254::G16ChunkPlan plan;
+    if (!bn254::g16_plan_chunk(plan, m, 0, 0, n_streams, false)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    if (bn254::g16_round256(m) > s.ws_cap) return set_err(BN254_E_BAD_ARG, "workspace of the key set smaller than the batch (internal sizing error)");
+    if (plan.concurrent) HIPCK(hipEventRecord(s.fork_ev, user));
+    for (int pi = 0; pi < plan.parts; pi++) {
+      const size_t lo = plan.part[pi].first, cnt = plan.part[pi].count;
+      hipStream_t st = (plan.concurrent && (pi & 1)) ? s.aux : user;
+      if (st != user && pi == 1) HIPCK(hipStreamWaitEvent(st, s.fork_ev, 0));
+      G16KeysLaunchArgs a;
+      a.proofs = proofs; a.stride = proof_stride; a.inputs = (const uint8_t*)d_inputs; a.input_stride = input_stride; a.n_proofs = (uint32_t)n;
+      a.m = cnt; a.slot0 = (uint32_t)(off + lo); a.n_slots = s.n_slots; a.slot_to_proof = s.slot_to_proof + off + lo; a.granule_key = s.granule_key + (off + lo) / G16_KEYS_GRANULE;
+      a.desc = s.desc; a.n_keys = n_keys; a.ws = s.ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.slot_status = s.slot_status + off + lo; a.status = (uint8_t*)d_status;
+      a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+      a.part_of_larger = plan.parts > 1 ? 1 : 0;
+      if ((e = bn254_launch_g16_keys(a, st)) != hipSuccess) return launch_err(e, "key-set pipeline");
+    }
+    if (plan.concurrent && plan.parts > 1) { HIPCK(hipEventRecord(s.join_ev, s.aux)); HIPCK(hipStreamWaitEvent(user, s.join_ev, 0)); }
+  }
+  if (pre)
+    for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
+      const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
+      if ((e = bn254_launch_g16_status_merge((uint8_t*)d_status + off, pre + off, (uint32_t)m, user)) != hipSuccess) return launch_err(e, "status merge");
+    }
+  HIPCK(hipEventRecord(s.busy_ev, user));
+  s.busy_valid = true;
+  return BN254_OK;
+}
+
+int grow_bytes(uint8_t** p, size_t* cap, size_t need) {
+  if (need <= *cap) return BN254_OK;
+  *cap = 0;
+  int rc = dev_alloc(p, need);
+  if (rc) return rc;
+  *cap = need;
+  return BN254_OK;
+}
+
+}  // namespace
+
+// bn254_groth16_vk_free: every cached set that contains the key goes
+void keys_sets_drop(const bn254_g16_pvk* member) { set_cache().drop(member); }
+
+extern "C" {
+
+int bn254_groth16_reserve_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, size_t n, int device) {
+  size_t max_public = 0;
+  int rc = check_key_list(pvks, n_keys, &max_public);
+  if (rc) return rc;
+  if ((rc = check_device(device))) return rc;
+  std::shared_ptr<KeySet> s = set_cache().get(pvks, n_keys, device, max_public);
+  std::lock_guard<std::mutex> lk(s->mu);
+  return ensure_set(*s, n ? n : 1);
+}
+
+int bn254_groth16_verify_batch_keys_device(const bn254_g16_pvk* const* pvks, size_t n_keys, const void* d_key_index, const void* d_proofs, size_t proof_stride,
+                                           const void* d_public_inputs, size_t input_stride, size_t n, void* d_status, int device, void* hip_stream, unsigned flags) {
+  size_t max_public = 0;
+  int rc = check_keys_args(pvks, n_keys, d_key_index, d_proofs, proof_stride, d_public_inputs, input_stride, n, d_status, flags, &max_public);
+  if (rc || n == 0) return rc;
+  if ((rc = check_device(device))) return rc;
+  std::shared_ptr<KeySet> s = set_cache().get(pvks, n_keys, device, max_public);
+  std::lock_guard<std::mutex> lk(s->mu);
+  if ((rc = ensure_set(*s, n))) return rc;
+  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_set_cmp(*s, n))) return rc;
+  return keys_enqueue(*s, d_key_index, d_proofs, proof_stride, d_public_inputs, input_stride, n, d_status, (hipStream_t)hip_stream, flags, 0);
+}
+
+// Host buffers.  Grouping is global (a chunk of slots refers to proofs anywhere in the batch), so this entry uploads everything first -- index, records and input rows
+// through a ring of pinned pieces on a copy stream, the host threads filling piece i + 1 while piece i travels -- and then runs the device entry's pipeline on the
+// copies.  The index is counted on the host beforehand: that is the range check the device entry cannot make, and it gives the exact number of slots, so no launch
+// covers slots that do not exist.
+int bn254_groth16_verify_batch_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride,
+                                    const uint8_t* public_inputs, size_t input_stride, size_t n, uint8_t* status, int device, unsigned flags) {
+  size_t max_public = 0;
+  int rc = check_keys_args(pvks, n_keys, key_index, proofs, proof_stride, public_inputs, input_stride, n, status, flags, &max_public);
+  if (rc || n == 0) return rc;
+  size_t exact_slots = 0;
+  {
+    std::vector<uint32_t> count(n_keys, 0);
+    for (size_t i = 0; i < n; i++) {
+      if (key_index[i] >= n_keys) return set_err(BN254_E_BAD_ARG, "key_index[" + std::to_string(i) + "] = " + std::to_string(key_index[i]) + " is outside the list of " + std::to_string(n_keys) + " keys");
+      count[key_index[i]]++;
+    }
+    for (size_t k = 0; k < n_keys; k++) exact_slots += bn254::keys_round_up(count[k]);
+  }
+  if ((rc = check_device(device))) return rc;
+  std::shared_ptr<KeySet> sp = set_cache().get(pvks, n_keys, device, max_public);
+  KeySet& s = *sp;
+  std::lock_guard<std::mutex> lk(s.mu);
+  if ((rc = ensure_set(s, n))) return rc;
+  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_set_cmp(s, n))) return rc;
+  const size_t in_bytes = max_public ? n * input_stride : 0;
+  if ((rc = grow_bytes(&s.st_proofs, &s.st_proofs_cap, n * proof_stride)) || (rc = grow_bytes(&s.st_inputs, &s.st_inputs_cap, in_bytes ? in_bytes : 32)) ||
+      (rc = grow_bytes(&s.st_index, &s.st_index_cap, n * 4)) || (rc = grow_bytes(&s.st_status, &s.st_status_cap, n)))
+    return rc;
+  if (!s.host_stream) {
+    HIPCK(hipStreamCreateWithFlags(&s.host_stream, hipStreamNonBlocking)); HIPCK(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
+    for (int i = 0; i < KEYS_HOST_RING; i++) { HIPCK(hipHostMalloc((void**)&s.pin[i], KEYS_HOST_PIECE, hipHostMallocDefault)); HIPCK(hipEventCreateWithFlags(&s.pin_ev[i], hipEventDisableTiming)); }
+  }
+  size_t uses = 0;
+  hipEvent_t last = nullptr;
+  auto fail = [&](int code) { const std::string keep = g_err; (void)hipStreamSynchronize(s.copy_stream); (void)hipStreamSynchronize(s.host_stream); g_err = keep; return code; };
+  auto push = [&](uint8_t* dst, const uint8_t* src, size_t len) -> int {
+    for (size_t from = 0; from < len;) {
+      const size_t k = len - from < KEYS_HOST_PIECE ? len - from : KEYS_HOST_PIECE;
+      const int slot = (int)(uses % KEYS_HOST_RING);
+      if (uses >= KEYS_HOST_RING) HIPCK(hipEventSynchronize(s.pin_ev[slot]));
+      parallel_copy(s.pin[slot], src + from, k);
+      HIPCK(hipMemcpyAsync(dst + from, s.pin[slot], k, hipMemcpyHostToDevice, s.copy_stream));
+      HIPCK(hipEventRecord(s.pin_ev[slot], s.copy_stream));
+      last = s.pin_ev[slot];
+      uses++; from += k;
+    }
+    return BN254_OK;
+  };
+  // the staging buffers may still be read by the previous batch of this set: the copies start after it
+  if (s.busy_valid) HIPCK(hipStreamWaitEvent(s.copy_stream, s.busy_ev, 0));
+  if ((rc = push(s.st_index, (const uint8_t*)key_index, n * 4)) || (rc = push(s.st_proofs, proofs, n * proof_stride)) || (in_bytes && (rc = push(s.st_inputs, public_inputs, in_bytes))))
+    return fail(rc);
+  if (last) HIPCK(hipStreamWaitEvent(s.host_stream, last, 0));
+  if ((rc = keys_enqueue(s, s.st_index, s.st_proofs, proof_stride, s.st_inputs, input_stride, n, s.st_status, s.host_stream, flags, exact_slots))) return fail(rc);
+  HIPCK(hipMemcpyAsync(status, s.st_status, n, hipMemcpyDeviceToHost, s.host_stream));
+  HIPCK(hipStreamSynchronize(s.host_stream));
+  return BN254_OK;
+}
+
+// The grouping of a batch, for the tests: device -1 runs the steps on the host (bn254_keys.h::keys_group_host), a device ordinal runs k_keys_count / _scan / _place.
+// out_slot_to_proof: bn254_dbg_g16_keys_slot_bound(n, n_keys) words (all ones in padding slots and past out_n_slots), out_granule_key: a word per 64 of them.
+size_t bn254_dbg_g16_keys_slot_bound(size_t n, size_t n_keys) { return (size_t)bn254::keys_slot_bound(n, n_keys); }
+int bn254_dbg_g16_keys_group(const unsigned* key_index, size_t n, size_t n_keys, int device, unsigned* out_slot_to_proof, unsigned* out_granule_key, size_t* out_n_slots) {
+  if (!key_index || !out_slot_to_proof || !out_granule_key || !out_n_slots || n == 0 || n_keys == 0 || n_keys > G16_KEYS_MAX_KEYS || bn254::keys_slot_bound(n, n_keys) > 0xffff0000ull)
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys), granules = bound / G16_KEYS_GRANULE;
+  if (device < 0) {
+    std::vector<uint32_t> count(n_keys), base(n_keys);
+    for (size_t sidx = 0; sidx < bound; sidx++) out_slot_to_proof[sidx] = G16_KEYS_NO_PROOF;
+    for (size_t g = 0; g < granules; g++) out_granule_key[g] = 0;
+    *out_n_slots = bn254::keys_group_host(key_index, (uint32_t)n, (uint32_t)n_keys, out_slot_to_proof, out_granule_key, count.data(), base.data());
+    return BN254_OK;
+  }
+  int rc = check_device(device);
+  if (rc) return rc;
+  uint32_t *idx = nullptr, *cnt = nullptr, *s2p = nullptr, *gk = nullptr; uint8_t* st = nullptr;
+  auto drop = [&]() { void* p[] = {idx, cnt, s2p, gk, st}; for (auto q : p) if (q) (void)hipFree(q); };
+  if ((rc = dev_alloc(&idx, n)) || (rc = dev_alloc(&cnt, 3 * n_keys + 1)) || (rc = dev_alloc(&s2p, bound)) || (rc = dev_alloc(&gk, granules + 1)) || (rc = dev_alloc(&st, n))) { drop(); return rc; }
+  hipError_t e = hipMemcpy(idx, key_index, n * 4, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = bn254_launch_keys_group(idx, (uint32_t)n, (uint32_t)n_keys, (uint32_t)bound, cnt, cnt + n_keys, cnt + 2 * n_keys, cnt + 3 * n_keys, s2p, gk, st, nullptr);
+  uint32_t ns = 0;
+  if (e == hipSuccess) e = hipMemcpy(&ns, cnt + 3 * n_keys, 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_slot_to_proof, s2p, bound * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess) e = hipMemcpy(out_granule_key, gk, granules * 4, hipMemcpyDeviceToHost);
+  drop();
+  if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("grouping: ") + hipGetErrorString(e));
+  *out_n_slots = ns;
+  return BN254_OK;
+}
+
+}  // extern "C"

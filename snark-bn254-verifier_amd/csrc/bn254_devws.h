@@ -80,6 +80,41 @@ __device__ __forceinline__ G1Aff msm_entry(const int32_t* __restrict__ msm_tab, 
   return q;
 }
 
+// ---- the key of a wavefront (batches over many keys, bn254_keys.h) ---------------------------------------------------------------------------------------
+// The fields of the descriptor of the key that granule `wave_first / 64` of the launch works for.  The descriptor and the tables it points to are read-only for
+// every kernel, so they are addressed through the CONSTANT address space: a pointer that was itself read from memory is a generic pointer to the compiler, and
+// loads through it are flat vector loads even at a wavefront-uniform address (k_miller_run_keys read its 108 line dwords per step that way, at twice the spilled
+// registers of k_miller_run); with the address space named they are the scalar loads k_miller_run makes from its kernel arguments.  The byte-window tables are read
+// at per-lane addresses: global address space, vector loads.  The index is clamped to the list: a granule past the batch's slots is never pending, but its word may
+// be anything.
+struct KeyView { const int32_t *msm_tab, *k0, *gtab, *dtab, *target; int n_public, inputs_match; };
+__device__ __forceinline__ const int32_t* keys_const_ptr(uint64_t bits) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)bits), hi = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
+  return (const int32_t*)(const __attribute__((address_space(4))) int32_t*)(((uint64_t)hi << 32) | lo);
+}
+__device__ __forceinline__ KeyView keys_view(const G16KeyDesc* __restrict__ desc, const uint32_t* __restrict__ granule_key, uint32_t wave_first, uint32_t n_keys) {
+  static_assert(sizeof(G16KeyDesc) == 48, "five pointers and two words");
+  uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)granule_key[wave_first / G16_KEYS_GRANULE]);
+  k = k < n_keys ? k : 0u;
+  const uint64_t b = (uint64_t)(desc + k);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+  const __attribute__((address_space(4))) uint64_t* f = (const __attribute__((address_space(4))) uint64_t*)(((uint64_t)hi << 32) | lo);
+  KeyView v;
+  const uint64_t tab = f[0];
+  v.msm_tab = (const int32_t*)(const __attribute__((address_space(1))) int32_t*)tab;
+  v.k0 = keys_const_ptr(f[1]); v.gtab = keys_const_ptr(f[2]); v.dtab = keys_const_ptr(f[3]); v.target = keys_const_ptr(f[4]);
+  const uint64_t w = f[5];
+  v.n_public = __builtin_amdgcn_readfirstlane((int)(uint32_t)w); v.inputs_match = __builtin_amdgcn_readfirstlane((int)(uint32_t)(w >> 32));
+  return v;
+}
+
+// big-endian 32-byte field (8 dwords as loaded little-endian from memory) -> little-endian words
+__device__ __forceinline__ void be_field_to_words(uint32_t w[8], const uint32_t* d) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = __builtin_bswap32(d[7 - i]);
+}
+__device__ __forceinline__ bool words_lt_p(const uint32_t w[8]) { return !words_ge(w, BN_P_WORDS); }
+
 // ---- every VM operation (bn254_vm.h) is its own kernel ------------------------------------------------------------------------
 // The VM programs (vm_miller_program, vm_final_exp_program) are host-compilable: the host walks them and enqueues one launch
 // per operation (~210 per batch, all asynchronous on the sub-batch's stream, so launch overhead hides behind the previous kernel

@@ -1,0 +1,300 @@
+// bn254_k_keys.hip -- the kernels of a Groth16 batch over many verifying keys (bn254_keys.h; bn254_groth16_verify_batch_keys): the proofs are brought into slots so
+// that every wavefront works for one key, and the four places where a key enters the single-key pipeline read it from the wavefront's descriptor instead of the
+// launch arguments.  Everything in between (k_vm_init, the final exponentiation program) never sees a key and runs unchanged on the slots.
+//   k_keys_count / k_keys_scan / k_keys_place   per-key histogram of key_index, exclusive scan of the counts rounded up to a granule, slot -> proof and granule -> key
+//   k_g16_prepare_keys      k_g16_prepare through the slot index: record and input row of the slot's proof, L from the key's byte-window tables
+//   k_g16_check_scalars_keys  BN254_FLAG_STRICT_SCALARS with the key's input count
+//   k_g16_subgroup_keys     k_g16_subgroup with the key's inputs_match
+//   k_g16_compare_keys      comparison with the key's e(alpha, beta) and the scatter of every slot's status byte back to proof order
+// (k_miller_run_keys is in bn254_k_miller.hip, beside the kernel it is an instance of.)
+#include <hip/hip_runtime.h>
+#include "bn254_devws.h"
+#include "bn254_keys.h"
+
+namespace bn254 {
+
+// ---- grouping ---------------------------------------------------------------------------------------------------------------------------------------------
+#define KEYS_LDS_COUNTERS 8192   // key lists up to this long are counted in LDS (32 KB) and flushed once per workgroup
+__global__ void __launch_bounds__(256) k_keys_count(const uint32_t* __restrict__ key_index, uint32_t n, uint32_t n_keys, uint32_t* __restrict__ count) {
+  __shared__ uint32_t lc[KEYS_LDS_COUNTERS];
+  const bool priv = n_keys <= KEYS_LDS_COUNTERS;
+  if (priv) { for (uint32_t k = threadIdx.x; k < n_keys; k += 256) lc[k] = 0; __syncthreads(); }
+  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
+    const uint32_t k = key_index[i];
+    if (k >= n_keys) continue;
+    if (priv) atomicAdd(&lc[k], 1u); else atomicAdd(&count[k], 1u);
+  }
+  if (priv) {
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < n_keys; k += 256) { const uint32_t c = lc[k]; if (c) atomicAdd(&count[k], c); }
+  }
+}
+// one workgroup of 1024 lanes: lane t scans keys [t per, (t + 1) per), the lanes' totals are scanned through LDS.  base[k]: first slot of key k; cursor[k]: the same,
+// advanced by k_keys_place; n_slots[0]: slots of the batch
+__global__ void __launch_bounds__(1024) k_keys_scan(const uint32_t* __restrict__ count, uint32_t n_keys, uint32_t* __restrict__ base, uint32_t* __restrict__ cursor, uint32_t* __restrict__ n_slots) {
+  __shared__ uint32_t tot[1024];
+  const uint32_t t = threadIdx.x, per = (n_keys + 1023u) / 1024u;
+  const uint32_t lo = t * per < n_keys ? t * per : n_keys, hi = lo + per < n_keys ? lo + per : n_keys;
+  uint32_t mine = 0;
+  for (uint32_t k = lo; k < hi; k++) mine += keys_round_up(count[k]);
+  tot[t] = mine;
+  __syncthreads();
+  for (uint32_t d = 1; d < 1024; d <<= 1) {   // inclusive scan of the lanes' totals
+    const uint32_t v = t >= d ? tot[t - d] : 0u;
+    __syncthreads();
+    tot[t] += v;
+    __syncthreads();
+  }
+  const uint32_t after = keys_scan_range(count, base, lo, hi, tot[t] - mine);
+  for (uint32_t k = lo; k < hi; k++) cursor[k] = base[k];
+  (void)after;
+  if (t == 1023) n_slots[0] = tot[1023];
+}
+// proof i takes the next slot of its key.  The lanes of a wavefront that hold the same key take their slots with ONE atomic (a batch of one key would otherwise send
+// every proof to the same counter); an index outside the list gets no slot and the proof's status is MALFORMED.
+__global__ void __launch_bounds__(256) k_keys_place(const uint32_t* __restrict__ key_index, uint32_t n, uint32_t n_keys, uint32_t* __restrict__ cursor,
+                                                    uint32_t* __restrict__ slot_to_proof, uint32_t* __restrict__ granule_key, uint8_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t k = i < n ? key_index[i] : 0xffffffffu;
+  bool todo = i < n && k < n_keys;
+  if (i < n && k >= n_keys) status[i] = BN254_ST_MALFORMED;
+  const uint32_t lane = threadIdx.x & 63u;
+  for (;;) {
+    const uint64_t left = __builtin_amdgcn_ballot_w64(todo);
+    if (left == 0) break;
+    const uint32_t lead = (uint32_t)__builtin_ctzll(left);
+    const uint32_t kk = (uint32_t)__builtin_amdgcn_readlane((int)k, (int)lead);
+    const uint64_t same = __builtin_amdgcn_ballot_w64(todo && k == kk);
+    uint32_t first = 0;
+    if (lane == lead) first = atomicAdd(&cursor[kk], (uint32_t)__builtin_popcountll(same));
+    first = (uint32_t)__builtin_amdgcn_readlane((int)first, (int)lead);
+    if (todo && k == kk) {
+      keys_place(slot_to_proof, granule_key, first + (uint32_t)__builtin_popcountll(same & ((1ull << lane) - 1ull)), i, k);
+      todo = false;
+    }
+  }
+}
+
+// ---- k_g16_prepare_keys ---------------------------------------------------------------------------------------------------------------------------------------
+// The launch covers slots [0, m) of ws / slot_status; slot_to_proof and granule_key point at the launch's first slot / granule.  live_slots: slots of the launch that
+// exist (n_slots[0] - slot0, clamped to m); every other slot, padding slots and slots whose proof index is out of range get status 0: not pending, so no later
+// kernel works on them.  The parse of A, B, C is k_g16_prepare's (bn254_kernels.hip), statement by statement.
+#define PREPK_LDS_ROW 65
+__global__ void __launch_bounds__(256, 2)
+k_g16_prepare_keys(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, size_t input_stride, uint32_t n_proofs, uint32_t m, uint32_t slot0,
+                   const uint32_t* __restrict__ n_slots, const uint32_t* __restrict__ slot_to_proof, const uint32_t* __restrict__ granule_key,
+                   const G16KeyDesc* __restrict__ desc, uint32_t n_keys, int32_t* ws, uint8_t* __restrict__ slot_status) {
+  __shared__ uint32_t lds[4 * 64 * PREPK_LDS_ROW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t first = blockIdx.x * 256u + (uint32_t)wave * 64u;
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_slots[0]);
+  const uint32_t live_slots = total > slot0 ? (total - slot0 < m ? total - slot0 : m) : 0u;
+  const bool wave_live = first < live_slots;       // granules are whole: a live wavefront's 64 slots all exist
+  const uint32_t i = first + lane;
+  uint32_t pi = wave_live ? slot_to_proof[i] : G16_KEYS_NO_PROOF;
+  const bool live = pi < n_proofs;
+  uint32_t* wl = lds + wave * 64 * PREPK_LDS_ROW;
+  const bool aligned = ((((uintptr_t)proofs) | stride) & 3) == 0;
+  if (wave_live) {
+    if (aligned) {
+      // record of slot j of this wave: one 256-byte contiguous segment per load instruction, sixteen loads in flight (as k_g16_prepare), the record's index from lane j
+      for (int j0 = 0; j0 < 64; j0 += 16) {
+        uint32_t v[16];
+#pragma unroll
+        for (int u = 0; u < 16; u++) { const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)pi, j0 + u); v[u] = rec < n_proofs ? *(const uint32_t*)(proofs + (size_t)rec * stride + (size_t)lane * 4) : 0u; }
+#pragma unroll
+        for (int u = 0; u < 16; u++) wl[(j0 + u) * PREPK_LDS_ROW + lane] = v[u];
+      }
+    } else {
+      for (int j = 0; j < 64; j++) {
+        const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)pi, j);
+        uint32_t v = 0;
+        if (rec < n_proofs) {
+          const uint8_t* p = proofs + (size_t)rec * stride + (size_t)lane * 4;
+          v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+        }
+        wl[j * PREPK_LDS_ROW + lane] = v;
+      }
+    }
+  }
+  __syncthreads();
+  if (!wave_live) { if (i < m) slot_status[i] = 0; return; }
+  const KeyView kv = keys_view(desc, granule_key, first, n_keys);
+  // padding lanes get an out-of-range lane offset: the descriptor's bounds check drops their stores
+  DevWs w(ws, m, live ? i : DEAD_LANE);
+  const uint32_t* my = wl + lane * PREPK_LDS_ROW;
+  uint32_t d[8], wx[8], wy[8];
+  int err = 0;       // first error in the reference's order: A, then B (member, curve), B subgroup (k_g16_subgroup_keys), then C
+  int err_c = 0;
+
+  // ---- A
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[k];
+  be_field_to_words(wx, d);
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[8 + k];
+  be_field_to_words(wy, d);
+  bool memb = words_lt_p(wx) & words_lt_p(wy);
+  G1Aff A; A.x = fp_from_words(wx); A.y = fp_from_words(wy);
+  if (!memb) err = BN254_ST_NOT_MEMBER; else if (!g1_on_curve(A)) err = BN254_ST_NOT_ON_CURVE;
+  w.st(VE_AX, A.x); w.st(VE_AY, A.y);
+
+  // ---- B : x.c1 | x.c0 | y.c1 | y.c0
+  G2Aff B;
+  bool membb = true;
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[16 + k];
+  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.x.c1 = fp_from_words(wx);
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[24 + k];
+  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.x.c0 = fp_from_words(wx);
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[32 + k];
+  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.y.c1 = fp_from_words(wx);
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[40 + k];
+  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.y.c0 = fp_from_words(wx);
+  if (err == 0) { if (!membb) err = BN254_ST_NOT_MEMBER; else if (!g2_on_curve(B)) err = BN254_ST_NOT_ON_CURVE; }
+  vst2(w, VE_B, B.x); vst2(w, VE_B + 2, B.y);
+
+  // ---- C
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[48 + k];
+  be_field_to_words(wx, d);
+#pragma unroll
+  for (int k = 0; k < 8; k++) d[k] = my[56 + k];
+  be_field_to_words(wy, d);
+  memb = words_lt_p(wx) & words_lt_p(wy);
+  G1Aff C; C.x = fp_from_words(wx); C.y = fp_from_words(wy);
+  if (!memb) err_c = BN254_ST_NOT_MEMBER; else if (!g1_on_curve(C)) err_c = BN254_ST_NOT_ON_CURVE;
+  w.st(VE_CX, C.x); w.st(VE_CY, C.y);
+
+  // ---- L = K0 + sum_s x_s K_s over the KEY's inputs (the loop bound is wavefront-uniform), x_s taken as raw 256-bit integers; byte windows: 32 table additions per
+  // input (the set's tables are 0.65 MB per point where a key's own 13-bit windows are 13 MB: bn254_capi_keys.hip)
+  const int32_t* k0 = kv.k0;
+  const int32_t* msm_tab = kv.msm_tab;
+  const int n_public = kv.inputs_match ? kv.n_public : 0;
+  G1Aff K0; K0.x = uni_ld(k0); K0.y = uni_ld(k0 + BN_NL);
+  G1Proj L = g1_from_affine(K0);
+  for (int s = 0; s < n_public; s++) {
+    uint32_t sw[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) sw[k] = 0u;       // a padding lane adds nothing
+    if (live) {
+      const uint8_t* sp = inputs + (size_t)pi * input_stride + (size_t)s * 32;
+      if (((((uintptr_t)inputs) | input_stride) & 3) == 0) {
+#pragma unroll
+        for (int k = 0; k < 8; k++) sw[k] = ((const uint32_t*)sp)[k];
+      } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) sw[k] = (uint32_t)sp[4 * k] | (uint32_t)sp[4 * k + 1] << 8 | (uint32_t)sp[4 * k + 2] << 16 | (uint32_t)sp[4 * k + 3] << 24;
+      }
+    }
+    for (int j = 0; j < 32; j++) {  // byte j of the big-endian scalar = window 31 - j (as in k_g16_msm_partial)
+      const int wi = 31 - j;
+      const uint32_t dig = sw[0] & 0xff;
+#pragma unroll
+      for (int k = 0; k < 7; k++) sw[k] = (sw[k] >> 8) | (sw[k + 1] << 24);
+      sw[7] >>= 8;
+      if (dig != 0) L = g1_add_mixed(L, msm_entry(msm_tab, (size_t)(s * 32 + wi) * 255 + (dig - 1)));
+    }
+  }
+  bool l_inf = g1_is_identity(L);
+  G1Aff La = g1_to_affine(L);
+  La.y = fp_select(l_inf, fp_one(), La.y);
+  w.st(VE_LX, La.x); w.st(VE_LY, La.y);
+  slot_status[i] = !live ? (uint8_t)0 : err ? (uint8_t)err : (uint8_t)(BN254_ST_PENDING | (l_inf ? BN254_ST_LINF : 0) | err_c);
+}
+
+// BN254_FLAG_STRICT_SCALARS (k_g16_check_scalars): a public input >= r makes the proof NOT_MEMBER ahead of every other outcome; the inputs counted are the key's
+__global__ void __launch_bounds__(256, 2)
+k_g16_check_scalars_keys(const uint8_t* __restrict__ inputs, size_t input_stride, uint32_t n_proofs, uint32_t m, const uint32_t* __restrict__ slot_to_proof,
+                         const uint32_t* __restrict__ granule_key, const G16KeyDesc* __restrict__ desc, uint32_t n_keys, uint8_t* __restrict__ slot_status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint32_t first = i & ~63u;
+  if (first >= m) return;
+  // status 0 is what k_g16_prepare_keys leaves in every slot without a proof (no loader status is 0): such a wavefront has no descriptor to read
+  const uint8_t st = slot_status[i];
+  if (__builtin_amdgcn_ballot_w64(st != 0) == 0) return;
+  const int n_public = keys_view(desc, granule_key, first, n_keys).n_public;
+  const uint32_t pi = slot_to_proof[i];
+  if (st == 0 || pi >= n_proofs) return;
+  bool bad = false;
+  for (int s = 0; s < n_public; s++) {
+    uint32_t w[8];
+    words_from_be(w, inputs + (size_t)pi * input_stride + (size_t)s * 32);
+    bad |= words_ge(w, BN_R_WORDS);
+  }
+  if (bad) slot_status[i] = BN254_ST_NOT_MEMBER;
+}
+
+// the prologue of the VM kernels (VM_KERNEL_PROLOGUE) for kernels that read a descriptor: a wavefront past the launch's slots leaves before it reads anything
+#define VM_KEYS_PROLOGUE()                                                                       \
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;                                           \
+  if ((i & ~63u) >= n) return;                                                                   \
+  const uint8_t st = status[i < n ? i : n - 1];                                                 \
+  if (__builtin_amdgcn_ballot_w64((st & BN254_ST_PENDING) != 0) == 0) return;                   \
+  DevWs w(ws, n, i < n ? i : DEAD_LANE)
+
+__global__ void __launch_bounds__(256, 2)
+k_g16_subgroup_keys(uint32_t n, int32_t* ws, uint8_t* __restrict__ status, const uint32_t* __restrict__ granule_key, const G16KeyDesc* __restrict__ desc, uint32_t n_keys, int e_t) {
+  VM_KEYS_PROLOGUE();
+  const int inputs_match_key = keys_view(desc, granule_key, i & ~63u, n_keys).inputs_match;
+  bool ok = vm_g2_ate_check(w, e_t, VE_B);
+  if (i < n && (st & BN254_ST_PENDING)) {
+    uint8_t out;
+    if (!ok) out = BN254_ST_NOT_IN_SUBGROUP;
+    else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
+    else if (!inputs_match_key) out = BN254_ST_INPUT_LEN;     // PrepareInputsFailed comes after every loader error
+    else out = BN254_ST_PENDING | (st & BN254_ST_LINF);
+    status[i] = out;
+  }
+}
+
+// == e(alpha, beta) of the wavefront's key, and every slot that holds a proof hands its status byte -- the verdict, or what an earlier kernel decided -- to the proof
+__global__ void __launch_bounds__(256, 2)
+k_g16_compare_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ slot_to_proof, const uint32_t* __restrict__ granule_key,
+                   const G16KeyDesc* __restrict__ desc, uint32_t n_keys, uint32_t n_proofs, uint8_t* __restrict__ out_status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if ((i & ~63u) >= n) return;
+  const uint8_t st = status[i < n ? i : n - 1];
+  if (__builtin_amdgcn_ballot_w64(st != 0) == 0) return;      // no proof in this wavefront's slots
+  uint8_t out = st;
+  if (__builtin_amdgcn_ballot_w64((st & BN254_ST_PENDING) != 0) != 0) {
+    DevWs w(ws, n, i < n ? i : DEAD_LANE);
+    const int32_t* target = keys_view(desc, granule_key, i & ~63u, n_keys).target;
+    const bool acc = vm_f12_eq_const(w, VE_S0, target);
+    if (st & BN254_ST_PENDING) out = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
+  }
+  if (i < n && st != 0) { const uint32_t pi = slot_to_proof[i]; if (pi < n_proofs) out_status[pi] = out; }
+}
+
+}  // namespace bn254
+
+using namespace bn254;
+hipError_t bn254_launch_keys_group(const uint32_t* key_index, uint32_t n, uint32_t n_keys, uint32_t slot_cap, uint32_t* count, uint32_t* base, uint32_t* cursor,
+                                   uint32_t* n_slots, uint32_t* slot_to_proof, uint32_t* granule_key, uint8_t* status, hipStream_t s) {
+  hipError_t e;
+  if ((e = hipMemsetAsync(count, 0, (size_t)n_keys * 4, s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(slot_to_proof, 0xff, (size_t)slot_cap * 4, s)) != hipSuccess) return e;
+  if ((e = hipMemsetAsync(granule_key, 0, (size_t)(slot_cap / G16_KEYS_GRANULE + 1) * 4, s)) != hipSuccess) return e;
+  const unsigned blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(k_keys_count, dim3(blocks < 1024 ? blocks : 1024), dim3(256), 0, s, key_index, n, n_keys, count);
+  hipLaunchKernelGGL(k_keys_scan, dim3(1), dim3(1024), 0, s, (const uint32_t*)count, n_keys, base, cursor, n_slots);
+  hipLaunchKernelGGL(k_keys_place, dim3(blocks), dim3(256), 0, s, key_index, n, n_keys, cursor, slot_to_proof, granule_key, status);
+  return hipGetLastError();
+}
+void bn254_launch_g16_prepare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_g16_prepare_keys, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.input_stride, a.n_proofs, (uint32_t)a.m, a.slot0, a.n_slots, a.slot_to_proof,
+                     a.granule_key, a.desc, a.n_keys, a.ws, a.slot_status);
+  if (a.strict_scalars)
+    hipLaunchKernelGGL(k_g16_check_scalars_keys, dim3(grid), dim3(256), 0, s, a.inputs, a.input_stride, a.n_proofs, (uint32_t)a.m, a.slot_to_proof, a.granule_key, a.desc, a.n_keys,
+                       a.slot_status);
+}
+void bn254_launch_g16_subgroup_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s, int e_t) {
+  hipLaunchKernelGGL(k_g16_subgroup_keys, dim3(grid), dim3(256), 0, s, (uint32_t)a.m, a.ws, a.slot_status, a.granule_key, a.desc, a.n_keys, e_t);
+}
+void bn254_launch_g16_compare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s) {
+  hipLaunchKernelGGL(k_g16_compare_keys, dim3(grid), dim3(256), 0, s, a.ws, (uint32_t)a.m, (const uint8_t*)a.slot_status, a.slot_to_proof, a.granule_key, a.desc, a.n_keys, a.n_proofs,
+                     a.status);
+}

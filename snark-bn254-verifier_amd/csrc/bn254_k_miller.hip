@@ -60,6 +60,21 @@ __global__ void __launch_bounds__(256, 2) k_miller_run(int32_t* ws, uint32_t n, 
                 e_p1, (st & inf_mask1) != 0);
 }
 
+// k_miller_run for a batch over many keys (bn254_keys.h): the same loop, the two line tables from the descriptor of the wavefront's key
+__global__ void __launch_bounds__(256, 2) k_miller_run_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, MillerKinds kinds, int s_begin, int s_end,
+                                                            int e_t, int e_b, int e, int e_pa, const G16KeyDesc* __restrict__ desc, uint32_t n_keys,
+                                                            const uint32_t* __restrict__ granule_key, int e_p0, int inf_mask0, int e_p1, int inf_mask1) {
+  __shared__ int32_t park_lds[72 * 256];
+  if (((blockIdx.x * 256u + threadIdx.x) & ~63u) >= n) return;      // a wavefront past the launch's slots has no granule word
+  VM_KERNEL_PROLOGUE();
+  w.lds = park_lds;
+  const KeyView kv = keys_view(desc, granule_key, i & ~63u, n_keys);
+  DevLines lines{kv.gtab, kv.dtab};
+  DevKinds dk{kinds};
+  vm_miller_run(w, lines, dk, __builtin_amdgcn_readfirstlane(s_begin), __builtin_amdgcn_readfirstlane(s_end), e_t, e_b, e, e_pa, e_p0, (st & inf_mask0) != 0,
+                e_p1, (st & inf_mask1) != 0);
+}
+
 // the loop of two table-driven pairs without a variable pair (bn254_vm.h::vm_miller_run_fixed2): the pairing check of a large PlonK batch
 __global__ void __launch_bounds__(256, 2) k_miller_run_fixed2(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, MillerKinds kinds, int s_begin, int s_end, int e,
                                                               const int32_t* __restrict__ tab0, int e_p0, int inf_mask0, const int32_t* __restrict__ tab1, int e_p1, int inf_mask1) {
@@ -81,6 +96,10 @@ void bn254_launch_miller_run_fixed2(const MillerKinds& kinds, int s_begin, int s
 void bn254_launch_miller_run(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
                              int e, int epa, const int32_t* tab0, int ep0, int inf0, const int32_t* tab1, int ep1, int inf1) {
   hipLaunchKernelGGL(k_miller_run, dim3(grid), dim3(256), 0, s, ws, n, status, kinds, s_begin, s_end, et, eb, e, epa, tab0, ep0, inf0, tab1, ep1, inf1);
+}
+void bn254_launch_miller_run_keys(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
+                                  int e, int epa, const G16KeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1) {
+  hipLaunchKernelGGL(k_miller_run_keys, dim3(grid), dim3(256), 0, s, ws, n, status, kinds, s_begin, s_end, et, eb, e, epa, desc, n_keys, granule_key, ep0, inf0, ep1, inf1);
 }
 void bn254_launch_miller_step(bool do_sqr, int kind, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb, int e, int epa,
                               const int32_t* t0, int ep0, int inf0, const int32_t* t1, int ep1, int inf1) {

@@ -98,6 +98,34 @@ void bn254_launch_miller_run(const MillerKinds& kinds, int s_begin, int s_end, i
 // the same for two table-driven pairs and no variable pair (bn254_vm.h::vm_miller_run_fixed2)
 void bn254_launch_miller_run_fixed2(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int e,
                                     const int32_t* tab0, int ep0, int inf0, const int32_t* tab1, int ep1, int inf1);
+// ---- batches over many keys (bn254_keys.h, bn254_k_keys.hip): one launch part = slots [slot0, slot0 + m) of the batch, m a multiple of G16_KEYS_GRANULE -----------------
+#include "bn254_keys.h"
+struct G16KeysLaunchArgs {
+  const uint8_t* proofs; size_t stride;          // the WHOLE batch, proof order (raw 256-byte records)
+  const uint8_t* inputs; size_t input_stride;    // the whole batch: row i = inputs of proof i
+  uint32_t n_proofs;
+  size_t m;                 // slots of this launch (<= G16_MAX_LAUNCH)
+  uint32_t slot0;           // first slot of this launch
+  const uint32_t* n_slots;  // device word: slots of the batch (slots from there on hold nothing)
+  const uint32_t* slot_to_proof;   // at slot0
+  const uint32_t* granule_key;     // at slot0 / G16_KEYS_GRANULE
+  const bn254::G16KeyDesc* desc; uint32_t n_keys;
+  int32_t* ws;              // G16_WS_BYTES_PER_PROOF * m bytes
+  uint8_t* slot_status;     // m bytes (at slot0)
+  uint8_t* status;          // the whole batch, proof order
+  int strict_scalars = 0;
+  int part_of_larger = 0;
+};
+// count, scan, place on stream s (the buffers: bn254_capi_keys.hip); an index >= n_keys gets no slot and status[i] = MALFORMED
+hipError_t bn254_launch_keys_group(const uint32_t* key_index, uint32_t n, uint32_t n_keys, uint32_t slot_cap, uint32_t* count, uint32_t* base, uint32_t* cursor,
+                                   uint32_t* n_slots, uint32_t* slot_to_proof, uint32_t* granule_key, uint8_t* status, hipStream_t s);
+void bn254_launch_g16_prepare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s);
+void bn254_launch_g16_subgroup_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s, int e_t);
+void bn254_launch_g16_compare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s);
+void bn254_launch_miller_run_keys(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
+                                  int e, int epa, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1);
+// the lane pipeline of bn254_launch_g16 on the slots of one launch part: prepare, k_vm_init, the Miller loop in runs, subgroup, final exponentiation, compare + scatter
+hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s);
 // fixed-base tables of a key built on the device (bn254_k_comb.hip).  form 0: comb tables (points * 8192 entries), 1: byte-window tables (points * 32 * 255 entries), both of
 // MSM_ENTRY_DWORDS dwords; pts = `points` affine points (18 dwords each, device memory); scratch: teeth_plane = 27 * points * teeth dwords, teeth_aff = 18 * points * teeth
 // dwords, plane = 27 * points * entries dwords (bn254_tab_build_teeth / _entries: 13 / 8192 and 256 / 8192)

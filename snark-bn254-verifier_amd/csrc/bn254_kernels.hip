@@ -86,12 +86,6 @@ __global__ void __launch_bounds__(256, 2) k_g16_compare(int32_t* ws, uint32_t n,
   if (i < n && (st & BN254_ST_PENDING)) status[i] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
 }
 
-// big-endian 32-byte field (8 dwords as loaded little-endian from memory) -> little-endian words
-__device__ __forceinline__ void be_field_to_words(uint32_t w[8], const uint32_t* d) {
-#pragma unroll
-  for (int i = 0; i < 8; i++) w[i] = __builtin_bswap32(d[7 - i]);
-}
-__device__ __forceinline__ bool words_lt_p(const uint32_t w[8]) { return !words_ge(w, BN_P_WORDS); }
 
 // =====================================================================================================================
 // k_g16_prepare
@@ -840,6 +834,7 @@ struct LaunchOps {
   const int32_t* tab[3];
   G16Prof* prof;
   int inf_mask[3] = {BN254_ST_LINF, 0, 0};   // status bits marking the G1 point of fixed pair 0 / 1 / 2 as the identity
+  const G16KeyDesc* key_desc = nullptr; uint32_t n_keys = 0; const uint32_t* granule_key = nullptr;   // a batch over many keys: miller_run reads the tables per wavefront
   int uni(int x) { return x; }
   void f12_sqr(int e) { BN_LAUNCH(KID_F12_SQR, k_f12_sqr, ws, n, status, e); }
   void miller_dbl_var(int et, int e, int ep) { BN_LAUNCH(KID_MILLER_DBL_VAR, k_miller_dbl_var, ws, n, status, et, e, ep); }
@@ -851,6 +846,7 @@ struct LaunchOps {
   void miller_run(int s_begin, int s_end, int et, int eb, int e, int epa, int ep0, int ep1) {
     static const MillerKinds kinds = [] { MillerKinds k; memset(&k, 0, sizeof k); for (int st_ = 0; st_ < BN_ATE_STEPS; st_++) k.nib[st_ >> 1] |= (uint8_t)(miller_step_kind(st_) << ((st_ & 1) * 4)); return k; }();
     ProfScope ps_(prof, KID_MILLER_RUN, s);
+    if (key_desc) { bn254_launch_miller_run_keys(kinds, s_begin, s_end, ws, n, status, grid, s, et, eb, e, epa, key_desc, n_keys, granule_key, ep0, inf_mask[0], ep1, inf_mask[1]); return; }
     bn254_launch_miller_run(kinds, s_begin, s_end, ws, n, status, grid, s, et, eb, e, epa, tab[0], ep0, inf_mask[0], tab[1], ep1, inf_mask[1]);
   }
   void miller_run_fixed2(int s_begin, int s_end, int e, int ep0, int ep1) {
@@ -968,6 +964,24 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
   vm_final_exp_program(ops);
   BN_LAUNCH(KID_COMPARE, k_g16_compare, a.ws, n, a.status, a.target, BN254_ST_REJECT);
   if (ev) (void)hipEventRecord(ev[4], s);
+  return hipGetLastError();
+}
+
+// ---- a batch over many keys (bn254_keys.h): the lane kernels at every size, the key read per wavefront -------------------------------------------------------
+hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s) {
+  unsigned grid = grid_for(a.m);
+  const uint32_t n = (uint32_t)a.m;
+  G16Prof* prof = nullptr;
+  static const int run_steps_env = [] { const char* e = getenv("BN254_MILLER_RUN_STEPS"); int v = e ? atoi(e) : -1; return v < 1 ? -1 : v; }();
+  bn254_launch_g16_prepare_keys(a, grid, s);
+  LaunchOps ops{a.ws, n, a.slot_status, grid, s, {nullptr, nullptr, nullptr}, prof};
+  ops.key_desc = a.desc; ops.n_keys = a.n_keys; ops.granule_key = a.granule_key;
+  BN_LAUNCH(KID_VM_INIT, k_vm_init, a.ws, n, (const uint8_t*)a.slot_status);
+  // steps per k_miller_run_keys launch: what the single-key lane form takes at this size (g16_launch_form)
+  vm_miller_program_runs(ops, g16_launch_form(a.m, 0, true, false, a.part_of_larger != 0, false, false, run_steps_env).run_steps);
+  bn254_launch_g16_subgroup_keys(a, grid, s, (int)VE_T);
+  vm_final_exp_program(ops);
+  bn254_launch_g16_compare_keys(a, grid, s);
   return hipGetLastError();
 }
 

@@ -107,6 +107,7 @@ N_PUBLIC = 2                          # BASELINE configs[2]
 TRIPS_BY_KERNEL = {                   # loops whose trip count is a launch parameter: (kernel, mads of one iteration) -> trips, why
     ("k_g16_prepare", "window_outer"): (N_PUBLIC, "one pass per public input"),
     ("k_rlc_group_points", "window_outer"): (N_PUBLIC, "one pass per public input"),
+    ("k_g16_prepare_keys", "window_outer"): (N_PUBLIC, "one pass per public input of the wavefront's key"),
     ("k_g16_msm_partial", "window_outer"): (16, "G16_WIDE_MSM_INPUTS_PER_LANE inputs per lane"),
     ("k_rlc_scale", "scalar_mul"): (64, "64 joint bit positions of the GLV weight k1 + k2 lambda"),
     ("k_g1_scalar_mul", "scalar_mul"): (128, "128 joint bit positions of the GLV halves of a 254-bit scalar"),
@@ -249,6 +250,12 @@ def model_kernel(name, ins):
                 weight_ranges.append((h, latches[-1], 19.0)); notes.append("19 doublings (%d mads each)" % c)
             elif own > 0:
                 unmodelled.append("loop +0x%x..+0x%x (%d mads) of k_g16_msm_partial_comb not recognised" % (h - ins[0][0], latches[-1] - ins[0][0], c))
+        elif name == "k_g16_prepare_keys" and c <= 8 and not inner:
+            # the records of a wavefront through the slot index, sixteen loads per trip: the multiply-adds are the 64-bit record offsets
+            weight_ranges.append((h, latches[-1], 4.0)); notes.append("record loop x4 (sixteen records per trip, %d address multiply-adds)" % c)
+        elif name == "k_g16_prepare_keys" and own > 3000:
+            # not a loop: the block of a wavefront without slots (status 0, return) is laid out behind the body and left through a backward branch into it
+            notes.append("the body is entered once (a backward branch from the early-exit block, not a loop)")
         elif _in(c, R_MIXED) and not inner:
             weight_ranges.append((h, latches[-1], 32.0 * 255.0 / 256.0))
             notes.append("byte-window loop: 32 windows per scalar, table addition (%d mads) unless the byte is zero" % c)
@@ -534,6 +541,14 @@ def main():
                                 "model_mads_per_lane": total, "note": pmc.get("note", "")}
         except Exception:
             pass
+    if "k_miller_run_keys" in kernels and "k_miller_run" in kernels:
+        # the same vm_miller_run with the line tables of the wavefront's key (bn254_keys.h): instruction for instruction the multiply-adds of k_miller_run
+        e, run = kernels["k_miller_run_keys"], kernels["k_miller_run"]
+        assert e["static_mads"] == run["static_mads"], ("k_miller_run_keys is no longer k_miller_run with other tables", e["static_mads"], run["static_mads"])
+        for f in ("mads_per_proof_launch", "mads_per_proof_batch", "per_pass"):
+            e[f] = run[f]
+        e["unmodelled"] = []
+        e["model"] = "k_miller_run with the line tables read from the descriptor of the wavefront's key: the same %d static multiply-adds, priced as k_miller_run" % e["static_mads"]
     if "k_f12_cyclo_sqr_n" in kernels:
         e = kernels["k_f12_cyclo_sqr_n"]
         e["mads_per_proof_batch"] = e["mads_per_proof_launch"] * 39     # all 39 launches of a batch together (exact: 186 squarings)
