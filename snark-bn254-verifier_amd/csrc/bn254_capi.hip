@@ -71,32 +71,32 @@ int check_device(int device) {
 // The fixed-base tables of a key, built on the current device from the key's points (bn254_k_comb.hip; form 0: comb tables, 1: byte windows; pts: 18 dwords per point):
 // 80 bytes x 8192 (8160) entries per point stay, the construction scratch (27 dwords per entry, passes of 256 points: 226 MB at most) is freed again.  *dst stays null unless
 // the table is complete (as upload(), bn254_capi_internal.h).
-int build_tables_on_device(int form, const std::vector<int32_t>& pts, int32_t** dst) {
-  if (*dst) return BN254_OK;
+int build_tables_on_device(int form, const std::vector<int32_t>& pts, DevBuf<int32_t>& dst) {
+  if (dst) return BN254_OK;
   const size_t np = pts.size() / (2 * BN_NL);
   const size_t per_point = bn254_tab_build_out_entries(form) * MSM_ENTRY_DWORDS;   // dwords of finished table per point
   const size_t teeth = bn254_tab_build_teeth(form), entries = bn254_tab_build_entries(form);
   const size_t slice_cap = ((size_t)256 << 13) / entries ? ((size_t)256 << 13) / entries : 1;   // points per pass: 2 M construction entries (226 MB of scratch) at most
   const size_t slice = np < slice_cap ? np : slice_cap;
-  int32_t *kp = nullptr, *tab = nullptr, *tplane = nullptr, *taff = nullptr, *plane = nullptr;
-  auto drop = [&]() { if (kp) (void)hipFree(kp); if (tplane) (void)hipFree(tplane); if (taff) (void)hipFree(taff); if (plane) (void)hipFree(plane); };
-  hipError_t e;
-  if ((e = hipMalloc((void**)&kp, pts.size() * sizeof(int32_t))) != hipSuccess || (e = hipMalloc((void**)&tab, np * per_point * sizeof(int32_t))) != hipSuccess ||
-      (e = hipMalloc((void**)&tplane, slice * teeth * 27 * sizeof(int32_t))) != hipSuccess || (e = hipMalloc((void**)&taff, slice * teeth * 2 * BN_NL * sizeof(int32_t))) != hipSuccess ||
-      (e = hipMalloc((void**)&plane, slice * entries * 27 * sizeof(int32_t))) != hipSuccess ||
-      (e = hipMemcpy(kp, pts.data(), pts.size() * sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess) {
-    drop(); if (tab) (void)hipFree(tab);
-    return set_err(BN254_E_HIP, std::string("fixed-base tables of the key: ") + hipGetErrorString(e));
-  }
+  DevBuf<int32_t> kp, tab, tplane, taff, plane;     // the scratch goes when this function returns
+  int rc;
+  if ((rc = kp.ensure(pts.size())) || (rc = tab.ensure(np * per_point)) || (rc = tplane.ensure(slice * teeth * 27)) || (rc = taff.ensure(slice * teeth * 2 * BN_NL)) ||
+      (rc = plane.ensure(slice * entries * 27)))
+    return rc;
+  hipError_t e = hipMemcpy(kp, pts.data(), pts.size() * sizeof(int32_t), hipMemcpyHostToDevice);
   for (size_t i0 = 0; i0 < np && e == hipSuccess; i0 += slice) {
     const size_t m = np - i0 < slice ? np - i0 : slice;            // the passes run one after the other on the null stream and share the scratch
     e = bn254_launch_tab_build(form, kp + i0 * 2 * BN_NL, (uint32_t)m, tab + i0 * per_point, tplane, taff, plane, nullptr);
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
-  drop();
-  if (e != hipSuccess) { (void)hipFree(tab); return set_err(BN254_E_HIP, std::string("fixed-base tables of the key: ") + hipGetErrorString(e)); }
-  *dst = tab;
+  if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("fixed-base tables of the key: ") + hipGetErrorString(e));
+  dst = std::move(tab);
   return BN254_OK;
+}
+// BN254_STREAMS = 1..4 sub-batches of a Groth16 chunk in flight (default 2: +4.5 % over one stream at 2^20, profiles/r01_streams.txt); a key set runs at most two
+int sub_batch_streams() {
+  static const int n = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
+  return n;
 }
 // Host threads of the staging copies (parallel_copy): one process-wide pool, started on first use.  (Spawning and joining 16 threads costs ~0.4 ms,
 // 8 % of a 4096-proof batch.)  run(n, fn) executes fn(0) on the caller and fn(1..n-1) on pool threads and returns when all
@@ -329,6 +329,7 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 // so no __HIPCC__) and drives the C ABI under the sanitizers.  There this file brings the other four files of the C ABI with it; hipcc builds each as its
 // own object (Makefile).
 #if !defined(__HIPCC__)
+#include <array>
 #include "bn254_capi_g16.hip"
 #include "bn254_capi_plonk.hip"
 #include "bn254_capi_sp1.hip"
@@ -342,11 +343,21 @@ void keys_sets_drop(const bn254_g16_pvk*) {}
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {
+  // (the harness's batches of 2^20 proofs repeat a few records: results are kept by record, three square roots per record are not made again)
+  struct Memo { uint32_t out[64]; uint8_t pre; };
+  thread_local std::map<std::array<uint32_t, 32>, Memo> memo;
   for (uint32_t i = 0; i < n; i++) {
-    uint32_t in[32], out[64];
-    memcpy(in, src + (size_t)i * stride, 128);
-    pre[i] = g16_decompress_record(in, out) ? 0 : 1;
-    memcpy(raw + (size_t)i * 256, out, 256);
+    std::array<uint32_t, 32> in;
+    memcpy(in.data(), src + (size_t)i * stride, 128);
+    auto it = memo.find(in);
+    if (it == memo.end()) {
+      if (memo.size() >= 4096) memo.clear();
+      Memo m;
+      m.pre = g16_decompress_record(in.data(), m.out) ? 0 : 1;
+      it = memo.emplace(in, m).first;
+    }
+    pre[i] = it->second.pre;
+    memcpy(raw + (size_t)i * 256, it->second.out, 256);
   }
   return hipSuccess;
 }

@@ -152,24 +152,20 @@ int bn254_dbg_rlc_wide_group(const uint8_t* kpts, const uint8_t alpha64[64], con
 }
 
 // ---------------------------------------------------------------- device-arithmetic probes (tests)
-struct DevBuf {   // frees on every exit path
-  uint8_t* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-};
 static int run_probe(size_t in_a, size_t in_b, size_t out_sz, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int device,
                      hipError_t (*launch)(const uint8_t*, const uint8_t*, uint8_t*, size_t)) {
   int rc = check_device(device);
   if (rc) return rc;
   if (n == 0) return BN254_OK;
-  DevBuf da, db, dout;
-  HIPCK(hipMalloc((void**)&da.p, in_a * n));
-  HIPCK(hipMemcpy(da.p, a, in_a * n, hipMemcpyHostToDevice));
-  if (in_b && b) { HIPCK(hipMalloc((void**)&db.p, in_b * n)); HIPCK(hipMemcpy(db.p, b, in_b * n, hipMemcpyHostToDevice)); }
-  HIPCK(hipMalloc((void**)&dout.p, out_sz * n));
-  hipError_t e = launch(da.p, db.p, dout.p, n);
+  DevBuf<uint8_t> da, db, dout;   // released on every exit path
+  if ((rc = da.ensure(in_a * n))) return rc;
+  HIPCK(hipMemcpy(da, a, in_a * n, hipMemcpyHostToDevice));
+  if (in_b && b) { if ((rc = db.ensure(in_b * n))) return rc; HIPCK(hipMemcpy(db, b, in_b * n, hipMemcpyHostToDevice)); }
+  if ((rc = dout.ensure(out_sz * n))) return rc;
+  hipError_t e = launch(da, db, dout, n);
   if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
   HIPCK(hipDeviceSynchronize());
-  HIPCK(hipMemcpy(o, dout.p, out_sz * n, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(o, dout, out_sz * n, hipMemcpyDeviceToHost));
   return BN254_OK;
 }
 // probe (tests): stage 1 of the device path alone -- zeta (32-byte big-endian, canonical; zero where the proof failed before the challenges) and the
@@ -187,17 +183,17 @@ int bn254_dbg_plonk_stage1(const bn254_plonk_pvk* pvk, const uint8_t* proofs, si
   PlonkCtx& c = lease.ctx(0);
   if ((rc = plonk_ensure_ctx(pvk, c, n, 0))) return rc;
   const size_t pb = n * proof_stride, ib = n * n_public * 32;
-  DevBuf in, zo, so;
-  HIPCK(hipMalloc((void**)&in.p, pb + ib + 4)); HIPCK(hipMalloc((void**)&zo.p, 32 * n)); HIPCK(hipMalloc((void**)&so.p, n));
-  HIPCK(hipMemcpy(in.p, proofs, pb, hipMemcpyHostToDevice));
-  if (ib) HIPCK(hipMemcpy(in.p + pb, public_inputs, ib, hipMemcpyHostToDevice));
+  DevBuf<uint8_t> in, zo, so;
+  if ((rc = in.ensure(pb + ib + 4)) || (rc = zo.ensure(32 * n)) || (rc = so.ensure(n))) return rc;
+  HIPCK(hipMemcpy(in, proofs, pb, hipMemcpyHostToDevice));
+  if (ib) HIPCK(hipMemcpy(in + pb, public_inputs, ib, hipMemcpyHostToDevice));
   uint32_t lam_key[11] = {0};
-  hipError_t e = bn254_launch_plonk_stage1(d->d_key, in.p, proof_stride, in.p + pb, n_public, n, lam_key, c.d_work, c.terms, c.flags, plonk_stage1_terms(pvk->key), c.stream);
-  if (e == hipSuccess) e = bn254_launch_plonk_dbg_zeta(c.d_work, n, zo.p, so.p, c.stream);
+  hipError_t e = bn254_launch_plonk_stage1(d->d_key, in, proof_stride, in + pb, n_public, n, lam_key, c.d_work, c.terms, c.flags, plonk_stage1_terms(pvk->key), c.stream);
+  if (e == hipSuccess) e = bn254_launch_plonk_dbg_zeta(c.d_work, n, zo, so, c.stream);
   if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
   HIPCK(hipStreamSynchronize(c.stream));
-  HIPCK(hipMemcpy(zeta_out, zo.p, 32 * n, hipMemcpyDeviceToHost));
-  HIPCK(hipMemcpy(status_out, so.p, n, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(zeta_out, zo, 32 * n, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(status_out, so, n, hipMemcpyDeviceToHost));
   return BN254_OK;
 }
 
@@ -221,17 +217,16 @@ int bn254_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n,
   return run_probe(32, 32, 32, a, b, out, n, device, [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_fp_mul(x, y, o, m, nullptr); });
 }
 static thread_local int g_probe_op = 0;
-static thread_local int32_t* g_probe_ws = nullptr;
-static thread_local uint8_t* g_probe_kinds = nullptr;
+static thread_local DevBuf<int32_t> g_probe_ws;      // held for the duration of one probe call: the launchers below are captureless lambdas
+static thread_local DevBuf<uint8_t> g_probe_kinds;
 static int probe_ws_alloc(size_t n, int device) {
   int rc = check_device(device);
   if (rc) return rc;
   if (n > G16_MAX_LAUNCH) return set_err(BN254_E_BAD_ARG, "probe batch too large");
-  HIPCK(hipMalloc((void**)&g_probe_ws, (n ? n : 1) * (size_t)G16_WS_BYTES_PER_PROOF));
-  HIPCK(hipMalloc((void**)&g_probe_kinds, n ? n : 1));  // status bytes of the probe lanes
+  if ((rc = g_probe_ws.ensure((n ? n : 1) * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = g_probe_kinds.ensure(n ? n : 1))) { g_probe_ws.release(); return rc; }  // kinds: status bytes of the probe lanes
   return BN254_OK;
 }
-static void probe_ws_free() { if (g_probe_ws) (void)hipFree(g_probe_ws); if (g_probe_kinds) (void)hipFree(g_probe_kinds); g_probe_ws = nullptr; g_probe_kinds = nullptr; }
+static void probe_ws_free() { g_probe_ws.release(); g_probe_kinds.release(); }
 int bn254_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device) {
   g_probe_op = op;
   int rc = probe_ws_alloc(n, device);

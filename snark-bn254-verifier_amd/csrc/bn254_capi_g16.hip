@@ -32,15 +32,6 @@ static long rlc_wide_pays_from(size_t n_public) {
   return g_rlc_wide_min_batch_env >= 0 ? g_rlc_wide_min_batch_env : (long)(RLC_WIDE_PAYS_FIXED + RLC_WIDE_PAYS_SCALE / (n_public ? n_public : 1));
 }
 
-static void rlc_dev_free(RlcDev& r) {
-  void* ptrs[] = {r.btab, r.tab, r.one, r.grp_status, r.idx, r.fb_proofs, r.fb_inputs, r.fb_status, r.grp_rows, r.grp_digits, r.grp_part};
-  for (auto q : ptrs) if (q) (void)hipFree(q);
-  if (r.h_status) (void)hipHostFree(r.h_status);
-  if (r.h_idx) (void)hipHostFree(r.h_idx);
-  const RlcDev keep = r;
-  r = RlcDev();
-  r.have_obs = keep.have_obs; r.fb_share = keep.fb_share; r.bypassed = keep.bypassed; r.bypassed_total = keep.bypassed_total;
-}
 #define OV_AGREE 3
 #define OV_REPROBE 256
 
@@ -53,96 +44,69 @@ int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n) {
   int rc = check_device(device);
   if (rc) return rc;
   if (!d.ready) {
-    if ((rc = upload(&d.k0, pvk->host.k0)) || (rc = upload(&d.gtab, pvk->host.gtab)) || (rc = upload(&d.dtab, pvk->host.dtab)) || (rc = upload(&d.target, pvk->host.target)))
+    if ((rc = upload(d.k0, pvk->host.k0)) || (rc = upload(d.gtab, pvk->host.gtab)) || (rc = upload(d.dtab, pvk->host.dtab)) || (rc = upload(d.target, pvk->host.target)))
       return rc;
     // comb tables above 16 inputs; 13-bit windows (bn254_fw.h) up to 16; byte windows only for the diagnostic BN254_WIDE_COMB=0 (k_g16_msm_partial)
-    if (!pvk->host.kpts.empty() && pvk->host.msm.empty()) { if ((rc = build_tables_on_device(g16_table_form(pvk->host), pvk->host.kpts, &d.msm))) return rc; }
-    else if ((rc = upload(&d.msm, pvk->host.msm))) return rc;
-    HIPCK(hipEventCreateWithFlags(&d.busy_ev, hipEventDisableTiming));
+    if (!pvk->host.kpts.empty() && pvk->host.msm.empty()) { if ((rc = build_tables_on_device(g16_table_form(pvk->host), pvk->host.kpts, d.msm))) return rc; }
+    else if ((rc = upload(d.msm, pvk->host.msm))) return rc;
+    if ((rc = d.busy_ev.ensure())) return rc;
     d.ready = true;
   }
   // what a reservation of n proofs needs (bn254_g16_plan.h: the same function the plan probe and its property test read)
   const G16Alloc need = g16_alloc_for(n, pvk->host.key_inputs(), pvk->host.msm_comb);
-  if (need.ws_proofs > d.ws_cap) {
-    if (d.ws) HIPCK(hipFree(d.ws));   // hipFree waits for the device: no batch is still using the old workspace
-    d.ws = nullptr; d.ws_cap = 0;
-    HIPCK(hipMalloc((void**)&d.ws, need.ws_proofs * (size_t)G16_WS_BYTES_PER_PROOF));
-    d.ws_cap = need.ws_proofs;
-  }
+  if ((rc = d.ws.ensure(need.ws_proofs * (size_t)(G16_WS_BYTES_PER_PROOF / 4)))) return rc;
   // keys with many public inputs: partial sums (and comb digits) of the public-input MSM, for the proofs of one launch.  Sized HERE (reserve /
   // the entry points call ensure_dev before they enqueue), so that the enqueue path itself never allocates or frees
   if (need.msm_part_proofs > d.msm_part_cap) {
-    if (d.msm_part) HIPCK(hipFree(d.msm_part));
-    d.msm_part = nullptr; d.msm_part_cap = 0;
-    HIPCK(hipMalloc((void**)&d.msm_part, need.msm_part_bytes + need.msm_digit_bytes));
+    d.msm_part_cap = 0;
+    if ((rc = d.msm_part.ensure((need.msm_part_bytes + need.msm_digit_bytes + 3) / 4))) return rc;
     d.msm_part_cap = need.msm_part_proofs; d.msm_chunks = need.msm_chunks;
   }
   if (g_profiling.load() && !d.ev_ready) {
-    for (int i = 0; i < 5; i++) HIPCK(hipEventCreate(&d.ev[i]));
+    for (auto& e : d.ev) if ((rc = e.ensure_timed())) return rc;
     const int cap = 1024;  // launches per sub-batch: ~720
-    d.prof_ev.resize(2 * cap); d.prof_kid.resize(cap);
-    for (auto& e : d.prof_ev) HIPCK(hipEventCreate(&e));
-    d.prof.ev = d.prof_ev.data(); d.prof.kid = d.prof_kid.data(); d.prof.cap = cap;
-    d.prof2_ev.resize(2 * cap); d.prof2_kid.resize(cap);
-    for (auto& e : d.prof2_ev) HIPCK(hipEventCreate(&e));
-    d.prof2.ev = d.prof2_ev.data(); d.prof2.kid = d.prof2_kid.data(); d.prof2.cap = cap;
+    auto pool = [&](std::vector<Event>& own, std::vector<hipEvent_t>& ev, std::vector<uint8_t>& kid, G16Prof& prof) -> int {
+      own.resize(2 * cap); ev.resize(2 * cap); kid.resize(cap);
+      for (int i = 0; i < 2 * cap; i++) { int r = own[i].ensure_timed(); if (r) return r; ev[i] = own[i]; }
+      prof.ev = ev.data(); prof.kid = kid.data(); prof.cap = cap;
+      return BN254_OK;
+    };
+    if ((rc = pool(d.prof_own, d.prof_ev, d.prof_kid, d.prof)) || (rc = pool(d.prof2_own, d.prof2_ev, d.prof2_kid, d.prof2))) return rc;
     d.ev_ready = true;
   }
   return BN254_OK;
 }
-// BN254_FLAG_COMPRESSED_PROOFS: the decompression scratch for a batch of n proofs (caller holds d.mu).  Grown here, by the entry points before they enqueue,
-// never by the enqueue path: a compressed batch allocates only when it is larger than every compressed batch before it on this (key, device)
-static int ensure_cmp(DevState& d, size_t n) {
-  const G16CmpAlloc need = g16_cmp_alloc(n);
-  if (need.proofs <= d.cmp_cap) return BN254_OK;
-  if (d.cmp) HIPCK(hipFree(d.cmp));   // hipFree waits for the device: no batch is still using the old scratch
-  d.cmp = nullptr; d.cmp_cap = 0;
-  HIPCK(hipMalloc((void**)&d.cmp, need.raw_bytes + need.pre_bytes));
-  d.cmp_cap = need.proofs;
+// BN254_FLAG_COMPRESSED_PROOFS / SP1 public inputs: the decompression scratch and the row scratch for a batch of n proofs (caller holds d.mu).  Grown here, by the
+// entry points before they enqueue, never by the enqueue path: such a batch allocates only when it is larger than every one before it on this (key, device)
+static int ensure_scratch(DevState& d, size_t n, unsigned flags, bool sp1) {
+  int rc;
+  if (flags & BN254_FLAG_COMPRESSED_PROOFS) { const G16CmpAlloc need = g16_cmp_alloc(n); if ((rc = d.cmp.ensure(need.raw_bytes + need.pre_bytes))) return rc; }
+  if (sp1) { const G16Sp1Alloc need = g16_sp1_alloc(n); if ((rc = d.sp1.ensure(need.row_bytes + need.pre_bytes))) return rc; }
   return BN254_OK;
 }
-// SP1 public inputs: the row scratch for a batch of n proofs (caller holds d.mu); grown like the decompression scratch above, never by the enqueue path
-static int ensure_sp1(DevState& d, size_t n) {
-  const G16Sp1Alloc need = g16_sp1_alloc(n);
-  if (need.proofs <= d.sp1_cap) return BN254_OK;
-  if (d.sp1) HIPCK(hipFree(d.sp1));
-  d.sp1 = nullptr; d.sp1_cap = 0;
-  HIPCK(hipMalloc((void**)&d.sp1, need.row_bytes + need.pre_bytes));
-  d.sp1_cap = need.proofs;
-  return BN254_OK;
-}
+// The sub-batches of a chunk that run side by side: part pi on slot pi % 4, slot 0 = the caller's stream, slots 1..3 = the auxiliary streams (created here, when a
+// batch first needs them).  parts_fork records where they start; part_begin makes an auxiliary stream wait for that point; part_join makes the caller's stream wait for
+// the last part of every auxiliary stream.
 static int ensure_aux(DevState& d, int count) {
-  if (count > 3) count = 3;
-  if (!d.fork_ev) {
-    HIPCK(hipEventCreateWithFlags(&d.fork_ev, hipEventDisableTiming));
-    for (int i = 0; i < 4; i++) HIPCK(hipEventCreateWithFlags(&d.join_ev[i], hipEventDisableTiming));
-  }
-  while (d.aux_count < count) { HIPCK(hipStreamCreateWithFlags(&d.aux[d.aux_count], hipStreamNonBlocking)); d.aux_count++; }
+  int rc;
+  if ((rc = d.fork_ev.ensure())) return rc;
+  for (auto& e : d.join_ev) if ((rc = e.ensure())) return rc;
+  for (int i = 0; i < count && i < 3; i++) if ((rc = d.aux[i].ensure())) return rc;
   return BN254_OK;
 }
-// part pi of a batch split over concurrent streams: slot pi % 4, slot 0 = the caller's stream, slots 1..3 = the auxiliary streams
-static inline hipStream_t part_stream(DevState& d, hipStream_t user, int pi) { const int k = pi % 4; return k == 0 ? user : d.aux[k - 1]; }
-static void dev_free(DevState& d) {
-  int32_t* ptrs[] = {d.k0, d.gtab, d.dtab, d.target, d.msm, d.ws, d.msm_part};
-  for (auto q : ptrs) if (q) (void)hipFree(q);
-  uint8_t* bp[] = {d.st_proofs, d.st_inputs, d.st_status, d.cmp, d.sp1, d.st_pv, d.st_off, d.st_vkh};
-  for (auto q : bp) if (q) (void)hipFree(q);
-  if (d.ev_ready) { for (int i = 0; i < 5; i++) (void)hipEventDestroy(d.ev[i]); for (auto& e : d.prof_ev) (void)hipEventDestroy(e); for (auto& e : d.prof2_ev) (void)hipEventDestroy(e); }
-  for (int i = 0; i < d.aux_count; i++) (void)hipStreamDestroy(d.aux[i]);
-  if (d.fork_ev) { (void)hipEventDestroy(d.fork_ev); for (int i = 0; i < 4; i++) (void)hipEventDestroy(d.join_ev[i]); }
-  if (d.busy_ev) (void)hipEventDestroy(d.busy_ev);
-  for (auto& e : d.ov_ev) if (e) (void)hipEventDestroy(e);
-  if (d.host_stream) (void)hipStreamDestroy(d.host_stream);
-  if (d.copy_stream) (void)hipStreamDestroy(d.copy_stream);
-  for (int i = 0; i < 3; i++) { if (d.pin[i]) (void)hipHostFree(d.pin[i]); if (d.pin_ev[i]) (void)hipEventDestroy(d.pin_ev[i]); }
-  rlc_dev_free(d.rlc);
+static int parts_fork(DevState& d, hipStream_t user, int parts) {
+  int rc = ensure_aux(d, parts - 1);
+  if (rc) return rc;
+  HIPCK(hipEventRecord(d.fork_ev, user));
+  return BN254_OK;
 }
-static int grow(uint8_t** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BN254_OK;
-  if (*p) HIPCK(hipFree(*p));
-  *p = nullptr; *cap = 0;
-  HIPCK(hipMalloc((void**)p, need));
-  *cap = need;
+static int part_begin(DevState& d, hipStream_t user, bool concurrent, int pi, hipStream_t* st) {
+  *st = (concurrent && pi % 4) ? (hipStream_t)d.aux[pi % 4 - 1] : user;
+  if (concurrent && pi < 4 && *st != user) HIPCK(hipStreamWaitEvent(*st, d.fork_ev, 0));
+  return BN254_OK;
+}
+static int part_join(DevState& d, hipStream_t user, bool concurrent, int pi, int parts, hipStream_t st) {
+  if (concurrent && (pi + 4 >= parts) && st != user) { HIPCK(hipEventRecord(d.join_ev[pi % 4], st)); HIPCK(hipStreamWaitEvent(user, d.join_ev[pi % 4], 0)); }
   return BN254_OK;
 }
 
@@ -176,10 +140,10 @@ int bn254_groth16_vk_prepare(const uint8_t* vk, size_t vk_len, unsigned mode, bn
 void bn254_groth16_vk_free(bn254_g16_pvk* pvk) {
   if (!pvk) return;
   keys_sets_drop(pvk);     // cached key sets that contain the key hold copies of its tables and its handle
-  for (auto& kv : pvk->dev) {
-    if (hipSetDevice(kv.first) != hipSuccess) continue;
+  for (auto it = pvk->dev.begin(); it != pvk->dev.end();) {
+    if (hipSetDevice(it->first) != hipSuccess) { ++it; continue; }   // (its state goes with the key below, without the wait)
     (void)hipDeviceSynchronize();
-    dev_free(kv.second);
+    it = pvk->dev.erase(it);      // the state's members release what they own on the device that is now current and idle
   }
   delete pvk;
 }
@@ -197,8 +161,7 @@ int bn254_groth16_reserve(const bn254_g16_pvk* pvk, size_t n, int device) {
 // Enqueue the exact pipeline for n proofs on `user`.  Caller holds d->mu and has called ensure_dev.
 static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* d_proofs, size_t proof_stride, const void* d_inputs,
                              size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
-  // BN254_STREAMS = 1..4 sub-batches in flight (default 2: +4.5 % over one stream at 2^20, profiles/r01_streams.txt)
-  static const int n_streams = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
+  const int n_streams = sub_batch_streams();
   // BN254_CHUNK_LOG2 (experiment): proofs per workspace chunk, default 2^20
   static const size_t chunk = [] { const char* e = getenv("BN254_CHUNK_LOG2"); int v = e ? atoi(e) : 20; if (v < 12) v = 12; if (v > 20) v = 20; return (size_t)1 << v; }();
   const int profiling = g_profiling.load();
@@ -238,19 +201,19 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
     const bool wide = plan.wide, concurrent = plan.concurrent, split_small = plan.split_small;
     const int parts = plan.parts;
     // the buffers were sized by ensure_dev (bn254_groth16_reserve or the entry point itself): this path only enqueues, after checking the plan against them
-    if (m > d->ws_cap) return set_err(BN254_E_BAD_ARG, "workspace smaller than the batch: bn254_groth16_reserve first");
+    if (m > d->ws_proofs()) return set_err(BN254_E_BAD_ARG, "workspace smaller than the batch: bn254_groth16_reserve first");
     if (wide) for (int pi = 0; pi < parts; pi++)
       if (plan.part[pi].count > d->msm_part_cap) return set_err(BN254_E_BAD_ARG, "workspace of a key with many public inputs is smaller than the batch: bn254_groth16_reserve first");
-    if (concurrent || split_small) { int rc = ensure_aux(*d, concurrent ? parts - 1 : 2); if (rc) return rc; }
-    if (concurrent) HIPCK(hipEventRecord(d->fork_ev, user));
+    int rc;
+    if ((rc = concurrent ? parts_fork(*d, user, parts) : split_small ? ensure_aux(*d, 2) : BN254_OK)) return rc;
     // the first two sub-batches of a batch that runs several, while the question is open -- and only when the two are of (nearly) equal size: a short second part
     // beside a long first one reads as "no overlap" whatever the queues do
     const bool measure_overlap = concurrent && parts >= 2 && d->ov_state == 0 && plan.part[1].count * 10 >= plan.part[0].count * 9;
-    if (measure_overlap) for (auto& e : d->ov_ev) if (!e) HIPCK(hipEventCreate(&e));
+    if (measure_overlap) for (auto& e : d->ov_ev) if ((rc = e.ensure_timed())) return rc;
     for (int pi = 0; pi < parts; pi++) {
       const size_t lo = plan.part[pi].first, hi = lo + plan.part[pi].count;
-      hipStream_t st = concurrent ? part_stream(*d, user, pi) : user;
-      if (concurrent && pi < 4 && st != user) HIPCK(hipStreamWaitEvent(st, d->fork_ev, 0));
+      hipStream_t st;
+      if ((rc = part_begin(*d, user, concurrent, pi, &st))) return rc;
       if (measure_overlap && pi < 2) HIPCK(hipEventRecord(d->ov_ev[2 * pi], st));
       G16LaunchArgs a;
       a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
@@ -260,7 +223,7 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
       a.inputs_match_key = pvk->host.inputs_match(n_public) ? 1 : 0;
       a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
       a.part_of_larger = parts > 1 ? 1 : 0;
-      a.msm_part = wide ? d->msm_part : nullptr;
+      a.msm_part = wide ? (int32_t*)d->msm_part : nullptr;
       a.msm_comb = pvk->host.msm_comb ? 1 : 0;
       a.msm_digits = (wide && pvk->host.msm_comb) ? (uint16_t*)(d->msm_part + d->msm_chunks * 27 * d->msm_part_cap) : nullptr;
       if (split_small && parts == 1) {
@@ -279,11 +242,12 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
       }
       const bool prof_second = profiling && d->ev_ready && pi == 1;
       if (prof_second) { d->prof2.mask = g_prof_mask.load(); if (!keep) d->prof2.used = 0; d->prof2_used = true; }
-      hipError_t e = bn254_launch_g16(a, st, prof_this ? d->ev : nullptr, prof_this ? &d->prof : (prof_second ? &d->prof2 : nullptr));
-      if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
-                                           std::string("kernel launch: ") + hipGetErrorString(e));
+      hipEvent_t phase_ev[5];
+      for (int k = 0; k < 5; k++) phase_ev[k] = d->ev[k];
+      hipError_t e = bn254_launch_g16(a, st, prof_this ? phase_ev : nullptr, prof_this ? &d->prof : (prof_second ? &d->prof2 : nullptr));
+      if (e != hipSuccess) return launch_err(e, nullptr);
       if (measure_overlap && pi < 2) HIPCK(hipEventRecord(d->ov_ev[2 * pi + 1], st));
-      if (concurrent && (pi + 4 >= parts) && st != user) { HIPCK(hipEventRecord(d->join_ev[pi % 4], st)); HIPCK(hipStreamWaitEvent(user, d->join_ev[pi % 4], 0)); }
+      if ((rc = part_join(*d, user, concurrent, pi, parts, st))) return rc;
     }
     if (measure_overlap) d->ov_state = 1;
   }
@@ -294,38 +258,28 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
 // ---- BN254_FLAG_RLC (bn254_rlc.h): first pass in groups, exact second pass over the proofs of groups that failed -----------------------------
 static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_public, size_t wide_groups) {
   RlcDev& r = d->rlc;
+  int rc;
   if (!r.ready) {
     {
       std::lock_guard<std::mutex> lk(pvk->mu);
       if (!pvk->rlc_host.ready && !prepare_g16_rlc(pvk->rlc_host, pvk->host)) return set_err(BN254_E_VK, "degenerate key element (RLC tables)");
     }
-    int rc;
-    if ((rc = upload(&r.btab, pvk->rlc_host.btab)) || (rc = upload(&r.one, pvk->rlc_host.one))) return rc;
-    if ((rc = build_tables_on_device(2, pvk->rlc_host.pts, &r.tab))) return rc;      // -alpha and K[0]: 13-bit windows like the key's own (vm_rlc_group_points reads both)
+    if ((rc = upload(r.btab, pvk->rlc_host.btab)) || (rc = upload(r.one, pvk->rlc_host.one))) return rc;
+    if ((rc = build_tables_on_device(2, pvk->rlc_host.pts, r.tab))) return rc;      // -alpha and K[0]: 13-bit windows like the key's own (vm_rlc_group_points reads both)
     r.ready = true;
   }
-  if (n > r.grp_cap) {
-    if (r.grp_status) HIPCK(hipFree(r.grp_status));
-    if (r.idx) HIPCK(hipFree(r.idx));
-    if (r.h_status) HIPCK(hipHostFree(r.h_status));
-    if (r.h_idx) HIPCK(hipHostFree(r.h_idx));
-    r.grp_status = nullptr; r.idx = nullptr; r.h_status = nullptr; r.h_idx = nullptr; r.grp_cap = r.idx_cap = r.h_cap = 0;
+  if (n > r.grp_cap) {   // the four are sized together: grp_cap is what ALL of them hold, 0 while any of them is being replaced
+    r.grp_cap = 0;
     const size_t cap = g16_rlc_alloc(n);               // group status regions of the launch parts are rounded up to 256 each (bn254_g16_plan.h)
-    HIPCK(hipMalloc((void**)&r.grp_status, cap));
-    HIPCK(hipMalloc((void**)&r.idx, cap * sizeof(uint32_t)));
-    HIPCK(hipHostMalloc((void**)&r.h_status, cap, hipHostMallocDefault));
-    HIPCK(hipHostMalloc((void**)&r.h_idx, cap * sizeof(uint32_t), hipHostMallocDefault));
-    r.grp_cap = r.idx_cap = r.h_cap = n;
+    if ((rc = r.grp_status.ensure(cap)) || (rc = r.idx.ensure(cap)) || (rc = r.h_status.ensure(cap)) || (rc = r.h_idx.ensure(cap))) return rc;
+    r.grp_cap = n;
   }
-  if (n_public > (size_t)RLC_MAX_PUBLIC && wide_groups > r.wide_cap) {
-    void* ptrs[] = {r.grp_rows, r.grp_digits, r.grp_part};
-    for (auto q : ptrs) if (q) HIPCK(hipFree(q));
-    r.grp_rows = nullptr; r.grp_digits = nullptr; r.grp_part = nullptr; r.wide_cap = 0;
+  if (n_public > (size_t)RLC_MAX_PUBLIC && wide_groups > r.wide_cap) {   // likewise, for wide_cap groups
+    r.wide_cap = 0;
     const size_t cap = g16_round256(wide_groups);
     const G16RlcWide a = g16_rlc_wide_alloc(cap, n_public, g16_table_form(pvk->host));
-    HIPCK(hipMalloc((void**)&r.grp_rows, a.rows_bytes));
-    if (a.digit_bytes) HIPCK(hipMalloc((void**)&r.grp_digits, a.digit_bytes));
-    if (a.part_bytes) HIPCK(hipMalloc((void**)&r.grp_part, a.part_bytes));
+    if ((rc = r.grp_rows.ensure(a.rows_bytes)) || (a.digit_bytes && (rc = r.grp_digits.ensure((a.digit_bytes + 1) / 2))) || (a.part_bytes && (rc = r.grp_part.ensure((a.part_bytes + 3) / 4))))
+      return rc;
     r.wide_cap = cap;
   }
   return BN254_OK;
@@ -333,7 +287,7 @@ static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_
 static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
                            size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
   (void)device;
-  static const int n_streams = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
+  const int n_streams = sub_batch_streams();
   static const int log2_group = [] { const char* e = getenv("BN254_RLC_GROUP_LOG2"); int v = e ? atoi(e) : 5; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
   // proofs per lane in the Miller loop (shared accumulator, one squaring of f per lane and step): 2^BN254_RLC_SHARE_LOG2, at most the group
   static const int log2_share_env = [] { const char* e = getenv("BN254_RLC_SHARE_LOG2"); int v = e ? atoi(e) : 3; return v < 0 ? 0 : (v > 3 ? 3 : v); }();
@@ -355,14 +309,14 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
     const size_t chunks_w = (n_public + G16_WIDE_MSM_INPUTS_PER_LANE - 1) / G16_WIDE_MSM_INPUTS_PER_LANE;
     size_t wide_off = 0;   // groups of the parts before this one (bn254_g16_plan.h::g16_rlc_wide_groups)
     const bool concurrent = parts > 1;
-    if (concurrent) { rc = ensure_aux(*d, parts - 1); if (rc) return rc; HIPCK(hipEventRecord(d->fork_ev, user)); }
+    if (concurrent && (rc = parts_fork(*d, user, parts))) return rc;
     const size_t per = ((m + parts - 1) / parts + 255) / 256 * 256;
     size_t grp_off = 0;
     for (int pi = 0; pi < parts; pi++) {
       const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
       if (lo >= hi) break;
-      hipStream_t st = concurrent ? part_stream(*d, user, pi) : user;
-      if (concurrent && pi < 4 && st != user) HIPCK(hipStreamWaitEvent(st, d->fork_ev, 0));
+      hipStream_t st;
+      if ((rc = part_begin(*d, user, concurrent, pi, &st))) return rc;
       G16LaunchArgs a;
       a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
       a.inputs = (const uint8_t*)d_inputs + (off + lo) * n_public * 32; a.n_public = (int)n_public; a.n = hi - lo;
@@ -389,9 +343,8 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
         wide_off += ra.plan.groups;
       }
       hipError_t e = bn254_launch_g16_rlc(a, ra, st);
-      if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
-                                           std::string("kernel launch (rlc): ") + hipGetErrorString(e));
-      if (concurrent && (pi + 4 >= parts) && st != user) { HIPCK(hipEventRecord(d->join_ev[pi % 4], st)); HIPCK(hipStreamWaitEvent(user, d->join_ev[pi % 4], 0)); }
+      if (e != hipSuccess) return launch_err(e, "rlc");
+      if ((rc = part_join(*d, user, concurrent, pi, parts, st))) return rc;
     }
     // which proofs are still pending (their group's product was not one)?  One stream synchronisation per chunk.
     HIPCK(hipMemcpyAsync(r.h_status, (const uint8_t*)d_status + off, m, hipMemcpyDeviceToHost, user));
@@ -403,14 +356,11 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
     }
     seen_checked += cnt; seen_fallback += cnt;
     if (cnt == 0) continue;
-    if (cnt > r.fb_cap || (size_t)cnt * n_public * 32 > r.fb_in_cap) {
-      void* ptrs[] = {r.fb_proofs, r.fb_inputs, r.fb_status};
-      for (auto q : ptrs) if (q) HIPCK(hipFree(q));
-      r.fb_proofs = r.fb_inputs = r.fb_status = nullptr; r.fb_cap = r.fb_in_cap = 0;
+    if (cnt > r.fb_cap || (size_t)cnt * n_public * 32 > r.fb_in_cap) {   // the three together, released first (this key may meet other input counts)
+      r.fb_cap = r.fb_in_cap = 0;
+      r.fb_proofs.release(); r.fb_inputs.release(); r.fb_status.release();
       const size_t cap = ((size_t)cnt + 4095) / 4096 * 4096;
-      HIPCK(hipMalloc((void**)&r.fb_proofs, cap * 256));
-      HIPCK(hipMalloc((void**)&r.fb_inputs, cap * (n_public ? n_public : 1) * 32));
-      HIPCK(hipMalloc((void**)&r.fb_status, cap));
+      if ((rc = r.fb_proofs.ensure(cap * 256)) || (rc = r.fb_inputs.ensure(cap * (n_public ? n_public : 1) * 32)) || (rc = r.fb_status.ensure(cap))) return rc;
       r.fb_cap = cap; r.fb_in_cap = cap * n_public * 32;
     }
     HIPCK(hipMemcpyAsync(r.idx, r.h_idx, (size_t)cnt * sizeof(uint32_t), hipMemcpyHostToDevice, user));
@@ -459,14 +409,13 @@ static int g16_enqueue_compressed(const bn254_g16_pvk* pvk, DevState* d, int dev
   const unsigned raw_flags = flags & ~(unsigned)BN254_FLAG_COMPRESSED_PROOFS;
   for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
     const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
-    if (g16_cmp_alloc(m).proofs > d->cmp_cap) return set_err(BN254_E_BAD_ARG, "decompression scratch smaller than the batch (internal sizing error)");
+    if (g16_cmp_alloc(m).proofs > d->cmp_proofs()) return set_err(BN254_E_BAD_ARG, "decompression scratch smaller than the batch (internal sizing error)");
     uint8_t* raw = d->cmp;
-    uint8_t* pre = d->cmp + d->cmp_cap * 256;
+    uint8_t* pre = d->cmp + d->cmp_proofs() * 256;
     uint8_t* st = (uint8_t*)d_status + off;
     const uint8_t* in = (const uint8_t*)d_inputs + off * n_public * 32;
     hipError_t e = bn254_launch_g16_decompress((const uint8_t*)d_proofs + off * proof_stride, proof_stride, (uint32_t)m, raw, pre, user);
-    if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
-                                         std::string("kernel launch (decompress): ") + hipGetErrorString(e));
+    if (e != hipSuccess) return launch_err(e, "decompress");
     int rc = rlc ? g16_enqueue_rlc(pvk, d, device, raw, 256, in, n_public, m, st, user, raw_flags)
                  : g16_enqueue_exact(pvk, d, raw, 256, in, n_public, m, st, user, raw_flags);
     if (rc) return rc;
@@ -475,51 +424,40 @@ static int g16_enqueue_compressed(const bn254_g16_pvk* pvk, DevState* d, int dev
   }
   return BN254_OK;
 }
+// the pipeline of one batch (or of one chunk of SP1 rows) on `user`
+static int g16_dispatch(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs, size_t n_public, size_t n,
+                        void* d_status, hipStream_t user, unsigned flags, bool rlc) {
+  if (flags & BN254_FLAG_COMPRESSED_PROOFS) return g16_enqueue_compressed(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags, rlc);
+  return rlc ? g16_enqueue_rlc(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags)
+             : g16_enqueue_exact(pvk, d, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
+}
 // one batch on `user`: waits for the previous batch of this (key, device), runs the exact or the RLC pipeline, records busy_ev.
-// use_rlc: -1 = decide here; 0 / 1 = the caller (the host-buffer entry, which must know before it cuts the batch into chunks) has decided
+// use_rlc: -1 = decide here; 0 / 1 = the caller (the host-buffer entry, which must know before it cuts the batch into chunks) has decided.
+// sp1 != nullptr, SP1 public inputs (d_inputs is not read, n_public is 2), chunk by chunk (at most G16_MAX_BATCH proofs, as g16_enqueue_compressed):
+// k_sp1_public_inputs writes the rows vkey_hash | digest and the pre-status bytes into the row scratch, the pipeline chosen for the whole batch (with
+// BN254_FLAG_COMPRESSED_PROOFS: decompression first) runs on the rows, and k_g16_status_merge makes MALFORMED override for a range outside the values buffer.
+// Everything is on `user`, so the next chunk's hashing overwrites the rows only after this chunk is done with them.
 static int g16_enqueue(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
-                       size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags, int use_rlc = -1) {
+                       size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags, int use_rlc = -1, const Sp1Src* sp1 = nullptr) {
+  if (sp1) n_public = 2;
   if (d->busy_valid) HIPCK(hipStreamWaitEvent(user, d->busy_ev, 0));
-  int rc;
+  int rc = BN254_OK;
   // BN254_FLAG_RLC is honoured where it pays: from RLC_PAYS_FROM proofs (bn254_set_rlc_params / BN254_RLC_MIN_BATCH at load time move the
   // threshold: the tests run the mode on small batches); smaller batches take the exact path -- same status bytes
   const bool rlc = use_rlc >= 0 ? use_rlc != 0 : (rlc_eligible(pvk, n_public, n, flags) && !rlc_bypass(d->rlc));
-  if (flags & BN254_FLAG_COMPRESSED_PROOFS) rc = g16_enqueue_compressed(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags, rlc);
-  else if (rlc) rc = g16_enqueue_rlc(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
-  else rc = g16_enqueue_exact(pvk, d, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags);
-  if (rc) return rc;
-  HIPCK(hipEventRecord(d->busy_ev, user));
-  d->busy_valid = true;
-  return BN254_OK;
-}
-
-// SP1 public inputs, chunk by chunk (at most G16_MAX_BATCH proofs, as g16_enqueue_compressed): k_sp1_public_inputs writes the rows vkey_hash | digest and the
-// pre-status bytes into the row scratch, the pipeline chosen for the whole batch (with BN254_FLAG_COMPRESSED_PROOFS: decompression first) runs on the rows with
-// n_public = 2, and k_g16_status_merge makes MALFORMED override for a range outside the values buffer.  Everything is on `user`, so the next chunk's hashing
-// overwrites the rows only after this chunk is done with them.  use_rlc as in g16_enqueue.
-static int g16_enqueue_sp1(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const Sp1Src& s, size_t n, void* d_status,
-                           hipStream_t user, unsigned flags, int use_rlc = -1) {
-  if (d->busy_valid) HIPCK(hipStreamWaitEvent(user, d->busy_ev, 0));
-  const bool rlc = use_rlc >= 0 ? use_rlc != 0 : (rlc_eligible(pvk, 2, n, flags) && !rlc_bypass(d->rlc));
-  const unsigned raw_flags = flags & ~(unsigned)BN254_FLAG_COMPRESSED_PROOFS;
-  for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
+  if (!sp1) rc = g16_dispatch(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, user, flags, rlc);
+  else for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
     const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
-    if (g16_sp1_alloc(m).proofs > d->sp1_cap) return set_err(BN254_E_BAD_ARG, "SP1 row scratch smaller than the batch (internal sizing error)");
+    if (g16_sp1_alloc(m).proofs > d->sp1_proofs()) return set_err(BN254_E_BAD_ARG, "SP1 row scratch smaller than the batch (internal sizing error)");
     uint8_t* rows = d->sp1;
-    uint8_t* pre = d->sp1 + d->sp1_cap * 64;
+    uint8_t* pre = d->sp1 + d->sp1_proofs() * 64;
     uint8_t* st = (uint8_t*)d_status + off;
-    const uint8_t* pr = (const uint8_t*)d_proofs + off * proof_stride;
-    hipError_t e = bn254_launch_sp1_public_inputs(s.vkh + off * s.vkh_stride, s.vkh_stride, s.pv, s.pv_bytes, s.pv_base, s.off + off, (uint32_t)m, rows, pre, user);
-    if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
-                                         std::string("kernel launch (SP1 public inputs): ") + hipGetErrorString(e));
-    int rc;
-    if (flags & BN254_FLAG_COMPRESSED_PROOFS) rc = g16_enqueue_compressed(pvk, d, device, pr, proof_stride, rows, 2, m, st, user, flags, rlc);
-    else if (rlc) rc = g16_enqueue_rlc(pvk, d, device, pr, proof_stride, rows, 2, m, st, user, raw_flags);
-    else rc = g16_enqueue_exact(pvk, d, pr, proof_stride, rows, 2, m, st, user, raw_flags);
-    if (rc) return rc;
-    e = bn254_launch_g16_status_merge(st, pre, (uint32_t)m, user);
-    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("kernel launch (status merge): ") + hipGetErrorString(e));
+    hipError_t e = bn254_launch_sp1_public_inputs(sp1->vkh + off * sp1->vkh_stride, sp1->vkh_stride, sp1->pv, sp1->pv_bytes, sp1->pv_base, sp1->off + off, (uint32_t)m, rows, pre, user);
+    if (e != hipSuccess) return launch_err(e, "SP1 public inputs");
+    if ((rc = g16_dispatch(pvk, d, device, (const uint8_t*)d_proofs + off * proof_stride, proof_stride, rows, 2, m, st, user, flags, rlc))) return rc;
+    if ((e = bn254_launch_g16_status_merge(st, pre, (uint32_t)m, user)) != hipSuccess) return set_err(BN254_E_HIP, std::string("kernel launch (status merge): ") + hipGetErrorString(e));
   }
+  if (rc) return rc;
   HIPCK(hipEventRecord(d->busy_ev, user));
   d->busy_valid = true;
   return BN254_OK;
@@ -528,10 +466,8 @@ int g16_sp1_device(const bn254_g16_pvk* pvk, const void* d_proofs, size_t proof_
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
   int rc;
-  if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
-  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
-  if ((rc = ensure_sp1(*d, n))) return rc;
-  return g16_enqueue_sp1(pvk, d, device, d_proofs, proof_stride, s, n, d_status, user, flags);
+  if ((rc = ensure_dev(pvk, *d, device, n)) || (rc = ensure_scratch(*d, n, flags, true))) return rc;
+  return g16_enqueue(pvk, d, device, d_proofs, proof_stride, nullptr, 2, n, d_status, user, flags, -1, &s);
 }
 
 extern "C" {
@@ -542,8 +478,7 @@ int bn254_groth16_verify_batch_device(const bn254_g16_pvk* pvk, const void* d_pr
   if (rc || n == 0) return rc;
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
-  if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
-  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
+  if ((rc = ensure_dev(pvk, *d, device, n)) || (rc = ensure_scratch(*d, n, flags, false))) return rc;
   return g16_enqueue(pvk, d, device, d_proofs, proof_stride, d_inputs, n_public, n, d_status, (hipStream_t)hip_stream, flags);
 }
 
@@ -647,29 +582,11 @@ int bn254_groth16_kernel_profile_all(const bn254_g16_pvk* pvk, int device, unsig
   return BN254_OK;
 }
 
-// Host buffers.  The caller's memory is pageable, and a hipMemcpyAsync from pageable memory is neither asynchronous nor fast (the runtime stages
-// it through its own bounce buffer while the calling thread waits).  So the library keeps a ring of three PINNED pieces per (key, device): host
-// threads copy piece i + 1 of the caller's buffers into the ring while piece i travels to the device (a true asynchronous copy on the copy
-// stream) and the previous compute chunk runs; a compute chunk (2^17 proofs first, so that the exposed copy is short, then 2^18) waits on the
-// GPU for the event of its last piece.  Only stream-scoped synchronisation, one status copy at the end.  The device lock is held for the whole
-// call: the staging buffers belong to this batch until its statuses are back.
-#define HOST_RING 3
-static int host_ring_ensure(DevState& d, size_t piece_bytes) {
-  if (piece_bytes <= d.pin_cap) return BN254_OK;
-  for (int i = 0; i < HOST_RING; i++) {
-    if (d.pin[i]) HIPCK(hipHostFree(d.pin[i]));
-    d.pin[i] = nullptr;
-  }
-  d.pin_cap = 0;
-  for (int i = 0; i < HOST_RING; i++) {
-    HIPCK(hipHostMalloc((void**)&d.pin[i], piece_bytes, hipHostMallocDefault));
-    if (!d.pin_ev[i]) HIPCK(hipEventCreateWithFlags(&d.pin_ev[i], hipEventDisableTiming));
-  }
-  d.pin_cap = piece_bytes;
-  return BN254_OK;
-}
 }  // extern "C"
 
+// Host buffers go through the key's ring of pinned pieces (PinRing, bn254_capi_owners.h): a compute chunk (2^17 proofs first, so that the exposed copy is short, then
+// 2^18) waits on the GPU for the event of its last piece; one status copy at the end.  The device lock is held for the whole call: the staging buffers belong to
+// this batch until its statuses are back.
 // The host-buffer batch.  sp1 = nullptr: the raw entry.  sp1 != nullptr (host buffers, offsets already checked to be non-decreasing): the public inputs are the
 // SP1 rows -- nothing is read from public_inputs; at the start of every compute chunk its offsets, values and vkey hashes go through the same pinned ring
 // ahead of its proofs (each byte once: the values are staged as bytes [off[0], off[n]) of the caller's buffer), the chunk is hashed on the device and the
@@ -679,19 +596,13 @@ static int g16_host_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_
   int rc;
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
-  if ((rc = ensure_dev(pvk, *d, device, n))) return rc;
-  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_cmp(*d, n))) return rc;
+  if ((rc = ensure_dev(pvk, *d, device, n)) || (rc = ensure_scratch(*d, n, flags, sp1 != nullptr))) return rc;
   if (sp1) n_public = 0;   // staged per proof: the proof only (the rows are made on the device)
   const size_t in_row = n_public * 32, row = proof_stride + in_row;
   size_t pb = n * proof_stride, ib = n * in_row;
-  if ((rc = grow(&d->st_proofs, &d->st_proofs_cap, pb)) || (rc = grow(&d->st_inputs, &d->st_inputs_cap, ib ? ib : 32)) ||
-      (rc = grow(&d->st_status, &d->st_status_cap, n)))
-    return rc;
+  if ((rc = d->st_proofs.ensure(pb)) || (rc = d->st_inputs.ensure(ib ? ib : 32)) || (rc = d->st_status.ensure(n))) return rc;
   const uint64_t pv_total = sp1 ? sp1->off[n] - sp1->off[0] : 0;
-  if (sp1 && ((rc = ensure_sp1(*d, n)) || (rc = grow(&d->st_pv, &d->st_pv_cap, pv_total ? pv_total : 4)) ||
-              (rc = grow(&d->st_off, &d->st_off_cap, (n + 1) * 8)) || (rc = grow(&d->st_vkh, &d->st_vkh_cap, sp1->vkh_stride ? n * 32 : 32))))
-    return rc;
-  if (!d->host_stream) { HIPCK(hipStreamCreateWithFlags(&d->host_stream, hipStreamNonBlocking)); HIPCK(hipStreamCreateWithFlags(&d->copy_stream, hipStreamNonBlocking)); }
+  if (sp1 && ((rc = d->st_pv.ensure(pv_total ? pv_total : 4)) || (rc = d->st_off.ensure((n + 1) * 8)) || (rc = d->st_vkh.ensure(sp1->vkh_stride ? n * 32 : 32)))) return rc;
   // compute chunks: a short first one (its copy is the only exposed one: 2^17 proofs = 42 MB, under a millisecond of DMA), then the rest in chunks
   // as large as the workspace allows -- every chunk boundary drains both sub-batch streams, so fewer chunks is faster
   static const size_t first_chunk = [] { const char* e = getenv("BN254_HOST_FIRST_CHUNK_LOG2"); int v = e ? atoi(e) : 17; if (v < 12) v = 12; if (v > 20) v = 20; return (size_t)1 << v; }();
@@ -701,7 +612,9 @@ static int g16_host_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_
   size_t piece = piece_bytes_target / row / 256 * 256;
   if (piece < 256) piece = 256;
   if (piece > n) piece = (n + 255) / 256 * 256;
-  if ((rc = host_ring_ensure(*d, piece * row))) return rc;
+  PinRing& ring = d->ring;
+  if ((rc = ring.ensure(piece * row))) return rc;
+  ring.begin();
   // the RLC mode forms its groups over the whole batch it is handed: keep it in one piece -- but only when this call really runs the mode
   // (same predicate as g16_enqueue, the adaptive bypass included, decided ONCE here); a flag that will be ignored keeps the chunked
   // copy / compute overlap
@@ -711,37 +624,22 @@ static int g16_host_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   double t_copy = 0, t_wait = 0, t_enq = 0;
   const auto t_begin = now();
-  size_t copied = 0, computed = 0, slot_uses = 0;
+  size_t copied = 0, computed = 0;
   // the first chunk is short (its copy is the only exposed one) unless the batch is small anyway
   size_t c_end = (use_rlc || n < 2 * first_chunk) ? n : first_chunk;
   while (computed < n) {
-    hipEvent_t last = nullptr;
-    // bytes [0, len) of a device buffer through the ring, fill(pin, from, k) writing bytes [from, from + k) into the pinned piece
-    auto push = [&](uint8_t* dst, size_t len, const std::function<void(uint8_t*, size_t, size_t)>& fill) -> int {
-      for (size_t from = 0; from < len;) {
-        const size_t k = len - from < d->pin_cap ? len - from : d->pin_cap;
-        const int slot = (int)(slot_uses % HOST_RING);
-        if (slot_uses >= HOST_RING) HIPCK(hipEventSynchronize(d->pin_ev[slot]));
-        fill(d->pin[slot], from, k);
-        HIPCK(hipMemcpyAsync(dst + from, d->pin[slot], k, hipMemcpyHostToDevice, d->copy_stream));
-        HIPCK(hipEventRecord(d->pin_ev[slot], d->copy_stream));
-        last = d->pin_ev[slot];
-        slot_uses++; from += k;
-      }
-      return BN254_OK;
-    };
     if (sp1) {   // this chunk's offsets (the first chunk: off[0 .. c_end], later ones off[computed + 1 .. c_end]), values and vkey hashes
       const size_t o_lo = computed ? computed + 1 : 0;
       const uint8_t* osrc = (const uint8_t*)(sp1->off + o_lo);
       const uint64_t v_lo = sp1->off[computed] - sp1->off[0], v_hi = sp1->off[c_end] - sp1->off[0];
       const uint8_t* vsrc = sp1->pv + sp1->off[computed];
       const size_t vk_stride = sp1->vkh_stride; const uint8_t* vk = sp1->vkh; const size_t first = computed;
-      if ((rc = push(d->st_off + o_lo * 8, (c_end + 1 - o_lo) * 8, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, osrc + f, k); })) ||
-          (rc = push(d->st_pv + v_lo, v_hi - v_lo, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, vsrc + f, k); })))
+      if ((rc = ring.push(d->st_off + o_lo * 8, (c_end + 1 - o_lo) * 8, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, osrc + f, k); })) ||
+          (rc = ring.push(d->st_pv + v_lo, v_hi - v_lo, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, vsrc + f, k); })))
         return rc;
-      if (vk_stride == 0 && computed == 0) rc = push(d->st_vkh, 32, [&](uint8_t* q, size_t, size_t) { memcpy(q, vk, 32); });
-      else if (vk_stride == 32) rc = push(d->st_vkh + first * 32, (c_end - first) * 32, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, vk + first * 32 + f, k); });
-      else if (vk_stride) rc = push(d->st_vkh + first * 32, (c_end - first) * 32, [&](uint8_t* q, size_t f, size_t k) {
+      if (vk_stride == 0 && computed == 0) rc = ring.push(d->st_vkh, 32, [&](uint8_t* q, size_t, size_t) { memcpy(q, vk, 32); });
+      else if (vk_stride == 32) rc = ring.push(d->st_vkh + first * 32, (c_end - first) * 32, [&](uint8_t* q, size_t f, size_t k) { parallel_copy(q, vk + first * 32 + f, k); });
+      else if (vk_stride) rc = ring.push(d->st_vkh + first * 32, (c_end - first) * 32, [&](uint8_t* q, size_t f, size_t k) {
         for (size_t b = f; b < f + k;) {   // compacted to 32 bytes per proof
           const size_t r = b / 32, o = b % 32, t = 32 - o < f + k - b ? 32 - o : f + k - b;
           memcpy(q + (b - f), vk + (first + r) * vk_stride + o, t);
@@ -750,44 +648,35 @@ static int g16_host_batch(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_
       });
       if (rc) return rc;
     }
-    while (copied < c_end) {
+    while (copied < c_end) {   // a piece of `m` records: the proofs, then their input rows
       const size_t m = c_end - copied < piece ? c_end - copied : piece;
-      const int slot = (int)(slot_uses % HOST_RING);
+      uint8_t* pin;
       auto ta = now();
-      if (slot_uses >= HOST_RING) HIPCK(hipEventSynchronize(d->pin_ev[slot]));     // the piece that used this slot has left for the device
+      if ((rc = ring.acquire(&pin))) return rc;
       auto tb = now();
-      parallel_copy(d->pin[slot], proofs + copied * proof_stride, m * proof_stride);
-      if (in_row) parallel_copy(d->pin[slot] + m * proof_stride, public_inputs + copied * in_row, m * in_row);
+      parallel_copy(pin, proofs + copied * proof_stride, m * proof_stride);
+      if (in_row) parallel_copy(pin + m * proof_stride, public_inputs + copied * in_row, m * in_row);
       auto tc = now();
       t_wait += ms(ta, tb); t_copy += ms(tb, tc);
-      HIPCK(hipMemcpyAsync(d->st_proofs + copied * proof_stride, d->pin[slot], m * proof_stride, hipMemcpyHostToDevice, d->copy_stream));
-      if (in_row) HIPCK(hipMemcpyAsync(d->st_inputs + copied * in_row, d->pin[slot] + m * proof_stride, m * in_row, hipMemcpyHostToDevice, d->copy_stream));
-      HIPCK(hipEventRecord(d->pin_ev[slot], d->copy_stream));
-      last = d->pin_ev[slot];
-      slot_uses++; copied += m;
+      HIPCK(hipMemcpyAsync(d->st_proofs + copied * proof_stride, pin, m * proof_stride, hipMemcpyHostToDevice, ring.copy));
+      if (in_row) HIPCK(hipMemcpyAsync(d->st_inputs + copied * in_row, pin + m * proof_stride, m * in_row, hipMemcpyHostToDevice, ring.copy));
+      if ((rc = ring.commit())) return rc;
+      copied += m;
     }
-    if (last) HIPCK(hipStreamWaitEvent(d->host_stream, last, 0));
+    if (ring.last()) HIPCK(hipStreamWaitEvent(ring.compute, ring.last(), 0));
     auto td = now();
-    if (sp1) {
-      const Sp1Src staged{d->st_vkh + (sp1->vkh_stride ? computed * 32 : 0), (size_t)(sp1->vkh_stride ? 32 : 0), d->st_pv, pv_total, sp1->off[0], (const uint64_t*)d->st_off + computed};
-      rc = g16_enqueue_sp1(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, staged, c_end - computed, d->st_status + computed, d->host_stream,
-                           flags, use_rlc);
-    } else
-      rc = g16_enqueue(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, d->st_inputs + computed * in_row, n_public, c_end - computed,
-                       d->st_status + computed, d->host_stream, flags, use_rlc);
-    if (rc) {   // pieces of the pinned ring and earlier chunks may still be in flight: the ring and the staging buffers must be quiescent when the lock is released
-      const std::string keep = g_err;
-      (void)hipStreamSynchronize(d->copy_stream); (void)hipStreamSynchronize(d->host_stream);
-      g_err = keep;
-      return rc;
-    }
+    const Sp1Src staged = sp1 ? Sp1Src{d->st_vkh + (sp1->vkh_stride ? computed * 32 : 0), (size_t)(sp1->vkh_stride ? 32 : 0), d->st_pv, pv_total, sp1->off[0], (const uint64_t*)(uint8_t*)d->st_off + computed}
+                              : Sp1Src{};
+    rc = g16_enqueue(pvk, d, device, d->st_proofs + computed * proof_stride, proof_stride, d->st_inputs + computed * in_row, n_public, c_end - computed,
+                     d->st_status + computed, ring.compute, flags, use_rlc, sp1 ? &staged : nullptr);
+    if (rc) return ring.drain(rc);
     t_enq += ms(td, now());
     computed = c_end;
     c_end = n - c_end < hchunk ? n : c_end + hchunk;
   }
   const auto t_enqueued = now();
-  HIPCK(hipMemcpyAsync(status, d->st_status, n, hipMemcpyDeviceToHost, d->host_stream));
-  HIPCK(hipStreamSynchronize(d->host_stream));
+  HIPCK(hipMemcpyAsync(status, d->st_status, n, hipMemcpyDeviceToHost, ring.compute));
+  HIPCK(hipStreamSynchronize(ring.compute));
   if (timing) fprintf(stderr, "host-buffer batch %zu: pieces of %zu proofs; host copies %.2f ms, ring waits %.2f ms, kernel enqueue %.2f ms, all enqueued after %.2f ms, done after %.2f ms\n",
                       n, piece, t_copy, t_wait, t_enq, ms(t_begin, t_enqueued), ms(t_begin, now()));
   return BN254_OK;

@@ -41,7 +41,12 @@ hipError_t bn254_launch_plonk_group_scatter(uint8_t* status, size_t n, const uin
 
 hipError_t bn254_launch_plonk_dbg_zeta(const void* d_work, size_t n, uint8_t* d_zeta, uint8_t* d_status, hipStream_t s);
 
+#pragma GCC visibility push(hidden)
+extern thread_local std::string g_err;     // bn254_last_error() of the calling thread
+int set_err(int code, const std::string& msg);
+#pragma GCC visibility pop
 #define HIPCK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return set_err(BN254_E_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
+#include "bn254_capi_owners.h"
 
 // Initial values of the knobs come from the environment, read ONCE when the library is loaded (getenv racing a host's setenv is undefined behaviour).
 static inline long env_long(const char* name, long dflt) { const char* e = getenv(name); return e ? atol(e) : dflt; }
@@ -49,13 +54,13 @@ static inline long env_long(const char* name, long dflt) { const char* e = geten
 // BN254_FLAG_RLC: per (key, device) buffers of the random-linear-combination batch mode (bn254_rlc.h)
 struct RlcDev {
   bool ready = false;
-  int32_t *btab = nullptr, *tab = nullptr, *one = nullptr;            // key-side tables (uploaded once)
-  uint8_t* grp_status = nullptr; size_t grp_cap = 0;
-  uint32_t* idx = nullptr; size_t idx_cap = 0;
-  uint8_t *fb_proofs = nullptr, *fb_inputs = nullptr, *fb_status = nullptr; size_t fb_cap = 0, fb_in_cap = 0;
-  uint8_t* h_status = nullptr; uint32_t* h_idx = nullptr; size_t h_cap = 0;   // pinned
+  DevBuf<int32_t> btab, tab, one;                                     // key-side tables (uploaded once)
+  // group status bytes and the indices of the pending proofs with their pinned copies: sized together for grp_cap proofs (rlc_ensure)
+  DevBuf<uint8_t> grp_status; DevBuf<uint32_t> idx; PinBuf<uint8_t> h_status; PinBuf<uint32_t> h_idx; size_t grp_cap = 0;
+  // the exact second pass: records, input rows and status bytes of the proofs of failed groups, for fb_cap proofs (grown by the pass that needs more)
+  DevBuf<uint8_t> fb_proofs, fb_inputs, fb_status; size_t fb_cap = 0, fb_in_cap = 0;
   // keys with more than RLC_MAX_PUBLIC inputs: group scalar rows, digits and chunk sums of the groups' MSM (bn254_g16_plan.h::g16_rlc_wide_alloc), for wide_cap groups
-  uint8_t* grp_rows = nullptr; uint16_t* grp_digits = nullptr; int32_t* grp_part = nullptr; size_t wide_cap = 0;
+  DevBuf<uint8_t> grp_rows; DevBuf<uint16_t> grp_digits; DevBuf<int32_t> grp_part; size_t wide_cap = 0;
   // adaptive use of the mode: share of the checked proofs the last RLC passes sent to the exact fallback (exponential average) and how many
   // calls have bypassed the mode since the last pass that measured it
   bool have_obs = false; float fb_share = 0.f; unsigned bypassed = 0, bypassed_total = 0;
@@ -68,34 +73,35 @@ struct RlcDev {
 struct DevState {
   std::mutex mu;
   bool ready = false;
-  int32_t *k0 = nullptr, *gtab = nullptr, *dtab = nullptr, *target = nullptr, *msm = nullptr;
-  int32_t* ws = nullptr; size_t ws_cap = 0;                         // proofs the workspace can hold
-  int32_t* msm_part = nullptr; size_t msm_part_cap = 0, msm_chunks = 0;             // wide keys: partial sums of the public-input MSM (proofs it holds)
-  uint8_t *st_proofs = nullptr, *st_inputs = nullptr, *st_status = nullptr;  // staging for the host-buffer entry point
-  size_t st_proofs_cap = 0, st_inputs_cap = 0, st_status_cap = 0;
-  hipStream_t host_stream = nullptr, copy_stream = nullptr;   // host-buffer entry: copy / compute overlap
-  uint8_t* pin[3] = {nullptr, nullptr, nullptr}; size_t pin_cap = 0; hipEvent_t pin_ev[3] = {nullptr, nullptr, nullptr};   // ring of pinned pieces (HOST_RING)
-  hipEvent_t busy_ev = nullptr; bool busy_valid = false;
-  hipEvent_t ev[5]; bool ev_ready = false; bool ev_recorded = false;
+  DevBuf<int32_t> k0, gtab, dtab, target, msm;
+  DevBuf<int32_t> ws;                                               // G16_WS_BYTES_PER_PROOF per proof
+  size_t ws_proofs() const { return ws.cap() / (size_t)(G16_WS_BYTES_PER_PROOF / 4); }
+  DevBuf<int32_t> msm_part; size_t msm_part_cap = 0, msm_chunks = 0;                // wide keys: partial sums of the public-input MSM (proofs it holds)
+  DevBuf<uint8_t> st_proofs, st_inputs, st_status;                  // staging for the host-buffer entry point, through `ring`
+  PinRing ring;                                                     // host-buffer entry: copy / compute overlap
+  Event busy_ev; bool busy_valid = false;
+  Event ev[5]; bool ev_ready = false; bool ev_recorded = false;
   // concurrent sub-batches (see g16_enqueue_exact): part 0 runs on the caller's stream, parts 1..3 on these, created when first needed -- every
   // stream of a process shares the runtime's few hardware queues (four by default), and a copy stream that lands on the queue of a busy compute
   // stream waits behind its kernels (measured: 3 GB/s instead of 55), so no stream is created that is not used
-  hipStream_t aux[3] = {nullptr, nullptr, nullptr}; int aux_count = 0; hipEvent_t fork_ev = nullptr, join_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  // per-launch timing of the first sub-batch (bn254_groth16_kernel_profile)
-  std::vector<hipEvent_t> prof_ev; std::vector<uint8_t> prof_kid; G16Prof prof{0, nullptr, nullptr, 0, 0}; size_t prof_n = 0; unsigned prof_epoch = 0;
+  Stream aux[3]; Event fork_ev, join_ev[4];
+  // per-launch timing of the first sub-batch (bn254_groth16_kernel_profile): prof_own owns the events, prof_ev is the array the launcher records into
+  std::vector<Event> prof_own; std::vector<hipEvent_t> prof_ev; std::vector<uint8_t> prof_kid; G16Prof prof{0, nullptr, nullptr, 0, 0}; size_t prof_n = 0; unsigned prof_epoch = 0;
   // the same for the SECOND sub-batch (its launches run on another stream beside the first's): bn254_groth16_kernel_profile_all
-  std::vector<hipEvent_t> prof2_ev; std::vector<uint8_t> prof2_kid; G16Prof prof2{0, nullptr, nullptr, 0, 0}; bool prof2_used = false;
+  std::vector<Event> prof2_own; std::vector<hipEvent_t> prof2_ev; std::vector<uint8_t> prof2_kid; G16Prof prof2{0, nullptr, nullptr, 0, 0}; bool prof2_used = false;
   RlcDev rlc;                                                       // BN254_FLAG_RLC buffers (bn254_rlc.hpp)
   // BN254_FLAG_COMPRESSED_PROOFS: raw records of the decompressed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_cmp_alloc); grown at the
-  // first compressed batch that needs more (cmp_cap proofs)
-  uint8_t* cmp = nullptr; size_t cmp_cap = 0;
-  // SP1 public inputs: rows vkey_hash | digest of the hashed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_sp1_alloc; sp1_cap proofs), grown at
+  // first compressed batch that needs more
+  DevBuf<uint8_t> cmp;
+  size_t cmp_proofs() const { return cmp.cap() / 257; }
+  // SP1 public inputs: rows vkey_hash | digest of the hashed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_sp1_alloc), grown at
   // the first SP1 batch that needs more.  The host-buffer entry stages the batch's values, offsets and vkey hashes in st_pv / st_off / st_vkh.
-  uint8_t* sp1 = nullptr; size_t sp1_cap = 0;
-  uint8_t *st_pv = nullptr, *st_off = nullptr, *st_vkh = nullptr; size_t st_pv_cap = 0, st_off_cap = 0, st_vkh_cap = 0;
+  DevBuf<uint8_t> sp1;
+  size_t sp1_proofs() const { return sp1.cap() / 65; }
+  DevBuf<uint8_t> st_pv, st_off, st_vkh;
   // do the sub-batch streams overlap?  ov_ev: start / end of part 0 and of part 1 of the first two-stream batch; ov_state 0: not measured, 1: events recorded,
   // 2: measured (ov_ratio = sum of the two durations / their union: ~2 side by side, ~1 one after the other); single_stream: fall back to one sub-batch per launch
-  hipEvent_t ov_ev[4] = {nullptr, nullptr, nullptr, nullptr}; int ov_state = 0; float ov_ratio = -1.f; bool single_stream = false;
+  Event ov_ev[4]; int ov_state = 0; float ov_ratio = -1.f; bool single_stream = false;
   // the decision is not taken from one measurement (another tenant's kernels, a profiler that serialises dispatches): OV_AGREE consecutive measurements must say
   // "serialised" before the plan changes, a measurement that says "side by side" resets the count; once on one sub-batch per launch, every OV_REPROBE-th batch runs two
   // again and is measured, so that a transient cause does not pin the key to the slower plan for its lifetime.  `diag`: the explanation, per (key, device), handed out by
@@ -119,24 +125,25 @@ struct bn254_g16_pvk {
 #define PLONK_MAX_LAUNCH 262144
 struct PlonkCtx {
   size_t cap = 0;                      // proofs the buffers below hold
-  hipStream_t stream = nullptr, aux = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  hipEvent_t tk[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // timing: before stage 1 | after it | MSM rows | sum | stage 2 | MSM rows | sums | pairing check
+  Stream stream, aux; Event ev_fork, ev_join;
+  Event tk[8];   // timing: before stage 1 | after it | MSM rows | sum | stage 2 | MSM rows | sums | pairing check
   float last_ms[BN254_PLONK_NUM_TIMINGS] = {0}; size_t last_lanes[2] = {0, 0}; bool last_valid = false;
-  int32_t *ws = nullptr, *part = nullptr, *glv_tab = nullptr;   // part: the rows of an MSM launch (bn254_msm.h); glv_tab: the window tables of its variable rows
+  DevBuf<int32_t> ws, part, glv_tab;   // part: the rows of an MSM launch (bn254_msm.h); glv_tab: the window tables of its variable rows
   size_t part_points = 0;              // projective points (rows x items) `part` holds (plonk_part_points of the capacity)
   size_t glv_lanes = 0;                // lanes glv_tab holds (plonk_scratch_lanes of the capacity); a launch checks its need against it before it is enqueued
-  MsmTerm* terms = nullptr; uint8_t* flags = nullptr; uint32_t* words = nullptr; uint8_t *inf = nullptr, *status = nullptr;
-  uint8_t* h_status = nullptr;         // pinned: the status bytes of a pass on their way back
-  // device-side stages (bn254_k_plonk.hip): the batch's proofs and inputs in device memory (through a pinned copy), per-proof state between the stages
-  uint8_t *d_in = nullptr, *h_in = nullptr; size_t in_cap = 0; void* d_work = nullptr;
+  DevBuf<MsmTerm> terms; DevBuf<uint8_t> flags; DevBuf<uint32_t> words; DevBuf<uint8_t> inf, status;
+  PinBuf<uint8_t> h_status;            // pinned: the status bytes of a pass on their way back
+  // device-side stages (bn254_k_plonk.hip): the batch's proofs and inputs in device memory (through a pinned copy: both of in_cap() bytes, or neither), per-proof state between the stages
+  DevBuf<uint8_t> d_in; PinBuf<uint8_t> h_in; DevBuf<uint8_t> d_work;
+  size_t in_cap() const { return h_in.cap(); }
   // BN254_FLAG_RLC: the pairing checks of a pass batched over groups of 64 proofs -- the groups' points and status bytes in a workspace of their own, failed groups counted
-  int32_t* grp_ws = nullptr; uint8_t* grp_status = nullptr; uint32_t* d_fail = nullptr; uint32_t* h_fail = nullptr;
+  DevBuf<int32_t> grp_ws; DevBuf<uint8_t> grp_status; DevBuf<uint32_t> d_fail; PinBuf<uint32_t> h_fail;
 };
 struct PlonkDev {
   bool ready = false;
-  int32_t *tab0 = nullptr, *tab1 = nullptr, *one = nullptr;
-  int32_t* fixed_tabs = nullptr;       // window tables of the key's G1 points (plonk_num_tables x MSM_FW_WINDOWS x MSM_FW_ENTRIES entries, bn254_fw.h)
-  void* d_key = nullptr;               // the parsed key (PlonkKey) for the device-side stages
+  DevBuf<int32_t> tab0, tab1, one;
+  DevBuf<int32_t> fixed_tabs;          // window tables of the key's G1 points (plonk_num_tables x MSM_FW_WINDOWS x MSM_FW_ENTRIES entries, bn254_fw.h)
+  DevBuf<uint8_t> d_key;               // the parsed key (PlonkKey) for the device-side stages
   PlonkCtx ctx[PLONK_WORKERS];
   // The contexts are handed out to calls: a call takes one per sub-batch (all at once, so two calls cannot wait for each other) and returns them when it
   // is done.  Calls on ONE prepared key from several host threads therefore run side by side, up to PLONK_WORKERS sub-batches in flight; at 4096 proofs a
@@ -145,7 +152,7 @@ struct PlonkDev {
   float last_ms[BN254_PLONK_NUM_TIMINGS] = {0}; size_t last_lanes[2] = {0, 0}; bool last_valid = false;   // first sub-batch of the call that finished last
   // SP1 entries (bn254_capi_sp1.hip): device buffers for the rows, pre-status bytes and staged values of a call.  A call takes one for itself (calls on one key run side
   // by side, so the rows cannot live in the key's state) and gives it back for the next call: a hipFree per call would wait for every other call's work on the device
-  std::mutex sp1_mu; std::vector<std::pair<uint8_t*, size_t>> sp1_bufs;
+  std::mutex sp1_mu; std::vector<DevBuf<uint8_t>> sp1_bufs;
 };
 struct PlonkLease {   // the contexts of one call
   PlonkDev* d; int idx[PLONK_WORKERS]; int n = 0;
@@ -212,8 +219,6 @@ class KeyCache {
 
 // Shared helpers (internal linkage across the bn254_capi*.hip objects only: none of them is part of the exported ABI)
 #pragma GCC visibility push(hidden)
-extern thread_local std::string g_err;     // bn254_last_error() of the calling thread
-int set_err(int code, const std::string& msg);
 int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* inputs, size_t n_public, size_t n, const void* status,
                      unsigned flags);
 int check_device(int device);
@@ -225,7 +230,8 @@ int check_keys_args(const bn254_g16_pvk* const* pvks, size_t n_keys, const void*
 void set_diag(const std::string& msg);     // bn254_last_diagnostic() of the calling thread (bn254_capi_g16.hip)
 void keys_sets_drop(const bn254_g16_pvk* member);   // bn254_capi_keys.hip: forget every cached key set that contains this key
 void parallel_copy(uint8_t* dst, const uint8_t* src, size_t bytes);
-int build_tables_on_device(int form, const std::vector<int32_t>& pts, int32_t** dst);
+int build_tables_on_device(int form, const std::vector<int32_t>& pts, DevBuf<int32_t>& dst);
+int sub_batch_streams();                   // BN254_STREAMS, read once: sub-batches of a Groth16 chunk in flight, 1 .. 4 (default 2)
 // bn254_capi_g16.hip
 DevState* dev_state(const bn254_g16_pvk* pvk, int device);
 int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n);
@@ -251,18 +257,18 @@ int plonk_batch_rows(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t p
                      bool resident);
 #pragma GCC visibility pop
 
-// *dst stays null unless the copy is complete: a caller that retries after a failure uploads exactly what is still missing (a sanitizer run of the
+// dst stays empty unless the copy is complete: a caller that retries after a failure uploads exactly what is still missing (a sanitizer run of the
 // allocation-failure paths found the retry overwriting -- leaking -- the tables an earlier, partly failed attempt had already uploaded)
-template <typename T> static int upload(T** dst, const std::vector<T>& src) {
-  if (*dst) return BN254_OK;
-  size_t bytes = (src.size() ? src.size() : 1) * sizeof(T);
-  T* p = nullptr;
-  HIPCK(hipMalloc((void**)&p, bytes));
+template <typename T> static int upload(DevBuf<T>& dst, const std::vector<T>& src) {
+  if (dst) return BN254_OK;
+  DevBuf<T> p;
+  int rc = p.ensure(src.size());
+  if (rc) return rc;
   if (!src.empty()) {
     hipError_t e = hipMemcpy(p, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(p); return set_err(BN254_E_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e)); }
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("hipMemcpy: ") + hipGetErrorString(e));
   }
-  *dst = p;
+  dst = std::move(p);
   return BN254_OK;
 }
 

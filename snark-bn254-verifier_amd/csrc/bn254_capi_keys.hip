@@ -12,7 +12,6 @@ using bn254::G16KeyDesc;
 // per point), all keys in one allocation each.
 #define KEYS_BLOB_DWORDS ((size_t)2 * BN_ATE_STEPS * FIXED_LINE_DWORDS + 2 * BN_NL + 12 * BN_NL)
 #define KEYS_TABLE_BYTES_PER_POINT ((size_t)32 * 255 * MSM_ENTRY_DWORDS * 4)
-#define KEYS_HOST_RING 3
 #define KEYS_HOST_PIECE ((size_t)16 << 20)
 
 namespace {
@@ -23,30 +22,22 @@ struct KeySet {
   size_t max_public = 0;
   std::mutex mu;                            // everything below: uploads, (re)allocation and the enqueue of a batch
   bool ready = false;
-  int32_t *blob = nullptr, *msm = nullptr; G16KeyDesc* desc = nullptr;
-  // what a reservation of n proofs sizes: the slot workspace (one chunk), the grouping buffers over keys_slot_bound(n, n_keys) slots
-  size_t cap_n = 0, slot_cap = 0, ws_cap = 0;
-  int32_t* ws = nullptr;
-  uint32_t *count = nullptr, *base = nullptr, *cursor = nullptr, *n_slots = nullptr, *slot_to_proof = nullptr, *granule_key = nullptr;
-  uint8_t* slot_status = nullptr;
-  uint8_t* cmp = nullptr; size_t cmp_cap = 0;                       // BN254_FLAG_COMPRESSED_PROOFS: raw records of the whole batch, then one pre-status byte per proof
-  hipStream_t aux = nullptr; hipEvent_t fork_ev = nullptr, join_ev = nullptr, busy_ev = nullptr; bool busy_valid = false;
-  // host-buffer entry: device copies of the caller's buffers, the pinned ring they travel through, its streams
-  uint8_t *st_proofs = nullptr, *st_inputs = nullptr, *st_index = nullptr, *st_status = nullptr; size_t st_proofs_cap = 0, st_inputs_cap = 0, st_index_cap = 0, st_status_cap = 0;
-  uint8_t* pin[KEYS_HOST_RING] = {nullptr, nullptr, nullptr}; hipEvent_t pin_ev[KEYS_HOST_RING] = {nullptr, nullptr, nullptr};
-  hipStream_t host_stream = nullptr, copy_stream = nullptr;
+  DevBuf<int32_t> blob, msm; DevBuf<G16KeyDesc> desc;
+  // what a reservation of n proofs sizes (ensure_set): the slot workspace (one chunk), the grouping buffers over keys_slot_bound(n, n_keys) slots
+  size_t cap_n = 0, slot_cap = 0;
+  DevBuf<int32_t> ws;
+  size_t ws_slots() const { return ws.cap() / (size_t)(G16_WS_BYTES_PER_PROOF / 4); }
+  DevBuf<uint32_t> count, base, cursor, n_slots, slot_to_proof, granule_key;
+  DevBuf<uint8_t> slot_status;
+  DevBuf<uint8_t> cmp; size_t cmp_cap = 0;                          // BN254_FLAG_COMPRESSED_PROOFS: raw records of the whole batch, then one pre-status byte per proof
+  Stream aux; Event fork_ev, join_ev, busy_ev; bool busy_valid = false;
+  // host-buffer entry: device copies of the caller's buffers, the pinned ring they travel through with its streams
+  DevBuf<uint8_t> st_proofs, st_inputs, st_index, st_status;
+  PinRing ring;
+  // the members release what they own; the set's device is made current and idle first
   ~KeySet() {
     if (!ready && !ws && !blob) return;
-    if (hipSetDevice(device) != hipSuccess) return;
-    (void)hipDeviceSynchronize();
-    void* ptrs[] = {blob, msm, desc, ws, count, base, cursor, n_slots, slot_to_proof, granule_key, slot_status, cmp, st_proofs, st_inputs, st_index, st_status};
-    for (auto q : ptrs) if (q) (void)hipFree(q);
-    for (auto q : pin) if (q) (void)hipHostFree(q);
-    for (auto e : pin_ev) if (e) (void)hipEventDestroy(e);
-    hipEvent_t evs[] = {fork_ev, join_ev, busy_ev};
-    for (auto e : evs) if (e) (void)hipEventDestroy(e);
-    hipStream_t ss[] = {aux, host_stream, copy_stream};
-    for (auto s : ss) if (s) (void)hipStreamDestroy(s);
+    if (hipSetDevice(device) == hipSuccess) (void)hipDeviceSynchronize();
   }
 };
 
@@ -86,16 +77,10 @@ struct SetCache {
 };
 SetCache& set_cache() { static auto* c = new SetCache(); return *c; }
 
-template <class T> int dev_alloc(T** p, size_t count) {
-  if (*p) { HIPCK(hipFree(*p)); *p = nullptr; }
-  hipError_t e = hipMalloc((void**)p, (count ? count : 1) * sizeof(T));
-  if (e == hipErrorOutOfMemory) { *p = nullptr; return set_err(BN254_E_NOMEM, "device memory exhausted (key set)"); }
-  if (e != hipSuccess) { *p = nullptr; return set_err(BN254_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-  return BN254_OK;
-}
-
-// caller holds s.mu.  First use: descriptors, line tables and byte-window tables of the distinct keys.  Then the buffers of a batch of n proofs.
-int ensure_set(KeySet& s, size_t n) {
+// caller holds s.mu.  First use: descriptors, line tables and byte-window tables of the distinct keys.  Then the buffers of a batch of n proofs (with
+// BN254_FLAG_COMPRESSED_PROOFS in flags: its decompression scratch too).  Device memory that runs out here is BN254_E_NOMEM, as for tables that do not fit.
+int ensure_set(KeySet& s, size_t n, unsigned flags) {
+  const int oom = BN254_E_NOMEM;
   int rc = check_device(s.device);
   if (rc) return rc;
   const size_t n_keys = s.list.size();
@@ -125,8 +110,8 @@ int ensure_set(KeySet& s, size_t n) {
     if (table_bytes + ((size_t)512 << 20) > free_b)
       return set_err(BN254_E_NOMEM, "the byte-window tables of the set (" + std::to_string(table_bytes >> 20) + " MB, 652 800 bytes per K point) do not fit the device's free memory (" +
                                         std::to_string(free_b >> 20) + " MB)");
-    if ((rc = upload(&s.blob, blob))) return rc;
-    if (n_points && (rc = build_tables_on_device(1, pts, &s.msm))) return rc;
+    if ((rc = upload(s.blob, blob))) return rc;
+    if (n_points && (rc = build_tables_on_device(1, pts, s.msm))) return rc;
     std::vector<G16KeyDesc> desc(n_keys);
     for (size_t k = 0; k < n_keys; k++) {
       const size_t u = uniq[s.list[k]];
@@ -138,51 +123,34 @@ int ensure_set(KeySet& s, size_t n) {
       d.n_public = (int32_t)h.key_inputs();
       d.inputs_match = h.n_k ? 1 : 0;
     }
-    if ((rc = upload(&s.desc, desc))) return rc;
-    HIPCK(hipEventCreateWithFlags(&s.busy_ev, hipEventDisableTiming));
-    HIPCK(hipEventCreateWithFlags(&s.fork_ev, hipEventDisableTiming));
-    HIPCK(hipEventCreateWithFlags(&s.join_ev, hipEventDisableTiming));
-    HIPCK(hipStreamCreateWithFlags(&s.aux, hipStreamNonBlocking));
-    if ((rc = dev_alloc(&s.count, n_keys)) || (rc = dev_alloc(&s.base, n_keys)) || (rc = dev_alloc(&s.cursor, n_keys)) || (rc = dev_alloc(&s.n_slots, 1))) return rc;
+    if ((rc = upload(s.desc, desc)) || (rc = s.busy_ev.ensure()) || (rc = s.fork_ev.ensure()) || (rc = s.join_ev.ensure()) || (rc = s.aux.ensure())) return rc;
+    if ((rc = s.count.ensure(n_keys, oom)) || (rc = s.base.ensure(n_keys, oom)) || (rc = s.cursor.ensure(n_keys, oom)) || (rc = s.n_slots.ensure(1, oom))) return rc;
     s.ready = true;
   }
-  if (n > s.cap_n) {
+  if (n > s.cap_n) {   // the workspace and the slot buffers are sized together: cap_n / slot_cap are what ALL of them hold, 0 while any of them is being replaced
     const size_t slot_cap = (size_t)bn254::keys_slot_bound(n, n_keys);
     const size_t ws_slots = bn254::g16_round256(slot_cap < (size_t)G16_MAX_BATCH ? slot_cap : (size_t)G16_MAX_BATCH);
-    s.cap_n = 0;
-    if (ws_slots > s.ws_cap) {
-      s.ws_cap = 0;
-      if (s.ws) { HIPCK(hipFree(s.ws)); s.ws = nullptr; }
-      hipError_t e = hipMalloc((void**)&s.ws, ws_slots * (size_t)G16_WS_BYTES_PER_PROOF);
-      if (e != hipSuccess) { s.ws = nullptr; return set_err(e == hipErrorOutOfMemory ? BN254_E_NOMEM : BN254_E_HIP, std::string("workspace of the key set: ") + hipGetErrorString(e)); }
-      s.ws_cap = ws_slots;
-    }
-    s.slot_cap = 0;
-    if ((rc = dev_alloc(&s.slot_to_proof, slot_cap)) || (rc = dev_alloc(&s.granule_key, slot_cap / G16_KEYS_GRANULE + 1)) || (rc = dev_alloc(&s.slot_status, slot_cap + 256))) return rc;
+    s.cap_n = s.slot_cap = 0;
+    if ((rc = s.ws.ensure(ws_slots * (size_t)(G16_WS_BYTES_PER_PROOF / 4), oom)) || (rc = s.slot_to_proof.ensure(slot_cap, oom)) ||
+        (rc = s.granule_key.ensure(slot_cap / G16_KEYS_GRANULE + 1, oom)) || (rc = s.slot_status.ensure(slot_cap + 256, oom)))
+      return rc;
     s.slot_cap = slot_cap; s.cap_n = n;
+  }
+  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && n > s.cmp_cap) {
+    s.cmp_cap = 0;
+    if ((rc = s.cmp.ensure(bn254::g16_round256(n) * 257, oom))) return rc;
+    s.cmp_cap = n;
   }
   return BN254_OK;
 }
-int ensure_set_cmp(KeySet& s, size_t n) {
-  if (n <= s.cmp_cap) return BN254_OK;
-  s.cmp_cap = 0;
-  int rc = dev_alloc(&s.cmp, bn254::g16_round256(n) * 257);
-  if (rc) return rc;
-  s.cmp_cap = n;
-  return BN254_OK;
-}
 
-int launch_err(hipError_t e, const char* what) {
-  return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP, std::string("kernel launch (") + what + "): " + hipGetErrorString(e));
-}
-
-// Enqueue one batch on `user`.  Caller holds s.mu and has called ensure_set (and ensure_set_cmp).  exact_slots: the batch's slots where the caller knows them (the
+// Enqueue one batch on `user`.  Caller holds s.mu and has called ensure_set with the batch's flags.  exact_slots: the batch's slots where the caller knows them (the
 // host-buffer entry has counted the index), 0: only the device will know -- the launches then cover keys_slot_bound(n, n_keys) slots and the wavefronts past the real
 // figure leave at once.  Chunks of G16_MAX_BATCH SLOTS share the workspace; a chunk's sub-batches run side by side on `user` and the set's second stream, as in
 // g16_enqueue_exact; both cuts are multiples of 256 slots, so they fall inside a key's run but never inside a granule.
 int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_t proof_stride, const void* d_inputs, size_t input_stride, size_t n, void* d_status, hipStream_t user,
                  unsigned flags, size_t exact_slots) {
-  static const int n_streams = [] { const char* e = getenv("BN254_STREAMS"); int v = e ? atoi(e) : 2; return v < 1 ? 1 : (v > 2 ? 2 : v); }();
+  const int n_streams = sub_batch_streams() < 2 ? sub_batch_streams() : 2;
   const uint32_t n_keys = (uint32_t)s.list.size();
   const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
   if (n > s.cap_n || bound > s.slot_cap) return set_err(BN254_E_BAD_ARG, "buffers of the key set smaller than the batch (internal sizing error)");
@@ -208,11 +176,11 @@ int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_
     const size_t m = slots - off < (size_t)G16_MAX_BATCH ? slots - off : (size_t)G16_MAX_BATCH;
     bn254::G16ChunkPlan plan;
     if (!bn254::g16_plan_chunk(plan, m, 0, 0, n_streams, false)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
-    if (bn254::g16_round256(m) > s.ws_cap) return set_err(BN254_E_BAD_ARG, "workspace of the key set smaller than the batch (internal sizing error)");
+    if (bn254::g16_round256(m) > s.ws_slots()) return set_err(BN254_E_BAD_ARG, "workspace of the key set smaller than the batch (internal sizing error)");
     if (plan.concurrent) HIPCK(hipEventRecord(s.fork_ev, user));
     for (int pi = 0; pi < plan.parts; pi++) {
       const size_t lo = plan.part[pi].first, cnt = plan.part[pi].count;
-      hipStream_t st = (plan.concurrent && (pi & 1)) ? s.aux : user;
+      hipStream_t st = (plan.concurrent && (pi & 1)) ? (hipStream_t)s.aux : user;
       if (st != user && pi == 1) HIPCK(hipStreamWaitEvent(st, s.fork_ev, 0));
       G16KeysLaunchArgs a;
       a.proofs = proofs; a.stride = proof_stride; a.inputs = (const uint8_t*)d_inputs; a.input_stride = input_stride; a.n_proofs = (uint32_t)n;
@@ -234,15 +202,6 @@ int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_
   return BN254_OK;
 }
 
-int grow_bytes(uint8_t** p, size_t* cap, size_t need) {
-  if (need <= *cap) return BN254_OK;
-  *cap = 0;
-  int rc = dev_alloc(p, need);
-  if (rc) return rc;
-  *cap = need;
-  return BN254_OK;
-}
-
 }  // namespace
 
 // bn254_groth16_vk_free: every cached set that contains the key goes
@@ -257,7 +216,7 @@ int bn254_groth16_reserve_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, 
   if ((rc = check_device(device))) return rc;
   std::shared_ptr<KeySet> s = set_cache().get(pvks, n_keys, device, max_public);
   std::lock_guard<std::mutex> lk(s->mu);
-  return ensure_set(*s, n ? n : 1);
+  return ensure_set(*s, n ? n : 1, 0);
 }
 
 int bn254_groth16_verify_batch_keys_device(const bn254_g16_pvk* const* pvks, size_t n_keys, const void* d_key_index, const void* d_proofs, size_t proof_stride,
@@ -268,8 +227,7 @@ int bn254_groth16_verify_batch_keys_device(const bn254_g16_pvk* const* pvks, siz
   if ((rc = check_device(device))) return rc;
   std::shared_ptr<KeySet> s = set_cache().get(pvks, n_keys, device, max_public);
   std::lock_guard<std::mutex> lk(s->mu);
-  if ((rc = ensure_set(*s, n))) return rc;
-  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_set_cmp(*s, n))) return rc;
+  if ((rc = ensure_set(*s, n, flags))) return rc;
   return keys_enqueue(*s, d_key_index, d_proofs, proof_stride, d_public_inputs, input_stride, n, d_status, (hipStream_t)hip_stream, flags, 0);
 }
 
@@ -295,40 +253,23 @@ int bn254_groth16_verify_batch_keys(const bn254_g16_pvk* const* pvks, size_t n_k
   std::shared_ptr<KeySet> sp = set_cache().get(pvks, n_keys, device, max_public);
   KeySet& s = *sp;
   std::lock_guard<std::mutex> lk(s.mu);
-  if ((rc = ensure_set(s, n))) return rc;
-  if ((flags & BN254_FLAG_COMPRESSED_PROOFS) && (rc = ensure_set_cmp(s, n))) return rc;
+  if ((rc = ensure_set(s, n, flags))) return rc;
   const size_t in_bytes = max_public ? n * input_stride : 0;
-  if ((rc = grow_bytes(&s.st_proofs, &s.st_proofs_cap, n * proof_stride)) || (rc = grow_bytes(&s.st_inputs, &s.st_inputs_cap, in_bytes ? in_bytes : 32)) ||
-      (rc = grow_bytes(&s.st_index, &s.st_index_cap, n * 4)) || (rc = grow_bytes(&s.st_status, &s.st_status_cap, n)))
+  const int oom = BN254_E_NOMEM;
+  if ((rc = s.st_proofs.ensure(n * proof_stride, oom)) || (rc = s.st_inputs.ensure(in_bytes ? in_bytes : 32, oom)) || (rc = s.st_index.ensure(n * 4, oom)) ||
+      (rc = s.st_status.ensure(n, oom)) || (rc = s.ring.ensure(KEYS_HOST_PIECE)))
     return rc;
-  if (!s.host_stream) {
-    HIPCK(hipStreamCreateWithFlags(&s.host_stream, hipStreamNonBlocking)); HIPCK(hipStreamCreateWithFlags(&s.copy_stream, hipStreamNonBlocking));
-    for (int i = 0; i < KEYS_HOST_RING; i++) { HIPCK(hipHostMalloc((void**)&s.pin[i], KEYS_HOST_PIECE, hipHostMallocDefault)); HIPCK(hipEventCreateWithFlags(&s.pin_ev[i], hipEventDisableTiming)); }
-  }
-  size_t uses = 0;
-  hipEvent_t last = nullptr;
-  auto fail = [&](int code) { const std::string keep = g_err; (void)hipStreamSynchronize(s.copy_stream); (void)hipStreamSynchronize(s.host_stream); g_err = keep; return code; };
-  auto push = [&](uint8_t* dst, const uint8_t* src, size_t len) -> int {
-    for (size_t from = 0; from < len;) {
-      const size_t k = len - from < KEYS_HOST_PIECE ? len - from : KEYS_HOST_PIECE;
-      const int slot = (int)(uses % KEYS_HOST_RING);
-      if (uses >= KEYS_HOST_RING) HIPCK(hipEventSynchronize(s.pin_ev[slot]));
-      parallel_copy(s.pin[slot], src + from, k);
-      HIPCK(hipMemcpyAsync(dst + from, s.pin[slot], k, hipMemcpyHostToDevice, s.copy_stream));
-      HIPCK(hipEventRecord(s.pin_ev[slot], s.copy_stream));
-      last = s.pin_ev[slot];
-      uses++; from += k;
-    }
-    return BN254_OK;
-  };
+  PinRing& ring = s.ring;
+  ring.begin();
+  auto push = [&](uint8_t* dst, const uint8_t* src, size_t len) { return ring.push(dst, len, [src](uint8_t* q, size_t from, size_t k) { parallel_copy(q, src + from, k); }); };
   // the staging buffers may still be read by the previous batch of this set: the copies start after it
-  if (s.busy_valid) HIPCK(hipStreamWaitEvent(s.copy_stream, s.busy_ev, 0));
+  if (s.busy_valid) HIPCK(hipStreamWaitEvent(ring.copy, s.busy_ev, 0));
   if ((rc = push(s.st_index, (const uint8_t*)key_index, n * 4)) || (rc = push(s.st_proofs, proofs, n * proof_stride)) || (in_bytes && (rc = push(s.st_inputs, public_inputs, in_bytes))))
-    return fail(rc);
-  if (last) HIPCK(hipStreamWaitEvent(s.host_stream, last, 0));
-  if ((rc = keys_enqueue(s, s.st_index, s.st_proofs, proof_stride, s.st_inputs, input_stride, n, s.st_status, s.host_stream, flags, exact_slots))) return fail(rc);
-  HIPCK(hipMemcpyAsync(status, s.st_status, n, hipMemcpyDeviceToHost, s.host_stream));
-  HIPCK(hipStreamSynchronize(s.host_stream));
+    return ring.drain(rc);
+  if (ring.last()) HIPCK(hipStreamWaitEvent(ring.compute, ring.last(), 0));
+  if ((rc = keys_enqueue(s, s.st_index, s.st_proofs, proof_stride, s.st_inputs, input_stride, n, s.st_status, ring.compute, flags, exact_slots))) return ring.drain(rc);
+  HIPCK(hipMemcpyAsync(status, s.st_status, n, hipMemcpyDeviceToHost, ring.compute));
+  HIPCK(hipStreamSynchronize(ring.compute));
   return BN254_OK;
 }
 
@@ -348,16 +289,15 @@ int bn254_dbg_g16_keys_group(const unsigned* key_index, size_t n, size_t n_keys,
   }
   int rc = check_device(device);
   if (rc) return rc;
-  uint32_t *idx = nullptr, *cnt = nullptr, *s2p = nullptr, *gk = nullptr; uint8_t* st = nullptr;
-  auto drop = [&]() { void* p[] = {idx, cnt, s2p, gk, st}; for (auto q : p) if (q) (void)hipFree(q); };
-  if ((rc = dev_alloc(&idx, n)) || (rc = dev_alloc(&cnt, 3 * n_keys + 1)) || (rc = dev_alloc(&s2p, bound)) || (rc = dev_alloc(&gk, granules + 1)) || (rc = dev_alloc(&st, n))) { drop(); return rc; }
+  DevBuf<uint32_t> idx, cnt, s2p, gk; DevBuf<uint8_t> st;
+  const int oom = BN254_E_NOMEM;
+  if ((rc = idx.ensure(n, oom)) || (rc = cnt.ensure(3 * n_keys + 1, oom)) || (rc = s2p.ensure(bound, oom)) || (rc = gk.ensure(granules + 1, oom)) || (rc = st.ensure(n, oom))) return rc;
   hipError_t e = hipMemcpy(idx, key_index, n * 4, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = bn254_launch_keys_group(idx, (uint32_t)n, (uint32_t)n_keys, (uint32_t)bound, cnt, cnt + n_keys, cnt + 2 * n_keys, cnt + 3 * n_keys, s2p, gk, st, nullptr);
   uint32_t ns = 0;
   if (e == hipSuccess) e = hipMemcpy(&ns, cnt + 3 * n_keys, 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(out_slot_to_proof, s2p, bound * 4, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(out_granule_key, gk, granules * 4, hipMemcpyDeviceToHost);
-  drop();
   if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("grouping: ") + hipGetErrorString(e));
   *out_n_slots = ns;
   return BN254_OK;

@@ -4,37 +4,17 @@
 
 #define PLONK_BIG_PIECE_DEFAULT 131072   // proofs per pass of a batch above 65 536 proofs (profiles/r05_plonk_piece_sweep.txt)
 
-static void plonk_ctx_free(PlonkCtx& c) {
-  void* ptrs[] = {c.ws, c.part, c.glv_tab, c.terms, c.flags, c.words, c.inf, c.status, c.d_in, c.d_work, c.grp_ws, c.grp_status, c.d_fail};
-  for (auto q : ptrs) if (q) (void)hipFree(q);
-  void* hp[] = {c.h_status, c.h_in, c.h_fail};
-  for (auto q : hp) if (q) (void)hipHostFree(q);
-  if (c.stream) (void)hipStreamDestroy(c.stream);
-  if (c.aux) (void)hipStreamDestroy(c.aux);
-  if (c.ev_fork) (void)hipEventDestroy(c.ev_fork);
-  if (c.ev_join) (void)hipEventDestroy(c.ev_join);
-  for (auto e : c.tk) if (e) (void)hipEventDestroy(e);
-  c = PlonkCtx();
-}
-static void plonk_dev_free(PlonkDev& d) {
-  void* ptrs[] = {d.tab0, d.tab1, d.one, d.fixed_tabs, d.d_key};
-  for (auto q : ptrs) if (q) (void)hipFree(q);
-  for (auto& c : d.ctx) plonk_ctx_free(c);
-  for (auto& b : d.sp1_bufs) (void)hipFree(b.first);
-  d.sp1_bufs.clear();
-  d.ready = false; d.tab0 = d.tab1 = d.one = d.fixed_tabs = nullptr; d.d_key = nullptr;
-}
 int plonk_ensure_dev(const bn254_plonk_pvk* pvk, int device, PlonkDev** out) {
   int rc = check_device(device);
   if (rc) return rc;
   PlonkDev& d = pvk->dev[device];
   if (!d.ready) {
-    if ((rc = upload(&d.tab0, pvk->tab0)) || (rc = upload(&d.tab1, pvk->tab1)) || (rc = upload(&d.one, pvk->one))) return rc;
-    if ((rc = build_tables_on_device(2, pvk->fixed_pts, &d.fixed_tabs))) return rc;
+    if ((rc = upload(d.tab0, pvk->tab0)) || (rc = upload(d.tab1, pvk->tab1)) || (rc = upload(d.one, pvk->one))) return rc;
+    if ((rc = build_tables_on_device(2, pvk->fixed_pts, d.fixed_tabs))) return rc;
     // the key and the field constants for the device-side stages
     if (sizeof(PlonkKey) != bn254_plonk_key_bytes()) return set_err(BN254_E_HIP, "PlonK key layout differs between the translation units");
     HIPCK(bn254_plonk_dev_init(device));
-    if (!d.d_key) HIPCK(hipMalloc(&d.d_key, sizeof(PlonkKey)));
+    if ((rc = d.d_key.ensure(sizeof(PlonkKey)))) return rc;
     HIPCK(hipMemcpy(d.d_key, &pvk->key, sizeof(PlonkKey), hipMemcpyHostToDevice));
     // known-answer check of the device stages on this GPU before the key is used there (bn254_k_plonk.hip::bn254_plonk_self_test); BN254_PLONK_SELFTEST=0 skips it
     static const bool selftest = [] { const char* e = getenv("BN254_PLONK_SELFTEST"); return !e || atoi(e) != 0; }();
@@ -114,30 +94,21 @@ void plonk_plan(size_t n, size_t piece, int max_workers, int* workers, size_t* p
 // n: proofs of the largest pass the context will run; in_bytes: the proof + input bytes of such a pass (device-side stages: staged through pinned memory).  Everything a pass
 // needs is sized HERE, before anything is enqueued: the run path itself neither allocates nor frees (a hipFree is a device-wide synchronisation while other contexts are in flight).
 int plonk_ensure_ctx(const bn254_plonk_pvk* pvk, PlonkCtx& c, size_t n, size_t in_bytes) {
-  if (!c.stream) {
-    HIPCK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking)); HIPCK(hipStreamCreateWithFlags(&c.aux, hipStreamNonBlocking));
-    HIPCK(hipEventCreateWithFlags(&c.ev_fork, hipEventDisableTiming)); HIPCK(hipEventCreateWithFlags(&c.ev_join, hipEventDisableTiming));
-    for (auto& e : c.tk) HIPCK(hipEventCreate(&e));
-  }
-  if (in_bytes > c.in_cap) {
-    if (c.d_in) HIPCK(hipFree(c.d_in));
-    if (c.h_in) HIPCK(hipHostFree(c.h_in));
-    c.d_in = nullptr; c.h_in = nullptr; c.in_cap = 0;
+  int rc;
+  if ((rc = c.stream.ensure()) || (rc = c.aux.ensure()) || (rc = c.ev_fork.ensure()) || (rc = c.ev_join.ensure())) return rc;
+  for (auto& e : c.tk) if ((rc = e.ensure_timed())) return rc;
+  if (in_bytes > c.in_cap()) {   // the staging pair: both, or neither
     const size_t cap = (in_bytes + 65535) / 65536 * 65536;
-    HIPCK(hipMalloc((void**)&c.d_in, cap));
-    HIPCK(hipHostMalloc((void**)&c.h_in, cap, hipHostMallocDefault));
-    c.in_cap = cap;
+    c.h_in.release();
+    if ((rc = c.d_in.ensure(cap)) || (rc = c.h_in.ensure(cap))) { c.d_in.release(); return rc; }
   }
   size_t need = n < PLONK_MAX_LAUNCH ? (n + 255) / 256 * 256 : (size_t)PLONK_MAX_LAUNCH;
   if (need <= c.cap) return BN254_OK;
-  // drop the old buffers and forget them BEFORE anything is allocated: if an allocation below fails the context is left empty (cap = 0, every
-  // pointer null), never with a stale pointer that a later call or plonk_ctx_free would free a second time
+  // The buffers of a pass are sized together for c.cap proofs, or not at all: the old ones go BEFORE anything is allocated, and if an allocation below fails the
+  // context is left empty (cap = 0, every buffer empty)
   auto drop = [&c] {
-    void** dp[] = {(void**)&c.ws, (void**)&c.part, (void**)&c.glv_tab, (void**)&c.terms, (void**)&c.flags, (void**)&c.words, (void**)&c.inf, (void**)&c.status, (void**)&c.d_work,
-                   (void**)&c.grp_ws, (void**)&c.grp_status, (void**)&c.d_fail};
-    for (auto q : dp) { if (*q) (void)hipFree(*q); *q = nullptr; }
-    void** hp[] = {(void**)&c.h_status, (void**)&c.h_fail};
-    for (auto q : hp) { if (*q) (void)hipHostFree(*q); *q = nullptr; }
+    c.ws.release(); c.part.release(); c.glv_tab.release(); c.terms.release(); c.flags.release(); c.words.release(); c.inf.release(); c.status.release(); c.d_work.release();
+    c.grp_ws.release(); c.grp_status.release(); c.d_fail.release(); c.h_status.release(); c.h_fail.release();
     c.cap = 0; c.glv_lanes = 0; c.part_points = 0;
   };
   drop();
@@ -146,30 +117,18 @@ int plonk_ensure_ctx(const bn254_plonk_pvk* pvk, PlonkCtx& c, size_t n, size_t i
   // window-table scratch of the variable rows: the bound over every batch size up to `need` and both launches (plonk_scratch_lanes)
   const int v1 = shape_var(pvk->shape1), v2 = shape_var(pvk->shape2_rlc);        // (the weighted form of the second launch has one variable term more)
   const size_t tab_lanes = plonk_scratch_lanes(need, v1 > v2 ? v1 : v2);
-  hipError_t e = hipSuccess;
-  auto dm = [&e](void** q, size_t bytes) { if (e == hipSuccess) e = hipMalloc(q, bytes ? bytes : 1); };
-  auto hm = [&e](void** q, size_t bytes) { if (e == hipSuccess) e = hipHostMalloc(q, bytes ? bytes : 1, hipHostMallocDefault); };
-  dm((void**)&c.ws, need * (size_t)G16_WS_BYTES_PER_PROOF);
   size_t pp = plonk_part_points(need, pvk->shape1);                              // one projective point per row and item of a launch's plan
   { const size_t b = plonk_part_points(need, pvk->shape2), c2 = plonk_part_points(need, pvk->shape2_rlc); if (b > pp) pp = b; if (c2 > pp) pp = c2; }
-  dm((void**)&c.part, pp * 27 * sizeof(int32_t));
-  c.part_points = pp;
-  dm((void**)&c.glv_tab, tab_lanes * (size_t)G1_GLV_TAB_BYTES_PER_LANE);       // 65536 lanes = 117 MB for capacities up to 8192 proofs
-  c.glv_lanes = tab_lanes;
-  dm((void**)&c.terms, need * tmax * sizeof(MsmTerm));
-  dm((void**)&c.flags, need * tmax);
-  dm((void**)&c.words, need * 16 * sizeof(uint32_t));
-  dm((void**)&c.inf, need);
-  dm((void**)&c.status, need);
-  dm((void**)&c.d_work, need * bn254_plonk_work_bytes());
   const size_t groups = (need / 64 + 255) / 256 * 256;                             // need is a multiple of 256: need / 64 groups, rounded to whole workgroups
-  dm((void**)&c.grp_ws, groups * (size_t)G16_WS_BYTES_PER_PROOF);
-  dm((void**)&c.grp_status, groups);
-  dm((void**)&c.d_fail, sizeof(uint32_t));
-  hm((void**)&c.h_status, need);
-  hm((void**)&c.h_fail, sizeof(uint32_t));
-  if (e != hipSuccess) { drop(); return set_err(BN254_E_HIP, std::string("PlonK context allocation: ") + hipGetErrorString(e)); }
-  c.cap = need;
+  if ((rc = c.ws.ensure(need * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = c.part.ensure(pp * 27)) ||
+      (rc = c.glv_tab.ensure(tab_lanes * (size_t)(G1_GLV_TAB_BYTES_PER_LANE / 4))) ||       // 65536 lanes = 117 MB for capacities up to 8192 proofs
+      (rc = c.terms.ensure(need * tmax)) || (rc = c.flags.ensure(need * tmax)) || (rc = c.words.ensure(need * 16)) || (rc = c.inf.ensure(need)) || (rc = c.status.ensure(need)) ||
+      (rc = c.d_work.ensure(need * bn254_plonk_work_bytes())) || (rc = c.grp_ws.ensure(groups * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = c.grp_status.ensure(groups)) ||
+      (rc = c.d_fail.ensure(1)) || (rc = c.h_status.ensure(need)) || (rc = c.h_fail.ensure(1))) {
+    drop();
+    return rc;
+  }
+  c.part_points = pp; c.glv_lanes = tab_lanes; c.cap = need;
   return BN254_OK;
 }
 
@@ -208,7 +167,11 @@ int bn254_plonk_vk_prepare(const uint8_t* vk, size_t vk_len, bn254_plonk_pvk** o
 }
 void bn254_plonk_vk_free(bn254_plonk_pvk* pvk) {
   if (!pvk) return;
-  for (auto& kv : pvk->dev) { if (hipSetDevice(kv.first) != hipSuccess) continue; (void)hipDeviceSynchronize(); plonk_dev_free(kv.second); }
+  for (auto it = pvk->dev.begin(); it != pvk->dev.end();) {
+    if (hipSetDevice(it->first) != hipSuccess) { ++it; continue; }   // (its state goes with the key below, without the wait)
+    (void)hipDeviceSynchronize();
+    it = pvk->dev.erase(it);      // the state's members release what they own on the device that is now current and idle
+  }
   delete pvk;
 }
 size_t bn254_plonk_vk_num_public(const bn254_plonk_pvk* pvk) { return pvk ? (size_t)pvk->key.nb_public : 0; }
@@ -223,7 +186,7 @@ static int plonk_msm(const PlonkDev* d, PlonkCtx& c, const MsmShape& shape, size
   if (!msm_plan_build(plan, shape, m_pad, msm_lane_budget(), force_a, plonk_joint_g(m_pad))) return set_err(BN254_E_BAD_ARG, "PlonK key shape needs more MSM rows than the launch supports");
   if (m > c.cap || bn254_g1_msm_scratch_lanes(plan, m) > c.glv_lanes || (size_t)plan.n_rows * m > c.part_points || (size_t)plan.n_rows > (size_t)MSM_MAX_ROWS)
     return set_err(BN254_E_HIP, "PlonK context smaller than the launch (internal sizing error)");
-  hipError_t e = bn254_launch_g1_msm_rows(plan, (const int32_t*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, d->fixed_tabs, c.stream);
+  hipError_t e = bn254_launch_g1_msm_rows(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, d->fixed_tabs, c.stream);
   if (ev_rows) HIPCK(hipEventRecord(ev_rows, c.stream));
   if (e == hipSuccess)
     e = to_words ? bn254_launch_g1_sum_rows(plan, c.part, m, c.words, c.inf, nullptr, nullptr, 0, 0, 0, 0, c.stream)
@@ -245,7 +208,7 @@ static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, Plonk
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   auto t0 = now();
   const size_t pb = m * proof_stride, ib = d_rows ? 0 : m * n_public * 32, need = pb + ib;
-  if (!resident && need > c.in_cap) return set_err(BN254_E_HIP, "PlonK context staging smaller than the pass (internal sizing error)");   // sized by plonk_ensure_ctx
+  if (!resident && need > c.in_cap()) return set_err(BN254_E_HIP, "PlonK context staging smaller than the pass (internal sizing error)");   // sized by plonk_ensure_ctx
   if (m > c.cap) return set_err(BN254_E_HIP, "PlonK context smaller than the pass (internal sizing error)");
   // The KZG batching scalar of every proof: fresh, uniform and unpredictable to the prover, as the reference draws it
   // (Fr::random(&mut OsRng), plonk/kzg.rs:149-154).  It MUST be secret until the proof is fixed: the two opening quotients are bound by
@@ -474,9 +437,9 @@ int bn254_plonk_footprint(const bn254_plonk_pvk* pvk, int device, size_t* bytes,
   const int T1 = plonk_stage1_terms(pvk->key), TT = plonk_stage2_terms(pvk->key) + 2;
   const size_t tmax = (size_t)(TT > T1 ? TT : T1);
   for (const PlonkCtx& c : d->ctx) {
-    if (!c.cap && !c.in_cap) continue;
+    if (!c.cap && !c.in_cap()) continue;
     if (contexts) (*contexts)++;
-    *bytes += c.in_cap + c.cap * (size_t)G16_WS_BYTES_PER_PROOF + c.part_points * 27 * sizeof(int32_t) + c.glv_lanes * (size_t)G1_GLV_TAB_BYTES_PER_LANE +
+    *bytes += c.in_cap() + c.cap * (size_t)G16_WS_BYTES_PER_PROOF + c.part_points * 27 * sizeof(int32_t) + c.glv_lanes * (size_t)G1_GLV_TAB_BYTES_PER_LANE +
               c.cap * tmax * (sizeof(MsmTerm) + 1) + c.cap * (16 * sizeof(uint32_t) + 2) + c.cap * bn254_plonk_work_bytes();
   }
   return BN254_OK;

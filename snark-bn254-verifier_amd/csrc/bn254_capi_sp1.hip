@@ -28,38 +28,27 @@ int check_sp1_args(bool plonk, const void* pvk, const void* proofs, size_t proof
 }
 
 namespace {
-struct Sp1DevBuf {   // device memory of one probe call
-  uint8_t* p = nullptr;
-  ~Sp1DevBuf() { if (p) (void)hipFree(p); }
-};
 // A buffer of PlonkDev::sp1_bufs held by one SP1 PlonK call: the smallest free one that is large enough, else a new one (a free buffer that is too small is
 // replaced, the only hipFree on this path).  Returned to the device's list when the call ends; every path out of a call has drained the work that used it.
 struct Sp1PlonkBuf {
-  PlonkDev* d; uint8_t* p = nullptr; size_t cap = 0;
+  PlonkDev* d; DevBuf<uint8_t> p;
   explicit Sp1PlonkBuf(PlonkDev* d_) : d(d_) {}
   int take(size_t need) {
     std::lock_guard<std::mutex> lk(d->sp1_mu);
     auto& v = d->sp1_bufs;
-    int best = -1;
-    for (int i = 0; i < (int)v.size(); i++)
-      if (v[i].second >= need && (best < 0 || v[i].second < v[best].second)) best = i;
-    if (best < 0 && !v.empty()) {   // none is large enough: the largest gives way
-      best = 0;
-      for (int i = 1; i < (int)v.size(); i++) if (v[i].second > v[best].second) best = i;
-      (void)hipFree(v[best].first);
-      v.erase(v.begin() + best);
-      best = -1;
+    int best = -1, largest = 0;
+    for (int i = 0; i < (int)v.size(); i++) {
+      if (v[i].cap() >= need && (best < 0 || v[i].cap() < v[best].cap())) best = i;
+      if (v[i].cap() > v[largest].cap()) largest = i;
     }
-    if (best >= 0) { p = v[best].first; cap = v[best].second; v.erase(v.begin() + best); return BN254_OK; }
-    const size_t bytes = (need + ((size_t)1 << 20) - 1) >> 20 << 20;
-    HIPCK(hipMalloc((void**)&p, bytes));
-    cap = bytes;
-    return BN254_OK;
+    if (best >= 0) { p = std::move(v[best]); v.erase(v.begin() + best); return BN254_OK; }
+    if (!v.empty()) v.erase(v.begin() + largest);   // none is large enough: the largest gives way
+    return p.ensure((need + ((size_t)1 << 20) - 1) >> 20 << 20);
   }
   ~Sp1PlonkBuf() {
     if (!p) return;
     std::lock_guard<std::mutex> lk(d->sp1_mu);
-    d->sp1_bufs.push_back({p, cap});
+    d->sp1_bufs.push_back(std::move(p));
   }
 };
 int sp1_plonk_dev(const bn254_plonk_pvk* pvk, int device, PlonkDev** d) {
@@ -72,8 +61,7 @@ int sp1_rows_enqueue(const Sp1Src& src, size_t n, uint8_t* rows, uint8_t* pre, h
     const size_t m = n - o < (size_t)G16_MAX_BATCH ? n - o : (size_t)G16_MAX_BATCH;
     hipError_t e = bn254_launch_sp1_public_inputs(src.vkh + o * src.vkh_stride, src.vkh_stride, src.pv, src.pv_bytes, src.pv_base, src.off + o, (uint32_t)m,
                                                   rows + o * 64, pre + o, s);
-    if (e != hipSuccess) return set_err(e == hipErrorNoBinaryForGpu || e == hipErrorInvalidDeviceFunction ? BN254_E_NO_DEVICE : BN254_E_HIP,
-                                         std::string("kernel launch (SP1 public inputs): ") + hipGetErrorString(e));
+    if (e != hipSuccess) return launch_err(e, "SP1 public inputs");
   }
   return BN254_OK;
 }
@@ -198,9 +186,9 @@ int bn254_dbg_sp1_public_inputs(const uint8_t* vkey_hashes, size_t vkey_stride, 
   int rc = check_device(device);
   if (rc) return rc;
   const size_t vk_bytes = vkey_stride ? (n - 1) * vkey_stride + 32 : 32, off_bytes = (n + 1) * 8;
-  Sp1DevBuf b;
-  HIPCK(hipMalloc((void**)&b.p, off_bytes + n * 65 + vk_bytes + (pv_bytes ? pv_bytes : 4)));
-  uint8_t *d_off = b.p, *d_rows = b.p + off_bytes, *d_pre = d_rows + n * 64, *d_vk = d_pre + n, *d_pv = d_vk + vk_bytes;
+  DevBuf<uint8_t> b;
+  if ((rc = b.ensure(off_bytes + n * 65 + vk_bytes + (pv_bytes ? pv_bytes : 4)))) return rc;
+  uint8_t *d_off = b, *d_rows = b + off_bytes, *d_pre = d_rows + n * 64, *d_vk = d_pre + n, *d_pv = d_vk + vk_bytes;
   HIPCK(hipMemcpy(d_off, pv_offsets, off_bytes, hipMemcpyHostToDevice));
   HIPCK(hipMemcpy(d_vk, vkey_hashes, vk_bytes, hipMemcpyHostToDevice));
   if (pv_bytes) HIPCK(hipMemcpy(d_pv, public_values, pv_bytes, hipMemcpyHostToDevice));

@@ -145,7 +145,7 @@ inline G16RlcWide g16_rlc_wide_alloc(size_t groups, size_t key_inputs, int msm_f
 // ---- BN254_FLAG_COMPRESSED_PROOFS: the decompression scratch of a (key, device) ------------------------------------------------------------------------------
 // A compressed batch is decompressed and verified in chunks of at most G16_MAX_BATCH proofs (the chunk of the exact and the RLC paths): per proof one raw
 // 256-byte record and one pre-status byte.  g16_cmp_alloc(n) is what a batch of n proofs needs (the pre bytes start at raw_bytes, a multiple of 256);
-// ensure_cmp grows the scratch to it and the enqueue checks every chunk against it.
+// ensure_scratch (bn254_capi_g16.hip) grows the scratch to it and the enqueue checks every chunk against it.
 inline size_t g16_cmp_chunk(size_t n) { return n < (size_t)G16_MAX_BATCH ? n : (size_t)G16_MAX_BATCH; }
 struct G16CmpAlloc { size_t proofs, raw_bytes, pre_bytes; };
 inline G16CmpAlloc g16_cmp_alloc(size_t n) {
@@ -159,7 +159,7 @@ inline G16CmpAlloc g16_cmp_alloc(size_t n) {
 // ---- SP1 public inputs (bn254_verify.h, "SP1 proofs from their public values"): the row scratch of a (key, device) ----------------------------------------------
 // An SP1 batch is hashed and verified in chunks of at most G16_MAX_BATCH proofs: per proof one 64-byte row vkey_hash | digest (the public inputs the raw
 // pipeline reads, n_public = 2) and one pre-status byte.  g16_sp1_alloc(n) is what a batch of n proofs needs (the pre bytes start at row_bytes, a multiple of
-// 256); ensure_sp1 grows the scratch to it and the enqueue checks every chunk against it.
+// 256); ensure_scratch grows the scratch to it and the enqueue checks every chunk against it.
 struct G16Sp1Alloc { size_t proofs, row_bytes, pre_bytes; };
 inline G16Sp1Alloc g16_sp1_alloc(size_t n) {
   G16Sp1Alloc a;

@@ -55,6 +55,44 @@ static void run_batch(const std::vector<bn254_g16_pvk*>& keys, size_t n, size_t 
   for (size_t i = n; i < n + 8; i++) CHECK(st[i] == 0xAB);
 }
 
+// An allocation failure at every allocation of bn254_groth16_reserve_keys and of a batch through the host and the device entry, raw and compressed records, on fresh
+// keys (so: a fresh set) each time: an error code, the list still works afterwards, and -- leak detection, the count at exit -- the set owns whatever the call left
+static void keys_alloc_failures() {
+  const size_t n = 3000, widths[3] = {0, 2, 5};
+  std::vector<uint8_t> vk(bn254_synth_groth16_vk_len(2)), raw(256 * 8), in8(64 * 8), ex(8), cp(128 * n), proofs(256 * n, 1), rows(512 * n + 1, 2), st(n + 8);
+  CHECK(bn254_synth_groth16(0x5D0000, 2, 8, 0, 1, 1, vk.data(), raw.data(), in8.data(), ex.data()) == 0);
+  for (size_t i = 0; i < n; i++) {     // gnark's compressed records of the eight proofs, repeated; every 7th does not decompress (compression flag 00 on A)
+    uint8_t* r = &cp[128 * i];
+    CHECK(bn254_g1_compress(&raw[256 * (i % 8)], r) == 0 && bn254_g2_compress(&raw[256 * (i % 8) + 64], r + 32) == 0 && bn254_g1_compress(&raw[256 * (i % 8) + 192], r + 96) == 0);
+    if (i % 7 == 3) { r[0] &= 0x3f; proofs[256 * i] = 0xEE; }
+  }
+  std::vector<unsigned> idx(n);
+  for (size_t i = 0; i < n; i++) idx[i] = (unsigned)(i * 7 % 3);
+  for (int variant = 0; variant < 5; variant++) {
+    const bool dev = variant & 1, cmp = variant & 2, reserve = variant == 4;
+    bool through = false;
+    for (size_t fail = 1; fail < 400 && !through; fail++) {
+      std::vector<bn254_g16_pvk*> list(3);
+      for (size_t k = 0; k < 3; k++) make_key(0x5E0000 + k, widths[k], &list[k]);
+      g_fake_alloc_counter = 0; g_fake_fail_alloc_after = fail;
+      memset(st.data(), 0xAB, st.size());
+      const uint8_t* p = cmp ? cp.data() : proofs.data(); const size_t stride = cmp ? 128 : 256; const unsigned flags = cmp ? BN254_FLAG_COMPRESSED_PROOFS : 0;
+      const int rc = reserve ? bn254_groth16_reserve_keys(list.data(), 3, n, 0)
+                     : dev   ? bn254_groth16_verify_batch_keys_device(list.data(), 3, idx.data(), p, stride, rows.data(), 512, n, st.data(), 0, nullptr, flags)
+                             : bn254_groth16_verify_batch_keys(list.data(), 3, idx.data(), p, stride, rows.data(), 512, n, st.data(), 0, flags);
+      g_fake_fail_alloc_after = 0;
+      if (rc == 0) {
+        through = true;
+        if (!reserve) for (size_t i = 0; i < n; i++) CHECK(st[i] == (i % 7 == 3 ? (cmp ? BN254_ERR_MALFORMED : BN254_REJECT) : BN254_ACCEPT));
+      } else CHECK(rc == BN254_E_HIP || rc == BN254_E_NOMEM);
+      CHECK(st[n] == 0xAB);
+      run_batch(list, 300, 512, 0);     // the same list (the cached set the failed call left) still works
+      for (auto k : list) bn254_groth16_vk_free(k);
+    }
+    CHECK(through);     // ended by a call that made every allocation, not by running out of iterations
+  }
+}
+
 int main(int argc, char** argv) {
   const long iters = argc > 1 ? atol(argv[1]) : 10;
   const bool threads_only = argc > 2 && std::string(argv[2]) == "threads";
@@ -84,6 +122,7 @@ int main(int argc, char** argv) {
     std::vector<uint8_t> st(4, 0xAB); unsigned bad_idx[4] = {0, 9, 0, 0}; std::vector<uint8_t> pr(1024, 1), rows(2048, 0);
     CHECK(bn254_groth16_verify_batch_keys(keys.data(), keys.size(), bad_idx, pr.data(), 256, rows.data(), 512, 4, st.data(), 0, 0) == BN254_E_BAD_ARG && st[1] == 0xAB);
     CHECK(bn254_groth16_verify_batch_keys(keys.data(), keys.size(), bad_idx, pr.data(), 256, rows.data(), 511, 4, st.data(), 0, 0) == BN254_E_BAD_ARG);
+    keys_alloc_failures();
   }
   // concurrent callers: the same list from several threads (serialised by the set's lock), different lists side by side (the cache's lock, eviction while a call
   // still holds an evicted set), and a thread that frees and re-prepares a member of its own lists meanwhile
@@ -104,6 +143,6 @@ int main(int argc, char** argv) {
     for (auto& x : th) x.join();
   }
   for (auto k : keys) bn254_groth16_vk_free(k);
-  printf("hostsan_keys: %ld stand-in launches\nhostsan_keys ok\n", g_launches.load());
+  printf("hostsan_keys: %ld stand-in launches, %zu allocations still live\nhostsan_keys ok\n", g_launches.load(), g_fake_live_allocs.load());
   return 0;
 }

@@ -3,7 +3,8 @@
 //   * malformed-bytes fuzz of bn254_groth16_vk_prepare / bn254_plonk_vk_prepare / bn254_sp1_fixture_parse / the point codecs (attacker-shaped lengths and counts:
 //     groth16/converter.rs:28-65, plonk/converter.rs:18-119), seeded from valid keys;
 //   * the batch entry points on a fake device: reservation and growth of contexts, the pinned ring and thread-pool copies of bn254_groth16_verify_batch, the RLC
-//     pass with a fallback, wide keys, PlonK's context pool with calls in flight, allocation failures on every allocation of a call.
+//     pass with a fallback, wide keys, PlonK's context pool with calls in flight, compressed proofs and the SP1 entries (the host build runs the bodies of their
+//     kernels: bn254_capi.hip, bottom), allocation failures on every allocation of a call.
 // The stand-in "kernels" only mark proofs: what is under test is everything AROUND the launches.  Prints "hostsan ok".
 #include "hip/hip_runtime.h"
 std::atomic<int> g_fake_device_count{1}, g_fake_fail_device{-1};
@@ -11,18 +12,21 @@ std::atomic<size_t> g_fake_live_allocs{0}, g_fake_fail_alloc_after{0}, g_fake_al
 thread_local int t_fake_current_device = 0;
 #include "../../snark-bn254-verifier_amd/csrc/bn254_capi.hip"
 #include <cstdio>
+#include <functional>
 #include <random>
 
 // ---- stand-ins for the launchers of bn254_kernels.hip / bn254_k_plonk.hip / bn254_k_msm.hip / bn254_coop12.hip -----------------------------------------------
 static std::atomic<long> g_launches{0};
 const char* const bn254_kernel_kind_names[KID_COUNT] = {};
-// a proof whose first byte is 0xEE is "invalid": REJECT on the exact path, and its RLC group stays pending
+// a proof whose first byte is 0xEE is "invalid": REJECT on the exact path, and its RLC group stays pending; so is a proof whose first public-input byte is 0xEE (no
+// scalar below r starts with it): the SP1 scenarios mark a proof through its vkey hash, the first half of the row the library makes for it
+static inline bool marked_invalid(const G16LaunchArgs& a, size_t i) { return a.proofs[i * a.stride] == 0xEE || (a.n_public && a.inputs[i * (size_t)a.n_public * 32] == 0xEE); }
 hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t, hipEvent_t* ev, G16Prof* prof) {
   g_launches++;
   for (size_t i = 0; i < a.n; i++) {
     (void)a.proofs[i * a.stride + 255];                                   // the last byte the loader reads: in bounds of the caller's buffer
     for (int k = 0; k < a.n_public; k++) (void)a.inputs[(i * (size_t)a.n_public + (size_t)k) * 32 + 31];
-    a.status[i] = a.proofs[i * a.stride] == 0xEE ? BN254_ST_REJECT : BN254_ST_ACCEPT;
+    a.status[i] = marked_invalid(a, i) ? BN254_ST_REJECT : BN254_ST_ACCEPT;
   }
   memset(a.ws, 0x5a, a.n * (size_t)G16_WS_BYTES_PER_PROOF);               // the launch owns its part of the workspace: ASan checks the extent
   if (a.msm_part) {
@@ -39,7 +43,7 @@ hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, 
   memset(r.grp_status, 0, ((size_t)r.plan.groups + 255) / 256 * 256);     // the region the real launch clears
   for (size_t i = 0; i < a.n; i++) a.status[i] = BN254_ST_ACCEPT;
   for (size_t i = 0; i < a.n; i++)
-    if (a.proofs[i * a.stride] == 0xEE) {                                  // every proof of its group stays pending
+    if (marked_invalid(a, i)) {                                            // every proof of its group stays pending
       const uint32_t g = rlc_group_of((uint32_t)i, r.plan);
       for (size_t j = 0; j < a.n; j++) if (rlc_group_of((uint32_t)j, r.plan) == g) a.status[j] = BN254_ST_PENDING;
     }
@@ -291,7 +295,168 @@ static void threaded_scenarios(const std::string& golden, bool big) {
   printf("hostsan: threaded scenarios ok (8 fake devices%s)\n", big ? ", 2^20 + 777 proofs over all of them" : "");
 }
 
+// ---- the allocation-failure loop: allocation number `fail` of big(h) on a fresh handle fails, for fail = 1, 2, ... until the call gets through: every failure is an
+// error code, the handle still works afterwards (small(h) succeeds), and whatever the aborted call left behind is still owned by the handle (leak detection at exit)
+static void alloc_failure_loop(const std::function<void*()>& prepare, const std::function<int(void*)>& big, const std::function<int(void*)>& small, const std::function<void(void*)>& release) {
+  bool through = false;
+  for (size_t fail = 1; fail < 400 && !through; fail++) {
+    void* h = prepare();
+    g_fake_alloc_counter = 0; g_fake_fail_alloc_after = fail;
+    const int rc = big(h);
+    g_fake_fail_alloc_after = 0;
+    if (rc == 0) through = true;
+    else CHECK(rc < 0 && small(h) == 0);
+    release(h);
+  }
+  CHECK(through);       // the loop ended because a call succeeded with every allocation it makes, not because it ran out of iterations
+}
+
+// ---- BN254_FLAG_COMPRESSED_PROOFS and the SP1 entries: the orchestration around the decompression / row launches (the stand-ins at the bottom of bn254_capi.hip run the
+// kernels' bodies on the host): scratch sizing on both sides of the 2^20 chunk, the staging of offsets, values and vkey hashes through the pinned ring, the per-call buffers
+// of the SP1 PlonK entries, and an allocation failure at every allocation of each
+static void compressed_and_sp1_scenarios(const std::string& golden) {
+  double t_lap = fake_now();
+  auto lap = [&](const char* what) { const double t = fake_now(); printf("hostsan:   %s: %.1f s\n", what, (t - t_lap) / 1000.0); t_lap = t; };
+  const size_t n_public = 2, big = ((size_t)1 << 20) + 300;
+  std::vector<uint8_t> vk(bn254_synth_groth16_vk_len(n_public)), raw(256 * 64), in64(64 * 64), ex(64);
+  CHECK(bn254_synth_groth16(0xB2540000, n_public, 64, 0, 1, 2, vk.data(), raw.data(), in64.data(), ex.data()) == 0);
+  bn254_g16_pvk* pvk = nullptr;
+  CHECK(bn254_groth16_vk_prepare(vk.data(), vk.size(), 0, &pvk) == 0);
+  bn254_set_rlc_params(64, 0, 1);
+  // 64 distinct compressed records (gnark: A 32 | B 64 | C 32 bytes), repeated; every 1000th does not decompress (compression flag 00 on A): MALFORMED
+  std::vector<uint8_t> rec(128 * 64), bad(128);
+  for (size_t i = 0; i < 64; i++)
+    CHECK(bn254_g1_compress(&raw[256 * i], &rec[128 * i]) == 0 && bn254_g2_compress(&raw[256 * i + 64], &rec[128 * i + 32]) == 0 && bn254_g1_compress(&raw[256 * i + 192], &rec[128 * i + 96]) == 0);
+  memcpy(bad.data(), rec.data(), 128); bad[0] &= 0x3f;
+  { uint8_t out[64], st = 0; CHECK(bn254_g1_decompress(bad.data(), out, 0, &st) == 0 && st == BN254_ERR_MALFORMED); CHECK(bn254_g1_decompress(rec.data(), out, 1, &st) == 0 && st == BN254_ACCEPT); }
+  for (size_t stride : {(size_t)128, (size_t)160}) {
+    const size_t n_max = stride == 128 ? big : 70000;
+    std::vector<uint8_t> cp(stride * n_max), inputs(64 * n_max), status(n_max + 8);
+    for (size_t i = 0; i < n_max; i++) { memcpy(&cp[stride * i], i % 1000 == 0 ? bad.data() : &rec[128 * (i % 64)], 128); memcpy(&inputs[64 * i], &in64[64 * (i % 64)], 64); }
+    auto check = [&](size_t m) { for (size_t i = 0; i < m; i++) CHECK(status[i] == (i % 1000 == 0 ? BN254_ERR_MALFORMED : BN254_ACCEPT)); CHECK(status[m] == 0xAB); };
+    std::vector<size_t> sizes = {1, 255, 70000};
+    if (stride == 128) { sizes.push_back((size_t)1 << 20); sizes.push_back(big); }
+    for (size_t m : sizes)
+      for (unsigned flags : {(unsigned)BN254_FLAG_COMPRESSED_PROOFS, (unsigned)(BN254_FLAG_COMPRESSED_PROOFS | BN254_FLAG_RLC)}) {
+        memset(status.data(), 0xAB, status.size());
+        CHECK(bn254_groth16_verify_batch(pvk, cp.data(), stride, inputs.data(), n_public, m, status.data(), 0, flags) == 0);
+        check(m);
+        memset(status.data(), 0xAB, status.size());
+        CHECK(bn254_groth16_verify_batch_device(pvk, cp.data(), stride, inputs.data(), n_public, m, status.data(), 0, nullptr, flags) == 0);
+        check(m);
+      }
+    if (stride != 128) continue;
+    lap("compressed batches");
+    for (int variant = 0; variant < 4; variant++) {
+      const unsigned flags = BN254_FLAG_COMPRESSED_PROOFS | (variant & 1 ? BN254_FLAG_RLC : 0);
+      alloc_failure_loop(
+          [&]() -> void* { bn254_g16_pvk* q = nullptr; CHECK(bn254_groth16_vk_prepare(vk.data(), vk.size(), 0, &q) == 0); return q; },
+          [&](void* q) { return variant & 2 ? bn254_groth16_verify_batch_device((bn254_g16_pvk*)q, cp.data(), stride, inputs.data(), n_public, 20000, status.data(), 0, nullptr, flags)
+                                            : bn254_groth16_verify_batch((bn254_g16_pvk*)q, cp.data(), stride, inputs.data(), n_public, 20000, status.data(), 0, flags); },
+          [&](void* q) { return bn254_groth16_verify_batch((bn254_g16_pvk*)q, cp.data(), stride, inputs.data(), n_public, 300, status.data(), 0, BN254_FLAG_COMPRESSED_PROOFS); },
+          [&](void* q) { bn254_groth16_vk_free((bn254_g16_pvk*)q); });
+    }
+  }
+  lap("compressed batches, failure loops");
+  // SP1: proof i comes with a vkey hash (stride 0: one for the batch) and the bytes [off[i], off[i + 1]) of the values.  A vkey hash that starts with 0xEE marks the proof
+  // for the Groth16 stand-ins (REJECT); the device entries cannot read the offsets, so there a decreasing pair is the proof's MALFORMED status
+  const size_t sn = 300000, pn = 12000, pstride = 904;
+  std::vector<uint8_t> proofs(256 * sn), pv(16 * sn + 64), status(sn + 8);
+  for (size_t i = 0; i < sn; i++) memcpy(&proofs[256 * i], &raw[256 * (i % 64)], 256);
+  for (size_t i = 0; i < pv.size(); i++) pv[i] = (uint8_t)(i * 131);
+  std::vector<uint64_t> off(sn + 1), off_bad(sn + 1);
+  for (size_t i = 0; i <= sn; i++) off[i] = 40 + (i / 3) * 48 + (i % 3 == 2 ? 48 : (i % 3) * 5);     // values of 5, 43 (more than one SHA-256 block with the padding) and 0 bytes
+  CHECK(off[sn] <= pv.size());
+  off_bad = off;
+  auto bad_range = [&](size_t i) { return i % 777 == 5; };
+  for (size_t i = 0; i < sn; i++) if (bad_range(i)) off_bad[i + 1] = off_bad[i] - 1;                 // proof i: its range ends before it starts; proof i + 1 is a longer, valid range
+  std::vector<uint8_t> pvkb = read_file(golden + "/plonk_vk.bin");
+  CHECK(pvkb.size() == 34368);
+  bn254_plonk_pvk* pk = nullptr;
+  CHECK(bn254_plonk_vk_prepare(pvkb.data(), pvkb.size(), &pk) == 0);
+  std::vector<uint8_t> pp(pstride * pn, 1);
+  for (size_t vstride : {(size_t)0, (size_t)32, (size_t)48}) {
+    std::vector<uint8_t> vkh(vstride ? vstride * sn : 32, 0x11);
+    for (size_t i = 0; vstride && i < sn; i += 1000) vkh[vstride * i] = 0xEE;
+    auto marked = [&](size_t i) { return vstride && i % 1000 == 0; };
+    for (size_t m : {(size_t)1, (size_t)4097, sn}) {       // the largest: two compute chunks of the host entry, several pieces of the ring each
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_groth16_verify_batch(pvk, proofs.data(), 256, vkh.data(), vstride, pv.data(), off.data(), m, status.data(), 0, 0) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == (marked(i) ? BN254_REJECT : BN254_ACCEPT));
+      CHECK(status[m] == 0xAB);
+    }
+    for (unsigned flags : {0u, (unsigned)BN254_FLAG_RLC}) {
+      const size_t m = 70000;
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_groth16_verify_batch_device(pvk, proofs.data(), 256, vkh.data(), vstride, pv.data(), pv.size(), off_bad.data(), m, status.data(), 0, nullptr, flags) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == (bad_range(i) ? BN254_ERR_MALFORMED : marked(i) ? BN254_REJECT : BN254_ACCEPT));
+      CHECK(status[m] == 0xAB);
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_groth16_verify_batch(pvk, proofs.data(), 256, vkh.data(), vstride, pv.data(), off.data(), m, status.data(), 0, flags) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == (marked(i) ? BN254_REJECT : BN254_ACCEPT));
+    }
+    // the all-ones vkey hash of stride 0 marks every proof
+    if (!vstride) {
+      std::vector<uint8_t> ee(32, 0xEE);
+      CHECK(bn254_sp1_groth16_verify_batch(pvk, proofs.data(), 256, ee.data(), 0, pv.data(), off.data(), 4097, status.data(), 0, 0) == 0);
+      for (size_t i = 0; i < 4097; i++) CHECK(status[i] == BN254_REJECT);
+    }
+    // PlonK: the stand-in stages accept every proof; a call's rows, pre-status bytes and staged values live in a buffer it takes from the device's list
+    for (size_t m : {(size_t)1, (size_t)3000, pn}) {
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_plonk_verify_batch(pk, pp.data(), pstride, vkh.data(), vstride, pv.data(), off.data(), m, status.data(), 0, m == pn ? BN254_FLAG_RLC : 0) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == BN254_ACCEPT);
+      CHECK(status[m] == 0xAB);
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_plonk_verify_batch_device(pk, pp.data(), pstride, vkh.data(), vstride, pv.data(), pv.size(), off_bad.data(), m, status.data(), 0, nullptr, 0) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == (bad_range(i) ? BN254_ERR_MALFORMED : BN254_ACCEPT));
+      CHECK(status[m] == 0xAB);
+    }
+  }
+  lap("SP1 batches");
+  // SP1 rows under compressed proofs: both scratch buffers of the key in one call
+  {
+    const size_t m = 70000;
+    std::vector<uint8_t> cp(128 * m), vkh(32 * m, 0x11);
+    for (size_t i = 0; i < m; i++) memcpy(&cp[128 * i], i % 1000 == 0 ? bad.data() : &rec[128 * (i % 64)], 128);
+    for (size_t i = 500; i < m; i += 1000) vkh[32 * i] = 0xEE;
+    for (unsigned flags : {(unsigned)BN254_FLAG_COMPRESSED_PROOFS, (unsigned)(BN254_FLAG_COMPRESSED_PROOFS | BN254_FLAG_RLC)}) {
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_groth16_verify_batch(pvk, cp.data(), 128, vkh.data(), 32, pv.data(), off.data(), m, status.data(), 0, flags) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == (i % 1000 == 0 ? BN254_ERR_MALFORMED : i % 1000 == 500 ? BN254_REJECT : BN254_ACCEPT));
+      memset(status.data(), 0xAB, status.size());
+      CHECK(bn254_sp1_groth16_verify_batch_device(pvk, cp.data(), 128, vkh.data(), 32, pv.data(), pv.size(), off.data(), m, status.data(), 0, nullptr, flags) == 0);
+      for (size_t i = 0; i < m; i++) CHECK(status[i] == (i % 1000 == 0 ? BN254_ERR_MALFORMED : i % 1000 == 500 ? BN254_REJECT : BN254_ACCEPT));
+      CHECK(status[m] == 0xAB);
+    }
+  }
+  lap("SP1 rows of compressed proofs");
+  // an allocation failure at every allocation of an SP1 call: host and device entries, vkey strides 48 and 0, both protocols
+  std::vector<uint8_t> vkh48(48 * 20000, 0x11), vkh0(32, 0x11);
+  for (int variant = 0; variant < 4; variant++) {
+    const bool dev = variant & 1; const size_t vs = variant & 2 ? 0 : 48; const uint8_t* vh = vs ? vkh48.data() : vkh0.data();
+    const unsigned flags = variant == 3 ? BN254_FLAG_RLC : 0;
+    alloc_failure_loop(
+        [&]() -> void* { bn254_g16_pvk* q = nullptr; CHECK(bn254_groth16_vk_prepare(vk.data(), vk.size(), 0, &q) == 0); return q; },
+        [&](void* q) { return dev ? bn254_sp1_groth16_verify_batch_device((bn254_g16_pvk*)q, proofs.data(), 256, vh, vs, pv.data(), pv.size(), off.data(), 20000, status.data(), 0, nullptr, flags)
+                                  : bn254_sp1_groth16_verify_batch((bn254_g16_pvk*)q, proofs.data(), 256, vh, vs, pv.data(), off.data(), 20000, status.data(), 0, flags); },
+        [&](void* q) { return bn254_sp1_groth16_verify_batch((bn254_g16_pvk*)q, proofs.data(), 256, vh, vs, pv.data(), off.data(), 300, status.data(), 0, 0); },
+        [&](void* q) { bn254_groth16_vk_free((bn254_g16_pvk*)q); });
+    alloc_failure_loop(
+        [&]() -> void* { bn254_plonk_pvk* q = nullptr; CHECK(bn254_plonk_vk_prepare(pvkb.data(), pvkb.size(), &q) == 0); return q; },
+        [&](void* q) { return dev ? bn254_sp1_plonk_verify_batch_device((bn254_plonk_pvk*)q, pp.data(), pstride, vh, vs, pv.data(), pv.size(), off.data(), 3000, status.data(), 0, nullptr, 0)
+                                  : bn254_sp1_plonk_verify_batch((bn254_plonk_pvk*)q, pp.data(), pstride, vh, vs, pv.data(), off.data(), 3000, status.data(), 0, 0); },
+        [&](void* q) { return bn254_sp1_plonk_verify_batch((bn254_plonk_pvk*)q, pp.data(), pstride, vh, vs, pv.data(), off.data(), 100, status.data(), 0, 0); },
+        [&](void* q) { bn254_plonk_vk_free((bn254_plonk_pvk*)q); });
+  }
+  lap("SP1 failure loops");
+  bn254_plonk_vk_free(pk);
+  bn254_groth16_vk_free(pvk);
+  printf("hostsan: compressed and SP1 scenarios ok\n");
+}
+
 int main(int argc, char** argv) {
+  setvbuf(stdout, nullptr, _IOLBF, 0);        // progress lines appear as the phases finish, also when the output is a file
   const std::string golden = argc > 1 ? argv[1] : "tests/golden";
   const long fuzz_iters = argc > 2 ? atol(argv[2]) : 300;
   if (argc > 3 && std::string(argv[3]) == "threads") {        // the -fsanitize=thread build runs these alone (the rest is single-threaded code the ASan build covers)
@@ -337,16 +502,18 @@ int main(int argc, char** argv) {
   for (size_t i = 0; i < n; i++) CHECK(status[i] == (proofs[256 * i] == 0xEE ? BN254_REJECT : BN254_ACCEPT));
   CHECK(bn254_groth16_verify_batch_multi(pvk, proofs.data(), 256, inputs.data(), n_public, 5000, status.data(), 1, 0) == 0);
   // allocation failure on every allocation of a fresh context: an error code, no leak, no crash; the key still works afterwards
-  for (size_t fail = 1; fail < 40; fail++) {
+  bool through = false;
+  for (size_t fail = 1; fail < 400 && !through; fail++) {
     bn254_g16_pvk* q = nullptr;
     CHECK(bn254_groth16_vk_prepare(vk.data(), vk.size(), 0, &q) == 0);
     g_fake_alloc_counter = 0; g_fake_fail_alloc_after = fail;
     int rc = bn254_groth16_verify_batch(q, proofs.data(), 256, inputs.data(), n_public, 70000, status.data(), 0, fail % 2 ? BN254_FLAG_RLC : 0);
     g_fake_fail_alloc_after = 0;
-    if (rc == 0) { bn254_groth16_vk_free(q); break; }
+    if (rc == 0) { bn254_groth16_vk_free(q); through = true; continue; }
     CHECK(bn254_groth16_verify_batch(q, proofs.data(), 256, inputs.data(), n_public, 300, status.data(), 0, 0) == 0);
     bn254_groth16_vk_free(q);
   }
+  CHECK(through);
   bn254_groth16_vk_free(pvk);
   // a key with many inputs: comb tables, partial-sum and digit buffers of the wide MSM
   {
@@ -362,6 +529,7 @@ int main(int argc, char** argv) {
     bn254_groth16_vk_free(q);
   }
   CHECK(bn254_groth16_verify(proofs.data(), 256, vk.data(), vk.size(), inputs.data(), n_public, 0, status.data()) == 0);
+  compressed_and_sp1_scenarios(golden);
   // ---------------------------------------------------------------- PlonK: the reference's key (tests/golden), mutated; batches through the context pool
   std::vector<uint8_t> pvkb = read_file(golden + "/plonk_vk.bin");
   CHECK(pvkb.size() == 34368);
@@ -380,15 +548,17 @@ int main(int argc, char** argv) {
     CHECK(ps[pn] == 0xAB);
     CHECK(bn254_plonk_verify_batch_flags(pk, pp.data(), pstride, pi.data(), 2, 100, ps.data(), 0, BN254_FLAG_RLC) == 0);          // below the threshold: the flag is ignored
     CHECK(bn254_plonk_verify_batch_flags(pk, pp.data(), pstride, pi.data(), 2, 100, ps.data(), 0, 0x80u) != 0);                   // an unknown flag is refused
-    for (size_t fail = 1; fail < 60; fail++) {
+    bool plonk_through = false;
+    for (size_t fail = 1; fail < 400 && !plonk_through; fail++) {
       bn254_plonk_pvk* q = nullptr;
       CHECK(bn254_plonk_vk_prepare(pvkb.data(), pvkb.size(), &q) == 0);
       g_fake_alloc_counter = 0; g_fake_fail_alloc_after = fail;
       int rc = bn254_plonk_verify_batch(q, pp.data(), pstride, pi.data(), 2, 3000, ps.data(), 0);
       g_fake_fail_alloc_after = 0;
       bn254_plonk_vk_free(q);
-      if (rc == 0) break;
+      if (rc == 0) plonk_through = true;
     }
+    CHECK(plonk_through);
     bn254_plonk_vk_free(pk);
     const std::vector<size_t> counts = {0, 72, 368, 372 + 32 + 160 + 33788};   // size, nb_public, n_qcp, n_cci
     long ok = 0;

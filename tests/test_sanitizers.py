@@ -5,7 +5,8 @@ sanitizers on the CPU builds only, the GPU pool has none:
   * the HOST HALF OF THE PRODUCT -- csrc/bn254_capi*.hip with its parsers, key preparation, plans, pinned ring, context pools and thread pool -- compiled with g++
     against a host-memory stand-in for the HIP runtime (tests/hostsan) and driven through the C ABI: malformed-bytes fuzz of the three parsers that take
     attacker-shaped lengths (groth16/converter.rs:28-65, plonk/converter.rs:18-119, the SP1 fixture reader), batches around every plan boundary on the fake
-    device, the RLC fallback, wide keys, PlonK calls in flight, an allocation failure at every allocation of a call.
+    device, the RLC fallback, wide keys, PlonK calls in flight, compressed proofs on both sides of the 2^20 chunk, the SP1 entries of both protocols with every vkey
+    stride, an allocation failure at every allocation of a call of each kind.
 A report aborts (-fno-sanitize-recover).  First run: one real finding, a left shift of a negative int in the inner loop of the constant-time inversion
 (bn254_fp.h, bn254_plonk.hpp: undefined before C++20), fixed."""
 import os

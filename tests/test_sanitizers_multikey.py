@@ -20,7 +20,8 @@ def _build(exe, flags):
 
 def test_key_sets_under_asan_ubsan():
     """batches around the granule and the sub-batch cut, lists that name a handle twice, more lists than cache slots, a member freed and a new list prepared, refused
-    calls, then the concurrent scenarios; leak detection on: whatever a dropped or evicted set held must have been released"""
+    calls, an allocation failure at every allocation of a reservation and of a batch (host and device entry, raw and compressed records), then the concurrent
+    scenarios; leak detection on: whatever a dropped or evicted set held must have been released"""
     exe = os.path.join(D, "hostsan_keys")
     _build(exe, ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
     r = subprocess.run([exe, "12"], cwd=ROOT, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"), capture_output=True, text=True, timeout=1500)
