@@ -189,10 +189,18 @@ struct Coop12Ops {
   const Coop12& co;
   __device__ __forceinline__ void f12_inv(int d, int a) { c12_inv(co, C12_SLOT(d), C12_SLOT(a)); }
   __device__ __forceinline__ void f12_conj(int d, int a) { c12_conj(co, C12_SLOT(d), C12_SLOT(a)); }
-  __device__ __forceinline__ void f12_mul(int d, int a, int b, bool conj_b = false) { c12_mul(co, C12_SLOT(d), C12_SLOT(a), C12_SLOT(b), conj_b); }
+  // a flagged VE_CONJ (bn254_vm.h): conj(a) b = conj(a conj(b)) and conj(a) conj(b) = conj(a b), so the conjugation of a moves to the result
+  __device__ __forceinline__ void f12_mul(int d, int a, int b, bool conj_b = false) {
+    c12_mul(co, C12_SLOT(d), C12_SLOT(ve_elem(a)), C12_SLOT(b), conj_b != ve_conj(a));
+    if (ve_conj(a)) c12_conj(co, C12_SLOT(d), C12_SLOT(d));
+  }
   __device__ __forceinline__ void f12_frob(int d, int a, int j) { c12_frob(co, C12_SLOT(d), C12_SLOT(a), j); }
-  __device__ __forceinline__ void f12_cyclo_sqr(int d, int a) { c12_cyclo_sqr_n(co, C12_SLOT(d), C12_SLOT(a), 1); }
-  __device__ __forceinline__ void f12_cyclo_sqr_n(int d, int a, int count) { c12_cyclo_sqr_n(co, C12_SLOT(d), C12_SLOT(a), count); }
+  // conj(a)^(2^count) = conj(a^(2^count))
+  __device__ __forceinline__ void f12_cyclo_sqr(int d, int a) { f12_cyclo_sqr_n(d, a, 1); }
+  __device__ __forceinline__ void f12_cyclo_sqr_n(int d, int a, int count) {
+    c12_cyclo_sqr_n(co, C12_SLOT(d), C12_SLOT(ve_elem(a)), count);
+    if (ve_conj(a)) c12_conj(co, C12_SLOT(d), C12_SLOT(d));
+  }
 };
 
 // ---- workspace access -----------------------------------------------------------------------------------------------------------------------------------------

@@ -126,5 +126,13 @@ __device__ __forceinline__ bool words_lt_p(const uint32_t w[8]) { return !words_
   if (__builtin_amdgcn_ballot_w64((st & BN254_ST_PENDING) != 0) == 0) return;                   \
   DevWs w(ws, n, i < n ? i : DEAD_LANE)
 
+// ---- what the r-torsion test of B (bn254_vm.h::vm_g2_ate_check) makes of a pending proof's status byte: the deferred statuses resolve in the reference's order ----
+// (k_g16_subgroup, and the tail of the run kernels when they end the Miller loop)
+__device__ __forceinline__ uint8_t g16_subgroup_status(uint8_t st, bool in_g2, int inputs_match_key) {
+  if (!in_g2) return BN254_ST_NOT_IN_SUBGROUP;
+  if (st & 0x3f) return st & 0x3f;                          // deferred error of C
+  if (!inputs_match_key) return BN254_ST_INPUT_LEN;         // PrepareInputsFailed comes after every loader error
+  return BN254_ST_PENDING | (st & BN254_ST_LINF);
+}
 
 }  // namespace bn254

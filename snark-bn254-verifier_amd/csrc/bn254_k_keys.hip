@@ -1,12 +1,13 @@
 // bn254_k_keys.hip -- the kernels of a Groth16 batch over many verifying keys (bn254_keys.h; bn254_groth16_verify_batch_keys): the proofs are brought into slots so
 // that every wavefront works for one key, and the four places where a key enters the single-key pipeline read it from the wavefront's descriptor instead of the
-// launch arguments.  Everything in between (k_vm_init, the final exponentiation program) never sees a key and runs unchanged on the slots.
+// launch arguments.  Everything in between (the final exponentiation program up to its last product) never sees a key and runs unchanged on the slots.
 //   k_keys_count / k_keys_scan / k_keys_place   per-key histogram of key_index, exclusive scan of the counts rounded up to a granule, slot -> proof and granule -> key
 //   k_g16_prepare_keys      k_g16_prepare through the slot index: record and input row of the slot's proof, L from the key's byte-window tables
 //   k_g16_check_scalars_keys  BN254_FLAG_STRICT_SCALARS with the key's input count
-//   k_g16_subgroup_keys     k_g16_subgroup with the key's inputs_match
-//   k_g16_compare_keys      comparison with the key's e(alpha, beta) and the scatter of every slot's status byte back to proof order
-// (k_miller_run_keys is in bn254_k_miller.hip, beside the kernel it is an instance of.)
+//   k_f12_mul_verdict_keys  the last product of the final exponentiation, the comparison with the key's e(alpha, beta) and the scatter of every slot's status byte
+//                           back to proof order
+// (k_miller_run_keys is in bn254_k_miller.hip, beside the kernel it is an instance of: its first launch sets f and T, its last one tests B's subgroup with the key's
+// inputs_match.)
 #include <hip/hip_runtime.h>
 #include "bn254_devws.h"
 #include "bn254_keys.h"
@@ -124,7 +125,7 @@ k_g16_prepare_keys(const uint8_t* __restrict__ proofs, size_t stride, const uint
   DevWs w(ws, m, live ? i : DEAD_LANE);
   const uint32_t* my = wl + lane * PREPK_LDS_ROW;
   uint32_t d[8], wx[8], wy[8];
-  int err = 0;       // first error in the reference's order: A, then B (member, curve), B subgroup (k_g16_subgroup_keys), then C
+  int err = 0;       // first error in the reference's order: A, then B (member, curve), B subgroup (the tail of k_miller_run_keys), then C
   int err_c = 0;
 
   // ---- A
@@ -228,33 +229,12 @@ k_g16_check_scalars_keys(const uint8_t* __restrict__ inputs, size_t input_stride
   if (bad) slot_status[i] = BN254_ST_NOT_MEMBER;
 }
 
-// the prologue of the VM kernels (VM_KERNEL_PROLOGUE) for kernels that read a descriptor: a wavefront past the launch's slots leaves before it reads anything
-#define VM_KEYS_PROLOGUE()                                                                       \
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;                                           \
-  if ((i & ~63u) >= n) return;                                                                   \
-  const uint8_t st = status[i < n ? i : n - 1];                                                 \
-  if (__builtin_amdgcn_ballot_w64((st & BN254_ST_PENDING) != 0) == 0) return;                   \
-  DevWs w(ws, n, i < n ? i : DEAD_LANE)
-
+// the last product of the final exponentiation, compared with e(alpha, beta) of the wavefront's key as it is stored (bn254_vm.h::vm_f12_mul_eq_const); then every slot
+// that holds a proof hands its status byte -- the verdict, or what an earlier kernel decided -- to the proof, also in a wavefront none of whose proofs is pending
 __global__ void __launch_bounds__(256, 2)
-k_g16_subgroup_keys(uint32_t n, int32_t* ws, uint8_t* __restrict__ status, const uint32_t* __restrict__ granule_key, const G16KeyDesc* __restrict__ desc, uint32_t n_keys, int e_t) {
-  VM_KEYS_PROLOGUE();
-  const int inputs_match_key = keys_view(desc, granule_key, i & ~63u, n_keys).inputs_match;
-  bool ok = vm_g2_ate_check(w, e_t, VE_B);
-  if (i < n && (st & BN254_ST_PENDING)) {
-    uint8_t out;
-    if (!ok) out = BN254_ST_NOT_IN_SUBGROUP;
-    else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
-    else if (!inputs_match_key) out = BN254_ST_INPUT_LEN;     // PrepareInputsFailed comes after every loader error
-    else out = BN254_ST_PENDING | (st & BN254_ST_LINF);
-    status[i] = out;
-  }
-}
-
-// == e(alpha, beta) of the wavefront's key, and every slot that holds a proof hands its status byte -- the verdict, or what an earlier kernel decided -- to the proof
-__global__ void __launch_bounds__(256, 2)
-k_g16_compare_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ slot_to_proof, const uint32_t* __restrict__ granule_key,
-                   const G16KeyDesc* __restrict__ desc, uint32_t n_keys, uint32_t n_proofs, uint8_t* __restrict__ out_status) {
+k_f12_mul_verdict_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, const uint32_t* __restrict__ slot_to_proof, const uint32_t* __restrict__ granule_key,
+                       const G16KeyDesc* __restrict__ desc, uint32_t n_keys, uint32_t n_proofs, uint8_t* __restrict__ out_status, int e_dst, int e_a, int e_b) {
+  __shared__ int32_t park_lds[72 * 256];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if ((i & ~63u) >= n) return;
   const uint8_t st = status[i < n ? i : n - 1];
@@ -262,8 +242,9 @@ k_g16_compare_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, 
   uint8_t out = st;
   if (__builtin_amdgcn_ballot_w64((st & BN254_ST_PENDING) != 0) != 0) {
     DevWs w(ws, n, i < n ? i : DEAD_LANE);
+    w.lds = park_lds;
     const int32_t* target = keys_view(desc, granule_key, i & ~63u, n_keys).target;
-    const bool acc = vm_f12_eq_const(w, VE_S0, target);
+    const bool acc = vm_f12_mul_eq_const(w, e_dst, e_a, e_b, target);
     if (st & BN254_ST_PENDING) out = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
   }
   if (i < n && st != 0) { const uint32_t pi = slot_to_proof[i]; if (pi < n_proofs) out_status[pi] = out; }
@@ -291,10 +272,7 @@ void bn254_launch_g16_prepare_keys(const G16KeysLaunchArgs& a, unsigned grid, hi
     hipLaunchKernelGGL(k_g16_check_scalars_keys, dim3(grid), dim3(256), 0, s, a.inputs, a.input_stride, a.n_proofs, (uint32_t)a.m, a.slot_to_proof, a.granule_key, a.desc, a.n_keys,
                        a.slot_status);
 }
-void bn254_launch_g16_subgroup_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s, int e_t) {
-  hipLaunchKernelGGL(k_g16_subgroup_keys, dim3(grid), dim3(256), 0, s, (uint32_t)a.m, a.ws, a.slot_status, a.granule_key, a.desc, a.n_keys, e_t);
-}
-void bn254_launch_g16_compare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s) {
-  hipLaunchKernelGGL(k_g16_compare_keys, dim3(grid), dim3(256), 0, s, a.ws, (uint32_t)a.m, (const uint8_t*)a.slot_status, a.slot_to_proof, a.granule_key, a.desc, a.n_keys, a.n_proofs,
-                     a.status);
+void bn254_launch_f12_mul_verdict_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s, int e_dst, int e_a, int e_b) {
+  hipLaunchKernelGGL(k_f12_mul_verdict_keys, dim3(grid), dim3(256), 0, s, a.ws, (uint32_t)a.m, (const uint8_t*)a.slot_status, a.slot_to_proof, a.granule_key, a.desc, a.n_keys,
+                     a.n_proofs, a.status, e_dst, e_a, e_b);
 }

@@ -91,10 +91,12 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
 // bn254_k_miller.hip: one whole step of the shared Miller loop (kind 0: doubling, with the squaring of f when do_sqr; 1..4: additions)
 void bn254_launch_miller_step(bool do_sqr, int kind, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb, int e, int epa,
                               const int32_t* t0, int ep0, int inf0, const int32_t* t1, int ep1, int inf1);
-// a run of steps [s_begin, s_end) in one launch (bn254_vm.h::vm_miller_run; tab0 / tab1: the WHOLE line tables); kinds: the step table, a nibble per step
+// a run of steps [s_begin, s_end) in one launch (bn254_vm.h::vm_miller_run; tab0 / tab1: the WHOLE line tables); kinds: the step table, a nibble per step.
+// fold: MR_FOLD_INIT | MR_FOLD_ATE (bn254_vm.h) -- the run from step 0 sets f = 1, T = (B, 1) itself, the run that ends the loop does k_g16_subgroup's work (and
+// WRITES status, with inputs_match_key); 0: neither
 struct MillerKinds { uint8_t nib[44]; };
-void bn254_launch_miller_run(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
-                             int e, int epa, const int32_t* tab0, int ep0, int inf0, const int32_t* tab1, int ep1, int inf1);
+void bn254_launch_miller_run(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
+                             int e, int epa, const int32_t* tab0, int ep0, int inf0, const int32_t* tab1, int ep1, int inf1, int fold, int inputs_match_key);
 // the same for two table-driven pairs and no variable pair (bn254_vm.h::vm_miller_run_fixed2)
 void bn254_launch_miller_run_fixed2(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int e,
                                     const int32_t* tab0, int ep0, int inf0, const int32_t* tab1, int ep1, int inf1);
@@ -120,11 +122,12 @@ struct G16KeysLaunchArgs {
 hipError_t bn254_launch_keys_group(const uint32_t* key_index, uint32_t n, uint32_t n_keys, uint32_t slot_cap, uint32_t* count, uint32_t* base, uint32_t* cursor,
                                    uint32_t* n_slots, uint32_t* slot_to_proof, uint32_t* granule_key, uint8_t* status, hipStream_t s);
 void bn254_launch_g16_prepare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s);
-void bn254_launch_g16_subgroup_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s, int e_t);
-void bn254_launch_g16_compare_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s);
-void bn254_launch_miller_run_keys(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
-                                  int e, int epa, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1);
-// the lane pipeline of bn254_launch_g16 on the slots of one launch part: prepare, k_vm_init, the Miller loop in runs, subgroup, final exponentiation, compare + scatter
+void bn254_launch_miller_run_keys(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, uint8_t* status, unsigned grid, hipStream_t s, int et, int eb,
+                                  int e, int epa, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1, int fold);
+// the last product of the final exponentiation, dst <- a * b, then the verdict against the key's target and the scatter of the slots' status bytes to proof order
+void bn254_launch_f12_mul_verdict_keys(const G16KeysLaunchArgs& a, unsigned grid, hipStream_t s, int e_dst, int e_a, int e_b);
+// the lane pipeline of bn254_launch_g16 on the slots of one launch part: prepare, the Miller loop in runs (the first sets f and T, the last tests B's subgroup), final
+// exponentiation, whose last product compares and scatters
 hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s);
 // fixed-base tables of a key built on the device (bn254_k_comb.hip).  form 0: comb tables (points * 8192 entries), 1: byte-window tables (points * 32 * 255 entries), both of
 // MSM_ENTRY_DWORDS dwords; pts = `points` affine points (18 dwords each, device memory); scratch: teeth_plane = 27 * points * teeth dwords, teeth_aff = 18 * points * teeth

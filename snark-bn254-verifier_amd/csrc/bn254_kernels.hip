@@ -3,13 +3,16 @@
 // Pipeline per batch (DESIGN.md "Kernels"):
 //   k_g16_prepare     parse 256 proof bytes (coalesced through LDS), range / on-curve checks of A, B, C, Montgomery
 //                     conversion, L = K0 + sum x_i K_i by fixed-base 8-bit windows      (groth16/converter.rs:14-26, verify.rs:53-63)
-//   k_vm_init, k_miller_step_dbl, k_miller_step_add
-//                     the shared Miller loop f = Miller(A,B) * lines_G(L) * lines_D(C), one launch per STEP (squaring, G2 step,
-//                     three line products; bn254_vm.h::vm_miller_step); G/D line tables shared by the batch  (verify.rs:73-77)
-//   k_g16_subgroup    r-torsion test of B from the loop's final G2 point, status precedence   (converter.rs:152)
-//   k_f12_inv, k_f12_conj, k_f12_frob, k_f12_mul, k_f12_cyclo_sqr(_n), k_f12_copy
-//                     f^((p^12-1)/r), bn254_vm.h::vm_final_exp_program                          (verify.rs:77)
-//   k_g16_compare     == e(alpha, beta) -> status byte                                          (verify.rs:77)
+//   k_miller_run (bn254_k_miller.hip)
+//                     the shared Miller loop f = Miller(A,B) * lines_G(L) * lines_D(C) in runs of steps, by default ONE launch
+//                     (bn254_vm.h::vm_miller_run); G/D line tables shared by the batch.  The first launch sets f = 1, T = (B, 1);
+//                     the last one ends with the r-torsion test of B on the loop's final G2 point and the status precedence
+//                                                                                               (verify.rs:73-77, converter.rs:152)
+//   k_f12_inv, k_f12_frob, k_f12_mul, k_f12_cyclo_sqr(_n)
+//                     f^((p^12-1)/r), bn254_vm.h::vm_final_exp_program: conjugations ride on their consumers' loads (verify.rs:77)
+//   k_f12_mul_verdict the program's last product, compared == e(alpha, beta) as it is stored -> status byte   (verify.rs:77)
+// The latency mode and the one-launch-per-step form (k_miller_step_dbl / _add, k_miller_*_var) keep k_vm_init, k_g16_subgroup and
+// k_g16_compare as launches of their own; so does the RLC mode.
 //
 // Workspace (bn254_vm.h element map): element e, digit l, proof i at dword (e * 9 + l) * n + i, accessed through ONE buffer
 // descriptor: the row offset (e, l) is wave-uniform and travels in an SGPR (soffset), the lane offset i * 4 is one VGPR shared
@@ -71,6 +74,14 @@ __global__ void __launch_bounds__(256, 2) k_f12_mul(int32_t* ws, uint32_t n, con
   VM_KERNEL_PROLOGUE();
   w.lds = park_lds;
   vm_f12_mul(w, d, a, b, conj_b != 0);
+}
+// the last product of the final exponentiation with k_g16_compare's work as its tail (bn254_vm.h::vm_f12_mul_eq_const): the other 59 products of a batch stay k_f12_mul
+__global__ void __launch_bounds__(256, 2) k_f12_mul_verdict(int32_t* ws, uint32_t n, uint8_t* status, int d, int a, int b, const int32_t* __restrict__ target, int reject_code) {
+  __shared__ int32_t park_lds[72 * 256];
+  VM_KERNEL_PROLOGUE();
+  w.lds = park_lds;
+  const bool acc = vm_f12_mul_eq_const(w, d, a, b, target);
+  if (i < n && (st & BN254_ST_PENDING)) status[i] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
 }
 __global__ void __launch_bounds__(256, 2) k_f12_copy(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a) { VM_KERNEL_PROLOGUE(); vm_f12_copy(w, d, a); }
 __global__ void __launch_bounds__(256, 2) k_f12_cyclo_sqr(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a) { VM_KERNEL_PROLOGUE(); vm_f12_cyclo_sqr(w, d, a); }
@@ -415,14 +426,7 @@ k_g16_subgroup(uint32_t n, int32_t* ws, uint8_t* __restrict__ status, int inputs
   // runs AFTER the Miller loop: the r-torsion test of B reads the loop's final G2 point (bn254_vm.h::vm_g2_ate_check)
   VM_KERNEL_PROLOGUE();
   bool ok = vm_g2_ate_check(w, e_t, VE_B);
-  if (i < n && (st & BN254_ST_PENDING)) {
-    uint8_t out;
-    if (!ok) out = BN254_ST_NOT_IN_SUBGROUP;
-    else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
-    else if (!inputs_match_key) out = BN254_ST_INPUT_LEN;     // PrepareInputsFailed comes after every loader error
-    else out = BN254_ST_PENDING | (st & BN254_ST_LINF);
-    status[i] = out;
-  }
+  if (i < n && (st & BN254_ST_PENDING)) status[i] = g16_subgroup_status(st, ok, inputs_match_key);
 }
 __global__ void __launch_bounds__(256, 2) k_dbg_g2_ate(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, uint8_t* o) {
   VM_KERNEL_PROLOGUE();
@@ -835,6 +839,7 @@ struct LaunchOps {
   G16Prof* prof;
   int inf_mask[3] = {BN254_ST_LINF, 0, 0};   // status bits marking the G1 point of fixed pair 0 / 1 / 2 as the identity
   const G16KeyDesc* key_desc = nullptr; uint32_t n_keys = 0; const uint32_t* granule_key = nullptr;   // a batch over many keys: miller_run reads the tables per wavefront
+  int run_fold = 0, inputs_match_key = 0;    // miller_run: MR_FOLD_INIT | MR_FOLD_ATE (the first run sets f and T, the last one tests B's subgroup and writes status)
   int uni(int x) { return x; }
   void f12_sqr(int e) { BN_LAUNCH(KID_F12_SQR, k_f12_sqr, ws, n, status, e); }
   void miller_dbl_var(int et, int e, int ep) { BN_LAUNCH(KID_MILLER_DBL_VAR, k_miller_dbl_var, ws, n, status, et, e, ep); }
@@ -846,8 +851,8 @@ struct LaunchOps {
   void miller_run(int s_begin, int s_end, int et, int eb, int e, int epa, int ep0, int ep1) {
     static const MillerKinds kinds = [] { MillerKinds k; memset(&k, 0, sizeof k); for (int st_ = 0; st_ < BN_ATE_STEPS; st_++) k.nib[st_ >> 1] |= (uint8_t)(miller_step_kind(st_) << ((st_ & 1) * 4)); return k; }();
     ProfScope ps_(prof, KID_MILLER_RUN, s);
-    if (key_desc) { bn254_launch_miller_run_keys(kinds, s_begin, s_end, ws, n, status, grid, s, et, eb, e, epa, key_desc, n_keys, granule_key, ep0, inf_mask[0], ep1, inf_mask[1]); return; }
-    bn254_launch_miller_run(kinds, s_begin, s_end, ws, n, status, grid, s, et, eb, e, epa, tab[0], ep0, inf_mask[0], tab[1], ep1, inf_mask[1]);
+    if (key_desc) { bn254_launch_miller_run_keys(kinds, s_begin, s_end, ws, n, (uint8_t*)status, grid, s, et, eb, e, epa, key_desc, n_keys, granule_key, ep0, inf_mask[0], ep1, inf_mask[1], run_fold); return; }
+    bn254_launch_miller_run(kinds, s_begin, s_end, ws, n, (uint8_t*)status, grid, s, et, eb, e, epa, tab[0], ep0, inf_mask[0], tab[1], ep1, inf_mask[1], run_fold, inputs_match_key);
   }
   void miller_run_fixed2(int s_begin, int s_end, int e, int ep0, int ep1) {
     static const MillerKinds kinds = [] { MillerKinds k; memset(&k, 0, sizeof k); for (int st_ = 0; st_ < BN_ATE_STEPS; st_++) k.nib[st_ >> 1] |= (uint8_t)(miller_step_kind(st_) << ((st_ & 1) * 4)); return k; }();
@@ -927,7 +932,13 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
     return hipGetLastError();
   }
   LaunchOps ops{a.ws, n, a.status, grid, s, {a.gtab, a.dtab, nullptr}, prof};
-  BN_LAUNCH(KID_VM_INIT, k_vm_init, a.ws, n, (const uint8_t*)a.status);
+  // The throughput form (the Miller loop as k_miller_run launches) has no k_vm_init, k_g16_subgroup or k_g16_compare: the run that starts at step 0 sets f = 1 and
+  // T = (B, 1), the run that ends the loop tests B's subgroup on the point it has just produced and resolves the deferred statuses, and the last product of the final
+  // exponentiation compares with e(alpha, beta) -- whichever launches of the plan (88, 44, 22 or 11 steps each) those are.  The latency mode and the one-launch-per-step
+  // kernels (BN254_MILLER_RUN_STEPS=0) keep the three kernels.
+  const bool folded = form.form == G16_FORM_LANES && form.run_steps > 0;
+  if (folded) { ops.run_fold = MR_FOLD_INIT | MR_FOLD_ATE; ops.inputs_match_key = a.inputs_match_key; }
+  else BN_LAUNCH(KID_VM_INIT, k_vm_init, a.ws, n, (const uint8_t*)a.status);
   if (form.form == G16_FORM_LATENCY) {
     // latency mode: Miller(A, B) on the launch stream, the two table-driven pairs as their own chains (accumulators in the free
     // slots VE_S1 / VE_S2) on two more streams; f = f_A f_B f_C afterwards.  Three times the squarings, 40 % less time at 4096.
@@ -959,10 +970,15 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
   }
   if (ev) (void)hipEventRecord(ev[2], s);
   // r-torsion test of B from the loop's final point; resolves the deferred statuses (C errors, input count)
-  BN_LAUNCH(KID_SUBGROUP, k_g16_subgroup, n, a.ws, a.status, a.inputs_match_key, (int)VE_T);
+  if (!folded) BN_LAUNCH(KID_SUBGROUP, k_g16_subgroup, n, a.ws, a.status, a.inputs_match_key, (int)VE_T);
   if (ev) (void)hipEventRecord(ev[3], s);
-  vm_final_exp_program(ops);
-  BN_LAUNCH(KID_COMPARE, k_g16_compare, a.ws, n, a.status, a.target, BN254_ST_REJECT);
+  if (folded) {
+    vm_final_exp_program_head(ops);
+    BN_LAUNCH(KID_F12_MUL, k_f12_mul_verdict, a.ws, n, a.status, (int)VE_S0, (int)VE_S2, (int)VE_S0, a.target, BN254_ST_REJECT);
+  } else {
+    vm_final_exp_program(ops);
+    BN_LAUNCH(KID_COMPARE, k_g16_compare, a.ws, n, a.status, a.target, BN254_ST_REJECT);
+  }
   if (ev) (void)hipEventRecord(ev[4], s);
   return hipGetLastError();
 }
@@ -976,12 +992,12 @@ hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s) {
   bn254_launch_g16_prepare_keys(a, grid, s);
   LaunchOps ops{a.ws, n, a.slot_status, grid, s, {nullptr, nullptr, nullptr}, prof};
   ops.key_desc = a.desc; ops.n_keys = a.n_keys; ops.granule_key = a.granule_key;
-  BN_LAUNCH(KID_VM_INIT, k_vm_init, a.ws, n, (const uint8_t*)a.slot_status);
+  // as in bn254_launch_g16: the first run sets f and T, the last one tests B's subgroup (inputs_match from the wavefront's key), the last product compares and scatters
+  ops.run_fold = MR_FOLD_INIT | MR_FOLD_ATE;
   // steps per k_miller_run_keys launch: what the single-key lane form takes at this size (g16_launch_form)
   vm_miller_program_runs(ops, g16_launch_form(a.m, 0, true, false, a.part_of_larger != 0, false, false, run_steps_env).run_steps);
-  bn254_launch_g16_subgroup_keys(a, grid, s, (int)VE_T);
-  vm_final_exp_program(ops);
-  bn254_launch_g16_compare_keys(a, grid, s);
+  vm_final_exp_program_head(ops);
+  bn254_launch_f12_mul_verdict_keys(a, grid, s, (int)VE_S0, (int)VE_S2, (int)VE_S0);
   return hipGetLastError();
 }
 

@@ -24,8 +24,14 @@ enum {
   VE_P3 = 82,                   // x^3 of the windowed exp-by-u
   VE_TMPA = 94, VE_TMPB = 100,  // two Fp6 temporaries of the general Fp12 product
   VE_P5 = 106, VE_P7 = 118,     // x^5, x^7
-  VE_COUNT = 130
+  VE_COUNT = 130,
+  // Flag on a SOURCE element index of vm_f12_mul (operand a), vm_f12_cyclo_sqr and vm_f12_cyclo_sqr_n: the operation reads conj(x) = x^(p^6), i.e. negates
+  // the odd coefficients k1, k3, k5 as it loads them, so a conjugation that feeds a product or a squaring is no pass over the workspace of its own.  It
+  // travels in the index so that every dispatcher (OPS) hands it through unchanged; ve_conj / ve_elem take it apart.
+  VE_CONJ = 0x100
 };
+BN_HD bool ve_conj(int e) { return (e & VE_CONJ) != 0; }
+BN_HD int ve_elem(int e) { return e & ~VE_CONJ; }
 
 template <class W> BN_HD Fp2 vld2(W& w, int e) { Fp2 r; r.c0 = w.ld(e); r.c1 = w.ld(e + 1); return r; }
 template <class W> BN_HD void vst2(W& w, int e, const Fp2& a) { w.st(e, a.c0); w.st(e + 1, a.c1); }
@@ -295,41 +301,45 @@ template <class W> BN_HD void mf_line_var(W& w, const G2Line& l, int e_pa, Fp2& 
   f5 = fp2_dotp(pp(d0, k5), pp(d3, k4), pp(d4, k2));
   f4 = n4;
 }
-template <class W> BN_HD void mf_line_fixed(W& w, const FixedLine& l0, int e_p0, bool inf0, Fp2& f4, Fp2& f5) {   // plain dot products
-  Fp px = w.ld(e_p0), d0 = w.ld(e_p0 + 1);
-  Fp2 d3 = fp2_mul_fp(l0.m, px);
+// key-side line of a run, f in flight on both sides: Karatsuba dot products (fp2_dotk), as in vm_f12_mul_line_fixed.  Both key-side lines of a step
+// take this form: next to the two in-flight coefficients the operand sums cost the run kernels no registers they do not already spill
+// (DESIGN.md section 9), and each line saves 971 multiply-adds per step against the plain dot products (fp2_dot_line).
+template <class W> BN_HD void mf_line_fixed(W& w, const FixedLine& l, int e_p, bool inf, Fp2& f4, Fp2& f5) {
+  Fp px = w.ld(e_p), d0 = w.ld(e_p + 1);
+  Fp2 d3 = fp2_mul_fp(l.m, px);
   Fp2 x3 = fp2_mul_xi(d3);
-  const Fp2 &d4 = l0.c, &x4 = l0.xc;
-  Fp2 k0 = w.unpark(0), k1 = w.unpark(1), k2 = w.unpark(2), k3 = w.unpark(3), k4 = f4, k5 = f5;
-  w.park(0, fp2_select(inf0, k0, fp2_dot_line(d0, k0, x3, k5, x4, k3)));
-  w.park(1, fp2_select(inf0, k1, fp2_dot_line(d0, k1, d3, k0, x4, k4)));
-  w.park(2, fp2_select(inf0, k2, fp2_dot_line(d0, k2, d3, k1, x4, k5)));
-  w.park(3, fp2_select(inf0, k3, fp2_dot_line(d0, k3, d3, k2, d4, k0)));
-  f4 = fp2_select(inf0, k4, fp2_dot_line(d0, k4, d3, k3, d4, k1));
-  f5 = fp2_select(inf0, k5, fp2_dot_line(d0, k5, d3, k4, d4, k2));
-}
-template <class W> BN_HD void mf_line_fixed_k(W& w, const FixedLine& l1, int e_p1, bool inf1, Fp2& f4, Fp2& f5) {   // Karatsuba dot products
-  Fp px = w.ld(e_p1), d0 = w.ld(e_p1 + 1);
-  Fp2 d3 = fp2_mul_fp(l1.m, px);
-  Fp2 x3 = fp2_mul_xi(d3);
-  const Fp2 &d4 = l1.c, &x4 = l1.xc;
+  const Fp2 &d4 = l.c, &x4 = l.xc;
   Fp2 k0 = w.unpark(0), k1 = w.unpark(1), k2 = w.unpark(2), k3 = w.unpark(3);
   const Fp2 k4 = f4, k5 = f5;
-  w.park(0, fp2_select(inf1, k0, fp2_dotk(kfp(k0, d0), kp(x3, k5), kp(x4, k3))));
-  w.park(1, fp2_select(inf1, k1, fp2_dotk(kfp(k1, d0), kp(d3, k0), kp(x4, k4))));
-  w.park(2, fp2_select(inf1, k2, fp2_dotk(kfp(k2, d0), kp(d3, k1), kp(x4, k5))));
-  w.park(3, fp2_select(inf1, k3, fp2_dotk(kfp(k3, d0), kp(d3, k2), kp(d4, k0))));
-  f4 = fp2_select(inf1, k4, fp2_dotk(kfp(k4, d0), kp(d3, k3), kp(d4, k1)));
-  f5 = fp2_select(inf1, k5, fp2_dotk(kfp(k5, d0), kp(d3, k4), kp(d4, k2)));
+  w.park(0, fp2_select(inf, k0, fp2_dotk(kfp(k0, d0), kp(x3, k5), kp(x4, k3))));
+  w.park(1, fp2_select(inf, k1, fp2_dotk(kfp(k1, d0), kp(d3, k0), kp(x4, k4))));
+  w.park(2, fp2_select(inf, k2, fp2_dotk(kfp(k2, d0), kp(d3, k1), kp(x4, k5))));
+  w.park(3, fp2_select(inf, k3, fp2_dotk(kfp(k3, d0), kp(d3, k2), kp(d4, k0))));
+  f4 = fp2_select(inf, k4, fp2_dotk(kfp(k4, d0), kp(d3, k3), kp(d4, k1)));
+  f5 = fp2_select(inf, k5, fp2_dotk(kfp(k5, d0), kp(d3, k4), kp(d4, k2)));
 }
+// f = 1 in flight and T = (B, 1) in the workspace: the state a run that starts at step 0 would otherwise load (what the init operation of the step
+// kernels stores; f itself first reaches the workspace at the end of the run)
+template <class W> BN_HD void mf_init(W& w, int e_t, int e_b, Fp2& f4, Fp2& f5) {
+  w.park(0, fp2_one()); w.park(1, fp2_zero()); w.park(2, fp2_zero()); w.park(3, fp2_zero());
+  f4 = fp2_zero(); f5 = fp2_zero();
+  vst2(w, e_t, vld2(w, e_b)); vst2(w, e_t + 2, vld2(w, e_b + 2)); vst2(w, e_t + 4, fp2_one());
+}
+// fold: what a run does beyond its steps.  MR_FOLD_INIT: a run that starts at step 0 sets f = 1, T = (B, 1) itself instead of loading them.
+// MR_FOLD_ATE: a run that ends with the loop returns the r-torsion test of B on the point it has just produced (vm_g2_ate_check below); every other
+// run returns true.
+enum { MR_FOLD_INIT = 1, MR_FOLD_ATE = 2 };
+template <class W> BN_HD bool vm_g2_ate_check(W& w, int e_t, int e_b);
 template <class W, class LINES, class KINDS>
-BN_HD void vm_miller_run(W& w, const LINES& lines, const KINDS& kinds, int s_begin, int s_end, int e_t, int e_b, int e, int e_pa, int e_p0, bool inf0, int e_p1, bool inf1) {
+BN_HD bool vm_miller_run(W& w, const LINES& lines, const KINDS& kinds, int s_begin, int s_end, int e_t, int e_b, int e, int e_pa, int e_p0, bool inf0, int e_p1, bool inf1,
+                         int fold = 0) {
   // steps [s_begin, s_end) of the loop; kinds.get(s): 0 doubling (with the squaring of f except in step 0), 1..4 addition of +B, -B, psi(B), -psi^2(B).
   // The doubling and the addition side of the (wave-uniform) branch each carry their own G2 formulas AND their own variable-line product, so that
   // the only state that crosses the join is f in flight; the two key-side line products are shared.  (Joining right after the G2 step instead --
   // the line and the new point as merged values -- costs 165 spilled registers.)
   Fp2 f4, f5;
-  mf_load(w, e, f4, f5);
+  if ((fold & MR_FOLD_INIT) && s_begin == 0) mf_init(w, e_t, e_b, f4, f5);
+  else mf_load(w, e, f4, f5);
   for (int s = s_begin; s < s_end; s++) {
     const int kind = kinds.get(s);
     if (kind == 0) {
@@ -343,9 +353,11 @@ BN_HD void vm_miller_run(W& w, const LINES& lines, const KINDS& kinds, int s_beg
     }
     BN_SCHED_FENCE();
     mf_line_fixed(w, lines.get(0, s), e_p0, inf0, f4, f5);
-    mf_line_fixed_k(w, lines.get(1, s), e_p1, inf1, f4, f5);
+    mf_line_fixed(w, lines.get(1, s), e_p1, inf1, f4, f5);
   }
   mf_store(w, e, f4, f5);
+  if ((fold & MR_FOLD_ATE) && s_end == BN_ATE_STEPS) return vm_g2_ate_check(w, e_t, e_b);
+  return true;
 }
 
 // The same run for TWO table-driven pairs and no variable pair (PlonK's KZG check e(P0, g2[0]) e(P1, g2[1]), plonk/kzg.rs:175-187): f <- [f^2] l0(P0) l1(P1)
@@ -358,7 +370,7 @@ BN_HD void vm_miller_run_fixed2(W& w, const LINES& lines, const KINDS& kinds, in
     if (kinds.get(s) == 0 && s != 0) mf_sqr(w, f4, f5);
     BN_SCHED_FENCE();
     mf_line_fixed(w, lines.get(0, s), e_p0, inf0, f4, f5);
-    mf_line_fixed_k(w, lines.get(1, s), e_p1, inf1, f4, f5);
+    mf_line_fixed(w, lines.get(1, s), e_p1, inf1, f4, f5);
   }
   mf_store(w, e, f4, f5);
 }
@@ -386,9 +398,25 @@ BN_HD bool vm_g2_ate_check(W& w, int e_t, int e_b) {
 // tower halves in k-order storage: c0 = (k0, k2, k4), c1 = (k1, k3, k5)
 template <class W> BN_HD Fp6 vld_half(W& w, int e, int h) { Fp6 r; r.c0 = vld2(w, e + 2 * h); r.c1 = vld2(w, e + 4 + 2 * h); r.c2 = vld2(w, e + 8 + 2 * h); return r; }
 template <class W> BN_HD void vst_half(W& w, int e, int h, const Fp6& a) { vst2(w, e + 2 * h, a.c0); vst2(w, e + 4 + 2 * h, a.c1); vst2(w, e + 8 + 2 * h, a.c2); }
-// conj_b: multiply by conj(b) = b^(p^6) (the inverse of b on the cyclotomic subgroup): the odd half of b is negated on load
-template <class W>
-BN_HD void vm_f12_mul(W& w, int e_dst, int e_a, int e_b, bool conj_b = false) {
+// conj_b: multiply by conj(b) = b^(p^6) (the inverse of b on the cyclotomic subgroup): the odd half of b is negated on load; e_a | VE_CONJ does the same
+// to a.  CMP: the product is also compared with `target` (12 Fp in k-order, uniform memory) as its halves are stored, and the verdict returned.
+BN_HD Fp vm_const_fp(const int32_t* target, int k) {
+  Fp t;
+#pragma unroll
+  for (int l = 0; l < BN_NL; l++) t.v[l] = target[k * BN_NL + l];
+  BN_SETB(t, 1.0, 0.5);
+  return t;
+}
+BN_HD bool vm_half_eq_const(const Fp6& c, int h, const int32_t* target) {   // half h of an Fp12 in k-order: coefficients k_h, k_(2+h), k_(4+h)
+  bool ok = fp_eq(c.c0.c0, vm_const_fp(target, 2 * h)) & fp_eq(c.c0.c1, vm_const_fp(target, 2 * h + 1));
+  ok &= fp_eq(c.c1.c0, vm_const_fp(target, 4 + 2 * h)) & fp_eq(c.c1.c1, vm_const_fp(target, 5 + 2 * h));
+  ok &= fp_eq(c.c2.c0, vm_const_fp(target, 8 + 2 * h)) & fp_eq(c.c2.c1, vm_const_fp(target, 9 + 2 * h));
+  return ok;
+}
+template <bool CMP, class W>
+BN_HD bool vm_f12_mul_impl(W& w, int e_dst, int e_a_flagged, int e_b, bool conj_b, const int32_t* target) {
+  const bool conj_a = ve_conj(e_a_flagged);
+  const int e_a = ve_elem(e_a_flagged);
   // Round 5 (tools/kbench MUL_T3F: 632 against 695 us per 2^20 products): v0 = a0 b0 waits in the parking slots (LDS); v1 = a1 b1 stays in registers just long enough to
   // form c0 = v0 + (xi v1.c2, v1.c0, v1.c1) -- held back in registers -- and t = v0 + v1, which takes v0's place in the parking slots; a0 and b0 are then read a SECOND
   // time straight into the operand sums a0 + a1, b0 + b1 (a1 and b1 are still in registers), and only after that is the first half of dst written, so dst may alias a or
@@ -397,6 +425,7 @@ BN_HD void vm_f12_mul(W& w, int e_dst, int e_a, int e_b, bool conj_b = false) {
   { Fp6 v0 = fp6_mul(vld_half(w, e_a, 0), vld_half(w, e_b, 0)); w.park(0, v0.c0); w.park(1, v0.c1); w.park(2, v0.c2); }
   BN_SCHED_FENCE();
   Fp6 a1 = vld_half(w, e_a, 1), b1 = vld_half(w, e_b, 1);
+  if (conj_a) a1 = fp6_neg(a1);
   if (conj_b) b1 = fp6_neg(b1);
   Fp6 c0;
   {
@@ -410,27 +439,40 @@ BN_HD void vm_f12_mul(W& w, int e_dst, int e_a, int e_b, bool conj_b = false) {
   a1 = fp6_add(vld_half(w, e_a, 0), a1);
   b1 = fp6_add(vld_half(w, e_b, 0), b1);
   vst_half(w, e_dst, 0, c0);
+  bool eq = true;
+  if constexpr (CMP) eq = vm_half_eq_const(c0, 0, target);
   BN_SCHED_FENCE();
   const Fp6 s = fp6_mul(a1, b1);
   BN_SCHED_FENCE();
   Fp6 c1;
   c1.c0 = fp2_sub(s.c0, w.unpark(0)); c1.c1 = fp2_sub(s.c1, w.unpark(1)); c1.c2 = fp2_sub(s.c2, w.unpark(2));
   vst_half(w, e_dst, 1, c1);
+  if constexpr (CMP) eq &= vm_half_eq_const(c1, 1, target);
+  return eq;
 }
+template <class W>
+BN_HD void vm_f12_mul(W& w, int e_dst, int e_a, int e_b, bool conj_b = false) { vm_f12_mul_impl<false>(w, e_dst, e_a, e_b, conj_b, nullptr); }
+// the last product of the final exponentiation: the result goes to the workspace as ever, and the comparison with the key's target rides on it
+template <class W>
+BN_HD bool vm_f12_mul_eq_const(W& w, int e_dst, int e_a, int e_b, const int32_t* target) { return vm_f12_mul_impl<true>(w, e_dst, e_a, e_b, false, target); }
 // ---- Granger-Scott squaring dst <- src^2 on the cyclotomic subgroup (dst may alias src) ---------------------------------------------
 template <class W>
-BN_HD void vm_f12_cyclo_sqr(W& w, int e_dst, int e_src) {
+BN_HD void vm_f12_cyclo_sqr(W& w, int e_dst, int e_src_flagged) {
+  const bool cj = ve_conj(e_src_flagged);   // square conj(src): k1, k3, k5 negated on load
+  const int e_src = ve_elem(e_src_flagged);
   // tower names -> k index: c0.c0 = k0, c1.c1 = k3, c1.c0 = k1, c0.c2 = k4, c0.c1 = k2, c1.c2 = k5.
   // The first pair only touches (k0, k3); the other two pairs read and write (k1, k2, k4, k5), so those four are loaded before
   // either result is stored (dst may alias src).  Splitting the work this way keeps the live set near 150 registers.
   {
     Fp2 k0 = vld2(w, e_src), k3 = vld2(w, e_src + 6);
+    if (cj) k3 = fp2_neg(k3);
     Fp2 za, zb;
     gs_pair(za, zb, k0, k3, k0, k3, false);
     vst2(w, e_dst, za); vst2(w, e_dst + 6, zb);
   }
   {
     Fp2 k1 = vld2(w, e_src + 2), k2 = vld2(w, e_src + 4), k4 = vld2(w, e_src + 8), k5 = vld2(w, e_src + 10);
+    if (cj) { k1 = fp2_neg(k1); k5 = fp2_neg(k5); }
     Fp2 z2, z5, z4, z1;
     gs_pair(z2, z5, k1, k4, k2, k5, false);   // z.c0.c1 (k2), z.c1.c2 (k5)
     gs_pair(z4, z1, k2, k5, k4, k1, true);    // z.c0.c2 (k4), z.c1.c0 (k1)
@@ -440,8 +482,11 @@ BN_HD void vm_f12_cyclo_sqr(W& w, int e_dst, int e_src) {
 // ---- dst <- src^(2^count): a run of Granger-Scott squarings with all six coefficients resident in registers -------------------------
 // (one load and one store of the element per run instead of per squaring; exp-by-u has runs of 4 to 7 squarings between products)
 template <class W>
-BN_HD void vm_f12_cyclo_sqr_n(W& w, int e_dst, int e_src, int count) {
+BN_HD void vm_f12_cyclo_sqr_n(W& w, int e_dst, int e_src_flagged, int count) {
+  const bool cj = ve_conj(e_src_flagged);
+  const int e_src = ve_elem(e_src_flagged);
   Fp2 k0 = vld2(w, e_src), k1 = vld2(w, e_src + 2), k2 = vld2(w, e_src + 4), k3 = vld2(w, e_src + 6), k4 = vld2(w, e_src + 8), k5 = vld2(w, e_src + 10);
+  if (cj) { k1 = fp2_neg(k1); k3 = fp2_neg(k3); k5 = fp2_neg(k5); }
   for (int it = 0; it < count; it++) {
     Fp2 n0, n3, n2, n5, n4, n1;
     gs_pair(n0, n3, k0, k3, k0, k3, false);
@@ -558,33 +603,39 @@ BN_HD void vm_exp_u(OPS& ops, int e_dst, int e_src) {
   }
   // BN_U_W4 ends in a non-zero digit (u is odd): no trailing run
 }
-// final exponentiation of VE_F; the result ends in VE_S0 (same exponent as bn254_pairing.h::final_exponentiation)
+// final exponentiation of VE_F; the result ends in VE_S0 (same exponent as bn254_pairing.h::final_exponentiation).  No conjugation is an operation of
+// its own: each rides on the load of the product or squaring that consumes it (VE_CONJ on operand a, conj_b on operand b), at both loads where a
+// conjugated value has two consumers.  The operands every product and squaring sees are digit for digit those of the program with explicit conjugations.
+// vm_final_exp_program_head is the program without its last product dst <- VE_S2 * VE_S0, for a caller that fuses something into that product
+// (the lane kernels: the comparison with the key's target, vm_f12_mul_eq_const).
 template <class OPS>
-BN_HD void vm_final_exp_program(OPS& ops) {
+BN_HD void vm_final_exp_program_head(OPS& ops) {
   // easy part: m = f^((p^6-1)(p^2+1)) -> VE_F
   ops.f12_inv(VE_S0, VE_F);
-  ops.f12_conj(VE_S1, VE_F);
-  ops.f12_mul(VE_S0, VE_S1, VE_S0, false);
+  ops.f12_mul(VE_S0, VE_F | VE_CONJ, VE_S0, false);
   ops.f12_frob(VE_S1, VE_S0, 2);
   ops.f12_mul(VE_F, VE_S1, VE_S0);
   // hard part
-  vm_exp_u(ops, VE_S0, VE_F); ops.f12_conj(VE_S0, VE_S0);      // t0 = m^-u
-  ops.f12_cyclo_sqr(VE_S0, VE_S0);                                     // -2u
+  vm_exp_u(ops, VE_S0, VE_F);                                          // S0 = m^u; t0 = conj(S0) = m^-u
+  ops.f12_cyclo_sqr(VE_S0, VE_S0 | VE_CONJ);                           // -2u
   ops.f12_cyclo_sqr(VE_S1, VE_S0);                                     // -4u
   ops.f12_mul(VE_S1, VE_S0, VE_S1);                                    // t1 = -6u
-  vm_exp_u(ops, VE_S2, VE_S1); ops.f12_conj(VE_S2, VE_S2);     // t2 = 6u^2
-  ops.f12_conj(VE_S3, VE_S1);                                          // t3 = 6u
-  ops.f12_mul(VE_S1, VE_S2, VE_S3);                                    // t1 = 6u^2 + 6u
-  ops.f12_cyclo_sqr(VE_S3, VE_S2);                                     // t3 = 12u^2
-  vm_exp_u(ops, VE_S4, VE_S3);                                  // t4 = 12u^3
+  vm_exp_u(ops, VE_S2, VE_S1);                                         // S2 = -6u^2; t2 = conj(S2) = 6u^2, conjugated at each of its three loads
+  ops.f12_mul(VE_S1, VE_S2 | VE_CONJ, VE_S1, true);                    // t1 = t2 * conj(t1) = 6u^2 + 6u
+  ops.f12_cyclo_sqr(VE_S3, VE_S2 | VE_CONJ);                           // t3 = 12u^2
+  vm_exp_u(ops, VE_S4, VE_S3);                                         // t4 = 12u^3
   ops.f12_mul(VE_S4, VE_S1, VE_S4);                                    // t4 = 12u^3 + 6u^2 + 6u
   ops.f12_mul(VE_S3, VE_S0, VE_S4);                                    // t3 = 12u^3 + 6u^2 + 4u
-  ops.f12_mul(VE_S0, VE_S2, VE_S4);                                    // t0 = 12u^3 + 12u^2 + 6u
+  ops.f12_mul(VE_S0, VE_S2 | VE_CONJ, VE_S4);                          // t0 = 12u^3 + 12u^2 + 6u
   ops.f12_mul(VE_S0, VE_F, VE_S0);                                     // + 1
   ops.f12_frob(VE_S2, VE_S3, 1); ops.f12_mul(VE_S0, VE_S2, VE_S0);
   ops.f12_frob(VE_S2, VE_S4, 2); ops.f12_mul(VE_S0, VE_S2, VE_S0);
-  ops.f12_conj(VE_S2, VE_F); ops.f12_mul(VE_S2, VE_S2, VE_S3);        // 12u^3 + 6u^2 + 4u - 1
+  ops.f12_mul(VE_S2, VE_F | VE_CONJ, VE_S3);                           // 12u^3 + 6u^2 + 4u - 1
   ops.f12_frob(VE_S2, VE_S2, 3);
+}
+template <class OPS>
+BN_HD void vm_final_exp_program(OPS& ops) {
+  vm_final_exp_program_head(ops);
   ops.f12_mul(VE_S0, VE_S2, VE_S0);
 }
 

@@ -181,10 +181,11 @@ def model_components(name, ins):
         # ONE copy of each piece: the two line products of a step form the loop body (address range head .. latch), the squaring of f sits outside that range and
         # is entered from the latch when the next step is a doubling step (64 of the 88 steps).  Until round 4 this model read the layout the other way round
         # ("loop body = squaring + two lines, the code behind = a peeled copy of the two lines") and priced the kernel at 908 632 multiply-adds per proof; the two
-        # pieces are the straight-line kernels k_f12_sqr (7425) and k_f12_mul_line_fixed2 (11 413), whose static counts need no model, and a pass executes
-        # 64 x 7425 + 88 x 11 413 = 1 479 544 of them (profiles/r05_plonk262144_onepass_kernel_stats.csv: 15.2 ms per 262 144 proofs = 0.77 of the peak, as k_miller_run).
+        # pieces are the straight-line kernels k_f12_sqr (7425) and, twice, k_f12_mul_line_fixed (5221: both lines of a run take the Karatsuba form; until the
+        # first one did, the pair was k_f12_mul_line_fixed2's 11 413), whose static counts need no model, and a pass executes 64 x 7425 + 88 x 10 442 = 1 394 096 of
+        # them (the plain form: 1 479 544, profiles/r05_plonk262144_onepass_kernel_stats.csv: 15.2 ms per 262 144 proofs = 0.77 of the peak, as k_miller_run).
         lines, sqr = c, len(mads) - c
-        assert 7000 <= sqr <= 8000 and 10500 <= lines <= 12500, ("k_miller_run_fixed2: layout changed", c, sqr, lines)
+        assert 7000 <= sqr <= 8000 and 9500 <= lines <= 11000, ("k_miller_run_fixed2: layout changed", c, sqr, lines)
         total = 64 * sqr + 88 * lines
         return {"static_mads": len(mads), "components": {"sqr": sqr, "two_lines": lines}, "mads_per_proof_launch": float(total), "mads_per_proof_batch": float(total), "per_pass": True,
                 "unmodelled": [], "model": "Miller loop of two table-driven pairs in one launch: squaring of f (%d multiply-adds) x64 + two line products (%d) x88" % (sqr, lines)}
@@ -333,7 +334,9 @@ def final_exp_ops():
     first a run of squarings and a product) and the fixed part."""
     d = u_w4_digits()
     nz = sum(1 for x in d[1:] if x != 0)
-    return {"inv": 1, "conj": 5, "frob": 4, "mul": 12 + 3 * (3 + nz), "cyclo_calls": 3 + 3 * (1 + nz), "cyclo_squarings": 3 + 3 * (1 + (len(d) - 1))}
+    # conjugations: none as an operation of the lane kernels (VE_CONJ rides on the consumer's load); the cooperative kernels conjugate the RESULT of each of the six
+    # consumers (Coop12Ops, bn254_coop12.hip)
+    return {"inv": 1, "conj": 6, "frob": 4, "mul": 12 + 3 * (3 + nz), "cyclo_calls": 3 + 3 * (1 + nz), "cyclo_squarings": 3 + 3 * (1 + (len(d) - 1))}
 
 
 def wcount(ins, ranges, rx):
@@ -527,13 +530,22 @@ def main():
         a, b = sorted(inst["k_miller_step_dbl"], key=lambda e: -e["static_mads"])
         add = kernels["k_miller_step_add"]
         total = 64 * a["mads_per_proof_launch"] + b["mads_per_proof_launch"] + 23 * add["mads_per_proof_launch"]
+        # ... except that the run takes BOTH key-side lines in the Karatsuba form (bn254_vm.h::mf_line_fixed), the step kernels only the second: per step the difference
+        # between a plain and a Karatsuba line, both known from straight-line kernels (k_f12_mul_line_fixed2 = one of each, k_f12_mul_line_fixed = the Karatsuba one);
+        # and the launch that ends the loop runs the r-torsion test of B as its tail (the multiply-adds of k_g16_subgroup, which the throughput form no longer launches)
+        line_delta = kernels["k_f12_mul_line_fixed2"]["static_mads"] - 2 * kernels["k_f12_mul_line_fixed"]["static_mads"]
+        tail = kernels["k_g16_subgroup"]["static_mads"]
+        assert 900 <= line_delta <= 1050 and tail < 2000, ("plain / Karatsuba line or subgroup test: counts changed", line_delta, tail)
+        steps_total = total
+        total = steps_total - 88 * line_delta + tail
         run["mads_per_proof_launch"] = total
         run["mads_per_proof_batch"] = total
         run["per_pass"] = True      # the 88 steps run in 1, 2, 4 or 8 launches depending on the sub-batch size: the count is per pass over a sub-batch
         run["unmodelled"] = []
         run["model"] = ("whole Miller loop in one launch = 64 doubling steps with the squaring of f (%d multiply-adds, k_miller_step_dbl<true>) + the first without (%d) + "
-                        "23 addition steps (%.1f on average, k_miller_step_add); static multiply-adds of the loop body with both branches: %d"
-                        % (a["static_mads"], b["static_mads"], add["mads_per_proof_launch"], run["static_mads"]))
+                        "23 addition steps (%.1f on average, k_miller_step_add) = %.0f, - 88 x %d (the first key-side line in the Karatsuba form as well) + %d (r-torsion test "
+                        "of B, tail of the last launch); static multiply-adds of the kernel with both branches and the tail: %d"
+                        % (a["static_mads"], b["static_mads"], add["mads_per_proof_launch"], steps_total, line_delta, tail, run["static_mads"]))
         try:
             pmc = json.load(open(os.path.join(ROOT, "profiles", "miller_run_pmc_counts.json")))
             # per wavefront (64 proofs = one lane each): the multiply-adds are a known share of the 64-bit integer instructions of the step kernels
