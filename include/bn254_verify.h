@@ -174,11 +174,15 @@ int bn254_groth16_reserve(const bn254_g16_pvk* pvk, size_t n, int device);
  * BN254_FLAG_RLC is accepted and IGNORED: by its contract the status bytes are those of the exact path, and that is the path a mixed batch takes (groups of the
  * random-linear-combination mode are per key; mixed-key groups do not exist yet).
  *   Limits of this revision, refused with BN254_E_BAD_ARG and a text in bn254_last_diagnostic(): a key with more than 16 public inputs in the list (such keys run
- * the wide multi-scalar-multiplication kernels, a different pipeline: one bn254_groth16_verify_batch call per key), and more than 65 536 entries.
- *   How it runs: the proofs are grouped on the device so that every wavefront (64 lanes) works for one key -- at most 63 idle lanes per key that has proofs, so the
- * workspace is that of n + min(n_keys, n) * 63 proofs -- and the one-proof-per-lane kernels run at every size: a SMALL mixed batch does not get the cooperative
- * small-batch kernels or the latency mode of the single-key entries.  The host-buffer entry uploads index, records and input rows first (through pinned memory) and
- * then runs the same pipeline; it returns when the status bytes are back.
+ * the wide multi-scalar-multiplication kernels, a different pipeline: one bn254_groth16_verify_batch call per key), and more than 65 536 entries.  A mixed batch has
+ * no latency mode (the three Miller chains on three streams of the single-key entries) and no random-linear-combination groups.
+ *   How it runs: in one of two forms, chosen from n alone (bn254_set_keys_params), with the same status bytes.  A SMALL batch -- up to keys_coop_max proofs -- takes
+ * the DIRECT form: no grouping and no padding, the records are parsed in proof order and one cooperative kernel (twelve lanes per proof, five proofs per wavefront,
+ * the key read per proof: the five proofs of a wavefront may belong to five keys) does the public-input sum, the Miller loop, the final exponentiation and the
+ * verdict: two launches, as the small batches of the single-key entries.  A larger batch takes the GROUPED form: the proofs are grouped on the device so that
+ * every wavefront (64 lanes) works for one key -- at most 63 idle lanes per key that has proofs -- and the one-proof-per-lane kernels run on those slots.  The
+ * workspace of a reservation is that of n + min(n_keys, n) * 63 proofs whatever the form, since the knob may move between calls.  The host-buffer entry uploads
+ * index, records and input rows first (through pinned memory) and then runs the same pipeline; it returns when the status bytes are back.
  *   Device state of a list: kept per (list of handles in order, device), the four most recently used lists, least recently used out first; bn254_groth16_vk_free of
  * a member drops every cached list that contains it (and a call with a list that names a freed key is undefined, as any use of a freed handle).  A list does NOT
  * build its members' own per-device tables (13 MB per K point): it keeps 38.5 KB of line tables per distinct key and byte-window tables of 652 800 bytes per K point
@@ -190,6 +194,10 @@ int bn254_groth16_verify_batch_keys(const bn254_g16_pvk* const* pvks, size_t n_k
 int bn254_groth16_verify_batch_keys_device(const bn254_g16_pvk* const* pvks, size_t n_keys, const void* d_key_index, const void* d_proofs, size_t proof_stride,
                                            const void* d_public_inputs, size_t input_stride, size_t n, void* d_status, int device, void* hip_stream, unsigned flags);
 int bn254_groth16_reserve_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, size_t n, int device);
+/* Knob of the plan of a batch over many keys (process-wide, atomic; a negative value leaves it alone; initial value from BN254_KEYS_COOP_MAX, read once at load
+ * time; default 30 720, the largest size at which the direct form was measured to gain at every key count: profiles/r10_multikey_small.txt): batches of up to
+ * coop_max proofs take the direct form, larger ones the grouped form.  0: always the grouped form; values above 30 720 (the range of the cooperative kernels) are clamped; BN254_COOP=0 in the environment switches the direct form off whatever the knob says.  Same status bytes whatever the plan. */
+void bn254_set_keys_params(long coop_max);
 
 /* Groth16Verifier::verify (lib.rs:44-49) as one call: one proof, one status byte, vk given as bytes on every call like the
  * reference.  The prepared form of the last four keys (exact byte match, per mode) is kept, so only the first call with a key pays
@@ -465,11 +473,17 @@ int bn254_dbg_comb_table_compare(const bn254_g16_pvk* pvk, int device, int input
  * kernels on that device */
 size_t bn254_dbg_g16_keys_slot_bound(size_t n, size_t n_keys);
 int bn254_dbg_g16_keys_group(const unsigned* key_index, size_t n, size_t n_keys, int device, unsigned* out_slot_to_proof, unsigned* out_granule_key, size_t* out_n_slots);
+/* the plan of a batch of n proofs over n_keys keys (csrc/bn254_g16_plan.h, the function the entries enqueue by; host only).  *form: 0 grouped lanes, 1 direct
+ * cooperative; *slots: n, or bn254_dbg_g16_keys_slot_bound(n, n_keys); *launches: kernels + memsets a raw-record batch enqueues through the device entry (without the
+ * kernel of BN254_FLAG_STRICT_SCALARS) */
+int bn254_dbg_g16_keys_plan(size_t n, size_t n_keys, int* form, size_t* slots, int* launches);
+/* the form of the last batch enqueued on the cached state of (list, device): 0 or 1 as above, -1 if there was none (also: the list is not cached) */
+int bn254_dbg_g16_keys_last_form(const bn254_g16_pvk* const* pvks, size_t n_keys, int device, int* form);
 int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t* mismatches);   /* the window tables of a PlonK key's points (csrc/bn254_fw.h): every window's first, middle and last entries and a pseudo-random sample */
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

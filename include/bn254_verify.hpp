@@ -231,6 +231,9 @@ struct Groth16Verifier {
     for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
     detail::check(bn254_groth16_reserve_keys(h.data(), h.size(), n, device));
   }
+  // the plan of a batch over many keys (bn254_set_keys_params): batches of up to coop_max proofs take the direct cooperative form; 0: always the grouped form;
+  // a negative value leaves the knob alone.  Process-wide.
+  static void set_keys_params(long coop_max) { bn254_set_keys_params(coop_max); }
   static Result<bool, Groth16Error> outcome(uint8_t status) { return detail::groth16_outcome(status); }
 };
 

@@ -162,6 +162,24 @@ def set_plonk_params(piece=-1, workers=-1, big_from=-1, big_piece=-1):
     L.bn254_set_plonk_params(piece, workers, big_from, big_piece)
 
 
+def set_keys_params(coop_max=-1):
+    """Knob of the plan of a batch over many keys (bn254_set_keys_params): batches of up to coop_max proofs take the direct cooperative form, larger ones the grouped
+    lane form; 0: always grouped; a negative value leaves the knob alone."""
+    L = lib()
+    L.bn254_set_keys_params.argtypes = [C.c_long]
+    L.bn254_set_keys_params.restype = None
+    L.bn254_set_keys_params(coop_max)
+
+
+def dbg_keys_plan(n, n_keys):
+    """The plan of a batch of n proofs over n_keys keys (bn254_dbg_g16_keys_plan): (form, slots, launches) -- form 0: grouped lanes, 1: direct cooperative."""
+    L = lib()
+    L.bn254_dbg_g16_keys_plan.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_int), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    form, slots, launches = C.c_int(-1), C.c_size_t(0), C.c_int(0)
+    _check(L.bn254_dbg_g16_keys_plan(n, n_keys, C.byref(form), C.byref(slots), C.byref(launches)))
+    return int(form.value), int(slots.value), int(launches.value)
+
+
 def _check(rc):
     if rc != 0:
         raise Bn254Error("bn254 error %d: %s" % (rc, lib().bn254_last_error().decode()))
@@ -502,6 +520,14 @@ class KeySet:
         fn = lib().bn254_groth16_reserve_keys
         fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_int]
         _check(fn(self._arr, len(self.keys), n, device))
+
+    def last_form(self, device=0):
+        """Form of the last batch enqueued with this list on `device` (bn254_dbg_g16_keys_last_form): 0 grouped lanes, 1 direct cooperative, -1 none yet."""
+        fn = lib().bn254_dbg_g16_keys_last_form
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
+        form = C.c_int(-1)
+        _check(fn(self._arr, len(self.keys), device, C.byref(form)))
+        return int(form.value)
 
 
 def dbg_keys_group(key_index, n_keys, device=-1):

@@ -340,6 +340,14 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 #else
 void keys_sets_drop(const bn254_g16_pvk*) {}
 #endif
+// the direct form of a batch over many keys: a host build starts with the knob at 0 (bn254_capi_keys.hip), so this is never reached unless a harness turns the knob --
+// and that harness brings its own stand-in (tests/hostsan/hostsan_keys_small.cpp)
+#if defined(BN254_HOSTSAN_KEYS) && !defined(BN254_HOSTSAN_KEYS_DIRECT)
+hipError_t bn254_launch_g16_keys_direct(const G16KeysDirectArgs&, hipStream_t) { return hipErrorInvalidDeviceFunction; }
+#endif
+#if defined(BN254_HOSTSAN_KEYS)
+hipError_t bn254_coop12_prepare() { return hipSuccess; }      // the step-kind table of the cooperative kernels: nothing to create without a device compiler
+#endif
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {

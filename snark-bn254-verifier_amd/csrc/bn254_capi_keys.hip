@@ -1,10 +1,25 @@
 // bn254_capi_keys.hip -- Groth16 batches over many verifying keys in one call (include/bn254_verify.h, "Batches over many keys"): the per (key list, device) state --
 // descriptors, the keys' line tables, byte-window tables of all their K points in one allocation, the slot workspace -- its cache, and the three entries.
-// The kernels are in bn254_k_keys.hip / bn254_k_miller.hip, the grouping arithmetic in bn254_keys.h.
+// The kernels are in bn254_k_keys.hip / bn254_k_miller.hip (grouped form) and bn254_coop12.hip (direct form), the grouping arithmetic in bn254_keys.h, the choice
+// between the forms in bn254_g16_plan.h.
 #include "bn254_capi_internal.h"
 #include "bn254_keys.h"
 
+#include "bn254_vm.h"
+
 using bn254::G16KeyDesc;
+
+// The knob of the plan (bn254_set_keys_params; BN254_KEYS_COOP_MAX gives the initial value once, at load time): batches of up to this many proofs take the direct form
+// (bn254_g16_plan.h::g16_keys_form).  A build without a device compiler (tests/hostsan) starts at 0 whatever the environment says: the grouped form at every size,
+// until a harness that brings a stand-in for the direct launcher turns the knob.
+static long keys_coop_clamp(long v) { return v > (long)COOP12_MAX_PROOFS ? (long)COOP12_MAX_PROOFS : v; }
+#if defined(__HIPCC__)
+static std::atomic<long> g_keys_coop_max{[] { long v = env_long("BN254_KEYS_COOP_MAX", (long)G16_KEYS_COOP_MAX_DEFAULT); return v < 0 ? (long)G16_KEYS_COOP_MAX_DEFAULT : keys_coop_clamp(v); }()};
+#else
+static std::atomic<long> g_keys_coop_max{0};
+#endif
+static bool keys_coop_on() { static const bool on = [] { const char* e = getenv("BN254_COOP"); return !e || atoi(e) != 0; }(); return on; }
+static int keys_form(size_t n) { return bn254::g16_keys_form(n, (size_t)g_keys_coop_max.load(std::memory_order_relaxed), keys_coop_on()); }
 
 // A set does NOT make its members' own per-device state ready: ensure_dev builds a key's 13-bit window tables (13 MB per K point, bn254_fw.h), and a key that is only
 // used through sets must never cost that.  The set keeps, per DISTINCT handle of the list (a handle may occur many times): both line tables, K[0] and e(alpha, beta)
@@ -31,6 +46,7 @@ struct KeySet {
   DevBuf<uint8_t> slot_status;
   DevBuf<uint8_t> cmp; size_t cmp_cap = 0;                          // BN254_FLAG_COMPRESSED_PROOFS: raw records of the whole batch, then one pre-status byte per proof
   Stream aux; Event fork_ev, join_ev, busy_ev; bool busy_valid = false;
+  int last_form = -1;                       // form of the last batch enqueued (bn254_dbg_g16_keys_last_form)
   // host-buffer entry: device copies of the caller's buffers, the pinned ring they travel through with its streams
   DevBuf<uint8_t> st_proofs, st_inputs, st_index, st_status;
   PinRing ring;
@@ -65,6 +81,12 @@ struct SetCache {
       v->set = out; v->tick = ++clock;
     }
     return out;
+  }
+  std::shared_ptr<KeySet> find(const bn254_g16_pvk* const* pvks, size_t n_keys, int device) {      // no insertion, no change of the order
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& x : e)
+      if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) return x.set;
+    return nullptr;
   }
   void drop(const bn254_g16_pvk* member) {
     std::vector<std::shared_ptr<KeySet>> gone;
@@ -125,6 +147,8 @@ int ensure_set(KeySet& s, size_t n, unsigned flags) {
     }
     if ((rc = upload(s.desc, desc)) || (rc = s.busy_ev.ensure()) || (rc = s.fork_ev.ensure()) || (rc = s.join_ev.ensure()) || (rc = s.aux.ensure())) return rc;
     if ((rc = s.count.ensure(n_keys, oom)) || (rc = s.base.ensure(n_keys, oom)) || (rc = s.cursor.ensure(n_keys, oom)) || (rc = s.n_slots.ensure(1, oom))) return rc;
+    // the direct form's kernel reads the step-kind table of the cooperative kernels, which is created on a device's first use: now, so that a batch only enqueues
+    if (bn254_coop12_prepare() != hipSuccess) return set_err(oom, "out of device memory for the step table of the cooperative kernels");
     s.ready = true;
   }
   if (n > s.cap_n) {   // the workspace and the slot buffers are sized together: cap_n / slot_cap are what ALL of them hold, 0 while any of them is being replaced
@@ -155,6 +179,7 @@ int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_
   const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
   if (n > s.cap_n || bound > s.slot_cap) return set_err(BN254_E_BAD_ARG, "buffers of the key set smaller than the batch (internal sizing error)");
   if (s.busy_valid) HIPCK(hipStreamWaitEvent(user, s.busy_ev, 0));
+  const int form = keys_form(n);
   const uint8_t* proofs = (const uint8_t*)d_proofs;
   uint8_t* pre = nullptr;
   if (flags & BN254_FLAG_COMPRESSED_PROOFS) {
@@ -168,29 +193,39 @@ int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_
     }
     proofs = s.cmp; proof_stride = 256;
   }
-  hipError_t e = bn254_launch_keys_group((const uint32_t*)d_key_index, (uint32_t)n, n_keys, (uint32_t)bound, s.count, s.base, s.cursor, s.n_slots, s.slot_to_proof, s.granule_key,
-                                         (uint8_t*)d_status, user);
-  if (e != hipSuccess) return launch_err(e, "grouping");
-  const size_t slots = exact_slots ? exact_slots : bound;
-  for (size_t off = 0; off < slots; off += G16_MAX_BATCH) {
-    const size_t m = slots - off < (size_t)G16_MAX_BATCH ? slots - off : (size_t)G16_MAX_BATCH;
-    bn254::G16ChunkPlan plan;
-    if (!bn254::g16_plan_chunk(plan, m, 0, 0, n_streams, false)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
-    if (bn254::g16_round256(m) > s.ws_slots()) return set_err(BN254_E_BAD_ARG, "workspace of the key set smaller than the batch (internal sizing error)");
-    if (plan.concurrent) HIPCK(hipEventRecord(s.fork_ev, user));
-    for (int pi = 0; pi < plan.parts; pi++) {
-      const size_t lo = plan.part[pi].first, cnt = plan.part[pi].count;
-      hipStream_t st = (plan.concurrent && (pi & 1)) ? (hipStream_t)s.aux : user;
-      if (st != user && pi == 1) HIPCK(hipStreamWaitEvent(st, s.fork_ev, 0));
-      G16KeysLaunchArgs a;
-      a.proofs = proofs; a.stride = proof_stride; a.inputs = (const uint8_t*)d_inputs; a.input_stride = input_stride; a.n_proofs = (uint32_t)n;
-      a.m = cnt; a.slot0 = (uint32_t)(off + lo); a.n_slots = s.n_slots; a.slot_to_proof = s.slot_to_proof + off + lo; a.granule_key = s.granule_key + (off + lo) / G16_KEYS_GRANULE;
-      a.desc = s.desc; a.n_keys = n_keys; a.ws = s.ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.slot_status = s.slot_status + off + lo; a.status = (uint8_t*)d_status;
-      a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
-      a.part_of_larger = plan.parts > 1 ? 1 : 0;
-      if ((e = bn254_launch_g16_keys(a, st)) != hipSuccess) return launch_err(e, "key-set pipeline");
+  hipError_t e = hipSuccess;
+  if (form == bn254::G16_KEYS_FORM_DIRECT) {
+    // one launch group over the n proofs on the caller's stream, at the start of the workspace: a slot is a proof, the status bytes are the caller's
+    if (bn254::g16_round256(n) > s.ws_slots()) return set_err(BN254_E_BAD_ARG, "workspace of the key set smaller than the batch (internal sizing error)");
+    G16KeysDirectArgs a;
+    a.proofs = proofs; a.stride = proof_stride; a.inputs = (const uint8_t*)d_inputs; a.input_stride = input_stride; a.n = n; a.key_index = (const uint32_t*)d_key_index;
+    a.desc = s.desc; a.n_keys = n_keys; a.ws = s.ws; a.status = (uint8_t*)d_status; a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+    if ((e = bn254_launch_g16_keys_direct(a, user)) != hipSuccess) return launch_err(e, "key-set pipeline (direct form)");
+  } else {
+    e = bn254_launch_keys_group((const uint32_t*)d_key_index, (uint32_t)n, n_keys, (uint32_t)bound, s.count, s.base, s.cursor, s.n_slots, s.slot_to_proof, s.granule_key,
+                                (uint8_t*)d_status, user);
+    if (e != hipSuccess) return launch_err(e, "grouping");
+    const size_t slots = exact_slots ? exact_slots : bound;
+    for (size_t off = 0; off < slots; off += G16_MAX_BATCH) {
+      const size_t m = slots - off < (size_t)G16_MAX_BATCH ? slots - off : (size_t)G16_MAX_BATCH;
+      bn254::G16ChunkPlan plan;
+      if (!bn254::g16_plan_chunk(plan, m, 0, 0, n_streams, false)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+      if (bn254::g16_round256(m) > s.ws_slots()) return set_err(BN254_E_BAD_ARG, "workspace of the key set smaller than the batch (internal sizing error)");
+      if (plan.concurrent) HIPCK(hipEventRecord(s.fork_ev, user));
+      for (int pi = 0; pi < plan.parts; pi++) {
+        const size_t lo = plan.part[pi].first, cnt = plan.part[pi].count;
+        hipStream_t st = (plan.concurrent && (pi & 1)) ? (hipStream_t)s.aux : user;
+        if (st != user && pi == 1) HIPCK(hipStreamWaitEvent(st, s.fork_ev, 0));
+        G16KeysLaunchArgs a;
+        a.proofs = proofs; a.stride = proof_stride; a.inputs = (const uint8_t*)d_inputs; a.input_stride = input_stride; a.n_proofs = (uint32_t)n;
+        a.m = cnt; a.slot0 = (uint32_t)(off + lo); a.n_slots = s.n_slots; a.slot_to_proof = s.slot_to_proof + off + lo; a.granule_key = s.granule_key + (off + lo) / G16_KEYS_GRANULE;
+        a.desc = s.desc; a.n_keys = n_keys; a.ws = s.ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.slot_status = s.slot_status + off + lo; a.status = (uint8_t*)d_status;
+        a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+        a.part_of_larger = plan.parts > 1 ? 1 : 0;
+        if ((e = bn254_launch_g16_keys(a, st)) != hipSuccess) return launch_err(e, "key-set pipeline");
+      }
+      if (plan.concurrent && plan.parts > 1) { HIPCK(hipEventRecord(s.join_ev, s.aux)); HIPCK(hipStreamWaitEvent(user, s.join_ev, 0)); }
     }
-    if (plan.concurrent && plan.parts > 1) { HIPCK(hipEventRecord(s.join_ev, s.aux)); HIPCK(hipStreamWaitEvent(user, s.join_ev, 0)); }
   }
   if (pre)
     for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
@@ -199,6 +234,7 @@ int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_
     }
   HIPCK(hipEventRecord(s.busy_ev, user));
   s.busy_valid = true;
+  s.last_form = form;
   return BN254_OK;
 }
 
@@ -270,6 +306,52 @@ int bn254_groth16_verify_batch_keys(const bn254_g16_pvk* const* pvks, size_t n_k
   if ((rc = keys_enqueue(s, s.st_index, s.st_proofs, proof_stride, s.st_inputs, input_stride, n, s.st_status, ring.compute, flags, exact_slots))) return ring.drain(rc);
   HIPCK(hipMemcpyAsync(status, s.st_status, n, hipMemcpyDeviceToHost, ring.compute));
   HIPCK(hipStreamSynchronize(ring.compute));
+  return BN254_OK;
+}
+
+void bn254_set_keys_params(long coop_max) {
+  if (coop_max >= 0) g_keys_coop_max.store(keys_coop_clamp(coop_max), std::memory_order_relaxed);
+}
+
+// The plan of a batch, for the tests: the form from the function keys_enqueue calls, and what that form enqueues for raw records through the device entry (which
+// covers keys_slot_bound(n, n_keys) slots).  The grouped form's kernels are counted by walking its programs with an operation counter.
+namespace {
+struct KeysCountOps {
+  int launches = 0;
+  void miller_run(int, int, int, int, int, int, int, int) { launches++; }
+  void f12_mul(int, int, int, bool = false) { launches++; }
+  void f12_cyclo_sqr(int, int) { launches++; }
+  void f12_cyclo_sqr_n(int, int, int) { launches++; }
+  void f12_frob(int, int, int) { launches++; }
+  void f12_inv(int, int) { launches++; }
+};
+}  // namespace
+int bn254_dbg_g16_keys_plan(size_t n, size_t n_keys, int* form, size_t* slots, int* launches) {
+  if (!form || !slots || !launches || n == 0 || n_keys == 0 || n_keys > G16_KEYS_MAX_KEYS || bn254::keys_slot_bound(n, n_keys) > 0xffff0000ull) return set_err(BN254_E_BAD_ARG, "bad argument");
+  *form = keys_form(n);
+  if (*form == bn254::G16_KEYS_FORM_DIRECT) { *slots = n; *launches = 2; return BN254_OK; }      // k_g16_prepare, k_coop12_miller_g16_keys
+  const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
+  const int n_streams = sub_batch_streams() < 2 ? sub_batch_streams() : 2;
+  int total = 6;                                   // bn254_launch_keys_group: three memsets, count, scan, place
+  for (size_t off = 0; off < bound; off += G16_MAX_BATCH) {
+    const size_t m = bound - off < (size_t)G16_MAX_BATCH ? bound - off : (size_t)G16_MAX_BATCH;
+    bn254::G16ChunkPlan plan;
+    if (!bn254::g16_plan_chunk(plan, m, 0, 0, n_streams, false)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    for (int pi = 0; pi < plan.parts; pi++) {
+      KeysCountOps ops;
+      bn254::vm_miller_program_runs(ops, bn254::g16_launch_form(plan.part[pi].count, 0, true, false, plan.parts > 1, false, false, -1).run_steps);
+      bn254::vm_final_exp_program_head(ops);
+      total += 1 + ops.launches + 1;               // k_g16_prepare_keys, the runs and the program, k_f12_mul_verdict_keys
+    }
+  }
+  *slots = bound; *launches = total;
+  return BN254_OK;
+}
+int bn254_dbg_g16_keys_last_form(const bn254_g16_pvk* const* pvks, size_t n_keys, int device, int* form) {
+  if (!pvks || !form || n_keys == 0) return set_err(BN254_E_BAD_ARG, "bad argument");
+  *form = -1;
+  std::shared_ptr<KeySet> s = set_cache().find(pvks, n_keys, device);
+  if (s) { std::lock_guard<std::mutex> lk(s->mu); *form = s->last_form; }
   return BN254_OK;
 }
 

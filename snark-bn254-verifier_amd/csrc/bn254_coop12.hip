@@ -17,6 +17,7 @@
 // Lock-step: a wavefront executes its LDS instructions in order, every operation reads all of its inputs before it writes
 // its output slot.
 #include <hip/hip_runtime.h>
+#include <cstddef>
 #include <mutex>
 #include "bn254_vm.h"
 #include "bn254_kernels.h"
@@ -468,6 +469,151 @@ k_coop12_miller_g16(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __r
   } else c12_store_f12(co, ws, n, p, F, VE_F, pending);
 }
 
+// ---- Groth16 over many keys, the DIRECT form (bn254_keys.h; bn254_g16_plan.h::g16_keys_form): k_coop12_miller_g16 with the key taken per PROOF --------------------
+// A slot is a proof and the key belongs to the twelve-lane group: the five proofs of a wavefront may belong to five keys.  Group p reads key_index[p] and the
+// descriptor of that entry with ordinary per-lane loads (all twelve lanes the same address), and every place where k_coop12_miller_g16 takes the key from its launch
+// arguments -- the two line tables, K0 and the fixed-base tables, n_public with inputs_match, the target -- takes it from there.  What differs otherwise:
+//   line tables   fetched per lane with vector loads (c12_key_g2 / c12_key_c1: 54 dwords per step), step s + 1's issued while step s computes; the scalar loads
+//                 of c12_line_entry need a wavefront-uniform key
+//   L             over the set's BYTE-window tables (32 windows of 8 bits per input: what k_g16_prepare_keys reads); the loop bound differs per group, all LDS
+//                 traffic comes after the loop
+//   prologue      the two status bytes the pipeline alone cannot decide, before the early return: an index outside the list is MALFORMED whatever the record holds,
+//                 and with BN254_FLAG_STRICT_SCALARS an input >= r among the key's n_public inputs is NOT_MEMBER ahead of every loader outcome
+struct C12Key { const int32_t *msm_tab, *k0, *gtab, *dtab, *target; int n_public, inputs_match; };
+// a pointer read from memory is a generic pointer to the compiler (flat loads): the descriptor's pointers are named global
+__device__ __forceinline__ const int32_t* c12_global_ptr(uint64_t bits) { return (const int32_t*)(const __attribute__((address_space(1))) int32_t*)bits; }
+__device__ __forceinline__ C12Key c12_key(const G16KeyDesc* __restrict__ desc, uint32_t k) {
+  // the descriptor as six 64-bit words: five pointers in this order, then the two ints
+  static_assert(sizeof(G16KeyDesc) == 48 && offsetof(G16KeyDesc, msm_tab) == 0 && offsetof(G16KeyDesc, k0) == 8 && offsetof(G16KeyDesc, gtab) == 16 &&
+                offsetof(G16KeyDesc, dtab) == 24 && offsetof(G16KeyDesc, target) == 32 && offsetof(G16KeyDesc, n_public) == 40 && offsetof(G16KeyDesc, inputs_match) == 44,
+                "c12_key reads G16KeyDesc by position");
+  const uint64_t* f = (const uint64_t*)(desc + k);
+  C12Key v;
+  v.msm_tab = c12_global_ptr(f[0]); v.k0 = c12_global_ptr(f[1]); v.gtab = c12_global_ptr(f[2]); v.dtab = c12_global_ptr(f[3]); v.target = c12_global_ptr(f[4]);
+  const uint64_t w = f[5];
+  v.n_public = (int)(uint32_t)w; v.inputs_match = (int)(uint32_t)(w >> 32);
+  return v;
+}
+// The line-table dwords a lane needs of step s.  The G2 rounds multiply m of table 0 and m of table 1 at coefficient position 5 only and c of table 0 at position 3
+// (doubling) or 4 (addition) only (c12_g2_double / c12_g2_add: the operands c12_sel6 picks), so a lane fetches ONE of m, c of table 0 -- the one its position
+// multiplies -- and passes it for both; every lane needs its halves of c of table 1 for the third line product.  54 dwords per lane and step instead of the 72 of
+// the two entries, in two groups that are each fetched right after their last use in the step before: no second copy is alive while a step computes.
+__device__ __forceinline__ Fp2 c12_tab_fp2(const int32_t* e) {
+  Fp2 r;
+#pragma unroll
+  for (int i = 0; i < BN_NL; i++) { r.c0.v[i] = e[i]; r.c1.v[i] = e[BN_NL + i]; }
+  return r;
+}
+struct C12KeyG2 { Fp2 mc0, m1; };   // table 0: m at position 5, c elsewhere; table 1: m
+__device__ __forceinline__ C12KeyG2 c12_key_g2(const int32_t* gtab, const int32_t* dtab, int s, uint32_t c) {
+  C12KeyG2 l;
+  l.mc0 = c12_tab_fp2(gtab + (size_t)s * FIXED_LINE_DWORDS + (c == 5 ? 0 : 2 * BN_NL));
+  l.m1 = c12_tab_fp2(dtab + (size_t)s * FIXED_LINE_DWORDS);
+  return l;
+}
+__device__ __forceinline__ Fp2 c12_key_c1(const int32_t* dtab, int s) { return c12_tab_fp2(dtab + (size_t)s * FIXED_LINE_DWORDS + 2 * BN_NL); }
+// L = K0 + sum_s x_s K_s by the twelve lanes of a proof over byte windows: lane l adds the entries of the windows w = l, l + 12, ... of the 32 n_public windows of its
+// proof's key (window wi of input s = byte 31 - wi of the big-endian scalar, entry (s * 32 + wi) * 255 + digit - 1), then the tree of c12_public_input_msm
+__device__ __noinline__ G1Proj c12_public_input_msm_keys(const Coop12 co, const uint8_t* in /* this proof's input row */, int n_public, const int32_t* tab, const int32_t* k0p) {
+  const uint32_t l12 = 2 * co.c + co.h;
+  const uint8_t* row = (const uint8_t*)(const __attribute__((address_space(1))) uint8_t*)in;
+  const int32_t *msm_tab = c12_global_ptr((uint64_t)tab), *k0 = c12_global_ptr((uint64_t)k0p);
+  G1Proj acc = g1_identity();
+  if (l12 == 0) { G1Aff K0; for (int l = 0; l < BN_NL; l++) { K0.x.v[l] = k0[l]; K0.y.v[l] = k0[BN_NL + l]; } acc = g1_from_affine(K0); }
+  const int windows = 32 * n_public;
+  for (int w = (int)l12; w < windows; w += 12) {
+    const int sidx = w >> 5, wi = w & 31;
+    const uint32_t dig = row[sidx * 32 + 31 - wi];
+    G1Proj nxt = g1_add_mixed(acc, c12_msm_entry(msm_tab, (size_t)(sidx * 32 + wi) * 255 + (dig ? dig - 1 : 0)));
+    const bool take = dig != 0;
+    acc.x = fp_select(take, nxt.x, acc.x); acc.y = fp_select(take, nxt.y, acc.y); acc.z = fp_select(take, nxt.z, acc.z);
+  }
+  auto publish = [&](const G1Proj& a) { co.put(C12_R1, fp_reduce(a.x)); co.put(C12_R2, fp_reduce(a.y)); co.put(C12_R3, fp_reduce(a.z)); };
+  auto fetch = [&](uint32_t i) { G1Proj r; r.x = co.at(C12_R1, co.g0 + i); r.y = co.at(C12_R2, co.g0 + i); r.z = co.at(C12_R3, co.g0 + i); return r; };
+  publish(acc);
+  acc = g1_add(acc, fetch(l12 < 6 ? l12 + 6 : l12));
+  publish(acc);
+  { const uint32_t b = l12 < 2 ? l12 : 0; acc = g1_add(g1_add(fetch(b), fetch(b + 2)), fetch(b + 4)); }
+  publish(acc);
+  acc = g1_add(fetch(0), fetch(1));
+  publish(acc);
+  return fetch(0);
+}
+__global__ void __launch_bounds__(64)
+k_coop12_miller_g16_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const uint32_t* __restrict__ key_index,
+                         const G16KeyDesc* __restrict__ desc, uint32_t n_keys, const uint8_t* __restrict__ inputs, size_t input_stride, int strict_scalars) {
+  extern __shared__ __attribute__((aligned(16))) int32_t c12_lds[];
+  const uint32_t lane = threadIdx.x & 63;
+  const bool act = lane < 12 * C12_PER_WAVE;
+  const uint32_t la = act ? lane : lane - 12;             // idle lanes shadow the last group
+  const uint32_t pl = la / 12, c = (la - pl * 12) >> 1, h = la & 1;
+  const uint32_t p = blockIdx.x * (uint32_t)C12_PER_WAVE + pl;
+  const bool live = act && p < n;
+  const uint32_t pc = p < n ? p : n - 1;
+  const uint32_t ki = key_index[pc];
+  const bool key_ok = ki < n_keys;
+  const C12Key key = c12_key(desc, key_ok ? ki : 0u);
+  const uint8_t* in = inputs + (size_t)pc * input_stride;
+  uint8_t st = status[pc];
+  {
+    bool bad = false;
+    if (strict_scalars)
+      for (int s = (int)(2 * c + h); s < key.n_public; s += 12) { uint32_t w[8]; words_from_be(w, in + (size_t)s * 32); bad |= words_ge(w, BN_R_WORDS); }
+    const bool group_bad = ((__builtin_amdgcn_ballot_w64(act && bad) >> (pl * 12u)) & 0xfffull) != 0;
+    const uint8_t fixed = !key_ok ? (uint8_t)BN254_ST_MALFORMED : group_bad ? (uint8_t)BN254_ST_NOT_MEMBER : st;
+    if (live && c == 0 && h == 0 && fixed != st) status[p] = fixed;
+    st = fixed;
+  }
+  const bool pending = live && (st & BN254_ST_PENDING) != 0;
+  if (__builtin_amdgcn_ballot_w64(pending) == 0) return;
+  Coop12 co{(c12_lds_i32*)c12_lds, lane, pl * 12, c, h};
+  const int F = C12_SLOT(VE_F);
+  const G1Proj Lp = c12_public_input_msm_keys(co, in, key.inputs_match ? key.n_public : 0, key.msm_tab, key.k0);
+  const bool l_inf = fp_is_zero(Lp.z);
+  const Fp xl = Lp.x, yl = fp_select(l_inf, fp_one(), Lp.y), zl = Lp.z;
+  co.put(F, (c == 0 && h == 0) ? fp_one() : fp_zero());
+  const Fp xa = c12_ws_ld(ws, n, pc, VE_AX), ya = c12_ws_ld(ws, n, pc, VE_AY);
+  const Fp xc = c12_ws_ld(ws, n, pc, VE_CX), yc = c12_ws_ld(ws, n, pc, VE_CY);
+  G2Aff q; q.x = c12_ws_ld2(ws, n, pc, VE_B); q.y = c12_ws_ld2(ws, n, pc, VE_B + 2);
+  G2Proj t = g2_from_affine(q);
+  C12KeyG2 kg = c12_key_g2(key.gtab, key.dtab, 0, c);
+  Fp2 kc1 = c12_key_c1(key.dtab, 0);
+  for (int s = 0; s < BN_ATE_STEPS; s++) {
+    const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
+    const int sn = s + 1 < BN_ATE_STEPS ? s + 1 : s;
+    if (kind == 0 && s != 0) c12_sqr(co, F);
+    C12Line ln;
+    if (kind == 0) {
+      c12_g2_double(co, t, xa, ya, kg.mc0, xl, kg.m1, xc, kg.mc0, zl, ln);
+    } else {
+      G2Aff b = q;
+      if (kind == 2) b = g2_neg(q);
+      else if (kind == 3) b = g2_psi_affine(q);
+      else if (kind == 4) b = g2_neg(g2_psi2_affine(q));
+      c12_g2_add(co, t, b.x, b.y, xa, ya, kg.mc0, xl, kg.m1, xc, kg.mc0, zl, ln);
+    }
+    kg = c12_key_g2(key.gtab, key.dtab, sn, c);      // step s + 1's: in flight during the three line products
+    c12_mul_line_fp2(co, F, c12_halves(ln.d0, h), c12_halves(ln.d3, h), c12_halves(ln.d4, h));
+    c12_mul_line_fp(co, F, yl, c12_halves(ln.s1, h), c12_halves(ln.cz, h), l_inf);      // (Y_L + m X_L w + c Z_L w^3): the line at L scaled by Z_L
+    c12_mul_line_fp(co, F, yc, c12_halves(ln.s2, h), c12_halves(kc1, h), false);
+    kc1 = c12_key_c1(key.dtab, sn);                  // in flight during the squaring and the G2 rounds of step s + 1
+  }
+  // the verdict tail of k_coop12_miller_g16 (fuse_final_exp && target) with the group's key
+  const Fp2 sx = fp2_mul(fp2_conj(q.x), frob_coeff(3, 2)), sy = fp2_neg(fp2_mul(fp2_conj(q.y), frob_coeff(3, 3)));
+  const bool in_g2 = !fp2_is_zero(t.z) & fp2_eq(t.x, fp2_mul(sx, t.z)) & fp2_eq(t.y, fp2_mul(sy, t.z));
+  Coop12Ops ops{co};
+  vm_final_exp_program(ops);
+  const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), key.target, pl);
+  if (pending && c == 0 && h == 0) {
+    uint8_t out;
+    if (!in_g2) out = BN254_ST_NOT_IN_SUBGROUP;
+    else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
+    else if (!key.inputs_match) out = BN254_ST_INPUT_LEN;     // PrepareInputsFailed comes after every loader error
+    else out = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
+    status[p] = out;
+  }
+}
+
 }  // namespace bn254
 
 using namespace bn254;
@@ -487,6 +633,7 @@ static const uint8_t* c12_kinds_dev() {
   }
   return dev[d];
 }
+hipError_t bn254_coop12_prepare() { return c12_kinds_dev() ? hipSuccess : hipErrorOutOfMemory; }
 hipError_t bn254_coop12_final_exp(int32_t* ws, uint8_t* status, size_t n, hipStream_t s) {
   const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
   (void)hipFuncSetAttribute((const void*)k_coop12_final_exp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -511,5 +658,14 @@ hipError_t bn254_coop12_miller_g16(int32_t* ws, uint8_t* status, size_t n, const
   (void)hipFuncSetAttribute((const void*)k_coop12_miller_g16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(k_coop12_miller_g16, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, tab0, tab1, inputs, n_public,
                      inputs_match_key, msm_tab, k0, l_from_ws, fuse_final_exp, target);
+  return hipGetLastError();
+}
+hipError_t bn254_coop12_miller_g16_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_index, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint8_t* inputs,
+                                        size_t input_stride, int strict_scalars, hipStream_t s) {
+  const uint8_t* kinds = c12_kinds_dev();
+  if (!kinds) return hipErrorOutOfMemory;
+  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
+  (void)hipFuncSetAttribute((const void*)k_coop12_miller_g16_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k_coop12_miller_g16_keys, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, key_index, desc, n_keys, inputs, input_stride, strict_scalars);
   return hipGetLastError();
 }

@@ -51,6 +51,17 @@ inline G16Form g16_launch_form(size_t n, size_t n_public, bool inputs_match_key,
   return f;
 }
 
+// ---- the form of a batch over many keys (bn254_groth16_verify_batch_keys[_device]) ---------------------------------------------------------------------------
+// From n alone: both entries know it on the host, the device entry does not know the slot count.  Up to keys_coop_max proofs (bn254_set_keys_params; never with
+// BN254_COOP=0) the DIRECT form: a slot is a proof, k_g16_prepare + k_coop12_miller_g16_keys, no grouping launches.  Otherwise the grouped lane form on
+// keys_slot_bound(n, n_keys) slots at most.
+enum { G16_KEYS_FORM_GROUPED = 0, G16_KEYS_FORM_DIRECT = 1 };
+// the hand-over: the largest measured n at which the direct form beats the grouped one (the parent revision's library) by more than the two cells' spreads at EVERY key
+// count measured: 30 720, the largest size measured -- 11.69 against 12.54 ms with one key, 12.10 against 42.15 ms with 4096 (profiles/r10_multikey_small.txt;
+// DESIGN.md section 9d)
+#define G16_KEYS_COOP_MAX_DEFAULT COOP12_MAX_PROOFS
+inline int g16_keys_form(size_t n, size_t keys_coop_max, bool coop_on) { return coop_on && n <= keys_coop_max && n <= (size_t)COOP12_MAX_PROOFS ? G16_KEYS_FORM_DIRECT : G16_KEYS_FORM_GROUPED; }
+
 // ---- one workspace chunk (at most G16_MAX_BATCH proofs) of a batch: its sub-batches -----------------------------------------------------------------------
 #define G16_MAX_PARTS 32
 struct G16Part {

@@ -129,6 +129,19 @@ void bn254_launch_f12_mul_verdict_keys(const G16KeysLaunchArgs& a, unsigned grid
 // the lane pipeline of bn254_launch_g16 on the slots of one launch part: prepare, the Miller loop in runs (the first sets f and T, the last tests B's subgroup), final
 // exponentiation, whose last product compares and scatters
 hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s);
+// the DIRECT form of a small batch over many keys (bn254_g16_plan.h::g16_keys_form): no grouping and no padding, a slot is a proof.  k_g16_prepare on the records in
+// proof order (it stops after C: the key never enters it), then k_coop12_miller_g16_keys, twelve lanes per proof with the key read per proof; two launches
+struct G16KeysDirectArgs {
+  const uint8_t* proofs; size_t stride;          // raw 256-byte records, proof order
+  const uint8_t* inputs; size_t input_stride;    // row i = inputs of proof i
+  size_t n;                 // <= COOP12_MAX_PROOFS
+  const uint32_t* key_index;
+  const bn254::G16KeyDesc* desc; uint32_t n_keys;
+  int32_t* ws;              // G16_WS_BYTES_PER_PROOF * n bytes
+  uint8_t* status;          // n bytes, proof order
+  int strict_scalars = 0;
+};
+hipError_t bn254_launch_g16_keys_direct(const G16KeysDirectArgs& a, hipStream_t s);
 // fixed-base tables of a key built on the device (bn254_k_comb.hip).  form 0: comb tables (points * 8192 entries), 1: byte-window tables (points * 32 * 255 entries), both of
 // MSM_ENTRY_DWORDS dwords; pts = `points` affine points (18 dwords each, device memory); scratch: teeth_plane = 27 * points * teeth dwords, teeth_aff = 18 * points * teeth
 // dwords, plane = 27 * points * entries dwords (bn254_tab_build_teeth / _entries: 13 / 8192 and 256 / 8192)
@@ -186,7 +199,12 @@ hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, c
 #define COOP12_MAX_PROOFS_FIXED 40960
 hipError_t bn254_coop12_miller_g16(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const uint8_t* inputs, int n_public,
                                    int inputs_match_key, const int32_t* msm_tab, const int32_t* k0, int l_from_ws, int fuse_final_exp, const int32_t* target, hipStream_t s);
+hipError_t bn254_coop12_miller_g16_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_index, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint8_t* inputs,
+                                        size_t input_stride, int strict_scalars, hipStream_t s);
 hipError_t bn254_coop12_final_exp(int32_t* ws, uint8_t* status, size_t n, hipStream_t s);
+// what the cooperative launchers create on the current device's first use (the 88-byte step-kind table: an allocation and a synchronous copy), created now: a
+// caller that reserves ahead calls this so that its later launches only enqueue
+hipError_t bn254_coop12_prepare();
 hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* tab0, const int32_t* tab1, const int32_t* tab2,
                                      int e_p0, int e_p1, int e_p2, int inf0, int inf1, int inf2, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s);
 static inline size_t bn254_coop_max_proofs() { return COOP12_MAX_PROOFS; }

@@ -1001,6 +1001,14 @@ hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s) {
   return hipGetLastError();
 }
 
+// ---- a SMALL batch over many keys, the direct form: the parse of the records in proof order, then the cooperative kernel that takes the key per proof -------------
+hipError_t bn254_launch_g16_keys_direct(const G16KeysDirectArgs& a, hipStream_t s) {
+  const uint32_t n = (uint32_t)a.n;
+  // wide_msm = 1: the kernel returns after C and never reads the inputs, the tables or K0
+  hipLaunchKernelGGL(k_g16_prepare, dim3(grid_for(a.n)), dim3(256), 0, s, a.proofs, a.stride, a.inputs, 0, n, a.ws, a.status, (const int32_t*)nullptr, (const int32_t*)nullptr, 1, 1);
+  return bn254_coop12_miller_g16_keys(a.ws, a.status, a.n, a.key_index, a.desc, a.n_keys, a.inputs, a.input_stride, a.strict_scalars, s);
+}
+
 // ---- RLC batch mode: per-proof stage, fold, group stage, scatter (bn254_rlc.h; orchestration of the fallback in bn254_capi.hip) ---------------------
 hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, hipStream_t s) {
   unsigned grid = grid_for(a.n);

@@ -370,8 +370,9 @@ def callee_straight(funcs, frag):
     return funcs[sym[0]]
 
 
-def coop12_callees(funcs, notes):
-    """Dynamic counts per call of the out-of-line operations."""
+def coop12_callees(funcs, notes, keys_notes):
+    """Dynamic counts per call of the out-of-line operations.  notes: what the records of the two older kernels carry; keys_notes: the callees of
+    k_coop12_miller_g16_keys alone."""
     ops = final_exp_ops()
     out = {}
     for name in ("c12_mul", "c12_conj", "c12_frob"):
@@ -405,10 +406,18 @@ def coop12_callees(funcs, notes):
     trips = -(-20 * N_PUBLIC // 12)
     out["msm"] = counts(ins, [(lg[0][0], lg[0][1][-1], float(trips))])
     notes.append("c12_public_input_msm: window loop x%d (%d multiply-adds per table addition)" % (trips, lg[0][2]))
+    # the same sum over the byte-window tables of a key set (k_coop12_miller_g16_keys): ceil(32 n_public / 12) window additions per lane
+    ins = callee_straight(funcs, "25c12_public_input_msm_keysENS")
+    lg, _ = loops_of(ins)
+    lg = [g for g in lg if g[2] > 1000]
+    assert len(lg) == 1, "c12_public_input_msm_keys: one window loop expected"
+    trips = -(-32 * N_PUBLIC // 12)
+    out["msm_keys"] = counts(ins, [(lg[0][0], lg[0][1][-1], float(trips))])
+    keys_notes.append("c12_public_input_msm_keys: byte-window loop x%d (%d multiply-adds per table addition)" % (trips, lg[0][2]))
     return out, ops
 
 
-def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2):
+def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2, msm="msm"):
     """kind 'g16': k_coop12_miller_g16; 'fixed': k_coop12_miller_fixed with n_pairs table-driven pairs."""
     ins = callee_straight(funcs, frag)
     lg, mads = loops_of(ins)
@@ -448,7 +457,7 @@ def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2):
                      % (s_m, p1_m, n_pairs))
     tot = counts(ins, ranges)
     if kind == "g16":
-        tot = add(tot, callees["msm"])
+        tot = add(tot, callees[msm])
     tot = add(tot, callees["c12_inv"], ops["inv"])
     tot = add(tot, callees["c12_conj"], ops["conj"])
     tot = add(tot, callees["c12_frob"], ops["frob"])
@@ -460,21 +469,22 @@ def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2):
 
 
 def model_coop12(funcs):
-    notes = []
-    callees, ops = coop12_callees(funcs, notes)
+    notes, keys_notes = [], []
+    callees, ops = coop12_callees(funcs, notes, keys_notes)
     pmc = None
     try:
         pmc = json.load(open(os.path.join(ROOT, "profiles", "coop12_pmc_counts.json")))
     except Exception:
         pass
     out = {}
-    for name, frag, kind in (("k_coop12_miller_g16", "19k_coop12_miller_g16E", "g16"), ("k_coop12_miller_fixed", "21k_coop12_miller_fixedE", "fixed")):
-        tot, n2 = coop12_kernel(funcs, frag, kind, callees, ops)
+    for name, frag, kind in (("k_coop12_miller_g16", "19k_coop12_miller_g16E", "g16"), ("k_coop12_miller_fixed", "21k_coop12_miller_fixedE", "fixed"),
+                             ("k_coop12_miller_g16_keys", "24k_coop12_miller_g16_keysE", "g16")):
+        tot, n2 = coop12_kernel(funcs, frag, kind, callees, ops, msm="msm_keys" if name.endswith("_keys") else "msm")
         e = {"lanes_per_proof": 12, "proofs_per_wavefront": 5,
              "wavefront_instructions": {k: round(v, 1) for k, v in tot.items()},
              "mads_per_proof_launch": tot["mads"] * 12,
              "static_mads": sum(1 for _, t, _ in callee_straight(funcs, frag) if MAD.match(t)),
-             "model": "; ".join(n2 + notes) + "; per proof = 12 lanes x the wavefront's count (lanes 60..63 idle)", "unmodelled": [], "symbol": frag}
+             "model": "; ".join(n2 + ([n for n in notes if not n.startswith("c12_public_input_msm:")] + keys_notes if name.endswith("_keys") else notes)) + "; per proof = 12 lanes x the wavefront's count (lanes 60..63 idle)", "unmodelled": [], "symbol": frag}
         if pmc and name in pmc:
             m = pmc[name]
             e["pmc_check"] = {"SQ_INSTS_VALU_INT64_per_wavefront": m["SQ_INSTS_VALU_INT64"], "model_int64": round(tot["int64"], 1),
