@@ -419,6 +419,15 @@ int bn254_dbg_plonk_plan(size_t n, size_t piece, int max_workers, int* workers, 
  * sizes against reservations: every launch inside the allocation, concurrent launches disjoint, the batch covered exactly once. */
 int bn254_dbg_g16_plan(size_t key_inputs, int comb, size_t reserved, size_t n, size_t n_public, int n_streams, int single_stream, uint64_t alloc[4], uint64_t* out,
                        int max_launches, int* n_launches);
+/* ... and of the compaction of its lane launches (csrc/bn254_g16_plan.h::g16_compacts, g16_compact_alloc): the same walk for a call with `flags`.  alloc = {slot -> proof
+ * bytes, slot status bytes, block count bytes} the context holds beside its workspace; out: 6 values per launch {compacts (0 / 1), first slot, slots, first block
+ * count, block counts, form} -- a launch that compacts addresses slots [first, first + slots rounded up to 256) and that many / 256 block counts. */
+int bn254_dbg_g16_compact_plan(size_t key_inputs, size_t reserved, size_t n, size_t n_public, unsigned flags, int n_streams, int single_stream, uint64_t alloc[3],
+                               uint64_t* out, int max_launches, int* n_launches);
+/* host restatement of the count -> scan -> write step of a launch that compacts (k_g16_classify's counts, k_g16_compact_write; the scan through the function the kernel
+ * runs): pending = n bytes (non-zero: the proof is still pending after the loader's final checks); slot_proof_out / slot_status_out receive n entries each,
+ * *n_pending_out the length of the dense list */
+int bn254_dbg_g16_compact(const uint8_t* pending, size_t n, unsigned* slot_proof_out, uint8_t* slot_status_out, unsigned* n_pending_out);
 /* ... and of BN254_FLAG_RLC's group status bytes: what the launch parts of a chunk of m proofs address (need) against what a context whose RLC buffers were sized
  * for `reserved` proofs holds (alloc) */
 int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, uint64_t* need, uint64_t* alloc);

@@ -38,6 +38,54 @@ int bn254_dbg_g16_plan(size_t key_inputs, int comb, size_t reserved, size_t n, s
   return BN254_OK;
 }
 
+// ... and of the compaction of the lane launches (bn254_g16_plan.h::g16_compacts / g16_compact_alloc): the walk of bn254_dbg_g16_plan for a call with `flags`; per launch
+// 6 values {compacts, first slot, slots, first block count, block counts, form}; alloc[] = {slot_proof bytes, slot_status bytes, block count bytes}
+int bn254_dbg_g16_compact_plan(size_t key_inputs, size_t reserved, size_t n, size_t n_public, unsigned flags, int n_streams, int single_stream, uint64_t alloc[3],
+                               uint64_t* out, int max_launches, int* n_launches) {
+  if (!alloc || !out || !n_launches || n_streams < 1 || n_streams > 4) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const G16CompactAlloc ca = g16_compact_alloc(g16_alloc_for(reserved, key_inputs, false).ws_proofs, key_inputs);
+  alloc[0] = ca.slot_proof_bytes; alloc[1] = ca.slot_status_bytes; alloc[2] = ca.count_bytes;
+  int k = 0;
+  for (size_t off = 0; off < n; off += G16_MAX_BATCH) {
+    const size_t m = n - off < (size_t)G16_MAX_BATCH ? n - off : (size_t)G16_MAX_BATCH;
+    G16ChunkPlan p;
+    if (!g16_plan_chunk(p, m, key_inputs, n_public, n_streams, single_stream != 0)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    for (int pi = 0; pi < p.parts; pi++) {
+      const G16Part& q = p.part[pi];
+      const G16Form f = g16_launch_form(q.count, n_public, n_public == key_inputs, p.wide, p.parts > 1, p.split_small && p.parts == 1, true, -1);
+      if (k < max_launches) {
+        uint64_t* o = out + 6 * (size_t)k;
+        o[0] = g16_compacts(f, key_inputs, (flags & BN254_FLAG_STRICT_SCALARS) != 0, (flags & BN254_FLAG_RLC) != 0) ? 1 : 0;
+        o[1] = q.first; o[2] = q.count; o[3] = q.first / G16_COMPACT_BLOCK; o[4] = (q.count + G16_COMPACT_BLOCK - 1) / G16_COMPACT_BLOCK; o[5] = (uint64_t)f.form;
+      }
+      k++;
+    }
+  }
+  *n_launches = k;
+  return BN254_OK;
+}
+// The count -> scan -> write step on the host: the counts k_g16_classify writes, then for every block what k_g16_compact_write does -- the 256 partial sums of
+// g16_compact_partial added up, the block's pending proofs ranked in order, the slots from n' on cleared
+int bn254_dbg_g16_compact(const uint8_t* pending, size_t n, unsigned* slot_proof_out, uint8_t* slot_status_out, unsigned* n_pending_out) {
+  if (!pending || !slot_proof_out || !slot_status_out || !n_pending_out || n == 0 || n > (size_t)G16_MAX_LAUNCH) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const uint32_t blocks = (uint32_t)((n + G16_COMPACT_BLOCK - 1) / G16_COMPACT_BLOCK);
+  std::vector<uint32_t> count(blocks, 0);
+  for (size_t i = 0; i < n; i++) if (pending[i]) count[i / G16_COMPACT_BLOCK]++;
+  for (uint32_t b = 0; b < blocks; b++) {
+    uint32_t before = 0, total = 0;
+    for (uint32_t t = 0; t < G16_COMPACT_BLOCK; t++) { uint32_t pb, pt; g16_compact_partial(count.data(), blocks, b, t, &pb, &pt); before += pb; total += pt; }
+    uint32_t j = before;
+    for (uint32_t t = 0; t < G16_COMPACT_BLOCK; t++) {
+      const size_t i = (size_t)b * G16_COMPACT_BLOCK + t;
+      if (i >= n) break;
+      if (pending[i]) { slot_proof_out[j] = (uint32_t)i; slot_status_out[j] = BN254_ST_PENDING; j++; }
+      if (i >= total) { slot_proof_out[i] = G16_COMPACT_NO_PROOF; slot_status_out[i] = 0; }
+    }
+    *n_pending_out = total;
+  }
+  return BN254_OK;
+}
+
 // ... and of the group status bytes of the RLC mode for a chunk of m proofs: what the launch parts address against what a context reserved for `reserved` proofs holds
 int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, uint64_t* need, uint64_t* alloc) {
   if (!need || !alloc || m == 0 || n_streams < 1 || n_streams > 4 || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > 3) return set_err(BN254_E_BAD_ARG, "bad argument");

@@ -55,6 +55,15 @@ int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n) {
   // what a reservation of n proofs needs (bn254_g16_plan.h: the same function the plan probe and its property test read)
   const G16Alloc need = g16_alloc_for(n, pvk->host.key_inputs(), pvk->host.msm_comb);
   if ((rc = d.ws.ensure(need.ws_proofs * (size_t)(G16_WS_BYTES_PER_PROOF / 4)))) return rc;
+  // launches that compact run on slots: slot -> proof, slot status bytes and the block counts, for as many proofs as the workspace holds
+  if (need.ws_proofs > d.compact_cap) {
+    const G16CompactAlloc ca = g16_compact_alloc(need.ws_proofs, pvk->host.key_inputs());
+    if (g16_key_may_compact(pvk->host.key_inputs())) {
+      d.compact_cap = 0;
+      if ((rc = d.compact.ensure((ca.slot_proof_bytes + ca.count_bytes + ca.slot_status_bytes + 3) / 4))) return rc;
+      d.compact_cap = need.ws_proofs;
+    }
+  }
   // keys with many public inputs: partial sums (and comb digits) of the public-input MSM, for the proofs of one launch.  Sized HERE (reserve /
   // the entry points call ensure_dev before they enqueue), so that the enqueue path itself never allocates or frees
   if (need.msm_part_proofs > d.msm_part_cap) {
@@ -226,6 +235,17 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
       a.msm_part = wide ? (int32_t*)d->msm_part : nullptr;
       a.msm_comb = pvk->host.msm_comb ? 1 : 0;
       a.msm_digits = (wide && pvk->host.msm_comb) ? (uint16_t*)(d->msm_part + d->msm_chunks * 27 * d->msm_part_cap) : nullptr;
+      // the slots of a launch that compacts (bn254_launch_g16 decides with g16_compacts, from the form it takes): the part's share of the three arrays, at its first
+      // proof like its share of the workspace.  The context of a key that may compact holds them for as many proofs as its workspace (ensure_dev): a smaller one is a
+      // sizing error, not a reason to run without compaction
+      a.key_inputs = pvk->host.key_inputs(); a.rlc = (flags & BN254_FLAG_RLC) ? 1 : 0;
+      if (g16_key_may_compact(a.key_inputs)) {
+        if (m > d->compact_cap) return set_err(BN254_E_BAD_ARG, "slot arrays smaller than the batch: bn254_groth16_reserve first");
+        const G16CompactAlloc ca = g16_compact_alloc(d->compact_cap, a.key_inputs);
+        a.slot_proof = (uint32_t*)d->compact + lo;
+        a.block_count = (uint32_t*)d->compact + ca.slot_proof_bytes / 4 + lo / G16_COMPACT_BLOCK;
+        a.slot_status = (uint8_t*)((uint32_t*)d->compact + (ca.slot_proof_bytes + ca.count_bytes) / 4) + lo;
+      }
       if (split_small && parts == 1) {
         a.split_streams[0] = d->aux[0]; a.split_streams[1] = d->aux[1];
         a.split_ev[0] = d->fork_ev; a.split_ev[1] = d->join_ev[1]; a.split_ev[2] = d->join_ev[2];

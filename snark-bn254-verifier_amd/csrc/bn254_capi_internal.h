@@ -77,6 +77,9 @@ struct DevState {
   DevBuf<int32_t> ws;                                               // G16_WS_BYTES_PER_PROOF per proof
   size_t ws_proofs() const { return ws.cap() / (size_t)(G16_WS_BYTES_PER_PROOF / 4); }
   DevBuf<int32_t> msm_part; size_t msm_part_cap = 0, msm_chunks = 0;                // wide keys: partial sums of the public-input MSM (proofs it holds)
+  // launches that compact (bn254_g16_plan.h::g16_compacts): slot_proof | block counts | slot_status for compact_cap proofs, sized with the workspace by ensure_dev
+  // (g16_compact_alloc); 0 for a key whose launches never compact
+  DevBuf<uint32_t> compact; size_t compact_cap = 0;
   DevBuf<uint8_t> st_proofs, st_inputs, st_status;                  // staging for the host-buffer entry point, through `ring`
   PinRing ring;                                                     // host-buffer entry: copy / compute overlap
   Event busy_ev; bool busy_valid = false;

@@ -51,6 +51,38 @@ inline G16Form g16_launch_form(size_t n, size_t n_public, bool inputs_match_key,
   return f;
 }
 
+// ---- compaction of a lane launch (k_g16_classify / k_g16_compact_write, bn254_kernels.hip) ----------------------------------------------
+// A proof the loader decides for good (a coordinate >= p, A or B off the curve) would still ride its wavefront through the Miller loop and the final
+// exponentiation.  A launch that compacts classifies first and runs k_g16_prepare and everything after it on the dense, order-preserving list of the proofs
+// still pending: slot j of the launch holds proof slot_proof[j], and the wavefronts past the list see slot status 0 and leave in their prologue.
+// Which launches: the lane form with the Miller loop as k_miller_run launches (the tail of the loop resolves a slot's status in place, and the verdict product, the
+// last launch, hands every slot's final byte to its proof through slot_proof), a key whose input sum runs inside k_g16_prepare, neither BN254_FLAG_STRICT_SCALARS
+// nor the RLC mode (its exact second pass included).  The cooperative kernels, the latency mode, wide keys and batches over many keys run as they always did.
+#define G16_COMPACT_BLOCK 256
+#define G16_COMPACT_NO_PROOF 0xffffffffu
+// the key's half of the predicate: its input sum runs inside k_g16_prepare.  What the allocator asks (a context of such a key holds the slot arrays) and what every call asks
+inline bool g16_key_may_compact(size_t key_inputs) { return key_inputs <= (size_t)G16_WIDE_MSM_MIN_INPUTS; }
+inline bool g16_compacts(const G16Form& f, size_t key_inputs, bool strict_scalars, bool rlc) {
+  return g16_key_may_compact(key_inputs) && f.form == G16_FORM_LANES && f.run_steps > 0 && !f.wide && !strict_scalars && !rlc;
+}
+// what ensure_dev allocates beside a workspace of ws_proofs proofs (a multiple of 256): slot_proof (4 B per slot), slot_status (1 B per slot) and one count of
+// pending proofs per block of 256.  A part of a chunk addresses them at its first proof (a multiple of 256), as it addresses the workspace.
+struct G16CompactAlloc { size_t slot_proof_bytes, slot_status_bytes, count_bytes; };
+inline G16CompactAlloc g16_compact_alloc(size_t ws_proofs, size_t key_inputs) {
+  G16CompactAlloc a = {0, 0, 0};
+  if (!g16_key_may_compact(key_inputs)) return a;
+  a.slot_proof_bytes = ws_proofs * sizeof(uint32_t); a.slot_status_bytes = ws_proofs;
+  a.count_bytes = (ws_proofs + G16_COMPACT_BLOCK - 1) / G16_COMPACT_BLOCK * sizeof(uint32_t);
+  return a;
+}
+// The scan step, shared by k_g16_compact_write and its host restatement (bn254_dbg_g16_compact): lane t of 256 sums the counts t, t + 256, ... below `block` into
+// *before and all of them into *total; the caller adds the 256 pairs up.  At most G16_MAX_LAUNCH / 256 = 3072 counts: twelve per lane.
+static inline __host__ __device__ void g16_compact_partial(const uint32_t* count, uint32_t blocks, uint32_t block, uint32_t t, uint32_t* before, uint32_t* total) {
+  uint32_t b = 0, a = 0;
+  for (uint32_t k = t; k < blocks; k += G16_COMPACT_BLOCK) { const uint32_t c = count[k]; a += c; if (k < block) b += c; }
+  *before = b; *total = a;
+}
+
 // ---- the form of a batch over many keys (bn254_groth16_verify_batch_keys[_device]) ---------------------------------------------------------------------------
 // From n alone: both entries know it on the host, the device entry does not know the slot count.  Up to keys_coop_max proofs (bn254_set_keys_params; never with
 // BN254_COOP=0) the DIRECT form: a slot is a proof, k_g16_prepare + k_coop12_miller_g16_keys, no grouping launches.  Otherwise the grouped lane form on

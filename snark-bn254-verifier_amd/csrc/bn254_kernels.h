@@ -48,6 +48,11 @@ struct G16LaunchArgs {
   int msm_comb = 0;         // msm_tab of a key with many inputs is in comb form
   uint16_t* msm_digits = nullptr;   // comb form: G16_COMB_COLS * n_public * n column digits (scratch)
   int part_of_larger = 0;   // this launch is one of several sub-batches of a larger batch: never the cooperative (small-batch) kernels
+  // a launch that compacts (bn254_g16_plan.h::g16_compacts, decided by bn254_launch_g16 from key_inputs, strict_scalars, rlc and the form it takes): n slot -> proof
+  // words, n slot status bytes and ceil(n / 256) block counts; nullptr: the launch never compacts
+  size_t key_inputs = 0;    // len(vk.K) - 1
+  int rlc = 0;              // the call carries BN254_FLAG_RLC (the exact second pass of the RLC mode included)
+  uint32_t* slot_proof = nullptr; uint8_t* slot_status = nullptr; uint32_t* block_count = nullptr;
   int32_t* msm_part;        // wide keys: ceil(n_public / G16_WIDE_MSM_INPUTS_PER_LANE) * 27 * n dwords of partial sums, else nullptr
   // small batches (n <= G16_SPLIT_MAX_PROOFS): two extra streams and three events (fork, join, join) let the three pairs run their
   // Miller loops as three concurrent chains (the GPU is mostly idle at such sizes: latency, not throughput, is what counts)

@@ -76,12 +76,23 @@ __global__ void __launch_bounds__(256, 2) k_f12_mul(int32_t* ws, uint32_t n, con
   vm_f12_mul(w, d, a, b, conj_b != 0);
 }
 // the last product of the final exponentiation with k_g16_compare's work as its tail (bn254_vm.h::vm_f12_mul_eq_const): the other 59 products of a batch stay k_f12_mul
-__global__ void __launch_bounds__(256, 2) k_f12_mul_verdict(int32_t* ws, uint32_t n, uint8_t* status, int d, int a, int b, const int32_t* __restrict__ target, int reject_code) {
+// slot_proof != nullptr (a launch that compacts): status holds the SLOTS' bytes, and every slot that holds a proof hands its final byte to out_status[slot_proof[slot]],
+// the caller's buffer in proof order -- the verdict, or what the tail of k_miller_run made of the slot (B outside G2, a deferred error of C, the input count; never 0,
+// which is what the slots past the list hold) -- also in a wavefront none of whose proofs is still pending (as k_f12_mul_verdict_keys does for a batch over many keys)
+__global__ void __launch_bounds__(256, 2) k_f12_mul_verdict(int32_t* ws, uint32_t n, uint8_t* status, int d, int a, int b, const int32_t* __restrict__ target, int reject_code,
+                                                            const uint32_t* __restrict__ slot_proof, uint8_t* __restrict__ out_status) {
   __shared__ int32_t park_lds[72 * 256];
-  VM_KERNEL_PROLOGUE();
-  w.lds = park_lds;
-  const bool acc = vm_f12_mul_eq_const(w, d, a, b, target);
-  if (i < n && (st & BN254_ST_PENDING)) status[i] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  const uint8_t st = status[i < n ? i : n - 1];
+  uint8_t out = st;
+  if (__builtin_amdgcn_ballot_w64((st & BN254_ST_PENDING) != 0) != 0) {
+    DevWs w(ws, n, i < n ? i : DEAD_LANE);
+    w.lds = park_lds;
+    const bool acc = vm_f12_mul_eq_const(w, d, a, b, target);
+    if (st & BN254_ST_PENDING) out = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
+    if (i < n && (st & BN254_ST_PENDING)) status[i] = out;
+  }
+  if (slot_proof && i < n && st != 0) out_status[slot_proof[i]] = out;
 }
 __global__ void __launch_bounds__(256, 2) k_f12_copy(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a) { VM_KERNEL_PROLOGUE(); vm_f12_copy(w, d, a); }
 __global__ void __launch_bounds__(256, 2) k_f12_cyclo_sqr(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a) { VM_KERNEL_PROLOGUE(); vm_f12_cyclo_sqr(w, d, a); }
@@ -102,28 +113,24 @@ __global__ void __launch_bounds__(256, 2) k_g16_compare(int32_t* ws, uint32_t n,
 // k_g16_prepare
 // =====================================================================================================================
 #define PREP_LDS_ROW 65  // 64 proof dwords + 1 pad: lane-per-proof reads hit 64 different banks
-__global__ void __launch_bounds__(256, 2)
-k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, int n_public, uint32_t n,
-              int32_t* ws, uint8_t* __restrict__ status, const int32_t* __restrict__ msm_tab, const int32_t* __restrict__ k0,
-              int inputs_match_key, int wide_msm) {
-  __shared__ uint32_t lds[4 * 64 * PREP_LDS_ROW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t first = blockIdx.x * 256u + (uint32_t)wave * 64u;
-  uint32_t* wl = lds + wave * 64 * PREP_LDS_ROW;
+// The records of the 64 lanes of a wavefront -> its LDS rows: lane j holds the index `rec` of ITS record (>= n: none, the row reads as zeros), the wavefront loads record
+// readlane(rec, j) as one 256-byte contiguous segment per load instruction.  One routine for the records in batch order (rec = the lane's own index) and for the
+// gather of a launch that compacts (rec = slot_proof of the lane's slot).
+__device__ __forceinline__ void g16_stage_records(uint32_t* wl, const uint8_t* __restrict__ proofs, size_t stride, uint32_t n, int lane, uint32_t rec_of_lane) {
   const bool aligned = ((((uintptr_t)proofs) | stride) & 3) == 0;
   if (aligned) {
-    // record j of this wave: one 256-byte contiguous segment per load instruction; SIXTEEN records per step, so that sixteen loads are in flight together (one
-    // record at a time compiled to load / wait / store: 64 dependent round trips to HBM per wavefront)
+    // SIXTEEN records per step, so that sixteen loads are in flight together (one record at a time compiled to load / wait / store: 64 dependent round trips to HBM
+    // per wavefront)
     for (int j0 = 0; j0 < 64; j0 += 16) {
       uint32_t v[16];
 #pragma unroll
-      for (int u = 0; u < 16; u++) { const uint32_t rec = first + (uint32_t)(j0 + u); v[u] = rec < n ? *(const uint32_t*)(proofs + (size_t)rec * stride + (size_t)lane * 4) : 0u; }
+      for (int u = 0; u < 16; u++) { const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)rec_of_lane, j0 + u); v[u] = rec < n ? *(const uint32_t*)(proofs + (size_t)rec * stride + (size_t)lane * 4) : 0u; }
 #pragma unroll
       for (int u = 0; u < 16; u++) wl[(j0 + u) * PREP_LDS_ROW + lane] = v[u];
     }
   } else {
     for (int j = 0; j < 64; j++) {
-      uint32_t rec = first + j;
+      const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)rec_of_lane, j);
       uint32_t v = 0;
       if (rec < n) {
         const uint8_t* p = proofs + (size_t)rec * stride + (size_t)lane * 4;
@@ -132,31 +139,23 @@ k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* 
       wl[j * PREP_LDS_ROW + lane] = v;
     }
   }
-  __syncthreads();
-  const uint32_t i = first + lane;
-  const bool live = i < n;
-  const uint32_t ii = live ? i : n - 1;
-  // dead lanes get an out-of-range lane offset: the descriptor's bounds check drops their stores
-  DevWs w(ws, n, live ? i : DEAD_LANE);
-  const uint32_t* my = wl + lane * PREP_LDS_ROW;
+}
+// The loader's checks of A and of B from a lane's LDS row (my: the record's 64 dwords): the first error in the reference's order, A, then B (member, curve); 0: none.
+// k_g16_prepare and k_g16_classify both decide through these two, so a proof the one calls decided is decided the same way by the other.
+__device__ __forceinline__ int g16_parse_a(const uint32_t* my, G1Aff& A) {
   uint32_t d[8], wx[8], wy[8];
-  int err = 0;       // first error in the reference's order: A, then B (member, curve), B subgroup (next kernel), then C
-  int err_c = 0;
-
-  // ---- A
 #pragma unroll
   for (int k = 0; k < 8; k++) d[k] = my[k];
   be_field_to_words(wx, d);
 #pragma unroll
   for (int k = 0; k < 8; k++) d[k] = my[8 + k];
   be_field_to_words(wy, d);
-  bool memb = words_lt_p(wx) & words_lt_p(wy);
-  G1Aff A; A.x = fp_from_words(wx); A.y = fp_from_words(wy);
-  if (!memb) err = BN254_ST_NOT_MEMBER; else if (!g1_on_curve(A)) err = BN254_ST_NOT_ON_CURVE;
-  w.st(VE_AX, A.x); w.st(VE_AY, A.y);
-
-  // ---- B : x.c1 | x.c0 | y.c1 | y.c0
-  G2Aff B;
+  const bool memb = words_lt_p(wx) & words_lt_p(wy);
+  A.x = fp_from_words(wx); A.y = fp_from_words(wy);
+  return !memb ? BN254_ST_NOT_MEMBER : !g1_on_curve(A) ? BN254_ST_NOT_ON_CURVE : 0;
+}
+__device__ __forceinline__ int g16_parse_b(const uint32_t* my, G2Aff& B, int err) {   // B : x.c1 | x.c0 | y.c1 | y.c0
+  uint32_t d[8], wx[8];
   bool membb = true;
 #pragma unroll
   for (int k = 0; k < 8; k++) d[k] = my[16 + k];
@@ -171,6 +170,96 @@ k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* 
   for (int k = 0; k < 8; k++) d[k] = my[40 + k];
   be_field_to_words(wx, d); membb &= words_lt_p(wx); B.y.c0 = fp_from_words(wx);
   if (err == 0) { if (!membb) err = BN254_ST_NOT_MEMBER; else if (!g2_on_curve(B)) err = BN254_ST_NOT_ON_CURVE; }
+  return err;
+}
+
+// ---- compaction (bn254_g16_plan.h::g16_compacts): classify, then count -> scan -> write ------------------------------------------------------------------------------
+// k_g16_classify, one proof per lane: the loader checks whose outcome is FINAL -- the range and curve checks of A and B, through the helpers and in the order of
+// k_g16_prepare; the checks of C are deferred there (the r-torsion test of B ranks ahead of them) and do not run here.  status[i], the CALLER's byte, becomes the
+// final status of a decided proof and BN254_ST_PENDING otherwise (so the buffer never keeps a byte of an earlier batch); block_count[b] = pending proofs of block b.
+__global__ void __launch_bounds__(256, 2)
+k_g16_classify(const uint8_t* __restrict__ proofs, size_t stride, uint32_t n, uint8_t* __restrict__ status, uint32_t* __restrict__ block_count) {
+  __shared__ uint32_t lds[4 * 64 * PREP_LDS_ROW];
+  __shared__ uint32_t wave_pending[4];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t first = blockIdx.x * 256u + (uint32_t)wave * 64u;
+  uint32_t* wl = lds + wave * 64 * PREP_LDS_ROW;
+  const uint32_t i = first + lane;
+  const bool live = i < n;
+  g16_stage_records(wl, proofs, stride, n, lane, i);
+  __syncthreads();
+  G1Aff A; G2Aff B;
+  int err = g16_parse_a(wl + lane * PREP_LDS_ROW, A);
+  err = g16_parse_b(wl + lane * PREP_LDS_ROW, B, err);
+  if (live) status[i] = err ? (uint8_t)err : (uint8_t)BN254_ST_PENDING;
+  const uint64_t pend = __builtin_amdgcn_ballot_w64(live && err == 0);
+  if (lane == 0) wave_pending[wave] = (uint32_t)__builtin_popcountll(pend);
+  __syncthreads();
+  if (threadIdx.x == 0) block_count[blockIdx.x] = wave_pending[0] + wave_pending[1] + wave_pending[2] + wave_pending[3];
+}
+// k_g16_compact_write, the grid of k_g16_classify: every block scans the (at most 3072) block counts for itself -- the pending proofs before it and in the whole
+// launch, n' -- ranks its own pending proofs in order, and writes slot_proof[j] = proof of slot j, slot_status[j] = PENDING for j < n'; the lane of slot j >= n'
+// writes slot_status[j] = 0 (no later kernel works on it) and slot_proof[j] = no proof.  Order-preserving and the same on every run: no slot is taken by an atomic.
+__global__ void __launch_bounds__(256)
+k_g16_compact_write(const uint8_t* __restrict__ status, uint32_t n, const uint32_t* __restrict__ block_count, uint32_t* __restrict__ slot_proof, uint8_t* __restrict__ slot_status) {
+  __shared__ uint32_t s_before[G16_COMPACT_BLOCK], s_total[G16_COMPACT_BLOCK], wave_pending[4];
+  const uint32_t t = threadIdx.x, wave = t >> 6, lane = t & 63u;
+  uint32_t before, total;
+  g16_compact_partial(block_count, gridDim.x, blockIdx.x, t, &before, &total);
+  s_before[t] = before; s_total[t] = total;
+  const uint32_t i = blockIdx.x * 256u + t;
+  const bool pend = i < n && status[i] == BN254_ST_PENDING;
+  const uint64_t mask = __builtin_amdgcn_ballot_w64(pend);
+  if (lane == 0) wave_pending[wave] = (uint32_t)__builtin_popcountll(mask);
+  __syncthreads();
+  for (uint32_t d = G16_COMPACT_BLOCK / 2; d > 0; d >>= 1) {
+    if (t < d) { s_before[t] += s_before[t + d]; s_total[t] += s_total[t + d]; }
+    __syncthreads();
+  }
+  const uint32_t n_pending = s_total[0];
+  uint32_t j = s_before[0] + (uint32_t)__builtin_popcountll(mask & ((1ull << lane) - 1ull));
+  for (uint32_t k = 0; k < wave; k++) j += wave_pending[k];
+  if (pend && j < n) { slot_proof[j] = i; slot_status[j] = BN254_ST_PENDING; }
+  if (i < n && i >= n_pending) { slot_proof[i] = G16_COMPACT_NO_PROOF; slot_status[i] = 0; }
+}
+
+// slot_proof != nullptr, a launch that compacts: the kernel works on SLOT i -- the record and the inputs of proof slot_proof[i], workspace column i, and its status
+// byte goes to slot_status[i], which k_g16_compact_write has set (PENDING below n', 0 from there on: such a wavefront has nothing to do).  The staging is then a
+// gather of whole 256-byte records, still one segment per load instruction.
+__global__ void __launch_bounds__(256, 2)
+k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, int n_public, uint32_t n,
+              int32_t* ws, uint8_t* __restrict__ status, const int32_t* __restrict__ msm_tab, const int32_t* __restrict__ k0,
+              int inputs_match_key, int wide_msm, const uint32_t* __restrict__ slot_proof, uint8_t* __restrict__ slot_status) {
+  __shared__ uint32_t lds[4 * 64 * PREP_LDS_ROW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const uint32_t first = blockIdx.x * 256u + (uint32_t)wave * 64u;
+  uint32_t* wl = lds + wave * 64 * PREP_LDS_ROW;
+  uint32_t pi = first + (uint32_t)lane;     // the proof of this lane
+  bool wave_live = true;
+  if (slot_proof) {
+    const bool slot_live = pi < n && (slot_status[pi] & BN254_ST_PENDING) != 0;
+    pi = slot_live ? slot_proof[pi] : G16_COMPACT_NO_PROOF;
+    wave_live = __builtin_amdgcn_ballot_w64(slot_live) != 0;
+  }
+  if (wave_live) g16_stage_records(wl, proofs, stride, n, lane, pi);
+  __syncthreads();
+  if (!wave_live) return;
+  uint8_t* const st_out = slot_proof ? slot_status : status;
+  const uint32_t i = first + lane;
+  const bool live = pi < n;
+  const uint32_t ii = live ? pi : n - 1;
+  // dead lanes get an out-of-range lane offset: the descriptor's bounds check drops their stores
+  DevWs w(ws, n, live ? i : DEAD_LANE);
+  const uint32_t* my = wl + lane * PREP_LDS_ROW;
+  uint32_t d[8], wx[8], wy[8];
+  int err_c = 0;
+
+  // ---- A, then B: the first error in the reference's order -- A, then B (member, curve), B subgroup (the Miller loop's tail), then C
+  G1Aff A;
+  int err = g16_parse_a(my, A);
+  w.st(VE_AX, A.x); w.st(VE_AY, A.y);
+  G2Aff B;
+  err = g16_parse_b(my, B, err);
   vst2(w, VE_B, B.x); vst2(w, VE_B + 2, B.y);
 
   // ---- C
@@ -180,7 +269,7 @@ k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* 
 #pragma unroll
   for (int k = 0; k < 8; k++) d[k] = my[56 + k];
   be_field_to_words(wy, d);
-  memb = words_lt_p(wx) & words_lt_p(wy);
+  const bool memb = words_lt_p(wx) & words_lt_p(wy);
   G1Aff C; C.x = fp_from_words(wx); C.y = fp_from_words(wy);
   if (!memb) err_c = BN254_ST_NOT_MEMBER; else if (!g1_on_curve(C)) err_c = BN254_ST_NOT_ON_CURVE;
   w.st(VE_CX, C.x); w.st(VE_CY, C.y);
@@ -188,7 +277,7 @@ k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* 
   // ---- L = K0 + sum_i x_i K_i, x_i taken as raw 256-bit integers (no range check, as bn::Fr::from_slice)
   if (wide_msm) {
     // many public inputs: L comes from k_g16_msm_partial / k_g16_msm_reduce (they also set the identity flag)
-    if (live) status[i] = err ? (uint8_t)err : (uint8_t)(BN254_ST_PENDING | err_c);
+    if (live) st_out[i] = err ? (uint8_t)err : (uint8_t)(BN254_ST_PENDING | err_c);
     return;
   }
   G1Aff K0; K0.x = uni_ld(k0); K0.y = uni_ld(k0 + BN_NL);
@@ -234,7 +323,7 @@ k_g16_prepare(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* 
   G1Aff La = g1_to_affine(L);
   La.y = fp_select(l_inf, fp_one(), La.y);
   w.st(VE_LX, La.x); w.st(VE_LY, La.y);
-  if (live) status[i] = err ? (uint8_t)err : (uint8_t)(BN254_ST_PENDING | (l_inf ? BN254_ST_LINF : 0) | err_c);
+  if (live) st_out[i] = err ? (uint8_t)err : (uint8_t)(BN254_ST_PENDING | (l_inf ? BN254_ST_LINF : 0) | err_c);
 }
 
 // BN254_FLAG_STRICT_SCALARS: a public input >= r makes the proof's status NOT_MEMBER, ahead of every other outcome (the
@@ -896,7 +985,20 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
   const G16Form form = g16_launch_form(a.n, (size_t)a.n_public, a.inputs_match_key != 0, a.msm_part != nullptr, a.part_of_larger != 0,
                                        a.split_streams[0] && a.split_streams[1], coop_on, run_steps_env);
   const bool wide = form.wide, coop = form.form == G16_FORM_COOP;
-  BN_LAUNCH(KID_PREPARE, k_g16_prepare, a.proofs, a.stride, a.inputs, a.n_public, n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, (wide || coop) ? 1 : 0);
+  // a launch that compacts (bn254_g16_plan.h): classify, count -> scan -> write, and from k_g16_prepare on every kernel works on the slots of the proofs still pending
+  const bool compact = a.slot_proof && a.slot_status && a.block_count && g16_compacts(form, a.key_inputs, a.strict_scalars != 0, a.rlc != 0);
+  uint8_t* const lane_status = compact ? a.slot_status : a.status;     // the status bytes the lane kernels read: the slots', or the caller's
+  const uint32_t* const slot_proof = compact ? a.slot_proof : nullptr;
+  {
+    // ONE profile scope, KID_PREPARE: the two launches of the compaction are part of what the loader costs, and the per-kernel profile shows them there
+    ProfScope ps_(prof, KID_PREPARE, s);
+    if (compact) {
+      hipLaunchKernelGGL(k_g16_classify, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, n, a.status, a.block_count);
+      hipLaunchKernelGGL(k_g16_compact_write, dim3(grid), dim3(256), 0, s, (const uint8_t*)a.status, n, (const uint32_t*)a.block_count, a.slot_proof, a.slot_status);
+    }
+    hipLaunchKernelGGL(k_g16_prepare, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.n_public, n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, (wide || coop) ? 1 : 0,
+                       slot_proof, a.slot_status);
+  }
   if (a.strict_scalars && a.n_public > 0) hipLaunchKernelGGL(k_g16_check_scalars, dim3(grid), dim3(256), 0, s, a.inputs, a.n_public, n, a.status);
   if (wide) {
     // inputs of one proof spread over `chunks` lanes, proofs in slices that fit the partial-sum buffer
@@ -931,7 +1033,7 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
     if (ev) { (void)hipEventRecord(ev[2], s); (void)hipEventRecord(ev[3], s); (void)hipEventRecord(ev[4], s); }
     return hipGetLastError();
   }
-  LaunchOps ops{a.ws, n, a.status, grid, s, {a.gtab, a.dtab, nullptr}, prof};
+  LaunchOps ops{a.ws, n, lane_status, grid, s, {a.gtab, a.dtab, nullptr}, prof};
   // The throughput form (the Miller loop as k_miller_run launches) has no k_vm_init, k_g16_subgroup or k_g16_compare: the run that starts at step 0 sets f = 1 and
   // T = (B, 1), the run that ends the loop tests B's subgroup on the point it has just produced and resolves the deferred statuses, and the last product of the final
   // exponentiation compares with e(alpha, beta) -- whichever launches of the plan (88, 44, 22 or 11 steps each) those are.  The latency mode and the one-launch-per-step
@@ -974,7 +1076,7 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
   if (ev) (void)hipEventRecord(ev[3], s);
   if (folded) {
     vm_final_exp_program_head(ops);
-    BN_LAUNCH(KID_F12_MUL, k_f12_mul_verdict, a.ws, n, a.status, (int)VE_S0, (int)VE_S2, (int)VE_S0, a.target, BN254_ST_REJECT);
+    BN_LAUNCH(KID_F12_MUL, k_f12_mul_verdict, a.ws, n, lane_status, (int)VE_S0, (int)VE_S2, (int)VE_S0, a.target, BN254_ST_REJECT, slot_proof, a.status);
   } else {
     vm_final_exp_program(ops);
     BN_LAUNCH(KID_COMPARE, k_g16_compare, a.ws, n, a.status, a.target, BN254_ST_REJECT);
@@ -1005,7 +1107,8 @@ hipError_t bn254_launch_g16_keys(const G16KeysLaunchArgs& a, hipStream_t s) {
 hipError_t bn254_launch_g16_keys_direct(const G16KeysDirectArgs& a, hipStream_t s) {
   const uint32_t n = (uint32_t)a.n;
   // wide_msm = 1: the kernel returns after C and never reads the inputs, the tables or K0
-  hipLaunchKernelGGL(k_g16_prepare, dim3(grid_for(a.n)), dim3(256), 0, s, a.proofs, a.stride, a.inputs, 0, n, a.ws, a.status, (const int32_t*)nullptr, (const int32_t*)nullptr, 1, 1);
+  hipLaunchKernelGGL(k_g16_prepare, dim3(grid_for(a.n)), dim3(256), 0, s, a.proofs, a.stride, a.inputs, 0, n, a.ws, a.status, (const int32_t*)nullptr, (const int32_t*)nullptr, 1, 1,
+                     (const uint32_t*)nullptr, (uint8_t*)nullptr);
   return bn254_coop12_miller_g16_keys(a.ws, a.status, a.n, a.key_index, a.desc, a.n_keys, a.inputs, a.input_stride, a.strict_scalars, s);
 }
 
@@ -1018,7 +1121,7 @@ hipError_t bn254_launch_g16_rlc(const G16LaunchArgs& a, const RlcLaunchArgs& r, 
   for (int i = 0; i < 8; i++) key.k[i] = r.key[i];
   for (int i = 0; i < 3; i++) key.nonce[i] = r.key[8 + i];
   // parse + checks; the public-input MSM is skipped (done once per group): the wide flag of k_g16_prepare returns before it
-  BN_LAUNCH(KID_PREPARE, k_g16_prepare, a.proofs, a.stride, a.inputs, a.n_public, n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, 1);
+  BN_LAUNCH(KID_PREPARE, k_g16_prepare, a.proofs, a.stride, a.inputs, a.n_public, n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, 1, (const uint32_t*)nullptr, (uint8_t*)nullptr);
   if (a.strict_scalars && a.n_public > 0) hipLaunchKernelGGL(k_g16_check_scalars, dim3(grid), dim3(256), 0, s, a.inputs, a.n_public, n, a.status);
   LaunchOps ops{a.ws, n, a.status, grid, s, {nullptr, nullptr, nullptr}, nullptr};
   BN_LAUNCH(KID_VM_INIT, k_vm_init, a.ws, n, (const uint8_t*)a.status);
