@@ -124,6 +124,30 @@ void bn254_groth16_vk_free(bn254_g16_pvk* pvk);
 /* number of public inputs the key expects (len(vk.K) - 1); SIZE_MAX for a key without K points: no input count satisfies groth16/verify.rs:54 */
 size_t bn254_groth16_vk_num_public(const bn254_g16_pvk* pvk);
 
+/* ---- Many keys prepared in one call ---------------------------------------------------------------------------------------------------------------
+ * bn254_groth16_vk_prepare for n_keys keys at once, with the per-key work on `device` (csrc/bn254_k_vkprep.hip): the compressed points of all keys are decoded one
+ * per lane, the two line tables of a key are walked projectively with ONE inversion per table (one lane per table), and e(alpha, beta) of all keys runs through the
+ * one-pair pairing program.  What a caller with a list for bn254_groth16_verify_batch_keys does before its first batch.
+ *   Definition of correctness.  For every i, key_status[i] is the return code of bn254_groth16_vk_prepare(vks[i], vk_lens[i], mode, &h): BN254_OK or BN254_E_VK.
+ *   out[i] is NULL for a key that does not load; otherwise it is a handle indistinguishable from h: its host image (bn254_dbg_g16_pvk_image) is equal dword for dword
+ *   and every entry point gives the same status bytes with it.  A key that fails does not disturb its neighbours.  The handles are independent of each other and of the
+ *   call: each is freed with bn254_groth16_vk_free, in any order, and may share a key list with handles of the single-key function.
+ *   Return value (infrastructure only): BN254_OK even when some keys fail.  BN254_E_BAD_ARG for a null pointer with n_keys > 0, a null vks[i] or mode > 1 -- reported
+ *   before any device is touched.  n_keys == 0 returns BN254_OK and looks at nothing.  BN254_E_NO_DEVICE, BN254_E_HIP, BN254_E_NOMEM as elsewhere; on any negative
+ *   return every out[i] is NULL and nothing is leaked.  There is no CPU fallback, as everywhere else in the library; with BN254_TABLES_HOST=1 in the environment
+ *   (the host construction of every table) the entry loops over bn254_groth16_vk_prepare and needs no device.
+ *   Behaviour.  Host-synchronous, on a stream of its own; safe from several host threads at once.  It touches no key's per-device state and builds no K-point tables:
+ *   those stay lazy (bn254_groth16_reserve, the first batch), as for a handle of the single-key function.  The list is worked through in passes of at most 4096 keys
+ *   and 2^18 compressed G1 points (a key with more points is a pass of its own), so the device scratch is bounded whatever n_keys is: 176 MB of line tables and
+ *   pairing workspace at 4096 keys plus 104 bytes per G1 point, and as much pinned host memory for the way back; freed when the call returns.  Keys whose structure
+ *   does not scan (a K count or a commitment-index count larger than the bytes that are there, a missing trailer) are refused on the host and never reach the device.
+ *   Cost (one MI355X, profiles/r11_vk_prepare_batch.txt): a call costs 14 ms whatever the list holds up to a few hundred keys -- 9.2 ms of it the
+ *   pairing program, a chain of small launches, 2.5 ms the line tables -- and grows from there: 1 key 14 ms, 256 keys 18 ms, 4096 keys 70 ms, 65 536 keys 0.74 s
+ *   (17 / 11 us a key), 16 keys of 1024 inputs 15 ms.  The same keys through bn254_groth16_vk_prepare on that box, 1.6 ms a key: 4096 keys 6.5 s on one host thread and
+ *   0.43 s on 16, 65 536 keys 104 s and 8.2 s.  CROSSOVER: against a loop on one host thread (a C or Rust caller) the batch entry wins from 16 two-input keys on (8
+ *   keys: 14.5 ms against 12.7 ms), against a loop spread over 16 host threads from 256 keys on (64 keys: 15.7 ms against 11.1 ms).  Below that, prepare key by key. */
+int bn254_groth16_vk_prepare_batch(const uint8_t* const* vks, const size_t* vk_lens, size_t n_keys, unsigned mode, int device, bn254_g16_pvk** out, int* key_status);
+
 /* verify_batch on host buffers.  proofs: n records of proof_stride bytes (>= 256; bytes beyond 256 -- gnark's commitment
  * count / commitments / PoK -- are ignored exactly as in groth16/converter.rs:15-25; with BN254_FLAG_COMPRESSED_PROOFS: gnark's compressed
  * proof, >= 128 bytes, bytes beyond 128 ignored).  public_inputs: n * n_public * 32 bytes,
@@ -488,11 +512,20 @@ int bn254_dbg_g16_keys_group(const unsigned* key_index, size_t n, size_t n_keys,
 int bn254_dbg_g16_keys_plan(size_t n, size_t n_keys, int* form, size_t* slots, int* launches);
 /* the form of the last batch enqueued on the cached state of (list, device): 0 or 1 as above, -1 if there was none (also: the list is not cached) */
 int bn254_dbg_g16_keys_last_form(const bn254_g16_pvk* const* pvks, size_t n_keys, int device, int* form);
+/* the host image of a prepared Groth16 key, serialised: dwords n_k (2) | msm_comb | k0, gtab, dtab, target, kpts, each as its length and its dwords | alpha (18),
+ * k0_pt (18), b_arg (36) as canonical digits.  Two handles of one key are interchangeable iff their images are equal.  *len: bytes of the image (always written);
+ * a null or too small out (cap bytes) is BN254_E_BAD_ARG */
+int bn254_dbg_g16_pvk_image(const bn254_g16_pvk* pvk, uint8_t* out, size_t cap, size_t* len);
+/* bn254_groth16_vk_prepare_batch with a choice of where the bodies of its kernels run (csrc/bn254_vkprep.h): device -1 is their host compile -- no device is touched,
+ * e(alpha, beta) by the host's Miller loop -- a device ordinal the kernels.  stage_ms: null, or 5 floats: G1 decode, G2 decode, fold, line tables, pairing program,
+ * summed over the passes, from HIP events (zero on the host) */
+int bn254_dbg_g16_vk_prepare_batch(const uint8_t* const* vks, const size_t* vk_lens, size_t n_keys, unsigned mode, int device, bn254_g16_pvk** out, int* key_status,
+                                   float* stage_ms);
 int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t* mismatches);   /* the window tables of a PlonK key's points (csrc/bn254_fw.h): every window's first, middle and last entries and a pseudo-random sample */
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys, bn254_set_keys_params -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

@@ -24,6 +24,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <memory>
 #include <vector>
 #include "bn254_verify.h"
 
@@ -183,12 +184,27 @@ class PreparedGroth16Vk {
     detail::check(bn254_groth16_verify_batch_device(h_, d_proofs, stride, d_public_inputs, n_public, n, d_status, device, hip_stream, flags));
   }
   void reserve(size_t n, int device = 0) const { detail::check(bn254_groth16_reserve(h_, n, device)); }
+  // takes over a handle the library made (Groth16Verifier::prepare_batch)
+  static PreparedGroth16Vk adopt(bn254_g16_pvk* h) { PreparedGroth16Vk k; k.h_ = h; return k; }
 
  private:
+  PreparedGroth16Vk() = default;
   bn254_g16_pvk* h_ = nullptr;
 };
 
 struct Groth16Verifier {
+  // Many keys prepared in one call, on `device` (bn254_groth16_vk_prepare_batch): entry i is the prepared key vks[i], equal to PreparedGroth16Vk(vks[i], mode) in
+  // everything a caller can observe, or empty for a key that does not load (where the single-key constructor throws Panic).  The keys are independent of each other.
+  static std::vector<std::unique_ptr<PreparedGroth16Vk>> prepare_batch(const std::vector<Bytes>& vks, unsigned mode = BN254_VK_REFERENCE, int device = 0) {
+    const size_t n = vks.size();
+    std::vector<const uint8_t*> ptrs(n); std::vector<size_t> lens(n); std::vector<bn254_g16_pvk*> out(n, nullptr); std::vector<int> status(n, 0);
+    static const uint8_t none = 0;
+    for (size_t i = 0; i < n; i++) { ptrs[i] = vks[i].empty() ? &none : vks[i].data(); lens[i] = vks[i].size(); }
+    detail::check(bn254_groth16_vk_prepare_batch(ptrs.data(), lens.data(), n, mode, device, out.data(), status.data()));
+    std::vector<std::unique_ptr<PreparedGroth16Vk>> keys(n);
+    for (size_t i = 0; i < n; i++) if (out[i]) keys[i].reset(new PreparedGroth16Vk(PreparedGroth16Vk::adopt(out[i])));
+    return keys;
+  }
   // lib.rs:44-49
   static Result<bool, Groth16Error> verify(const Bytes& proof, const Bytes& vk, const std::vector<Fr>& public_inputs, unsigned mode = BN254_VK_REFERENCE) {
     uint8_t st = 0xEE;

@@ -89,6 +89,17 @@ impl PreparedGroth16Vk {
         check(unsafe { sys::bn254_groth16_vk_prepare(vk.as_ptr(), vk.len(), mode as u32, &mut h) })?;
         Ok(Self { h })
     }
+    /// Many keys prepared in one call, on `device` (`bn254_groth16_vk_prepare_batch`): entry `i` is `vks[i]` prepared -- equal to `new(vks[i], mode)` in everything a
+    /// caller can observe -- or `None` for a key that does not load (where `new` answers `BN254_E_VK`).  The keys are independent: each is dropped on its own.
+    pub fn prepare_batch(vks: &[&[u8]], mode: VkMode, device: i32) -> Result<Vec<Option<Self>>, Error> {
+        static NONE: u8 = 0;
+        let ptrs: Vec<*const u8> = vks.iter().map(|v| if v.is_empty() { &NONE as *const u8 } else { v.as_ptr() }).collect();
+        let lens: Vec<usize> = vks.iter().map(|v| v.len()).collect();
+        let mut out: Vec<*mut sys::Bn254G16Pvk> = vec![core::ptr::null_mut(); vks.len()];
+        let mut status: Vec<c_int> = vec![0; vks.len()];
+        check(unsafe { sys::bn254_groth16_vk_prepare_batch(ptrs.as_ptr() as *mut *const u8, lens.as_ptr(), vks.len(), mode as u32, device, out.as_mut_ptr(), status.as_mut_ptr()) })?;
+        Ok(out.into_iter().map(|h| if h.is_null() { None } else { Some(Self { h }) }).collect())
+    }
     pub fn num_public(&self) -> usize { unsafe { sys::bn254_groth16_vk_num_public(self.h) } }
     /// Allocations ahead of the first batch (otherwise the first call makes them).
     pub fn reserve(&self, n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_groth16_reserve(self.h, n, device) }) }

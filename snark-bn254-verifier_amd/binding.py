@@ -480,6 +480,65 @@ class PreparedVk:
             pass
 
 
+def _adopt_vk(handle):
+    """A PreparedVk around a handle the library already made (prepare_vks)."""
+    k = PreparedVk.__new__(PreparedVk)
+    k._h = C.c_void_p(handle)
+    k.n_public = lib().bn254_groth16_vk_num_public(k._h)
+    return k
+
+
+def _prepare_vks_call(fn, vks, mode, device, extra=()):
+    vks = [bytes(v) for v in vks]
+    n = len(vks)
+    ptrs = (C.c_char_p * max(n, 1))(*vks)
+    lens = (C.c_size_t * max(n, 1))(*[len(v) for v in vks])
+    out = (C.c_void_p * max(n, 1))()
+    status = (C.c_int * max(n, 1))()
+    try:
+        _check(fn(ptrs, lens, n, mode, device, out, status, *extra))
+    except Exception:
+        for h in out[:n]:
+            if h:
+                lib().bn254_groth16_vk_free(h)
+        raise
+    return [_adopt_vk(out[i]) if out[i] else None for i in range(n)], [int(status[i]) for i in range(n)]
+
+
+def prepare_vks(vks, mode=VK_REFERENCE, device=0, with_status=False):
+    """Many Groth16 verifying keys prepared in one call, on `device` (bn254_groth16_vk_prepare_batch): a list with a PreparedVk per key that loads and None per key
+    that does not -- each handle equal to PreparedVk(vk, mode) in everything a caller can observe, independent of the others.  with_status: also the per-key return
+    codes (0, or -4 for a key that does not load), as a second list."""
+    fn = lib().bn254_groth16_vk_prepare_batch
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.c_void_p]
+    keys, status = _prepare_vks_call(fn, vks, mode, device)
+    return (keys, status) if with_status else keys
+
+
+def dbg_prepare_vks(vks, mode=VK_REFERENCE, device=-1):
+    """prepare_vks through the probe (bn254_dbg_g16_vk_prepare_batch): device -1 runs the kernels' bodies compiled for the host (csrc/bn254_vkprep.h) and touches no
+    GPU.  Returns (keys, status, stage_ms) -- stage_ms: G1 decode, G2 decode, fold, line tables, pairing of the device passes, from HIP events."""
+    fn = lib().bn254_dbg_g16_vk_prepare_batch
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    ms = (C.c_float * 5)()
+    keys, status = _prepare_vks_call(fn, vks, mode, device, (ms,))
+    return keys, status, dict(zip(VK_PREPARE_STAGES, [float(x) for x in ms]))
+
+
+VK_PREPARE_STAGES = ("k_vkp_dec_g1", "k_vkp_dec_g2", "k_vkp_fold", "k_vkp_lines", "pairing_program")
+
+
+def dbg_pvk_image(key):
+    """The host image of a prepared Groth16 key as bytes (bn254_dbg_g16_pvk_image): two handles of one key are interchangeable iff their images are equal."""
+    fn = lib().bn254_dbg_g16_pvk_image
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    ln = C.c_size_t(0)
+    fn(key.handle, None, 0, C.byref(ln))
+    buf = (C.c_uint8 * max(ln.value, 1))()
+    _check(fn(key.handle, buf, ln.value, C.byref(ln)))
+    return bytes(buf)[:ln.value]
+
+
 class KeySet:
     """A list of prepared Groth16 keys for batches over many keys (bn254_groth16_verify_batch_keys): proof i is verified against keys[key_index[i]].  keys: PreparedVk
     objects (one may occur more than once); the list keeps them alive.  Keys with more than 16 public inputs are refused by the library."""

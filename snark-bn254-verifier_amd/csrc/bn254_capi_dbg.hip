@@ -199,6 +199,36 @@ int bn254_dbg_rlc_wide_group(const uint8_t* kpts, const uint8_t alpha64[64], con
   return BN254_OK;
 }
 
+// The host image of a prepared Groth16 key, for the tests that hold two handles of the same key against each other (bn254_groth16_vk_prepare_batch against
+// bn254_groth16_vk_prepare): dwords n_k (2) | msm_comb | then k0, gtab, dtab, target, kpts, each as its length and its dwords | alpha (18), k0_pt (18), b_arg (36) as
+// canonical digits.  *len: the bytes the image takes (written whenever the pointer is given); out may be null or too small (cap): BN254_E_BAD_ARG then.
+int bn254_dbg_g16_pvk_image(const bn254_g16_pvk* pvk, uint8_t* out, size_t cap, size_t* len) {
+  if (!pvk || !len) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const G16Prepared& h = pvk->host;
+  std::vector<int32_t> im;
+  im.push_back((int32_t)(uint32_t)h.n_k); im.push_back((int32_t)(uint32_t)((uint64_t)h.n_k >> 32)); im.push_back(h.msm_comb ? 1 : 0);
+  for (const std::vector<int32_t>* v : {&h.k0, &h.gtab, &h.dtab, &h.target, &h.kpts}) { im.push_back((int32_t)v->size()); im.insert(im.end(), v->begin(), v->end()); }
+  int32_t d[2 * BN_NL];
+  fp_to_limbs(d, h.alpha.x); fp_to_limbs(d + BN_NL, h.alpha.y); im.insert(im.end(), d, d + 2 * BN_NL);
+  fp_to_limbs(d, h.k0_pt.x); fp_to_limbs(d + BN_NL, h.k0_pt.y); im.insert(im.end(), d, d + 2 * BN_NL);
+  put_fp2(d, h.b_arg.x); im.insert(im.end(), d, d + 2 * BN_NL);
+  put_fp2(d, h.b_arg.y); im.insert(im.end(), d, d + 2 * BN_NL);
+  *len = im.size() * 4;
+  if (!out || cap < *len) return set_err(BN254_E_BAD_ARG, "image buffer too small");
+  memcpy(out, im.data(), *len);
+  return BN254_OK;
+}
+// bn254_groth16_vk_prepare_batch with a choice of where the kernels' bodies run: device -1 is their host compile (csrc/bn254_vkprep.h; no device is touched), a device
+// ordinal the kernels.  stage_ms: null, or 5 floats -- G1 decode, G2 decode, fold, line tables, pairing, summed over the passes, from HIP events (zero on the host).
+// (bn254_capi_vkbatch.hip is not part of the one-translation-unit host build: a harness that includes it defines BN254_HOSTSAN_VKBATCH.)
+#if defined(__HIPCC__) || defined(BN254_HOSTSAN_VKBATCH)
+int bn254_dbg_g16_vk_prepare_batch(const uint8_t* const* vks, const size_t* vk_lens, size_t n_keys, unsigned mode, int device, bn254_g16_pvk** out, int* key_status,
+                                   float* stage_ms) {
+  if (device < -1) return set_err(BN254_E_BAD_ARG, "bad argument");
+  return vkp_prepare_batch(vks, vk_lens, n_keys, mode, device == -1, device, out, key_status, stage_ms);
+}
+#endif
+
 // ---------------------------------------------------------------- device-arithmetic probes (tests)
 static int run_probe(size_t in_a, size_t in_b, size_t out_sz, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int device,
                      hipError_t (*launch)(const uint8_t*, const uint8_t*, uint8_t*, size_t)) {

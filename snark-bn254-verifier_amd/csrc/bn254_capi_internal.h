@@ -235,6 +235,10 @@ void keys_sets_drop(const bn254_g16_pvk* member);   // bn254_capi_keys.hip: forg
 void parallel_copy(uint8_t* dst, const uint8_t* src, size_t bytes);
 int build_tables_on_device(int form, const std::vector<int32_t>& pts, DevBuf<int32_t>& dst);
 int sub_batch_streams();                   // BN254_STREAMS, read once: sub-batches of a Groth16 chunk in flight, 1 .. 4 (default 2)
+// bn254_capi_vkbatch.hip: bn254_groth16_vk_prepare_batch and its probe (on_host: the kernels' bodies compiled for the host, no device touched; stage_ms: null or
+// the five per-stage times of the device passes)
+int vkp_prepare_batch(const uint8_t* const* vks, const size_t* vk_lens, size_t n_keys, unsigned mode, bool on_host, int device, bn254_g16_pvk** out, int* key_status,
+                      float* stage_ms);
 // bn254_capi_g16.hip
 DevState* dev_state(const bn254_g16_pvk* pvk, int device);
 int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n);

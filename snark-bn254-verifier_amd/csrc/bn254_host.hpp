@@ -41,29 +41,44 @@ struct G16Key {
   std::vector<G1Aff> k;
 };
 inline uint32_t be32(const uint8_t* b) { return (uint32_t)b[0] << 24 | (uint32_t)b[1] << 16 | (uint32_t)b[2] << 8 | b[3]; }
-// groth16/converter.rs:28-89; every slice-index panic of the reference becomes DEC_MALFORMED
-inline int parse_g16_vk(G16Key& vk, const uint8_t* b, size_t n, int mode) {
-  if (n < 292) return DEC_MALFORMED;
-  G1Aff beta1, delta1;
-  if (dec_g1_compressed(vk.alpha, b) || dec_g1_compressed(beta1, b + 32) || dec_g2_compressed(vk.beta, b + 64, mode) ||
-      dec_g2_compressed(vk.gamma, b + 128, mode) || dec_g1_compressed(delta1, b + 192) || dec_g2_compressed(vk.delta, b + 224, mode))
-    return DEC_MALFORMED;
-  uint32_t nk = be32(b + 288);
+// The structure of a gnark verifying key, walked on lengths alone (groth16/converter.rs:28-89; every slice-index panic of the reference is a `false` here): the six
+// fixed points, the K count against the remaining bytes, the commitment-index vectors and the 128 trailing bytes.  Where every compressed point lies: alpha 0, beta1 32,
+// beta 64, gamma 128, delta1 192, delta 224 (G16_VK_*), K[i] at k_off + 32 i, the two points of the commitment key at ck_off and ck_off + 64.  Nothing is decoded and
+// nothing is allocated: a count an attacker chose is only ever compared with the bytes that are there.  Shared by parse_g16_vk and the batch preparation
+// (bn254_capi_vkbatch.hip), so the two cannot drift.
+enum { G16_VK_ALPHA = 0, G16_VK_BETA1 = 32, G16_VK_BETA = 64, G16_VK_GAMMA = 128, G16_VK_DELTA1 = 192, G16_VK_DELTA = 224 };
+struct G16VkLayout { uint32_t nk = 0; size_t k_off = 0, ck_off = 0; };
+inline bool scan_g16_vk(G16VkLayout& l, const uint8_t* b, size_t n) {
+  if (n < 292) return false;
+  const uint32_t nk = be32(b + 288);
   size_t off = 292;
-  if ((n - off) / 32 < nk) return DEC_MALFORMED;
-  vk.k.resize(nk);
-  for (uint32_t i = 0; i < nk; i++, off += 32) if (dec_g1_compressed(vk.k[i], b + off)) return DEC_MALFORMED;
-  if (n < off + 4) return DEC_MALFORMED;
+  if ((n - off) / 32 < nk) return false;
+  l.nk = nk; l.k_off = off;
+  off += 32 * (size_t)nk;
+  if (n < off + 4) return false;
   uint32_t outer = be32(b + off); off += 4;
   for (uint32_t i = 0; i < outer; i++) {
-    if (n < off + 4) return DEC_MALFORMED;
+    if (n < off + 4) return false;
     uint32_t cnt = be32(b + off); off += 4;
-    if ((n - off) / 4 < cnt) return DEC_MALFORMED;
+    if ((n - off) / 4 < cnt) return false;
     off += 4 * (size_t)cnt;
   }
-  if (n < off + 128) return DEC_MALFORMED;
+  if (n < off + 128) return false;
+  l.ck_off = off;
+  return true;
+}
+// every point of a key that scanned, decoded (the order of the tests does not show: every failure is DEC_MALFORMED)
+inline int parse_g16_vk(G16Key& vk, const uint8_t* b, size_t n, int mode) {
+  G16VkLayout l;
+  if (!scan_g16_vk(l, b, n)) return DEC_MALFORMED;
+  G1Aff beta1, delta1;
+  if (dec_g1_compressed(vk.alpha, b + G16_VK_ALPHA) || dec_g1_compressed(beta1, b + G16_VK_BETA1) || dec_g2_compressed(vk.beta, b + G16_VK_BETA, mode) ||
+      dec_g2_compressed(vk.gamma, b + G16_VK_GAMMA, mode) || dec_g1_compressed(delta1, b + G16_VK_DELTA1) || dec_g2_compressed(vk.delta, b + G16_VK_DELTA, mode))
+    return DEC_MALFORMED;
+  vk.k.resize(l.nk);
+  for (uint32_t i = 0; i < l.nk; i++) if (dec_g1_compressed(vk.k[i], b + l.k_off + 32 * (size_t)i)) return DEC_MALFORMED;
   G2Aff ck;  // Pedersen commitment key: parsed (so that its errors surface like in the reference), never used
-  if (dec_g2_compressed(ck, b + off, mode) || dec_g2_compressed(ck, b + off + 64, mode)) return DEC_MALFORMED;
+  if (dec_g2_compressed(ck, b + l.ck_off, mode) || dec_g2_compressed(ck, b + l.ck_off + 64, mode)) return DEC_MALFORMED;
   return DEC_OK;
 }
 
@@ -150,6 +165,11 @@ inline void build_comb_table(int32_t* out /* (1 << G16_COMB_TEETH) * MSM_ENTRY_D
     fp_to_limbs(o, aff[e].x); fp_to_limbs(o + BN_NL, aff[e].y); o[18] = 0; o[19] = 0;
   }
 }
+// keys with more than G16_WIDE_MSM_MIN_INPUTS inputs: comb tables (BN254_WIDE_COMB=0 keeps the byte-window form for comparison)
+inline bool g16_key_uses_comb(size_t nb) {
+  const char* ce = getenv("BN254_WIDE_COMB");
+  return nb > (size_t)G16_WIDE_MSM_MIN_INPUTS && !(ce && atoi(ce) == 0);
+}
 // mode 0: reference-literal equation  e(A,B) e(L, gamma') e(C, -delta') == e(alpha, -beta')   (groth16/verify.rs:70-77, converter.rs:79)
 // mode 1: gnark                       e(A,B) e(L, -gamma) e(C, -delta)  == e(alpha, beta)
 // Returns false only if a line table cannot be built.  That does not happen for a key that parsed: its G2 elements are ON THE TWIST by construction (y is computed
@@ -181,9 +201,7 @@ inline bool prepare_g16(G16Prepared& out, const G16Key& vk, int mode) {
   out.target.resize(12 * BN_NL);
   put_fp12(out.target.data(), t);
   size_t nb = out.key_inputs();
-  // keys with more than G16_WIDE_MSM_MIN_INPUTS inputs: comb tables (BN254_WIDE_COMB=0 keeps the byte-window form for comparison)
-  const char* ce = getenv("BN254_WIDE_COMB");
-  out.msm_comb = nb > (size_t)G16_WIDE_MSM_MIN_INPUTS && !(ce && atoi(ce) == 0);
+  out.msm_comb = g16_key_uses_comb(nb);
   const size_t per_base = (out.msm_comb ? ((size_t)1 << G16_COMB_TEETH) : (size_t)32 * 255) * MSM_ENTRY_DWORDS;
   // the tables are built on the device that uses them (bn254_k_comb.hip: milliseconds instead of 2.2 s of host threads and a 671 MB upload for 1024 inputs, 0.18 s for 16);
   // BN254_TABLES_HOST=1 (or its round-5 name BN254_COMB_HOST=1) keeps the host construction
