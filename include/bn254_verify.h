@@ -408,6 +408,29 @@ int bn254_synth_groth16_range(uint64_t seed, size_t n_public, size_t first, size
  * 256-byte raw proof per row: the SP1 tests need proofs for inputs they cannot choose (a digest) */
 int bn254_synth_groth16_for_inputs(uint64_t seed, size_t n_public, size_t n, const uint8_t* inputs, int threads, uint8_t* vk_out, uint8_t* proofs_out);
 
+/* ---- synthetic PlonK workload generator (bench / tests; host threads, no GPU) ----------------------------------------
+ * Deterministic (SplitMix64 seed).  Writes a verifying key in the reference's layout (plonk/converter.rs:18-119; bn254_synth_plonk_vk_len(n_qcp) = 34 328 + 40 n_qcp
+ * bytes, the skipped 33 788 bytes zero) with n_public public inputs, n_qcp BSB22 commitments (at most 8) and a domain of 2^log2_size rows (1..28, at least
+ * n_public + n_qcp), n DISTINCT proofs that the verifier accepts (bn254_synth_plonk_proof_len(n_qcp) = 808 + 96 n_qcp bytes each, at proof_stride bytes from one
+ * another; a record is zero past its proof), their public inputs (n x n_public x 32 bytes, canonical) and the status the verifier must return.  The proofs come from
+ * the KZG secret, which the generator draws with the key: it opens random commitments to random claimed values.  If invalid_every > 0 every
+ * invalid_every-th proof is corrupted, cycling through: public input 0 + 1 (OPENING_MISMATCH), the shifted opening proof + G1 (PAIRING_FAILED), L.y + 1
+ * (NOT_ON_CURVE), Z.x >= p (NOT_MEMBER), the first commitment's claimed selector value + 1 (PAIRING_FAILED), the last commitment dropped (BSB22_MISMATCH).  A class
+ * the key has nothing for (no inputs: the first; no commitments: the last two) becomes the second.  The key is a function of (seed, n_public, n_qcp, log2_size)
+ * alone, proof i of (seed, i) and the key.  BN254_E_BAD_ARG (nothing written): n_qcp > 8, log2_size outside 1..28, a domain smaller than n_public + n_qcp,
+ * proof_stride below the proof length, a null buffer that would be written. */
+size_t bn254_synth_plonk_vk_len(size_t n_qcp);
+size_t bn254_synth_plonk_proof_len(size_t n_qcp);
+int bn254_synth_plonk(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t n, int invalid_every, int threads,
+                      uint8_t* vk_out, uint8_t* proofs_out, size_t proof_stride, uint8_t* inputs_out, uint8_t* expected_status_out);
+/* proofs [first, first + n) of the same stream, written to positions 0 .. n-1; the key is the same for every range */
+int bn254_synth_plonk_range(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t first, size_t n, int invalid_every, int threads,
+                            uint8_t* vk_out, uint8_t* proofs_out, size_t proof_stride, uint8_t* inputs_out, uint8_t* expected_status_out);
+/* the key of bn254_synth_plonk for the same arguments and, for n given input rows (n x n_public x 32 bytes, big-endian, each below r: BN254_E_BAD_ARG otherwise),
+ * one valid proof per row: the SP1 entry needs proofs for inputs the caller cannot choose (a digest) */
+int bn254_synth_plonk_for_inputs(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t n, const uint8_t* inputs, int threads,
+                                 uint8_t* vk_out, uint8_t* proofs_out, size_t proof_stride);
+
 /* ---- probes of the device arithmetic, used by the GPU parity tests (tests/test_gpu_*.py) ---------------------------
  * Each runs one lane per item on `device` and copies the result back.  Fp12 layout: 12 x 32 bytes in tower order
  * c0.c0.c0, c0.c0.c1, c0.c1.c0, ... c1.c2.c1; G1: x | y; G2: x.c1 | x.c0 | y.c1 | y.c0 (gnark order). */

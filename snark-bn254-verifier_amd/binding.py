@@ -658,3 +658,44 @@ def synth_groth16(seed, n_public, n, invalid_every=16, agree=True, threads=0, l_
     # l_identity: every proof with index = 3 mod 7 gets public inputs that make its public-input point L the identity (a valid proof)
     _check(L.bn254_synth_groth16_range(seed, n_public, first, n, invalid_every, (1 if agree else 0) | (2 if l_identity else 0), threads, vk, proofs, inputs, exp))
     return bytes(vk), bytes(proofs)[:256 * n], bytes(inputs)[:32 * n_public * n], bytes(exp)[:n]
+
+
+def _synth_plonk_lib():
+    L = lib()
+    L.bn254_synth_plonk_vk_len.restype = C.c_size_t; L.bn254_synth_plonk_vk_len.argtypes = [C.c_size_t]
+    L.bn254_synth_plonk_proof_len.restype = C.c_size_t; L.bn254_synth_plonk_proof_len.argtypes = [C.c_size_t]
+    L.bn254_synth_plonk_range.argtypes = [C.c_uint64, C.c_size_t, C.c_size_t, C.c_uint, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p, C.c_void_p]
+    L.bn254_synth_plonk_for_inputs.argtypes = [C.c_uint64, C.c_size_t, C.c_size_t, C.c_uint, C.c_size_t, C.c_char_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t]
+    return L
+
+
+def synth_plonk(seed, n_public, n_qcp, log2_size, n, invalid_every=16, threads=0, first=0, proof_stride=None):
+    """Deterministic synthetic PlonK workload for a key with n_public inputs, n_qcp BSB22 commitments and 2^log2_size rows: (vk, proofs, inputs, expected_status)
+    as bytes, the proofs all distinct and proof_stride bytes apart (default: the proof length, 808 + 96 n_qcp).  first: global index of the first proof (proof i
+    of the stream depends on (seed, i) and the key only)."""
+    L = _synth_plonk_lib()
+    if n_qcp > 8:
+        raise Bn254Error("bn254_synth_plonk: at most 8 commitments")
+    stride = L.bn254_synth_plonk_proof_len(n_qcp) if proof_stride is None else proof_stride
+    vk = (C.c_uint8 * L.bn254_synth_plonk_vk_len(n_qcp))()
+    proofs = (C.c_uint8 * max(stride * n, 1))()
+    inputs = (C.c_uint8 * max(32 * n_public * n, 1))()
+    exp = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_synth_plonk_range(seed, n_public, n_qcp, log2_size, first, n, invalid_every, threads, vk, proofs, stride, inputs, exp))
+    return bytes(vk), bytes(proofs)[:stride * n], bytes(inputs)[:32 * n_public * n], bytes(exp)[:n]
+
+
+def synth_plonk_for_inputs(seed, n_public, n_qcp, log2_size, inputs, n=None, threads=0, proof_stride=None):
+    """(vk, proofs): the key of synth_plonk for the same arguments and one valid proof per input row (n x n_public x 32 bytes, each value below r)."""
+    L = _synth_plonk_lib()
+    if n_qcp > 8:
+        raise Bn254Error("bn254_synth_plonk_for_inputs: at most 8 commitments")
+    inputs = bytes(inputs)
+    if n is None:
+        n = len(inputs) // (32 * n_public)
+    stride = L.bn254_synth_plonk_proof_len(n_qcp) if proof_stride is None else proof_stride
+    vk = (C.c_uint8 * L.bn254_synth_plonk_vk_len(n_qcp))()
+    proofs = (C.c_uint8 * max(stride * n, 1))()
+    _check(L.bn254_synth_plonk_for_inputs(seed, n_public, n_qcp, log2_size, n, inputs, threads, vk, proofs, stride))
+    return bytes(vk), bytes(proofs)[:stride * n]

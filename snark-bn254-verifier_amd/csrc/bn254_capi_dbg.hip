@@ -508,13 +508,15 @@ size_t bn254_synth_groth16_vk_len(size_t n_public) { return 292 + 32 * (n_public
 // the key of the synthetic workload and its trapdoors: the first part of the stream of `seed` (every range and bn254_synth_groth16_for_inputs make the same key)
 namespace {
 struct SynthKey { U256 alpha, beta, gamma, delta; std::vector<U256> kk; GenTables* tabs; };
-void synth_key(uint64_t seed, size_t n_public, int agree, uint8_t* vk_out, SynthKey& key) {
+GenTables* synth_tables() {   // the window tables of the two generators, built at the first use and shared by the Groth16 and the PlonK generator
   static GenTables* tabs = nullptr;
   static std::mutex tmu;
-  {
-    std::lock_guard<std::mutex> lk(tmu);
-    if (!tabs) { tabs = new GenTables(); build_gen_tables(*tabs); }
-  }
+  std::lock_guard<std::mutex> lk(tmu);
+  if (!tabs) { tabs = new GenTables(); build_gen_tables(*tabs); }
+  return tabs;
+}
+void synth_key(uint64_t seed, size_t n_public, int agree, uint8_t* vk_out, SynthKey& key) {
+  GenTables* tabs = synth_tables();
   SplitMix64 rng{seed};
   // trapdoors; beta, gamma, delta rejection-sampled into the mode-agreement set when asked:
   // y(beta G2), y(gamma G2) must have c0 / c1 in DIFFERENT halves of [0,p), y(delta G2) in the SAME half
@@ -656,6 +658,240 @@ int bn254_synth_groth16_for_inputs(uint64_t seed, size_t n_public, size_t n, con
   for (int t = 0; t < threads; t++) th.emplace_back(worker, t);
   for (auto& x : th) x.join();
   return BN254_OK;
+}
+
+// ---------------------------------------------------------------- synthetic PlonK workload generator
+// Valid proofs for a key of any shape, from the KZG secret: a simulator that knows tau and the discrete logarithm of every commitment can open any
+// commitment to any value, so it draws the commitments and the claimed values at random, derives the challenges as the verifier does, sets the one
+// value the verifier recomputes (the opening of the linearised polynomial's constant term) and solves the two KZG quotients.
+// The formulas below restate plonk/verify.rs:97-284 and kzg.rs:46-72 over scalars; only Challenge and bsb22_hash_to_field are the verifier's own code.
+// Whether a proof made here passes is decided by the oracle (tests/test_plonk_synth_cpu.py), not by this file.
+size_t bn254_synth_plonk_vk_len(size_t n_qcp) { return 34328 + 40 * n_qcp; }
+size_t bn254_synth_plonk_proof_len(size_t n_qcp) { return 808 + 96 * n_qcp; }
+
+namespace {
+enum { SP_L = 0, SP_R, SP_O, SP_Z, SP_H0, SP_H1, SP_H2, SP_BSB0, SP_MAX_PTS = SP_BSB0 + PLONK_MAX_QCP };
+enum { SK_S1 = 0, SK_S2, SK_S3, SK_QL, SK_QR, SK_QM, SK_QO, SK_QK, SK_QCP0 };       // the order of the key's points in its bytes and in PlonkKey::enc
+struct SynthPlonkKey { PlonkKey vk; FrM tau; FrM k[SK_QCP0 + PLONK_MAX_QCP]; GenTables* tabs; size_t n_public; int n_qcp; };
+inline FrM frm_of(const U256& u) { const FrM c = {{u.l[0], u.l[1], u.l[2], u.l[3]}}; return fr_ctx().from_canon(c); }
+inline U256 u256_of(const FrM& a) { const FrM c = fr_ctx().to_canon(a); const U256 u = {{c.l[0], c.l[1], c.l[2], c.l[3]}}; return u; }
+inline FrM frm_random(SplitMix64& g, bool nonzero) { return frm_of(fr_random(g, nonzero)); }
+inline void put_be64(uint8_t* b, uint64_t v) { for (int j = 0; j < 8; j++) b[j] = (uint8_t)(v >> (56 - 8 * j)); }
+inline void put_be32(uint8_t* b, uint32_t v) { for (int j = 0; j < 4; j++) b[j] = (uint8_t)(v >> (24 - 8 * j)); }
+inline void put_g1_mul(uint8_t* out64, const GenTables& t, const FrM& k) {           // k G uncompressed; the identity as 64 zero bytes
+  const G1Proj p = g1_mul_gen(t, u256_of(k));
+  if (g1_is_identity(p)) memset(out64, 0, 64); else enc_g1_uncompressed(out64, g1_to_affine(p));
+}
+int synth_plonk_args(size_t n_public, size_t n_qcp, unsigned log2_size, size_t n, size_t proof_stride, const void* vk_out, const void* proofs_out) {
+  if (n_qcp > (size_t)PLONK_MAX_QCP || log2_size < 1 || log2_size > 28) return set_err(BN254_E_BAD_ARG, "bad argument: at most 8 commitments, log2_size in 1..28");
+  const size_t size = (size_t)1 << log2_size;
+  if (n_public > size || n_qcp > size - n_public) return set_err(BN254_E_BAD_ARG, "bad argument: the domain is smaller than n_public + n_qcp");
+  if (proof_stride < bn254_synth_plonk_proof_len(n_qcp)) return set_err(BN254_E_BAD_ARG, "bad argument: proof_stride below the proof length");
+  if (!vk_out || (n && !proofs_out)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  return BN254_OK;
+}
+// the key of (seed, n_public, n_qcp, log2_size) and its trapdoors.  Arguments checked by the caller.
+void synth_plonk_key(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, uint8_t* vk_out, SynthPlonkKey& key) {
+  const FrCtx& F = fr_ctx();
+  GenTables* tabs = synth_tables();
+  SplitMix64 rng{(seed ^ 0x504c4f4e4b5f564bull) + 0x9e3779b97f4a7c15ull * ((uint64_t)n_public * 0x100000001b3ull + (uint64_t)n_qcp * 64 + log2_size)};
+  const uint64_t size = (uint64_t)1 << log2_size;
+  uint8_t* b = vk_out;
+  memset(b, 0, bn254_synth_plonk_vk_len(n_qcp));
+  // the domain: omega = x^((r - 1) / size) of exact order size (r - 1 = 2^28 * odd)
+  U256 e = u256_r(); e.l[0] -= 1;
+  for (unsigned s = 0; s < log2_size; s++) { for (int i = 0; i < 3; i++) e.l[i] = (e.l[i] >> 1) | (e.l[i + 1] << 63); e.l[3] >>= 1; }
+  FrM omega;
+  for (;;) {
+    const FrM x = frm_random(rng, true);
+    omega = F.one;
+    for (int i = 255; i >= 0; i--) { omega = F.mul(omega, omega); if ((e.l[i >> 6] >> (i & 63)) & 1) omega = F.mul(omega, x); }
+    if (!F.eq(F.pow_u64(omega, size >> 1), F.one)) break;
+  }
+  const FrM coset = frm_random(rng, true);
+  put_be64(b, size); F.to_be(b + 8, F.inverse(F.from_u64(size))); F.to_be(b + 40, omega); put_be64(b + 72, (uint64_t)n_public); F.to_be(b + 80, coset);
+  key.tau = frm_random(rng, true);
+  for (size_t i = 0; i < SK_QCP0 + n_qcp; i++) key.k[i] = frm_random(rng, true);
+  for (int i = 0; i < 8; i++) enc_g1_compressed(b + 112 + 32 * i, g1_to_affine(g1_mul_gen(*tabs, u256_of(key.k[i]))));
+  put_be32(b + 368, (uint32_t)n_qcp);
+  size_t off = 372;
+  for (size_t i = 0; i < n_qcp; i++, off += 32) enc_g1_compressed(b + off, g1_to_affine(g1_mul_gen(*tabs, u256_of(key.k[SK_QCP0 + i]))));
+  G1Aff g1gen; g1gen.x = fp_one(); g1gen.y = fp_add(fp_one(), fp_one());
+  enc_g1_compressed(b + off, g1gen);
+  // g2 = [sigma G2, sigma tau G2], re-sampled until both compressed points decode back to themselves in the loader's reading of the root order (parse_plonk_vk)
+  for (;;) {
+    const FrM sigma = frm_random(rng, true);
+    const G2Aff q[2] = {g2_mul_gen(*tabs, u256_of(sigma)), g2_mul_gen(*tabs, u256_of(F.mul(sigma, key.tau)))};
+    bool same = true;
+    for (int j = 0; j < 2 && same; j++) {
+      uint8_t want[128], got[128]; G2Aff back;
+      enc_g2_compressed(b + off + 32 + 64 * j, q[j]);
+      same = dec_g2_compressed(back, b + off + 32 + 64 * j, 0) == DEC_OK;
+      if (same) { enc_g2_uncompressed(want, q[j]); enc_g2_uncompressed(got, back); same = memcmp(want, got, 128) == 0; }
+    }
+    if (same) break;
+    key.tau = frm_random(rng, true);
+  }
+  off += 160 + 33788;            // the precomputed lines the loader skips: zeros
+  put_be64(b + off, (uint64_t)n_qcp); off += 8;
+  // the commitment constraints: n_qcp distinct ascending rows of [0, size - n_public)
+  uint64_t cci[PLONK_MAX_QCP];
+  const uint64_t range = size - (uint64_t)n_public;
+  for (size_t i = 0; i < n_qcp;) {
+    const uint64_t v = rng.next() % range;
+    bool fresh = true;
+    for (size_t j = 0; j < i; j++) fresh = fresh && cci[j] != v;
+    if (fresh) cci[i++] = v;
+  }
+  std::sort(cci, cci + n_qcp);
+  for (size_t i = 0; i < n_qcp; i++, off += 8) put_be64(b + off, cci[i]);
+  (void)parse_plonk_vk(key.vk, b, off);       // the loader's own image of the bytes: encodings, transcript prefix, omega^(n_public + cci)
+  key.tabs = tabs; key.n_public = n_public; key.n_qcp = (int)n_qcp;
+}
+// One proof for the input row `in` (n_public canonical values), randomness from g; cls: -1 valid, 1..5 the corruption classes that touch the proof (class 0 touches
+// the inputs: the caller's).  p: proof_len bytes, zeroed.
+void synth_plonk_proof(const SynthPlonkKey& key, SplitMix64& g, const uint8_t* in, int cls, uint8_t* p) {
+  const FrCtx& F = fr_ctx();
+  const PlonkKey& vk = key.vk;
+  const GenTables& tabs = *key.tabs;
+  const int q = key.n_qcp, nd = 6 + q, npts = SP_BSB0 + q;
+  const size_t off_claimed = 516, off_zs = off_claimed + 32 * (size_t)nd, off_bsb = off_zs + 100;
+  // 1. the commitments: known multiples of G
+  FrM d[SP_MAX_PTS]; G1Proj pj[SP_MAX_PTS]; G1Aff pa[SP_MAX_PTS];
+  for (int k = 0; k < npts; k++) { d[k] = frm_random(g, true); pj[k] = g1_mul_gen(tabs, u256_of(d[k])); }
+  g1_batch_to_affine(pa, pj, (size_t)npts);
+  for (int k = 0; k < SP_BSB0; k++) enc_g1_uncompressed(p + 64 * k, pa[k]);
+  for (int j = 0; j < q; j++) enc_g1_uncompressed(p + off_bsb + 64 * j, pa[SP_BSB0 + j]);
+  put_be32(p + 512, (uint32_t)nd); put_be32(p + off_zs + 96, (uint32_t)q);
+  // 2. gamma, beta, alpha, zeta (verify.rs:62-95)
+  uint8_t dg[32], db[32], da[32], dz[32];
+  Challenge cg(vk.gamma_mid); cg.bind(in, 32 * key.n_public); cg.bind(p, 192);
+  const FrM gamma = cg.finish(dg);
+  Challenge cb("beta", 4, dg);
+  const FrM beta = cb.finish(db);
+  Challenge ca("alpha", 5, db); ca.bind(p + off_bsb, 64 * (size_t)q); ca.bind(p + 192, 64);
+  const FrM alpha = ca.finish(da);
+  Challenge cz("zeta", 4, da); cz.bind(p + 256, 192);
+  const FrM zeta = cz.finish(dz);
+  // 3. the claimed values at random, but the first: the constant term of the linearised polynomial as verify.rs:97-207 computes it
+  FrM cl[PLONK_MAX_CLAIMED];
+  for (int k = 1; k < nd; k++) cl[k] = frm_random(g, false);
+  const FrM zu = frm_random(g, false);
+  const FrM &l = cl[1], &r = cl[2], &o = cl[3], &s1 = cl[4], &s2 = cl[5];
+  const FrM zeta_n = F.pow_u64(zeta, vk.size), zh = F.sub(zeta_n, F.one), zs = F.mul(zh, vk.size_inv);
+  const FrM lagrange_one = F.mul(zs, F.inverse(F.sub(zeta, F.one)));
+  FrM pi = {{0, 0, 0, 0}}, accw = F.one;
+  for (size_t i = 0; i < key.n_public; i++) {
+    pi = F.add(pi, F.mul(F.mul(F.mul(zs, F.inverse(F.sub(zeta, accw))), accw), F.from_be32(in + 32 * i)));
+    accw = F.mul(accw, vk.generator);
+  }
+  for (int j = 0; j < q; j++) pi = F.add(pi, F.mul(F.mul(F.mul(zs, vk.wpow[j]), F.inverse(F.sub(zeta, vk.wpow[j]))), bsb22_hash_to_field(p + off_bsb + 64 * j)));
+  const FrM a2l1 = F.mul(F.mul(lagrange_one, alpha), alpha);
+  const FrM bs1 = F.add(F.add(F.mul(beta, s1), gamma), l), bs2 = F.add(F.add(F.mul(beta, s2), gamma), r);
+  cl[0] = F.neg(F.add(F.sub(F.mul(F.mul(F.mul(F.mul(bs1, bs2), F.add(o, gamma)), alpha), zu), a2l1), pi));
+  // 4. the linearised digest's discrete logarithm: the combination of verify.rs:216-284 over scalars
+  const FrM c_s3 = F.mul(F.mul(F.mul(F.mul(bs1, bs2), beta), alpha), zu);
+  const FrM u = F.mul(beta, vk.coset_shift), u2 = F.mul(u, vk.coset_shift);
+  FrM t = F.add(F.add(F.mul(beta, zeta), gamma), l);
+  t = F.mul(t, F.add(F.add(F.mul(u, zeta), gamma), r));
+  t = F.mul(t, F.add(F.add(F.mul(u2, zeta), gamma), o));
+  const FrM c_z = F.sub(a2l1, F.mul(t, alpha));
+  const FrM zn2 = F.mul(zeta_n, F.mul(zeta, zeta));
+  FrM lin = F.mul(key.k[SK_QL], l);
+  lin = F.add(lin, F.mul(key.k[SK_QR], r));
+  lin = F.add(lin, F.mul(key.k[SK_QM], F.mul(l, r)));
+  lin = F.add(lin, F.mul(key.k[SK_QO], o));
+  lin = F.add(lin, key.k[SK_QK]);
+  lin = F.add(lin, F.mul(key.k[SK_S3], c_s3));
+  lin = F.add(lin, F.mul(d[SP_Z], c_z));
+  lin = F.sub(lin, F.mul(zh, F.add(d[SP_H0], F.mul(zn2, F.add(d[SP_H1], F.mul(zn2, d[SP_H2]))))));
+  for (int j = 0; j < q; j++) lin = F.add(lin, F.mul(d[SP_BSB0 + j], cl[6 + j]));
+  for (int k = 0; k < nd; k++) F.to_be(p + off_claimed + 32 * k, cl[k]);
+  F.to_be(p + off_zs + 64, zu);
+  // 5. the folding challenge (kzg.rs:46-72) and the two quotients
+  uint8_t b32[32], lin_enc[64], dgam[32];
+  put_g1_mul(lin_enc, tabs, lin);
+  Challenge cf("gamma", 5, nullptr);
+  F.to_be(b32, zeta); cf.bind(b32, 32);
+  cf.bind(lin_enc, 64); cf.bind(p, 192); cf.bind(vk.enc[SK_S1], 64); cf.bind(vk.enc[SK_S2], 64);
+  for (int j = 0; j < q; j++) cf.bind(vk.enc[SK_QCP0 + j], 64);
+  cf.bind(p + off_claimed, 32 * (size_t)nd); cf.bind(p + off_zs + 64, 32);
+  const FrM fold = cf.finish(dgam);
+  FrM dig[PLONK_MAX_CLAIMED] = {lin, d[SP_L], d[SP_R], d[SP_O], key.k[SK_S1], key.k[SK_S2]};
+  for (int j = 0; j < q; j++) dig[6 + j] = key.k[SK_QCP0 + j];
+  FrM num = {{0, 0, 0, 0}}, gk = F.one;
+  for (int k = 0; k < nd; k++) { num = F.add(num, F.mul(gk, F.sub(dig[k], cl[k]))); gk = F.mul(gk, fold); }
+  const FrM h = F.mul(num, F.inverse(F.sub(key.tau, zeta)));
+  FrM hs = F.mul(F.sub(d[SP_Z], zu), F.inverse(F.sub(key.tau, F.mul(zeta, vk.generator))));
+  if (cls == 1) hs = F.add(hs, F.one);                                                   // H' + G
+  put_g1_mul(p + 448, tabs, h);
+  put_g1_mul(p + off_zs, tabs, hs);
+  // the corruptions of a finished proof
+  if (cls == 2) fp_to_be(p + 32, fp_add(pa[SP_L].y, fp_one()));                           // L.y + 1 mod p
+  if (cls == 3) memset(p + 192, 0xff, 32);                                                // Z.x = 2^256 - 1
+  if (cls == 4) F.to_be(p + off_claimed + 32 * 6, F.add(cl[6], F.one));                   // the first commitment's selector claim + 1
+  if (cls == 5) { put_be32(p + off_zs + 96, (uint32_t)(q - 1)); memset(p + off_bsb + 64 * (size_t)(q - 1), 0, 64); }   // the last commitment dropped
+}
+int synth_plonk_run(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t first, size_t n, int invalid_every, const uint8_t* given, int threads,
+                    uint8_t* vk_out, uint8_t* proofs_out, size_t proof_stride, uint8_t* inputs_out, uint8_t* expected) {
+  SynthPlonkKey key;
+  synth_plonk_key(seed, n_public, n_qcp, log2_size, vk_out, key);
+  if (n == 0) return BN254_OK;
+  const FrCtx& F = fr_ctx();
+  static const uint8_t none = 0;
+  if (threads <= 0) { threads = (int)std::thread::hardware_concurrency(); if (threads <= 0) threads = 1; }
+  if ((size_t)threads > n) threads = (int)n;
+  auto worker = [&](int tid) {
+    for (size_t li = tid; li < n; li += threads) {
+      const size_t i = first + li;     // global index: seeds the proof and selects its class
+      SplitMix64 g{seed * 0x9e3779b97f4a7c15ull + 0x2000 + i};
+      uint8_t* p = proofs_out + proof_stride * li;
+      memset(p, 0, proof_stride);
+      const uint8_t* in = !n_public ? &none : given ? given + li * n_public * 32 : inputs_out + li * n_public * 32;
+      if (!given) for (size_t s = 0; s < n_public; s++) u256_to_be(inputs_out + (li * n_public + s) * 32, fr_random(g, false));
+      int cls = -1;
+      if (!given && invalid_every > 0 && (i % (size_t)invalid_every) == (size_t)invalid_every - 1) cls = (int)((i / (size_t)invalid_every) % 6);
+      if ((cls == 0 && n_public == 0) || ((cls == 4 || cls == 5) && n_qcp == 0)) cls = 1;
+      synth_plonk_proof(key, g, in, cls, p);
+      if (cls == 0) F.to_be(inputs_out + li * n_public * 32, F.add(F.from_be32(in), F.one));   // public input 0 + 1 mod r
+      if (expected) {
+        static const uint8_t st[6] = {BN254_ERR_OPENING_MISMATCH, BN254_ERR_PAIRING_FAILED, BN254_ERR_NOT_ON_CURVE, BN254_ERR_NOT_MEMBER, BN254_ERR_PAIRING_FAILED, BN254_ERR_BSB22_MISMATCH};
+        expected[li] = cls < 0 ? (uint8_t)BN254_ACCEPT : st[cls];
+      }
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 0; t < threads; t++) th.emplace_back(worker, t);
+  for (auto& x : th) x.join();
+  return BN254_OK;
+}
+}  // namespace
+int bn254_synth_plonk(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t n, int invalid_every, int threads, uint8_t* vk_out, uint8_t* proofs_out,
+                      size_t proof_stride, uint8_t* inputs_out, uint8_t* expected) {
+  return bn254_synth_plonk_range(seed, n_public, n_qcp, log2_size, 0, n, invalid_every, threads, vk_out, proofs_out, proof_stride, inputs_out, expected);
+}
+// proofs [first, first + n) of the stream of bn254_synth_plonk (proof i is a function of (seed, i) and the key alone), written to positions 0 .. n-1
+int bn254_synth_plonk_range(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t first, size_t n, int invalid_every, int threads, uint8_t* vk_out,
+                            uint8_t* proofs_out, size_t proof_stride, uint8_t* inputs_out, uint8_t* expected) {
+  int rc = synth_plonk_args(n_public, n_qcp, log2_size, n, proof_stride, vk_out, proofs_out);
+  if (rc) return rc;
+  if (n && (!expected || (n_public && !inputs_out))) return set_err(BN254_E_BAD_ARG, "bad argument");
+  return synth_plonk_run(seed, n_public, n_qcp, log2_size, first, n, invalid_every, nullptr, threads, vk_out, proofs_out, proof_stride, inputs_out, expected);
+}
+// the key of bn254_synth_plonk for the same arguments and one valid proof per given input row (n x n_public x 32 bytes, big-endian, each below r)
+int bn254_synth_plonk_for_inputs(uint64_t seed, size_t n_public, size_t n_qcp, unsigned log2_size, size_t n, const uint8_t* inputs, int threads, uint8_t* vk_out,
+                                 uint8_t* proofs_out, size_t proof_stride) {
+  int rc = synth_plonk_args(n_public, n_qcp, log2_size, n, proof_stride, vk_out, proofs_out);
+  if (rc) return rc;
+  if (n && n_public && !inputs) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const U256 r = u256_r();
+  for (size_t k = 0; k < n * n_public; k++) {
+    U256 x;
+    for (int l = 0; l < 4; l++) x.l[l] = be64(inputs + 32 * k + (3 - l) * 8);
+    if (u256_cmp(x, r) >= 0) return set_err(BN254_E_BAD_ARG, "bad argument: a public input is not below r");
+  }
+  static const uint8_t none = 0;     // `given` non-null selects the caller's rows
+  return synth_plonk_run(seed, n_public, n_qcp, log2_size, 0, n, 0, n_public ? inputs : &none, threads, vk_out, proofs_out, proof_stride, nullptr, nullptr);
 }
 
 }  // extern "C"
