@@ -441,6 +441,31 @@ int bn254_dbg_valu_peak_sustained(int device, double ms_target, double* mads_per
 int bn254_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device);                 /* n x 32 B each */
 int bn254_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device);        /* 0 mul 1 sqr 2 inv 3 cyclo_sqr(after easy part) 4 frob1 */
 int bn254_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* out_gt, size_t n, int device);          /* e(P_i, Q_i), n x 384 B */
+/* Value-level probes of the Fp12 operations (tests).  An Fp12 value travels in one of two formats, twelve Fp numbers in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..):
+ *   format 0  384 bytes, 32 big-endian canonical bytes per number;
+ *   format 1  108 int32: per number the nine balanced 29-bit digits (digit 0 first) of a representative of its Montgomery form x 2^261 mod p, stored into
+ *             and read from the workspace AS GIVEN -- the caller chooses the representative and must stay inside the operation's input contract
+ *             (the eight low digits in [-2^28, 2^28], |value| <= 2.42 p).
+ * bn254_dbg_fp12_op_fmt: the lane kernels; op as bn254_dbg_fp12_op and 5 cyclo_sqr 6 frob2 7 frob3 8 a conj(b) 9 conj(a) b (the conjugations as the kernels fuse them).
+ * bn254_dbg_coop12_op: ONE operation of the cooperative layout (csrc/bn254_coop12.hip), five proofs per wavefront, called as the product calls it.  For the
+ * line products b is the Fp12 d0 + d3 w + d4 w^3 (every other coefficient zero; d0 in Fp for ops 8 and 9); arg: the squaring count (1 .. 64) or the Frobenius power (1 .. 3).
+ * op of bn254_dbg_coop12_op: 0 a b; 1 a conj(b) (conj_b of c12_mul); 2 conj(a) b (a flagged VE_CONJ, rewritten by Coop12Ops); 3 general squaring; 4 cyclotomic
+ * squarings, arg of them; 5 Frobenius, power arg; 6 inverse; 7 conjugate; 8 c12_mul_line_fp; 9 the same with keep (the line counts as 1: a is returned);
+ * 10 c12_mul_line_fp2; 11 k_coop12_final_exp. */
+int bn254_dbg_fp12_op_fmt(int op, const void* a, const void* b, void* out, size_t n, int in_format, int out_format, int device);
+int bn254_dbg_coop12_op(int op, const void* a, const void* b, void* out, size_t n, int in_format, int out_format, int arg, int device);
+/* The compares that decide a verdict, on values the caller places: n values a (and b), ONE target of twelve numbers in format 0; out_status: n bytes,
+ * BN254_ACCEPT or BN254_REJECT.  form 0: k_g16_compare (a == target); 1: k_f12_mul_verdict (a b == target, compared as the product is stored);
+ * 2: c12_eq_const of the cooperative kernels (a == target).  (k_f12_mul_verdict_keys takes its target from a key set's descriptors: it has no probe.) */
+int bn254_dbg_verdict(int form, const void* a, const void* b, const uint8_t target[384], uint8_t* out_status, size_t n, int in_format, int device);
+/* The cooperative kernels in their store modes, with the line tables of a prepared key (gamma side: table 0, delta side: table 1; bn254_groth16_vk_prepare says
+ * which signs they hold).  _fixed: k_coop12_miller_fixed with fuse_final_exp and no target on n_pairs (1 or 2) table-driven pairs: g1_0 / g1_1 n x 64 bytes
+ * (g1_1 unused for one pair), identity: null or n bytes, bit t = the G1 point of pair t is the identity (its bytes are then ignored); out_gt n x 384 bytes.
+ * _g16: k_g16_prepare and k_coop12_miller_g16 (fuse_final_exp, no target) on n raw 256-byte proofs with their inputs (keys with at most 16 inputs);
+ * out_status[i]: BN254_ACCEPT where the proof reached the pairing and out_gt holds its value, else the loader's status (out_gt is then unspecified). */
+int bn254_dbg_coop12_miller_fixed(const bn254_g16_pvk* pvk, int n_pairs, const uint8_t* g1_0, const uint8_t* g1_1, const uint8_t* identity, uint8_t* out_gt, size_t n, int device);
+int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_public, size_t n, uint8_t* out_gt, uint8_t* out_status,
+                                int device);
 int bn254_dbg_g2_subgroup(const uint8_t* g2, uint8_t* out_flags, size_t n, int device);                       /* 1 = in G2 (gnark's psi relation, one kernel) */
 int bn254_dbg_g2_subgroup_ate(const uint8_t* g1, const uint8_t* g2, uint8_t* out_flags, size_t n, int device); /* 1 = in G2: the product's test, from the Miller loop's final point (g1: any G1 points) */
 

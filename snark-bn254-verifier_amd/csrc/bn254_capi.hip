@@ -348,6 +348,15 @@ hipError_t bn254_launch_g16_keys_direct(const G16KeysDirectArgs&, hipStream_t) {
 #if defined(BN254_HOSTSAN_KEYS)
 hipError_t bn254_coop12_prepare() { return hipSuccess; }      // the step-kind table of the cooperative kernels: nothing to create without a device compiler
 #endif
+// the launchers of the value-level probes (bn254_capi_dbg.hip: bn254_dbg_coop12_op, bn254_dbg_verdict, ..): no kernels in a host build, so the probes there check
+// their arguments, move their buffers and return what those held; every harness links these, whichever stand-ins it brings for the launchers of the product
+hipError_t bn254_launch_dbg_fp12_op_fmt(int, const uint8_t*, const uint8_t*, uint8_t*, size_t, int32_t*, uint8_t*, int, int, hipStream_t) { return hipSuccess; }
+hipError_t bn254_launch_dbg_load(int32_t*, size_t, uint8_t*, int, const void*, int, hipStream_t) { return hipSuccess; }
+hipError_t bn254_launch_dbg_store(int32_t*, size_t, int, void*, int, hipStream_t) { return hipSuccess; }
+hipError_t bn254_launch_dbg_verdict(int, int32_t*, size_t, uint8_t*, const int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs&, hipStream_t) { return hipSuccess; }
+hipError_t bn254_coop12_dbg_op(int32_t*, uint8_t*, size_t, int, int, const int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t bn254_coop12_miller_fixed(int32_t*, uint8_t*, size_t, int, const int32_t*, const int32_t*, const int32_t*, int, int, int, int, int, int, int, const int32_t*, int, hipStream_t) { return hipSuccess; }
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {

@@ -305,11 +305,163 @@ static int probe_ws_alloc(size_t n, int device) {
   return BN254_OK;
 }
 static void probe_ws_free() { g_probe_ws.release(); g_probe_kinds.release(); }
-int bn254_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device) {
-  g_probe_op = op;
+// Fp12 operands and results of the value-level probes: format 0 = 384 bytes, 1 = 108 raw int32 digits per value (include/bn254_verify.h)
+static inline size_t probe_fmt_bytes(int format) { return format ? (size_t)12 * BN_NL * sizeof(int32_t) : (size_t)384; }
+static thread_local int g_probe_in = 0, g_probe_out = 0;
+int bn254_dbg_fp12_op_fmt(int op, const void* a, const void* b, void* out, size_t n, int in_format, int out_format, int device) {
+  const bool two = op == 0 || op == 8 || op == 9;
+  if (op < 0 || op > 9 || (in_format | out_format) & ~1 || (n && (!a || !out || (two && !b)))) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > (size_t)G16_MAX_LAUNCH) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  g_probe_op = op; g_probe_in = in_format; g_probe_out = out_format;
   int rc = probe_ws_alloc(n, device);
   if (rc) return rc;
-  rc = run_probe(384, b ? 384 : 0, 384, a, b, out, n, device, [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_fp12_op(g_probe_op, x, y, o, m, g_probe_ws, g_probe_kinds, nullptr); });
+  rc = run_probe(probe_fmt_bytes(in_format), two ? probe_fmt_bytes(in_format) : 0, probe_fmt_bytes(out_format), (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, n, device,
+                 [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) { return bn254_launch_dbg_fp12_op_fmt(g_probe_op, x, y, o, m, g_probe_ws, g_probe_kinds, g_probe_in, g_probe_out, nullptr); });
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device) {
+  // the entry as it always was: ops 0 .. 4 (anything else: frob1), b read for the product only
+  const int o = op >= 0 && op <= 3 ? op : 4;
+  return bn254_dbg_fp12_op_fmt(o, a, o == 0 ? b : nullptr, out, n, 0, 0, device);
+}
+// op numbers of bn254_dbg_coop12_op (include/bn254_verify.h lists them; bn254_coop12.hip::k_coop12_dbg_op takes them as they are)
+enum { C12_DBG_MUL = 0, C12_DBG_MUL_CONJ_A = 2, C12_DBG_CYCLO_SQR_N = 4, C12_DBG_FROB = 5, C12_DBG_MUL_LINE_FP = 8, C12_DBG_MUL_LINE_FP2 = 10, C12_DBG_FINAL_EXP = 11, C12_DBG_EQ = 12 };
+static thread_local int g_probe_arg = 0;
+static thread_local DevBuf<int32_t> g_probe_target;
+int bn254_dbg_coop12_op(int op, const void* a, const void* b, void* out, size_t n, int in_format, int out_format, int arg, int device) {
+  const bool two = op <= C12_DBG_MUL_CONJ_A || (op >= C12_DBG_MUL_LINE_FP && op <= C12_DBG_MUL_LINE_FP2);
+  if (op < 0 || op > C12_DBG_FINAL_EXP || (in_format | out_format) & ~1 || n == 0 || !a || !out || (two && !b) || (op == C12_DBG_CYCLO_SQR_N && (arg < 1 || arg > 64)) ||
+      (op == C12_DBG_FROB && (arg < 1 || arg > 3)))
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > bn254_coop_max_proofs()) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  g_probe_op = op; g_probe_in = in_format; g_probe_out = out_format; g_probe_arg = arg;
+  int rc = probe_ws_alloc(n, device);
+  if (rc) return rc;
+  rc = run_probe(probe_fmt_bytes(in_format), two ? probe_fmt_bytes(in_format) : 0, probe_fmt_bytes(out_format), (const uint8_t*)a, (const uint8_t*)b, (uint8_t*)out, n, device,
+                 [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) {
+                   const int kind = g_probe_in ? 3 : 0;
+                   (void)hipMemsetAsync(g_probe_ws, 0, m * (size_t)G16_WS_BYTES_PER_PROOF, nullptr);    // VE_S1 of the one-operand operations: zeros, not stale words
+                   hipError_t e = bn254_launch_dbg_load(g_probe_ws, m, g_probe_kinds, (int)VE_F, x, kind, nullptr);
+                   if (e == hipSuccess && y) e = bn254_launch_dbg_load(g_probe_ws, m, g_probe_kinds, (int)VE_S1, y, kind, nullptr);
+                   if (e == hipSuccess) e = bn254_coop12_dbg_op(g_probe_ws, g_probe_kinds, m, g_probe_op, g_probe_arg, nullptr, nullptr);
+                   if (e == hipSuccess) e = bn254_launch_dbg_store(g_probe_ws, m, (int)VE_S0, o, g_probe_out, nullptr);
+                   return e;
+                 });
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_verdict(int form, const void* a, const void* b, const uint8_t target[384], uint8_t* out_status, size_t n, int in_format, int device) {
+  if (form < 0 || form > 2 || in_format & ~1 || n == 0 || !a || (form == 1 && !b) || !target || !out_status) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > (form == 2 ? bn254_coop_max_proofs() : (size_t)G16_MAX_LAUNCH)) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  // the target as a key holds it (bn254_host.hpp::put_fp12): reduced digits of the Montgomery form, k-order
+  int32_t tgt[12 * BN_NL];
+  {
+    Fp12 t;
+    const int korder[6] = {0, 2, 4, 1, 3, 5};
+    Fp2* k[6] = {&K0(t), &K1(t), &K2(t), &K3(t), &K4(t), &K5(t)};
+    for (int i = 0; i < 6; i++) {
+      for (int hf = 0; hf < 2; hf++) {
+        uint32_t w[8];
+        words_from_be(w, target + 64 * i + 32 * hf);
+        if (words_ge(w, BN_P_WORDS)) return set_err(BN254_E_BAD_ARG, "target is not canonical");
+      }
+      k[korder[i]]->c0 = fp_from_be(target + 64 * i); k[korder[i]]->c1 = fp_from_be(target + 64 * i + 32);
+    }
+    put_fp12(tgt, t);
+  }
+  g_probe_op = form; g_probe_in = in_format;
+  int rc = probe_ws_alloc(n, device);
+  if (rc) return rc;
+  if ((rc = g_probe_target.ensure(12 * BN_NL))) { probe_ws_free(); return rc; }
+  hipError_t ce = hipMemcpy(g_probe_target, tgt, sizeof tgt, hipMemcpyHostToDevice);
+  if (ce != hipSuccess) { probe_ws_free(); g_probe_target.release(); return set_err(BN254_E_HIP, std::string("probe copy: ") + hipGetErrorString(ce)); }
+  rc = run_probe(probe_fmt_bytes(in_format), form == 1 ? probe_fmt_bytes(in_format) : 0, 1, (const uint8_t*)a, (const uint8_t*)b, out_status, n, device,
+                 [](const uint8_t* x, const uint8_t* y, uint8_t* o, size_t m) {
+                   const int kind = g_probe_in ? 3 : 0, form = g_probe_op;
+                   // where the product holds the operands: k_g16_compare reads VE_S0; k_f12_mul_verdict multiplies VE_S2 by VE_S0; the cooperative probe reads VE_F
+                   hipError_t e = bn254_launch_dbg_load(g_probe_ws, m, g_probe_kinds, form == 0 ? (int)VE_S0 : form == 1 ? (int)VE_S2 : (int)VE_F, x, kind, nullptr);
+                   if (e == hipSuccess && form == 1) e = bn254_launch_dbg_load(g_probe_ws, m, g_probe_kinds, (int)VE_S0, y, kind, nullptr);
+                   if (e == hipSuccess) e = form == 2 ? bn254_coop12_dbg_op(g_probe_ws, g_probe_kinds, m, C12_DBG_EQ, 0, g_probe_target, nullptr)
+                                                      : bn254_launch_dbg_verdict(form, g_probe_ws, m, g_probe_kinds, g_probe_target, nullptr);
+                   if (e == hipSuccess) e = hipMemcpyAsync(o, g_probe_kinds, m, hipMemcpyDeviceToDevice, nullptr);
+                   return e;
+                 });
+  probe_ws_free(); g_probe_target.release();
+  return rc;
+}
+// the cooperative kernels in their store modes with a prepared key's line tables
+static int probe_key_dev(const bn254_g16_pvk* pvk, int device, DevState** out) {
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  int rc = ensure_dev(pvk, *d, device, 1);
+  if (rc) return rc;
+  *out = d;
+  return BN254_OK;
+}
+int bn254_dbg_coop12_miller_fixed(const bn254_g16_pvk* pvk, int n_pairs, const uint8_t* g1_0, const uint8_t* g1_1, const uint8_t* identity, uint8_t* out_gt, size_t n, int device) {
+  if (!pvk || n_pairs < 1 || n_pairs > 2 || !g1_0 || (n_pairs == 2 && !g1_1) || !out_gt || n == 0) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > bn254_coop_max_proofs_fixed()) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  DevState* d;
+  int rc = probe_key_dev(pvk, device, &d);
+  if (rc) return rc;
+  if ((rc = probe_ws_alloc(n, device))) return rc;
+  DevBuf<uint8_t> in, out;
+  std::vector<uint8_t> st(n);
+  for (size_t i = 0; i < n; i++) st[i] = (uint8_t)(BN254_ST_PENDING | (identity && (identity[i] & 1) ? BN254_ST_LINF : 0) | (identity && (identity[i] & 2) ? BN254_ST_LINF2 : 0));
+  auto run = [&]() -> int {
+    int r;
+    if ((r = in.ensure(128 * n)) || (r = out.ensure(384 * n))) return r;
+    HIPCK(hipMemsetAsync(g_probe_ws, 0, n * (size_t)G16_WS_BYTES_PER_PROOF, nullptr));
+    HIPCK(hipMemcpy(in, g1_0, 64 * n, hipMemcpyHostToDevice));
+    if (n_pairs == 2) HIPCK(hipMemcpy(in + 64 * n, g1_1, 64 * n, hipMemcpyHostToDevice));
+    hipError_t e = bn254_launch_dbg_load(g_probe_ws, n, g_probe_kinds, (int)VE_LX, in, 4, nullptr);
+    if (e == hipSuccess && n_pairs == 2) e = bn254_launch_dbg_load(g_probe_ws, n, g_probe_kinds, (int)VE_CX, in + 64 * n, 4, nullptr);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
+    HIPCK(hipMemcpy(g_probe_kinds, st.data(), n, hipMemcpyHostToDevice));      // after the loads (same stream): they set PENDING alone
+    // the arguments of bn254_launch_pairing2_fixed's cooperative call, without the target
+    e = bn254_coop12_miller_fixed(g_probe_ws, g_probe_kinds, n, n_pairs, d->gtab, d->dtab, d->gtab, VE_LX, VE_CX, VE_LX, BN254_ST_LINF, BN254_ST_LINF2, 0, 1, nullptr, 0, nullptr);
+    if (e == hipSuccess) e = bn254_launch_dbg_store(g_probe_ws, n, (int)VE_S0, out, 0, nullptr);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
+    HIPCK(hipDeviceSynchronize());
+    HIPCK(hipMemcpy(out_gt, out, 384 * n, hipMemcpyDeviceToHost));
+    return BN254_OK;
+  };
+  rc = run();
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_public, size_t n, uint8_t* out_gt, uint8_t* out_status,
+                                int device) {
+  if (!pvk || !proofs || (n_public && !public_inputs) || !out_gt || !out_status || n == 0 || n_public > (size_t)G16_WIDE_MSM_MIN_INPUTS) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > bn254_coop_max_proofs()) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  if (!pvk->host.inputs_match(n_public)) return set_err(BN254_E_BAD_ARG, "the key takes another number of public inputs");
+  DevState* d;
+  int rc = probe_key_dev(pvk, device, &d);
+  if (rc) return rc;
+  if ((rc = probe_ws_alloc(n, device))) return rc;
+  DevBuf<uint8_t> in, out;
+  auto run = [&]() -> int {
+    int r;
+    const size_t pb = 256 * n, ib = 32 * n_public * n;
+    if ((r = in.ensure(pb + ib + 4)) || (r = out.ensure(384 * n))) return r;
+    HIPCK(hipMemsetAsync(g_probe_ws, 0, n * (size_t)G16_WS_BYTES_PER_PROOF, nullptr));
+    HIPCK(hipMemcpy(in, proofs, pb, hipMemcpyHostToDevice));
+    if (ib) HIPCK(hipMemcpy(in + pb, public_inputs, ib, hipMemcpyHostToDevice));
+    G16LaunchArgs a;
+    a.proofs = in; a.stride = 256; a.inputs = in + pb; a.n_public = (int)n_public; a.n = n; a.ws = g_probe_ws; a.status = g_probe_kinds;
+    a.msm_tab = d->msm; a.k0 = d->k0; a.gtab = d->gtab; a.dtab = d->dtab; a.target = nullptr; a.inputs_match_key = 1; a.msm_part = nullptr;
+    hipError_t e = bn254_launch_dbg_coop12_g16(a, nullptr);
+    if (e == hipSuccess) e = bn254_launch_dbg_store(g_probe_ws, n, (int)VE_S0, out, 0, nullptr);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
+    HIPCK(hipDeviceSynchronize());
+    HIPCK(hipMemcpy(out_gt, out, 384 * n, hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(out_status, g_probe_kinds, n, hipMemcpyDeviceToHost));
+    // a proof the loader passed keeps PENDING (with a deferred error of C in the low bits, which the pairing does not look at): it reached the pairing
+    for (size_t i = 0; i < n; i++) if (out_status[i] & BN254_ST_PENDING) out_status[i] = (out_status[i] & 0x3f) ? (uint8_t)(out_status[i] & 0x3f) : (uint8_t)BN254_ACCEPT;
+    return BN254_OK;
+  };
+  rc = run();
   probe_ws_free();
   return rc;
 }

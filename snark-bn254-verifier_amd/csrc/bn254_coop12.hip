@@ -264,6 +264,43 @@ __global__ void __launch_bounds__(64) k_coop12_final_exp(int32_t* ws, uint32_t n
   c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
 }
 
+// ---- probe (bn254_dbg_coop12_op / bn254_dbg_verdict; tests): ONE operation on workspace values, called as the kernels of this file call it ---------------------------
+// Operands: VE_F (and VE_S1: the second factor, or a line d0 + d3 w + d4 w^3 given as the Fp12 with k0 = d0, k1 = d3, k3 = d4); result: VE_S0.  op 12 is the
+// comparison of the fused kernels: VE_F against `target`, the verdict to the status byte.  Five proofs per wavefront, the shadow lanes and the groups past
+// the batch run along as they do in the product.
+__global__ void __launch_bounds__(64) k_coop12_dbg_op(int32_t* ws, uint32_t n, uint8_t* status, int op_, int arg_, const int32_t* __restrict__ target) {
+  C12_PROLOGUE();
+  const int op = __builtin_amdgcn_readfirstlane(op_), arg = __builtin_amdgcn_readfirstlane(arg_);
+  const int F = C12_SLOT(VE_F), S0 = C12_SLOT(VE_S0), S1 = C12_SLOT(VE_S1);
+  co.put(F, c12_ws_ld(ws, n, pc, VE_F + 2 * (int)c + (int)h));
+  co.put(S1, c12_ws_ld(ws, n, pc, VE_S1 + 2 * (int)c + (int)h));
+  Coop12Ops ops{co};
+  int res = S0;
+  if (op == 0) ops.f12_mul(VE_S0, VE_F, VE_S1);
+  else if (op == 1) ops.f12_mul(VE_S0, VE_F, VE_S1, true);
+  else if (op == 2) ops.f12_mul(VE_S0, VE_F | VE_CONJ, VE_S1);
+  else if (op == 3) { c12_sqr(co, F); res = F; }
+  else if (op == 4) ops.f12_cyclo_sqr_n(VE_S0, VE_F, arg);
+  else if (op == 5) ops.f12_frob(VE_S0, VE_F, arg);
+  else if (op == 6) ops.f12_inv(VE_S0, VE_F);
+  else if (op == 7) ops.f12_conj(VE_S0, VE_F);
+  else if (op == 8 || op == 9) {
+    const Fp d0 = c12_ws_ld(ws, n, pc, VE_S1);
+    const Fp2 d3 = c12_ws_ld2(ws, n, pc, VE_S1 + 2), d4 = c12_ws_ld2(ws, n, pc, VE_S1 + 6);
+    c12_mul_line_fp(co, F, d0, c12_halves(d3, h), c12_halves(d4, h), op == 9);
+    res = F;
+  } else if (op == 10) {
+    const Fp2 d0 = c12_ws_ld2(ws, n, pc, VE_S1), d3 = c12_ws_ld2(ws, n, pc, VE_S1 + 2), d4 = c12_ws_ld2(ws, n, pc, VE_S1 + 6);
+    c12_mul_line_fp2(co, F, c12_halves(d0, h), c12_halves(d3, h), c12_halves(d4, h));
+    res = F;
+  } else {
+    const bool acc = c12_eq_const(co, F, target, pl);
+    if (pending && c == 0 && h == 0) status[p] = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
+    return;
+  }
+  c12_store_f12(co, ws, n, p, res, VE_S0, pending);
+}
+
 // ---- Miller loop of the table-driven pairs only (PlonK's two-pair check): f = prod_t Miller(P_t, Q_t), then (optionally) the final exponentiation -------------
 __global__ void __launch_bounds__(64)
 k_coop12_miller_fixed(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, int n_pairs,
@@ -667,5 +704,14 @@ hipError_t bn254_coop12_miller_g16_keys(int32_t* ws, uint8_t* status, size_t n, 
   const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
   (void)hipFuncSetAttribute((const void*)k_coop12_miller_g16_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(k_coop12_miller_g16_keys, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, key_index, desc, n_keys, inputs, input_stride, strict_scalars);
+  return hipGetLastError();
+}
+// probe: op 0 mul 1 mul by conj(b) 2 conj(a) * b 3 sqr 4 cyclo_sqr_n (arg squarings) 5 frob (j = arg) 6 inv 7 conj 8 mul_line_fp 9 mul_line_fp with keep
+// 10 mul_line_fp2 11 k_coop12_final_exp 12 c12_eq_const against target
+hipError_t bn254_coop12_dbg_op(int32_t* ws, uint8_t* status, size_t n, int op, int arg, const int32_t* target, hipStream_t s) {
+  if (op == 11) return bn254_coop12_final_exp(ws, status, n, s);
+  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
+  (void)hipFuncSetAttribute((const void*)k_coop12_dbg_op, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k_coop12_dbg_op, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, op, arg, target);
   return hipGetLastError();
 }

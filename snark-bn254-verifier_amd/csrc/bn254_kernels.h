@@ -217,7 +217,17 @@ static inline size_t bn254_coop_max_proofs_fixed() { return COOP12_MAX_PROOFS_FI
 double bn254_measure_valu_sustained(double ms_target);   // the same kernel back to back for ms_target milliseconds, one interval
 double bn254_measure_valu_peak(int reps);   // lane-level v_mad_u64_u32 per second of the current device at four wavefronts per SIMD
 hipError_t bn254_launch_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, hipStream_t s);
-hipError_t bn254_launch_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s);
+// formats of the Fp12 probes: 0 = 384 bytes (12 x 32, big-endian canonical, tower order), 1 = raw digits (12 x 9 int32 as the workspace holds them, same order)
+hipError_t bn254_launch_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s);     // formats 0, 0
+hipError_t bn254_launch_dbg_fp12_op_fmt(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, int in_format, int out_format, hipStream_t s);
+// k_dbg_load (kind 0 Fp12 bytes, 3 Fp12 raw digits -> element e; 4: G1 bytes -> e, e + 1; every kind sets the status bytes to PENDING) and the matching stores
+hipError_t bn254_launch_dbg_load(int32_t* ws, size_t n, uint8_t* status, int e, const void* src, int kind, hipStream_t s);
+hipError_t bn254_launch_dbg_store(int32_t* ws, size_t n, int e, void* dst, int format, hipStream_t s);
+hipError_t bn254_launch_dbg_verdict(int form, int32_t* ws, size_t n, uint8_t* status, const int32_t* target, hipStream_t s);
+hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs& a, hipStream_t s);
+// bn254_coop12.hip: ONE operation of the cooperative layout on workspace values (operands at VE_F and VE_S1, result at VE_S0; op numbers: bn254_verify.h,
+// bn254_dbg_coop12_op), or c12_eq_const of VE_F against target as the fused kernels vote it (op 12: status <- ACCEPT / REJECT)
+hipError_t bn254_coop12_dbg_op(int32_t* ws, uint8_t* status, size_t n, int op, int arg, const int32_t* target, hipStream_t s);
 // e(P_i, Q_i): needs a workspace of G16_WS_BYTES_PER_PROOF * n bytes and the step program
 hipError_t bn254_launch_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s);
 hipError_t bn254_launch_dbg_g2_ate(const uint8_t* g1, const uint8_t* g2, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s);

@@ -873,6 +873,8 @@ __global__ void __launch_bounds__(256, 2) k_dbg_fp_mul(const uint8_t* a, const u
 // Fp12 / pairing probes: bytes (tower order) <-> workspace (k order); the operations themselves are the product's VM kernels
 __global__ void __launch_bounds__(256, 2) k_dbg_load(int32_t* ws, uint32_t n, uint8_t* status, int e, const uint8_t* src, int kind) {
   // kind 0: Fp12 (384 B, tower order) -> element e; kind 1: G1 (64 B) -> VE_AX; kind 2: G2 (128 B, gnark order) -> VE_B; also marks the lane pending
+  // kind 3: Fp12 as RAW DIGITS (12 x 9 int32, the twelve numbers in the tower order of kind 0, digit 0 first) -> element e, stored as given: the caller chooses the
+  // representative (bn254_fp.h: Montgomery form, R = 2^261, balanced 29-bit digits) and answers for the operation's input contract; kind 4: G1 (64 B) -> e, e + 1
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   DevWs w(ws, n, i);
@@ -880,6 +882,12 @@ __global__ void __launch_bounds__(256, 2) k_dbg_load(int32_t* ws, uint32_t n, ui
     const int korder[6] = {0, 2, 4, 1, 3, 5};
     const uint8_t* p = src + 384 * (size_t)i;
     for (int t = 0; t < 6; t++) { w.st(e + 2 * korder[t], probe_ld_fp(p + 64 * t)); w.st(e + 2 * korder[t] + 1, probe_ld_fp(p + 64 * t + 32)); }
+  } else if (kind == 3) {
+    const int korder[6] = {0, 2, 4, 1, 3, 5};
+    const int32_t* p = (const int32_t*)src + 12 * BN_NL * (size_t)i;
+    for (int t = 0; t < 12; t++) { Fp a; for (int l = 0; l < BN_NL; l++) a.v[l] = p[t * BN_NL + l]; w.st(e + 2 * korder[t >> 1] + (t & 1), a); }
+  } else if (kind == 4) {
+    w.st(e, probe_ld_fp(src + 64 * (size_t)i)); w.st(e + 1, probe_ld_fp(src + 64 * (size_t)i + 32));
   } else if (kind == 1) {
     w.st(VE_AX, probe_ld_fp(src + 64 * (size_t)i)); w.st(VE_AY, probe_ld_fp(src + 64 * (size_t)i + 32));
   } else {
@@ -895,6 +903,15 @@ __global__ void __launch_bounds__(256, 2) k_dbg_store(int32_t* ws, uint32_t n, i
   const int korder[6] = {0, 2, 4, 1, 3, 5};
   uint8_t* p = dst + 384 * (size_t)i;
   for (int t = 0; t < 6; t++) { probe_st_fp(p + 64 * t, w.ld(e + 2 * korder[t])); probe_st_fp(p + 64 * t + 32, w.ld(e + 2 * korder[t] + 1)); }
+}
+// the digits of element e as the workspace holds them (12 x 9 int32 per proof, the order of k_dbg_load's kind 3)
+__global__ void __launch_bounds__(256, 2) k_dbg_store_raw(int32_t* ws, uint32_t n, int e, int32_t* dst) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  DevWs w(ws, n, i);
+  const int korder[6] = {0, 2, 4, 1, 3, 5};
+  int32_t* p = dst + 12 * BN_NL * (size_t)i;
+  for (int t = 0; t < 12; t++) { const Fp a = w.ld(e + 2 * korder[t >> 1] + (t & 1)); for (int l = 0; l < BN_NL; l++) p[t * BN_NL + l] = a.v[l]; }
 }
 __global__ void __launch_bounds__(256, 2) k_dbg_g2_subgroup(const uint8_t* g2, uint8_t* o, size_t n) {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1265,21 +1282,56 @@ hipError_t bn254_launch_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* 
   hipLaunchKernelGGL(k_dbg_fp_mul, dim3(grid_for(n)), dim3(256), 0, s, a, b, o, n);
   return hipGetLastError();
 }
-// op: 0 mul 1 sqr 2 inv 3 cyclo_sqr(easy part) 4 frob1.  status: n scratch bytes on the device
+hipError_t bn254_launch_dbg_load(int32_t* ws, size_t n, uint8_t* status, int e, const void* src, int kind, hipStream_t s) {
+  hipLaunchKernelGGL(k_dbg_load, dim3(grid_for(n)), dim3(256), 0, s, ws, (uint32_t)n, status, e, (const uint8_t*)src, kind);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_dbg_store(int32_t* ws, size_t n, int e, void* dst, int format, hipStream_t s) {
+  if (format) hipLaunchKernelGGL(k_dbg_store_raw, dim3(grid_for(n)), dim3(256), 0, s, ws, (uint32_t)n, e, (int32_t*)dst);
+  else hipLaunchKernelGGL(k_dbg_store, dim3(grid_for(n)), dim3(256), 0, s, ws, (uint32_t)n, e, (uint8_t*)dst);
+  return hipGetLastError();
+}
+// op: 0 mul 1 sqr 2 inv 3 cyclo_sqr(easy part) 4 frob1 5 cyclo_sqr 6 frob2 7 frob3 8 mul by conj(b) 9 conj(a) * b (VE_CONJ on a).  status: n scratch bytes on the
+// device.  in_format / out_format: 0 bytes (384 per value), 1 raw digits (k_dbg_load kind 3 / k_dbg_store_raw)
 hipError_t bn254_launch_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s) {
+  return bn254_launch_dbg_fp12_op_fmt(op, a, b, o, n, ws, status, 0, 0, s);
+}
+hipError_t bn254_launch_dbg_fp12_op_fmt(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, int in_format, int out_format, hipStream_t s) {
   unsigned g = grid_for(n);
   uint32_t nn = (uint32_t)n;
   LaunchOps ops{ws, nn, status, g, s, {nullptr, nullptr, nullptr}, nullptr};
-  hipLaunchKernelGGL(k_dbg_load, dim3(g), dim3(256), 0, s, ws, nn, status, (int)VE_F, a, 0);
-  if (op == 0) { hipLaunchKernelGGL(k_dbg_load, dim3(g), dim3(256), 0, s, ws, nn, status, (int)VE_S1, b, 0); ops.f12_mul(VE_S0, VE_F, VE_S1); }
+  const int kind = in_format ? 3 : 0;
+  hipLaunchKernelGGL(k_dbg_load, dim3(g), dim3(256), 0, s, ws, nn, status, (int)VE_F, a, kind);
+  if (op == 0 || op == 8 || op == 9) {
+    hipLaunchKernelGGL(k_dbg_load, dim3(g), dim3(256), 0, s, ws, nn, status, (int)VE_S1, b, kind);
+    ops.f12_mul(VE_S0, op == 9 ? (VE_F | VE_CONJ) : VE_F, VE_S1, op == 8);
+  }
   else if (op == 1) { ops.f12_sqr(VE_F); ops.f12_conj(VE_S0, VE_F); ops.f12_conj(VE_S0, VE_S0); }
   else if (op == 2) ops.f12_inv(VE_S0, VE_F);
   else if (op == 3) {
     ops.f12_inv(VE_S0, VE_F); ops.f12_conj(VE_S1, VE_F); ops.f12_mul(VE_S0, VE_S1, VE_S0); ops.f12_frob(VE_S1, VE_S0, 2);
     ops.f12_mul(VE_S0, VE_S1, VE_S0); ops.f12_cyclo_sqr(VE_S0, VE_S0);
-  } else ops.f12_frob(VE_S0, VE_F, 1);
-  hipLaunchKernelGGL(k_dbg_store, dim3(g), dim3(256), 0, s, ws, nn, (int)VE_S0, o);
+  }
+  else if (op == 5) ops.f12_cyclo_sqr(VE_S0, VE_F);
+  else ops.f12_frob(VE_S0, VE_F, op == 6 ? 2 : op == 7 ? 3 : 1);
+  (void)bn254_launch_dbg_store(ws, n, (int)VE_S0, o, out_format, s);
   return hipGetLastError();
+}
+// the two compares of the lane kernels on values a caller placed (bn254_dbg_verdict): form 0 k_g16_compare of VE_S0; form 1 k_f12_mul_verdict, the product's last
+// launch dst = VE_S0 <- VE_S2 * VE_S0 compared as it is stored.  status: PENDING on entry, ACCEPT / REJECT on return
+hipError_t bn254_launch_dbg_verdict(int form, int32_t* ws, size_t n, uint8_t* status, const int32_t* target, hipStream_t s) {
+  unsigned grid = grid_for(n);
+  uint32_t nn = (uint32_t)n;
+  if (form == 0) hipLaunchKernelGGL(k_g16_compare, dim3(grid), dim3(256), 0, s, ws, nn, status, target, (int)BN254_ST_REJECT);
+  else hipLaunchKernelGGL(k_f12_mul_verdict, dim3(grid), dim3(256), 0, s, ws, nn, status, (int)VE_S0, (int)VE_S2, (int)VE_S0, target, (int)BN254_ST_REJECT, (const uint32_t*)nullptr, status);
+  return hipGetLastError();
+}
+// k_g16_prepare as a cooperative launch runs it, then k_coop12_miller_g16 in its store mode (fuse_final_exp, no target): the GT value of every proof still pending
+// after the loader is left in VE_S0, its status byte keeps PENDING.  Keys with at most G16_WIDE_MSM_MIN_INPUTS inputs (L by the cooperative kernel itself)
+hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(k_g16_prepare, dim3(grid_for(a.n)), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.n_public, (uint32_t)a.n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, 1,
+                     (const uint32_t*)nullptr, (uint8_t*)nullptr);
+  return bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, 0, 1, nullptr, s);
 }
 hipError_t bn254_launch_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s) {
   unsigned g = grid_for(n);

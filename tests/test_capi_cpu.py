@@ -452,3 +452,77 @@ def test_groth16_rlc_group_buffer_fits(pkg):
                     for min_lanes in (1, 65536):
                         assert L.bn254_dbg_g16_rlc_plan(m, m, n_streams, lg, ls, min_lanes, C.byref(need), C.byref(alloc)) == 0
                         assert need.value <= alloc.value, (m, n_streams, lg, ls, min_lanes, need.value, alloc.value)
+
+
+def test_value_probe_arguments_are_checked(pkg):
+    """The value-level probes (bn254_dbg_coop12_op, bn254_dbg_fp12_op_fmt, bn254_dbg_verdict, bn254_dbg_coop12_miller_fixed / _g16) refuse null pointers, unknown
+    operations, forms and formats, n = 0 and a batch beyond what their kernels take -- before any device is looked for."""
+    L = pkg.lib()
+    BAD = -1
+    L.bn254_dbg_coop12_op.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.bn254_dbg_fp12_op_fmt.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int]
+    L.bn254_dbg_verdict.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int]
+    L.bn254_dbg_coop12_miller_fixed.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int]
+    L.bn254_dbg_coop12_miller_g16.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int]
+    a, out, st = bytes(432), (C.c_uint8 * 432)(), (C.c_uint8 * 4)()
+    one = (1).to_bytes(32, "big") + bytes(352)
+    for args in ((0, None, a, out, 1, 0, 0, 0, 0), (0, a, None, out, 1, 0, 0, 0, 0), (0, a, a, None, 1, 0, 0, 0, 0),          # null a, b (a product), out
+                 (8, a, None, out, 1, 0, 0, 0, 0),                                                                             # a line product without its line
+                 (-1, a, a, out, 1, 0, 0, 0, 0), (12, a, a, out, 1, 0, 0, 0, 0), (99, a, a, out, 1, 0, 0, 0, 0),               # unknown op (12 is the verdict's own)
+                 (0, a, a, out, 0, 0, 0, 0, 0), (0, a, a, out, 30721, 0, 0, 0, 0),                                             # n = 0, n beyond COOP12_MAX_PROOFS
+                 (0, a, a, out, 1, 2, 0, 0, 0), (0, a, a, out, 1, 0, -1, 0, 0),                                                # formats
+                 (4, a, None, out, 1, 0, 0, 0, 0), (4, a, None, out, 1, 0, 0, 65, 0), (5, a, None, out, 1, 0, 0, 0, 0), (5, a, None, out, 1, 0, 0, 4, 0)):   # count, power
+        assert L.bn254_dbg_coop12_op(*args) == BAD, args
+    for args in ((0, None, a, out, 1, 0, 0, 0), (0, a, None, out, 1, 0, 0, 0), (1, a, None, None, 1, 0, 0, 0), (10, a, a, out, 1, 0, 0, 0), (-1, a, a, out, 1, 0, 0, 0),
+                 (1, a, None, out, 1, 2, 0, 0), (1, a, None, out, 1, 0, 2, 0), (1, a, None, out, 786433, 0, 0, 0)):
+        assert L.bn254_dbg_fp12_op_fmt(*args) == BAD, args
+    for args in ((0, None, None, one, st, 1, 0, 0), (1, a, None, one, st, 1, 0, 0), (0, a, None, None, st, 1, 0, 0), (0, a, None, one, None, 1, 0, 0),
+                 (3, a, a, one, st, 1, 0, 0), (-1, a, a, one, st, 1, 0, 0), (0, a, None, one, st, 0, 0, 0), (2, a, None, one, st, 30721, 0, 0), (0, a, None, one, st, 786433, 0, 0),
+                 (0, a, None, one, st, 1, 2, 0), (0, a, None, b"\xff" * 384, st, 1, 0, 0)):                                    # .. and a target that is not canonical
+        assert L.bn254_dbg_verdict(*args) == BAD, args
+    vk = pkg.synth_groth16(7, 2, 0)[0]
+    pvk = pkg.PreparedVk(vk, pkg.VK_GNARK)
+    g1, pr, gt = bytes(64), bytes(256), (C.c_uint8 * 384)()
+    for args in ((None, 1, g1, None, None, gt, 1, 0), (pvk.handle, 0, g1, g1, None, gt, 1, 0), (pvk.handle, 3, g1, g1, None, gt, 1, 0), (pvk.handle, 1, None, None, None, gt, 1, 0),
+                 (pvk.handle, 2, g1, None, None, gt, 1, 0), (pvk.handle, 1, g1, None, None, None, 1, 0), (pvk.handle, 1, g1, None, None, gt, 0, 0),
+                 (pvk.handle, 1, g1, None, None, gt, 40961, 0)):
+        assert L.bn254_dbg_coop12_miller_fixed(*args) == BAD, args
+    for args in ((None, pr, a, 2, 1, gt, st, 0), (pvk.handle, None, a, 2, 1, gt, st, 0), (pvk.handle, pr, None, 2, 1, gt, st, 0), (pvk.handle, pr, a, 2, 1, None, st, 0),
+                 (pvk.handle, pr, a, 2, 1, gt, None, 0), (pvk.handle, pr, a, 2, 0, gt, st, 0), (pvk.handle, pr, a, 2, 30721, gt, st, 0), (pvk.handle, pr, a, 3, 1, gt, st, 0),
+                 (pvk.handle, pr, a, 17, 1, gt, st, 0)):                                                                       # .. another input count than the key's; a wide key's
+        assert L.bn254_dbg_coop12_miller_g16(*args) == BAD, args
+    pvk.close()
+    # the entry the existing tests use keeps its meaning: n = 0 is an empty batch
+    assert L.bn254_dbg_fp12_op(0, a, a, out, C.c_size_t(0), 0) == 0 or _no_gpu()
+
+
+def test_digit_encoder_of_the_value_probes():
+    """tests/fp12_digits.py, the encoder behind the raw-digit operands: integers round-trip, the eight low digits are balanced, m, m + p and m - p decode to the same
+    field value and lie inside the operations' contract, the digit patterns are what they say and stay below p."""
+    import random
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fp12_digits as D
+    rng = random.Random(0xD161)
+    xs = [0, 1, 2, D.P - 1, D.P - 2, (D.P - 1) // 2, D.R261_INV, (D.P - D.R261_INV) % D.P] + [rng.randrange(D.P) for _ in range(500)]
+    for x in xs:
+        m = D.mont(x)
+        assert 0 <= m < D.P and m * D.R261_INV % D.P == x
+        for s in (0, 1, -1):
+            d = D.encode(m + s * D.P)
+            assert len(d) == 9 and all(-(1 << 28) <= v < (1 << 28) for v in d[:8]) and -(1 << 31) <= d[8] < (1 << 31)
+            assert D.decode(d) == m + s * D.P and D.field_value(d) == x and D.in_contract(d)
+        assert D.encode(-m) == [-v for v in D.encode(m)] or (1 << 28) in [abs(v) for v in D.encode(m)[:8]]     # balanced digits negate digit-wise (but for -2^28)
+    for v in (-(1 << 259), (1 << 259) - 1, 3 * D.P, -3 * D.P, 1 << 232, (1 << 28), -(1 << 28) - 1):
+        assert D.decode(D.encode(v)) == v
+    assert not D.in_contract(D.encode(2 * D.P + 1)) and not D.in_contract(D.encode(-2 * D.P - 1)) and D.in_contract(D.encode(2 * D.P))
+    assert not D.in_contract([1 << 28] + [0] * 8) and D.in_contract([-(1 << 28)] + [0] * 8)
+    with pytest.raises(ValueError):
+        D.encode(1 << 263)
+    for kind, low in ((0, [-(1 << 28)] * 8), (1, [(1 << 28) - 1] * 8), (2, [-(1 << 28), (1 << 28) - 1] * 4), (3, [(1 << 28) - 1, -(1 << 28)] * 4)):
+        for top in (1, 2000, 3000000):
+            d = D.pattern(kind, top)
+            assert d == low + [top] and D.in_contract(d, 1) and D.encode(D.decode(d)) == d
+    reps = [D.encode(D.mont(x)) for x in xs[:12]]
+    assert D.unpack12(D.pack12(reps)) == reps and len(D.pack12(reps)) == 432
+    assert D.vals12(D.bytes12(xs[:12])) == xs[:12]
