@@ -295,6 +295,47 @@ void bn254_set_plonk_params(long piece, int workers, long big_from, long big_pie
 #define BN254_PLONK_NUM_TIMINGS 9
 int bn254_plonk_last_timing(const bn254_plonk_pvk* pvk, int device, float ms[BN254_PLONK_NUM_TIMINGS], size_t lanes[2]);
 
+/* ---- PlonK batches over many keys ---------------------------------------------------------------------------------------------------------------------------
+ * One call for PlonK proofs of many circuits, the twin of bn254_groth16_verify_batch_keys.  pvks: a list of n_keys prepared keys (1 .. 256 entries; a handle may occur
+ * more than once; the keys may differ in public-input count, domain size and KZG points).  Proof i is verified against pvks[key_index[i]] (key_index: n 32-bit
+ * unsigned little-endian words).  Its public inputs are the first 32 * num_public(that key) bytes of row i of public_inputs; rows are input_stride bytes apart, bytes
+ * behind a key's inputs are never read, and input_stride must be at least 32 * the largest num_public of the list, else BN254_E_BAD_ARG (a list of keys without
+ * inputs may pass a null pointer and stride 0).  Records are proof_stride >= 808 + 96 * n_qcp bytes apart.
+ *   DEFINITION OF CORRECTNESS: status[i] equals, byte for byte, what bn254_plonk_verify_batch_flags(pvks[key_index[i]], proof_i, inputs_i, n_public =
+ * bn254_plonk_vk_num_public(that key), 1, ..., flags = 0) writes.  n_keys == 1 gives the single-key bytes.  Because the width of a row comes from the proof's key,
+ * BN254_ERR_INPUT_LEN cannot occur.
+ *   ALL ENTRIES OF A LIST MUST HAVE THE SAME NUMBER OF BSB22 COMMITMENTS: that number fixes the term counts and the multi-scalar-multiplication plans of a pass (one
+ * list per commitment count).  A list that mixes counts, and one of more than 256 entries, is refused with BN254_E_BAD_ARG and a text in bn254_last_diagnostic().
+ *   Argument errors (BN254_E_BAD_ARG, before any device is touched, status untouched): a null pointer with n > 0, an empty list, a null member, proof_stride below
+ * 808 + 96 * n_qcp, input_stride below the widest key's row, any flag other than BN254_FLAG_RLC.  n == 0 returns BN254_OK and touches nothing.
+ *   key_index[i] >= n_keys: the host-buffer entry checks the whole vector first, returns BN254_E_BAD_ARG, names the position in bn254_last_error() and leaves status
+ * untouched; the device entry cannot, writes BN254_ERR_MALFORMED for that proof and verifies the others.
+ *   BN254_FLAG_RLC is accepted and IGNORED: by its contract the status bytes are those of the exact path (a group of 64 proofs would hold up to 64 keys).
+ *   How it runs: the proofs are grouped on the device so that every granule of 64 slots holds proofs of one key (at most 63 idle slots per key that has proofs), the
+ * plan of the single-key entry (bn254_set_plonk_params) is made over slots with every cut on a granule boundary, and each pass gathers its records and input rows
+ * into slot order, runs the stage, multi-scalar-multiplication and pairing kernels with the key read per granule, and scatters the status bytes back.  A pass always
+ * takes the one-proof-per-lane (throughput) form of the pairing check; the cooperative and two-chain forms of the single-key entry read one key per launch.  SMALL
+ * BATCHES OF FEW KEYS ARE NOT THIS REVISION'S TARGET.  Measured on one MI355X (profiles/r13_plonk_keys.txt; device-resident proofs of the SP1
+ * key shape, n proofs spread evenly over K keys): one call beats one bn254_plonk_verify_batch_device call per key in every cell with K >= 4 -- n = 4096: 10.8 ms
+ * against 13.3 ms (K = 4), 52.7 ms (16), 209 ms (64); n = 65 536: 20.5 / 20.9 / 21.2 ms against 41.2 / 55.5 / 213 ms; n = 262 144: 78.4 / 74.7 / 75.5 ms against
+ * 82.8 / 166 / 222 ms -- and from 65 536 proofs on it takes 0.95 to 1.01 of the single-key entry's time on as many proofs of ONE key.  It loses where the list has
+ * one key and the batch is small: 4096 proofs of one key take 10.8 ms through a list and 3.6 ms through the single-key entry, which runs the cooperative kernel.
+ *   Both entries are host-synchronous, like bn254_plonk_verify_batch_device; the _device entry first waits for hip_stream.  Calls on one list from several host threads
+ * run side by side (the list owns eight pass contexts, leased as a key's are).
+ *   Device state of a list: kept per (list of handles in order, device), the four most recently used lists; bn254_plonk_vk_free of a member drops every cached list
+ * that contains it.  A list uses its members' OWN per-device tables: its first use makes every distinct member ready on the device (window tables of 13 MB per key
+ * point, 131 MB for the SP1 key shape, and the key's self-test), after which the member is ready for single-key calls too.
+ *   bn254_plonk_reserve_keys: after it, a call with the same handles in the same order, records of the same proof_stride and up to n proofs allocates nothing
+ * (contexts for keys_slot_bound = n + min(n_keys, n) * 63 slots, the grouping buffers and the staging of the host-buffer entry for rows of 32 * the widest key);
+ * BN254_E_NOMEM when the tables or the contexts do not fit.
+ *   Not in this revision: lists that mix commitment counts, RLC groups, the cooperative / latency pairing forms for small mixed batches, a _multi entry, SP1 proofs
+ * from their public values over a list, more than 256 entries. */
+int bn254_plonk_verify_batch_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride,
+                                  const uint8_t* public_inputs, size_t input_stride, size_t n, uint8_t* status, int device, unsigned flags);
+int bn254_plonk_verify_batch_keys_device(const bn254_plonk_pvk* const* pvks, size_t n_keys, const void* d_key_index, const void* d_proofs, size_t proof_stride,
+                                         const void* d_public_inputs, size_t input_stride, size_t n, void* d_status, int device, void* hip_stream, unsigned flags);
+int bn254_plonk_reserve_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, size_t n, size_t proof_stride, int device);
+
 /* ---- gnark / SP1 formats, both directions (host only) ------------------------------------------------------------------
  * Point codecs of verifier/src/converter.rs:23-153.  compress: uncompressed big-endian coordinates (G1: x | y; G2: x.c1 | x.c0 |
  * y.c1 | y.c0) -> gnark compressed form (flag 0b10 / 0b11 = lexicographically smallest / largest y in the top two bits).
@@ -560,6 +601,11 @@ int bn254_dbg_g16_keys_group(const unsigned* key_index, size_t n, size_t n_keys,
 int bn254_dbg_g16_keys_plan(size_t n, size_t n_keys, int* form, size_t* slots, int* launches);
 /* the form of the last batch enqueued on the cached state of (list, device): 0 or 1 as above, -1 if there was none (also: the list is not cached) */
 int bn254_dbg_g16_keys_last_form(const bn254_g16_pvk* const* pvks, size_t n_keys, int device, int* form);
+/* The plan of a PlonK batch over many keys (host arithmetic only): n proofs over n_keys entries whose grouping came to `slots` slots (a multiple of 64), under the
+ * current knobs.  slot_bound: n + min(n_keys, n) * 63 rounded to 64; workers / per_worker / per_pass: sub-batches side by side, slots per sub-batch, slots per pass;
+ * ctx_capacity: slots a context holds after bn254_plonk_reserve_keys for (n, n_keys); pass_first: the first slot of each pass (up to cap entries), n_passes: how many. */
+int bn254_dbg_plonk_keys_plan(size_t n, size_t n_keys, size_t slots, size_t* slot_bound, int* workers, size_t* per_worker, size_t* per_pass, size_t* ctx_capacity,
+                              size_t* pass_first, size_t cap, size_t* n_passes);
 /* the host image of a prepared Groth16 key, serialised: dwords n_k (2) | msm_comb | k0, gtab, dtab, target, kpts, each as its length and its dwords | alpha (18),
  * k0_pt (18), b_arg (36) as canonical digits.  Two handles of one key are interchangeable iff their images are equal.  *len: bytes of the image (always written);
  * a null or too small out (cap bytes) is BN254_E_BAD_ARG */

@@ -293,6 +293,7 @@ class PreparedPlonkVk {
     detail::check(bn254_plonk_verify_batch_device(h_, d_proofs, stride, d_public_inputs, n_public, n, d_status, device, hip_stream, flags));
   }
   void reserve(size_t n, size_t proof_stride = 0, int device = 0) const { detail::check(bn254_plonk_reserve(h_, n, proof_stride, device)); }
+  const bn254_plonk_pvk* handle() const { return h_; }
 
  private:
   bn254_plonk_pvk* h_ = nullptr;
@@ -331,6 +332,22 @@ struct PlonkVerifier {
       if (bad) st[i] = BN254_ERR_MALFORMED;
     }
     return st;
+  }
+  // one batch over many keys (bn254_verify.h, "PlonK batches over many keys"): proof i is verified against keys[key_index[i]]; its inputs are the first
+  // 32 * num_public(that key) bytes of row i of public_inputs (rows input_stride bytes apart).  At most 256 keys, all with the same number of BSB22 commitments
+  static Bytes verify_batch_keys(const std::vector<const PreparedPlonkVk*>& keys, const std::vector<unsigned>& key_index, const uint8_t* proofs, size_t stride,
+                                 const uint8_t* public_inputs, size_t input_stride, int device = 0, unsigned flags = 0) {
+    std::vector<const bn254_plonk_pvk*> h(keys.size());
+    for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
+    Bytes st(key_index.size() ? key_index.size() : 1);
+    detail::check(bn254_plonk_verify_batch_keys(h.data(), h.size(), key_index.data(), proofs, stride, public_inputs, input_stride, key_index.size(), st.data(), device, flags));
+    st.resize(key_index.size());
+    return st;
+  }
+  static void reserve_keys(const std::vector<const PreparedPlonkVk*>& keys, size_t n, size_t proof_stride, int device = 0) {
+    std::vector<const bn254_plonk_pvk*> h(keys.size());
+    for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
+    detail::check(bn254_plonk_reserve_keys(h.data(), h.size(), n, proof_stride, device));
   }
   static Result<bool, PlonkError> outcome(uint8_t status) { return detail::plonk_outcome(status); }
 };

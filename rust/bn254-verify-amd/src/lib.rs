@@ -276,6 +276,25 @@ impl PlonkVerifier {
             s => panic!("loader error {s:?}"),                                // lib.rs:70-71
         }
     }
+    /// One batch over many keys (`bn254_plonk_verify_batch_keys`): proof `i` is verified against `keys[key_index[i]]`; its inputs are the first
+    /// `32 * num_public(that key)` bytes of row `i` of `public_inputs` (`input_stride` bytes per row, at least 32 x the largest input count of the list).  At most 256
+    /// keys, all with the same number of BSB22 commitments; a key may occur more than once; an index outside the list is refused (`BN254_E_BAD_ARG`).
+    /// `BN254_FLAG_RLC` is accepted and ignored.  The device state of the list is cached by the library under the handles in order.
+    pub fn verify_batch_keys(keys: &[&PreparedPlonkVk], key_index: &[u32], proofs: &[u8], proof_stride: usize, public_inputs: &[u8], input_stride: usize, device: i32,
+                             flags: u32) -> Result<Vec<Status>, Error> {
+        let n = key_index.len();
+        assert!(proofs.len() >= n * proof_stride && public_inputs.len() >= n * input_stride);
+        let h: Vec<*const sys::Bn254PlonkPvk> = keys.iter().map(|k| k.h as *const sys::Bn254PlonkPvk).collect();
+        let mut st = vec![0u8; n];
+        check(unsafe { sys::bn254_plonk_verify_batch_keys(h.as_ptr() as *mut *const sys::Bn254PlonkPvk, h.len(), key_index.as_ptr(), proofs.as_ptr(), proof_stride, public_inputs.as_ptr(), input_stride, n,
+                                                          st.as_mut_ptr(), device, flags) })?;
+        Ok(st.into_iter().map(Status::from).collect())
+    }
+    /// Members' tables, contexts and staging of a key list ahead of its first batch of up to `n` proofs of `proof_stride` bytes (`bn254_plonk_reserve_keys`).
+    pub fn reserve_keys(keys: &[&PreparedPlonkVk], n: usize, proof_stride: usize, device: i32) -> Result<(), Error> {
+        let h: Vec<*const sys::Bn254PlonkPvk> = keys.iter().map(|k| k.h as *const sys::Bn254PlonkPvk).collect();
+        check(unsafe { sys::bn254_plonk_reserve_keys(h.as_ptr() as *mut *const sys::Bn254PlonkPvk, h.len(), n, proof_stride, device) })
+    }
     pub fn verify_batch(proofs: &[&[u8]], vk: &[u8], public_inputs: &[&[[u8; 32]]]) -> Result<Vec<Status>, Error> {
         assert_eq!(proofs.len(), public_inputs.len());
         let pvk = PreparedPlonkVk::new(vk)?;

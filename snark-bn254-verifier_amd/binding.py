@@ -589,6 +589,60 @@ class KeySet:
         return int(form.value)
 
 
+class PlonkKeySet:
+    """A list of prepared PlonK keys for batches over many keys (bn254_plonk_verify_batch_keys): proof i is verified against keys[key_index[i]].  keys:
+    PreparedPlonkVk objects (one may occur more than once; at most 256 entries, all with the same number of BSB22 commitments); the list keeps them alive."""
+
+    def __init__(self, keys):
+        self.keys = list(keys)
+        self._arr = (C.c_void_p * max(len(self.keys), 1))(*[k._h.value for k in self.keys])
+        self.input_stride = 32 * max([k.n_public for k in self.keys] or [0])
+
+    def verify_batch(self, key_index, proofs, public_inputs, n=None, proof_stride=904, input_stride=None, device=0, flags=0):
+        """key_index: n ints; proofs: n records of proof_stride bytes; public_inputs: n rows of input_stride bytes (default: 32 x the largest input count of the
+        list), row i holding the inputs of proof i's key first.  Returns n status bytes."""
+        import array
+        idx = array.array("I", key_index)
+        n = len(idx) if n is None else n
+        st = (C.c_uint8 * max(n, 1))()
+        fn = lib().bn254_plonk_verify_batch_keys
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_uint]
+        _check(fn(self._arr, len(self.keys), idx.buffer_info()[0] if len(idx) else None, bytes(proofs), proof_stride, bytes(public_inputs) if public_inputs is not None else None,
+                  self.input_stride if input_stride is None else input_stride, n, st, device, flags))
+        return bytes(st)[:n]
+
+    def verify_batch_device(self, d_key_index, d_proofs, d_inputs, d_status, n, proof_stride=904, input_stride=None, device=0, stream=None, flags=0):
+        """Raw device pointers (ints; d_key_index: n uint32 values).  Host-synchronous: waits for `stream`, returns when the status bytes are in d_status."""
+        fn = lib().bn254_plonk_verify_batch_keys_device
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+        _check(fn(self._arr, len(self.keys), d_key_index, d_proofs, proof_stride, d_inputs, self.input_stride if input_stride is None else input_stride, n, d_status, device,
+                  stream, flags))
+
+    def reserve(self, n, proof_stride=904, device=0):
+        fn = lib().bn254_plonk_reserve_keys
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+        _check(fn(self._arr, len(self.keys), n, proof_stride, device))
+
+
+def dbg_plonk_keys_plan(n, n_keys, slots):
+    """The plan of a PlonK batch over many keys (bn254_dbg_plonk_keys_plan): dict with slot_bound, workers, per_worker, per_pass, ctx_capacity and pass_first."""
+    fn = lib().bn254_dbg_plonk_keys_plan
+    P = C.POINTER(C.c_size_t)
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, P, C.POINTER(C.c_int), P, P, P, P, C.c_size_t, P]
+    bound, per, pas, cap, np_ = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+    w = C.c_int(0)
+    first = (C.c_size_t * 8192)()
+    _check(fn(n, n_keys, slots, C.byref(bound), C.byref(w), C.byref(per), C.byref(pas), C.byref(cap), first, 8192, C.byref(np_)))
+    assert np_.value <= 8192
+    return dict(slot_bound=bound.value, workers=w.value, per_worker=per.value, per_pass=pas.value, ctx_capacity=cap.value, pass_first=list(first[:np_.value]))
+
+
+def last_diagnostic():
+    """bn254_last_diagnostic() of the calling thread."""
+    lib().bn254_last_diagnostic.restype = C.c_char_p
+    return (lib().bn254_last_diagnostic() or b"").decode()
+
+
 def dbg_keys_group(key_index, n_keys, device=-1):
     """The grouping of a batch over many keys (bn254_dbg_g16_keys_group; device -1: the host compile of csrc/bn254_keys.h): (slot_to_proof, granule_key, n_slots) --
     slot_to_proof has the workspace bound's length (0xffffffff: no proof), granule_key one entry per 64 slots."""

@@ -340,6 +340,14 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 #else
 void keys_sets_drop(const bn254_g16_pvk*) {}
 #endif
+// PlonK batches over many keys: tests/hostsan/hostsan_plonk_keys.cpp brings the file (after this one) and stand-ins for its launchers; every other harness only needs
+// the hook of bn254_plonk_vk_free
+#if !defined(BN254_HOSTSAN_PLONK_KEYS)
+void plonk_keys_sets_drop(const bn254_plonk_pvk*) {}
+hipError_t bn254_launch_g1_msm_rows_keys(const MsmPlan&, const int32_t*, const uint8_t*, size_t, int, int32_t*, int32_t*, const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, hipStream_t) {
+  return hipErrorInvalidDeviceFunction;      // plonk_msm (bn254_capi_plonk.hip) names it; without the key-set file nothing passes it a key list
+}
+#endif
 // the direct form of a batch over many keys: a host build starts with the knob at 0 (bn254_capi_keys.hip), so this is never reached unless a harness turns the knob --
 // and that harness brings its own stand-in (tests/hostsan/hostsan_keys_small.cpp)
 #if defined(BN254_HOSTSAN_KEYS) && !defined(BN254_HOSTSAN_KEYS_DIRECT)

@@ -14,6 +14,7 @@
 #include "bn254_plonk.hpp"
 #include "bn254_rlc.h"
 #include "bn254_g16_plan.h"
+#include "bn254_keys.h"
 #include <sys/random.h>
 #include <atomic>
 #include <thread>
@@ -36,6 +37,13 @@ hipError_t bn254_launch_plonk_stage1(const void* d_key, const uint8_t* d_proofs,
                                      void* d_work, void* d_terms, uint8_t* d_flags, int T1, hipStream_t s);
 hipError_t bn254_launch_plonk_stage2(const void* d_key, const uint8_t* d_proofs, size_t stride, size_t n, void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf,
                                      void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2, const uint32_t* weight_key, hipStream_t s);
+// the stages over the slots of a batch over many keys (bn254_keys.h: the key per granule of 64 slots)
+hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t proof_len,
+                                          const uint8_t* d_inputs, size_t in_stride, size_t staged_public, size_t n, const uint32_t lam_key[11], void* d_work, void* d_terms,
+                                          uint8_t* d_flags, int T1, hipStream_t s);
+hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                          void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
+                                          hipStream_t s);
 hipError_t bn254_launch_plonk_group_sums(int32_t* ws, const uint8_t* status, size_t n, int32_t* grp_ws, uint8_t* grp_status, int e_p0, int inf0, int e_p1, int inf1, hipStream_t s);
 hipError_t bn254_launch_plonk_group_scatter(uint8_t* status, size_t n, const uint8_t* grp_status, uint32_t* n_failed, hipStream_t s);
 
@@ -258,6 +266,13 @@ size_t msm_lane_budget();
 size_t plonk_scratch_lanes(size_t need, int n_var);
 size_t plonk_part_points(size_t need, const MsmShape& shape);
 void plonk_plan(size_t n, size_t piece, int max_workers, int* workers, size_t* per, size_t* pass);
+void plonk_plan_for(size_t n, int* workers, size_t* per, size_t* pass_cap);     // the plan of a batch of n proofs (or slots) under the current knobs
+size_t plonk_piece_for(size_t n, int* max_workers);
+int plonk_plan_breaks(size_t out[4]);
+// one MSM launch of a pass on context c (rows + sums).  keys: the descriptors and the granule -> key words of a pass over the slots of a batch over many keys
+struct PlonkKeysRef { const bn254::PlonkKeyDesc* desc; uint32_t n_keys; const uint32_t* granule_key; };
+int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows);
+void plonk_keys_sets_drop(const bn254_plonk_pvk* member);   // bn254_capi_plonk_keys.hip: forget every cached PlonK key set that contains this key
 // a PlonK batch whose public inputs are already rows of two inputs in device memory (d_rows, 64 bytes per proof): resident = true, proofs and status are device
 // memory too; false, they are host buffers and only the proofs are staged
 int plonk_batch_rows(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* d_rows, size_t n, uint8_t* status, int device, unsigned flags,

@@ -167,6 +167,7 @@ int bn254_plonk_vk_prepare(const uint8_t* vk, size_t vk_len, bn254_plonk_pvk** o
 }
 void bn254_plonk_vk_free(bn254_plonk_pvk* pvk) {
   if (!pvk) return;
+  plonk_keys_sets_drop(pvk);      // every cached key set that contains it (their descriptors point into the device state released below)
   for (auto it = pvk->dev.begin(); it != pvk->dev.end();) {
     if (hipSetDevice(it->first) != hipSuccess) { ++it; continue; }   // (its state goes with the key below, without the wait)
     (void)hipDeviceSynchronize();
@@ -176,9 +177,12 @@ void bn254_plonk_vk_free(bn254_plonk_pvk* pvk) {
 }
 size_t bn254_plonk_vk_num_public(const bn254_plonk_pvk* pvk) { return pvk ? (size_t)pvk->key.nb_public : 0; }
 
+}  // extern "C"
+
 // One MSM launch of a sub-batch: plan the rows for this batch size (bn254_msm.h: a pure function of the launch's term kinds, the item count and the lane
 // budget), check the plan against what the context holds -- the launch form follows the BATCH, the buffers the context's CAPACITY -- and enqueue rows + sums.
-static int plonk_msm(const PlonkDev* d, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows) {
+// keys != nullptr (a batch over many keys, bn254_capi_plonk_keys.hip): the items are slots and the window tables are those of every granule's key
+int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows) {
   MsmPlan plan;
   const size_t m_pad = (m + 63) & ~(size_t)63;
   // BN254_MSM_SPLIT_AT (experiments): the bit position at which the variable terms' low and high rows meet, instead of the planner's choice
@@ -186,7 +190,8 @@ static int plonk_msm(const PlonkDev* d, PlonkCtx& c, const MsmShape& shape, size
   if (!msm_plan_build(plan, shape, m_pad, msm_lane_budget(), force_a, plonk_joint_g(m_pad))) return set_err(BN254_E_BAD_ARG, "PlonK key shape needs more MSM rows than the launch supports");
   if (m > c.cap || bn254_g1_msm_scratch_lanes(plan, m) > c.glv_lanes || (size_t)plan.n_rows * m > c.part_points || (size_t)plan.n_rows > (size_t)MSM_MAX_ROWS)
     return set_err(BN254_E_HIP, "PlonK context smaller than the launch (internal sizing error)");
-  hipError_t e = bn254_launch_g1_msm_rows(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, d->fixed_tabs, c.stream);
+  hipError_t e = keys ? bn254_launch_g1_msm_rows_keys(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, keys->desc, keys->n_keys, keys->granule_key, c.stream)
+                      : bn254_launch_g1_msm_rows(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, fixed_tabs, c.stream);
   if (ev_rows) HIPCK(hipEventRecord(ev_rows, c.stream));
   if (e == hipSuccess)
     e = to_words ? bn254_launch_g1_sum_rows(plan, c.part, m, c.words, c.inf, nullptr, nullptr, 0, 0, 0, 0, c.stream)
@@ -195,6 +200,9 @@ static int plonk_msm(const PlonkDev* d, PlonkCtx& c, const MsmShape& shape, size
   if (lanes_out) *lanes_out = (size_t)plan.n_rows * m_pad;
   return BN254_OK;
 }
+
+extern "C" {
+
 // The same sub-batch with BOTH host stages on the device (bn254_k_plonk.hip): one H2D copy of the proofs and inputs, stage 1 -> digest MSM -> stage 2 ->
 // folding MSMs -> pairing check on the context's stream without a host wait in between, one D2H copy of the status bytes.
 // resident: proofs / public_inputs / status are DEVICE memory of `device` (bn254_plonk_verify_batch_device): no staging copy, the status bytes leave with a device-to-device copy.
@@ -232,7 +240,7 @@ static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, Plonk
   hipError_t e = bn254_launch_plonk_stage1(d->d_key, d_proofs, proof_stride, d_inputs, n_public, m, lam_key, c.d_work, c.terms, c.flags, T1, c.stream);
   if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("PlonK stage 1 launch: ") + hipGetErrorString(e));
   HIPCK(hipEventRecord(c.tk[1], c.stream));
-  int mrc = plonk_msm(d, c, pvk->shape1, m, T1, true, &c.last_lanes[0], c.tk[2]);
+  int mrc = plonk_msm(d->fixed_tabs, nullptr, c, pvk->shape1, m, T1, true, &c.last_lanes[0], c.tk[2]);
   if (mrc) return mrc;
   HIPCK(hipEventRecord(c.tk[3], c.stream));
   // BN254_FLAG_RLC: the pairing checks of the pass batched over groups of 64 proofs -- honoured from g_plonk_rlc_min proofs per pass (below, the one remaining
@@ -241,7 +249,7 @@ static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, Plonk
   e = bn254_launch_plonk_stage2(d->d_key, d_proofs, proof_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, rlc ? lam_key : nullptr, c.stream);
   HIPCK(hipEventRecord(c.tk[4], c.stream));
   if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("PlonK stage 2 launch: ") + hipGetErrorString(e));
-  mrc = plonk_msm(d, c, rlc ? pvk->shape2_rlc : pvk->shape2, m, TT, false, &c.last_lanes[1], c.tk[5]);
+  mrc = plonk_msm(d->fixed_tabs, nullptr, c, rlc ? pvk->shape2_rlc : pvk->shape2, m, TT, false, &c.last_lanes[1], c.tk[5]);
   if (mrc) return mrc;
   HIPCK(hipEventRecord(c.tk[6], c.stream));
   bool exact = !rlc;
@@ -296,13 +304,26 @@ int bn254_plonk_last_timing(const bn254_plonk_pvk* pvk, int device, float ms[BN2
 }  // extern "C"
 
 // the plan of a batch of n proofs under the current knobs: sub-batches side by side, proofs per sub-batch, proofs per pass
-static void plonk_plan_for(size_t n, int* workers, size_t* per, size_t* pass_cap) {
-  int max_workers = g_plonk_workers.load();
+// piece: the most proofs a pass of a batch of n may hold; *max_workers: the most sub-batches side by side
+size_t plonk_piece_for(size_t n, int* max_workers) {
+  *max_workers = g_plonk_workers.load();
   size_t piece;
   const long big_from = g_plonk_big_from.load();
-  if (big_from == 0) plonk_auto_plan(n, (size_t)g_plonk_piece.load(), (size_t)g_plonk_big_piece.load(), max_workers, &piece, &max_workers);
+  if (big_from == 0) plonk_auto_plan(n, (size_t)g_plonk_piece.load(), (size_t)g_plonk_big_piece.load(), *max_workers, &piece, max_workers);
   else piece = n >= (size_t)big_from ? (size_t)g_plonk_big_piece.load() : (size_t)g_plonk_piece.load();
+  return piece;
+}
+void plonk_plan_for(size_t n, int* workers, size_t* per, size_t* pass_cap) {
+  int max_workers;
+  const size_t piece = plonk_piece_for(n, &max_workers);
   plonk_plan(n, piece, max_workers, workers, per, pass_cap);
+}
+// the batch sizes that END a segment of the plan: within a segment the piece and the worker count do not fall as n grows (plonk_auto_plan, or big_from)
+int plonk_plan_breaks(size_t out[4]) {
+  const long big_from = g_plonk_big_from.load();
+  if (big_from == 0) { out[0] = 9000; out[1] = 20000; out[2] = 40000; out[3] = 65536; return 4; }
+  if (big_from > 1) { out[0] = (size_t)big_from - 1; return 1; }
+  return 0;
 }
 
 // One batch.  resident = false: proofs / public_inputs / status are the caller's host buffers (each pass stages its share through the context's pinned memory);

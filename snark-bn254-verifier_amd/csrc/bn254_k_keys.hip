@@ -250,9 +250,65 @@ k_f12_mul_verdict_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ stat
   if (i < n && st != 0) { const uint32_t pi = slot_to_proof[i]; if (pi < n_proofs) out_status[pi] = out; }
 }
 
+// ---- PlonK batches over many keys: the records and input rows of a pass into slot order, the slots' status bytes back ------------------------------------------
+// One wavefront per slot, the lanes on consecutive dwords (a byte path for unaligned sources, as k_gather_rows).  Of a proof's input row only the 32 n_public(key)
+// bytes of its key are read; the rest of the slot's row, and the whole record and row of a padding slot, are zero -- an all-zero record is malformed for every key
+// (its count of claimed values is not 6 + n_qcp), so stage 1 decides a padding slot and nothing later sees it as pending.
+__global__ void __launch_bounds__(256) k_plonk_keys_gather(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, size_t input_stride, uint32_t n_proofs,
+                                                           const uint32_t* __restrict__ slot_to_proof, const uint32_t* __restrict__ granule_key, const PlonkKeyDesc* __restrict__ desc,
+                                                           uint32_t n_keys, uint32_t m, uint8_t* __restrict__ recs, uint32_t rec_stride, uint32_t rec_bytes, uint8_t* __restrict__ rows,
+                                                           uint32_t row_stride) {
+  const uint32_t j = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+  if (j >= m) return;
+  const uint32_t pi = (uint32_t)__builtin_amdgcn_readfirstlane((int)slot_to_proof[j]);
+  const bool live = pi < n_proofs;
+  uint32_t* dr = (uint32_t*)(recs + (size_t)j * rec_stride);
+  const uint8_t* sr = proofs + (size_t)(live ? pi : 0) * stride;
+  const bool aligned = ((((uintptr_t)proofs) | stride) & 3) == 0;
+  for (uint32_t d = lane; d < rec_stride / 4; d += 64) {
+    uint32_t v = 0;
+    if (live && 4 * d < rec_bytes) {
+      if (aligned) v = *(const uint32_t*)(sr + 4 * (size_t)d);
+      else { const uint8_t* p = sr + 4 * (size_t)d; for (uint32_t b = 0; b < 4 && 4 * d + b < rec_bytes; b++) v |= (uint32_t)p[b] << (8 * b); }   // (never past the last record)
+    }
+    dr[d] = v;
+  }
+  if (row_stride == 0) return;
+  const uint32_t in_bytes = live ? 32u * plonk_keys_view(desc, granule_key, j & ~63u, n_keys).n_public : 0u;
+  uint32_t* di = (uint32_t*)(rows + (size_t)j * row_stride);
+  const uint8_t* si = inputs + (size_t)(live ? pi : 0) * input_stride;
+  const bool in_aligned = ((((uintptr_t)inputs) | input_stride) & 3) == 0;
+  for (uint32_t d = lane; d < row_stride / 4; d += 64) {
+    uint32_t v = 0;
+    if (4 * d < in_bytes) {
+      if (in_aligned) v = *(const uint32_t*)(si + 4 * (size_t)d);
+      else { const uint8_t* p = si + 4 * (size_t)d; v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+    }
+    di[d] = v;
+  }
+}
+__global__ void __launch_bounds__(256) k_plonk_keys_scatter(const uint8_t* __restrict__ slot_status, const uint32_t* __restrict__ slot_to_proof, uint32_t m, uint32_t n_proofs,
+                                                            uint8_t* __restrict__ status) {
+  const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+  if (j >= m) return;
+  const uint32_t pi = slot_to_proof[j];
+  if (pi < n_proofs) status[pi] = slot_status[j];
+}
+
 }  // namespace bn254
 
 using namespace bn254;
+hipError_t bn254_launch_plonk_keys_gather(const uint8_t* proofs, size_t stride, const uint8_t* inputs, size_t input_stride, uint32_t n_proofs, const uint32_t* slot_to_proof,
+                                          const uint32_t* granule_key, const PlonkKeyDesc* desc, uint32_t n_keys, uint32_t m, uint8_t* recs, uint32_t rec_stride, uint32_t rec_bytes,
+                                          uint8_t* rows, uint32_t row_stride, hipStream_t s) {
+  hipLaunchKernelGGL(k_plonk_keys_gather, dim3((m + 3) / 4), dim3(256), 0, s, proofs, stride, inputs, input_stride, n_proofs, slot_to_proof, granule_key, desc, n_keys, m, recs,
+                     rec_stride, rec_bytes, rows, row_stride);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_plonk_keys_scatter(const uint8_t* slot_status, const uint32_t* slot_to_proof, uint32_t m, uint32_t n_proofs, uint8_t* status, hipStream_t s) {
+  hipLaunchKernelGGL(k_plonk_keys_scatter, dim3((m + 255) / 256), dim3(256), 0, s, slot_status, slot_to_proof, m, n_proofs, status);
+  return hipGetLastError();
+}
 hipError_t bn254_launch_keys_group(const uint32_t* key_index, uint32_t n, uint32_t n_keys, uint32_t slot_cap, uint32_t* count, uint32_t* base, uint32_t* cursor,
                                    uint32_t* n_slots, uint32_t* slot_to_proof, uint32_t* granule_key, uint8_t* status, hipStream_t s) {
   hipError_t e;

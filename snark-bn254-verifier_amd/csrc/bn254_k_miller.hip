@@ -93,9 +93,27 @@ __global__ void __launch_bounds__(256, 2) k_miller_run_fixed2(int32_t* ws, uint3
   vm_miller_run_fixed2(w, lines, dk, __builtin_amdgcn_readfirstlane(s_begin), __builtin_amdgcn_readfirstlane(s_end), e, e_p0, (st & inf_mask0) != 0, e_p1, (st & inf_mask1) != 0);
 }
 
+// k_miller_run_fixed2 for a batch over many PlonK keys (bn254_keys.h): the same loop, the lines of the two KZG G2 points from the descriptor of the wavefront's key
+__global__ void __launch_bounds__(256, 2) k_miller_run_fixed2_keys(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, MillerKinds kinds, int s_begin, int s_end, int e,
+                                                                   const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, const uint32_t* __restrict__ granule_key,
+                                                                   int e_p0, int inf_mask0, int e_p1, int inf_mask1) {
+  __shared__ int32_t park_lds[72 * 256];
+  if (((blockIdx.x * 256u + threadIdx.x) & ~63u) >= n) return;      // a wavefront past the launch's slots has no granule word
+  VM_KERNEL_PROLOGUE();
+  w.lds = park_lds;
+  const PlonkKeyView kv = plonk_keys_view(desc, granule_key, i & ~63u, n_keys);
+  DevLines lines{kv.tab0, kv.tab1};
+  DevKinds dk{kinds};
+  vm_miller_run_fixed2(w, lines, dk, __builtin_amdgcn_readfirstlane(s_begin), __builtin_amdgcn_readfirstlane(s_end), e, e_p0, (st & inf_mask0) != 0, e_p1, (st & inf_mask1) != 0);
+}
+
 }  // namespace bn254
 
 using namespace bn254;
+void bn254_launch_miller_run_fixed2_keys(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int e,
+                                         const PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1) {
+  hipLaunchKernelGGL(k_miller_run_fixed2_keys, dim3(grid), dim3(256), 0, s, ws, n, status, kinds, s_begin, s_end, e, desc, n_keys, granule_key, ep0, inf0, ep1, inf1);
+}
 void bn254_launch_miller_run_fixed2(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int e,
                                     const int32_t* tab0, int ep0, int inf0, const int32_t* tab1, int ep1, int inf1) {
   hipLaunchKernelGGL(k_miller_run_fixed2, dim3(grid), dim3(256), 0, s, ws, n, status, kinds, s_begin, s_end, e, tab0, ep0, inf0, tab1, ep1, inf1);

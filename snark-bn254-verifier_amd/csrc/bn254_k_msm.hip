@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include "bn254_devws.h"
 #include "bn254_msm.h"
+#include "bn254_keys.h"
 
 namespace bn254 {
 
@@ -64,25 +65,39 @@ struct DevMsmIO {
 
 // The plan travels by value in the kernel arguments and is read THERE (scalar loads from the kernarg segment, indexed by the wave-uniform row): indexing
 // the by-value copy would make the compiler spill the whole struct to scratch memory first.
-__global__ void __launch_bounds__(256, 2)
-k_g1_msm_rows(MsmPlan plan_arg, const int32_t* __restrict__ terms, const uint8_t* __restrict__ flags, uint32_t n, uint32_t n_pad, int n_terms,
-              int32_t* __restrict__ part, int32_t* __restrict__ glv_tab, const int32_t* __restrict__ tabs) {
+// (tabs_of(i): the window tables the lane's item multiplies with -- the launch's, or those of the key of the item's granule)
+template <class TABS>
+__device__ __forceinline__ void msm_rows_body(const int32_t* __restrict__ terms, const uint8_t* __restrict__ flags, uint32_t n, uint32_t n_pad, int n_terms,
+                                              int32_t* __restrict__ part, int32_t* __restrict__ glv_tab, const TABS& tabs_of) {
   typedef __attribute__((address_space(4))) const MsmPlan KernargPlan;
   const MsmPlan& plan = *(const MsmPlan*)(KernargPlan*)__builtin_amdgcn_kernarg_segment_ptr();     // plan_arg is the first argument: offset 0
-  (void)plan_arg;
   const uint32_t g = blockIdx.x * 256u + threadIdx.x;
   const int r = __builtin_amdgcn_readfirstlane((int)(g / n_pad));        // n_pad is a multiple of 64: uniform over the wavefront
   if (r >= plan.n_rows) return;
   const uint32_t i = g - (uint32_t)r * n_pad;
   const bool live = i < n;
   const uint32_t ii = live ? i : n - 1;
-  DevMsmIO io{terms + (size_t)ii * (size_t)n_terms * MSM_TERM_DWORDS, flags + (size_t)ii * (size_t)n_terms, tabs};
+  DevMsmIO io{terms + (size_t)ii * (size_t)n_terms * MSM_TERM_DWORDS, flags + (size_t)ii * (size_t)n_terms, tabs_of(i)};
   DevGlvTab tab{glv_tab + ((size_t)plan.row[r].glv_slot * n_pad + i) * (size_t)(G1_GLV_TAB_BYTES_PER_LANE / 4), (size_t)n_pad * (size_t)(G1_GLV_TAB_BYTES_PER_LANE / 4)};
   const G1Proj acc = msm_row_eval(plan, r, io, tab);
   if (!live) return;
   int32_t* o = part + (size_t)r * 27 * n + i;
 #pragma unroll
   for (int l = 0; l < BN_NL; l++) { o[(size_t)l * n] = acc.x.v[l]; o[(size_t)(9 + l) * n] = acc.y.v[l]; o[(size_t)(18 + l) * n] = acc.z.v[l]; }
+}
+__global__ void __launch_bounds__(256, 2)
+k_g1_msm_rows(MsmPlan plan_arg, const int32_t* __restrict__ terms, const uint8_t* __restrict__ flags, uint32_t n, uint32_t n_pad, int n_terms,
+              int32_t* __restrict__ part, int32_t* __restrict__ glv_tab, const int32_t* __restrict__ tabs) {
+  (void)plan_arg;
+  msm_rows_body(terms, flags, n, n_pad, n_terms, part, glv_tab, [tabs](uint32_t) { return tabs; });
+}
+// k_g1_msm_rows for a batch over many keys (bn254_keys.h): the items are slots, and the 64 items of a wavefront are one granule (n_pad is a multiple of 64, so
+// i / 64 is uniform): the window tables are those of that granule's key
+__global__ void __launch_bounds__(256, 2)
+k_g1_msm_rows_keys(MsmPlan plan_arg, const int32_t* __restrict__ terms, const uint8_t* __restrict__ flags, uint32_t n, uint32_t n_pad, int n_terms,
+                   int32_t* __restrict__ part, int32_t* __restrict__ glv_tab, const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, const uint32_t* __restrict__ granule_key) {
+  (void)plan_arg;
+  msm_rows_body(terms, flags, n, n_pad, n_terms, part, glv_tab, [=](uint32_t i) { return plonk_keys_view(desc, granule_key, (i < n ? i : n - 1) & ~63u, n_keys).fixed_tabs; });
 }
 
 // per item: the sum of rows [first, first + count) of `part`, to affine.  out_words != nullptr: 16 little-endian words (x | y, canonical) and a flag byte
@@ -205,6 +220,14 @@ hipError_t bn254_launch_g1_msm_rows(const MsmPlan& plan, const int32_t* terms, c
   const size_t n_pad = (n + 63) & ~(size_t)63;
   const size_t lanes = (size_t)plan.n_rows * n_pad;
   hipLaunchKernelGGL(k_g1_msm_rows, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, plan, terms, flags, (uint32_t)n, (uint32_t)n_pad, n_terms, part, glv_tab, tabs);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_g1_msm_rows_keys(const MsmPlan& plan, const int32_t* terms, const uint8_t* flags, size_t n, int n_terms, int32_t* part, int32_t* glv_tab,
+                                         const PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, hipStream_t s) {
+  const size_t n_pad = (n + 63) & ~(size_t)63;
+  const size_t lanes = (size_t)plan.n_rows * n_pad;
+  hipLaunchKernelGGL(k_g1_msm_rows_keys, dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, s, plan, terms, flags, (uint32_t)n, (uint32_t)n_pad, n_terms, part, glv_tab, desc, n_keys,
+                     granule_key);
   return hipGetLastError();
 }
 // the rows of sum 0 (and of sum 1 when the plan has two) added up: out_words / out_inf (canonical words for the host or the next stage) or the workspace

@@ -17,6 +17,7 @@
 #include <vector>
 #include "bn254_plonk.hpp"
 #include "bn254_rlc.h"
+#include "bn254_keys.h"
 
 using namespace bn254host;
 
@@ -40,8 +41,9 @@ __device__ __forceinline__ void pl_stage_rows(uint8_t* dst0, uint32_t lane_strid
     }
   }
 }
-__device__ __forceinline__ const uint8_t* pl_stage_lds(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, size_t n_public, uint32_t n,
-                                                     uint32_t lane_stride, const uint8_t** lane_inputs) {
+// in_stride: bytes between the input rows of consecutive records (32 n_public in a single-key batch; the row width of the widest key in a batch over many keys)
+__device__ __forceinline__ const uint8_t* pl_stage_lds_rows(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, size_t in_stride, size_t n_public,
+                                                          uint32_t n, uint32_t lane_stride, const uint8_t** lane_inputs) {
   extern __shared__ uint8_t pl_dyn_lds[];
   // bn254_plonk.hpp::pl_lane_lds addresses the lanes' slots by LDS OFFSET (it may be compiled out of line, where the array has no name): that is only right while
   // this array starts at offset 0, i.e. while neither the kernels nor anything the compiler places (a promoted alloca, a static __shared__ of an inlined callee)
@@ -51,19 +53,19 @@ __device__ __forceinline__ const uint8_t* pl_stage_lds(const uint8_t* __restrict
   const size_t pbytes = stride < PL_STAGE_MAX_PROOF ? stride : PL_STAGE_MAX_PROOF;
   const size_t ibytes = n_public * 32 <= PL_STAGE_MAX_INPUT ? n_public * 32 : 0;
   const uint32_t first = blockIdx.x * 64u;
-  const bool aligned = (((uintptr_t)proofs | stride | (uintptr_t)inputs) & 3) == 0;
+  const bool aligned = (((uintptr_t)proofs | stride | (uintptr_t)inputs | in_stride) & 3) == 0;
   const size_t nt = blockDim.x;             // 64 (k_plonk_stage2) or 128 (k_plonk_stage1: chain + helper wavefront, the same 64 proofs)
   if (aligned) {
     // SIXTEEN records per step: a thread's sixteen loads are in flight together (one record at a time was 64 dependent round trips to HBM: 85 us of a 390 us launch)
     pl_stage_rows(pl_dyn_lds + 16 + 64, lane_stride, proofs, stride, pbytes, first, n, nt);
-    if (ibytes) pl_stage_rows(pl_dyn_lds + 16 + 64 + ((pbytes + 3) & ~(size_t)3), lane_stride, inputs, n_public * 32, ibytes, first, n, nt);
+    if (ibytes) pl_stage_rows(pl_dyn_lds + 16 + 64 + ((pbytes + 3) & ~(size_t)3), lane_stride, inputs, in_stride, ibytes, first, n, nt);
   } else {
     for (uint32_t j = 0; j < 64; j++) {
       const uint32_t rec = first + j;
       if (rec >= n) break;
       uint8_t* dst = pl_dyn_lds + 16 + (size_t)j * lane_stride + 64;
       const uint8_t* src = proofs + (size_t)rec * stride;
-      const uint8_t* isrc = inputs + (size_t)rec * n_public * 32;
+      const uint8_t* isrc = inputs + (size_t)rec * in_stride;
       for (size_t off = threadIdx.x; off < pbytes; off += nt) dst[off] = src[off];
       for (size_t off = threadIdx.x; off < ibytes; off += nt) dst[((pbytes + 3) & ~(size_t)3) + off] = isrc[off];
     }
@@ -72,8 +74,12 @@ __device__ __forceinline__ const uint8_t* pl_stage_lds(const uint8_t* __restrict
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t i = first + lane;
   const uint8_t* mine = pl_dyn_lds + 16 + (size_t)lane * lane_stride + 64;
-  *lane_inputs = ibytes ? mine + ((pbytes + 3) & ~(size_t)3) : inputs + (size_t)(i < n ? i : 0) * n_public * 32;
+  *lane_inputs = ibytes ? mine + ((pbytes + 3) & ~(size_t)3) : inputs + (size_t)(i < n ? i : 0) * in_stride;
   return mine;
+}
+__device__ __forceinline__ const uint8_t* pl_stage_lds(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, size_t n_public, uint32_t n,
+                                                     uint32_t lane_stride, const uint8_t** lane_inputs) {
+  return pl_stage_lds_rows(proofs, stride, inputs, n_public * 32, n_public, n, lane_stride, lane_inputs);
 }
 static uint32_t pl_lane_stride(size_t stride, size_t n_public) {
   const size_t pbytes = stride < PL_STAGE_MAX_PROOF ? stride : PL_STAGE_MAX_PROOF;
@@ -88,11 +94,19 @@ static uint32_t pl_lane_stride(size_t stride, size_t n_public) {
 // hash_to_field, lambda.  Wavefront 1 (lanes 64..127) does those for the same 64 proofs while wavefront 0 runs transcripts -> zeta^n -> denominators -> inversion
 // from the proof's bytes and its layout alone; they meet at ONE barrier (the parsed proof and the hashes travel through work[i], the status precedence is the
 // reference's: a loader error of any point beats everything the chain lane found), then wavefront 0 finishes (public-input sum, opening check, terms).
+// The stage behind the staging is pl_stage1_body, below the kernel: my_proof / my_inputs are the lane's record (stride: the length the parser is told) and input
+// row.  One body for k_plonk_stage1 and k_plonk_stage1_keys, which differ in where the key and the input width come from
+__device__ __forceinline__ void pl_stage1_body(const PlonkKey* __restrict__ key, const uint8_t* my_proof, const uint8_t* my_inputs, size_t stride, size_t n_public, uint32_t n,
+                                               const ChaChaKey& lam_key, PlonkWork* work, MsmTerm* terms, uint8_t* flags, int T1);
 __global__ void __launch_bounds__(128) k_plonk_stage1(const PlonkKey* __restrict__ key, const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs,
                                                       size_t n_public, uint32_t n, ChaChaKey lam_key, PlonkWork* work, MsmTerm* terms,
                                                       uint8_t* flags, int T1, uint32_t lane_stride) {
   const uint8_t* my_inputs;
   const uint8_t* my_proof = pl_stage_lds(proofs, stride, inputs, n_public, n, lane_stride, &my_inputs);
+  pl_stage1_body(key, my_proof, my_inputs, stride, n_public, n, lam_key, work, terms, flags, T1);
+}
+__device__ __forceinline__ void pl_stage1_body(const PlonkKey* __restrict__ key, const uint8_t* my_proof, const uint8_t* my_inputs, size_t stride, size_t n_public, uint32_t n,
+                                               const ChaChaKey& lam_key, PlonkWork* work, MsmTerm* terms, uint8_t* flags, int T1) {
   const bool helper = threadIdx.x >= 64u;
   const uint32_t i = blockIdx.x * 64u + (threadIdx.x & 63u);
   const bool live = i < n;                      // no early return: every lane reaches the barrier
@@ -145,13 +159,22 @@ __global__ void __launch_bounds__(128) k_plonk_stage1(const PlonkKey* __restrict
   if (st != PL_OK) for (int k = 0; k < T1; k++) { for (int q = 0; q < 18; q++) t[k].pt[q] = 0; for (int q = 0; q < 8; q++) t[k].k[q] = 0; fl[k] = 0; }
   wk.status = st;
 }
+// k_plonk_stage1 for a batch over many keys (bn254_keys.h): the 64 slots of the workgroup are one granule, so the key and the width of the input rows come from that
+// granule's descriptor.  recs / inputs: the pass's records and rows in SLOT order (k_plonk_keys_gather), rec_stride / in_stride bytes apart; proof_len: the caller's
+// proof_stride, the length the parser is told; lane_stride: one launch-wide value, from the widest staged key
+__global__ void __launch_bounds__(128) k_plonk_stage1_keys(const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, const uint32_t* __restrict__ granule_key,
+                                                           const uint8_t* __restrict__ recs, size_t rec_stride, size_t proof_len, const uint8_t* __restrict__ inputs, size_t in_stride,
+                                                           uint32_t n, ChaChaKey lam_key, PlonkWork* work, MsmTerm* terms, uint8_t* flags, int T1, uint32_t lane_stride) {
+  const PlonkKeyView kv = plonk_keys_view(desc, granule_key, blockIdx.x * 64u, n_keys);
+  const uint8_t* my_inputs;
+  const uint8_t* my_proof = pl_stage_lds_rows(recs, rec_stride, inputs, in_stride, (size_t)kv.n_public, n, lane_stride, &my_inputs);
+  pl_stage1_body((const PlonkKey*)kv.key, my_proof, my_inputs, proof_len, (size_t)kv.n_public, n, lam_key, work, terms, flags, T1);
+}
 
-__global__ void __launch_bounds__(64) k_plonk_stage2(const PlonkKey* __restrict__ key, const uint8_t* __restrict__ proofs, size_t stride, uint32_t n,
-                                                     PlonkWork* __restrict__ work, const uint32_t* __restrict__ lin_words, const uint8_t* __restrict__ lin_inf,
-                                                     MsmTerm* __restrict__ terms, uint8_t* __restrict__ flags, uint8_t* __restrict__ status, int TT, int T2, uint32_t lane_stride,
-                                                     ChaChaKey w_key, int weighted) {
-  const uint8_t* unused_inputs;
-  const uint8_t* my_proof = pl_stage_lds(proofs, stride, proofs, 0, n, lane_stride, &unused_inputs);
+// one body for k_plonk_stage2 and k_plonk_stage2_keys
+__device__ __forceinline__ void pl_stage2_body(const PlonkKey* __restrict__ key, const uint8_t* my_proof, uint32_t n, PlonkWork* __restrict__ work, const uint32_t* __restrict__ lin_words,
+                                               const uint8_t* __restrict__ lin_inf, MsmTerm* __restrict__ terms, uint8_t* __restrict__ flags, uint8_t* __restrict__ status, int TT, int T2,
+                                               const ChaChaKey& w_key, int weighted) {
   const uint32_t i = blockIdx.x * 64u + threadIdx.x;
   if (i >= n) return;
   MsmTerm* t = terms + (size_t)i * TT;
@@ -178,6 +201,23 @@ __global__ void __launch_bounds__(64) k_plonk_stage2(const PlonkKey* __restrict_
   } else {
     status[i] = (uint8_t)wk.status;
   }
+}
+__global__ void __launch_bounds__(64) k_plonk_stage2(const PlonkKey* __restrict__ key, const uint8_t* __restrict__ proofs, size_t stride, uint32_t n,
+                                                     PlonkWork* __restrict__ work, const uint32_t* __restrict__ lin_words, const uint8_t* __restrict__ lin_inf,
+                                                     MsmTerm* __restrict__ terms, uint8_t* __restrict__ flags, uint8_t* __restrict__ status, int TT, int T2, uint32_t lane_stride,
+                                                     ChaChaKey w_key, int weighted) {
+  const uint8_t* unused_inputs;
+  const uint8_t* my_proof = pl_stage_lds(proofs, stride, proofs, 0, n, lane_stride, &unused_inputs);
+  pl_stage2_body(key, my_proof, n, work, lin_words, lin_inf, terms, flags, status, TT, T2, w_key, weighted);
+}
+__global__ void __launch_bounds__(64) k_plonk_stage2_keys(const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, const uint32_t* __restrict__ granule_key,
+                                                          const uint8_t* __restrict__ recs, size_t rec_stride, uint32_t n, PlonkWork* __restrict__ work,
+                                                          const uint32_t* __restrict__ lin_words, const uint8_t* __restrict__ lin_inf, MsmTerm* __restrict__ terms, uint8_t* __restrict__ flags,
+                                                          uint8_t* __restrict__ status, int TT, int T2, uint32_t lane_stride, ChaChaKey w_key, int weighted) {
+  const PlonkKeyView kv = plonk_keys_view(desc, granule_key, blockIdx.x * 64u, n_keys);
+  const uint8_t* unused_inputs;
+  const uint8_t* my_proof = pl_stage_lds_rows(recs, rec_stride, recs, 0, 0, n, lane_stride, &unused_inputs);
+  pl_stage2_body((const PlonkKey*)kv.key, my_proof, n, work, lin_words, lin_inf, terms, flags, status, TT, T2, w_key, weighted);
 }
 
 }  // namespace bn254
@@ -210,6 +250,33 @@ hipError_t bn254_launch_plonk_stage1(const void* d_key, const uint8_t* d_proofs,
   if (lds > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ae != hipSuccess) return ae; }
   hipLaunchKernelGGL(k_plonk_stage1, dim3((unsigned)((n + 63) / 64)), dim3(128), lds, s, (const PlonkKey*)d_key, d_proofs, stride, d_inputs, n_public, (uint32_t)n, key,
                      (PlonkWork*)d_work, (MsmTerm*)d_terms, d_flags, T1, ls);
+  return hipGetLastError();
+}
+// the same over the slots of a batch over many keys: recs / inputs in slot order (rec_stride / in_stride apart), the key per granule.  staged_public: the most inputs
+// any key of the list stages in LDS (keys above PL_STAGE_MAX_INPUT / 32 read theirs from the rows): it sizes the one lane stride of the launch
+hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t proof_len,
+                                          const uint8_t* d_inputs, size_t in_stride, size_t staged_public, size_t n, const uint32_t lam_key[11], void* d_work, void* d_terms,
+                                          uint8_t* d_flags, int T1, hipStream_t s) {
+  ChaChaKey key;
+  for (int i = 0; i < 8; i++) key.k[i] = lam_key[i];
+  for (int i = 0; i < 3; i++) key.nonce[i] = lam_key[8 + i];
+  const uint32_t ls = pl_lane_stride(rec_stride, staged_public);
+  const size_t lds = 16 + 64 * (size_t)ls + 64 * (size_t)PL_HELPER_SHA_STRIDE;
+  if (lds > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage1_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ae != hipSuccess) return ae; }
+  hipLaunchKernelGGL(k_plonk_stage1_keys, dim3((unsigned)((n + 63) / 64)), dim3(128), lds, s, desc, n_keys, granule_key, d_recs, rec_stride, proof_len, d_inputs, in_stride, (uint32_t)n,
+                     key, (PlonkWork*)d_work, (MsmTerm*)d_terms, d_flags, T1, ls);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                          void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
+                                          hipStream_t s) {
+  ChaChaKey wkey;
+  for (int i = 0; i < 8; i++) wkey.k[i] = 0u;
+  for (int i = 0; i < 3; i++) wkey.nonce[i] = 0u;
+  const uint32_t ls = pl_lane_stride(rec_stride, 0);
+  if (16 + 64 * (size_t)ls > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage2_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 + 64 * (size_t)ls)); if (ae != hipSuccess) return ae; }
+  hipLaunchKernelGGL(k_plonk_stage2_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 16 + 64 * (size_t)ls, s, desc, n_keys, granule_key, d_recs, rec_stride, (uint32_t)n, (PlonkWork*)d_work,
+                     d_lin_words, d_lin_inf, (MsmTerm*)d_terms, d_flags, d_status, TT, T2, ls, wkey, 0);
   return hipGetLastError();
 }
 // weight_key != nullptr: BN254_FLAG_RLC -- every scalar of the proof's two sums carries the proof's weight (the call's key with another nonce word: a stream of its own)

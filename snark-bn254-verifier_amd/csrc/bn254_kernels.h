@@ -189,8 +189,22 @@ namespace bn254 { struct MsmPlan; }
 size_t bn254_g1_msm_scratch_lanes(const bn254::MsmPlan& plan, size_t n);   // lanes of window-table scratch (G1_GLV_TAB_BYTES_PER_LANE each) a launch over n items needs
 hipError_t bn254_launch_g1_msm_rows(const bn254::MsmPlan& plan, const int32_t* terms, const uint8_t* flags, size_t n, int n_terms, int32_t* part, int32_t* glv_tab,
                                     const int32_t* tabs, hipStream_t s);
+hipError_t bn254_launch_g1_msm_rows_keys(const bn254::MsmPlan& plan, const int32_t* terms, const uint8_t* flags, size_t n, int n_terms, int32_t* part, int32_t* glv_tab,
+                                         const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, hipStream_t s);   // tabs per granule of 64 items
 hipError_t bn254_launch_g1_sum_rows(const bn254::MsmPlan& plan, const int32_t* part, size_t n, uint32_t* out_words, uint8_t* out_inf, int32_t* ws, uint8_t* status, int e_x, int inf_bit,
                                     int e_x_b, int inf_bit_b, hipStream_t s);
+// the same for a batch over many PlonK keys (bn254_keys.h): n slots, the two line tables from the descriptor of every wavefront's granule.  Always the throughput
+// form (k_vm_init, k_miller_run_fixed2_keys, the final exponentiation, k_g16_compare): the cooperative and the two-chain forms read one key per launch
+void bn254_launch_miller_run_fixed2_keys(const MillerKinds& kinds, int s_begin, int s_end, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int e,
+                                         const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1);
+hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key,
+                                            const int32_t* target_one, int reject_code, hipStream_t s);
+// records and input rows of a pass in slot order / the slots' status bytes back to proof order (bn254_k_keys.hip).  slot_to_proof / granule_key: at the pass's first
+// slot; rec_bytes <= rec_stride, both multiples of 4; a padding slot gets an all-zero record (malformed: decided in stage 1) and is skipped on the way back
+hipError_t bn254_launch_plonk_keys_gather(const uint8_t* proofs, size_t stride, const uint8_t* inputs, size_t input_stride, uint32_t n_proofs, const uint32_t* slot_to_proof,
+                                          const uint32_t* granule_key, const bn254::PlonkKeyDesc* desc, uint32_t n_keys, uint32_t m, uint8_t* recs, uint32_t rec_stride,
+                                          uint32_t rec_bytes, uint8_t* rows, uint32_t row_stride, hipStream_t s);
+hipError_t bn254_launch_plonk_keys_scatter(const uint8_t* slot_status, const uint32_t* slot_to_proof, uint32_t m, uint32_t n_proofs, uint8_t* status, hipStream_t s);
 hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const int32_t* target_one,
                                        int reject_code, hipStream_t s, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);
 // cooperative layout for small batches (bn254_coop12.hip): twelve lanes per proof (one Fp number of every Fp12 value per lane), 39 KB of LDS per

@@ -945,6 +945,7 @@ struct LaunchOps {
   G16Prof* prof;
   int inf_mask[3] = {BN254_ST_LINF, 0, 0};   // status bits marking the G1 point of fixed pair 0 / 1 / 2 as the identity
   const G16KeyDesc* key_desc = nullptr; uint32_t n_keys = 0; const uint32_t* granule_key = nullptr;   // a batch over many keys: miller_run reads the tables per wavefront
+  const PlonkKeyDesc* plonk_desc = nullptr;  // a PlonK batch over many keys: miller_run_fixed2 reads the tables per wavefront (n_keys, granule_key as above)
   int run_fold = 0, inputs_match_key = 0;    // miller_run: MR_FOLD_INIT | MR_FOLD_ATE (the first run sets f and T, the last one tests B's subgroup and writes status)
   int uni(int x) { return x; }
   void f12_sqr(int e) { BN_LAUNCH(KID_F12_SQR, k_f12_sqr, ws, n, status, e); }
@@ -963,6 +964,7 @@ struct LaunchOps {
   void miller_run_fixed2(int s_begin, int s_end, int e, int ep0, int ep1) {
     static const MillerKinds kinds = [] { MillerKinds k; memset(&k, 0, sizeof k); for (int st_ = 0; st_ < BN_ATE_STEPS; st_++) k.nib[st_ >> 1] |= (uint8_t)(miller_step_kind(st_) << ((st_ & 1) * 4)); return k; }();
     ProfScope ps_(prof, KID_MILLER_RUN, s);
+    if (plonk_desc) { bn254_launch_miller_run_fixed2_keys(kinds, s_begin, s_end, ws, n, status, grid, s, e, plonk_desc, n_keys, granule_key, ep0, inf_mask[0], ep1, inf_mask[1]); return; }
     bn254_launch_miller_run_fixed2(kinds, s_begin, s_end, ws, n, status, grid, s, e, tab[0], ep0, inf_mask[0], tab[1], ep1, inf_mask[1]);
   }
   void miller_sqr_dbl_var(int et, int e, int ep) { BN_LAUNCH(KID_MILLER_SQR_DBL_VAR, k_miller_sqr_dbl_var, ws, n, status, et, e, ep); }
@@ -1407,6 +1409,22 @@ hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, c
       }
     }
   }
+  vm_final_exp_program(ops);
+  BN_LAUNCH(KID_COMPARE, k_g16_compare, ws, nn, status, target_one, reject_code);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const int32_t* target_one,
+                                            int reject_code, hipStream_t s) {
+  unsigned grid = grid_for(n);
+  uint32_t nn = (uint32_t)n;
+  G16Prof* prof = nullptr;
+  LaunchOps ops{ws, nn, status, grid, s, {nullptr, nullptr, nullptr}, nullptr};
+  ops.inf_mask[0] = BN254_ST_LINF; ops.inf_mask[1] = BN254_ST_LINF2;
+  ops.plonk_desc = desc; ops.n_keys = n_keys; ops.granule_key = granule_key;
+  BN_LAUNCH(KID_VM_INIT, k_vm_init, ws, nn, (const uint8_t*)status);
+  // steps per launch as in the single-key form (BN254_MILLER_RUN_STEPS; 0 there selects the one-launch-per-operation kernels, which read one key per launch: the whole loop here)
+  static const int run_steps = [] { const char* e = getenv("BN254_MILLER_RUN_STEPS"); int v = e ? atoi(e) : BN_ATE_STEPS; return v <= 0 ? BN_ATE_STEPS : v; }();
+  for (int s0 = 0; s0 < BN_ATE_STEPS; s0 += run_steps) ops.miller_run_fixed2(s0, s0 + run_steps < BN_ATE_STEPS ? s0 + run_steps : BN_ATE_STEPS, VE_F, VE_LX, VE_CX);
   vm_final_exp_program(ops);
   BN_LAUNCH(KID_COMPARE, k_g16_compare, ws, nn, status, target_one, reject_code);
   return hipGetLastError();

@@ -62,4 +62,41 @@ inline uint32_t keys_group_host(const uint32_t* key_index, uint32_t n, uint32_t 
   return n_slots;
 }
 
+// ---- PlonK batches over many keys (bn254_plonk_verify_batch_keys, bn254_capi_plonk_keys.hip) ------------------------------------------------------------------------
+// The same slots and granules.  What a kernel of a PlonK pass reads about entry k of the list: the parsed key of the stage kernels, the window tables of its points
+// (k_g1_msm_rows_keys), the line tables of its two KZG G2 points (k_miller_run_fixed2_keys).  All four are the member's OWN per-device state (PlonkDev).
+#define PLONK_KEYS_MAX_KEYS 256u
+struct PlonkKeyDesc {
+  const void* key;             // PlonkKey (bn254_plonk.hpp)
+  const int32_t* fixed_tabs;   // plonk_num_tables x MSM_FW_WINDOWS x MSM_FW_ENTRIES entries
+  const int32_t* tab0;         // BN_ATE_STEPS * FIXED_LINE_DWORDS: lines of kzg_g2[0]
+  const int32_t* tab1;         // the same for kzg_g2[1]
+  uint32_t n_public;           // the key's nb_public: the width of its proofs' input rows
+  uint32_t pad_;
+};
+#if defined(__HIPCC__)
+// The descriptor of the granule that starts at slot wave_first of the launch, read through the constant address space with a readfirstlane'd index (scalar loads;
+// bn254_devws.h::keys_view has the measurement of what generic pointers cost).  fixed_tabs is read at per-lane addresses: global address space.
+struct PlonkKeyView { const void* key; const int32_t *fixed_tabs, *tab0, *tab1; uint32_t n_public; };
+__device__ __forceinline__ PlonkKeyView plonk_keys_view(const PlonkKeyDesc* __restrict__ desc, const uint32_t* __restrict__ granule_key, uint32_t wave_first, uint32_t n_keys) {
+  static_assert(sizeof(PlonkKeyDesc) == 40, "four pointers and two words");
+  typedef const __attribute__((address_space(4))) uint64_t* cptr64;
+  uint32_t k = (uint32_t)__builtin_amdgcn_readfirstlane((int)granule_key[wave_first / G16_KEYS_GRANULE]);
+  k = k < n_keys ? k : 0u;
+  const uint64_t b = (uint64_t)(desc + k);
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)b), hi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
+  cptr64 f = (cptr64)(((uint64_t)hi << 32) | lo);
+  auto cst = [](uint64_t bits) {
+    const uint32_t l = __builtin_amdgcn_readfirstlane((uint32_t)bits), h = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
+    return (const int32_t*)(const __attribute__((address_space(4))) int32_t*)(((uint64_t)h << 32) | l);
+  };
+  PlonkKeyView v;
+  v.key = (const void*)cst(f[0]);
+  v.fixed_tabs = (const int32_t*)(const __attribute__((address_space(1))) int32_t*)f[1];
+  v.tab0 = cst(f[2]); v.tab1 = cst(f[3]);
+  v.n_public = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)f[4]);
+  return v;
+}
+#endif
+
 }  // namespace bn254

@@ -137,6 +137,9 @@ def model_components(name, ins):
     groups = [(h, l, count_in(mads, h, l[-1])) for h, l in loop_groups(ins, mads)]
     groups = [g for g in groups if g[2] > 0]
     comp, in_loops = {}, 0
+    # the twins for batches over many PlonK keys (bn254_keys.h) share their bodies with these kernels: the same loops, the tables read from the descriptor of the
+    # wavefront's granule.  They are recognised by the same layouts; model_all asserts that their static counts are their twins'
+    name = {"k_g1_msm_rows_keys": "k_g1_msm_rows", "k_miller_run_fixed2_keys": "k_miller_run_fixed2"}.get(name, name)
     if name == "k_g1_msm_rows":
         # Two copies of the variable-term code, in address order: the JOINT rows (a loop over the row's terms that holds a table head + the 3 x 3 table loop, then
         # the step loop: a conditional pair of doublings + one addition per term and step) and the single-term rows (table, step loop, trailing doublings); then
@@ -508,7 +511,7 @@ def main():
             continue
         if name.startswith("k_coop"):
             continue                          # cooperative kernels: model_coop12 (call graph + step program)
-        if name in ("k_valu_peak", "k_plonk_stage1", "k_plonk_stage2", "k_plonk_dbg_zeta"):
+        if name in ("k_valu_peak", "k_plonk_stage1", "k_plonk_stage2", "k_plonk_stage1_keys", "k_plonk_stage2_keys", "k_plonk_dbg_zeta"):
             continue                          # the measurement kernel; the PlonK stages (transcripts + Fr arithmetic on 32-bit words: < 1 % of a proof's multiply-adds, counted by PMC only)
         e = model_components(name, ins) or model_kernel(name, ins)
         e.pop("weights", None)
@@ -571,6 +574,11 @@ def main():
             e[f] = run[f]
         e["unmodelled"] = []
         e["model"] = "k_miller_run with the line tables read from the descriptor of the wavefront's key: the same %d static multiply-adds, priced as k_miller_run" % e["static_mads"]
+    for twin, base in (("k_miller_run_fixed2_keys", "k_miller_run_fixed2"), ("k_g1_msm_rows_keys", "k_g1_msm_rows")):
+        if twin in kernels and base in kernels:
+            e, b = kernels[twin], kernels[base]
+            assert e["static_mads"] == b["static_mads"] and e["mads_per_proof_launch"] == b["mads_per_proof_launch"], (twin + " is no longer " + base + " with other tables", e["static_mads"], b["static_mads"])
+            e["model"] = base + " with the tables read from the descriptor of the wavefront's key (PlonK batches over many keys): " + e["model"]
     if "k_f12_cyclo_sqr_n" in kernels:
         e = kernels["k_f12_cyclo_sqr_n"]
         e["mads_per_proof_batch"] = e["mads_per_proof_launch"] * 39     # all 39 launches of a batch together (exact: 186 squarings)
