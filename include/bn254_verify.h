@@ -287,6 +287,10 @@ int bn254_plonk_verify(const uint8_t* proof, size_t proof_len, const uint8_t* vk
  * ~9000 proofs, one pass up to ~20 000, two passes side by side up to ~40 000, one pass up to 65 536, passes of big_piece (default 131 072) on up to eight contexts beyond.
  * Same status bytes whatever the plan. */
 void bn254_set_plonk_params(long piece, int workers, long big_from, long big_piece);
+/* The pass size from which BN254_FLAG_RLC is honoured by the PlonK entries, on one key and over a key list (initial value: BN254_PLONK_RLC_MIN, default 8192: below,
+ * the one remaining pairing is the same latency-bound launch as the per-proof checks).  Process-wide and atomic; never below 64 (a group is 64 proofs); a negative
+ * value leaves it alone.  It changes no status byte. */
+void bn254_set_plonk_rlc_params(long min_pass);
 /* Durations (ms) of the first sub-batch of the bn254_plonk_verify_batch that finished last on `device`, from HIP events on the sub-batch's stream:
  *   [0] host: staging copy into pinned memory                                                           [1] k_plonk_stage1
  *   [2] k_g1_msm_rows of the linearised-polynomial digest   [3] its k_g1_sum_affine                   [4] k_plonk_stage2
@@ -310,16 +314,22 @@ int bn254_plonk_last_timing(const bn254_plonk_pvk* pvk, int device, float ms[BN2
  * 808 + 96 * n_qcp, input_stride below the widest key's row, any flag other than BN254_FLAG_RLC.  n == 0 returns BN254_OK and touches nothing.
  *   key_index[i] >= n_keys: the host-buffer entry checks the whole vector first, returns BN254_E_BAD_ARG, names the position in bn254_last_error() and leaves status
  * untouched; the device entry cannot, writes BN254_ERR_MALFORMED for that proof and verifies the others.
- *   BN254_FLAG_RLC is accepted and IGNORED: by its contract the status bytes are those of the exact path (a group of 64 proofs would hold up to 64 keys).
+ *   BN254_FLAG_RLC is honoured from passes of bn254_set_plonk_rlc_params' min_pass slots on (default 8192, the single-key entry's threshold; smaller passes take
+ * the exact path): the pairing checks of a pass are batched over its granules -- a granule's 64 slots hold proofs of one key, so it is a group as the 64 proofs of
+ * a wavefront are on one key --, one cooperative check per group with the group's key, and only if a group fails the exact check runs, on the wavefronts of the
+ * failed groups.  The status bytes are, as the flag's contract says, those of the exact path; a forged proof is accepted with probability ~ 2^-127, as on one key.
  *   How it runs: the proofs are grouped on the device so that every granule of 64 slots holds proofs of one key (at most 63 idle slots per key that has proofs), the
  * plan of the single-key entry (bn254_set_plonk_params) is made over slots with every cut on a granule boundary, and each pass gathers its records and input rows
- * into slot order, runs the stage, multi-scalar-multiplication and pairing kernels with the key read per granule, and scatters the status bytes back.  A pass always
- * takes the one-proof-per-lane (throughput) form of the pairing check; the cooperative and two-chain forms of the single-key entry read one key per launch.  SMALL
- * BATCHES OF FEW KEYS ARE NOT THIS REVISION'S TARGET.  Measured on one MI355X (profiles/r13_plonk_keys.txt; device-resident proofs of the SP1
+ * into slot order, runs the stage, multi-scalar-multiplication and pairing kernels with the key read per granule, and scatters the status bytes back.  The per-proof
+ * pairing check of a pass of up to bn254_set_plonk_keys_params' coop_max slots (default 40 960, the range of the cooperative kernel) runs in the cooperative form --
+ * twelve lanes per slot, Miller loop, final exponentiation and verdict in one launch, the line tables of the slot's key fetched per lane --, larger passes in the
+ * one-proof-per-lane (throughput) form; BN254_COOP=0 switches the cooperative form off.  Measured on one MI355X with the lane form for every pass
+ * (profiles/r13_plonk_keys.txt; device-resident proofs of the SP1
  * key shape, n proofs spread evenly over K keys): one call beats one bn254_plonk_verify_batch_device call per key in every cell with K >= 4 -- n = 4096: 10.8 ms
  * against 13.3 ms (K = 4), 52.7 ms (16), 209 ms (64); n = 65 536: 20.5 / 20.9 / 21.2 ms against 41.2 / 55.5 / 213 ms; n = 262 144: 78.4 / 74.7 / 75.5 ms against
- * 82.8 / 166 / 222 ms -- and from 65 536 proofs on it takes 0.95 to 1.01 of the single-key entry's time on as many proofs of ONE key.  It loses where the list has
- * one key and the batch is small: 4096 proofs of one key take 10.8 ms through a list and 3.6 ms through the single-key entry, which runs the cooperative kernel.
+ * 82.8 / 166 / 222 ms -- and from 65 536 proofs on it takes 0.95 to 1.01 of the single-key entry's time on as many proofs of ONE key.  The cooperative form of a
+ * pass and the flag over a list have NOT been measured yet (tools/bench_plonk_keys.py --lane --rlc takes the table; DESIGN.md section 9g says what is open): the
+ * default of coop_max is the range of the cooperative kernel, as on one key, until that table says otherwise.
  *   Both entries are host-synchronous, like bn254_plonk_verify_batch_device; the _device entry first waits for hip_stream.  Calls on one list from several host threads
  * run side by side (the list owns eight pass contexts, leased as a key's are).
  *   Device state of a list: kept per (list of handles in order, device), the four most recently used lists; bn254_plonk_vk_free of a member drops every cached list
@@ -328,13 +338,20 @@ int bn254_plonk_last_timing(const bn254_plonk_pvk* pvk, int device, float ms[BN2
  *   bn254_plonk_reserve_keys: after it, a call with the same handles in the same order, records of the same proof_stride and up to n proofs allocates nothing
  * (contexts for keys_slot_bound = n + min(n_keys, n) * 63 slots, the grouping buffers and the staging of the host-buffer entry for rows of 32 * the widest key);
  * BN254_E_NOMEM when the tables or the contexts do not fit.
- *   Not in this revision: lists that mix commitment counts, RLC groups, the cooperative / latency pairing forms for small mixed batches, a _multi entry, SP1 proofs
- * from their public values over a list, more than 256 entries. */
+ *   bn254_set_plonk_keys_params(coop_max): process-wide and atomic; passes of up to coop_max slots take the cooperative pairing form, 0: always the lane form; clamped
+ * to 40 960; a negative value leaves the knob alone.  BN254_PLONK_KEYS_COOP_MAX, read when the library is loaded, gives the initial value.
+ *   bn254_plonk_keys_state: counters of the cached (list, device) state since it was created -- out[0] passes that ran the joint check of BN254_FLAG_RLC, out[1] the
+ * groups those passes checked (slots / 64 each), out[2] the groups that failed, out[3] passes whose per-proof pairing check ran in the cooperative form.
+ * BN254_E_BAD_ARG for a null pointer or a list that is not cached (no batch or reservation yet, or evicted).
+ *   Not in this revision: lists that mix commitment counts, the two-chain (latency) pairing form, a _multi entry, SP1 proofs from their public values over a list,
+ * more than 256 entries, an adaptive bypass of the flag. */
 int bn254_plonk_verify_batch_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride,
                                   const uint8_t* public_inputs, size_t input_stride, size_t n, uint8_t* status, int device, unsigned flags);
 int bn254_plonk_verify_batch_keys_device(const bn254_plonk_pvk* const* pvks, size_t n_keys, const void* d_key_index, const void* d_proofs, size_t proof_stride,
                                          const void* d_public_inputs, size_t input_stride, size_t n, void* d_status, int device, void* hip_stream, unsigned flags);
 int bn254_plonk_reserve_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, size_t n, size_t proof_stride, int device);
+void bn254_set_plonk_keys_params(long coop_max);
+int bn254_plonk_keys_state(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device, uint64_t out[4]);
 
 /* ---- gnark / SP1 formats, both directions (host only) ------------------------------------------------------------------
  * Point codecs of verifier/src/converter.rs:23-153.  compress: uncompressed big-endian coordinates (G1: x | y; G2: x.c1 | x.c0 |
@@ -606,6 +623,14 @@ int bn254_dbg_g16_keys_last_form(const bn254_g16_pvk* const* pvks, size_t n_keys
  * ctx_capacity: slots a context holds after bn254_plonk_reserve_keys for (n, n_keys); pass_first: the first slot of each pass (up to cap entries), n_passes: how many. */
 int bn254_dbg_plonk_keys_plan(size_t n, size_t n_keys, size_t slots, size_t* slot_bound, int* workers, size_t* per_worker, size_t* per_pass, size_t* ctx_capacity,
                               size_t* pass_first, size_t cap, size_t* n_passes);
+/* k_coop12_miller_fixed_keys, the cooperative two-pair check with the key per item, in store mode on the line tables of prepared PlonK keys (shaped as
+ * bn254_dbg_coop12_miller_fixed; the members are made ready on the device first): item i belongs to pvks[key_words[i >> key_shift]] (a word >= n_keys reads key 0),
+ * g1_0 / g1_1: n affine G1 points of 64 bytes each, identity: null or per item bit 0 / bit 1 = pair 0 / pair 1 is the identity, out_gt: 384 bytes per item, the
+ * final-exponentiated e(P0, Q0_k) e(P1, Q1_k) with the two KZG G2 points of the item's key.  n at most 40 960. */
+int bn254_dbg_coop12_miller_fixed_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_words, unsigned key_shift, const uint8_t* g1_0,
+                                       const uint8_t* g1_1, const uint8_t* identity, uint8_t* out_gt, size_t n, int device);
+/* the knobs of a PlonK batch over a key list as they are now: out[0] coop_max (bn254_set_plonk_keys_params), out[1] min_pass (bn254_set_plonk_rlc_params) */
+int bn254_dbg_plonk_keys_knobs(long out[2]);
 /* the host image of a prepared Groth16 key, serialised: dwords n_k (2) | msm_comb | k0, gtab, dtab, target, kpts, each as its length and its dwords | alpha (18),
  * k0_pt (18), b_arg (36) as canonical digits.  Two handles of one key are interchangeable iff their images are equal.  *len: bytes of the image (always written);
  * a null or too small out (cap bytes) is BN254_E_BAD_ARG */

@@ -349,6 +349,19 @@ struct PlonkVerifier {
     for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
     detail::check(bn254_plonk_reserve_keys(h.data(), h.size(), n, proof_stride, device));
   }
+  // counters of the list's cached state on `device` (bn254_plonk_keys_state): passes that ran the joint check of BN254_FLAG_RLC, the groups they checked, the groups
+  // that failed, passes whose per-proof pairing check ran in the cooperative form
+  static std::array<uint64_t, 4> keys_state(const std::vector<const PreparedPlonkVk*>& keys, int device = 0) {
+    std::vector<const bn254_plonk_pvk*> h(keys.size());
+    for (size_t k = 0; k < keys.size(); k++) h[k] = keys[k] ? keys[k]->handle() : nullptr;
+    std::array<uint64_t, 4> out{};
+    detail::check(bn254_plonk_keys_state(h.data(), h.size(), device, out.data()));
+    return out;
+  }
+  // passes of up to coop_max slots of a batch over a key list take the cooperative pairing form (0: always the lane form; negative: unchanged)
+  static void set_keys_params(long coop_max) { bn254_set_plonk_keys_params(coop_max); }
+  // the pass size from which BN254_FLAG_RLC is honoured, on one key and over a list (never below 64; negative: unchanged)
+  static void set_rlc_params(long min_pass) { bn254_set_plonk_rlc_params(min_pass); }
   static Result<bool, PlonkError> outcome(uint8_t status) { return detail::plonk_outcome(status); }
 };
 

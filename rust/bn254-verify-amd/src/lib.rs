@@ -295,6 +295,18 @@ impl PlonkVerifier {
         let h: Vec<*const sys::Bn254PlonkPvk> = keys.iter().map(|k| k.h as *const sys::Bn254PlonkPvk).collect();
         check(unsafe { sys::bn254_plonk_reserve_keys(h.as_ptr() as *mut *const sys::Bn254PlonkPvk, h.len(), n, proof_stride, device) })
     }
+    /// Counters of the list's cached state on `device` (`bn254_plonk_keys_state`): passes that ran the joint check of `BN254_FLAG_RLC`, the groups they checked,
+    /// the groups that failed, passes whose per-proof pairing check ran in the cooperative form.
+    pub fn keys_state(keys: &[&PreparedPlonkVk], device: i32) -> Result<[u64; 4], Error> {
+        let h: Vec<*const sys::Bn254PlonkPvk> = keys.iter().map(|k| k.h as *const sys::Bn254PlonkPvk).collect();
+        let mut out = [0u64; 4];
+        check(unsafe { sys::bn254_plonk_keys_state(h.as_ptr() as *mut *const sys::Bn254PlonkPvk, h.len(), device, out.as_mut_ptr()) })?;
+        Ok(out)
+    }
+    /// Passes of up to `coop_max` slots of a batch over a key list take the cooperative pairing form (`bn254_set_plonk_keys_params`; 0: always the lane form).
+    pub fn set_keys_params(coop_max: i64) { unsafe { sys::bn254_set_plonk_keys_params(coop_max as core::ffi::c_long) } }
+    /// The pass size from which `BN254_FLAG_RLC` is honoured, on one key and over a list (`bn254_set_plonk_rlc_params`; never below 64).
+    pub fn set_rlc_params(min_pass: i64) { unsafe { sys::bn254_set_plonk_rlc_params(min_pass as core::ffi::c_long) } }
     pub fn verify_batch(proofs: &[&[u8]], vk: &[u8], public_inputs: &[&[[u8; 32]]]) -> Result<Vec<Status>, Error> {
         assert_eq!(proofs.len(), public_inputs.len());
         let pvk = PreparedPlonkVk::new(vk)?;

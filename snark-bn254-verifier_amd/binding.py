@@ -624,6 +624,53 @@ class PlonkKeySet:
         _check(fn(self._arr, len(self.keys), n, proof_stride, device))
 
 
+    def state(self, device=0):
+        """Counters of this list's cached state on `device` since the state was created (bn254_plonk_keys_state): (passes that ran the joint check of FLAG_RLC, groups
+        they checked, groups that failed, passes whose per-proof pairing check ran in the cooperative form).  Raises if the list is not cached."""
+        fn = lib().bn254_plonk_keys_state
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_uint64)]
+        out = (C.c_uint64 * 4)()
+        _check(fn(self._arr, len(self.keys), device, out))
+        return tuple(int(v) for v in out)
+
+    def dbg_coop12_miller_fixed(self, key_words, key_shift, g1_0, g1_1, identity=None, n=None, device=0):
+        """The cooperative two-pair check with the key per item in store mode (bn254_dbg_coop12_miller_fixed_keys): item i belongs to keys[key_words[i >> key_shift]];
+        g1_0 / g1_1: n affine G1 points of 64 bytes; identity: None or n bytes (bit 0 / 1: pair 0 / 1 is the identity).  Returns n values of 384 bytes."""
+        import array
+        n = len(g1_0) // 64 if n is None else n
+        kw = array.array("I", key_words)
+        fn = lib().bn254_dbg_coop12_miller_fixed_keys
+        fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint, C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_int]
+        out = (C.c_uint8 * (384 * max(n, 1)))()
+        _check(fn(self._arr, len(self.keys), kw.buffer_info()[0] if len(kw) else None, key_shift, bytes(g1_0), bytes(g1_1), bytes(identity) if identity is not None else None, out, n, device))
+        raw = bytes(out)
+        return [raw[384 * i:384 * (i + 1)] for i in range(n)]
+
+
+def set_plonk_keys_params(coop_max=-1):
+    """bn254_set_plonk_keys_params: passes of up to coop_max slots of a PlonK batch over a key list take the cooperative pairing form (0: always the lane form; clamped
+    to the cooperative kernel's range; negative: unchanged)."""
+    fn = lib().bn254_set_plonk_keys_params
+    fn.argtypes = [C.c_long]; fn.restype = None
+    fn(coop_max)
+
+
+def set_plonk_rlc_params(min_pass=-1):
+    """bn254_set_plonk_rlc_params: the pass size from which the PlonK entries honour FLAG_RLC (one key and key lists; never below 64; negative: unchanged)."""
+    fn = lib().bn254_set_plonk_rlc_params
+    fn.argtypes = [C.c_long]; fn.restype = None
+    fn(min_pass)
+
+
+def dbg_plonk_keys_knobs():
+    """(coop_max, rlc_min_pass) as they are now (bn254_dbg_plonk_keys_knobs)."""
+    fn = lib().bn254_dbg_plonk_keys_knobs
+    fn.argtypes = [C.POINTER(C.c_long)]
+    out = (C.c_long * 2)()
+    _check(fn(out))
+    return int(out[0]), int(out[1])
+
+
 def dbg_plonk_keys_plan(n, n_keys, slots):
     """The plan of a PlonK batch over many keys (bn254_dbg_plonk_keys_plan): dict with slot_bound, workers, per_worker, per_pass, ctx_capacity and pass_first."""
     fn = lib().bn254_dbg_plonk_keys_plan

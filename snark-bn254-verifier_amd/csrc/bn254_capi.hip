@@ -348,6 +348,15 @@ hipError_t bn254_launch_g1_msm_rows_keys(const MsmPlan&, const int32_t*, const u
   return hipErrorInvalidDeviceFunction;      // plonk_msm (bn254_capi_plonk.hip) names it; without the key-set file nothing passes it a key list
 }
 #endif
+// BN254_FLAG_RLC over a PlonK key list is honoured only from the threshold on (bn254_set_plonk_rlc_params), which tests/hostsan/hostsan_plonk_keys.cpp stays below: its
+// launchers are never reached there, and the harness that reaches them brings its own stand-ins (tests/hostsan/hostsan_plonk_keys_rlc.cpp)
+#if defined(BN254_HOSTSAN_PLONK_KEYS) && !defined(BN254_HOSTSAN_PLONK_KEYS_RLC)
+hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const uint8_t*, size_t, size_t, void*, const uint32_t*, const uint8_t*, void*, uint8_t*,
+                                                   uint8_t*, int, int, const uint32_t*, hipStream_t) { return hipErrorInvalidDeviceFunction; }
+hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t*, uint8_t*, size_t, const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const int32_t*, int, hipStream_t) {
+  return hipErrorInvalidDeviceFunction;
+}
+#endif
 // the direct form of a batch over many keys: a host build starts with the knob at 0 (bn254_capi_keys.hip), so this is never reached unless a harness turns the knob --
 // and that harness brings its own stand-in (tests/hostsan/hostsan_keys_small.cpp)
 #if defined(BN254_HOSTSAN_KEYS) && !defined(BN254_HOSTSAN_KEYS_DIRECT)
@@ -364,6 +373,7 @@ hipError_t bn254_launch_dbg_store(int32_t*, size_t, int, void*, int, hipStream_t
 hipError_t bn254_launch_dbg_verdict(int, int32_t*, size_t, uint8_t*, const int32_t*, hipStream_t) { return hipSuccess; }
 hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs&, hipStream_t) { return hipSuccess; }
 hipError_t bn254_coop12_dbg_op(int32_t*, uint8_t*, size_t, int, int, const int32_t*, hipStream_t) { return hipSuccess; }
+hipError_t bn254_coop12_miller_fixed_keys(int32_t*, uint8_t*, size_t, const uint32_t*, uint32_t, const bn254::PlonkKeyDesc*, uint32_t, int, int, int, int, int, const int32_t*, int, hipStream_t) { return hipSuccess; }
 hipError_t bn254_coop12_miller_fixed(int32_t*, uint8_t*, size_t, int, const int32_t*, const int32_t*, const int32_t*, int, int, int, int, int, int, int, const int32_t*, int, hipStream_t) { return hipSuccess; }
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.

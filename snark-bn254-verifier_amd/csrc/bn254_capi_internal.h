@@ -44,6 +44,9 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
 hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
                                           void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
                                           hipStream_t s);
+hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                                   void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT,
+                                                   int T2, const uint32_t weight_key[11], hipStream_t s);   // BN254_FLAG_RLC: the weight stream of bn254_launch_plonk_stage2
 hipError_t bn254_launch_plonk_group_sums(int32_t* ws, const uint8_t* status, size_t n, int32_t* grp_ws, uint8_t* grp_status, int e_p0, int inf0, int e_p1, int inf1, hipStream_t s);
 hipError_t bn254_launch_plonk_group_scatter(uint8_t* status, size_t n, const uint8_t* grp_status, uint32_t* n_failed, hipStream_t s);
 
@@ -269,6 +272,7 @@ void plonk_plan(size_t n, size_t piece, int max_workers, int* workers, size_t* p
 void plonk_plan_for(size_t n, int* workers, size_t* per, size_t* pass_cap);     // the plan of a batch of n proofs (or slots) under the current knobs
 size_t plonk_piece_for(size_t n, int* max_workers);
 int plonk_plan_breaks(size_t out[4]);
+size_t plonk_rlc_min();                    // BN254_FLAG_RLC is honoured from this many proofs (slots) per pass (bn254_set_plonk_rlc_params)
 // one MSM launch of a pass on context c (rows + sums).  keys: the descriptors and the granule -> key words of a pass over the slots of a batch over many keys
 struct PlonkKeysRef { const bn254::PlonkKeyDesc* desc; uint32_t n_keys; const uint32_t* granule_key; };
 int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows);

@@ -72,6 +72,7 @@ static std::atomic<int> g_plonk_workers{[] { long v = env_long("BN254_PLONK_WORK
 static std::atomic<long> g_plonk_big_from{[] { long v = env_long("BN254_PLONK_BIG_FROM", 0); return v < 0 ? 0 : v; }()};      // 0: the measured plan of plonk_auto_plan
 // BN254_FLAG_RLC on the PlonK entry: honoured from this many proofs per pass (BN254_PLONK_RLC_MIN gives the initial value)
 static std::atomic<long> g_plonk_rlc_min{[] { long v = env_long("BN254_PLONK_RLC_MIN", 8192); return v < 64 ? 64 : v; }()};
+size_t plonk_rlc_min() { return (size_t)g_plonk_rlc_min.load(); }
 static std::atomic<long> g_plonk_big_piece{[] { long v = env_long("BN254_PLONK_BIG_PIECE", PLONK_BIG_PIECE_DEFAULT); return v < 256 ? 256 : (v > PLONK_MAX_LAUNCH ? (long)PLONK_MAX_LAUNCH : v); }()};
 // the plan of a batch (bn254_plonk_verify_batch): sub-batches side by side, proofs per sub-batch, proofs per pass of a sub-batch
 // The default plan by batch size (profiles/r04_plonk_plan_sweep.txt, one MI355X): chains of 5040-proof passes side by side up to ~9000 proofs (8192: 7.06 ms against
@@ -471,6 +472,11 @@ void bn254_set_plonk_params(long piece, int workers, long big_from, long big_pie
   if (workers >= 0) g_plonk_workers.store(workers < 1 ? 1 : (workers > PLONK_WORKERS ? PLONK_WORKERS : workers));
   if (big_from >= 0) g_plonk_big_from.store(big_from);      // 0: the measured default plan
   if (big_piece >= 0) g_plonk_big_piece.store(big_piece < 256 ? 256 : (big_piece > PLONK_MAX_LAUNCH ? (long)PLONK_MAX_LAUNCH : big_piece));
+}
+
+// the pass size from which BN254_FLAG_RLC is honoured, on one key and over a list (initial value: BN254_PLONK_RLC_MIN, default 8192): a group is 64 proofs, so never below 64
+void bn254_set_plonk_rlc_params(long min_pass) {
+  if (min_pass >= 0) g_plonk_rlc_min.store(min_pass < 64 ? 64 : min_pass);
 }
 
 int bn254_plonk_verify(const uint8_t* proof, size_t proof_len, const uint8_t* vk, size_t vk_len, const uint8_t* public_inputs,

@@ -11,6 +11,16 @@ using bn254::PlonkKeyDesc;
 #define PLONK_KEYS_HOST_PIECE ((size_t)16 << 20)
 #define PLONK_KEYS_MAX_PUBLIC ((size_t)1 << 20)     // a key that claims more inputs than this is not one a row can be passed for
 
+// The knob of a pass's per-proof pairing check (bn254_set_plonk_keys_params; BN254_PLONK_KEYS_COOP_MAX gives the initial value once, at load time): passes of up to
+// this many slots take the cooperative form (k_coop12_miller_fixed_keys), larger ones the lane form; 0: always the lane form.  BN254_COOP=0 switches it off
+#define PLONK_KEYS_COOP_MAX_DEFAULT COOP12_MAX_PROOFS_FIXED
+static long pk_coop_clamp(long v) { return v > (long)COOP12_MAX_PROOFS_FIXED ? (long)COOP12_MAX_PROOFS_FIXED : v; }
+static std::atomic<long> g_pk_coop_max{[] { long v = env_long("BN254_PLONK_KEYS_COOP_MAX", (long)PLONK_KEYS_COOP_MAX_DEFAULT); return v < 0 ? (long)PLONK_KEYS_COOP_MAX_DEFAULT : pk_coop_clamp(v); }()};
+bool plonk_keys_coop_form(size_t n) {
+  static const bool coop_on = [] { const char* e = getenv("BN254_COOP"); return !e || atoi(e) != 0; }();
+  return coop_on && n <= (size_t)g_pk_coop_max.load(std::memory_order_relaxed);
+}
+
 namespace {
 
 inline size_t up64(size_t v) { return (v + 63) & ~(size_t)63; }
@@ -67,6 +77,8 @@ struct PlonkKeySet {
   PlonkDev pool;
   PkCtxExtra extra[PLONK_WORKERS];
   std::vector<std::unique_ptr<PkCall>> free_calls;
+  // bn254_plonk_keys_state: passes that ran the joint check | groups they checked | groups that failed | passes whose per-proof check ran in the cooperative form
+  std::atomic<uint64_t> stat[4] = {};
   ~PlonkKeySet() {
     if (!ready && free_calls.empty()) return;
     if (hipSetDevice(device) == hipSuccess) (void)hipDeviceSynchronize();      // the members below release what they own on a device that is current and idle
@@ -104,6 +116,12 @@ struct PkSetCache {
       v->set = out; v->tick = ++clock;
     }
     return out;
+  }
+  std::shared_ptr<PlonkKeySet> peek(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device) {      // the cached set of this list, or none: nothing is created
+    std::lock_guard<std::mutex> lk(mu);
+    for (auto& x : e)
+      if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) return x.set;
+    return nullptr;
   }
   void drop(const bn254_plonk_pvk* member) {
     std::vector<std::shared_ptr<PlonkKeySet>> gone;
@@ -217,12 +235,15 @@ int pk_ensure_ctx(PlonkKeySet& s, const PlonkLease& lease, int w, size_t slots, 
   PkCtxExtra& x = s.extra[lease.idx[w]];
   const size_t rec_stride = (pk_rec_bytes(proof_stride) + 3) & ~(size_t)3;
   if ((rc = x.recs.ensure(c.cap * rec_stride, BN254_E_NOMEM)) || (rc = x.rows.ensure(c.cap * 32 * s.max_public, BN254_E_NOMEM))) return rc;
+  // BN254_FLAG_RLC: one group per granule of the capacity, points and status byte, and the failure count with its pinned copy
+  if (c.grp_ws.cap() < c.cap / 64 * (size_t)(G16_WS_BYTES_PER_PROOF / 4) || c.grp_status.cap() < c.cap / 64 || !c.d_fail || !c.h_fail)
+    return set_err(BN254_E_HIP, "PlonK key-set context without the group buffers of its capacity (internal sizing error)");
   return BN254_OK;
 }
 
 // ---- one pass: slots [s0, s0 + m) of the call's grouping on context c --------------------------------------------------------------------------------------------
 int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, size_t s0, size_t m, const uint8_t* d_proofs, size_t proof_stride, const uint8_t* d_inputs,
-                size_t input_stride, size_t n, uint8_t* d_status) {
+                size_t input_stride, size_t n, uint8_t* d_status, unsigned flags) {
   HIPCK(hipSetDevice(s.device));
   const bn254_plonk_pvk* m0 = s.list[0];
   const int T1 = plonk_stage1_terms(m0->key), T2 = plonk_stage2_terms(m0->key), TT = T2 + 2;
@@ -247,12 +268,38 @@ int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, 
   if (e != hipSuccess) return launch_err(e, "PlonK stage 1 over keys");
   int rc = plonk_msm(nullptr, &ref, c, m0->shape1, m, T1, true, nullptr, nullptr);
   if (rc) return rc;
-  e = bn254_launch_plonk_stage2_keys(s.desc, n_keys, gk, x.recs, rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, c.stream);
+  // BN254_FLAG_RLC, honoured from plonk_rlc_min slots per pass: the sequence of plonk_run_device over slots.  A group of 64 slots is a granule, so all its proofs have
+  // one key, and group g of the pass is checked against the tables of granule g; a padding slot is decided by stage 1 and contributes the identity
+  const bool rlc = (flags & BN254_FLAG_RLC) != 0 && m >= plonk_rlc_min();
+  if (rlc) {
+    if (m / 64 * (size_t)(G16_WS_BYTES_PER_PROOF / 4) > c.grp_ws.cap() || m / 64 > c.grp_status.cap()) return set_err(BN254_E_HIP, "PlonK key-set context smaller than the pass's groups (internal sizing error)");
+    e = bn254_launch_plonk_stage2_keys_weighted(s.desc, n_keys, gk, x.recs, rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, lam_key, c.stream);
+  } else
+    e = bn254_launch_plonk_stage2_keys(s.desc, n_keys, gk, x.recs, rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, c.stream);
   if (e != hipSuccess) return launch_err(e, "PlonK stage 2 over keys");
-  if ((rc = plonk_msm(nullptr, &ref, c, m0->shape2, m, TT, false, nullptr, nullptr))) return rc;
-  // always the throughput form of the pairing check: the cooperative and the two-chain forms read one key per launch
-  e = bn254_launch_pairing2_fixed_keys(c.ws, c.status, m, s.desc, n_keys, gk, s.one, BN254_ERR_PAIRING_FAILED, c.stream);
-  if (e != hipSuccess) return launch_err(e, "PlonK pairing check over keys");
+  if ((rc = plonk_msm(nullptr, &ref, c, rlc ? m0->shape2_rlc : m0->shape2, m, TT, false, nullptr, nullptr))) return rc;
+  bool exact = !rlc;
+  if (rlc) {
+    // group sums -> one cooperative pairing check per group with the group's key -> pending proofs of passed groups accepted.  The proofs of a failed group stay
+    // pending, and the exact check below runs on their wavefronts alone: every other wavefront of its kernels exits at once
+    const size_t groups = m / 64;
+    HIPCK(hipMemsetAsync(c.d_fail, 0, sizeof(uint32_t), c.stream));
+    e = bn254_launch_plonk_group_sums(c.ws, c.status, m, c.grp_ws, c.grp_status, VE_LX_ELEM, BN254_ST_LINF, VE_CX_ELEM, BN254_ST_LINF2, c.stream);
+    if (e == hipSuccess) e = bn254_launch_pairing2_fixed_groups_keys(c.grp_ws, c.grp_status, groups, s.desc, n_keys, gk, s.one, BN254_ERR_PAIRING_FAILED, c.stream);
+    if (e == hipSuccess) e = bn254_launch_plonk_group_scatter(c.status, m, c.grp_status, c.d_fail, c.stream);
+    if (e != hipSuccess) return launch_err(e, "PlonK joint pairing check over keys");
+    HIPCK(hipMemcpyAsync(c.h_fail, c.d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    HIPCK(hipStreamSynchronize(c.stream));
+    const uint32_t failed = *c.h_fail;
+    s.stat[0].fetch_add(1, std::memory_order_relaxed); s.stat[1].fetch_add(groups, std::memory_order_relaxed); s.stat[2].fetch_add(failed, std::memory_order_relaxed);
+    exact = failed != 0;
+  }
+  if (exact) {
+    // the form follows the pass's size (bn254_set_plonk_keys_params): cooperative with the key per item, or the lane form with the key per wavefront
+    e = bn254_launch_pairing2_fixed_keys(c.ws, c.status, m, s.desc, n_keys, gk, s.one, BN254_ERR_PAIRING_FAILED, c.stream);
+    if (e != hipSuccess) return launch_err(e, "PlonK pairing check over keys");
+    if (plonk_keys_coop_form(m)) s.stat[3].fetch_add(1, std::memory_order_relaxed);
+  }
   e = bn254_launch_plonk_keys_scatter(c.status, s2p, (uint32_t)m, (uint32_t)n, d_status, c.stream);
   if (e != hipSuccess) return launch_err(e, "PlonK key-set scatter");
   HIPCK(hipStreamSynchronize(c.stream));
@@ -262,7 +309,7 @@ int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, 
 // One batch on device buffers.  The grouping runs on the call's stream (after whatever that stream still copies); its slot count is read back -- 4 bytes, one wait: the
 // entries are synchronous anyway -- and the passes of the plan over that many slots run on leased contexts, one host thread per worker.
 int pk_batch(PlonkKeySet& s, PkCall& call, const uint32_t* d_index, const uint8_t* d_proofs, size_t proof_stride, const uint8_t* d_inputs, size_t input_stride, size_t n,
-             uint8_t* d_status) {
+             uint8_t* d_status, unsigned flags) {
   const uint32_t n_keys = (uint32_t)s.list.size();
   const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
   hipStream_t cs = call.ring.compute;
@@ -282,7 +329,7 @@ int pk_batch(PlonkKeySet& s, PkCall& call, const uint32_t* d_index, const uint8_
     const size_t lo = (size_t)w * plan.per, hi = lo + plan.per < slots ? lo + plan.per : slots;
     for (size_t off = lo; off < hi; off += plan.pass) {
       const size_t m = hi - off < plan.pass ? hi - off : plan.pass;
-      int r = pk_run_pass(s, lease.ctx(w), s.extra[lease.idx[w]], call, off, m, d_proofs, proof_stride, d_inputs, input_stride, n, d_status);
+      int r = pk_run_pass(s, lease.ctx(w), s.extra[lease.idx[w]], call, off, m, d_proofs, proof_stride, d_inputs, input_stride, n, d_status, flags);
       if (r) {   // work of this pass may still be enqueued: drain before the lease hands the context to the next call
         rcs[w] = r; errs[w] = g_err;
         (void)hipStreamSynchronize(lease.ctx(w).stream);
@@ -349,7 +396,7 @@ int bn254_plonk_verify_batch_keys_device(const bn254_plonk_pvk* const* pvks, siz
   if (rc) return rc;
   CallLease cl(*s);
   if ((rc = pk_ensure_call(*s, *cl.c, n, false, proof_stride, input_stride))) return rc;
-  return pk_batch(*s, *cl.c, (const uint32_t*)d_key_index, (const uint8_t*)d_proofs, proof_stride, (const uint8_t*)d_public_inputs, input_stride, n, (uint8_t*)d_status);
+  return pk_batch(*s, *cl.c, (const uint32_t*)d_key_index, (const uint8_t*)d_proofs, proof_stride, (const uint8_t*)d_public_inputs, input_stride, n, (uint8_t*)d_status, flags);
 }
 
 // Host buffers: the index is checked on the host first (the range check the device entry cannot make), then index, records and input rows go up through the call's
@@ -375,9 +422,60 @@ int bn254_plonk_verify_batch_keys(const bn254_plonk_pvk* const* pvks, size_t n_k
       (in_bytes && (rc = push(c.st_inputs, public_inputs, in_bytes))))
     return ring.drain(rc);
   if (ring.last()) HIPCK(hipStreamWaitEvent(ring.compute, ring.last(), 0));
-  if ((rc = pk_batch(*s, c, c.st_index, c.st_proofs, proof_stride, in_bytes ? (const uint8_t*)c.st_inputs : nullptr, input_stride, n, c.st_status))) return ring.drain(rc);
+  if ((rc = pk_batch(*s, c, c.st_index, c.st_proofs, proof_stride, in_bytes ? (const uint8_t*)c.st_inputs : nullptr, input_stride, n, c.st_status, flags))) return ring.drain(rc);
   HIPCK(hipMemcpyAsync(status, c.st_status, n, hipMemcpyDeviceToHost, ring.compute));
   HIPCK(hipStreamSynchronize(ring.compute));
+  return BN254_OK;
+}
+
+void bn254_set_plonk_keys_params(long coop_max) {
+  if (coop_max >= 0) g_pk_coop_max.store(pk_coop_clamp(coop_max));
+}
+// the two knobs a batch over a list follows, as they are now (the setters clamp): out[0] coop_max, out[1] the pass size from which BN254_FLAG_RLC is honoured
+int bn254_dbg_plonk_keys_knobs(long out[2]) {
+  if (!out) return set_err(BN254_E_BAD_ARG, "bad argument");
+  out[0] = g_pk_coop_max.load(); out[1] = (long)plonk_rlc_min();
+  return BN254_OK;
+}
+int bn254_plonk_keys_state(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device, uint64_t out[4]) {
+  if (!pvks || !out || n_keys == 0) return set_err(BN254_E_BAD_ARG, "bad argument");
+  for (size_t k = 0; k < n_keys; k++) if (!pvks[k]) return set_err(BN254_E_BAD_ARG, "bad argument: null key in the list");
+  std::shared_ptr<PlonkKeySet> s = pk_cache().peek(pvks, n_keys, device);
+  if (!s) return set_err(BN254_E_BAD_ARG, "no cached state for this key list on this device (no batch or reservation yet, or it was evicted)");
+  for (int i = 0; i < 4; i++) out[i] = s->stat[i].load(std::memory_order_relaxed);
+  return BN254_OK;
+}
+// k_coop12_miller_fixed_keys in store mode on the line tables of prepared PlonK keys, shaped as bn254_dbg_coop12_miller_fixed: item i belongs to entry
+// key_words[i >> key_shift] of the list; out_gt: the final-exponentiated product of its two pairings, 384 bytes per item
+int bn254_dbg_coop12_miller_fixed_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_words, unsigned key_shift, const uint8_t* g1_0, const uint8_t* g1_1,
+                                       const uint8_t* identity, uint8_t* out_gt, size_t n, int device) {
+  if (!pvks || !key_words || !g1_0 || !g1_1 || !out_gt || n == 0 || key_shift > 31) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > bn254_coop_max_proofs_fixed()) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  size_t max_public = 0;
+  int rc = pk_check_list(pvks, n_keys, &max_public);
+  if (rc) return rc;
+  if ((rc = check_device(device))) return rc;
+  std::shared_ptr<PlonkKeySet> s = pk_get_ready(pvks, n_keys, device, max_public, &rc);      // the members' tables on the device, the descriptors
+  if (rc) return rc;
+  const size_t n_words = ((n - 1) >> key_shift) + 1;
+  DevBuf<int32_t> ws; DevBuf<uint8_t> st_d, in, out; DevBuf<uint32_t> kw;
+  std::vector<uint8_t> st(n);
+  for (size_t i = 0; i < n; i++) st[i] = (uint8_t)(BN254_ST_PENDING | (identity && (identity[i] & 1) ? BN254_ST_LINF : 0) | (identity && (identity[i] & 2) ? BN254_ST_LINF2 : 0));
+  if ((rc = ws.ensure(n * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = st_d.ensure(n)) || (rc = in.ensure(128 * n)) || (rc = out.ensure(384 * n)) || (rc = kw.ensure(n_words))) return rc;
+  HIPCK(hipMemsetAsync(ws, 0, n * (size_t)G16_WS_BYTES_PER_PROOF, nullptr));
+  HIPCK(hipMemcpy(in, g1_0, 64 * n, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(in + 64 * n, g1_1, 64 * n, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(kw, key_words, n_words * sizeof(uint32_t), hipMemcpyHostToDevice));
+  hipError_t e = bn254_launch_dbg_load(ws, n, st_d, (int)VE_LX_ELEM, in, 4, nullptr);
+  if (e == hipSuccess) e = bn254_launch_dbg_load(ws, n, st_d, (int)VE_CX_ELEM, in + 64 * n, 4, nullptr);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipMemcpy(st_d, st.data(), n, hipMemcpyHostToDevice));      // after the loads (same stream): they set PENDING alone
+  // the arguments of the product's cooperative calls, without the target
+  e = bn254_coop12_miller_fixed_keys(ws, st_d, n, kw, key_shift, s->desc, (uint32_t)n_keys, VE_LX_ELEM, VE_CX_ELEM, BN254_ST_LINF, BN254_ST_LINF2, 1, nullptr, 0, nullptr);
+  if (e == hipSuccess) e = bn254_launch_dbg_store(ws, n, (int)VE_S0, out, 0, nullptr);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipDeviceSynchronize());
+  HIPCK(hipMemcpy(out_gt, out, 384 * n, hipMemcpyDeviceToHost));
   return BN254_OK;
 }
 

@@ -651,6 +651,56 @@ k_coop12_miller_g16_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t
   }
 }
 
+// ---- PlonK's two-pair check with the KEY TAKEN PER ITEM (a pass of a batch over many keys, and the groups of its BN254_FLAG_RLC form) ------------------------------
+// k_coop12_miller_fixed for exactly two pairs, except that item p belongs to key key_words[p >> key_shift] of the list (key_shift 6: a pass over slots with the
+// pass's granule -> key words; key_shift 0: one word per item, the groups of a pass, whose group g is its granule g) and takes tab0 / tab1 from that key's descriptor.
+// The five items of a wavefront may belong to five keys, so the tables are read at per-lane addresses (vector loads from pointers named global, as c12_key does):
+// every lane needs m and c of both entries whole -- c12_halves takes both components -- and leaves xi c where it is: 72 dwords per lane and step instead of the 108
+// of the two entries.  An entry of step s + 1 is requested right after the line coefficients of step s are formed from it, so it is in flight during that line
+// product and no second copy is alive.  A key word >= n_keys cannot occur for a pending slot; it reads key 0 and nothing outside the descriptors.
+struct C12TabMC { Fp2 m, c; };
+__device__ __forceinline__ C12TabMC c12_tab_mc(const int32_t* tab, int s) {
+  C12TabMC t;
+  t.m = c12_tab_fp2(tab + (size_t)s * FIXED_LINE_DWORDS); t.c = c12_tab_fp2(tab + (size_t)s * FIXED_LINE_DWORDS + 2 * BN_NL);
+  return t;
+}
+__global__ void __launch_bounds__(64)
+k_coop12_miller_fixed_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const uint32_t* __restrict__ key_words, uint32_t key_shift,
+                           const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, int e_p0, int e_p1, int inf0, int inf1, int fuse_final_exp,
+                           const int32_t* __restrict__ target, int reject_code) {
+  C12_PROLOGUE();
+  static_assert(sizeof(PlonkKeyDesc) == 40 && offsetof(PlonkKeyDesc, tab0) == 16 && offsetof(PlonkKeyDesc, tab1) == 24, "the descriptor's line tables are read by position");
+  const uint32_t kw = key_words[pc >> key_shift];
+  const uint64_t* kd = (const uint64_t*)(desc + (kw < n_keys ? kw : 0u));
+  const int32_t *tab0 = c12_global_ptr(kd[2]), *tab1 = c12_global_ptr(kd[3]);
+  const int F = C12_SLOT(VE_F);
+  co.put(F, (c == 0 && h == 0) ? fp_one() : fp_zero());
+  const Fp px0 = c12_ws_ld(ws, n, pc, e_p0), py0 = c12_ws_ld(ws, n, pc, e_p0 + 1), px1 = c12_ws_ld(ws, n, pc, e_p1), py1 = c12_ws_ld(ws, n, pc, e_p1 + 1);
+  const bool i0 = (st & inf0) != 0, i1 = (st & inf1) != 0;
+  C12TabMC l0 = c12_tab_mc(tab0, 0), l1 = c12_tab_mc(tab1, 0);
+  for (int s = 0; s < BN_ATE_STEPS; s++) {
+    const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
+    const int sn = s + 1 < BN_ATE_STEPS ? s + 1 : s;
+    if (kind == 0 && s != 0) c12_sqr(co, F);
+    { const C12H m = c12_halves(l0.m, h), d4 = c12_halves(l0.c, h);
+      C12H d3; d3.p = fp_mul(m.p, px0); d3.q = fp_mul(m.q, px0);
+      c12_mul_line_fp(co, F, py0, d3, d4, i0); }
+    l0 = c12_tab_mc(tab0, sn);        // step s + 1's: in flight during the second line product and the squaring of step s + 1
+    { const C12H m = c12_halves(l1.m, h), d4 = c12_halves(l1.c, h);
+      C12H d3; d3.p = fp_mul(m.p, px1); d3.q = fp_mul(m.q, px1);
+      c12_mul_line_fp(co, F, py1, d3, d4, i1); }
+    l1 = c12_tab_mc(tab1, sn);        // in flight during the squaring and the first line product of step s + 1
+  }
+  if (fuse_final_exp) {
+    Coop12Ops ops{co};
+    vm_final_exp_program(ops);
+    if (target) {
+      const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
+      if (pending && c == 0 && h == 0) status[p] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
+    } else c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
+  } else c12_store_f12(co, ws, n, p, F, VE_F, pending);
+}
+
 }  // namespace bn254
 
 using namespace bn254;
@@ -704,6 +754,17 @@ hipError_t bn254_coop12_miller_g16_keys(int32_t* ws, uint8_t* status, size_t n, 
   const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
   (void)hipFuncSetAttribute((const void*)k_coop12_miller_g16_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   hipLaunchKernelGGL(k_coop12_miller_g16_keys, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, key_index, desc, n_keys, inputs, input_stride, strict_scalars);
+  return hipGetLastError();
+}
+hipError_t bn254_coop12_miller_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_words, uint32_t key_shift, const bn254::PlonkKeyDesc* desc, uint32_t n_keys,
+                                          int e_p0, int e_p1, int inf0, int inf1, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s) {
+  const uint8_t* kinds = c12_kinds_dev();
+  if (!kinds) return hipErrorOutOfMemory;
+  if (n == 0 || n_keys == 0 || key_shift > 31) return hipErrorInvalidValue;
+  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
+  (void)hipFuncSetAttribute((const void*)k_coop12_miller_fixed_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(k_coop12_miller_fixed_keys, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, key_words, key_shift, desc, n_keys, e_p0, e_p1, inf0, inf1,
+                     fuse_final_exp, target, reject_code);
   return hipGetLastError();
 }
 // probe: op 0 mul 1 mul by conj(b) 2 conj(a) * b 3 sqr 4 cyclo_sqr_n (arg squarings) 5 frob (j = arg) 6 inv 7 conj 8 mul_line_fp 9 mul_line_fp with keep

@@ -267,17 +267,30 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
                      key, (PlonkWork*)d_work, (MsmTerm*)d_terms, d_flags, T1, ls);
   return hipGetLastError();
 }
-hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
-                                          void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
-                                          hipStream_t s) {
+static hipError_t plonk_stage2_keys_launch(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                           void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
+                                           const uint32_t* weight_key /* 11 words or nullptr */, hipStream_t s) {
   ChaChaKey wkey;
-  for (int i = 0; i < 8; i++) wkey.k[i] = 0u;
-  for (int i = 0; i < 3; i++) wkey.nonce[i] = 0u;
+  for (int i = 0; i < 8; i++) wkey.k[i] = weight_key ? weight_key[i] : 0u;
+  for (int i = 0; i < 3; i++) wkey.nonce[i] = weight_key ? weight_key[8 + i] : 0u;
+  if (weight_key) wkey.nonce[2] ^= 0x00524c43u;      // the weight stream of bn254_launch_plonk_stage2
   const uint32_t ls = pl_lane_stride(rec_stride, 0);
   if (16 + 64 * (size_t)ls > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage2_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 + 64 * (size_t)ls)); if (ae != hipSuccess) return ae; }
   hipLaunchKernelGGL(k_plonk_stage2_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 16 + 64 * (size_t)ls, s, desc, n_keys, granule_key, d_recs, rec_stride, (uint32_t)n, (PlonkWork*)d_work,
-                     d_lin_words, d_lin_inf, (MsmTerm*)d_terms, d_flags, d_status, TT, T2, ls, wkey, 0);
+                     d_lin_words, d_lin_inf, (MsmTerm*)d_terms, d_flags, d_status, TT, T2, ls, wkey, weight_key ? 1 : 0);
   return hipGetLastError();
+}
+hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                          void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
+                                          hipStream_t s) {
+  return plonk_stage2_keys_launch(desc, n_keys, granule_key, d_recs, rec_stride, n, d_work, d_lin_words, d_lin_inf, d_terms, d_flags, d_status, TT, T2, nullptr, s);
+}
+// BN254_FLAG_RLC over a list: every scalar of a slot's two sums carries the slot's weight (the pass's ChaCha key, the weight stream of the single-key launch)
+hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                                   void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT,
+                                                   int T2, const uint32_t weight_key[11], hipStream_t s) {
+  if (!weight_key) return hipErrorInvalidValue;
+  return plonk_stage2_keys_launch(desc, n_keys, granule_key, d_recs, rec_stride, n, d_work, d_lin_words, d_lin_inf, d_terms, d_flags, d_status, TT, T2, weight_key, s);
 }
 // weight_key != nullptr: BN254_FLAG_RLC -- every scalar of the proof's two sums carries the proof's weight (the call's key with another nonce word: a stream of its own)
 hipError_t bn254_launch_plonk_stage2(const void* d_key, const uint8_t* d_proofs, size_t stride, size_t n, void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf,

@@ -199,6 +199,12 @@ void bn254_launch_miller_run_fixed2_keys(const MillerKinds& kinds, int s_begin, 
                                          const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, int ep0, int inf0, int ep1, int inf1);
 hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key,
                                             const int32_t* target_one, int reject_code, hipStream_t s);
+// ... which takes the cooperative form (k_coop12_miller_fixed_keys, one launch) for a pass of up to bn254_set_plonk_keys_params' coop_max slots: the knob lives with the
+// host code of the lists (bn254_capi_plonk_keys.hip), which also counts the passes that took it
+bool plonk_keys_coop_form(size_t n);
+// the joint pairing check of a pass's groups (BN254_FLAG_RLC): group g belongs to the key of granule g.  Always cooperative
+hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t* grp_ws, uint8_t* grp_status, size_t groups, const bn254::PlonkKeyDesc* desc, uint32_t n_keys,
+                                                   const uint32_t* granule_key, const int32_t* target_one, int reject_code, hipStream_t s);
 // records and input rows of a pass in slot order / the slots' status bytes back to proof order (bn254_k_keys.hip).  slot_to_proof / granule_key: at the pass's first
 // slot; rec_bytes <= rec_stride, both multiples of 4; a padding slot gets an all-zero record (malformed: decided in stage 1) and is skipped on the way back
 hipError_t bn254_launch_plonk_keys_gather(const uint8_t* proofs, size_t stride, const uint8_t* inputs, size_t input_stride, uint32_t n_proofs, const uint32_t* slot_to_proof,
@@ -226,6 +232,9 @@ hipError_t bn254_coop12_final_exp(int32_t* ws, uint8_t* status, size_t n, hipStr
 hipError_t bn254_coop12_prepare();
 hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* tab0, const int32_t* tab1, const int32_t* tab2,
                                      int e_p0, int e_p1, int e_p2, int inf0, int inf1, int inf2, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s);
+// the two-pair check with the key per item: item p belongs to key key_words[p >> key_shift] of the list and reads that key's tab0 / tab1 (store mode without a target)
+hipError_t bn254_coop12_miller_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_words, uint32_t key_shift, const bn254::PlonkKeyDesc* desc, uint32_t n_keys,
+                                          int e_p0, int e_p1, int inf0, int inf1, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s);
 static inline size_t bn254_coop_max_proofs() { return COOP12_MAX_PROOFS; }
 static inline size_t bn254_coop_max_proofs_fixed() { return COOP12_MAX_PROOFS_FIXED; }
 double bn254_measure_valu_sustained(double ms_target);   // the same kernel back to back for ms_target milliseconds, one interval

@@ -1421,6 +1421,9 @@ hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t
   LaunchOps ops{ws, nn, status, grid, s, {nullptr, nullptr, nullptr}, nullptr};
   ops.inf_mask[0] = BN254_ST_LINF; ops.inf_mask[1] = BN254_ST_LINF2;
   ops.plonk_desc = desc; ops.n_keys = n_keys; ops.granule_key = granule_key;
+  // a pass of up to the knob's slots (bn254_set_plonk_keys_params; BN254_COOP=0: never): the cooperative layout with the key of every item's granule, ONE launch
+  if (plonk_keys_coop_form(n))
+    return bn254_coop12_miller_fixed_keys(ws, status, n, granule_key, 6, desc, n_keys, VE_LX, VE_CX, BN254_ST_LINF, BN254_ST_LINF2, 1, target_one, reject_code, s);
   BN_LAUNCH(KID_VM_INIT, k_vm_init, ws, nn, (const uint8_t*)status);
   // steps per launch as in the single-key form (BN254_MILLER_RUN_STEPS; 0 there selects the one-launch-per-operation kernels, which read one key per launch: the whole loop here)
   static const int run_steps = [] { const char* e = getenv("BN254_MILLER_RUN_STEPS"); int v = e ? atoi(e) : BN_ATE_STEPS; return v <= 0 ? BN_ATE_STEPS : v; }();
@@ -1428,4 +1431,11 @@ hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t
   vm_final_exp_program(ops);
   BN_LAUNCH(KID_COMPARE, k_g16_compare, ws, nn, status, target_one, reject_code);
   return hipGetLastError();
+}
+// the joint check of a pass with BN254_FLAG_RLC: one "item" per group of 64 slots (k_plonk_group_sums), and group g of a pass is its granule g, so the pass's granule ->
+// key words are the key per item.  At most PLONK_MAX_LAUNCH / 64 groups and neighbours of different keys: always the cooperative kernel
+hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t* grp_ws, uint8_t* grp_status, size_t groups, const PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key,
+                                                   const int32_t* target_one, int reject_code, hipStream_t s) {
+  if (groups > bn254_coop_max_proofs_fixed()) return hipErrorInvalidValue;
+  return bn254_coop12_miller_fixed_keys(grp_ws, grp_status, groups, granule_key, 0, desc, n_keys, VE_LX, VE_CX, BN254_ST_LINF, BN254_ST_LINF2, 1, target_one, reject_code, s);
 }

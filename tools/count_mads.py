@@ -421,7 +421,7 @@ def coop12_callees(funcs, notes, keys_notes):
 
 
 def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2, msm="msm"):
-    """kind 'g16': k_coop12_miller_g16; 'fixed': k_coop12_miller_fixed with n_pairs table-driven pairs."""
+    """kind 'g16': k_coop12_miller_g16; 'fixed': k_coop12_miller_fixed with n_pairs table-driven pairs; 'fixed_keys': its twin with the key per item, two pairs."""
     ins = callee_straight(funcs, frag)
     lg, mads = loops_of(ins)
     h, latches, c = max(lg, key=lambda g: g[2])              # the Miller loop: the loop holding the most multiply-adds
@@ -448,6 +448,20 @@ def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2, msm="msm"):
         ranges += [(s_lo, s_hi, 64.0 / steps), (a_lo, a_hi, 23.0 / steps), (d_lo, d_hi, 65.0 / steps)]
         notes.append("Miller loop x88: squaring of f (%d multiply-adds) x64, G2 addition rounds (%d) x23, G2 doubling rounds (%d) x65, three line products (%d) x88"
                      % (s_m, a_m, d_m, count_in(mads, lo, hi) - s_m - a_m - d_m))
+    elif kind == "fixed_keys":
+        # k_coop12_miller_fixed_keys, two layouts of the same loop: sqr as a forward-branched block ahead of the two pairs and one latch; or the two pairs, a first
+        # latch (taken when the next step does not square) and sqr as the fall-through to the second
+        assert (len(latches), len(conds)) in ((1, 1), (2, 0)), ("k_coop12_miller_fixed_keys: layout changed", latches, conds)
+        if conds:
+            (s_lo, s_hi, s_m), = conds
+        else:
+            s_lo, s_hi = latches[0] + 1, latches[1]
+            s_m = count_in(mads, s_lo, s_hi)
+        p_m = count_in(mads, lo, hi) - s_m
+        assert 700 <= s_m <= 800 and 1600 <= p_m <= 1800 and p_m % 2 == 0, (s_m, p_m)
+        ranges += [(s_lo, s_hi, 64.0 / steps)]
+        notes.append("Miller loop x88: squaring of f (%d multiply-adds) x64, line product of a table-driven pair (%d) x88 for each of the 2 pairs, the tables of the item's key"
+                     % (s_m, p_m // 2))
     else:
         # sqr (conditional), pair 0, pair 1 (conditional: n_pairs > 1), first latch (taken when n_pairs <= 2), pair 2, second latch
         assert len(latches) == 2 and len(conds) == 2, ("k_coop12_miller_fixed: layout changed", latches, conds)
@@ -481,13 +495,13 @@ def model_coop12(funcs):
         pass
     out = {}
     for name, frag, kind in (("k_coop12_miller_g16", "19k_coop12_miller_g16E", "g16"), ("k_coop12_miller_fixed", "21k_coop12_miller_fixedE", "fixed"),
-                             ("k_coop12_miller_g16_keys", "24k_coop12_miller_g16_keysE", "g16")):
-        tot, n2 = coop12_kernel(funcs, frag, kind, callees, ops, msm="msm_keys" if name.endswith("_keys") else "msm")
+                             ("k_coop12_miller_g16_keys", "24k_coop12_miller_g16_keysE", "g16"), ("k_coop12_miller_fixed_keys", "26k_coop12_miller_fixed_keysE", "fixed_keys")):
+        tot, n2 = coop12_kernel(funcs, frag, kind, callees, ops, msm="msm_keys" if name.endswith("g16_keys") else "msm")
         e = {"lanes_per_proof": 12, "proofs_per_wavefront": 5,
              "wavefront_instructions": {k: round(v, 1) for k, v in tot.items()},
              "mads_per_proof_launch": tot["mads"] * 12,
              "static_mads": sum(1 for _, t, _ in callee_straight(funcs, frag) if MAD.match(t)),
-             "model": "; ".join(n2 + ([n for n in notes if not n.startswith("c12_public_input_msm:")] + keys_notes if name.endswith("_keys") else notes)) + "; per proof = 12 lanes x the wavefront's count (lanes 60..63 idle)", "unmodelled": [], "symbol": frag}
+             "model": "; ".join(n2 + ([n for n in notes if not n.startswith("c12_public_input_msm:")] + keys_notes if name.endswith("g16_keys") else notes)) + "; per proof = 12 lanes x the wavefront's count (lanes 60..63 idle)", "unmodelled": [], "symbol": frag}
         if pmc and name in pmc:
             m = pmc[name]
             e["pmc_check"] = {"SQ_INSTS_VALU_INT64_per_wavefront": m["SQ_INSTS_VALU_INT64"], "model_int64": round(tot["int64"], 1),
