@@ -344,15 +344,19 @@ void keys_sets_drop(const bn254_g16_pvk*) {}
 // the hook of bn254_plonk_vk_free
 #if !defined(BN254_HOSTSAN_PLONK_KEYS)
 void plonk_keys_sets_drop(const bn254_plonk_pvk*) {}
+// plonk_msm and the launch helpers of plonk_pass (bn254_capi_plonk.hip) name the launchers of a pass over a key list; without the key-set file nothing passes them one
 hipError_t bn254_launch_g1_msm_rows_keys(const MsmPlan&, const int32_t*, const uint8_t*, size_t, int, int32_t*, int32_t*, const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, hipStream_t) {
-  return hipErrorInvalidDeviceFunction;      // plonk_msm (bn254_capi_plonk.hip) names it; without the key-set file nothing passes it a key list
+  return hipErrorInvalidDeviceFunction;
 }
+hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const uint8_t*, size_t, size_t, const uint8_t*, size_t, size_t, size_t, const uint32_t*, void*, void*,
+                                          uint8_t*, int, hipStream_t) { return hipErrorInvalidDeviceFunction; }
+hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const uint8_t*, size_t, size_t, void*, const uint32_t*, const uint8_t*, void*, uint8_t*, uint8_t*,
+                                          int, int, const uint32_t*, hipStream_t) { return hipErrorInvalidDeviceFunction; }
+hipError_t bn254_launch_pairing2_fixed_keys(int32_t*, uint8_t*, size_t, const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const int32_t*, int, hipStream_t) { return hipErrorInvalidDeviceFunction; }
 #endif
-// BN254_FLAG_RLC over a PlonK key list is honoured only from the threshold on (bn254_set_plonk_rlc_params), which tests/hostsan/hostsan_plonk_keys.cpp stays below: its
-// launchers are never reached there, and the harness that reaches them brings its own stand-ins (tests/hostsan/hostsan_plonk_keys_rlc.cpp)
-#if defined(BN254_HOSTSAN_PLONK_KEYS) && !defined(BN254_HOSTSAN_PLONK_KEYS_RLC)
-hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const uint8_t*, size_t, size_t, void*, const uint32_t*, const uint8_t*, void*, uint8_t*,
-                                                   uint8_t*, int, int, const uint32_t*, hipStream_t) { return hipErrorInvalidDeviceFunction; }
+// BN254_FLAG_RLC over a PlonK key list is honoured only from the threshold on (bn254_set_plonk_rlc_params), which tests/hostsan/hostsan_plonk_keys.cpp stays below: the
+// joint check over keys is never reached there, and the harness that reaches it brings its own stand-in (tests/hostsan/hostsan_plonk_keys_rlc.cpp)
+#if !defined(BN254_HOSTSAN_PLONK_KEYS_RLC)
 hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t*, uint8_t*, size_t, const bn254::PlonkKeyDesc*, uint32_t, const uint32_t*, const int32_t*, int, hipStream_t) {
   return hipErrorInvalidDeviceFunction;
 }

@@ -41,12 +41,10 @@ hipError_t bn254_launch_plonk_stage2(const void* d_key, const uint8_t* d_proofs,
 hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t proof_len,
                                           const uint8_t* d_inputs, size_t in_stride, size_t staged_public, size_t n, const uint32_t lam_key[11], void* d_work, void* d_terms,
                                           uint8_t* d_flags, int T1, hipStream_t s);
+// weight_key != nullptr: BN254_FLAG_RLC, the weight stream of bn254_launch_plonk_stage2
 hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
                                           void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
-                                          hipStream_t s);
-hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
-                                                   void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT,
-                                                   int T2, const uint32_t weight_key[11], hipStream_t s);   // BN254_FLAG_RLC: the weight stream of bn254_launch_plonk_stage2
+                                          const uint32_t* weight_key, hipStream_t s);
 hipError_t bn254_launch_plonk_group_sums(int32_t* ws, const uint8_t* status, size_t n, int32_t* grp_ws, uint8_t* grp_status, int e_p0, int inf0, int e_p1, int inf1, hipStream_t s);
 hipError_t bn254_launch_plonk_group_scatter(uint8_t* status, size_t n, const uint8_t* grp_status, uint32_t* n_failed, hipStream_t s);
 
@@ -231,6 +229,51 @@ class KeyCache {
   std::mutex mu_; std::vector<Entry> e_ = std::vector<Entry>((size_t)(slots() > 0 ? slots() : 1)); uint64_t clock_ = 0;
 };
 
+// ---- key sets of the batches over many keys (bn254_capi_keys.hip, bn254_capi_plonk_keys.hip): the last KEYS_SET_SLOTS (list, device) pairs, least recently used out
+// first.  Set has the members `list` (the handles as passed), `device` and `max_public`, which get() fills; everything else of a set is made ready by its first user,
+// under the set's own lock.  Entries are shared_ptrs: a set that is evicted, or dropped because one of its members was freed, releases its device memory when the last
+// call that still holds it returns.  Never destroyed (as the key cache: device memory must not be freed from a static destructor).
+#define KEYS_SET_SLOTS 4
+template <class Set, class Handle>
+struct KeySetCache {
+  std::shared_ptr<Set> get(const Handle* const* pvks, size_t n_keys, int device, size_t max_public) {
+    std::shared_ptr<Set> evicted, out;      // evicted: released outside the lock (its destructor waits for the device)
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      if (Entry* x = lookup(pvks, n_keys, device)) { x->tick = ++clock_; return x->set; }
+      Entry* v = &e_[0];
+      for (auto& x : e_) { if (!x.set) { v = &x; break; } if (x.tick < v->tick) v = &x; }
+      evicted = std::move(v->set);
+      out = std::make_shared<Set>();
+      out->list.assign(pvks, pvks + n_keys); out->device = device; out->max_public = max_public;
+      v->set = out; v->tick = ++clock_;
+    }
+    return out;
+  }
+  std::shared_ptr<Set> find(const Handle* const* pvks, size_t n_keys, int device) {      // the cached set of this list, or none: no insertion, no change of the order
+    std::lock_guard<std::mutex> lk(mu_);
+    Entry* x = lookup(pvks, n_keys, device);
+    return x ? x->set : nullptr;
+  }
+  void drop(const Handle* member) {      // every set that contains the handle; released outside the lock
+    std::vector<std::shared_ptr<Set>> gone;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      for (auto& x : e_)
+        if (x.set && std::find(x.set->list.begin(), x.set->list.end(), member) != x.set->list.end()) gone.push_back(std::move(x.set));
+    }
+  }
+
+ private:
+  struct Entry { std::shared_ptr<Set> set; uint64_t tick = 0; };
+  Entry* lookup(const Handle* const* pvks, size_t n_keys, int device) {
+    for (auto& x : e_)
+      if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) return &x;
+    return nullptr;
+  }
+  std::mutex mu_; Entry e_[KEYS_SET_SLOTS]; uint64_t clock_ = 0;
+};
+
 // Shared helpers (internal linkage across the bn254_capi*.hip objects only: none of them is part of the exported ABI)
 #pragma GCC visibility push(hidden)
 int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* inputs, size_t n_public, size_t n, const void* status,
@@ -273,9 +316,27 @@ void plonk_plan_for(size_t n, int* workers, size_t* per, size_t* pass_cap);     
 size_t plonk_piece_for(size_t n, int* max_workers);
 int plonk_plan_breaks(size_t out[4]);
 size_t plonk_rlc_min();                    // BN254_FLAG_RLC is honoured from this many proofs (slots) per pass (bn254_set_plonk_rlc_params)
-// one MSM launch of a pass on context c (rows + sums).  keys: the descriptors and the granule -> key words of a pass over the slots of a batch over many keys
-struct PlonkKeysRef { const bn254::PlonkKeyDesc* desc; uint32_t n_keys; const uint32_t* granule_key; };
-int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows);
+// What a pass runs against: ONE key's device state, or (desc != nullptr) the descriptors of a key list with the key of every granule of 64 slots.  The pass driver
+// itself never asks which: plonk_msm and the four launch helpers beside it (bn254_capi_plonk.hip) pick the launcher, and launched() the code of a launch that failed
+struct PlonkTables {
+  const PlonkDev* key; const bn254::PlonkKeyDesc* desc; uint32_t n_keys; const uint32_t* granule_key;
+  const int32_t* one;      // 1 in GT, the target of the pairing checks
+  int launched(hipError_t e, const char* what) const;
+};
+// The records and input rows of a pass in device memory, rec_stride bytes from one record to the next.  One key: the caller's own layout, rows of n_public inputs.
+// A list: gathered in slot order, proof_len the stride of the caller's records, rows in_stride bytes apart (null: no key has inputs), staged_public as
+// bn254_launch_plonk_stage1_keys takes it
+struct PlonkPassIn { const uint8_t* recs; size_t rec_stride; const uint8_t* inputs; size_t n_public, proof_len, in_stride, staged_public; };
+// what the joint check of a pass did (BN254_FLAG_RLC honoured: ran), and whether the per-proof check ran
+struct PlonkPassReport { bool joint = false; size_t groups = 0; uint32_t failed = 0; bool exact = false; };
+// one MSM launch of a pass on context c (rows + sums)
+int plonk_msm(const PlonkTables& t, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows);
+// One pass of m proofs (slots) on context c, from "records and rows are in device memory" to "the status bytes are in c.status", all enqueued on c.stream; shapes: the
+// key whose term counts and MSM shapes the pass has.  tk: null, or the eight timing events of PlonkCtx::tk
+int plonk_pass(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, unsigned flags, const Event* tk, PlonkPassReport* rep);
+// The passes of a plan -- worker w has items [w per, (w + 1) per) of `total`, `pass` at a time -- on the contexts of a lease: run_pass(w, first, m) inline for one
+// worker, on one host thread each otherwise.  The first failure is the call's (set_err)
+int plonk_run_workers(const PlonkLease& lease, int workers, size_t per, size_t pass, size_t total, const std::function<int(int, size_t, size_t)>& run_pass);
 void plonk_keys_sets_drop(const bn254_plonk_pvk* member);   // bn254_capi_plonk_keys.hip: forget every cached PlonK key set that contains this key
 // a PlonK batch whose public inputs are already rows of two inputs in device memory (d_rows, 64 bytes per proof): resident = true, proofs and status are device
 // memory too; false, they are host buffers and only the proofs are staged

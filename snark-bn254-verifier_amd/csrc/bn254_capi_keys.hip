@@ -1,5 +1,5 @@
 // bn254_capi_keys.hip -- Groth16 batches over many verifying keys in one call (include/bn254_verify.h, "Batches over many keys"): the per (key list, device) state --
-// descriptors, the keys' line tables, byte-window tables of all their K points in one allocation, the slot workspace -- its cache, and the three entries.
+// descriptors, the keys' line tables, byte-window tables of all their K points in one allocation, the slot workspace -- and the three entries (the cache of the sets: bn254_capi_internal.h, KeySetCache).
 // The kernels are in bn254_k_keys.hip / bn254_k_miller.hip (grouped form) and bn254_coop12.hip (direct form), the grouping arithmetic in bn254_keys.h, the choice
 // between the forms in bn254_g16_plan.h.
 #include "bn254_capi_internal.h"
@@ -57,47 +57,7 @@ struct KeySet {
   }
 };
 
-// The cache: the last KEYS_SET_SLOTS (list, device) pairs, least recently used out first.  Entries are shared_ptrs: a set that is evicted, or dropped because one of its
-// members was freed, releases its device memory when the last call that still holds it returns.  Never destroyed (as the key cache: device memory must not be freed from
-// a static destructor).
-#define KEYS_SET_SLOTS 4
-struct SetCache {
-  std::mutex mu;
-  struct Entry { std::shared_ptr<KeySet> set; uint64_t tick = 0; };
-  Entry e[KEYS_SET_SLOTS];
-  uint64_t clock = 0;
-  std::shared_ptr<KeySet> get(const bn254_g16_pvk* const* pvks, size_t n_keys, int device, size_t max_public) {
-    std::shared_ptr<KeySet> evicted;      // released outside the lock: its destructor waits for the device
-    std::shared_ptr<KeySet> out;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (auto& x : e)
-        if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) { x.tick = ++clock; return x.set; }
-      Entry* v = &e[0];
-      for (auto& x : e) { if (!x.set) { v = &x; break; } if (x.tick < v->tick) v = &x; }
-      evicted = std::move(v->set);
-      out = std::make_shared<KeySet>();
-      out->list.assign(pvks, pvks + n_keys); out->device = device; out->max_public = max_public;
-      v->set = out; v->tick = ++clock;
-    }
-    return out;
-  }
-  std::shared_ptr<KeySet> find(const bn254_g16_pvk* const* pvks, size_t n_keys, int device) {      // no insertion, no change of the order
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& x : e)
-      if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) return x.set;
-    return nullptr;
-  }
-  void drop(const bn254_g16_pvk* member) {
-    std::vector<std::shared_ptr<KeySet>> gone;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (auto& x : e)
-        if (x.set && std::find(x.set->list.begin(), x.set->list.end(), member) != x.set->list.end()) gone.push_back(std::move(x.set));
-    }
-  }
-};
-SetCache& set_cache() { static auto* c = new SetCache(); return *c; }
+KeySetCache<KeySet, bn254_g16_pvk>& set_cache() { static auto* c = new KeySetCache<KeySet, bn254_g16_pvk>(); return *c; }      // bn254_capi_internal.h
 
 // caller holds s.mu.  First use: descriptors, line tables and byte-window tables of the distinct keys.  Then the buffers of a batch of n proofs (with
 // BN254_FLAG_COMPRESSED_PROOFS in flags: its decompression scratch too).  Device memory that runs out here is BN254_E_NOMEM, as for tables that do not fit.

@@ -1,5 +1,6 @@
-// bn254_capi_plonk.hip -- the PlonK half of the C ABI (include/bn254_verify.h): the key's device tables and context pool, the batch plan, the
-// pass driver (every stage on the device: bn254_k_plonk.hip, bn254_k_msm.hip) and every bn254_plonk_* entry.
+// bn254_capi_plonk.hip -- the PlonK half of the C ABI (include/bn254_verify.h): the key's device tables and context pool, the batch plan, the pass
+// (plonk_pass: every stage on the device, bn254_k_plonk.hip and bn254_k_msm.hip; the one pass of single keys and of key lists, bn254_capi_plonk_keys.hip) with the
+// worker loop that runs the passes of a plan, and every bn254_plonk_* entry on one key.
 #include "bn254_capi_internal.h"
 
 #define PLONK_BIG_PIECE_DEFAULT 131072   // proofs per pass of a batch above 65 536 proofs (profiles/r05_plonk_piece_sweep.txt)
@@ -182,8 +183,8 @@ size_t bn254_plonk_vk_num_public(const bn254_plonk_pvk* pvk) { return pvk ? (siz
 
 // One MSM launch of a sub-batch: plan the rows for this batch size (bn254_msm.h: a pure function of the launch's term kinds, the item count and the lane
 // budget), check the plan against what the context holds -- the launch form follows the BATCH, the buffers the context's CAPACITY -- and enqueue rows + sums.
-// keys != nullptr (a batch over many keys, bn254_capi_plonk_keys.hip): the items are slots and the window tables are those of every granule's key
-int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows) {
+// Over a key list (bn254_capi_plonk_keys.hip) the items are slots and the window tables are those of every granule's key
+int plonk_msm(const PlonkTables& t, PlonkCtx& c, const MsmShape& shape, size_t m, int n_terms, bool to_words, size_t* lanes_out, hipEvent_t ev_rows) {
   MsmPlan plan;
   const size_t m_pad = (m + 63) & ~(size_t)63;
   // BN254_MSM_SPLIT_AT (experiments): the bit position at which the variable terms' low and high rows meet, instead of the planner's choice
@@ -191,8 +192,8 @@ int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, 
   if (!msm_plan_build(plan, shape, m_pad, msm_lane_budget(), force_a, plonk_joint_g(m_pad))) return set_err(BN254_E_BAD_ARG, "PlonK key shape needs more MSM rows than the launch supports");
   if (m > c.cap || bn254_g1_msm_scratch_lanes(plan, m) > c.glv_lanes || (size_t)plan.n_rows * m > c.part_points || (size_t)plan.n_rows > (size_t)MSM_MAX_ROWS)
     return set_err(BN254_E_HIP, "PlonK context smaller than the launch (internal sizing error)");
-  hipError_t e = keys ? bn254_launch_g1_msm_rows_keys(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, keys->desc, keys->n_keys, keys->granule_key, c.stream)
-                      : bn254_launch_g1_msm_rows(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, fixed_tabs, c.stream);
+  hipError_t e = t.desc ? bn254_launch_g1_msm_rows_keys(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, t.desc, t.n_keys, t.granule_key, c.stream)
+                        : bn254_launch_g1_msm_rows(plan, (const int32_t*)(MsmTerm*)c.terms, c.flags, m, n_terms, c.part, c.glv_tab, t.key->fixed_tabs, c.stream);
   if (ev_rows) HIPCK(hipEventRecord(ev_rows, c.stream));
   if (e == hipSuccess)
     e = to_words ? bn254_launch_g1_sum_rows(plan, c.part, m, c.words, c.inf, nullptr, nullptr, 0, 0, 0, 0, c.stream)
@@ -201,35 +202,107 @@ int plonk_msm(const int32_t* fixed_tabs, const PlonkKeysRef* keys, PlonkCtx& c, 
   if (lanes_out) *lanes_out = (size_t)plan.n_rows * m_pad;
   return BN254_OK;
 }
+// The other launches of a pass that differ between one key and a list: each picks the launcher and hands it its arguments, nothing else.
+int PlonkTables::launched(hipError_t e, const char* what) const {
+  if (e == hipSuccess) return BN254_OK;
+  return desc ? launch_err(e, what) : set_err(BN254_E_HIP, std::string(what) + " launch: " + hipGetErrorString(e));
+}
+static int pass_stage1(const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, const uint32_t lam_key[11], int T1) {
+  return t.launched(t.desc ? bn254_launch_plonk_stage1_keys(t.desc, t.n_keys, t.granule_key, in.recs, in.rec_stride, in.proof_len, in.inputs, in.in_stride, in.staged_public, m, lam_key,
+                                                            c.d_work, c.terms, c.flags, T1, c.stream)
+                           : bn254_launch_plonk_stage1(t.key->d_key, in.recs, in.rec_stride, in.inputs, in.n_public, m, lam_key, c.d_work, c.terms, c.flags, T1, c.stream),
+                    "PlonK stage 1");
+}
+static int pass_stage2(const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, int TT, int T2, const uint32_t* weight_key) {
+  return t.launched(t.desc ? bn254_launch_plonk_stage2_keys(t.desc, t.n_keys, t.granule_key, in.recs, in.rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2,
+                                                            weight_key, c.stream)
+                           : bn254_launch_plonk_stage2(t.key->d_key, in.recs, in.rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, weight_key, c.stream),
+                    "PlonK stage 2");
+}
+// the pairing check of every pending proof: over a list in the form that follows the pass's size (bn254_set_plonk_keys_params: cooperative with the key per item, or
+// the lane form with the key per wavefront)
+static hipError_t pass_check_items(const PlonkTables& t, PlonkCtx& c, size_t m) {
+  return t.desc ? bn254_launch_pairing2_fixed_keys(c.ws, c.status, m, t.desc, t.n_keys, t.granule_key, t.one, BN254_ERR_PAIRING_FAILED, c.stream)
+                : bn254_launch_pairing2_fixed(c.ws, c.status, m, t.key->tab0, t.key->tab1, t.one, BN254_ERR_PAIRING_FAILED, c.stream, c.aux, c.ev_fork, c.ev_join);
+}
+// the pairing check of every group of 64.  Over a list a group is a granule, so all its proofs have one key, and group g of the pass is checked against the tables of
+// granule g
+static hipError_t pass_check_groups(const PlonkTables& t, PlonkCtx& c, size_t groups) {
+  return t.desc ? bn254_launch_pairing2_fixed_groups_keys(c.grp_ws, c.grp_status, groups, t.desc, t.n_keys, t.granule_key, t.one, BN254_ERR_PAIRING_FAILED, c.stream)
+                : bn254_launch_pairing2_fixed(c.grp_ws, c.grp_status, groups, t.key->tab0, t.key->tab1, t.one, BN254_ERR_PAIRING_FAILED, c.stream, c.aux, c.ev_fork, c.ev_join);
+}
+
+// The KZG batching scalar of every proof: fresh, uniform and unpredictable to the prover, as the reference draws it
+// (Fr::random(&mut OsRng), plonk/kzg.rs:149-154).  It MUST be secret until the proof is fixed: the two opening quotients are bound by
+// no transcript, so a prover who knows lambda can shift them by (lambda D, -D) and cancel a wrong evaluation
+// (tests/test_oracle_golden.py::test_kzg_batching_scalar_must_be_unpredictable).  A ChaCha20 key and nonce from getrandom(2) per pass;
+// k_plonk_stage1 gives proof i the 384 bits of blocks 3i .. 3i+2 reduced mod r.
+static int plonk_fresh_lam_key(uint32_t lam_key[11]) {
+  for (size_t got = 0; got < 11 * sizeof(uint32_t);) {
+    ssize_t k = getrandom((uint8_t*)lam_key + got, 11 * sizeof(uint32_t) - got, 0);
+    if (k <= 0) return set_err(BN254_E_HIP, "getrandom failed: no KZG batching scalars");
+    got += (size_t)k;
+  }
+  return BN254_OK;
+}
+
+// One pass with BOTH host stages on the device (bn254_k_plonk.hip): stage 1 -> digest MSM -> stage 2 -> folding MSMs -> pairing check on the context's stream, without
+// a host wait in between unless BN254_FLAG_RLC is honoured.  Over a list a padding slot is decided by stage 1 and contributes the identity to everything after it.
+int plonk_pass(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, unsigned flags, const Event* tk, PlonkPassReport* rep) {
+  const int T1 = plonk_stage1_terms(shapes->key), T2 = plonk_stage2_terms(shapes->key), TT = T2 + 2;
+  *rep = PlonkPassReport();
+  if (m > c.cap) return set_err(BN254_E_HIP, "PlonK context smaller than the pass (internal sizing error)");
+  uint32_t lam_key[11];
+  int rc = plonk_fresh_lam_key(lam_key);
+  if (rc) return rc;
+  auto mark = [&](int k) { return tk ? hipEventRecord(tk[k], c.stream) : hipSuccess; };
+  HIPCK(mark(0));
+  if ((rc = pass_stage1(t, in, c, m, lam_key, T1))) return rc;
+  HIPCK(mark(1));
+  if ((rc = plonk_msm(t, c, shapes->shape1, m, T1, true, &c.last_lanes[0], tk ? (hipEvent_t)tk[2] : nullptr))) return rc;
+  HIPCK(mark(3));
+  // BN254_FLAG_RLC: the pairing checks of the pass batched over groups of 64 proofs -- honoured from plonk_rlc_min proofs (slots) per pass (below, the one remaining
+  // pairing is the same latency-bound launch as the per-proof checks and nothing is gained)
+  const bool rlc = (flags & BN254_FLAG_RLC) != 0 && m >= plonk_rlc_min();
+  const size_t groups = (m + 63) / 64;
+  if (rlc && (groups * (size_t)(G16_WS_BYTES_PER_PROOF / 4) > c.grp_ws.cap() || groups > c.grp_status.cap()))
+    return set_err(BN254_E_HIP, "PlonK context smaller than the pass's groups (internal sizing error)");
+  if ((rc = pass_stage2(t, in, c, m, TT, T2, rlc ? lam_key : nullptr))) return rc;
+  HIPCK(mark(4));
+  if ((rc = plonk_msm(t, c, rlc ? shapes->shape2_rlc : shapes->shape2, m, TT, false, &c.last_lanes[1], tk ? (hipEvent_t)tk[5] : nullptr))) return rc;
+  HIPCK(mark(6));
+  rep->exact = !rlc;
+  if (rlc) {
+    // group sums (weighted points of the 64 proofs of a wavefront) -> one pairing check per group -> pending proofs of passed groups accepted; the proofs of a
+    // failed group stay pending and the exact check below runs on exactly their wavefronts (every other wavefront of its kernels exits at once)
+    HIPCK(hipMemsetAsync(c.d_fail, 0, sizeof(uint32_t), c.stream));
+    hipError_t e = bn254_launch_plonk_group_sums(c.ws, c.status, m, c.grp_ws, c.grp_status, VE_LX_ELEM, BN254_ST_LINF, VE_CX_ELEM, BN254_ST_LINF2, c.stream);
+    if (e == hipSuccess) e = pass_check_groups(t, c, groups);
+    if (e == hipSuccess) e = bn254_launch_plonk_group_scatter(c.status, m, c.grp_status, c.d_fail, c.stream);
+    if ((rc = t.launched(e, "PlonK joint pairing check"))) return rc;
+    HIPCK(hipMemcpyAsync(c.h_fail, c.d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    HIPCK(hipStreamSynchronize(c.stream));
+    rep->joint = true; rep->groups = groups; rep->failed = *c.h_fail;
+    rep->exact = rep->failed != 0;
+  }
+  if (rep->exact && (rc = t.launched(pass_check_items(t, c, m), "PlonK pairing check"))) return rc;
+  HIPCK(mark(7));
+  return BN254_OK;
+}
 
 extern "C" {
 
-// The same sub-batch with BOTH host stages on the device (bn254_k_plonk.hip): one H2D copy of the proofs and inputs, stage 1 -> digest MSM -> stage 2 ->
-// folding MSMs -> pairing check on the context's stream without a host wait in between, one D2H copy of the status bytes.
+// One sub-batch of a batch on ONE key: one H2D copy of the proofs and inputs, the pass, one D2H copy of the status bytes.
 // resident: proofs / public_inputs / status are DEVICE memory of `device` (bn254_plonk_verify_batch_device): no staging copy, the status bytes leave with a device-to-device copy.
 // d_rows (SP1 public inputs): the pass's public inputs are already in device memory (n_public = 2), so with host buffers only the proofs are staged
 static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, PlonkCtx& c, int device, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
                             size_t n_public, size_t m, uint8_t* status, unsigned flags, bool resident, const uint8_t* d_rows = nullptr) {
   HIPCK(hipSetDevice(device));
-  const PlonkKey& key = pvk->key;
-  const int T1 = plonk_stage1_terms(key), T2 = plonk_stage2_terms(key), TT = T2 + 2;
   auto now = [] { return std::chrono::steady_clock::now(); };
   auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
   auto t0 = now();
   const size_t pb = m * proof_stride, ib = d_rows ? 0 : m * n_public * 32, need = pb + ib;
   if (!resident && need > c.in_cap()) return set_err(BN254_E_HIP, "PlonK context staging smaller than the pass (internal sizing error)");   // sized by plonk_ensure_ctx
-  if (m > c.cap) return set_err(BN254_E_HIP, "PlonK context smaller than the pass (internal sizing error)");
-  // The KZG batching scalar of every proof: fresh, uniform and unpredictable to the prover, as the reference draws it
-  // (Fr::random(&mut OsRng), plonk/kzg.rs:149-154).  It MUST be secret until the proof is fixed: the two opening quotients are bound by
-  // no transcript, so a prover who knows lambda can shift them by (lambda D, -D) and cancel a wrong evaluation
-  // (tests/test_oracle_golden.py::test_kzg_batching_scalar_must_be_unpredictable).  A ChaCha20 key and nonce from getrandom(2) per call;
-  // k_plonk_stage1 gives proof i the 384 bits of blocks 3i .. 3i+2 reduced mod r.
-  uint32_t lam_key[11];
-  for (size_t got = 0; got < sizeof lam_key;) {
-    ssize_t k = getrandom((uint8_t*)lam_key + got, sizeof lam_key - got, 0);
-    if (k <= 0) return set_err(BN254_E_HIP, "getrandom failed: no KZG batching scalars");
-    got += (size_t)k;
-  }
   if (!resident) {
     parallel_copy(c.h_in, proofs, pb);
     if (ib) parallel_copy(c.h_in + pb, public_inputs, ib);
@@ -237,41 +310,9 @@ static int plonk_run_device(const bn254_plonk_pvk* pvk, const PlonkDev* d, Plonk
   auto t1_ = now();
   if (!resident) HIPCK(hipMemcpyAsync(c.d_in, c.h_in, need, hipMemcpyHostToDevice, c.stream));
   const uint8_t* d_proofs = resident ? proofs : c.d_in; const uint8_t* d_inputs = d_rows ? d_rows : resident ? public_inputs : c.d_in + pb;
-  HIPCK(hipEventRecord(c.tk[0], c.stream));
-  hipError_t e = bn254_launch_plonk_stage1(d->d_key, d_proofs, proof_stride, d_inputs, n_public, m, lam_key, c.d_work, c.terms, c.flags, T1, c.stream);
-  if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("PlonK stage 1 launch: ") + hipGetErrorString(e));
-  HIPCK(hipEventRecord(c.tk[1], c.stream));
-  int mrc = plonk_msm(d->fixed_tabs, nullptr, c, pvk->shape1, m, T1, true, &c.last_lanes[0], c.tk[2]);
-  if (mrc) return mrc;
-  HIPCK(hipEventRecord(c.tk[3], c.stream));
-  // BN254_FLAG_RLC: the pairing checks of the pass batched over groups of 64 proofs -- honoured from g_plonk_rlc_min proofs per pass (below, the one remaining
-  // pairing is the same latency-bound launch as the per-proof checks and nothing is gained)
-  const bool rlc = (flags & BN254_FLAG_RLC) != 0 && m >= (size_t)g_plonk_rlc_min.load();
-  e = bn254_launch_plonk_stage2(d->d_key, d_proofs, proof_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, rlc ? lam_key : nullptr, c.stream);
-  HIPCK(hipEventRecord(c.tk[4], c.stream));
-  if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("PlonK stage 2 launch: ") + hipGetErrorString(e));
-  mrc = plonk_msm(d->fixed_tabs, nullptr, c, rlc ? pvk->shape2_rlc : pvk->shape2, m, TT, false, &c.last_lanes[1], c.tk[5]);
-  if (mrc) return mrc;
-  HIPCK(hipEventRecord(c.tk[6], c.stream));
-  bool exact = !rlc;
-  if (rlc) {
-    // group sums (weighted points of the 64 proofs of a wavefront) -> one pairing check per group -> pending proofs of passed groups accepted; the proofs of a
-    // failed group stay pending and the exact check below runs on exactly their wavefronts (every other wavefront of its kernels exits at once)
-    const size_t groups = (m + 63) / 64;
-    HIPCK(hipMemsetAsync(c.d_fail, 0, sizeof(uint32_t), c.stream));
-    e = bn254_launch_plonk_group_sums(c.ws, c.status, m, c.grp_ws, c.grp_status, VE_LX_ELEM, BN254_ST_LINF, VE_CX_ELEM, BN254_ST_LINF2, c.stream);
-    if (e == hipSuccess) e = bn254_launch_pairing2_fixed(c.grp_ws, c.grp_status, groups, d->tab0, d->tab1, d->one, BN254_ERR_PAIRING_FAILED, c.stream, c.aux, c.ev_fork, c.ev_join);
-    if (e == hipSuccess) e = bn254_launch_plonk_group_scatter(c.status, m, c.grp_status, c.d_fail, c.stream);
-    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("joint pairing launch: ") + hipGetErrorString(e));
-    HIPCK(hipMemcpyAsync(c.h_fail, c.d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-    HIPCK(hipStreamSynchronize(c.stream));
-    exact = *c.h_fail != 0;
-  }
-  if (exact) {
-    e = bn254_launch_pairing2_fixed(c.ws, c.status, m, d->tab0, d->tab1, d->one, BN254_ERR_PAIRING_FAILED, c.stream, c.aux, c.ev_fork, c.ev_join);
-    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("pairing launch: ") + hipGetErrorString(e));
-  }
-  HIPCK(hipEventRecord(c.tk[7], c.stream));
+  PlonkPassReport rep;
+  int rc = plonk_pass(pvk, PlonkTables{d, nullptr, 0, nullptr, d->one}, PlonkPassIn{d_proofs, proof_stride, d_inputs, n_public, 0, 0, 0}, c, m, flags, c.tk, &rep);
+  if (rc) return rc;
   if (resident) HIPCK(hipMemcpyAsync(status, c.status, m, hipMemcpyDeviceToDevice, c.stream));
   else HIPCK(hipMemcpyAsync(c.h_status, c.status, m, hipMemcpyDeviceToHost, c.stream));
   HIPCK(hipStreamSynchronize(c.stream));
@@ -327,6 +368,31 @@ int plonk_plan_breaks(size_t out[4]) {
   return 0;
 }
 
+int plonk_run_workers(const PlonkLease& lease, int workers, size_t per, size_t pass, size_t total, const std::function<int(int, size_t, size_t)>& run_pass) {
+  std::vector<int> rcs(workers, BN254_OK); std::vector<std::string> errs(workers);
+  auto body = [&](int w) {
+    const size_t lo = (size_t)w * per, hi = lo + per < total ? lo + per : total;
+    for (size_t off = lo; off < hi; off += pass) {
+      int r = run_pass(w, off, hi - off < pass ? hi - off : pass);
+      if (r) {
+        // work of this pass may still be enqueued on the context's streams: drain them before the lease hands the context (its staging, its term and status
+        // buffers) to the next call
+        rcs[w] = r; errs[w] = g_err;
+        (void)hipStreamSynchronize(lease.ctx(w).stream); (void)hipStreamSynchronize(lease.ctx(w).aux);
+        return;
+      }
+    }
+  };
+  if (workers == 1) body(0);
+  else {
+    std::vector<std::thread> th;
+    for (int w = 0; w < workers; w++) th.emplace_back(body, w);
+    for (auto& t : th) t.join();
+  }
+  for (int w = 0; w < workers; w++) if (rcs[w]) return set_err(rcs[w], errs[w]);
+  return BN254_OK;
+}
+
 // One batch.  resident = false: proofs / public_inputs / status are the caller's host buffers (each pass stages its share through the context's pinned memory);
 // resident = true: they are device memory of `device` and nothing is staged.  Either way the call returns when every status byte is where the caller asked for it.
 // d_rows: see plonk_run_device (public_inputs is then ignored and n_public must be 2)
@@ -347,30 +413,10 @@ static int plonk_batch(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t
   plonk_plan_for(n, &workers, &per, &pass_cap);
   PlonkLease lease(d, workers);   // waits until that many contexts are free
   for (int w = 0; w < workers; w++) if ((rc = plonk_ensure_ctx(pvk, lease.ctx(w), pass_cap, !resident ? pass_cap * (proof_stride + (d_rows ? 0 : n_public * 32)) : 0))) return rc;
-  std::vector<int> rcs(workers, BN254_OK); std::vector<std::string> errs(workers);
-  auto body = [&](int w) {
-    const size_t lo = (size_t)w * per, hi = lo + per < n ? lo + per : n;
-    for (size_t off = lo; off < hi; off += pass_cap) {
-      const size_t m = hi - off < pass_cap ? hi - off : pass_cap;
-      int r = plonk_run_device(pvk, d, lease.ctx(w), device, proofs + off * proof_stride, proof_stride, d_rows ? nullptr : public_inputs + off * n_public * 32, n_public, m,
-                               status + off, flags, resident, d_rows ? d_rows + off * 64 : nullptr);
-      if (r) {
-        // work of this pass may still be enqueued on the context's streams: drain them before the lease hands the context (its staging, its term and status
-        // buffers) to the next call
-        rcs[w] = r; errs[w] = g_err;
-        (void)hipStreamSynchronize(lease.ctx(w).stream); (void)hipStreamSynchronize(lease.ctx(w).aux);
-        return;
-      }
-    }
-  };
-  if (workers == 1) body(0);
-  else {
-    std::vector<std::thread> th;
-    for (int w = 0; w < workers; w++) th.emplace_back(body, w);
-    for (auto& t : th) t.join();
-  }
-  for (int w = 0; w < workers; w++) if (rcs[w]) return set_err(rcs[w], errs[w]);
-  return BN254_OK;
+  return plonk_run_workers(lease, workers, per, pass_cap, n, [&](int w, size_t off, size_t m) {
+    return plonk_run_device(pvk, d, lease.ctx(w), device, proofs + off * proof_stride, proof_stride, d_rows ? nullptr : public_inputs + off * n_public * 32, n_public, m, status + off,
+                            flags, resident, d_rows ? d_rows + off * 64 : nullptr);
+  });
 }
 int plonk_batch_rows(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* d_rows, size_t n, uint8_t* status, int device, unsigned flags,
                      bool resident) {

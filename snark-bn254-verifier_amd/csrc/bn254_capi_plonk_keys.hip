@@ -1,13 +1,13 @@
 // bn254_capi_plonk_keys.hip -- PlonK batches over many verifying keys in one call (include/bn254_verify.h, "PlonK batches over many keys"): the per (key list,
-// device) state -- the descriptors of the members' own device tables, a pool of pass contexts, the buffers of a call -- its cache, the plan over slots, the pass
-// driver and the three entries.  The grouping is Groth16's (bn254_keys.h, k_keys_count / _scan / _place); the kernels of a pass are the `_keys` twins of the
-// single-key ones, beside them in bn254_k_plonk.hip, bn254_k_msm.hip, bn254_k_miller.hip, and the gather / scatter pair in bn254_k_keys.hip.
+// device) state -- the descriptors of the members' own device tables, a pool of pass contexts, the buffers of a call -- the plan over slots, what a pass over slots
+// has around the one pass of bn254_capi_plonk.hip (plonk_pass: gather before, scatter after, the counters) and the three entries.  The grouping is Groth16's
+// (bn254_keys.h, k_keys_count / _scan / _place) and so is the cache of the sets (bn254_capi_internal.h, KeySetCache); the kernels of a pass are the `_keys` twins of
+// the single-key ones, beside them in bn254_k_plonk.hip, bn254_k_msm.hip, bn254_k_miller.hip, and the gather / scatter pair in bn254_k_keys.hip.
 #include "bn254_capi_internal.h"
 #include "bn254_keys.h"
 
 using bn254::PlonkKeyDesc;
 
-#define PLONK_KEYS_SET_SLOTS 4
 #define PLONK_KEYS_HOST_PIECE ((size_t)16 << 20)
 #define PLONK_KEYS_MAX_PUBLIC ((size_t)1 << 20)     // a key that claims more inputs than this is not one a row can be passed for
 
@@ -68,7 +68,8 @@ struct PkCtxExtra { DevBuf<uint8_t> recs, rows; };      // the records and input
 struct PlonkKeySet {
   std::vector<const bn254_plonk_pvk*> list;   // the handles as passed (order matters: key_index refers to it)
   int device = 0;
-  size_t max_public = 0, staged_public = 0; uint32_t n_qcp = 0;
+  size_t max_public = 0;
+  size_t staged_public = 0;                   // the most inputs any member stages in LDS (bn254_launch_plonk_stage1_keys); with the descriptors, at the first use
   std::mutex mu;                              // the first use (descriptors) and the list of free call buffers
   bool ready = false;
   DevBuf<PlonkKeyDesc> desc;
@@ -94,45 +95,7 @@ struct CallLease {    // a call's buffers: taken from the set's free list (or ne
   ~CallLease() { std::lock_guard<std::mutex> lk(s.mu); s.free_calls.push_back(std::move(c)); }
 };
 
-// The cache: the last PLONK_KEYS_SET_SLOTS (list, device) pairs, least recently used out first (as the Groth16 sets': entries are shared_ptrs, never destroyed from a
-// static destructor)
-struct PkSetCache {
-  std::mutex mu;
-  struct Entry { std::shared_ptr<PlonkKeySet> set; uint64_t tick = 0; };
-  Entry e[PLONK_KEYS_SET_SLOTS];
-  uint64_t clock = 0;
-  std::shared_ptr<PlonkKeySet> get(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device, size_t max_public) {
-    std::shared_ptr<PlonkKeySet> evicted, out;      // evicted: released outside the lock (its destructor waits for the device)
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (auto& x : e)
-        if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) { x.tick = ++clock; return x.set; }
-      Entry* v = &e[0];
-      for (auto& x : e) { if (!x.set) { v = &x; break; } if (x.tick < v->tick) v = &x; }
-      evicted = std::move(v->set);
-      out = std::make_shared<PlonkKeySet>();
-      out->list.assign(pvks, pvks + n_keys); out->device = device; out->max_public = max_public; out->n_qcp = pvks[0]->key.n_qcp;
-      for (size_t k = 0; k < n_keys; k++) { const size_t p = (size_t)pvks[k]->key.nb_public; if (p * 32 <= 256 && p > out->staged_public) out->staged_public = p; }
-      v->set = out; v->tick = ++clock;
-    }
-    return out;
-  }
-  std::shared_ptr<PlonkKeySet> peek(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device) {      // the cached set of this list, or none: nothing is created
-    std::lock_guard<std::mutex> lk(mu);
-    for (auto& x : e)
-      if (x.set && x.set->device == device && x.set->list.size() == n_keys && memcmp(x.set->list.data(), pvks, n_keys * sizeof(*pvks)) == 0) return x.set;
-    return nullptr;
-  }
-  void drop(const bn254_plonk_pvk* member) {
-    std::vector<std::shared_ptr<PlonkKeySet>> gone;
-    {
-      std::lock_guard<std::mutex> lk(mu);
-      for (auto& x : e)
-        if (x.set && std::find(x.set->list.begin(), x.set->list.end(), member) != x.set->list.end()) gone.push_back(std::move(x.set));
-    }
-  }
-};
-PkSetCache& pk_cache() { static auto* c = new PkSetCache(); return *c; }
+KeySetCache<PlonkKeySet, bn254_plonk_pvk>& pk_cache() { static auto* c = new KeySetCache<PlonkKeySet, bn254_plonk_pvk>(); return *c; }
 
 // ---- arguments ---------------------------------------------------------------------------------------------------------------------------------------------------
 int pk_check_list(const bn254_plonk_pvk* const* pvks, size_t n_keys, size_t* max_public) {
@@ -197,6 +160,8 @@ int pk_ensure_set(PlonkKeySet& s) {
   std::vector<PlonkKeyDesc> desc(s.list.size());
   for (size_t k = 0; k < s.list.size(); k++) {
     const bn254_plonk_pvk* p = s.list[k];
+    const size_t pub = (size_t)p->key.nb_public;
+    if (pub * 32 <= 256 && pub > s.staged_public) s.staged_public = pub;
     PlonkDev* d;
     {
       std::lock_guard<std::mutex> lk(p->mu);
@@ -241,65 +206,25 @@ int pk_ensure_ctx(PlonkKeySet& s, const PlonkLease& lease, int w, size_t slots, 
   return BN254_OK;
 }
 
-// ---- one pass: slots [s0, s0 + m) of the call's grouping on context c --------------------------------------------------------------------------------------------
+// ---- one pass: slots [s0, s0 + m) of the call's grouping on context c: gather, the pass (plonk_pass), scatter ----------------------------------------------------
 int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, size_t s0, size_t m, const uint8_t* d_proofs, size_t proof_stride, const uint8_t* d_inputs,
                 size_t input_stride, size_t n, uint8_t* d_status, unsigned flags) {
   HIPCK(hipSetDevice(s.device));
-  const bn254_plonk_pvk* m0 = s.list[0];
-  const int T1 = plonk_stage1_terms(m0->key), T2 = plonk_stage2_terms(m0->key), TT = T2 + 2;
   const uint32_t n_keys = (uint32_t)s.list.size();
   const size_t rec_bytes = pk_rec_bytes(proof_stride), rec_stride = (rec_bytes + 3) & ~(size_t)3, row_stride = 32 * s.max_public;
   if (m > c.cap || m * rec_stride > x.recs.cap() || m * row_stride > x.rows.cap() || (m & 63)) return set_err(BN254_E_HIP, "PlonK key-set context smaller than the pass (internal sizing error)");
-  // the KZG batching scalars of the pass: a fresh ChaCha20 key and nonce (plonk_run_device has the reason)
-  uint32_t lam_key[11];
-  for (size_t got = 0; got < sizeof lam_key;) {
-    ssize_t k = getrandom((uint8_t*)lam_key + got, sizeof lam_key - got, 0);
-    if (k <= 0) return set_err(BN254_E_HIP, "getrandom failed: no KZG batching scalars");
-    got += (size_t)k;
-  }
   const uint32_t* s2p = call.slot_to_proof + s0;
   const uint32_t* gk = call.granule_key + s0 / G16_KEYS_GRANULE;
-  const PlonkKeysRef ref{s.desc, n_keys, gk};
   hipError_t e = bn254_launch_plonk_keys_gather(d_proofs, proof_stride, d_inputs, input_stride, (uint32_t)n, s2p, gk, s.desc, n_keys, (uint32_t)m, x.recs, (uint32_t)rec_stride,
                                                 (uint32_t)rec_bytes, x.rows, (uint32_t)row_stride, c.stream);
   if (e != hipSuccess) return launch_err(e, "PlonK key-set gather");
-  e = bn254_launch_plonk_stage1_keys(s.desc, n_keys, gk, x.recs, rec_stride, proof_stride, row_stride ? (const uint8_t*)x.rows : nullptr, row_stride, s.staged_public, m, lam_key, c.d_work,
-                                     c.terms, c.flags, T1, c.stream);
-  if (e != hipSuccess) return launch_err(e, "PlonK stage 1 over keys");
-  int rc = plonk_msm(nullptr, &ref, c, m0->shape1, m, T1, true, nullptr, nullptr);
+  // all members share the shapes of a pass: member 0 stands for them
+  PlonkPassReport rep;
+  int rc = plonk_pass(s.list[0], PlonkTables{nullptr, s.desc, n_keys, gk, s.one},
+                      PlonkPassIn{x.recs, rec_stride, row_stride ? (const uint8_t*)x.rows : nullptr, 0, proof_stride, row_stride, s.staged_public}, c, m, flags, nullptr, &rep);
   if (rc) return rc;
-  // BN254_FLAG_RLC, honoured from plonk_rlc_min slots per pass: the sequence of plonk_run_device over slots.  A group of 64 slots is a granule, so all its proofs have
-  // one key, and group g of the pass is checked against the tables of granule g; a padding slot is decided by stage 1 and contributes the identity
-  const bool rlc = (flags & BN254_FLAG_RLC) != 0 && m >= plonk_rlc_min();
-  if (rlc) {
-    if (m / 64 * (size_t)(G16_WS_BYTES_PER_PROOF / 4) > c.grp_ws.cap() || m / 64 > c.grp_status.cap()) return set_err(BN254_E_HIP, "PlonK key-set context smaller than the pass's groups (internal sizing error)");
-    e = bn254_launch_plonk_stage2_keys_weighted(s.desc, n_keys, gk, x.recs, rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, lam_key, c.stream);
-  } else
-    e = bn254_launch_plonk_stage2_keys(s.desc, n_keys, gk, x.recs, rec_stride, m, c.d_work, c.words, c.inf, c.terms, c.flags, c.status, TT, T2, c.stream);
-  if (e != hipSuccess) return launch_err(e, "PlonK stage 2 over keys");
-  if ((rc = plonk_msm(nullptr, &ref, c, rlc ? m0->shape2_rlc : m0->shape2, m, TT, false, nullptr, nullptr))) return rc;
-  bool exact = !rlc;
-  if (rlc) {
-    // group sums -> one cooperative pairing check per group with the group's key -> pending proofs of passed groups accepted.  The proofs of a failed group stay
-    // pending, and the exact check below runs on their wavefronts alone: every other wavefront of its kernels exits at once
-    const size_t groups = m / 64;
-    HIPCK(hipMemsetAsync(c.d_fail, 0, sizeof(uint32_t), c.stream));
-    e = bn254_launch_plonk_group_sums(c.ws, c.status, m, c.grp_ws, c.grp_status, VE_LX_ELEM, BN254_ST_LINF, VE_CX_ELEM, BN254_ST_LINF2, c.stream);
-    if (e == hipSuccess) e = bn254_launch_pairing2_fixed_groups_keys(c.grp_ws, c.grp_status, groups, s.desc, n_keys, gk, s.one, BN254_ERR_PAIRING_FAILED, c.stream);
-    if (e == hipSuccess) e = bn254_launch_plonk_group_scatter(c.status, m, c.grp_status, c.d_fail, c.stream);
-    if (e != hipSuccess) return launch_err(e, "PlonK joint pairing check over keys");
-    HIPCK(hipMemcpyAsync(c.h_fail, c.d_fail, sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
-    HIPCK(hipStreamSynchronize(c.stream));
-    const uint32_t failed = *c.h_fail;
-    s.stat[0].fetch_add(1, std::memory_order_relaxed); s.stat[1].fetch_add(groups, std::memory_order_relaxed); s.stat[2].fetch_add(failed, std::memory_order_relaxed);
-    exact = failed != 0;
-  }
-  if (exact) {
-    // the form follows the pass's size (bn254_set_plonk_keys_params): cooperative with the key per item, or the lane form with the key per wavefront
-    e = bn254_launch_pairing2_fixed_keys(c.ws, c.status, m, s.desc, n_keys, gk, s.one, BN254_ERR_PAIRING_FAILED, c.stream);
-    if (e != hipSuccess) return launch_err(e, "PlonK pairing check over keys");
-    if (plonk_keys_coop_form(m)) s.stat[3].fetch_add(1, std::memory_order_relaxed);
-  }
+  if (rep.joint) { s.stat[0].fetch_add(1, std::memory_order_relaxed); s.stat[1].fetch_add(rep.groups, std::memory_order_relaxed); s.stat[2].fetch_add(rep.failed, std::memory_order_relaxed); }
+  if (rep.exact && plonk_keys_coop_form(m)) s.stat[3].fetch_add(1, std::memory_order_relaxed);
   e = bn254_launch_plonk_keys_scatter(c.status, s2p, (uint32_t)m, (uint32_t)n, d_status, c.stream);
   if (e != hipSuccess) return launch_err(e, "PlonK key-set scatter");
   HIPCK(hipStreamSynchronize(c.stream));
@@ -324,27 +249,9 @@ int pk_batch(PlonkKeySet& s, PkCall& call, const uint32_t* d_index, const uint8_
   PlonkLease lease(&s.pool, plan.workers);
   int rc;
   for (int w = 0; w < plan.workers; w++) if ((rc = pk_ensure_ctx(s, lease, w, plan.pass, proof_stride))) return rc;
-  std::vector<int> rcs(plan.workers, BN254_OK); std::vector<std::string> errs(plan.workers);
-  auto body = [&](int w) {
-    const size_t lo = (size_t)w * plan.per, hi = lo + plan.per < slots ? lo + plan.per : slots;
-    for (size_t off = lo; off < hi; off += plan.pass) {
-      const size_t m = hi - off < plan.pass ? hi - off : plan.pass;
-      int r = pk_run_pass(s, lease.ctx(w), s.extra[lease.idx[w]], call, off, m, d_proofs, proof_stride, d_inputs, input_stride, n, d_status, flags);
-      if (r) {   // work of this pass may still be enqueued: drain before the lease hands the context to the next call
-        rcs[w] = r; errs[w] = g_err;
-        (void)hipStreamSynchronize(lease.ctx(w).stream);
-        return;
-      }
-    }
-  };
-  if (plan.workers == 1) body(0);
-  else {
-    std::vector<std::thread> th;
-    for (int w = 0; w < plan.workers; w++) th.emplace_back(body, w);
-    for (auto& t : th) t.join();
-  }
-  for (int w = 0; w < plan.workers; w++) if (rcs[w]) return set_err(rcs[w], errs[w]);
-  return BN254_OK;
+  return plonk_run_workers(lease, plan.workers, plan.per, plan.pass, slots, [&](int w, size_t off, size_t m) {
+    return pk_run_pass(s, lease.ctx(w), s.extra[lease.idx[w]], call, off, m, d_proofs, proof_stride, d_inputs, input_stride, n, d_status, flags);
+  });
 }
 
 std::shared_ptr<PlonkKeySet> pk_get_ready(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device, size_t max_public, int* rc) {
@@ -440,7 +347,7 @@ int bn254_dbg_plonk_keys_knobs(long out[2]) {
 int bn254_plonk_keys_state(const bn254_plonk_pvk* const* pvks, size_t n_keys, int device, uint64_t out[4]) {
   if (!pvks || !out || n_keys == 0) return set_err(BN254_E_BAD_ARG, "bad argument");
   for (size_t k = 0; k < n_keys; k++) if (!pvks[k]) return set_err(BN254_E_BAD_ARG, "bad argument: null key in the list");
-  std::shared_ptr<PlonkKeySet> s = pk_cache().peek(pvks, n_keys, device);
+  std::shared_ptr<PlonkKeySet> s = pk_cache().find(pvks, n_keys, device);
   if (!s) return set_err(BN254_E_BAD_ARG, "no cached state for this key list on this device (no batch or reservation yet, or it was evicted)");
   for (int i = 0; i < 4; i++) out[i] = s->stat[i].load(std::memory_order_relaxed);
   return BN254_OK;

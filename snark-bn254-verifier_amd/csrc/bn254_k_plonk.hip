@@ -240,11 +240,18 @@ hipError_t bn254_plonk_dev_init(int device) {
   if (e == hipSuccess) done[device] = true;
   return e;
 }
+// The ChaCha20 key and nonce of a pass from its 11 words (null: all zero, for a launch that draws nothing).  weights: the stream of the BN254_FLAG_RLC weights --
+// "RLC" in nonce word 2: not the stream the KZG batching scalars come from
+static ChaChaKey pl_chacha_key(const uint32_t* words, bool weights) {
+  ChaChaKey key;
+  for (int i = 0; i < 8; i++) key.k[i] = words ? words[i] : 0u;
+  for (int i = 0; i < 3; i++) key.nonce[i] = words ? words[8 + i] : 0u;
+  if (weights) key.nonce[2] ^= 0x00524c43u;
+  return key;
+}
 hipError_t bn254_launch_plonk_stage1(const void* d_key, const uint8_t* d_proofs, size_t stride, const uint8_t* d_inputs, size_t n_public, size_t n, const uint32_t lam_key[11],
                                      void* d_work, void* d_terms, uint8_t* d_flags, int T1, hipStream_t s) {
-  ChaChaKey key;
-  for (int i = 0; i < 8; i++) key.k[i] = lam_key[i];
-  for (int i = 0; i < 3; i++) key.nonce[i] = lam_key[8 + i];
+  const ChaChaKey key = pl_chacha_key(lam_key, false);
   const uint32_t ls = pl_lane_stride(stride, n_public);
   const size_t lds = 16 + 64 * (size_t)ls + 64 * (size_t)PL_HELPER_SHA_STRIDE;     // + the SHA blocks of the helper wavefront's lanes (bn254_plonk.hpp::pl_lane_lds)
   if (lds > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ae != hipSuccess) return ae; }
@@ -257,9 +264,7 @@ hipError_t bn254_launch_plonk_stage1(const void* d_key, const uint8_t* d_proofs,
 hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t proof_len,
                                           const uint8_t* d_inputs, size_t in_stride, size_t staged_public, size_t n, const uint32_t lam_key[11], void* d_work, void* d_terms,
                                           uint8_t* d_flags, int T1, hipStream_t s) {
-  ChaChaKey key;
-  for (int i = 0; i < 8; i++) key.k[i] = lam_key[i];
-  for (int i = 0; i < 3; i++) key.nonce[i] = lam_key[8 + i];
+  const ChaChaKey key = pl_chacha_key(lam_key, false);
   const uint32_t ls = pl_lane_stride(rec_stride, staged_public);
   const size_t lds = 16 + 64 * (size_t)ls + 64 * (size_t)PL_HELPER_SHA_STRIDE;
   if (lds > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage1_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); if (ae != hipSuccess) return ae; }
@@ -267,38 +272,21 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
                      key, (PlonkWork*)d_work, (MsmTerm*)d_terms, d_flags, T1, ls);
   return hipGetLastError();
 }
-static hipError_t plonk_stage2_keys_launch(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
-                                           void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
-                                           const uint32_t* weight_key /* 11 words or nullptr */, hipStream_t s) {
-  ChaChaKey wkey;
-  for (int i = 0; i < 8; i++) wkey.k[i] = weight_key ? weight_key[i] : 0u;
-  for (int i = 0; i < 3; i++) wkey.nonce[i] = weight_key ? weight_key[8 + i] : 0u;
-  if (weight_key) wkey.nonce[2] ^= 0x00524c43u;      // the weight stream of bn254_launch_plonk_stage2
+// weight_key != nullptr: BN254_FLAG_RLC over a list -- every scalar of a slot's two sums carries the slot's weight (the weight stream of the single-key launch)
+hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
+                                          void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
+                                          const uint32_t* weight_key /* 11 words or nullptr */, hipStream_t s) {
+  const ChaChaKey wkey = pl_chacha_key(weight_key, true);
   const uint32_t ls = pl_lane_stride(rec_stride, 0);
   if (16 + 64 * (size_t)ls > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage2_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 + 64 * (size_t)ls)); if (ae != hipSuccess) return ae; }
   hipLaunchKernelGGL(k_plonk_stage2_keys, dim3((unsigned)((n + 63) / 64)), dim3(64), 16 + 64 * (size_t)ls, s, desc, n_keys, granule_key, d_recs, rec_stride, (uint32_t)n, (PlonkWork*)d_work,
                      d_lin_words, d_lin_inf, (MsmTerm*)d_terms, d_flags, d_status, TT, T2, ls, wkey, weight_key ? 1 : 0);
   return hipGetLastError();
 }
-hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
-                                          void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
-                                          hipStream_t s) {
-  return plonk_stage2_keys_launch(desc, n_keys, granule_key, d_recs, rec_stride, n, d_work, d_lin_words, d_lin_inf, d_terms, d_flags, d_status, TT, T2, nullptr, s);
-}
-// BN254_FLAG_RLC over a list: every scalar of a slot's two sums carries the slot's weight (the pass's ChaCha key, the weight stream of the single-key launch)
-hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
-                                                   void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT,
-                                                   int T2, const uint32_t weight_key[11], hipStream_t s) {
-  if (!weight_key) return hipErrorInvalidValue;
-  return plonk_stage2_keys_launch(desc, n_keys, granule_key, d_recs, rec_stride, n, d_work, d_lin_words, d_lin_inf, d_terms, d_flags, d_status, TT, T2, weight_key, s);
-}
 // weight_key != nullptr: BN254_FLAG_RLC -- every scalar of the proof's two sums carries the proof's weight (the call's key with another nonce word: a stream of its own)
 hipError_t bn254_launch_plonk_stage2(const void* d_key, const uint8_t* d_proofs, size_t stride, size_t n, void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf,
                                      void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2, const uint32_t* weight_key /* 11 words or nullptr */, hipStream_t s) {
-  ChaChaKey wkey;
-  for (int i = 0; i < 8; i++) wkey.k[i] = weight_key ? weight_key[i] : 0u;
-  for (int i = 0; i < 3; i++) wkey.nonce[i] = weight_key ? weight_key[8 + i] : 0u;
-  wkey.nonce[2] ^= 0x00524c43u;      // "RLC": not the stream the KZG batching scalars come from
+  const ChaChaKey wkey = pl_chacha_key(weight_key, true);
   const uint32_t ls = pl_lane_stride(stride, 0);
   if (16 + 64 * (size_t)ls > 65536) { hipError_t ae = hipFuncSetAttribute((const void*)k_plonk_stage2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(16 + 64 * (size_t)ls)); if (ae != hipSuccess) return ae; }
   hipLaunchKernelGGL(k_plonk_stage2, dim3((unsigned)((n + 63) / 64)), dim3(64), 16 + 64 * (size_t)ls, s, (const PlonkKey*)d_key, d_proofs, stride, (uint32_t)n, (PlonkWork*)d_work, d_lin_words,
@@ -355,7 +343,7 @@ hipError_t bn254_plonk_self_test(const void* key_host, const void* d_key, std::s
     }
   }
   {
-    ChaChaKey ck; for (int i = 0; i < 8; i++) ck.k[i] = lam_key[i]; for (int i = 0; i < 3; i++) ck.nonce[i] = lam_key[8 + i];
+    const ChaChaKey ck = pl_chacha_key(lam_key, false);
     uint32_t lw[12]; for (int j = 0; j < 3; j++) chacha20_block4(lw + 4 * j, ck, (uint32_t)j);
     uint8_t lb[48]; for (int j = 0; j < 12; j++) { lb[4 * j] = (uint8_t)lw[j]; lb[4 * j + 1] = (uint8_t)(lw[j] >> 8); lb[4 * j + 2] = (uint8_t)(lw[j] >> 16); lb[4 * j + 3] = (uint8_t)(lw[j] >> 24); }
     hw.lambda = F.from_be_reduce(lb, 48);

@@ -54,13 +54,29 @@ hipError_t bn254_launch_gather_rows(uint8_t* dst, const uint8_t* src, size_t src
   return hipSuccess;
 }
 hipError_t bn254_launch_scatter_status(uint8_t* status, const uint8_t* fb, const uint32_t* idx, uint32_t m, hipStream_t) { for (uint32_t k = 0; k < m; k++) status[idx[k]] = fb[k]; return hipSuccess; }
+// Every PlonK pass draws its own KZG batching key: the stand-ins for stage 1 (here and in hostsan_plonk_keys*.cpp) record the 44 bytes they are handed -- under a lock,
+// passes run on several host threads -- and main checks that no two passes of the run saw the same
+static std::mutex g_lam_mu;
+static std::vector<std::array<uint32_t, 11>> g_lam_seen;
+static void lam_record(const uint32_t* lam_key) {
+  std::array<uint32_t, 11> k;
+  memcpy(k.data(), lam_key, sizeof k);
+  std::lock_guard<std::mutex> lk(g_lam_mu);
+  g_lam_seen.push_back(k);
+}
+static bool lam_all_fresh() {
+  std::lock_guard<std::mutex> lk(g_lam_mu);
+  std::sort(g_lam_seen.begin(), g_lam_seen.end());
+  return !g_lam_seen.empty() && std::adjacent_find(g_lam_seen.begin(), g_lam_seen.end()) == g_lam_seen.end();
+}
 size_t bn254_plonk_work_bytes() { return sizeof(PlonkWork); }
 size_t bn254_plonk_key_bytes() { return sizeof(PlonkKey); }
 hipError_t bn254_plonk_dev_init(int) { return hipSuccess; }
 hipError_t bn254_plonk_self_test(const void*, const void*, std::string* why) { why->clear(); return hipSuccess; }
-hipError_t bn254_launch_plonk_stage1(const void*, const uint8_t* d_proofs, size_t stride, const uint8_t* d_inputs, size_t n_public, size_t n, const uint32_t*, void* d_work, void* d_terms, uint8_t* d_flags,
+hipError_t bn254_launch_plonk_stage1(const void*, const uint8_t* d_proofs, size_t stride, const uint8_t* d_inputs, size_t n_public, size_t n, const uint32_t* lam_key, void* d_work, void* d_terms, uint8_t* d_flags,
                                      int T1, hipStream_t) {
   g_launches++;
+  lam_record(lam_key);
   for (size_t i = 0; i < n; i++) { (void)d_proofs[i * stride + stride - 1]; if (n_public) (void)d_inputs[(i * n_public + n_public - 1) * 32 + 31]; }
   memset(d_work, 0, n * sizeof(PlonkWork)); memset(d_terms, 0, n * (size_t)T1 * sizeof(MsmTerm)); memset(d_flags, 0, n * (size_t)T1);
   return hipSuccess;
@@ -461,6 +477,7 @@ int main(int argc, char** argv) {
   const long fuzz_iters = argc > 2 ? atol(argv[2]) : 300;
   if (argc > 3 && std::string(argv[3]) == "threads") {        // the -fsanitize=thread build runs these alone (the rest is single-threaded code the ASan build covers)
     threaded_scenarios(golden, false);
+    CHECK(lam_all_fresh());
     printf("hostsan ok\n");
     return 0;
   }
@@ -622,6 +639,7 @@ int main(int argc, char** argv) {
     }
   }
   threaded_scenarios(golden, true);
+  CHECK(lam_all_fresh());
   printf("hostsan: %ld stand-in launches, %zu allocations still live (key caches of the single-proof entries)\n", g_launches.load(), g_fake_live_allocs.load());
   printf("hostsan ok\n");
   return 0;

@@ -48,7 +48,7 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
                                           const uint8_t* d_inputs, size_t in_stride, size_t staged_public, size_t n, const uint32_t* lam_key, void* d_work, void* d_terms, uint8_t* d_flags,
                                           int T1, hipStream_t) {
   g_launches++;
-  (void)lam_key[10];
+  lam_record(lam_key);
   CHECK(n % 64 == 0 && proof_len >= 808 && staged_public <= 8);
   unsigned sum = 0;
   for (size_t i = 0; i < n; i++) {
@@ -61,8 +61,10 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
   return hipSuccess;
 }
 hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n, void*,
-                                          const uint32_t* words, const uint8_t* inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int, hipStream_t) {
+                                          const uint32_t* words, const uint8_t* inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int, const uint32_t* weight_key,
+                                          hipStream_t) {
   g_launches++;
+  CHECK(!weight_key);      // this harness stays below the threshold of BN254_FLAG_RLC
   (void)words[n * 16 - 1]; (void)inf[n - 1];
   memset(d_terms, 0, n * (size_t)TT * sizeof(MsmTerm)); memset(d_flags, 0, n * (size_t)TT);
   for (size_t i = 0; i < n; i++) {
@@ -211,6 +213,7 @@ int main(int argc, char** argv) {
     for (auto& x : th) x.join();
   }
   for (auto k : keys) bn254_plonk_vk_free(k);
+  CHECK(lam_all_fresh());
   printf("hostsan_plonk_keys: %ld stand-in launches, %zu allocations still live\nhostsan_plonk_keys ok\n", g_launches.load(), g_fake_live_allocs.load());
   return 0;
 }

@@ -1,7 +1,7 @@
 // BN254_FLAG_RLC over PlonK key lists (csrc/bn254_capi_plonk_keys.hip::pk_run_pass) under the sanitizers: the host half of the library as ONE translation unit
-// with the stand-in HIP runtime of hostsan_main.cpp (whose main is set aside), the stand-ins of hostsan_plonk_keys.cpp for the launchers of a pass, and stand-ins for
-// the two launchers the flag adds: the weighted stage 2 and the joint check of a pass's groups, which read the descriptor's line tables of EVERY group's key, the
-// target and the whole group workspace, and write every group's status byte.  The group stage of hostsan_main.cpp makes group g of a pass fail when g % 16 == 3, so a
+// with the stand-in HIP runtime of hostsan_main.cpp (whose main is set aside), the stand-ins of hostsan_plonk_keys.cpp for the launchers of a pass -- stage 2 counts
+// the launches that come with a weight key -- and a stand-in for the launcher the flag adds: the joint check of a pass's groups, which reads the descriptor's line
+// tables of EVERY group's key, the target and the whole group workspace, and writes every group's status byte.  The group stage of hostsan_main.cpp makes group g of a pass fail when g % 16 == 3, so a
 // pass of 16 granules and more runs the exact check behind the joint one and a smaller pass does not.  The threshold is set to 64 slots here; the older harness
 // stays below the default and never reaches these launchers.
 //   hostsan_plonk_keys_rlc <iterations> [threads]     (threads: only the concurrent scenario, for the -fsanitize=thread build)
@@ -16,6 +16,7 @@ static inline hipError_t hipMemGetInfo(size_t* free_b, size_t* total_b) { *free_
 #include "../../snark-bn254-verifier_amd/csrc/bn254_capi_plonk_keys.hip"
 #include <thread>
 
+static std::atomic<long> g_weighted{0}, g_group_checks{0}, g_exact{0};
 hipError_t bn254_launch_keys_group(const uint32_t* key_index, uint32_t n, uint32_t n_keys, uint32_t slot_cap, uint32_t* count, uint32_t* base, uint32_t* cursor, uint32_t* n_slots,
                                    uint32_t* slot_to_proof, uint32_t* granule_key, uint8_t* status, hipStream_t) {
   g_launches++;
@@ -50,7 +51,7 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
                                           const uint8_t* d_inputs, size_t in_stride, size_t staged_public, size_t n, const uint32_t* lam_key, void* d_work, void* d_terms, uint8_t* d_flags,
                                           int T1, hipStream_t) {
   g_launches++;
-  (void)lam_key[10];
+  lam_record(lam_key);
   CHECK(n % 64 == 0 && proof_len >= 808 && staged_public <= 8);
   unsigned sum = 0;
   for (size_t i = 0; i < n; i++) {
@@ -63,8 +64,10 @@ hipError_t bn254_launch_plonk_stage1_keys(const bn254::PlonkKeyDesc* desc, uint3
   return hipSuccess;
 }
 hipError_t bn254_launch_plonk_stage2_keys(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n, void*,
-                                          const uint32_t* words, const uint8_t* inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int, hipStream_t) {
+                                          const uint32_t* words, const uint8_t* inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int, const uint32_t* weight_key,
+                                          hipStream_t) {
   g_launches++;
+  if (weight_key) { g_weighted++; (void)weight_key[10]; }
   (void)words[n * 16 - 1]; (void)inf[n - 1];
   memset(d_terms, 0, n * (size_t)TT * sizeof(MsmTerm)); memset(d_flags, 0, n * (size_t)TT);
   for (size_t i = 0; i < n; i++) {
@@ -102,14 +105,6 @@ hipError_t bn254_launch_plonk_keys_scatter(const uint8_t* slot_status, const uin
   return hipSuccess;
 }
 
-static std::atomic<long> g_weighted{0}, g_group_checks{0}, g_exact{0};
-hipError_t bn254_launch_plonk_stage2_keys_weighted(const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key, const uint8_t* d_recs, size_t rec_stride, size_t n,
-                                                   void* d_work, const uint32_t* words, const uint8_t* inf, void* d_terms, uint8_t* d_flags, uint8_t* d_status, int TT, int T2,
-                                                   const uint32_t* weight_key, hipStream_t s) {
-  g_weighted++;
-  (void)weight_key[10];
-  return bn254_launch_plonk_stage2_keys(desc, n_keys, granule_key, d_recs, rec_stride, n, d_work, words, inf, d_terms, d_flags, d_status, TT, T2, s);
-}
 hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t* grp_ws, uint8_t* grp_status, size_t groups, const bn254::PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key,
                                                    const int32_t* one, int reject_code, hipStream_t) {
   g_launches++; g_group_checks++;
@@ -246,6 +241,7 @@ int main(int argc, char** argv) {
     CHECK(state_of(keys, 0).v[0] >= (uint64_t)iters);
   }
   for (auto k : keys) bn254_plonk_vk_free(k);
+  CHECK(lam_all_fresh());
   printf("hostsan_plonk_keys_rlc: %ld stand-in launches, %ld joint checks, %zu allocations still live\nhostsan_plonk_keys_rlc ok\n", g_launches.load(), g_group_checks.load(), g_fake_live_allocs.load());
   return 0;
 }
