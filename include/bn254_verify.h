@@ -410,8 +410,8 @@ int bn254_sp1_plonk_verify_batch_device(const bn254_plonk_pvk* pvk, const void* 
 
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * A sub-batch above COOP12_MAX_PROOFS runs as about 110 kernel launches: k_g16_prepare, the whole Miller loop as ONE k_miller_run (or a few, g16_launch_form; the
- * first sets f and T, the last tests B's subgroup) and one launch per Fp12-level operation of the final exponentiation (k_f12_mul x 60, the last of them with the
- * comparison as its tail, k_f12_cyclo_sqr_n x 39, ...); up to COOP12_MAX_PROOFS as two (k_g16_prepare, the cooperative kernel).  When profiling is enabled, verify_batch_device records HIP
+ * first sets f and T, the last tests B's subgroup) and one launch per Fp12-level operation of the final exponentiation (k_f12_mul x 54, the last of them with the
+ * comparison as its tail, k_f12_cyclo_sqr_n x 36, ...); up to COOP12_MAX_PROOFS as two (k_g16_prepare, the cooperative kernel).  When profiling is enabled, verify_batch_device records HIP
  * events on the launch stream (a) at the four phase boundaries (prepare | subgroup | Miller loop | final exponentiation) and
  * (b) around every launch whose kernel kind is selected by bn254_set_profile_kernels (bit i = kind i, default all).
  * After the stream has been synchronised bn254_groth16_last_kernel_ms returns the phase durations and

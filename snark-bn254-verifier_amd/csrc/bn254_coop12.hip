@@ -26,7 +26,7 @@ namespace bn254 {
 
 static_assert(COOP_T_ELEM == VE_S2, "COOP_T_ELEM must name a workspace slot that neither VE_T nor the result slot VE_S0 overlays");
 #define C12_STRIDE 12
-#define C12_SLOT(e) (((e) - VE_F) / 12)   // VE_F 0, VE_S0 1, S1 2, S2 3, S3 4, S4 5, P3 6, (7: scratch), P5 8, P7 9
+#define C12_SLOT(e) (((e) - VE_F) / 12)   // VE_F 0, VE_S0 1, S1 2, S2 3, S3 4, S4 5, UT0 6, (7: scratch), UT1 8, UT2 9
 #define C12_X 10     // xi-multiples of an operand
 #define C12_I 11     // i-multiples of an operand
 #define C12_B 7      // conj(b) of a general product

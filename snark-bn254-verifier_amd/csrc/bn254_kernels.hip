@@ -75,7 +75,7 @@ __global__ void __launch_bounds__(256, 2) k_f12_mul(int32_t* ws, uint32_t n, con
   w.lds = park_lds;
   vm_f12_mul(w, d, a, b, conj_b != 0);
 }
-// the last product of the final exponentiation with k_g16_compare's work as its tail (bn254_vm.h::vm_f12_mul_eq_const): the other 59 products of a batch stay k_f12_mul
+// the last product of the final exponentiation with k_g16_compare's work as its tail (bn254_vm.h::vm_f12_mul_eq_const): the other 53 products of a batch stay k_f12_mul
 // slot_proof != nullptr (a launch that compacts): status holds the SLOTS' bytes, and every slot that holds a proof hands its final byte to out_status[slot_proof[slot]],
 // the caller's buffer in proof order -- the verdict, or what the tail of k_miller_run made of the slot (B outside G2, a deferred error of C, the input count; never 0,
 // which is what the slots past the list hold) -- also in a wavefront none of whose proofs is still pending (as k_f12_mul_verdict_keys does for a batch over many keys)

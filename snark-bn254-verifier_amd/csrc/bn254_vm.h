@@ -21,9 +21,9 @@ enum {
   VE_F = 10,                 // Miller accumulator, then m = easy part of the final exponentiation
   VE_T = 22,                 // Miller loop: running G2 point (X, Y, Z)
   VE_S0 = 22, VE_S1 = 34, VE_S2 = 46, VE_S3 = 58, VE_S4 = 70,  // final exponentiation slots (S0 aliases T)
-  VE_P3 = 82,                   // x^3 of the windowed exp-by-u
+  VE_UT0 = 82,                  // table entry 0 of the exp-by-u chain (BN_U_CHAIN_TABLE: x^5)
   VE_TMPA = 94, VE_TMPB = 100,  // two Fp6 temporaries of the general Fp12 product
-  VE_P5 = 106, VE_P7 = 118,     // x^5, x^7
+  VE_UT1 = 106, VE_UT2 = 118,   // table entries 1 and 2 (x^9, x^19)
   VE_COUNT = 130,
   // Flag on a SOURCE element index of vm_f12_mul (operand a), vm_f12_cyclo_sqr and vm_f12_cyclo_sqr_n: the operation reads conj(x) = x^(p^6), i.e. negates
   // the odd coefficients k1, k3, k5 as it loads them, so a conjugation that feeds a product or a squaring is no pass over the workspace of its own.  It
@@ -579,29 +579,30 @@ BN_HD void vm_miller_program_runs(OPS& ops, int per_run) {
   for (int s = 0; s < BN_ATE_STEPS; s += per_run)
     ops.miller_run(s, s + per_run < BN_ATE_STEPS ? s + per_run : BN_ATE_STEPS, VE_T, VE_B, VE_F, VE_AX, VE_LX, VE_CX);
 }
-// x^u on the cyclotomic subgroup: dst <- src^u (dst != src), width-4 signed windows of u (BN_U_W4: digits +-1, +-3, +-5, +-7).
-// x^3, x^5, x^7 go to VE_P3/P5/P7; a negative digit multiplies by the conjugate (= inverse) of the table entry.
-// 63 cyclotomic squarings + 16 products (NAF(u): 62 + 23 and two conjugations).
+// x^u on the cyclotomic subgroup: dst <- src^u (dst != src) by the addition-subtraction chain BN_U_CHAIN_* (bn254_constants.h; found by
+// tools/search_u_chain.py): the table x^5, x^9, x^19 goes to VE_UT0/1/2, with e_dst -- free until the accumulator starts -- as the one temporary
+// (x^4, x^10); then the digits +-19, +-9, +-5, +-1, a negative one multiplying by the conjugate (= inverse) of its table entry.
+// 61 cyclotomic squarings + 14 products (the width-4 signed windows it replaces: 63 + 16; NAF(u): 62 + 23).  Nothing but e_dst and the three
+// table slots is written.
+BN_HD int vm_exp_u_operand(int k, int e_dst, int e_src) { return k == 0 ? e_src : k == 1 ? e_dst : k == 2 ? VE_UT0 : k == 3 ? VE_UT1 : VE_UT2; }
 template <class OPS>
 BN_HD void vm_exp_u(OPS& ops, int e_dst, int e_src) {
-  ops.f12_cyclo_sqr(e_dst, e_src);                 // x^2
-  ops.f12_mul(VE_P3, e_dst, e_src, false);
-  ops.f12_mul(VE_P5, VE_P3, e_dst, false);
-  ops.f12_mul(VE_P7, VE_P5, e_dst, false);
-  // leading digit of BN_U_W4 is +1; x^2 in e_dst is no longer needed once the table is built
-  int run = 0, first = 1;
-  for (int i = 1; i < BN_U_W4_LEN; i++) {
-    run++;
-    int d = BN_U_W4[i];
-    if (d != 0) {
-      // the first run squares src straight into dst (leading digit +1: the accumulator starts as x)
-      ops.f12_cyclo_sqr_n(e_dst, first ? e_src : e_dst, run);
-      run = 0; first = 0;
-      int a = d < 0 ? -d : d;
-      ops.f12_mul(e_dst, e_dst, a == 1 ? e_src : a == 3 ? VE_P3 : a == 5 ? VE_P5 : VE_P7, d < 0);
-    }
+  static_assert(BN_U_CHAIN_TABLE_LEN <= 3, "vm_exp_u has three table slots");
+  for (int i = 0; i < BN_U_CHAIN_BUILD_LEN; i++) {
+    const int op = BN_U_CHAIN_BUILD[i][0], d = vm_exp_u_operand(BN_U_CHAIN_BUILD[i][1], e_dst, e_src), a = vm_exp_u_operand(BN_U_CHAIN_BUILD[i][2], e_dst, e_src);
+    const int b = BN_U_CHAIN_BUILD[i][3];
+    if (op == 1) ops.f12_mul(d, a, vm_exp_u_operand(b, e_dst, e_src), false);
+    else if (b == 1) ops.f12_cyclo_sqr(d, a);
+    else ops.f12_cyclo_sqr_n(d, a, b);
   }
-  // BN_U_W4 ends in a non-zero digit (u is odd): no trailing run
+  // the accumulator starts as the operand of the leading digit (positive): the first run squares from that slot straight into dst
+  int acc = vm_exp_u_operand(BN_U_CHAIN_DIGIT[0] - 1, e_dst, e_src);
+  for (int i = 0; i < BN_U_CHAIN_LEN; i++) {
+    const int dg = BN_U_CHAIN_DIGIT[i];
+    if (i != 0) ops.f12_mul(e_dst, e_dst, vm_exp_u_operand((dg < 0 ? -dg : dg) - 1, e_dst, e_src), dg < 0);
+    // the chain ends in a digit (u is odd): no trailing run
+    if (BN_U_CHAIN_RUN[i] != 0) { ops.f12_cyclo_sqr_n(e_dst, acc, BN_U_CHAIN_RUN[i]); acc = e_dst; }
+  }
 }
 // final exponentiation of VE_F; the result ends in VE_S0 (same exponent as bn254_pairing.h::final_exponentiation).  No conjugation is an operation of
 // its own: each rides on the load of the product or squaring that consumes it (VE_CONJ on operand a, conj_b on operand b), at both loads where a

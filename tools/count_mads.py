@@ -112,7 +112,6 @@ TRIPS_BY_KERNEL = {                   # loops whose trip count is a launch param
     ("k_rlc_scale", "scalar_mul"): (64, "64 joint bit positions of the GLV weight k1 + k2 lambda"),
     ("k_g1_scalar_mul", "scalar_mul"): (128, "128 joint bit positions of the GLV halves of a 254-bit scalar"),
     ("k_rlc_scale", "fr_products"): (N_PUBLIC, "one Fr product pair per public input"),
-    ("k_f12_cyclo_sqr_n", "cyclo_sqr"): (186 / 39.0, "3 x 62 squarings of exp-by-u in 39 launches (BN_U_W4)"),
 }
 
 
@@ -326,20 +325,33 @@ INT64 = re.compile(r"^\s*(v_mad_[iu]64_[iu]32|v_lshl_add_u64|v_ashrrev_i64)\b") 
 CLASSES = {"mads": MAD, "int64": INT64, "valu": VALU}
 
 
-def u_w4_digits():
+def u_chain():
+    """The chain vm_exp_u runs, read from the generated header (BN_U_CHAIN_*): -> products, single squarings (k_f12_cyclo_sqr), runs (k_f12_cyclo_sqr_n)
+    and the squarings in those runs, per exponentiation."""
     src = open(os.path.join(ROOT, "snark-bn254-verifier_amd", "csrc", "bn254_constants.h")).read()
-    m = re.search(r"BN_U_W4\[\d+\]\s*=\s*\{([^}]*)\}", src)
-    return [int(x) for x in m.group(1).split(",")]
+    build = re.search(r"BN_U_CHAIN_BUILD\[\d+\]\[4\]\s*=\s*\{(.*?)\};", src).group(1)
+    build = [tuple(int(x) for x in st.split(",")) for st in re.findall(r"\{([^{}]*)\}", build)]
+    runs = [int(x) for x in re.search(r"BN_U_CHAIN_RUN\[\d+\]\s*=\s*\{([^}]*)\}", src).group(1).split(",")]
+    sq = [st[3] for st in build if st[0] == 0]
+    main = [r for r in runs if r]
+    return {"mul": sum(1 for st in build if st[0] == 1) + len(runs) - 1, "sqr": sum(1 for b in sq if b == 1),
+            "runs": sum(1 for b in sq if b > 1) + len(main), "run_squarings": sum(b for b in sq if b > 1) + sum(main)}
 
 
 def final_exp_ops():
-    """Operation counts of vm_final_exp_program (bn254_vm.h): three vm_exp_u (one squaring + 3 table products + per non-zero digit after the
+    """Operation counts of vm_final_exp_program (bn254_vm.h): three vm_exp_u (the chain of bn254_constants.h: table steps, then per digit after the
     first a run of squarings and a product) and the fixed part."""
-    d = u_w4_digits()
-    nz = sum(1 for x in d[1:] if x != 0)
+    c = u_chain()
     # conjugations: none as an operation of the lane kernels (VE_CONJ rides on the consumer's load); the cooperative kernels conjugate the RESULT of each of the six
     # consumers (Coop12Ops, bn254_coop12.hip)
-    return {"inv": 1, "conj": 6, "frob": 4, "mul": 12 + 3 * (3 + nz), "cyclo_calls": 3 + 3 * (1 + nz), "cyclo_squarings": 3 + 3 * (1 + (len(d) - 1))}
+    return {"inv": 1, "conj": 6, "frob": 4, "mul": 12 + 3 * c["mul"], "cyclo_calls": 3 + 3 * (c["sqr"] + c["runs"]), "cyclo_squarings": 3 + 3 * (c["sqr"] + c["run_squarings"]),
+            "cyclo_sqr_n_launches": 3 * c["runs"], "cyclo_sqr_n_squarings": 3 * c["run_squarings"]}
+
+
+_FE = final_exp_ops()
+TRIPS_BY_KERNEL[("k_f12_cyclo_sqr_n", "cyclo_sqr")] = (
+    _FE["cyclo_sqr_n_squarings"] / float(_FE["cyclo_sqr_n_launches"]),
+    "3 x %d squarings of exp-by-u in %d launches (BN_U_CHAIN)" % (_FE["cyclo_sqr_n_squarings"] // 3, _FE["cyclo_sqr_n_launches"]))
 
 
 def wcount(ins, ranges, rx):
@@ -506,7 +518,9 @@ def model_coop12(funcs):
             m = pmc[name]
             e["pmc_check"] = {"SQ_INSTS_VALU_INT64_per_wavefront": m["SQ_INSTS_VALU_INT64"], "model_int64": round(tot["int64"], 1),
                               "SQ_INSTS_VALU_per_wavefront": m["SQ_INSTS_VALU"], "model_valu": round(tot["valu"], 1),
-                              "int64_error": tot["int64"] / m["SQ_INSTS_VALU_INT64"] - 1.0, "valu_error": tot["valu"] / m["SQ_INSTS_VALU"] - 1.0}
+                              "int64_error": tot["int64"] / m["SQ_INSTS_VALU_INT64"] - 1.0, "valu_error": tot["valu"] / m["SQ_INSTS_VALU"] - 1.0,
+                              "note": "the counters were recorded while exp-by-u ran width-4 signed windows (60 products, 192 squarings per final exponentiation): "
+                                      "the model of the chain that replaced them reads below them by what the chain saves"}
         out[name] = e
     return out
 
@@ -595,7 +609,7 @@ def main():
             e["model"] = base + " with the tables read from the descriptor of the wavefront's key (PlonK batches over many keys): " + e["model"]
     if "k_f12_cyclo_sqr_n" in kernels:
         e = kernels["k_f12_cyclo_sqr_n"]
-        e["mads_per_proof_batch"] = e["mads_per_proof_launch"] * 39     # all 39 launches of a batch together (exact: 186 squarings)
+        e["mads_per_proof_batch"] = e["mads_per_proof_launch"] * _FE["cyclo_sqr_n_launches"]     # all launches of a batch together (exact: the squarings of the three chains' runs)
     # keys with many public inputs: one lane per (proof, 16-input chunk); the per-proof figure is for BASELINE configs[4] (1024 inputs: 64 lanes)
     for name in ("k_g16_msm_partial", "k_g16_msm_partial_comb"):
         if name in kernels:
