@@ -517,9 +517,9 @@ int bn254_dbg_coop12_op(int op, const void* a, const void* b, void* out, size_t 
  * 2: c12_eq_const of the cooperative kernels (a == target).  (k_f12_mul_verdict_keys takes its target from a key set's descriptors: it has no probe.) */
 int bn254_dbg_verdict(int form, const void* a, const void* b, const uint8_t target[384], uint8_t* out_status, size_t n, int in_format, int device);
 /* The cooperative kernels in their store modes, with the line tables of a prepared key (gamma side: table 0, delta side: table 1; bn254_groth16_vk_prepare says
- * which signs they hold).  _fixed: k_coop12_miller_fixed with fuse_final_exp and no target on n_pairs (1 or 2) table-driven pairs: g1_0 / g1_1 n x 64 bytes
+ * which signs they hold).  _fixed: k_coop12_miller_fixed without a target (its store mode) on n_pairs (1 or 2) table-driven pairs: g1_0 / g1_1 n x 64 bytes
  * (g1_1 unused for one pair), identity: null or n bytes, bit t = the G1 point of pair t is the identity (its bytes are then ignored); out_gt n x 384 bytes.
- * _g16: k_g16_prepare and k_coop12_miller_g16 (fuse_final_exp, no target) on n raw 256-byte proofs with their inputs (keys with at most 16 inputs);
+ * _g16: k_g16_prepare and k_coop12_miller_g16 (store mode: no target) on n raw 256-byte proofs with their inputs (keys with at most 16 inputs);
  * out_status[i]: BN254_ACCEPT where the proof reached the pairing and out_gt holds its value, else the loader's status (out_gt is then unspecified). */
 int bn254_dbg_coop12_miller_fixed(const bn254_g16_pvk* pvk, int n_pairs, const uint8_t* g1_0, const uint8_t* g1_1, const uint8_t* identity, uint8_t* out_gt, size_t n, int device);
 int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_public, size_t n, uint8_t* out_gt, uint8_t* out_status,

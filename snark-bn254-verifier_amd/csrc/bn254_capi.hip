@@ -377,8 +377,8 @@ hipError_t bn254_launch_dbg_store(int32_t*, size_t, int, void*, int, hipStream_t
 hipError_t bn254_launch_dbg_verdict(int, int32_t*, size_t, uint8_t*, const int32_t*, hipStream_t) { return hipSuccess; }
 hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs&, hipStream_t) { return hipSuccess; }
 hipError_t bn254_coop12_dbg_op(int32_t*, uint8_t*, size_t, int, int, const int32_t*, hipStream_t) { return hipSuccess; }
-hipError_t bn254_coop12_miller_fixed_keys(int32_t*, uint8_t*, size_t, const uint32_t*, uint32_t, const bn254::PlonkKeyDesc*, uint32_t, int, int, int, int, int, const int32_t*, int, hipStream_t) { return hipSuccess; }
-hipError_t bn254_coop12_miller_fixed(int32_t*, uint8_t*, size_t, int, const int32_t*, const int32_t*, const int32_t*, int, int, int, int, int, int, int, const int32_t*, int, hipStream_t) { return hipSuccess; }
+hipError_t bn254_coop12_miller_fixed_keys(int32_t*, uint8_t*, size_t, const uint32_t*, uint32_t, const bn254::PlonkKeyDesc*, uint32_t, const int32_t*, int, hipStream_t) { return hipSuccess; }
+hipError_t bn254_coop12_miller_fixed(int32_t*, uint8_t*, size_t, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) { return hipSuccess; }
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
 // the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {

@@ -420,7 +420,7 @@ int bn254_dbg_coop12_miller_fixed(const bn254_g16_pvk* pvk, int n_pairs, const u
     if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
     HIPCK(hipMemcpy(g_probe_kinds, st.data(), n, hipMemcpyHostToDevice));      // after the loads (same stream): they set PENDING alone
     // the arguments of bn254_launch_pairing2_fixed's cooperative call, without the target
-    e = bn254_coop12_miller_fixed(g_probe_ws, g_probe_kinds, n, n_pairs, d->gtab, d->dtab, d->gtab, VE_LX, VE_CX, VE_LX, BN254_ST_LINF, BN254_ST_LINF2, 0, 1, nullptr, 0, nullptr);
+    e = bn254_coop12_miller_fixed(g_probe_ws, g_probe_kinds, n, n_pairs, d->gtab, d->dtab, nullptr, 0, nullptr);
     if (e == hipSuccess) e = bn254_launch_dbg_store(g_probe_ws, n, (int)VE_S0, out, 0, nullptr);
     if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
     HIPCK(hipDeviceSynchronize());

@@ -378,7 +378,7 @@ int bn254_dbg_coop12_miller_fixed_keys(const bn254_plonk_pvk* const* pvks, size_
   if (e != hipSuccess) return launch_err(e, "probe");
   HIPCK(hipMemcpy(st_d, st.data(), n, hipMemcpyHostToDevice));      // after the loads (same stream): they set PENDING alone
   // the arguments of the product's cooperative calls, without the target
-  e = bn254_coop12_miller_fixed_keys(ws, st_d, n, kw, key_shift, s->desc, (uint32_t)n_keys, VE_LX_ELEM, VE_CX_ELEM, BN254_ST_LINF, BN254_ST_LINF2, 1, nullptr, 0, nullptr);
+  e = bn254_coop12_miller_fixed_keys(ws, st_d, n, kw, key_shift, s->desc, (uint32_t)n_keys, nullptr, 0, nullptr);
   if (e == hipSuccess) e = bn254_launch_dbg_store(ws, n, (int)VE_S0, out, 0, nullptr);
   if (e != hipSuccess) return launch_err(e, "probe");
   HIPCK(hipDeviceSynchronize());

@@ -24,7 +24,6 @@
 
 namespace bn254 {
 
-static_assert(COOP_T_ELEM == VE_S2, "COOP_T_ELEM must name a workspace slot that neither VE_T nor the result slot VE_S0 overlays");
 #define C12_STRIDE 12
 #define C12_SLOT(e) (((e) - VE_F) / 12)   // VE_F 0, VE_S0 1, S1 2, S2 3, S3 4, S4 5, UT0 6, (7: scratch), UT1 8, UT2 9
 #define C12_X 10     // xi-multiples of an operand
@@ -241,7 +240,9 @@ __device__ __forceinline__ bool c12_eq_const(const Coop12& co, int slot, const i
   return ((m >> (pl * 12u)) & 0xfffull) == 0xfffull;
 }
 
-#define C12_PROLOGUE()                                                                                        \
+// A kernel's first lines, in two parts: where the lane sits (group pl of the wavefront, coefficient c, half h, proof p; pc: p clamped into the batch), and --
+// given the proof's status byte -- whether it is still pending, the return of a wavefront with nothing pending, and the LDS image
+#define C12_LANES()                                                                                           \
   extern __shared__ __attribute__((aligned(16))) int32_t c12_lds[];                                           \
   const uint32_t lane = threadIdx.x & 63;                                                                     \
   const bool act = lane < 12 * C12_PER_WAVE;                                                                  \
@@ -249,11 +250,15 @@ __device__ __forceinline__ bool c12_eq_const(const Coop12& co, int slot, const i
   const uint32_t pl = la / 12, c = (la - pl * 12) >> 1, h = la & 1;                                           \
   const uint32_t p = blockIdx.x * (uint32_t)C12_PER_WAVE + pl;                                                \
   const bool live = act && p < n;                                                                             \
-  const uint32_t pc = p < n ? p : n - 1;                                                                      \
-  const uint8_t st = status[pc];                                                                              \
-  const bool pending = live && (st & BN254_ST_PENDING) != 0;                                                  \
+  const uint32_t pc = p < n ? p : n - 1
+#define C12_PENDING(st)                                                                                       \
+  const bool pending = live && ((st) & BN254_ST_PENDING) != 0;                                                \
   if (__builtin_amdgcn_ballot_w64(pending) == 0) return;                                                      \
   Coop12 co{(c12_lds_i32*)c12_lds, lane, pl * 12, c, h}
+#define C12_PROLOGUE()                                                                                        \
+  C12_LANES();                                                                                                \
+  const uint8_t st = status[pc];                                                                              \
+  C12_PENDING(st)
 
 // ---- final exponentiation of VE_F (workspace) -> VE_S0 (workspace), the whole program in one launch ---------------------------------------------------------
 __global__ void __launch_bounds__(64) k_coop12_final_exp(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status) {
@@ -301,38 +306,104 @@ __global__ void __launch_bounds__(64) k_coop12_dbg_op(int32_t* ws, uint32_t n, u
   c12_store_f12(co, ws, n, p, res, VE_S0, pending);
 }
 
-// ---- Miller loop of the table-driven pairs only (PlonK's two-pair check): f = prod_t Miller(P_t, Q_t), then (optionally) the final exponentiation -------------
-__global__ void __launch_bounds__(64)
-k_coop12_miller_fixed(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, int n_pairs,
-                      const int32_t* __restrict__ tab0, const int32_t* __restrict__ tab1, const int32_t* __restrict__ tab2,
-                      int e_p0, int e_p1, int e_p2, int inf0, int inf1, int inf2, int fuse_final_exp, const int32_t* __restrict__ target, int reject_code) {
-  C12_PROLOGUE();
+// ---- Miller loop of the table-driven pairs only (PlonK's two-pair check): f = prod_t Miller(P_t, Q_t), then the final exponentiation ----------------------------
+// One loop and one finish serve two kernels, which differ in where the line tables come from:
+//   k_coop12_miller_fixed        the key of the launch: tab0 / tab1 are launch arguments, n_pairs is 1 or 2
+//   k_coop12_miller_fixed_keys   the key TAKEN PER ITEM (a pass of a batch over many keys, and the groups of its BN254_FLAG_RLC form), exactly two pairs: item p belongs
+//                                to key key_words[p >> key_shift] of the list (key_shift 6: a pass over slots with the pass's granule -> key words; key_shift 0: one
+//                                word per item, the groups of a pass, whose group g is its granule g) and takes tab0 / tab1 from that key's descriptor
+// The loop is templated on the table source, which hands out (m, c) of a pair's entry of step s and is told when a pair's line product has been issued.
+// a pointer read from memory is a generic pointer to the compiler (flat loads): the descriptors' pointers are named global
+__device__ __forceinline__ const int32_t* c12_global_ptr(uint64_t bits) { return (const int32_t*)(const __attribute__((address_space(1))) int32_t*)bits; }
+__device__ __forceinline__ Fp2 c12_tab_fp2(const int32_t* e) {
+  Fp2 r;
+#pragma unroll
+  for (int i = 0; i < BN_NL; i++) { r.c0.v[i] = e[i]; r.c1.v[i] = e[BN_NL + i]; }
+  return r;
+}
+struct C12TabMC { Fp2 m, c; };
+__device__ __forceinline__ C12TabMC c12_tab_mc(const int32_t* tab, int s) {
+  C12TabMC t;
+  t.m = c12_tab_fp2(tab + (size_t)s * FIXED_LINE_DWORDS); t.c = c12_tab_fp2(tab + (size_t)s * FIXED_LINE_DWORDS + 2 * BN_NL);
+  return t;
+}
+__device__ __forceinline__ int c12_next_step(int s) { return s + 1 < BN_ATE_STEPS ? s + 1 : s; }
+// the key of the launch: a wavefront-uniform entry, scalar loads where the pair's product needs it
+struct C12FixedUniform {
+  const int32_t *tab0, *tab1;
+  __device__ __forceinline__ static C12TabMC entry(const int32_t* tab, int s) { const FixedLine l = c12_line_entry(tab + (size_t)s * FIXED_LINE_DWORDS); return C12TabMC{l.m, l.c}; }
+  __device__ __forceinline__ C12TabMC pair0(int s) const { return entry(tab0, s); }
+  __device__ __forceinline__ C12TabMC pair1(int s) const { return entry(tab1, s); }
+  __device__ __forceinline__ void after_pair0(int) {}
+  __device__ __forceinline__ void after_pair1(int) {}
+};
+// The key of the item.  The five items of a wavefront may belong to five keys, so the tables are read at per-lane addresses (vector loads): every lane needs m and c
+// of both entries whole -- c12_halves takes both components -- and leaves xi c where it is: 72 dwords per lane and step instead of the 108 of the two entries.  An
+// entry of step s + 1 is requested right after the line coefficients of step s are formed from it, so it is in flight during that line product and no second copy is
+// alive.  A key word >= n_keys cannot occur for a pending slot; it reads key 0 and nothing outside the descriptors.
+struct C12FixedPerItem {
+  const int32_t *tab0, *tab1;
+  C12TabMC l0, l1;
+  __device__ __forceinline__ C12FixedPerItem(const PlonkKeyDesc* desc, uint32_t n_keys, uint32_t kw) {
+    static_assert(sizeof(PlonkKeyDesc) == 40 && offsetof(PlonkKeyDesc, tab0) == 16 && offsetof(PlonkKeyDesc, tab1) == 24, "the descriptor's line tables are read by position");
+    const uint64_t* kd = (const uint64_t*)(desc + (kw < n_keys ? kw : 0u));
+    tab0 = c12_global_ptr(kd[2]); tab1 = c12_global_ptr(kd[3]);
+    l0 = c12_tab_mc(tab0, 0); l1 = c12_tab_mc(tab1, 0);
+  }
+  __device__ __forceinline__ C12TabMC pair0(int) const { return l0; }
+  __device__ __forceinline__ C12TabMC pair1(int) const { return l1; }
+  __device__ __forceinline__ void after_pair0(int s) { l0 = c12_tab_mc(tab0, c12_next_step(s)); }   // in flight during the second line product and the squaring of step s + 1
+  __device__ __forceinline__ void after_pair1(int s) { l1 = c12_tab_mc(tab1, c12_next_step(s)); }   // in flight during the squaring and the first line product of step s + 1
+};
+// f <- f * (the line y_P + m x_P w + c w^3 of a table-driven pair): (m x_P)_h = m_h x_P and (i m x_P)_h = (i m)_h x_P, one Fp product each.  inf: P is the identity
+__device__ __forceinline__ void c12_fixed_pair(const Coop12& co, int F, const Fp2& m, const Fp2& c, const Fp& px, const Fp& py, bool inf) {
+  const C12H mh = c12_halves(m, co.h);
+  C12H d3; d3.p = fp_mul(mh.p, px); d3.q = fp_mul(mh.q, px);
+  c12_mul_line_fp(co, F, py, d3, c12_halves(c, co.h), inf);
+}
+// P_0 = (VE_LX, VE_LY), P_1 = (VE_CX, VE_CY) with the identity flags BN254_ST_LINF, BN254_ST_LINF2 of the status byte
+template <class Src>
+__device__ __forceinline__ void c12_fixed_miller(const Coop12& co, const int32_t* ws, uint32_t n, uint32_t pc, uint8_t st, const uint8_t* __restrict__ kinds, int np, Src& src) {
   const int F = C12_SLOT(VE_F);
-  co.put(F, (c == 0 && h == 0) ? fp_one() : fp_zero());
-  const int np = __builtin_amdgcn_readfirstlane(n_pairs);
-  const Fp px0 = c12_ws_ld(ws, n, pc, e_p0), py0 = c12_ws_ld(ws, n, pc, e_p0 + 1), px1 = c12_ws_ld(ws, n, pc, e_p1), py1 = c12_ws_ld(ws, n, pc, e_p1 + 1);
-  const Fp px2 = c12_ws_ld(ws, n, pc, e_p2), py2 = c12_ws_ld(ws, n, pc, e_p2 + 1);
-  const bool i0 = (st & inf0) != 0, i1 = (st & inf1) != 0, i2 = (st & inf2) != 0;
+  co.put(F, (co.c == 0 && co.h == 0) ? fp_one() : fp_zero());
+  const Fp px0 = c12_ws_ld(ws, n, pc, VE_LX), py0 = c12_ws_ld(ws, n, pc, VE_LY), px1 = c12_ws_ld(ws, n, pc, VE_CX), py1 = c12_ws_ld(ws, n, pc, VE_CY);
+  const bool i0 = (st & BN254_ST_LINF) != 0, i1 = (st & BN254_ST_LINF2) != 0;
   for (int s = 0; s < BN_ATE_STEPS; s++) {
     const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
     if (kind == 0 && s != 0) c12_sqr(co, F);
-    // (m x_P)_h = m_h x_P and (i m x_P)_h = (i m)_h x_P: one Fp product each
-    { const FixedLine l = c12_line_entry(tab0 + (size_t)s * FIXED_LINE_DWORDS); const C12H m = c12_halves(l.m, h);
-      C12H d3; d3.p = fp_mul(m.p, px0); d3.q = fp_mul(m.q, px0); c12_mul_line_fp(co, F, py0, d3, c12_halves(l.c, h), i0); }
-    if (np > 1) { const FixedLine l = c12_line_entry(tab1 + (size_t)s * FIXED_LINE_DWORDS); const C12H m = c12_halves(l.m, h);
-      C12H d3; d3.p = fp_mul(m.p, px1); d3.q = fp_mul(m.q, px1); c12_mul_line_fp(co, F, py1, d3, c12_halves(l.c, h), i1); }
-    if (np > 2) { const FixedLine l = c12_line_entry(tab2 + (size_t)s * FIXED_LINE_DWORDS); const C12H m = c12_halves(l.m, h);
-      C12H d3; d3.p = fp_mul(m.p, px2); d3.q = fp_mul(m.q, px2); c12_mul_line_fp(co, F, py2, d3, c12_halves(l.c, h), i2); }
+    { const C12TabMC l = src.pair0(s); c12_fixed_pair(co, F, l.m, l.c, px0, py0, i0); }
+    src.after_pair0(s);
+    if (np > 1) {
+      { const C12TabMC l = src.pair1(s); c12_fixed_pair(co, F, l.m, l.c, px1, py1, i1); }
+      src.after_pair1(s);
+    }
   }
-  if (fuse_final_exp) {
-    Coop12Ops ops{co};
-    vm_final_exp_program(ops);
-    if (target) {
-      // the verdict in the same launch (k_g16_compare's rule): the result never reaches the workspace
-      const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
-      if (pending && c == 0 && h == 0) status[p] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
-    } else c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
-  } else c12_store_f12(co, ws, n, p, F, VE_F, pending);
+}
+// final exponentiation, then the verdict in the same launch (k_g16_compare's rule: the result never reaches the workspace) or, without a target, the store of VE_S0
+__device__ __forceinline__ void c12_fixed_finish(const Coop12& co, int32_t* ws, uint32_t n, uint8_t* status, uint32_t p, uint32_t pl, bool pending, const int32_t* __restrict__ target,
+                                                 int reject_code) {
+  Coop12Ops ops{co};
+  vm_final_exp_program(ops);
+  if (target) {
+    const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
+    if (pending && co.c == 0 && co.h == 0) status[p] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
+  } else c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
+}
+__global__ void __launch_bounds__(64)
+k_coop12_miller_fixed(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, int n_pairs, const int32_t* __restrict__ tab0,
+                      const int32_t* __restrict__ tab1, const int32_t* __restrict__ target, int reject_code) {
+  C12_PROLOGUE();
+  C12FixedUniform src{tab0, tab1};
+  c12_fixed_miller(co, ws, n, pc, st, kinds, __builtin_amdgcn_readfirstlane(n_pairs), src);
+  c12_fixed_finish(co, ws, n, status, p, pl, pending, target, reject_code);
+}
+__global__ void __launch_bounds__(64)
+k_coop12_miller_fixed_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const uint32_t* __restrict__ key_words, uint32_t key_shift,
+                           const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, const int32_t* __restrict__ target, int reject_code) {
+  C12_PROLOGUE();
+  C12FixedPerItem src(desc, n_keys, key_words[pc >> key_shift]);
+  c12_fixed_miller(co, ws, n, pc, st, kinds, 2, src);
+  c12_fixed_finish(co, ws, n, status, p, pl, pending, target, reject_code);
 }
 
 // ---- Groth16: public-input MSM, the shared Miller loop of (A, B) with the running G2 point and the two table-driven pairs, final exponentiation --------------
@@ -409,26 +480,21 @@ __device__ __forceinline__ G1Aff c12_msm_entry(const int32_t* __restrict__ msm_t
   q.y.v[7] = v4.x; q.y.v[8] = v4.y;
   return q;
 }
-// L = K0 + sum_i x_i K_i (groth16/verify.rs:53-63) by the twelve lanes of a proof: lane l adds the table entries of the windows w = l, l + 12, ...
-// (MSM_FW_WINDOWS = 20 windows of 13 bits per input, bn254_fw.h); the twelve partial sums are then added through LDS (lanes 0..5: own + lane l + 6; lanes 0, 1: l, l + 2, l + 4; 0 + 1).
+// L = K0 + sum_i x_i K_i (groth16/verify.rs:53-63) by the twelve lanes of a proof: lane l starts from K0 (lane 0) or the identity and adds the table entries of the
+// windows w = l, l + 12, ... of its proof's inputs; the twelve partial sums are then added through LDS.  The two MSM functions differ in their window loops only.
 // L stays PROJECTIVE: the line of the pair (L, g') is scaled by Z_L, an Fp factor the final exponentiation removes.
-__device__ __noinline__ G1Proj c12_public_input_msm(const Coop12 co, const uint8_t* __restrict__ in /* this proof's inputs */, int n_public, bool use_inputs,
-                                                    const int32_t* __restrict__ msm_tab, const int32_t* __restrict__ k0) {
-  const uint32_t l12 = 2 * co.c + co.h;
+__device__ __forceinline__ G1Proj c12_msm_k0(uint32_t l12, const int32_t* k0) {
   G1Proj acc = g1_identity();
   if (l12 == 0) { G1Aff K0; for (int l = 0; l < BN_NL; l++) { K0.x.v[l] = k0[l]; K0.y.v[l] = k0[BN_NL + l]; } acc = g1_from_affine(K0); }
-  const int windows = use_inputs ? MSM_FW_WINDOWS * n_public : 0;
-  for (int w = (int)l12; w < windows; w += 12) {
-    const int sidx = w / MSM_FW_WINDOWS, wi = w - sidx * MSM_FW_WINDOWS;
-    // window wi = bits 13 wi .. 13 wi + 12 of the big-endian scalar (bn254_fw.h): at most three of its bytes, byte 31 - k holding bits 8 k .. 8 k + 7
-    const int bit = MSM_FW_BITS * wi, k0b = bit >> 3;
-    const uint8_t* sc = in + (size_t)sidx * 32;
-    const uint32_t three = (uint32_t)sc[31 - k0b] | (k0b + 1 < 32 ? (uint32_t)sc[30 - k0b] << 8 : 0u) | (k0b + 2 < 32 ? (uint32_t)sc[29 - k0b] << 16 : 0u);
-    const uint32_t dig = (three >> (bit & 7)) & MSM_FW_ENTRIES;
-    G1Proj nxt = g1_add_mixed(acc, c12_msm_entry(msm_tab, (size_t)(sidx * MSM_FW_WINDOWS + wi) * MSM_FW_ENTRIES + (dig ? dig - 1 : 0)));
-    const bool take = dig != 0;
-    acc.x = fp_select(take, nxt.x, acc.x); acc.y = fp_select(take, nxt.y, acc.y); acc.z = fp_select(take, nxt.z, acc.z);
-  }
+  return acc;
+}
+// acc <- acc + entry where the window's digit is not zero (the mixed addition is computed either way)
+__device__ __forceinline__ void c12_msm_take(G1Proj& acc, const G1Aff& entry, bool take) {
+  const G1Proj nxt = g1_add_mixed(acc, entry);
+  acc.x = fp_select(take, nxt.x, acc.x); acc.y = fp_select(take, nxt.y, acc.y); acc.z = fp_select(take, nxt.z, acc.z);
+}
+// the sum of the twelve lanes' values, to every lane: lanes 0..5: own + lane l + 6; lanes 0, 1: l, l + 2, l + 4; 0 + 1
+__device__ __forceinline__ G1Proj c12_msm_tree(const Coop12& co, G1Proj acc, uint32_t l12) {
   auto publish = [&](const G1Proj& a) { co.put(C12_R1, fp_reduce(a.x)); co.put(C12_R2, fp_reduce(a.y)); co.put(C12_R3, fp_reduce(a.z)); };
   auto fetch = [&](uint32_t i) { G1Proj r; r.x = co.at(C12_R1, co.g0 + i); r.y = co.at(C12_R2, co.g0 + i); r.z = co.at(C12_R3, co.g0 + i); return r; };
   publish(acc);
@@ -440,85 +506,151 @@ __device__ __noinline__ G1Proj c12_public_input_msm(const Coop12 co, const uint8
   publish(acc);
   return fetch(0);
 }
-__global__ void __launch_bounds__(64)
-k_coop12_miller_g16(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const int32_t* __restrict__ tab0,
-                    const int32_t* __restrict__ tab1, const uint8_t* __restrict__ inputs, int n_public, int inputs_match_key,
-                    const int32_t* __restrict__ msm_tab, const int32_t* __restrict__ k0, int l_from_ws, int fuse_final_exp, const int32_t* __restrict__ target) {
-  C12_PROLOGUE();
+// the key of the launch: MSM_FW_WINDOWS = 20 windows of 13 bits per input (bn254_fw.h)
+__device__ __noinline__ G1Proj c12_public_input_msm(const Coop12 co, const uint8_t* __restrict__ in /* this proof's inputs */, int n_public, bool use_inputs,
+                                                    const int32_t* __restrict__ msm_tab, const int32_t* __restrict__ k0) {
+  const uint32_t l12 = 2 * co.c + co.h;
+  G1Proj acc = c12_msm_k0(l12, k0);
+  const int windows = use_inputs ? MSM_FW_WINDOWS * n_public : 0;
+  for (int w = (int)l12; w < windows; w += 12) {
+    const int sidx = w / MSM_FW_WINDOWS, wi = w - sidx * MSM_FW_WINDOWS;
+    // window wi = bits 13 wi .. 13 wi + 12 of the big-endian scalar (bn254_fw.h): at most three of its bytes, byte 31 - k holding bits 8 k .. 8 k + 7
+    const int bit = MSM_FW_BITS * wi, k0b = bit >> 3;
+    const uint8_t* sc = in + (size_t)sidx * 32;
+    const uint32_t three = (uint32_t)sc[31 - k0b] | (k0b + 1 < 32 ? (uint32_t)sc[30 - k0b] << 8 : 0u) | (k0b + 2 < 32 ? (uint32_t)sc[29 - k0b] << 16 : 0u);
+    const uint32_t dig = (three >> (bit & 7)) & MSM_FW_ENTRIES;
+    c12_msm_take(acc, c12_msm_entry(msm_tab, (size_t)(sidx * MSM_FW_WINDOWS + wi) * MSM_FW_ENTRIES + (dig ? dig - 1 : 0)), dig != 0);
+  }
+  return c12_msm_tree(co, acc, l12);
+}
+
+// The shared Miller loop, templated on where the two line tables (table 0: the pair (L, g'), table 1: the pair (C, d')) come from.  A source hands out the operands
+// of a step -- m0, c0, m1 for the G2 rounds, c1 for the third line product -- and is called at four points, of which each source uses two:
+//   start()          before the first step                      C12G16PerGroup: the fetches of step 0
+//   enter(s)         the squaring of step s is issued           C12G16Uniform: the scalar loads of both entries of step s
+//   after_rounds(s)  the G2 rounds of step s are issued         C12G16PerGroup: requests m0 / c0 / m1 of step s + 1
+//   after_lines(s)   the three line products of step s are      C12G16PerGroup: requests c1 of step s + 1
+// The request points are the per-group source's contract (what is alive while a step computes: see its comment); the loop never asks which source it serves.
+// the key of the launch: wavefront-uniform entries, scalar loads of both at the top of the step
+struct C12G16Uniform {
+  const int32_t *tab0, *tab1;
+  FixedLine l0, l1;
+  __device__ __forceinline__ void start() {}
+  __device__ __forceinline__ void enter(int s) {
+    l0 = c12_line_entry(tab0 + (size_t)s * FIXED_LINE_DWORDS);
+    l1 = c12_line_entry(tab1 + (size_t)s * FIXED_LINE_DWORDS);
+  }
+  __device__ __forceinline__ const Fp2& m0() const { return l0.m; }
+  __device__ __forceinline__ const Fp2& c0() const { return l0.c; }
+  __device__ __forceinline__ const Fp2& m1() const { return l1.m; }
+  __device__ __forceinline__ const Fp2& c1() const { return l1.c; }
+  __device__ __forceinline__ void after_rounds(int) {}
+  __device__ __forceinline__ void after_lines(int) {}
+};
+// The key of the group: the line-table dwords a lane needs of a step.  The G2 rounds multiply m of table 0 and m of table 1 at coefficient position 5 only and c of
+// table 0 at position 3 (doubling) or 4 (addition) only (c12_g2_double / c12_g2_add: the operands c12_sel6 picks), so a lane fetches ONE of m, c of table 0 -- the one
+// its position multiplies -- and hands it out for both; every lane needs its halves of c of table 1 for the third line product.  54 dwords per lane and step instead
+// of the 72 of the two entries, in two groups that are each fetched right after their last use in the step before: no second copy is alive while a step computes.
+struct C12G16PerGroup {
+  const int32_t *gtab, *dtab;
+  uint32_t c;
+  Fp2 mc0, m1v, c1v;      // table 0: m at position 5, c elsewhere; table 1: m; table 1: c
+  __device__ __forceinline__ void fetch_g2(int s) {
+    mc0 = c12_tab_fp2(gtab + (size_t)s * FIXED_LINE_DWORDS + (c == 5 ? 0 : 2 * BN_NL));
+    m1v = c12_tab_fp2(dtab + (size_t)s * FIXED_LINE_DWORDS);
+  }
+  __device__ __forceinline__ void fetch_c1(int s) { c1v = c12_tab_fp2(dtab + (size_t)s * FIXED_LINE_DWORDS + 2 * BN_NL); }
+  __device__ __forceinline__ void start() { fetch_g2(0); fetch_c1(0); }
+  __device__ __forceinline__ void enter(int) {}
+  __device__ __forceinline__ const Fp2& m0() const { return mc0; }
+  __device__ __forceinline__ const Fp2& c0() const { return mc0; }
+  __device__ __forceinline__ const Fp2& m1() const { return m1v; }
+  __device__ __forceinline__ const Fp2& c1() const { return c1v; }
+  __device__ __forceinline__ void after_rounds(int s) { fetch_g2(c12_next_step(s)); }      // step s + 1's: in flight during the three line products
+  __device__ __forceinline__ void after_lines(int s) { fetch_c1(c12_next_step(s)); }       // in flight during the squaring and the G2 rounds of step s + 1
+};
+// On return q is B and t the loop's final point.
+template <class Src>
+__device__ __forceinline__ void c12_g16_miller(const Coop12& co, const int32_t* ws, uint32_t n, uint32_t pc, const uint8_t* __restrict__ kinds, const G1Proj& Lp, Src& src, G2Aff& q,
+                                               G2Proj& t) {
   const int F = C12_SLOT(VE_F);
-  // keys with many public inputs: L was computed by the wide MSM kernels (affine, in the workspace, identity flag in the status byte)
-  G1Proj Lp;
-  if (l_from_ws) { Lp.x = c12_ws_ld(ws, n, pc, VE_LX); Lp.y = c12_ws_ld(ws, n, pc, VE_LY); Lp.z = (st & BN254_ST_LINF) ? fp_zero() : fp_one(); }
-  else Lp = c12_public_input_msm(co, inputs + (size_t)pc * (size_t)n_public * 32, n_public, inputs_match_key != 0, msm_tab, k0);
+  const uint32_t h = co.h;
   const bool l_inf = fp_is_zero(Lp.z);
   const Fp xl = Lp.x, yl = fp_select(l_inf, fp_one(), Lp.y), zl = Lp.z;
-  co.put(F, (c == 0 && h == 0) ? fp_one() : fp_zero());
+  co.put(F, (co.c == 0 && h == 0) ? fp_one() : fp_zero());
   const Fp xa = c12_ws_ld(ws, n, pc, VE_AX), ya = c12_ws_ld(ws, n, pc, VE_AY);
   const Fp xc = c12_ws_ld(ws, n, pc, VE_CX), yc = c12_ws_ld(ws, n, pc, VE_CY);
-  G2Aff q; q.x = c12_ws_ld2(ws, n, pc, VE_B); q.y = c12_ws_ld2(ws, n, pc, VE_B + 2);
-  G2Proj t = g2_from_affine(q);
+  q.x = c12_ws_ld2(ws, n, pc, VE_B); q.y = c12_ws_ld2(ws, n, pc, VE_B + 2);
+  t = g2_from_affine(q);
+  src.start();
   for (int s = 0; s < BN_ATE_STEPS; s++) {
     const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
     if (kind == 0 && s != 0) c12_sqr(co, F);
-    const FixedLine l0 = c12_line_entry(tab0 + (size_t)s * FIXED_LINE_DWORDS), l1 = c12_line_entry(tab1 + (size_t)s * FIXED_LINE_DWORDS);
+    src.enter(s);
     C12Line ln;
     if (kind == 0) {
-      c12_g2_double(co, t, xa, ya, l0.m, xl, l1.m, xc, l0.c, zl, ln);
+      c12_g2_double(co, t, xa, ya, src.m0(), xl, src.m1(), xc, src.c0(), zl, ln);
     } else {
       G2Aff b = q;
       if (kind == 2) b = g2_neg(q);
       else if (kind == 3) b = g2_psi_affine(q);
       else if (kind == 4) b = g2_neg(g2_psi2_affine(q));
-      c12_g2_add(co, t, b.x, b.y, xa, ya, l0.m, xl, l1.m, xc, l0.c, zl, ln);
+      c12_g2_add(co, t, b.x, b.y, xa, ya, src.m0(), xl, src.m1(), xc, src.c0(), zl, ln);
     }
+    src.after_rounds(s);
     c12_mul_line_fp2(co, F, c12_halves(ln.d0, h), c12_halves(ln.d3, h), c12_halves(ln.d4, h));
     c12_mul_line_fp(co, F, yl, c12_halves(ln.s1, h), c12_halves(ln.cz, h), l_inf);      // (Y_L + m X_L w + c Z_L w^3): the line at L scaled by Z_L
-    c12_mul_line_fp(co, F, yc, c12_halves(ln.s2, h), c12_halves(l1.c, h), false);
+    c12_mul_line_fp(co, F, yc, c12_halves(ln.s2, h), c12_halves(src.c1(), h), false);
+    src.after_lines(s);
   }
-  if (fuse_final_exp && target) {
-    // The whole verdict in this launch (what k_g16_subgroup and k_g16_compare do for the lane kernels).  The r-torsion test of B from the loop's final
-    // point (bn254_vm.h::vm_g2_ate_check: T == -psi^3(B) projectively) costs four Fp2 products: every lane holds T and B whole and computes it for itself.
-    const Fp2 sx = fp2_mul(fp2_conj(q.x), frob_coeff(3, 2)), sy = fp2_neg(fp2_mul(fp2_conj(q.y), frob_coeff(3, 3)));
-    const bool in_g2 = !fp2_is_zero(t.z) & fp2_eq(t.x, fp2_mul(sx, t.z)) & fp2_eq(t.y, fp2_mul(sy, t.z));
-    Coop12Ops ops{co};
-    vm_final_exp_program(ops);
-    const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
-    if (pending && c == 0 && h == 0) {
-      uint8_t out;
-      if (!in_g2) out = BN254_ST_NOT_IN_SUBGROUP;
-      else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
-      else if (!inputs_match_key) out = BN254_ST_INPUT_LEN;     // PrepareInputsFailed comes after every loader error
-      else out = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
-      status[p] = out;
-    }
-    return;
-  }
-  // the running point goes back to the workspace for the r-torsion test (k_g16_subgroup): lanes of coefficients 0..2 store X, Y, Z.  Not at
-  // VE_T, which the result slot VE_S0 overlays: at COOP_T_ELEM
-  if (pending && c < 3) {
-    const Fp2 tc = c == 0 ? t.x : c == 1 ? t.y : t.z;
-    c12_ws_st(ws, n, p, COOP_T_ELEM + 2 * (int)c + (int)h, h ? tc.c1 : tc.c0);
-  }
-  if (fuse_final_exp) {
-    Coop12Ops ops{co};
-    vm_final_exp_program(ops);
-    c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
-  } else c12_store_f12(co, ws, n, p, F, VE_F, pending);
+}
+// The whole verdict in the launch (what k_g16_subgroup and k_g16_compare do for the lane kernels).  The r-torsion test of B from the loop's final
+// point (bn254_vm.h::vm_g2_ate_check: T == -psi^3(B) projectively) costs four Fp2 products: every lane holds T and B whole and computes it for itself.
+__device__ __forceinline__ void c12_g16_verdict(const Coop12& co, uint8_t* status, uint32_t p, uint32_t pl, uint8_t st, bool pending, const G2Aff& q, const G2Proj& t,
+                                                const int32_t* target, int inputs_match) {
+  const Fp2 sx = fp2_mul(fp2_conj(q.x), frob_coeff(3, 2)), sy = fp2_neg(fp2_mul(fp2_conj(q.y), frob_coeff(3, 3)));
+  const bool in_g2 = !fp2_is_zero(t.z) & fp2_eq(t.x, fp2_mul(sx, t.z)) & fp2_eq(t.y, fp2_mul(sy, t.z));
+  Coop12Ops ops{co};
+  vm_final_exp_program(ops);
+  const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
+  uint8_t out;
+  if (!in_g2) out = BN254_ST_NOT_IN_SUBGROUP;
+  else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
+  else if (!inputs_match) out = BN254_ST_INPUT_LEN;         // PrepareInputsFailed comes after every loader error
+  else out = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
+  if (pending && co.c == 0 && co.h == 0) status[p] = out;
+}
+// without a target (the probe's store mode) the GT value goes to VE_S0 of the workspace instead
+__global__ void __launch_bounds__(64)
+k_coop12_miller_g16(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const int32_t* __restrict__ tab0,
+                    const int32_t* __restrict__ tab1, const uint8_t* __restrict__ inputs, int n_public, int inputs_match_key,
+                    const int32_t* __restrict__ msm_tab, const int32_t* __restrict__ k0, int l_from_ws, const int32_t* __restrict__ target) {
+  C12_PROLOGUE();
+  // keys with many public inputs: L was computed by the wide MSM kernels (affine, in the workspace, identity flag in the status byte)
+  G1Proj Lp;
+  if (l_from_ws) { Lp.x = c12_ws_ld(ws, n, pc, VE_LX); Lp.y = c12_ws_ld(ws, n, pc, VE_LY); Lp.z = (st & BN254_ST_LINF) ? fp_zero() : fp_one(); }
+  else Lp = c12_public_input_msm(co, inputs + (size_t)pc * (size_t)n_public * 32, n_public, inputs_match_key != 0, msm_tab, k0);
+  C12G16Uniform src{tab0, tab1};
+  G2Aff q;
+  G2Proj t;
+  c12_g16_miller(co, ws, n, pc, kinds, Lp, src, q, t);
+  if (target) { c12_g16_verdict(co, status, p, pl, st, pending, q, t, target, inputs_match_key); return; }
+  Coop12Ops ops{co};
+  vm_final_exp_program(ops);
+  c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
 }
 
 // ---- Groth16 over many keys, the DIRECT form (bn254_keys.h; bn254_g16_plan.h::g16_keys_form): k_coop12_miller_g16 with the key taken per PROOF --------------------
 // A slot is a proof and the key belongs to the twelve-lane group: the five proofs of a wavefront may belong to five keys.  Group p reads key_index[p] and the
 // descriptor of that entry with ordinary per-lane loads (all twelve lanes the same address), and every place where k_coop12_miller_g16 takes the key from its launch
 // arguments -- the two line tables, K0 and the fixed-base tables, n_public with inputs_match, the target -- takes it from there.  What differs otherwise:
-//   line tables   fetched per lane with vector loads (c12_key_g2 / c12_key_c1: 54 dwords per step), step s + 1's issued while step s computes; the scalar loads
+//   line tables   fetched per lane with vector loads (C12G16PerGroup: 54 dwords per step), step s + 1's issued while step s computes; the scalar loads
 //                 of c12_line_entry need a wavefront-uniform key
 //   L             over the set's BYTE-window tables (32 windows of 8 bits per input: what k_g16_prepare_keys reads); the loop bound differs per group, all LDS
 //                 traffic comes after the loop
 //   prologue      the two status bytes the pipeline alone cannot decide, before the early return: an index outside the list is MALFORMED whatever the record holds,
 //                 and with BN254_FLAG_STRICT_SCALARS an input >= r among the key's n_public inputs is NOT_MEMBER ahead of every loader outcome
 struct C12Key { const int32_t *msm_tab, *k0, *gtab, *dtab, *target; int n_public, inputs_match; };
-// a pointer read from memory is a generic pointer to the compiler (flat loads): the descriptor's pointers are named global
-__device__ __forceinline__ const int32_t* c12_global_ptr(uint64_t bits) { return (const int32_t*)(const __attribute__((address_space(1))) int32_t*)bits; }
 __device__ __forceinline__ C12Key c12_key(const G16KeyDesc* __restrict__ desc, uint32_t k) {
   // the descriptor as six 64-bit words: five pointers in this order, then the two ints
   static_assert(sizeof(G16KeyDesc) == 48 && offsetof(G16KeyDesc, msm_tab) == 0 && offsetof(G16KeyDesc, k0) == 8 && offsetof(G16KeyDesc, gtab) == 16 &&
@@ -531,62 +663,24 @@ __device__ __forceinline__ C12Key c12_key(const G16KeyDesc* __restrict__ desc, u
   v.n_public = (int)(uint32_t)w; v.inputs_match = (int)(uint32_t)(w >> 32);
   return v;
 }
-// The line-table dwords a lane needs of step s.  The G2 rounds multiply m of table 0 and m of table 1 at coefficient position 5 only and c of table 0 at position 3
-// (doubling) or 4 (addition) only (c12_g2_double / c12_g2_add: the operands c12_sel6 picks), so a lane fetches ONE of m, c of table 0 -- the one its position
-// multiplies -- and passes it for both; every lane needs its halves of c of table 1 for the third line product.  54 dwords per lane and step instead of the 72 of
-// the two entries, in two groups that are each fetched right after their last use in the step before: no second copy is alive while a step computes.
-__device__ __forceinline__ Fp2 c12_tab_fp2(const int32_t* e) {
-  Fp2 r;
-#pragma unroll
-  for (int i = 0; i < BN_NL; i++) { r.c0.v[i] = e[i]; r.c1.v[i] = e[BN_NL + i]; }
-  return r;
-}
-struct C12KeyG2 { Fp2 mc0, m1; };   // table 0: m at position 5, c elsewhere; table 1: m
-__device__ __forceinline__ C12KeyG2 c12_key_g2(const int32_t* gtab, const int32_t* dtab, int s, uint32_t c) {
-  C12KeyG2 l;
-  l.mc0 = c12_tab_fp2(gtab + (size_t)s * FIXED_LINE_DWORDS + (c == 5 ? 0 : 2 * BN_NL));
-  l.m1 = c12_tab_fp2(dtab + (size_t)s * FIXED_LINE_DWORDS);
-  return l;
-}
-__device__ __forceinline__ Fp2 c12_key_c1(const int32_t* dtab, int s) { return c12_tab_fp2(dtab + (size_t)s * FIXED_LINE_DWORDS + 2 * BN_NL); }
-// L = K0 + sum_s x_s K_s by the twelve lanes of a proof over byte windows: lane l adds the entries of the windows w = l, l + 12, ... of the 32 n_public windows of its
-// proof's key (window wi of input s = byte 31 - wi of the big-endian scalar, entry (s * 32 + wi) * 255 + digit - 1), then the tree of c12_public_input_msm
+// byte windows: window wi of input s = byte 31 - wi of the big-endian scalar, entry (s * 32 + wi) * 255 + digit - 1, of the 32 n_public windows of the proof's key
 __device__ __noinline__ G1Proj c12_public_input_msm_keys(const Coop12 co, const uint8_t* in /* this proof's input row */, int n_public, const int32_t* tab, const int32_t* k0p) {
   const uint32_t l12 = 2 * co.c + co.h;
   const uint8_t* row = (const uint8_t*)(const __attribute__((address_space(1))) uint8_t*)in;
   const int32_t *msm_tab = c12_global_ptr((uint64_t)tab), *k0 = c12_global_ptr((uint64_t)k0p);
-  G1Proj acc = g1_identity();
-  if (l12 == 0) { G1Aff K0; for (int l = 0; l < BN_NL; l++) { K0.x.v[l] = k0[l]; K0.y.v[l] = k0[BN_NL + l]; } acc = g1_from_affine(K0); }
+  G1Proj acc = c12_msm_k0(l12, k0);
   const int windows = 32 * n_public;
   for (int w = (int)l12; w < windows; w += 12) {
     const int sidx = w >> 5, wi = w & 31;
     const uint32_t dig = row[sidx * 32 + 31 - wi];
-    G1Proj nxt = g1_add_mixed(acc, c12_msm_entry(msm_tab, (size_t)(sidx * 32 + wi) * 255 + (dig ? dig - 1 : 0)));
-    const bool take = dig != 0;
-    acc.x = fp_select(take, nxt.x, acc.x); acc.y = fp_select(take, nxt.y, acc.y); acc.z = fp_select(take, nxt.z, acc.z);
+    c12_msm_take(acc, c12_msm_entry(msm_tab, (size_t)(sidx * 32 + wi) * 255 + (dig ? dig - 1 : 0)), dig != 0);
   }
-  auto publish = [&](const G1Proj& a) { co.put(C12_R1, fp_reduce(a.x)); co.put(C12_R2, fp_reduce(a.y)); co.put(C12_R3, fp_reduce(a.z)); };
-  auto fetch = [&](uint32_t i) { G1Proj r; r.x = co.at(C12_R1, co.g0 + i); r.y = co.at(C12_R2, co.g0 + i); r.z = co.at(C12_R3, co.g0 + i); return r; };
-  publish(acc);
-  acc = g1_add(acc, fetch(l12 < 6 ? l12 + 6 : l12));
-  publish(acc);
-  { const uint32_t b = l12 < 2 ? l12 : 0; acc = g1_add(g1_add(fetch(b), fetch(b + 2)), fetch(b + 4)); }
-  publish(acc);
-  acc = g1_add(fetch(0), fetch(1));
-  publish(acc);
-  return fetch(0);
+  return c12_msm_tree(co, acc, l12);
 }
 __global__ void __launch_bounds__(64)
 k_coop12_miller_g16_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const uint32_t* __restrict__ key_index,
                          const G16KeyDesc* __restrict__ desc, uint32_t n_keys, const uint8_t* __restrict__ inputs, size_t input_stride, int strict_scalars) {
-  extern __shared__ __attribute__((aligned(16))) int32_t c12_lds[];
-  const uint32_t lane = threadIdx.x & 63;
-  const bool act = lane < 12 * C12_PER_WAVE;
-  const uint32_t la = act ? lane : lane - 12;             // idle lanes shadow the last group
-  const uint32_t pl = la / 12, c = (la - pl * 12) >> 1, h = la & 1;
-  const uint32_t p = blockIdx.x * (uint32_t)C12_PER_WAVE + pl;
-  const bool live = act && p < n;
-  const uint32_t pc = p < n ? p : n - 1;
+  C12_LANES();
   const uint32_t ki = key_index[pc];
   const bool key_ok = ki < n_keys;
   const C12Key key = c12_key(desc, key_ok ? ki : 0u);
@@ -601,110 +695,18 @@ k_coop12_miller_g16_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t
     if (live && c == 0 && h == 0 && fixed != st) status[p] = fixed;
     st = fixed;
   }
-  const bool pending = live && (st & BN254_ST_PENDING) != 0;
-  if (__builtin_amdgcn_ballot_w64(pending) == 0) return;
-  Coop12 co{(c12_lds_i32*)c12_lds, lane, pl * 12, c, h};
-  const int F = C12_SLOT(VE_F);
+  C12_PENDING(st);
   const G1Proj Lp = c12_public_input_msm_keys(co, in, key.inputs_match ? key.n_public : 0, key.msm_tab, key.k0);
-  const bool l_inf = fp_is_zero(Lp.z);
-  const Fp xl = Lp.x, yl = fp_select(l_inf, fp_one(), Lp.y), zl = Lp.z;
-  co.put(F, (c == 0 && h == 0) ? fp_one() : fp_zero());
-  const Fp xa = c12_ws_ld(ws, n, pc, VE_AX), ya = c12_ws_ld(ws, n, pc, VE_AY);
-  const Fp xc = c12_ws_ld(ws, n, pc, VE_CX), yc = c12_ws_ld(ws, n, pc, VE_CY);
-  G2Aff q; q.x = c12_ws_ld2(ws, n, pc, VE_B); q.y = c12_ws_ld2(ws, n, pc, VE_B + 2);
-  G2Proj t = g2_from_affine(q);
-  C12KeyG2 kg = c12_key_g2(key.gtab, key.dtab, 0, c);
-  Fp2 kc1 = c12_key_c1(key.dtab, 0);
-  for (int s = 0; s < BN_ATE_STEPS; s++) {
-    const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
-    const int sn = s + 1 < BN_ATE_STEPS ? s + 1 : s;
-    if (kind == 0 && s != 0) c12_sqr(co, F);
-    C12Line ln;
-    if (kind == 0) {
-      c12_g2_double(co, t, xa, ya, kg.mc0, xl, kg.m1, xc, kg.mc0, zl, ln);
-    } else {
-      G2Aff b = q;
-      if (kind == 2) b = g2_neg(q);
-      else if (kind == 3) b = g2_psi_affine(q);
-      else if (kind == 4) b = g2_neg(g2_psi2_affine(q));
-      c12_g2_add(co, t, b.x, b.y, xa, ya, kg.mc0, xl, kg.m1, xc, kg.mc0, zl, ln);
-    }
-    kg = c12_key_g2(key.gtab, key.dtab, sn, c);      // step s + 1's: in flight during the three line products
-    c12_mul_line_fp2(co, F, c12_halves(ln.d0, h), c12_halves(ln.d3, h), c12_halves(ln.d4, h));
-    c12_mul_line_fp(co, F, yl, c12_halves(ln.s1, h), c12_halves(ln.cz, h), l_inf);      // (Y_L + m X_L w + c Z_L w^3): the line at L scaled by Z_L
-    c12_mul_line_fp(co, F, yc, c12_halves(ln.s2, h), c12_halves(kc1, h), false);
-    kc1 = c12_key_c1(key.dtab, sn);                  // in flight during the squaring and the G2 rounds of step s + 1
-  }
-  // the verdict tail of k_coop12_miller_g16 (fuse_final_exp && target) with the group's key
-  const Fp2 sx = fp2_mul(fp2_conj(q.x), frob_coeff(3, 2)), sy = fp2_neg(fp2_mul(fp2_conj(q.y), frob_coeff(3, 3)));
-  const bool in_g2 = !fp2_is_zero(t.z) & fp2_eq(t.x, fp2_mul(sx, t.z)) & fp2_eq(t.y, fp2_mul(sy, t.z));
-  Coop12Ops ops{co};
-  vm_final_exp_program(ops);
-  const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), key.target, pl);
-  if (pending && c == 0 && h == 0) {
-    uint8_t out;
-    if (!in_g2) out = BN254_ST_NOT_IN_SUBGROUP;
-    else if (st & 0x3f) out = st & 0x3f;                      // deferred error of C
-    else if (!key.inputs_match) out = BN254_ST_INPUT_LEN;     // PrepareInputsFailed comes after every loader error
-    else out = acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
-    status[p] = out;
-  }
-}
-
-// ---- PlonK's two-pair check with the KEY TAKEN PER ITEM (a pass of a batch over many keys, and the groups of its BN254_FLAG_RLC form) ------------------------------
-// k_coop12_miller_fixed for exactly two pairs, except that item p belongs to key key_words[p >> key_shift] of the list (key_shift 6: a pass over slots with the
-// pass's granule -> key words; key_shift 0: one word per item, the groups of a pass, whose group g is its granule g) and takes tab0 / tab1 from that key's descriptor.
-// The five items of a wavefront may belong to five keys, so the tables are read at per-lane addresses (vector loads from pointers named global, as c12_key does):
-// every lane needs m and c of both entries whole -- c12_halves takes both components -- and leaves xi c where it is: 72 dwords per lane and step instead of the 108
-// of the two entries.  An entry of step s + 1 is requested right after the line coefficients of step s are formed from it, so it is in flight during that line
-// product and no second copy is alive.  A key word >= n_keys cannot occur for a pending slot; it reads key 0 and nothing outside the descriptors.
-struct C12TabMC { Fp2 m, c; };
-__device__ __forceinline__ C12TabMC c12_tab_mc(const int32_t* tab, int s) {
-  C12TabMC t;
-  t.m = c12_tab_fp2(tab + (size_t)s * FIXED_LINE_DWORDS); t.c = c12_tab_fp2(tab + (size_t)s * FIXED_LINE_DWORDS + 2 * BN_NL);
-  return t;
-}
-__global__ void __launch_bounds__(64)
-k_coop12_miller_fixed_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, const uint32_t* __restrict__ key_words, uint32_t key_shift,
-                           const PlonkKeyDesc* __restrict__ desc, uint32_t n_keys, int e_p0, int e_p1, int inf0, int inf1, int fuse_final_exp,
-                           const int32_t* __restrict__ target, int reject_code) {
-  C12_PROLOGUE();
-  static_assert(sizeof(PlonkKeyDesc) == 40 && offsetof(PlonkKeyDesc, tab0) == 16 && offsetof(PlonkKeyDesc, tab1) == 24, "the descriptor's line tables are read by position");
-  const uint32_t kw = key_words[pc >> key_shift];
-  const uint64_t* kd = (const uint64_t*)(desc + (kw < n_keys ? kw : 0u));
-  const int32_t *tab0 = c12_global_ptr(kd[2]), *tab1 = c12_global_ptr(kd[3]);
-  const int F = C12_SLOT(VE_F);
-  co.put(F, (c == 0 && h == 0) ? fp_one() : fp_zero());
-  const Fp px0 = c12_ws_ld(ws, n, pc, e_p0), py0 = c12_ws_ld(ws, n, pc, e_p0 + 1), px1 = c12_ws_ld(ws, n, pc, e_p1), py1 = c12_ws_ld(ws, n, pc, e_p1 + 1);
-  const bool i0 = (st & inf0) != 0, i1 = (st & inf1) != 0;
-  C12TabMC l0 = c12_tab_mc(tab0, 0), l1 = c12_tab_mc(tab1, 0);
-  for (int s = 0; s < BN_ATE_STEPS; s++) {
-    const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
-    const int sn = s + 1 < BN_ATE_STEPS ? s + 1 : s;
-    if (kind == 0 && s != 0) c12_sqr(co, F);
-    { const C12H m = c12_halves(l0.m, h), d4 = c12_halves(l0.c, h);
-      C12H d3; d3.p = fp_mul(m.p, px0); d3.q = fp_mul(m.q, px0);
-      c12_mul_line_fp(co, F, py0, d3, d4, i0); }
-    l0 = c12_tab_mc(tab0, sn);        // step s + 1's: in flight during the second line product and the squaring of step s + 1
-    { const C12H m = c12_halves(l1.m, h), d4 = c12_halves(l1.c, h);
-      C12H d3; d3.p = fp_mul(m.p, px1); d3.q = fp_mul(m.q, px1);
-      c12_mul_line_fp(co, F, py1, d3, d4, i1); }
-    l1 = c12_tab_mc(tab1, sn);        // in flight during the squaring and the first line product of step s + 1
-  }
-  if (fuse_final_exp) {
-    Coop12Ops ops{co};
-    vm_final_exp_program(ops);
-    if (target) {
-      const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
-      if (pending && c == 0 && h == 0) status[p] = acc ? BN254_ST_ACCEPT : (uint8_t)reject_code;
-    } else c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending);
-  } else c12_store_f12(co, ws, n, p, F, VE_F, pending);
+  C12G16PerGroup src{key.gtab, key.dtab, c};
+  G2Aff q;
+  G2Proj t;
+  c12_g16_miller(co, ws, n, pc, kinds, Lp, src, q, t);
+  c12_g16_verdict(co, status, p, pl, st, pending, q, t, key.target, key.inputs_match);
 }
 
 }  // namespace bn254
 
 using namespace bn254;
-static inline unsigned c12_grid(size_t n) { return (unsigned)((n + C12_PER_WAVE - 1) / C12_PER_WAVE); }
 // device copy of the step-kind table (88 bytes), created on first use per device
 static const uint8_t* c12_kinds_dev() {
   static uint8_t* dev[64] = {nullptr};
@@ -721,58 +723,40 @@ static const uint8_t* c12_kinds_dev() {
   return dev[d];
 }
 hipError_t bn254_coop12_prepare() { return c12_kinds_dev() ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t bn254_coop12_final_exp(int32_t* ws, uint8_t* status, size_t n, hipStream_t s) {
+// one wavefront per five proofs with its LDS image; every kernel starts (ws, n, status), a Miller kernel takes the step-kind table next
+template <bool KINDS, class Kernel, class... Args>
+static hipError_t c12_launch(Kernel kernel, int32_t* ws, uint8_t* status, size_t n, hipStream_t s, Args... args) {
   const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
-  (void)hipFuncSetAttribute((const void*)k_coop12_final_exp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_coop12_final_exp, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, (const uint8_t*)status);
+  const dim3 grid((unsigned)((n + C12_PER_WAVE - 1) / C12_PER_WAVE));
+  (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if constexpr (KINDS) {
+    const uint8_t* kinds = c12_kinds_dev();
+    if (!kinds) return hipErrorOutOfMemory;
+    hipLaunchKernelGGL(kernel, grid, dim3(64), lds, s, ws, (uint32_t)n, status, kinds, args...);
+  } else hipLaunchKernelGGL(kernel, grid, dim3(64), lds, s, ws, (uint32_t)n, status, args...);
   return hipGetLastError();
 }
-hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* tab0, const int32_t* tab1, const int32_t* tab2,
-                                     int e_p0, int e_p1, int e_p2, int inf0, int inf1, int inf2, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s) {
-  const uint8_t* kinds = c12_kinds_dev();
-  if (!kinds) return hipErrorOutOfMemory;
-  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
-  (void)hipFuncSetAttribute((const void*)k_coop12_miller_fixed, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_coop12_miller_fixed, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, n_pairs, tab0, tab1, tab2,
-                     e_p0, e_p1, e_p2, inf0, inf1, inf2, fuse_final_exp, target, reject_code);
-  return hipGetLastError();
+hipError_t bn254_coop12_final_exp(int32_t* ws, uint8_t* status, size_t n, hipStream_t s) { return c12_launch<false>(k_coop12_final_exp, ws, status, n, s); }
+hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* tab0, const int32_t* tab1, const int32_t* target, int reject_code,
+                                     hipStream_t s) {
+  return c12_launch<true>(k_coop12_miller_fixed, ws, status, n, s, n_pairs, tab0, tab1, target, reject_code);
 }
 hipError_t bn254_coop12_miller_g16(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const uint8_t* inputs, int n_public,
-                                   int inputs_match_key, const int32_t* msm_tab, const int32_t* k0, int l_from_ws, int fuse_final_exp, const int32_t* target, hipStream_t s) {
-  const uint8_t* kinds = c12_kinds_dev();
-  if (!kinds) return hipErrorOutOfMemory;
-  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
-  (void)hipFuncSetAttribute((const void*)k_coop12_miller_g16, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_coop12_miller_g16, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, tab0, tab1, inputs, n_public,
-                     inputs_match_key, msm_tab, k0, l_from_ws, fuse_final_exp, target);
-  return hipGetLastError();
+                                   int inputs_match_key, const int32_t* msm_tab, const int32_t* k0, int l_from_ws, const int32_t* target, hipStream_t s) {
+  return c12_launch<true>(k_coop12_miller_g16, ws, status, n, s, tab0, tab1, inputs, n_public, inputs_match_key, msm_tab, k0, l_from_ws, target);
 }
 hipError_t bn254_coop12_miller_g16_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_index, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint8_t* inputs,
                                         size_t input_stride, int strict_scalars, hipStream_t s) {
-  const uint8_t* kinds = c12_kinds_dev();
-  if (!kinds) return hipErrorOutOfMemory;
-  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
-  (void)hipFuncSetAttribute((const void*)k_coop12_miller_g16_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_coop12_miller_g16_keys, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, key_index, desc, n_keys, inputs, input_stride, strict_scalars);
-  return hipGetLastError();
+  return c12_launch<true>(k_coop12_miller_g16_keys, ws, status, n, s, key_index, desc, n_keys, inputs, input_stride, strict_scalars);
 }
 hipError_t bn254_coop12_miller_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_words, uint32_t key_shift, const bn254::PlonkKeyDesc* desc, uint32_t n_keys,
-                                          int e_p0, int e_p1, int inf0, int inf1, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s) {
-  const uint8_t* kinds = c12_kinds_dev();
-  if (!kinds) return hipErrorOutOfMemory;
+                                          const int32_t* target, int reject_code, hipStream_t s) {
   if (n == 0 || n_keys == 0 || key_shift > 31) return hipErrorInvalidValue;
-  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
-  (void)hipFuncSetAttribute((const void*)k_coop12_miller_fixed_keys, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_coop12_miller_fixed_keys, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, kinds, key_words, key_shift, desc, n_keys, e_p0, e_p1, inf0, inf1,
-                     fuse_final_exp, target, reject_code);
-  return hipGetLastError();
+  return c12_launch<true>(k_coop12_miller_fixed_keys, ws, status, n, s, key_words, key_shift, desc, n_keys, target, reject_code);
 }
 // probe: op 0 mul 1 mul by conj(b) 2 conj(a) * b 3 sqr 4 cyclo_sqr_n (arg squarings) 5 frob (j = arg) 6 inv 7 conj 8 mul_line_fp 9 mul_line_fp with keep
 // 10 mul_line_fp2 11 k_coop12_final_exp 12 c12_eq_const against target
 hipError_t bn254_coop12_dbg_op(int32_t* ws, uint8_t* status, size_t n, int op, int arg, const int32_t* target, hipStream_t s) {
   if (op == 11) return bn254_coop12_final_exp(ws, status, n, s);
-  const size_t lds = (size_t)C12_WAVE_DWORDS * 4;
-  (void)hipFuncSetAttribute((const void*)k_coop12_dbg_op, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  hipLaunchKernelGGL(k_coop12_dbg_op, dim3(c12_grid(n)), dim3(64), lds, s, ws, (uint32_t)n, status, op, arg, target);
-  return hipGetLastError();
+  return c12_launch<false>(k_coop12_dbg_op, ws, status, n, s, op, arg, target);
 }

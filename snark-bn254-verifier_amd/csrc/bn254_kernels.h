@@ -216,25 +216,26 @@ hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, c
 // cooperative layout for small batches (bn254_coop12.hip): twelve lanes per proof (one Fp number of every Fp12 value per lane), 39 KB of LDS per
 // wavefront, the whole Miller loop / final exponentiation in one launch.  (The first generation, six lanes per proof, was retired in round 3:
 // 2.95 ms against 2.11 ms at 4096 proofs; DESIGN.md section 5.4 keeps its measurements.)
-#define COOP_T_ELEM 46          // = VE_S2: where the cooperative Miller loop leaves the running G2 point for k_g16_subgroup
 // Groth16: passes of 1024 wavefronts x 5 proofs, 1.98 ms each.  6 passes = 11.8 ms against 12.9 ms of the lane kernels (one sub-batch, k_miller_run) at 30 720 proofs;
 // 7 passes = 13.7 ms against 13.0 ms at 32 768 (profiles/r03_mid_batch_sweep.txt; until k_miller_run the hand-over was at 40 960)
 #define COOP12_MAX_PROOFS 30720
 // two-pair check of the PlonK path: its lane form is still one launch per operation, the cooperative kernel keeps the range it had
 #define COOP12_MAX_PROOFS_FIXED 40960
 hipError_t bn254_coop12_miller_g16(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const uint8_t* inputs, int n_public,
-                                   int inputs_match_key, const int32_t* msm_tab, const int32_t* k0, int l_from_ws, int fuse_final_exp, const int32_t* target, hipStream_t s);
+                                   int inputs_match_key, const int32_t* msm_tab, const int32_t* k0, int l_from_ws, const int32_t* target, hipStream_t s);
 hipError_t bn254_coop12_miller_g16_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_index, const bn254::G16KeyDesc* desc, uint32_t n_keys, const uint8_t* inputs,
                                         size_t input_stride, int strict_scalars, hipStream_t s);
 hipError_t bn254_coop12_final_exp(int32_t* ws, uint8_t* status, size_t n, hipStream_t s);
 // what the cooperative launchers create on the current device's first use (the 88-byte step-kind table: an allocation and a synchronous copy), created now: a
 // caller that reserves ahead calls this so that its later launches only enqueue
 hipError_t bn254_coop12_prepare();
-hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* tab0, const int32_t* tab1, const int32_t* tab2,
-                                     int e_p0, int e_p1, int e_p2, int inf0, int inf1, int inf2, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s);
+// the table-driven pairs alone (PlonK): P_0 at VE_LX with the flag BN254_ST_LINF, P_1 (n_pairs 2) at VE_CX with BN254_ST_LINF2; with a target the verdict (ACCEPT or
+// reject_code) in the same launch, without one the GT value to VE_S0
+hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* tab0, const int32_t* tab1, const int32_t* target, int reject_code,
+                                     hipStream_t s);
 // the two-pair check with the key per item: item p belongs to key key_words[p >> key_shift] of the list and reads that key's tab0 / tab1 (store mode without a target)
 hipError_t bn254_coop12_miller_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_words, uint32_t key_shift, const bn254::PlonkKeyDesc* desc, uint32_t n_keys,
-                                          int e_p0, int e_p1, int inf0, int inf1, int fuse_final_exp, const int32_t* target, int reject_code, hipStream_t s);
+                                          const int32_t* target, int reject_code, hipStream_t s);
 static inline size_t bn254_coop_max_proofs() { return COOP12_MAX_PROOFS; }
 static inline size_t bn254_coop_max_proofs_fixed() { return COOP12_MAX_PROOFS_FIXED; }
 double bn254_measure_valu_sustained(double ms_target);   // the same kernel back to back for ms_target milliseconds, one interval

@@ -1046,7 +1046,7 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
   if (coop) {
     // small batch: cooperative layout (bn254_coop12.hip): public-input MSM, Miller loop of the three pairs, final exponentiation and the verdict in ONE launch
     hipError_t e;
-    { ProfScope ps_(prof, KID_COOP_G16, s); e = bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, wide ? 1 : 0, 1, a.target, s); }
+    { ProfScope ps_(prof, KID_COOP_G16, s); e = bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, wide ? 1 : 0, a.target, s); }
     if (e != hipSuccess) return e;
     // the r-torsion test of B, the status precedence and the comparison with e(alpha, beta) are the tail of the same launch
     if (ev) { (void)hipEventRecord(ev[2], s); (void)hipEventRecord(ev[3], s); (void)hipEventRecord(ev[4], s); }
@@ -1328,12 +1328,12 @@ hipError_t bn254_launch_dbg_verdict(int form, int32_t* ws, size_t n, uint8_t* st
   else hipLaunchKernelGGL(k_f12_mul_verdict, dim3(grid), dim3(256), 0, s, ws, nn, status, (int)VE_S0, (int)VE_S2, (int)VE_S0, target, (int)BN254_ST_REJECT, (const uint32_t*)nullptr, status);
   return hipGetLastError();
 }
-// k_g16_prepare as a cooperative launch runs it, then k_coop12_miller_g16 in its store mode (fuse_final_exp, no target): the GT value of every proof still pending
+// k_g16_prepare as a cooperative launch runs it, then k_coop12_miller_g16 in its store mode (no target): the GT value of every proof still pending
 // after the loader is left in VE_S0, its status byte keeps PENDING.  Keys with at most G16_WIDE_MSM_MIN_INPUTS inputs (L by the cooperative kernel itself)
 hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_g16_prepare, dim3(grid_for(a.n)), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.n_public, (uint32_t)a.n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, 1,
                      (const uint32_t*)nullptr, (uint8_t*)nullptr);
-  return bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, 0, 1, nullptr, s);
+  return bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, 0, nullptr, s);
 }
 hipError_t bn254_launch_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s) {
   unsigned g = grid_for(n);
@@ -1378,7 +1378,7 @@ hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, c
   static const size_t coop_fixed_max = [] { const char* e = getenv("BN254_COOP_FIXED_MAX"); return e ? (size_t)atol(e) : bn254_coop_max_proofs_fixed(); }();
   if (coop_on && n <= coop_fixed_max) {
     // small batch: the cooperative layout (bn254_coop12.hip), Miller loop of the two pairs, final exponentiation and the comparison in ONE launch
-    return bn254_coop12_miller_fixed(ws, status, n, 2, tab0, tab1, tab0, VE_LX, VE_CX, VE_LX, BN254_ST_LINF, BN254_ST_LINF2, 0, 1, target_one, reject_code, s);
+    return bn254_coop12_miller_fixed(ws, status, n, 2, tab0, tab1, target_one, reject_code, s);
   }
   BN_LAUNCH(KID_VM_INIT, k_vm_init, ws, nn, (const uint8_t*)status);
   const uint8_t* kinds = step_kinds_host();
@@ -1423,7 +1423,7 @@ hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t
   ops.plonk_desc = desc; ops.n_keys = n_keys; ops.granule_key = granule_key;
   // a pass of up to the knob's slots (bn254_set_plonk_keys_params; BN254_COOP=0: never): the cooperative layout with the key of every item's granule, ONE launch
   if (plonk_keys_coop_form(n))
-    return bn254_coop12_miller_fixed_keys(ws, status, n, granule_key, 6, desc, n_keys, VE_LX, VE_CX, BN254_ST_LINF, BN254_ST_LINF2, 1, target_one, reject_code, s);
+    return bn254_coop12_miller_fixed_keys(ws, status, n, granule_key, 6, desc, n_keys, target_one, reject_code, s);
   BN_LAUNCH(KID_VM_INIT, k_vm_init, ws, nn, (const uint8_t*)status);
   // steps per launch as in the single-key form (BN254_MILLER_RUN_STEPS; 0 there selects the one-launch-per-operation kernels, which read one key per launch: the whole loop here)
   static const int run_steps = [] { const char* e = getenv("BN254_MILLER_RUN_STEPS"); int v = e ? atoi(e) : BN_ATE_STEPS; return v <= 0 ? BN_ATE_STEPS : v; }();
@@ -1437,5 +1437,5 @@ hipError_t bn254_launch_pairing2_fixed_keys(int32_t* ws, uint8_t* status, size_t
 hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t* grp_ws, uint8_t* grp_status, size_t groups, const PlonkKeyDesc* desc, uint32_t n_keys, const uint32_t* granule_key,
                                                    const int32_t* target_one, int reject_code, hipStream_t s) {
   if (groups > bn254_coop_max_proofs_fixed()) return hipErrorInvalidValue;
-  return bn254_coop12_miller_fixed_keys(grp_ws, grp_status, groups, granule_key, 0, desc, n_keys, VE_LX, VE_CX, BN254_ST_LINF, BN254_ST_LINF2, 1, target_one, reject_code, s);
+  return bn254_coop12_miller_fixed_keys(grp_ws, grp_status, groups, granule_key, 0, desc, n_keys, target_one, reject_code, s);
 }

@@ -434,7 +434,7 @@ def test_coop12_miller_fixed_values(L, O, key):
 
 
 def test_coop12_miller_g16_values(L, O, key):
-    """k_coop12_miller_g16 with fuse_final_exp and no target on a 13-proof synthetic batch: every failure class (wrong input, wrong C, B outside G2 reach the pairing;
+    """k_coop12_miller_g16 in its store mode (no target) on a 13-proof synthetic batch: every failure class (wrong input, wrong C, B outside G2 reach the pairing;
     A off the curve and A.x >= p stop at the loader) and proofs whose public-input point L is the identity.  The GT value of every proof that reaches the pairing is
     e(A, B) e(L, -gamma) e(C, -delta) of the oracle, with L from the oracle's group law; for an accepted proof it is also the key's target e(alpha, beta)."""
     out, st = (C.c_uint8 * (384 * NC))(), (C.c_uint8 * NC)()

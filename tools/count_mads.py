@@ -475,13 +475,14 @@ def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2, msm="msm"):
         notes.append("Miller loop x88: squaring of f (%d multiply-adds) x64, line product of a table-driven pair (%d) x88 for each of the 2 pairs, the tables of the item's key"
                      % (s_m, p_m // 2))
     else:
-        # sqr (conditional), pair 0, pair 1 (conditional: n_pairs > 1), first latch (taken when n_pairs <= 2), pair 2, second latch
-        assert len(latches) == 2 and len(conds) == 2, ("k_coop12_miller_fixed: layout changed", latches, conds)
-        (s_lo, s_hi, s_m), (p1_lo, p1_hi, p1_m) = conds
-        p2_lo, p2_hi = latches[0] + 1, latches[1]
-        p2_m = count_in(mads, p2_lo, p2_hi)
-        assert 700 <= s_m <= 800 and 800 <= p1_m <= 900 and p1_m == p2_m, (s_m, p1_m, p2_m)
-        ranges += [(s_lo, s_hi, 64.0 / steps), (p1_lo, p1_hi, 1.0 if n_pairs > 1 else 0.0), (p2_lo, p2_hi, 1.0 if n_pairs > 2 else 0.0)]
+        # sqr (conditional), pair 0, first latch (taken when n_pairs is 1), pair 1 as the fall-through to the second latch
+        assert len(latches) == 2 and len(conds) == 1, ("k_coop12_miller_fixed: layout changed", latches, conds)
+        (s_lo, s_hi, s_m), = conds
+        p1_lo, p1_hi = latches[0] + 1, latches[1]
+        p1_m = count_in(mads, p1_lo, p1_hi)
+        p0_m = count_in(mads, lo, hi) - s_m - p1_m
+        assert 700 <= s_m <= 800 and 800 <= p1_m <= 900 and p0_m == p1_m, (s_m, p0_m, p1_m)
+        ranges += [(s_lo, s_hi, 64.0 / steps), (p1_lo, p1_hi, 1.0 if n_pairs > 1 else 0.0)]
         notes.append("Miller loop x88: squaring of f (%d multiply-adds) x64, line product of a table-driven pair (%d) x88 for each of the %d pairs"
                      % (s_m, p1_m, n_pairs))
     tot = counts(ins, ranges)
