@@ -57,7 +57,8 @@ enum {
                                (short buffer, flag 0b00, no square root; groth16/converter.rs:28-89, plonk/converter.rs:18-119).  Status byte equivalent: BN254_ERR_MALFORMED.
                                A key that LOADS is never refused: no K points at all (every proof: loader error, else BN254_ERR_INPUT_LEN), G2 elements outside the r-torsion
                                (the loaders are "unchecked", converter.rs:113-133: computed on, as the reference does) */
-  BN254_E_NOMEM = -5
+  BN254_E_NOMEM = -5,
+  BN254_E_SELFTEST = -6     /* the device failed its known-answer self-test (bn254_device_selftest below): nothing is launched on it, no status byte is written */
 };
 
 /* ---- verifying-key interpretation ---------------------------------------------------------
@@ -408,6 +409,57 @@ int bn254_sp1_plonk_verify_batch_device(const bn254_plonk_pvk* pvk, const void* 
                                         const void* d_public_values, size_t pv_bytes, const uint64_t* d_pv_offsets, size_t n, void* d_status, int device,
                                         void* hip_stream, unsigned flags);
 
+/* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
+ * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
+ * before a device is first used the library runs the kernels IT SHIPS on THAT device on small built-in inputs and compares every output byte with a known answer.
+ *
+ * The automatic run happens once per process and device, at the places that make a device ready: the first bn254_groth16_* / bn254_plonk_* / bn254_sp1_* call that
+ * touches the device (reservations included: bn254_*_reserve* pay it, so a _device call enqueued after a reservation stays free of synchronous work), the first use
+ * of a key list, bn254_groth16_vk_prepare_batch on a device.  Concurrent first calls on one device wait for the one run.  It runs on a stream of its own (of the
+ * lowest priority: it takes no hardware queue from the pool the process's other streams share), synchronises with that stream only, and frees everything it
+ * allocated before it returns.
+ * If a check disagrees the state is sticky: every entry that would launch verification work on that device returns BN254_E_SELFTEST at once, with the recorded text
+ * in bn254_last_error(), and writes no status byte -- until an explicit bn254_device_selftest on that device passes.  (A run that could not be made -- no memory, a
+ * runtime error -- returns that error and records nothing: the next call tries again.)
+ * BN254_SELFTEST=0 in the environment, read once when the library is loaded, skips the automatic run (state 2); the explicit entry still works.
+ * BN254_PLONK_SELFTEST and the per-key self-test of the PlonK stage kernels are independent of this and stay as they were.
+ *
+ * The checks (bit k of a failed mask; the names are part of the interface):
+ *    0 fp            the lane Fp product on 64 operand pairs: 0, 1, p - 1, p - 2, all-ones and alternating digits, pseudo-random values
+ *    1 fp12_lane     the lane Fp12 kernels: product, square, inverse, cyclotomic square (after the easy part, and on a cyclotomic element), Frobenius 1..3
+ *    2 fp12_coop     single operations of the cooperative layout on 6 values (two wavefronts): product, square, 3 cyclotomic squarings, Frobenius 1..3, inverse,
+ *                    k_coop12_final_exp
+ *    3 pairing_lane  the variable-Q Miller loop and the final-exponentiation program: e(G1, G2), e(aG1, bG2), e(-aG1, bG2) and one more pair
+ *    4 g16_lane      the exact Groth16 lane form (k_g16_prepare, k_miller_run, the final exponentiation with its verdict product) through bn254_launch_g16, forced whatever
+ *                    BN254_COOP or any knob says: a built-in 2-input key and 64 proofs, valid ones and every corruption class of bn254_synth_groth16; status bytes
+ *    5 g16_coop      k_g16_prepare and k_coop12_miller_g16 on the same key and proofs
+ *    6 pair2_lane    the lane form of the PlonK pairing check (k_miller_run_fixed2, final exponentiation, k_g16_compare) on the built-in key's two line tables: 64 items,
+ *                    accepted ones, rejected ones, items with an identity argument
+ *    7 pair2_coop    k_coop12_miller_fixed on the same items
+ *    8 codec         k_g16_decompress: 8 compressed proofs, flag 0b00, an x without a square root, the G2 infinity flag
+ *    9 sha256        k_sp1_public_inputs: values of 0, 55, 56, 64, 119, 120 and 1000 bytes at unaligned offsets and one range outside the buffer
+ * Expected values: the status bytes of checks 4 .. 7 are tables generated with the key's trapdoors (gen_constants.py -> csrc/bn254_constants.h; no pairing is
+ * computed for them at run time); everything else is the host's compile of the same arithmetic source, computed once per process while the device runs.
+ * NOT covered in this revision: the _keys variants of the kernels (batches over many keys), the RLC group kernels, the MSM row kernels and the wide-key MSM kernels,
+ * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
+ *
+ * Cost on one MI355X (profiles/selftest_cost.txt): one run is 40 ms of wall time in a warm process, all of it device time on the run's own stream (g16_lane 11.2 ms,
+ * pairing_lane 9.0, pair2_lane 8.3, g16_coop 1.9, the built-in key's window tables 1.5, codec 1.4, pair2_coop 1.3, fp12_coop 1.1, fp12_lane 0.7); the host's share (the key
+ * 3 ms, the expected values 7.8 ms, once per process) runs while the device works.  A process's first single-proof bn254_groth16_verify -- runtime initialisation, code
+ * objects, key preparation -- took 261 ms (median of five processes) before this feature, 295 ms with the automatic run, 270 ms with BN254_SELFTEST=0.
+ *
+ * bn254_device_selftest: runs all checks NOW on `device`, whatever ran before and whatever the environment says.  *failed_mask: bit k set when check k disagrees;
+ *   *ms: the wall time of the run; either may be null.  BN254_OK when every check agrees; BN254_E_SELFTEST when one does not -- bn254_last_error() then names the first
+ *   failing check and gives a short hex prefix of the device's value and of the expected one; BN254_E_NO_DEVICE / BN254_E_BAD_ARG / BN254_E_HIP / BN254_E_NOMEM as
+ *   everywhere.  Its result REPLACES the device's recorded state: a pass clears an earlier failure.  An operator's health check.
+ * bn254_device_selftest_state: *state = -1 (not run yet), 0 (failed), 1 (passed), 2 (skipped: BN254_SELFTEST=0); *failed_mask (may be null): the mask of the recorded
+ *   run.  Touches no device.
+ * bn254_selftest_check_name: the name of check 0 .. 9, "" outside. */
+#define BN254_SELFTEST_NUM_CHECKS 10
+int bn254_device_selftest(int device, unsigned* failed_mask, float* ms);
+int bn254_device_selftest_state(int device, int* state, unsigned* failed_mask);
+const char* bn254_selftest_check_name(int check);
+
 /* ---- measurement support ------------------------------------------------------------------------------------------
  * A sub-batch above COOP12_MAX_PROOFS runs as about 110 kernel launches: k_g16_prepare, the whole Miller loop as ONE k_miller_run (or a few, g16_launch_form; the
  * first sets f and T, the last tests B's subgroup) and one launch per Fp12-level operation of the final exponentiation (k_f12_mul x 54, the last of them with the
@@ -526,6 +578,27 @@ int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs,
                                 int device);
 int bn254_dbg_g2_subgroup(const uint8_t* g2, uint8_t* out_flags, size_t n, int device);                       /* 1 = in G2 (gnark's psi relation, one kernel) */
 int bn254_dbg_g2_subgroup_ate(const uint8_t* g1, const uint8_t* g2, uint8_t* out_flags, size_t n, int device); /* 1 = in G2: the product's test, from the Miller loop's final point (g1: any G1 points) */
+
+/* The vectors of the device self-test and a run with a fault injected (tests).
+ * bn254_dbg_selftest_vectors (host only): the inputs and the expected outputs of check k.  *in_len / *exp_len are always written; BN254_E_BAD_ARG if a buffer is too small.
+ * Layouts (Fp12: 384 bytes, G1: 64, G2: 128, as above):
+ *    0  in a[64] | b[64], 32 bytes each                                      expect 64 products
+ *    1  in a[2] | b[2] | c[2] (c cyclotomic)                                 expect 8 x 2 values: a b, a^2, 1/a, cyclo_sqr(easy(a)), frob1 a, cyclo_sqr(c), frob2 a, frob3 a
+ *    2  in a[6] | b[6] | c[6]                                                expect 8 x 6 values: a b, a^2, c^(2^3), frob1 a, frob2 a, frob3 a, 1/a, final_exp(a)
+ *    3  in g1[4] | g2[4]                                                     expect 4 GT values
+ *    4, 5  in vk (520 bytes, gnark) | 64 raw proofs | 64 rows of 2 inputs    expect 64 status bytes (key mode BN254_VK_REFERENCE)
+ *    6, 7  in Q_0 | Q_1 | target (GT) | P_0[64] | P_1[64] | 64 flag bytes (bit t: P_t is the identity, its bytes are then x = 0, y = 1)
+ *                                                                            expect 64 status bytes: BN254_ACCEPT where e(P_0, Q_0) e(P_1, Q_1) = target, else BN254_ERR_PAIRING_FAILED
+ *    8  in 11 compressed records of 128 bytes                                expect 11 raw records of 256 bytes | 11 pre bytes (1: does not decompress)
+ *    9  in 8 vkey hashes | 9 offsets (u64 LE) | pv_bytes (u64 LE) | the values' buffer (1424 bytes)     expect 8 rows (vkey hash | digest) | 8 pre bytes (1: range outside)
+ * bn254_dbg_selftest: the run of bn254_device_selftest with one bit of the DEVICE-SIDE INPUT of check corrupt_check flipped before the upload (-1: none), the expected
+ * values untouched: the kernels honestly compute something else -- wrong values, never a fault -- and the comparison must see it (for the status checks the bit changes
+ * a proof's status).  record 0: the device's recorded state is not touched; 1: the result is recorded as the automatic run's would be.
+ * bn254_dbg_selftest_ms: of the last run in this process: the time between the events around each check (gpu_ms[0 .. 9]; gpu_ms[10]: the built-in key's upload and
+ * window tables), the host time spent on the key and the expected values meanwhile, and the run's wall time. */
+int bn254_dbg_selftest_vectors(int check, uint8_t* in, size_t in_cap, size_t* in_len, uint8_t* expect, size_t exp_cap, size_t* exp_len);
+int bn254_dbg_selftest(int device, int corrupt_check, int record, unsigned* failed_mask);
+int bn254_dbg_selftest_ms(float gpu_ms[BN254_SELFTEST_NUM_CHECKS + 1], float* host_ms, float* wall_ms);
 
 /* stage 1 of the PlonK path as the DEVICE runs it (csrc/bn254_k_plonk.hip), for n proofs: zeta -- the last of the four chained Fiat-Shamir challenges
  * (plonk/verify.rs:62-95), 32-byte big-endian, canonical -- and the stage's status per proof (BN254_ACCEPT: alive; else the error it decided) */

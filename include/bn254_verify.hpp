@@ -68,6 +68,10 @@ struct InfrastructureError : std::runtime_error {
   int code;
   explicit InfrastructureError(int c) : std::runtime_error(std::string("bn254_verify: ") + bn254_last_error()), code(c) {}
 };
+// BN254_E_SELFTEST: a shipped kernel disagrees with its known answer on the device, which is refused until a device_selftest on it passes; what() names the check
+struct SelfTestError : InfrastructureError {
+  explicit SelfTestError() : InfrastructureError(BN254_E_SELFTEST) {}
+};
 
 template <class T, class E>
 class Result {   // Result<bool, Groth16Error> / Result<bool, PlonkError>
@@ -87,7 +91,7 @@ class Result {   // Result<bool, Groth16Error> / Result<bool, PlonkError>
 };
 
 namespace detail {
-inline void check(int rc) { if (rc != BN254_OK) throw InfrastructureError(rc); }
+inline void check(int rc) { if (rc == BN254_E_SELFTEST) throw SelfTestError(); if (rc != BN254_OK) throw InfrastructureError(rc); }
 inline Bytes flatten(const std::vector<Fr>& v) { Bytes b(32 * v.size()); for (size_t i = 0; i < v.size(); i++) std::copy(v[i].begin(), v[i].end(), b.begin() + 32 * i); return b; }
 inline Result<bool, Groth16Error> groth16_outcome(int st) {
   switch (st) {
@@ -364,5 +368,31 @@ struct PlonkVerifier {
   static void set_rlc_params(long min_pass) { bn254_set_plonk_rlc_params(min_pass); }
   static Result<bool, PlonkError> outcome(uint8_t status) { return detail::plonk_outcome(status); }
 };
+
+// The known-answer self-test of the verdict kernels on `device`, now (bn254_device_selftest): an operator's health check.  The library runs it by itself before a
+// device is first used (after which a device that failed makes every verification entry throw SelfTestError); this call runs it whatever ran before, and its result
+// replaces the device's recorded state.  A check that disagrees is a report with passed == false; a run that could not be made throws InfrastructureError.
+struct SelfTestReport {
+  bool passed = false;
+  unsigned failed_mask = 0;              // bit k: check k disagrees
+  std::vector<std::string> failed;       // their names (bn254_selftest_check_name)
+  float ms = 0.f;                        // wall time of the run
+  std::string message;                   // bn254_last_error() of a failed run: the first failing check, the device's value and the expected one
+};
+inline SelfTestReport device_selftest(int device = 0) {
+  SelfTestReport r;
+  const int rc = bn254_device_selftest(device, &r.failed_mask, &r.ms);
+  if (rc != BN254_OK && rc != BN254_E_SELFTEST) detail::check(rc);
+  r.passed = rc == BN254_OK;
+  if (!r.passed) r.message = bn254_last_error();
+  for (int k = 0; k < BN254_SELFTEST_NUM_CHECKS; k++) if (r.failed_mask >> k & 1u) r.failed.push_back(bn254_selftest_check_name(k));
+  return r;
+}
+// the recorded state of a device: -1 not run yet, 0 failed, 1 passed, 2 skipped (BN254_SELFTEST=0).  Touches no device
+inline std::pair<int, unsigned> device_selftest_state(int device = 0) {
+  int state = -1; unsigned mask = 0;
+  detail::check(bn254_device_selftest_state(device, &state, &mask));
+  return {state, mask};
+}
 
 }  // namespace snark_bn254_verifier

@@ -31,13 +31,45 @@ impl From<u8> for Status {
         }
     }
 }
-/// Infrastructure failure (no device, HIP error, bad argument): `rc` of the C ABI with `bn254_last_error()`.
+/// What keeps the library from running: not an outcome of a proof.  `message` is `bn254_last_error()` of the call.
 #[derive(Debug, Clone)]
-pub struct Error { pub code: c_int, pub message: String }
+pub enum Error {
+    /// no device, HIP error, bad argument, out of memory: `code` is the `BN254_E_*` value
+    Infrastructure { code: c_int, message: String },
+    /// `BN254_E_SELFTEST`: a shipped kernel disagrees with its known answer on the device, which is refused until a `device_selftest` on it passes; the
+    /// message names the first failing check
+    SelfTest { message: String },
+}
+impl Error {
+    pub fn code(&self) -> c_int { match self { Error::Infrastructure { code, .. } => *code, Error::SelfTest { .. } => sys::BN254_E_SELFTEST } }
+    pub fn message(&self) -> &str { match self { Error::Infrastructure { message, .. } | Error::SelfTest { message } => message } }
+}
 fn check(rc: c_int) -> Result<(), Error> {
     if rc == sys::BN254_OK { return Ok(()); }
     let message = unsafe { CStr::from_ptr(sys::bn254_last_error()) }.to_string_lossy().into_owned();
-    Err(Error { code: rc, message })
+    Err(if rc == sys::BN254_E_SELFTEST { Error::SelfTest { message } } else { Error::Infrastructure { code: rc, message } })
+}
+
+/// What `device_selftest` found: the checks that disagree (bit k of `failed_mask` = check k, `failed` their names) and the wall time of the run.
+#[derive(Debug, Clone)]
+pub struct SelfTestReport { pub passed: bool, pub failed_mask: u32, pub failed: Vec<String>, pub ms: f32, pub message: Option<String> }
+
+/// The known-answer self-test of the verdict kernels on `device`, now (`bn254_device_selftest`): an operator's health check.  The library runs it by itself before a
+/// device is first used; this call runs it whatever ran before, and its result replaces the device's recorded state (a pass clears an earlier failure).  A check
+/// that disagrees is a report with `passed == false`, not an `Err`: `Err` is for a run that could not be made.
+pub fn device_selftest(device: i32) -> Result<SelfTestReport, Error> {
+    let (mut mask, mut ms) = (0 as core::ffi::c_uint, 0f32);
+    let rc = unsafe { sys::bn254_device_selftest(device as c_int, &mut mask, &mut ms) };
+    let message = match check(rc) { Ok(()) => None, Err(Error::SelfTest { message }) => Some(message), Err(e) => return Err(e) };
+    let failed = (0..sys::BN254_SELFTEST_NUM_CHECKS as c_int).filter(|k| mask >> k & 1 == 1)
+        .map(|k| unsafe { CStr::from_ptr(sys::bn254_selftest_check_name(k)) }.to_string_lossy().into_owned()).collect();
+    Ok(SelfTestReport { passed: rc == sys::BN254_OK, failed_mask: mask as u32, failed, ms, message })
+}
+/// (state, failed mask) of the device's recorded self-test: -1 not run yet, 0 failed, 1 passed, 2 skipped (`BN254_SELFTEST=0`).  Touches no device.
+pub fn device_selftest_state(device: i32) -> Result<(i32, u32), Error> {
+    let (mut state, mut mask) = (-1 as c_int, 0 as core::ffi::c_uint);
+    check(unsafe { sys::bn254_device_selftest_state(device as c_int, &mut state, &mut mask) })?;
+    Ok((state as i32, mask as u32))
 }
 
 /// Which reading of a compressed G2 point the key loader uses: the reference's literal function, or gnark's.

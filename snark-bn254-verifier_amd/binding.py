@@ -14,8 +14,18 @@ NUM_KERNELS = 4
 ABI_VERSION = 5   # include/bn254_verify.h: BN254_ABI_VERSION
 
 
+E_SELFTEST = -6      # BN254_E_SELFTEST: the device failed its known-answer self-test and is refused
+SELFTEST_NUM_CHECKS = 10
+
+
 class Bn254Error(RuntimeError):
-    pass
+    """An infrastructure error of the C ABI; `code` is the BN254_E_* value (None where the binding itself refuses)."""
+    code = None
+
+
+class Bn254SelfTestError(Bn254Error):
+    """BN254_E_SELFTEST: a shipped kernel disagrees with its known answer on the device (device_selftest); the text names the check."""
+    code = E_SELFTEST
 
 
 def lib_path():
@@ -182,7 +192,44 @@ def dbg_keys_plan(n, n_keys):
 
 def _check(rc):
     if rc != 0:
-        raise Bn254Error("bn254 error %d: %s" % (rc, lib().bn254_last_error().decode()))
+        e = (Bn254SelfTestError if rc == E_SELFTEST else Bn254Error)("bn254 error %d: %s" % (rc, lib().bn254_last_error().decode()))
+        e.code = rc
+        raise e
+
+
+def selftest_check_names():
+    L = lib()
+    L.bn254_selftest_check_name.restype = C.c_char_p
+    return [L.bn254_selftest_check_name(k).decode() for k in range(SELFTEST_NUM_CHECKS)]
+
+
+def device_selftest(device=0):
+    """The known-answer self-test of the verdict kernels on `device`, now (bn254_device_selftest): {"passed", "failed": names of the checks that disagree, "mask", "ms",
+    "error": the library's text for the first failing check or None}.  The result replaces the device's recorded state.  Raises for everything but a failed check
+    (no device, out of memory, ..)."""
+    L = lib()
+    mask, ms = C.c_uint(0), C.c_float(0)
+    rc = L.bn254_device_selftest(int(device), C.byref(mask), C.byref(ms))
+    if rc != 0 and rc != E_SELFTEST:
+        _check(rc)
+    names = selftest_check_names()
+    return {"passed": rc == 0, "failed": [names[k] for k in range(SELFTEST_NUM_CHECKS) if mask.value >> k & 1], "mask": int(mask.value), "ms": float(ms.value),
+            "error": L.bn254_last_error().decode() if rc else None}
+
+
+def selftest_state(device=0):
+    """(state, failed mask) of the device's recorded self-test (bn254_device_selftest_state): -1 not run yet, 0 failed, 1 passed, 2 skipped (BN254_SELFTEST=0)."""
+    state, mask = C.c_int(-1), C.c_uint(0)
+    _check(lib().bn254_device_selftest_state(int(device), C.byref(state), C.byref(mask)))
+    return int(state.value), int(mask.value)
+
+
+def dbg_selftest(device=0, corrupt_check=-1, record=False):
+    """bn254_dbg_selftest: the self-test with one bit of check corrupt_check's device-side input flipped (-1: none): (return code, failed mask, error text)."""
+    L = lib()
+    mask = C.c_uint(0)
+    rc = L.bn254_dbg_selftest(int(device), int(corrupt_check), 1 if record else 0, C.byref(mask))
+    return rc, int(mask.value), L.bn254_last_error().decode() if rc else ""
 
 
 def _inputs_bytes(public_inputs):

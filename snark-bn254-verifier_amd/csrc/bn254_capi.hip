@@ -1,9 +1,12 @@
 // bn254_capi.hip -- implementation of the C ABI declared in include/bn254_verify.h: version, errors and status strings, the host plumbing the
 // protocol files share, the point codecs and the SP1 fixture parser, the shard plan and the status all-gather of multi-device jobs.
 // The protocols live beside it: bn254_capi_g16.hip (Groth16), bn254_capi_plonk.hip (PlonK), bn254_capi_sp1.hip (SP1 proofs from their public values),
-// bn254_capi_dbg.hip (test probes, workload generator).
+// bn254_capi_dbg.hip (test probes, workload generator), bn254_capi_selftest.hip (the device self-test and its gate).
 // Host orchestration only: key preparation (bn254_host.hpp), device buffers, kernel launches (bn254_kernels.hip).
 // There is deliberately no CPU implementation of verify here: if HIP is unusable the calls fail (BN254_E_NO_DEVICE).
+#if !defined(__HIPCC__)
+#define BN254_SELFTEST_TABLES 1      // the one-unit host build (bottom of this file) brings bn254_capi_selftest.hip, which reads the tables of bn254_constants.h
+#endif
 #include "bn254_capi_internal.h"
 
 static_assert(BN254_REJECT == BN254_ST_REJECT && BN254_ACCEPT == BN254_ST_ACCEPT && BN254_ERR_NOT_MEMBER == BN254_ST_NOT_MEMBER &&
@@ -334,6 +337,16 @@ int bn254_status_all_gather(void* nccl_comm, int world, int rank, const void* d_
 #include "bn254_capi_plonk.hip"
 #include "bn254_capi_sp1.hip"
 #include "bn254_capi_dbg.hip"
+#include "bn254_capi_selftest.hip"
+// the device half of the self-test (bn254_selftest_dev.hip): nothing to launch in a host build, so every check "computes" its expected bytes and the device passes;
+// tests/hostsan/hostsan_selftest.cpp brings a stand-in that can fail
+#if !defined(BN254_HOSTSAN_SELFTEST)
+int bn254_selftest_device(int, const std::vector<uint8_t>*, const bn254st::HostSide&, std::vector<uint8_t> got[bn254st::CK_COUNT], float gpu_ms[bn254st::MS_COUNT]) {
+  for (int k = 0; k < bn254st::CK_COUNT; k++) got[k] = bn254_selftest_expected(k);
+  for (int k = 0; k < bn254st::MS_COUNT; k++) gpu_ms[k] = 0.f;
+  return BN254_OK;
+}
+#endif
 // batches over many keys: tests/hostsan/hostsan_keys.cpp brings the file and stand-ins for its launchers; the older harness only needs the hook of bn254_groth16_vk_free
 #if defined(BN254_HOSTSAN_KEYS)
 #include "bn254_capi_keys.hip"

@@ -42,7 +42,7 @@ DevState* dev_state(const bn254_g16_pvk* pvk, int device) {
 // caller holds d.mu
 int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n) {
   int rc = check_device(device);
-  if (rc) return rc;
+  if (rc || (rc = selftest_gate(device))) return rc;
   if (!d.ready) {
     if ((rc = upload(d.k0, pvk->host.k0)) || (rc = upload(d.gtab, pvk->host.gtab)) || (rc = upload(d.dtab, pvk->host.dtab)) || (rc = upload(d.target, pvk->host.target)))
       return rc;

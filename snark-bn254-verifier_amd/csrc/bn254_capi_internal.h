@@ -279,6 +279,9 @@ struct KeySetCache {
 int check_batch_args(bool plonk, const void* pvk, const void* proofs, size_t proof_stride, const void* inputs, size_t n_public, size_t n, const void* status,
                      unsigned flags);
 int check_device(int device);
+// bn254_capi_selftest.hip: the known-answer self-test of the verdict kernels, once per process and device (include/bn254_verify.h, bn254_device_selftest).  Called after
+// check_device by everything that makes a device ready: BN254_OK once the device has passed (or BN254_SELFTEST=0), BN254_E_SELFTEST with the recorded text on one that failed
+int selftest_gate(int device);
 // a batch over a key list (bn254_capi_keys.hip): the list itself (every handle non-null, at most G16_KEYS_MAX_KEYS entries, no key above G16_KEYS_MAX_PUBLIC inputs; the
 // limits are refused with a bn254_last_diagnostic() text) -> *max_public, the largest input count; then the batch arguments against it
 int check_key_list(const bn254_g16_pvk* const* pvks, size_t n_keys, size_t* max_public);

@@ -64,7 +64,7 @@ KeySetCache<KeySet, bn254_g16_pvk>& set_cache() { static auto* c = new KeySetCac
 int ensure_set(KeySet& s, size_t n, unsigned flags) {
   const int oom = BN254_E_NOMEM;
   int rc = check_device(s.device);
-  if (rc) return rc;
+  if (rc || (rc = selftest_gate(s.device))) return rc;
   const size_t n_keys = s.list.size();
   if (!s.ready) {
     std::map<const bn254_g16_pvk*, size_t> uniq;        // handle -> its number among the distinct ones

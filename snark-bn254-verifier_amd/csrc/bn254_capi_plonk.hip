@@ -7,7 +7,7 @@
 
 int plonk_ensure_dev(const bn254_plonk_pvk* pvk, int device, PlonkDev** out) {
   int rc = check_device(device);
-  if (rc) return rc;
+  if (rc || (rc = selftest_gate(device))) return rc;
   PlonkDev& d = pvk->dev[device];
   if (!d.ready) {
     if ((rc = upload(d.tab0, pvk->tab0)) || (rc = upload(d.tab1, pvk->tab1)) || (rc = upload(d.one, pvk->one))) return rc;

@@ -138,9 +138,9 @@ int pk_check_args(const bn254_plonk_pvk* const* pvks, size_t n_keys, const void*
 // caller holds s.mu.  First use: every distinct member's own device state (plonk_ensure_dev: window tables, line tables, the parsed key, its self-test) and the
 // descriptors that point into it.
 int pk_ensure_set(PlonkKeySet& s) {
-  if (s.ready) return BN254_OK;
+  if (s.ready) return selftest_gate(s.device);      // (the device passed its self-test before the set became ready: this only reads the recorded state)
   int rc = check_device(s.device);
-  if (rc) return rc;
+  if (rc || (rc = selftest_gate(s.device))) return rc;
   std::vector<const bn254_plonk_pvk*> order;
   for (auto p : s.list) if (std::find(order.begin(), order.end(), p) == order.end()) order.push_back(p);
   // the window tables still to build must fit beside their construction scratch and leave room for contexts

@@ -173,7 +173,7 @@ int vkp_prepare_batch(const uint8_t* const* vks, const size_t* vk_lens, size_t n
     }
     return BN254_OK;
   }
-  if (!on_host) { int rc = check_device(device); if (rc) return rc; }
+  if (!on_host) { int rc = check_device(device); if (rc || (rc = selftest_gate(device))) return rc; }
   try {
     VkpDev dev;
     VkpPass pass;

@@ -297,7 +297,7 @@ hipError_t bn254_launch_plonk_stage2(const void* d_key, const uint8_t* d_proofs,
 // ---- known-answer self-test of the device stages, run once per (key, device) before the key is used there ------------------------------------------------------
 // Round 4 met a build in which k_plonk_stage1 derived a wrong first challenge from a correct SHA-256 digest; round 5 rebuilt that flag combination (FrCtx::mul_w32 inlined
 // by force, no register barrier in FrCtx::from_be32: tools/gpu_repro.sh) and the defect had MOVED -- the challenges were right, the opening check behind them rejected the
-// reference's valid fixtures (no reduced test case exists: kernels cut down from k_plonk_stage1 compute correctly).  Two source-level workarounds are
+// reference's valid fixtures (the reduced test cases are in tools/repro/, its README.md says how to build and read them).  Two source-level workarounds are
 // in; the cause inside the compiler is not known, and a deployment does not run the GPU test suite -- so the library checks THE KERNELS IT SHIPS, on THIS device, against
 // the host's compile of the same stage source (which multiplies in the 64-bit form), end to end:
 //   * a synthetic proof whose points are the key's own (on the curve), random scalars and the key's number of public inputs, with claimed[0] set to the value the opening

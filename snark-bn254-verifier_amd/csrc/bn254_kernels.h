@@ -213,6 +213,9 @@ hipError_t bn254_launch_plonk_keys_gather(const uint8_t* proofs, size_t stride, 
 hipError_t bn254_launch_plonk_keys_scatter(const uint8_t* slot_status, const uint32_t* slot_to_proof, uint32_t m, uint32_t n_proofs, uint8_t* status, hipStream_t s);
 hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const int32_t* target_one,
                                        int reject_code, hipStream_t s, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);
+// the lane form of bn254_launch_pairing2_fixed at any size (what that launcher runs above its cooperative range; the device self-test calls it at 64 items)
+hipError_t bn254_launch_pairing2_fixed_lanes(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const int32_t* target_one,
+                                             int reject_code, hipStream_t s, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join);
 // cooperative layout for small batches (bn254_coop12.hip): twelve lanes per proof (one Fp number of every Fp12 value per lane), 39 KB of LDS per
 // wavefront, the whole Miller loop / final exponentiation in one launch.  (The first generation, six lanes per proof, was retired in round 3:
 // 2.95 ms against 2.11 ms at 4096 proofs; DESIGN.md section 5.4 keeps its measurements.)

@@ -1328,12 +1328,13 @@ hipError_t bn254_launch_dbg_verdict(int form, int32_t* ws, size_t n, uint8_t* st
   else hipLaunchKernelGGL(k_f12_mul_verdict, dim3(grid), dim3(256), 0, s, ws, nn, status, (int)VE_S0, (int)VE_S2, (int)VE_S0, target, (int)BN254_ST_REJECT, (const uint32_t*)nullptr, status);
   return hipGetLastError();
 }
-// k_g16_prepare as a cooperative launch runs it, then k_coop12_miller_g16 in its store mode (no target): the GT value of every proof still pending
-// after the loader is left in VE_S0, its status byte keeps PENDING.  Keys with at most G16_WIDE_MSM_MIN_INPUTS inputs (L by the cooperative kernel itself)
+// k_g16_prepare as a cooperative launch runs it, then k_coop12_miller_g16 in its store mode (a.target null): the GT value of every proof still pending
+// after the loader is left in VE_S0, its status byte keeps PENDING; with a.target the kernel's own verdict, as bn254_launch_g16 launches it whatever BN254_COOP says.
+// Keys with at most G16_WIDE_MSM_MIN_INPUTS inputs (L by the cooperative kernel itself)
 hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_g16_prepare, dim3(grid_for(a.n)), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.n_public, (uint32_t)a.n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, 1,
                      (const uint32_t*)nullptr, (uint8_t*)nullptr);
-  return bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, 0, nullptr, s);
+  return bn254_coop12_miller_g16(a.ws, a.status, a.n, a.gtab, a.dtab, a.inputs, a.n_public, a.inputs_match_key, a.msm_tab, a.k0, 0, a.target, s);
 }
 hipError_t bn254_launch_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s) {
   unsigned g = grid_for(n);
@@ -1369,17 +1370,22 @@ hipError_t bn254_launch_dbg_g2_subgroup(const uint8_t* g2, uint8_t* o, size_t n,
 // (P_0 at VE_LX, P_1 at VE_CX; identity flags BN254_ST_LINF / BN254_ST_LINF2 in the status byte): ACCEPT or reject_code
 hipError_t bn254_launch_pairing2_fixed(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const int32_t* target_one,
                                        int reject_code, hipStream_t s, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join) {
-  unsigned grid = grid_for(n);
-  uint32_t nn = (uint32_t)n;
-  G16Prof* prof = nullptr;
-  LaunchOps ops{ws, nn, status, grid, s, {tab0, tab1, nullptr}, nullptr};
-  ops.inf_mask[0] = BN254_ST_LINF; ops.inf_mask[1] = BN254_ST_LINF2;
   static const bool coop_on = [] { const char* e = getenv("BN254_COOP"); return !e || atoi(e) != 0; }();
   static const size_t coop_fixed_max = [] { const char* e = getenv("BN254_COOP_FIXED_MAX"); return e ? (size_t)atol(e) : bn254_coop_max_proofs_fixed(); }();
   if (coop_on && n <= coop_fixed_max) {
     // small batch: the cooperative layout (bn254_coop12.hip), Miller loop of the two pairs, final exponentiation and the comparison in ONE launch
     return bn254_coop12_miller_fixed(ws, status, n, 2, tab0, tab1, target_one, reject_code, s);
   }
+  return bn254_launch_pairing2_fixed_lanes(ws, status, n, tab0, tab1, target_one, reject_code, s, aux, ev_fork, ev_join);
+}
+// the lane form of the check, whatever the size and the knobs say (the device self-test runs it at 64 items: bn254_selftest_dev.hip)
+hipError_t bn254_launch_pairing2_fixed_lanes(int32_t* ws, uint8_t* status, size_t n, const int32_t* tab0, const int32_t* tab1, const int32_t* target_one,
+                                             int reject_code, hipStream_t s, hipStream_t aux, hipEvent_t ev_fork, hipEvent_t ev_join) {
+  unsigned grid = grid_for(n);
+  uint32_t nn = (uint32_t)n;
+  G16Prof* prof = nullptr;
+  LaunchOps ops{ws, nn, status, grid, s, {tab0, tab1, nullptr}, nullptr};
+  ops.inf_mask[0] = BN254_ST_LINF; ops.inf_mask[1] = BN254_ST_LINF2;
   BN_LAUNCH(KID_VM_INIT, k_vm_init, ws, nn, (const uint8_t*)status);
   const uint8_t* kinds = step_kinds_host();
   if (aux && n <= G16_SPLIT_MAX_PROOFS) {

@@ -123,6 +123,174 @@ def u_chain():
             "operand_digits": [sign(d) * (operand[abs(d)] + 1) for d in digits]}
 
 
+# ---- built-in vectors of the device self-test (csrc/bn254_capi_selftest.hip): a 2-input Groth16 key, 64 proofs and 64 items of the two-pair check, made from the
+# trapdoors so that every status is known by construction (tests/test_selftest_cpu.py holds them against the oracle).  Python integers only, like everything above.
+ST_N = 64
+ST_ACCEPT, ST_REJECT, ST_NOT_MEMBER, ST_NOT_ON_CURVE, ST_NOT_IN_SUBGROUP, ST_PAIRING_FAILED = 1, 0, 2, 3, 4, 8
+G2_GEN = ((10857046999023057135944570762232829481370756359578518086990519993285655852781, 11559732032986387107991004021392285783925812861821192530917403151452391805634),
+          (8495653923123431417604973247489272438418190587263600148770280649306958101930, 4082367875863433681332203403145435568316851327593401208105741076214120093531))
+HALF = (P - 1) // 2
+
+
+class _Fp:
+    """the two coordinate fields behind one interface, for the affine group law below"""
+    zero, one = 0, 1
+    mul = staticmethod(lambda a, b: a * b % P)
+    add = staticmethod(lambda a, b: (a + b) % P)
+    sub = staticmethod(lambda a, b: (a - b) % P)
+    inv = staticmethod(lambda a: pow(a, -1, P))
+    small = staticmethod(lambda a, k: a * k % P)
+
+
+class _Fp2:
+    zero, one = (0, 0), (1, 0)
+    mul = staticmethod(f2mul)
+    add = staticmethod(lambda a, b: ((a[0] + b[0]) % P, (a[1] + b[1]) % P))
+    sub = staticmethod(lambda a, b: ((a[0] - b[0]) % P, (a[1] - b[1]) % P))
+    inv = staticmethod(f2inv)
+    small = staticmethod(lambda a, k: (a[0] * k % P, a[1] * k % P))
+
+
+def ec_add(F, p, q):
+    """affine addition on y^2 = x^3 + b (b does not enter); None is the identity"""
+    if p is None:
+        return q
+    if q is None:
+        return p
+    if p[0] == q[0]:
+        if F.add(p[1], q[1]) == F.zero:
+            return None
+        lam = F.mul(F.small(F.mul(p[0], p[0]), 3), F.inv(F.small(p[1], 2)))
+    else:
+        lam = F.mul(F.sub(q[1], p[1]), F.inv(F.sub(q[0], p[0])))
+    x = F.sub(F.sub(F.mul(lam, lam), p[0]), q[0])
+    return (x, F.sub(F.mul(lam, F.sub(p[0], x)), p[1]))
+
+
+def ec_mul(F, p, k):
+    acc = None
+    for bit in bin(k)[2:]:
+        acc = ec_add(F, acc, acc)
+        if bit == "1":
+            acc = ec_add(F, acc, p)
+    return acc
+
+
+def f2sqrt(a):
+    """a square root in Fp2 = Fp[i] / (i^2 + 1) by the norm method, or None"""
+    def fsqrt(v):
+        s = pow(v, (P + 1) // 4, P)
+        return s if s * s % P == v % P else None
+    n = fsqrt((a[0] * a[0] + a[1] * a[1]) % P)
+    if n is None:
+        return None
+    for sgn in (1, -1):
+        x0 = fsqrt((a[0] + sgn * n) * pow(2, -1, P) % P)
+        if x0:
+            y = (x0, a[1] * pow(2 * x0, -1, P) % P)
+            if f2mul(y, y) == (a[0] % P, a[1] % P):
+                return y
+    return None
+
+
+def selftest_vectors():
+    import hashlib
+
+    def rnd(tag, i=0, nonzero=True):
+        c = 0
+        while True:
+            v = int.from_bytes(hashlib.sha256(("bn254-selftest|%s|%d|%d" % (tag, i, c)).encode()).digest(), "big") % R_ORD
+            if v or not nonzero:
+                return v
+            c += 1
+
+    be = lambda v: v.to_bytes(32, "big")
+    G1 = (1, 2)
+    g1 = lambda k: ec_mul(_Fp, G1, k % R_ORD)
+    g2 = lambda k: ec_mul(_Fp2, G2_GEN, k % R_ORD)
+    enc_g1 = lambda p: be(p[0]) + be(p[1])
+    enc_g2 = lambda q: be(q[0][1]) + be(q[0][0]) + be(q[1][1]) + be(q[1][0])
+
+    def cmp_g1(p):
+        b = bytearray(be(p[0])); b[0] |= 0xc0 if p[1] > HALF else 0x80
+        return bytes(b)
+
+    def cmp_g2(q):      # gnark: the flag says whether y is the lexicographically larger root, by (c1, c0)
+        y = q[1]
+        large = y[1] > HALF if y[1] else y[0] > HALF
+        b = bytearray(be(q[0][1]) + be(q[0][0])); b[0] |= 0xc0 if large else 0x80
+        return bytes(b)
+
+    # the key: beta and gamma with the halves of y.c0, y.c1 different, delta with them equal, so that the reference's reading of the compressed roots (by c0 alone)
+    # and gnark's verify the same proofs (SURVEY.md Appendix D.3, as bn254_synth_groth16 samples its keys)
+    same_half = lambda q: (q[1][0] > HALF) == (q[1][1] > HALF)
+
+    def trapdoor(tag, want_same):
+        i = 0
+        while True:
+            k = rnd(tag, i); q = g2(k)
+            if same_half(q) == want_same:
+                return k, q
+            i += 1
+    alpha = rnd("alpha")
+    beta, beta2 = trapdoor("beta", False)
+    gamma, gamma2 = trapdoor("gamma", False)
+    delta, delta2 = trapdoor("delta", True)
+    kk = [rnd("k", i) for i in range(3)]
+    vk = cmp_g1(g1(alpha)) + cmp_g1(g1(beta)) + cmp_g2(beta2) + cmp_g2(gamma2) + cmp_g1(g1(delta)) + cmp_g2(delta2) + (3).to_bytes(4, "big")
+    vk += b"".join(cmp_g1(g1(k)) for k in kk) + bytes(4) + (b"\x40" + bytes(63)) * 2      # no commitments; the two points of the commitment key: the infinity flag
+    # a twist point outside the r-torsion
+    bt = f2mul((3, 0), f2inv(XI))
+    i = 0
+    while True:
+        x = (rnd("bad-x0", i, False) % P, rnd("bad-x1", i, False) % P)
+        y = f2sqrt(_Fp2.add(f2mul(f2mul(x, x), x), bt))
+        if y is not None and ec_mul(_Fp2, (x, y), R_ORD) is not None:
+            bad_b = (x, y)
+            break
+        i += 1
+    dinv = pow(delta, -1, R_ORD)
+    proofs, inputs, status = b"", b"", []
+    for i in range(ST_N):
+        a, b = rnd("a", i), rnd("b", i)
+        xs = [rnd("x", 2 * i, False), rnd("x", 2 * i + 1, False)]
+        ell = (kk[0] + xs[0] * kk[1] + xs[1] * kk[2]) % R_ORD
+        c = (a * b - alpha * beta - gamma * ell) * dinv % R_ORD
+        A, B, C = g1(a), g2(b), g1(c)
+        st = ST_ACCEPT
+        cls = (i // 8) % 5 if i % 8 == 7 else -1          # every eighth proof is corrupted, the five classes of bn254_synth_groth16 in turn
+        if cls == 0:
+            xs[0] += 1; st = ST_REJECT                     # (as a raw integer: stays below 2^256)
+        if cls == 1:
+            C = ec_add(_Fp, C, G1); st = ST_REJECT
+        if cls == 3:
+            B = bad_b; st = ST_NOT_IN_SUBGROUP
+        rec = bytearray(enc_g1(A) + enc_g2(B) + enc_g1(C))
+        if cls == 2:
+            rec[32:64] = be((A[1] + 1) % P); st = ST_NOT_ON_CURVE
+        if cls == 4:
+            rec[0:32] = b"\xff" * 32; st = ST_NOT_MEMBER
+        proofs += bytes(rec); inputs += be(xs[0]) + be(xs[1]); status.append(st)
+    assert set(status) == {ST_ACCEPT, ST_REJECT, ST_NOT_MEMBER, ST_NOT_ON_CURVE, ST_NOT_IN_SUBGROUP}
+    # the two-pair check against the key's line tables, which hold -gamma G2 and -delta G2 (csrc/bn254_host.hpp::prepare_g16, reference mode):
+    # e(a G1, -gamma G2) e(s G1, -delta G2) = 1  iff  s = -a gamma / delta
+    ident = bytes(32) + be(1)                              # the identity as the workspace holds it: x = 0, y = 1, and its flag
+    items, flags, p2 = b"", [], []
+    for i in range(ST_N):
+        a = rnd("p2", i)
+        s = (-a * gamma * dinv) % R_ORD
+        ok = i % 4 != 3
+        p0, p1 = enc_g1(g1(a)), enc_g1(g1(s if ok else s + 1))
+        fl = 0
+        if i == ST_N - 6:
+            p0, fl, ok = ident, 1, False                  # e(O, .) e(P_1, .) != 1
+        if i == ST_N - 2:
+            p0, p1, fl, ok = ident, ident, 3, True        # the empty product
+        items += p0 + p1; flags.append(fl); p2.append(ST_ACCEPT if ok else ST_PAIRING_FAILED)
+    return {"BN_ST_VK": vk, "BN_ST_PROOFS": proofs, "BN_ST_INPUTS": inputs, "BN_ST_STATUS": bytes(status), "BN_ST_PAIR2": items, "BN_ST_PAIR2_FLAGS": bytes(flags),
+            "BN_ST_PAIR2_STATUS": bytes(p2)}
+
+
 def main():
     o = []
     w = o.append
@@ -203,6 +371,18 @@ def main():
     w("static const uint32_t BN_R_WORDS[8] = {%s};" % ", ".join("0x%08xu" % ((R_ORD >> (32 * i)) & 0xffffffff) for i in range(8)))
     w("static const uint32_t BN_P_WORDS[8] = {%s};" % ", ".join("0x%08xu" % ((P >> (32 * i)) & 0xffffffff) for i in range(8)))
     w("static const uint32_t BN_P_HALF_WORDS[8] = {%s}; /* (p-1)/2 */" % ", ".join("0x%08xu" % ((((P - 1) // 2) >> (32 * i)) & 0xffffffff) for i in range(8)))
+    # the self-test's tables: seen only by the translation unit that asks for them
+    w("#if defined(BN254_SELFTEST_TABLES)")
+    w("/* Built-in vectors of the device self-test (bn254_capi_selftest.hip; include/bn254_verify.h, bn254_device_selftest): a 2-input Groth16 key in gnark's bytes,")
+    w("   %d raw proofs with their inputs and statuses (every eighth corrupted: input + 1, C + G1, A.y + 1, B outside G2, A.x >= p), and %d items P_0 | P_1 of the" % (ST_N, ST_N))
+    w("   two-pair check against the key's line tables (flags: bit t = P_t is the identity) with ACCEPT or BN254_ERR_PAIRING_FAILED. */")
+    w("#define BN_ST_N %d" % ST_N)
+    for name, data in selftest_vectors().items():
+        w("static const uint8_t %s[%d] = {" % (name, len(data)))
+        for i in range(0, len(data), 32):
+            w("  " + ",".join("0x%02x" % b for b in data[i:i + 32]) + ",")
+        w("};")
+    w("#endif")
     sys.stdout.write("\n".join(o) + "\n")
 
 
