@@ -576,6 +576,33 @@ int bn254_dbg_verdict(int form, const void* a, const void* b, const uint8_t targ
 int bn254_dbg_coop12_miller_fixed(const bn254_g16_pvk* pvk, int n_pairs, const uint8_t* g1_0, const uint8_t* g1_1, const uint8_t* identity, uint8_t* out_gt, size_t n, int device);
 int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_public, size_t n, uint8_t* out_gt, uint8_t* out_status,
                                 int device);
+/* The G1 layer of the PlonK path by value (csrc/bn254_k_msm.hip), through the product's own launchers; layouts are converted on the host.  Every argument is checked
+ * before anything is launched (BN254_E_BAD_ARG: null pointers, indices outside their lists, n = 0 or above the probe's cap, more rows than MSM_MAX_ROWS = 32, coordinates
+ * that are not canonical, digits outside the contract), and before the device is looked at.  Points are 64 bytes x | y big-endian; the identity never travels as bytes.
+ * bn254_dbg_g1_msm: ONE launch of k_g1_msm_rows (n_keys = 1) or k_g1_msm_rows_keys (n_keys > 1) over n items (at most 32 768) and the row sum after it, planned by
+ * msm_plan_build(shape, round_up(n, 64), lane_budget (0: the library's), joint_g) as the PlonK path plans its launches.
+ *    shape       shape_ints ints: n_sums | per sum n_var, n_unit, n_fixed | per sum its variable terms, unit terms, fixed terms, the fixed terms' table indices
+ *    terms       n x n_terms records of 129 bytes: point (64) | k1 (16, big-endian) | k2 (16) | scalar (32, LITTLE-endian: the eight canonical words of a fixed term) |
+ *                flag byte (bit 0: the point is the identity, bits 1 / 2: the signs of k1 / k2; a unit term's sign is bit 1).  n_terms at most 64.
+ *    bases       n_keys x n_bases curve points: the window tables of key k are built on the device from bases[k * n_bases ..] (n_bases <= 32, n_keys <= 8)
+ *    granule_key n_keys > 1: one key index per 64 items (ceil(n / 64) words)
+ *    out_mode 0  out_points receives n x n_sums points (item-major; zero bytes where out_inf says identity), out_inf n x n_sums bytes (1: identity).  Two sums are
+ *                added up by one launch of k_g1_sum_affine each (its words form holds one sum per item)
+ *    out_mode 1  the call of the second PlonK launch: both sums in one launch into workspace elements VE_LX / VE_CX with BN254_ST_LINF / _LINF2 OR-ed into `status`
+ *                (n bytes, the caller's on entry, the kernel's on return); out_points receives n x 2 points as stored: (x, y) of VE_LX, then of VE_CX; out_inf unused
+ *    info        {rows, rows with a window table, rows of sum 0, rows of sum 1, form (0 split, 1 unsplit, 2 joint rows), longest row in the planner's units}
+ * bn254_dbg_g1_sum_rows: k_g1_sum_affine alone on count_a + count_b (count_b = 0: one sum) rows of n projective points the caller places (n at most 65 536):
+ *    rows        row r, item i at index r * n + i.  format 0: 96 bytes X | Y | Z, big-endian canonical field values; format 1: 27 int32, the nine digits of X, of Y and of
+ *                Z, stored as given -- inside what the kernel declares for a row it loads: the eight low digits in [-2^28, 2^28], |value| <= 3 p per coordinate
+ *    outputs     as above (out_mode 0: n x (1 or 2) points; out_mode 1: n x 2 points and `status`)
+ * bn254_dbg_plonk_group_sums: k_plonk_group_sums on n pairs of affine points p0 / p1 (at VE_LX / VE_CX of n proofs, n at most 65 536) with the caller's n status
+ * bytes: out_p0 / out_p1 receive the ceil(n / 64) group points as stored, out_group_status the groups' status bytes.  group_verdicts != null: k_plonk_group_scatter
+ * then runs with THESE ceil(n / 64) bytes as the groups' status; status_out receives the n status bytes after it and *n_failed its count. */
+int bn254_dbg_g1_msm(const int* shape, size_t shape_ints, const uint8_t* terms, size_t n_terms, const uint8_t* bases, size_t n_bases, size_t n_keys, const unsigned* granule_key,
+                     size_t n, size_t lane_budget, int joint_g, int out_mode, uint8_t* out_points, uint8_t* out_inf, uint8_t* status, int info[6], int device);
+int bn254_dbg_g1_sum_rows(const void* rows, int format, int count_a, int count_b, size_t n, int out_mode, uint8_t* out_points, uint8_t* out_inf, uint8_t* status, int device);
+int bn254_dbg_plonk_group_sums(const uint8_t* p0, const uint8_t* p1, const uint8_t* status, size_t n, uint8_t* out_p0, uint8_t* out_p1, uint8_t* out_group_status,
+                               const uint8_t* group_verdicts, uint8_t* status_out, unsigned* n_failed, int device);
 int bn254_dbg_g2_subgroup(const uint8_t* g2, uint8_t* out_flags, size_t n, int device);                       /* 1 = in G2 (gnark's psi relation, one kernel) */
 int bn254_dbg_g2_subgroup_ate(const uint8_t* g1, const uint8_t* g2, uint8_t* out_flags, size_t n, int device); /* 1 = in G2: the product's test, from the Miller loop's final point (g1: any G1 points) */
 

@@ -654,6 +654,253 @@ int bn254_dbg_comb_mul(const uint8_t p64[64], const uint8_t x32[32], uint8_t out
   return BN254_OK;
 }
 
+// ---------------------------------------------------------------- value-level probes of the G1 layer of the PlonK path (tests/test_gpu_g1_msm_values.py)
+// k_g1_msm_rows[_keys], k_g1_sum_affine, k_plonk_group_sums / _scatter through the launchers the product calls, on data the caller places.  Every argument is
+// checked here, on the host, before the device is looked at: nothing a kernel reads -- an index, a count, a digit -- is taken on trust.
+namespace {
+enum { G1P_MAX_MSM_ITEMS = 32768, G1P_MAX_ITEMS = 65536, G1P_MAX_TERMS = 64, G1P_MAX_BASES = 32, G1P_MAX_KEYS = 8 };
+inline uint32_t g1p_be_word(const uint8_t* q) { return (uint32_t)q[0] << 24 | (uint32_t)q[1] << 16 | (uint32_t)q[2] << 8 | (uint32_t)q[3]; }
+inline uint32_t g1p_le_word(const uint8_t* q) { return (uint32_t)q[3] << 24 | (uint32_t)q[2] << 16 | (uint32_t)q[1] << 8 | (uint32_t)q[0]; }
+// what k_g1_sum_affine declares for a row it loads (BN_SETB(t, 3.0, 0.5)), exactly: the eight low digits in [-2^28, 2^28] and |value| <= 3 p.  3 p -+ v is carried
+// with floor shifts, so the sign of the number is the sign of what arrives at the top digit.
+bool g1p_row_digits_ok(const int32_t* d) {
+  for (int i = 0; i < BN_NL - 1; i++) if (d[i] < -BN_HALF || d[i] > BN_HALF) return false;
+  for (int sign = -1; sign <= 1; sign += 2) {
+    int64_t c = 0;
+    for (int i = 0; i < BN_NL - 1; i++) c = (c + 3 * (int64_t)bn_p_limb(i) + sign * (int64_t)d[i]) >> BN_LB;
+    if (c + 3 * (int64_t)bn_p_limb(BN_NL - 1) + sign * (int64_t)d[BN_NL - 1] < 0) return false;
+  }
+  return true;
+}
+// the int encoding of tests/hostsim's hs_msm_rows_joint, every index against its list; kind[t]: bit 0 variable, 1 unit, 2 fixed
+bool g1p_parse_shape(const int* q, size_t len, size_t n_terms, size_t n_bases, MsmShape& sh, uint8_t* kind) {
+  memset(&sh, 0, sizeof sh);
+  memset(kind, 0, n_terms);
+  if (len < 1 || q[0] < 1 || q[0] > 2 || len < 1 + 3 * (size_t)q[0]) return false;
+  sh.n_sums = q[0];
+  size_t need = 1 + 3 * (size_t)sh.n_sums;
+  for (int s = 0; s < sh.n_sums; s++) {
+    const int v = q[1 + 3 * s], u = q[2 + 3 * s], f = q[3 + 3 * s];
+    if (v < 0 || v > MSM_MAX_FIXED || u < 0 || u > 4 || f < 0 || f > MSM_MAX_FIXED) return false;
+    sh.n_var[s] = v; sh.n_unit[s] = u; sh.n_fixed[s] = f;
+    need += (size_t)v + (size_t)u + 2 * (size_t)f;
+  }
+  if (len != need) return false;
+  const int* p = q + 1 + 3 * sh.n_sums;
+  auto term = [&](int t, uint8_t bit) { if (t < 0 || (size_t)t >= n_terms) return false; kind[t] |= bit; return true; };
+  for (int s = 0; s < sh.n_sums; s++) {
+    for (int i = 0; i < sh.n_var[s]; i++, p++) { if (!term(*p, 1)) return false; sh.var_term[s][i] = (int8_t)*p; }
+    for (int i = 0; i < sh.n_unit[s]; i++, p++) { if (!term(*p, 2)) return false; sh.unit_term[s][i] = (int8_t)*p; }
+    for (int i = 0; i < sh.n_fixed[s]; i++, p++) { if (!term(*p, 4)) return false; sh.fixed_term[s][i] = (int8_t)*p; }
+    for (int i = 0; i < sh.n_fixed[s]; i++, p++) { if (*p < 0 || (size_t)*p >= n_bases) return false; sh.fixed_tab[s][i] = (int8_t)*p; }
+  }
+  for (size_t t = 0; t < n_terms; t++) if ((kind[t] & 4) && (kind[t] & 3)) return false;      // a record's scalar words are its GLV halves OR its fixed scalar
+  return true;
+}
+int g1p_plan_form(const MsmPlan& p) {
+  bool split = false;
+  for (int r = 0; r < p.n_rows; r++) {
+    if (p.row[r].n_joint) return 2;
+    if (p.row[r].var_term >= 0 && (p.row[r].pos_lo != 0 || p.row[r].pos_hi != 128)) split = true;
+  }
+  return split ? 0 : 1;
+}
+// n affine points of 64 bytes: every coordinate below p
+bool g1p_points_canonical(const uint8_t* p, size_t n) {
+  for (size_t i = 0; i < 2 * n; i++) if (!be_lt_p(p + 32 * i)) return false;
+  return true;
+}
+inline void g1p_words_point(uint8_t* out64, const uint32_t* w16, bool inf) {
+  if (inf) { memset(out64, 0, 64); return; }
+  words_to_be(out64, w16); words_to_be(out64 + 32, w16 + 8);
+}
+// k_g1_sum_affine over `part` (the plan's rows x 27 x n dwords on the device) in one of the two output modes of the probes
+int g1p_sum_and_fetch(const MsmPlan& plan, const int32_t* part, size_t n, int out_mode, uint8_t* out_points, uint8_t* out_inf, uint8_t* status) {
+  int rc;
+  const int n_sums = plan.count[1] > 0 ? 2 : 1;
+  if (out_mode == 0) {
+    DevBuf<uint32_t> words; DevBuf<uint8_t> inf;
+    if ((rc = words.ensure(16 * n)) || (rc = inf.ensure(n))) return rc;
+    std::vector<uint32_t> hw(16 * n); std::vector<uint8_t> hi(n);
+    for (int s = 0; s < n_sums; s++) {
+      MsmPlan one = plan;                                   // the words form of the kernel holds one sum per item: sum s alone
+      one.first[0] = plan.first[s]; one.count[0] = plan.count[s]; one.first[1] = 0; one.count[1] = 0;
+      hipError_t e = bn254_launch_g1_sum_rows(one, part, n, words, inf, nullptr, nullptr, 0, 0, 0, 0, nullptr);
+      if (e != hipSuccess) return launch_err(e, "probe");
+      HIPCK(hipDeviceSynchronize());
+      HIPCK(hipMemcpy(hw.data(), words, hw.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+      HIPCK(hipMemcpy(hi.data(), inf, n, hipMemcpyDeviceToHost));
+      for (size_t i = 0; i < n; i++) {
+        out_inf[i * n_sums + s] = hi[i];
+        g1p_words_point(out_points + 64 * (i * n_sums + s), hw.data() + 16 * i, hi[i] != 0);
+      }
+    }
+    return BN254_OK;
+  }
+  DevBuf<int32_t> ws; DevBuf<uint8_t> st, out;
+  const size_t st_bytes = (n + 3) & ~(size_t)3;             // the identity flags are OR-ed into whole status words
+  if ((rc = ws.ensure(n * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = st.ensure(st_bytes)) || (rc = out.ensure(384 * n))) return rc;
+  HIPCK(hipMemset(ws, 0, n * (size_t)G16_WS_BYTES_PER_PROOF));
+  HIPCK(hipMemset(st, 0, st_bytes));
+  HIPCK(hipMemcpy(st, status, n, hipMemcpyHostToDevice));
+  hipError_t e = bn254_launch_g1_sum_rows(plan, part, n, nullptr, nullptr, ws, st, VE_LX_ELEM, BN254_ST_LINF, VE_CX_ELEM, BN254_ST_LINF2, nullptr);   // plonk_msm's call
+  // elements 6 .. 17 as one Fp12 in the store's byte order: (VE_CX, VE_CY) first, (VE_LX, VE_LY) fourth
+  if (e == hipSuccess) e = bn254_launch_dbg_store(ws, n, (int)VE_CX_ELEM, out, 0, nullptr);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipDeviceSynchronize());
+  std::vector<uint8_t> ho(384 * n);
+  HIPCK(hipMemcpy(ho.data(), out, ho.size(), hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(status, st, n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; i++) { memcpy(out_points + 128 * i, ho.data() + 384 * i + 192, 64); memcpy(out_points + 128 * i + 64, ho.data() + 384 * i, 64); }
+  return BN254_OK;
+}
+}  // namespace
+static_assert(VE_LX_ELEM == VE_CX_ELEM + 2, "the workspace store of the G1 probes reads both points as one Fp12 at VE_CX");
+
+int bn254_dbg_g1_msm(const int* shape, size_t shape_ints, const uint8_t* terms, size_t n_terms, const uint8_t* bases, size_t n_bases, size_t n_keys, const unsigned* granule_key,
+                     size_t n, size_t lane_budget, int joint_g, int out_mode, uint8_t* out_points, uint8_t* out_inf, uint8_t* status, int info[6], int device) {
+  if (!shape || !terms || !bases || !out_points || !info || (out_mode == 0 && !out_inf) || (out_mode == 1 && !status) || (out_mode & ~1)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n == 0 || n > (size_t)G1P_MAX_MSM_ITEMS) return set_err(BN254_E_BAD_ARG, "bad argument: n is 1 .. 32768");
+  if (n_terms == 0 || n_terms > (size_t)G1P_MAX_TERMS || n_bases == 0 || n_bases > (size_t)G1P_MAX_BASES || n_keys == 0 || n_keys > (size_t)G1P_MAX_KEYS)
+    return set_err(BN254_E_BAD_ARG, "bad argument: up to 64 terms, 32 bases, 8 keys");
+  if ((lane_budget && lane_budget < 64) || joint_g < 0 || joint_g > MSM_MAX_JOINT) return set_err(BN254_E_BAD_ARG, "bad argument: lane_budget is 0 or at least 64, joint_g 0 .. 8");
+  const size_t n_pad = (n + 63) & ~(size_t)63, granules = n_pad / 64;
+  if (n_keys > 1) {
+    if (!granule_key) return set_err(BN254_E_BAD_ARG, "bad argument: a key list needs the granules' key indices");
+    for (size_t g = 0; g < granules; g++) if (granule_key[g] >= n_keys) return set_err(BN254_E_BAD_ARG, "bad argument: key index outside the list");
+  }
+  MsmShape sh;
+  uint8_t kind[G1P_MAX_TERMS];
+  if (!g1p_parse_shape(shape, shape_ints, n_terms, n_bases, sh, kind)) return set_err(BN254_E_BAD_ARG, "bad argument: shape (a count, a term index or a table index outside its list)");
+  MsmPlan plan;
+  if (!msm_plan_build(plan, sh, n_pad, lane_budget ? lane_budget : msm_lane_budget(), 0, joint_g) || plan.n_rows > MSM_MAX_ROWS)
+    return set_err(BN254_E_BAD_ARG, "bad argument: the shape needs more MSM rows than a launch has");
+  for (size_t k = 0; k < n_keys * n_bases; k++) {
+    G1Aff K; K.x = fp_from_be(bases + 64 * k); K.y = fp_from_be(bases + 64 * k + 32);
+    if (!g1p_points_canonical(bases + 64 * k, 1) || !g1_on_curve(K)) return set_err(BN254_E_BAD_ARG, "bad argument: a base is not a curve point");
+  }
+  // the records as the stage kernels leave them: MsmTerm digits and scalar words, flag bytes
+  std::vector<int32_t> ht(n * n_terms * (size_t)MSM_TERM_DWORDS, 0);
+  std::vector<uint8_t> hf(n * n_terms);
+  for (size_t k = 0; k < n * n_terms; k++) {
+    const uint8_t* e = terms + 129 * k;
+    int32_t* o = ht.data() + k * (size_t)MSM_TERM_DWORDS;
+    hf[k] = e[128];
+    if (kind[k % n_terms] & 4) { for (int w = 0; w < 8; w++) o[18 + w] = (int32_t)g1p_le_word(e + 96 + 4 * w); continue; }
+    if (!g1p_points_canonical(e, 1)) return set_err(BN254_E_BAD_ARG, "bad argument: a coordinate of a term's point is not below p");
+    fp_to_limbs(o, fp_from_be(e)); fp_to_limbs(o + BN_NL, fp_from_be(e + 32));
+    for (int w = 0; w < 4; w++) { o[18 + w] = (int32_t)g1p_be_word(e + 64 + 4 * (3 - w)); o[22 + w] = (int32_t)g1p_be_word(e + 80 + 4 * (3 - w)); }
+  }
+  info[0] = plan.n_rows; info[1] = plan.n_var_rows; info[2] = plan.count[0]; info[3] = plan.count[1]; info[4] = g1p_plan_form(plan); info[5] = msm_plan_chain(plan);
+  int rc = check_device(device);
+  if (rc) return rc;
+  DevBuf<int32_t> tabs[G1P_MAX_KEYS], d_terms, part, glv;
+  DevBuf<uint8_t> d_flags;
+  DevBuf<PlonkKeyDesc> d_desc;
+  DevBuf<uint32_t> d_gk;
+  for (size_t k = 0; k < n_keys; k++) {
+    std::vector<int32_t> pts(n_bases * 2 * BN_NL);
+    for (size_t b = 0; b < n_bases; b++) {
+      const uint8_t* q = bases + 64 * (k * n_bases + b);
+      fp_to_limbs(pts.data() + b * 2 * BN_NL, fp_from_be(q)); fp_to_limbs(pts.data() + b * 2 * BN_NL + BN_NL, fp_from_be(q + 32));
+    }
+    if ((rc = build_tables_on_device(2, pts, tabs[k]))) return rc;
+  }
+  const size_t lanes = bn254_g1_msm_scratch_lanes(plan, n);
+  if ((rc = d_terms.ensure(ht.size())) || (rc = d_flags.ensure(hf.size())) || (rc = part.ensure((size_t)plan.n_rows * 27 * n)) ||
+      (rc = glv.ensure((lanes ? lanes : 1) * (size_t)(G1_GLV_TAB_BYTES_PER_LANE / 4))))
+    return rc;
+  HIPCK(hipMemcpy(d_terms, ht.data(), ht.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(d_flags, hf.data(), hf.size(), hipMemcpyHostToDevice));
+  hipError_t e;
+  if (n_keys > 1) {
+    // the descriptors of a key set as far as this kernel reads them: the window tables
+    std::vector<PlonkKeyDesc> hd(n_keys);
+    for (size_t k = 0; k < n_keys; k++) { memset(&hd[k], 0, sizeof hd[k]); hd[k].fixed_tabs = tabs[k]; }
+    if ((rc = d_desc.ensure(n_keys)) || (rc = d_gk.ensure(granules))) return rc;
+    HIPCK(hipMemcpy(d_desc, hd.data(), n_keys * sizeof(PlonkKeyDesc), hipMemcpyHostToDevice));
+    HIPCK(hipMemcpy(d_gk, granule_key, granules * sizeof(uint32_t), hipMemcpyHostToDevice));
+    e = bn254_launch_g1_msm_rows_keys(plan, d_terms, d_flags, n, (int)n_terms, part, glv, d_desc, (uint32_t)n_keys, d_gk, nullptr);
+  } else {
+    e = bn254_launch_g1_msm_rows(plan, d_terms, d_flags, n, (int)n_terms, part, glv, tabs[0], nullptr);
+  }
+  if (e != hipSuccess) return launch_err(e, "probe");
+  return g1p_sum_and_fetch(plan, part, n, out_mode, out_points, out_inf, status);
+}
+
+int bn254_dbg_g1_sum_rows(const void* rows, int format, int count_a, int count_b, size_t n, int out_mode, uint8_t* out_points, uint8_t* out_inf, uint8_t* status, int device) {
+  if (!rows || !out_points || (format & ~1) || (out_mode & ~1) || (out_mode == 0 && !out_inf) || (out_mode == 1 && !status)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n == 0 || n > (size_t)G1P_MAX_ITEMS) return set_err(BN254_E_BAD_ARG, "bad argument: n is 1 .. 65536");
+  if (count_a < 1 || count_b < 0 || count_a > MSM_MAX_ROWS || count_b > MSM_MAX_ROWS || count_a + count_b > MSM_MAX_ROWS) return set_err(BN254_E_BAD_ARG, "bad argument: 1 .. 32 rows in all");
+  const size_t n_rows = (size_t)(count_a + count_b);
+  // to the kernel's layout: dword (r * 27 + l) * n + i
+  std::vector<int32_t> hp(n_rows * 27 * n);
+  for (size_t r = 0; r < n_rows; r++)
+    for (size_t i = 0; i < n; i++) {
+      int32_t d[27];
+      if (format) {
+        memcpy(d, (const int32_t*)rows + (r * n + i) * 27, sizeof d);
+        for (int c = 0; c < 3; c++) if (!g1p_row_digits_ok(d + BN_NL * c)) return set_err(BN254_E_BAD_ARG, "bad argument: digits outside the contract of a row (low digits within 2^28, |value| <= 3 p)");
+      } else {
+        const uint8_t* q = (const uint8_t*)rows + (r * n + i) * 96;
+        for (int c = 0; c < 3; c++) {
+          if (!be_lt_p(q + 32 * c)) return set_err(BN254_E_BAD_ARG, "bad argument: a coordinate is not below p");
+          fp_to_limbs(d + BN_NL * c, fp_from_be(q + 32 * c));
+        }
+      }
+      for (int l = 0; l < 27; l++) hp[(r * 27 + (size_t)l) * n + i] = d[l];
+    }
+  MsmPlan plan;
+  memset(&plan, 0, sizeof plan);
+  plan.n_rows = (int32_t)n_rows; plan.first[0] = 0; plan.count[0] = count_a; plan.first[1] = count_a; plan.count[1] = count_b;
+  int rc = check_device(device);
+  if (rc) return rc;
+  DevBuf<int32_t> part;
+  if ((rc = part.ensure(hp.size()))) return rc;
+  HIPCK(hipMemcpy(part, hp.data(), hp.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  return g1p_sum_and_fetch(plan, part, n, out_mode, out_points, out_inf, status);
+}
+
+int bn254_dbg_plonk_group_sums(const uint8_t* p0, const uint8_t* p1, const uint8_t* status, size_t n, uint8_t* out_p0, uint8_t* out_p1, uint8_t* out_group_status,
+                               const uint8_t* group_verdicts, uint8_t* status_out, unsigned* n_failed, int device) {
+  if (!p0 || !p1 || !status || !out_p0 || !out_p1 || !out_group_status || (group_verdicts && (!status_out || !n_failed))) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n == 0 || n > (size_t)G1P_MAX_ITEMS) return set_err(BN254_E_BAD_ARG, "bad argument: n is 1 .. 65536");
+  if (!g1p_points_canonical(p0, n) || !g1p_points_canonical(p1, n)) return set_err(BN254_E_BAD_ARG, "bad argument: a coordinate is not below p");
+  const size_t groups = (n + 63) / 64;
+  int rc = check_device(device);
+  if (rc) return rc;
+  DevBuf<int32_t> ws, gws; DevBuf<uint8_t> st, gst, in, out; DevBuf<uint32_t> fail;
+  if ((rc = ws.ensure(n * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = gws.ensure(groups * (size_t)(G16_WS_BYTES_PER_PROOF / 4))) || (rc = st.ensure(n)) || (rc = gst.ensure(groups)) ||
+      (rc = in.ensure(128 * n)) || (rc = out.ensure(384 * groups)) || (rc = fail.ensure(1)))
+    return rc;
+  HIPCK(hipMemset(ws, 0, n * (size_t)G16_WS_BYTES_PER_PROOF));
+  HIPCK(hipMemset(gws, 0, groups * (size_t)G16_WS_BYTES_PER_PROOF));
+  HIPCK(hipMemset(gst, 0xEE, groups));
+  HIPCK(hipMemcpy(in, p0, 64 * n, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(in + 64 * n, p1, 64 * n, hipMemcpyHostToDevice));
+  hipError_t e = bn254_launch_dbg_load(ws, n, st, (int)VE_LX_ELEM, in, 4, nullptr);
+  if (e == hipSuccess) e = bn254_launch_dbg_load(ws, n, st, (int)VE_CX_ELEM, in + 64 * n, 4, nullptr);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipMemcpy(st, status, n, hipMemcpyHostToDevice));      // after the loads (same stream): they set PENDING alone
+  e = bn254_launch_plonk_group_sums(ws, st, n, gws, gst, VE_LX_ELEM, BN254_ST_LINF, VE_CX_ELEM, BN254_ST_LINF2, nullptr);      // plonk_pass's call
+  if (e == hipSuccess) e = bn254_launch_dbg_store(gws, groups, (int)VE_CX_ELEM, out, 0, nullptr);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipDeviceSynchronize());
+  std::vector<uint8_t> ho(384 * groups);
+  HIPCK(hipMemcpy(ho.data(), out, ho.size(), hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(out_group_status, gst, groups, hipMemcpyDeviceToHost));
+  for (size_t g = 0; g < groups; g++) { memcpy(out_p0 + 64 * g, ho.data() + 384 * g + 192, 64); memcpy(out_p1 + 64 * g, ho.data() + 384 * g, 64); }
+  if (!group_verdicts) return BN254_OK;
+  HIPCK(hipMemcpy(gst, group_verdicts, groups, hipMemcpyHostToDevice));
+  HIPCK(hipMemset(fail, 0, sizeof(uint32_t)));
+  e = bn254_launch_plonk_group_scatter(st, n, gst, fail, nullptr);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipDeviceSynchronize());
+  HIPCK(hipMemcpy(status_out, st, n, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(n_failed, fail, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return BN254_OK;
+}
+
 // ---------------------------------------------------------------- synthetic workload generator
 size_t bn254_synth_groth16_vk_len(size_t n_public) { return 292 + 32 * (n_public + 1) + 4 + 128; }
 

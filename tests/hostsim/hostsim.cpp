@@ -12,7 +12,10 @@
 #include "../../snark-bn254-verifier_amd/csrc/bn254_rlc.h"
 #include "../../snark-bn254-verifier_amd/csrc/bn254_msm.h"
 #endif
+#include <array>
 #include <cstring>
+#include <map>
+#include <vector>
 using namespace bn254;
 
 static Fp fp_in(const uint8_t* be, int inflate) {

@@ -357,10 +357,25 @@ struct HsMsmIO {
     for (int b = 0; b < MSM_FW_BITS; b++) { const int bit = MSM_FW_BITS * w + b; if (bit < 256 && ((q[bit >> 3] >> (bit & 7)) & 1)) v |= 1u << b; }
     return v;
   }
-  G1Aff entry(int tab, int w, uint32_t d) const {   // (d + 1) 2^(MSM_FW_BITS w) base, by plain double-and-add
-    G1Aff b = g1_in(bases + 64 * (size_t)tab);
-    G1Proj bw = g1_from_affine(b);
-    for (int i = 0; i < MSM_FW_BITS * w; i++) bw = g1_dbl(bw);
+  // (d + 1) 2^(MSM_FW_BITS w) base, by plain double-and-add; 2^(MSM_FW_BITS w) base is kept per base (the tests run hundreds of items against the same bases)
+  // The memo is process-wide state shared by every HsMsmIO and is NOT thread-safe: the callers are single-threaded ctypes tests.  It only saves doublings:
+  // an entry is a function of the base's bytes alone, so clearing it or missing it changes no value.
+  const G1Proj& window_base(int tab, int w) const {
+    static std::map<std::array<uint8_t, 64>, std::vector<G1Proj>> memo;
+    std::array<uint8_t, 64> key;
+    memcpy(key.data(), bases + 64 * (size_t)tab, 64);
+    auto it = memo.find(key);
+    if (it == memo.end()) {
+      if (memo.size() >= 64) memo.clear();
+      std::vector<G1Proj> bw(MSM_FW_WINDOWS);
+      G1Proj b = g1_from_affine(g1_in(key.data()));
+      for (int k = 0; k < MSM_FW_WINDOWS; k++) { bw[k] = b; for (int i = 0; i < MSM_FW_BITS; i++) b = g1_dbl(b); }
+      it = memo.emplace(key, bw).first;
+    }
+    return it->second[w];
+  }
+  G1Aff entry(int tab, int w, uint32_t d) const {
+    const G1Proj bw = window_base(tab, w);
     G1Proj acc = g1_identity();
     for (int bit = MSM_FW_BITS; bit >= 0; bit--) { acc = g1_dbl(acc); if (((d + 1) >> bit) & 1) acc = g1_add(acc, bw); }
     G1Aff r = g1_to_affine(acc);
@@ -368,6 +383,17 @@ struct HsMsmIO {
     return r;
   }
 };
+// A row as it travels from k_g1_msm_rows to k_g1_sum_affine: msm_rows_body stores the digits of the accumulator as they are, and the sum kernel declares
+// BN_SETB(t, 3.0, 0.5) on what it loads.  The row must be inside that declaration by the tracker's own account; then it carries the DECLARED bound, so that the
+// addition the device performs is the one the tracker checks.
+static G1Proj hs_row_through_memory(G1Proj row) {
+  Fp* c[3] = {&row.x, &row.y, &row.z};
+  for (int k = 0; k < 3; k++) {
+    if (BN_VB(*c[k]) > 3.0 || BN_LBD(*c[k]) > 0.5) fp_dbg_fail("an MSM row exceeds the bound k_g1_sum_affine declares for it", BN_VB(*c[k]));
+    BN_SETB(*c[k], 3.0, 0.5);
+  }
+  return row;
+}
 int hs_msm_rows_joint(uint8_t* out, int* info, const int* shape, const uint8_t* terms, const uint8_t* bases, unsigned n_pad, unsigned lane_budget, int joint_g);
 int hs_msm_rows(uint8_t* out, int* info, const int* shape, const uint8_t* terms, const uint8_t* bases, unsigned n_pad, unsigned lane_budget) {
   return hs_msm_rows_joint(out, info, shape, terms, bases, n_pad, lane_budget, 0);
@@ -393,11 +419,32 @@ int hs_msm_rows_joint(uint8_t* out, int* info, const int* shape, const uint8_t* 
       static G1Proj store[16 * MSM_MAX_JOINT];
       HsGlvTab tab(store);
       G1Proj row = msm_row_eval(plan, r, io, tab);
-      row.x = fp_reduce(row.x); row.y = fp_reduce(row.y); row.z = fp_reduce(row.z);   // the rows travel through memory as reduced digits
-      sum = g1_add(sum, row);
+      sum = g1_add(sum, hs_row_through_memory(row));
     }
     g1_out(out + 64 * s, sum);
   }
   info[0] = plan.n_rows; info[1] = plan.n_var_rows; info[2] = msm_plan_chain(plan); info[3] = plan.count[0]; info[4] = plan.count[1];
+  return 1;
+}
+// k_g1_sum_affine on rows the caller places as raw digits (27 int32 per row: X, Y, Z as given, declared at the kernel's bound for a loaded row): lane q of lpi
+// (1 or 4) adds rows q, q + lpi, ..., then the butterfly steps of the kernel; out: the affine sum (zero = identity).  Returns 0 on a bad argument.
+int hs_g1_sum_rows_raw(uint8_t* out, const int32_t* rows, int count, int lpi) {
+  if (count < 1 || count > MSM_MAX_ROWS || (lpi != 1 && lpi != 4)) return 0;
+  G1Proj L[4];
+  for (int q = 0; q < lpi; q++) {
+    L[q] = g1_identity();
+    for (int cc = q; cc < count; cc += lpi) {
+      G1Proj t;
+      for (int l = 0; l < BN_NL; l++) { t.x.v[l] = rows[27 * cc + l]; t.y.v[l] = rows[27 * cc + 9 + l]; t.z.v[l] = rows[27 * cc + 18 + l]; }
+      BN_SETB(t.x, 3.0, 0.5); BN_SETB(t.y, 3.0, 0.5); BN_SETB(t.z, 3.0, 0.5);
+      L[q] = g1_add(L[q], t);
+    }
+  }
+  for (int m = 1; m < lpi; m <<= 1) {
+    G1Proj N[4];
+    for (int q = 0; q < lpi; q++) N[q] = g1_add(L[q], L[q ^ m]);
+    for (int q = 0; q < lpi; q++) L[q] = N[q];
+  }
+  g1_out(out, L[0]);
   return 1;
 }

@@ -7,70 +7,18 @@ import random
 
 import pytest
 
+import msm_records as M
+
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
 
 
-def _glv(L, k):
-    k1, k2 = (C.c_uint8 * 16)(), (C.c_uint8 * 16)()
-    n1, n2 = C.c_int(), C.c_int()
-    assert L.bn254_dbg_glv_decompose(int(k % R).to_bytes(32, "big"), k1, k2, C.byref(n1), C.byref(n2)) == 0
-    return bytes(k1), bytes(k2), (2 if n1.value else 0) | (4 if n2.value else 0)
-
-
-def _shape_ints(sums):
-    """sums: [(var terms, unit terms, [(fixed term, table)])]"""
-    out = [len(sums)]
-    for v, u, f in sums:
-        out += [len(v), len(u), len(f)]
-    for v, u, f in sums:
-        out += list(v) + list(u) + [t for t, _ in f] + [b for _, b in f]
-    return (C.c_int * len(out))(*out)
-
-
 def _run(hostsim, L, O, rng, sums, n_terms, n_pad, budget, zero_scalar_terms=(), identity_terms=(), joint_g=0):
-    g = O.g1_gen()
-    n_tabs = 1 + max([b for _, _, f in sums for _, b in f] + [0])
-    bases = [O.g1_mul(g, rng.randrange(1, R)) for _ in range(n_tabs)]
-    recs, want = [], []
-    kinds = {}
-    for s, (v, u, f) in enumerate(sums):
-        for t in v: kinds[t] = ("var", s, None)
-        for t in u: kinds[t] = ("unit", s, None)
-        for t, b in f: kinds[t] = ("fixed", s, b)
-    acc = [bytes(64)] * len(sums)
-
-    def add(s, pt):
-        if pt == bytes(64):
-            return
-        acc[s] = pt if acc[s] == bytes(64) else O.g1_add(acc[s], pt)
-
-    for t in range(n_terms):
-        kind, s, b = kinds.get(t, ("none", 0, None))
-        p = O.g1_mul(g, rng.randrange(1, R))
-        k = 0 if t in zero_scalar_terms else rng.choice([rng.randrange(R), rng.randrange(1 << 64), R - 1, 1, rng.randrange(R)])
-        if kind == "var":
-            k1, k2, fl = _glv(L, k)
-            if t in identity_terms:
-                recs.append(bytes(64) + k1 + k2 + bytes(32) + bytes([fl | 1]))
-            else:
-                recs.append(p + k1 + k2 + bytes(32) + bytes([fl]))
-                add(s, O.g1_mul(p, k) if k % R else bytes(64))
-        elif kind == "unit":
-            neg = rng.randrange(2)
-            recs.append(p + bytes(32) + bytes(32) + bytes([2 if neg else 0]))
-            add(s, O.g1_mul(p, R - 1) if neg else p)
-        elif kind == "fixed":
-            recs.append(bytes(64) + bytes(32) + (k % R).to_bytes(32, "little") + bytes([0]))
-            add(s, O.g1_mul(bases[b], k) if k % R else bytes(64))
-        else:
-            recs.append(bytes(129))
-    out = (C.c_uint8 * (64 * len(sums)))()
-    info = (C.c_int * 5)()
-    assert hostsim.hs_msm_rows_joint(out, info, _shape_ints(sums), b"".join(recs), b"".join(bases), n_pad, budget, joint_g) == 1
-    got = bytes(out)
+    """one item of random terms (tests/msm_records.py builds the records and the oracle's sums) through the rows of the launch hs_msm_rows_joint plans"""
+    records, bases, want = M.build_items(L, O, rng, sums, n_terms, 1, zero_scalar_terms=zero_scalar_terms, identity_terms=identity_terms)
+    got, info = M.host_sums(hostsim, sums, n_terms, records, bases, 1, n_pad, budget, joint_g)
     for s in range(len(sums)):
-        assert got[64 * s:64 * s + 64] == acc[s], (sums, n_pad, budget, s)
-    return list(info)
+        assert got[0][s] == want[0][s], (sums, n_pad, budget, s)
+    return info
 
 
 def test_msm_rows_plonk_shapes_vs_oracle(hostsim, pkg, O):
