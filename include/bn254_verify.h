@@ -654,6 +654,11 @@ int bn254_dbg_g16_plan(size_t key_inputs, int comb, size_t reserved, size_t n, s
  * count, block counts, form} -- a launch that compacts addresses slots [first, first + slots rounded up to 256) and that many / 256 block counts. */
 int bn254_dbg_g16_compact_plan(size_t key_inputs, size_t reserved, size_t n, size_t n_public, unsigned flags, int n_streams, int single_stream, uint64_t alloc[3],
                                uint64_t* out, int max_launches, int* n_launches);
+/* the launch knobs of the environment as this process read them, once (csrc/bn254_g16_plan.h::launch_knobs; host only, no device): out = {1 unless BN254_COOP=0;
+ * what BN254_MILLER_RUN_STEPS means to the four launchers that read it -- steps per launch of a Groth16 batch under one key and over a key list (-1: the plan's
+ * choice; 0, one key only: one launch per step), of PlonK's two-pair check under one key (0: one launch per operation) and over a key list; BN254_COOP_FIXED_MAX, the
+ * largest two-pair check that takes the cooperative kernel, clamped to an int} */
+int bn254_dbg_launch_knobs(int out[6]);
 /* host restatement of the count -> scan -> write step of a launch that compacts (k_g16_classify's counts, k_g16_compact_write; the scan through the function the kernel
  * runs): pending = n bytes (non-zero: the proof is still pending after the loader's final checks); slot_proof_out / slot_status_out receive n entries each,
  * *n_pending_out the length of the dense list */

@@ -2,7 +2,7 @@
 // protocol files share, the point codecs and the SP1 fixture parser, the shard plan and the status all-gather of multi-device jobs.
 // The protocols live beside it: bn254_capi_g16.hip (Groth16), bn254_capi_plonk.hip (PlonK), bn254_capi_sp1.hip (SP1 proofs from their public values),
 // bn254_capi_dbg.hip (test probes, workload generator), bn254_capi_selftest.hip (the device self-test and its gate).
-// Host orchestration only: key preparation (bn254_host.hpp), device buffers, kernel launches (bn254_kernels.hip).
+// Host orchestration only: key preparation (bn254_host.hpp), device buffers, kernel launches (the launchers of the kernel units, bn254_kernels.h).
 // There is deliberately no CPU implementation of verify here: if HIP is unusable the calls fail (BN254_E_NO_DEVICE).
 #if !defined(__HIPCC__)
 #define BN254_SELFTEST_TABLES 1      // the one-unit host build (bottom of this file) brings bn254_capi_selftest.hip, which reads the tables of bn254_constants.h
@@ -393,7 +393,7 @@ hipError_t bn254_coop12_dbg_op(int32_t*, uint8_t*, size_t, int, int, const int32
 hipError_t bn254_coop12_miller_fixed_keys(int32_t*, uint8_t*, size_t, const uint32_t*, uint32_t, const bn254::PlonkKeyDesc*, uint32_t, const int32_t*, int, hipStream_t) { return hipSuccess; }
 hipError_t bn254_coop12_miller_fixed(int32_t*, uint8_t*, size_t, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) { return hipSuccess; }
 // Without a device compiler there is no k_g16_decompress / k_g16_status_merge: the host build runs their bodies (bn254_codec.h) in place, synchronously, on
-// the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_kernels.hip.
+// the host memory such a build allocates.  hipcc builds never see these definitions; the library's launchers are in bn254_k_g16_load.hip.
 hipError_t bn254_launch_g16_decompress(const uint8_t* src, size_t stride, uint32_t n, uint8_t* raw, uint8_t* pre, hipStream_t) {
   // (the harness's batches of 2^20 proofs repeat a few records: results are kept by record, three square roots per record are not made again)
   struct Memo { uint32_t out[64]; uint8_t pre; };

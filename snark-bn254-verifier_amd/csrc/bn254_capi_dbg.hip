@@ -1,6 +1,7 @@
 // bn254_capi_dbg.hip -- the bn254_dbg_* probes of the C ABI (include/bn254_verify.h; tests and tools): device arithmetic, plans, tables, the
 // VALU peak -- and the synthetic workload generator of the bench and the tests.
 #include "bn254_capi_internal.h"
+#include <climits>
 
 extern "C" {
 
@@ -62,6 +63,17 @@ int bn254_dbg_g16_compact_plan(size_t key_inputs, size_t reserved, size_t n, siz
     }
   }
   *n_launches = k;
+  return BN254_OK;
+}
+// The launch knobs of the environment as this process read them (bn254_g16_plan.h::launch_knobs, host only): out = {BN254_COOP on, then what BN254_MILLER_RUN_STEPS
+// means to bn254_launch_g16, bn254_launch_g16_keys (-1: the plan's choice), bn254_launch_pairing2_fixed_lanes and bn254_launch_pairing2_fixed_keys, then
+// BN254_COOP_FIXED_MAX clamped to an int}
+int bn254_dbg_launch_knobs(int out[6]) {
+  if (!out) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const size_t fixed_max = knob_coop_fixed_max();
+  out[0] = knob_coop_on() ? 1 : 0;
+  out[1] = knob_run_steps_g16(); out[2] = knob_run_steps_g16_keys(); out[3] = knob_run_steps_pairing2_lanes(); out[4] = knob_run_steps_pairing2_keys();
+  out[5] = fixed_max > (size_t)INT_MAX ? INT_MAX : (int)fixed_max;
   return BN254_OK;
 }
 // The count -> scan -> write step on the host: the counts k_g16_classify writes, then for every block what k_g16_compact_write does -- the 256 partial sums of

@@ -18,8 +18,7 @@ static std::atomic<long> g_keys_coop_max{[] { long v = env_long("BN254_KEYS_COOP
 #else
 static std::atomic<long> g_keys_coop_max{0};
 #endif
-static bool keys_coop_on() { static const bool on = [] { const char* e = getenv("BN254_COOP"); return !e || atoi(e) != 0; }(); return on; }
-static int keys_form(size_t n) { return bn254::g16_keys_form(n, (size_t)g_keys_coop_max.load(std::memory_order_relaxed), keys_coop_on()); }
+static int keys_form(size_t n) { return bn254::g16_keys_form(n, (size_t)g_keys_coop_max.load(std::memory_order_relaxed), bn254::knob_coop_on()); }
 
 // A set does NOT make its members' own per-device state ready: ensure_dev builds a key's 13-bit window tables (13 MB per K point, bn254_fw.h), and a key that is only
 // used through sets must never cost that.  The set keeps, per DISTINCT handle of the list (a handle may occur many times): both line tables, K[0] and e(alpha, beta)

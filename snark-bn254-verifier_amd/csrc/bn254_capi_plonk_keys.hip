@@ -16,10 +16,7 @@ using bn254::PlonkKeyDesc;
 #define PLONK_KEYS_COOP_MAX_DEFAULT COOP12_MAX_PROOFS_FIXED
 static long pk_coop_clamp(long v) { return v > (long)COOP12_MAX_PROOFS_FIXED ? (long)COOP12_MAX_PROOFS_FIXED : v; }
 static std::atomic<long> g_pk_coop_max{[] { long v = env_long("BN254_PLONK_KEYS_COOP_MAX", (long)PLONK_KEYS_COOP_MAX_DEFAULT); return v < 0 ? (long)PLONK_KEYS_COOP_MAX_DEFAULT : pk_coop_clamp(v); }()};
-bool plonk_keys_coop_form(size_t n) {
-  static const bool coop_on = [] { const char* e = getenv("BN254_COOP"); return !e || atoi(e) != 0; }();
-  return coop_on && n <= (size_t)g_pk_coop_max.load(std::memory_order_relaxed);
-}
+bool plonk_keys_coop_form(size_t n) { return bn254::knob_coop_on() && n <= (size_t)g_pk_coop_max.load(std::memory_order_relaxed); }
 
 namespace {
 

@@ -21,6 +21,7 @@
 #include <mutex>
 #include "bn254_vm.h"
 #include "bn254_kernels.h"
+#include "bn254_launch_ops.h"   // miller_step_table
 
 namespace bn254 {
 
@@ -715,10 +716,8 @@ static const uint8_t* c12_kinds_dev() {
   int d = 0; (void)hipGetDevice(&d);
   if (d < 0 || d >= 64) return nullptr;
   if (!dev[d]) {
-    uint8_t h[BN_ATE_STEPS];
-    for (int i = 0; i < BN_ATE_STEPS; i++) h[i] = (uint8_t)miller_step_kind(i);
     if (hipMalloc((void**)&dev[d], BN_ATE_STEPS) != hipSuccess) return nullptr;
-    (void)hipMemcpy(dev[d], h, BN_ATE_STEPS, hipMemcpyHostToDevice);
+    (void)hipMemcpy(dev[d], miller_step_table().kind, BN_ATE_STEPS, hipMemcpyHostToDevice);
   }
   return dev[d];
 }

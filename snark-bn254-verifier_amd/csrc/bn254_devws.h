@@ -1,4 +1,5 @@
-// bn254_devws.h -- device-side workspace accessor shared by the kernel translation units (bn254_kernels.hip, bn254_k_miller.hip, bn254_k_rlc.hip).
+// bn254_devws.h -- device-side workspace accessor shared by the lane-kernel translation units (bn254_kernels.hip, bn254_k_g16_load.hip, bn254_k_rlc.hip,
+// bn254_k_probe.hip, bn254_k_miller.hip, bn254_k_keys.hip, bn254_k_msm.hip).
 // Workspace (bn254_vm.h element map): element e, digit l, proof i at dword (e * 9 + l) * n + i, accessed through ONE buffer descriptor: the row
 // offset (e, l) is wave-uniform and travels in an SGPR (soffset), the lane offset i * 4 is one VGPR shared by every access, so no per-access address
 // arithmetic exists and a wave-level access is one contiguous 256-byte segment (buffer_load_dword / buffer_store_dword).  Lanes past the end of the
@@ -116,9 +117,10 @@ __device__ __forceinline__ void be_field_to_words(uint32_t w[8], const uint32_t*
 __device__ __forceinline__ bool words_lt_p(const uint32_t w[8]) { return !words_ge(w, BN_P_WORDS); }
 
 // ---- every VM operation (bn254_vm.h) is its own kernel ------------------------------------------------------------------------
-// The VM programs (vm_miller_program, vm_final_exp_program) are host-compilable: the host walks them and enqueues one launch
-// per operation (~210 per batch, all asynchronous on the sub-batch's stream, so launch overhead hides behind the previous kernel
-// for any batch that matters).  No device-side function calls: each kernel gets exactly the registers it needs and no stack.
+// The VM programs (vm_miller_program, vm_final_exp_program) are host-compilable: the host walks them (LaunchOps, bn254_launch_ops.h) and
+// enqueues one launch per operation, all asynchronous on the sub-batch's stream, so launch overhead hides behind the previous kernel for
+// any batch that matters.  (The throughput form runs the Miller loop as k_miller_run launches, bn254_k_miller.hip, and walks only the final
+// exponentiation.)  No device-side function calls: each kernel gets exactly the registers it needs and no stack.
 // A wave whose 64 proofs have all failed earlier checks exits at once.
 #define VM_KERNEL_PROLOGUE()                                                                     \
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;                                           \

@@ -6,6 +6,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include "bn254_kernels.h"
 
 namespace bn254 {
@@ -51,7 +52,41 @@ inline G16Form g16_launch_form(size_t n, size_t n_public, bool inputs_match_key,
   return f;
 }
 
-// ---- compaction of a lane launch (k_g16_classify / k_g16_compact_write, bn254_kernels.hip) ----------------------------------------------
+// ---- the launch knobs of the environment ------------------------------------------------------------------------------------------------------------------
+// BN254_COOP, BN254_MILLER_RUN_STEPS, BN254_COOP_FIXED_MAX and BN254_WIDE_PER are read ONCE per process, here and nowhere else, as raw values (set_*: the variable
+// is there at all).  What a value means is each launcher's own rule: the one-line functions below, side by side.  bn254_dbg_launch_knobs shows them as the process
+// sees them.
+#define G16_MILLER_STEPS 88   // BN_ATE_STEPS (bn254_constants.h; static_asserted in bn254_kernels.hip)
+struct LaunchKnobs { bool set_coop, set_run_steps, set_coop_fixed_max, set_wide_per; int coop, run_steps, wide_per; long coop_fixed_max; };
+inline const LaunchKnobs& launch_knobs() {
+  static const LaunchKnobs knobs = [] {
+    LaunchKnobs k = {false, false, false, false, 0, 0, 0, 0};
+    if (const char* e = getenv("BN254_COOP")) { k.set_coop = true; k.coop = atoi(e); }
+    if (const char* e = getenv("BN254_MILLER_RUN_STEPS")) { k.set_run_steps = true; k.run_steps = atoi(e); }
+    if (const char* e = getenv("BN254_COOP_FIXED_MAX")) { k.set_coop_fixed_max = true; k.coop_fixed_max = atol(e); }
+    if (const char* e = getenv("BN254_WIDE_PER")) { k.set_wide_per = true; k.wide_per = atoi(e); }
+    return k;
+  }();
+  return knobs;
+}
+// BN254_COOP=0 switches every cooperative form off: the lane kernels at every size
+inline bool knob_coop_on() { const LaunchKnobs& k = launch_knobs(); return !k.set_coop || k.coop != 0; }
+// BN254_MILLER_RUN_STEPS, Groth16: the steps per k_miller_run launch handed to g16_launch_form; -1: the plan's own choice
+//   bn254_launch_g16: 0 selects the one-launch-per-step kernels (k_miller_step_dbl / _add, with k_vm_init, k_g16_subgroup and k_g16_compare as launches of their own)
+inline int knob_run_steps_g16() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps < -1 ? -1 : k.run_steps; }
+//   bn254_launch_g16_keys: only k_miller_run_keys reads the key per wavefront, so 0 is the plan's choice too
+inline int knob_run_steps_g16_keys() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps < 1 ? -1 : k.run_steps; }
+// BN254_MILLER_RUN_STEPS, PlonK's two-pair check: the steps per k_miller_run_fixed2 launch; by default the whole loop
+//   bn254_launch_pairing2_fixed_lanes: 0 selects one launch per operation (k_f12_sqr, k_f12_mul_line_fixed2)
+inline int knob_run_steps_pairing2_lanes() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps < 0 ? G16_MILLER_STEPS : k.run_steps; }
+//   bn254_launch_pairing2_fixed_keys: the one-launch-per-operation kernels read one key per launch, so 0 is the whole loop too
+inline int knob_run_steps_pairing2_keys() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps <= 0 ? G16_MILLER_STEPS : k.run_steps; }
+// BN254_COOP_FIXED_MAX: the largest two-pair check that takes the cooperative kernel (bn254_launch_pairing2_fixed)
+inline size_t knob_coop_fixed_max() { const LaunchKnobs& k = launch_knobs(); return k.set_coop_fixed_max ? (size_t)k.coop_fixed_max : (size_t)COOP12_MAX_PROOFS_FIXED; }
+// BN254_WIDE_PER (experiments): inputs per lane of the wide MSM, at least G16_WIDE_MSM_INPUTS_PER_LANE (the partial-sum buffer is sized for that many chunks); 0: the default
+inline int knob_wide_per() { const LaunchKnobs& k = launch_knobs(); return k.set_wide_per && k.wide_per >= G16_WIDE_MSM_INPUTS_PER_LANE && k.wide_per <= 256 ? k.wide_per : 0; }
+
+// ---- compaction of a lane launch (k_g16_classify / k_g16_compact_write, bn254_k_g16_load.hip) ----------------------------------------------
 // A proof the loader decides for good (a coordinate >= p, A or B off the curve) would still ride its wavefront through the Miller loop and the final
 // exponentiation.  A launch that compacts classifies first and runs k_g16_prepare and everything after it on the dense, order-preserving list of the proofs
 // still pending: slot j of the launch holds proof slot_proof[j], and the wavefronts past the list see slot status 0 and leave in their prologue.

@@ -10,6 +10,7 @@
 // inputs_match.)
 #include <hip/hip_runtime.h>
 #include "bn254_devws.h"
+#include "bn254_g16_loader.h"
 #include "bn254_keys.h"
 
 namespace bn254 {
@@ -79,13 +80,12 @@ __global__ void __launch_bounds__(256) k_keys_place(const uint32_t* __restrict__
 // ---- k_g16_prepare_keys ---------------------------------------------------------------------------------------------------------------------------------------
 // The launch covers slots [0, m) of ws / slot_status; slot_to_proof and granule_key point at the launch's first slot / granule.  live_slots: slots of the launch that
 // exist (n_slots[0] - slot0, clamped to m); every other slot, padding slots and slots whose proof index is out of range get status 0: not pending, so no later
-// kernel works on them.  The parse of A, B, C is k_g16_prepare's (bn254_kernels.hip), statement by statement.
-#define PREPK_LDS_ROW 65
+// kernel works on them.  The staging of the records and the parse of A, B, C are k_g16_prepare's (bn254_g16_loader.h).
 __global__ void __launch_bounds__(256, 2)
 k_g16_prepare_keys(const uint8_t* __restrict__ proofs, size_t stride, const uint8_t* __restrict__ inputs, size_t input_stride, uint32_t n_proofs, uint32_t m, uint32_t slot0,
                    const uint32_t* __restrict__ n_slots, const uint32_t* __restrict__ slot_to_proof, const uint32_t* __restrict__ granule_key,
                    const G16KeyDesc* __restrict__ desc, uint32_t n_keys, int32_t* ws, uint8_t* __restrict__ slot_status) {
-  __shared__ uint32_t lds[4 * 64 * PREPK_LDS_ROW];
+  __shared__ uint32_t lds[4 * 64 * PREP_LDS_ROW];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const uint32_t first = blockIdx.x * 256u + (uint32_t)wave * 64u;
   const uint32_t total = (uint32_t)__builtin_amdgcn_readfirstlane((int)n_slots[0]);
@@ -94,80 +94,24 @@ k_g16_prepare_keys(const uint8_t* __restrict__ proofs, size_t stride, const uint
   const uint32_t i = first + lane;
   uint32_t pi = wave_live ? slot_to_proof[i] : G16_KEYS_NO_PROOF;
   const bool live = pi < n_proofs;
-  uint32_t* wl = lds + wave * 64 * PREPK_LDS_ROW;
-  const bool aligned = ((((uintptr_t)proofs) | stride) & 3) == 0;
-  if (wave_live) {
-    if (aligned) {
-      // record of slot j of this wave: one 256-byte contiguous segment per load instruction, sixteen loads in flight (as k_g16_prepare), the record's index from lane j
-      for (int j0 = 0; j0 < 64; j0 += 16) {
-        uint32_t v[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) { const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)pi, j0 + u); v[u] = rec < n_proofs ? *(const uint32_t*)(proofs + (size_t)rec * stride + (size_t)lane * 4) : 0u; }
-#pragma unroll
-        for (int u = 0; u < 16; u++) wl[(j0 + u) * PREPK_LDS_ROW + lane] = v[u];
-      }
-    } else {
-      for (int j = 0; j < 64; j++) {
-        const uint32_t rec = (uint32_t)__builtin_amdgcn_readlane((int)pi, j);
-        uint32_t v = 0;
-        if (rec < n_proofs) {
-          const uint8_t* p = proofs + (size_t)rec * stride + (size_t)lane * 4;
-          v = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
-        }
-        wl[j * PREPK_LDS_ROW + lane] = v;
-      }
-    }
-  }
+  uint32_t* wl = lds + wave * 64 * PREP_LDS_ROW;
+  if (wave_live) g16_stage_records(wl, proofs, stride, n_proofs, lane, pi);      // the record of slot j of this wave: its index from lane j
   __syncthreads();
   if (!wave_live) { if (i < m) slot_status[i] = 0; return; }
   const KeyView kv = keys_view(desc, granule_key, first, n_keys);
   // padding lanes get an out-of-range lane offset: the descriptor's bounds check drops their stores
   DevWs w(ws, m, live ? i : DEAD_LANE);
-  const uint32_t* my = wl + lane * PREPK_LDS_ROW;
-  uint32_t d[8], wx[8], wy[8];
-  int err = 0;       // first error in the reference's order: A, then B (member, curve), B subgroup (the tail of k_miller_run_keys), then C
-  int err_c = 0;
+  const uint32_t* my = wl + lane * PREP_LDS_ROW;
 
-  // ---- A
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[k];
-  be_field_to_words(wx, d);
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[8 + k];
-  be_field_to_words(wy, d);
-  bool memb = words_lt_p(wx) & words_lt_p(wy);
-  G1Aff A; A.x = fp_from_words(wx); A.y = fp_from_words(wy);
-  if (!memb) err = BN254_ST_NOT_MEMBER; else if (!g1_on_curve(A)) err = BN254_ST_NOT_ON_CURVE;
+  // ---- A, then B: the first error in the reference's order -- A, then B (member, curve), B subgroup (the tail of k_miller_run_keys), then C
+  G1Aff A;
+  int err = g16_parse_a(my, A);
   w.st(VE_AX, A.x); w.st(VE_AY, A.y);
-
-  // ---- B : x.c1 | x.c0 | y.c1 | y.c0
   G2Aff B;
-  bool membb = true;
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[16 + k];
-  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.x.c1 = fp_from_words(wx);
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[24 + k];
-  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.x.c0 = fp_from_words(wx);
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[32 + k];
-  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.y.c1 = fp_from_words(wx);
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[40 + k];
-  be_field_to_words(wx, d); membb &= words_lt_p(wx); B.y.c0 = fp_from_words(wx);
-  if (err == 0) { if (!membb) err = BN254_ST_NOT_MEMBER; else if (!g2_on_curve(B)) err = BN254_ST_NOT_ON_CURVE; }
+  err = g16_parse_b(my, B, err);
   vst2(w, VE_B, B.x); vst2(w, VE_B + 2, B.y);
-
-  // ---- C
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[48 + k];
-  be_field_to_words(wx, d);
-#pragma unroll
-  for (int k = 0; k < 8; k++) d[k] = my[56 + k];
-  be_field_to_words(wy, d);
-  memb = words_lt_p(wx) & words_lt_p(wy);
-  G1Aff C; C.x = fp_from_words(wx); C.y = fp_from_words(wy);
-  if (!memb) err_c = BN254_ST_NOT_MEMBER; else if (!g1_on_curve(C)) err_c = BN254_ST_NOT_ON_CURVE;
+  G1Aff C;
+  const int err_c = g16_parse_c(my, C);
   w.st(VE_CX, C.x); w.st(VE_CY, C.y);
 
   // ---- L = K0 + sum_s x_s K_s over the KEY's inputs (the loop bound is wavefront-uniform), x_s taken as raw 256-bit integers; byte windows: 32 table additions per

@@ -1,4 +1,6 @@
-// bn254_kernels.h -- host-visible launch interface of bn254_kernels.hip (internal to the library).
+// bn254_kernels.h -- the host-visible launch interface of the kernel units (internal to the library): the launchers of bn254_kernels.hip, bn254_k_g16_load.hip,
+// bn254_k_rlc.hip, bn254_k_probe.hip, bn254_k_miller.hip, bn254_k_keys.hip, bn254_k_msm.hip, bn254_k_comb.hip and bn254_coop12.hip, their argument records and the
+// sizes both halves of the library agree on.  (What only hipcc units share -- LaunchOps, kernel declarations -- is in bn254_launch_ops.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -245,7 +247,6 @@ double bn254_measure_valu_sustained(double ms_target);   // the same kernel back
 double bn254_measure_valu_peak(int reps);   // lane-level v_mad_u64_u32 per second of the current device at four wavefronts per SIMD
 hipError_t bn254_launch_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, hipStream_t s);
 // formats of the Fp12 probes: 0 = 384 bytes (12 x 32, big-endian canonical, tower order), 1 = raw digits (12 x 9 int32 as the workspace holds them, same order)
-hipError_t bn254_launch_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, hipStream_t s);     // formats 0, 0
 hipError_t bn254_launch_dbg_fp12_op_fmt(int op, const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n, int32_t* ws, uint8_t* status, int in_format, int out_format, hipStream_t s);
 // k_dbg_load (kind 0 Fp12 bytes, 3 Fp12 raw digits -> element e; 4: G1 bytes -> e, e + 1; every kind sets the status bytes to PENDING) and the matching stores
 hipError_t bn254_launch_dbg_load(int32_t* ws, size_t n, uint8_t* status, int e, const void* src, int kind, hipStream_t s);

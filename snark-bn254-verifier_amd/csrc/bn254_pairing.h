@@ -77,7 +77,7 @@ inline bool fixed_line_table(FixedLine* out /* BN_ATE_STEPS */, const G2Aff& q) 
 
 // ---- generic Miller loop: one variable pair (pa, qb) and NF fixed pairs (affine G1 points) -----------------------
 // Used on the host (vk preparation: e(alpha, beta)), by the PlonK path and by tests; the Groth16 kernel has its own
-// loop with the same structure (bn254_kernels.hip) so that its G1 arguments can stay projective.
+// loop with the same structure (bn254_vm.h::vm_miller_run, bn254_k_miller.hip) so that its G1 arguments can stay projective.
 template <int NF>
 BN_HD Fp12 miller_loop(const G1Aff& pa, const G2Aff& qb, const G1Aff* pf, const FixedLine* const* tabs) {
   Fp12 f = fp12_one();

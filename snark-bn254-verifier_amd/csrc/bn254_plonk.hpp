@@ -5,7 +5,7 @@
 //   once per key (host)   the loader, the transcript prefix (the window tables of the key's points, plonk_table_point, are built on each device: bn254_k_comb.hip)
 //   per proof, DEVICE     everything: parsing, the Fiat-Shamir transcripts (SHA-256), BSB22 hash-to-field, the Fr arithmetic of the linearisation and the GLV
 //                         decomposition (PlonkStage1 / PlonkStage2 below, one proof per lane in csrc/bn254_k_plonk.hip), then every group operation: the two
-//                         multi-scalar multiplications as rows (bn254_msm.h, k_g1_msm_rows) and the two-pair pairing check (bn254_kernels.hip / bn254_coop12.hip)
+//                         multi-scalar multiplications as rows (bn254_msm.h, k_g1_msm_rows) and the two-pair pairing check (bn254_launch_pairing2_fixed*: bn254_kernels.hip / bn254_coop12.hip)
 // The same stage code compiles for the host: the library's known-answer self-test of the device stages, the BN254_PLONK_MARKS dumps, tools/repro and the
 // sanitizer harness of tests/hostsan run it there.  The second transcript hashes the first MSM's result, so a pass is stage 1 -> MSM -> stage 2 -> MSM -> pairing, all on one stream.
 // Nothing here is shared with oracle/: this is product code.

@@ -8,7 +8,7 @@
 // ~0.6 MB of workspace traffic per proof, all of it 4-byte-per-lane coalesced rows.
 //
 // Everything is templated on the workspace accessor W (ld/st of an Fp by element index): the kernels instantiate it with buffer
-// loads (bn254_kernels.hip: SGPR row offset + one VGPR lane offset), tests/hostsim with plain arrays, so the exact operation
+// loads (bn254_devws.h::DevWs: SGPR row offset + one VGPR lane offset), tests/hostsim with plain arrays, so the exact operation
 // sequence the GPU runs is checked against the oracle on the CPU.
 #pragma once
 #include "bn254_pairing.h"
@@ -540,7 +540,7 @@ BN_HD bool vm_f12_eq_const(W& w, int e, const int32_t* target /* 12 Fp in k-orde
 }
 
 // =======================================================================================================================================
-// Programs.  OPS is the dispatcher that decides how an operation is invoked: LaunchOps (bn254_kernels.hip) enqueues one kernel
+// Programs.  OPS is the dispatcher that decides how an operation is invoked: LaunchOps (bn254_launch_ops.h) enqueues one kernel
 // launch per operation, HostOps (tests/hostsim) calls the operation directly on plain arrays.
 // =======================================================================================================================================
 // step table of the optimal-ate loop: one entry per Miller step (BN_ATE_STEPS = 88): 0 = doubling (with f squaring),

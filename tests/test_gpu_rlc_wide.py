@@ -1,5 +1,5 @@
 """GPU tests of BN254_FLAG_RLC for keys with more than 8 public inputs: the public-input sum once per group from group scalars
-(snark-bn254-verifier_amd/csrc/bn254_rlc.h, bn254_kernels.hip: k_rlc_group_scalars, k_rlc_group_points_wide).  Every status byte equals the exact path's and
+(snark-bn254-verifier_amd/csrc/bn254_rlc.h, bn254_k_rlc.hip: k_rlc_group_scalars, k_rlc_group_points_wide).  Every status byte equals the exact path's and
 the generator's, and on a sample the oracle's; the mode really runs (rlc_state reports a fallback share)."""
 import random
 

@@ -231,7 +231,7 @@ def model_kernel(name, ins):
             weight_ranges.append((latches[0] + 1, latches[1], float(INV_SET_BITS)))
             notes.append("Fermat inversion: %d squarings + %d products" % (INV_SQUARINGS, INV_SET_BITS))
         elif name == "k_g16_msm_partial_comb":
-            # comb tables (bn254_kernels.hip): 20 columns x 16 inputs per lane; the compiler lays the column loop out as a doubling region followed
+            # comb tables (bn254_k_g16_load.hip): 20 columns x 16 inputs per lane; the compiler lays the column loop out as a doubling region followed
             # by the input loop, so the two pieces are weighted directly: 19 doublings (none in the top column), 320 table additions unless the
             # 13-bit column digit is zero
             if 2650 <= c <= 3150:

@@ -35,7 +35,7 @@ __global__ void k_fill(int32_t* tab, size_t entries) {
   }
 }
 
-// ---- today's loop (bn254_kernels.hip::k_g16_msm_partial_comb without the digit array) ------------------------------------------------------------------------------
+// ---- today's loop (bn254_k_g16_load.hip::k_g16_msm_partial_comb without the digit array) ------------------------------------------------------------------------------
 #ifndef LBW
 #define LBW 2
 #endif
