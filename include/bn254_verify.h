@@ -671,6 +671,13 @@ int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_gr
  * per launch part {first group, groups}, as the enqueue places them (at most max_parts written, *n_parts = parts) */
 int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, size_t key_inputs, int msm_form, uint64_t alloc[3],
                                 uint64_t* parts_out, int max_parts, int* n_parts);
+/* the decision of bn254_groth16_stream_overlap replayed over n_batches batches of one (key, device), host only (csrc/bn254_overlap_vote.h: the functions the enqueue
+ * itself calls, in its order -- read the measurement an earlier batch recorded, begin the batch, measure it if the question is open).  kind[b]: 0 the batch cannot be
+ * measured (it would not run two sub-batches of nearly equal size side by side); 1 it can, and its events will read timings[4 b ..] = {a0, a1, s1, e1} ms: the durations
+ * of part 0 and part 1, start and end of part 1 after the start of part 0 (overlap = (a0 + a1) / their union); 2 it can, but its timings cannot be had.  fallback:
+ * BN254_STREAM_FALLBACK (0 reports only).  out[4 b ..] = {1: the batch is a re-probe, the single_stream its chunks are planned with, state after the batch (0 open,
+ * 1 this batch is being measured, 2 settled), "one after the other" readings in a row}; ratio_out[b] = the last overlap read (-1: none yet) */
+int bn254_dbg_overlap_replay(const uint8_t* kind, const float* timings, size_t n_batches, int fallback, int* out, float* ratio_out);
 /* host compile of k_g16_decompress's body (csrc/bn254_codec.h::g16_decompress_record) over k compressed records at `stride` (>= 128): raw_out receives k raw 256-byte
  * records, pre_out k bytes (0: decompressed, 1: one of the three points did not decompress -- its raw record is then all ones) */
 int bn254_dbg_g16_decompress(const uint8_t* records, size_t stride, size_t k, uint8_t* raw_out, uint8_t* pre_out);

@@ -12,5 +12,5 @@ from .binding import (  # noqa: F401
     sp1_public_values_digest, sp1_pack_values, dbg_sp1_public_inputs, synth_groth16_for_inputs, KeySet, dbg_keys_group,
     set_keys_params, dbg_keys_plan, prepare_vks, dbg_prepare_vks, dbg_pvk_image, VK_PREPARE_STAGES, synth_plonk, synth_plonk_for_inputs,
     PlonkKeySet, dbg_plonk_keys_plan, last_diagnostic, set_plonk_keys_params, set_plonk_rlc_params, dbg_plonk_keys_knobs,
-    device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST,
+    device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST, dbg_overlap_replay,
 )

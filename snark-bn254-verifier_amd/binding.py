@@ -147,6 +147,19 @@ def dbg_rlc_wide_plan(m, n_streams=2, log2_group=5, log2_share=3, min_lanes=6553
     return {"rows": alloc[0], "digits": alloc[1], "part": alloc[2]}, [(parts[2 * i], parts[2 * i + 1]) for i in range(k.value)]
 
 
+def dbg_overlap_replay(batches, fallback=True):
+    """The stream-overlap decision over a sequence of batches, without a device (bn254_dbg_overlap_replay).  batches: per batch None (cannot be measured), "untimed"
+    (measured, timings cannot be had) or (a0, a1, s1, e1) in ms.  Returns per batch (probe_now, single_stream, state, serial votes, last ratio read)."""
+    L = lib()
+    L.bn254_dbg_overlap_replay.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.c_size_t, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    n = len(batches)
+    kind = bytes(0 if b is None else 2 if b == "untimed" else 1 for b in batches)
+    timings = (C.c_float * (4 * n))(*[x for b in batches for x in (b if isinstance(b, tuple) else (0, 0, 0, 0))])
+    out = (C.c_int * (4 * n))(); ratio = (C.c_float * n)()
+    _check(L.bn254_dbg_overlap_replay(kind, timings, n, 1 if fallback else 0, out, ratio))
+    return [(out[4 * i], out[4 * i + 1], out[4 * i + 2], out[4 * i + 3], ratio[i]) for i in range(n)]
+
+
 def dbg_rlc_wide_group(kpts, alpha, weights, live, inputs, n_public, n, log2_group=5, log2_share=0, group=0):
     """Host compile of the wide FLAG_RLC group stage (bn254_dbg_rlc_wide_group).  kpts: K_0 .. K_n_public (64-byte uncompressed each, concatenated), alpha: 64 bytes,
     weights: 16 bytes per proof (k1, k2 little-endian u64), live: n bytes, inputs: n x n_public x 32 bytes.  Returns (per group a list of n_public 32-byte scalars

@@ -101,7 +101,9 @@ int bn254_dbg_g16_compact(const uint8_t* pending, size_t n, unsigned* slot_proof
 // ... and of the group status bytes of the RLC mode for a chunk of m proofs: what the launch parts address against what a context reserved for `reserved` proofs holds
 int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, uint64_t* need, uint64_t* alloc) {
   if (!need || !alloc || m == 0 || n_streams < 1 || n_streams > 4 || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > 3) return set_err(BN254_E_BAD_ARG, "bad argument");
-  *need = g16_rlc_need(m, n_streams, log2_group, log2_share, min_lanes); *alloc = g16_rlc_alloc(reserved);
+  G16RlcChunkPlan p;
+  if (!g16_plan_rlc_chunk(p, m, n_streams, log2_group, log2_share, min_lanes)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+  *need = p.need; *alloc = g16_rlc_alloc(reserved);
   return BN254_OK;
 }
 
@@ -112,19 +114,34 @@ int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log
   if (!alloc || !n_parts || m == 0 || m > (size_t)G16_MAX_BATCH || n_streams < 1 || n_streams > 4 || log2_group < 1 || log2_group > 16 || log2_share < 0 || log2_share > 3 ||
       msm_form < 0 || msm_form > 2 || (max_parts > 0 && !parts_out))
     return set_err(BN254_E_BAD_ARG, "bad argument");
-  const G16RlcWide a = g16_rlc_wide_alloc(g16_round256(g16_rlc_wide_groups(m, n_streams, log2_group, log2_share, min_lanes)), key_inputs, msm_form);
+  G16RlcChunkPlan p;
+  if (!g16_plan_rlc_chunk(p, m, n_streams, log2_group, log2_share, min_lanes)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+  const G16RlcWide a = g16_rlc_wide_alloc(g16_round256(p.wide_groups), key_inputs, msm_form);
   alloc[0] = a.rows_bytes; alloc[1] = a.digit_bytes; alloc[2] = a.part_bytes;
-  const int parts = g16_rlc_parts(m, n_streams);
-  const size_t per = ((m + parts - 1) / parts + 255) / 256 * 256;
-  size_t off = 0; int k = 0;
-  for (int pi = 0; pi < parts; pi++) {
-    const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
-    if (lo >= hi) break;
-    const RlcPlan pl = rlc_plan((uint32_t)(hi - lo), log2_group, g16_rlc_share(hi - lo, log2_group, log2_share, min_lanes < 1 ? 1 : min_lanes));
-    if (k < max_parts) { parts_out[2 * k] = off; parts_out[2 * k + 1] = pl.groups; }
-    off += pl.groups; k++;
+  for (int k = 0; k < p.parts && k < max_parts; k++) { parts_out[2 * k] = p.part[k].wide_off; parts_out[2 * k + 1] = p.part[k].plan.groups; }
+  *n_parts = p.parts;
+  return BN254_OK;
+}
+
+// The stream-overlap decision (bn254_overlap_vote.h) replayed over the batches of one (key, device), without a device: the functions g16_enqueue_exact calls, in its
+// order, every recorded measurement there to be read by the next batch (arguments: include/bn254_verify.h)
+int bn254_dbg_overlap_replay(const uint8_t* kind, const float* timings, size_t n_batches, int fallback, int* out, float* ratio_out) {
+  if (n_batches && (!kind || !timings || !out || !ratio_out)) return set_err(BN254_E_BAD_ARG, "bad argument");
+  OvVote v;
+  size_t recorded = 0;   // the batch whose events are waiting to be read
+  for (size_t b = 0; b < n_batches; b++) {
+    if (kind[b] > 2) return set_err(BN254_E_BAD_ARG, "bad argument");
+    if (v.state == 1) {
+      const float* t = timings + 4 * recorded;
+      const float ratio = ov_ratio(t[0], t[1], t[2], t[3]);
+      ov_read(v, kind[recorded] == 1 ? &ratio : nullptr, fallback != 0);
+    }
+    const bool probe_now = ov_begin_batch(v), single_stream = v.single_stream && !probe_now;
+    if (ov_measures(v, kind[b] != 0 && !single_stream, 2, 1, 1)) { v.state = 1; recorded = b; }
+    int* o = out + 4 * b;
+    o[0] = probe_now; o[1] = single_stream; o[2] = v.state; o[3] = v.serial_votes;
+    ratio_out[b] = v.ratio;
   }
-  *n_parts = k;
   return BN254_OK;
 }
 

@@ -32,9 +32,6 @@ static long rlc_wide_pays_from(size_t n_public) {
   return g_rlc_wide_min_batch_env >= 0 ? g_rlc_wide_min_batch_env : (long)(RLC_WIDE_PAYS_FIXED + RLC_WIDE_PAYS_SCALE / (n_public ? n_public : 1));
 }
 
-#define OV_AGREE 3
-#define OV_REPROBE 256
-
 DevState* dev_state(const bn254_g16_pvk* pvk, int device) {
   std::lock_guard<std::mutex> lk(pvk->mu);
   return &pvk->dev[device];   // std::map nodes never move
@@ -74,13 +71,11 @@ int ensure_dev(const bn254_g16_pvk* pvk, DevState& d, int device, size_t n) {
   if (g_profiling.load() && !d.ev_ready) {
     for (auto& e : d.ev) if ((rc = e.ensure_timed())) return rc;
     const int cap = 1024;  // launches per sub-batch: ~720
-    auto pool = [&](std::vector<Event>& own, std::vector<hipEvent_t>& ev, std::vector<uint8_t>& kid, G16Prof& prof) -> int {
-      own.resize(2 * cap); ev.resize(2 * cap); kid.resize(cap);
-      for (int i = 0; i < 2 * cap; i++) { int r = own[i].ensure_timed(); if (r) return r; ev[i] = own[i]; }
-      prof.ev = ev.data(); prof.kid = kid.data(); prof.cap = cap;
-      return BN254_OK;
-    };
-    if ((rc = pool(d.prof_own, d.prof_ev, d.prof_kid, d.prof)) || (rc = pool(d.prof2_own, d.prof2_ev, d.prof2_kid, d.prof2))) return rc;
+    for (G16ProfPool& p : d.prof) {
+      p.own.resize(2 * cap); p.ev.resize(2 * cap); p.kid.resize(cap);
+      for (int i = 0; i < 2 * cap; i++) { if ((rc = p.own[i].ensure_timed())) return rc; p.ev[i] = p.own[i]; }
+      p.prof.ev = p.ev.data(); p.prof.kid = p.kid.data(); p.prof.cap = cap;
+    }
     d.ev_ready = true;
   }
   return BN254_OK;
@@ -167,6 +162,21 @@ int bn254_groth16_reserve(const bn254_g16_pvk* pvk, size_t n, int device) {
 
 }  // extern "C"
 
+// What both enqueue paths hand a launch part in the same way: proofs [off + lo, off + lo + count) of the batch, at `lo` in the chunk's workspace.  Each path adds what
+// differs: inputs_match_key, part_of_larger, the partial-sum buffer of a wide key, the compaction slots, the split streams
+static G16LaunchArgs g16_part_args(const bn254_g16_pvk* pvk, DevState* d, const void* d_proofs, size_t proof_stride, const void* d_inputs, size_t n_public, size_t off,
+                                   size_t lo, size_t count, void* d_status, unsigned flags) {
+  G16LaunchArgs a;
+  a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
+  a.inputs = (const uint8_t*)d_inputs + (off + lo) * n_public * 32; a.n_public = (int)n_public; a.n = count;
+  a.ws = d->ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.status = (uint8_t*)d_status + off + lo; a.msm_tab = d->msm; a.k0 = d->k0;
+  a.gtab = d->gtab; a.dtab = d->dtab; a.target = d->target;
+  a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+  a.msm_comb = pvk->host.msm_comb ? 1 : 0; a.msm_part = nullptr;
+  a.key_inputs = pvk->host.key_inputs(); a.rlc = (flags & BN254_FLAG_RLC) ? 1 : 0;
+  return a;
+}
+
 // Enqueue the exact pipeline for n proofs on `user`.  Caller holds d->mu and has called ensure_dev.
 static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* d_proofs, size_t proof_stride, const void* d_inputs,
                              size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
@@ -175,38 +185,26 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
   static const size_t chunk = [] { const char* e = getenv("BN254_CHUNK_LOG2"); int v = e ? atoi(e) : 20; if (v < 12) v = 12; if (v > 20) v = 20; return (size_t)1 << v; }();
   const int profiling = g_profiling.load();
   // the overlap of the sub-batch streams, measured on an earlier batch: read it once it is there (no waiting)
-  if (d->ov_state == 1 && hipEventQuery(d->ov_ev[1]) == hipSuccess && hipEventQuery(d->ov_ev[3]) == hipSuccess) {
+  OvVote& ov = d->ov;
+  if (ov.state == 1 && hipEventQuery(d->ov_ev[1]) == hipSuccess && hipEventQuery(d->ov_ev[3]) == hipSuccess) {
+    static const bool fallback = [] { const char* e = getenv("BN254_STREAM_FALLBACK"); return !e || atoi(e) != 0; }();
     float a0 = 0, a1 = 0, s1 = 0, e1 = 0;
-    if (hipEventElapsedTime(&a0, d->ov_ev[0], d->ov_ev[1]) == hipSuccess && hipEventElapsedTime(&a1, d->ov_ev[2], d->ov_ev[3]) == hipSuccess &&
-        hipEventElapsedTime(&s1, d->ov_ev[0], d->ov_ev[2]) == hipSuccess && hipEventElapsedTime(&e1, d->ov_ev[0], d->ov_ev[3]) == hipSuccess) {
-      const float lo_ = s1 < 0 ? s1 : 0, hi_ = e1 > a0 ? e1 : a0;
-      d->ov_ratio = (a0 + a1) / (hi_ - lo_ > 1e-6f ? hi_ - lo_ : 1e-6f);
-      static const bool fallback = [] { const char* e = getenv("BN254_STREAM_FALLBACK"); return !e || atoi(e) != 0; }();
-      if (d->ov_ratio < 1.15f) {
-        d->ov_serial_votes++;
-        if (d->ov_serial_votes >= OV_AGREE || d->ov_probe) {
-          d->single_stream = fallback;
-          d->diag = "the two sub-batch streams of a Groth16 batch ran one after the other on this device (overlap " + std::to_string(d->ov_ratio) + ", " +
-                    std::to_string(d->ov_serial_votes) + " measurements in a row): the process's streams share a hardware queue -- give it more queues (GPU_MAX_HW_QUEUES, read when the HIP runtime "
-                    "initialises; INTEGRATION.md)" + (fallback ? "; using one sub-batch per launch, re-measured every " + std::to_string(OV_REPROBE) + " batches" : "");
-        }
-      } else {
-        d->ov_serial_votes = 0;
-        if (d->single_stream) d->diag = "the sub-batch streams overlap again (" + std::to_string(d->ov_ratio) + "): back to two sub-batches side by side";
-        d->single_stream = false;
-      }
-      // keep measuring until the question is settled either way: OV_AGREE agreeing answers
-      d->ov_state = (d->ov_serial_votes > 0 && d->ov_serial_votes < OV_AGREE && !d->single_stream) ? 0 : 2;
-    } else d->ov_state = 2;
-    d->ov_probe = false;
+    const bool timed = hipEventElapsedTime(&a0, d->ov_ev[0], d->ov_ev[1]) == hipSuccess && hipEventElapsedTime(&a1, d->ov_ev[2], d->ov_ev[3]) == hipSuccess &&
+                       hipEventElapsedTime(&s1, d->ov_ev[0], d->ov_ev[2]) == hipSuccess && hipEventElapsedTime(&e1, d->ov_ev[0], d->ov_ev[3]) == hipSuccess;
+    const float ratio = timed ? ov_ratio(a0, a1, s1, e1) : 0.f;
+    const OvChange change = ov_read(ov, timed ? &ratio : nullptr, fallback);
+    if (change == OV_SERIALISED)
+      ov.diag = "the two sub-batch streams of a Groth16 batch ran one after the other on this device (overlap " + std::to_string(ov.ratio) + ", " +
+                std::to_string(ov.serial_votes) + " measurements in a row): the process's streams share a hardware queue -- give it more queues (GPU_MAX_HW_QUEUES, read when the HIP runtime "
+                "initialises; INTEGRATION.md)" + (fallback ? "; using one sub-batch per launch, re-measured every " + std::to_string(OV_REPROBE) + " batches" : "");
+    else if (change == OV_RESTORED) ov.diag = "the sub-batch streams overlap again (" + std::to_string(ov.ratio) + "): back to two sub-batches side by side";
   }
-  // on one sub-batch per launch: every OV_REPROBE-th batch tries two streams again and is measured
-  bool probe_now = false;
-  if (d->single_stream && d->ov_state == 2 && ++d->ov_batches % OV_REPROBE == 0) { probe_now = true; d->ov_probe = true; d->ov_state = 0; }
+  const bool probe_now = ov_begin_batch(ov);                            // a re-probe runs two streams again and is measured
+  const bool single_stream = ov.single_stream && !probe_now;
   for (size_t off = 0; off < n; off += chunk) {
     size_t m = n - off < chunk ? n - off : chunk;
     G16ChunkPlan plan;
-    if (!g16_plan_chunk(plan, m, pvk->host.key_inputs(), n_public, n_streams, d->single_stream && !probe_now)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    if (!g16_plan_chunk(plan, m, pvk->host.key_inputs(), n_public, n_streams, single_stream)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
     const bool wide = plan.wide, concurrent = plan.concurrent, split_small = plan.split_small;
     const int parts = plan.parts;
     // the buffers were sized by ensure_dev (bn254_groth16_reserve or the entry point itself): this path only enqueues, after checking the plan against them
@@ -215,30 +213,21 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
       if (plan.part[pi].count > d->msm_part_cap) return set_err(BN254_E_BAD_ARG, "workspace of a key with many public inputs is smaller than the batch: bn254_groth16_reserve first");
     int rc;
     if ((rc = concurrent ? parts_fork(*d, user, parts) : split_small ? ensure_aux(*d, 2) : BN254_OK)) return rc;
-    // the first two sub-batches of a batch that runs several, while the question is open -- and only when the two are of (nearly) equal size: a short second part
-    // beside a long first one reads as "no overlap" whatever the queues do
-    const bool measure_overlap = concurrent && parts >= 2 && d->ov_state == 0 && plan.part[1].count * 10 >= plan.part[0].count * 9;
+    const bool measure_overlap = ov_measures(ov, concurrent, parts, plan.part[0].count, parts >= 2 ? plan.part[1].count : 0);
     if (measure_overlap) for (auto& e : d->ov_ev) if ((rc = e.ensure_timed())) return rc;
     for (int pi = 0; pi < parts; pi++) {
-      const size_t lo = plan.part[pi].first, hi = lo + plan.part[pi].count;
+      const size_t lo = plan.part[pi].first;
       hipStream_t st;
       if ((rc = part_begin(*d, user, concurrent, pi, &st))) return rc;
       if (measure_overlap && pi < 2) HIPCK(hipEventRecord(d->ov_ev[2 * pi], st));
-      G16LaunchArgs a;
-      a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
-      a.inputs = (const uint8_t*)d_inputs + (off + lo) * n_public * 32; a.n_public = (int)n_public; a.n = hi - lo;
-      a.ws = d->ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.status = (uint8_t*)d_status + off + lo; a.msm_tab = d->msm; a.k0 = d->k0;
-      a.gtab = d->gtab; a.dtab = d->dtab; a.target = d->target;
+      G16LaunchArgs a = g16_part_args(pvk, d, d_proofs, proof_stride, d_inputs, n_public, off, lo, plan.part[pi].count, d_status, flags);
       a.inputs_match_key = pvk->host.inputs_match(n_public) ? 1 : 0;
-      a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
       a.part_of_larger = parts > 1 ? 1 : 0;
-      a.msm_part = wide ? (int32_t*)d->msm_part : nullptr;
-      a.msm_comb = pvk->host.msm_comb ? 1 : 0;
-      a.msm_digits = (wide && pvk->host.msm_comb) ? (uint16_t*)(d->msm_part + d->msm_chunks * 27 * d->msm_part_cap) : nullptr;
+      if (wide) a.msm_part = (int32_t*)d->msm_part;
+      if (wide && pvk->host.msm_comb) a.msm_digits = (uint16_t*)(d->msm_part + d->msm_chunks * 27 * d->msm_part_cap);
       // the slots of a launch that compacts (bn254_launch_g16 decides with g16_compacts, from the form it takes): the part's share of the three arrays, at its first
       // proof like its share of the workspace.  The context of a key that may compact holds them for as many proofs as its workspace (ensure_dev): a smaller one is a
       // sizing error, not a reason to run without compaction
-      a.key_inputs = pvk->host.key_inputs(); a.rlc = (flags & BN254_FLAG_RLC) ? 1 : 0;
       if (g16_key_may_compact(a.key_inputs)) {
         if (m > d->compact_cap) return set_err(BN254_E_BAD_ARG, "slot arrays smaller than the batch: bn254_groth16_reserve first");
         const G16CompactAlloc ca = g16_compact_alloc(d->compact_cap, a.key_inputs);
@@ -250,33 +239,34 @@ static int g16_enqueue_exact(const bn254_g16_pvk* pvk, DevState* d, const void* 
         a.split_streams[0] = d->aux[0]; a.split_streams[1] = d->aux[1];
         a.split_ev[0] = d->fork_ev; a.split_ev[1] = d->join_ev[1]; a.split_ev[2] = d->join_ev[2];
       }
-      // the events bracket the kernels of the LAST chunk only (one chunk for n <= 2^20)
-      const bool prof_this = profiling && d->ev_ready && pi == 0;
-      // mode 1: the event pairs of THIS batch; mode 2: the pairs accumulate over the batches enqueued since the last call of a profiling setter (a caller that
-      // times many back-to-back batches reads them once at the end instead of synchronising with every batch; a full pool simply stops recording)
-      const unsigned epoch = g_prof_epoch.load();
-      const bool keep = profiling == 2 && d->prof_epoch == epoch && d->prof.used > 0;
-      if (prof_this) {
-        d->prof.mask = g_prof_mask.load(); d->prof_n = a.n; d->prof_epoch = epoch;
-        if (!keep) { d->prof.used = 0; d->prof2.used = 0; d->prof2_used = false; }
+      // the first two parts record per-launch event pairs, each into its pool; the phase events bracket the kernels of part 0 of the LAST chunk only (one chunk
+      // for n <= 2^20).  Mode 1: the event pairs of THIS batch; mode 2: the pairs accumulate over the batches enqueued since the last call of a profiling setter (a
+      // caller that times many back-to-back batches reads them once at the end instead of synchronising with every batch; a full pool simply stops recording)
+      G16Prof* prof = profiling && d->ev_ready && pi < 2 ? &d->prof[pi].prof : nullptr;
+      if (prof) {
+        const unsigned epoch = g_prof_epoch.load();
+        const bool keep = profiling == 2 && d->prof_epoch == epoch && d->prof[0].prof.used > 0;
+        prof->mask = g_prof_mask.load();
+        if (!keep) prof->used = 0;
+        if (pi == 0) { d->prof_n = a.n; d->prof_epoch = epoch; if (!keep) d->prof[1].prof.used = 0; }
+        d->prof2_used = pi == 1 || (keep && d->prof2_used);
       }
-      const bool prof_second = profiling && d->ev_ready && pi == 1;
-      if (prof_second) { d->prof2.mask = g_prof_mask.load(); if (!keep) d->prof2.used = 0; d->prof2_used = true; }
       hipEvent_t phase_ev[5];
       for (int k = 0; k < 5; k++) phase_ev[k] = d->ev[k];
-      hipError_t e = bn254_launch_g16(a, st, prof_this ? phase_ev : nullptr, prof_this ? &d->prof : (prof_second ? &d->prof2 : nullptr));
+      hipError_t e = bn254_launch_g16(a, st, prof && pi == 0 ? phase_ev : nullptr, prof);
       if (e != hipSuccess) return launch_err(e, nullptr);
       if (measure_overlap && pi < 2) HIPCK(hipEventRecord(d->ov_ev[2 * pi + 1], st));
       if ((rc = part_join(*d, user, concurrent, pi, parts, st))) return rc;
     }
-    if (measure_overlap) d->ov_state = 1;
+    if (measure_overlap) ov.state = 1;
   }
   d->ev_recorded = profiling && d->ev_ready;
   return BN254_OK;
 }
 
 // ---- BN254_FLAG_RLC (bn254_rlc.h): first pass in groups, exact second pass over the proofs of groups that failed -----------------------------
-static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_public, size_t wide_groups) {
+// n: proofs of the chunk; plan: its launch parts (the wide buffers hold plan.wide_groups groups)
+static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_public, const G16RlcChunkPlan& plan) {
   RlcDev& r = d->rlc;
   int rc;
   if (!r.ready) {
@@ -294,9 +284,9 @@ static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_
     if ((rc = r.grp_status.ensure(cap)) || (rc = r.idx.ensure(cap)) || (rc = r.h_status.ensure(cap)) || (rc = r.h_idx.ensure(cap))) return rc;
     r.grp_cap = n;
   }
-  if (n_public > (size_t)RLC_MAX_PUBLIC && wide_groups > r.wide_cap) {   // likewise, for wide_cap groups
+  if (n_public > (size_t)RLC_MAX_PUBLIC && plan.wide_groups > r.wide_cap) {   // likewise, for wide_cap groups
     r.wide_cap = 0;
-    const size_t cap = g16_round256(wide_groups);
+    const size_t cap = g16_round256(plan.wide_groups);
     const G16RlcWide a = g16_rlc_wide_alloc(cap, n_public, g16_table_form(pvk->host));
     if ((rc = r.grp_rows.ensure(a.rows_bytes)) || (a.digit_bytes && (rc = r.grp_digits.ensure((a.digit_bytes + 1) / 2))) || (a.part_bytes && (rc = r.grp_part.ensure((a.part_bytes + 3) / 4))))
       return rc;
@@ -317,50 +307,37 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
   const size_t chunk = G16_MAX_BATCH;
   for (size_t off = 0; off < n; off += chunk) {
     const size_t m = n - off < chunk ? n - off : chunk;
-    const long ml0 = g_rlc_share_min_lanes.load();
-    const size_t min_lanes = ml0 < 1 ? 1 : (size_t)ml0;
+    // ONE plan per chunk (and one reading of the knob: bn254_set_rlc_params may run beside this call): what rlc_ensure sizes for is what the parts address
+    G16RlcChunkPlan plan;
+    const long ml = g_rlc_share_min_lanes.load();
+    if (!g16_plan_rlc_chunk(plan, m, n_streams, log2_group, log2_share_env, ml < 1 ? 1 : (size_t)ml)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
     const bool wide = n_public > (size_t)RLC_MAX_PUBLIC;
-    int rc = rlc_ensure(pvk, d, m, n_public, wide ? g16_rlc_wide_groups(m, n_streams, log2_group, log2_share_env, min_lanes) : 0);
+    int rc = rlc_ensure(pvk, d, m, n_public, plan);
     if (rc) return rc;
     RlcDev& r = d->rlc;
-    const int parts = g16_rlc_parts(m, n_streams);
-    if (g16_rlc_need(m, n_streams, log2_group, log2_share_env, min_lanes) > g16_rlc_alloc(r.grp_cap)) return set_err(BN254_E_HIP, "RLC group buffer smaller than the batch (internal sizing error)");
-    const int msm_form = g16_table_form(pvk->host);
+    if (plan.need > g16_rlc_alloc(r.grp_cap)) return set_err(BN254_E_HIP, "RLC group buffer smaller than the batch (internal sizing error)");
+    if (wide && plan.wide_groups > r.wide_cap) return set_err(BN254_E_HIP, "RLC group scalar buffer smaller than the batch (internal sizing error)");
+    const int msm_form = g16_table_form(pvk->host), parts = plan.parts;
     const size_t chunks_w = (n_public + G16_WIDE_MSM_INPUTS_PER_LANE - 1) / G16_WIDE_MSM_INPUTS_PER_LANE;
-    size_t wide_off = 0;   // groups of the parts before this one (bn254_g16_plan.h::g16_rlc_wide_groups)
     const bool concurrent = parts > 1;
     if (concurrent && (rc = parts_fork(*d, user, parts))) return rc;
-    const size_t per = ((m + parts - 1) / parts + 255) / 256 * 256;
-    size_t grp_off = 0;
     for (int pi = 0; pi < parts; pi++) {
-      const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
-      if (lo >= hi) break;
+      const G16RlcPart& q = plan.part[pi];
       hipStream_t st;
       if ((rc = part_begin(*d, user, concurrent, pi, &st))) return rc;
-      G16LaunchArgs a;
-      a.proofs = (const uint8_t*)d_proofs + (off + lo) * proof_stride; a.stride = proof_stride;
-      a.inputs = (const uint8_t*)d_inputs + (off + lo) * n_public * 32; a.n_public = (int)n_public; a.n = hi - lo;
-      a.ws = d->ws + lo * (size_t)(G16_WS_BYTES_PER_PROOF / 4); a.status = (uint8_t*)d_status + off + lo; a.msm_tab = d->msm; a.k0 = d->k0;
-      a.gtab = d->gtab; a.dtab = d->dtab; a.target = d->target;
+      G16LaunchArgs a = g16_part_args(pvk, d, d_proofs, proof_stride, d_inputs, n_public, off, q.first, q.count, d_status, flags);
       a.inputs_match_key = 1;
-      a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
-      a.msm_part = nullptr;
       RlcLaunchArgs ra;
       memcpy(ra.key, key, sizeof key);
-      ra.counter_base = (uint32_t)(off + lo);
-      // sharing needs enough lanes to fill the GPU; small parts keep one proof per lane
-      const long ml = g_rlc_share_min_lanes.load();
-      const int log2_share = g16_rlc_share(a.n, log2_group, log2_share_env, ml < 1 ? 1 : (size_t)ml);
-      ra.plan = rlc_plan((uint32_t)a.n, log2_group, log2_share);
-      ra.grp_status = r.grp_status + grp_off; grp_off += ((size_t)ra.plan.groups + 255) / 256 * 256;
+      ra.counter_base = (uint32_t)(off + q.first);
+      ra.plan = q.plan;
+      ra.grp_status = r.grp_status + q.grp_off;
       ra.btab = r.btab; ra.rlc_tab = r.tab; ra.one = r.one;
       if (wide) {
-        if (wide_off + ra.plan.groups > r.wide_cap) return set_err(BN254_E_HIP, "RLC group scalar buffer smaller than the batch (internal sizing error)");
-        ra.grp_rows = r.grp_rows + wide_off * n_public * 32;
-        ra.grp_digits = r.grp_digits ? r.grp_digits + wide_off * (size_t)G16_COMB_COLS * n_public : nullptr;
-        ra.grp_part = r.grp_part ? r.grp_part + wide_off * chunks_w * 27 : nullptr;
+        ra.grp_rows = r.grp_rows + q.wide_off * n_public * 32;
+        ra.grp_digits = r.grp_digits ? r.grp_digits + q.wide_off * (size_t)G16_COMB_COLS * n_public : nullptr;
+        ra.grp_part = r.grp_part ? r.grp_part + q.wide_off * chunks_w * 27 : nullptr;
         ra.msm_form = msm_form;
-        wide_off += ra.plan.groups;
       }
       hipError_t e = bn254_launch_g16_rlc(a, ra, st);
       if (e != hipSuccess) return launch_err(e, "rlc");
@@ -525,9 +502,9 @@ int bn254_groth16_stream_overlap(const bn254_g16_pvk* pvk, int device, float* ov
   if (!pvk || !overlap) return set_err(BN254_E_BAD_ARG, "bad argument");
   DevState* d = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(d->mu);
-  *overlap = d->ov_ratio;            // -1 until the first measurement has been read
-  if (single_stream) *single_stream = d->single_stream ? 1 : 0;
-  g_diag = d->diag;                  // the explanation belongs to the (key, device); the caller's thread receives it here
+  *overlap = d->ov.ratio;            // -1 until the first measurement has been read
+  if (single_stream) *single_stream = d->ov.single_stream ? 1 : 0;
+  g_diag = d->ov.diag;               // the explanation belongs to the (key, device); the caller's thread receives it here
   return BN254_OK;
 }
 
@@ -542,52 +519,34 @@ int bn254_groth16_last_kernel_ms(const bn254_g16_pvk* pvk, int device, float ms[
   return BN254_OK;
 }
 
-int bn254_groth16_kernel_profile(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], size_t* proofs_per_launch) {
-  if (!pvk || !launches || !total_ms) return set_err(BN254_E_BAD_ARG, "bad argument");
-  DevState* dp = dev_state(pvk, device);
-  std::lock_guard<std::mutex> lk(dp->mu);
-  DevState& d = *dp;
-  if (!d.ev_recorded) return set_err(BN254_E_BAD_ARG, "no profiled batch on this device");
-  HIPCK(hipSetDevice(device));
-  for (int k = 0; k < KID_COUNT; k++) { launches[k] = 0; total_ms[k] = 0.f; }
-  for (int i = 0; i < d.prof.used; i++) {
-    HIPCK(hipEventSynchronize(d.prof.ev[2 * i + 1]));
-    float ms = 0.f;
-    HIPCK(hipEventElapsedTime(&ms, d.prof.ev[2 * i], d.prof.ev[2 * i + 1]));
-    launches[d.prof.kid[i]]++; total_ms[d.prof.kid[i]] += ms;
-  }
-  if (proofs_per_launch) *proofs_per_launch = d.prof_n;
-  return BN254_OK;
-}
+}  // extern "C"
 
-// Launches, summed durations AND the union of the launch intervals per kernel kind over the first TWO sub-batches of the last profiled batch (they
-// run on two streams side by side).  union_ms[k] = length of the union of the intervals [start, end] of every launch of kind k, on a common time
-// base (HIP events of both streams against the first sub-batch's first event): for two streams that run the same kernel at the same time it is
-// about one launch's duration, for launches that happen to run one after the other it is the sum -- either way "work of all those launches / union"
-// is the rate the GPU delivered while that kernel kind was running.
-int bn254_groth16_kernel_profile_all(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], float union_ms[], size_t* proofs_per_launch) {
-  if (!pvk || !launches || !total_ms || !union_ms) return set_err(BN254_E_BAD_ARG, "bad argument");
+// The per-launch event pairs of the last profiled batch: launches and summed durations per kernel kind.  union_ms == nullptr: the first sub-batch alone, each launch
+// from its own pair of events.  Otherwise the first TWO sub-batches (they run on two streams side by side), every launch as an interval [start, end] on a common
+// time base (the first sub-batch's first event), and union_ms[k] = the length of the union of the intervals of kind k: for two streams that run the same kernel at
+// the same time about one launch's duration, for launches that happen to run one after the other the sum -- either way "work of all those launches / union" is the
+// rate the GPU delivered while that kernel kind was running.
+static int g16_read_profile(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], float union_ms[], size_t* proofs_per_launch) {
   DevState* dp = dev_state(pvk, device);
   std::lock_guard<std::mutex> lk(dp->mu);
   DevState& d = *dp;
-  if (!d.ev_recorded || d.prof.used == 0) return set_err(BN254_E_BAD_ARG, "no profiled batch on this device");
+  if (!d.ev_recorded || (union_ms && d.prof[0].prof.used == 0)) return set_err(BN254_E_BAD_ARG, "no profiled batch on this device");
   HIPCK(hipSetDevice(device));
   std::vector<std::vector<std::pair<float, float>>> iv(KID_COUNT);
-  for (int k = 0; k < KID_COUNT; k++) { launches[k] = 0; total_ms[k] = 0.f; union_ms[k] = 0.f; }
-  const hipEvent_t ref = d.prof.ev[0];
-  const G16Prof* ps[2] = {&d.prof, d.prof2_used ? &d.prof2 : nullptr};
-  for (const G16Prof* p : ps) {
-    if (!p) continue;
-    for (int i = 0; i < p->used; i++) {
-      HIPCK(hipEventSynchronize(p->ev[2 * i + 1]));
+  for (int k = 0; k < KID_COUNT; k++) { launches[k] = 0; total_ms[k] = 0.f; if (union_ms) union_ms[k] = 0.f; }
+  const int pools = union_ms && d.prof2_used ? 2 : 1;
+  for (int pi = 0; pi < pools; pi++) {
+    const G16Prof& p = d.prof[pi].prof;
+    for (int i = 0; i < p.used; i++) {
+      HIPCK(hipEventSynchronize(p.ev[2 * i + 1]));
       float a = 0.f, b = 0.f;
-      HIPCK(hipEventElapsedTime(&a, ref, p->ev[2 * i]));
-      HIPCK(hipEventElapsedTime(&b, ref, p->ev[2 * i + 1]));
-      launches[p->kid[i]]++; total_ms[p->kid[i]] += b - a;
-      iv[p->kid[i]].push_back({a, b});
+      if (union_ms) HIPCK(hipEventElapsedTime(&a, d.prof[0].prof.ev[0], p.ev[2 * i]));
+      HIPCK(hipEventElapsedTime(&b, union_ms ? d.prof[0].prof.ev[0] : p.ev[2 * i], p.ev[2 * i + 1]));
+      launches[p.kid[i]]++; total_ms[p.kid[i]] += b - a;
+      if (union_ms) iv[p.kid[i]].push_back({a, b});
     }
   }
-  for (int k = 0; k < KID_COUNT; k++) {
+  for (int k = 0; union_ms && k < KID_COUNT; k++) {
     auto& v = iv[k];
     std::sort(v.begin(), v.end());
     float cur_lo = 0.f, cur_hi = 0.f; bool open = false;
@@ -600,6 +559,17 @@ int bn254_groth16_kernel_profile_all(const bn254_g16_pvk* pvk, int device, unsig
   }
   if (proofs_per_launch) *proofs_per_launch = d.prof_n;
   return BN254_OK;
+}
+
+extern "C" {
+
+int bn254_groth16_kernel_profile(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], size_t* proofs_per_launch) {
+  if (!pvk || !launches || !total_ms) return set_err(BN254_E_BAD_ARG, "bad argument");
+  return g16_read_profile(pvk, device, launches, total_ms, nullptr, proofs_per_launch);
+}
+int bn254_groth16_kernel_profile_all(const bn254_g16_pvk* pvk, int device, unsigned launches[], float total_ms[], float union_ms[], size_t* proofs_per_launch) {
+  if (!pvk || !launches || !total_ms || !union_ms) return set_err(BN254_E_BAD_ARG, "bad argument");
+  return g16_read_profile(pvk, device, launches, total_ms, union_ms, proofs_per_launch);
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include "bn254_plonk.hpp"
 #include "bn254_rlc.h"
 #include "bn254_g16_plan.h"
+#include "bn254_overlap_vote.h"
 #include "bn254_keys.h"
 #include <sys/random.h>
 #include <atomic>
@@ -75,6 +76,8 @@ struct RlcDev {
   bool have_obs = false; float fb_share = 0.f; unsigned bypassed = 0, bypassed_total = 0;
 };
 
+// per-launch timing of one sub-batch: `own` owns the events, `ev` is the array the launcher records into (prof.ev), `kid` the kind of each pair (prof.kid)
+struct G16ProfPool { std::vector<Event> own; std::vector<hipEvent_t> ev; std::vector<uint8_t> kid; G16Prof prof{0, nullptr, nullptr, 0, 0}; };
 
 // Per (key, device) state.  `mu` serialises everything that touches it: uploads, (re)allocation and the enqueue of a batch.  The
 // workspace and the staging buffers are shared by all batches against this key on this device, so a batch first waits (on the GPU:
@@ -97,10 +100,9 @@ struct DevState {
   // stream of a process shares the runtime's few hardware queues (four by default), and a copy stream that lands on the queue of a busy compute
   // stream waits behind its kernels (measured: 3 GB/s instead of 55), so no stream is created that is not used
   Stream aux[3]; Event fork_ev, join_ev[4];
-  // per-launch timing of the first sub-batch (bn254_groth16_kernel_profile): prof_own owns the events, prof_ev is the array the launcher records into
-  std::vector<Event> prof_own; std::vector<hipEvent_t> prof_ev; std::vector<uint8_t> prof_kid; G16Prof prof{0, nullptr, nullptr, 0, 0}; size_t prof_n = 0; unsigned prof_epoch = 0;
-  // the same for the SECOND sub-batch (its launches run on another stream beside the first's): bn254_groth16_kernel_profile_all
-  std::vector<Event> prof2_own; std::vector<hipEvent_t> prof2_ev; std::vector<uint8_t> prof2_kid; G16Prof prof2{0, nullptr, nullptr, 0, 0}; bool prof2_used = false;
+  // per-launch timing of the first sub-batch (pool 0: bn254_groth16_kernel_profile) and of the SECOND, whose launches run on another stream beside the first's
+  // (pool 1, when prof2_used: bn254_groth16_kernel_profile_all)
+  G16ProfPool prof[2]; bool prof2_used = false; size_t prof_n = 0; unsigned prof_epoch = 0;
   RlcDev rlc;                                                       // BN254_FLAG_RLC buffers (bn254_rlc.hpp)
   // BN254_FLAG_COMPRESSED_PROOFS: raw records of the decompressed chunk, then one pre-status byte per proof (bn254_g16_plan.h::g16_cmp_alloc); grown at the
   // first compressed batch that needs more
@@ -111,14 +113,9 @@ struct DevState {
   DevBuf<uint8_t> sp1;
   size_t sp1_proofs() const { return sp1.cap() / 65; }
   DevBuf<uint8_t> st_pv, st_off, st_vkh;
-  // do the sub-batch streams overlap?  ov_ev: start / end of part 0 and of part 1 of the first two-stream batch; ov_state 0: not measured, 1: events recorded,
-  // 2: measured (ov_ratio = sum of the two durations / their union: ~2 side by side, ~1 one after the other); single_stream: fall back to one sub-batch per launch
-  Event ov_ev[4]; int ov_state = 0; float ov_ratio = -1.f; bool single_stream = false;
-  // the decision is not taken from one measurement (another tenant's kernels, a profiler that serialises dispatches): OV_AGREE consecutive measurements must say
-  // "serialised" before the plan changes, a measurement that says "side by side" resets the count; once on one sub-batch per launch, every OV_REPROBE-th batch runs two
-  // again and is measured, so that a transient cause does not pin the key to the slower plan for its lifetime.  `diag`: the explanation, per (key, device), handed out by
-  // bn254_groth16_stream_overlap through bn254_last_diagnostic() of the calling thread
-  int ov_serial_votes = 0; unsigned ov_batches = 0; bool ov_probe = false; std::string diag;
+  // do the sub-batch streams overlap?  ov_ev: start / end of part 0 and of part 1 of a measured two-stream batch; ov: what was read from them and what follows
+  // from it (bn254_overlap_vote.h)
+  Event ov_ev[4]; OvVote ov;
 };
 struct bn254_g16_pvk {
   G16Prepared host;

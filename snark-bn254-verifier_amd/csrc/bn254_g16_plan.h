@@ -2,7 +2,9 @@
 // for a reservation: PURE functions of the sizes, shared by the code that allocates (bn254_capi.hip::ensure_dev), the code that enqueues
 // (g16_enqueue_exact, bn254_launch_g16) and the probe tests/test_capi_cpu.py reads through bn254_dbg_g16_plan.  The launch form of a batch follows the
 // BATCH's size, the buffers the RESERVATION's: the property test walks batch sizes against reservations and asserts that every launch fits (the class of
-// the PlonK scratch overflow of round 3, found there by a sweep instead of a test).
+// the PlonK scratch overflow of round 3, found there by a sweep instead of a test).  BN254_FLAG_RLC has a chunk plan of its own, G16RlcChunkPlan, shared in the
+// same way by rlc_ensure, g16_enqueue_rlc and the probes bn254_dbg_g16_rlc_plan / bn254_dbg_g16_rlc_wide_plan.  (Whether a chunk's sub-batches run side by side
+// at all is decided from measurements: bn254_overlap_vote.h.)
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -167,47 +169,47 @@ inline bool g16_plan_chunk(G16ChunkPlan& p, size_t m, size_t key_inputs, size_t 
   return true;
 }
 
-// ---- BN254_FLAG_RLC: the group status bytes of one workspace chunk --------------------------------------------------------------------------------------
-// A chunk of m proofs runs as `parts` launch parts; part pi forms rlc_plan(its proofs).groups groups whose status bytes sit in a region rounded up to 256
-// (k_rlc_* grids are multiples of 256 lanes).  g16_rlc_alloc(m) is what rlc_ensure allocates for a chunk of m proofs, g16_rlc_need what the parts address.
+// ---- BN254_FLAG_RLC: one workspace chunk, its launch parts and where their groups sit -------------------------------------------------------------------------
+// A chunk of m proofs runs as `parts` launch parts; part pi forms rlc_plan(its proofs).groups groups.  Their status bytes sit in a region rounded up to 256
+// (k_rlc_* grids are multiples of 256 lanes), one part's region after the other; for keys with more than RLC_MAX_PUBLIC inputs the group scalars and the groups'
+// MSM scratch of the parts sit side by side, unrounded.  g16_plan_rlc_chunk is the ONE walk over the parts: rlc_ensure sizes from it, g16_enqueue_rlc addresses by
+// it, bn254_dbg_g16_rlc_plan / _rlc_wide_plan show it.  g16_rlc_alloc(m) is what rlc_ensure allocates for the status bytes of a chunk of m proofs.
 inline size_t g16_rlc_alloc(size_t m) { return g16_round256(m) + 1024; }
-inline int g16_rlc_parts(size_t m, int n_streams) {
+struct G16RlcPart {
+  size_t first, count;       // proofs [first, first + count) of the chunk
+  int log2_share;            // 2^log2_share proofs per lane of the Miller loop: at most the group, and only while the part keeps min_lanes lanes
+  RlcPlan plan;
+  size_t grp_off;            // its status region: the sum of round256(groups) of the parts before it
+  size_t wide_off;           // its group scalars and MSM scratch (wide keys): the sum of the groups of the parts before it
+};
+struct G16RlcChunkPlan {
+  int parts;
+  size_t need;               // status bytes the parts address: against g16_rlc_alloc of the reservation
+  size_t wide_groups;        // groups of all parts: what the wide buffers hold (g16_rlc_wide_alloc of it, rounded up to 256)
+  G16RlcPart part[G16_MAX_PARTS];
+};
+// m: proofs of the chunk; n_streams: BN254_STREAMS; log2_group / log2_share_env: BN254_RLC_GROUP_LOG2 / BN254_RLC_SHARE_LOG2; min_lanes: bn254_set_rlc_params
+inline bool g16_plan_rlc_chunk(G16RlcChunkPlan& p, size_t m, int n_streams, int log2_group, int log2_share_env, size_t min_lanes) {
   int parts = (n_streams > 1 && m >= (size_t)n_streams * 16384) ? n_streams : 1;
   while ((m + parts - 1) / parts > (size_t)G16_MAX_LAUNCH) parts++;
-  return parts;
-}
-inline int g16_rlc_share(size_t part_n, int log2_group, int log2_share_env, size_t min_lanes) {
-  int log2_share = log2_share_env < log2_group ? log2_share_env : log2_group;
-  while (log2_share > 0 && (part_n >> log2_share) < (min_lanes < 1 ? 1 : min_lanes)) log2_share--;   // sharing needs enough lanes to fill the GPU
-  return log2_share;
-}
-inline size_t g16_rlc_need(size_t m, int n_streams, int log2_group, int log2_share_env, size_t min_lanes) {
-  const int parts = g16_rlc_parts(m, n_streams);
+  if (parts > G16_MAX_PARTS) return false;
   const size_t per = g16_round256((m + parts - 1) / parts);
-  size_t off = 0;
+  p.parts = 0; p.need = 0; p.wide_groups = 0;
   for (int pi = 0; pi < parts; pi++) {
     const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
     if (lo >= hi) break;
-    const RlcPlan pl = rlc_plan((uint32_t)(hi - lo), log2_group, g16_rlc_share(hi - lo, log2_group, log2_share_env, min_lanes));
-    off += g16_round256(pl.groups);
+    G16RlcPart& q = p.part[p.parts++];
+    q.first = lo; q.count = hi - lo;
+    q.log2_share = log2_share_env < log2_group ? log2_share_env : log2_group;
+    while (q.log2_share > 0 && (q.count >> q.log2_share) < (min_lanes < 1 ? 1 : min_lanes)) q.log2_share--;   // sharing needs enough lanes to fill the GPU
+    q.plan = rlc_plan((uint32_t)q.count, log2_group, q.log2_share);
+    q.grp_off = p.need; q.wide_off = p.wide_groups;
+    p.need += g16_round256(q.plan.groups); p.wide_groups += q.plan.groups;
   }
-  return off;
+  return true;
 }
 
 // ---- BN254_FLAG_RLC, keys with more than RLC_MAX_PUBLIC inputs: the group scalars and the groups' MSM scratch of one workspace chunk ------------------------
-// The launch parts of a chunk (the walk of g16_rlc_need) put their groups side by side: part pi starts at the sum of the groups before it.
-// g16_rlc_wide_groups(m, ...) is that sum, what rlc_ensure sizes the buffers for and what g16_enqueue_rlc checks every part against.
-inline size_t g16_rlc_wide_groups(size_t m, int n_streams, int log2_group, int log2_share_env, size_t min_lanes) {
-  const int parts = g16_rlc_parts(m, n_streams);
-  const size_t per = g16_round256((m + parts - 1) / parts);
-  size_t groups = 0;
-  for (int pi = 0; pi < parts; pi++) {
-    const size_t lo = (size_t)pi * per, hi = lo + per < m ? lo + per : m;
-    if (lo >= hi) break;
-    groups += rlc_plan((uint32_t)(hi - lo), log2_group, g16_rlc_share(hi - lo, log2_group, log2_share_env, min_lanes)).groups;
-  }
-  return groups;
-}
 // bytes per group: its row of scalars (key_inputs x 32 B, big-endian like an input row), and for the tables of keys with more than 16 inputs (form 0: comb,
 // 1: byte windows; 2: the 13-bit windows of up to 16 inputs need neither) the column digits (form 0) and the chunk sums of k_g16_msm_partial(_comb)
 struct G16RlcWide { size_t rows_bytes, digit_bytes, part_bytes; };

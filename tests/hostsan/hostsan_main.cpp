@@ -531,6 +531,21 @@ int main(int argc, char** argv) {
     bn254_groth16_vk_free(q);
   }
   CHECK(through);
+  // the stream-overlap vote (bn254_overlap_vote.h) through the enqueue: the fake device runs the two sub-batches of a batch above 65 536 proofs one after the other.  A
+  // batch's measurement is read by the next batch, so the fourth batch reads the third serial measurement and is the first on one sub-batch per launch
+  {
+    bn254_g16_pvk* q = nullptr;
+    CHECK(bn254_groth16_vk_prepare(vk.data(), vk.size(), 0, &q) == 0);
+    float ov = 0; int single_stream = -1;
+    for (int b = 1; b <= 4; b++) {
+      CHECK(bn254_groth16_verify_batch_device(q, proofs.data(), 256, inputs.data(), n_public, n, status.data(), 0, nullptr, 0) == 0);
+      CHECK(bn254_groth16_stream_overlap(q, 0, &ov, &single_stream) == 0);
+      CHECK(b == 1 ? ov == -1.f : ov > 0.5f && ov < 1.15f);
+      CHECK(single_stream == (b == 4 ? 1 : 0));
+      CHECK((strstr(bn254_last_diagnostic(), "ran one after the other") != nullptr) == (b == 4));
+    }
+    bn254_groth16_vk_free(q);
+  }
   bn254_groth16_vk_free(pvk);
   // a key with many inputs: comb tables, partial-sum and digit buffers of the wide MSM
   {

@@ -1,6 +1,7 @@
 """GPU tests of BN254_FLAG_RLC for keys with more than 8 public inputs: the public-input sum once per group from group scalars
 (snark-bn254-verifier_amd/csrc/bn254_rlc.h, bn254_k_rlc.hip: k_rlc_group_scalars, k_rlc_group_points_wide).  Every status byte equals the exact path's and
-the generator's, and on a sample the oracle's; the mode really runs (rlc_state reports a fallback share)."""
+the generator's, and on a sample the oracle's; the mode really runs (rlc_state reports a fallback share).  One test runs a narrow key beside a wide one:
+the offsets of the second launch part of an RLC pass are the same plan for both."""
 import random
 
 import pytest
@@ -122,6 +123,30 @@ def test_rlc_wide_fallback_in_several_launches(pkg, L):
     try:
         assert pvk.verify_batch(proofs, inputs, flags=pkg.FLAG_RLC) == exp == pvk.verify_batch(proofs, inputs)
         assert pvk.rlc_state()[0] > 0.9
+    finally:
+        pvk.close()
+
+
+@pytest.mark.parametrize("n_public", [2, 9])
+def test_rlc_second_launch_part_falls_back(pkg, L, n_public):
+    """32 768 + 256 proofs: the smallest batch the RLC pass runs as two launch parts on two streams, so the second part's group status bytes, group scalars and MSM
+    scratch start past the first part's (csrc/bn254_g16_plan.h: G16RlcChunkPlan, grp_off and wide_off).  One invalid proof in each part: its group falls back to
+    the exact pass.  A narrow key (the t_j slots per lane) and one just above RLC_MAX_PUBLIC (group scalars); status bytes equal to the exact path's."""
+    n = 32768 + 256
+    vk, proofs, inputs, exp = pkg.synth_groth16(0xB2547000 + n_public, n_public, n, invalid_every=0, agree=True, threads=16)
+    assert exp == b"\x01" * n
+    bad = bytearray(inputs)
+    row = 32 * n_public
+    for i in (5, n - 3):
+        bad[row * i + 31] ^= 1                                    # another first public input: the pairing check fails
+    bad = bytes(bad)
+    pvk = pkg.PreparedVk(vk)
+    try:
+        exact = pvk.verify_batch(proofs, bad)
+        assert exact == bytes(pkg.REJECT if i in (5, n - 3) else pkg.ACCEPT for i in range(n))
+        assert pvk.rlc_state()[0] == -1.0
+        assert pvk.verify_batch(proofs, bad, flags=pkg.FLAG_RLC) == exact
+        assert 0.0 < pvk.rlc_state()[0] < 0.01                    # the mode ran, and the proofs of two groups of 32 went to the exact pass
     finally:
         pvk.close()
 

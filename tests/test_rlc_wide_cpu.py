@@ -1,6 +1,6 @@
 """BN254_FLAG_RLC for keys with more than 8 public inputs, on the CPU: the host compile of the group-scalar fold and of the wide group stage
 (snark-bn254-verifier_amd/csrc/bn254_rlc.h: rlc_group_scalar, vm_rlc_group_points_wide; probe bn254_dbg_rlc_wide_group) against Python and the oracle,
-and the sizing of the wide form's buffers (bn254_g16_plan.h: g16_rlc_wide_groups / g16_rlc_wide_alloc) against every launch part it places."""
+and the sizing of the wide form's buffers (bn254_g16_plan.h: g16_plan_rlc_chunk / g16_rlc_wide_alloc) against every launch part it places."""
 import random
 import struct
 
@@ -126,3 +126,26 @@ def test_wide_buffers_hold_every_part(pkg):
                 assert off * key_inputs * 32 <= alloc["rows"]
                 assert alloc["digits"] == (off + 255) // 256 * 256 * 20 * key_inputs * 2 if form == 0 else alloc["digits"] == 0
                 assert off * chunks * 27 * 4 <= alloc["part"] if form != 2 else alloc["part"] == 0
+
+
+def test_status_regions_of_the_parts(pkg):
+    """The group status bytes of the same parts, over the same grid: part k's region starts at the sum of round256(groups) of the parts before it (the probe hands
+    out the groups; the offsets are derived from them here), every region lies inside what the context allocates for the chunk, and the last one ends at what
+    bn254_dbg_g16_rlc_plan reports as the chunk's need."""
+    import ctypes as C
+    L = pkg.lib()
+    L.bn254_dbg_g16_rlc_plan.argtypes = [C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+    need, held = C.c_uint64(), C.c_uint64()
+    sizes = [1, 63, 64, 255, 257, 4096, 4097, 16383, 32768, 32769, 65536, 100001, 262144, 786433, 1 << 20]
+    for m in sizes:
+        for n_streams, lg, ls, min_lanes in ((1, 5, 3, 65536), (2, 5, 3, 65536), (2, 1, 0, 1), (4, 8, 3, 1), (2, 16, 3, 1024)):
+            _, parts = pkg.dbg_rlc_wide_plan(m, n_streams, lg, ls, min_lanes, 9, 2)
+            assert L.bn254_dbg_g16_rlc_plan(m, m, n_streams, lg, ls, min_lanes, C.byref(need), C.byref(held)) == 0
+            want = _parts(m, n_streams)
+            assert len(parts) == len(want)
+            grp_off = 0
+            for (_, groups), (lo, hi) in zip(parts, want):
+                assert groups == rlc_plan(hi - lo, lg, _share(hi - lo, lg, ls, min_lanes))[1]
+                grp_off += (groups + 255) // 256 * 256
+                assert grp_off <= held.value, (m, n_streams, lg, ls, min_lanes)
+            assert grp_off == need.value, (m, n_streams, lg, ls, min_lanes)
