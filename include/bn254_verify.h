@@ -409,6 +409,43 @@ int bn254_sp1_plonk_verify_batch_device(const bn254_plonk_pvk* pvk, const void* 
                                         const void* d_public_values, size_t pv_bytes, const uint64_t* d_pv_offsets, size_t n, void* d_status, int device,
                                         void* hip_stream, unsigned flags);
 
+/* ---- Batch pairing-product checks over caller-supplied (G1, G2) pairs -----------------------------------------------------------------------------------------
+ * The primitive both verifiers of the reference are built on, bn::pairing_batch(&[(G1, G2)]) (groth16/verify.rs:73-77, plonk/kzg.rs:175-187), without a key and
+ * without a proof format: for a Groth16 key that is not a gnark file (snarkjs, arkworks, EVM calldata), a KZG opening of one's own, an fflonk or halo2-KZG tail,
+ * or the EVM's ecPairing precompile (EIP-197) in bulk.  One item per lane on the device (new kernels, csrc/bn254_k_pairing.hip); up to eight pairs per item.
+ *
+ *   Definition.  Item i holds n_pairs records of BN254_PAIRING_PAIR_LEN = 192 bytes at pairs + i * item_stride: G1 x | y (64 bytes), then G2 x.c1 | x.c0 | y.c1 | y.c0
+ *   (128 bytes), every coordinate 32 bytes big-endian -- gnark's order, which is also EIP-197's (the imaginary part first).  item_stride >= 192 * n_pairs; bytes past
+ *   the records are ignored.  A point whose bytes are all zero is the identity; a pair with an identity on either side contributes 1 to the product, and its other
+ *   point is still validated, as EIP-197 does.  status[i] is decided in two phases:
+ *     phase 1  the first failure in record order (pair 0 G1, pair 0 G2, pair 1 G1, ...): a coordinate >= p gives BN254_ERR_NOT_MEMBER, otherwise a point off its
+ *              curve gives BN254_ERR_NOT_ON_CURVE;
+ *     phase 2  only if phase 1 found nothing: BN254_ERR_NOT_IN_SUBGROUP if any finite G2 point lies outside the r-torsion (G1 has cofactor 1: nothing to test);
+ *     otherwise BN254_ACCEPT if prod_j e(P_j, Q_j) == 1, else BN254_REJECT.
+ *   EIP-197 correspondence: the precompile's input is one item with item_stride = 192 * k; it returns 1 for BN254_ACCEPT, 0 for BN254_REJECT and fails (consumes all
+ *   gas) for the three error codes.  More than eight pairs per call are not taken in this revision.
+ *
+ *   bn254_pairing_batch writes, instead of the verdict, the final-exponentiated product prod_j e(P_j, Q_j) of item i to out_gt + 384 * i in format 0 of the probes
+ *   (12 x 32 bytes big-endian, tower order, as bn254_dbg_pairing), and status[i] = BN254_ACCEPT where that value is valid; otherwise status[i] is the error of phase 1
+ *   or 2 and the item's 384 bytes are unspecified.
+ *
+ *   Argument errors (BN254_E_BAD_ARG before any device is touched, status untouched): a null pointer with n > 0, n_pairs 0 or above BN254_PAIRING_MAX_PAIRS, an
+ *   item_stride below 192 * n_pairs.  n == 0 returns BN254_OK.  There is no CPU fallback (BN254_E_NO_DEVICE); the first use of a device runs the device self-test
+ *   (below) as every other entry that makes a device ready, bn254_pairing_reserve included.
+ *
+ *   One workspace per device (4680 bytes per item, for at most 2^18 items: a larger batch runs as several launches), shared by all calls: calls on a device are
+ *   serialised like the calls on a (key, device) of the Groth16 entries -- the enqueue under a lock, after a wait on the GPU for the previous call's completion --
+ *   and are safe from several host threads.  bn254_pairing_check_batch_device only enqueues on hip_stream (the caller synchronises it), like
+ *   bn254_groth16_verify_batch_device; once bn254_pairing_reserve(n', device) with n' >= min(n, 2^18) has returned it allocates nothing.  The host-buffer entries
+ *   stage the records through pinned memory in passes (at most 2^18 items and 48 MB of records each) and return with the status bytes.
+ *   Only the one-item-per-lane form exists: batches far below 16 384 items leave most of the GPU idle (no cooperative form in this revision). */
+#define BN254_PAIRING_MAX_PAIRS 8
+#define BN254_PAIRING_PAIR_LEN 192   /* G1 x | y (64)  then  G2 x.c1 | x.c0 | y.c1 | y.c0 (128): gnark's order, which is also EIP-197's */
+int bn254_pairing_check_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* status, int device);
+int bn254_pairing_check_batch_device(const void* d_pairs, size_t item_stride, size_t n_pairs, size_t n, void* d_status, int device, void* hip_stream);
+int bn254_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt /* n x 384 */, uint8_t* status, int device);
+int bn254_pairing_reserve(size_t n, int device);
+
 /* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
  * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
  * before a device is first used the library runs the kernels IT SHIPS on THAT device on small built-in inputs and compares every output byte with a known answer.
@@ -441,6 +478,7 @@ int bn254_sp1_plonk_verify_batch_device(const bn254_plonk_pvk* pvk, const void* 
  * Expected values: the status bytes of checks 4 .. 7 are tables generated with the key's trapdoors (gen_constants.py -> csrc/bn254_constants.h; no pairing is
  * computed for them at run time); everything else is the host's compile of the same arithmetic source, computed once per process while the device runs.
  * NOT covered in this revision: the _keys variants of the kernels (batches over many keys), the RLC group kernels, the MSM row kernels and the wide-key MSM kernels,
+ * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store; its final exponentiation and compare are checks 1 .. 3's kernels),
  * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
  *
  * Cost on one MI355X (profiles/selftest_cost.txt): one run is 40 ms of wall time in a warm process, all of it device time on the run's own stream (g16_lane 11.2 ms,
@@ -551,6 +589,14 @@ int bn254_dbg_valu_peak_sustained(int device, double ms_target, double* mads_per
 int bn254_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device);                 /* n x 32 B each */
 int bn254_dbg_fp12_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out, size_t n, int device);        /* 0 mul 1 sqr 2 inv 3 cyclo_sqr(after easy part) 4 frob1 */
 int bn254_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* out_gt, size_t n, int device);          /* e(P_i, Q_i), n x 384 B */
+/* The batch pairing product (bn254_pairing_check_batch above; same arguments and argument errors) with a choice of where it runs: status[i] as
+ * bn254_pairing_check_batch defines it AND, when out_gt is non-null, the GT value of every item that reached the pairing as bn254_pairing_batch writes it, from one
+ * run.  device -1: the HOST compile of the same loader, Miller run (vm_miller_run_var) and final-exponentiation program on a plain-array accessor, no device is
+ * touched; a device ordinal: the kernels. */
+int bn254_dbg_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device);
+/* host-only probe of its pass plan for a call of n items of n_pairs pairs: out = {items a reservation of n allocates workspace for, items per pass of the host
+ * entries, passes of the host entries, pinned bytes of the records of one pass} */
+int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]);
 /* Value-level probes of the Fp12 operations (tests).  An Fp12 value travels in one of two formats, twelve Fp numbers in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..):
  *   format 0  384 bytes, 32 big-endian canonical bytes per number;
  *   format 1  108 int32: per number the nine balanced 29-bit digits (digit 0 first) of a representative of its Montgomery form x 2^261 mod p, stored into

@@ -395,4 +395,34 @@ inline std::pair<int, unsigned> device_selftest_state(int device = 0) {
   return {state, mask};
 }
 
+// ---- batch pairing-product checks over caller-supplied pairs (bn254_pairing_check_batch; bn::pairing_batch of groth16/verify.rs:73-77 and plonk/kzg.rs:175-187) ------
+// pairs: n items of n_pairs (1 .. 8) records G1 x | y (64 bytes), G2 x.c1 | x.c0 | y.c1 | y.c0 (128 bytes), item_stride bytes apart (0: packed, 192 * n_pairs); an
+// all-zero point is the identity.  The status bytes as the header defines them; pairing_outcome maps one the way the verifiers above map theirs: true / false for
+// "the product is 1 / is not", Panic for what bn's AffineG1::new / AffineG2::new turn into an error (a coordinate >= p, off the curve, outside the r-torsion).
+inline bool pairing_outcome(int st) {
+  if (st == BN254_ACCEPT) return true;
+  if (st == BN254_REJECT) return false;
+  throw Panic(st);
+}
+inline std::vector<uint8_t> pairing_check_batch(const Bytes& pairs, size_t n_pairs, size_t n, int device = 0, size_t item_stride = 0) {
+  const size_t stride = item_stride ? item_stride : (size_t)BN254_PAIRING_PAIR_LEN * n_pairs;
+  if (n && pairs.size() < (n - 1) * stride + (size_t)BN254_PAIRING_PAIR_LEN * n_pairs) throw std::invalid_argument("pairing_check_batch: the buffer is shorter than n items");
+  std::vector<uint8_t> status(n);
+  detail::check(bn254_pairing_check_batch(pairs.data(), stride, n_pairs, n, status.data(), device));
+  return status;
+}
+// the final-exponentiated product of every item (384 bytes each: 12 x 32 big-endian, tower order) into *out_gt; status BN254_ACCEPT where the value is valid, else
+// the loader's error
+inline std::vector<uint8_t> pairing_batch(const Bytes& pairs, size_t n_pairs, size_t n, Bytes* out_gt, int device = 0, size_t item_stride = 0) {
+  const size_t stride = item_stride ? item_stride : (size_t)BN254_PAIRING_PAIR_LEN * n_pairs;
+  if (!out_gt) throw std::invalid_argument("pairing_batch: out_gt is null");
+  if (n && pairs.size() < (n - 1) * stride + (size_t)BN254_PAIRING_PAIR_LEN * n_pairs) throw std::invalid_argument("pairing_batch: the buffer is shorter than n items");
+  std::vector<uint8_t> status(n);
+  out_gt->assign(384 * n, 0);
+  detail::check(bn254_pairing_batch(pairs.data(), stride, n_pairs, n, out_gt->data(), status.data(), device));
+  return status;
+}
+// makes `device` ready for batches of n items: a later bn254_pairing_check_batch_device of up to n items only enqueues
+inline void pairing_reserve(size_t n, int device = 0) { detail::check(bn254_pairing_reserve(n, device)); }
+
 }  // namespace snark_bn254_verifier

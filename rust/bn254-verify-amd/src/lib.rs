@@ -287,6 +287,25 @@ impl PreparedPlonkVk {
 }
 impl Drop for PreparedPlonkVk { fn drop(&mut self) { unsafe { sys::bn254_plonk_vk_free(self.h) } } }
 
+/// At most this many (G1, G2) pairs per item of `pairing_check_batch`.
+pub const PAIRING_MAX_PAIRS: usize = sys::BN254_PAIRING_MAX_PAIRS as usize;
+/// Bytes of one pair: G1 `x | y` (64), then G2 `x.c1 | x.c0 | y.c1 | y.c0` (128), 32-byte big-endian coordinates -- gnark's order and EIP-197's.
+pub const PAIRING_PAIR_LEN: usize = sys::BN254_PAIRING_PAIR_LEN as usize;
+
+/// `bn::pairing_batch(&[(G1, G2)])` checked against 1, for `n` items at once on the GPU (`bn254_pairing_check_batch`): item `i` holds `n_pairs` records of
+/// `PAIRING_PAIR_LEN` bytes at `pairs[i * item_stride..]`; an all-zero point is the identity.  Per item `Status::Accept` (the product of its pairings is 1),
+/// `Status::Reject`, or what `AffineG1::new` / `AffineG2::new` refuse: `NotMember`, `NotOnCurve`, `NotInSubgroup` (the header has the order).
+pub fn pairing_check_batch(pairs: &[u8], item_stride: usize, n_pairs: usize, n: usize, device: i32) -> Result<Vec<Status>, Error> {
+    let short = Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "pairing_check_batch: n_pairs is 1..=8 and the buffer holds n items of item_stride bytes".into() };
+    if n_pairs < 1 || n_pairs > PAIRING_MAX_PAIRS || item_stride < PAIRING_PAIR_LEN * n_pairs { return Err(short); }
+    if n > 0 && (n - 1).checked_mul(item_stride).and_then(|b| b.checked_add(PAIRING_PAIR_LEN * n_pairs)).map_or(true, |b| pairs.len() < b) { return Err(short); }
+    let mut status = vec![0u8; n];
+    check(unsafe { sys::bn254_pairing_check_batch(pairs.as_ptr(), item_stride, n_pairs, n, status.as_mut_ptr(), device as c_int) })?;
+    Ok(status.into_iter().map(Status::from).collect())
+}
+/// Makes `device` ready for pairing batches of `n` items (its self-test at first use, the workspace).
+pub fn pairing_reserve(n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_pairing_reserve(n, device as c_int) }) }
+
 /// The library this crate was generated for?  (`bn254_abi_version`: bumped whenever a function changes its arguments, an array its length or a slot its meaning.)
 pub fn abi_matches() -> bool { unsafe { sys::bn254_abi_version() == sys::BN254_ABI_VERSION } }
 

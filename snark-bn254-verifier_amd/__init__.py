@@ -13,4 +13,5 @@ from .binding import (  # noqa: F401
     set_keys_params, dbg_keys_plan, prepare_vks, dbg_prepare_vks, dbg_pvk_image, VK_PREPARE_STAGES, synth_plonk, synth_plonk_for_inputs,
     PlonkKeySet, dbg_plonk_keys_plan, last_diagnostic, set_plonk_keys_params, set_plonk_rlc_params, dbg_plonk_keys_knobs,
     device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST, dbg_overlap_replay,
+    pairing_check_batch, pairing_batch, pairing_check_batch_device, pairing_reserve, dbg_pairing_batch, dbg_pairing_plan, PAIRING_MAX_PAIRS, PAIRING_PAIR_LEN,
 )

@@ -860,3 +860,79 @@ def synth_plonk_for_inputs(seed, n_public, n_qcp, log2_size, inputs, n=None, thr
     proofs = (C.c_uint8 * max(stride * n, 1))()
     _check(L.bn254_synth_plonk_for_inputs(seed, n_public, n_qcp, log2_size, n, inputs, threads, vk, proofs, stride))
     return bytes(vk), bytes(proofs)[:stride * n]
+
+
+# ---- batch pairing-product checks over caller-supplied (G1, G2) pairs (bn254_pairing_check_batch, include/bn254_verify.h) ----
+PAIRING_MAX_PAIRS = 8
+PAIRING_PAIR_LEN = 192
+
+
+def _pairing_lib():
+    L = lib()
+    host = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.bn254_pairing_check_batch.argtypes = host + [C.c_void_p, C.c_int]
+    L.bn254_pairing_batch.argtypes = host + [C.c_void_p, C.c_void_p, C.c_int]
+    L.bn254_dbg_pairing_batch.argtypes = host + [C.c_void_p, C.c_void_p, C.c_int]
+    L.bn254_pairing_check_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+    L.bn254_pairing_reserve.argtypes = [C.c_size_t, C.c_int]
+    L.bn254_dbg_pairing_plan.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+    return L
+
+
+def _pairing_shape(pairs, n_pairs, n, item_stride):
+    pairs = bytes(pairs)
+    if item_stride is None:
+        item_stride = PAIRING_PAIR_LEN * n_pairs
+    if n is None:
+        n = len(pairs) // item_stride if item_stride else 0
+    if n and len(pairs) < (n - 1) * item_stride + PAIRING_PAIR_LEN * n_pairs:
+        raise Bn254Error("pairing batch: the buffer is shorter than n items")
+    return pairs, n, item_stride
+
+
+def pairing_check_batch(pairs, n_pairs, n=None, item_stride=None, device=0):
+    """n items of n_pairs records G1 (64) | G2 (128: x.c1 | x.c0 | y.c1 | y.c0), item_stride bytes apart -> n status bytes: ACCEPT where the product of the item's
+    pairings is 1, REJECT where it is not, or the loader error (bn254_pairing_check_batch; EIP-197's ecPairing per item)."""
+    L = _pairing_lib()
+    pairs, n, item_stride = _pairing_shape(pairs, n_pairs, n, item_stride)
+    status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_pairing_check_batch(pairs, item_stride, n_pairs, n, status, device))
+    return bytes(status)[:n]
+
+
+def pairing_batch(pairs, n_pairs, n=None, item_stride=None, device=0):
+    """(n GT values of 384 bytes -- the final-exponentiated product of each item's pairings, tower order -- and n status bytes: ACCEPT where the value is valid,
+    else the loader error)  (bn254_pairing_batch)."""
+    L = _pairing_lib()
+    pairs, n, item_stride = _pairing_shape(pairs, n_pairs, n, item_stride)
+    gt = (C.c_uint8 * max(384 * n, 1))(); status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_pairing_batch(pairs, item_stride, n_pairs, n, gt, status, device))
+    return bytes(gt)[:384 * n], bytes(status)[:n]
+
+
+def pairing_check_batch_device(d_pairs, n_pairs, n, d_status, item_stride=None, device=0, stream=0):
+    """bn254_pairing_check_batch_device on device pointers (ints): enqueues on `stream` (a hipStream_t as int) and returns; the caller synchronises the stream."""
+    L = _pairing_lib()
+    _check(L.bn254_pairing_check_batch_device(d_pairs, PAIRING_PAIR_LEN * n_pairs if item_stride is None else item_stride, n_pairs, n, d_status, device, stream))
+
+
+def pairing_reserve(n, device=0):
+    """Makes `device` ready for pairing batches of n items (self-test at its first use, the workspace): a later pairing_check_batch_device of up to n items only enqueues."""
+    _check(_pairing_lib().bn254_pairing_reserve(n, device))
+
+
+def dbg_pairing_batch(pairs, n_pairs, n=None, item_stride=None, device=-1, want_gt=True):
+    """bn254_dbg_pairing_batch: (GT values or None, status bytes of the CHECK) from one run; device -1 is the host compile of the kernels' bodies, no GPU needed."""
+    L = _pairing_lib()
+    pairs, n, item_stride = _pairing_shape(pairs, n_pairs, n, item_stride)
+    gt = (C.c_uint8 * max(384 * n, 1))() if want_gt else None
+    status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_dbg_pairing_batch(pairs, item_stride, n_pairs, n, gt, status, device))
+    return (bytes(gt)[:384 * n] if want_gt else None), bytes(status)[:n]
+
+
+def dbg_pairing_plan(n_pairs, n):
+    """{"ws_items", "pass_items", "passes", "pinned_bytes"} of a pairing batch of n items (bn254_dbg_pairing_plan, host only)."""
+    out = (C.c_uint64 * 4)()
+    _check(_pairing_lib().bn254_dbg_pairing_plan(n_pairs, n, out))
+    return {"ws_items": out[0], "pass_items": out[1], "passes": out[2], "pinned_bytes": out[3]}

@@ -1,0 +1,179 @@
+// bn254_capi_pairing.hip -- the batch pairing product over caller-supplied (G1, G2) pairs (include/bn254_verify.h: bn254_pairing_check_batch, _device,
+// bn254_pairing_batch, bn254_pairing_reserve) and its probe bn254_dbg_pairing_batch.  No key: one workspace per DEVICE, shared by every call on it, so calls on a
+// device are serialised the way a (key, device) is in the Groth16 entries -- the enqueue under the device's lock, after a wait (on the GPU) for the completion event
+// of the previous call.
+// Not part of the one-translation-unit host build of bn254_capi.hip (tests/hostsan/hostsan_main.cpp): a harness that wants it includes this file itself
+// (tests/hostsan/hostsan_pairing.cpp).
+#include "bn254_capi_internal.h"
+#include "bn254_pairing_batch.h"
+
+// items per pass: what the workspace of a device holds at most (1.2 GB) and what one launch works on
+#define PB_PASS_ITEMS ((size_t)1 << 18)
+// the host entries stage a pass's records through pinned memory of at most this many bytes: 2^18 items of one pair, 32 768 items of eight
+#define PB_STAGE_BYTES ((size_t)48 << 20)
+
+// BN254_PAIRING_PASS (tests; read once when the library is loaded) lowers the items per pass, 64 at least
+static const size_t g_pb_pass_items = [] { long v = env_long("BN254_PAIRING_PASS", (long)PB_PASS_ITEMS); return (size_t)(v < 64 ? 64 : (v > (long)PB_PASS_ITEMS ? (long)PB_PASS_ITEMS : v)); }();
+
+// The passes of a call, without a device (bn254_dbg_pairing_plan reads the same functions).  ws_items: the workspace a reservation of n items allocates; host_pass:
+// the items per pass of the host entries, every one of which fits that reservation
+static inline size_t pb_ws_items(size_t n) { return n < g_pb_pass_items ? n : g_pb_pass_items; }
+static inline size_t pb_host_pass(size_t n_pairs, size_t n) {
+  size_t pass = PB_STAGE_BYTES / ((size_t)PB_PAIR_LEN * n_pairs);
+  if (pass > g_pb_pass_items) pass = g_pb_pass_items;
+  return n < pass ? n : pass;
+}
+
+namespace {
+
+struct PbDev {
+  std::mutex mu;                       // uploads, (re)allocation, the enqueue of a call; held for the whole of a host-buffer call (the staging belongs to one call at a time)
+  bool ready = false;
+  DevBuf<int32_t> ws, one;             // G16_WS_BYTES_PER_PROOF per item; 1 in GT
+  size_t ws_items() const { return ws.cap() / (size_t)(G16_WS_BYTES_PER_PROOF / 4); }
+  Event busy_ev; bool busy_valid = false;
+  // host-buffer entries: the records, status bytes and GT values of a pass on both sides
+  Stream stream;
+  DevBuf<uint8_t> d_in, d_status, d_gt;
+  PinBuf<uint8_t> h_in, h_status, h_gt;
+};
+// never destroyed (device memory must not be freed from a static destructor: bn254_capi_internal.h, KeyCache); map nodes never move
+PbDev* pb_dev(int device) {
+  static std::mutex mu;
+  static std::map<int, PbDev>* devs = new std::map<int, PbDev>();
+  std::lock_guard<std::mutex> lk(mu);
+  return &(*devs)[device];
+}
+// caller holds d.mu: the device made ready (self-test at its first use) and the workspace grown to what a reservation of n items holds
+int pb_ensure(PbDev& d, int device, size_t n) {
+  int rc = check_device(device);
+  if (rc || (rc = selftest_gate(device))) return rc;
+  if (!d.ready) {
+    std::vector<int32_t> one(12 * BN_NL);
+    put_fp12(one.data(), bn254::fp12_one());
+    if ((rc = upload(d.one, one)) || (rc = d.busy_ev.ensure())) return rc;
+    d.ready = true;
+  }
+  return d.ws.ensure(pb_ws_items(n) * (size_t)(G16_WS_BYTES_PER_PROOF / 4));
+}
+// caller holds d.mu; everything on `user`, nothing allocated.  verdict: the status bytes are ACCEPT / REJECT; d_gt (may be null): the GT values
+int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* d_status, uint8_t* d_gt, bool verdict, hipStream_t user) {
+  const size_t cap = d.ws_items();
+  if (cap == 0) return set_err(BN254_E_BAD_ARG, "pairing workspace not allocated (internal sizing error)");
+  if (d.busy_valid) HIPCK(hipStreamWaitEvent(user, d.busy_ev, 0));
+  for (size_t off = 0; off < n; off += cap) {
+    bn254::PairingLaunchArgs a;
+    a.pairs = d_pairs + off * item_stride; a.item_stride = item_stride; a.n_pairs = (int)n_pairs; a.n = n - off < cap ? n - off : cap;
+    a.ws = d.ws; a.status = d_status + off; a.one = verdict ? (const int32_t*)d.one : nullptr; a.out_gt = d_gt ? d_gt + 384 * off : nullptr;
+    const hipError_t e = bn254_launch_pairing_batch(a, user);
+    if (e != hipSuccess) return launch_err(e, "pairing batch");
+  }
+  HIPCK(hipEventRecord(d.busy_ev, user));
+  d.busy_valid = true;
+  return BN254_OK;
+}
+
+// BN254_E_BAD_ARG before any device is touched; *done: n == 0, nothing to do
+int pb_check_args(const void* pairs, size_t item_stride, size_t n_pairs, size_t n, const void* status, const void* out_gt, bool wants_gt, bool* done) {
+  *done = false;
+  if (n_pairs < 1 || n_pairs > BN254_PAIRING_MAX_PAIRS) return set_err(BN254_E_BAD_ARG, "bad argument: n_pairs is 1 .. 8");
+  if (item_stride < (size_t)BN254_PAIRING_PAIR_LEN * n_pairs) return set_err(BN254_E_BAD_ARG, "bad argument: item_stride below 192 * n_pairs");
+  if (n && (!pairs || !status || (wants_gt && !out_gt))) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n && item_stride > SIZE_MAX / n) return set_err(BN254_E_BAD_ARG, "bad argument: n items of item_stride bytes overflow the address space");
+  *done = n == 0;
+  return BN254_OK;
+}
+
+// a host-buffer call: passes of pb_host_pass items through the pinned staging; returns with the status bytes (and GT values) of every item
+int pb_host_call(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device, bool verdict) {
+  PbDev* d = pb_dev(device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  const size_t pass = pb_host_pass(n_pairs, n), rec = (size_t)PB_PAIR_LEN * n_pairs;
+  int rc;
+  if ((rc = pb_ensure(*d, device, pass)) || (rc = d->stream.ensure())) return rc;
+  if ((rc = d->h_in.ensure(pass * rec)) || (rc = d->h_status.ensure(pass)) || (rc = d->d_in.ensure(pass * rec)) || (rc = d->d_status.ensure(pass))) return rc;
+  if (out_gt && ((rc = d->h_gt.ensure(pass * 384)) || (rc = d->d_gt.ensure(pass * 384)))) return rc;
+  hipStream_t s = d->stream;
+  auto one_pass = [&](size_t off, size_t m) -> int {
+    if (item_stride == rec) parallel_copy(d->h_in, pairs + off * rec, m * rec);
+    else for (size_t i = 0; i < m; i++) memcpy(d->h_in + i * rec, pairs + (off + i) * item_stride, rec);
+    HIPCK(hipMemcpyAsync(d->d_in, d->h_in, m * rec, hipMemcpyHostToDevice, s));
+    int r = pb_enqueue(*d, d->d_in, rec, n_pairs, m, d->d_status, out_gt ? (uint8_t*)d->d_gt : nullptr, verdict, s);
+    if (r) return r;
+    HIPCK(hipMemcpyAsync(d->h_status, d->d_status, m, hipMemcpyDeviceToHost, s));
+    if (out_gt) HIPCK(hipMemcpyAsync(d->h_gt, d->d_gt, m * 384, hipMemcpyDeviceToHost, s));
+    HIPCK(hipStreamSynchronize(s));
+    memcpy(status + off, d->h_status, m);
+    if (out_gt) memcpy(out_gt + 384 * off, d->h_gt, m * 384);
+    return BN254_OK;
+  };
+  for (size_t off = 0; off < n; off += pass) {
+    if ((rc = one_pass(off, n - off < pass ? n - off : pass))) {
+      const std::string keep = g_err;      // the staging must be quiescent when the lock is released; the failure's text is the one the caller reads
+      (void)hipStreamSynchronize(s);
+      return set_err(rc, keep);
+    }
+  }
+  return BN254_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bn254_pairing_reserve(size_t n, int device) {
+  PbDev* d = pb_dev(device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  return pb_ensure(*d, device, n ? n : 1);
+}
+
+int bn254_pairing_check_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* status, int device) {
+  bool done;
+  int rc = pb_check_args(pairs, item_stride, n_pairs, n, status, nullptr, false, &done);
+  if (rc || done) return rc;
+  return pb_host_call(pairs, item_stride, n_pairs, n, nullptr, status, device, true);
+}
+
+int bn254_pairing_check_batch_device(const void* d_pairs, size_t item_stride, size_t n_pairs, size_t n, void* d_status, int device, void* hip_stream) {
+  bool done;
+  int rc = pb_check_args(d_pairs, item_stride, n_pairs, n, d_status, nullptr, false, &done);
+  if (rc || done) return rc;
+  PbDev* d = pb_dev(device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  // no allocation when the workspace already holds min(n, PB_PASS_ITEMS) items (bn254_pairing_reserve, or an earlier call of that size); a batch above
+  // PB_PASS_ITEMS runs as several launches, one after the other
+  if ((rc = pb_ensure(*d, device, n))) return rc;
+  return pb_enqueue(*d, (const uint8_t*)d_pairs, item_stride, n_pairs, n, (uint8_t*)d_status, nullptr, true, (hipStream_t)hip_stream);
+}
+
+int bn254_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device) {
+  bool done;
+  int rc = pb_check_args(pairs, item_stride, n_pairs, n, status, out_gt, true, &done);
+  if (rc || done) return rc;
+  return pb_host_call(pairs, item_stride, n_pairs, n, out_gt, status, device, false);
+}
+
+// The probe: the status bytes of bn254_pairing_check_batch AND (out_gt non-null) the GT values of bn254_pairing_batch, from one run.  device -1: the host compile of
+// the same loader, vm_miller_run_var and final-exponentiation program on plain arrays (bn254_pairing_batch.h::pb_item_on_host), no device touched; a device ordinal:
+// the kernels, through the host-buffer path above
+int bn254_dbg_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device) {
+  bool done;
+  int rc = pb_check_args(pairs, item_stride, n_pairs, n, status, nullptr, false, &done);
+  if (rc || done) return rc;
+  if (device < -1) return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (device >= 0) return pb_host_call(pairs, item_stride, n_pairs, n, out_gt, status, device, true);
+  const int run_steps = bn254::knob_run_steps_pairing_batch();      // the loop cut into runs as the launcher cuts it (BN254_MILLER_RUN_STEPS)
+  for (size_t i = 0; i < n; i++) status[i] = bn254::pb_item_on_host(pairs + i * item_stride, (int)n_pairs, out_gt ? out_gt + 384 * i : nullptr, run_steps);
+  return BN254_OK;
+}
+
+// host-only probe of the pass plan: for a call of n items of n_pairs pairs -- out = {items a reservation of n allocates workspace for, items per pass of the host
+// entries, passes of the host entries, pinned bytes of a pass's records}
+int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]) {
+  if (!out || n_pairs < 1 || n_pairs > BN254_PAIRING_MAX_PAIRS) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const size_t pass = pb_host_pass(n_pairs, n);
+  out[0] = pb_ws_items(n); out[1] = pass; out[2] = pass ? (n + pass - 1) / pass : 0; out[3] = (uint64_t)pass * PB_PAIR_LEN * n_pairs;
+  return BN254_OK;
+}
+
+}  // extern "C"

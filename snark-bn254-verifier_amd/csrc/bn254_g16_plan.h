@@ -83,6 +83,8 @@ inline int knob_run_steps_g16_keys() { const LaunchKnobs& k = launch_knobs(); re
 inline int knob_run_steps_pairing2_lanes() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps < 0 ? G16_MILLER_STEPS : k.run_steps; }
 //   bn254_launch_pairing2_fixed_keys: the one-launch-per-operation kernels read one key per launch, so 0 is the whole loop too
 inline int knob_run_steps_pairing2_keys() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps <= 0 ? G16_MILLER_STEPS : k.run_steps; }
+//   bn254_launch_pairing_batch: k_miller_run_var is the only form of the variable-pair loop, so 0 is the whole loop too
+inline int knob_run_steps_pairing_batch() { const LaunchKnobs& k = launch_knobs(); return !k.set_run_steps || k.run_steps <= 0 ? G16_MILLER_STEPS : k.run_steps; }
 // BN254_COOP_FIXED_MAX: the largest two-pair check that takes the cooperative kernel (bn254_launch_pairing2_fixed)
 inline size_t knob_coop_fixed_max() { const LaunchKnobs& k = launch_knobs(); return k.set_coop_fixed_max ? (size_t)k.coop_fixed_max : (size_t)COOP12_MAX_PROOFS_FIXED; }
 // BN254_WIDE_PER (experiments): inputs per lane of the wide MSM, at least G16_WIDE_MSM_INPUTS_PER_LANE (the partial-sum buffer is sized for that many chunks); 0: the default

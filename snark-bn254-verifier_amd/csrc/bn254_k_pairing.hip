@@ -1,0 +1,75 @@
+// bn254_k_pairing.hip -- the batch pairing product over caller-supplied pairs (bn::pairing_batch of groth16/verify.rs:73-77 and plonk/kzg.rs:175-187, without a key;
+// include/bn254_verify.h, bn254_pairing_check_batch): one item of up to eight (G1, G2) pairs per lane.  Its own translation unit for the reason bn254_k_miller.hip gives:
+// a run kernel is ~300 KB of straight-line code.
+//   k_pairing_load     the item's records -> points, identity bits and the status byte (bn254_pairing_batch.h::pb_load_item: the range and on-curve checks)
+//   k_miller_run_var   steps [s_begin, s_end) of the optimal-ate loop for the item's pairs, f in flight (bn254_vm.h::vm_miller_run_var); the run that ends the loop
+//                      decides the r-torsion tests and writes the status of an item that failed one
+//   k_pairing_store    the store tail: VE_S0 in the 384-byte format 0 of bn254_dbg_pairing
+// then vm_final_exp_program through LaunchOps and k_g16_compare against 1 in GT (the kernels of bn254_kernels.hip).
+// Only the lane form exists: a cooperative twelve-lane form for small batches is out of scope of this revision (bn254_pairing_batch.h).
+#include <hip/hip_runtime.h>
+#include "bn254_launch_ops.h"
+#include "bn254_g16_plan.h"
+#include "bn254_pairing_batch.h"
+
+namespace bn254 {
+
+__global__ void __launch_bounds__(256, 2) k_pairing_load(const uint8_t* __restrict__ pairs, size_t item_stride, int n_pairs, uint32_t n, int32_t* ws, uint8_t* __restrict__ status) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  DevWs w(ws, n, i);
+  int np = __builtin_amdgcn_readfirstlane(n_pairs);
+  np = np < 1 ? 1 : (np > PB_MAX_PAIRS ? PB_MAX_PAIRS : np);
+  const bool aligned = ((((uintptr_t)pairs) | item_stride) & 3) == 0;
+  status[i] = (uint8_t)pb_load_item(w, pairs + (size_t)i * item_stride, np, aligned);
+}
+
+struct PairKinds {   // the step table (88 entries, 0..4), two steps per byte, by value in the kernel arguments
+  MillerKinds k;
+  __device__ __forceinline__ int get(int s) const { return __builtin_amdgcn_readfirstlane((k.nib[s >> 1] >> ((s & 1) * 4)) & 15); }
+};
+__global__ void __launch_bounds__(256, 2) k_miller_run_var(int32_t* ws, uint32_t n, uint8_t* status, MillerKinds kinds, int s_begin, int s_end, int n_pairs, int e, int fold) {
+  __shared__ int32_t park_lds[72 * 256];
+  VM_KERNEL_PROLOGUE();
+  w.lds = park_lds;
+  PairKinds pk{kinds};
+  const int s_last = __builtin_amdgcn_readfirstlane(s_end), fl = __builtin_amdgcn_readfirstlane(fold);
+  int np = __builtin_amdgcn_readfirstlane(n_pairs);
+  np = np < 1 ? 1 : (np > PB_MAX_PAIRS ? PB_MAX_PAIRS : np);
+  const uint32_t ident = pb_ident(w);
+  const int failed = vm_miller_run_var(w, pk, __builtin_amdgcn_readfirstlane(s_begin), s_last, np, ident, e, fl);
+  if ((fl & MR_FOLD_ATE) && s_last == BN_ATE_STEPS && i < n && (st & BN254_ST_PENDING) && failed >= 0) status[i] = BN254_ST_NOT_IN_SUBGROUP;
+}
+
+// finalize: the store is the launch's last word on a pending item -- its status becomes ACCEPT ("out_gt holds the value")
+__global__ void __launch_bounds__(256, 2) k_pairing_store(int32_t* ws, uint32_t n, uint8_t* status, uint8_t* __restrict__ out_gt, int finalize) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n || !(status[i] & BN254_ST_PENDING)) return;
+  DevWs w(ws, n, i);
+  const int korder[6] = {0, 2, 4, 1, 3, 5};
+  uint8_t* p = out_gt + 384 * (size_t)i;
+  for (int t = 0; t < 6; t++)
+    for (int h = 0; h < 2; h++) { uint32_t v[8]; fp_to_words(v, w.ld(VE_S0 + 2 * korder[t] + h)); words_to_be(p + 64 * t + 32 * h, v); }
+  if (finalize) status[i] = BN254_ST_ACCEPT;
+}
+
+}  // namespace bn254
+
+using namespace bn254;
+hipError_t bn254_launch_pairing_batch(const PairingLaunchArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  if (a.n > (size_t)G16_MAX_LAUNCH || a.n_pairs < 1 || a.n_pairs > PB_MAX_PAIRS || a.item_stride < (size_t)PB_PAIR_LEN * (size_t)a.n_pairs || (!a.one && !a.out_gt)) return hipErrorInvalidValue;
+  const unsigned grid = grid_for(a.n);
+  const uint32_t nn = (uint32_t)a.n;
+  hipLaunchKernelGGL(k_pairing_load, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, nn, a.ws, a.status);
+  const MillerKinds& kinds = miller_step_table().packed;
+  const int per = knob_run_steps_pairing_batch();
+  for (int s0 = 0; s0 < BN_ATE_STEPS; s0 += per)
+    hipLaunchKernelGGL(k_miller_run_var, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, kinds, s0, s0 + per < BN_ATE_STEPS ? s0 + per : BN_ATE_STEPS, a.n_pairs, (int)VE_F,
+                       (int)(MR_FOLD_INIT | MR_FOLD_ATE));
+  LaunchOps ops{a.ws, nn, a.status, grid, s, {nullptr, nullptr, nullptr}, nullptr};
+  vm_final_exp_program(ops);
+  if (a.out_gt) hipLaunchKernelGGL(k_pairing_store, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.out_gt, a.one ? 0 : 1);
+  if (a.one) hipLaunchKernelGGL(k_g16_compare, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.one, (int)BN254_ST_REJECT);
+  return hipGetLastError();
+}

@@ -30,6 +30,18 @@ enum {
   // travels in the index so that every dispatcher (OPS) hands it through unchanged; ve_conj / ve_elem take it apart.
   VE_CONJ = 0x100
 };
+// ---- the same workspace as the batch pairing product reads it (vm_miller_run_var: up to VP_MAX_PAIRS variable pairs per item, no key) ----------------------------
+// Pair 0 sits where the Groth16 path keeps its variable pair: P at VE_AX / VE_AY, Q at VE_B, the running point T at VE_T.  Pair j = 1 .. 7 takes VP_PAIR_ELEMS = 12 Fp
+// from VE_S1 on -- P (2) | Q (4: x.c0 x.c1 y.c0 y.c1) | T (6: X Y Z) -- i.e. elements 34 + 12 (j - 1) .. 45 + 12 (j - 1), the last one ending at 117 (VE_UT2 - 1).
+// Those slots (VE_S1 .. VE_S4, VE_UT0, VE_TMPA / VE_TMPB, VE_UT1) are dead during the Miller loop; the final exponentiation overwrites them, and VE_S0 = VE_T of pair 0
+// with them, only after the loop's last run has decided the r-torsion tests.  VE_COUNT is unchanged.
+// The identity bits of an item -- bit 2j: P_j is the identity, bit 2j + 1: Q_j is -- are sixteen and do not fit the status byte: they are digit 0 of the element
+// VP_IDENT = VE_CX, which this path has no other use for (the key-side G1 points VE_CX .. VE_LY belong to the protocols with fixed pairs).
+enum { VP_MAX_PAIRS = 8, VP_PAIR_ELEMS = 12, VP_EXTRA = VE_S1, VP_IDENT = VE_CX };
+static_assert(VP_EXTRA + (VP_MAX_PAIRS - 1) * VP_PAIR_ELEMS <= VE_COUNT, "the extra pairs fit the slots of the final exponentiation");
+BN_HD int vp_p(int j) { return j == 0 ? (int)VE_AX : VP_EXTRA + VP_PAIR_ELEMS * (j - 1); }
+BN_HD int vp_q(int j) { return j == 0 ? (int)VE_B : VP_EXTRA + VP_PAIR_ELEMS * (j - 1) + 2; }
+BN_HD int vp_t(int j) { return j == 0 ? (int)VE_T : VP_EXTRA + VP_PAIR_ELEMS * (j - 1) + 6; }
 BN_HD bool ve_conj(int e) { return (e & VE_CONJ) != 0; }
 BN_HD int ve_elem(int e) { return e & ~VE_CONJ; }
 
@@ -373,6 +385,63 @@ BN_HD void vm_miller_run_fixed2(W& w, const LINES& lines, const KINDS& kinds, in
     mf_line_fixed(w, lines.get(1, s), e_p1, inf1, f4, f5);
   }
   mf_store(w, e, f4, f5);
+}
+
+// The run for np VARIABLE pairs and no key (the batch pairing product, bn::pairing_batch of groth16/verify.rs:73-77 and plonk/kzg.rs:175-187 on caller-supplied
+// pairs): per step mf_sqr once, then for every pair j its G2 step on T_j and its line into the accumulator in flight.  np (1 .. VP_MAX_PAIRS) is wave-uniform and a
+// run-time value, and so are the element indices of pair j (vp_p / vp_q / vp_t): ONE instantiation serves every pair count.  ident: the item's identity bits
+// (VP_IDENT); a pair with an identity on either side contributes 1, so its line product keeps f by selecting the OUTPUT (as mf_line_fixed does with inf) -- its G2
+// steps still run: the r-torsion test of a finite Q_j paired with the identity of G1 needs T_j.  The G2 steps of an identity Q_j work on zeros and are never read.
+// As in vm_miller_run the doubling and the addition side of the branch each carry their own G2 formulas and line product, so only f in flight crosses the join.
+template <class W> BN_HD void mf_line_var_sel(W& w, const G2Line& l, int e_pa, bool skip, Fp2& f4, Fp2& f5) {
+  Fp px = w.ld(e_pa), py = w.ld(e_pa + 1);
+  Fp2 d0 = fp2_mul_fp(l.r0, py), d3 = fp2_mul_fp(l.r1, px), d4 = l.r2;
+  Fp2 x3 = fp2_mul_xi(d3), x4 = fp2_mul_xi(d4);
+  Fp2 k0 = w.unpark(0), k1 = w.unpark(1), k2 = w.unpark(2), k3 = w.unpark(3);
+  const Fp2 k4 = f4, k5 = f5;
+  w.park(0, fp2_select(skip, k0, fp2_dotp(pp(d0, k0), pp(x3, k5), pp(x4, k3))));
+  w.park(1, fp2_select(skip, k1, fp2_dotp(pp(d0, k1), pp(d3, k0), pp(x4, k4))));
+  w.park(2, fp2_select(skip, k2, fp2_dotp(pp(d0, k2), pp(d3, k1), pp(x4, k5))));
+  w.park(3, fp2_select(skip, k3, fp2_dotp(pp(d0, k3), pp(d3, k2), pp(d4, k0))));
+  f4 = fp2_select(skip, k4, fp2_dotp(pp(d0, k4), pp(d3, k3), pp(d4, k1)));
+  f5 = fp2_select(skip, k5, fp2_dotp(pp(d0, k5), pp(d3, k4), pp(d4, k2)));
+}
+BN_HD bool vp_skips(uint32_t ident, int j) { return ((ident >> (2 * j)) & 3u) != 0; }
+BN_HD bool vp_q_finite(uint32_t ident, int j) { return ((ident >> (2 * j + 1)) & 1u) == 0; }
+// Returns -1, or with MR_FOLD_ATE at the end of the loop the first pair whose finite Q_j fails the r-torsion test (vm_g2_ate_check on T_j).
+template <class W, class KINDS>
+BN_HD int vm_miller_run_var(W& w, const KINDS& kinds, int s_begin, int s_end, int np, uint32_t ident, int e, int fold = 0) {
+  Fp2 f4, f5;
+  if ((fold & MR_FOLD_INIT) && s_begin == 0) {
+    mf_init(w, vp_t(0), vp_q(0), f4, f5);
+    for (int j = 1; j < np; j++) { const int et = vp_t(j), eb = vp_q(j); vst2(w, et, vld2(w, eb)); vst2(w, et + 2, vld2(w, eb + 2)); vst2(w, et + 4, fp2_one()); }
+  } else mf_load(w, e, f4, f5);
+  for (int s = s_begin; s < s_end; s++) {
+    const int kind = kinds.get(s);
+    if (kind == 0) {
+      if (s != 0) mf_sqr(w, f4, f5);
+      for (int j = 0; j < np; j++) {
+        BN_SCHED_FENCE();
+        G2Line l = mf_g2(w, 0, vp_t(j), vp_q(j));
+        mf_line_var_sel(w, l, vp_p(j), vp_skips(ident, j), f4, f5);
+      }
+    } else {
+      for (int j = 0; j < np; j++) {
+        BN_SCHED_FENCE();
+        G2Line l = mf_g2(w, kind, vp_t(j), vp_q(j));
+        mf_line_var_sel(w, l, vp_p(j), vp_skips(ident, j), f4, f5);
+      }
+    }
+    BN_SCHED_FENCE();
+  }
+  mf_store(w, e, f4, f5);
+  int failed = -1;
+  if ((fold & MR_FOLD_ATE) && s_end == BN_ATE_STEPS)
+    for (int j = 0; j < np; j++) {
+      const bool ok = vm_g2_ate_check(w, vp_t(j), vp_q(j));
+      if (failed < 0 && vp_q_finite(ident, j) && !ok) failed = j;
+    }
+  return failed;
 }
 
 // ---- r-torsion test of B from the point the Miller loop has already computed ----------------------------------------------------------

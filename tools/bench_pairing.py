@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Rates of the batch pairing product (bn254_pairing_check_batch_device) on one GPU: device-resident items, n in {4096, 65536} x n_pairs in {1, 2, 3, 4, 8}, items/s per
+cell, and in the same session the exact Groth16 rate (bn254_groth16_verify_batch_device, 2 public inputs) at the same n for orientation.
+  python tools/bench_pairing.py [--sizes 4096,65536] [--pairs 1,2,3,4,8] [--steps 5] [--out profiles/r14_pairing_batch.txt]
+The items are made of the A (G1) and B (G2) points of a synthetic Groth16 workload, pair j of item i being (A[i + 7 j], B[i + 13 j]) (indices modulo n): distinct valid
+points, so every item runs its loops to the end and is REJECT (checked).  Every call is timed on its own from the call to the status bytes on the device, after one
+warm-up call and a reservation; the median of --steps calls is reported.  Writes the table to --out and prints one JSON line."""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--sizes", type=str, default="4096,65536")
+    ap.add_argument("--pairs", type=str, default="1,2,3,4,8")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "r14_pairing_batch.txt"))
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    pkg = importlib.import_module("snark-bn254-verifier_amd")
+    dev = torch.device("cuda:0")
+    stream = torch.cuda.current_stream(dev)
+    sizes = [int(x) for x in args.sizes.split(",")]
+    pairs = [int(x) for x in args.pairs.split(",")]
+
+    def timed(fn):
+        times = []
+        for it in range(args.steps + 1):
+            torch.cuda.synchronize(dev)
+            t = time.perf_counter()
+            fn()
+            torch.cuda.synchronize(dev)
+            if it:
+                times.append(time.perf_counter() - t)
+        return statistics.median(times) * 1e3
+
+    rows, lines = [], []
+    for n in sizes:
+        vk, proofs, inputs, expected = pkg.synth_groth16(0xB2549000, 2, n, invalid_every=0, agree=True, threads=16)
+        rec = np.frombuffer(proofs, dtype=np.uint8).reshape(n, 256)
+        a, b = rec[:, 0:64], rec[:, 64:192]
+        pvk = pkg.PreparedVk(vk, pkg.VK_REFERENCE)
+        d_proofs = torch.from_numpy(rec.copy()).to(dev)
+        d_inputs = torch.frombuffer(bytearray(inputs), dtype=torch.uint8).to(dev)
+        d_status = torch.zeros(n, dtype=torch.uint8, device=dev)
+        pvk.reserve(n, 0)
+
+        def g16():
+            pvk.verify_batch_device(d_proofs.data_ptr(), d_inputs.data_ptr(), d_status.data_ptr(), n, 256, 2, 0, stream.cuda_stream)
+
+        g16_ms = timed(g16)
+        assert bytes(d_status.cpu().numpy().tobytes()) == expected
+        lines.append("n = %d   exact Groth16 (2 inputs, device entry): %.3f ms, %.0f proofs/s" % (n, g16_ms, n / g16_ms * 1e3))
+        pkg.pairing_reserve(n, device=0)
+        for k in pairs:
+            items = np.empty((n, 192 * k), dtype=np.uint8)
+            for j in range(k):
+                items[:, 192 * j:192 * j + 64] = np.roll(a, -7 * j, axis=0)
+                items[:, 192 * j + 64:192 * j + 192] = np.roll(b, -13 * j, axis=0)
+            d_items = torch.from_numpy(items).to(dev)
+            d_status.fill_(0xEE)
+
+            def run():
+                pkg.pairing_check_batch_device(d_items.data_ptr(), k, n, d_status.data_ptr(), device=0, stream=stream.cuda_stream)
+
+            ms = timed(run)
+            got = bytes(d_status.cpu().numpy().tobytes())
+            assert got == bytes([pkg.REJECT]) * n, "unexpected status bytes: %r" % {s: got.count(bytes([s])) for s in set(got)}
+            rows.append({"n": n, "n_pairs": k, "ms": round(ms, 3), "items_per_s": round(n / ms * 1e3), "pairs_per_s": round(n * k / ms * 1e3), "groth16_ms": round(g16_ms, 3)})
+            lines.append("n = %d   n_pairs = %d: %.3f ms, %.0f items/s, %.0f pairs/s, %.2f x the Groth16 batch's time" % (n, k, ms, n / ms * 1e3, n * k / ms * 1e3, ms / g16_ms))
+    head = ["bn254_pairing_check_batch_device, device-resident items, one GPU (%s); median of %d calls per cell, each timed from the call to the status bytes on the device"
+            % (torch.cuda.get_device_name(0), args.steps), ""]
+    with open(args.out, "w") as f:
+        f.write("\n".join(head + lines) + "\n")
+    print(json.dumps({"bench": "pairing_batch", "rows": rows}))
+
+
+if __name__ == "__main__":
+    main()
