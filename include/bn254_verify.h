@@ -438,13 +438,24 @@ int bn254_sp1_plonk_verify_batch_device(const bn254_plonk_pvk* pvk, const void* 
  *   and are safe from several host threads.  bn254_pairing_check_batch_device only enqueues on hip_stream (the caller synchronises it), like
  *   bn254_groth16_verify_batch_device; once bn254_pairing_reserve(n', device) with n' >= min(n, 2^18) has returned it allocates nothing.  The host-buffer entries
  *   stage the records through pinned memory in passes (at most 2^18 items and 48 MB of records each) and return with the status bytes.
- *   Only the one-item-per-lane form exists: batches far below 16 384 items leave most of the GPU idle (no cooperative form in this revision). */
+ *
+ *   Two forms of a launch, with the same status and GT bytes.  The lane form (one item per lane) fills the GPU from about 16 384 items; below that its time is one
+ *   wavefront's instruction stream whatever the size.  A launch of up to coop_max items therefore takes the COOPERATIVE form: the same loader, then one kernel with
+ *   twelve lanes per item (csrc/bn254_coop12.hip, k_coop12_miller_pairs) that runs the Miller loop of every pair, the r-torsion tests and the final exponentiation.
+ *   bn254_set_pairing_params(coop_max): process-wide and atomic; 0: always the lane form; clamped to 30 720, the cooperative kernels' range; negative: unchanged.
+ *   Default 16 384, the largest measured size at which it is not slower than the lane form at any pair count (4096 items of 1 / 8 pairs: 1.7 / 6.6 ms against
+ *   8.9 / 31.5 ms).  The environment variable BN254_PAIRING_COOP_MAX gives the initial value, BN254_COOP=0 switches the cooperative form off.  A launch takes one
+ *   form whole.  bn254_pairing_params reads the knob back (out[0] = coop_max); bn254_pairing_state counts the launches enqueued so far by this process: out[0] in the
+ *   cooperative form, out[1] in the lane form. */
 #define BN254_PAIRING_MAX_PAIRS 8
 #define BN254_PAIRING_PAIR_LEN 192   /* G1 x | y (64)  then  G2 x.c1 | x.c0 | y.c1 | y.c0 (128): gnark's order, which is also EIP-197's */
 int bn254_pairing_check_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* status, int device);
 int bn254_pairing_check_batch_device(const void* d_pairs, size_t item_stride, size_t n_pairs, size_t n, void* d_status, int device, void* hip_stream);
 int bn254_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt /* n x 384 */, uint8_t* status, int device);
 int bn254_pairing_reserve(size_t n, int device);
+void bn254_set_pairing_params(long coop_max);
+int bn254_pairing_params(long out[1]);
+int bn254_pairing_state(uint64_t out[2]);
 
 /* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
  * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
@@ -594,6 +605,11 @@ int bn254_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* out_gt, siz
  * run.  device -1: the HOST compile of the same loader, Miller run (vm_miller_run_var) and final-exponentiation program on a plain-array accessor, no device is
  * touched; a device ordinal: the kernels. */
 int bn254_dbg_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device);
+/* The same with the form of every launch forced: form 0 is bn254_dbg_pairing_batch; 1 (the lane kernels) and 2 (the cooperative kernel) need a device ordinal, and
+ * form 2 takes at most 30 720 items -- otherwise BN254_E_BAD_ARG with the buffers untouched. */
+int bn254_dbg_pairing_batch_form(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device, int form);
+/* the form a launch of n items of n_pairs pairs takes under the knobs as they are now: *form = 1 lane, 2 cooperative; no device is touched */
+int bn254_dbg_pairing_form(size_t n_pairs, size_t n, int* form);
 /* host-only probe of its pass plan for a call of n items of n_pairs pairs: out = {items a reservation of n allocates workspace for, items per pass of the host
  * entries, passes of the host entries, pinned bytes of the records of one pass} */
 int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]);
@@ -802,7 +818,7 @@ int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

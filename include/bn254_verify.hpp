@@ -424,5 +424,10 @@ inline std::vector<uint8_t> pairing_batch(const Bytes& pairs, size_t n_pairs, si
 }
 // makes `device` ready for batches of n items: a later bn254_pairing_check_batch_device of up to n items only enqueues
 inline void pairing_reserve(size_t n, int device = 0) { detail::check(bn254_pairing_reserve(n, device)); }
+// launches of up to coop_max items take the cooperative twelve-lane form (0: always the lane form; clamped to 30 720; negative: unchanged) / the knob as it is now
+inline void set_pairing_params(long coop_max) { bn254_set_pairing_params(coop_max); }
+inline long pairing_params() { long out[1] = {0}; detail::check(bn254_pairing_params(out)); return out[0]; }
+// launches enqueued so far by this process: {in the cooperative form, in the lane form}
+inline std::array<uint64_t, 2> pairing_state() { std::array<uint64_t, 2> out{}; detail::check(bn254_pairing_state(out.data())); return out; }
 
 }  // namespace snark_bn254_verifier

@@ -305,6 +305,21 @@ pub fn pairing_check_batch(pairs: &[u8], item_stride: usize, n_pairs: usize, n: 
 }
 /// Makes `device` ready for pairing batches of `n` items (its self-test at first use, the workspace).
 pub fn pairing_reserve(n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_pairing_reserve(n, device as c_int) }) }
+/// Launches of up to `coop_max` items of a pairing batch take the cooperative twelve-lane form (`bn254_set_pairing_params`; 0: always the lane form; clamped to
+/// 30 720; negative: unchanged).
+pub fn set_pairing_params(coop_max: i64) { unsafe { sys::bn254_set_pairing_params(coop_max as core::ffi::c_long) } }
+/// The knob as it is now (`bn254_pairing_params`).
+pub fn pairing_params() -> Result<i64, Error> {
+    let mut out: [core::ffi::c_long; 1] = [0];
+    check(unsafe { sys::bn254_pairing_params(out.as_mut_ptr()) })?;
+    Ok(out[0] as i64)
+}
+/// Launches of pairing batches enqueued so far by this process: (in the cooperative form, in the lane form)  (`bn254_pairing_state`).
+pub fn pairing_state() -> Result<(u64, u64), Error> {
+    let mut out = [0u64; 2];
+    check(unsafe { sys::bn254_pairing_state(out.as_mut_ptr()) })?;
+    Ok((out[0], out[1]))
+}
 
 /// The library this crate was generated for?  (`bn254_abi_version`: bumped whenever a function changes its arguments, an array its length or a slot its meaning.)
 pub fn abi_matches() -> bool { unsafe { sys::bn254_abi_version() == sys::BN254_ABI_VERSION } }

@@ -14,4 +14,5 @@ from .binding import (  # noqa: F401
     PlonkKeySet, dbg_plonk_keys_plan, last_diagnostic, set_plonk_keys_params, set_plonk_rlc_params, dbg_plonk_keys_knobs,
     device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST, dbg_overlap_replay,
     pairing_check_batch, pairing_batch, pairing_check_batch_device, pairing_reserve, dbg_pairing_batch, dbg_pairing_plan, PAIRING_MAX_PAIRS, PAIRING_PAIR_LEN,
+    set_pairing_params, pairing_params, pairing_state, dbg_pairing_form, PAIRING_FORM_LANES, PAIRING_FORM_COOP,
 )

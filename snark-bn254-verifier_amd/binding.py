@@ -921,14 +921,58 @@ def pairing_reserve(n, device=0):
     _check(_pairing_lib().bn254_pairing_reserve(n, device))
 
 
-def dbg_pairing_batch(pairs, n_pairs, n=None, item_stride=None, device=-1, want_gt=True):
-    """bn254_dbg_pairing_batch: (GT values or None, status bytes of the CHECK) from one run; device -1 is the host compile of the kernels' bodies, no GPU needed."""
+def dbg_pairing_batch(pairs, n_pairs, n=None, item_stride=None, device=-1, want_gt=True, form=None):
+    """bn254_dbg_pairing_batch: (GT values or None, status bytes of the CHECK) from one run; device -1 is the host compile of the kernels' bodies, no GPU needed.
+    form (1: the lane kernels, 2: the cooperative kernel; 0: as without it) forces the form of every launch through bn254_dbg_pairing_batch_form."""
     L = _pairing_lib()
     pairs, n, item_stride = _pairing_shape(pairs, n_pairs, n, item_stride)
     gt = (C.c_uint8 * max(384 * n, 1))() if want_gt else None
     status = (C.c_uint8 * max(n, 1))()
-    _check(L.bn254_dbg_pairing_batch(pairs, item_stride, n_pairs, n, gt, status, device))
+    if form is None:
+        _check(L.bn254_dbg_pairing_batch(pairs, item_stride, n_pairs, n, gt, status, device))
+    else:
+        fn = L.bn254_dbg_pairing_batch_form
+        fn.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        _check(fn(pairs, item_stride, n_pairs, n, gt, status, device, form))
     return (bytes(gt)[:384 * n] if want_gt else None), bytes(status)[:n]
+
+
+PAIRING_FORM_LANES, PAIRING_FORM_COOP = 1, 2
+
+
+def set_pairing_params(coop_max=-1):
+    """bn254_set_pairing_params: launches of up to coop_max items of a pairing batch take the cooperative twelve-lane form (0: always the lane form; clamped to the
+    cooperative kernels' range; negative: unchanged)."""
+    fn = lib().bn254_set_pairing_params
+    fn.argtypes = [C.c_long]; fn.restype = None
+    fn(coop_max)
+
+
+def pairing_params():
+    """coop_max as it is now (bn254_pairing_params)."""
+    fn = lib().bn254_pairing_params
+    fn.argtypes = [C.POINTER(C.c_long)]
+    out = (C.c_long * 1)()
+    _check(fn(out))
+    return int(out[0])
+
+
+def pairing_state():
+    """(launches enqueued so far in the cooperative form, in the lane form)  (bn254_pairing_state)."""
+    fn = lib().bn254_pairing_state
+    fn.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 2)()
+    _check(fn(out))
+    return int(out[0]), int(out[1])
+
+
+def dbg_pairing_form(n_pairs, n):
+    """The form a launch of n items of n_pairs pairs takes under the knobs as they are now: 1 lane, 2 cooperative (bn254_dbg_pairing_form, host only)."""
+    fn = lib().bn254_dbg_pairing_form
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.POINTER(C.c_int)]
+    out = C.c_int()
+    _check(fn(n_pairs, n, C.byref(out)))
+    return out.value
 
 
 def dbg_pairing_plan(n_pairs, n):

@@ -1,5 +1,6 @@
 // bn254_capi_pairing.hip -- the batch pairing product over caller-supplied (G1, G2) pairs (include/bn254_verify.h: bn254_pairing_check_batch, _device,
-// bn254_pairing_batch, bn254_pairing_reserve) and its probe bn254_dbg_pairing_batch.  No key: one workspace per DEVICE, shared by every call on it, so calls on a
+// bn254_pairing_batch, bn254_pairing_reserve; the knob and the counters of a launch's form: bn254_set_pairing_params, bn254_pairing_params, bn254_pairing_state) and its
+// probes bn254_dbg_pairing_batch, bn254_dbg_pairing_batch_form, bn254_dbg_pairing_form, bn254_dbg_pairing_plan.  No key: one workspace per DEVICE, shared by every call on it, so calls on a
 // device are serialised the way a (key, device) is in the Groth16 entries -- the enqueue under the device's lock, after a wait (on the GPU) for the completion event
 // of the previous call.
 // Not part of the one-translation-unit host build of bn254_capi.hip (tests/hostsan/hostsan_main.cpp): a harness that wants it includes this file itself
@@ -14,6 +15,14 @@
 
 // BN254_PAIRING_PASS (tests; read once when the library is loaded) lowers the items per pass, 64 at least
 static const size_t g_pb_pass_items = [] { long v = env_long("BN254_PAIRING_PASS", (long)PB_PASS_ITEMS); return (size_t)(v < 64 ? 64 : (v > (long)PB_PASS_ITEMS ? (long)PB_PASS_ITEMS : v)); }();
+
+// The knob of a launch's form (bn254_set_pairing_params; BN254_PAIRING_COOP_MAX gives the initial value once, at load time): launches of up to this many items take the
+// cooperative form (k_coop12_miller_pairs), larger ones the lane form; 0: always the lane form.  BN254_COOP=0 switches it off (bn254_g16_plan.h::pairing_form)
+static long pb_coop_clamp(long v) { return v > (long)COOP12_MAX_PROOFS ? (long)COOP12_MAX_PROOFS : v; }
+static std::atomic<long> g_pb_coop_max{[] { long v = env_long("BN254_PAIRING_COOP_MAX", (long)PAIRING_COOP_MAX_DEFAULT); return v < 0 ? (long)PAIRING_COOP_MAX_DEFAULT : pb_coop_clamp(v); }()};
+static inline int pb_form(size_t n_pairs, size_t n) { return bn254::pairing_form(n_pairs, n, (size_t)g_pb_coop_max.load(std::memory_order_relaxed), bn254::knob_coop_on()); }
+// bn254_pairing_state: launches enqueued so far in the cooperative | the lane form
+static std::atomic<uint64_t> g_pb_launches[2];
 
 // The passes of a call, without a device (bn254_dbg_pairing_plan reads the same functions).  ws_items: the workspace a reservation of n items allocates; host_pass:
 // the items per pass of the host entries, every one of which fits that reservation
@@ -57,7 +66,9 @@ int pb_ensure(PbDev& d, int device, size_t n) {
   return d.ws.ensure(pb_ws_items(n) * (size_t)(G16_WS_BYTES_PER_PROOF / 4));
 }
 // caller holds d.mu; everything on `user`, nothing allocated.  verdict: the status bytes are ACCEPT / REJECT; d_gt (may be null): the GT values
-int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* d_status, uint8_t* d_gt, bool verdict, hipStream_t user) {
+// force: PAIRING_FORM_PLAN, or the form every launch takes (the probe; the caller has checked n against the cooperative range).  A launch is never split between forms
+int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* d_status, uint8_t* d_gt, bool verdict, hipStream_t user,
+               int force = bn254::PAIRING_FORM_PLAN) {
   const size_t cap = d.ws_items();
   if (cap == 0) return set_err(BN254_E_BAD_ARG, "pairing workspace not allocated (internal sizing error)");
   if (d.busy_valid) HIPCK(hipStreamWaitEvent(user, d.busy_ev, 0));
@@ -65,8 +76,10 @@ int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pa
     bn254::PairingLaunchArgs a;
     a.pairs = d_pairs + off * item_stride; a.item_stride = item_stride; a.n_pairs = (int)n_pairs; a.n = n - off < cap ? n - off : cap;
     a.ws = d.ws; a.status = d_status + off; a.one = verdict ? (const int32_t*)d.one : nullptr; a.out_gt = d_gt ? d_gt + 384 * off : nullptr;
+    a.form = force != bn254::PAIRING_FORM_PLAN ? force : pb_form(n_pairs, a.n);
     const hipError_t e = bn254_launch_pairing_batch(a, user);
     if (e != hipSuccess) return launch_err(e, "pairing batch");
+    g_pb_launches[a.form == bn254::PAIRING_FORM_COOP ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
   }
   HIPCK(hipEventRecord(d.busy_ev, user));
   d.busy_valid = true;
@@ -85,7 +98,7 @@ int pb_check_args(const void* pairs, size_t item_stride, size_t n_pairs, size_t 
 }
 
 // a host-buffer call: passes of pb_host_pass items through the pinned staging; returns with the status bytes (and GT values) of every item
-int pb_host_call(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device, bool verdict) {
+int pb_host_call(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device, bool verdict, int force = bn254::PAIRING_FORM_PLAN) {
   PbDev* d = pb_dev(device);
   std::lock_guard<std::mutex> lk(d->mu);
   const size_t pass = pb_host_pass(n_pairs, n), rec = (size_t)PB_PAIR_LEN * n_pairs;
@@ -98,7 +111,7 @@ int pb_host_call(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_
     if (item_stride == rec) parallel_copy(d->h_in, pairs + off * rec, m * rec);
     else for (size_t i = 0; i < m; i++) memcpy(d->h_in + i * rec, pairs + (off + i) * item_stride, rec);
     HIPCK(hipMemcpyAsync(d->d_in, d->h_in, m * rec, hipMemcpyHostToDevice, s));
-    int r = pb_enqueue(*d, d->d_in, rec, n_pairs, m, d->d_status, out_gt ? (uint8_t*)d->d_gt : nullptr, verdict, s);
+    int r = pb_enqueue(*d, d->d_in, rec, n_pairs, m, d->d_status, out_gt ? (uint8_t*)d->d_gt : nullptr, verdict, s, force);
     if (r) return r;
     HIPCK(hipMemcpyAsync(d->h_status, d->d_status, m, hipMemcpyDeviceToHost, s));
     if (out_gt) HIPCK(hipMemcpyAsync(d->h_gt, d->d_gt, m * 384, hipMemcpyDeviceToHost, s));
@@ -164,6 +177,38 @@ int bn254_dbg_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_p
   if (device >= 0) return pb_host_call(pairs, item_stride, n_pairs, n, out_gt, status, device, true);
   const int run_steps = bn254::knob_run_steps_pairing_batch();      // the loop cut into runs as the launcher cuts it (BN254_MILLER_RUN_STEPS)
   for (size_t i = 0; i < n; i++) status[i] = bn254::pb_item_on_host(pairs + i * item_stride, (int)n_pairs, out_gt ? out_gt + 384 * i : nullptr, run_steps);
+  return BN254_OK;
+}
+
+// bn254_dbg_pairing_batch with the form of every launch forced: 0 as that probe (device -1: the host compile), 1 the lane kernels, 2 the cooperative kernel
+int bn254_dbg_pairing_batch_form(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device, int form) {
+  if (form == bn254::PAIRING_FORM_PLAN) return bn254_dbg_pairing_batch(pairs, item_stride, n_pairs, n, out_gt, status, device);
+  bool done;
+  int rc = pb_check_args(pairs, item_stride, n_pairs, n, status, nullptr, false, &done);
+  if (rc) return rc;
+  if ((form != bn254::PAIRING_FORM_LANES && form != bn254::PAIRING_FORM_COOP) || device < 0) return set_err(BN254_E_BAD_ARG, "bad argument: form 1 (lane) and 2 (cooperative) run on a device");
+  if (form == bn254::PAIRING_FORM_COOP && n > (size_t)COOP12_MAX_PROOFS) return set_err(BN254_E_BAD_ARG, "bad argument: the cooperative form takes at most 30 720 items");
+  if (done) return BN254_OK;
+  return pb_host_call(pairs, item_stride, n_pairs, n, out_gt, status, device, true, form);
+}
+// the plan's answer for a launch of n items of n_pairs pairs under the knobs as they are now (1 lane, 2 cooperative); no device touched
+int bn254_dbg_pairing_form(size_t n_pairs, size_t n, int* form) {
+  if (!form || n_pairs < 1 || n_pairs > BN254_PAIRING_MAX_PAIRS) return set_err(BN254_E_BAD_ARG, "bad argument");
+  *form = pb_form(n_pairs, n);
+  return BN254_OK;
+}
+
+void bn254_set_pairing_params(long coop_max) {
+  if (coop_max >= 0) g_pb_coop_max.store(pb_coop_clamp(coop_max));
+}
+int bn254_pairing_params(long out[1]) {
+  if (!out) return set_err(BN254_E_BAD_ARG, "bad argument");
+  out[0] = g_pb_coop_max.load();
+  return BN254_OK;
+}
+int bn254_pairing_state(uint64_t out[2]) {
+  if (!out) return set_err(BN254_E_BAD_ARG, "bad argument");
+  for (int i = 0; i < 2; i++) out[i] = g_pb_launches[i].load(std::memory_order_relaxed);
   return BN254_OK;
 }
 

@@ -107,12 +107,14 @@ __device__ __forceinline__ void c12_mul_line_fp(const Coop12& co, int s, const F
   const Fp r = fp_dot(dplus(k, d0), dplus(k1.c0, d3.p), dplus(k1.c1, d3.q), dplus(k3.c0, d4.p), dplus(k3.c1, d4.q));
   co.put(s, fp_select(keep, k, r));
 }
-__device__ __forceinline__ void c12_mul_line_fp2(const Coop12& co, int s, const C12H& d0, const C12H& d3, const C12H& d4) {
+// d0 in Fp2 (the line of a variable pair).  keep as above: the own half of k_c is already in hand
+__device__ __forceinline__ void c12_mul_line_fp2(const Coop12& co, int s, const C12H& d0, const C12H& d3, const C12H& d4, bool keep = false) {
   c12_publish_xi(co, s);
   const uint32_t c = co.c;
   const Fp2 k0 = co.coef(s, c);
   const Fp2 k1 = co.coef(c >= 1 ? s : C12_X, (c + 5) % 6), k3 = co.coef(c >= 3 ? s : C12_X, (c + 3) % 6);
-  co.put(s, fp_dot(dplus(k0.c0, d0.p), dplus(k0.c1, d0.q), dplus(k1.c0, d3.p), dplus(k1.c1, d3.q), dplus(k3.c0, d4.p), dplus(k3.c1, d4.q)));
+  const Fp r = fp_dot(dplus(k0.c0, d0.p), dplus(k0.c1, d0.q), dplus(k1.c0, d3.p), dplus(k1.c1, d3.q), dplus(k3.c0, d4.p), dplus(k3.c1, d4.q));
+  co.put(s, fp_select(keep, fp_select(co.h != 0, k0.c1, k0.c0), r));
 }
 // ---- general product d <- a * (conj?) b:  r_j = sum_t (xi if t > j) a_t b_((j - t) mod 6): xi image of a, i image of (conj?) b --------------------------------
 __device__ __noinline__ void c12_mul(const Coop12 co, int d, int a, int b, bool conj_b) {
@@ -419,26 +421,29 @@ __device__ __forceinline__ Fp c12_prod(const Coop12& co, const Fp2& u, const Fp2
   return fp_dot(dplus(u.c0, vh.p), dplus(u.c1, vh.q));
 }
 struct C12Line { Fp2 d0, d3, d4, s1, s2, cz; };   // the variable pair's line at A; m1 X_L, m2 x_C and c1 Z_L of the two table-driven pairs (L projective)
-__device__ __forceinline__ void c12_g2_double(const Coop12& co, G2Proj& t, const Fp& xa, const Fp& ya, const Fp2& m1, const Fp& xl, const Fp2& m2, const Fp& xc, const Fp2& c1,
-                                              const Fp& zl, C12Line& out) {
+// KEYS: the three key-side products ride in the rounds' free positions (Groth16).  Without them (the batch pairing product: variable pairs only) those positions repeat
+// a neighbour's operands and s1, s2, cz are left alone; the rounds are the same code either way
+template <bool KEYS>
+__device__ __forceinline__ void c12_g2_double_t(const Coop12& co, G2Proj& t, const Fp& xa, const Fp& ya, const Fp2& m1, const Fp& xl, const Fp2& m2, const Fp& xc, const Fp2& c1,
+                                                const Fp& zl, C12Line& out) {
   const uint32_t c = co.c;
   const Fp2 yz = fp2_add(t.y, t.z);
   // round 1: X Y, Y^2, Z^2, X^2, (Y + Z)^2, m1 xl
-  co.put(C12_R1, c12_prod(co, c12_sel6(c, t.x, t.y, t.z, t.x, yz, m1), c12_sel6(c, t.y, t.y, t.z, t.x, yz, c12_fp_as_fp2(xl))));
+  co.put(C12_R1, c12_prod(co, c12_sel6(c, t.x, t.y, t.z, t.x, yz, KEYS ? m1 : yz), c12_sel6(c, t.y, t.y, t.z, t.x, yz, KEYS ? c12_fp_as_fp2(xl) : yz)));
   const Fp2 A = co.coef(C12_R1, 0), B = co.coef(C12_R1, 1), C = co.coef(C12_R1, 2), J = co.coef(C12_R1, 3), S = co.coef(C12_R1, 4);
-  out.s1 = co.coef(C12_R1, 5);
+  if constexpr (KEYS) out.s1 = co.coef(C12_R1, 5);
   const Fp2 H = fp2_sub2(S, B, C);                       // 2 Y Z
   // round 2: B H, -, b3 C, H ya, J xa, m2 xc
   const Fp2 b3 = fp2_from_limbs(BN_TWIST_3B0, BN_TWIST_3B1);
-  co.put(C12_R2, c12_prod(co, c12_sel6(c, B, B, b3, H, J, m2), c12_sel6(c, H, B, C, c12_fp_as_fp2(ya), c12_fp_as_fp2(xa), c12_fp_as_fp2(xc))));
+  co.put(C12_R2, c12_prod(co, c12_sel6(c, B, B, b3, H, J, KEYS ? m2 : J), c12_sel6(c, H, B, C, c12_fp_as_fp2(ya), c12_fp_as_fp2(xa), c12_fp_as_fp2(KEYS ? xc : xa))));
   const Fp2 BH = co.coef(C12_R2, 0), E = co.coef(C12_R2, 2), Hy = co.coef(C12_R2, 3), Jx = co.coef(C12_R2, 4);
-  out.s2 = co.coef(C12_R2, 5);
+  if constexpr (KEYS) out.s2 = co.coef(C12_R2, 5);
   const Fp2 F = fp2_mul_small(E, 3);
   const Fp2 BmF = fp2_sub(B, F), BF = fp2_add(B, F);
   // round 3: E^2, A (B - F), (B + F)^2, c1 zl
-  co.put(C12_R3, c12_prod(co, c12_sel6(c, E, A, BF, c1, E, E), c12_sel6(c, E, BmF, BF, c12_fp_as_fp2(zl), E, E)));
+  co.put(C12_R3, c12_prod(co, c12_sel6(c, E, A, BF, KEYS ? c1 : E, E, E), c12_sel6(c, E, BmF, BF, KEYS ? c12_fp_as_fp2(zl) : E, E, E)));
   const Fp2 E2 = co.coef(C12_R3, 0), AX = co.coef(C12_R3, 1), BF2 = co.coef(C12_R3, 2);
-  out.cz = co.coef(C12_R3, 3);
+  if constexpr (KEYS) out.cz = co.coef(C12_R3, 3);
   t.x = fp2_dbl(AX);
   t.y = fp2_sub(BF2, fp2_mul_small(E2, 12));
   t.z = fp2_mul_small(BH, 4);
@@ -446,22 +451,23 @@ __device__ __forceinline__ void c12_g2_double(const Coop12& co, G2Proj& t, const
   out.d3 = fp2_mul_small(Jx, 3);
   out.d4 = fp2_sub(E, B);
 }
-__device__ __forceinline__ void c12_g2_add(const Coop12& co, G2Proj& t, const Fp2& qx, const Fp2& qy, const Fp& xa, const Fp& ya, const Fp2& m1, const Fp& xl, const Fp2& m2,
-                                           const Fp& xc, const Fp2& c1, const Fp& zl, C12Line& out) {
+template <bool KEYS>
+__device__ __forceinline__ void c12_g2_add_t(const Coop12& co, G2Proj& t, const Fp2& qx, const Fp2& qy, const Fp& xa, const Fp& ya, const Fp2& m1, const Fp& xl, const Fp2& m2,
+                                             const Fp& xc, const Fp2& c1, const Fp& zl, C12Line& out) {
   const uint32_t c = co.c;
   // round 1: yQ Z, xQ Z, -, -, -, m1 xl
-  co.put(C12_R1, c12_prod(co, c12_sel6(c, qy, qx, qx, qx, qx, m1), c12_sel6(c, t.z, t.z, t.z, t.z, t.z, c12_fp_as_fp2(xl))));
+  co.put(C12_R1, c12_prod(co, c12_sel6(c, qy, qx, qx, qx, qx, KEYS ? m1 : qx), c12_sel6(c, t.z, t.z, t.z, t.z, t.z, KEYS ? c12_fp_as_fp2(xl) : t.z)));
   const Fp2 O = fp2_sub(t.y, co.coef(C12_R1, 0)), L = fp2_sub(t.x, co.coef(C12_R1, 1));
-  out.s1 = co.coef(C12_R1, 5);
+  if constexpr (KEYS) out.s1 = co.coef(C12_R1, 5);
   // round 2: O^2, L^2, xQ O, L yQ, L ya, m2 xc
-  co.put(C12_R2, c12_prod(co, c12_sel6(c, O, L, qx, L, L, m2), c12_sel6(c, O, L, O, qy, c12_fp_as_fp2(ya), c12_fp_as_fp2(xc))));
+  co.put(C12_R2, c12_prod(co, c12_sel6(c, O, L, qx, L, L, KEYS ? m2 : L), c12_sel6(c, O, L, O, qy, c12_fp_as_fp2(ya), c12_fp_as_fp2(KEYS ? xc : ya))));
   const Fp2 Cc = co.coef(C12_R2, 0), D = co.coef(C12_R2, 1), xqO = co.coef(C12_R2, 2), Lyq = co.coef(C12_R2, 3);
   out.d0 = co.coef(C12_R2, 4);
-  out.s2 = co.coef(C12_R2, 5);
+  if constexpr (KEYS) out.s2 = co.coef(C12_R2, 5);
   // round 3: L D, Z C, X D, O xa, c1 zl
-  co.put(C12_R3, c12_prod(co, c12_sel6(c, L, t.z, t.x, O, c1, O), c12_sel6(c, D, Cc, D, c12_fp_as_fp2(xa), c12_fp_as_fp2(zl), O)));
+  co.put(C12_R3, c12_prod(co, c12_sel6(c, L, t.z, t.x, O, KEYS ? c1 : O, O), c12_sel6(c, D, Cc, D, c12_fp_as_fp2(xa), KEYS ? c12_fp_as_fp2(zl) : O, O)));
   const Fp2 E = co.coef(C12_R3, 0), Fz = co.coef(C12_R3, 1), G = co.coef(C12_R3, 2), Ox = co.coef(C12_R3, 3);
-  out.cz = co.coef(C12_R3, 4);
+  if constexpr (KEYS) out.cz = co.coef(C12_R3, 4);
   const Fp2 H = fp2_sub(fp2_add(E, Fz), fp2_dbl(G));
   const Fp2 GmH = fp2_sub(G, H);
   // round 4: L H, (G - H) O, Y E, E Z     (round-1 slot reused: its values are in registers by now)
@@ -471,6 +477,21 @@ __device__ __forceinline__ void c12_g2_add(const Coop12& co, G2Proj& t, const Fp
   t.z = co.coef(C12_R1, 3);
   out.d3 = fp2_neg(Ox);
   out.d4 = fp2_sub(xqO, Lyq);
+}
+__device__ __forceinline__ void c12_g2_double(const Coop12& co, G2Proj& t, const Fp& xa, const Fp& ya, const Fp2& m1, const Fp& xl, const Fp2& m2, const Fp& xc, const Fp2& c1,
+                                              const Fp& zl, C12Line& out) {
+  c12_g2_double_t<true>(co, t, xa, ya, m1, xl, m2, xc, c1, zl, out);
+}
+__device__ __forceinline__ void c12_g2_add(const Coop12& co, G2Proj& t, const Fp2& qx, const Fp2& qy, const Fp& xa, const Fp& ya, const Fp2& m1, const Fp& xl, const Fp2& m2,
+                                           const Fp& xc, const Fp2& c1, const Fp& zl, C12Line& out) {
+  c12_g2_add_t<true>(co, t, qx, qy, xa, ya, m1, xl, m2, xc, c1, zl, out);
+}
+// the variable pair alone: d0, d3, d4 of `out`
+__device__ __forceinline__ void c12_g2_double_var(const Coop12& co, G2Proj& t, const Fp& xa, const Fp& ya, C12Line& out) {
+  c12_g2_double_t<false>(co, t, xa, ya, t.x, xa, t.x, xa, t.x, xa, out);
+}
+__device__ __forceinline__ void c12_g2_add_var(const Coop12& co, G2Proj& t, const Fp2& qx, const Fp2& qy, const Fp& xa, const Fp& ya, C12Line& out) {
+  c12_g2_add_t<false>(co, t, qx, qy, xa, ya, qx, xa, qx, xa, qx, xa, out);
 }
 __device__ __forceinline__ G1Aff c12_msm_entry(const int32_t* __restrict__ msm_tab, size_t idx) {
   const int4* e = (const int4*)(msm_tab + idx * MSM_ENTRY_DWORDS);
@@ -705,6 +726,72 @@ k_coop12_miller_g16_keys(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t
   c12_g16_verdict(co, status, p, pl, st, pending, q, t, key.target, key.inputs_match);
 }
 
+// ---- the batch pairing product (bn254_pairing_batch.h): 1 .. VP_MAX_PAIRS VARIABLE pairs per item and no key, after the unchanged k_pairing_load -----------------
+// bn254_vm.h::vm_miller_run_var step for step: the squaring of f once per doubling step, then for every pair j its G2 step on T_j and the product of f with its line.
+// T_j cannot stay in registers for eight pairs.  The Miller loop touches the slots 0 (f), 7 (C12_R1 / C12_B), 10 (C12_X), 11 (C12_I / C12_R2) and 12 (C12_R3); the
+// eight others (1 .. 6, 8, 9) hold values of the final exponentiation and are dead until it starts.  A slot is 12 Fp per item, exactly the 12 Fp of a pair in the
+// workspace map: lane (c, h) of the item keeps Fp number 2 c + h of P (2) | Q (4) | T (6), so Q is coefficients 1, 2 of the slot and T coefficients 3, 4, 5.
+// Pair j lives in slot c12_pair_slot(j); the image stays at 13 slots.  A G2 step reads P, Q and T whole before the lanes of T write their halves back.
+__device__ __forceinline__ int c12_pair_slot(int j) { return j < 6 ? j + 1 : j + 2; }
+static_assert(VP_MAX_PAIRS == 8 && VP_PAIR_ELEMS == 12, "one LDS slot per pair: eight slots are free during the Miller loop, a slot is twelve Fp per item");
+__global__ void __launch_bounds__(64)
+k_coop12_miller_pairs(int32_t* ws, uint32_t n, uint8_t* status, const uint8_t* __restrict__ kinds, int n_pairs, const int32_t* __restrict__ target) {
+  C12_PROLOGUE();
+  int np = __builtin_amdgcn_readfirstlane(n_pairs);
+  np = np < 1 ? 1 : (np > VP_MAX_PAIRS ? VP_MAX_PAIRS : np);
+  const int F = C12_SLOT(VE_F);
+  const uint32_t l12 = 2 * c + h;
+  const uint32_t ident = (uint32_t)ws[(size_t)VP_IDENT * BN_NL * n + pc];      // digit 0 of VP_IDENT: the item's identity bits
+  co.put(F, l12 == 0 ? fp_one() : fp_zero());
+  for (int j = 0; j < np; j++) {   // P | Q as the loader left them (vp_p(j) .. + 5), T = (Q, 1)
+    const Fp v = c12_ws_ld(ws, n, pc, l12 < 6 ? vp_p(j) + (int)l12 : l12 < 10 ? vp_q(j) + (int)l12 - 6 : vp_p(j));
+    co.put(c12_pair_slot(j), l12 == 10 ? fp_one() : l12 == 11 ? fp_zero() : v);
+  }
+  for (int s = 0; s < BN_ATE_STEPS; s++) {
+    const int kind = __builtin_amdgcn_readfirstlane((int)kinds[s]);
+    if (kind == 0 && s != 0) c12_sqr(co, F);
+    for (int j = 0; j < np; j++) {
+      const int sl = c12_pair_slot(j);
+      const Fp xa = co.at(sl, co.g0), ya = co.at(sl, co.g0 + 1);
+      G2Proj t; t.x = co.coef(sl, 3); t.y = co.coef(sl, 4); t.z = co.coef(sl, 5);
+      C12Line ln;
+      if (kind == 0) {
+        c12_g2_double_var(co, t, xa, ya, ln);
+      } else {
+        G2Aff q; q.x = co.coef(sl, 1); q.y = co.coef(sl, 2);
+        G2Aff b = q;
+        if (kind == 2) b = g2_neg(q);
+        else if (kind == 3) b = g2_psi_affine(q);
+        else if (kind == 4) b = g2_neg(g2_psi2_affine(q));
+        c12_g2_add_var(co, t, b.x, b.y, xa, ya, ln);
+      }
+      if (c >= 3) { const Fp2 nt = fp2_select(c == 3, t.x, fp2_select(c == 4, t.y, t.z)); co.put(sl, fp_select(h != 0, nt.c1, nt.c0)); }
+      // a pair with an identity on either side contributes 1; its G2 steps above still ran: the r-torsion test of a finite Q_j beside the identity of G1 needs T_j
+      c12_mul_line_fp2(co, F, c12_halves(ln.d0, h), c12_halves(ln.d3, h), c12_halves(ln.d4, h), vp_skips(ident, j));
+    }
+  }
+  // the r-torsion test of every finite Q_j from T_j (vm_g2_ate_check; c12_g16_verdict), every lane for itself, before the final exponentiation takes the slots
+  bool in_g2 = true;
+  for (int j = 0; j < np; j++) {
+    const int sl = c12_pair_slot(j);
+    const Fp2 qx = co.coef(sl, 1), qy = co.coef(sl, 2), X = co.coef(sl, 3), Y = co.coef(sl, 4), Z = co.coef(sl, 5);
+    const Fp2 sx = fp2_mul(fp2_conj(qx), frob_coeff(3, 2)), sy = fp2_neg(fp2_mul(fp2_conj(qy), frob_coeff(3, 3)));
+    const bool ok = !fp2_is_zero(Z) & fp2_eq(X, fp2_mul(sx, Z)) & fp2_eq(Y, fp2_mul(sy, Z));
+    in_g2 &= ok | !vp_q_finite(ident, j);
+  }
+  Coop12Ops ops{co};
+  vm_final_exp_program(ops);
+  const bool writer = pending && c == 0 && h == 0;
+  if (target) {   // the verdict in the launch
+    const bool acc = c12_eq_const(co, C12_SLOT(VE_S0), target, pl);
+    if (writer) status[p] = !in_g2 ? BN254_ST_NOT_IN_SUBGROUP : acc ? BN254_ST_ACCEPT : BN254_ST_REJECT;
+    return;
+  }
+  // the GT value to VE_S0 for the tails of the lane form (k_pairing_store, k_g16_compare), which pass over an item that is no longer pending
+  if (writer && !in_g2) status[p] = BN254_ST_NOT_IN_SUBGROUP;
+  c12_store_f12(co, ws, n, p, C12_SLOT(VE_S0), VE_S0, pending && in_g2);
+}
+
 }  // namespace bn254
 
 using namespace bn254;
@@ -752,6 +839,10 @@ hipError_t bn254_coop12_miller_fixed_keys(int32_t* ws, uint8_t* status, size_t n
                                           const int32_t* target, int reject_code, hipStream_t s) {
   if (n == 0 || n_keys == 0 || key_shift > 31) return hipErrorInvalidValue;
   return c12_launch<true>(k_coop12_miller_fixed_keys, ws, status, n, s, key_words, key_shift, desc, n_keys, target, reject_code);
+}
+hipError_t bn254_coop12_miller_pairs(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* target, hipStream_t s) {
+  if (n == 0 || n > (size_t)COOP12_MAX_PROOFS || n_pairs < 1 || n_pairs > VP_MAX_PAIRS) return hipErrorInvalidValue;
+  return c12_launch<true>(k_coop12_miller_pairs, ws, status, n, s, n_pairs, target);
 }
 // probe: op 0 mul 1 mul by conj(b) 2 conj(a) * b 3 sqr 4 cyclo_sqr_n (arg squarings) 5 frob (j = arg) 6 inv 7 conj 8 mul_line_fp 9 mul_line_fp with keep
 // 10 mul_line_fp2 11 k_coop12_final_exp 12 c12_eq_const against target

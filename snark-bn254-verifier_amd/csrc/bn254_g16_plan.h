@@ -133,6 +133,19 @@ enum { G16_KEYS_FORM_GROUPED = 0, G16_KEYS_FORM_DIRECT = 1 };
 #define G16_KEYS_COOP_MAX_DEFAULT COOP12_MAX_PROOFS
 inline int g16_keys_form(size_t n, size_t keys_coop_max, bool coop_on) { return coop_on && n <= keys_coop_max && n <= (size_t)COOP12_MAX_PROOFS ? G16_KEYS_FORM_DIRECT : G16_KEYS_FORM_GROUPED; }
 
+// ---- the form of ONE launch of the batch pairing product (bn254_launch_pairing_batch) ---------------------------------------------------------------------------
+// Up to coop_max items (bn254_set_pairing_params; never with BN254_COOP=0, never above the cooperative kernels' range) the cooperative form: k_pairing_load, then
+// k_coop12_miller_pairs, twelve lanes per item.  Otherwise the lane form, one item per lane.  A launch takes one form whole.  The rule is n <= coop_max, not
+// n * n_pairs <= coop_max, because that is what was measured (profiles/r15_pairing_coop.txt): with both forms alternating in one session at
+// n in {1, 256, 1024, 4096, 8192, 16 384, 30 720} and 1, 2, 3, 4, 8 pairs, the largest size at which the cooperative median is not above the lane median is 16 384 at
+// EVERY pair count (8 pairs: 24.3 against 31.9 ms there, 35.9 against 32.1 ms at 30 720; 1 pair: 6.30 against 9.05 and 9.22 against 9.18) -- the default.
+enum { PAIRING_FORM_PLAN = 0, PAIRING_FORM_LANES = 1, PAIRING_FORM_COOP = 2 };
+#define PAIRING_COOP_MAX_DEFAULT 16384
+inline int pairing_form(size_t n_pairs, size_t n, size_t coop_max, bool coop_on) {
+  (void)n_pairs;
+  return coop_on && n <= coop_max && n <= (size_t)COOP12_MAX_PROOFS ? PAIRING_FORM_COOP : PAIRING_FORM_LANES;
+}
+
 // ---- one workspace chunk (at most G16_MAX_BATCH proofs) of a batch: its sub-batches -----------------------------------------------------------------------
 #define G16_MAX_PARTS 32
 struct G16Part {

@@ -6,7 +6,8 @@
 //                      decides the r-torsion tests and writes the status of an item that failed one
 //   k_pairing_store    the store tail: VE_S0 in the 384-byte format 0 of bn254_dbg_pairing
 // then vm_final_exp_program through LaunchOps and k_g16_compare against 1 in GT (the kernels of bn254_kernels.hip).
-// Only the lane form exists: a cooperative twelve-lane form for small batches is out of scope of this revision (bn254_pairing_batch.h).
+// A small launch (bn254_g16_plan.h::pairing_form) takes the cooperative form instead: k_pairing_load, then bn254_coop12.hip::k_coop12_miller_pairs, twelve lanes per
+// item, and -- unless the verdict alone is wanted, which that kernel writes itself -- the same tails.  The choice is made here, in bn254_launch_pairing_batch.
 #include <hip/hip_runtime.h>
 #include "bn254_launch_ops.h"
 #include "bn254_g16_plan.h"
@@ -61,7 +62,19 @@ hipError_t bn254_launch_pairing_batch(const PairingLaunchArgs& a, hipStream_t s)
   if (a.n > (size_t)G16_MAX_LAUNCH || a.n_pairs < 1 || a.n_pairs > PB_MAX_PAIRS || a.item_stride < (size_t)PB_PAIR_LEN * (size_t)a.n_pairs || (!a.one && !a.out_gt)) return hipErrorInvalidValue;
   const unsigned grid = grid_for(a.n);
   const uint32_t nn = (uint32_t)a.n;
+  const int form = a.form != PAIRING_FORM_PLAN ? a.form : pairing_form((size_t)a.n_pairs, a.n, (size_t)PAIRING_COOP_MAX_DEFAULT, knob_coop_on());
+  if (form != PAIRING_FORM_LANES && (form != PAIRING_FORM_COOP || a.n > (size_t)COOP12_MAX_PROOFS)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_pairing_load, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, nn, a.ws, a.status);
+  if (form == PAIRING_FORM_COOP) {
+    // twelve lanes per item: the Miller loop, the r-torsion tests and the final exponentiation in one launch -- with the verdict when that is all the caller wants,
+    // otherwise the GT value to VE_S0 and the tails of the lane form
+    const bool fused = a.one && !a.out_gt;
+    const hipError_t e = bn254_coop12_miller_pairs(a.ws, a.status, a.n, a.n_pairs, fused ? a.one : nullptr, s);
+    if (e != hipSuccess || fused) return e;
+    if (a.out_gt) hipLaunchKernelGGL(k_pairing_store, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.out_gt, a.one ? 0 : 1);
+    if (a.one) hipLaunchKernelGGL(k_g16_compare, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.one, (int)BN254_ST_REJECT);
+    return hipGetLastError();
+  }
   const MillerKinds& kinds = miller_step_table().packed;
   const int per = knob_run_steps_pairing_batch();
   for (int s0 = 0; s0 < BN_ATE_STEPS; s0 += per)

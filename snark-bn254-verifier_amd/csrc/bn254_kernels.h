@@ -241,6 +241,10 @@ hipError_t bn254_coop12_miller_fixed(int32_t* ws, uint8_t* status, size_t n, int
 // the two-pair check with the key per item: item p belongs to key key_words[p >> key_shift] of the list and reads that key's tab0 / tab1 (store mode without a target)
 hipError_t bn254_coop12_miller_fixed_keys(int32_t* ws, uint8_t* status, size_t n, const uint32_t* key_words, uint32_t key_shift, const bn254::PlonkKeyDesc* desc, uint32_t n_keys,
                                           const int32_t* target, int reject_code, hipStream_t s);
+// the batch pairing product (bn254_pairing_batch.h) on n <= COOP12_MAX_PROOFS items of n_pairs variable pairs each, after k_pairing_load: the Miller loop of every pair,
+// the r-torsion tests (NOT_IN_SUBGROUP to the status byte), the final exponentiation; with a target the verdict ACCEPT / REJECT in the same launch, without one the GT
+// value of every item still pending to VE_S0
+hipError_t bn254_coop12_miller_pairs(int32_t* ws, uint8_t* status, size_t n, int n_pairs, const int32_t* target, hipStream_t s);
 static inline size_t bn254_coop_max_proofs() { return COOP12_MAX_PROOFS; }
 static inline size_t bn254_coop_max_proofs_fixed() { return COOP12_MAX_PROOFS_FIXED; }
 double bn254_measure_valu_sustained(double ms_target);   // the same kernel back to back for ms_target milliseconds, one interval

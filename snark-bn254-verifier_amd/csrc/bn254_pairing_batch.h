@@ -3,8 +3,9 @@
 // like bn254_vm.h: the loader of one item (range and on-curve checks in record order, the points and the identity bits into the workspace), and the whole item on a
 // plain-array accessor -- loader, vm_miller_run_var, vm_final_exp_program, the compare with 1 -- so that the operation sequence the GPU runs is checked against the
 // oracle without one.
-// Only the LANE form (one item per lane) exists.  A cooperative twelve-lane form for small batches, as the Groth16 path has (bn254_coop12.hip), is out of scope of
-// this revision: a small batch leaves most of the GPU idle.
+// Two forms of the launches: the LANE form (one item per lane, bn254_k_pairing.hip) and, for small batches, which leave most of the GPU idle in the lane form, the
+// cooperative twelve-lane form (bn254_coop12.hip::k_coop12_miller_pairs after the same loader).  bn254_g16_plan.h::pairing_form chooses; the status and GT bytes are
+// the same.
 #pragma once
 #include "bn254_vm.h"
 #include "bn254_kernels.h"
@@ -126,6 +127,7 @@ struct PairingLaunchArgs {
   const int32_t* one;                         // 108 dwords: 1 in GT (the verdict tail's target); null: no verdict
   uint8_t* out_gt;                            // n x 384 bytes (the store tail), or null.  With a store tail AND a verdict the status bytes are the verdict's; with the
                                               // store tail alone a pending item ends as BN254_ST_ACCEPT ("the value is valid")
+  int form = 0;                               // bn254_g16_plan.h: PAIRING_FORM_PLAN (pairing_form at the default threshold), _LANES, _COOP (n <= COOP12_MAX_PROOFS)
 };
 
 }  // namespace bn254

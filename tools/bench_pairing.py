@@ -4,7 +4,12 @@ cell, and in the same session the exact Groth16 rate (bn254_groth16_verify_batch
   python tools/bench_pairing.py [--sizes 4096,65536] [--pairs 1,2,3,4,8] [--steps 5] [--out profiles/r14_pairing_batch.txt]
 The items are made of the A (G1) and B (G2) points of a synthetic Groth16 workload, pair j of item i being (A[i + 7 j], B[i + 13 j]) (indices modulo n): distinct valid
 points, so every item runs its loops to the end and is REJECT (checked).  Every call is timed on its own from the call to the status bytes on the device, after one
-warm-up call and a reservation; the median of --steps calls is reported.  Writes the table to --out and prints one JSON line."""
+warm-up call and a reservation; the median of --steps calls is reported.  Writes the table to --out and prints one JSON line.
+  --form plan   the form the library chooses (bn254_set_pairing_params as it stands; the default)
+  --form lane   bn254_set_pairing_params(0): the one-item-per-lane kernels at every size
+  --form coop   bn254_set_pairing_params(30720): the cooperative twelve-lane kernel wherever it can run (n <= 30 720)
+  --form both   both, ALTERNATING call by call inside every cell (lane, coop, lane, coop, ...), so that a drift of the machine meets both alike: the lane form of the
+                same session is the reference of every cooperative figure; the cell also gives the spread (min .. max) of each form's calls"""
 import argparse
 import importlib
 import json
@@ -23,6 +28,8 @@ def main():
     ap.add_argument("--pairs", type=str, default="1,2,3,4,8")
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "r14_pairing_batch.txt"))
+    ap.add_argument("--form", choices=("plan", "lane", "coop", "both"), default="plan")
+    ap.add_argument("--no-groth16", action="store_true", help="skip the Groth16 batch timed for orientation")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -43,23 +50,47 @@ def main():
                 times.append(time.perf_counter() - t)
         return statistics.median(times) * 1e3
 
+    COOP_MAX = 30720
+    knob0 = pkg.pairing_params()
+
+    def timed_both(fn):
+        """lane and cooperative calls alternating; -> {form: (median, min, max)} in ms"""
+        times = {"lane": [], "coop": []}
+        for it in range(args.steps + 1):
+            for form, knob in (("lane", 0), ("coop", COOP_MAX)):
+                pkg.set_pairing_params(knob)
+                torch.cuda.synchronize(dev)
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize(dev)
+                if it:
+                    times[form].append((time.perf_counter() - t) * 1e3)
+        pkg.set_pairing_params(knob0)
+        return {f: (statistics.median(v), min(v), max(v)) for f, v in times.items()}
+
+    if args.form == "lane":
+        pkg.set_pairing_params(0)
+    elif args.form == "coop":
+        pkg.set_pairing_params(COOP_MAX)
     rows, lines = [], []
     for n in sizes:
         vk, proofs, inputs, expected = pkg.synth_groth16(0xB2549000, 2, n, invalid_every=0, agree=True, threads=16)
         rec = np.frombuffer(proofs, dtype=np.uint8).reshape(n, 256)
         a, b = rec[:, 0:64], rec[:, 64:192]
-        pvk = pkg.PreparedVk(vk, pkg.VK_REFERENCE)
-        d_proofs = torch.from_numpy(rec.copy()).to(dev)
-        d_inputs = torch.frombuffer(bytearray(inputs), dtype=torch.uint8).to(dev)
         d_status = torch.zeros(n, dtype=torch.uint8, device=dev)
-        pvk.reserve(n, 0)
+        g16_ms = None
+        if not args.no_groth16:
+            pvk = pkg.PreparedVk(vk, pkg.VK_REFERENCE)
+            d_proofs = torch.from_numpy(rec.copy()).to(dev)
+            d_inputs = torch.frombuffer(bytearray(inputs), dtype=torch.uint8).to(dev)
+            pvk.reserve(n, 0)
 
-        def g16():
-            pvk.verify_batch_device(d_proofs.data_ptr(), d_inputs.data_ptr(), d_status.data_ptr(), n, 256, 2, 0, stream.cuda_stream)
+            def g16():
+                pvk.verify_batch_device(d_proofs.data_ptr(), d_inputs.data_ptr(), d_status.data_ptr(), n, 256, 2, 0, stream.cuda_stream)
 
-        g16_ms = timed(g16)
-        assert bytes(d_status.cpu().numpy().tobytes()) == expected
-        lines.append("n = %d   exact Groth16 (2 inputs, device entry): %.3f ms, %.0f proofs/s" % (n, g16_ms, n / g16_ms * 1e3))
+            g16_ms = timed(g16)
+            assert bytes(d_status.cpu().numpy().tobytes()) == expected
+            lines.append("n = %d   exact Groth16 (2 inputs, device entry): %.3f ms, %.0f proofs/s" % (n, g16_ms, n / g16_ms * 1e3))
         pkg.pairing_reserve(n, device=0)
         for k in pairs:
             items = np.empty((n, 192 * k), dtype=np.uint8)
@@ -72,13 +103,25 @@ def main():
             def run():
                 pkg.pairing_check_batch_device(d_items.data_ptr(), k, n, d_status.data_ptr(), device=0, stream=stream.cuda_stream)
 
+            if args.form == "both" and n <= COOP_MAX:
+                both = timed_both(run)
+                got = bytes(d_status.cpu().numpy().tobytes())
+                assert got == bytes([pkg.REJECT]) * n, "unexpected status bytes: %r" % {s: got.count(bytes([s])) for s in set(got)}
+                (lm, llo, lhi), (cm, clo, chi) = both["lane"], both["coop"]
+                rows.append({"n": n, "n_pairs": k, "lane_ms": round(lm, 3), "lane_min": round(llo, 3), "lane_max": round(lhi, 3), "coop_ms": round(cm, 3), "coop_min": round(clo, 3),
+                             "coop_max": round(chi, 3)})
+                lines.append("n = %6d   n_pairs = %d:  lane %8.3f ms (%.3f .. %.3f)   coop %8.3f ms (%.3f .. %.3f)   coop / lane %.2f" % (n, k, lm, llo, lhi, cm, clo, chi, cm / lm))
+                continue
             ms = timed(run)
             got = bytes(d_status.cpu().numpy().tobytes())
             assert got == bytes([pkg.REJECT]) * n, "unexpected status bytes: %r" % {s: got.count(bytes([s])) for s in set(got)}
-            rows.append({"n": n, "n_pairs": k, "ms": round(ms, 3), "items_per_s": round(n / ms * 1e3), "pairs_per_s": round(n * k / ms * 1e3), "groth16_ms": round(g16_ms, 3)})
-            lines.append("n = %d   n_pairs = %d: %.3f ms, %.0f items/s, %.0f pairs/s, %.2f x the Groth16 batch's time" % (n, k, ms, n / ms * 1e3, n * k / ms * 1e3, ms / g16_ms))
-    head = ["bn254_pairing_check_batch_device, device-resident items, one GPU (%s); median of %d calls per cell, each timed from the call to the status bytes on the device"
-            % (torch.cuda.get_device_name(0), args.steps), ""]
+            rows.append({"n": n, "n_pairs": k, "form": args.form, "ms": round(ms, 3), "items_per_s": round(n / ms * 1e3), "pairs_per_s": round(n * k / ms * 1e3),
+                         "groth16_ms": round(g16_ms, 3) if g16_ms else None})
+            lines.append("n = %d   n_pairs = %d: %.3f ms, %.0f items/s, %.0f pairs/s%s" % (n, k, ms, n / ms * 1e3, n * k / ms * 1e3,
+                                                                                        ", %.2f x the Groth16 batch's time" % (ms / g16_ms) if g16_ms else ""))
+    pkg.set_pairing_params(knob0)
+    head = ["bn254_pairing_check_batch_device, device-resident items, one GPU (%s); median of %d calls per cell, each timed from the call to the status bytes on the device; "
+            "form: %s" % (torch.cuda.get_device_name(0), args.steps, "lane and cooperative alternating call by call (median, min .. max)" if args.form == "both" else args.form), ""]
     with open(args.out, "w") as f:
         f.write("\n".join(head + lines) + "\n")
     print(json.dumps({"bench": "pairing_batch", "rows": rows}))

@@ -432,8 +432,59 @@ def coop12_callees(funcs, notes, keys_notes):
     return out, ops
 
 
+def coop12_pairs_kernel(funcs, frag, callees, ops, n_pairs):
+    """k_coop12_miller_pairs (the batch pairing product: n_pairs VARIABLE pairs per item, a run-time value; priced here for n_pairs pairs).  The step loop holds, in
+    address order: the squaring of f (a forward-branched block), ONE copy of the line product, which every path of the pair loop runs into, the addition side of the
+    pair loop (a forward-branched block: first the psi / psi^2 maps with their own copy of the addition rounds -- 2 of the 23 addition steps -- then the rounds of the
+    21 others) and the doubling side behind it, up to the next back edge.  Behind the loop: the r-torsion tests, one loop trip per pair."""
+    ins = callee_straight(funcs, frag)
+    lg, mads = loops_of(ins)
+    big = [g for g in lg if g[2] > 1000]
+    tail = [g for g in big if 1800 <= g[2] <= 2200 and len(g[1]) == 1]
+    assert len(tail) == 1, ("k_coop12_miller_pairs: one loop of r-torsion tests expected", big)
+    body = [g for g in big if g is not tail[0]]
+    lo, hi = min(g[0] for g in body), max(g[1][-1] for g in body)
+    assert hi < tail[0][0], ("k_coop12_miller_pairs: layout changed", big)
+    conds = []
+    for a, text, tgt in ins:
+        if lo <= a <= hi and tgt is not None and a < tgt <= hi + 8 and text.startswith("s_cbranch"):
+            m = count_in(mads, a + 1, tgt - 1)
+            if m >= 100:
+                conds.append((a + 1, tgt - 1, m))
+    sq = [c for c in conds if 700 <= c[2] <= 800]
+    side = [c for c in conds if 2400 <= c[2] <= 2800]
+    maps = [c for c in conds if 1500 <= c[2] <= 1700 and side and side[0][0] <= c[0] and c[1] <= side[0][1]]
+    assert len(sq) == 1 and len(side) == 1 and len(maps) == 1, ("k_coop12_miller_pairs: layout changed", conds)
+    (s_lo, s_hi, s_m), (a_lo, a_hi, a_m), (p_lo, p_hi, p_m) = sq[0], side[0], maps[0]
+    r_lo, r_hi = p_hi + 1, a_hi                                   # the addition rounds of the steps without a map
+    r_m = count_in(mads, r_lo, r_hi)
+    d_lo = a_hi + 1
+    d_hi = min(l for g in lg for l in g[1] if l > d_lo)
+    d_m = count_in(mads, d_lo, d_hi)
+    line_m = count_in(mads, lo, hi) - s_m - a_m - d_m
+    assert 950 <= r_m <= 1000 and 800 <= d_m <= 900 and 560 <= line_m <= 640 and p_m - r_m >= 600, (s_m, a_m, p_m, r_m, d_m, line_m)
+    steps, k = 88.0, float(n_pairs)
+    ranges = [(lo, hi, steps * k), (s_lo, s_hi, 64.0 / steps / k), (p_lo, p_hi, 2.0 / steps), (r_lo, r_hi, 21.0 / steps), (d_lo, d_hi, 65.0 / steps),
+              (tail[0][0], tail[0][1][-1], k)]
+    notes = ["priced for %d pairs per item (a run-time value): Miller loop x88: squaring of f (%d multiply-adds) x64; per pair the G2 doubling rounds (%d) x65, the G2 addition "
+             "rounds (%d) x23, the psi / psi^2 maps (%d) in 2 of those, the line product (%d) x88; then the r-torsion test of every pair (%d)"
+             % (n_pairs, s_m, d_m, r_m, p_m - r_m, line_m, tail[0][2])]
+    tot = counts(ins, ranges)
+    tot = add(tot, callees["c12_inv"], ops["inv"])
+    tot = add(tot, callees["c12_conj"], ops["conj"])
+    tot = add(tot, callees["c12_frob"], ops["frob"])
+    tot = add(tot, callees["c12_mul"], ops["mul"])
+    tot = add(tot, callees["cyclo_call"], ops["cyclo_calls"])
+    tot = add(tot, callees["cyclo_sq"], ops["cyclo_squarings"])
+    notes.append("final exponentiation: %(inv)d inversion, %(mul)d products, %(cyclo_squarings)d cyclotomic squarings in %(cyclo_calls)d calls, %(frob)d Frobenius maps, %(conj)d conjugations" % ops)
+    return tot, notes
+
+
 def coop12_kernel(funcs, frag, kind, callees, ops, n_pairs=2, msm="msm"):
-    """kind 'g16': k_coop12_miller_g16; 'fixed': k_coop12_miller_fixed with n_pairs table-driven pairs; 'fixed_keys': its twin with the key per item, two pairs."""
+    """kind 'g16': k_coop12_miller_g16; 'fixed': k_coop12_miller_fixed with n_pairs table-driven pairs; 'fixed_keys': its twin with the key per item, two pairs;
+    'pairs': k_coop12_miller_pairs with n_pairs variable pairs."""
+    if kind == "pairs":
+        return coop12_pairs_kernel(funcs, frag, callees, ops, n_pairs)
     ins = callee_straight(funcs, frag)
     lg, mads = loops_of(ins)
     h, latches, c = max(lg, key=lambda g: g[2])              # the Miller loop: the loop holding the most multiply-adds
@@ -508,7 +559,8 @@ def model_coop12(funcs):
         pass
     out = {}
     for name, frag, kind in (("k_coop12_miller_g16", "19k_coop12_miller_g16E", "g16"), ("k_coop12_miller_fixed", "21k_coop12_miller_fixedE", "fixed"),
-                             ("k_coop12_miller_g16_keys", "24k_coop12_miller_g16_keysE", "g16"), ("k_coop12_miller_fixed_keys", "26k_coop12_miller_fixed_keysE", "fixed_keys")):
+                             ("k_coop12_miller_g16_keys", "24k_coop12_miller_g16_keysE", "g16"), ("k_coop12_miller_fixed_keys", "26k_coop12_miller_fixed_keysE", "fixed_keys"),
+                             ("k_coop12_miller_pairs", "21k_coop12_miller_pairsE", "pairs")):
         tot, n2 = coop12_kernel(funcs, frag, kind, callees, ops, msm="msm_keys" if name.endswith("g16_keys") else "msm")
         e = {"lanes_per_proof": 12, "proofs_per_wavefront": 5,
              "wavefront_instructions": {k: round(v, 1) for k, v in tot.items()},
