@@ -457,6 +457,47 @@ void bn254_set_pairing_params(long coop_max);
 int bn254_pairing_params(long out[1]);
 int bn254_pairing_state(uint64_t out[2]);
 
+/* ---- Pairing batches with shared, prepared G2 points ------------------------------------------------------------------------------------------------------------
+ * In the uses named above most G2 arguments are the same point in every item: a restated Groth16 proof has one variable G2 (B) and three of the key (beta, gamma,
+ * delta); a KZG check has [1]_2 and [tau]_2 and no other.  A caller says so per POSITION of the item: bit j of shared_mask (j < n_pairs) means "the G2 point of
+ * position j is this one, for every item" (arkworks' G2Prepared, gnark's precomputed lines).
+ *
+ *   bn254_g2_prepare (host work, no device) turns the 128 bytes x.c1 | x.c0 | y.c1 | y.c0 of a G2 point -- the G2 half of a pair record -- into a PREPARED RECORD of
+ *   BN254_G2_PREPARED_LEN bytes: a header of four dwords (a magic word, the layout version, flags with bit 0 = identity, a reserved word), the affine point as the
+ *   four field elements of the workspace layout, and the 88 affine lines of the optimal-ate loop in the encoding of the key tables (54 dwords each).  *status:
+ *   BN254_ACCEPT, out written; or BN254_ERR_NOT_MEMBER, BN254_ERR_NOT_ON_CURVE, BN254_ERR_NOT_IN_SUBGROUP -- the checks of phase 1 and phase 2 of the definition
+ *   above, in that order -- and out untouched.  The return code is BN254_OK in all four cases (as bn254_g2_decompress); a null pointer returns BN254_E_BAD_ARG.
+ *   All-zero bytes are the identity: accepted, and flagged in the record.  The record is plain data: the caller owns it, may keep it beside its key, and copies it to
+ *   the device itself (no handle, no lifetime, no per-device state).  A record is valid only for the layout version that wrote it: keep the 128 bytes, not the record,
+ *   across versions of the library.
+ *
+ *   The entries.  prepared holds popcount(shared_mask) records, in ascending position order.  The item is PACKED: a shared position occupies BN254_PAIRING_G1_LEN = 64
+ *   bytes (G1 x | y), a variable position 192 bytes as above, positions in order; item_stride >= the sum.  d_prepared must be 4-byte aligned (the lines are fetched
+ *   by dword loads at wavefront-uniform addresses).
+ *   Definition: status[i] and the GT value are those bn254_pairing_check_batch / bn254_pairing_batch give the EXPANDED item, in which every shared position carries
+ *   the 128 bytes its record was prepared from.  So: phase 1 runs in record order over what the record holds (for a shared position the G1 point alone); the r-torsion
+ *   test applies to the variable positions (with every position shared BN254_ERR_NOT_IN_SUBGROUP cannot occur); a shared identity makes its pair contribute 1 while its
+ *   G1 point is still validated; the GT bytes are identical (the affine line of a table differs from the projective one by a factor in Fp2, which the final
+ *   exponentiation removes -- what the Groth16 path has relied on since its first revision).
+ *   Argument errors (BN254_E_BAD_ARG before any device is touched, status untouched): those of the entries above, a bit of shared_mask at or above n_pairs, prepared
+ *   null with a non-zero mask, an item_stride below the packed size, and -- in the host entries, which can read it -- a record whose magic word or version is wrong.
+ *   bn254_pairing_check_batch_shared_device cannot read the record on the host: its loader kernel reads the header words, and on a mismatch every item of the call
+ *   ends as BN254_ERR_MALFORMED and no table is read.  shared_mask == 0 is the entry above: same kernels, same bytes.
+ *   Workspace, reservation (bn254_pairing_reserve), locking and passes are those of the entries above; a host call stages the prepared records with every pass's items
+ *   (so a pass holds 48 MB less popcount * 19 168 bytes of items).  Launches count in bn254_pairing_state by their form as well.
+ *   Kernels: the lane form reads the packed item (k_pairing_load_shared) and runs k_miller_run_mix -- per step the G2 step and line of every variable position, then one
+ *   table-driven line product per shared position, no G2 arithmetic, no r-torsion test and no G2 bytes for those.  A launch of up to coop_max items takes the
+ *   cooperative form after the same loader; that form gains nothing from the tables (the shared point is in the workspace as if it had come from the item). */
+#define BN254_G2_PREPARED_LEN 19168  /* (4 + 4 * 9 + 88 * 54) * 4; a static_assert in csrc/bn254_capi_pairing.hip holds it to the structures */
+#define BN254_PAIRING_G1_LEN 64      /* a shared position of a packed item: G1 x | y */
+int bn254_g2_prepare(const uint8_t g2[128], uint8_t out[BN254_G2_PREPARED_LEN], uint8_t* status);
+int bn254_pairing_check_batch_shared(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared,
+                                     size_t n, uint8_t* status, int device);
+int bn254_pairing_check_batch_shared_device(const void* d_items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const void* d_prepared,
+                                            size_t n, void* d_status, int device, void* hip_stream);
+int bn254_pairing_batch_shared(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared,
+                               size_t n, uint8_t* out_gt /* n x 384 */, uint8_t* status, int device);
+
 /* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
  * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
  * before a device is first used the library runs the kernels IT SHIPS on THAT device on small built-in inputs and compares every output byte with a known answer.
@@ -489,7 +530,8 @@ int bn254_pairing_state(uint64_t out[2]);
  * Expected values: the status bytes of checks 4 .. 7 are tables generated with the key's trapdoors (gen_constants.py -> csrc/bn254_constants.h; no pairing is
  * computed for them at run time); everything else is the host's compile of the same arithmetic source, computed once per process while the device runs.
  * NOT covered in this revision: the _keys variants of the kernels (batches over many keys), the RLC group kernels, the MSM row kernels and the wide-key MSM kernels,
- * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store; its final exponentiation and compare are checks 1 .. 3's kernels),
+ * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store, and k_pairing_load_shared, k_miller_run_mix of the entries with shared G2 points; its final exponentiation and
+ * compare are checks 1 .. 3's kernels),
  * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
  *
  * Cost on one MI355X (profiles/selftest_cost.txt): one run is 40 ms of wall time in a warm process, all of it device time on the run's own stream (g16_lane 11.2 ms,
@@ -610,6 +652,11 @@ int bn254_dbg_pairing_batch(const uint8_t* pairs, size_t item_stride, size_t n_p
 int bn254_dbg_pairing_batch_form(const uint8_t* pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* out_gt, uint8_t* status, int device, int form);
 /* the form a launch of n items of n_pairs pairs takes under the knobs as they are now: *form = 1 lane, 2 cooperative; no device is touched */
 int bn254_dbg_pairing_form(size_t n_pairs, size_t n, int* form);
+/* The same probe for items with shared, prepared G2 points (bn254_pairing_check_batch_shared: same arguments and argument errors): device -1 with form 0 runs the
+ * host compile of k_pairing_load_shared, k_miller_run_mix and the final-exponentiation program, the loop cut by BN254_MILLER_RUN_STEPS; a device ordinal runs the
+ * kernels with form 0 (the plan), 1 (lane) or 2 (cooperative). */
+int bn254_dbg_pairing_batch_shared(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared,
+                                   size_t n, uint8_t* out_gt, uint8_t* status, int device, int form);
 /* host-only probe of its pass plan for a call of n items of n_pairs pairs: out = {items a reservation of n allocates workspace for, items per pass of the host
  * entries, passes of the host entries, pinned bytes of the records of one pass} */
 int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]);
@@ -818,7 +865,7 @@ int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

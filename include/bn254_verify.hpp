@@ -422,6 +422,43 @@ inline std::vector<uint8_t> pairing_batch(const Bytes& pairs, size_t n_pairs, si
   detail::check(bn254_pairing_batch(pairs.data(), stride, n_pairs, n, out_gt->data(), status.data(), device));
   return status;
 }
+// ---- the same with shared, prepared G2 points (bn254_g2_prepare, bn254_pairing_check_batch_shared) ----
+// The prepared record (BN254_G2_PREPARED_LEN bytes: header, affine point, 88 lines) of the G2 point x.c1 | x.c0 | y.c1 | y.c0 (128 bytes; all zero: the identity);
+// Panic with BN254_ERR_NOT_MEMBER / _NOT_ON_CURVE / _NOT_IN_SUBGROUP when the point is refused.  Host work; valid only for the layout version that wrote it.
+inline Bytes g2_prepare(const Bytes& g2) {
+  if (g2.size() != 128) throw std::invalid_argument("g2_prepare: 128 bytes expected");
+  Bytes out(BN254_G2_PREPARED_LEN);
+  uint8_t st = 0;
+  detail::check(bn254_g2_prepare(g2.data(), out.data(), &st));
+  if (st != BN254_ACCEPT) throw Panic(st);
+  return out;
+}
+// bytes of a packed item: BN254_PAIRING_G1_LEN per position whose bit of shared_mask is set, BN254_PAIRING_PAIR_LEN per other one
+inline size_t pairing_packed_len(size_t n_pairs, unsigned shared_mask) {
+  size_t len = 0;
+  for (size_t j = 0; j < n_pairs; j++) len += ((shared_mask >> j) & 1u) ? (size_t)BN254_PAIRING_G1_LEN : (size_t)BN254_PAIRING_PAIR_LEN;
+  return len;
+}
+// items: n PACKED items (a shared position holds its G1 point alone), item_stride bytes apart (0: packed); prepared: the records of the shared positions, ascending.
+// The status bytes are those pairing_check_batch gives the expanded items.
+inline std::vector<uint8_t> pairing_check_batch_shared(const Bytes& items, size_t n_pairs, unsigned shared_mask, const Bytes& prepared, size_t n, int device = 0, size_t item_stride = 0) {
+  const size_t packed = pairing_packed_len(n_pairs, shared_mask), stride = item_stride ? item_stride : packed;
+  if (n && items.size() < (n - 1) * stride + packed) throw std::invalid_argument("pairing_check_batch_shared: the buffer is shorter than n packed items");
+  if (prepared.size() < (size_t)BN254_G2_PREPARED_LEN * (size_t)__builtin_popcount(shared_mask)) throw std::invalid_argument("pairing_check_batch_shared: fewer prepared records than shared positions");
+  std::vector<uint8_t> status(n);
+  detail::check(bn254_pairing_check_batch_shared(items.data(), stride, n_pairs, shared_mask, prepared.data(), n, status.data(), device));
+  return status;
+}
+inline std::vector<uint8_t> pairing_batch_shared(const Bytes& items, size_t n_pairs, unsigned shared_mask, const Bytes& prepared, size_t n, Bytes* out_gt, int device = 0, size_t item_stride = 0) {
+  const size_t packed = pairing_packed_len(n_pairs, shared_mask), stride = item_stride ? item_stride : packed;
+  if (!out_gt) throw std::invalid_argument("pairing_batch_shared: out_gt is null");
+  if (n && items.size() < (n - 1) * stride + packed) throw std::invalid_argument("pairing_batch_shared: the buffer is shorter than n packed items");
+  if (prepared.size() < (size_t)BN254_G2_PREPARED_LEN * (size_t)__builtin_popcount(shared_mask)) throw std::invalid_argument("pairing_batch_shared: fewer prepared records than shared positions");
+  std::vector<uint8_t> status(n);
+  out_gt->assign(384 * n, 0);
+  detail::check(bn254_pairing_batch_shared(items.data(), stride, n_pairs, shared_mask, prepared.data(), n, out_gt->data(), status.data(), device));
+  return status;
+}
 // makes `device` ready for batches of n items: a later bn254_pairing_check_batch_device of up to n items only enqueues
 inline void pairing_reserve(size_t n, int device = 0) { detail::check(bn254_pairing_reserve(n, device)); }
 // launches of up to coop_max items take the cooperative twelve-lane form (0: always the lane form; clamped to 30 720; negative: unchanged) / the knob as it is now

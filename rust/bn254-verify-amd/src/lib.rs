@@ -303,6 +303,36 @@ pub fn pairing_check_batch(pairs: &[u8], item_stride: usize, n_pairs: usize, n: 
     check(unsafe { sys::bn254_pairing_check_batch(pairs.as_ptr(), item_stride, n_pairs, n, status.as_mut_ptr(), device as c_int) })?;
     Ok(status.into_iter().map(Status::from).collect())
 }
+/// Bytes of a prepared G2 record (`g2_prepare`): a header, the affine point and its 88 lines.  Valid only for the layout version that wrote it.
+pub const G2_PREPARED_LEN: usize = sys::BN254_G2_PREPARED_LEN;
+/// Bytes of a shared position of a packed item: G1 `x | y` alone.
+pub const PAIRING_G1_LEN: usize = sys::BN254_PAIRING_G1_LEN;
+
+/// The prepared record of the G2 point `x.c1 | x.c0 | y.c1 | y.c0` (all zero: the identity) for the positions of a batch that share it (`bn254_g2_prepare`; host
+/// work, no device): `Ok(record)`, or `Err(Status::NotMember | NotOnCurve | NotInSubgroup)` as the inner error when the point is refused.
+pub fn g2_prepare(g2: &[u8; 128]) -> Result<Result<Vec<u8>, Status>, Error> {
+    let mut out = vec![0u8; G2_PREPARED_LEN];
+    let mut st = 0u8;
+    check(unsafe { sys::bn254_g2_prepare(g2.as_ptr(), out.as_mut_ptr(), &mut st) })?;
+    Ok(if st == sys::BN254_ACCEPT { Ok(out) } else { Err(Status::from(st)) })
+}
+/// Bytes of a packed item of `n_pairs` positions: `PAIRING_G1_LEN` per position whose bit of `shared_mask` is set, `PAIRING_PAIR_LEN` per other one.
+pub fn pairing_packed_len(n_pairs: usize, shared_mask: u32) -> usize {
+    (0..n_pairs).map(|j| if (shared_mask >> j) & 1 == 1 { PAIRING_G1_LEN } else { PAIRING_PAIR_LEN }).sum()
+}
+/// `pairing_check_batch` for items in which the G2 point of every position `j` with bit `j` of `shared_mask` set is the same for the whole batch
+/// (`bn254_pairing_check_batch_shared`): `prepared` holds the records of those positions (`g2_prepare`) in ascending position order, and the items are packed --
+/// a shared position holds its G1 point alone.  The statuses are those of `pairing_check_batch` on the expanded items.
+pub fn pairing_check_batch_shared(items: &[u8], item_stride: usize, n_pairs: usize, shared_mask: u32, prepared: &[u8], n: usize, device: i32) -> Result<Vec<Status>, Error> {
+    let short = Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "pairing_check_batch_shared: n_pairs is 1..=8, shared_mask has bits below n_pairs only, prepared holds a record per shared position and the buffer holds n packed items of item_stride bytes".into() };
+    if n_pairs < 1 || n_pairs > PAIRING_MAX_PAIRS || (shared_mask >> n_pairs) != 0 { return Err(short); }
+    let packed = pairing_packed_len(n_pairs, shared_mask);
+    if item_stride < packed || prepared.len() < G2_PREPARED_LEN * shared_mask.count_ones() as usize { return Err(short); }
+    if n > 0 && (n - 1).checked_mul(item_stride).and_then(|b| b.checked_add(packed)).map_or(true, |b| items.len() < b) { return Err(short); }
+    let mut status = vec![0u8; n];
+    check(unsafe { sys::bn254_pairing_check_batch_shared(items.as_ptr(), item_stride, n_pairs, shared_mask as core::ffi::c_uint, prepared.as_ptr(), n, status.as_mut_ptr(), device as c_int) })?;
+    Ok(status.into_iter().map(Status::from).collect())
+}
 /// Makes `device` ready for pairing batches of `n` items (its self-test at first use, the workspace).
 pub fn pairing_reserve(n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_pairing_reserve(n, device as c_int) }) }
 /// Launches of up to `coop_max` items of a pairing batch take the cooperative twelve-lane form (`bn254_set_pairing_params`; 0: always the lane form; clamped to

@@ -15,4 +15,6 @@ from .binding import (  # noqa: F401
     device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST, dbg_overlap_replay,
     pairing_check_batch, pairing_batch, pairing_check_batch_device, pairing_reserve, dbg_pairing_batch, dbg_pairing_plan, PAIRING_MAX_PAIRS, PAIRING_PAIR_LEN,
     set_pairing_params, pairing_params, pairing_state, dbg_pairing_form, PAIRING_FORM_LANES, PAIRING_FORM_COOP,
+    g2_prepare, pairing_check_batch_shared, pairing_batch_shared, pairing_check_batch_shared_device, dbg_pairing_batch_shared, pairing_packed_len, G2_PREPARED_LEN,
+    PAIRING_G1_LEN,
 )

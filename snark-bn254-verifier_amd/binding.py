@@ -939,6 +939,91 @@ def dbg_pairing_batch(pairs, n_pairs, n=None, item_stride=None, device=-1, want_
 
 PAIRING_FORM_LANES, PAIRING_FORM_COOP = 1, 2
 
+# ---- pairing batches with shared, prepared G2 points (bn254_g2_prepare, bn254_pairing_check_batch_shared) ----
+G2_PREPARED_LEN = 19168
+PAIRING_G1_LEN = 64
+
+
+def g2_prepare(g2):
+    """(status, record): the prepared record (G2_PREPARED_LEN bytes: header, affine point, 88 lines) of the G2 point x.c1 | x.c0 | y.c1 | y.c0 (128 bytes; all zero:
+    the identity) when status is ACCEPT, else None with ERR_NOT_MEMBER / ERR_NOT_ON_CURVE / ERR_NOT_IN_SUBGROUP  (bn254_g2_prepare; host work, no device)."""
+    g2 = bytes(g2)
+    if len(g2) != 128:
+        raise Bn254Error("g2_prepare: 128 bytes expected")
+    fn = lib().bn254_g2_prepare
+    fn.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p]
+    out = (C.c_uint8 * G2_PREPARED_LEN)(); st = C.c_uint8(0xEE)
+    _check(fn(g2, out, C.byref(st)))
+    return st.value, (bytes(out) if st.value == ACCEPT else None)
+
+
+def pairing_packed_len(n_pairs, shared_mask):
+    """bytes of a packed item: PAIRING_G1_LEN per shared position, PAIRING_PAIR_LEN per variable one"""
+    return sum(PAIRING_G1_LEN if (shared_mask >> j) & 1 else PAIRING_PAIR_LEN for j in range(n_pairs))
+
+
+def _shared_lib():
+    L = lib()
+    host = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_char_p, C.c_size_t]
+    L.bn254_pairing_check_batch_shared.argtypes = host + [C.c_void_p, C.c_int]
+    L.bn254_pairing_batch_shared.argtypes = host + [C.c_void_p, C.c_void_p, C.c_int]
+    L.bn254_dbg_pairing_batch_shared.argtypes = host + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.bn254_pairing_check_batch_shared_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+    return L
+
+
+def _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride):
+    items = bytes(items)
+    prepared = b"".join(prepared) if isinstance(prepared, (list, tuple)) else bytes(prepared)
+    packed = pairing_packed_len(n_pairs, shared_mask)
+    if item_stride is None:
+        item_stride = packed
+    if n is None:
+        n = len(items) // item_stride if item_stride else 0
+    if n and len(items) < (n - 1) * item_stride + packed:
+        raise Bn254Error("pairing batch: the buffer is shorter than n packed items")
+    if len(prepared) < G2_PREPARED_LEN * bin(shared_mask).count("1"):
+        raise Bn254Error("pairing batch: fewer prepared records than shared positions")
+    return items, prepared, n, item_stride
+
+
+def pairing_check_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, device=0):
+    """pairing_check_batch for items whose G2 point of every position j with bit j of shared_mask set is shared by the whole batch: `prepared` holds their records
+    (g2_prepare; bytes, or a list of records) in ascending position order, and the items are PACKED -- 64 bytes (G1) per shared position, 192 per variable one.
+    The status bytes are those of pairing_check_batch on the expanded items  (bn254_pairing_check_batch_shared)."""
+    L = _shared_lib()
+    items, prepared, n, item_stride = _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride)
+    status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_pairing_check_batch_shared(items, item_stride, n_pairs, shared_mask, prepared, n, status, device))
+    return bytes(status)[:n]
+
+
+def pairing_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, device=0):
+    """(GT values, status bytes) as pairing_batch, for packed items with shared positions  (bn254_pairing_batch_shared)."""
+    L = _shared_lib()
+    items, prepared, n, item_stride = _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride)
+    gt = (C.c_uint8 * max(384 * n, 1))(); status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_pairing_batch_shared(items, item_stride, n_pairs, shared_mask, prepared, n, gt, status, device))
+    return bytes(gt)[:384 * n], bytes(status)[:n]
+
+
+def pairing_check_batch_shared_device(d_items, n_pairs, shared_mask, d_prepared, n, d_status, item_stride=None, device=0, stream=0):
+    """bn254_pairing_check_batch_shared_device on device pointers (ints; d_prepared 4-byte aligned): enqueues on `stream` and returns."""
+    L = _shared_lib()
+    _check(L.bn254_pairing_check_batch_shared_device(d_items, pairing_packed_len(n_pairs, shared_mask) if item_stride is None else item_stride, n_pairs, shared_mask, d_prepared, n,
+                                                     d_status, device, stream))
+
+
+def dbg_pairing_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, device=-1, want_gt=True, form=0):
+    """bn254_dbg_pairing_batch_shared: (GT values or None, status bytes of the CHECK) from one run; device -1 is the host compile of the shared loader and the mixed
+    Miller run; on a device form 1 forces the lane kernels, 2 the cooperative kernel."""
+    L = _shared_lib()
+    items, prepared, n, item_stride = _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride)
+    gt = (C.c_uint8 * max(384 * n, 1))() if want_gt else None
+    status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_dbg_pairing_batch_shared(items, item_stride, n_pairs, shared_mask, prepared, n, gt, status, device, form))
+    return (bytes(gt)[:384 * n] if want_gt else None), bytes(status)[:n]
+
 
 def set_pairing_params(coop_max=-1):
     """bn254_set_pairing_params: launches of up to coop_max items of a pairing batch take the cooperative twelve-lane form (0: always the lane form; clamped to the

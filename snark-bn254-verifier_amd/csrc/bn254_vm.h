@@ -444,6 +444,63 @@ BN_HD int vm_miller_run_var(W& w, const KINDS& kinds, int s_begin, int s_end, in
   return failed;
 }
 
+// The run for an item whose positions are of TWO kinds (the batch pairing product with shared, prepared G2 points: bn254_pairing_check_batch_shared): the variable
+// positions (bits of var_mask) take the G2 step and mf_line_var_sel of vm_miller_run_var, the shared ones (bits of sh_mask) take mf_line_fixed on the line
+// lines.get(t, s) of their prepared table, t counting the shared positions in ascending order -- no G2 arithmetic, no r-torsion test.  Both masks are wave-uniform
+// (launch-uniform on the GPU), so the two kinds are two loops over position lists and no lane ever branches on the kind of a position.  A pair with an identity on
+// either side keeps f by selecting the output, as in the two runs this one is made of; the identity bit of a shared Q comes from its record (pb_load_item_shared).
+// VAR = false (var_mask is then 0) is the instantiation for items without a variable position: it holds no G2 formulas at all and is vm_miller_run_fixed2's loop for
+// any number of tables; the kernels carry both, so the all-shared launch does not pay for the registers the G2 formulas spill.  Returns -1, or with MR_FOLD_ATE at the end of the loop the first VARIABLE position
+// whose finite Q_j fails the r-torsion test.
+BN_HD int vp_first(uint32_t m) { return __builtin_ctz(m); }
+template <bool VAR, class W, class LINES, class KINDS>
+BN_HD int vm_miller_run_mix(W& w, const LINES& lines, const KINDS& kinds, int s_begin, int s_end, uint32_t var_mask, uint32_t sh_mask, uint32_t ident, int e, int fold = 0) {
+  Fp2 f4, f5;
+  if ((fold & MR_FOLD_INIT) && s_begin == 0) {
+    w.park(0, fp2_one()); w.park(1, fp2_zero()); w.park(2, fp2_zero()); w.park(3, fp2_zero());
+    f4 = fp2_zero(); f5 = fp2_zero();
+    if constexpr (VAR)
+      for (uint32_t m = var_mask; m; m &= m - 1) { const int j = vp_first(m), et = vp_t(j), eb = vp_q(j); vst2(w, et, vld2(w, eb)); vst2(w, et + 2, vld2(w, eb + 2)); vst2(w, et + 4, fp2_one()); }
+  } else mf_load(w, e, f4, f5);
+  for (int s = s_begin; s < s_end; s++) {
+    const int kind = kinds.get(s);
+    if (kind == 0) {
+      if (s != 0) mf_sqr(w, f4, f5);
+      if constexpr (VAR)
+        for (uint32_t m = var_mask; m; m &= m - 1) {
+          const int j = vp_first(m);
+          BN_SCHED_FENCE();
+          G2Line l = mf_g2(w, 0, vp_t(j), vp_q(j));
+          mf_line_var_sel(w, l, vp_p(j), vp_skips(ident, j), f4, f5);
+        }
+    } else if constexpr (VAR) {
+      for (uint32_t m = var_mask; m; m &= m - 1) {
+        const int j = vp_first(m);
+        BN_SCHED_FENCE();
+        G2Line l = mf_g2(w, kind, vp_t(j), vp_q(j));
+        mf_line_var_sel(w, l, vp_p(j), vp_skips(ident, j), f4, f5);
+      }
+    }
+    BN_SCHED_FENCE();
+    int t = 0;
+    for (uint32_t m = sh_mask; m; m &= m - 1, t++) {
+      const int j = vp_first(m);
+      mf_line_fixed(w, lines.get(t, s), vp_p(j), vp_skips(ident, j), f4, f5);
+      BN_SCHED_FENCE();
+    }
+  }
+  mf_store(w, e, f4, f5);
+  int failed = -1;
+  if constexpr (VAR)
+    if ((fold & MR_FOLD_ATE) && s_end == BN_ATE_STEPS)
+      for (uint32_t m = var_mask; m; m &= m - 1) {
+        const int j = vp_first(m);
+        const bool ok = vm_g2_ate_check(w, vp_t(j), vp_q(j));
+        if (failed < 0 && vp_q_finite(ident, j) && !ok) failed = j;
+      }
+  return failed;
+}
+
 // ---- r-torsion test of B from the point the Miller loop has already computed ----------------------------------------------------------
 // After vm_miller_program the running point is T = [6u+2]B + psi(B) - psi^2(B).  For B on the twist E'(Fp2):
 //     B in G2  <=>  T == -psi^3(B)          (T finite)

@@ -9,7 +9,11 @@ warm-up call and a reservation; the median of --steps calls is reported.  Writes
   --form lane   bn254_set_pairing_params(0): the one-item-per-lane kernels at every size
   --form coop   bn254_set_pairing_params(30720): the cooperative twelve-lane kernel wherever it can run (n <= 30 720)
   --form both   both, ALTERNATING call by call inside every cell (lane, coop, lane, coop, ...), so that a drift of the machine meets both alike: the lane form of the
-                same session is the reference of every cooperative figure; the cell also gives the spread (min .. max) of each form's calls"""
+                same session is the reference of every cooperative figure; the cell also gives the spread (min .. max) of each form's calls
+  --shared SHAPES   times bn254_pairing_check_batch_shared_device instead: SHAPES is a comma-separated list of K:MASK (or MASK alone, for every pair count of --pairs
+                that holds it), e.g. 2:0x3,4:0xe,8:0xff,8:0xaa.  The G2 point of a shared position j is B[13 j] for every item, prepared once (bn254_g2_prepare); the
+                shared entry on the PACKED items and the all-variable entry on the EXPANDED items (the same points) run ALTERNATING call by call in one session, in the
+                form --form names (plan, lane or coop); a cell gives both medians, each one's min .. max and the ratio"""
 import argparse
 import importlib
 import json
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--out", type=str, default=os.path.join(ROOT, "profiles", "r14_pairing_batch.txt"))
     ap.add_argument("--form", choices=("plan", "lane", "coop", "both"), default="plan")
+    ap.add_argument("--shared", type=str, default="", help="K:MASK[,K:MASK...]: time the shared entry against the all-variable entry on the expanded items")
     ap.add_argument("--no-groth16", action="store_true", help="skip the Groth16 batch timed for orientation")
     args = ap.parse_args()
     import numpy as np
@@ -68,6 +73,27 @@ def main():
         pkg.set_pairing_params(knob0)
         return {f: (statistics.median(v), min(v), max(v)) for f, v in times.items()}
 
+    def timed_pair(fns):
+        """the calls of fns (name -> callable) alternating; -> {name: (median, min, max)} in ms"""
+        times = {name: [] for name in fns}
+        for it in range(args.steps + 1):
+            for name, fn in fns.items():
+                torch.cuda.synchronize(dev)
+                t = time.perf_counter()
+                fn()
+                torch.cuda.synchronize(dev)
+                if it:
+                    times[name].append((time.perf_counter() - t) * 1e3)
+        return {f: (statistics.median(v), min(v), max(v)) for f, v in times.items()}
+
+    shapes = []
+    for tok in [t for t in args.shared.split(",") if t]:
+        if ":" in tok:
+            shapes.append((int(tok.split(":")[0]), int(tok.split(":")[1], 0)))
+        else:
+            shapes += [(k, int(tok, 0)) for k in pairs if int(tok, 0) >> k == 0]
+    if shapes and args.form == "both":
+        ap.error("--shared compares the two ENTRIES in one form: --form plan, lane or coop")
     if args.form == "lane":
         pkg.set_pairing_params(0)
     elif args.form == "coop":
@@ -92,7 +118,38 @@ def main():
             assert bytes(d_status.cpu().numpy().tobytes()) == expected
             lines.append("n = %d   exact Groth16 (2 inputs, device entry): %.3f ms, %.0f proofs/s" % (n, g16_ms, n / g16_ms * 1e3))
         pkg.pairing_reserve(n, device=0)
-        for k in pairs:
+        for k, mask in shapes:
+            expanded = np.empty((n, 192 * k), dtype=np.uint8)
+            packed, recs = [], []
+            for j in range(k):
+                pj = np.roll(a, -7 * j, axis=0)
+                qj = np.roll(b, -13 * j, axis=0)
+                if (mask >> j) & 1:
+                    qj = np.repeat(qj[:1], n, axis=0)                    # the point of position j, for every item
+                    st, r = pkg.g2_prepare(qj[0].tobytes())
+                    assert st == pkg.ACCEPT
+                    recs.append(r)
+                    packed.append(pj)
+                else:
+                    packed += [pj, qj]
+                expanded[:, 192 * j:192 * j + 64] = pj
+                expanded[:, 192 * j + 64:192 * j + 192] = qj
+            d_exp = torch.from_numpy(expanded).to(dev)
+            d_packed = torch.from_numpy(np.ascontiguousarray(np.concatenate(packed, axis=1))).to(dev)
+            d_prep = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(dev)
+            d_st2 = torch.full((n,), 0xEE, dtype=torch.uint8, device=dev)
+            d_status.fill_(0xEE)
+            res = timed_pair({
+                "shared": lambda: pkg.pairing_check_batch_shared_device(d_packed.data_ptr(), k, mask, d_prep.data_ptr(), n, d_status.data_ptr(), device=0, stream=stream.cuda_stream),
+                "variable": lambda: pkg.pairing_check_batch_device(d_exp.data_ptr(), k, n, d_st2.data_ptr(), device=0, stream=stream.cuda_stream)})
+            got, ref = bytes(d_status.cpu().numpy().tobytes()), bytes(d_st2.cpu().numpy().tobytes())
+            assert got == ref == bytes([pkg.REJECT]) * n, "unexpected status bytes: %r / %r" % ({x: got.count(bytes([x])) for x in set(got)}, {x: ref.count(bytes([x])) for x in set(ref)})
+            (sm, slo, shi), (vm, vlo, vhi) = res["shared"], res["variable"]
+            rows.append({"n": n, "n_pairs": k, "shared_mask": mask, "form": args.form, "shared_ms": round(sm, 3), "shared_min": round(slo, 3), "shared_max": round(shi, 3),
+                         "variable_ms": round(vm, 3), "variable_min": round(vlo, 3), "variable_max": round(vhi, 3)})
+            lines.append("n = %6d   n_pairs = %d  mask = 0x%02x:  shared %8.3f ms (%.3f .. %.3f)   all-variable %8.3f ms (%.3f .. %.3f)   shared / all-variable %.2f"
+                         % (n, k, mask, sm, slo, shi, vm, vlo, vhi, sm / vm))
+        for k in ([] if shapes else pairs):
             items = np.empty((n, 192 * k), dtype=np.uint8)
             for j in range(k):
                 items[:, 192 * j:192 * j + 64] = np.roll(a, -7 * j, axis=0)
@@ -120,6 +177,14 @@ def main():
             lines.append("n = %d   n_pairs = %d: %.3f ms, %.0f items/s, %.0f pairs/s%s" % (n, k, ms, n / ms * 1e3, n * k / ms * 1e3,
                                                                                         ", %.2f x the Groth16 batch's time" % (ms / g16_ms) if g16_ms else ""))
     pkg.set_pairing_params(knob0)
+    if shapes:
+        head = ["bn254_pairing_check_batch_shared_device on packed items against bn254_pairing_check_batch_device on the expanded items (the same points), device-resident, one GPU "
+                "(%s); the two entries alternating call by call, median of %d calls each (min .. max), each timed from the call to the status bytes on the device; form: %s"
+                % (torch.cuda.get_device_name(0), args.steps, args.form), ""]
+        with open(args.out, "w") as f:
+            f.write("\n".join(head + lines) + "\n")
+        print(json.dumps({"bench": "pairing_batch_shared", "rows": rows}))
+        return
     head = ["bn254_pairing_check_batch_device, device-resident items, one GPU (%s); median of %d calls per cell, each timed from the call to the status bytes on the device; "
             "form: %s" % (torch.cuda.get_device_name(0), args.steps, "lane and cooperative alternating call by call (median, min .. max)" if args.form == "both" else args.form), ""]
     with open(args.out, "w") as f:
