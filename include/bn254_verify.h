@@ -498,6 +498,60 @@ int bn254_pairing_check_batch_shared_device(const void* d_items, size_t item_str
 int bn254_pairing_batch_shared(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared,
                                size_t n, uint8_t* out_gt /* n x 384 */, uint8_t* status, int device);
 
+/* ---- Batch verification of KZG openings ---------------------------------------------------------------------------------------------------------------------------
+ * The reference's plonk/kzg.rs::batch_verify_multi_points (lines 128-190) for openings a caller holds (a KZG opening of one's own, an fflonk or halo2-KZG tail): the
+ * G1 fold runs on the device, the pairing check is the shared-G2 batch above.
+ *
+ *   An OPENING is BN254_KZG_OPENING_LEN = 192 bytes: the commitment C x | y, the quotient H x | y, the point z, the claimed value y -- 32-byte big-endian each.
+ *   A KEY is BN254_KZG_KEY_LEN bytes of plain data (no handle, no lifetime, no per-device state -- like a prepared G2 record, and valid for the layout version that
+ *   wrote it): 16 bytes (a magic word, the layout version, flags with bit 0 = g1 is the identity, a reserved word), g1 as the two field elements of the workspace
+ *   layout (72 bytes), and the prepared records of g2 and tau_g2, byte for byte what bn254_g2_prepare writes.
+ *
+ *   bn254_kzg_key_prepare (host work, no device): *status is BN254_ACCEPT and out written, or the first failure over g1, g2, tau_g2 -- BN254_ERR_NOT_MEMBER,
+ *   BN254_ERR_NOT_ON_CURVE and, for the G2 points, BN254_ERR_NOT_IN_SUBGROUP -- and out untouched.  The return code is BN254_OK in all of these cases; a null pointer
+ *   returns BN254_E_BAD_ARG.  All-zero bytes are the identity: accepted and flagged.
+ *
+ *   Definition of status[i] (flags without BN254_FLAG_RLC), in this order:
+ *     1. With BN254_FLAG_STRICT_SCALARS a z or y >= r is BN254_ERR_NOT_MEMBER; without it the scalars are used modulo r, the library's convention everywhere.
+ *     2. The points in record order, C then H: a coordinate >= p is BN254_ERR_NOT_MEMBER, a point off the curve BN254_ERR_NOT_ON_CURVE; all-zero is the identity.
+ *     3. BN254_ACCEPT if e(C - y g1 + z H, g2) e(-H, tau_g2) == 1, else BN254_REJECT.
+ *   Equivalently: what bn254_pairing_check_batch_shared gives the two-pair item (F_i, -H_i), F_i = C_i - y_i g1 + z_i H_i, with mask 0b11 and the key's two records.
+ *   A pair with an identity on either side contributes 1; BN254_ERR_NOT_IN_SUBGROUP cannot occur.
+ *   Argument errors (BN254_E_BAD_ARG before any device is touched, status untouched): a null pointer with n > 0, a stride below 192, any flag other than
+ *   BN254_FLAG_STRICT_SCALARS and BN254_FLAG_RLC, a d_key that is not 4-byte aligned and -- in the host entry -- a key whose magic word or version is wrong.  The device
+ *   entry cannot read the key on the host: its loader kernel reads the header words, and on a mismatch every opening ends BN254_ERR_MALFORMED and no table is read.
+ *   n == 0 returns BN254_OK.
+ *
+ *   BN254_FLAG_RLC (the reference's batching, across openings): every opening gets a fresh odd 128-bit weight r_i -- ChaCha20, expanded on the device from a key drawn
+ *   with getrandom(2) once per call -- folded into its scalars: F'_i = r_i C_i + (r_i z_i) H_i - (r_i y_i) g1, H'_i = -r_i H_i.  The weighted points of the 64 openings
+ *   of a wavefront are summed (decided openings and identities drop out) and one two-pair check runs per group; a group that passes accepts its pending openings, the
+ *   openings of a failed group go through the per-opening check on their weighted points (r_i is invertible mod r: the verdict is that of the unweighted points).
+ *   Contract: the status bytes are those of the exact path, except that a false ACCEPT has probability about 2^-127.  The flag is honoured from rlc_min openings per
+ *   launch on (bn254_set_kzg_params: process-wide, atomic, a negative value leaves it alone, never below 64; initial value BN254_KZG_RLC_MIN, default 65 536; read
+ *   back by bn254_kzg_params).  With the flag honoured BOTH entries synchronise once per launch to learn which groups failed, as the Groth16 flag does.  Without it
+ *   bn254_kzg_verify_batch_device only enqueues on hip_stream, and after bn254_kzg_reserve(n', device) with n' >= min(n, 2^18) it allocates nothing.
+ *   bn254_kzg_state: out[0] launches that ran the joint check, out[1] the groups they checked, out[2] the groups that failed, out[3] launches on the exact path.
+ *
+ *   Measured on one MI355X (profiles/r17_kzg_batch.txt, tools/bench_kzg.py; device-resident valid openings, exact | BN254_FLAG_RLC honoured | the pairing alone on
+ *   the same openings with F_i precomputed, median of 5 alternating calls): 4096 openings 2.98 | 2.98 | 2.27 ms, 65 536 openings 10.73 | 5.16 | 9.32 ms, 262 144
+ *   openings 35.99 | 13.74 | 30.88 ms.  So the exact entry costs 1.15 .. 1.31 of its pairing, and the weighted call ties at 4096 and takes 0.48 and 0.38 of the exact
+ *   time at the two larger sizes: the default of rlc_min is 65 536, the smallest measured size where it wins by more than the spread.
+ *   Workspace and locking: the per-device workspace, lock and completion event of the pairing batch (a KZG call and a pairing call on one device serialise), plus the
+ *   term records, rows and window-table scratch of the G1 walk (about 4.5 KB per opening of the largest launch; the weighted form twice that and the groups).  A launch
+ *   holds at most 2^18 openings; the host entry stages the key and the openings in passes through pinned memory.  The first use of a device runs the self-test.
+ *   Kernels: k_kzg_load (checks, scalars mod r, the weight, glv_decompose, term records), k_g1_msm_rows / k_g1_sum_affine (the G1 walk; g1 is walked as a variable
+ *   term, a plain-data key has no window table), k_kzg_ident, then the launches of the pairing batch behind its load step; weighted: k_plonk_group_sums /
+ *   k_plonk_group_scatter around the groups' check. */
+#define BN254_KZG_OPENING_LEN 192    /* commitment x|y (64) | quotient H x|y (64) | point z (32) | claimed value y (32), big-endian */
+#define BN254_KZG_KEY_LEN 38424      /* 16 (magic, layout version, flags: bit 0 = g1 is the identity, reserved) + 72 (g1 affine, workspace digits) + 2 * BN254_G2_PREPARED_LEN; a static_assert in csrc/bn254_capi_kzg.hip holds it to the structures */
+int bn254_kzg_key_prepare(const uint8_t g1[64], const uint8_t g2[128], const uint8_t tau_g2[128], uint8_t out[BN254_KZG_KEY_LEN], uint8_t* status);
+int bn254_kzg_verify_batch(const uint8_t* key, const uint8_t* openings, size_t stride, size_t n, uint8_t* status, int device, unsigned flags);
+int bn254_kzg_verify_batch_device(const void* d_key, const void* d_openings, size_t stride, size_t n, void* d_status, int device, void* hip_stream, unsigned flags);
+int bn254_kzg_reserve(size_t n, int device);
+void bn254_set_kzg_params(long rlc_min);
+int bn254_kzg_params(long out[1]);
+int bn254_kzg_state(uint64_t out[4]);   /* [0] launches that ran the joint check, [1] groups they checked, [2] groups that failed, [3] launches on the exact path */
+
 /* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
  * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
  * before a device is first used the library runs the kernels IT SHIPS on THAT device on small built-in inputs and compares every output byte with a known answer.
@@ -531,7 +585,7 @@ int bn254_pairing_batch_shared(const uint8_t* items, size_t item_stride, size_t 
  * computed for them at run time); everything else is the host's compile of the same arithmetic source, computed once per process while the device runs.
  * NOT covered in this revision: the _keys variants of the kernels (batches over many keys), the RLC group kernels, the MSM row kernels and the wide-key MSM kernels,
  * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store, and k_pairing_load_shared, k_miller_run_mix of the entries with shared G2 points; its final exponentiation and
- * compare are checks 1 .. 3's kernels),
+ * compare are checks 1 .. 3's kernels), the kernels of the KZG batch (k_kzg_load, k_kzg_ident, k_kzg_fetch),
  * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
  *
  * Cost on one MI355X (profiles/selftest_cost.txt): one run is 40 ms of wall time in a warm process, all of it device time on the run's own stream (g16_lane 11.2 ms,
@@ -660,6 +714,15 @@ int bn254_dbg_pairing_batch_shared(const uint8_t* items, size_t item_stride, siz
 /* host-only probe of its pass plan for a call of n items of n_pairs pairs: out = {items a reservation of n allocates workspace for, items per pass of the host
  * entries, passes of the host entries, pinned bytes of the records of one pass} */
 int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]);
+/* The probe of the KZG batch (bn254_kzg_verify_batch: same key, openings and argument errors; one pass: n at most what a launch holds): the points the loader and the
+ * G1 walk leave per opening -- out_f: vp_p(0), F_i or F'_i; out_h: vp_p(1), -H_i or H'_i = -r_i H_i; 64 big-endian bytes each, zero for the identity and for an opening
+ * the loader decided; out_inf: their two identity flags -- and the status bytes of the check.  flags may carry BN254_FLAG_RLC: then the weighted path runs whatever the
+ * knob says, with the caller's weights (n x 16 bytes, big-endian, forced odd; null: all 1) in the ChaCha20 stream's place, so that every value is checkable; out_group
+ * (null, or groups x 131 bytes) receives per group of 64 openings the two sums, their identity flags and the group's status byte (BN254_ACCEPT, BN254_REJECT).
+ * weights and out_group need BN254_FLAG_RLC.  device -1 (form 0) runs the host compile of the same code (kzg_load_opening, the rows of the plan, the group sums, the
+ * mixed Miller run); a device ordinal the kernels, with the pairing launches in form 0 (the plan), 1 (lane) or 2 (cooperative). */
+int bn254_dbg_kzg_fold(const uint8_t* key, const uint8_t* openings, size_t stride, size_t n, const uint8_t* weights, unsigned flags, uint8_t* out_f, uint8_t* out_h,
+                       uint8_t* out_inf, uint8_t* out_status, uint8_t* out_group, int device, int form);
 /* Value-level probes of the Fp12 operations (tests).  An Fp12 value travels in one of two formats, twelve Fp numbers in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..):
  *   format 0  384 bytes, 32 big-endian canonical bytes per number;
  *   format 1  108 int32: per number the nine balanced 29-bit digits (digit 0 first) of a representative of its Montgomery form x 2^261 mod p, stored into
@@ -865,7 +928,7 @@ int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries, the bn254_kzg_* entries -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

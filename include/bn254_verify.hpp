@@ -467,4 +467,40 @@ inline long pairing_params() { long out[1] = {0}; detail::check(bn254_pairing_pa
 // launches enqueued so far by this process: {in the cooperative form, in the lane form}
 inline std::array<uint64_t, 2> pairing_state() { std::array<uint64_t, 2> out{}; detail::check(bn254_pairing_state(out.data())); return out; }
 
+// ---- batch verification of KZG openings (bn254_kzg_key_prepare, bn254_kzg_verify_batch) ----
+// The key is plain data (BN254_KZG_KEY_LEN bytes: header, g1, the prepared records of g2 and tau_g2): no handle, no per-device state.  prepare: Panic with the first
+// failure over g1 (64 bytes), g2, tau_g2 (128 bytes each) when a point is refused.  verify_batch: n openings C | H | z | y (BN254_KZG_OPENING_LEN bytes), stride bytes
+// apart (0: packed); status[i] is BN254_ACCEPT where e(C - y g1 + z H, g2) e(-H, tau_g2) == 1, BN254_REJECT where it is not, or the loader error.  flags:
+// BN254_FLAG_STRICT_SCALARS, BN254_FLAG_RLC (the joint check over groups of 64 openings, honoured from set_kzg_params' rlc_min openings per launch on)
+class KzgVerifier {
+ public:
+  static KzgVerifier prepare(const Bytes& g1, const Bytes& g2, const Bytes& tau_g2) {
+    if (g1.size() != 64 || g2.size() != 128 || tau_g2.size() != 128) throw std::invalid_argument("KzgVerifier::prepare: 64, 128 and 128 bytes expected");
+    KzgVerifier v;
+    v.key_.resize(BN254_KZG_KEY_LEN);
+    uint8_t st = 0;
+    detail::check(bn254_kzg_key_prepare(g1.data(), g2.data(), tau_g2.data(), v.key_.data(), &st));
+    if (st != BN254_ACCEPT) throw Panic(st);
+    return v;
+  }
+  const Bytes& key() const { return key_; }      // for a caller that keeps the openings on the device (bn254_kzg_verify_batch_device)
+  std::vector<uint8_t> verify_batch(const Bytes& openings, size_t n, int device = 0, unsigned flags = 0, size_t stride = 0) const {
+    const size_t s = stride ? stride : (size_t)BN254_KZG_OPENING_LEN;
+    if (n && (s < (size_t)BN254_KZG_OPENING_LEN || openings.size() < (n - 1) * s + BN254_KZG_OPENING_LEN)) throw std::invalid_argument("KzgVerifier::verify_batch: the buffer is shorter than n openings");
+    std::vector<uint8_t> status(n);
+    detail::check(bn254_kzg_verify_batch(key_.data(), openings.data(), s, n, status.data(), device, flags));
+    return status;
+  }
+  // makes `device` ready for batches of n openings: a later bn254_kzg_verify_batch_device of up to n openings without BN254_FLAG_RLC only enqueues
+  static void reserve(size_t n, int device = 0) { detail::check(bn254_kzg_reserve(n, device)); }
+
+ private:
+  Bytes key_;
+};
+// BN254_FLAG_RLC is honoured from rlc_min openings per launch on (never below 64; negative: unchanged) / the knob as it is now
+inline void set_kzg_params(long rlc_min) { bn254_set_kzg_params(rlc_min); }
+inline long kzg_params() { long out[1] = {0}; detail::check(bn254_kzg_params(out)); return out[0]; }
+// {launches that ran the joint check, groups they checked, groups that failed, launches on the exact path}
+inline std::array<uint64_t, 4> kzg_state() { std::array<uint64_t, 4> out{}; detail::check(bn254_kzg_state(out.data())); return out; }
+
 }  // namespace snark_bn254_verifier

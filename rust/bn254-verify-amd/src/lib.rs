@@ -351,6 +351,46 @@ pub fn pairing_state() -> Result<(u64, u64), Error> {
     Ok((out[0], out[1]))
 }
 
+/// Bytes of a KZG opening: commitment `x | y`, quotient `x | y`, point `z`, claimed value `y`, 32-byte big-endian each.
+pub const KZG_OPENING_LEN: usize = sys::BN254_KZG_OPENING_LEN;
+/// Bytes of a KZG key (`kzg_key_prepare`): plain data -- a header, g1 and the prepared records of g2 and tau_g2.  Valid only for the layout version that wrote it.
+pub const KZG_KEY_LEN: usize = sys::BN254_KZG_KEY_LEN;
+
+/// The key of a KZG setup (`bn254_kzg_key_prepare`; host work, no device): `Ok(key)`, or the first failure over g1, g2, tau_g2 as the inner error.
+pub fn kzg_key_prepare(g1: &[u8; 64], g2: &[u8; 128], tau_g2: &[u8; 128]) -> Result<Result<Vec<u8>, Status>, Error> {
+    let mut out = vec![0u8; KZG_KEY_LEN];
+    let mut st = 0u8;
+    check(unsafe { sys::bn254_kzg_key_prepare(g1.as_ptr(), g2.as_ptr(), tau_g2.as_ptr(), out.as_mut_ptr(), &mut st) })?;
+    Ok(if st == sys::BN254_ACCEPT { Ok(out) } else { Err(Status::from(st)) })
+}
+/// Batch verification of `n` KZG openings of `stride` bytes each (`bn254_kzg_verify_batch`): `Accept` where `e(C - y g1 + z H, g2) e(-H, tau_g2) == 1`, `Reject` where
+/// it is not, or the loader error.  `flags`: `FLAG_STRICT_SCALARS`, `FLAG_RLC` (the joint check over groups of 64 openings, honoured from `set_kzg_params`' `rlc_min`
+/// openings per launch on: the same statuses except for a false accept with probability about 2^-127).
+pub fn kzg_verify_batch(key: &[u8], openings: &[u8], stride: usize, n: usize, device: i32, flags: u32) -> Result<Vec<Status>, Error> {
+    let short = Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "kzg_verify_batch: the key holds KZG_KEY_LEN bytes, stride is at least KZG_OPENING_LEN and the buffer holds n openings of stride bytes".into() };
+    if key.len() < KZG_KEY_LEN || stride < KZG_OPENING_LEN { return Err(short); }
+    if n > 0 && (n - 1).checked_mul(stride).and_then(|b| b.checked_add(KZG_OPENING_LEN)).map_or(true, |b| openings.len() < b) { return Err(short); }
+    let mut status = vec![0u8; n];
+    check(unsafe { sys::bn254_kzg_verify_batch(key.as_ptr(), openings.as_ptr(), stride, n, status.as_mut_ptr(), device as c_int, flags as core::ffi::c_uint) })?;
+    Ok(status.into_iter().map(Status::from).collect())
+}
+/// Makes `device` ready for KZG batches of `n` openings (its self-test at first use, the workspace and the buffers of the G1 walk).
+pub fn kzg_reserve(n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_kzg_reserve(n, device as c_int) }) }
+/// `FLAG_RLC` is honoured from `rlc_min` openings per launch on (`bn254_set_kzg_params`; never below 64; negative: unchanged).
+pub fn set_kzg_params(rlc_min: i64) { unsafe { sys::bn254_set_kzg_params(rlc_min as core::ffi::c_long) } }
+/// The knob as it is now (`bn254_kzg_params`).
+pub fn kzg_params() -> Result<i64, Error> {
+    let mut out: [core::ffi::c_long; 1] = [0];
+    check(unsafe { sys::bn254_kzg_params(out.as_mut_ptr()) })?;
+    Ok(out[0] as i64)
+}
+/// (launches that ran the joint check, groups they checked, groups that failed, launches on the exact path)  (`bn254_kzg_state`).
+pub fn kzg_state() -> Result<(u64, u64, u64, u64), Error> {
+    let mut out = [0u64; 4];
+    check(unsafe { sys::bn254_kzg_state(out.as_mut_ptr()) })?;
+    Ok((out[0], out[1], out[2], out[3]))
+}
+
 /// The library this crate was generated for?  (`bn254_abi_version`: bumped whenever a function changes its arguments, an array its length or a slot its meaning.)
 pub fn abi_matches() -> bool { unsafe { sys::bn254_abi_version() == sys::BN254_ABI_VERSION } }
 

@@ -17,4 +17,5 @@ from .binding import (  # noqa: F401
     set_pairing_params, pairing_params, pairing_state, dbg_pairing_form, PAIRING_FORM_LANES, PAIRING_FORM_COOP,
     g2_prepare, pairing_check_batch_shared, pairing_batch_shared, pairing_check_batch_shared_device, dbg_pairing_batch_shared, pairing_packed_len, G2_PREPARED_LEN,
     PAIRING_G1_LEN,
+    kzg_key_prepare, kzg_verify_batch, kzg_verify_batch_device, kzg_reserve, set_kzg_params, kzg_params, kzg_state, dbg_kzg_fold, KZG_OPENING_LEN, KZG_KEY_LEN,
 )

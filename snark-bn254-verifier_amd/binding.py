@@ -1065,3 +1065,104 @@ def dbg_pairing_plan(n_pairs, n):
     out = (C.c_uint64 * 4)()
     _check(_pairing_lib().bn254_dbg_pairing_plan(n_pairs, n, out))
     return {"ws_items": out[0], "pass_items": out[1], "passes": out[2], "pinned_bytes": out[3]}
+
+
+# ---- batch verification of KZG openings (bn254_kzg_key_prepare, bn254_kzg_verify_batch, include/bn254_verify.h) ----
+KZG_OPENING_LEN = 192
+KZG_KEY_LEN = 38424
+
+
+def kzg_key_prepare(g1, g2, tau_g2):
+    """(status, key): the KZG key (KZG_KEY_LEN bytes of plain data: header, g1, the prepared records of g2 and tau_g2) when status is ACCEPT, else None with the first
+    failure over g1 (64 bytes), g2, tau_g2 (128 bytes each)  (bn254_kzg_key_prepare; host work, no device)."""
+    g1, g2, tau_g2 = bytes(g1), bytes(g2), bytes(tau_g2)
+    if len(g1) != 64 or len(g2) != 128 or len(tau_g2) != 128:
+        raise Bn254Error("kzg_key_prepare: 64, 128 and 128 bytes expected")
+    fn = lib().bn254_kzg_key_prepare
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p]
+    out = (C.c_uint8 * KZG_KEY_LEN)(); st = C.c_uint8(0xEE)
+    _check(fn(g1, g2, tau_g2, out, C.byref(st)))
+    return st.value, (bytes(out) if st.value == ACCEPT else None)
+
+
+def _kzg_shape(key, openings, n, stride):
+    key, openings = bytes(key), bytes(openings)
+    if stride is None:
+        stride = KZG_OPENING_LEN
+    if n is None:
+        n = len(openings) // stride if stride else 0
+    if len(key) < KZG_KEY_LEN:
+        raise Bn254Error("KZG batch: the key is shorter than KZG_KEY_LEN")
+    if n and stride >= KZG_OPENING_LEN and len(openings) < (n - 1) * stride + KZG_OPENING_LEN:
+        raise Bn254Error("KZG batch: the buffer is shorter than n openings")
+    return key, openings, n, stride
+
+
+def kzg_verify_batch(key, openings, n=None, stride=None, device=0, flags=0):
+    """n status bytes: ACCEPT where e(C - y g1 + z H, g2) e(-H, tau_g2) == 1 for the opening C | H | z | y (KZG_OPENING_LEN bytes), REJECT where it is not, or the
+    loader error.  flags: FLAG_STRICT_SCALARS, FLAG_RLC (the joint check over groups of 64 openings, honoured from kzg_params() openings on)  (bn254_kzg_verify_batch)."""
+    fn = lib().bn254_kzg_verify_batch
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_uint]
+    key, openings, n, stride = _kzg_shape(key, openings, n, stride)
+    status = (C.c_uint8 * max(n, 1))()
+    _check(fn(key, openings, stride, n, status, device, flags))
+    return bytes(status)[:n]
+
+
+def kzg_verify_batch_device(d_key, d_openings, n, d_status, stride=KZG_OPENING_LEN, device=0, stream=0, flags=0):
+    """bn254_kzg_verify_batch_device on device pointers (ints; d_key 4-byte aligned): enqueues on `stream` and returns (with FLAG_RLC honoured it synchronises once)."""
+    fn = lib().bn254_kzg_verify_batch_device
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+    _check(fn(d_key, d_openings, stride, n, d_status, device, stream, flags))
+
+
+def kzg_reserve(n, device=0):
+    """Makes `device` ready for KZG batches of n openings: a later kzg_verify_batch_device of up to n openings without FLAG_RLC only enqueues  (bn254_kzg_reserve)."""
+    fn = lib().bn254_kzg_reserve
+    fn.argtypes = [C.c_size_t, C.c_int]
+    _check(fn(n, device))
+
+
+def set_kzg_params(rlc_min=-1):
+    """bn254_set_kzg_params: FLAG_RLC is honoured from rlc_min openings per launch on (never below 64; negative: unchanged)."""
+    fn = lib().bn254_set_kzg_params
+    fn.argtypes = [C.c_long]; fn.restype = None
+    fn(rlc_min)
+
+
+def kzg_params():
+    """rlc_min as it is now (bn254_kzg_params)."""
+    fn = lib().bn254_kzg_params
+    fn.argtypes = [C.POINTER(C.c_long)]
+    out = (C.c_long * 1)()
+    _check(fn(out))
+    return int(out[0])
+
+
+def kzg_state():
+    """(launches that ran the joint check, groups they checked, groups that failed, launches on the exact path)  (bn254_kzg_state)."""
+    fn = lib().bn254_kzg_state
+    fn.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    _check(fn(out))
+    return tuple(int(x) for x in out)
+
+
+def dbg_kzg_fold(key, openings, n=None, stride=None, weights=None, flags=0, device=-1, form=0, want_groups=False):
+    """bn254_dbg_kzg_fold: {"f", "h": n x 64 bytes (vp_p(0), vp_p(1); zero: identity or decided), "inf": n x 2 flags, "status": n bytes, "groups": None or a list of
+    (F sum, H sum, flags, status) per 64 openings}.  weights: None or n 128-bit integers (FLAG_RLC; forced odd); device -1 is the host compile, no GPU needed."""
+    fn = lib().bn254_dbg_kzg_fold
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_char_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    key, openings, n, stride = _kzg_shape(key, openings, n, stride)
+    wb = None if weights is None else b"".join(int(w).to_bytes(16, "big") for w in weights)
+    if wb is not None and len(wb) != 16 * n:
+        raise Bn254Error("dbg_kzg_fold: one weight per opening")
+    groups = (n + 63) // 64
+    f = (C.c_uint8 * max(64 * n, 1))(); h = (C.c_uint8 * max(64 * n, 1))(); inf = (C.c_uint8 * max(2 * n, 1))(); status = (C.c_uint8 * max(n, 1))()
+    grp = (C.c_uint8 * max(131 * groups, 1))() if want_groups else None
+    _check(fn(key, openings, stride, n, wb, flags, f, h, inf, status, grp, device, form))
+    out = {"f": bytes(f)[:64 * n], "h": bytes(h)[:64 * n], "inf": bytes(inf)[:2 * n], "status": bytes(status)[:n], "groups": None}
+    if want_groups:
+        g = bytes(grp)
+        out["groups"] = [(g[131 * q:131 * q + 64], g[131 * q + 64:131 * q + 128], g[131 * q + 128:131 * q + 130], g[131 * q + 130]) for q in range(groups)]
+    return out

@@ -1,6 +1,7 @@
 // bn254_capi_dbg.hip -- the bn254_dbg_* probes of the C ABI (include/bn254_verify.h; tests and tools): device arithmetic, plans, tables, the
 // VALU peak -- and the synthetic workload generator of the bench and the tests.
 #include "bn254_capi_internal.h"
+#include "bn254_capi_kzg.h"
 #include <climits>
 
 extern "C" {
@@ -929,6 +930,27 @@ int bn254_dbg_plonk_group_sums(const uint8_t* p0, const uint8_t* p1, const uint8
   HIPCK(hipMemcpy(n_failed, fail, sizeof(uint32_t), hipMemcpyDeviceToHost));
   return BN254_OK;
 }
+
+// ---------------------------------------------------------------- the KZG batch (bn254_capi_kzg.hip)
+// Part of the library and of a harness that brings bn254_capi_kzg.hip (tests/hostsan/hostsan_kzg.cpp defines BN254_HOSTSAN_KZG); the one-unit host build of
+// bn254_capi.hip leaves it out, like the pairing batch
+#if defined(__HIPCC__) || defined(BN254_HOSTSAN_KZG)
+int bn254_dbg_kzg_fold(const uint8_t* key, const uint8_t* openings, size_t stride, size_t n, const uint8_t* weights, unsigned flags, uint8_t* out_f, uint8_t* out_h,
+                       uint8_t* out_inf, uint8_t* out_status, uint8_t* out_group, int device, int form) {
+  bool done;
+  int rc = kzg_check_args(key, openings, stride, n, out_status, flags, true, &done);
+  if (rc) return rc;
+  const bool weighted = (flags & BN254_FLAG_RLC) != 0;
+  if ((n && (!out_f || !out_h || !out_inf)) || ((weights || out_group) && !weighted)) return set_err(BN254_E_BAD_ARG, "bad argument: weights and out_group need BN254_FLAG_RLC");
+  if (device < -1 || form < 0 || form > bn254::PAIRING_FORM_COOP || (form != bn254::PAIRING_FORM_PLAN && device < 0))
+    return set_err(BN254_E_BAD_ARG, "bad argument: form 0 runs anywhere, form 1 (lane) and 2 (cooperative) run on a device");
+  if (n > (size_t)G1P_MAX_ITEMS || (form == bn254::PAIRING_FORM_COOP && n > (size_t)COOP12_MAX_PROOFS)) return set_err(BN254_E_BAD_ARG, "bad argument: n is at most 65536 (30 720 in the cooperative form)");
+  if (done) return BN254_OK;
+  KzgProbeHost ph{out_f, out_h, out_inf, out_group};
+  if (device < 0) return kzg_fold_on_host(key, openings, stride, n, weights, flags, weighted, ph, out_status);
+  return kzg_host_call(key, openings, stride, n, out_status, device, flags, form, weights, weighted, &ph);
+}
+#endif
 
 // ---------------------------------------------------------------- synthetic workload generator
 size_t bn254_synth_groth16_vk_len(size_t n_public) { return 292 + 32 * (n_public + 1) + 4 + 128; }

@@ -9,6 +9,7 @@
 // (tests/hostsan/hostsan_pairing.cpp, hostsan_pairing_shared.cpp).
 #include "bn254_capi_internal.h"
 #include "bn254_pairing_batch.h"
+#include "bn254_capi_pairing.h"
 
 // items per pass: what the workspace of a device holds at most (1.2 GB) and what one launch works on
 #define PB_PASS_ITEMS ((size_t)1 << 18)
@@ -22,9 +23,10 @@ static const size_t g_pb_pass_items = [] { long v = env_long("BN254_PAIRING_PASS
 // cooperative form (k_coop12_miller_pairs), larger ones the lane form; 0: always the lane form.  BN254_COOP=0 switches it off (bn254_g16_plan.h::pairing_form)
 static long pb_coop_clamp(long v) { return v > (long)COOP12_MAX_PROOFS ? (long)COOP12_MAX_PROOFS : v; }
 static std::atomic<long> g_pb_coop_max{[] { long v = env_long("BN254_PAIRING_COOP_MAX", (long)PAIRING_COOP_MAX_DEFAULT); return v < 0 ? (long)PAIRING_COOP_MAX_DEFAULT : pb_coop_clamp(v); }()};
-static inline int pb_form(size_t n_pairs, size_t n) { return bn254::pairing_form(n_pairs, n, (size_t)g_pb_coop_max.load(std::memory_order_relaxed), bn254::knob_coop_on()); }
+int pb_form(size_t n_pairs, size_t n) { return bn254::pairing_form(n_pairs, n, (size_t)g_pb_coop_max.load(std::memory_order_relaxed), bn254::knob_coop_on()); }
 // bn254_pairing_state: launches enqueued so far in the cooperative | the lane form
 static std::atomic<uint64_t> g_pb_launches[2];
+void pb_count_launch(int form) { g_pb_launches[form == bn254::PAIRING_FORM_COOP ? 0 : 1].fetch_add(1, std::memory_order_relaxed); }
 
 // The passes of a call, without a device (bn254_dbg_pairing_plan reads the same functions).  ws_items: the workspace a reservation of n items allocates; host_pass:
 // the items per pass of the host entries, every one of which fits that reservation
@@ -47,17 +49,8 @@ struct PbShared {
   size_t bytes() const { return count() * PB_PREP_LEN; }
 };
 
-struct PbDev {
-  std::mutex mu;                       // uploads, (re)allocation, the enqueue of a call; held for the whole of a host-buffer call (the staging belongs to one call at a time)
-  bool ready = false;
-  DevBuf<int32_t> ws, one;             // G16_WS_BYTES_PER_PROOF per item; 1 in GT
-  size_t ws_items() const { return ws.cap() / (size_t)(G16_WS_BYTES_PER_PROOF / 4); }
-  Event busy_ev; bool busy_valid = false;
-  // host-buffer entries: the records, status bytes and GT values of a pass on both sides
-  Stream stream;
-  DevBuf<uint8_t> d_in, d_status, d_gt;
-  PinBuf<uint8_t> h_in, h_status, h_gt;
-};
+}  // namespace
+
 // never destroyed (device memory must not be freed from a static destructor: bn254_capi_internal.h, KeyCache); map nodes never move
 PbDev* pb_dev(int device) {
   static std::mutex mu;
@@ -77,6 +70,8 @@ int pb_ensure(PbDev& d, int device, size_t n) {
   }
   return d.ws.ensure(pb_ws_items(n) * (size_t)(G16_WS_BYTES_PER_PROOF / 4));
 }
+namespace {
+
 // caller holds d.mu; everything on `user`, nothing allocated.  verdict: the status bytes are ACCEPT / REJECT; d_gt (may be null): the GT values
 // force: PAIRING_FORM_PLAN, or the form every launch takes (the probe; the caller has checked n against the cooperative range).  A launch is never split between forms
 int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pairs, size_t n, uint8_t* d_status, uint8_t* d_gt, bool verdict, hipStream_t user,
@@ -92,7 +87,7 @@ int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pa
     a.shared_mask = sh.mask; a.prepared = (const int32_t*)sh.prepared;
     const hipError_t e = bn254_launch_pairing_batch(a, user);
     if (e != hipSuccess) return launch_err(e, "pairing batch");
-    g_pb_launches[a.form == bn254::PAIRING_FORM_COOP ? 0 : 1].fetch_add(1, std::memory_order_relaxed);
+    pb_count_launch(a.form);
   }
   HIPCK(hipEventRecord(d.busy_ev, user));
   d.busy_valid = true;

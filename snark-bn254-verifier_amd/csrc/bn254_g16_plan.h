@@ -59,14 +59,15 @@ inline G16Form g16_launch_form(size_t n, size_t n_public, bool inputs_match_key,
 // is there at all).  What a value means is each launcher's own rule: the one-line functions below, side by side.  bn254_dbg_launch_knobs shows them as the process
 // sees them.
 #define G16_MILLER_STEPS 88   // BN_ATE_STEPS (bn254_constants.h; static_asserted in bn254_kernels.hip)
-struct LaunchKnobs { bool set_coop, set_run_steps, set_coop_fixed_max, set_wide_per; int coop, run_steps, wide_per; long coop_fixed_max; };
+struct LaunchKnobs { bool set_coop, set_run_steps, set_coop_fixed_max, set_wide_per; int coop, run_steps, wide_per; long coop_fixed_max; bool set_kzg_rlc_min; long kzg_rlc_min; };
 inline const LaunchKnobs& launch_knobs() {
   static const LaunchKnobs knobs = [] {
-    LaunchKnobs k = {false, false, false, false, 0, 0, 0, 0};
+    LaunchKnobs k = {false, false, false, false, 0, 0, 0, 0, false, 0};
     if (const char* e = getenv("BN254_COOP")) { k.set_coop = true; k.coop = atoi(e); }
     if (const char* e = getenv("BN254_MILLER_RUN_STEPS")) { k.set_run_steps = true; k.run_steps = atoi(e); }
     if (const char* e = getenv("BN254_COOP_FIXED_MAX")) { k.set_coop_fixed_max = true; k.coop_fixed_max = atol(e); }
     if (const char* e = getenv("BN254_WIDE_PER")) { k.set_wide_per = true; k.wide_per = atoi(e); }
+    if (const char* e = getenv("BN254_KZG_RLC_MIN")) { k.set_kzg_rlc_min = true; k.kzg_rlc_min = atol(e); }
     return k;
   }();
   return knobs;
@@ -89,6 +90,8 @@ inline int knob_run_steps_pairing_batch() { const LaunchKnobs& k = launch_knobs(
 inline size_t knob_coop_fixed_max() { const LaunchKnobs& k = launch_knobs(); return k.set_coop_fixed_max ? (size_t)k.coop_fixed_max : (size_t)COOP12_MAX_PROOFS_FIXED; }
 // BN254_WIDE_PER (experiments): inputs per lane of the wide MSM, at least G16_WIDE_MSM_INPUTS_PER_LANE (the partial-sum buffer is sized for that many chunks); 0: the default
 inline int knob_wide_per() { const LaunchKnobs& k = launch_knobs(); return k.set_wide_per && k.wide_per >= G16_WIDE_MSM_INPUTS_PER_LANE && k.wide_per <= 256 ? k.wide_per : 0; }
+// BN254_KZG_RLC_MIN: the initial value of bn254_set_kzg_params (bn254_capi_kzg.hip clamps it); -1: not set
+inline long knob_kzg_rlc_min() { const LaunchKnobs& k = launch_knobs(); return k.set_kzg_rlc_min && k.kzg_rlc_min >= 0 ? k.kzg_rlc_min : -1; }
 
 // ---- compaction of a lane launch (k_g16_classify / k_g16_compact_write, bn254_k_g16_load.hip) ----------------------------------------------
 // A proof the loader decides for good (a coordinate >= p, A or B off the curve) would still ride its wavefront through the Miller loop and the final

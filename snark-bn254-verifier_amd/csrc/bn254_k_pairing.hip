@@ -109,13 +109,14 @@ using namespace bn254;
 hipError_t bn254_launch_pairing_batch(const PairingLaunchArgs& a, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   if (a.n > (size_t)G16_MAX_LAUNCH || a.n_pairs < 1 || a.n_pairs > PB_MAX_PAIRS || (!a.one && !a.out_gt)) return hipErrorInvalidValue;
-  if ((a.shared_mask >> a.n_pairs) != 0 || (a.shared_mask && (!a.prepared || ((uintptr_t)a.prepared & 3))) || a.item_stride < pb_item_len(a.n_pairs, a.shared_mask)) return hipErrorInvalidValue;
+  if ((a.shared_mask >> a.n_pairs) != 0 || (a.shared_mask && (!a.prepared || ((uintptr_t)a.prepared & 3))) || (!a.skip_load && a.item_stride < pb_item_len(a.n_pairs, a.shared_mask))) return hipErrorInvalidValue;
   const unsigned grid = grid_for(a.n);
   const uint32_t nn = (uint32_t)a.n;
   const int form = a.form != PAIRING_FORM_PLAN ? a.form : pairing_form((size_t)a.n_pairs, a.n, (size_t)PAIRING_COOP_MAX_DEFAULT, knob_coop_on());
   if (form != PAIRING_FORM_LANES && (form != PAIRING_FORM_COOP || a.n > (size_t)COOP12_MAX_PROOFS)) return hipErrorInvalidValue;
-  // shared_mask == 0 is the path of the all-variable entry, kernel for kernel
-  if (a.shared_mask) hipLaunchKernelGGL(k_pairing_load_shared, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, (uint32_t)a.shared_mask, a.prepared, nn, a.ws, a.status);
+  // shared_mask == 0 is the path of the all-variable entry, kernel for kernel; skip_load: the caller's own loader has filled the workspace and the status bytes
+  if (a.skip_load) {}
+  else if (a.shared_mask) hipLaunchKernelGGL(k_pairing_load_shared, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, (uint32_t)a.shared_mask, a.prepared, nn, a.ws, a.status);
   else hipLaunchKernelGGL(k_pairing_load, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, nn, a.ws, a.status);
   if (form == PAIRING_FORM_COOP) {
     // twelve lanes per item (after k_pairing_load_shared as well: the shared points are in the workspace as if they had come from the item, and the form has no use

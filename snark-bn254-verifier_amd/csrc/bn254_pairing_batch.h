@@ -206,13 +206,10 @@ inline uint8_t pb_item_on_host(const uint8_t* rec, int np, uint8_t* out_gt, int 
 
 // pb_item_on_host for the packed record of an item with shared positions: pb_load_item_shared, vm_miller_run_mix, the same final exponentiation and compare.
 // prepared: the records of the shared positions, headers checked by the caller
-inline uint8_t pb_item_shared_on_host(const uint8_t* rec, int np, uint32_t mask, const int32_t* prepared, uint8_t* out_gt, int run_steps = BN_ATE_STEPS) {
+// the part of pb_item_shared_on_host behind the loader: a lane whose points and identity bits are in place (bn254_kzg.h fills one from the G1 walk)
+inline uint8_t pb_lane_shared_on_host(PbHostLane& w, int np, uint32_t mask, const int32_t* prepared, uint8_t* out_gt, int run_steps = BN_ATE_STEPS) {
   static const PbHostKinds kinds;
-  PbHostLane w;
-  for (auto& x : w.e) x = fp_zero();
   const uint32_t all = (1u << np) - 1u;
-  int st = pb_load_item_shared(w, rec, np, mask & all, prepared, false);
-  if (!(st & BN254_ST_PENDING)) return (uint8_t)st;
   const uint32_t ident = pb_ident(w);
   if (run_steps < 1) run_steps = 1;
   const PbRecLines lines{prepared};
@@ -235,6 +232,14 @@ inline uint8_t pb_item_shared_on_host(const uint8_t* rec, int np, uint32_t mask,
   for (int l = 0; l < BN_NL; l++) one[l] = BN_ONE[l];
   return vm_f12_eq_const(w, VE_S0, one) ? BN254_ST_ACCEPT : BN254_ST_REJECT;
 }
+inline uint8_t pb_item_shared_on_host(const uint8_t* rec, int np, uint32_t mask, const int32_t* prepared, uint8_t* out_gt, int run_steps = BN_ATE_STEPS) {
+  PbHostLane w;
+  for (auto& x : w.e) x = fp_zero();
+  const uint32_t all = (1u << np) - 1u;
+  int st = pb_load_item_shared(w, rec, np, mask & all, prepared, false);
+  if (!(st & BN254_ST_PENDING)) return (uint8_t)st;
+  return pb_lane_shared_on_host(w, np, mask, prepared, out_gt, run_steps);
+}
 
 // ---- the launches of one pass (bn254_k_pairing.hip): load, the Miller loop in runs, the final exponentiation, the tail ----------------------------------------
 struct PairingLaunchArgs {
@@ -249,6 +254,8 @@ struct PairingLaunchArgs {
   int form = 0;                               // bn254_g16_plan.h: PAIRING_FORM_PLAN (pairing_form at the default threshold), _LANES, _COOP (n <= COOP12_MAX_PROOFS)
   unsigned shared_mask = 0;                   // bit j: position j's G2 is shared; then the items are PACKED (pb_item_len) and
   const int32_t* prepared = nullptr;          // device memory, 4-byte aligned: popcount(shared_mask) records of PB_PREP_LEN bytes, ascending position order
+  bool skip_load = false;                     // the workspace and the status bytes are what a loader left already (bn254_kzg.h: the G1 points come from the G1 walk);
+                                              // pairs / item_stride are not read.  Every launch behind the load step is the same
 };
 
 }  // namespace bn254

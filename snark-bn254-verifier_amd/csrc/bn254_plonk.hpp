@@ -690,7 +690,13 @@ static_assert(sizeof(MsmTerm) == 104, "term layout");
 // c1 = floor(k g1 / 2^256), c2 = floor(k g2 / 2^256) with g1 = floor(2^256 b2 / r), g2 = floor(-2^256 b1 / r);  k1 = k - c1 a1 - c2 a2,
 // k2 = -c1 b1 - c2 b2.  (tests/test_capi_cpu.py::test_glv_decomposition checks the identity and the bounds through bn254_dbg_glv_decompose.)
 struct Glv { uint64_t k1[2], k2[2]; bool neg1, neg2; };
-PL_HD Glv glv_decompose(const FrM& kc /* canonical, < r */) {
+// (also a device function outside the PlonK stages' translation unit: the loader of bn254_kzg.h splits its scalars on the device)
+#if defined(__HIPCC__)
+#define PL_GLV_HD __host__ __device__ inline
+#else
+#define PL_GLV_HD inline
+#endif
+PL_GLV_HD Glv glv_decompose(const FrM& kc /* canonical, < r */) {
   typedef unsigned __int128 u128;
   const uint64_t A1 = 0x89d3256894d213e3ull;
   const uint64_t B1[2] = {0x8211bbeb7d4f1128ull, 0x6f4d8248eeb859fcull};        // |b1|

@@ -292,6 +292,14 @@ def model_kernel(name, ins):
                 if h < h2 and l2[-1] < latches[-1] and count_in(mads, h2, l2[-1]) == 0:
                     weight_ranges.append((h2, l2[-1], 29.0))
             notes.append("binary-GCD inversion: 18 rounds of 29 steps (%d multiply-adds per round)" % c)
+        elif name == "k_kzg_load" and len([1 for a_, t_, _ in ins if a_ >= latches[-1] and not t_.startswith("s_nop")]) <= 16 and count_in(mads, latches[-1], ins[-1][0]) == 0:
+            # not loops: the kernel ends in a chain of branches back INTO its body (behind them a few scalar instructions and padding) -- trampolines of the lane-divergent regions (an opening
+            # the loader decides, the weighted and the exact records), entered by forward branches.  Every block runs once per opening; the Fr products, the GLV split
+            # and the curve checks in them are unrolled
+            if not any(n_.startswith("tail trampolines") for n_ in notes):
+                notes.append("tail trampolines back into the body (unconditional branches, not loops): every block once per opening")
+        elif name == "k_kzg_fetch" and not inner:
+            weight_ranges.append((h, latches[-1], 2.0)); notes.append("the two G1 points of an item (%d mads per point: two conversions to canonical words)" % c)
         elif own > 0:
             unmodelled.append("loop +0x%x..+0x%x (%d mads, %d of its own) counted once" % (h - ins[0][0], latches[-1] - ins[0][0], c, own))
     total = 0.0
