@@ -843,6 +843,10 @@ int bn254_dbg_g16_rlc_plan(size_t reserved, size_t m, int n_streams, int log2_gr
  * per launch part {first group, groups}, as the enqueue places them (at most max_parts written, *n_parts = parts) */
 int bn254_dbg_g16_rlc_wide_plan(size_t m, int n_streams, int log2_group, int log2_share, size_t min_lanes, size_t key_inputs, int msm_form, uint64_t alloc[3],
                                 uint64_t* parts_out, int max_parts, int* n_parts);
+/* ... and the groups themselves, under the knobs as this process holds them (BN254_RLC_GROUP_LOG2, BN254_RLC_SHARE_LOG2, BN254_STREAMS, share_min_lanes of
+ * bn254_set_rlc_params) -- the plan the enqueue makes for a chunk of m proofs (at most 1 048 576), host only: out_group[i] = the group of proof i, numbered through the
+ * chunk (the groups of the launch parts before its own come first); out_log2_share[i] = log2 of the proofs per Miller-loop lane in its launch part */
+int bn254_dbg_g16_rlc_groups(size_t m, unsigned* out_group, uint8_t* out_log2_share);
 /* the decision of bn254_groth16_stream_overlap replayed over n_batches batches of one (key, device), host only (csrc/bn254_overlap_vote.h: the functions the enqueue
  * itself calls, in its order -- read the measurement an earlier batch recorded, begin the batch, measure it if the question is open).  kind[b]: 0 the batch cannot be
  * measured (it would not run two sub-batches of nearly equal size side by side); 1 it can, and its events will read timings[4 b ..] = {a0, a1, s1, e1} ms: the durations

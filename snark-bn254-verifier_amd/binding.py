@@ -147,6 +147,16 @@ def dbg_rlc_wide_plan(m, n_streams=2, log2_group=5, log2_share=3, min_lanes=6553
     return {"rows": alloc[0], "digits": alloc[1], "part": alloc[2]}, [(parts[2 * i], parts[2 * i + 1]) for i in range(k.value)]
 
 
+def dbg_rlc_groups(m):
+    """The groups a chunk of m proofs forms under FLAG_RLC with the knobs as they stand (bn254_dbg_g16_rlc_groups: the plan the enqueue makes, host only).
+    Returns (group of every proof, numbered through the chunk; log2 of the proofs per Miller-loop lane of every proof's launch part)."""
+    L = lib()
+    L.bn254_dbg_g16_rlc_groups.argtypes = [C.c_size_t, C.POINTER(C.c_uint), C.POINTER(C.c_uint8)]
+    group = (C.c_uint * m)(); share = (C.c_uint8 * m)()
+    _check(L.bn254_dbg_g16_rlc_groups(m, group, share))
+    return list(group), list(share)
+
+
 def dbg_overlap_replay(batches, fallback=True):
     """The stream-overlap decision over a sequence of batches, without a device (bn254_dbg_overlap_replay).  batches: per batch None (cannot be measured), "untimed"
     (measured, timings cannot be had) or (a0, a1, s1, e1) in ms.  Returns per batch (probe_now, single_stream, state, serial votes, last ratio read)."""

@@ -294,13 +294,18 @@ static int rlc_ensure(const bn254_g16_pvk* pvk, DevState* d, size_t n, size_t n_
   }
   return BN254_OK;
 }
-static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
-                           size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
-  (void)device;
-  const int n_streams = sub_batch_streams();
+// The RLC plan of a chunk of m proofs under the knobs as they stand: the ONE reading of BN254_RLC_GROUP_LOG2, BN254_RLC_SHARE_LOG2 (once per process), BN254_STREAMS
+// and share_min_lanes (bn254_set_rlc_params may run beside a batch: one load per chunk).  g16_enqueue_rlc launches by it; bn254_dbg_g16_rlc_groups shows it.
+static bool g16_rlc_chunk_plan_now(G16RlcChunkPlan& plan, size_t m) {
   static const int log2_group = [] { const char* e = getenv("BN254_RLC_GROUP_LOG2"); int v = e ? atoi(e) : 5; return v < 1 ? 1 : (v > 16 ? 16 : v); }();
   // proofs per lane in the Miller loop (shared accumulator, one squaring of f per lane and step): 2^BN254_RLC_SHARE_LOG2, at most the group
   static const int log2_share_env = [] { const char* e = getenv("BN254_RLC_SHARE_LOG2"); int v = e ? atoi(e) : 3; return v < 0 ? 0 : (v > 3 ? 3 : v); }();
+  const long ml = g_rlc_share_min_lanes.load();
+  return g16_plan_rlc_chunk(plan, m, sub_batch_streams(), log2_group, log2_share_env, ml < 1 ? 1 : (size_t)ml);
+}
+static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, const void* d_proofs, size_t proof_stride, const void* d_inputs,
+                           size_t n_public, size_t n, void* d_status, hipStream_t user, unsigned flags) {
+  (void)device;
   uint32_t key[11];
   if (getrandom(key, sizeof key, 0) != (ssize_t)sizeof key) return set_err(BN254_E_HIP, "getrandom failed: no weights for the RLC mode");
   size_t seen_checked = 0, seen_fallback = 0;
@@ -309,8 +314,7 @@ static int g16_enqueue_rlc(const bn254_g16_pvk* pvk, DevState* d, int device, co
     const size_t m = n - off < chunk ? n - off : chunk;
     // ONE plan per chunk (and one reading of the knob: bn254_set_rlc_params may run beside this call): what rlc_ensure sizes for is what the parts address
     G16RlcChunkPlan plan;
-    const long ml = g_rlc_share_min_lanes.load();
-    if (!g16_plan_rlc_chunk(plan, m, n_streams, log2_group, log2_share_env, ml < 1 ? 1 : (size_t)ml)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+    if (!g16_rlc_chunk_plan_now(plan, m)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
     const bool wide = n_public > (size_t)RLC_MAX_PUBLIC;
     int rc = rlc_ensure(pvk, d, m, n_public, plan);
     if (rc) return rc;
@@ -483,6 +487,22 @@ void bn254_set_rlc_params(long min_batch, int adaptive, long share_min_lanes) {
   if (min_batch >= 0) g_rlc_min_batch.store(min_batch < RLC_MIN_BATCH ? (long)RLC_MIN_BATCH : min_batch);
   if (adaptive >= 0) g_rlc_adaptive.store(adaptive ? 1 : 0);
   if (share_min_lanes >= 0) g_rlc_share_min_lanes.store(share_min_lanes < 1 ? 1 : share_min_lanes);
+}
+
+// Host-only probe: the groups a chunk of m proofs forms under BN254_FLAG_RLC with the knobs as they stand -- the plan g16_enqueue_rlc makes for that chunk.
+// out_group[i]: proof i's group, numbered through the chunk (the groups of the launch parts before its own come first); out_log2_share[i]: its part's log2_share
+int bn254_dbg_g16_rlc_groups(size_t m, unsigned* out_group, uint8_t* out_log2_share) {
+  if (!out_group || !out_log2_share || m == 0 || m > (size_t)G16_MAX_BATCH) return set_err(BN254_E_BAD_ARG, "bad argument");
+  G16RlcChunkPlan plan;
+  if (!g16_rlc_chunk_plan_now(plan, m)) return set_err(BN254_E_BAD_ARG, "batch cannot be planned");
+  for (int pi = 0; pi < plan.parts; pi++) {
+    const G16RlcPart& q = plan.part[pi];
+    for (size_t i = 0; i < q.count; i++) {
+      out_group[q.first + i] = (unsigned)q.wide_off + rlc_group_of((uint32_t)i, q.plan);
+      out_log2_share[q.first + i] = (uint8_t)q.log2_share;
+    }
+  }
+  return BN254_OK;
 }
 
 int bn254_groth16_rlc_state(const bn254_g16_pvk* pvk, int device, float* fallback_share, unsigned* bypassed_calls) {

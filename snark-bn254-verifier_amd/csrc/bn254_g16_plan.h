@@ -191,7 +191,7 @@ inline bool g16_plan_chunk(G16ChunkPlan& p, size_t m, size_t key_inputs, size_t 
 // A chunk of m proofs runs as `parts` launch parts; part pi forms rlc_plan(its proofs).groups groups.  Their status bytes sit in a region rounded up to 256
 // (k_rlc_* grids are multiples of 256 lanes), one part's region after the other; for keys with more than RLC_MAX_PUBLIC inputs the group scalars and the groups'
 // MSM scratch of the parts sit side by side, unrounded.  g16_plan_rlc_chunk is the ONE walk over the parts: rlc_ensure sizes from it, g16_enqueue_rlc addresses by
-// it, bn254_dbg_g16_rlc_plan / _rlc_wide_plan show it.  g16_rlc_alloc(m) is what rlc_ensure allocates for the status bytes of a chunk of m proofs.
+// it, bn254_dbg_g16_rlc_plan / _rlc_wide_plan / _rlc_groups show it.  g16_rlc_alloc(m) is what rlc_ensure allocates for the status bytes of a chunk of m proofs.
 inline size_t g16_rlc_alloc(size_t m) { return g16_round256(m) + 1024; }
 struct G16RlcPart {
   size_t first, count;       // proofs [first, first + count) of the chunk

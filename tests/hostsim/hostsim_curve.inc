@@ -177,6 +177,8 @@ int hs_vm_pairing2_fixed(uint8_t* o, const uint8_t* p0, const uint8_t* q0, const
 // proofs: n x 256 B (A | B | C, gnark uncompressed), inputs: n x n_public x 32 B big-endian, alpha: 64 B (negated here), ks: (n_public + 1) x 64 B,
 // qg / qd / qb: the key-side G2 arguments g', d', b' (128 B each).  key44: ChaCha key (32 B) + nonce (12 B).  out_groups[g] = 1 if group g's
 // product is one; out_group_of[i] = group of proof i; bad_mask bit i: treat proof i as a loader error (neutral lane).  Returns the group count.
+// weight_mode 0: proof i draws ChaCha20 counter i, as k_rlc_scale does; 1 (this stand-in's own, for tests/test_rlc_forgery_cpu.py): every proof draws counter 0,
+// so all weights are equal -- the defect a pair of proofs with opposite errors passes under.
 struct HostWs2 {
   HostWs *lo, *hi;
   void park(int slot, const Fp2& a) { lo->park(slot, a); }
@@ -205,7 +207,7 @@ struct HostWsM {
 };
 int hs_rlc_pipeline(int n, const uint8_t* proofs, const uint8_t* inputs, int n_public, const uint8_t* alpha, const uint8_t* ks,
                     const uint8_t* qg, const uint8_t* qd, const uint8_t* qb, const uint8_t* key44, int log2_group, uint32_t bad_mask,
-                    uint8_t* out_groups, uint32_t* out_group_of, int log2_share) {
+                    uint8_t* out_groups, uint32_t* out_group_of, int log2_share, int weight_mode) {
   static FixedLine tg[BN_ATE_STEPS], td[BN_ATE_STEPS], tb[BN_ATE_STEPS];
   if (!fixed_line_table(tg, g2_in(qg)) || !fixed_line_table(td, g2_in(qd)) || !fixed_line_table(tb, g2_in(qb))) return -1;
   ChaChaKey key;
@@ -224,7 +226,7 @@ int hs_rlc_pipeline(int n, const uint8_t* proofs, const uint8_t* inputs, int n_p
     w.el[VE_F] = fp_one();
     w.el[VE_T] = B.x.c0; w.el[VE_T + 1] = B.x.c1; w.el[VE_T + 2] = B.y.c0; w.el[VE_T + 3] = B.y.c1; w.el[VE_T + 4] = fp_one();
     uint32_t r[4];
-    chacha20_block4(r, key, (uint32_t)i);
+    chacha20_block4(r, key, weight_mode == 1 ? 0u : (uint32_t)i);
     const uint8_t* in = inputs + (size_t)i * n_public * 32;
     vm_rlc_scale(w, r, n_public, [&](int j, uint32_t* o) { words_from_be(o, in + 32 * j); });
     if (log2_share == 0) {

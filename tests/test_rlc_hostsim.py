@@ -142,7 +142,7 @@ def test_rlc_group_pipeline(hostsim, pkg, O, n, log2_group, bad, log2_share):
     alpha, ks, qg, qd, qb = _key_points(pkg, vk, n_public)
     key = hashlib.sha256(b"rlc-test-key").digest() + bytes(12)
     groups = (C.c_uint8 * n)(); group_of = (C.c_uint32 * n)()
-    ng = hostsim.hs_rlc_pipeline(n, bytes(proofs), bytes(inputs), n_public, alpha, ks, qg, qd, qb, key, log2_group, 0, groups, group_of, log2_share)
+    ng = hostsim.hs_rlc_pipeline(n, bytes(proofs), bytes(inputs), n_public, alpha, ks, qg, qd, qb, key, log2_group, 0, groups, group_of, log2_share, 0)
     assert ng >= 1
     bad_groups = {group_of[i] for i in bad}
     assert [groups[g] for g in range(ng)] == [0 if g in bad_groups else 1 for g in range(ng)]
@@ -150,5 +150,5 @@ def test_rlc_group_pipeline(hostsim, pkg, O, n, log2_group, bad, log2_share):
     if bad:
         # the same batch with the bad proofs masked out as loader errors: their lanes are neutral, all groups pass
         mask = sum(1 << i for i in bad)
-        ng2 = hostsim.hs_rlc_pipeline(n, bytes(proofs), bytes(inputs), n_public, alpha, ks, qg, qd, qb, key, log2_group, mask, groups, group_of, log2_share)
+        ng2 = hostsim.hs_rlc_pipeline(n, bytes(proofs), bytes(inputs), n_public, alpha, ks, qg, qd, qb, key, log2_group, mask, groups, group_of, log2_share, 0)
         assert ng2 == ng and all(groups[g] == 1 for g in range(ng))
