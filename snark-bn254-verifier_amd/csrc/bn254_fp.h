@@ -60,6 +60,23 @@
 #else
 #define BN_SCHED_FENCE() do { } while (0)
 #endif
+// carry ride: an identity on a 64-bit column accumulator that the IR optimiser cannot see through, so that `acc = BN_OPQ(acc) + a * b` stays one
+// v_mad_i64_i32 whose addend is the running sum.  Without it Reassociate ranks the previous column's carry highest, starts every column's multiply-adds
+// from 0 and adds the carry with a separate v_lshl_add_u64 (multiply-add issue rate).  Relies on llvm.amdgcn.softwqm being lowered to a plain COPY in a
+// compute kernel (SIWholeQuadMode), which the register coalescer deletes: no instruction, no exec change, no hazard nop in the code object.  Device only;
+// the host sees the plain value.  -DBN_NO_CARRY_RIDE gives back the reassociated chains (A/B builds, and units whose kernels spill more with the ride).
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(BN_NO_CARRY_RIDE)
+__device__ int64_t bn_opq_i64(int64_t) __asm("llvm.amdgcn.softwqm.i64");
+#define BN_OPQ(x) bn_opq_i64(x)
+#else
+#define BN_OPQ(x) (x)
+#endif
+// the form a sum takes where its caller does not say (template flag RIDE of the dot products): carry first, or -- without the ride -- the sums as they were written before it
+#if defined(BN_NO_CARRY_RIDE)
+#define BN_RIDE_DEFAULT false
+#else
+#define BN_RIDE_DEFAULT true
+#endif
 
 #if defined(BN_TRACK_BOUNDS) && !defined(__HIP_DEVICE_COMPILE__)
 #include <cmath>
@@ -118,6 +135,10 @@ BN_HD int32_t bn_p_limb(int i) {
     case 5: return BN_P5; case 6: return BN_P6; case 7: return BN_P7; default: return BN_P8;
   }
 }
+// acc += a * b with the running sum in the multiply-add's addend slot (signed and wrapping flavours).  RIDE = false is the plain sum, which the compiler
+// reassociates: the form of the callers whose kernels spill more, or issue more, with the pinned chain (profiles/carry_chain_resources.txt)
+template <bool RIDE = BN_RIDE_DEFAULT> BN_HD void bn_ride(int64_t& acc, int32_t a, int32_t b) { acc = (RIDE ? BN_OPQ(acc) : acc) + (int64_t)a * (int64_t)b; }
+template <bool RIDE = BN_RIDE_DEFAULT> BN_HD void bn_ride(uint64_t& acc, int32_t a, int32_t b) { acc = (RIDE ? (uint64_t)BN_OPQ((int64_t)acc) : acc) + (uint64_t)((int64_t)a * (int64_t)b); }
 BN_HD int32_t bn_sext29(uint32_t x) { return (int32_t)(x << 3) >> 3; }  // low 29 bits as a balanced digit
 
 BN_HD Fp fp_from_limbs(const int32_t* c) {  // a precomputed constant (balanced digits, value in [0, p))
@@ -201,20 +222,37 @@ BN_HD Fp fp_lincomb(int32_t k1, const Fp& a, int32_t k2, const Fp& b) {
 // reduce(k1*a + k2*b): q = floor(top * C / 2^52), C = floor(2^284 / p), estimates (k1 a + k2 b) / p from the top digits alone
 // (the lower digits move the quotient by < (|k1| + |k2|) * 2^232 / p < 1e-5); result in (-1e-5, 1 + 1e-5) * p.  The
 // combination never has to be representable (64-bit pass), so any input bounds are fine.
+template <bool RIDE = BN_RIDE_DEFAULT>
 BN_HD Fp fp_lincomb_reduce(int32_t k1, const Fp& a, int32_t k2, const Fp& b) {
   const int64_t C = 1420063842;
   int64_t top = (int64_t)k1 * (int64_t)a.v[BN_NL - 1] + (int64_t)k2 * (int64_t)b.v[BN_NL - 1];
   int32_t q = (int32_t)((top * C) >> 52);
   Fp r;
-  int64_t acc = 0;
+  if (RIDE) {
+    const int32_t nq = -q;   // |q| < 2^31: the estimate of a quotient below 1e5
+    int64_t acc = (int64_t)k1 * (int64_t)a.v[0] + BN_HALF;
 #pragma unroll
-  for (int i = 0; i < BN_NL - 1; i++) {
-    acc += (int64_t)k1 * (int64_t)a.v[i] + (int64_t)k2 * (int64_t)b.v[i] - (int64_t)q * (int64_t)bn_p_limb(i) + BN_HALF;
-    r.v[i] = (int32_t)((uint32_t)acc & BN_MASK) - BN_HALF;
-    acc >>= BN_LB;
+    for (int i = 0; i < BN_NL - 1; i++) {
+      if (i > 0) { acc += BN_HALF; bn_ride(acc, k1, a.v[i]); }
+      bn_ride(acc, k2, b.v[i]);
+      bn_ride(acc, nq, bn_p_limb(i));
+      r.v[i] = (int32_t)((uint32_t)acc & BN_MASK) - BN_HALF;
+      acc >>= BN_LB;
+    }
+    acc += top;
+    bn_ride(acc, nq, bn_p_limb(BN_NL - 1));
+    r.v[BN_NL - 1] = (int32_t)acc;
+  } else {
+    int64_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < BN_NL - 1; i++) {
+      acc += (int64_t)k1 * (int64_t)a.v[i] + (int64_t)k2 * (int64_t)b.v[i] - (int64_t)q * (int64_t)bn_p_limb(i) + BN_HALF;
+      r.v[i] = (int32_t)((uint32_t)acc & BN_MASK) - BN_HALF;
+      acc >>= BN_LB;
+    }
+    acc += top - (int64_t)q * (int64_t)bn_p_limb(BN_NL - 1);
+    r.v[BN_NL - 1] = (int32_t)acc;
   }
-  acc += top - (int64_t)q * (int64_t)bn_p_limb(BN_NL - 1);
-  r.v[BN_NL - 1] = (int32_t)acc;
 #if BN_TRACKING
   if (a.vb * (k1 < 0 ? -k1 : k1) + b.vb * (k2 < 0 ? -k2 : k2) > 1e5) fp_dbg_fail("fp_lincomb_reduce: out of range", a.vb + b.vb);
   if (a.lb > 1.01 || b.lb > 1.01) fp_dbg_fail("fp_lincomb_reduce: digits too large", a.lb + b.lb);
@@ -222,79 +260,121 @@ BN_HD Fp fp_lincomb_reduce(int32_t k1, const Fp& a, int32_t k2, const Fp& b) {
 #endif
   return r;
 }
-BN_HD Fp fp_reduce(const Fp& a) { return fp_lincomb_reduce(1, a, 0, a); }
+BN_HD Fp fp_reduce(const Fp& a) { return fp_lincomb_reduce<false>(1, a, 0, a); }   // (one product per digit: nothing for the carry to ride on but the sign extension)
 
 // ---- sum-of-products Montgomery reduction ----------------------------------------------------------------------------------
 // fp_dot(T...) = (sum_t sign_t * a_t * b_t) / R  mod p, reduced once.  Finely integrated product scanning: for each of the
 // 17 columns the partial products of ALL terms go into one 64-bit accumulator (a second one collects the terms with a minus
 // sign), then one Montgomery digit is retired.  Head-room: sum_t 9 lb_a lb_b 2^58 + 9 * 2^56 < 2^63.
+struct DotAcc { int64_t p1, m1, p2, m2; };  // +1, -1, +2, -2 weighted partial sums of one column; p1 starts from the previous column's carry
+#define BN_DCOL_RANGE constexpr int LO = K < BN_NL ? 0 : K - (BN_NL - 1); constexpr int HI = K < BN_NL ? K : BN_NL - 1
+template <int SIGN, int K, bool RIDE>
+BN_HD void dot_add(DotAcc& c, int32_t a, int32_t b) {
+  if (SIGN == 1 && K > 0) bn_ride<RIDE>(c.p1, a, b);   // the class that holds the carry (column 0 starts from a known 0)
+  else if (SIGN == 1) c.p1 += (int64_t)a * (int64_t)b;
+  else if (SIGN == -1) c.m1 += (int64_t)a * (int64_t)b;
+  else if (SIGN == 2) c.p2 += (int64_t)a * (int64_t)b;
+  else c.m2 += (int64_t)a * (int64_t)b;
+}
 template <int SIGN>  // +1, -1, +2, -2: weight of the product in the sum
 struct DotTerm {
   const Fp& a;
   const Fp& b;
+  static constexpr int cls = SIGN, cls_cross = SIGN;
+  // column k of one term: sum_{i=LO..HI} a_i b_{k-i}; LO, HI are compile-time so that everything unrolls into straight mads
+  template <int K, bool RIDE> BN_HD void col(DotAcc& c) const {
+    BN_DCOL_RANGE;
+#pragma unroll
+    for (int i = LO; i <= HI; i++) dot_add<SIGN, K, RIDE>(c, a.v[i], b.v[K - i]);
+  }
+#if BN_TRACKING
+  double cap() const { return 9.0 * (SIGN < 0 ? -SIGN : SIGN) * a.lb * b.lb; }
+  double val() const { return (SIGN < 0 ? -SIGN : SIGN) * a.vb * b.vb; }
+#endif
+};
+// SIGN * a^2 (SIGN = +1, -1) with the mirrored digit products written once: the diagonal a_i a_i goes to class SIGN, a cross product a_i a_j (i < j) once to the
+// class of weight 2 SIGN, which a sum that holds doubled products merges anyway.  (The reassociation that used to merge a_i a_j + a_j a_i is what the carry ride pins.)
+template <int SIGN>
+struct DotSq {
+  const Fp& a;
+  static constexpr int cls = SIGN, cls_cross = 2 * SIGN;
+  template <int K, bool RIDE> BN_HD void col(DotAcc& c) const {
+    BN_DCOL_RANGE;
+#pragma unroll
+    for (int i = LO; i <= HI; i++) {
+      if (!RIDE) dot_add<SIGN, K, RIDE>(c, a.v[i], a.v[K - i]);   // every product: the compiler merges the mirrored ones
+      else if (i < K - i) dot_add<2 * SIGN, K, RIDE>(c, a.v[i], a.v[K - i]);
+      else if (i == K - i) dot_add<SIGN, K, RIDE>(c, a.v[i], a.v[i]);
+    }
+  }
+#if BN_TRACKING
+  double cap() const { return 9.0 * a.lb * a.lb; }
+  double val() const { return a.vb * a.vb; }
+#endif
+};
+struct DotNone {  // no product: the empty slot of a term that fills fewer dot-product slots than its neighbours (fp2_dotp)
+  static constexpr int cls = 1, cls_cross = 1;
+  template <int K, bool RIDE> BN_HD void col(DotAcc&) const {}
+#if BN_TRACKING
+  double cap() const { return 0.0; }
+  double val() const { return 0.0; }
+#endif
 };
 BN_HD DotTerm<1> dplus(const Fp& a, const Fp& b) { return DotTerm<1>{a, b}; }
 BN_HD DotTerm<-1> dminus(const Fp& a, const Fp& b) { return DotTerm<-1>{a, b}; }
 template <int S> BN_HD DotTerm<S> dterm(const Fp& a, const Fp& b) { return DotTerm<S>{a, b}; }
+template <int S> BN_HD DotSq<S> dsq(const Fp& a) { return DotSq<S>{a}; }
 
-struct DotAcc { int64_t p1, m1, p2, m2; };  // +1, -1, +2, -2 weighted partial sums of one column
-// column k of one term: sum_{i=LO..HI} a_i b_{k-i}; LO, HI are compile-time so that everything unrolls into straight mads
-template <int SIGN, int K>
-BN_HD void dot_col(DotAcc& c, const DotTerm<SIGN>& t) {
-  constexpr int LO = K < BN_NL ? 0 : K - (BN_NL - 1);
-  constexpr int HI = K < BN_NL ? K : BN_NL - 1;
-#pragma unroll
-  for (int i = LO; i <= HI; i++) {
-    int64_t pr = (int64_t)t.a.v[i] * (int64_t)t.b.v[K - i];
-    if (SIGN == 1) c.p1 += pr; else if (SIGN == -1) c.m1 += pr; else if (SIGN == 2) c.p2 += pr; else c.m2 += pr;
-  }
-}
-constexpr int bn_iabs(int x) { return x < 0 ? -x : x; }
-template <int K, int... SIGNS>
-BN_HD void dot_step(int64_t& acc, int32_t (&m)[BN_NL], Fp& r, const DotTerm<SIGNS>&... terms) {
-  constexpr bool has_m1 = ((SIGNS == -1) || ...), has_p2 = ((SIGNS == 2) || ...), has_m2 = ((SIGNS == -2) || ...);
+template <int K, bool RIDE, class... T>
+BN_HD void dot_step(int64_t& acc, int32_t (&m)[BN_NL], Fp& r, const T&... terms) {
+  constexpr bool has_m1 = ((T::cls == -1) || ...), has_p2 = ((T::cls == 2 || (RIDE && T::cls_cross == 2)) || ...), has_m2 = ((T::cls == -2 || (RIDE && T::cls_cross == -2)) || ...);
   DotAcc c; c.p1 = acc; c.m1 = 0; c.p2 = 0; c.m2 = 0;
-  (dot_col<SIGNS, K>(c, terms), ...);
+  (terms.template col<K, RIDE>(c), ...);
   acc = c.p1;
+  // carry first: the +1 products, then the m[i] p terms ride on the carry in one dependent chain; the other classes are chains from zero, merged once
+  if constexpr (K < BN_NL) {
+#pragma unroll
+    for (int i = 0; i < K; i++) bn_ride<RIDE>(acc, m[i], bn_p_limb(K - i));
+  } else {
+#pragma unroll
+    for (int i = K - (BN_NL - 1); i < BN_NL; i++) bn_ride<RIDE>(acc, m[i], bn_p_limb(K - i));
+  }
   if (has_m1) acc -= c.m1;
   if (has_p2 && has_m2) acc += 2 * (c.p2 - c.m2);
   else if (has_p2) acc += 2 * c.p2;
   else if (has_m2) acc -= 2 * c.m2;
   if constexpr (K < BN_NL) {
-#pragma unroll
-    for (int i = 0; i < K; i++) acc += (int64_t)m[i] * (int64_t)bn_p_limb(K - i);
     m[K] = bn_sext29((uint32_t)acc * BN_PINV);
-    acc += (int64_t)m[K] * (int64_t)bn_p_limb(0);
+    bn_ride<RIDE>(acc, m[K], bn_p_limb(0));
     acc >>= BN_LB;  // exact: the low 29 bits are zero
   } else {
-#pragma unroll
-    for (int i = K - (BN_NL - 1); i < BN_NL; i++) acc += (int64_t)m[i] * (int64_t)bn_p_limb(K - i);
     acc += BN_HALF;
     r.v[K - BN_NL] = (int32_t)((uint32_t)acc & BN_MASK) - BN_HALF;
     acc >>= BN_LB;
   }
 }
-template <int... KS, int... SIGNS>
-BN_HD void dot_all(std::integer_sequence<int, KS...>, int64_t& acc, int32_t (&m)[BN_NL], Fp& r, const DotTerm<SIGNS>&... terms) {
-  (dot_step<KS, SIGNS...>(acc, m, r, terms...), ...);
+template <bool RIDE, int... KS, class... T>
+BN_HD void dot_all(std::integer_sequence<int, KS...>, int64_t& acc, int32_t (&m)[BN_NL], Fp& r, const T&... terms) {
+  (dot_step<KS, RIDE, T...>(acc, m, r, terms...), ...);
 }
-template <int... SIGNS>
-BN_HD Fp fp_dot(const DotTerm<SIGNS>&... terms) {
+template <bool RIDE, class... T>
+BN_HD Fp fp_dot_r(const T&... terms) {
   BN_SCHED_FENCE();
   int64_t acc = 0;
   int32_t m[BN_NL];
   Fp r;
-  dot_all(std::make_integer_sequence<int, 2 * BN_NL - 1>{}, acc, m, r, terms...);
+  dot_all<RIDE>(std::make_integer_sequence<int, 2 * BN_NL - 1>{}, acc, m, r, terms...);
   r.v[BN_NL - 1] = (int32_t)acc;
   BN_SCHED_FENCE();
 #if BN_TRACKING
-  double cap = ((9.0 * bn_iabs(SIGNS) * terms.a.lb * terms.b.lb) + ...);  // in units of 2^58
+  double cap = (terms.cap() + ...);  // in units of 2^58
   if (cap + 9.0 * 0.25 + 0.01 > 32.0) fp_dbg_fail("fp_dot: accumulator may overflow", cap);
-  double s = ((bn_iabs(SIGNS) * terms.a.vb * terms.b.vb) + ...);
+  double s = (terms.val() + ...);
   BN_SETB(r, 1.0 + s / 169.0 + 1e-6, 0.5);
 #endif
   return r;
 }
+template <class... T> BN_HD Fp fp_dot(const T&... terms) { return fp_dot_r<BN_RIDE_DEFAULT>(terms...); }
 BN_HD Fp fp_mul(const Fp& a, const Fp& b) { return fp_dot(dplus(a, b)); }
 // squaring: cross products once against a doubled operand (45 + 81 mads instead of 162)
 BN_HD Fp fp_sqr(const Fp& a) {
@@ -310,18 +390,19 @@ BN_HD Fp fp_sqr(const Fp& a) {
 #pragma unroll
     for (int i = 0; i < BN_NL; i++) {
       int j = k - i;
-      if (j >= 0 && j < BN_NL && i < j) acc += (int64_t)a2[i] * (int64_t)a.v[j];
+      if (j >= 0 && j < BN_NL && i < j) bn_ride(acc, a2[i], a.v[j]);
     }
-    if ((k & 1) == 0) acc += (int64_t)a.v[k / 2] * (int64_t)a.v[k / 2];
+    if (k == 0) acc = (int64_t)a.v[0] * (int64_t)a.v[0];
+    else if ((k & 1) == 0) bn_ride(acc, a.v[k / 2], a.v[k / 2]);
     if (k < BN_NL) {
 #pragma unroll
-      for (int i = 0; i < k; i++) acc += (int64_t)m[i] * (int64_t)bn_p_limb(k - i);
+      for (int i = 0; i < k; i++) bn_ride(acc, m[i], bn_p_limb(k - i));
       m[k] = bn_sext29((uint32_t)acc * BN_PINV);
-      acc += (int64_t)m[k] * (int64_t)bn_p_limb(0);
+      bn_ride(acc, m[k], bn_p_limb(0));
       acc >>= BN_LB;
     } else {
 #pragma unroll
-      for (int i = k - (BN_NL - 1); i < BN_NL; i++) acc += (int64_t)m[i] * (int64_t)bn_p_limb(k - i);
+      for (int i = k - (BN_NL - 1); i < BN_NL; i++) bn_ride(acc, m[i], bn_p_limb(k - i));
       acc += BN_HALF;
       r.v[k - BN_NL] = (int32_t)((uint32_t)acc & BN_MASK) - BN_HALF;
       acc >>= BN_LB;

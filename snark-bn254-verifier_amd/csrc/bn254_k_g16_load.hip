@@ -16,6 +16,9 @@
 #include "bn254_sha256.h"
 
 namespace bn254 {
+// Compiled twice (Makefile): the first object holds everything but the body of k_g16_decompress; the second (-DBN_PLAIN_HALF -DBN_NO_CARRY_RIDE) holds only that kernel,
+// which keeps the reassociated carry chains: with the carry ride it spills more (profiles/carry_chain_resources.txt).
+#ifndef BN_PLAIN_HALF
 
 // ---- compaction (bn254_g16_plan.h::g16_compacts): classify, then count -> scan -> write ------------------------------------------------------------------------------
 // k_g16_classify, one proof per lane: the loader checks whose outcome is FINAL -- the range and curve checks of A and B, through the helpers and in the order of
@@ -361,7 +364,10 @@ __global__ void k_scatter_status(uint8_t* __restrict__ status, const uint8_t* __
 // host) -> the 256-byte raw record at raw + 256 i, and pre[i] = 1 if it did not decompress (its raw record is then all ones, which the loader answers with
 // NOT_MEMBER; k_g16_status_merge turns the final status into MALFORMED).  About 1 900 field products per lane (two Fp roots, one Fp2 root): compute-bound,
 // so the 128-byte record is simply loaded per lane -- four 16-byte loads when the records are 16-byte aligned (stride 128), bytes otherwise.
-__global__ void __launch_bounds__(256, 2) k_g16_decompress(const uint8_t* __restrict__ src, size_t stride, uint32_t n, uint8_t* __restrict__ raw, uint8_t* __restrict__ pre) {
+#endif
+__global__ void __launch_bounds__(256, 2) k_g16_decompress(const uint8_t* __restrict__ src, size_t stride, uint32_t n, uint8_t* __restrict__ raw, uint8_t* __restrict__ pre)
+#ifdef BN_PLAIN_HALF
+{
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   if (i >= n) return;
   const uint8_t* p = src + (size_t)i * stride;
@@ -379,6 +385,10 @@ __global__ void __launch_bounds__(256, 2) k_g16_decompress(const uint8_t* __rest
   for (int k = 0; k < 16; k++) q[k] = make_uint4(out[4 * k], out[4 * k + 1], out[4 * k + 2], out[4 * k + 3]);
   pre[i] = ok ? 0 : 1;
 }
+#else
+;
+#endif
+#ifndef BN_PLAIN_HALF
 // after the raw pipeline over the decompressed records: a record that did not decompress is MALFORMED, whatever the loader said about its all-ones stand-in
 __global__ void __launch_bounds__(256) k_g16_status_merge(uint8_t* __restrict__ status, const uint8_t* __restrict__ pre, uint32_t n) {
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
@@ -411,7 +421,9 @@ __global__ void __launch_bounds__(256) k_sp1_public_inputs(const uint8_t* __rest
   pre[i] = ok ? 0 : 1;
 }
 
+#endif
 }  // namespace bn254
+#ifndef BN_PLAIN_HALF
 
 // ---- launch wrappers (C++ linkage, declared in bn254_kernels.h) -----------------------------------------------------------
 using namespace bn254;
@@ -437,3 +449,4 @@ hipError_t bn254_launch_sp1_public_inputs(const uint8_t* vkh, size_t vkh_stride,
   if (n) hipLaunchKernelGGL(k_sp1_public_inputs, dim3(grid_for(n)), dim3(256), 0, s, vkh, vkh_stride, pv, pv_bytes, pv_base, off, n, rows, pre);
   return hipGetLastError();
 }
+#endif

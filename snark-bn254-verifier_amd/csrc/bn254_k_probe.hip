@@ -5,6 +5,9 @@
 #include "bn254_launch_ops.h"
 
 namespace bn254 {
+// Compiled twice (Makefile): the first object holds everything but the body of k_dbg_g2_subgroup; the second (-DBN_PLAIN_HALF -DBN_NO_CARRY_RIDE) holds only that kernel,
+// which keeps the reassociated carry chains: with the carry ride it spills more (profiles/carry_chain_resources.txt).
+#ifndef BN_PLAIN_HALF
 
 // =====================================================================================================================
 // the issue rate of the instruction every field product is made of, measured on THIS device: sixteen independent v_mad_u64_u32 chains per lane, two
@@ -28,6 +31,7 @@ __global__ void __launch_bounds__(256) k_valu_peak(uint32_t* out, uint32_t seed,
   out[tid] = x;
 }
 
+#endif
 // =====================================================================================================================
 // probes for the GPU parity tests
 // =====================================================================================================================
@@ -41,6 +45,7 @@ __device__ __forceinline__ void probe_st_fp(uint8_t* p, const Fp& a) {
   fp_to_words(w, a);
   words_to_be(p, w);
 }
+#ifndef BN_PLAIN_HALF
 __global__ void __launch_bounds__(256, 2) k_dbg_fp_mul(const uint8_t* a, const uint8_t* b, uint8_t* o, size_t n) {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
@@ -89,20 +94,29 @@ __global__ void __launch_bounds__(256, 2) k_dbg_store_raw(int32_t* ws, uint32_t 
   int32_t* p = dst + 12 * BN_NL * (size_t)i;
   for (int t = 0; t < 12; t++) { const Fp a = w.ld(e + 2 * korder[t >> 1] + (t & 1)); for (int l = 0; l < BN_NL; l++) p[t * BN_NL + l] = a.v[l]; }
 }
-__global__ void __launch_bounds__(256, 2) k_dbg_g2_subgroup(const uint8_t* g2, uint8_t* o, size_t n) {
+#endif
+__global__ void __launch_bounds__(256, 2) k_dbg_g2_subgroup(const uint8_t* g2, uint8_t* o, size_t n)
+#ifdef BN_PLAIN_HALF
+{
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   G2Aff q; q.x.c1 = probe_ld_fp(g2 + 128 * i); q.x.c0 = probe_ld_fp(g2 + 128 * i + 32);
   q.y.c1 = probe_ld_fp(g2 + 128 * i + 64); q.y.c0 = probe_ld_fp(g2 + 128 * i + 96);
   o[i] = (g2_on_curve(q) && g2_in_subgroup(q)) ? 1 : 0;
 }
+#else
+;
+#endif
+#ifndef BN_PLAIN_HALF
 __global__ void __launch_bounds__(256, 2) k_dbg_g2_ate(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, uint8_t* o) {
   VM_KERNEL_PROLOGUE();
   bool ok = vm_g2_ate_check(w, VE_T, VE_B);
   if (i < n) o[i] = ok ? 1 : 0;
 }
 
+#endif
 }  // namespace bn254
+#ifndef BN_PLAIN_HALF
 
 using namespace bn254;
 // lane-level multiply-adds per second of the current device: the best launch of k_valu_peak at four wavefronts per SIMD, each about 2 ms long (a
@@ -237,3 +251,4 @@ hipError_t bn254_launch_dbg_g2_subgroup(const uint8_t* g2, uint8_t* o, size_t n,
   hipLaunchKernelGGL(k_dbg_g2_subgroup, dim3(grid_for(n)), dim3(256), 0, s, g2, o, n);
   return hipGetLastError();
 }
+#endif

@@ -28,6 +28,9 @@
 static_assert(G16_MILLER_STEPS == BN_ATE_STEPS, "bn254_g16_plan.h counts the Miller steps of bn254_constants.h");
 
 namespace bn254 {
+// Compiled twice (Makefile): the first object holds everything but the body of k_f12_mul_verdict; the second (-DBN_PLAIN_HALF -DBN_NO_CARRY_RIDE) holds only that kernel,
+// which keeps the reassociated carry chains: with the carry ride it spills more (profiles/carry_chain_resources.txt).
+#ifndef BN_PLAIN_HALF
 
 __global__ void __launch_bounds__(256, 2) k_vm_init(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status) {  // f = 1, T = B
   VM_KERNEL_PROLOGUE();
@@ -74,8 +77,11 @@ __global__ void __launch_bounds__(256, 2) k_f12_mul(int32_t* ws, uint32_t n, con
 // slot_proof != nullptr (a launch that compacts): status holds the SLOTS' bytes, and every slot that holds a proof hands its final byte to out_status[slot_proof[slot]],
 // the caller's buffer in proof order -- the verdict, or what the tail of k_miller_run made of the slot (B outside G2, a deferred error of C, the input count; never 0,
 // which is what the slots past the list hold) -- also in a wavefront none of whose proofs is still pending (as k_f12_mul_verdict_keys does for a batch over many keys)
+#endif
 __global__ void __launch_bounds__(256, 2) k_f12_mul_verdict(int32_t* ws, uint32_t n, uint8_t* status, int d, int a, int b, const int32_t* __restrict__ target, int reject_code,
-                                                            const uint32_t* __restrict__ slot_proof, uint8_t* __restrict__ out_status) {
+                                                            const uint32_t* __restrict__ slot_proof, uint8_t* __restrict__ out_status)
+#ifdef BN_PLAIN_HALF
+{
   __shared__ int32_t park_lds[72 * 256];
   const uint32_t i = blockIdx.x * 256u + threadIdx.x;
   const uint8_t st = status[i < n ? i : n - 1];
@@ -89,6 +95,10 @@ __global__ void __launch_bounds__(256, 2) k_f12_mul_verdict(int32_t* ws, uint32_
   }
   if (slot_proof && i < n && st != 0) out_status[slot_proof[i]] = out;
 }
+#else
+;
+#endif
+#ifndef BN_PLAIN_HALF
 __global__ void __launch_bounds__(256, 2) k_f12_copy(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a) { VM_KERNEL_PROLOGUE(); vm_f12_copy(w, d, a); }
 __global__ void __launch_bounds__(256, 2) k_f12_cyclo_sqr(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a) { VM_KERNEL_PROLOGUE(); vm_f12_cyclo_sqr(w, d, a); }
 __global__ void __launch_bounds__(256, 2) k_f12_cyclo_sqr_n(int32_t* ws, uint32_t n, const uint8_t* __restrict__ status, int d, int a, int count) {
@@ -114,7 +124,9 @@ k_g16_subgroup(uint32_t n, int32_t* ws, uint8_t* __restrict__ status, int inputs
   if (i < n && (st & BN254_ST_PENDING)) status[i] = g16_subgroup_status(st, ok, inputs_match_key);
 }
 
+#endif
 }  // namespace bn254
+#ifndef BN_PLAIN_HALF
 
 // ---- launch wrappers (C++ linkage, declared in bn254_kernels.h) -----------------------------------------------------------
 using namespace bn254;
@@ -334,3 +346,4 @@ hipError_t bn254_launch_pairing2_fixed_groups_keys(int32_t* grp_ws, uint8_t* grp
   if (groups > bn254_coop_max_proofs_fixed()) return hipErrorInvalidValue;
   return bn254_coop12_miller_fixed_keys(grp_ws, grp_status, groups, granule_key, 0, desc, n_keys, target_one, reject_code, s);
 }
+#endif

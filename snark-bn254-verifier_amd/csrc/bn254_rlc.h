@@ -208,11 +208,11 @@ BN_HD void vm_miller_var_multi(W& w, int kind, int G, uint32_t deadmask) {
     k3.c0 = w.ld0(VE_F + 6); k3.c1 = w.ld0(VE_F + 7); k4.c0 = w.ld0(VE_F + 8); k4.c1 = w.ld0(VE_F + 9); k5.c0 = w.ld0(VE_F + 10); k5.c1 = w.ld0(VE_F + 11);
     if constexpr (DO_SQR) {
       Fp2 x3 = fp2_mul_xi(k3), x4 = fp2_mul_xi(k4), x5 = fp2_mul_xi(k5);
-      w.park(0, fp2_dotp(pp(k0, k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
+      w.park(0, fp2_dotp(psq(k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
       w.park(1, fp2_dotp(pp2(k0, k1), pp2(k2, x5), pp2(k3, x4)));
-      w.park(2, fp2_dotp(pp2(k0, k2), pp(k1, k1), pp2(k3, x5), pp(k4, x4)));
+      w.park(2, fp2_dotp(pp2(k0, k2), psq(k1), pp2(k3, x5), pp(k4, x4)));
       w.park(3, fp2_dotp(pp2(k0, k3), pp2(k1, k2), pp2(k4, x5)));
-      f4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), pp(k2, k2), pp(k5, x5));
+      f4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), psq(k2), pp(k5, x5));
       f5 = fp2_dotp(pp2(k0, k5), pp2(k1, k4), pp2(k2, k3));
     } else {
       w.park(0, k0); w.park(1, k1); w.park(2, k2); w.park(3, k3); f4 = k4; f5 = k5;
@@ -266,11 +266,11 @@ BN_HD void vm_miller_step_fixed3(W& w, int e, const FixedLine& l0, int e_p0, boo
     Fp2 k0 = vld2(w, e), k1 = vld2(w, e + 2), k2 = vld2(w, e + 4), k3 = vld2(w, e + 6), k4 = vld2(w, e + 8), k5 = vld2(w, e + 10);
     if constexpr (DO_SQR) {
       Fp2 x3 = fp2_mul_xi(k3), x4 = fp2_mul_xi(k4), x5 = fp2_mul_xi(k5);
-      w.park(0, fp2_dotp(pp(k0, k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
+      w.park(0, fp2_dotp(psq(k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
       w.park(1, fp2_dotp(pp2(k0, k1), pp2(k2, x5), pp2(k3, x4)));
-      w.park(2, fp2_dotp(pp2(k0, k2), pp(k1, k1), pp2(k3, x5), pp(k4, x4)));
+      w.park(2, fp2_dotp(pp2(k0, k2), psq(k1), pp2(k3, x5), pp(k4, x4)));
       w.park(3, fp2_dotp(pp2(k0, k3), pp2(k1, k2), pp2(k4, x5)));
-      f4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), pp(k2, k2), pp(k5, x5));
+      f4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), psq(k2), pp(k5, x5));
       f5 = fp2_dotp(pp2(k0, k5), pp2(k1, k4), pp2(k2, k3));
     } else {
       w.park(0, k0); w.park(1, k1); w.park(2, k2); w.park(3, k3); f4 = k4; f5 = k5;

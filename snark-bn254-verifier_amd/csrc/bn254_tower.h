@@ -45,13 +45,27 @@ BN_HD P2<1> pp(const Fp2& x, const Fp2& y) { return P2<1>{x, y}; }
 BN_HD P2<-1> pm(const Fp2& x, const Fp2& y) { return P2<-1>{x, y}; }
 BN_HD P2<2> pp2(const Fp2& x, const Fp2& y) { return P2<2>{x, y}; }
 BN_HD P2<-2> pm2(const Fp2& x, const Fp2& y) { return P2<-2>{x, y}; }
-template <int... W>
-BN_HD Fp2 fp2_dotp(const P2<W>&... t) {
+// x^2 as a term of the sum: re = x0^2 - x1^2 with the mirrored digit products once (DotSq), im = 2 x0 x1 once with weight 2
+struct P2Sq {
+  const Fp2& x;
+};
+BN_HD P2Sq psq(const Fp2& x) { return P2Sq{x}; }
+template <int W> BN_HD DotTerm<W> p2_re0(const P2<W>& t) { return dterm<W>(t.x.c0, t.y.c0); }
+template <int W> BN_HD DotTerm<-W> p2_re1(const P2<W>& t) { return dterm<-W>(t.x.c1, t.y.c1); }
+template <bool RIDE, int W> BN_HD DotTerm<W> p2_im0(const P2<W>& t) { return dterm<W>(t.x.c0, t.y.c1); }
+template <bool RIDE, int W> BN_HD DotTerm<W> p2_im1(const P2<W>& t) { return dterm<W>(t.x.c1, t.y.c0); }
+BN_HD DotSq<1> p2_re0(const P2Sq& t) { return dsq<1>(t.x.c0); }
+BN_HD DotSq<-1> p2_re1(const P2Sq& t) { return dsq<-1>(t.x.c1); }
+template <bool RIDE> BN_HD auto p2_im0(const P2Sq& t) { if constexpr (RIDE) return dterm<2>(t.x.c0, t.x.c1); else return dterm<1>(t.x.c0, t.x.c1); }
+template <bool RIDE> BN_HD auto p2_im1(const P2Sq& t) { if constexpr (RIDE) return DotNone{}; else return dterm<1>(t.x.c1, t.x.c0); }
+template <bool RIDE, class... T>
+BN_HD Fp2 fp2_dotp_r(const T&... t) {
   Fp2 r;
-  r.c0 = fp_dot(dterm<W>(t.x.c0, t.y.c0)..., dterm<-W>(t.x.c1, t.y.c1)...);
-  r.c1 = fp_dot(dterm<W>(t.x.c0, t.y.c1)..., dterm<W>(t.x.c1, t.y.c0)...);
+  r.c0 = fp_dot_r<RIDE>(p2_re0(t)..., p2_re1(t)...);
+  r.c1 = fp_dot_r<RIDE>(p2_im0<RIDE>(t)..., p2_im1<RIDE>(t)...);
   return r;
 }
+template <class... T> BN_HD Fp2 fp2_dotp(const T&... t) { return fp2_dotp_r<BN_RIDE_DEFAULT>(t...); }
 
 // ---- Karatsuba form of the same sum: re and im of sum_t W_t x_t y_t retired TOGETHER, column by column ------------------------
 // Three 9x9 digit products per Fp2 product instead of four.  Per column and weight class |W| in {1, 2} two partial sums
@@ -73,7 +87,7 @@ struct KProd {
     for (int i = LO; i <= HI; i++) {
       c.a[AW - 1][0] += bn_dmul(x0.v[i], y0.v[K - i]);
       c.a[AW - 1][1] += bn_dmul(nx1.v[i], y1.v[K - i]);
-      c.im += bn_dmul(sxw.v[i], sy.v[K - i]);
+      if (K > 0) bn_ride(c.im, sxw.v[i], sy.v[K - i]); else c.im += bn_dmul(sxw.v[i], sy.v[K - i]);   // im holds the carry (column 0: a known 0)
     }
   }
 #if BN_TRACKING
@@ -91,8 +105,8 @@ struct KDirect {  // re += u_re * v_re, im += u_im * v_im (plain products)
     BN_KCOL_RANGE;
 #pragma unroll
     for (int i = LO; i <= HI; i++) {
-      c.re += bn_dmul(ure.v[i], vre.v[K - i]);
-      c.im += bn_dmul(uim.v[i], vim.v[K - i]);
+      if (K > 0) { bn_ride(c.re, ure.v[i], vre.v[K - i]); bn_ride(c.im, uim.v[i], vim.v[K - i]); }
+      else { c.re += bn_dmul(ure.v[i], vre.v[K - i]); c.im += bn_dmul(uim.v[i], vim.v[K - i]); }
     }
   }
 #if BN_TRACKING
@@ -129,18 +143,18 @@ BN_HD void dotk_step(int64_t& cre, int64_t& cim, int32_t (&mre)[BN_NL], int32_t 
   (t.template col<K>(c), ...);
   if constexpr (K < BN_NL) {
 #pragma unroll
-    for (int i = 0; i < K; i++) { c.re += bn_dmul(mre[i], bn_p_limb(K - i)); c.im += bn_dmul(mim[i], bn_p_limb(K - i)); }
+    for (int i = 0; i < K; i++) { bn_ride(c.re, mre[i], bn_p_limb(K - i)); bn_ride(c.im, mim[i], bn_p_limb(K - i)); }
   } else {
 #pragma unroll
-    for (int i = K - (BN_NL - 1); i < BN_NL; i++) { c.re += bn_dmul(mre[i], bn_p_limb(K - i)); c.im += bn_dmul(mim[i], bn_p_limb(K - i)); }
+    for (int i = K - (BN_NL - 1); i < BN_NL; i++) { bn_ride(c.re, mre[i], bn_p_limb(K - i)); bn_ride(c.im, mim[i], bn_p_limb(K - i)); }
   }
   if (has1) { c.re += c.a[0][0] + c.a[0][1]; c.im += c.a[0][1] - c.a[0][0]; }
   if (has2) { c.re += (c.a[1][0] + c.a[1][1]) << 1; c.im += (c.a[1][1] - c.a[1][0]) << 1; }
   if constexpr (K < BN_NL) {
     mre[K] = bn_sext29((uint32_t)c.re * BN_PINV);
     mim[K] = bn_sext29((uint32_t)c.im * BN_PINV);
-    c.re += bn_dmul(mre[K], bn_p_limb(0));
-    c.im += bn_dmul(mim[K], bn_p_limb(0));
+    bn_ride(c.re, mre[K], bn_p_limb(0));
+    bn_ride(c.im, mim[K], bn_p_limb(0));
     cre = (int64_t)c.re >> BN_LB;  // exact: the low 29 bits are zero
     cim = (int64_t)c.im >> BN_LB;
   } else {
@@ -184,10 +198,11 @@ BN_HD Fp2 fp2_sqr(const Fp2& a) {
 }
 BN_HD Fp2 fp2_mul_fp(const Fp2& a, const Fp& f) { Fp2 r; r.c0 = fp_mul(a.c0, f); r.c1 = fp_mul(a.c1, f); return r; }
 // (a0 + a1 i)(9 + i) = (9 a0 - a1) + (a0 + 9 a1) i, reduced in the same pass
+template <bool RIDE = BN_RIDE_DEFAULT>
 BN_HD Fp2 fp2_mul_xi(const Fp2& a) {
   Fp2 r;
-  r.c0 = fp_lincomb_reduce(9, a.c0, -1, a.c1);
-  r.c1 = fp_lincomb_reduce(1, a.c0, 9, a.c1);
+  r.c0 = fp_lincomb_reduce<RIDE>(9, a.c0, -1, a.c1);
+  r.c1 = fp_lincomb_reduce<RIDE>(1, a.c0, 9, a.c1);
   return r;
 }
 BN_HD Fp2 fp2_mul_small(const Fp2& a, int32_t k) {  // k * a reduced
@@ -196,14 +211,15 @@ BN_HD Fp2 fp2_mul_small(const Fp2& a, int32_t k) {  // k * a reduced
   r.c1 = fp_lincomb_reduce(k, a.c1, 0, a.c1);
   return r;
 }
+template <bool RIDE = BN_RIDE_DEFAULT>
 BN_HD Fp2 fp2_lincomb_reduce(int32_t k1, const Fp2& a, int32_t k2, const Fp2& b) {  // k1 a + k2 b, reduced
   Fp2 r;
-  r.c0 = fp_lincomb_reduce(k1, a.c0, k2, b.c0);
-  r.c1 = fp_lincomb_reduce(k1, a.c1, k2, b.c1);
+  r.c0 = fp_lincomb_reduce<RIDE>(k1, a.c0, k2, b.c0);
+  r.c1 = fp_lincomb_reduce<RIDE>(k1, a.c1, k2, b.c1);
   return r;
 }
 BN_HD Fp2 fp2_inv(const Fp2& a) {  // 0 -> 0
-  Fp n = fp_dot(dplus(a.c0, a.c0), dplus(a.c1, a.c1));
+  Fp n = fp_dot(dsq<1>(a.c0), dsq<1>(a.c1));
   Fp ni = fp_inv(n);
   Fp2 r;
   r.c0 = fp_mul(a.c0, ni);
@@ -252,9 +268,9 @@ BN_HD Fp6 fp6_mul_plain(const Fp6& x, const Fp6& y) {
 BN_HD Fp6 fp6_sqr(const Fp6& x) {
   Fp2 X2 = fp2_mul_xi(x.c2);
   Fp6 r;
-  r.c0 = fp2_dotp(pp(x.c0, x.c0), pp2(x.c1, X2));
+  r.c0 = fp2_dotp(psq(x.c0), pp2(x.c1, X2));
   r.c1 = fp2_dotp(pp2(x.c0, x.c1), pp(x.c2, X2));
-  r.c2 = fp2_dotp(pp2(x.c0, x.c2), pp(x.c1, x.c1));
+  r.c2 = fp2_dotp(pp2(x.c0, x.c2), psq(x.c1));
   return r;
 }
 BN_HD Fp6 fp6_mul_fp2(const Fp6& a, const Fp2& b) { Fp6 r; r.c0 = fp2_mul(a.c0, b); r.c1 = fp2_mul(a.c1, b); r.c2 = fp2_mul(a.c2, b); return r; }
@@ -262,9 +278,9 @@ BN_HD_NOINLINE Fp6 fp6_mul_nl(const Fp6& a, const Fp6& b) { return fp6_mul(a, b)
 BN_HD Fp6 fp6_inv(const Fp6& a) {
   // A = a0^2 - xi a1 a2, B = xi a2^2 - a0 a1, C = a1^2 - a0 a2, F = a0 A + xi (a2 B + a1 C); 1/a = (A, B, C)/F
   Fp2 X1 = fp2_mul_xi(a.c1), X2 = fp2_mul_xi(a.c2);
-  Fp2 A = fp2_dotp(pp(a.c0, a.c0), pm(X1, a.c2));
+  Fp2 A = fp2_dotp(psq(a.c0), pm(X1, a.c2));
   Fp2 B = fp2_dotp(pp(X2, a.c2), pm(a.c0, a.c1));
-  Fp2 C = fp2_dotp(pp(a.c1, a.c1), pm(a.c0, a.c2));
+  Fp2 C = fp2_dotp(psq(a.c1), pm(a.c0, a.c2));
   Fp2 F = fp2_dotp(pp(a.c0, A), pp(X2, B), pp(X1, C));
   Fp2 Fi = fp2_inv(F);
   Fp6 r;
@@ -304,11 +320,11 @@ BN_HD Fp12 fp12_mul(const Fp12& a, const Fp12& b) {
 BN_HD Fp12 fp12_sqr(const Fp12& f) {
   Fp2 x3 = fp2_mul_xi(K3(f)), x4 = fp2_mul_xi(K4(f)), x5 = fp2_mul_xi(K5(f));
   Fp12 r;
-  K0(r) = fp2_dotp(pp(K0(f), K0(f)), pp2(K1(f), x5), pp2(K2(f), x4), pp(K3(f), x3));
+  K0(r) = fp2_dotp(psq(K0(f)), pp2(K1(f), x5), pp2(K2(f), x4), pp(K3(f), x3));
   K1(r) = fp2_dotp(pp2(K0(f), K1(f)), pp2(K2(f), x5), pp2(K3(f), x4));
-  K2(r) = fp2_dotp(pp2(K0(f), K2(f)), pp(K1(f), K1(f)), pp2(K3(f), x5), pp(K4(f), x4));
+  K2(r) = fp2_dotp(pp2(K0(f), K2(f)), psq(K1(f)), pp2(K3(f), x5), pp(K4(f), x4));
   K3(r) = fp2_dotp(pp2(K0(f), K3(f)), pp2(K1(f), K2(f)), pp2(K4(f), x5));
-  K4(r) = fp2_dotp(pp2(K0(f), K4(f)), pp2(K1(f), K3(f)), pp(K2(f), K2(f)), pp(K5(f), x5));
+  K4(r) = fp2_dotp(pp2(K0(f), K4(f)), pp2(K1(f), K3(f)), psq(K2(f)), pp(K5(f), x5));
   K5(r) = fp2_dotp(pp2(K0(f), K5(f)), pp2(K1(f), K4(f)), pp2(K2(f), K3(f)));
   return r;
 }
@@ -381,11 +397,12 @@ BN_HD Fp12 fp12_frob(const Fp12& a, int j) {
 //   (a, b; sub, add) = (c0.c0, c1.c1; c0.c0, c1.c1), (c1.c0, c0.c2; c0.c1, c1.c2), (c0.c1, c1.c2; c0.c2, c1.c0)
 // each bracket is one sum of products; the linear part is folded in by a reducing linear combination.
 BN_HD void gs_pair(Fp2& za, Fp2& zb, const Fp2& a, const Fp2& b, const Fp2& sub, const Fp2& add, bool xi_on_cross) {
-  Fp2 xb = fp2_mul_xi(b);
-  Fp2 S = fp2_dotp(pp(xb, b), pp(a, a));
-  Fp2 T = xi_on_cross ? fp2_dotp(pp2(a, xb)) : fp2_dotp(pp2(a, b));
-  za = fp2_lincomb_reduce(3, S, -2, sub);
-  zb = fp2_lincomb_reduce(3, T, 2, add);
+  // the reassociated form throughout: with the carry pinned every Granger-Scott kernel spills more (k_f12_cyclo_sqr_n: 2 -> 37 VGPRs) and issues more
+  Fp2 xb = fp2_mul_xi<false>(b);
+  Fp2 S = fp2_dotp_r<false>(pp(xb, b), pp(a, a));
+  Fp2 T = xi_on_cross ? fp2_dotp_r<false>(pp2(a, xb)) : fp2_dotp_r<false>(pp2(a, b));
+  za = fp2_lincomb_reduce<false>(3, S, -2, sub);
+  zb = fp2_lincomb_reduce<false>(3, T, 2, add);
 }
 BN_HD Fp12 fp12_cyclo_sqr(const Fp12& x) {
   Fp12 z;

@@ -55,11 +55,11 @@ template <class W>
 BN_HD void vm_f12_sqr(W& w, int e) {
   Fp2 k0 = vld2(w, e), k1 = vld2(w, e + 2), k2 = vld2(w, e + 4), k3 = vld2(w, e + 6), k4 = vld2(w, e + 8), k5 = vld2(w, e + 10);
   Fp2 x3 = fp2_mul_xi(k3), x4 = fp2_mul_xi(k4), x5 = fp2_mul_xi(k5);
-  vst2(w, e, fp2_dotp(pp(k0, k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
+  vst2(w, e, fp2_dotp(psq(k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
   vst2(w, e + 2, fp2_dotp(pp2(k0, k1), pp2(k2, x5), pp2(k3, x4)));
-  vst2(w, e + 4, fp2_dotp(pp2(k0, k2), pp(k1, k1), pp2(k3, x5), pp(k4, x4)));
+  vst2(w, e + 4, fp2_dotp(pp2(k0, k2), psq(k1), pp2(k3, x5), pp(k4, x4)));
   vst2(w, e + 6, fp2_dotp(pp2(k0, k3), pp2(k1, k2), pp2(k4, x5)));
-  vst2(w, e + 8, fp2_dotp(pp2(k0, k4), pp2(k1, k3), pp(k2, k2), pp(k5, x5)));
+  vst2(w, e + 8, fp2_dotp(pp2(k0, k4), pp2(k1, k3), psq(k2), pp(k5, x5)));
   vst2(w, e + 10, fp2_dotp(pp2(k0, k5), pp2(k1, k4), pp2(k2, k3)));
 }
 // ---- f <- f * (yP + (m xP) w + c w^3): precomputed affine line of a fixed G2 argument; inf: the G1 point is the identity -----------
@@ -156,11 +156,11 @@ BN_HD void vm_miller_sqr_dbl_var(W& w, int e_t, int e, int e_px) {
   {
     Fp2 k0 = vld2(w, e), k1 = vld2(w, e + 2), k2 = vld2(w, e + 4), k3 = vld2(w, e + 6), k4 = vld2(w, e + 8), k5 = vld2(w, e + 10);
     Fp2 x3 = fp2_mul_xi(k3), x4 = fp2_mul_xi(k4), x5 = fp2_mul_xi(k5);
-    w.park(0, fp2_dotp(pp(k0, k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
+    w.park(0, fp2_dotp(psq(k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
     w.park(1, fp2_dotp(pp2(k0, k1), pp2(k2, x5), pp2(k3, x4)));
-    w.park(2, fp2_dotp(pp2(k0, k2), pp(k1, k1), pp2(k3, x5), pp(k4, x4)));
+    w.park(2, fp2_dotp(pp2(k0, k2), psq(k1), pp2(k3, x5), pp(k4, x4)));
     w.park(3, fp2_dotp(pp2(k0, k3), pp2(k1, k2), pp2(k4, x5)));
-    r4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), pp(k2, k2), pp(k5, x5));
+    r4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), psq(k2), pp(k5, x5));
     r5 = fp2_dotp(pp2(k0, k5), pp2(k1, k4), pp2(k2, k3));
   }
   G2Line l;
@@ -196,11 +196,11 @@ BN_HD void vm_miller_step(W& w, int kind, int e_t, int e_b, int e, int e_pa, con
   if constexpr (DO_SQR) {
     Fp2 k0 = vld2(w, e), k1 = vld2(w, e + 2), k2 = vld2(w, e + 4), k3 = vld2(w, e + 6), k4 = vld2(w, e + 8), k5 = vld2(w, e + 10);
     Fp2 x3 = fp2_mul_xi(k3), x4 = fp2_mul_xi(k4), x5 = fp2_mul_xi(k5);
-    w.park(0, fp2_dotp(pp(k0, k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
+    w.park(0, fp2_dotp(psq(k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
     w.park(1, fp2_dotp(pp2(k0, k1), pp2(k2, x5), pp2(k3, x4)));
-    w.park(2, fp2_dotp(pp2(k0, k2), pp(k1, k1), pp2(k3, x5), pp(k4, x4)));
+    w.park(2, fp2_dotp(pp2(k0, k2), psq(k1), pp2(k3, x5), pp(k4, x4)));
     w.park(3, fp2_dotp(pp2(k0, k3), pp2(k1, k2), pp2(k4, x5)));
-    f4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), pp(k2, k2), pp(k5, x5));
+    f4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), psq(k2), pp(k5, x5));
     f5 = fp2_dotp(pp2(k0, k5), pp2(k1, k4), pp2(k2, k3));
   }
   G2Line l;
@@ -277,11 +277,11 @@ template <class W> BN_HD void mf_store(W& w, int e, const Fp2& f4, const Fp2& f5
 template <class W> BN_HD void mf_sqr(W& w, Fp2& f4, Fp2& f5) {
   Fp2 k0 = w.unpark(0), k1 = w.unpark(1), k2 = w.unpark(2), k3 = w.unpark(3), k4 = f4, k5 = f5;
   Fp2 x3 = fp2_mul_xi(k3), x4 = fp2_mul_xi(k4), x5 = fp2_mul_xi(k5);
-  w.park(0, fp2_dotp(pp(k0, k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
+  w.park(0, fp2_dotp(psq(k0), pp2(k1, x5), pp2(k2, x4), pp(k3, x3)));
   w.park(1, fp2_dotp(pp2(k0, k1), pp2(k2, x5), pp2(k3, x4)));
-  w.park(2, fp2_dotp(pp2(k0, k2), pp(k1, k1), pp2(k3, x5), pp(k4, x4)));
+  w.park(2, fp2_dotp(pp2(k0, k2), psq(k1), pp2(k3, x5), pp(k4, x4)));
   w.park(3, fp2_dotp(pp2(k0, k3), pp2(k1, k2), pp2(k4, x5)));
-  Fp2 n4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), pp(k2, k2), pp(k5, x5));
+  Fp2 n4 = fp2_dotp(pp2(k0, k4), pp2(k1, k3), psq(k2), pp(k5, x5));
   f5 = fp2_dotp(pp2(k0, k5), pp2(k1, k4), pp2(k2, k3));
   f4 = n4;
 }
