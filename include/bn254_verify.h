@@ -552,6 +552,41 @@ void bn254_set_kzg_params(long rlc_min);
 int bn254_kzg_params(long out[1]);
 int bn254_kzg_state(uint64_t out[4]);   /* [0] launches that ran the joint check, [1] groups they checked, [2] groups that failed, [3] launches on the exact path */
 
+/* ---- Batch verification of KZG batch-opening proofs (k commitments at one point, one quotient) ----------------------------------------------------------------------
+ * The other half of the reference's KZG layer, plonk/kzg.rs::fold_proof (lines 46-126; gnark's BatchOpeningProof / BatchVerifySinglePoint), for proofs a caller holds:
+ * several committed columns opened at one point -- a PlonK variant of one's own, a lookup argument.  The fold runs on the device; the key is the KZG key of above.
+ *
+ *   A RECORD is BN254_KZG_FOLD_LEN(k, data_len) = 96 + 96 k + data_len bytes: the digests D_0 .. D_{k-1} (x | y, 64 bytes each), the quotient H (64), the point z (32),
+ *   the claimed values y_0 .. y_{k-1} (32 each), then data_len bytes of caller data that only the transcript reads.  Field values are 32-byte big-endian, an all-zero
+ *   point is the identity.  k = n_digests and data_len are the same for every record of a call: 1 <= k <= BN254_KZG_FOLD_MAX_DIGESTS, data_len <=
+ *   BN254_KZG_FOLD_MAX_DATA, stride >= the record length -- anything else is BN254_E_BAD_ARG before any device is touched, as are the argument errors of
+ *   bn254_kzg_verify_batch.  With k = 1 and data_len = 0 a record is an opening, and the status bytes are those of bn254_kzg_verify_batch.  With k = 1 the
+ *   fold does not depend on gamma (only gamma^0 = 1 enters it): the entries then run the opening's loader kernel, hash nothing and do not read the data bytes at all.
+ *   A device or pinned allocation that fails for lack of memory is BN254_E_NOMEM in these three entries.
+ *   BN254_KZG_FOLD_MAX_DIGESTS is the largest k for which both forms of the G1 walk plan whatever the batch size: the weighted form has k + 3 variable terms, a
+ *   small launch walks each in two rows, and a launch has 32 rows (csrc/bn254_msm.h; a static_assert in csrc/bn254_kzg.h and tests/test_kzg_fold_cpu.py hold it there).
+ *
+ *   status[i]:  gamma = SHA-256("gamma" | be32(z mod r) | D_0 .. D_{k-1} as they stand in the record | be32(y_0 mod r) .. be32(y_{k-1} mod r) | data) read big-endian
+ *   and reduced mod r (transcript.rs:68-107 with one challenge and no predecessor, kzg.rs:46-72);  D = sum gamma^i D_i,  y^ = sum gamma^i y_i;  BN254_ACCEPT iff
+ *   e(D - y^ g1 + z H, g2) e(-H, tau_g2) == 1, else BN254_REJECT.  Loader errors in the order of bn254_kzg_verify_batch: with BN254_FLAG_STRICT_SCALARS any of z, y_i
+ *   >= r is BN254_ERR_NOT_MEMBER first; then the points in record order, the digests before H, inside a point a coordinate >= p (NOT_MEMBER) before the curve equation
+ *   (NOT_ON_CURVE); a malformed key makes every record BN254_ERR_MALFORMED.
+ *
+ *   BN254_FLAG_RLC has the meaning it has for openings -- one odd 128-bit weight per record folded into all its scalars, the weighted points of the 64 records of a
+ *   wavefront summed, one two-pair check per group, the records of a failed group re-checked on their weighted points -- and is honoured under exactly the same
+ *   condition: from bn254_kzg_params() records per launch on (bn254_set_kzg_params; one knob for both kinds of record).  bn254_kzg_state counts these launches too.
+ *   Without the flag honoured bn254_kzg_verify_folded_batch_device only enqueues on hip_stream, and after bn254_kzg_fold_reserve(n', k', device) with k' = k and n' >=
+ *   min(n, the records of a pass) it allocates nothing.  A pass holds at most min(2^18, floor(2^18 * 4 / (k + 2)) rounded down to a multiple of 64) records.
+ *   Kernels: k_kzg_fold_load (the checks, the transcript hashed straight from the record, the running power of gamma, glv_decompose, k + 2 or k + 3 term records),
+ *   then everything bn254_kzg_verify_batch runs behind k_kzg_load.  Measured: profiles/r18_kzg_fold.txt (tools/bench_kzg.py --digests). */
+#define BN254_KZG_FOLD_MAX_DIGESTS 13
+#define BN254_KZG_FOLD_MAX_DATA 64
+#define BN254_KZG_FOLD_LEN(k, data_len) ((size_t)96 + (size_t)96 * (size_t)(k) + (size_t)(data_len))
+int bn254_kzg_verify_folded_batch(const uint8_t* key, const uint8_t* records, size_t stride, size_t n, size_t n_digests, size_t data_len, uint8_t* status, int device, unsigned flags);
+int bn254_kzg_verify_folded_batch_device(const void* d_key, const void* d_records, size_t stride, size_t n, size_t n_digests, size_t data_len, void* d_status, int device,
+                                         void* hip_stream, unsigned flags);
+int bn254_kzg_fold_reserve(size_t n, size_t n_digests, int device);
+
 /* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
  * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
  * before a device is first used the library runs the kernels IT SHIPS on THAT device on small built-in inputs and compares every output byte with a known answer.
@@ -585,7 +620,7 @@ int bn254_kzg_state(uint64_t out[4]);   /* [0] launches that ran the joint check
  * computed for them at run time); everything else is the host's compile of the same arithmetic source, computed once per process while the device runs.
  * NOT covered in this revision: the _keys variants of the kernels (batches over many keys), the RLC group kernels, the MSM row kernels and the wide-key MSM kernels,
  * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store, and k_pairing_load_shared, k_miller_run_mix of the entries with shared G2 points; its final exponentiation and
- * compare are checks 1 .. 3's kernels), the kernels of the KZG batch (k_kzg_load, k_kzg_ident, k_kzg_fetch),
+ * compare are checks 1 .. 3's kernels), the kernels of the KZG batch (k_kzg_load, k_kzg_fold_load, k_kzg_ident, k_kzg_fetch),
  * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
  *
  * Cost on one MI355X (profiles/selftest_cost.txt): one run is 40 ms of wall time in a warm process, all of it device time on the run's own stream (g16_lane 11.2 ms,
@@ -723,6 +758,13 @@ int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]);
  * mixed Miller run); a device ordinal the kernels, with the pairing launches in form 0 (the plan), 1 (lane) or 2 (cooperative). */
 int bn254_dbg_kzg_fold(const uint8_t* key, const uint8_t* openings, size_t stride, size_t n, const uint8_t* weights, unsigned flags, uint8_t* out_f, uint8_t* out_h,
                        uint8_t* out_inf, uint8_t* out_status, uint8_t* out_group, int device, int form);
+/* ... and of the batch-opening records (bn254_kzg_verify_folded_batch: same arguments and argument errors): everything bn254_dbg_kzg_fold writes, and out_fold, n x 64
+ * bytes: per record the 32-byte digest gamma is reduced from, then y^ = sum gamma^i y_i as 32 canonical big-endian bytes (all zero for a record the loader decided). */
+int bn254_dbg_kzg_fold_proof(const uint8_t* key, const uint8_t* records, size_t stride, size_t n, size_t n_digests, size_t data_len, const uint8_t* weights, unsigned flags,
+                             uint8_t* out_fold, uint8_t* out_f, uint8_t* out_h, uint8_t* out_inf, uint8_t* out_status, uint8_t* out_group, int device, int form);
+/* host only: BN254_OK iff the G1 walk of n records of n_digests digests plans (weighted: the BN254_FLAG_RLC shape) within lane_budget lanes (0: the library's) and joint
+ * rows of joint_g terms (negative: the library's choice for n); *rows (optional): the rows of the plan */
+int bn254_dbg_kzg_fold_plan(size_t n_digests, int weighted, size_t n, size_t lane_budget, int joint_g, int* rows);
 /* Value-level probes of the Fp12 operations (tests).  An Fp12 value travels in one of two formats, twelve Fp numbers in tower order (c0.c0.c0, c0.c0.c1, c0.c1.c0, ..):
  *   format 0  384 bytes, 32 big-endian canonical bytes per number;
  *   format 1  108 int32: per number the nine balanced 29-bit digits (digit 0 first) of a representative of its Montgomery form x 2^261 mod p, stored into
@@ -932,7 +974,7 @@ int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries, the bn254_kzg_* entries -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries, the bn254_kzg_* entries, bn254_kzg_verify_folded_batch / _device / bn254_kzg_fold_reserve and their probes -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

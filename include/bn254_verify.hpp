@@ -493,6 +493,20 @@ class KzgVerifier {
   }
   // makes `device` ready for batches of n openings: a later bn254_kzg_verify_batch_device of up to n openings without BN254_FLAG_RLC only enqueues
   static void reserve(size_t n, int device = 0) { detail::check(bn254_kzg_reserve(n, device)); }
+  // batch-opening proofs (bn254_kzg_verify_folded_batch): n records of n_digests digests and data_len bytes of caller data each, BN254_KZG_FOLD_LEN(n_digests,
+  // data_len) bytes, stride bytes apart (0: packed): D_0 .. D_{k-1} | H | z | y_0 .. y_{k-1} | data.  status[i] is BN254_ACCEPT where the digests folded with the
+  // transcript's gamma open to the folded values, BN254_REJECT where they do not, or the loader error; flags as verify_batch
+  std::vector<uint8_t> verify_folded_batch(const Bytes& records, size_t n, size_t n_digests, size_t data_len = 0, int device = 0, unsigned flags = 0, size_t stride = 0) const {
+    if (n_digests < 1 || n_digests > (size_t)BN254_KZG_FOLD_MAX_DIGESTS || data_len > (size_t)BN254_KZG_FOLD_MAX_DATA)
+      throw std::invalid_argument("KzgVerifier::verify_folded_batch: n_digests is 1 .. BN254_KZG_FOLD_MAX_DIGESTS, data_len at most BN254_KZG_FOLD_MAX_DATA");
+    const size_t len = BN254_KZG_FOLD_LEN(n_digests, data_len), s = stride ? stride : len;
+    if (n && (s < len || records.size() < (n - 1) * s + len)) throw std::invalid_argument("KzgVerifier::verify_folded_batch: the buffer is shorter than n records");
+    std::vector<uint8_t> status(n);
+    detail::check(bn254_kzg_verify_folded_batch(key_.data(), records.data(), s, n, n_digests, data_len, status.data(), device, flags));
+    return status;
+  }
+  // ... a later bn254_kzg_verify_folded_batch_device of up to n records of n_digests digests without BN254_FLAG_RLC only enqueues
+  static void reserve_folded(size_t n, size_t n_digests, int device = 0) { detail::check(bn254_kzg_fold_reserve(n, n_digests, device)); }
 
  private:
   Bytes key_;

@@ -376,6 +376,26 @@ pub fn kzg_verify_batch(key: &[u8], openings: &[u8], stride: usize, n: usize, de
 }
 /// Makes `device` ready for KZG batches of `n` openings (its self-test at first use, the workspace and the buffers of the G1 walk).
 pub fn kzg_reserve(n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_kzg_reserve(n, device as c_int) }) }
+/// The most digests a batch-opening record holds, and the most bytes of caller data (`kzg_verify_folded_batch`).
+pub const KZG_FOLD_MAX_DIGESTS: usize = sys::BN254_KZG_FOLD_MAX_DIGESTS as usize;
+pub const KZG_FOLD_MAX_DATA: usize = sys::BN254_KZG_FOLD_MAX_DATA as usize;
+/// Bytes of a batch-opening record: `D_0 .. D_{k-1}` (64 each), `H` (64), `z` (32), `y_0 .. y_{k-1}` (32 each), then `data_len` bytes of caller data.
+pub const fn kzg_fold_len(n_digests: usize, data_len: usize) -> usize { 96 + 96 * n_digests + data_len }
+/// Batch verification of `n` KZG batch-opening proofs (`bn254_kzg_verify_folded_batch`; the reference's `kzg::fold_proof`): `n_digests` commitments opened at one
+/// point with one quotient, folded with the challenge of the SHA-256 transcript over the point, the digests, the claimed values and the data.  `Accept` where the
+/// folded opening verifies, `Reject` where it does not, or the loader error; `flags` as `kzg_verify_batch`.
+pub fn kzg_verify_folded_batch(key: &[u8], records: &[u8], stride: usize, n: usize, n_digests: usize, data_len: usize, device: i32, flags: u32) -> Result<Vec<Status>, Error> {
+    let short = Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "kzg_verify_folded_batch: the key holds KZG_KEY_LEN bytes, n_digests is 1 ..= KZG_FOLD_MAX_DIGESTS, data_len at most KZG_FOLD_MAX_DATA, stride at least kzg_fold_len(n_digests, data_len) and the buffer holds n records of stride bytes".into() };
+    if key.len() < KZG_KEY_LEN || n_digests < 1 || n_digests > KZG_FOLD_MAX_DIGESTS || data_len > KZG_FOLD_MAX_DATA { return Err(short); }
+    let len = kzg_fold_len(n_digests, data_len);
+    if stride < len { return Err(short); }
+    if n > 0 && (n - 1).checked_mul(stride).and_then(|b| b.checked_add(len)).map_or(true, |b| records.len() < b) { return Err(short); }
+    let mut status = vec![0u8; n];
+    check(unsafe { sys::bn254_kzg_verify_folded_batch(key.as_ptr(), records.as_ptr(), stride, n, n_digests, data_len, status.as_mut_ptr(), device as c_int, flags as core::ffi::c_uint) })?;
+    Ok(status.into_iter().map(Status::from).collect())
+}
+/// Makes `device` ready for batches of `n` records of `n_digests` digests (`bn254_kzg_fold_reserve`).
+pub fn kzg_fold_reserve(n: usize, n_digests: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_kzg_fold_reserve(n, n_digests, device as c_int) }) }
 /// `FLAG_RLC` is honoured from `rlc_min` openings per launch on (`bn254_set_kzg_params`; never below 64; negative: unchanged).
 pub fn set_kzg_params(rlc_min: i64) { unsafe { sys::bn254_set_kzg_params(rlc_min as core::ffi::c_long) } }
 /// The knob as it is now (`bn254_kzg_params`).

@@ -18,4 +18,5 @@ from .binding import (  # noqa: F401
     g2_prepare, pairing_check_batch_shared, pairing_batch_shared, pairing_check_batch_shared_device, dbg_pairing_batch_shared, pairing_packed_len, G2_PREPARED_LEN,
     PAIRING_G1_LEN,
     kzg_key_prepare, kzg_verify_batch, kzg_verify_batch_device, kzg_reserve, set_kzg_params, kzg_params, kzg_state, dbg_kzg_fold, KZG_OPENING_LEN, KZG_KEY_LEN,
+    kzg_verify_folded_batch, kzg_verify_folded_batch_device, kzg_fold_reserve, dbg_kzg_fold_proof, dbg_kzg_fold_plan, kzg_fold_len, KZG_FOLD_MAX_DIGESTS, KZG_FOLD_MAX_DATA,
 )

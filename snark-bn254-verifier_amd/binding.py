@@ -1176,3 +1176,86 @@ def dbg_kzg_fold(key, openings, n=None, stride=None, weights=None, flags=0, devi
         g = bytes(grp)
         out["groups"] = [(g[131 * q:131 * q + 64], g[131 * q + 64:131 * q + 128], g[131 * q + 128:131 * q + 130], g[131 * q + 130]) for q in range(groups)]
     return out
+
+
+# ---- batch verification of KZG batch-opening proofs (bn254_kzg_verify_folded_batch, include/bn254_verify.h) ----
+KZG_FOLD_MAX_DIGESTS = 13
+KZG_FOLD_MAX_DATA = 64
+
+
+def kzg_fold_len(n_digests, data_len=0):
+    """BN254_KZG_FOLD_LEN: D_0 .. D_{k-1} (64 each) | H (64) | z (32) | y_0 .. y_{k-1} (32 each) | data"""
+    return 96 + 96 * n_digests + data_len
+
+
+def _kzg_fold_shape(key, records, n, stride, n_digests, data_len):
+    key, records = bytes(key), bytes(records)
+    rec = kzg_fold_len(n_digests, data_len)
+    if stride is None:
+        stride = rec
+    if n is None:
+        n = len(records) // stride if stride else 0
+    if len(key) < KZG_KEY_LEN:
+        raise Bn254Error("KZG batch: the key is shorter than KZG_KEY_LEN")
+    if n and 1 <= n_digests <= KZG_FOLD_MAX_DIGESTS and 0 <= data_len <= KZG_FOLD_MAX_DATA and stride >= rec and len(records) < (n - 1) * stride + rec:
+        raise Bn254Error("KZG batch: the buffer is shorter than n records")
+    return key, records, n, stride
+
+
+def kzg_verify_folded_batch(key, records, n_digests, data_len=0, n=None, stride=None, device=0, flags=0):
+    """n status bytes for batch-opening records of n_digests digests and data_len bytes of caller data each (kzg_fold_len bytes): gamma from the SHA-256 transcript over
+    the point, the digests, the claimed values and the data; ACCEPT where e(sum gamma^i D_i - (sum gamma^i y_i) g1 + z H, g2) e(-H, tau_g2) == 1, REJECT where it is
+    not, or the loader error.  flags as kzg_verify_batch  (bn254_kzg_verify_folded_batch)."""
+    fn = lib().bn254_kzg_verify_folded_batch
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_uint]
+    key, records, n, stride = _kzg_fold_shape(key, records, n, stride, n_digests, data_len)
+    status = (C.c_uint8 * max(n, 1))()
+    _check(fn(key, records, stride, n, n_digests, data_len, status, device, flags))
+    return bytes(status)[:n]
+
+
+def kzg_verify_folded_batch_device(d_key, d_records, n, n_digests, d_status, data_len=0, stride=None, device=0, stream=0, flags=0):
+    """bn254_kzg_verify_folded_batch_device on device pointers (ints; d_key 4-byte aligned): enqueues on `stream` and returns (with FLAG_RLC honoured it synchronises once)."""
+    fn = lib().bn254_kzg_verify_folded_batch_device
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+    _check(fn(d_key, d_records, kzg_fold_len(n_digests, data_len) if stride is None else stride, n, n_digests, data_len, d_status, device, stream, flags))
+
+
+def kzg_fold_reserve(n, n_digests, device=0):
+    """Makes `device` ready for batches of n records of n_digests digests: a later kzg_verify_folded_batch_device of up to n such records without FLAG_RLC only
+    enqueues  (bn254_kzg_fold_reserve)."""
+    fn = lib().bn254_kzg_fold_reserve
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.c_int]
+    _check(fn(n, n_digests, device))
+
+
+def dbg_kzg_fold_proof(key, records, n_digests, data_len=0, n=None, stride=None, weights=None, flags=0, device=-1, form=0, want_groups=False):
+    """bn254_dbg_kzg_fold_proof: what dbg_kzg_fold returns, and "gamma" (n x 32 bytes: the digest gamma is reduced from) and "yhat" (n x 32 bytes, canonical); both zero
+    for a record the loader decided.  device -1 is the host compile, no GPU needed."""
+    fn = lib().bn254_dbg_kzg_fold_proof
+    fn.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_char_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.c_void_p, C.c_int, C.c_int]
+    key, records, n, stride = _kzg_fold_shape(key, records, n, stride, n_digests, data_len)
+    wb = None if weights is None else b"".join(int(w).to_bytes(16, "big") for w in weights)
+    if wb is not None and len(wb) != 16 * n:
+        raise Bn254Error("dbg_kzg_fold_proof: one weight per record")
+    groups = (n + 63) // 64
+    fold = (C.c_uint8 * max(64 * n, 1))()
+    f = (C.c_uint8 * max(64 * n, 1))(); h = (C.c_uint8 * max(64 * n, 1))(); inf = (C.c_uint8 * max(2 * n, 1))(); status = (C.c_uint8 * max(n, 1))()
+    grp = (C.c_uint8 * max(131 * groups, 1))() if want_groups else None
+    _check(fn(key, records, stride, n, n_digests, data_len, wb, flags, fold, f, h, inf, status, grp, device, form))
+    fb = bytes(fold)
+    out = {"gamma": b"".join(fb[64 * i:64 * i + 32] for i in range(n)), "yhat": b"".join(fb[64 * i + 32:64 * i + 64] for i in range(n)),
+           "f": bytes(f)[:64 * n], "h": bytes(h)[:64 * n], "inf": bytes(inf)[:2 * n], "status": bytes(status)[:n], "groups": None}
+    if want_groups:
+        g = bytes(grp)
+        out["groups"] = [(g[131 * q:131 * q + 64], g[131 * q + 64:131 * q + 128], g[131 * q + 128:131 * q + 130], g[131 * q + 130]) for q in range(groups)]
+    return out
+
+
+def dbg_kzg_fold_plan(n_digests, weighted, n, lane_budget=0, joint_g=-1):
+    """rows of the G1 walk of n records of n_digests digests, or None when the shape does not plan  (bn254_dbg_kzg_fold_plan; host only)."""
+    fn = lib().bn254_dbg_kzg_fold_plan
+    fn.argtypes = [C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
+    rows = C.c_int(0)
+    return int(rows.value) if fn(n_digests, 1 if weighted else 0, n, lane_budget, joint_g, C.byref(rows)) == 0 else None

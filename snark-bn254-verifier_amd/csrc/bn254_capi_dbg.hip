@@ -2,6 +2,7 @@
 // VALU peak -- and the synthetic workload generator of the bench and the tests.
 #include "bn254_capi_internal.h"
 #include "bn254_capi_kzg.h"
+#include "bn254_kzg.h"
 #include <climits>
 
 extern "C" {
@@ -949,6 +950,34 @@ int bn254_dbg_kzg_fold(const uint8_t* key, const uint8_t* openings, size_t strid
   KzgProbeHost ph{out_f, out_h, out_inf, out_group};
   if (device < 0) return kzg_fold_on_host(key, openings, stride, n, weights, flags, weighted, ph, out_status);
   return kzg_host_call(key, openings, stride, n, out_status, device, flags, form, weights, weighted, &ph);
+}
+// ... and of the batch-opening records (bn254_kzg_verify_folded_batch): the same, and out_fold (n x 64 bytes): per record the digest gamma is reduced from and y^ = sum
+// gamma^i y_i, canonical (zero for a record the loader decided)
+int bn254_dbg_kzg_fold_proof(const uint8_t* key, const uint8_t* records, size_t stride, size_t n, size_t n_digests, size_t data_len, const uint8_t* weights, unsigned flags,
+                             uint8_t* out_fold, uint8_t* out_f, uint8_t* out_h, uint8_t* out_inf, uint8_t* out_status, uint8_t* out_group, int device, int form) {
+  KzgForm kf;
+  bool done;
+  int rc = kzg_fold_form(n_digests, data_len, &kf);
+  if (rc || (rc = kzg_check_args(key, records, stride, n, out_status, flags, true, &done, kf))) return rc;
+  const bool weighted = (flags & BN254_FLAG_RLC) != 0;
+  if ((n && (!out_fold || !out_f || !out_h || !out_inf)) || ((weights || out_group) && !weighted)) return set_err(BN254_E_BAD_ARG, "bad argument: weights and out_group need BN254_FLAG_RLC");
+  if (device < -1 || form < 0 || form > bn254::PAIRING_FORM_COOP || (form != bn254::PAIRING_FORM_PLAN && device < 0))
+    return set_err(BN254_E_BAD_ARG, "bad argument: form 0 runs anywhere, form 1 (lane) and 2 (cooperative) run on a device");
+  if (n > (size_t)G1P_MAX_ITEMS || (form == bn254::PAIRING_FORM_COOP && n > (size_t)COOP12_MAX_PROOFS)) return set_err(BN254_E_BAD_ARG, "bad argument: n is at most 65536 (30 720 in the cooperative form)");
+  if (done) return BN254_OK;
+  KzgProbeHost ph{out_f, out_h, out_inf, out_group, out_fold};
+  if (device < 0) return kzg_fold_on_host(key, records, stride, n, weights, flags, weighted, ph, out_status, kf);
+  return kzg_host_call(key, records, stride, n, out_status, device, flags, form, weights, weighted, &ph, kf);
+}
+// whether the G1 walk of n records of n_digests digests plans (both forms must, for every n: what BN254_KZG_FOLD_MAX_DIGESTS is held to); rows: the plan's rows or null
+int bn254_dbg_kzg_fold_plan(size_t n_digests, int weighted, size_t n, size_t lane_budget, int joint_g, int* rows) {
+  if (n_digests < 1 || n_digests > (size_t)MSM_MAX_FIXED || n == 0) return set_err(BN254_E_BAD_ARG, "bad argument");
+  const size_t n_pad = (n + 63) & ~(size_t)63;
+  MsmPlan plan;
+  if (!msm_plan_build(plan, bn254::kzg_fold_msm_shape((int)n_digests, weighted != 0), n_pad, lane_budget ? lane_budget : msm_lane_budget(), 0, joint_g >= 0 ? joint_g : plonk_joint_g(n_pad)))
+    return set_err(BN254_E_BAD_ARG, "shape cannot be planned");
+  if (rows) *rows = plan.n_rows;
+  return BN254_OK;
 }
 #endif
 

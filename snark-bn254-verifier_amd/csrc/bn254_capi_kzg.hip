@@ -16,6 +16,14 @@ static_assert(BN254_KZG_OPENING_LEN == KZG_OPENING_LEN, "an opening is six field
 static_assert(BN254_KZG_KEY_LEN == KZG_KEY_LEN && KZG_KEY_LEN == 16 + 2 * sizeof(bn254::Fp::v) + 2 * BN254_G2_PREPARED_LEN && sizeof(bn254::Fp::v) == 36,
               "BN254_KZG_KEY_LEN is the header of four dwords, the digits of g1's two Fp and two prepared G2 records");
 static_assert(KZG_KEY_REC0_DWORD * 4 % 8 == 0, "the records inside a key keep the key's alignment");
+static_assert(BN254_KZG_FOLD_MAX_DIGESTS == KZG_FOLD_MAX_DIGESTS && BN254_KZG_FOLD_MAX_DATA == KZG_FOLD_MAX_DATA && BN254_KZG_FOLD_LEN(1, 0) == BN254_KZG_OPENING_LEN &&
+              BN254_KZG_FOLD_LEN(KZG_FOLD_MAX_DIGESTS, KZG_FOLD_MAX_DATA) == KZG_FOLD_LEN(KZG_FOLD_MAX_DIGESTS, KZG_FOLD_MAX_DATA), "the header's limits and record length are the loader's");
+
+size_t KzgForm::rec_len() const { return k ? KZG_FOLD_LEN(k, data_len) : (size_t)KZG_OPENING_LEN; }
+int KzgForm::n_terms(bool weighted) const { return k ? KZG_FOLD_TERMS(k, weighted) : weighted ? KZG_TERMS_RLC : KZG_TERMS_EXACT; }
+int KzgForm::n_var(bool weighted) const { return k ? k + (weighted ? 3 : 1) : weighted ? 4 : 2; }
+size_t KzgForm::max_launch() const { return k ? bn254::kzg_fold_max_launch((size_t)k) : KZG_MAX_LAUNCH; }
+static MsmShape kzg_form_shape(const KzgForm& f, bool weighted) { return f.k ? bn254::kzg_fold_msm_shape(f.k, weighted) : bn254::kzg_msm_shape(weighted); }
 
 // the host entries stage a pass through pinned memory of at most this many bytes: the key, then the openings packed
 #define KZG_STAGE_BYTES ((size_t)48 << 20)
@@ -45,15 +53,16 @@ KzgDev* kzg_dev(int device) {      // never destroyed, map nodes never move (pb_
 inline size_t kzg_pad4(size_t n) { return (n + 3) & ~(size_t)3; }
 // caller holds d.mu.  The device ready (self-test at its first use), the pairing workspace and the walk's buffers grown to what launches of up to min(n, the
 // workspace's items, KZG_MAX_LAUNCH) openings need; *launch: that many.  weighted: the larger records, rows and scratch of the weighted form and the group buffers
-int kzg_ensure(PbDev& d, KzgDev& k, int device, size_t n, bool weighted, size_t* launch) {
-  int rc = pb_ensure(d, device, n < KZG_MAX_LAUNCH ? n : KZG_MAX_LAUNCH);
+int kzg_ensure(PbDev& d, KzgDev& k, int device, size_t n, bool weighted, size_t* launch, const KzgForm& form = KzgForm()) {
+  const size_t max_launch = form.max_launch();
+  int rc = pb_ensure(d, device, n < max_launch ? n : max_launch);
   if (rc) return rc;
-  size_t cap = d.ws_items() < KZG_MAX_LAUNCH ? d.ws_items() : KZG_MAX_LAUNCH;
+  size_t cap = d.ws_items() < max_launch ? d.ws_items() : max_launch;
   const size_t need = n < cap ? n : cap;
   *launch = need;
-  const int n_terms = weighted ? KZG_TERMS_RLC : KZG_TERMS_EXACT;
-  const MsmShape sh = bn254::kzg_msm_shape(weighted);
-  const size_t lanes = plonk_scratch_lanes(need, weighted ? 4 : 2), points = plonk_part_points(need, sh);
+  const int n_terms = form.n_terms(weighted);
+  const MsmShape sh = kzg_form_shape(form, weighted);
+  const size_t lanes = plonk_scratch_lanes(need, form.n_var(weighted)), points = plonk_part_points(need, sh);
   if ((rc = k.terms.ensure(need * (size_t)n_terms * MSM_TERM_DWORDS)) || (rc = k.flags.ensure(need * (size_t)n_terms)) || (rc = k.st.ensure(kzg_pad4(need)))) return rc;
   if (points > k.part_points) { k.part_points = 0; if ((rc = k.part.ensure(points * 27))) return rc; k.part_points = points; }
   if (lanes > k.glv_lanes) { k.glv_lanes = 0; if ((rc = k.glv.ensure(lanes * (size_t)(G1_GLV_TAB_BYTES_PER_LANE / 4)))) return rc; k.glv_lanes = lanes; }
@@ -79,18 +88,19 @@ int kzg_pairing(PbDev& d, int32_t* ws, uint8_t* st, size_t n, const int32_t* d_k
 // One launch of m openings, everything on s; caller holds d.mu and has run kzg_ensure.  d_status: m bytes of the caller's (any alignment).  weighted: the joint check
 // (d_weights: the probe's weights, else the ChaCha20 stream of wkey), which synchronises s once.  pr: the probe's device buffers or null
 int kzg_launch(PbDev& d, KzgDev& k, const int32_t* d_key, const uint8_t* d_open, size_t stride, size_t m, uint8_t* d_status, bool strict, bool weighted, const uint32_t* d_weights,
-               const bn254::ChaChaKey& wkey, int force, hipStream_t s, const KzgProbeDev* pr) {
+               const bn254::ChaChaKey& wkey, int force, hipStream_t s, const KzgProbeDev* pr, const KzgForm& form) {
   const size_t m_pad = (m + 63) & ~(size_t)63, groups = m_pad / 64;
-  const int n_terms = weighted ? KZG_TERMS_RLC : KZG_TERMS_EXACT;
+  const int n_terms = form.n_terms(weighted);
   MsmPlan plan;
-  if (!msm_plan_build(plan, bn254::kzg_msm_shape(weighted), m_pad, msm_lane_budget(), 0, plonk_joint_g(m_pad))) return set_err(BN254_E_HIP, "KZG: the G1 walk needs more rows than a launch has");
-  if (m > d.ws_items() || m > KZG_MAX_LAUNCH || bn254_g1_msm_scratch_lanes(plan, m) > k.glv_lanes || (size_t)plan.n_rows * m > k.part_points ||
+  if (!msm_plan_build(plan, kzg_form_shape(form, weighted), m_pad, msm_lane_budget(), 0, plonk_joint_g(m_pad))) return set_err(BN254_E_HIP, "KZG: the G1 walk needs more rows than a launch has");
+  if (m > d.ws_items() || m > form.max_launch() || bn254_g1_msm_scratch_lanes(plan, m) > k.glv_lanes || (size_t)plan.n_rows * m > k.part_points ||
       k.terms.cap() < m * (size_t)n_terms * MSM_TERM_DWORDS || k.flags.cap() < m * (size_t)n_terms || k.st.cap() < kzg_pad4(m) ||
       (weighted && (k.grp_ws.cap() < groups * (size_t)(G16_WS_BYTES_PER_PROOF / 4) || k.grp_st.cap() < kzg_pad4(groups))))
     return set_err(BN254_E_HIP, "KZG buffers smaller than the launch (internal sizing error)");
   bn254::KzgLoadArgs a;
   a.key = d_key; a.openings = d_open; a.stride = stride; a.n = m; a.ws = d.ws; a.status = k.st; a.terms = k.terms; a.flags = k.flags; a.strict = strict; a.weighted = weighted;
   a.weights = d_weights; a.wkey = wkey;
+  a.n_digests = form.k; a.data_len = form.data_len; a.dbg = pr ? pr->fold : nullptr;
   hipError_t e = bn254_launch_kzg_load(a, s);
   // no fixed-base term: the table pointer is never read (any device address)
   if (e == hipSuccess) e = bn254_launch_g1_msm_rows(plan, k.terms, k.flags, m, n_terms, k.part, k.glv, d_key, s);
@@ -139,7 +149,7 @@ int kzg_fresh_key(bn254::ChaChaKey& key) {
 // the launches of a call on device memory: caller holds d.mu; launches of weighted_from openings or more take the weighted form (SIZE_MAX: none; kzg_ensure was told).
 // The weights of launch j come from the call's key with the launch number in a nonce word
 int kzg_enqueue(PbDev& d, KzgDev& k, const int32_t* d_key, const uint8_t* d_open, size_t stride, size_t n, uint8_t* d_status, unsigned flags, size_t launch, int force, hipStream_t s,
-                size_t weighted_from, const uint32_t* d_weights = nullptr, const KzgProbeDev* pr = nullptr) {
+                size_t weighted_from, const uint32_t* d_weights = nullptr, const KzgProbeDev* pr = nullptr, const KzgForm& form = KzgForm()) {
   if (d.busy_valid) HIPCK(hipStreamWaitEvent(s, d.busy_ev, 0));
   bn254::ChaChaKey wkey;
   memset(&wkey, 0, sizeof wkey);
@@ -152,7 +162,7 @@ int kzg_enqueue(PbDev& d, KzgDev& k, const int32_t* d_key, const uint8_t* d_open
     if (weighted && !d_weights && !have_key) { if ((rc = kzg_fresh_key(wkey))) break; have_key = true; }
     bn254::ChaChaKey pk = wkey;
     pk.nonce[2] ^= pass;
-    rc = kzg_launch(d, k, d_key, d_open + off * stride, stride, m, d_status + off, (flags & BN254_FLAG_STRICT_SCALARS) != 0, weighted, d_weights ? d_weights + 4 * off : nullptr, pk, force, s, pr);
+    rc = kzg_launch(d, k, d_key, d_open + off * stride, stride, m, d_status + off, (flags & BN254_FLAG_STRICT_SCALARS) != 0, weighted, d_weights ? d_weights + 4 * off : nullptr, pk, force, s, pr, form);
   }
   // also after a failure: whatever was enqueued must be behind the event the next call waits for
   const hipError_t e = hipEventRecord(d.busy_ev, s);
@@ -175,10 +185,16 @@ bool kzg_key_host_ok(const uint8_t* key) {
 }  // namespace
 
 // BN254_E_BAD_ARG before any device is touched; *done: n == 0
-int kzg_check_args(const void* key, const void* openings, size_t stride, size_t n, const void* status, unsigned flags, bool host_key, bool* done) {
+int kzg_fold_form(size_t n_digests, size_t data_len, KzgForm* form) {
+  if (n_digests < 1 || n_digests > (size_t)KZG_FOLD_MAX_DIGESTS) return set_err(BN254_E_BAD_ARG, "bad argument: n_digests is 1 .. BN254_KZG_FOLD_MAX_DIGESTS");
+  if (data_len > (size_t)KZG_FOLD_MAX_DATA) return set_err(BN254_E_BAD_ARG, "bad argument: data_len above BN254_KZG_FOLD_MAX_DATA");
+  form->k = (int)n_digests; form->data_len = (int)data_len;
+  return BN254_OK;
+}
+int kzg_check_args(const void* key, const void* openings, size_t stride, size_t n, const void* status, unsigned flags, bool host_key, bool* done, const KzgForm& form) {
   *done = false;
   if (flags & ~(unsigned)(BN254_FLAG_STRICT_SCALARS | BN254_FLAG_RLC)) return set_err(BN254_E_BAD_ARG, "bad argument: flags other than BN254_FLAG_STRICT_SCALARS and BN254_FLAG_RLC");
-  if (stride < KZG_OPENING_LEN) return set_err(BN254_E_BAD_ARG, "bad argument: stride below 192");
+  if (stride < form.rec_len()) return set_err(BN254_E_BAD_ARG, form.k ? "bad argument: stride below BN254_KZG_FOLD_LEN(n_digests, data_len)" : "bad argument: stride below 192");
   if (n && (!key || !openings || !status)) return set_err(BN254_E_BAD_ARG, "bad argument");
   if (n && stride > SIZE_MAX / n) return set_err(BN254_E_BAD_ARG, "bad argument: n openings of stride bytes overflow the address space");
   if (n && host_key && !kzg_key_host_ok((const uint8_t*)key)) return set_err(BN254_E_BAD_ARG, "bad argument: a KZG key with a wrong magic word or layout version (bn254_kzg_key_prepare of this library writes it)");
@@ -189,7 +205,7 @@ int kzg_check_args(const void* key, const void* openings, size_t stride, size_t 
 
 // a host-buffer call: passes through the pinned staging of the pairing entries (the key in front of every pass's openings, packed); weights: the probe's (n x 16 bytes)
 int kzg_host_call(const uint8_t* key, const uint8_t* openings, size_t stride, size_t n, uint8_t* status, int device, unsigned flags, int force, const uint8_t* weights, bool force_weighted,
-                  KzgProbeHost* ph) {
+                  KzgProbeHost* ph, const KzgForm& form) {
   std::vector<uint8_t> unit;
   if (force_weighted && !weights) {      // the probe without weights: all 1, never the ChaCha20 stream
     unit.assign(16 * n, 0);
@@ -199,13 +215,14 @@ int kzg_host_call(const uint8_t* key, const uint8_t* openings, size_t stride, si
   PbDev* d = pb_dev(device);
   KzgDev* k = kzg_dev(device);
   std::lock_guard<std::mutex> lk(d->mu);
-  const size_t lead = KZG_KEY_LEN, wbytes = weights ? 16 : 0, rec = KZG_OPENING_LEN + wbytes;
+  // a staged record: padded to whole dwords (the weights behind the records and the loader's dword loads want it)
+  const size_t lead = KZG_KEY_LEN, wbytes = weights ? 16 : 0, olen = form.rec_len(), slen = (olen + 3) & ~(size_t)3, rec = slen + wbytes;
   size_t launch = 0;
   int rc;
   // ONE reading of the knob per call (bn254_set_kzg_params may run beside it): what kzg_ensure sizes for is what the launches take
   const size_t rlc_min = (size_t)g_kzg_rlc_min.load(std::memory_order_relaxed);
   const size_t weighted_from = force_weighted ? 0 : ((flags & BN254_FLAG_RLC) && n >= rlc_min) ? rlc_min : SIZE_MAX;
-  if ((rc = kzg_ensure(*d, *k, device, n, weighted_from != SIZE_MAX, &launch)) || (rc = d->stream.ensure())) return rc;
+  if ((rc = kzg_ensure(*d, *k, device, n, weighted_from != SIZE_MAX, &launch, form)) || (rc = d->stream.ensure())) return rc;
   size_t pass = (KZG_STAGE_BYTES - lead) / rec;
   if (pass > launch) pass = launch;
   if (ph && n > pass) return set_err(BN254_E_BAD_ARG, "bad argument: the probe takes one pass");
@@ -214,9 +231,10 @@ int kzg_host_call(const uint8_t* key, const uint8_t* openings, size_t stride, si
   KzgProbeDev pr; DevBuf<uint8_t> probe_buf;
   const size_t groups = (n + 63) / 64;
   if (ph) {
-    if ((rc = probe_buf.ensure(130 * n + 131 * groups))) return rc;
+    if ((rc = probe_buf.ensure(130 * n + 131 * groups + (ph->fold ? 64 * n : 0)))) return rc;
     uint8_t* b = probe_buf;
     pr.f = b; pr.h = b + 64 * n; pr.inf = b + 128 * n;
+    if (ph->fold) pr.fold = b + 130 * n + 131 * groups;
     b += 130 * n;
     pr.grp_f = pr.grp_h = pr.grp_inf = pr.grp_st = nullptr;
     if (ph->grp) { pr.grp_f = b; pr.grp_h = b + 64 * groups; pr.grp_inf = b + 128 * groups; pr.grp_st = b + 130 * groups; }
@@ -224,21 +242,22 @@ int kzg_host_call(const uint8_t* key, const uint8_t* openings, size_t stride, si
   auto one_pass = [&](size_t off, size_t m) -> int {
     memcpy(d->h_in, key, lead);
     uint8_t* o = d->h_in + lead;
-    if (stride == KZG_OPENING_LEN) parallel_copy(o, openings + off * stride, m * KZG_OPENING_LEN);
-    else for (size_t i = 0; i < m; i++) memcpy(o + i * KZG_OPENING_LEN, openings + (off + i) * stride, KZG_OPENING_LEN);
+    if (stride == olen && olen == slen) parallel_copy(o, openings + off * stride, m * slen);
+    else for (size_t i = 0; i < m; i++) memcpy(o + i * slen, openings + (off + i) * stride, olen);
     if (weights)      // as little-endian words behind the openings (a multiple of 4 bytes in)
-      for (size_t i = 0; i < m; i++) { uint32_t w4[4]; kzg_weight_words(w4, weights + 16 * (off + i)); memcpy(o + m * KZG_OPENING_LEN + 16 * i, w4, 16); }
+      for (size_t i = 0; i < m; i++) { uint32_t w4[4]; kzg_weight_words(w4, weights + 16 * (off + i)); memcpy(o + m * slen + 16 * i, w4, 16); }
     HIPCK(hipMemcpyAsync(d->d_in, d->h_in, lead + m * rec, hipMemcpyHostToDevice, s));
     const uint8_t* d_open = d->d_in + lead;
-    int r = kzg_enqueue(*d, *k, (const int32_t*)(uint8_t*)d->d_in, d_open, KZG_OPENING_LEN, m, k->d_out, flags, launch, force, s,
-                        weighted_from, weights ? (const uint32_t*)(d_open + m * KZG_OPENING_LEN) : nullptr, ph ? &pr : nullptr);
+    int r = kzg_enqueue(*d, *k, (const int32_t*)(uint8_t*)d->d_in, d_open, slen, m, k->d_out, flags, launch, force, s,
+                        weighted_from, weights ? (const uint32_t*)(d_open + m * slen) : nullptr, ph ? &pr : nullptr, form);
     if (r) return r;
     HIPCK(hipMemcpyAsync(k->h_out, k->d_out, m, hipMemcpyDeviceToHost, s));
     HIPCK(hipStreamSynchronize(s));
     memcpy(status + off, k->h_out, m);
     if (ph) {
-      std::vector<uint8_t> hb(130 * n + 131 * groups);
+      std::vector<uint8_t> hb(130 * n + 131 * groups + (ph->fold ? 64 * n : 0));
       HIPCK(hipMemcpy(hb.data(), probe_buf, hb.size(), hipMemcpyDeviceToHost));
+      if (ph->fold) memcpy(ph->fold, hb.data() + 130 * n + 131 * groups, 64 * n);
       memcpy(ph->f, hb.data(), 64 * n); memcpy(ph->h, hb.data() + 64 * n, 64 * n); memcpy(ph->inf, hb.data() + 128 * n, 2 * n);
       if (ph->grp) {
         const uint8_t* g = hb.data() + 130 * n;
@@ -316,14 +335,15 @@ void kzg_host_fetch(const bn254::PbHostLane& w, uint8_t st, uint8_t* f, uint8_t*
 }
 }  // namespace
 
-int kzg_fold_on_host(const uint8_t* key_bytes, const uint8_t* openings, size_t stride, size_t n, const uint8_t* weights, unsigned flags, bool weighted, KzgProbeHost& ph, uint8_t* status) {
+int kzg_fold_on_host(const uint8_t* key_bytes, const uint8_t* openings, size_t stride, size_t n, const uint8_t* weights, unsigned flags, bool weighted, KzgProbeHost& ph, uint8_t* status,
+                     const KzgForm& form) {
   using namespace bn254;
   std::vector<int32_t> key(KZG_KEY_DWORDS);      // the caller's bytes need not be aligned
   memcpy(key.data(), key_bytes, KZG_KEY_LEN);
-  const int n_terms = weighted ? KZG_TERMS_RLC : KZG_TERMS_EXACT;
+  const int n_terms = form.n_terms(weighted);
   const size_t n_pad = (n + 63) & ~(size_t)63, groups = n_pad / 64;
   MsmPlan plan;
-  if (!msm_plan_build(plan, kzg_msm_shape(weighted), n_pad, msm_lane_budget(), 0, plonk_joint_g(n_pad))) return set_err(BN254_E_HIP, "KZG: the G1 walk needs more rows than a launch has");
+  if (!msm_plan_build(plan, kzg_form_shape(form, weighted), n_pad, msm_lane_budget(), 0, plonk_joint_g(n_pad))) return set_err(BN254_E_HIP, "KZG: the G1 walk needs more rows than a launch has");
   const int run_steps = knob_run_steps_pairing_batch();
   const int32_t* recs = key.data() + KZG_KEY_REC0_DWORD;
   std::vector<PbHostLane> ws(n), gws(weighted ? groups : 0);
@@ -334,10 +354,14 @@ int kzg_fold_on_host(const uint8_t* key_bytes, const uint8_t* openings, size_t s
   for (size_t i = 0; i < n; i++) {
     PbHostLane& w = ws[i];
     for (auto& x : w.e) x = fp_zero();
+    if (ph.fold) memset(ph.fold + 64 * i, 0, 64);
     if (!key_ok) { st[i] = BN254_ST_MALFORMED; continue; }
     uint32_t wgt[4] = {1, 0, 0, 0};
     if (weights) kzg_weight_words(wgt, weights + 16 * i);
-    st[i] = (uint8_t)kzg_load_opening(w, openings + i * stride, false, key.data(), (flags & BN254_FLAG_STRICT_SCALARS) != 0, weighted ? wgt : nullptr, terms.data(), fl.data());
+    const bool strict = (flags & BN254_FLAG_STRICT_SCALARS) != 0;
+    st[i] = form.k ? (uint8_t)kzg_fold_load_record(w, openings + i * stride, false, form.k, form.data_len, key.data(), strict, weighted ? wgt : nullptr, terms.data(), fl.data(),
+                                                   ph.fold ? ph.fold + 64 * i : nullptr)
+                   : (uint8_t)kzg_load_opening(w, openings + i * stride, false, key.data(), strict, weighted ? wgt : nullptr, terms.data(), fl.data());
     KzgHostIO io{terms.data(), fl.data()};
     kzg_host_sum(plan, 0, io, w, st[i], vp_p(0), KZG_ST_F_INF);
     if (weighted) kzg_host_sum(plan, 1, io, w, st[i], vp_p(1), KZG_ST_H_INF);
@@ -440,6 +464,47 @@ int bn254_kzg_verify_batch_device(const void* d_key, const void* d_openings, siz
   if ((rc = kzg_ensure(*d, *k, device, n, weighted_from != SIZE_MAX, &launch))) return rc;
   return kzg_enqueue(*d, *k, (const int32_t*)d_key, (const uint8_t*)d_openings, stride, n, (uint8_t*)d_status, flags, launch, bn254::PAIRING_FORM_PLAN, (hipStream_t)hip_stream,
                      weighted_from);
+}
+
+// the batch-opening entries answer BN254_E_NOMEM for memory that runs out, on the device or pinned (the entries on openings keep the code they had; the owners of
+// bn254_capi_owners.h name the runtime's error in the message)
+static int kzg_fold_rc(int rc) { return rc == BN254_E_HIP && g_err.find("out of memory") != std::string::npos ? set_err(BN254_E_NOMEM, std::string(g_err)) : rc; }
+
+int bn254_kzg_fold_reserve(size_t n, size_t n_digests, int device) {
+  KzgForm form;
+  const int rc = kzg_fold_form(n_digests, 0, &form);
+  if (rc) return rc;
+  PbDev* d = pb_dev(device);
+  KzgDev* k = kzg_dev(device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  size_t launch;
+  return kzg_fold_rc(kzg_ensure(*d, *k, device, n ? n : 1, false, &launch, form));
+}
+
+int bn254_kzg_verify_folded_batch(const uint8_t* key, const uint8_t* records, size_t stride, size_t n, size_t n_digests, size_t data_len, uint8_t* status, int device, unsigned flags) {
+  KzgForm form;
+  bool done;
+  int rc = kzg_fold_form(n_digests, data_len, &form);
+  if (rc || (rc = kzg_check_args(key, records, stride, n, status, flags, true, &done, form)) || done) return rc;
+  return kzg_fold_rc(kzg_host_call(key, records, stride, n, status, device, flags, bn254::PAIRING_FORM_PLAN, nullptr, false, nullptr, form));
+}
+
+int bn254_kzg_verify_folded_batch_device(const void* d_key, const void* d_records, size_t stride, size_t n, size_t n_digests, size_t data_len, void* d_status, int device, void* hip_stream,
+                                         unsigned flags) {
+  KzgForm form;
+  bool done;
+  int rc = kzg_fold_form(n_digests, data_len, &form);
+  if (rc || (rc = kzg_check_args(d_key, d_records, stride, n, d_status, flags, false, &done, form)) || done) return rc;
+  PbDev* d = pb_dev(device);
+  KzgDev* k = kzg_dev(device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  // as bn254_kzg_verify_batch_device: without BN254_FLAG_RLC nothing is allocated when a reservation of min(n, a pass) records of n_digests digests stands
+  const size_t rlc_min = (size_t)g_kzg_rlc_min.load(std::memory_order_relaxed);
+  const size_t weighted_from = ((flags & BN254_FLAG_RLC) && n >= rlc_min) ? rlc_min : SIZE_MAX;
+  size_t launch;
+  if ((rc = kzg_ensure(*d, *k, device, n, weighted_from != SIZE_MAX, &launch, form))) return kzg_fold_rc(rc);
+  return kzg_fold_rc(kzg_enqueue(*d, *k, (const int32_t*)d_key, (const uint8_t*)d_records, stride, n, (uint8_t*)d_status, flags, launch, bn254::PAIRING_FORM_PLAN, (hipStream_t)hip_stream,
+                                 weighted_from, nullptr, nullptr, form));
 }
 
 void bn254_set_kzg_params(long rlc_min) {

@@ -602,6 +602,9 @@ def main():
             continue                          # cooperative kernels: model_coop12 (call graph + step program)
         if name in ("k_valu_peak", "k_plonk_stage1", "k_plonk_stage2", "k_plonk_stage1_keys", "k_plonk_stage2_keys", "k_plonk_dbg_zeta"):
             continue                          # the measurement kernel; the PlonK stages (transcripts + Fr arithmetic on 32-bit words: < 1 % of a proof's multiply-adds, counted by PMC only)
+        if name == "k_kzg_fold_load":
+            continue                          # its loops run once per digest and per block of the transcript: the count depends on the call's k and data_len, so one figure
+                                              # per record and launch does not exist (a static count would read as a cost and be an undercount for every k > 1)
         e = model_components(name, ins) or model_kernel(name, ins)
         e.pop("weights", None)
         e["symbol"] = sym
