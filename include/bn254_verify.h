@@ -622,6 +622,9 @@ int bn254_kzg_fold_reserve(size_t n, size_t n_digests, int device);
  * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store, and k_pairing_load_shared, k_miller_run_mix of the entries with shared G2 points; its final exponentiation and
  * compare are checks 1 .. 3's kernels), the kernels of the KZG batch (k_kzg_load, k_kzg_fold_load, k_kzg_ident, k_kzg_fetch),
  * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
+ * Nor does a run of it see the PlonK stage kernels: those have the per-key self-test -- one synthetic proof, lane 0 of workgroup 0, ChaCha20 blocks 0 .. 2 -- and, in the
+ * test suite, a batch-wide value test (bn254_dbg_plonk_stages, tests/test_gpu_plonk_stage_values.py) that holds every lane's zeta, lambda, opening, hash-to-field values and
+ * pairing operands, the lambda stream (blocks 3i .. 3i + 2 per slot) and the weight stream of BN254_FLAG_RLC to the oracle, under one key and over key lists.
  *
  * Cost on one MI355X (profiles/selftest_cost.txt): one run is 40 ms of wall time in a warm process, all of it device time on the run's own stream (g16_lane 11.2 ms,
  * pairing_lane 9.0, pair2_lane 8.3, g16_coop 1.9, the built-in key's window tables 1.5, codec 1.4, pair2_coop 1.3, fp12_coop 1.1, fp12_lane 0.7); the host's share (the key
@@ -845,6 +848,28 @@ int bn254_dbg_selftest_ms(float gpu_ms[BN254_SELFTEST_NUM_CHECKS + 1], float* ho
  * (plonk/verify.rs:62-95), 32-byte big-endian, canonical -- and the stage's status per proof (BN254_ACCEPT: alive; else the error it decided) */
 int bn254_dbg_plonk_stage1(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n,
                            uint8_t* zeta_out, uint8_t* status_out, int device);
+/* Both stages and both MSMs of the PlonK path as the product runs them -- the first part of its one pass, stage 1 -> digest MSM -> stage 2 -> KZG MSM, up to the operands of
+ * the pairing check -- under a ChaCha20 key the CALLER gives (lam_key: 8 key words, 3 nonce words), for n <= 4096 proofs; tests/test_gpu_plonk_stage_values.py holds every
+ * value to the oracle.  The public entries cannot be given a key: they draw a fresh one per pass.  The arguments are those of bn254_plonk_verify_batch (of
+ * bn254_plonk_verify_batch_keys for the list form); of flags only BN254_FLAG_RLC is looked at, and it forces the weighted form whatever the batch size: every scalar of both
+ * sums times the proof's weight, 128 bits of the key's second stream (nonce word 2 xor "RLC"), forced odd.  Every argument error is BN254_E_BAD_ARG before a device is touched.
+ * out: n records of 560 bytes in proof order, field values 32-byte canonical big-endian, points x | y:
+ *     0  the stage-1 status (BN254_ACCEPT: alive, else the error the stage decided)
+ *     1  the status after stage 2: BN254_ACCEPT for a proof that reached the pairing check, else the error
+ *     2  1: the linearised-polynomial digest is the identity      3  1: P0 is the identity      4  1: P1 is the identity      5 .. 7  zero
+ *     8  the slot the proof was given, u32 little-endian (its own index under one key): lambda is drawn from blocks 3 slot .. 3 slot + 2, the weight from block slot
+ *    12 .. 15 zero
+ *    16  zeta      48  lambda, the KZG batching scalar      80  lin_opening, the value stage 1 computed for the opening of the linearised polynomial
+ *   112  the linearised-polynomial digest, the first MSM's result (no oracle call gives it: it localises a wrong P0)
+ *   176  hash_to_field of the BSB22 commitments, 8 x 32 bytes, the key's n_qcp first ones used
+ *   432  P0      496  P1: the G1 operands of e(P0, g2[0]) e(P1, g2[1]) == 1 as the second MSM stored them (zero for the identity)
+ * Everything but the two status bytes and the slot is zero for a proof the stages decided, except zeta on an opening mismatch (as bn254_dbg_plonk_stage1).
+ * device -1 (one key only) touches no device: the host compile of the same stage source, lambda and the weight derived as the per-key self-test restates them, and each
+ * sum added up term by term with the host's G1 arithmetic, without a plan or tables -- what proves the tests' expectations where there is no GPU. */
+int bn254_dbg_plonk_stages(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n,
+                           const unsigned lam_key[11], unsigned flags, uint8_t* out, int device);
+int bn254_dbg_plonk_stages_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride,
+                                const uint8_t* public_inputs, size_t input_stride, size_t n, const unsigned lam_key[11], unsigned flags, uint8_t* out, int device);
 
 /* host-only probe of the GLV scalar decomposition the PlonK MSMs use: k = (-1)^neg1 k1 + (-1)^neg2 k2 lambda (mod r), k1, k2 < 2^127 */
 int bn254_dbg_glv_decompose(const uint8_t k32[32], uint8_t k1_16[16], uint8_t k2_16[16], int* neg1, int* neg2);

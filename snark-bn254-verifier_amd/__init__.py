@@ -10,7 +10,7 @@ from .binding import (  # noqa: F401
     set_profile_kernels, PreparedPlonkVk, PlonkVerifier, FLAG_STRICT_SCALARS, FLAG_RLC, RAW_PROOF_LEN, proof_write_raw, shard_plan, set_rlc_params, set_plonk_params,
     dbg_rlc_wide_group, dbg_rlc_wide_plan, dbg_rlc_groups, FLAG_COMPRESSED_PROOFS, COMPRESSED_PROOF_LEN, compress_proof, dbg_g16_decompress,
     sp1_public_values_digest, sp1_pack_values, dbg_sp1_public_inputs, synth_groth16_for_inputs, KeySet, dbg_keys_group,
-    set_keys_params, dbg_keys_plan, prepare_vks, dbg_prepare_vks, dbg_pvk_image, VK_PREPARE_STAGES, synth_plonk, synth_plonk_for_inputs,
+    set_keys_params, dbg_keys_plan, prepare_vks, dbg_prepare_vks, dbg_pvk_image, VK_PREPARE_STAGES, synth_plonk, synth_plonk_for_inputs, dbg_plonk_stages, dbg_plonk_stages_keys,
     PlonkKeySet, dbg_plonk_keys_plan, last_diagnostic, set_plonk_keys_params, set_plonk_rlc_params, dbg_plonk_keys_knobs,
     device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST, dbg_overlap_replay,
     pairing_check_batch, pairing_batch, pairing_check_batch_device, pairing_reserve, dbg_pairing_batch, dbg_pairing_plan, PAIRING_MAX_PAIRS, PAIRING_PAIR_LEN,

@@ -872,6 +872,51 @@ def synth_plonk_for_inputs(seed, n_public, n_qcp, log2_size, inputs, n=None, thr
     return bytes(vk), bytes(proofs)[:stride * n]
 
 
+PLONK_STAGES_REC = 560
+
+
+def _plonk_stage_records(raw, n):
+    """The records of bn254_dbg_plonk_stages (include/bn254_verify.h has the layout) as dicts of bytes / ints."""
+    out = []
+    for i in range(n):
+        r = raw[PLONK_STAGES_REC * i:PLONK_STAGES_REC * (i + 1)]
+        out.append({"status1": r[0], "status": r[1], "lin_inf": r[2], "p0_inf": r[3], "p1_inf": r[4], "slot": int.from_bytes(r[8:12], "little"), "zeta": r[16:48],
+                    "lambda": r[48:80], "lin_opening": r[80:112], "lin": r[112:176], "h2f": [r[176 + 32 * k:208 + 32 * k] for k in range(8)],
+                    "p0": r[432:496], "p1": r[496:560], "pad": r[5:8] + r[12:16]})
+    return out
+
+
+def dbg_plonk_stages(key, proofs, public_inputs, lam_key, n=None, proof_stride=904, n_public=None, flags=0, device=0):
+    """bn254_dbg_plonk_stages: the product's pass up to the pairing operands on n <= 4096 proofs under the caller's ChaCha20 key (lam_key: 11 ints below 2^32).
+    key: a PreparedPlonkVk.  device -1: the host compile of the stages, no device.  Returns one dict per proof ("h2f": all eight values, those past the key's
+    commitment count zero)."""
+    n_public = key.n_public if n_public is None else n_public
+    if n is None:
+        n = len(proofs) // proof_stride
+    fn = lib().bn254_dbg_plonk_stages
+    fn.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint, C.c_void_p, C.c_int]
+    out = (C.c_uint8 * (PLONK_STAGES_REC * max(n, 1)))()
+    lk = (C.c_uint32 * 11)(*lam_key) if lam_key is not None else None
+    _check(fn(key._h if key is not None else None, bytes(proofs) if proofs is not None else None, proof_stride, bytes(public_inputs) if public_inputs is not None else None,
+              n_public, n, lk, flags, out, device))
+    return _plonk_stage_records(bytes(out), n)
+
+
+def dbg_plonk_stages_keys(key_set, key_index, proofs, public_inputs, lam_key, n=None, proof_stride=904, input_stride=None, flags=0, device=0):
+    """bn254_dbg_plonk_stages_keys: the same over a PlonkKeySet, through the gather of a batch over many keys; a record's "slot" is the slot the grouping gave the
+    proof (lambda and the weight are drawn per slot)."""
+    import array
+    idx = array.array("I", key_index)
+    n = len(idx) if n is None else n
+    fn = lib().bn254_dbg_plonk_stages_keys
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint32), C.c_uint, C.c_void_p, C.c_int]
+    out = (C.c_uint8 * (PLONK_STAGES_REC * max(n, 1)))()
+    lk = (C.c_uint32 * 11)(*lam_key) if lam_key is not None else None
+    _check(fn(key_set._arr, len(key_set.keys), idx.buffer_info()[0] if len(idx) else None, bytes(proofs), proof_stride, bytes(public_inputs) if public_inputs is not None else None,
+              key_set.input_stride if input_stride is None else input_stride, n, lk, flags, out, device))
+    return _plonk_stage_records(bytes(out), n)
+
+
 # ---- batch pairing-product checks over caller-supplied (G1, G2) pairs (bn254_pairing_check_batch, include/bn254_verify.h) ----
 PAIRING_MAX_PAIRS = 8
 PAIRING_PAIR_LEN = 192

@@ -306,6 +306,186 @@ int bn254_dbg_plonk_stage1(const bn254_plonk_pvk* pvk, const uint8_t* proofs, si
   return BN254_OK;
 }
 
+// ---------------------------------------------------------------- value-level probes of the PlonK stages (tests/test_gpu_plonk_stage_values.py)
+// The product's own pass up to the pairing operands (plonk_pass_points: stage 1 -> digest MSM -> stage 2 -> KZG MSM) under a ChaCha20 key the CALLER gives, and what it
+// left for every proof, in proof order, as records of PLS_REC bytes (include/bn254_verify.h has the layout).  The public entries cannot be handed a key: they draw
+// theirs inside plonk_pass.
+namespace {
+enum { PLS_REC = 560, PLS_MAX_PROOFS = 4096, PLS_O_P0 = 432, PLS_O_P1 = 496 };
+// the record of one proof from what the device (or the host compile) left: dev = the PLONK_DBG_STAGES_DEV_BYTES of k_plonk_dbg_stages, p0 / p1 = the affine points as
+// stored at VE_LX / VE_CX (read only while the proof is pending)
+void pls_record(uint8_t* rec, const uint8_t* dev, const uint8_t* p0, const uint8_t* p1, uint32_t slot) {
+  memset(rec, 0, PLS_REC);
+  memcpy(rec, dev, PLONK_DBG_STAGES_DEV_BYTES);
+  const uint8_t st = dev[1];
+  for (int k = 0; k < 4; k++) rec[8 + k] = (uint8_t)(slot >> (8 * k));
+  if (!(st & BN254_ST_PENDING)) return;       // decided: the byte is the proof's status, and no point of it was stored
+  rec[1] = (st & 0x1f) ? (uint8_t)(st & 0x1f) : (uint8_t)BN254_ACCEPT;
+  rec[3] = (st & BN254_ST_LINF) ? 1 : 0; rec[4] = (st & BN254_ST_LINF2) ? 1 : 0;
+  if (!rec[3]) memcpy(rec + PLS_O_P0, p0, 64);
+  if (!rec[4]) memcpy(rec + PLS_O_P1, p1, 64);
+}
+// sum s of a launch's shape over the terms a stage wrote for one proof, term by term with the host's G1 arithmetic: no plan, no rows, no window tables
+G1Proj pls_host_sum(const PlonkKey& key, const MsmShape& sh, int s, const MsmTerm* t, const uint8_t* fl) {
+  auto mul = [](const G1Aff& P, const uint32_t* w, int nw) {
+    G1Proj acc = g1_identity();
+    const G1Proj b = g1_from_affine(P);
+    for (int bit = 32 * nw - 1; bit >= 0; bit--) { acc = g1_dbl(acc); if ((w[bit >> 5] >> (bit & 31)) & 1u) acc = g1_add(acc, b); }
+    return acc;
+  };
+  auto point = [](const MsmTerm& e) { G1Aff P; P.x = fp_from_limbs(e.pt); P.y = fp_from_limbs(e.pt + BN_NL); return P; };
+  G1Proj L = g1_identity();
+  for (int i = 0; i < sh.n_var[s]; i++) {            // (+-k1 +- k2 lambda) P, the halves and signs as put_term left them; flag bit 0: P is the identity
+    const int q = sh.var_term[s][i];
+    if (fl[q] & 1) continue;
+    const G1Aff P = point(t[q]);
+    G1Aff P2; P2.x = fp_mul(P.x, fp_from_limbs(BN_GLV_BETA)); P2.y = P.y;
+    L = g1_add(L, mul((fl[q] & 2) ? g1_neg(P) : P, t[q].k, 4));
+    L = g1_add(L, mul((fl[q] & 4) ? g1_neg(P2) : P2, t[q].k + 4, 4));
+  }
+  for (int i = 0; i < sh.n_unit[s]; i++) {
+    const int q = sh.unit_term[s][i];
+    if (fl[q] & 1) continue;
+    const G1Aff P = point(t[q]);
+    L = g1_add(L, g1_from_affine((fl[q] & 2) ? g1_neg(P) : P));
+  }
+  for (int i = 0; i < sh.n_fixed[s]; i++) L = g1_add(L, mul(plonk_table_point(key, sh.fixed_tab[s][i]), t[sh.fixed_term[s][i]].k, 8));
+  return L;
+}
+// The host compile of the same stage source, proof by proof: plonk_stage1, lambda and the weight derived as bn254_plonk_self_test restates them, plonk_stage2, and each
+// sum added up by pls_host_sum.  No device is touched
+int pls_on_host(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n, const uint32_t lam_key[11],
+                bool weighted, uint8_t* out) {
+  const PlonkKey& key = pvk->key;
+  const FrCtx& F = fr_ctx();
+  const int T1 = plonk_stage1_terms(key), T2 = plonk_stage2_terms(key), TT = T2 + 2;
+  bn254::ChaChaKey lk, wk_;
+  for (int i = 0; i < 8; i++) lk.k[i] = lam_key[i];
+  for (int i = 0; i < 3; i++) lk.nonce[i] = lam_key[8 + i];
+  wk_ = lk; wk_.nonce[2] ^= 0x00524c43u;
+  std::vector<MsmTerm> t1((size_t)T1), t2((size_t)TT); std::vector<uint8_t> f1((size_t)T1), f2((size_t)TT);
+  auto put_point = [](uint8_t* o, const G1Proj& L) { if (!g1_is_identity(L)) enc_g1_uncompressed(o, g1_to_affine(L)); };
+  for (size_t i = 0; i < n; i++) {
+    uint8_t dev[PLONK_DBG_STAGES_DEV_BYTES], p0[64], p1[64];
+    memset(dev, 0, sizeof dev); memset(p0, 0, 64); memset(p1, 0, 64);
+    const uint8_t* proof = proofs + i * proof_stride;
+    PlonkWork wk; memset((void*)&wk, 0, sizeof wk);
+    memset((void*)t1.data(), 0, t1.size() * sizeof(MsmTerm)); memset(f1.data(), 0, f1.size());
+    const int st = plonk_stage1(key, proof, proof_stride, public_inputs + i * n_public * 32, n_public, wk, t1.data(), f1.data());
+    dev[0] = dev[1] = (uint8_t)st;
+    if (st == PL_OK || st == PL_OPENING) F.to_be(dev + 16, wk.zeta);
+    if (st == PL_OK) {
+      uint32_t lw[12]; for (int j = 0; j < 3; j++) bn254::chacha20_block4(lw + 4 * j, lk, 3u * (uint32_t)i + (uint32_t)j);
+      uint8_t lb[48]; for (int j = 0; j < 12; j++) { lb[4 * j] = (uint8_t)lw[j]; lb[4 * j + 1] = (uint8_t)(lw[j] >> 8); lb[4 * j + 2] = (uint8_t)(lw[j] >> 16); lb[4 * j + 3] = (uint8_t)(lw[j] >> 24); }
+      wk.lambda = F.from_be_reduce(lb, 48);
+      F.to_be(dev + 48, wk.lambda); F.to_be(dev + 80, wk.lin_opening);
+      for (uint32_t k = 0; k < key.n_qcp; k++) F.to_be(dev + 176 + 32 * k, bsb22_hash_to_field(proof + wk.pr.off_bsb + 64 * (size_t)k));
+      const G1Proj lin = pls_host_sum(key, pvk->shape1, 0, t1.data(), f1.data());
+      const bool lin_inf = g1_is_identity(lin);
+      uint32_t lin_words[16] = {0};
+      if (lin_inf) dev[2] = 1;
+      else { const G1Aff a = g1_to_affine(lin); fp_to_words(lin_words, a.x); fp_to_words(lin_words + 8, a.y); enc_g1_uncompressed(dev + 112, a); }
+      FrM wgt = {{0, 0, 0, 0}};
+      if (weighted) {
+        uint32_t rw[4]; bn254::chacha20_block4(rw, wk_, (uint32_t)i);
+        uint8_t rb[16];
+        rw[0] |= 1u;
+        for (int j = 0; j < 4; j++) { rb[15 - 4 * j] = (uint8_t)rw[j]; rb[14 - 4 * j] = (uint8_t)(rw[j] >> 8); rb[13 - 4 * j] = (uint8_t)(rw[j] >> 16); rb[12 - 4 * j] = (uint8_t)(rw[j] >> 24); }
+        wgt = F.from_be_reduce(rb, 16);
+      }
+      wk.pr.raw = proof;
+      plonk_stage2(key, proof, wk, lin_words, lin_inf, t2.data(), f2.data(), t2.data() + T2, weighted ? &wgt : nullptr);
+      const MsmShape& sh2 = weighted ? pvk->shape2_rlc : pvk->shape2;
+      const G1Proj P0 = pls_host_sum(key, sh2, 0, t2.data(), f2.data()), P1 = pls_host_sum(key, sh2, 1, t2.data(), f2.data());
+      dev[1] = (uint8_t)(BN254_ST_PENDING | (g1_is_identity(P0) ? BN254_ST_LINF : 0) | (g1_is_identity(P1) ? BN254_ST_LINF2 : 0));
+      put_point(p0, P0); put_point(p1, P1);
+    }
+    pls_record(out + i * PLS_REC, dev, p0, p1, (uint32_t)i);
+  }
+  return BN254_OK;
+}
+#if defined(__HIPCC__)
+// what a pass of m proofs (slots) left on context c -> the device halves of the records and the stored points, on the host.  Enqueued behind the pass on c.stream
+int pls_fetch(PlonkCtx& c, size_t m, uint32_t n_h2f, std::vector<uint8_t>& dev, std::vector<uint8_t>& pts) {
+  int rc;
+  DevBuf<uint8_t> d_dev, d_pts;
+  if ((rc = d_dev.ensure(m * (size_t)PLONK_DBG_STAGES_DEV_BYTES)) || (rc = d_pts.ensure(384 * m))) return rc;
+  hipError_t e = bn254_launch_plonk_dbg_stages(c.d_work, c.words, c.inf, c.status, m, n_h2f, d_dev, c.stream);
+  // elements 6 .. 17 as one Fp12 in the store's byte order: (VE_CX, VE_CY) first, (VE_LX, VE_LY) fourth (as bn254_dbg_g1_msm reads them in out_mode 1)
+  if (e == hipSuccess) e = bn254_launch_dbg_store(c.ws, m, (int)VE_CX_ELEM, d_pts, 0, c.stream);
+  if (e != hipSuccess) return launch_err(e, "probe");
+  HIPCK(hipStreamSynchronize(c.stream));
+  dev.resize(m * (size_t)PLONK_DBG_STAGES_DEV_BYTES); pts.resize(384 * m);
+  HIPCK(hipMemcpy(dev.data(), d_dev, dev.size(), hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(pts.data(), d_pts, pts.size(), hipMemcpyDeviceToHost));
+  return BN254_OK;
+}
+int pls_on_device(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n, const uint32_t lam_key[11],
+                  bool weighted, uint8_t* out, int device) {
+  PlonkDev* d;
+  int rc;
+  {
+    std::lock_guard<std::mutex> lk(pvk->mu);
+    if ((rc = plonk_ensure_dev(pvk, device, &d))) return rc;
+  }
+  PlonkLease lease(d, 1);
+  PlonkCtx& c = lease.ctx(0);
+  if ((rc = plonk_ensure_ctx(pvk, c, n, 0))) return rc;
+  const size_t pb = n * proof_stride, ib = n * n_public * 32;
+  DevBuf<uint8_t> in;
+  if ((rc = in.ensure(pb + ib + 4))) return rc;
+  HIPCK(hipMemcpy(in, proofs, pb, hipMemcpyHostToDevice));
+  if (ib) HIPCK(hipMemcpy(in + pb, public_inputs, ib, hipMemcpyHostToDevice));
+  // the arguments of plonk_run_device: records and rows back to back, as the host-buffer entry stages them
+  std::vector<uint8_t> dev, pts;
+  rc = plonk_pass_points(pvk, PlonkTables{d, nullptr, 0, nullptr, d->one}, PlonkPassIn{in, proof_stride, in + pb, n_public, 0, 0, 0}, c, n, lam_key, weighted, nullptr);
+  if (!rc) rc = pls_fetch(c, n, pvk->key.n_qcp, dev, pts);
+  if (rc) { const std::string keep = g_err; (void)hipStreamSynchronize(c.stream); return set_err(rc, keep); }
+  for (size_t i = 0; i < n; i++) pls_record(out + i * PLS_REC, dev.data() + i * PLONK_DBG_STAGES_DEV_BYTES, pts.data() + 384 * i + 192, pts.data() + 384 * i, (uint32_t)i);
+  return BN254_OK;
+}
+#endif
+}  // namespace
+static_assert(PLONK_DBG_STAGES_DEV_BYTES == PLS_O_P0, "the device half of a probe record ends where the points begin");
+
+int bn254_dbg_plonk_stages(const bn254_plonk_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n,
+                           const unsigned lam_key[11], unsigned flags, uint8_t* out, int device) {
+  int rc = check_batch_args(true, pvk, proofs, proof_stride, public_inputs, n_public, n, out, flags);
+  if (rc) return rc;
+  if (!lam_key || !out || !proofs || n == 0 || n > (size_t)PLS_MAX_PROOFS || device < -1) return set_err(BN254_E_BAD_ARG, "bad argument: 1 .. 4096 proofs, a key of 11 words, device -1 (host) or an ordinal");
+  const bool weighted = (flags & BN254_FLAG_RLC) != 0;
+  if (device < 0) return pls_on_host(pvk, proofs, proof_stride, public_inputs, n_public, n, lam_key, weighted, out);
+#if defined(__HIPCC__)
+  return pls_on_device(pvk, proofs, proof_stride, public_inputs, n_public, n, lam_key, weighted, out, device);
+#else
+  return set_err(BN254_E_NO_DEVICE, "the device half of the probe is not part of a host build");
+#endif
+}
+#if defined(__HIPCC__)
+int bn254_dbg_plonk_stages_keys(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride,
+                                const uint8_t* public_inputs, size_t input_stride, size_t n, const unsigned lam_key[11], unsigned flags, uint8_t* out, int device) {
+  if (!lam_key || !out || n == 0 || n > (size_t)PLS_MAX_PROOFS || device < 0) return set_err(BN254_E_BAD_ARG, "bad argument: 1 .. 4096 proofs, a key of 11 words, a device ordinal");
+  const bool weighted = (flags & BN254_FLAG_RLC) != 0;
+  return plonk_keys_probe_pass(pvks, n_keys, key_index, proofs, proof_stride, public_inputs, input_stride, n, flags, device, [&](const PlonkKeysProbePass& p) -> int {
+    int rc = plonk_pass_points(p.shapes, p.t, p.in, *p.c, p.slots, lam_key, weighted, nullptr);
+    std::vector<uint8_t> dev, pts;
+    if (rc || (rc = pls_fetch(*p.c, p.slots, p.shapes->key.n_qcp, dev, pts))) return rc;
+    std::vector<uint32_t> s2p(p.slots);
+    HIPCK(hipMemcpy(s2p.data(), p.slot_to_proof, p.slots * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    std::vector<uint8_t> seen(n, 0);
+    for (size_t j = 0; j < p.slots; j++) {
+      const uint32_t i = s2p[j];
+      if (i >= n) continue;                                 // a padding slot
+      if (seen[i]) return set_err(BN254_E_HIP, "grouping gave a proof two slots");
+      seen[i] = 1;
+      pls_record(out + (size_t)i * PLS_REC, dev.data() + j * PLONK_DBG_STAGES_DEV_BYTES, pts.data() + 384 * j + 192, pts.data() + 384 * j, (uint32_t)j);
+    }
+    for (size_t i = 0; i < n; i++) if (!seen[i]) return set_err(BN254_E_HIP, "grouping left a proof without a slot");
+    return BN254_OK;
+  });
+}
+#endif
+
 // the multiply-add issue rate of THIS device (lane-level v_mad_u64_u32 per second, sixteen independent chains per lane, four wavefronts per SIMD, best of five
 // launches of ~0.25 ms): what bench.py divides its VALU rooflines by (the constant of profiles/r01_ubench_valu.txt, 35.1e12, stays as the reference)
 int bn254_dbg_valu_peak(int device, double* mads_per_s) {

@@ -50,6 +50,10 @@ hipError_t bn254_launch_plonk_group_sums(int32_t* ws, const uint8_t* status, siz
 hipError_t bn254_launch_plonk_group_scatter(uint8_t* status, size_t n, const uint8_t* grp_status, uint32_t* n_failed, hipStream_t s);
 
 hipError_t bn254_launch_plonk_dbg_zeta(const void* d_work, size_t n, uint8_t* d_zeta, uint8_t* d_status, hipStream_t s);
+// the values the stages left for n proofs (slots), PLONK_DBG_STAGES_DEV_BYTES per proof (k_plonk_dbg_stages has the layout; n_h2f: hash-to-field values per proof, at most 8)
+#define PLONK_DBG_STAGES_DEV_BYTES 432
+hipError_t bn254_launch_plonk_dbg_stages(const void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, const uint8_t* d_status, size_t n, uint32_t n_h2f, uint8_t* d_out,
+                                         hipStream_t s);
 
 #pragma GCC visibility push(hidden)
 extern thread_local std::string g_err;     // bn254_last_error() of the calling thread
@@ -334,6 +338,14 @@ int plonk_msm(const PlonkTables& t, PlonkCtx& c, const MsmShape& shape, size_t m
 // One pass of m proofs (slots) on context c, from "records and rows are in device memory" to "the status bytes are in c.status", all enqueued on c.stream; shapes: the
 // key whose term counts and MSM shapes the pass has.  tk: null, or the eight timing events of PlonkCtx::tk
 int plonk_pass(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, unsigned flags, const Event* tk, PlonkPassReport* rep);
+// The first part of that pass under the CALLER's ChaCha20 key: stage 1 -> digest MSM -> stage 2 -> KZG MSM, to the pairing operands at VE_LX / VE_CX of c.ws and the
+// status bytes in c.status.  plonk_pass calls it with a key it has just drawn; the only other callers are the value probes of bn254_capi_dbg.hip
+int plonk_pass_points(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, const uint32_t lam_key[11], bool weighted, const Event* tk);
+// bn254_capi_plonk_keys.hip, for the value probe over a key list: the arguments of bn254_plonk_verify_batch_keys checked, the batch grouped, and ALL its slots gathered
+// as one pass on a leased context (pk_run_pass's front).  body sees what that pass would hand to plonk_pass; slot_to_proof: the slots' proof indices, on the device
+struct PlonkKeysProbePass { const bn254_plonk_pvk* shapes; PlonkTables t; PlonkPassIn in; PlonkCtx* c; size_t slots; const uint32_t* slot_to_proof; };
+int plonk_keys_probe_pass(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                          size_t input_stride, size_t n, unsigned flags, int device, const std::function<int(const PlonkKeysProbePass&)>& body);
 // The passes of a plan -- worker w has items [w per, (w + 1) per) of `total`, `pass` at a time -- on the contexts of a lease: run_pass(w, first, m) inline for one
 // worker, on one host thread each otherwise.  The first failure is the call's (set_err)
 int plonk_run_workers(const PlonkLease& lease, int workers, size_t per, size_t pass, size_t total, const std::function<int(int, size_t, size_t)>& run_pass);

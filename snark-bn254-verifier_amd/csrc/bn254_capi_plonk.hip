@@ -246,31 +246,42 @@ static int plonk_fresh_lam_key(uint32_t lam_key[11]) {
   return BN254_OK;
 }
 
-// One pass with BOTH host stages on the device (bn254_k_plonk.hip): stage 1 -> digest MSM -> stage 2 -> folding MSMs -> pairing check on the context's stream, without
-// a host wait in between unless BN254_FLAG_RLC is honoured.  Over a list a padding slot is decided by stage 1 and contributes the identity to everything after it.
-int plonk_pass(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, unsigned flags, const Event* tk, PlonkPassReport* rep) {
+// The first part of a pass, up to the row sums of the second MSM: stage 1 -> digest MSM -> stage 2 -> KZG MSM, all enqueued on c.stream.  It leaves the pairing
+// operands of every pending proof at VE_LX / VE_CX of c.ws and the status bytes in c.status.  lam_key: the 11 words of the pass's ChaCha20 key and nonce; weighted: every
+// scalar of both sums carries the proof's weight from the key's second stream (the form the joint check of BN254_FLAG_RLC needs).  The key is the CALLER's: plonk_pass
+// below hands it a fresh one, and beside it only the value probes of bn254_capi_dbg.hip call this (tests/test_capi_cpu.py holds that).
+int plonk_pass_points(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, const uint32_t lam_key[11], bool weighted, const Event* tk) {
   const int T1 = plonk_stage1_terms(shapes->key), T2 = plonk_stage2_terms(shapes->key), TT = T2 + 2;
-  *rep = PlonkPassReport();
   if (m > c.cap) return set_err(BN254_E_HIP, "PlonK context smaller than the pass (internal sizing error)");
-  uint32_t lam_key[11];
-  int rc = plonk_fresh_lam_key(lam_key);
-  if (rc) return rc;
+  int rc;
   auto mark = [&](int k) { return tk ? hipEventRecord(tk[k], c.stream) : hipSuccess; };
   HIPCK(mark(0));
   if ((rc = pass_stage1(t, in, c, m, lam_key, T1))) return rc;
   HIPCK(mark(1));
   if ((rc = plonk_msm(t, c, shapes->shape1, m, T1, true, &c.last_lanes[0], tk ? (hipEvent_t)tk[2] : nullptr))) return rc;
   HIPCK(mark(3));
+  if ((rc = pass_stage2(t, in, c, m, TT, T2, weighted ? lam_key : nullptr))) return rc;
+  HIPCK(mark(4));
+  if ((rc = plonk_msm(t, c, weighted ? shapes->shape2_rlc : shapes->shape2, m, TT, false, &c.last_lanes[1], tk ? (hipEvent_t)tk[5] : nullptr))) return rc;
+  HIPCK(mark(6));
+  return BN254_OK;
+}
+
+// One pass with BOTH host stages on the device (bn254_k_plonk.hip): the first part above under a fresh key, then the pairing check, on the context's stream, without
+// a host wait in between unless BN254_FLAG_RLC is honoured.  Over a list a padding slot is decided by stage 1 and contributes the identity to everything after it.
+int plonk_pass(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkPassIn& in, PlonkCtx& c, size_t m, unsigned flags, const Event* tk, PlonkPassReport* rep) {
+  *rep = PlonkPassReport();
+  if (m > c.cap) return set_err(BN254_E_HIP, "PlonK context smaller than the pass (internal sizing error)");
+  uint32_t lam_key[11];
+  int rc = plonk_fresh_lam_key(lam_key);
+  if (rc) return rc;
   // BN254_FLAG_RLC: the pairing checks of the pass batched over groups of 64 proofs -- honoured from plonk_rlc_min proofs (slots) per pass (below, the one remaining
   // pairing is the same latency-bound launch as the per-proof checks and nothing is gained)
   const bool rlc = (flags & BN254_FLAG_RLC) != 0 && m >= plonk_rlc_min();
   const size_t groups = (m + 63) / 64;
   if (rlc && (groups * (size_t)(G16_WS_BYTES_PER_PROOF / 4) > c.grp_ws.cap() || groups > c.grp_status.cap()))
     return set_err(BN254_E_HIP, "PlonK context smaller than the pass's groups (internal sizing error)");
-  if ((rc = pass_stage2(t, in, c, m, TT, T2, rlc ? lam_key : nullptr))) return rc;
-  HIPCK(mark(4));
-  if ((rc = plonk_msm(t, c, rlc ? shapes->shape2_rlc : shapes->shape2, m, TT, false, &c.last_lanes[1], tk ? (hipEvent_t)tk[5] : nullptr))) return rc;
-  HIPCK(mark(6));
+  if ((rc = plonk_pass_points(shapes, t, in, c, m, lam_key, rlc, tk))) return rc;
   rep->exact = !rlc;
   if (rlc) {
     // group sums (weighted points of the 64 proofs of a wavefront) -> one pairing check per group -> pending proofs of passed groups accepted; the proofs of a
@@ -286,7 +297,7 @@ int plonk_pass(const bn254_plonk_pvk* shapes, const PlonkTables& t, const PlonkP
     rep->exact = rep->failed != 0;
   }
   if (rep->exact && (rc = t.launched(pass_check_items(t, c, m), "PlonK pairing check"))) return rc;
-  HIPCK(mark(7));
+  if (tk) HIPCK(hipEventRecord(tk[7], c.stream));
   return BN254_OK;
 }
 

@@ -204,8 +204,9 @@ int pk_ensure_ctx(PlonkKeySet& s, const PlonkLease& lease, int w, size_t slots, 
 }
 
 // ---- one pass: slots [s0, s0 + m) of the call's grouping on context c: gather, the pass (plonk_pass), scatter ----------------------------------------------------
-int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, size_t s0, size_t m, const uint8_t* d_proofs, size_t proof_stride, const uint8_t* d_inputs,
-                size_t input_stride, size_t n, uint8_t* d_status, unsigned flags) {
+// the front of a pass: its records and rows gathered in slot order on c.stream; *t / *in: what the pass then runs on
+int pk_gather_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, size_t s0, size_t m, const uint8_t* d_proofs, size_t proof_stride, const uint8_t* d_inputs,
+                   size_t input_stride, size_t n, PlonkTables* t, PlonkPassIn* in) {
   HIPCK(hipSetDevice(s.device));
   const uint32_t n_keys = (uint32_t)s.list.size();
   const size_t rec_bytes = pk_rec_bytes(proof_stride), rec_stride = (rec_bytes + 3) & ~(size_t)3, row_stride = 32 * s.max_public;
@@ -215,11 +216,20 @@ int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, 
   hipError_t e = bn254_launch_plonk_keys_gather(d_proofs, proof_stride, d_inputs, input_stride, (uint32_t)n, s2p, gk, s.desc, n_keys, (uint32_t)m, x.recs, (uint32_t)rec_stride,
                                                 (uint32_t)rec_bytes, x.rows, (uint32_t)row_stride, c.stream);
   if (e != hipSuccess) return launch_err(e, "PlonK key-set gather");
+  *t = PlonkTables{nullptr, s.desc, n_keys, gk, s.one};
+  *in = PlonkPassIn{x.recs, rec_stride, row_stride ? (const uint8_t*)x.rows : nullptr, 0, proof_stride, row_stride, s.staged_public};
+  return BN254_OK;
+}
+int pk_run_pass(PlonkKeySet& s, PlonkCtx& c, PkCtxExtra& x, const PkCall& call, size_t s0, size_t m, const uint8_t* d_proofs, size_t proof_stride, const uint8_t* d_inputs,
+                size_t input_stride, size_t n, uint8_t* d_status, unsigned flags) {
+  PlonkTables t; PlonkPassIn in;
+  int rc = pk_gather_pass(s, c, x, call, s0, m, d_proofs, proof_stride, d_inputs, input_stride, n, &t, &in);
+  if (rc) return rc;
+  const uint32_t* s2p = call.slot_to_proof + s0;
   // all members share the shapes of a pass: member 0 stands for them
   PlonkPassReport rep;
-  int rc = plonk_pass(s.list[0], PlonkTables{nullptr, s.desc, n_keys, gk, s.one},
-                      PlonkPassIn{x.recs, rec_stride, row_stride ? (const uint8_t*)x.rows : nullptr, 0, proof_stride, row_stride, s.staged_public}, c, m, flags, nullptr, &rep);
-  if (rc) return rc;
+  if ((rc = plonk_pass(s.list[0], t, in, c, m, flags, nullptr, &rep))) return rc;
+  hipError_t e;
   if (rep.joint) { s.stat[0].fetch_add(1, std::memory_order_relaxed); s.stat[1].fetch_add(rep.groups, std::memory_order_relaxed); s.stat[2].fetch_add(rep.failed, std::memory_order_relaxed); }
   if (rep.exact && plonk_keys_coop_form(m)) s.stat[3].fetch_add(1, std::memory_order_relaxed);
   e = bn254_launch_plonk_keys_scatter(c.status, s2p, (uint32_t)m, (uint32_t)n, d_status, c.stream);
@@ -262,6 +272,46 @@ std::shared_ptr<PlonkKeySet> pk_get_ready(const bn254_plonk_pvk* const* pvks, si
 
 // bn254_plonk_vk_free: every cached set that contains the key goes
 void plonk_keys_sets_drop(const bn254_plonk_pvk* member) { pk_cache().drop(member); }
+
+// The value probe over a key list (bn254_dbg_plonk_stages_keys): the host entry's checks, the batch's buffers on the device, the grouping, and every slot gathered as
+// ONE pass on one leased context -- then `body` instead of plonk_pass.  The pass is not cut: a probe batch is small, and the slot a proof is given is what its lambda
+// and weight are drawn by
+int plonk_keys_probe_pass(const bn254_plonk_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                          size_t input_stride, size_t n, unsigned flags, int device, const std::function<int(const PlonkKeysProbePass&)>& body) {
+  size_t max_public = 0;
+  int rc = pk_check_args(pvks, n_keys, key_index, proofs, proof_stride, public_inputs, input_stride, n, proofs, flags, &max_public);
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++)
+    if (key_index[i] >= n_keys) return set_err(BN254_E_BAD_ARG, "key_index[" + std::to_string(i) + "] = " + std::to_string(key_index[i]) + " is outside the list of " + std::to_string(n_keys) + " keys");
+  if ((rc = check_device(device))) return rc;
+  std::shared_ptr<PlonkKeySet> s = pk_get_ready(pvks, n_keys, device, max_public, &rc);
+  if (rc) return rc;
+  CallLease cl(*s);
+  PkCall& c = *cl.c;
+  if ((rc = pk_ensure_call(*s, c, n, true, proof_stride, input_stride))) return rc;
+  const size_t in_bytes = max_public ? n * input_stride : 0;
+  HIPCK(hipMemcpy((uint32_t*)c.st_index, key_index, n * 4, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(c.st_proofs, proofs, n * proof_stride, hipMemcpyHostToDevice));
+  if (in_bytes) HIPCK(hipMemcpy(c.st_inputs, public_inputs, in_bytes, hipMemcpyHostToDevice));
+  const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
+  hipStream_t cs = c.ring.compute;
+  hipError_t e = bn254_launch_keys_group(c.st_index, (uint32_t)n, (uint32_t)n_keys, (uint32_t)bound, c.count, c.base, c.cursor, c.n_slots, c.slot_to_proof, c.granule_key, c.st_status, cs);
+  if (e != hipSuccess) return launch_err(e, "grouping");
+  HIPCK(hipMemcpyAsync(c.h_slots, c.n_slots, sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+  HIPCK(hipStreamSynchronize(cs));
+  const size_t slots = *c.h_slots;
+  if (slots == 0 || slots > bound || (slots & 63)) return set_err(BN254_E_HIP, "grouping returned an impossible slot count");
+  PlonkLease lease(&s->pool, 1);
+  if ((rc = pk_ensure_ctx(*s, lease, 0, slots, proof_stride))) return rc;
+  PlonkCtx& ctx = lease.ctx(0);
+  PlonkKeysProbePass p;
+  p.shapes = s->list[0]; p.c = &ctx; p.slots = slots; p.slot_to_proof = c.slot_to_proof;
+  rc = pk_gather_pass(*s, ctx, s->extra[lease.idx[0]], c, 0, slots, c.st_proofs, proof_stride, in_bytes ? (const uint8_t*)c.st_inputs : nullptr, input_stride, n, &p.t, &p.in);
+  if (!rc) rc = body(p);
+  if (rc) { const std::string keep = g_err; (void)hipStreamSynchronize(ctx.stream); return set_err(rc, keep); }      // nothing of the pass in flight when the lease ends
+  HIPCK(hipStreamSynchronize(ctx.stream));
+  return BN254_OK;
+}
 
 extern "C" {
 

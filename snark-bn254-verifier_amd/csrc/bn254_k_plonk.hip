@@ -408,6 +408,33 @@ __global__ void k_plonk_dbg_zeta(const PlonkWork* __restrict__ work, uint32_t n,
   for (int j = 0; j < 32; j++) zeta_out[(size_t)i * 32 + j] = work[i].status == PL_OK || work[i].status == PL_OPENING ? z[j] : 0;
   status_out[i] = (uint8_t)work[i].status;
 }
+// probe for the value tests (bn254_dbg_plonk_stages): what both stages and the digest MSM left for proof (slot) i, 432 bytes, field values canonical big-endian:
+//   0 stage-1 status | 1 the status byte after stage 2 as stored | 2 the digest is the identity | 3 .. 15 zero
+//   16 zeta | 48 lambda | 80 lin_opening | 112 the linearised-polynomial digest (x | y, zero for the identity) | 176 h2f[0 .. n_h2f)
+// Everything but the two status bytes is zero for a proof stage 1 decided, except zeta on an opening mismatch (as k_plonk_dbg_zeta)
+__global__ void __launch_bounds__(64) k_plonk_dbg_stages(const PlonkWork* __restrict__ work, const uint32_t* __restrict__ lin_words, const uint8_t* __restrict__ lin_inf,
+                                                         const uint8_t* __restrict__ status, uint32_t n, uint32_t n_h2f, uint8_t* __restrict__ out) {
+  const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+  if (i >= n) return;
+  const FrCtx& F = fr_ctx();
+  const PlonkWork& wk = work[i];
+  uint8_t* o = out + (size_t)i * 432;
+  for (int j = 0; j < 432; j++) o[j] = 0;
+  o[0] = (uint8_t)wk.status; o[1] = status[i];
+  uint8_t b[32];
+  auto put = [&](int at, const FrM& v) { F.to_be(b, v); for (int j = 0; j < 32; j++) o[at + j] = b[j]; };
+  if (wk.status == PL_OK || wk.status == PL_OPENING) put(16, wk.zeta);
+  if (wk.status != PL_OK) return;
+  put(48, wk.lambda); put(80, wk.lin_opening);
+  if (lin_inf[i]) o[2] = 1;
+  else {
+    uint32_t w[16];
+    for (int q = 0; q < 16; q++) w[q] = lin_words[(size_t)i * 16 + q];
+    words_to_be(b, w); for (int j = 0; j < 32; j++) o[112 + j] = b[j];
+    words_to_be(b, w + 8); for (int j = 0; j < 32; j++) o[144 + j] = b[j];
+  }
+  for (uint32_t k = 0; k < n_h2f && k < (uint32_t)PLONK_MAX_QCP; k++) put(176 + 32 * (int)k, wk.h2f[k]);
+}
 }  // namespace bn254
 #if defined(BN254_PLONK_MARKS)
 // diagnostics build: the clock stamps of the last stage launches (100 MHz ticks; bn254_plonk.hpp::PL_MARK)
@@ -422,5 +449,11 @@ extern "C" int bn254_dbg_plonk_dump_device(uint8_t out[64 * 32]) { return (int)h
 #endif
 hipError_t bn254_launch_plonk_dbg_zeta(const void* d_work, size_t n, uint8_t* d_zeta, uint8_t* d_status, hipStream_t s) {
   hipLaunchKernelGGL(k_plonk_dbg_zeta, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const PlonkWork*)d_work, (uint32_t)n, d_zeta, d_status);
+  return hipGetLastError();
+}
+hipError_t bn254_launch_plonk_dbg_stages(const void* d_work, const uint32_t* d_lin_words, const uint8_t* d_lin_inf, const uint8_t* d_status, size_t n, uint32_t n_h2f, uint8_t* d_out,
+                                         hipStream_t s) {
+  if (n_h2f > (uint32_t)PLONK_MAX_QCP) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_plonk_dbg_stages, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (const PlonkWork*)d_work, d_lin_words, d_lin_inf, d_status, (uint32_t)n, n_h2f, d_out);
   return hipGetLastError();
 }

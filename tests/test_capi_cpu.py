@@ -273,7 +273,19 @@ def test_kzg_batching_scalar_keyed_per_call_and_expanded_on_the_device():
     assert "getrandom((uint8_t*)lam_key" in draw
     one_pass = body(src, "int plonk_pass(const bn254_plonk_pvk* shapes,")
     assert sum(t.count("plonk_fresh_lam_key(") for t in capi.values()) == 2 and one_pass.count("plonk_fresh_lam_key(lam_key)") == 1      # the definition and the one call
-    assert one_pass.index("plonk_fresh_lam_key(lam_key)") < one_pass.index("pass_stage1(t, in, c, m, lam_key, T1)")
+    # the pass hands the key it has just drawn to its first part (stage 1 .. the second MSM's row sums), which launches stage 1 with exactly the key it is given
+    points = body(src, "int plonk_pass_points(const bn254_plonk_pvk* shapes,")
+    assert one_pass.index("plonk_fresh_lam_key(lam_key)") < one_pass.index("plonk_pass_points(shapes, t, in, c, m, lam_key, rlc, tk)")
+    assert points.count("pass_stage1(t, in, c, m, lam_key, T1)") == 1 and "getrandom" not in points and "pass_stage1(" not in one_pass
+    assert "pass_stage2(t, in, c, m, TT, T2, weighted ? lam_key : nullptr)" in points
+    # that caller-keyed part is reachable from the pass and from the value probes of bn254_capi_dbg.hip only: no public entry can be handed a key
+    calls = {f: len(re.findall(r"\bplonk_pass_points\(", t)) for f, t in capi.items()}
+    assert calls.pop("bn254_capi_plonk.hip") == 2 and calls.pop("bn254_capi_dbg.hip") == 2 and not any(calls.values()), calls      # definition + plonk_pass | the two probes
+    dbg = capi["bn254_capi_dbg.hip"]
+    for m in re.finditer(r"\bplonk_pass_points\(", dbg):
+        head = dbg.rfind("\nint ", 0, m.start())
+        assert dbg[head + 1:dbg.index("(", head)] in ("int pls_on_device", "int bn254_dbg_plonk_stages_keys"), dbg[head:head + 80]
+    assert not re.search(r"lam_key", body(src, "int bn254_plonk_verify_batch_flags(")) and not re.search(r"lam_key", body(src, "static int plonk_batch("))
     assert "bn254_launch_plonk_stage1(" in body(src, "static int pass_stage1(") and "bn254_launch_plonk_stage1_keys(" in body(src, "static int pass_stage1(")
     # both drivers run that pass, and nothing else in the C ABI launches a stage 1 with a key of its own
     assert "plonk_pass(pvk, " in body(src, "static int plonk_run_device(")

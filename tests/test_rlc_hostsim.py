@@ -3,9 +3,10 @@ instantiate, run by tests/hostsim on plain arrays under the bound tracker, judge
 import ctypes as C
 import hashlib
 import random
-import struct
 
 import pytest
+
+from plonk_stage_ref import chacha_block as _chacha_block
 
 P = 21888242871839275222246405745257275088696311157297823662689037894645226208583
 R = 21888242871839275222246405745257275088548364400416034343698204186575808495617
@@ -13,24 +14,6 @@ R = 2188824287183927522224640574525727508854836440041603434369820418657580849561
 
 def be(v):
     return int(v).to_bytes(32, "big")
-
-
-def _chacha_block(key, counter, nonce):
-    def rotl(x, n):
-        return ((x << n) | (x >> (32 - n))) & 0xffffffff
-
-    def qr(s, a, b, c, d):
-        s[a] = (s[a] + s[b]) & 0xffffffff; s[d] = rotl(s[d] ^ s[a], 16)
-        s[c] = (s[c] + s[d]) & 0xffffffff; s[b] = rotl(s[b] ^ s[c], 12)
-        s[a] = (s[a] + s[b]) & 0xffffffff; s[d] = rotl(s[d] ^ s[a], 8)
-        s[c] = (s[c] + s[d]) & 0xffffffff; s[b] = rotl(s[b] ^ s[c], 7)
-
-    init = [0x61707865, 0x3320646e, 0x79622d32, 0x6b206574] + list(struct.unpack("<8I", key)) + [counter] + list(struct.unpack("<3I", nonce))
-    s = list(init)
-    for _ in range(10):
-        qr(s, 0, 4, 8, 12); qr(s, 1, 5, 9, 13); qr(s, 2, 6, 10, 14); qr(s, 3, 7, 11, 15)
-        qr(s, 0, 5, 10, 15); qr(s, 1, 6, 11, 12); qr(s, 2, 7, 8, 13); qr(s, 3, 4, 9, 14)
-    return [(a + b) & 0xffffffff for a, b in zip(s, init)]
 
 
 def test_chacha20_block_rfc8439(hostsim):
