@@ -587,6 +587,60 @@ int bn254_kzg_verify_folded_batch_device(const void* d_key, const void* d_record
                                          void* hip_stream, unsigned flags);
 int bn254_kzg_fold_reserve(size_t n, size_t n_digests, int device);
 
+/* ---- Batch G1 multi-scalar multiplication with per-item and shared bases ------------------------------------------------------------------------------------------
+ * The G1 work in front of a pairing check, for callers who do not bring a gnark key: the public-input sum IC_0 + sum x_j IC_j of a Groth16 key of one's own (the
+ * restated item of bn254_pairing_check_batch_shared needs it), linear combinations of commitments, Pedersen openings, the EVM's ecAdd and ecMul (EIP-196) in bulk.
+ *
+ *   An ITEM is n_var pairs (point x | y, 64 bytes; scalar, 32 bytes), then n_unit bare points (64 bytes each), then n_shared scalars (32 bytes each): BN254_G1_MSM_ITEM_LEN(v,
+ *   u, s) = 96 v + 64 u + 32 s bytes.  Every field is 32-byte big-endian, an all-zero point is the identity.  The shape (n_var, n_unit, n_shared) is the call's: 0 <= n_var
+ *   <= BN254_G1_MSM_MAX_VAR, 0 <= n_unit <= BN254_G1_MSM_MAX_UNIT, 0 <= n_shared <= BN254_G1_MSM_MAX_SHARED, one term at least; item_stride >= the item length (bytes behind
+ *   the item are ignored).  The limits are the row planner's (csrc/bn254_msm.h: MSM_MAX_FIXED, four unit terms, 32 rows; tests/test_g1_msm_cpu.py walks it over every shape).
+ *   ecAdd is the shape (0, 2, 0), ecMul (1, 0, 0).
+ *
+ *   Result of item i:  S_i = sum_{t < n_var} k_t P_t + sum_{t < n_unit} U_t + sum_{j < n_shared} c_j B_j,  B_j the j-th point of the prepared bases.  out receives 64 bytes
+ *   x | y per item, all-zero for the identity and for an item that ends in an error.  status[i], decided in this order (the order of bn254_kzg_verify_batch):
+ *     1. with BN254_FLAG_STRICT_SCALARS any scalar of the item >= r is BN254_ERR_NOT_MEMBER (without the flag scalars are used modulo r, as EIP-196 defines ecMul);
+ *     2. the points in record order: a coordinate >= p is BN254_ERR_NOT_MEMBER, then a point off the curve BN254_ERR_NOT_ON_CURVE;
+ *     3. BN254_ACCEPT: out holds S_i.
+ *   A failing item does not disturb its neighbours.  Any other flag is BN254_E_BAD_ARG.
+ *
+ *   bn254_g1_bases_prepare takes 1 .. BN254_G1_MSM_MAX_SHARED points (64 bytes each), checks them by rule 2 -- *status is BN254_ACCEPT, or the first failure with *out null
+ *   and return code BN254_OK, as bn254_kzg_key_prepare does -- builds their 13-bit window tables on `device` (about 13 MB per point; the builder of the PlonK keys) and
+ *   returns a handle bound to that device.  The handle is a void* (an opaque owner; bn254_g1_bases_count reads its size, 0 for anything else).  An identity base is
+ *   accepted and its terms contribute nothing.  bn254_g1_bases_free waits for the device the handle belongs to, so work enqueued with the handle has finished.  `bases` may
+ *   be null exactly when n_shared == 0; a call whose device is not the handle's is BN254_E_BAD_ARG.
+ *
+ *   Argument errors are BN254_E_BAD_ARG before any device is touched, out and status untouched: null pointers with n > 0, a shape outside the limits or without a term,
+ *   a stride below the item length, n_shared above the handle's count, unknown flags.  n == 0 returns BN254_OK.  Lack of memory is BN254_E_NOMEM.  The first use of a
+ *   device runs the self-test, as elsewhere; there is no CPU fallback.
+ *   bn254_g1_msm_batch stages passes through pinned memory and returns when out and status are back.  bn254_g1_msm_batch_device only enqueues on hip_stream, and after
+ *   bn254_g1_msm_reserve(n', the same shape, device) with n' >= min(n, the items of a pass) it allocates nothing.
+ *   A PASS holds at most  min(2^18, floor(2^31 / (105 (v + u + s) + 1792 v + 3522)) rounded down to a multiple of 64)  items: per item a term record and flag byte per
+ *   term (105 bytes), 1792 bytes of window-table scratch per variable term, up to 32 rows of 108 bytes and 66 bytes of sum, identity flag and loader status -- 2 GiB per
+ *   pass at most ((1,0,0) and (2,0,0): 2^18 items; (16,0,0): 63 360).  BN254_G1_MSM_PASS in the environment, read once at load time, lowers it (tests; 64 at least).
+ *   Workspace and locking: a per-device workspace of this entry's own -- the buffers of that formula for the largest reservation or call so far, and for the host entry
+ *   pinned and device staging of a pass's items and 65 result bytes per item -- with its own lock and completion event: calls on one device serialise among themselves,
+ *   and with no other entry (the pairing workspace is not used; the host entry borrows the stream of the pairing batch's host entries, so it adds no stream to the process).
+ *   Kernels: k_g1_msm_load (checks, scalars mod r, glv_decompose, term records), k_g1_msm_rows / k_g1_sum_affine (the G1 walk of csrc/bn254_msm.h: variable terms in two-bit
+ *   windows -- split, unsplit or joint by the launch's size -- unit terms one mixed addition, shared terms at most 20 mixed additions from the handle's tables),
+ *   k_g1_msm_store (64 big-endian bytes and the status byte).
+ *   Measured on one MI355X (profiles/r19_g1_msm.txt, tools/bench_g1_msm.py; device-resident valid items, median of 5 calls alternating over the shapes, ms per call at
+ *   4096 | 65 536 | 262 144 items):  (1,0,0) 0.68 | 0.98 | 3.73;  (2,0,0) 0.69 | 1.42 | 5.67;  (8,0,0) 0.83 | 4.52 | 20.7;  (16,0,0) 1.12 | 9.82 | 38.0;  (0,2,0) 0.11 |
+ *   0.12 | 0.34;  (2,1,0) 0.70 | 1.55 | 5.93;  (0,0,2) 0.27 | 0.30 | 1.04;  (0,0,16) 0.83 | 1.61 | 6.35;  (2,1,16) 0.75 | 3.09 | 13.2.  Beside them in the same session:
+ *   bn254_kzg_verify_batch exact minus the pairing alone, which is the (2,1,0) walk behind another loader, 0.70 | 1.56 | 5.39 ms. */
+#define BN254_G1_MSM_MAX_VAR 16
+#define BN254_G1_MSM_MAX_UNIT 4
+#define BN254_G1_MSM_MAX_SHARED 16
+#define BN254_G1_MSM_ITEM_LEN(v, u, s) ((size_t)96 * (size_t)(v) + (size_t)64 * (size_t)(u) + (size_t)32 * (size_t)(s))
+int bn254_g1_bases_prepare(const uint8_t* points, size_t n_bases, int device, void** out, uint8_t* status);
+void bn254_g1_bases_free(void* bases);
+size_t bn254_g1_bases_count(const void* bases);
+int bn254_g1_msm_batch(const uint8_t* items, size_t item_stride, size_t n_var, size_t n_unit, size_t n_shared, const void* bases, size_t n, uint8_t* out, uint8_t* status,
+                       int device, unsigned flags);
+int bn254_g1_msm_batch_device(const void* d_items, size_t item_stride, size_t n_var, size_t n_unit, size_t n_shared, const void* bases, size_t n, void* d_out, void* d_status,
+                              int device, void* hip_stream, unsigned flags);
+int bn254_g1_msm_reserve(size_t n, size_t n_var, size_t n_unit, size_t n_shared, int device);
+
 /* ---- Known-answer self-test of the verdict kernels, per device ----------------------------------------------------------------------------------------------
  * Every verdict comes out of hand-written gfx950 kernels, and the compiler has already produced one wrong build of this code (tools/repro/).  So
  * before a device is first used the library runs the kernels IT SHIPS on THAT device on small built-in inputs and compares every output byte with a known answer.

@@ -517,4 +517,53 @@ inline long kzg_params() { long out[1] = {0}; detail::check(bn254_kzg_params(out
 // {launches that ran the joint check, groups they checked, groups that failed, launches on the exact path}
 inline std::array<uint64_t, 4> kzg_state() { std::array<uint64_t, 4> out{}; detail::check(bn254_kzg_state(out.data())); return out; }
 
+// ---- batch G1 multi-scalar multiplication with per-item and shared bases (bn254_g1_bases_prepare, bn254_g1_msm_batch) ----
+// An item is n_var pairs (point x | y, scalar), n_unit points, n_shared scalars for the shared bases: BN254_G1_MSM_ITEM_LEN(n_var, n_unit, n_shared) bytes, 32-byte
+// big-endian fields.  G1Bases owns the window tables of 1 .. BN254_G1_MSM_MAX_SHARED points on one device: prepare throws Panic with the first failure over the points;
+// the destructor waits for the device and frees them.  msm_batch: per item the 64 bytes of sum k_t P_t + sum U_t + sum c_j B_j (zero: the identity, or an item that
+// ended in an error) and status[i], BN254_ACCEPT or the loader error.  flags: BN254_FLAG_STRICT_SCALARS
+inline size_t g1_msm_item_len(size_t n_var, size_t n_unit, size_t n_shared) { return BN254_G1_MSM_ITEM_LEN(n_var, n_unit, n_shared); }
+class G1Bases {
+ public:
+  static G1Bases prepare(const Bytes& points, int device = 0) {
+    if (points.empty() || points.size() % 64 || points.size() / 64 > (size_t)BN254_G1_MSM_MAX_SHARED) throw std::invalid_argument("G1Bases::prepare: 1 .. BN254_G1_MSM_MAX_SHARED points of 64 bytes");
+    G1Bases b;
+    uint8_t st = 0;
+    detail::check(bn254_g1_bases_prepare(points.data(), points.size() / 64, device, &b.h_, &st));
+    if (st != BN254_ACCEPT || !b.h_) throw Panic(st);
+    b.device_ = device;
+    return b;
+  }
+  G1Bases(G1Bases&& o) noexcept : h_(o.h_), device_(o.device_) { o.h_ = nullptr; }
+  G1Bases& operator=(G1Bases&& o) noexcept { if (this != &o) { bn254_g1_bases_free(h_); h_ = o.h_; device_ = o.device_; o.h_ = nullptr; } return *this; }
+  G1Bases(const G1Bases&) = delete;
+  G1Bases& operator=(const G1Bases&) = delete;
+  ~G1Bases() { bn254_g1_bases_free(h_); }
+  const void* handle() const { return h_; }      // for a caller that keeps the items on the device (bn254_g1_msm_batch_device)
+  size_t size() const { return bn254_g1_bases_count(h_); }
+  int device() const { return device_; }
+
+ private:
+  G1Bases() = default;
+  void* h_ = nullptr; int device_ = 0;
+};
+struct G1MsmResult { Bytes out; std::vector<uint8_t> status; };      // 64 bytes x | y and a status byte per item
+inline G1MsmResult g1_msm_batch(const Bytes& items, size_t n, size_t n_var, size_t n_unit, size_t n_shared, const G1Bases* bases = nullptr, int device = 0, unsigned flags = 0,
+                                size_t stride = 0) {
+  const size_t len = g1_msm_item_len(n_var, n_unit, n_shared), s = stride ? stride : len;
+  if (n && (s < len || items.size() < (n - 1) * s + len)) throw std::invalid_argument("g1_msm_batch: the buffer is shorter than n items");
+  G1MsmResult r;
+  r.out.resize(64 * n); r.status.resize(n);
+  detail::check(bn254_g1_msm_batch(items.data(), s, n_var, n_unit, n_shared, bases ? bases->handle() : nullptr, n, r.out.data(), r.status.data(), device, flags));
+  return r;
+}
+// enqueues on hip_stream and returns: d_out receives 64 n bytes, d_status n
+inline void g1_msm_batch_device(const void* d_items, size_t n, size_t n_var, size_t n_unit, size_t n_shared, const G1Bases* bases, void* d_out, void* d_status, int device = 0,
+                                void* hip_stream = nullptr, unsigned flags = 0, size_t stride = 0) {
+  detail::check(bn254_g1_msm_batch_device(d_items, stride ? stride : g1_msm_item_len(n_var, n_unit, n_shared), n_var, n_unit, n_shared, bases ? bases->handle() : nullptr, n, d_out,
+                                          d_status, device, hip_stream, flags));
+}
+// makes `device` ready for batches of n items of this shape: a later g1_msm_batch_device of up to n such items only enqueues
+inline void g1_msm_reserve(size_t n, size_t n_var, size_t n_unit, size_t n_shared, int device = 0) { detail::check(bn254_g1_msm_reserve(n, n_var, n_unit, n_shared, device)); }
+
 }  // namespace snark_bn254_verifier

@@ -411,6 +411,65 @@ pub fn kzg_state() -> Result<(u64, u64, u64, u64), Error> {
     Ok((out[0], out[1], out[2], out[3]))
 }
 
+/// The most variable, unit and shared terms of a `g1_msm_batch` item.
+pub const G1_MSM_MAX_VAR: usize = sys::BN254_G1_MSM_MAX_VAR as usize;
+pub const G1_MSM_MAX_UNIT: usize = sys::BN254_G1_MSM_MAX_UNIT as usize;
+pub const G1_MSM_MAX_SHARED: usize = sys::BN254_G1_MSM_MAX_SHARED as usize;
+/// Bytes of an item: `n_var` pairs (point `x | y`, scalar), `n_unit` points, `n_shared` scalars, 32-byte big-endian fields (`BN254_G1_MSM_ITEM_LEN`).
+pub const fn g1_msm_item_len(n_var: usize, n_unit: usize, n_shared: usize) -> usize { 96 * n_var + 64 * n_unit + 32 * n_shared }
+/// The shared bases of `g1_msm_batch` on one device (`bn254_g1_bases_prepare`): their window tables live in device memory until the value is dropped, which waits
+/// for the device first.
+pub struct G1Bases { handle: *mut core::ffi::c_void, device: i32 }
+unsafe impl Send for G1Bases {}
+unsafe impl Sync for G1Bases {}
+impl G1Bases {
+    /// `Ok(bases)` from 1 ..= `G1_MSM_MAX_SHARED` points of 64 bytes, or the first failure over the points as the inner error.
+    pub fn prepare(points: &[u8], device: i32) -> Result<Result<G1Bases, Status>, Error> {
+        if points.is_empty() || points.len() % 64 != 0 || points.len() / 64 > G1_MSM_MAX_SHARED {
+            return Err(Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "G1Bases::prepare: 1 ..= G1_MSM_MAX_SHARED points of 64 bytes".into() });
+        }
+        let mut handle: *mut core::ffi::c_void = core::ptr::null_mut();
+        let mut st = 0u8;
+        check(unsafe { sys::bn254_g1_bases_prepare(points.as_ptr(), points.len() / 64, device as c_int, &mut handle, &mut st) })?;
+        Ok(if st == sys::BN254_ACCEPT && !handle.is_null() { Ok(G1Bases { handle, device }) } else { Err(Status::from(st)) })
+    }
+    /// The number of points (`bn254_g1_bases_count`).
+    pub fn len(&self) -> usize { unsafe { sys::bn254_g1_bases_count(self.handle) } }
+    pub fn is_empty(&self) -> bool { self.len() == 0 }
+    /// The device the tables live on.
+    pub fn device(&self) -> i32 { self.device }
+}
+impl Drop for G1Bases {
+    fn drop(&mut self) { unsafe { sys::bn254_g1_bases_free(self.handle) } }
+}
+/// Batch G1 multi-scalar multiplication (`bn254_g1_msm_batch`): per item `sum k_t P_t + sum U_t + sum c_j B_j` as 64 bytes `x | y` (zero: the identity, or an item
+/// that ended in an error) and its status (`Accept`, or the loader error).  `bases` is needed exactly when `n_shared > 0`.  `flags`: `FLAG_STRICT_SCALARS`.
+pub fn g1_msm_batch(items: &[u8], stride: usize, n_var: usize, n_unit: usize, n_shared: usize, bases: Option<&G1Bases>, n: usize, device: i32, flags: u32) -> Result<(Vec<u8>, Vec<Status>), Error> {
+    let short = Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "g1_msm_batch: a shape within the limits with a term, stride at least g1_msm_item_len(n_var, n_unit, n_shared) and a buffer of n items of stride bytes".into() };
+    if n_var > G1_MSM_MAX_VAR || n_unit > G1_MSM_MAX_UNIT || n_shared > G1_MSM_MAX_SHARED || n_var + n_unit + n_shared == 0 { return Err(short); }
+    let len = g1_msm_item_len(n_var, n_unit, n_shared);
+    if stride < len { return Err(short); }
+    if n > 0 && (n - 1).checked_mul(stride).and_then(|b| b.checked_add(len)).map_or(true, |b| items.len() < b) { return Err(short); }
+    let mut out = vec![0u8; 64 * n];
+    let mut status = vec![0u8; n];
+    let handle = bases.map_or(core::ptr::null(), |b| b.handle as *const core::ffi::c_void);
+    check(unsafe { sys::bn254_g1_msm_batch(items.as_ptr(), stride, n_var, n_unit, n_shared, handle, n, out.as_mut_ptr(), status.as_mut_ptr(), device as c_int, flags as core::ffi::c_uint) })?;
+    Ok((out, status.into_iter().map(Status::from).collect()))
+}
+/// `bn254_g1_msm_batch_device` on device pointers: enqueues on `hip_stream` and returns; `d_out` receives 64 n bytes, `d_status` n.
+///
+/// # Safety
+/// The pointers must be device memory of the sizes the call implies and stay valid until the stream has run the work.
+pub unsafe fn g1_msm_batch_device(d_items: *const core::ffi::c_void, stride: usize, n_var: usize, n_unit: usize, n_shared: usize, bases: Option<&G1Bases>, n: usize,
+                                  d_out: *mut core::ffi::c_void, d_status: *mut core::ffi::c_void, device: i32, hip_stream: *mut core::ffi::c_void, flags: u32) -> Result<(), Error> {
+    let handle = bases.map_or(core::ptr::null(), |b| b.handle as *const core::ffi::c_void);
+    check(sys::bn254_g1_msm_batch_device(d_items, stride, n_var, n_unit, n_shared, handle, n, d_out, d_status, device as c_int, hip_stream, flags as core::ffi::c_uint))
+}
+/// Makes `device` ready for batches of `n` items of a shape: a later `g1_msm_batch_device` of up to `n` such items only enqueues (`bn254_g1_msm_reserve`).
+pub fn g1_msm_reserve(n: usize, n_var: usize, n_unit: usize, n_shared: usize, device: i32) -> Result<(), Error> {
+    check(unsafe { sys::bn254_g1_msm_reserve(n, n_var, n_unit, n_shared, device as c_int) })
+}
+
 /// The library this crate was generated for?  (`bn254_abi_version`: bumped whenever a function changes its arguments, an array its length or a slot its meaning.)
 pub fn abi_matches() -> bool { unsafe { sys::bn254_abi_version() == sys::BN254_ABI_VERSION } }
 

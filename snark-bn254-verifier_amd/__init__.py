@@ -19,4 +19,6 @@ from .binding import (  # noqa: F401
     PAIRING_G1_LEN,
     kzg_key_prepare, kzg_verify_batch, kzg_verify_batch_device, kzg_reserve, set_kzg_params, kzg_params, kzg_state, dbg_kzg_fold, KZG_OPENING_LEN, KZG_KEY_LEN,
     kzg_verify_folded_batch, kzg_verify_folded_batch_device, kzg_fold_reserve, dbg_kzg_fold_proof, dbg_kzg_fold_plan, kzg_fold_len, KZG_FOLD_MAX_DIGESTS, KZG_FOLD_MAX_DATA,
+    g1_bases_prepare, G1Bases, g1_msm_batch, g1_msm_batch_device, g1_msm_reserve, g1_msm_item_len, dbg_g1_msm_batch, dbg_g1_msm_batch_plan, dbg_g1_msm_batch_state,
+    G1_MSM_MAX_VAR, G1_MSM_MAX_UNIT, G1_MSM_MAX_SHARED,
 )

@@ -1304,3 +1304,134 @@ def dbg_kzg_fold_plan(n_digests, weighted, n, lane_budget=0, joint_g=-1):
     fn.argtypes = [C.c_size_t, C.c_int, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
     rows = C.c_int(0)
     return int(rows.value) if fn(n_digests, 1 if weighted else 0, n, lane_budget, joint_g, C.byref(rows)) == 0 else None
+
+
+# ---- batch G1 multi-scalar multiplication with per-item and shared bases (bn254_g1_bases_prepare, bn254_g1_msm_batch, include/bn254_verify.h) ----
+G1_MSM_MAX_VAR = 16
+G1_MSM_MAX_UNIT = 4
+G1_MSM_MAX_SHARED = 16
+
+
+def g1_msm_item_len(n_var, n_unit, n_shared):
+    """BN254_G1_MSM_ITEM_LEN: n_var pairs (point 64, scalar 32), n_unit points (64), n_shared scalars (32)."""
+    return 96 * n_var + 64 * n_unit + 32 * n_shared
+
+
+class G1Bases:
+    """Owner of a bn254_g1_bases_prepare handle: the window tables of up to G1_MSM_MAX_SHARED points on one device.  close() (or the end of a `with`) frees them after
+    waiting for the device."""
+
+    def __init__(self, handle, device):
+        self._h, self.device = handle, device
+
+    @property
+    def handle(self):
+        if not self._h:
+            raise Bn254Error("G1Bases: the handle has been freed")
+        return self._h
+
+    def __len__(self):
+        fn = lib().bn254_g1_bases_count
+        fn.argtypes = [C.c_void_p]; fn.restype = C.c_size_t
+        return int(fn(self.handle))
+
+    def close(self):
+        if self._h:
+            fn = lib().bn254_g1_bases_free
+            fn.argtypes = [C.c_void_p]; fn.restype = None
+            fn(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def g1_bases_prepare(points, device=0):
+    """(status, G1Bases or None): the shared bases of g1_msm_batch from 1 .. G1_MSM_MAX_SHARED points of 64 bytes; status is ACCEPT, or the first failure (a coordinate
+    >= p: ERR_NOT_MEMBER, off the curve: ERR_NOT_ON_CURVE) and no handle  (bn254_g1_bases_prepare)."""
+    points = bytes(points)
+    if len(points) % 64:
+        raise Bn254Error("g1_bases_prepare: points of 64 bytes expected")
+    fn = lib().bn254_g1_bases_prepare
+    fn.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
+    h = C.c_void_p(None); st = C.c_uint8(0xEE)
+    _check(fn(points, len(points) // 64, device, C.byref(h), C.byref(st)))
+    return st.value, (G1Bases(h.value, device) if st.value == ACCEPT and h.value else None)
+
+
+def _g1_msm_shape(items, n_var, n_unit, n_shared, n, stride):
+    items = bytes(items)
+    ilen = g1_msm_item_len(n_var, n_unit, n_shared)
+    if stride is None:
+        stride = ilen
+    if n is None:
+        n = len(items) // stride if stride else 0
+    if n and stride >= ilen and len(items) < (n - 1) * stride + ilen:
+        raise Bn254Error("G1 MSM batch: the buffer is shorter than n items")
+    return items, n, stride
+
+
+def g1_msm_batch(items, n_var, n_unit, n_shared, bases=None, n=None, stride=None, device=0, flags=0):
+    """(out, status): per item the 64 bytes x | y of  sum k_t P_t + sum U_t + sum c_j B_j  (zero: the identity, or an item that ended in an error) and its status byte
+    (ACCEPT, or the loader error).  bases: a G1Bases (n_shared > 0).  flags: FLAG_STRICT_SCALARS  (bn254_g1_msm_batch)."""
+    fn = lib().bn254_g1_msm_batch
+    fn.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_uint]
+    items, n, stride = _g1_msm_shape(items, n_var, n_unit, n_shared, n, stride)
+    out = (C.c_uint8 * max(64 * n, 1))(); status = (C.c_uint8 * max(n, 1))()
+    _check(fn(items, stride, n_var, n_unit, n_shared, bases.handle if bases is not None else None, n, out, status, device, flags))
+    return bytes(out)[:64 * n], bytes(status)[:n]
+
+
+def g1_msm_batch_device(d_items, n_var, n_unit, n_shared, n, d_out, d_status, bases=None, stride=None, device=0, stream=0, flags=0):
+    """bn254_g1_msm_batch_device on device pointers (ints): enqueues on `stream` and returns; d_out receives 64 n bytes, d_status n."""
+    fn = lib().bn254_g1_msm_batch_device
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+    _check(fn(d_items, g1_msm_item_len(n_var, n_unit, n_shared) if stride is None else stride, n_var, n_unit, n_shared, bases.handle if bases is not None else None, n, d_out,
+              d_status, device, stream, flags))
+
+
+def g1_msm_reserve(n, n_var, n_unit, n_shared, device=0):
+    """Makes `device` ready for batches of n items of this shape: a later g1_msm_batch_device of up to n such items only enqueues  (bn254_g1_msm_reserve)."""
+    fn = lib().bn254_g1_msm_reserve
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    _check(fn(n, n_var, n_unit, n_shared, device))
+
+
+def dbg_g1_msm_batch(items, n_var, n_unit, n_shared, base_points=b"", n=None, stride=None, flags=0, lane_budget=0, joint_g=-1, device=-1):
+    """bn254_dbg_g1_msm_batch, one pass with the plan's form forced: {"out": n x 64 bytes, "status": n bytes, "rows", "var_rows", "form": "split" | "unsplit" | "joint",
+    "chain"}.  base_points: the shared bases as raw 64-byte points.  device -1 is the host compile, no GPU needed."""
+    fn = lib().bn254_dbg_g1_msm_batch
+    fn.argtypes = [C.c_char_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p,
+                   C.POINTER(C.c_int), C.c_int]
+    items, n, stride = _g1_msm_shape(items, n_var, n_unit, n_shared, n, stride)
+    base_points = bytes(base_points)
+    out = (C.c_uint8 * max(64 * n, 1))(); status = (C.c_uint8 * max(n, 1))(); info = (C.c_int * 6)()
+    _check(fn(items, stride, n_var, n_unit, n_shared, base_points or None, len(base_points) // 64, n, flags, lane_budget, joint_g, out, status, info, device))
+    return {"out": bytes(out)[:64 * n], "status": bytes(status)[:n], "rows": info[0], "var_rows": info[1], "form": ("split", "unsplit", "joint")[info[4]], "chain": info[5]}
+
+
+def dbg_g1_msm_batch_plan(n_var, n_unit, n_shared, n, lane_budget=0, joint_g=-1):
+    """rows of the G1 walk of n items of a shape, or None when the shape does not plan  (bn254_dbg_g1_msm_batch_plan; host only)."""
+    fn = lib().bn254_dbg_g1_msm_batch_plan
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int)]
+    rows = C.c_int(0)
+    return int(rows.value) if fn(n_var, n_unit, n_shared, n, lane_budget, joint_g, C.byref(rows)) == 0 else None
+
+
+def dbg_g1_msm_batch_state(n_var, n_unit, n_shared):
+    """{"pass_items": items of a pass of the shape (BN254_G1_MSM_PASS applied), "formula_items", "bytes_per_item", "allocs": device and pinned allocations the entry has
+    made so far}  (bn254_dbg_g1_msm_batch_state; host only)."""
+    fn = lib().bn254_dbg_g1_msm_batch_state
+    fn.argtypes = [C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    _check(fn(n_var, n_unit, n_shared, out))
+    return {"pass_items": int(out[0]), "formula_items": int(out[1]), "bytes_per_item": int(out[2]), "allocs": int(out[3])}

@@ -59,15 +59,16 @@ inline G16Form g16_launch_form(size_t n, size_t n_public, bool inputs_match_key,
 // is there at all).  What a value means is each launcher's own rule: the one-line functions below, side by side.  bn254_dbg_launch_knobs shows them as the process
 // sees them.
 #define G16_MILLER_STEPS 88   // BN_ATE_STEPS (bn254_constants.h; static_asserted in bn254_kernels.hip)
-struct LaunchKnobs { bool set_coop, set_run_steps, set_coop_fixed_max, set_wide_per; int coop, run_steps, wide_per; long coop_fixed_max; bool set_kzg_rlc_min; long kzg_rlc_min; };
+struct LaunchKnobs { bool set_coop, set_run_steps, set_coop_fixed_max, set_wide_per; int coop, run_steps, wide_per; long coop_fixed_max; bool set_kzg_rlc_min; long kzg_rlc_min; bool set_g1_msm_pass; long g1_msm_pass; };
 inline const LaunchKnobs& launch_knobs() {
   static const LaunchKnobs knobs = [] {
-    LaunchKnobs k = {false, false, false, false, 0, 0, 0, 0, false, 0};
+    LaunchKnobs k = {false, false, false, false, 0, 0, 0, 0, false, 0, false, 0};
     if (const char* e = getenv("BN254_COOP")) { k.set_coop = true; k.coop = atoi(e); }
     if (const char* e = getenv("BN254_MILLER_RUN_STEPS")) { k.set_run_steps = true; k.run_steps = atoi(e); }
     if (const char* e = getenv("BN254_COOP_FIXED_MAX")) { k.set_coop_fixed_max = true; k.coop_fixed_max = atol(e); }
     if (const char* e = getenv("BN254_WIDE_PER")) { k.set_wide_per = true; k.wide_per = atoi(e); }
     if (const char* e = getenv("BN254_KZG_RLC_MIN")) { k.set_kzg_rlc_min = true; k.kzg_rlc_min = atol(e); }
+    if (const char* e = getenv("BN254_G1_MSM_PASS")) { k.set_g1_msm_pass = true; k.g1_msm_pass = atol(e); }
     return k;
   }();
   return knobs;
@@ -92,6 +93,8 @@ inline size_t knob_coop_fixed_max() { const LaunchKnobs& k = launch_knobs(); ret
 inline int knob_wide_per() { const LaunchKnobs& k = launch_knobs(); return k.set_wide_per && k.wide_per >= G16_WIDE_MSM_INPUTS_PER_LANE && k.wide_per <= 256 ? k.wide_per : 0; }
 // BN254_KZG_RLC_MIN: the initial value of bn254_set_kzg_params (bn254_capi_kzg.hip clamps it); -1: not set
 inline long knob_kzg_rlc_min() { const LaunchKnobs& k = launch_knobs(); return k.set_kzg_rlc_min && k.kzg_rlc_min >= 0 ? k.kzg_rlc_min : -1; }
+// BN254_G1_MSM_PASS (tests): lowers the items per pass of bn254_g1_msm_batch, 64 at least (bn254_capi_g1msm.hip); 0: not set
+inline size_t knob_g1_msm_pass() { const LaunchKnobs& k = launch_knobs(); return !k.set_g1_msm_pass ? 0 : k.g1_msm_pass < 64 ? (size_t)64 : (size_t)k.g1_msm_pass; }
 
 // ---- compaction of a lane launch (k_g16_classify / k_g16_compact_write, bn254_k_g16_load.hip) ----------------------------------------------
 // A proof the loader decides for good (a coordinate >= p, A or B off the curve) would still ride its wavefront through the Miller loop and the final
