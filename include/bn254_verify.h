@@ -847,6 +847,35 @@ int bn254_dbg_verdict(int form, const void* a, const void* b, const uint8_t targ
 int bn254_dbg_coop12_miller_fixed(const bn254_g16_pvk* pvk, int n_pairs, const uint8_t* g1_0, const uint8_t* g1_1, const uint8_t* identity, uint8_t* out_gt, size_t n, int device);
 int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_public, size_t n, uint8_t* out_gt, uint8_t* out_status,
                                 int device);
+/* The Groth16 loader stage by value: what a batch's launches leave in the workspace BEFORE the pairing -- A, B, C as parsed and L = K_0 + sum x_j K_j -- through
+ * the product's own launcher of the stage (csrc/bn254_kernels.hip, bn254_launch_g16_loader: k_g16_classify / k_g16_compact_write, k_g16_prepare, k_g16_check_scalars,
+ * and for a key with more than 16 inputs the digit, partial-sum and reduction launches).  Every argument is checked on the host before a device is looked at
+ * (BN254_E_BAD_ARG); n is at most 32 768.
+ * bn254_dbg_g16_loader: n raw 256-byte records at proof_stride and n rows of n_public inputs under one prepared key.
+ *    flags       0 or BN254_FLAG_STRICT_SCALARS
+ *    form        what the sizes and knobs would otherwise decide: 0 the lane form, L by the whole k_g16_prepare; 1 the same on compacted slots; 2 wide, the chunk sums
+ *                added by k_g16_msm_reduce; 3 wide, by k_g16_msm_reduce8.  A combination no launch of the product takes is refused: forms 0 / 1 with a key of more
+ *                than 16 inputs and its own input count, forms 2 / 3 with any other key or count, form 1 under BN254_FLAG_STRICT_SCALARS, form 3 with fewer than 16
+ *                chunk sums per proof.  (Form 2 at 16 chunks and more is what the product launches above 65 536 proofs.)  Comb or byte-window tables: as the key was
+ *                prepared.
+ *    misalign    0 .. 3: the device copy of the input rows starts that many bytes past a 4-byte boundary (the kernels' byte-wise load branch)
+ *    out_status  n bytes, the caller's status buffer as the stage leaves it: per proof a final loader status, or BN254 internal PENDING (0x80) | 0x40 when L is the
+ *                identity | the deferred status of C.  Form 1: what k_g16_classify left (final, or 0x80), and the slots' bytes in out_slot_status
+ *    out_slot_status, out_slot_proof   form 1 only (else unused, may be null): n slot status bytes (0 past the pending proofs) and n slot -> proof words
+ *    out_points  n x 320 bytes, per proof (form 1: per slot) A (64) | B (128: x.c1 x.c0 y.c1 y.c0) | C (64) | L (64; (0, 1) for the identity), canonical big-endian
+ *                values of the workspace elements; meaningful where the status byte is pending
+ *    info        what the launcher recorded at its launch sites as it enqueued them (not the request echoed): {form that ran (0 .. 3 as above; -1: none of them),
+ *                chunk sums per proof (0: not wide), reduction kernel (0 none, 1 k_g16_msm_reduce, 2 k_g16_msm_reduce8), partial-sum kernel (0 none: L by
+ *                k_g16_prepare's 13-bit windows, 1 k_g16_msm_partial_comb, 2 k_g16_msm_partial), k_g16_check_scalars launched, k_g16_comb_digits launched}
+ * bn254_dbg_g16_loader_keys: the same stage of a batch over a key list in its grouped form (the grouping launches, then k_g16_prepare_keys and under the strict
+ *    flag k_g16_check_scalars_keys over all slots as one launch part); arguments as bn254_groth16_verify_batch_keys.  Per slot: out_slot_proof (all ones in a padding
+ *    slot), out_slot_status (0 there), out_points as above; the arrays hold max_slots entries (the batch's slots: every key's count rounded up to 64), *out_n_slots
+ *    receives the count the device found. */
+int bn254_dbg_g16_loader(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n, unsigned flags, int form,
+                         int misalign, uint8_t* out_status, uint8_t* out_slot_status, unsigned* out_slot_proof, uint8_t* out_points, int info[6], int device);
+int bn254_dbg_g16_loader_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                              size_t input_stride, size_t n, unsigned flags, int misalign, size_t max_slots, unsigned* out_slot_proof, uint8_t* out_slot_status, uint8_t* out_points,
+                              size_t* out_n_slots, int device);
 /* The G1 layer of the PlonK path by value (csrc/bn254_k_msm.hip), through the product's own launchers; layouts are converted on the host.  Every argument is checked
  * before anything is launched (BN254_E_BAD_ARG: null pointers, indices outside their lists, n = 0 or above the probe's cap, more rows than MSM_MAX_ROWS = 32, coordinates
  * that are not canonical, digits outside the contract), and before the device is looked at.  Points are 64 bytes x | y big-endian; the identity never travels as bytes.

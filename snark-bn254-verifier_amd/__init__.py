@@ -21,4 +21,5 @@ from .binding import (  # noqa: F401
     kzg_verify_folded_batch, kzg_verify_folded_batch_device, kzg_fold_reserve, dbg_kzg_fold_proof, dbg_kzg_fold_plan, kzg_fold_len, KZG_FOLD_MAX_DIGESTS, KZG_FOLD_MAX_DATA,
     g1_bases_prepare, G1Bases, g1_msm_batch, g1_msm_batch_device, g1_msm_reserve, g1_msm_item_len, dbg_g1_msm_batch, dbg_g1_msm_batch_plan, dbg_g1_msm_batch_state,
     G1_MSM_MAX_VAR, G1_MSM_MAX_UNIT, G1_MSM_MAX_SHARED,
+    dbg_g16_loader, dbg_g16_loader_keys, G16_LOADER_LANES, G16_LOADER_COMPACT, G16_LOADER_WIDE, G16_LOADER_WIDE8, G16_LOADER_POINTS_LEN,
 )

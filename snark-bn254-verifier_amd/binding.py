@@ -1435,3 +1435,50 @@ def dbg_g1_msm_batch_state(n_var, n_unit, n_shared):
     out = (C.c_uint64 * 4)()
     _check(fn(n_var, n_unit, n_shared, out))
     return {"pass_items": int(out[0]), "formula_items": int(out[1]), "bytes_per_item": int(out[2]), "allocs": int(out[3])}
+
+
+G16_LOADER_LANES, G16_LOADER_COMPACT, G16_LOADER_WIDE, G16_LOADER_WIDE8 = range(4)      # form of dbg_g16_loader
+G16_LOADER_POINTS_LEN = 320                                                              # A (64) | B (128) | C (64) | L (64)
+
+
+def _loader_args():
+    return [C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+            C.POINTER(C.c_int), C.c_int]
+
+
+def dbg_g16_loader(key, proofs, public_inputs, n_public, n, form, flags=0, misalign=0, proof_stride=256, device=0):
+    """The loader stage of a Groth16 batch under one prepared key, in a forced form (bn254_dbg_g16_loader): {"status": n bytes as the stage leaves them, "points": n
+    records A | B | C | L of 320 bytes (per slot when form is G16_LOADER_COMPACT), "slot_status" / "slot_proof" (compaction only), "form", "chunks", "reduce": None |
+    "k_g16_msm_reduce" | "k_g16_msm_reduce8", "tables": "comb" | "bytes" | "fw13" (the sum's kernel), "check_scalars", "comb_digits"} -- the last six as the launcher
+    recorded them at its launch sites."""
+    fn = lib().bn254_dbg_g16_loader
+    fn.argtypes = _loader_args()
+    st = (C.c_uint8 * n)(); sst = (C.c_uint8 * n)(); sp = (C.c_uint32 * n)(); pts = (C.c_uint8 * (G16_LOADER_POINTS_LEN * n))(); info = (C.c_int * 6)()
+    compact = form == G16_LOADER_COMPACT
+    _check(fn(key.handle, bytes(proofs), proof_stride, bytes(public_inputs) or None, n_public, n, flags, form, misalign, st, sst if compact else None, sp if compact else None, pts,
+              info, device))
+    pts = bytes(pts)
+    return {"status": bytes(st), "points": [pts[G16_LOADER_POINTS_LEN * i:G16_LOADER_POINTS_LEN * (i + 1)] for i in range(n)],
+            "slot_status": bytes(sst) if compact else None, "slot_proof": list(sp) if compact else None, "form": info[0], "chunks": info[1],
+            "reduce": (None, "k_g16_msm_reduce", "k_g16_msm_reduce8")[info[2]], "tables": ("fw13", "comb", "bytes")[info[3]], "check_scalars": bool(info[4]),
+            "comb_digits": bool(info[5])}
+
+
+def dbg_g16_loader_keys(key_set, key_index, proofs, public_inputs, n=None, flags=0, misalign=0, proof_stride=256, input_stride=None, device=0):
+    """The loader stage of a batch over a KeySet in its grouped form (bn254_dbg_g16_loader_keys): {"n_slots", "slot_proof": per slot the proof index or None for a
+    padding slot, "slot_status": bytes, "points": per slot A | B | C | L}."""
+    fn = lib().bn254_dbg_g16_loader_keys
+    fn.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p,
+                   C.POINTER(C.c_size_t), C.c_int]
+    idx = key_set._index(key_index)
+    n = len(idx) if n is None else n
+    counts = {}
+    for k in idx:
+        counts[k] = counts.get(k, 0) + 1
+    slots = sum((c + 63) // 64 * 64 for c in counts.values())
+    sp = (C.c_uint32 * max(slots, 1))(); sst = (C.c_uint8 * max(slots, 1))(); pts = (C.c_uint8 * max(G16_LOADER_POINTS_LEN * slots, 1))(); ns = C.c_size_t(0)
+    _check(fn(key_set._arr, len(key_set.keys), idx.buffer_info()[0] if len(idx) else None, bytes(proofs), proof_stride, bytes(public_inputs) or None,
+              key_set.input_stride if input_stride is None else input_stride, n, flags, misalign, slots, sp, sst, pts, C.byref(ns), device))
+    pts = bytes(pts)
+    return {"n_slots": int(ns.value), "slot_proof": [None if v == 0xffffffff else int(v) for v in sp][:slots], "slot_status": bytes(sst)[:slots],
+            "points": [pts[G16_LOADER_POINTS_LEN * i:G16_LOADER_POINTS_LEN * (i + 1)] for i in range(slots)]}

@@ -352,6 +352,9 @@ int bn254_selftest_device(int, const std::vector<uint8_t>*, const bn254st::HostS
 #include "bn254_capi_keys.hip"
 #else
 void keys_sets_drop(const bn254_g16_pvk*) {}
+// .. and, without the key-set file, nothing the loader probe over a key list could run on
+int g16_keys_probe_loader(const bn254_g16_pvk* const*, size_t, const unsigned*, const uint8_t*, size_t, const uint8_t*, size_t, size_t, unsigned, int, size_t, unsigned*, uint8_t*, uint8_t*, size_t*,
+                          int, void (*)(const uint8_t*, size_t, uint8_t*)) { return set_err(BN254_E_NO_DEVICE, "no key sets in this build"); }
 #endif
 // PlonK batches over many keys: tests/hostsan/hostsan_plonk_keys.cpp brings the file (after this one) and stand-ins for its launchers; every other harness only needs
 // the hook of bn254_plonk_vk_free
@@ -381,6 +384,7 @@ hipError_t bn254_launch_g16_keys_direct(const G16KeysDirectArgs&, hipStream_t) {
 #endif
 #if defined(BN254_HOSTSAN_KEYS)
 hipError_t bn254_coop12_prepare() { return hipSuccess; }      // the step-kind table of the cooperative kernels: nothing to create without a device compiler
+void bn254_launch_g16_prepare_keys(const G16KeysLaunchArgs&, unsigned, hipStream_t) {}      // the loader probe over a key list (g16_keys_probe_loader): no kernels in a host build
 #endif
 // the launchers of the value-level probes (bn254_capi_dbg.hip: bn254_dbg_coop12_op, bn254_dbg_verdict, ..): no kernels in a host build, so the probes there check
 // their arguments, move their buffers and return what those held; every harness links these, whichever stand-ins it brings for the launchers of the product
@@ -389,6 +393,7 @@ hipError_t bn254_launch_dbg_load(int32_t*, size_t, uint8_t*, int, const void*, i
 hipError_t bn254_launch_dbg_store(int32_t*, size_t, int, void*, int, hipStream_t) { return hipSuccess; }
 hipError_t bn254_launch_dbg_verdict(int, int32_t*, size_t, uint8_t*, const int32_t*, hipStream_t) { return hipSuccess; }
 hipError_t bn254_launch_dbg_coop12_g16(const G16LaunchArgs&, hipStream_t) { return hipSuccess; }
+void bn254_launch_g16_loader(const G16LaunchArgs&, const G16LoaderForm&, hipStream_t, G16Prof*, G16LoaderRan*) {}
 hipError_t bn254_coop12_dbg_op(int32_t*, uint8_t*, size_t, int, int, const int32_t*, hipStream_t) { return hipSuccess; }
 hipError_t bn254_coop12_miller_fixed_keys(int32_t*, uint8_t*, size_t, const uint32_t*, uint32_t, const bn254::PlonkKeyDesc*, uint32_t, const int32_t*, int, hipStream_t) { return hipSuccess; }
 hipError_t bn254_coop12_miller_fixed(int32_t*, uint8_t*, size_t, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) { return hipSuccess; }

@@ -676,6 +676,115 @@ int bn254_dbg_coop12_miller_g16(const bn254_g16_pvk* pvk, const uint8_t* proofs,
   probe_ws_free();
   return rc;
 }
+// ---- the Groth16 loader stage by value (include/bn254_verify.h: bn254_dbg_g16_loader, bn254_dbg_g16_loader_keys) ----------------------------------------------------
+// What the stage left in the workspace, read through k_dbg_store from VE_AX on: twelve elements in the store's order -- (AX, AY), B.y, (LX, LY), B.x, (CX, CY), two
+// more -- turned into the 320 bytes A | B (x.c1 x.c0 y.c1 y.c0, as a record holds it) | C | L of every item
+#define G16_LOADER_PROBE_MAX 32768
+static void g16_loader_points(const uint8_t* stored, size_t m, uint8_t* out) {
+  for (size_t i = 0; i < m; i++) {
+    const uint8_t* p = stored + 384 * i;
+    uint8_t* o = out + 320 * i;
+    memcpy(o, p, 64);                                                   // A
+    memcpy(o + 64, p + 192 + 32, 32); memcpy(o + 96, p + 192, 32);      // B.x: c1, c0
+    memcpy(o + 128, p + 64 + 32, 32); memcpy(o + 160, p + 64, 32);      // B.y: c1, c0
+    memcpy(o + 192, p + 256, 64);                                       // C
+    memcpy(o + 256, p + 128, 64);                                       // L
+  }
+}
+int bn254_dbg_g16_loader(const bn254_g16_pvk* pvk, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs, size_t n_public, size_t n, unsigned flags, int form,
+                         int misalign, uint8_t* out_status, uint8_t* out_slot_status, unsigned* out_slot_proof, uint8_t* out_points, int info[6], int device) {
+  if (!pvk || !proofs || (n_public && !public_inputs) || !out_status || !out_points || !info || n == 0 || proof_stride < 256 || proof_stride > 4096 || n_public > 4096 ||
+      form < 0 || form > 3 || misalign < 0 || misalign > 3 || (flags & ~(unsigned)BN254_FLAG_STRICT_SCALARS) || (form == 1 && (!out_slot_status || !out_slot_proof)))
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > (size_t)G16_LOADER_PROBE_MAX) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  // a combination bn254_launch_g16 could never reach is refused: the plan's own predicates, with the form in the place of the sizes and the knobs
+  const size_t key_inputs = pvk->host.key_inputs();
+  const bool match = pvk->host.inputs_match(n_public), strict = (flags & BN254_FLAG_STRICT_SCALARS) != 0;
+  const bool wide = form >= 2;
+  const int per = g16_wide_per(knob_wide_per()), chunks = wide ? g16_wide_chunks(n_public, per) : 0;
+  if (wide ? !(match && n_public > (size_t)G16_WIDE_MSM_MIN_INPUTS) : (match && n_public > (size_t)G16_WIDE_MSM_MIN_INPUTS))
+    return set_err(BN254_E_BAD_ARG, wide ? "the wide forms take a key with more than 16 inputs and its own input count" : "a key with more than 16 inputs sums them in the wide forms");
+  if (form == 1 && !(g16_key_may_compact(key_inputs) && !strict)) return set_err(BN254_E_BAD_ARG, "no launch compacts for this key and these flags");
+  if (form == 3 && !g16_wide_reduce8((size_t)chunks, n)) return set_err(BN254_E_BAD_ARG, "k_g16_msm_reduce8 is launched from 16 chunk sums per proof on");
+  DevState* d = dev_state(pvk, device);
+  std::lock_guard<std::mutex> lk(d->mu);
+  int rc = ensure_dev(pvk, *d, device, n);
+  if (rc) return rc;
+  if ((rc = probe_ws_alloc(n, device))) return rc;
+  DevBuf<uint8_t> in, out;
+  auto run = [&]() -> int {
+    int r;
+    const size_t pb = (n - 1) * proof_stride + 256, pb4 = (pb + 3) & ~(size_t)3, ib = 32 * n_public * n;
+    if ((r = in.ensure(pb4 + ib + 8)) || (r = out.ensure(384 * n))) return r;
+    HIPCK(hipDeviceSynchronize());                                     // the key's buffers may still serve an earlier batch on another stream
+    HIPCK(hipMemsetAsync(g_probe_ws, 0, n * (size_t)G16_WS_BYTES_PER_PROOF, nullptr));
+    HIPCK(hipMemsetAsync(g_probe_kinds, 0xEE, n, nullptr));            // the caller's status buffer holds whatever it held: the stage writes every byte
+    HIPCK(hipMemcpy(in, proofs, pb, hipMemcpyHostToDevice));
+    if (ib) HIPCK(hipMemcpy(in + pb4 + misalign, public_inputs, ib, hipMemcpyHostToDevice));
+    G16LaunchArgs a;
+    a.proofs = in; a.stride = proof_stride; a.inputs = in + pb4 + misalign; a.n_public = (int)n_public; a.n = n; a.ws = g_probe_ws; a.status = g_probe_kinds;
+    a.msm_tab = d->msm; a.k0 = d->k0; a.gtab = d->gtab; a.dtab = d->dtab; a.target = d->target; a.inputs_match_key = match ? 1 : 0; a.strict_scalars = strict ? 1 : 0;
+    a.msm_comb = pvk->host.msm_comb ? 1 : 0; a.msm_part = nullptr; a.key_inputs = key_inputs;
+    if (wide) {
+      if (n > d->msm_part_cap || (size_t)chunks > d->msm_chunks) return set_err(BN254_E_BAD_ARG, "partial-sum buffer smaller than the batch (internal sizing error)");
+      a.msm_part = (int32_t*)d->msm_part;
+      if (pvk->host.msm_comb) a.msm_digits = (uint16_t*)(d->msm_part + d->msm_chunks * 27 * d->msm_part_cap);
+    }
+    if (form == 1) {
+      if (n > d->compact_cap) return set_err(BN254_E_BAD_ARG, "slot arrays smaller than the batch (internal sizing error)");
+      const G16CompactAlloc ca = g16_compact_alloc(d->compact_cap, key_inputs);
+      a.slot_proof = (uint32_t*)d->compact;
+      a.block_count = (uint32_t*)d->compact + ca.slot_proof_bytes / 4;
+      a.slot_status = (uint8_t*)((uint32_t*)d->compact + (ca.slot_proof_bytes + ca.count_bytes) / 4);
+    }
+    G16LoaderForm f;
+    f.wide = wide; f.coop = false; f.compact = form == 1; f.reduce = form == 3 ? G16_REDUCE_EIGHT : G16_REDUCE_PLAIN;
+    G16LoaderRan ran;
+    bn254_launch_g16_loader(a, f, nullptr, nullptr, &ran);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = bn254_launch_dbg_store(g_probe_ws, n, (int)VE_AX, out, 0, nullptr);
+    if (e != hipSuccess) return set_err(BN254_E_HIP, std::string("probe launch: ") + hipGetErrorString(e));
+    HIPCK(hipDeviceSynchronize());
+    std::vector<uint8_t> stored(384 * n);
+    HIPCK(hipMemcpy(stored.data(), out, 384 * n, hipMemcpyDeviceToHost));
+    HIPCK(hipMemcpy(out_status, g_probe_kinds, n, hipMemcpyDeviceToHost));
+    if (form == 1) {
+      HIPCK(hipMemcpy(out_slot_status, a.slot_status, n, hipMemcpyDeviceToHost));
+      HIPCK(hipMemcpy(out_slot_proof, a.slot_proof, n * 4, hipMemcpyDeviceToHost));
+    }
+    g16_loader_points(stored.data(), n, out_points);
+    // what the launcher says it enqueued, not what was asked for
+    info[0] = ran.compaction ? 1 : ran.prepare_full ? 0 : ran.reduce == 2 ? 3 : ran.reduce == 1 ? 2 : -1; info[1] = ran.chunks; info[2] = ran.reduce; info[3] = ran.partial;
+    info[4] = ran.check_scalars; info[5] = ran.comb_digits;
+    return BN254_OK;
+  };
+  rc = run();
+  probe_ws_free();
+  return rc;
+}
+int bn254_dbg_g16_loader_keys(const bn254_g16_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                              size_t input_stride, size_t n, unsigned flags, int misalign, size_t max_slots, unsigned* out_slot_proof, uint8_t* out_slot_status, uint8_t* out_points,
+                              size_t* out_n_slots, int device) {
+  size_t max_public = 0;
+  if (!out_slot_proof || !out_slot_status || !out_points || !out_n_slots || n == 0 || misalign < 0 || misalign > 3 || (flags & ~(unsigned)BN254_FLAG_STRICT_SCALARS) ||
+      proof_stride > 4096 || input_stride > 65536)
+    return set_err(BN254_E_BAD_ARG, "bad argument");
+  if (n > (size_t)G16_LOADER_PROBE_MAX) return set_err(BN254_E_BAD_ARG, "probe batch too large");
+  int rc = check_keys_args(pvks, n_keys, key_index, proofs, proof_stride, public_inputs, input_stride, n, out_slot_status, flags, &max_public);
+  if (rc) return rc;
+  size_t slots = 0;
+  {
+    std::vector<uint32_t> count(n_keys, 0);
+    for (size_t i = 0; i < n; i++) {
+      if (key_index[i] >= n_keys) return set_err(BN254_E_BAD_ARG, "key_index[" + std::to_string(i) + "] is outside the list");
+      count[key_index[i]]++;
+    }
+    for (size_t k = 0; k < n_keys; k++) slots += bn254::keys_round_up(count[k]);
+  }
+  if (slots > max_slots) return set_err(BN254_E_BAD_ARG, "the batch fills more slots than the output arrays hold");
+  return g16_keys_probe_loader(pvks, n_keys, key_index, proofs, proof_stride, public_inputs, input_stride, n, flags, misalign, slots, out_slot_proof, out_slot_status, out_points,
+                               out_n_slots, device, g16_loader_points);
+}
 int bn254_dbg_pairing(const uint8_t* g1, const uint8_t* g2, uint8_t* out_gt, size_t n, int device) {
   int rc = probe_ws_alloc(n, device);
   if (rc) return rc;

@@ -290,6 +290,13 @@ int check_keys_args(const bn254_g16_pvk* const* pvks, size_t n_keys, const void*
                     size_t n, const void* status, unsigned flags, size_t* max_public);
 void set_diag(const std::string& msg);     // bn254_last_diagnostic() of the calling thread (bn254_capi_g16.hip)
 void keys_sets_drop(const bn254_g16_pvk* member);   // bn254_capi_keys.hip: forget every cached key set that contains this key
+// bn254_capi_keys.hip, for the value probe of the loader over a key list (bn254_dbg_g16_loader_keys, which has checked the arguments and counted the slots): the set
+// of the list made ready, the batch grouped, bn254_launch_g16_prepare_keys over all its slots, and what it left read back -- slot_to_proof and the slots' status bytes
+// as they are, the twelve elements from VE_AX through `points` (384 stored bytes per slot -> 320).  misalign: the device copy of the rows starts that many bytes
+// past a 4-byte boundary
+int g16_keys_probe_loader(const bn254_g16_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                          size_t input_stride, size_t n, unsigned flags, int misalign, size_t slots, unsigned* out_slot_proof, uint8_t* out_slot_status, uint8_t* out_points,
+                          size_t* out_n_slots, int device, void (*points)(const uint8_t*, size_t, uint8_t*));
 void parallel_copy(uint8_t* dst, const uint8_t* src, size_t bytes);
 int build_tables_on_device(int form, const std::vector<int32_t>& pts, DevBuf<int32_t>& dst);
 int sub_batch_streams();                   // BN254_STREAMS, read once: sub-batches of a Groth16 chunk in flight, 1 .. 4 (default 2)

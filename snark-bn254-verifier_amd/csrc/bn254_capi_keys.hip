@@ -199,6 +199,52 @@ int keys_enqueue(KeySet& s, const void* d_key_index, const void* d_proofs, size_
 
 }  // namespace
 
+// The loader of the grouped form alone, for bn254_dbg_g16_loader_keys (bn254_capi_dbg.hip): the front of keys_enqueue's grouped branch -- bn254_launch_keys_group, then
+// bn254_launch_g16_prepare_keys over the batch's slots as ONE launch part -- on the null stream, and the slots read back.  slots: the exact count (a multiple of 64)
+int g16_keys_probe_loader(const bn254_g16_pvk* const* pvks, size_t n_keys, const unsigned* key_index, const uint8_t* proofs, size_t proof_stride, const uint8_t* public_inputs,
+                          size_t input_stride, size_t n, unsigned flags, int misalign, size_t slots, unsigned* out_slot_proof, uint8_t* out_slot_status, uint8_t* out_points,
+                          size_t* out_n_slots, int device, void (*points)(const uint8_t*, size_t, uint8_t*)) {
+  size_t max_public = 0;
+  int rc = check_key_list(pvks, n_keys, &max_public);
+  if (rc || (rc = check_device(device))) return rc;
+  std::shared_ptr<KeySet> sp = set_cache().get(pvks, n_keys, device, max_public);
+  KeySet& s = *sp;
+  std::lock_guard<std::mutex> lk(s.mu);
+  if ((rc = ensure_set(s, n, flags))) return rc;
+  const size_t bound = (size_t)bn254::keys_slot_bound(n, n_keys);
+  if (slots == 0 || slots > bound || bound > s.slot_cap || bn254::g16_round256(slots) > s.ws_slots()) return set_err(BN254_E_BAD_ARG, "buffers of the key set smaller than the batch (internal sizing error)");
+  const size_t in_bytes = max_public ? (n - 1) * input_stride + 32 * max_public : 0, pb = (n - 1) * proof_stride + 256;
+  DevBuf<uint8_t> d_proofs, d_inputs, d_status, d_out; DevBuf<uint32_t> d_index;
+  const int oom = BN254_E_NOMEM;
+  if ((rc = d_proofs.ensure(pb, oom)) || (rc = d_inputs.ensure(in_bytes + 8, oom)) || (rc = d_index.ensure(n, oom)) || (rc = d_status.ensure(n, oom)) || (rc = d_out.ensure(384 * slots, oom)))
+    return rc;
+  HIPCK(hipDeviceSynchronize());                                       // the set's buffers may still serve an earlier batch on another stream
+  HIPCK(hipMemsetAsync(s.ws, 0, bn254::g16_round256(slots) * (size_t)G16_WS_BYTES_PER_PROOF, nullptr));
+  HIPCK(hipMemcpy(d_proofs, proofs, pb, hipMemcpyHostToDevice));
+  if (in_bytes) HIPCK(hipMemcpy(d_inputs + misalign, public_inputs, in_bytes, hipMemcpyHostToDevice));
+  HIPCK(hipMemcpy(d_index, key_index, n * 4, hipMemcpyHostToDevice));
+  hipError_t e = bn254_launch_keys_group(d_index, (uint32_t)n, (uint32_t)n_keys, (uint32_t)bound, s.count, s.base, s.cursor, s.n_slots, s.slot_to_proof, s.granule_key, d_status, nullptr);
+  if (e != hipSuccess) return launch_err(e, "grouping");
+  G16KeysLaunchArgs a;
+  a.proofs = d_proofs; a.stride = proof_stride; a.inputs = d_inputs + misalign; a.input_stride = input_stride; a.n_proofs = (uint32_t)n;
+  a.m = slots; a.slot0 = 0; a.n_slots = s.n_slots; a.slot_to_proof = s.slot_to_proof; a.granule_key = s.granule_key;
+  a.desc = s.desc; a.n_keys = (uint32_t)n_keys; a.ws = s.ws; a.slot_status = s.slot_status; a.status = d_status;
+  a.strict_scalars = (flags & BN254_FLAG_STRICT_SCALARS) ? 1 : 0;
+  bn254_launch_g16_prepare_keys(a, (unsigned)((slots + 255) / 256), nullptr);
+  if ((e = hipGetLastError()) == hipSuccess) e = bn254_launch_dbg_store(s.ws, slots, (int)bn254::VE_AX, d_out, 0, nullptr);
+  if (e != hipSuccess) return launch_err(e, "key-set loader");
+  HIPCK(hipDeviceSynchronize());
+  std::vector<uint8_t> stored(384 * slots);
+  uint32_t ns = 0;
+  HIPCK(hipMemcpy(stored.data(), d_out, 384 * slots, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(out_slot_proof, s.slot_to_proof, slots * 4, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(out_slot_status, s.slot_status, slots, hipMemcpyDeviceToHost));
+  HIPCK(hipMemcpy(&ns, s.n_slots, 4, hipMemcpyDeviceToHost));
+  points(stored.data(), slots, out_points);
+  *out_n_slots = ns;
+  return BN254_OK;
+}
+
 // bn254_groth16_vk_free: every cached set that contains the key goes
 void keys_sets_drop(const bn254_g16_pvk* member) { set_cache().drop(member); }
 

@@ -54,6 +54,13 @@ inline G16Form g16_launch_form(size_t n, size_t n_public, bool inputs_match_key,
   return f;
 }
 
+// ---- the reduction of a wide launch (bn254_launch_g16_loader) -------------------------------------------------------------------------------------------------
+// inputs per lane of the partial sums (wide_per_knob: knob_wide_per(), 0 = the default), the chunk sums per proof that follow, and which kernel adds them up: eight
+// lanes per proof (k_g16_msm_reduce8) from 16 chunks on while the launch is at most one wavefront per SIMD, one lane's chain (k_g16_msm_reduce) otherwise
+inline int g16_wide_per(int wide_per_knob) { return wide_per_knob ? wide_per_knob : G16_WIDE_MSM_INPUTS_PER_LANE; }
+inline int g16_wide_chunks(size_t n_public, int per) { return (int)((n_public + (size_t)per - 1) / (size_t)per); }
+inline bool g16_wide_reduce8(size_t chunks, size_t n) { return chunks >= 16 && n <= 65536; }
+
 // ---- the launch knobs of the environment ------------------------------------------------------------------------------------------------------------------
 // BN254_COOP, BN254_MILLER_RUN_STEPS, BN254_COOP_FIXED_MAX and BN254_WIDE_PER are read ONCE per process, here and nowhere else, as raw values (set_*: the variable
 // is there at all).  What a value means is each launcher's own rule: the one-line functions below, side by side.  bn254_dbg_launch_knobs shows them as the process

@@ -95,6 +95,16 @@ struct G16Prof {
   int cap, used;
 };
 hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* ev, G16Prof* prof);
+// The loader stage of a launch as a function of its own -- what bn254_launch_g16 enqueues before its ev[1] record: k_g16_classify / k_g16_compact_write (compact),
+// k_g16_prepare (in full, or stopping after C when wide or coop), k_g16_check_scalars (a.strict_scalars), and for wide the digit, partial-sum and reduction launches.
+// reduce: which reduction kernel a wide launch takes -- the rule of bn254_g16_plan.h::g16_wide_reduce8 (the product, always) or one of the two (the value probe)
+enum { G16_REDUCE_RULE = -1, G16_REDUCE_PLAIN = 0, G16_REDUCE_EIGHT = 1 };
+struct G16LoaderForm { bool wide = false, coop = false, compact = false; int reduce = G16_REDUCE_RULE; };
+// what a call of the launcher enqueued, written at each launch site (ran: nullptr in the product): the compaction launches, k_g16_prepare in full (0: stopping after
+// C), k_g16_check_scalars, k_g16_comb_digits, the partial-sum kernel (0 none, 1 k_g16_msm_partial_comb, 2 k_g16_msm_partial) with its chunk sums per proof, and the
+// reduction kernel (0 none, 1 k_g16_msm_reduce, 2 k_g16_msm_reduce8)
+struct G16LoaderRan { int compaction = 0, prepare_full = 0, check_scalars = 0, comb_digits = 0, partial = 0, chunks = 0, reduce = 0; };
+void bn254_launch_g16_loader(const G16LaunchArgs& a, const G16LoaderForm& f, hipStream_t s, G16Prof* prof, G16LoaderRan* ran = nullptr);
 // bn254_k_miller.hip: one whole step of the shared Miller loop (kind 0: doubling, with the squaring of f when do_sqr; 1..4: additions)
 void bn254_launch_miller_step(bool do_sqr, int kind, int32_t* ws, uint32_t n, const uint8_t* status, unsigned grid, hipStream_t s, int et, int eb, int e, int epa,
                               const int32_t* t0, int ep0, int inf0, const int32_t* t1, int ep1, int inf1);

@@ -134,6 +134,57 @@ const char* const bn254_kernel_kind_names[KID_COUNT] = {
   "k_g16_prepare", "k_g16_subgroup", "k_vm_init", "k_f12_sqr", "k_f12_mul_line_fixed",
   "k_f12_mul", "k_f12_cyclo_sqr", "k_f12_conj", "k_f12_frob", "k_f12_inv", "k_g16_compare", "k_f12_copy", "k_f12_cyclo_sqr_n", "k_miller_dbl_var", "k_miller_add_var", "k_g16_msm_partial", "k_g16_msm_reduce", "k_f12_mul_line_fixed2", "k_miller_sqr_dbl_var", "k_miller_step_dbl", "k_miller_step_add", "k_coop12_miller_g16", "k_miller_run"};
 
+// The loader stage of ONE launch, everything before the pairing: the compaction launches, k_g16_prepare, the strict-scalar check and, for a key with many inputs, the
+// digit, partial-sum and reduction launches of L.  f says what the caller decided from the launch's form (bn254_g16_plan.h::G16LoaderForm): bn254_launch_g16 fills it
+// from g16_launch_form and g16_compacts and leaves the reduction to the rule (g16_wide_reduce8); the value probe bn254_dbg_g16_loader forces each member in turn.
+void bn254_launch_g16_loader(const G16LaunchArgs& a, const G16LoaderForm& f, hipStream_t s, G16Prof* prof, G16LoaderRan* ran) {
+  G16LoaderRan none;
+  G16LoaderRan& r = ran ? *ran : none;      // what is launched, noted where it is launched
+  const unsigned grid = grid_for(a.n);
+  const uint32_t n = (uint32_t)a.n;
+  const bool wide = f.wide, coop = f.coop, compact = f.compact;
+  const uint32_t* const slot_proof = compact ? a.slot_proof : nullptr;
+  {
+    // ONE profile scope, KID_PREPARE: the two launches of the compaction are part of what the loader costs, and the per-kernel profile shows them there
+    ProfScope ps_(prof, KID_PREPARE, s);
+    if (compact) {
+      hipLaunchKernelGGL(k_g16_classify, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, n, a.status, a.block_count);
+      hipLaunchKernelGGL(k_g16_compact_write, dim3(grid), dim3(256), 0, s, (const uint8_t*)a.status, n, (const uint32_t*)a.block_count, a.slot_proof, a.slot_status);
+      r.compaction = 1;
+    }
+    hipLaunchKernelGGL(k_g16_prepare, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.n_public, n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, (wide || coop) ? 1 : 0,
+                       slot_proof, a.slot_status);
+    r.prepare_full = (wide || coop) ? 0 : 1;
+  }
+  if (a.strict_scalars && a.n_public > 0) { hipLaunchKernelGGL(k_g16_check_scalars, dim3(grid), dim3(256), 0, s, a.inputs, a.n_public, n, a.status); r.check_scalars = 1; }
+  if (wide) {
+    // inputs of one proof spread over `chunks` lanes, proofs in slices that fit the partial-sum buffer
+    const int per = g16_wide_per(knob_wide_per()), chunks = g16_wide_chunks((size_t)a.n_public, per);
+    unsigned pg = (unsigned)(((size_t)n * chunks + 255) / 256);
+    const bool reduce8 = f.reduce < 0 ? g16_wide_reduce8((size_t)chunks, a.n) : f.reduce == G16_REDUCE_EIGHT;
+    {
+      ProfScope ps_(prof, KID_MSM_PARTIAL, s);
+      if (a.msm_comb) {
+        const size_t scalars = (size_t)n * (size_t)a.n_public;
+        hipLaunchKernelGGL(k_g16_comb_digits, dim3((unsigned)((scalars + 255) / 256)), dim3(256), 0, s, a.inputs, a.n_public, n, a.msm_digits);
+        hipLaunchKernelGGL(k_g16_msm_partial_comb, dim3(pg), dim3(256), 0, s, (const uint16_t*)a.msm_digits, a.n_public, n, per, chunks, (const uint8_t*)a.status, a.msm_tab, a.msm_part);
+        r.comb_digits = 1; r.partial = 1;
+      }
+      else { hipLaunchKernelGGL(k_g16_msm_partial, dim3(pg), dim3(256), 0, s, a.inputs, a.n_public, n, per, chunks, (const uint8_t*)a.status, a.msm_tab, a.msm_part); r.partial = 2; }
+      r.chunks = chunks;
+    }
+    if (reduce8) {
+      // eight lanes per proof: below one wavefront per SIMD the reduction is one lane's chain of additions
+      ProfScope ps_(prof, KID_MSM_REDUCE, s);
+      hipLaunchKernelGGL(k_g16_msm_reduce8, dim3((unsigned)((a.n + 31) / 32)), dim3(256), 0, s, (const int32_t*)a.msm_part, chunks, n, a.ws, a.status, a.k0);
+      r.reduce = 2;
+    } else {
+      BN_LAUNCH(KID_MSM_REDUCE, k_g16_msm_reduce, (const int32_t*)a.msm_part, chunks, n, a.ws, a.status, a.k0);
+      r.reduce = 1;
+    }
+  }
+}
+
 hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* ev /* 5 events or nullptr */, G16Prof* prof) {
   unsigned grid = grid_for(a.n);
   uint32_t n = (uint32_t)a.n;
@@ -148,38 +199,9 @@ hipError_t bn254_launch_g16(const G16LaunchArgs& a, hipStream_t s, hipEvent_t* e
   const bool compact = a.slot_proof && a.slot_status && a.block_count && g16_compacts(form, a.key_inputs, a.strict_scalars != 0, a.rlc != 0);
   uint8_t* const lane_status = compact ? a.slot_status : a.status;     // the status bytes the lane kernels read: the slots', or the caller's
   const uint32_t* const slot_proof = compact ? a.slot_proof : nullptr;
-  {
-    // ONE profile scope, KID_PREPARE: the two launches of the compaction are part of what the loader costs, and the per-kernel profile shows them there
-    ProfScope ps_(prof, KID_PREPARE, s);
-    if (compact) {
-      hipLaunchKernelGGL(k_g16_classify, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, n, a.status, a.block_count);
-      hipLaunchKernelGGL(k_g16_compact_write, dim3(grid), dim3(256), 0, s, (const uint8_t*)a.status, n, (const uint32_t*)a.block_count, a.slot_proof, a.slot_status);
-    }
-    hipLaunchKernelGGL(k_g16_prepare, dim3(grid), dim3(256), 0, s, a.proofs, a.stride, a.inputs, a.n_public, n, a.ws, a.status, a.msm_tab, a.k0, a.inputs_match_key, (wide || coop) ? 1 : 0,
-                       slot_proof, a.slot_status);
-  }
-  if (a.strict_scalars && a.n_public > 0) hipLaunchKernelGGL(k_g16_check_scalars, dim3(grid), dim3(256), 0, s, a.inputs, a.n_public, n, a.status);
-  if (wide) {
-    // inputs of one proof spread over `chunks` lanes, proofs in slices that fit the partial-sum buffer
-    const int per = knob_wide_per() ? knob_wide_per() : G16_WIDE_MSM_INPUTS_PER_LANE, chunks = (a.n_public + per - 1) / per;
-    unsigned pg = (unsigned)(((size_t)n * chunks + 255) / 256);
-    {
-      ProfScope ps_(prof, KID_MSM_PARTIAL, s);
-      if (a.msm_comb) {
-        const size_t scalars = (size_t)n * (size_t)a.n_public;
-        hipLaunchKernelGGL(k_g16_comb_digits, dim3((unsigned)((scalars + 255) / 256)), dim3(256), 0, s, a.inputs, a.n_public, n, a.msm_digits);
-        hipLaunchKernelGGL(k_g16_msm_partial_comb, dim3(pg), dim3(256), 0, s, (const uint16_t*)a.msm_digits, a.n_public, n, per, chunks, (const uint8_t*)a.status, a.msm_tab, a.msm_part);
-      }
-      else hipLaunchKernelGGL(k_g16_msm_partial, dim3(pg), dim3(256), 0, s, a.inputs, a.n_public, n, per, chunks, (const uint8_t*)a.status, a.msm_tab, a.msm_part);
-    }
-    if (chunks >= 16 && a.n <= 65536) {
-      // eight lanes per proof: below one wavefront per SIMD the reduction is one lane's chain of additions
-      ProfScope ps_(prof, KID_MSM_REDUCE, s);
-      hipLaunchKernelGGL(k_g16_msm_reduce8, dim3((unsigned)((a.n + 31) / 32)), dim3(256), 0, s, (const int32_t*)a.msm_part, chunks, n, a.ws, a.status, a.k0);
-    } else {
-      BN_LAUNCH(KID_MSM_REDUCE, k_g16_msm_reduce, (const int32_t*)a.msm_part, chunks, n, a.ws, a.status, a.k0);
-    }
-  }
+  G16LoaderForm lf;
+  lf.wide = wide; lf.coop = coop; lf.compact = compact; lf.reduce = G16_REDUCE_RULE;
+  bn254_launch_g16_loader(a, lf, s, prof);
   if (ev) (void)hipEventRecord(ev[1], s);
   if (coop) {
     // small batch: cooperative layout (bn254_coop12.hip): public-input MSM, Miller loop of the three pairs, final exponentiation and the verdict in ONE launch
