@@ -498,6 +498,52 @@ int bn254_pairing_check_batch_shared_device(const void* d_items, size_t item_str
 int bn254_pairing_batch_shared(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared,
                                size_t n, uint8_t* out_gt /* n x 384 */, uint8_t* status, int device);
 
+/* ---- BN254_FLAG_RLC for the pairing-product check ------------------------------------------------------------------------------------------------------------------
+ * bn254_pairing_check_batch_flags[_device] are bn254_pairing_check_batch_shared[_device] with a flags word: items, packing, shared_mask, prepared, argument errors,
+ * workspace, lock and reservation are theirs; shared_mask == 0 with prepared == NULL is the all-variable item.  flags may hold BN254_FLAG_RLC only (anything else is
+ * BN254_E_BAD_ARG); with flags == 0 the entry runs exactly the launches the shared entry runs.  bn254_pairing_batch* (GT values out) takes no flag.
+ *
+ *   BN254_FLAG_RLC: every item that passes phase 1 draws a fresh odd 128-bit weight r_i -- ChaCha20 block i of a key drawn with getrandom(2) once per call, the launch
+ *   number in a nonce word -- and every finite G1 point of it is replaced by r_i P_ij (G1 has cofactor 1, so no identity flag changes).  The Miller loop then runs per
+ *   item over the VARIABLE positions alone, without a final exponentiation; the r-torsion test of every variable G2 point decides at its end exactly as in the exact
+ *   entry (BN254_ERR_NOT_IN_SUBGROUP).  Behind it the 64 consecutive items of a wavefront form a group: per shared position the sum of the pending items' weighted
+ *   points, and the product of their Miller values; ONE table-driven Miller loop over the shared positions, one product and ONE final exponentiation decide the
+ *   group.  A group that passes accepts its pending items; the items of a failed group go through the exact check on their weighted points (r_i is invertible mod r and
+ *   GT has prime order r, so the verdict is that of the unweighted item).
+ *   Contract: the status bytes are those of the exact entry, except that a false BN254_ACCEPT has probability about 2^-127 per item (a forged item passes only if a
+ *   non-trivial relation in the random r_i holds; the reasoning of bn254_kzg_verify_batch).  The flag is honoured for a launch of rlc_min items or more
+ *   (bn254_set_pairing_rlc_params: process-wide, atomic, a negative value leaves it alone, never below 64; initial value BN254_PAIRING_RLC_MIN; read back by
+ *   bn254_pairing_rlc_params) whose items have NO variable position (every position shared); any other launch is the exact launch and counts in out[3].  With the flag honoured BOTH entries synchronise ONCE per launch, to
+ *   learn which groups failed; a launch that does not honour it is the exact launch, and then bn254_pairing_check_batch_flags_device only enqueues on hip_stream and,
+ *   after bn254_pairing_reserve, allocates nothing.  The weighted form grows a group workspace and status bytes of its own under the device's lock.
+ *   bn254_pairing_rlc_state: out[0] launches that ran the joint check, out[1] the groups they checked, out[2] the groups that failed, out[3] launches of these
+ *   entries on the exact path (flags == 0 goes through the shared entry and counts nowhere here).
+ *   out[1] counts the groups of every joint launch, ceil(m / 64), whether or not a group holds a pending item; out[2] those whose check failed.
+ *   Measured on one MI355X (profiles/r20_pairing_rlc.txt, tools/bench_pairing.py --rlc; device-resident all-valid items, flag | exact alternating, median of 5):
+ *   (2, 0b11) 4.43 | 2.33 ms at 4096 items, 4.44 | 8.89 at 16 384, 4.71 | 9.28 at 65 536; (8, 0xff) 15.1 | 6.5, 15.2 | 24.5, 15.8 | 17.4; (4, 0b1110) 15.5 | 3.8, 15.5 | 14.2,
+ *   16.6 | 14.9; (1, 0) 6.7 | 1.6, 6.7 | 6.1, 7.3 | 10.1; (4, 0) 19.7 | 3.8, 19.8 | 14.3, 21.4 | 20.7; (8, 0) 36.9 | 6.6, 37.2 | 24.5, 39.9 | 34.6 -- spreads below 0.3 ms.
+ *   The 262 144-item rows the rule was also to be read from could not be produced (every attempt lost its GPU machine before the command ran): K = 0 and the
+ *   default rest on three sizes, with the losing ratios still falling with n, and are PROVISIONAL until `tools/bench_pairing.py --rlc ... --sizes 262144` has been run.
+ *   The default of rlc_min is 16 384, the smallest measured size at which the flag wins at (2, 0b11).  This DEPARTS from the rule the entry was specified with, a win at
+ *   (2, 0b11) AND at (4, 0b1110): (4, 0b1110) wins at no size up to 65 536, so that rule gives no threshold and (2, 0b11) alone sets it ((8, 0xff) agrees).  K = 0: a
+ *   shape with more than 0 variable positions is not honoured, because (4, 0b1110), (4, 0) and (8, 0) lose at 4096, 16 384 and 65 536 (those lines of the profile), and
+ *   a rule by the count of variable positions cannot honour (1, 0), which wins at 65 536, without honouring (4, 0b1110).  K = 0 comes from THIS implementation, not
+ *   from the method: the weight step is a plain 128-step double-and-always-add per G1 point and lane with one inversion per point, run for identity positions too -- one
+ *   dependent chain per SIMD, so the weighted time hardly moves with n up to 65 536 and grows with the points per item (4.4 ms for two, 15 for four).  A windowed
+ *   multiplication with a shared inversion would move every line; until then the joint check of shapes with a variable position (k_miller_run_sub,
+ *   k_pairing_rlc_group_prod) is reachable through the probes alone.  With one invalid item in every group of 64 (the worst case of the fallback) 65 536 items of
+ *   (2, 0b11) take 13.9 ms against 9.2 exact, of (8, 0xff) 32.9 against 17.1.  Not measured: 262 144 items (the runs could not be made: see DESIGN.md section 9j.2), the host entry.
+ *   Kernels: the loader of the exact entry, k_pairing_rlc_weigh, k_miller_run_sub (k_miller_run_var when no position is shared) in the lane form at every size,
+ *   k_pairing_rlc_group_sums, k_pairing_rlc_group_prod, then on the groups the launches of the exact entry in the form bn254_set_pairing_params gives their count,
+ *   k_plonk_group_scatter, and after the synchronisation the exact launch behind its loader for the items of failed groups. */
+int bn254_pairing_check_batch_flags(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared,
+                                    size_t n, uint8_t* status, int device, unsigned flags);
+int bn254_pairing_check_batch_flags_device(const void* d_items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const void* d_prepared,
+                                           size_t n, void* d_status, int device, void* hip_stream, unsigned flags);
+void bn254_set_pairing_rlc_params(long rlc_min);
+int bn254_pairing_rlc_params(long out[1]);
+int bn254_pairing_rlc_state(uint64_t out[4]);   /* [0] launches that ran the joint check, [1] groups they checked, [2] groups that failed, [3] launches on the exact path */
+
 /* ---- Batch verification of KZG openings ---------------------------------------------------------------------------------------------------------------------------
  * The reference's plonk/kzg.rs::batch_verify_multi_points (lines 128-190) for openings a caller holds (a KZG opening of one's own, an fflonk or halo2-KZG tail): the
  * G1 fold runs on the device, the pairing check is the shared-G2 batch above.
@@ -674,7 +720,8 @@ int bn254_g1_msm_reserve(size_t n, size_t n_var, size_t n_unit, size_t n_shared,
  * computed for them at run time); everything else is the host's compile of the same arithmetic source, computed once per process while the device runs.
  * NOT covered in this revision: the _keys variants of the kernels (batches over many keys), the RLC group kernels, the MSM row kernels and the wide-key MSM kernels,
  * the kernels of the batch pairing product (k_pairing_load, k_miller_run_var, k_pairing_store, and k_pairing_load_shared, k_miller_run_mix of the entries with shared G2 points; its final exponentiation and
- * compare are checks 1 .. 3's kernels), the kernels of the KZG batch (k_kzg_load, k_kzg_fold_load, k_kzg_ident, k_kzg_fetch),
+ * compare are checks 1 .. 3's kernels), the kernels of its BN254_FLAG_RLC mode (k_pairing_rlc_weigh, k_miller_run_sub, k_pairing_rlc_group_sums, k_pairing_rlc_group_prod),
+ * the kernels of the KZG batch (k_kzg_load, k_kzg_fold_load, k_kzg_ident, k_kzg_fetch),
  * the table builders (the window tables of the built-in key are built on the device, so a wrong table fails checks 4 and 5, but no table is compared).
  * Nor does a run of it see the PlonK stage kernels: those have the per-key self-test -- one synthetic proof, lane 0 of workgroup 0, ChaCha20 blocks 0 .. 2 -- and, in the
  * test suite, a batch-wide value test (bn254_dbg_plonk_stages, tests/test_gpu_plonk_stage_values.py) that holds every lane's zeta, lambda, opening, hash-to-field values and
@@ -806,6 +853,18 @@ int bn254_dbg_pairing_batch_shared(const uint8_t* items, size_t item_stride, siz
 /* host-only probe of its pass plan for a call of n items of n_pairs pairs: out = {items a reservation of n allocates workspace for, items per pass of the host
  * entries, passes of the host entries, pinned bytes of the records of one pass} */
 int bn254_dbg_pairing_plan(size_t n_pairs, size_t n, uint64_t out[4]);
+/* test-only: BN254_FLAG_RLC on the pairing batch is honoured for shapes of at most max_var variable positions (0 .. 8; negative: the default, 0); returns the value
+ * it replaces */
+int bn254_dbg_set_pairing_rlc_max_var(int max_var);
+/* The probe of BN254_FLAG_RLC on the pairing batch (bn254_pairing_check_batch_flags: same items, records and argument errors; one pass): ONE weighted launch whatever
+ * the knob says, with the caller's weights (n x 16 bytes big-endian, forced odd; null: the real draw on a device, all 1 in the host compile) in the ChaCha20 stream's
+ * place, so that every value is checkable.  out_item_gt (null, or n x 384): the final-exponentiated value of every item that reached the groups, on its weighted points
+ * (zero for an item decided before); out_group_gt (null, or ceil(n / 64) x 384) and out_group_status (null, or one byte per group): the value and the verdict of every
+ * group (1 and BN254_ACCEPT for a group without a pending item); status: what the entry answers.  device -1 (form 0) runs the host compile of the same code (the weight
+ * step, the Miller run over the variable positions, the group sums and product, the group check); a device ordinal the kernels, with the group check and the exact check
+ * in form 0 (the plan), 1 (lane) or 2 (cooperative). */
+int bn254_dbg_pairing_batch_rlc(const uint8_t* items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const uint8_t* prepared, size_t n, const uint8_t* weights,
+                                uint8_t* out_item_gt, uint8_t* out_group_gt, uint8_t* out_group_status, uint8_t* status, int device, int form);
 /* The probe of the KZG batch (bn254_kzg_verify_batch: same key, openings and argument errors; one pass: n at most what a launch holds): the points the loader and the
  * G1 walk leave per opening -- out_f: vp_p(0), F_i or F'_i; out_h: vp_p(1), -H_i or H'_i = -r_i H_i; 64 big-endian bytes each, zero for the identity and for an opening
  * the loader decided; out_inf: their two identity flags -- and the status bytes of the check.  flags may carry BN254_FLAG_RLC: then the weighted path runs whatever the
@@ -1082,7 +1141,7 @@ int bn254_dbg_plonk_table_compare(const bn254_plonk_pvk* pvk, int device, size_t
 
 /* Revision of this header's binary interface: bumped whenever a function changes its arguments, an array argument its length or a slot its meaning (5:
  * BN254_PLONK_NUM_TIMINGS has been 9 since revision 4, bn254_dbg_plonk_msm_plan writes 9 ints per row).  Entries that are only ADDED -- the batches over many
- * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries, the bn254_kzg_* entries, bn254_kzg_verify_folded_batch / _device / bn254_kzg_fold_reserve and their probes -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
+ * keys, bn254_set_keys_params, bn254_groth16_vk_prepare_batch, bn254_set_pairing_params / bn254_pairing_params / bn254_pairing_state, bn254_g2_prepare and the bn254_pairing_*_shared entries, the bn254_kzg_* entries, bn254_kzg_verify_folded_batch / _device / bn254_kzg_fold_reserve, bn254_pairing_check_batch_flags / _device, bn254_set_pairing_rlc_params / bn254_pairing_rlc_params / bn254_pairing_rlc_state and their probes -- change no existing function, array or slot, so the revision stays: a binding that needs them finds out when it resolves their symbols.  A binding compares it with the value it was generated for. */
 #define BN254_ABI_VERSION 5
 int bn254_abi_version(void);
 const char* bn254_status_string(int status_byte);

@@ -461,6 +461,31 @@ inline std::vector<uint8_t> pairing_batch_shared(const Bytes& items, size_t n_pa
 }
 // makes `device` ready for batches of n items: a later bn254_pairing_check_batch_device of up to n items only enqueues
 inline void pairing_reserve(size_t n, int device = 0) { detail::check(bn254_pairing_reserve(n, device)); }
+// pairing_check_batch_shared with a flags word (bn254_pairing_check_batch_flags): flags may hold BN254_FLAG_RLC only, 0 is the exact entry, shared_mask 0 with empty
+// `prepared` the all-variable item.  With the flag honoured (launches of pairing_rlc_params() items or more of a shape WITHOUT a variable position; any other launch is the exact one) the 64 items of a wavefront are checked jointly under fresh
+// random weights: the statuses of the exact entry except that a false ACCEPT has probability about 2^-127 per item; the call synchronises once per launch
+inline std::vector<uint8_t> pairing_check_batch_flags(const Bytes& items, size_t n_pairs, unsigned shared_mask, const Bytes& prepared, size_t n, unsigned flags, int device = 0,
+                                                      size_t item_stride = 0) {
+  if (n_pairs < 1 || n_pairs > (size_t)BN254_PAIRING_MAX_PAIRS || (shared_mask >> n_pairs)) throw std::invalid_argument("pairing_check_batch_flags: n_pairs is 1 .. 8 and shared_mask has bits below n_pairs only");
+  size_t packed = 0;
+  for (size_t j = 0; j < n_pairs; j++) packed += ((shared_mask >> j) & 1u) ? (size_t)BN254_PAIRING_G1_LEN : (size_t)BN254_PAIRING_PAIR_LEN;
+  const size_t stride = item_stride ? item_stride : packed;
+  if (n && (stride < packed || items.size() < (n - 1) * stride + packed)) throw std::invalid_argument("pairing_check_batch_flags: the buffer is shorter than n packed items");
+  if (prepared.size() < (size_t)BN254_G2_PREPARED_LEN * (size_t)__builtin_popcount(shared_mask)) throw std::invalid_argument("pairing_check_batch_flags: fewer prepared records than shared positions");
+  std::vector<uint8_t> status(n);
+  detail::check(bn254_pairing_check_batch_flags(items.data(), stride, n_pairs, shared_mask, shared_mask ? prepared.data() : nullptr, n, status.data(), device, flags));
+  return status;
+}
+// enqueues on hip_stream; a launch that honours BN254_FLAG_RLC synchronises it once
+inline void pairing_check_batch_flags_device(const void* d_items, size_t item_stride, size_t n_pairs, unsigned shared_mask, const void* d_prepared, size_t n, void* d_status,
+                                             unsigned flags, int device = 0, void* hip_stream = nullptr) {
+  detail::check(bn254_pairing_check_batch_flags_device(d_items, item_stride, n_pairs, shared_mask, d_prepared, n, d_status, device, hip_stream, flags));
+}
+// BN254_FLAG_RLC on the pairing batch is honoured from rlc_min items per launch on (never below 64; negative: unchanged)
+inline void set_pairing_rlc_params(long rlc_min) { bn254_set_pairing_rlc_params(rlc_min); }
+inline long pairing_rlc_params() { long out[1] = {0}; detail::check(bn254_pairing_rlc_params(out)); return out[0]; }
+// {launches that ran the joint check, groups they checked, groups that failed, launches on the exact path}
+inline std::array<uint64_t, 4> pairing_rlc_state() { std::array<uint64_t, 4> out{}; detail::check(bn254_pairing_rlc_state(out.data())); return out; }
 // launches of up to coop_max items take the cooperative twelve-lane form (0: always the lane form; clamped to 30 720; negative: unchanged) / the knob as it is now
 inline void set_pairing_params(long coop_max) { bn254_set_pairing_params(coop_max); }
 inline long pairing_params() { long out[1] = {0}; detail::check(bn254_pairing_params(out)); return out[0]; }

@@ -333,6 +333,43 @@ pub fn pairing_check_batch_shared(items: &[u8], item_stride: usize, n_pairs: usi
     check(unsafe { sys::bn254_pairing_check_batch_shared(items.as_ptr(), item_stride, n_pairs, shared_mask as core::ffi::c_uint, prepared.as_ptr(), n, status.as_mut_ptr(), device as c_int) })?;
     Ok(status.into_iter().map(Status::from).collect())
 }
+/// `pairing_check_batch_shared` with a flags word (`bn254_pairing_check_batch_flags`): `flags` may hold `FLAG_RLC` only, 0 is the exact entry, and `shared_mask == 0`
+/// with an empty `prepared` is the all-variable item.  With the flag honoured (launches of `pairing_rlc_params()` items or more of a shape without a variable position; any other launch is the exact one) the 64 items of a wavefront are
+/// checked jointly under fresh random 128-bit weights: the statuses are those of the exact entry except that a false `Accept` has probability about 2^-127 per item,
+/// and the call synchronises once per launch.
+pub fn pairing_check_batch_flags(items: &[u8], item_stride: usize, n_pairs: usize, shared_mask: u32, prepared: &[u8], n: usize, device: i32, flags: u32) -> Result<Vec<Status>, Error> {
+    let short = Error::Infrastructure { code: sys::BN254_E_BAD_ARG, message: "pairing_check_batch_flags: n_pairs is 1..=8, shared_mask has bits below n_pairs only, prepared holds a record per shared position and the buffer holds n packed items of item_stride bytes".into() };
+    if n_pairs < 1 || n_pairs > PAIRING_MAX_PAIRS || (shared_mask >> n_pairs) != 0 { return Err(short); }
+    let packed = pairing_packed_len(n_pairs, shared_mask);
+    if item_stride < packed || prepared.len() < G2_PREPARED_LEN * shared_mask.count_ones() as usize { return Err(short); }
+    if n > 0 && (n - 1).checked_mul(item_stride).and_then(|b| b.checked_add(packed)).map_or(true, |b| items.len() < b) { return Err(short); }
+    let mut status = vec![0u8; n];
+    let recs = if shared_mask == 0 { core::ptr::null() } else { prepared.as_ptr() };
+    check(unsafe { sys::bn254_pairing_check_batch_flags(items.as_ptr(), item_stride, n_pairs, shared_mask as core::ffi::c_uint, recs, n, status.as_mut_ptr(), device as c_int, flags as core::ffi::c_uint) })?;
+    Ok(status.into_iter().map(Status::from).collect())
+}
+/// `bn254_pairing_check_batch_flags_device` on device pointers: enqueues on `hip_stream`; a launch that honours `FLAG_RLC` synchronises the stream once.
+///
+/// # Safety
+/// The pointers must be device memory of the sizes the call implies (`d_prepared` 4-byte aligned) and stay valid until the stream has run the work.
+pub unsafe fn pairing_check_batch_flags_device(d_items: *const core::ffi::c_void, item_stride: usize, n_pairs: usize, shared_mask: u32, d_prepared: *const core::ffi::c_void, n: usize,
+                                               d_status: *mut core::ffi::c_void, device: i32, hip_stream: *mut core::ffi::c_void, flags: u32) -> Result<(), Error> {
+    check(sys::bn254_pairing_check_batch_flags_device(d_items, item_stride, n_pairs, shared_mask as core::ffi::c_uint, d_prepared, n, d_status, device as c_int, hip_stream, flags as core::ffi::c_uint))
+}
+/// `FLAG_RLC` on the pairing batch is honoured from `rlc_min` items per launch on (`bn254_set_pairing_rlc_params`; never below 64; negative: unchanged).
+pub fn set_pairing_rlc_params(rlc_min: i64) { unsafe { sys::bn254_set_pairing_rlc_params(rlc_min as core::ffi::c_long) } }
+/// The knob as it is now (`bn254_pairing_rlc_params`).
+pub fn pairing_rlc_params() -> Result<i64, Error> {
+    let mut out: [core::ffi::c_long; 1] = [0];
+    check(unsafe { sys::bn254_pairing_rlc_params(out.as_mut_ptr()) })?;
+    Ok(out[0] as i64)
+}
+/// (launches that ran the joint check, groups they checked, groups that failed, launches on the exact path)  (`bn254_pairing_rlc_state`).
+pub fn pairing_rlc_state() -> Result<(u64, u64, u64, u64), Error> {
+    let mut out = [0u64; 4];
+    check(unsafe { sys::bn254_pairing_rlc_state(out.as_mut_ptr()) })?;
+    Ok((out[0], out[1], out[2], out[3]))
+}
 /// Makes `device` ready for pairing batches of `n` items (its self-test at first use, the workspace).
 pub fn pairing_reserve(n: usize, device: i32) -> Result<(), Error> { check(unsafe { sys::bn254_pairing_reserve(n, device as c_int) }) }
 /// Launches of up to `coop_max` items of a pairing batch take the cooperative twelve-lane form (`bn254_set_pairing_params`; 0: always the lane form; clamped to

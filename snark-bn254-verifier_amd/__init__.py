@@ -14,7 +14,7 @@ from .binding import (  # noqa: F401
     PlonkKeySet, dbg_plonk_keys_plan, last_diagnostic, set_plonk_keys_params, set_plonk_rlc_params, dbg_plonk_keys_knobs,
     device_selftest, selftest_state, selftest_check_names, dbg_selftest, Bn254SelfTestError, E_SELFTEST, dbg_overlap_replay,
     pairing_check_batch, pairing_batch, pairing_check_batch_device, pairing_reserve, dbg_pairing_batch, dbg_pairing_plan, PAIRING_MAX_PAIRS, PAIRING_PAIR_LEN,
-    set_pairing_params, pairing_params, pairing_state, dbg_pairing_form, PAIRING_FORM_LANES, PAIRING_FORM_COOP,
+    set_pairing_params, pairing_params, pairing_state, set_pairing_rlc_params, pairing_rlc_params, pairing_rlc_state, dbg_pairing_batch_rlc, dbg_set_pairing_rlc_max_var, dbg_pairing_form, PAIRING_FORM_LANES, PAIRING_FORM_COOP,
     g2_prepare, pairing_check_batch_shared, pairing_batch_shared, pairing_check_batch_shared_device, dbg_pairing_batch_shared, pairing_packed_len, G2_PREPARED_LEN,
     PAIRING_G1_LEN,
     kzg_key_prepare, kzg_verify_batch, kzg_verify_batch_device, kzg_reserve, set_kzg_params, kzg_params, kzg_state, dbg_kzg_fold, KZG_OPENING_LEN, KZG_KEY_LEN,

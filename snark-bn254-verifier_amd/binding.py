@@ -1024,6 +1024,9 @@ def _shared_lib():
     L.bn254_pairing_batch_shared.argtypes = host + [C.c_void_p, C.c_void_p, C.c_int]
     L.bn254_dbg_pairing_batch_shared.argtypes = host + [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.bn254_pairing_check_batch_shared_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+    L.bn254_pairing_check_batch_flags.argtypes = host + [C.c_void_p, C.c_int, C.c_uint]
+    L.bn254_pairing_check_batch_flags_device.argtypes = [C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_uint]
+    L.bn254_dbg_pairing_batch_rlc.argtypes = host + [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     return L
 
 
@@ -1042,14 +1045,19 @@ def _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride):
     return items, prepared, n, item_stride
 
 
-def pairing_check_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, device=0):
+def pairing_check_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, device=0, flags=0):
     """pairing_check_batch for items whose G2 point of every position j with bit j of shared_mask set is shared by the whole batch: `prepared` holds their records
     (g2_prepare; bytes, or a list of records) in ascending position order, and the items are PACKED -- 64 bytes (G1) per shared position, 192 per variable one.
-    The status bytes are those of pairing_check_batch on the expanded items  (bn254_pairing_check_batch_shared)."""
+    The status bytes are those of pairing_check_batch on the expanded items  (bn254_pairing_check_batch_shared).  flags: FLAG_RLC takes the call through
+    bn254_pairing_check_batch_flags (the joint check of 64 items at a time from pairing_rlc_params() items per launch on, for shapes without a variable position -- others take the exact path; shared_mask 0 with no records is the
+    all-variable item)."""
     L = _shared_lib()
     items, prepared, n, item_stride = _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride)
     status = (C.c_uint8 * max(n, 1))()
-    _check(L.bn254_pairing_check_batch_shared(items, item_stride, n_pairs, shared_mask, prepared, n, status, device))
+    if flags:
+        _check(L.bn254_pairing_check_batch_flags(items, item_stride, n_pairs, shared_mask, prepared if shared_mask else None, n, status, device, flags))
+    else:
+        _check(L.bn254_pairing_check_batch_shared(items, item_stride, n_pairs, shared_mask, prepared, n, status, device))
     return bytes(status)[:n]
 
 
@@ -1062,11 +1070,64 @@ def pairing_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_str
     return bytes(gt)[:384 * n], bytes(status)[:n]
 
 
-def pairing_check_batch_shared_device(d_items, n_pairs, shared_mask, d_prepared, n, d_status, item_stride=None, device=0, stream=0):
-    """bn254_pairing_check_batch_shared_device on device pointers (ints; d_prepared 4-byte aligned): enqueues on `stream` and returns."""
+def pairing_check_batch_shared_device(d_items, n_pairs, shared_mask, d_prepared, n, d_status, item_stride=None, device=0, stream=0, flags=0):
+    """bn254_pairing_check_batch_shared_device on device pointers (ints; d_prepared 4-byte aligned): enqueues on `stream` and returns.  flags: FLAG_RLC takes the call
+    through bn254_pairing_check_batch_flags_device, which synchronises `stream` once per launch that honours the flag."""
     L = _shared_lib()
-    _check(L.bn254_pairing_check_batch_shared_device(d_items, pairing_packed_len(n_pairs, shared_mask) if item_stride is None else item_stride, n_pairs, shared_mask, d_prepared, n,
-                                                     d_status, device, stream))
+    stride = pairing_packed_len(n_pairs, shared_mask) if item_stride is None else item_stride
+    if flags:
+        _check(L.bn254_pairing_check_batch_flags_device(d_items, stride, n_pairs, shared_mask, d_prepared, n, d_status, device, stream, flags))
+    else:
+        _check(L.bn254_pairing_check_batch_shared_device(d_items, stride, n_pairs, shared_mask, d_prepared, n, d_status, device, stream))
+
+
+def set_pairing_rlc_params(rlc_min=-1):
+    """bn254_set_pairing_rlc_params: FLAG_RLC on the pairing batch is honoured from rlc_min items per launch on (never below 64; negative: unchanged)."""
+    fn = lib().bn254_set_pairing_rlc_params
+    fn.argtypes = [C.c_long]; fn.restype = None
+    fn(rlc_min)
+
+
+def pairing_rlc_params():
+    """rlc_min as it is now (bn254_pairing_rlc_params)."""
+    fn = lib().bn254_pairing_rlc_params
+    fn.argtypes = [C.POINTER(C.c_long)]
+    out = (C.c_long * 1)()
+    _check(fn(out))
+    return int(out[0])
+
+
+def pairing_rlc_state():
+    """(launches that ran the joint check, groups they checked, groups that failed, launches on the exact path)  (bn254_pairing_rlc_state)."""
+    fn = lib().bn254_pairing_rlc_state
+    fn.argtypes = [C.POINTER(C.c_uint64)]
+    out = (C.c_uint64 * 4)()
+    _check(fn(out))
+    return tuple(int(x) for x in out)
+
+
+def dbg_set_pairing_rlc_max_var(max_var=-1):
+    """bn254_dbg_set_pairing_rlc_max_var (tests): FLAG_RLC on the pairing batch is honoured for shapes of at most max_var variable positions (negative: the default,
+    0); returns the value it replaces."""
+    fn = lib().bn254_dbg_set_pairing_rlc_max_var
+    fn.argtypes = [C.c_int]; fn.restype = C.c_int
+    return fn(max_var)
+
+
+def dbg_pairing_batch_rlc(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, weights=None, device=-1, form=0):
+    """bn254_dbg_pairing_batch_rlc: one weighted launch whatever the knob says.  weights: None (the real draw on a device, all 1 in the host compile) or n x 16 bytes
+    big-endian, forced odd.  {"item_gt": n x 384 bytes (the final-exponentiated value of an item that reached the groups, on its weighted points; zero otherwise),
+    "group_gt": groups x 384, "group_status": groups bytes, "status": n bytes}.  device -1 is the host compile."""
+    L = _shared_lib()
+    items, prepared, n, item_stride = _shared_shape(items, n_pairs, shared_mask, prepared, n, item_stride)
+    if weights is not None:
+        weights = bytes(weights)
+        if len(weights) < 16 * n:
+            raise Bn254Error("pairing batch: fewer weights than items")
+    groups = (n + 63) // 64
+    item_gt = (C.c_uint8 * max(384 * n, 1))(); grp_gt = (C.c_uint8 * max(384 * groups, 1))(); grp_st = (C.c_uint8 * max(groups, 1))(); status = (C.c_uint8 * max(n, 1))()
+    _check(L.bn254_dbg_pairing_batch_rlc(items, item_stride, n_pairs, shared_mask, prepared if shared_mask else None, n, weights, item_gt, grp_gt, grp_st, status, device, form))
+    return {"item_gt": bytes(item_gt)[:384 * n], "group_gt": bytes(grp_gt)[:384 * groups], "group_status": bytes(grp_st)[:groups], "status": bytes(status)[:n]}
 
 
 def dbg_pairing_batch_shared(items, n_pairs, shared_mask, prepared, n=None, item_stride=None, device=-1, want_gt=True, form=0):

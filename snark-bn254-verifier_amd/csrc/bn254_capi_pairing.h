@@ -15,8 +15,21 @@ struct PbDev {
   DevBuf<uint8_t> d_in, d_status, d_gt;
   PinBuf<uint8_t> h_in, h_status, h_gt;
 };
+// the shared positions of a call (bn254_pairing_check_batch_shared): mask 0 is the all-variable entry.  prepared: popcount(mask) records of BN254_G2_PREPARED_LEN
+// bytes -- host memory in the host entries, device memory in the enqueue
+struct PbShared {
+  unsigned mask = 0; const uint8_t* prepared = nullptr;
+  size_t count() const { return (size_t)__builtin_popcount(mask); }
+  size_t bytes() const { return count() * PB_PREP_LEN; }
+};
 #pragma GCC visibility push(hidden)
 PbDev* pb_dev(int device);
+// BN254_E_BAD_ARG before any device is touched; *done: n == 0, nothing to do.  host_records: sh.prepared is host memory, so the headers of its records are checked too
+int pb_check_args(const void* pairs, size_t item_stride, size_t n_pairs, size_t n, const void* status, const void* out_gt, bool wants_gt, bool* done,
+                  const PbShared& sh = PbShared(), bool host_records = false);
+// items per pass of a host entry whose staged item takes rec bytes behind lead bytes of records; items a reservation of n allocates workspace for
+size_t pb_host_pass_of(size_t rec, size_t lead, size_t n);
+size_t pb_ws_items_of(size_t n);
 // caller holds d.mu: the device made ready (self-test at its first use) and the workspace grown to what a reservation of n items holds
 int pb_ensure(PbDev& d, int device, size_t n);
 // the form a launch of n items of n_pairs pairs takes under bn254_set_pairing_params, and the launch counted for bn254_pairing_state

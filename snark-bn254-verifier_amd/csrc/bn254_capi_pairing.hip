@@ -31,25 +31,14 @@ void pb_count_launch(int form) { g_pb_launches[form == bn254::PAIRING_FORM_COOP 
 // The passes of a call, without a device (bn254_dbg_pairing_plan reads the same functions).  ws_items: the workspace a reservation of n items allocates; host_pass:
 // the items per pass of the host entries, every one of which fits that reservation
 static inline size_t pb_ws_items(size_t n) { return n < g_pb_pass_items ? n : g_pb_pass_items; }
+size_t pb_ws_items_of(size_t n) { return pb_ws_items(n); }
 // rec: the bytes of an item as staged; lead: bytes staged in front of a pass's items (the prepared records of a call with shared positions)
-static inline size_t pb_host_pass_of(size_t rec, size_t lead, size_t n) {
+size_t pb_host_pass_of(size_t rec, size_t lead, size_t n) {
   size_t pass = (PB_STAGE_BYTES - lead) / rec;
   if (pass > g_pb_pass_items) pass = g_pb_pass_items;
   return n < pass ? n : pass;
 }
 static inline size_t pb_host_pass(size_t n_pairs, size_t n) { return pb_host_pass_of((size_t)PB_PAIR_LEN * n_pairs, 0, n); }
-
-namespace {
-
-// the shared positions of a call (bn254_pairing_check_batch_shared): mask 0 is the all-variable entry.  prepared: popcount(mask) records of BN254_G2_PREPARED_LEN
-// bytes -- host memory in the host entries, device memory in pb_enqueue
-struct PbShared {
-  unsigned mask = 0; const uint8_t* prepared = nullptr;
-  size_t count() const { return (size_t)__builtin_popcount(mask); }
-  size_t bytes() const { return count() * PB_PREP_LEN; }
-};
-
-}  // namespace
 
 // never destroyed (device memory must not be freed from a static destructor: bn254_capi_internal.h, KeyCache); map nodes never move
 PbDev* pb_dev(int device) {
@@ -94,10 +83,12 @@ int pb_enqueue(PbDev& d, const uint8_t* d_pairs, size_t item_stride, size_t n_pa
   return BN254_OK;
 }
 
+}  // namespace
+
 // BN254_E_BAD_ARG before any device is touched; *done: n == 0, nothing to do
 // sh: the shared positions (the _shared entries); host_records: sh.prepared is host memory, so the header words of its records are checked here as well
 int pb_check_args(const void* pairs, size_t item_stride, size_t n_pairs, size_t n, const void* status, const void* out_gt, bool wants_gt, bool* done,
-                  const PbShared& sh = PbShared(), bool host_records = false) {
+                  const PbShared& sh, bool host_records) {
   *done = false;
   if (n_pairs < 1 || n_pairs > BN254_PAIRING_MAX_PAIRS) return set_err(BN254_E_BAD_ARG, "bad argument: n_pairs is 1 .. 8");
   if (sh.mask >> n_pairs) return set_err(BN254_E_BAD_ARG, "bad argument: shared_mask has a bit at or above n_pairs");
@@ -117,6 +108,8 @@ int pb_check_args(const void* pairs, size_t item_stride, size_t n_pairs, size_t 
   *done = n == 0;
   return BN254_OK;
 }
+
+namespace {
 
 // a host-buffer call: passes of pb_host_pass items through the pinned staging; returns with the status bytes (and GT values) of every item
 // sh: the prepared records (host memory) travel in front of every pass's items, in the same pinned buffer and the same copy; the items are then the packed ones

@@ -118,6 +118,15 @@ hipError_t bn254_launch_pairing_batch(const PairingLaunchArgs& a, hipStream_t s)
   if (a.skip_load) {}
   else if (a.shared_mask) hipLaunchKernelGGL(k_pairing_load_shared, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, (uint32_t)a.shared_mask, a.prepared, nn, a.ws, a.status);
   else hipLaunchKernelGGL(k_pairing_load, dim3(grid), dim3(256), 0, s, a.pairs, a.item_stride, a.n_pairs, nn, a.ws, a.status);
+  if (a.load_only) return hipGetLastError();
+  if (a.miller_only && (form != PAIRING_FORM_LANES || a.skip_miller)) return hipErrorInvalidValue;
+  if (a.skip_miller && form == PAIRING_FORM_COOP) {      // VE_F -> VE_S0 in one launch, then the tails of the lane form
+    const hipError_t e = bn254_coop12_final_exp(a.ws, a.status, a.n, s);
+    if (e != hipSuccess) return e;
+    if (a.out_gt) hipLaunchKernelGGL(k_pairing_store, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.out_gt, a.one ? 0 : 1);
+    if (a.one) hipLaunchKernelGGL(k_g16_compare, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.one, (int)BN254_ST_REJECT);
+    return hipGetLastError();
+  }
   if (form == PAIRING_FORM_COOP) {
     // twelve lanes per item (after k_pairing_load_shared as well: the shared points are in the workspace as if they had come from the item, and the form has no use
     // for the tables): the Miller loop, the r-torsion tests and the final exponentiation in one launch -- with the verdict when that is all the caller wants,
@@ -131,13 +140,14 @@ hipError_t bn254_launch_pairing_batch(const PairingLaunchArgs& a, hipStream_t s)
   }
   const MillerKinds& kinds = miller_step_table().packed;
   const int per = knob_run_steps_pairing_batch();
-  for (int s0 = 0; s0 < BN_ATE_STEPS; s0 += per)
+  for (int s0 = 0; s0 < BN_ATE_STEPS && !a.skip_miller; s0 += per)
     if (a.shared_mask)
       hipLaunchKernelGGL(a.shared_mask == (1u << a.n_pairs) - 1u ? k_miller_run_mix<false> : k_miller_run_mix<true>, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, kinds, s0, s0 + per < BN_ATE_STEPS ? s0 + per : BN_ATE_STEPS, a.n_pairs, (uint32_t)a.shared_mask,
                          a.prepared, (int)VE_F, (int)(MR_FOLD_INIT | MR_FOLD_ATE));
     else
       hipLaunchKernelGGL(k_miller_run_var, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, kinds, s0, s0 + per < BN_ATE_STEPS ? s0 + per : BN_ATE_STEPS, a.n_pairs, (int)VE_F,
                        (int)(MR_FOLD_INIT | MR_FOLD_ATE));
+  if (a.miller_only) return hipGetLastError();
   LaunchOps ops{a.ws, nn, a.status, grid, s, {nullptr, nullptr, nullptr}, nullptr};
   vm_final_exp_program(ops);
   if (a.out_gt) hipLaunchKernelGGL(k_pairing_store, dim3(grid), dim3(256), 0, s, a.ws, nn, a.status, a.out_gt, a.one ? 0 : 1);

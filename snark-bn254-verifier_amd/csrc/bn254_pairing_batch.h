@@ -256,6 +256,9 @@ struct PairingLaunchArgs {
   const int32_t* prepared = nullptr;          // device memory, 4-byte aligned: popcount(shared_mask) records of PB_PREP_LEN bytes, ascending position order
   bool skip_load = false;                     // the workspace and the status bytes are what a loader left already (bn254_kzg.h: the G1 points come from the G1 walk);
                                               // pairs / item_stride are not read.  Every launch behind the load step is the same
+  // A launch cut into its parts (bn254_pairing_rlc.h; none of them set: the whole launch).  load_only: the loader alone.  miller_only (lane form): the loader unless
+  // skipped, then the Miller runs with the r-torsion tests; f stays in VE_F.  skip_miller: the final exponentiation of VE_F in the launch's form and the tails.
+  bool load_only = false, miller_only = false, skip_miller = false;
 };
 
 }  // namespace bn254
